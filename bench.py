@@ -28,6 +28,10 @@ FIXED grid (250 x 8, SSIMULACRA2 + DSSIM) partitioned over the same ranks and ti
 and 5 as the main workload are fixed grids => "strong".  torch.distributed (gloo, host side only) carries the barriers,
 the max-over-ranks of the time and the gather of the tiny score lists — no RCCL anywhere (north_star).
 
+--dump-outputs DIR: after the timed region, the scores of its last step over the whole global grid go to DIR/<metric>.npy
+(float64, one entry per pair, pairs sorted by (group, reference, variant, quality index)); the grid is seeded, so two builds
+run with the same arguments can be compared score for score.
+
 Extra JSON objects: "roofline" (the dominant kernel: algorithmic bytes per launch over its HIP-event duration alone on
 the GPU = `frac`, in the timed region = `in_region_*`; the roof that binds it from the SQ counters under profiles/;
 every kernel's row in `kernels`; the step against this round's and round 2's frozen byte model), "per_metric",
@@ -88,7 +92,12 @@ def parse():
                     help="experiment: all 24 references of a Kodak set in the 768x512 shape (one bucket, same pixel count)")
     ap.add_argument("--depth", type=int, default=0, help="copies of a SMALL grid's batches (default 2 when the grid is under 1 GP per step, else 1)")
     ap.add_argument("--inflight", type=int, default=0, help="batches launched and not yet collected (default: 2 * batches - 1 of a small grid, 3 of the sweep)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the scores of the last one to DIR/<metric>.npy (float64, global pair order)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ---- plain `python bench.py --gpus N`: start the ranks ourselves ------------------------------------------------------------
@@ -398,14 +407,36 @@ def main():
         local = time.perf_counter() - t0
         return scores, local, max_over_ranks(local)
 
-    def gather_and_check(wk, res, scores):
-        """Scores of the last step in global order on rank 0; one item of every other rank is recomputed there."""
-        info = [None] * world
-        dist.all_gather_object(info, (wk.mp_per_step, wk.pairs_per_step))
+    def score_rows(wk, res, scores):
+        """[(global key, (dssim, ssimulacra2, butteraugli, psnr))] of this rank's pairs, in launch order."""
         local = []
         for (g, c, _, _, group), sc in zip(res.sets[0], scores):
             for pid, s in zip(g.pair_ids, sc):
                 local.append((wk.key(group, c, pid), (s.dssim, s.ssimulacra2, s.butteraugli, s.psnr)))
+        return local
+
+    def dump_outputs(out_dir, wk, res, scores):
+        """--dump-outputs: the last timed step's scores of the whole global grid, one float64 array per enabled metric,
+        pairs in global key order (group, reference, variant, quality), written by rank 0."""
+        local = score_rows(wk, res, scores)
+        merged = [local]
+        if dist is not None:
+            merged = [None] * world if rank == 0 else None
+            dist.gather_object(local, merged, dst=0)
+        if rank != 0:
+            return
+        rows = sorted((t for part in merged for t in part), key=lambda t: t[0])
+        assert len(rows) * len(wk.metrics_on) * 8 <= 64 << 20, "score dump over 64 MB"
+        os.makedirs(out_dir, exist_ok=True)
+        for m in wk.metrics_on:
+            col = METRIC_NAMES.index(m)
+            np.save(os.path.join(out_dir, f"{m}.npy"), np.array([v[col] for _, v in rows], np.float64))
+
+    def gather_and_check(wk, res, scores):
+        """Scores of the last step in global order on rank 0; one item of every other rank is recomputed there."""
+        info = [None] * world
+        dist.all_gather_object(info, (wk.mp_per_step, wk.pairs_per_step))
+        local = score_rows(wk, res, scores)
         merged = [None] * world if rank == 0 else None
         dist.gather_object(local, merged, dst=0)
         all_mp, all_pairs = [x[0] for x in info], [x[1] for x in info]
@@ -465,6 +496,8 @@ def main():
     scores, local_elapsed, elapsed = timed(res, args.steps, args.warmup, inflight, serial=args.serial)
     in_region = res.stats() if (events or args.serial) else {}
     res.prof(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, wkl, res, scores)
 
     shard = None
     all_mp, all_pairs = [wkl.mp_per_step], [wkl.pairs_per_step]

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -18,15 +19,21 @@ def _json_lines(out):
     return [json.loads(l) for l in out.splitlines() if l.startswith("{")]
 
 
-def test_single_gpu_line():
-    out = subprocess.run([sys.executable, "bench.py", "--quick", "--steps", "4", "--warmup", "1"], cwd=ROOT, capture_output=True,
-                         text=True, timeout=600)
+def test_single_gpu_line(tmp_path):
+    dump = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, "bench.py", "--quick", "--steps", "4", "--warmup", "1", "--dump-outputs", str(dump)], cwd=ROOT,
+                         capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = _json_lines(out.stdout)
     assert len(lines) == 1
     d = lines[0]
     assert REQUIRED <= set(d), REQUIRED - set(d)
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "MP/s" and d["scaling"] == "weak"
+    # --dump-outputs: the last timed step's scores, one float64 array per metric of the line, one entry per pair
+    assert sorted(os.listdir(dump)) == sorted(f"{m}.npy" for m in d["config"]["metrics"])
+    for m in d["config"]["metrics"]:
+        a = np.load(dump / f"{m}.npy")
+        assert a.dtype == np.float64 and a.shape == (d["config"]["pairs_per_step"],) and np.isfinite(a).all()
     assert d["higher_is_better"] is True and d["vs_baseline"] is None and d["data"] == "synthetic" and d["dtype"] == "f32"
     assert "workload" in d["config"] and "model" not in d["config"]
     # the line measures the metric it names: all three perceptual metrics on every pair, with a per-metric breakdown
