@@ -26,6 +26,11 @@ int fail(ce_ctx *ctx, int code, const std::string &msg)
     return code;
 }
 
+int bad_length(ce_ctx *ctx, size_t want, size_t got)
+{
+    return fail(ctx, CE_ERR_BAD_LENGTH, "Invalid image size: expected " + std::to_string(want) + " bytes, got " + std::to_string(got));
+}
+
 // validation order of calculate_ssimulacra2 / calculate_butteraugli
 // (src/metrics/ssimulacra2.rs:65-82, src/metrics/butteraugli.rs:51-67)
 int validate_pair(ce_ctx *ctx, size_t ref_len, size_t test_len, size_t w, size_t h)
@@ -33,11 +38,11 @@ int validate_pair(ce_ctx *ctx, size_t ref_len, size_t test_len, size_t w, size_t
     if (ref_len != test_len)
         return fail(ctx, CE_ERR_DIM_MISMATCH, "Dimension mismatch: reference " + std::to_string(ref_len) +
                                                    " bytes, test " + std::to_string(test_len) + " bytes");
-    if (ref_len != w * h * 3)
-        return fail(ctx, CE_ERR_BAD_LENGTH, "Invalid image size: expected " + std::to_string(w * h * 3) +
-                                                 " bytes, got " + std::to_string(ref_len));
+    if (ref_len != w * h * 3) return bad_length(ctx, w * h * 3, ref_len);
     return CE_OK;
 }
+
+constexpr uint32_t kKnownMetrics = CE_METRIC_DSSIM | CE_METRIC_SSIMULACRA2 | CE_METRIC_BUTTERAUGLI | CE_METRIC_PSNR;
 
 double psnr_from_sse(unsigned long long sse, size_t w, size_t h)
 {
@@ -261,21 +266,26 @@ struct ce_fork_helpers {
     } w[2];
     explicit ce_fork_helpers(int device)
     {
-        for (auto &x : w)
-            x.th = std::thread([&x, device] {
-                (void)hipSetDevice(device);
-                std::unique_lock<std::mutex> lk(x.m);
-                for (;;) {
-                    x.cv.wait(lk, [&] { return x.has_job || x.stop; });
-                    if (x.stop) return;
-                    x.has_job = false;
-                    lk.unlock();
-                    x.job();
-                    lk.lock();
-                    x.done = true;
-                    x.cv.notify_all();
-                }
-            });
+        try {
+            for (auto &x : w)
+                x.th = std::thread([&x, device] {
+                    (void)hipSetDevice(device);
+                    std::unique_lock<std::mutex> lk(x.m);
+                    for (;;) {
+                        x.cv.wait(lk, [&] { return x.has_job || x.stop; });
+                        if (x.stop) return;
+                        x.has_job = false;
+                        lk.unlock();
+                        x.job();
+                        lk.lock();
+                        x.done = true;
+                        x.cv.notify_all();
+                    }
+                });
+        } catch (...) {  // a thread could not be created: stop and join the ones that were, then let the caller fall back
+            stop_all();
+            throw;
+        }
     }
     void submit(int i, std::function<void()> f)
     {
@@ -290,7 +300,8 @@ struct ce_fork_helpers {
         std::unique_lock<std::mutex> lk(w[i].m);
         w[i].cv.wait(lk, [&] { return w[i].done; });
     }
-    ~ce_fork_helpers()
+    ~ce_fork_helpers() { stop_all(); }
+    void stop_all()
     {
         for (auto &x : w) {
             {
@@ -453,40 +464,16 @@ static void invalidate_reference_state(ce_batch *b)
     b->refs_rt_valid = false;
 }
 
-static bool is_pinned_host(const void *p);
-
-static int upload(ce_batch *b, uint8_t *dst, const uint8_t *src, bool allow_inline = true)
+// true if the runtime knows `p` as page-locked host memory (hipHostMalloc / hipHostRegister): the DMA engine can
+// read it directly
+static bool is_pinned_host(const void *p)
 {
-    ce_ctx *ctx = b->ctx;
-    // pageable source -> pinned staging ring -> device on the batch's upload stream.  The caller's buffer is
-    // consumed before this returns; the DMA of this slot overlaps the host copy into the next one and the
-    // kernels of other batches.  A launched-but-uncollected run of THIS batch still reads the slabs: wait for it.
-    CE_HIP(ctx, hipSetDevice(ctx->device));  // the calling thread's current device may be another one (multi-device hosts)
-    // A small batch (the one-pair-per-call regime of a reference handle) uploads on the context's own stream: its launch
-    // follows at once, and a cross-stream event between the copy and the first kernel costs ~25 us of its ~0.5 ms
-    // (not for an image that a format conversion or a colour table follows on the upload stream: allow_inline = false)
-    const bool inline_copy = allow_inline && (double)b->max_pairs * b->w * b->h <= 4e6;
-    hipStream_t us = inline_copy ? ctx->stream : b->up_stream;
-    if (b->run_pending && !inline_copy) {
-        CE_HIP(ctx, hipStreamWaitEvent(b->up_stream, b->ev_run, 0));
-        b->run_pending = false;  // ordered from here on
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();  // an ordinary pageable pointer is reported as an error: clear it
+        return false;
     }
-    // A BLOCKING entry point (ce_ref_compare*, which collects before it returns) whose caller's image is page-locked
-    // (ce_host_alloc) needs no staging copy: the DMA engine reads the caller's buffer, which outlives the call's kernels.
-    if (b->caller_blocks && is_pinned_host(src)) {
-        CE_HIP(ctx, hipMemcpyAsync(dst, src, b->img_bytes, hipMemcpyHostToDevice, us));
-        if (!inline_copy) b->uploads_pending = true;
-        return CE_OK;
-    }
-    const int k = b->next_stage;
-    b->next_stage = (k + 1) % ce_batch::kStages;
-    if (b->stage_busy[k]) CE_HIP(ctx, hipEventSynchronize(b->ev_stage[k]));
-    std::memcpy(b->h_stage[k], src, b->img_bytes);
-    CE_HIP(ctx, hipMemcpyAsync(dst, b->h_stage[k], b->img_bytes, hipMemcpyHostToDevice, us));
-    CE_HIP(ctx, hipEventRecord(b->ev_stage[k], us));
-    b->stage_busy[k] = true;
-    if (!inline_copy) b->uploads_pending = true;
-    return CE_OK;
+    return a.type == hipMemoryTypeHost;
 }
 
 // kernels (context stream) must see everything uploaded so far
@@ -500,24 +487,73 @@ static int flush_uploads(ce_batch *b)
     return CE_OK;
 }
 
+// Called before every write into a slot; the one ordering rule of slot writes.  A slot is written either on the context's
+// stream (the inline route of a small batch, upload()) or on the batch's upload stream (everything else).  A write on the
+// context's stream while uploads are pending runs flush_uploads first; a write on the upload stream waits for the batch's
+// last launch, which may still read the slabs, and after an inline write that no launch has followed yet, for the
+// context's stream.  A batch whose images all take one route never meets either fence.
+static int order_write(ce_batch *b, bool on_ctx_stream)
+{
+    ce_ctx *ctx = b->ctx;
+    if (on_ctx_stream) {
+        b->inline_pending = true;  // cleared by the next launch, which runs behind it on the same stream
+        return flush_uploads(b);
+    }
+    if (b->run_pending) {
+        CE_HIP(ctx, hipStreamWaitEvent(b->up_stream, b->ev_run, 0));
+        b->run_pending = false;  // ordered from here on
+    }
+    if (b->inline_pending) {
+        CE_HIP(ctx, hipEventRecord(b->ev_up, ctx->stream));
+        CE_HIP(ctx, hipStreamWaitEvent(b->up_stream, b->ev_up, 0));
+        b->inline_pending = false;
+    }
+    return CE_OK;
+}
+
+// One image into a device slot on stream `s`; returns the HIP error (no ctx->err), so that upload threads can call it.
+// stage < 0: a page-locked source the DMA engine reads in place (the caller collects before it can go away); otherwise
+// the source goes through pinned staging slot `stage` (once its previous DMA is done) and is consumed on return.
+static hipError_t copy_in(ce_batch *b, int stage, uint8_t *dst, const uint8_t *src, hipStream_t s)
+{
+    if (stage < 0) return hipMemcpyAsync(dst, src, b->img_bytes, hipMemcpyHostToDevice, s);
+    hipError_t e = b->stage_busy[stage] ? hipEventSynchronize(b->ev_stage[stage]) : hipSuccess;
+    if (e == hipSuccess) {
+        std::memcpy(b->h_stage[stage], src, b->img_bytes);
+        e = hipMemcpyAsync(dst, b->h_stage[stage], b->img_bytes, hipMemcpyHostToDevice, s);
+    }
+    if (e == hipSuccess) e = hipEventRecord(b->ev_stage[stage], s);
+    b->stage_busy[stage] = true;
+    return e;
+}
+
+static int upload(ce_batch *b, uint8_t *dst, const uint8_t *src, bool allow_inline = true)
+{
+    ce_ctx *ctx = b->ctx;
+    // pageable source -> pinned staging ring -> device on the batch's upload stream: the DMA of this slot overlaps the
+    // host copy into the next one and the kernels of other batches
+    CE_HIP(ctx, hipSetDevice(ctx->device));  // the calling thread's current device may be another one (multi-device hosts)
+    // A small batch (the one-pair-per-call regime of a reference handle) uploads on the context's own stream: its launch
+    // follows at once, and a cross-stream event between the copy and the first kernel costs ~25 us of its ~0.5 ms
+    // (not for an image that a format conversion or a colour table follows on the upload stream: allow_inline = false)
+    const bool inline_copy = allow_inline && (double)b->max_pairs * b->w * b->h <= 4e6;
+    if (int rc = order_write(b, inline_copy)) return rc;
+    // A BLOCKING entry point (ce_ref_compare*, which collects before it returns) whose caller's image is page-locked
+    // (ce_host_alloc) needs no staging copy: the DMA engine reads the caller's buffer, which outlives the call's kernels.
+    const int stage = b->caller_blocks && is_pinned_host(src) ? -1 : b->next_stage;
+    if (stage >= 0) b->next_stage = (stage + 1) % ce_batch::kStages;
+    const hipError_t e = copy_in(b, stage, dst, src, inline_copy ? ctx->stream : b->up_stream);
+    if (!inline_copy) b->uploads_pending = true;
+    if (e != hipSuccess) return fail(ctx, CE_ERR_BACKEND, std::string("upload: ") + hipGetErrorString(e));
+    return CE_OK;
+}
+
 // Many images at once (ce_eval_batch): the host copies into the pinned ring are spread over a few threads, each
 // with its own pair of ring slots, because one thread's memcpy (~12 GB/s) is slower than the PCIe link.
 struct upload_job {
     uint8_t *dst;
     const uint8_t *src;
 };
-
-// true if the runtime knows `p` as page-locked host memory (hipHostMalloc / hipHostRegister): the DMA engine can
-// read it directly
-static bool is_pinned_host(const void *p)
-{
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();  // an ordinary pageable pointer is reported as an error: clear it
-        return false;
-    }
-    return a.type == hipMemoryTypeHost;
-}
 
 static int upload_many(ce_batch *b, const std::vector<upload_job> &jobs)
 {
@@ -527,12 +563,16 @@ static int upload_many(ce_batch *b, const std::vector<upload_job> &jobs)
     // Page-locked sources skip the staging ring: one asynchronous copy per image straight from the caller's buffer.
     // Only ce_eval_batch comes through here, and it collects (synchronises) before it returns, so the buffers
     // outlive the copies.
-    bool all_pinned = true;
-    for (const auto &j : jobs)
-        if (!is_pinned_host(j.src)) {
-            all_pinned = false;
-            break;
+    const bool all_pinned = std::all_of(jobs.begin(), jobs.end(), [](const upload_job &j) { return is_pinned_host(j.src); });
+    const int n_threads = (int)std::min<size_t>({(size_t)ce_batch::kStages / 2, jobs.size(),
+                                                 (size_t)std::max(1u, std::thread::hardware_concurrency())});
+    if (!all_pinned && (n_threads <= 1 || b->img_bytes < (64u << 10))) {
+        for (const auto &j : jobs) {
+            int rc = upload(b, j.dst, j.src, false);
+            if (rc != CE_OK) return rc;
         }
+        return CE_OK;
+    }
     // One stream moves a 786 KB image in 38 us (20.6 GB/s): the 1.88 GB of the Kodak + CID22 sweep would take as long as its
     // kernels.  The copies of a chunk therefore alternate between the batch's upload stream and a second one of the context,
     // which is fenced on both sides so that everything else keeps seeing "the uploads are on up_stream".
@@ -555,62 +595,20 @@ static int upload_many(ce_batch *b, const std::vector<upload_job> &jobs)
         CE_HIP(ctx, hipStreamWaitEvent(b->up_stream, ctx->ev_up2, 0));
         return CE_OK;
     };
-    if (all_pinned) {
-        if (b->run_pending) {
-            CE_HIP(ctx, hipStreamWaitEvent(b->up_stream, b->ev_run, 0));
-            b->run_pending = false;
-        }
-        if (two_up) {
-            int rc = up2_begin();
-            if (rc != CE_OK) return rc;
-            for (size_t i = 0; i < jobs.size(); i++)
-                CE_HIP(ctx, hipMemcpyAsync(jobs[i].dst, jobs[i].src, b->img_bytes, hipMemcpyHostToDevice, (i & 1) ? ctx->up2_stream : b->up_stream));
-            rc = up2_end();
-            if (rc != CE_OK) return rc;
-        } else {
-            for (const auto &j : jobs)
-                CE_HIP(ctx, hipMemcpyAsync(j.dst, j.src, b->img_bytes, hipMemcpyHostToDevice, b->up_stream));
-        }
-        b->uploads_pending = true;
-        return CE_OK;
-    }
-    const int n_threads = (int)std::min<size_t>({(size_t)ce_batch::kStages / 2, jobs.size(),
-                                                 (size_t)std::max(1u, std::thread::hardware_concurrency())});
-    if (n_threads <= 1 || b->img_bytes < (64u << 10)) {
-        for (const auto &j : jobs) {
-            int rc = upload(b, j.dst, j.src, false);
-            if (rc != CE_OK) return rc;
-        }
-        return CE_OK;
-    }
-    if (b->run_pending) {
-        CE_HIP(ctx, hipStreamWaitEvent(b->up_stream, b->ev_run, 0));
-        b->run_pending = false;
-    }
-    if (two_up) {
-        int rc = up2_begin();
-        if (rc != CE_OK) return rc;
-    }
+    if (int rc = order_write(b, false)) return rc;
+    if (two_up)
+        if (int rc = up2_begin()) return rc;
     std::atomic<size_t> next{0};
     std::atomic<int> err{(int)hipSuccess};
     const int device = ctx->device;
     auto worker = [&](int t) {
         if (hipSetDevice(device) != hipSuccess) return;
-        const hipStream_t us = (two_up && (t & 1)) ? ctx->up2_stream : b->up_stream;  // a worker's two ring slots stay on its stream
-        int flip = 0;
-        for (;;) {
+        for (int flip = 0;; flip ^= 1) {
             const size_t i = next.fetch_add(1);
             if (i >= jobs.size()) break;
-            const int k = 2 * t + flip;
-            flip ^= 1;
-            hipError_t e = hipSuccess;
-            if (b->stage_busy[k]) e = hipEventSynchronize(b->ev_stage[k]);
-            if (e == hipSuccess) {
-                std::memcpy(b->h_stage[k], jobs[i].src, b->img_bytes);
-                e = hipMemcpyAsync(jobs[i].dst, b->h_stage[k], b->img_bytes, hipMemcpyHostToDevice, us);
-            }
-            if (e == hipSuccess) e = hipEventRecord(b->ev_stage[k], us);
-            b->stage_busy[k] = true;
+            // page-locked: one thread whose copies alternate between the streams; staged: a worker's two ring slots stay on its stream
+            const hipStream_t us = (two_up && ((all_pinned ? i : (size_t)t) & 1)) ? ctx->up2_stream : b->up_stream;
+            const hipError_t e = copy_in(b, all_pinned ? -1 : 2 * t + flip, jobs[i].dst, jobs[i].src, us);
             if (e != hipSuccess) {
                 err.store((int)e);
                 break;
@@ -618,7 +616,7 @@ static int upload_many(ce_batch *b, const std::vector<upload_job> &jobs)
         }
     };
     std::vector<std::thread> pool;
-    for (int t = 1; t < n_threads; t++) {
+    for (int t = 1; t < (all_pinned ? 1 : n_threads); t++) {
         try {
             pool.emplace_back(worker, t);
         } catch (...) {  // no thread to be had: the calling thread's loop below takes whatever is left (nothing may be thrown across the C ABI)
@@ -628,14 +626,10 @@ static int upload_many(ce_batch *b, const std::vector<upload_job> &jobs)
     worker(0);
     for (auto &th : pool) th.join();
     b->uploads_pending = true;
-    if (two_up) {
-        int rc = up2_end();
-        if (rc != CE_OK) return rc;
-    }
-    if (err.load() != (int)hipSuccess) {
-        ctx->err = std::string("upload: ") + hipGetErrorString((hipError_t)err.load());
-        return CE_ERR_BACKEND;
-    }
+    if (two_up)
+        if (int rc = up2_end()) return rc;
+    if (err.load() != (int)hipSuccess)
+        return fail(ctx, CE_ERR_BACKEND, std::string("upload: ") + hipGetErrorString((hipError_t)err.load()));
     return CE_OK;
 }
 
@@ -643,9 +637,7 @@ int ce_batch_set_reference(ce_batch *b, uint32_t ref_index, const uint8_t *rgb, 
 {
     if (!b || !rgb) return CE_ERR_INVALID_ARG;
     if (ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "ref_index out of range");
-    if (len != b->img_bytes)
-        return fail(b->ctx, CE_ERR_BAD_LENGTH, "Invalid image size: expected " + std::to_string(b->img_bytes) +
-                                                    " bytes, got " + std::to_string(len));
+    if (len != b->img_bytes) return bad_length(b->ctx, b->img_bytes, len);
     invalidate_reference_state(b);  // cached reference-side planes are stale
     return upload(b, b->d_refs + (size_t)ref_index * b->img_bytes, rgb);
 }
@@ -656,9 +648,7 @@ static int upload_fmt(ce_batch *b, uint8_t *dst, const void *pixels, size_t len,
     ce_ctx *ctx = b->ctx;
     const size_t bpp = ce_pixel_bytes(format), n_px = (size_t)b->w * b->h;
     if (bpp == 0) return fail(ctx, CE_ERR_INVALID_ARG, "unknown pixel format");
-    if (len != n_px * bpp)
-        return fail(ctx, CE_ERR_BAD_LENGTH, "Invalid image size: expected " + std::to_string(n_px * bpp) + " bytes, got " +
-                                                std::to_string(len));
+    if (len != n_px * bpp) return bad_length(ctx, n_px * bpp, len);
     if (format == CE_PIXEL_RGB8) return upload(b, dst, static_cast<const uint8_t *>(pixels), false);
     CE_HIP(ctx, hipSetDevice(ctx->device));  // the staging allocations and the ingest launch below go to the context's device
     const int k = b->next_wide;
@@ -668,10 +658,7 @@ static int upload_fmt(ce_batch *b, uint8_t *dst, const void *pixels, size_t len,
         CE_HIP(ctx, hipMalloc((void **)&b->d_wide[k], n_px * 8));
         CE_HIP(ctx, hipEventCreateWithFlags(&b->ev_wide[k], hipEventDisableTiming));
     }
-    if (b->run_pending) {
-        CE_HIP(ctx, hipStreamWaitEvent(b->up_stream, b->ev_run, 0));
-        b->run_pending = false;
-    }
+    if (int rc = order_write(b, false)) return rc;
     if (b->wide_busy[k]) CE_HIP(ctx, hipEventSynchronize(b->ev_wide[k]));  // this staging pair's previous image has been converted
     std::memcpy(b->h_wide[k], pixels, len);
     CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], len, hipMemcpyHostToDevice, b->up_stream));
@@ -745,16 +732,14 @@ static int apply_lut(ce_batch *b, uint8_t *slot, const ce_lut *lut)
 
 int ce_batch_set_reference_lut(ce_batch *b, uint32_t ref_index, const void *pixels, size_t len, int format, const ce_lut *lut)
 {
-    int rc = ce_batch_set_reference_fmt(b, ref_index, pixels, len, format);
-    if (rc != CE_OK) return rc;
+    if (int rc = ce_batch_set_reference_fmt(b, ref_index, pixels, len, format)) return rc;
     return apply_lut(b, b->d_refs + (size_t)ref_index * b->img_bytes, lut);
 }
 
 int ce_batch_set_test_lut(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format,
                           const ce_lut *lut)
 {
-    int rc = ce_batch_set_test_fmt(b, pair_index, ref_index, pixels, len, format);
-    if (rc != CE_OK) return rc;
+    if (int rc = ce_batch_set_test_fmt(b, pair_index, ref_index, pixels, len, format)) return rc;
     return apply_lut(b, b->d_tests + (size_t)pair_index * b->img_bytes, lut);
 }
 
@@ -774,19 +759,15 @@ int ce_batch_bind_pair(ce_batch *b, uint32_t pair_index, uint32_t ref_index)
 int ce_batch_set_test(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const uint8_t *rgb, size_t len)
 {
     if (!b || !rgb) return CE_ERR_INVALID_ARG;
-    int rc = ce_batch_bind_pair(b, pair_index, ref_index);
-    if (rc != CE_OK) return rc;
-    if (len != b->img_bytes)
-        return fail(b->ctx, CE_ERR_BAD_LENGTH, "Invalid image size: expected " + std::to_string(b->img_bytes) +
-                                                    " bytes, got " + std::to_string(len));
+    if (int rc = ce_batch_bind_pair(b, pair_index, ref_index)) return rc;
+    if (len != b->img_bytes) return bad_length(b->ctx, b->img_bytes, len);
     return upload(b, b->d_tests + (size_t)pair_index * b->img_bytes, rgb);
 }
 
 int ce_batch_set_test_fmt(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format)
 {
     if (!b || !pixels) return CE_ERR_INVALID_ARG;
-    int rc = ce_batch_bind_pair(b, pair_index, ref_index);
-    if (rc != CE_OK) return rc;
+    if (int rc = ce_batch_bind_pair(b, pair_index, ref_index)) return rc;
     return upload_fmt(b, b->d_tests + (size_t)pair_index * b->img_bytes, pixels, len, format);
 }
 
@@ -803,8 +784,7 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
     if (!b) return CE_ERR_INVALID_ARG;
     ce_ctx *ctx = b->ctx;
     if (n_pairs == 0 || n_pairs > b->max_pairs) return fail(ctx, CE_ERR_INVALID_ARG, "n_pairs out of range");
-    const uint32_t known = CE_METRIC_DSSIM | CE_METRIC_SSIMULACRA2 | CE_METRIC_BUTTERAUGLI | CE_METRIC_PSNR;
-    if (metric_mask & ~known) return fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
+    if (metric_mask & ~kKnownMetrics) return fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
     CE_HIP(ctx, hipSetDevice(ctx->device));
     {
         int rc = flush_uploads(b);
@@ -995,6 +975,7 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
     CE_HIP(ctx, hipMemcpyAsync(b->h_scores, b->d_scores, sizeof(ce_dev_scores) * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
     CE_HIP(ctx, hipEventRecord(b->ev_run, ctx->stream));
     b->run_pending = true;
+    b->inline_pending = false;  // the next write on up_stream waits for ev_run, which is behind every inline write
     if (!b->counted_in_flight) {
         in_flight_of(ctx).fetch_add(1, std::memory_order_relaxed);
         b->counted_in_flight = true;
@@ -1059,8 +1040,7 @@ int ce_batch_butteraugli_pnorm3(ce_batch *b, uint32_t n_pairs, double *out)
 int ce_batch_run(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_t flags, float intensity_target,
                  ce_scores *out)
 {
-    int rc = ce_batch_launch(b, n_pairs, metric_mask, flags, intensity_target);
-    if (rc != CE_OK) return rc;
+    if (int rc = ce_batch_launch(b, n_pairs, metric_mask, flags, intensity_target)) return rc;
     return ce_batch_collect(b, n_pairs, out);
 }
 
@@ -1178,12 +1158,22 @@ static int shape_batch(ce_ctx *ctx, uint32_t w, uint32_t h, uint32_t need_pairs,
     return CE_OK;
 }
 
+// a failed call may leave copies from the caller's page-locked buffers queued: drain them before the buffers can go away
+static void drain_batch(ce_batch *b)
+{
+    hipStreamSynchronize(b->up_stream);
+    if (b->ctx->up2_stream) hipStreamSynchronize(b->ctx->up2_stream);
+    hipStreamSynchronize(b->ctx->stream);
+}
+
 int ce_eval_batch(ce_ctx *ctx, size_t n, const ce_pair_desc *pairs, uint32_t metric_mask, uint32_t flags,
                   float intensity_target, ce_scores *out)
 {
     return ce_eval_batch_lut(ctx, n, pairs, nullptr, metric_mask, flags, intensity_target, out);
 }
 
+// Each bucket streams through up to kPoolRing pooled batches in the chunks of its plan (ce_plan.h); chunks are collected in
+// launch order, or before their ring slot's batch is filled again.
 int ce_eval_batch_lut(ce_ctx *ctx, size_t n, const ce_pair_desc *pairs, const ce_lut *const *test_luts, uint32_t metric_mask,
                       uint32_t flags, float intensity_target, ce_scores *out)
 {
@@ -1200,138 +1190,83 @@ int ce_eval_batch_lut(ce_ctx *ctx, size_t n, const ce_pair_desc *pairs, const ce
             out[i].status = rc;
             continue;
         }
+        if (test_luts && test_luts[i] && test_luts[i]->ctx->device != ctx->device)
+            return fail(ctx, CE_ERR_INVALID_ARG, "colour table and batch are on different devices");
         buckets[{d.width, d.height}].push_back(i);
     }
-    // Phase 1: fill and launch.  A bucket is streamed through up to kPoolRing pooled batches in chunks of whole
-    // references (all pairs of a reference stay together, identical reference pointers share one device slot): the
-    // uploads of a chunk run on that batch's upload stream and overlap the kernels of the chunk before it.
-    // Phase 2: collect, in launch order.
-    struct chunk {
-        ce_batch *b;
-        std::vector<size_t> items;  // indices into pairs[] / out[]
+    if (buckets.empty()) return CE_OK;
+    // what ce_batch_launch would reject is rejected before anything is uploaded
+    if (metric_mask & ~kKnownMetrics) return fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
+    static const size_t forced_chunks = [] {  // CE_EVAL_BATCH_CHUNKS (1..3) forces the chunk count for A/B runs
+        const char *e = std::getenv("CE_EVAL_BATCH_CHUNKS");
+        const int v = e ? std::atoi(e) : 0;
+        return (size_t)(v >= 1 && v <= (int)ce_ctx::kPoolRing ? v : 0);
+    }();
+    static const size_t ramp0 = [] {  // CE_EVAL_BATCH_RAMP: pairs of the call's first chunk (0 = every chunk at the target)
+        const char *e = std::getenv("CE_EVAL_BATCH_RAMP");
+        return (size_t)(e ? std::max(0, std::atoi(e)) : 64);  // 2000 pairs of 512x512: off 106.5 ms, 32 -> 102.1, 64 -> 100.0, 128 -> 101.1
+    }();
+    std::vector<ce_plan_chunk> plan;
+    struct launched { ce_batch *b = nullptr; std::vector<size_t> items; };
+    std::vector<launched> running;  // per chunk, while launched and not collected: its batch and items in pair order
+    ce_batch *filling = nullptr;    // the batch of the chunk begun last
+    int rc = CE_OK;
+    auto collect = [&](size_t c) -> int {  // waits for the chunk's ev_run; its scores reach out[] only while the call succeeds
+        const launched l = std::exchange(running[c], launched{});
+        std::vector<ce_scores> tmp(l.items.size());
+        const int r = ce_batch_collect(l.b, (uint32_t)tmp.size(), tmp.data());
+        for (size_t k = 0; k < tmp.size() && r == CE_OK && rc == CE_OK; k++) out[l.items[k]] = tmp[k];
+        return r;
     };
-    std::vector<chunk> chunks;
+    auto run_chunk = [&](uint32_t w, uint32_t h, size_t c) -> int {
+        const ce_plan_chunk &p = plan[c];
+        if (p.collect_first != ce_plan_none)  // the ring slot's batch still runs an earlier chunk of this call
+            if (int r = collect(p.collect_first)) return r;
+        ce_batch *b = nullptr;
+        if (int r = shape_batch(ctx, w, h, p.max_pairs, p.slot, &b)) return r;
+        filling = b;
+        std::vector<upload_job> jobs;
+        std::vector<size_t> items;
+        for (uint32_t s = 0; s < p.refs.size(); s++) {
+            jobs.push_back({b->d_refs + (size_t)s * b->img_bytes, pairs[p.refs[s][0]].reference});
+            for (size_t i : p.refs[s]) {
+                if (int r = ce_batch_bind_pair(b, (uint32_t)items.size(), s)) return r;
+                jobs.push_back({b->d_tests + items.size() * b->img_bytes, pairs[i].test});
+                items.push_back(i);
+            }
+        }
+        invalidate_reference_state(b);
+        if (int r = upload_many(b, jobs)) return r;
+        if (test_luts)  // ICC -> sRGB of the decoded images, on the upload stream behind their copies (icc.rs:69-103)
+            for (size_t k = 0; k < items.size(); k++)
+                if (int r = apply_lut(b, b->d_tests + k * b->img_bytes, test_luts[items[k]])) return r;
+        if (int r = ce_batch_launch(b, (uint32_t)items.size(), metric_mask, flags, intensity_target)) return r;
+        running[c] = {b, std::move(items)};
+        return CE_OK;
+    };
     uint32_t ring = 0;
-    for (auto &kv : buckets) {
-        const std::vector<size_t> &idx = kv.second;
-        // group the bucket's items by reference pointer, first-appearance order
-        std::map<const uint8_t *, size_t> group_of;
-        std::vector<std::vector<size_t>> groups;
-        for (size_t i : idx) {
-            auto it = group_of.find(pairs[i].reference);
-            if (it == group_of.end()) {
-                group_of[pairs[i].reference] = groups.size();
-                groups.emplace_back();
-                groups.back().push_back(i);
-            } else {
-                groups[it->second].push_back(i);
-            }
-        }
-        // How many chunks a bucket that fits is cut into (the upload of one chunk then overlaps the kernels of the one
-        // before).  Measured on the 54-pair Kodak bucket with three metrics (round 2): one chunk 9.1 ms per grid, two 12.7,
-        // three 10.1 - small launches cost more than the hidden upload saves - so a bucket is only cut once it holds at
-        // least 64 pairs per chunk; buckets of different shapes still overlap (each has its own batch and upload stream).
-        // CE_EVAL_BATCH_CHUNKS (1..3) forces the count for A/B runs.
-        static const size_t forced_chunks = [] {
-            const char *e = std::getenv("CE_EVAL_BATCH_CHUNKS");
-            const int v = e ? std::atoi(e) : 0;
-            return (size_t)(v >= 1 && v <= (int)ce_ctx::kPoolRing ? v : 0);
-        }();
-        const size_t n_chunks = forced_chunks ? std::min<size_t>(forced_chunks, std::max<size_t>(1, idx.size()))
-                                              : std::min<size_t>(ce_ctx::kPoolRing, std::max<size_t>(1, idx.size() / 64));
-        size_t target = (idx.size() + n_chunks - 1) / n_chunks;
-        // ... and a chunk must fit the device: cap the pairs per chunk by bytes per pair (every pair budgeted with a
-        // reference of its own) against a share of the free memory; a grid larger than that streams through the ring
-        // in more chunks.  A reference with more tests than the cap is split (its reference is uploaded once per part).
-        {
-            const size_t per_pair = ce_estimate_batch_bytes(kv.first.first, kv.first.second, 1, 2, metric_mask) -
-                                    ce_estimate_batch_bytes(kv.first.first, kv.first.second, 1, 1, metric_mask) +
-                                    ce_estimate_batch_bytes(kv.first.first, kv.first.second, 2, 1, metric_mask) -
-                                    ce_estimate_batch_bytes(kv.first.first, kv.first.second, 1, 1, metric_mask);  // a pair with a reference of its own
-            const size_t cap = std::max<size_t>(1, chunk_budget(ctx) / std::max<size_t>(per_pair, 1));
-            target = std::min(target, cap);
-            // a pooled batch of this shape that is a little smaller than today's target (the estimate above and what
-            // hipMemGetInfo reports move by a few per cent between calls) is used as it is rather than reallocated
-            {
-                auto it0 = ctx->shape_pool.find(std::make_tuple(kv.first.first, kv.first.second, 0u));
-                if (it0 != ctx->shape_pool.end() && it0->second->max_pairs < target && (size_t)it0->second->max_pairs * 4 >= target * 3)
-                    target = it0->second->max_pairs;
-            }
-            std::vector<std::vector<size_t>> split;
-            for (auto &g : groups)
-                for (size_t o = 0; o < g.size(); o += target)
-                    split.emplace_back(g.begin() + o, g.begin() + std::min(g.size(), o + target));
-            groups.swap(split);
-        }
-        // The upload of the FIRST chunk of a call overlaps nothing, so a bucket that needs several chunks starts with a
-        // small one and grows geometrically up to the target (an upload costs about half of what the kernels of the same
-        // pairs do, so each chunk's kernels still cover the upload of the next, twice as large).  CE_EVAL_BATCH_RAMP = pairs
-        // of the first chunk (0 = every chunk at the target).
-        static const size_t ramp0 = [] {
-            const char *e = std::getenv("CE_EVAL_BATCH_RAMP");
-            return (size_t)(e ? std::max(0, std::atoi(e)) : 64);  // 2000 pairs of 512x512: off 106.5 ms, 32 -> 102.1, 64 -> 100.0, 128 -> 101.1
-        }();
-        const bool several = idx.size() > target;
-        size_t limit = (several && ramp0 && ring == 0) ? std::min(ramp0, target) : target;
-        size_t g0 = 0;
-        while (g0 < groups.size()) {
-            size_t g1 = g0, count = 0;
-            while (g1 < groups.size() && (count == 0 || count + groups[g1].size() <= limit)) count += groups[g1++].size();
-            limit = std::min(target, limit * 2);
-            // a ring slot may still be in flight from an earlier chunk of this call: collect it first
-            const uint32_t slot = ring++ % ce_ctx::kPoolRing;
-            for (auto &c : chunks)
-                if (c.b && std::get<2>(c.b->pool_key) == slot && std::get<0>(c.b->pool_key) == kv.first.first &&
-                    std::get<1>(c.b->pool_key) == kv.first.second && !c.items.empty() && c.b->run_pending) {
-                    std::vector<ce_scores> tmp(c.items.size());
-                    int rc = ce_batch_collect(c.b, (uint32_t)c.items.size(), tmp.data());
-                    if (rc != CE_OK) return rc;
-                    for (size_t k = 0; k < c.items.size(); k++) out[c.items[k]] = tmp[k];
-                    c.b = nullptr;  // collected
-                }
-            ce_batch *b = nullptr;
-            // (a bucket cut into several chunks sizes every ring slot for the target: the small first chunks do not make a
-            // slot that a later, larger chunk of the same call would have to reallocate)
-            int rc = shape_batch(ctx, kv.first.first, kv.first.second, (uint32_t)(several ? std::max(count, target) : count), slot, &b);
-            if (rc != CE_OK) return rc;
-            b->pool_key = std::make_tuple(kv.first.first, kv.first.second, slot);
-            chunk ch{b, {}};
-            std::vector<upload_job> jobs;
-            uint32_t k = 0;
-            for (size_t g = g0; g < g1; g++) {
-                const uint32_t ref_slot = (uint32_t)(g - g0);
-                jobs.push_back({b->d_refs + (size_t)ref_slot * b->img_bytes, pairs[groups[g][0]].reference});
-                for (size_t i : groups[g]) {
-                    rc = ce_batch_bind_pair(b, k, ref_slot);
-                    if (rc != CE_OK) return rc;
-                    jobs.push_back({b->d_tests + (size_t)k * b->img_bytes, pairs[i].test});
-                    ch.items.push_back(i);
-                    k++;
-                }
-            }
-            invalidate_reference_state(b);
-            rc = upload_many(b, jobs);
-            if (rc != CE_OK) return rc;
-            if (test_luts)  // ICC -> sRGB of the decoded images, on the upload stream behind their copies (icc.rs:69-103)
-                for (uint32_t kk = 0; kk < k; kk++)
-                    if (const ce_lut *lut = test_luts[ch.items[kk]]) {
-                        rc = apply_lut(b, b->d_tests + (size_t)kk * b->img_bytes, lut);
-                        if (rc != CE_OK) return rc;
-                    }
-            rc = ce_batch_launch(b, k, metric_mask, flags, intensity_target);
-            if (rc != CE_OK) return rc;
-            chunks.push_back(std::move(ch));
-            g0 = g1;
-        }
+    for (auto it = buckets.begin(); it != buckets.end() && rc == CE_OK; ++it) {
+        const uint32_t w = it->first.first, h = it->first.second;
+        std::vector<const void *> refs;
+        for (size_t i : it->second) refs.push_back(pairs[i].reference);
+        const size_t per_pair = ce_estimate_batch_bytes(w, h, 1, 2, metric_mask) - ce_estimate_batch_bytes(w, h, 1, 1, metric_mask) +
+                                ce_estimate_batch_bytes(w, h, 2, 1, metric_mask) - ce_estimate_batch_bytes(w, h, 1, 1, metric_mask);  // a pair with a reference of its own
+        auto pooled = ctx->shape_pool.find(std::make_tuple(w, h, 0u));
+        const ce_plan_inputs in{chunk_budget(ctx), per_pair, pooled != ctx->shape_pool.end() ? pooled->second->max_pairs : 0u, forced_chunks, ramp0};
+        const size_t first = plan.size();
+        ce_plan_bucket(it->second, refs, in, ring, plan);
+        running.resize(plan.size());
+        for (size_t c = first; c < plan.size() && rc == CE_OK; c++) rc = run_chunk(w, h, c);
     }
-    for (auto &c : chunks) {
-        if (!c.b) continue;  // already collected when its ring slot was reused
-        std::vector<ce_scores> tmp(c.items.size());
-        int rc = ce_batch_collect(c.b, (uint32_t)c.items.size(), tmp.data());
-        if (rc != CE_OK) return rc;
-        for (size_t k = 0; k < c.items.size(); k++) out[c.items[k]] = tmp[k];
-    }
-    return CE_OK;
+    // the one exit: every launched chunk is waited for (its batch leaves the in-flight count), and a failed call drains the
+    // batch it was filling before the caller's buffers can go away
+    for (size_t c = 0; c < plan.size(); c++)
+        if (running[c].b) {
+            const int r = collect(c);
+            if (rc == CE_OK) rc = r;
+        }
+    if (rc != CE_OK && filling) drain_batch(filling);
+    return rc;
 }
 
 int ce_eval_pair(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test, size_t test_len,
@@ -1456,10 +1391,7 @@ int ce_ref_create(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, u
 {
     if (!ctx || !reference || !out) return CE_ERR_INVALID_ARG;
     *out = nullptr;
-    if (reference_len != (size_t)width * height * 3)
-        return fail(ctx, CE_ERR_BAD_LENGTH, "Invalid image size: expected " +
-                                                 std::to_string((size_t)width * height * 3) + " bytes, got " +
-                                                 std::to_string(reference_len));
+    if (reference_len != (size_t)width * height * 3) return bad_length(ctx, (size_t)width * height * 3, reference_len);
     ce_batch *b = nullptr;
     int rc = ce_batch_create(ctx, width, height, 1, 1, &b);
     if (rc != CE_OK) return rc;
@@ -1514,10 +1446,7 @@ int ce_ref_compare_many(ce_ref *ref, const uint8_t *const *tests, const size_t *
     for (uint32_t i = 0; i < n_tests && rc == CE_OK; i++)
         rc = out[i].status != CE_OK ? ce_batch_bind_pair(b, i, 0) : ce_batch_set_test(b, i, 0, tests[i], test_lens[i]);
     if (rc == CE_OK) rc = ce_batch_run(b, n_tests, metric_mask, ref->flags, intensity_target, tmp.data());
-    if (rc != CE_OK) {  // copies straight from the caller's memory may still be queued: drain them before the buffers go away
-        hipStreamSynchronize(b->up_stream);
-        hipStreamSynchronize(ctx->stream);
-    }
+    if (rc != CE_OK) drain_batch(b);  // copies straight from the caller's memory may still be queued
     b->caller_blocks = false;
     if (rc != CE_OK) return rc;
     for (uint32_t i = 0; i < n_tests; i++)

@@ -14,6 +14,7 @@
 
 #include "ce_metrics.h"
 #include "ce_metrics_debug.h"
+#include "ce_plan.h"
 
 #define CE_MAX_SCALES 6      // SSIMULACRA2 pyramid depth
 #define CE_SSIM2_STREAMS 5   // blur(a), blur(b), blur(a*a), blur(b*b), blur(a*b)
@@ -74,7 +75,7 @@ struct ce_ctx {
     // scratch batches for the single-pair / mixed-shape entry points, keyed by shape
     // scratch pool for the host-buffer entry points: up to kPoolRing batches per shape (ce_eval_batch streams a large
     // bucket through them in chunks so that the upload of one chunk overlaps the kernels of the previous one)
-    static constexpr uint32_t kPoolRing = 3;
+    static constexpr uint32_t kPoolRing = ce_plan_ring_slots;
     // largest device footprint one ce_eval_batch chunk is sized for (ce_api.cpp: chunk_budget)
     static constexpr size_t kChunkBytesMax = (size_t)48 << 30;
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, ce_batch *> shape_pool;
@@ -126,7 +127,6 @@ struct ce_batch {
     uint32_t *d_ref_off = nullptr, *d_ref_idx = nullptr;  // ... then reference -> its pairs (CSR: [max_refs + 1] offsets, [max_pairs] pair indices)
     std::vector<uint32_t> h_pair_ref;
     bool pair_ref_dirty = true;
-    std::tuple<uint32_t, uint32_t, uint32_t> pool_key{0, 0, 0};  // (w, h, ring slot) when owned by a context's scratch pool
     uint32_t pair_ref_version = 0;  // bumped whenever the pair -> reference table changes
     // pinned staging ring for host -> device uploads: the host copy into slot k overlaps the DMA of slot k-1
     static constexpr int kStages = 8;  // two per upload worker (ce_eval_batch fills a bucket with 4 host threads)
@@ -138,6 +138,7 @@ struct ce_batch {
     hipStream_t up_stream = nullptr;
     hipEvent_t ev_up = nullptr, ev_run = nullptr;  // uploads done / last launch done
     bool uploads_pending = false, run_pending = false;
+    bool inline_pending = false;  // a slot was written on the context's stream since the last launch (ce_api.cpp: order_write)
     bool counted_in_flight = false;  // this batch is in the device's launched-and-not-collected count (ce_api.cpp: g_in_flight)
     // wide ingest (RGBA8 / 16-bit sources): one pinned + one device staging image of 8 B/px, made on first use
     // (two of each: while image k's copy and conversion are in flight the host fills the other pair, so a sweep of wide

@@ -1,0 +1,71 @@
+// How ce_eval_batch cuts a shape bucket into chunks: plain C++ without device calls, checked on the host by
+// tests/cpp/test_eval_plan.cpp.  The executor (ce_api.cpp) reads the inputs from its context and runs the chunks in order.
+#pragma once
+
+#include <algorithm>
+#include <cstdint>
+#include <map>
+#include <vector>
+
+inline constexpr uint32_t ce_plan_ring_slots = 3;  // pooled batches per shape a bucket streams through (ce_ctx::kPoolRing)
+inline constexpr size_t ce_plan_none = ~(size_t)0;
+
+struct ce_plan_inputs {
+    size_t budget;          // bytes one chunk may allocate (chunk_budget, read once per bucket)
+    size_t per_pair;        // estimated device bytes of one pair with a reference of its own
+    uint32_t pooled_pairs;  // max_pairs of this shape's pooled batch on ring slot 0, 0 if there is none
+    size_t forced_chunks;   // CE_EVAL_BATCH_CHUNKS, 0 = by size
+    size_t ramp;            // CE_EVAL_BATCH_RAMP: pairs of the call's first chunk, 0 = every chunk at the target
+};
+
+struct ce_plan_chunk {
+    uint32_t slot;                          // ring slot: the pooled batch (w, h, slot) the chunk runs on
+    uint32_t max_pairs;                     // pairs that batch is allocated for
+    size_t collect_first;                   // the earlier chunk on the same batch, collected before this one is filled
+    std::vector<std::vector<size_t>> refs;  // per reference slot, its items (indices into the call's pairs)
+};
+
+// Appends the chunks of one bucket to `plan`.  refs[j] is the reference pointer of items[j]; ring counts the call's
+// chunks so far (0: the next one is the call's first).
+inline void ce_plan_bucket(const std::vector<size_t> &items, const std::vector<const void *> &refs, const ce_plan_inputs &in,
+                           uint32_t &ring, std::vector<ce_plan_chunk> &plan)
+{
+    // all pairs of a reference stay together, identical reference pointers share one device slot (first-appearance order)
+    std::map<const void *, size_t> group_of;
+    std::vector<std::vector<size_t>> groups;
+    for (size_t j = 0; j < items.size(); j++) {
+        const size_t g = group_of.emplace(refs[j], groups.size()).first->second;
+        if (g == groups.size()) groups.emplace_back();
+        groups[g].push_back(items[j]);
+    }
+    // A bucket that fits is cut into chunks (the upload of one overlaps the kernels of the one before) only once it holds
+    // 64 pairs per chunk: on the 54-pair Kodak bucket with three metrics one chunk took 9.1 ms per grid, two 12.7, three
+    // 10.1 (round 2).  Buckets of different shapes still overlap: each has its own batch and upload stream.
+    const size_t n = items.size();
+    const size_t n_chunks = in.forced_chunks ? std::min<size_t>(in.forced_chunks, std::max<size_t>(1, n))
+                                             : std::min<size_t>(ce_plan_ring_slots, std::max<size_t>(1, n / 64));
+    // ... and fits the budget (a larger grid streams through the ring in more chunks; a reference with more tests than
+    // that is split and uploaded once per part)
+    size_t target = std::min((n + n_chunks - 1) / n_chunks, std::max<size_t>(1, in.budget / std::max<size_t>(in.per_pair, 1)));
+    // a pooled batch a little smaller than that (estimate and free memory move by a few per cent) is used as it is
+    if (in.pooled_pairs < target && (size_t)in.pooled_pairs * 4 >= target * 3) target = in.pooled_pairs;
+    std::vector<std::vector<size_t>> split;
+    for (auto &g : groups)
+        for (size_t o = 0; o < g.size(); o += target) split.emplace_back(g.begin() + o, g.begin() + std::min(g.size(), o + target));
+    // The call's FIRST upload overlaps nothing, so its chunks start small and double up to the target (an upload costs
+    // about half of the same pairs' kernels, so each chunk's kernels still cover the next one's upload).
+    const bool several = n > target;
+    size_t limit = (several && in.ramp && ring == 0) ? std::min(in.ramp, target) : target;
+    const size_t bucket_begin = plan.size();
+    for (size_t g0 = 0, g1 = 0; g0 < split.size(); g0 = g1) {
+        size_t count = 0;
+        while (g1 < split.size() && (count == 0 || count + split[g1].size() <= limit)) count += split[g1++].size();
+        limit = std::min(target, limit * 2);
+        // several chunks: every ring slot is sized for the target, so that a later, larger chunk does not reallocate it
+        ce_plan_chunk c{ring++ % ce_plan_ring_slots, (uint32_t)(several ? std::max(count, target) : count), ce_plan_none,
+                        std::vector<std::vector<size_t>>(split.begin() + g0, split.begin() + g1)};
+        for (size_t p = bucket_begin; p < plan.size(); p++)
+            if (plan[p].slot == c.slot) c.collect_first = p;  // the latest one; the earlier ones it collected itself
+        plan.push_back(std::move(c));
+    }
+}

@@ -171,3 +171,72 @@ def test_icc_profiles_of_decoded_images_are_applied_on_the_device_exactly(gpu_ct
     ses.evaluate_image("again.png", S.ImageData.rgb(src, w, h))
     assert len(calls) == 2  # tables are cached per profile for the session's lifetime
     ses.close()
+
+
+def _scores(s):
+    return (s.psnr, s.ssimulacra2, s.dssim, s.butteraugli, s.status)
+
+
+def test_inline_and_upload_stream_writes_to_one_slot_keep_their_order(gpu_ctx, ce, workloads):
+    """A batch small enough for the inline route (ce_batch_set_test copies on the context's stream) also takes
+    ce_batch_set_test_fmt (upload stream + ingest kernel): the later write into a slot wins, in either order."""
+    w, h = 96, 64
+    ref = workloads.make_reference(w, h, 11)
+    a, b = workloads.distort(ref, 30), workloads.distort(ref, 90)
+    cfg = ce.MetricConfig.all()
+
+    def rgba(img):
+        return np.concatenate([img.reshape(-1, 3), np.full((w * h, 1), 77, np.uint8)], axis=1)
+
+    want = {}
+    for name, img in (("a", a), ("b", b)):
+        bt = ce.Batch(gpu_ctx, w, h, 1, 1)
+        bt.set_reference(0, ref)
+        bt.set_test(0, 0, img)
+        want[name] = _scores(bt.run(1, cfg)[0])
+        bt.close()
+    assert want["a"] != want["b"]
+    bt = ce.Batch(gpu_ctx, w, h, 1, 1)
+    bt.set_reference(0, ref)
+    bt.set_test(0, 0, a)
+    bt.set_test_fmt(0, 0, rgba(b), ce.PIXEL_RGBA8)
+    assert _scores(bt.run(1, cfg)[0]) == want["b"]
+    bt.set_test_fmt(0, 0, rgba(b), ce.PIXEL_RGBA8)
+    bt.set_test(0, 0, a)
+    assert _scores(bt.run(1, cfg)[0]) == want["a"]
+    bt.close()
+
+
+def test_eval_batch_error_leaves_the_context_clean(gpu_ctx, ce, workloads):
+    """An unknown metric bit over page-locked images that a small CE_EVAL_BATCH_BYTES cuts into several chunks fails with
+    CE_ERR_INVALID_ARG; the buffers are then overwritten with the real images and a clean call on the same context scores
+    them bit for bit like a call on a fresh context."""
+    w, h, n_refs, n_tests = 128, 96, 4, 3
+    cfg = ce.MetricConfig.all()
+    slab = gpu_ctx.host_buffer(n_refs * (n_tests + 1) * w * h * 3).reshape(n_refs * (n_tests + 1), w * h * 3)
+    slab[:] = np.random.default_rng(5).integers(0, 256, slab.shape, dtype=np.uint8)
+    items = [(slab[(n_tests + 1) * i], slab[(n_tests + 1) * i + 1 + k], w, h) for i in range(n_refs) for k in range(n_tests)]
+    pl = ce.PairList(items)
+    per_pair = ce.estimate_batch_bytes(w, h, 2, 2, cfg) - ce.estimate_batch_bytes(w, h, 1, 1, cfg)
+    old = os.environ.get("CE_EVAL_BATCH_BYTES")
+    try:
+        os.environ["CE_EVAL_BATCH_BYTES"] = str(per_pair * 4)  # 12 pairs in chunks of <= 4
+        out = (ce.CeScores * len(items))()
+        rc = ce.lib().ce_eval_batch(gpu_ctx._h, len(items), pl.descs, cfg.mask | (1 << 30), 0, ce.DEFAULT_INTENSITY_TARGET, out)
+        assert rc == ce.CE_ERR_INVALID_ARG
+        assert gpu_ctx._err() == "unknown metric bit"
+        for i in range(n_refs):
+            ref = workloads.make_reference(w, h, 600 + i)
+            slab[(n_tests + 1) * i] = ref.reshape(-1)
+            for k, q in enumerate((35, 70, 92)):
+                slab[(n_tests + 1) * i + 1 + k] = workloads.distort(ref, q).reshape(-1)
+        got = [_scores(s) for s in gpu_ctx.eval_batch(pl, cfg)]
+        with ce.Context(0) as fresh:
+            want = [_scores(s) for s in fresh.eval_batch(pl, cfg)]
+    finally:
+        if old is None:
+            os.environ.pop("CE_EVAL_BATCH_BYTES", None)
+        else:
+            os.environ["CE_EVAL_BATCH_BYTES"] = old
+    assert got == want
+    assert all(s[4] == 0 for s in want) and len({s[1] for s in want}) == len(want)

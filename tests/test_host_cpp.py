@@ -33,6 +33,16 @@ def test_host_mirror_on_gpu(ce, tmp_path):
     assert out.returncode == 0, out.stdout + out.stderr
 
 
+def test_eval_batch_chunk_plan(tmp_path):
+    """ce_eval_batch's chunk planner (codec-eval_amd/csrc/ce_plan.h: plain C++) against plans derived by hand from the
+    rules it implements (tests/cpp/test_eval_plan.cpp)."""
+    exe = str(tmp_path / "test_eval_plan")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "codec-eval_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "cpp", "test_eval_plan.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+
+
 def test_cpp_report_writers_match_the_python_ones(ce, tmp_path):
     """codec_eval_report.hpp (JSON + CSV of the reference's wire formats) against codec-eval_amd/reports.py, which is
     pinned on the reference's own baselines/*.json."""
