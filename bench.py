@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — BASELINE.json's metric on the MI355X hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run measures the headline alone: it generates and uploads the grid, runs W warm-up steps and K timed ones,
+writes --dump-outputs if asked, and prints the result line (its extra objects are null).  --full adds everything
+else the line can carry (the solo pass, HIP events in the timed region and the roofline built from them, the other
+legs listed at the end of this text, the CPU baseline with the oracle check, and for N > 1 the recomputed shard
+sample and the strong-scaling leg); the --no-* options switch single legs of a --full run off.
 
 N > 1 runs either way: under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (the
 driver's form), or as the plain command above — then this process, which makes no GPU call, starts N rank processes
@@ -21,9 +27,9 @@ round 1-2's headline (the 72-pair Kodak grid alone) for continuity.
 Butteraugli; 4 = CID22 x 8 qualities, SSIMULACRA2 + DSSIM; 5 = codec-iter dense sweep, all metrics, XYB on/off).
 
 N > 1: ONE global grid is partitioned over the ranks by codec-eval_amd/sharding.py (by reference image; config 5
-falls back to (image, codec-config) units when that balances better), no data-path collective, the scores are
-gathered to rank 0 in global order and a sample of them is recomputed there.  Default workload: the global grid is N
-sweeps, so per-GPU work is fixed => "scaling": "weak"; the same line then carries `strong`: BASELINE configs[3]'s
+falls back to (image, codec-config) units when that balances better), no data-path collective; with --full the scores
+are gathered to rank 0 in global order and a sample of them is recomputed there.  Default workload: the global grid is N
+sweeps, so per-GPU work is fixed => "scaling": "weak"; with --full the same line then carries `strong`: BASELINE configs[3]'s
 FIXED grid (250 x 8, SSIMULACRA2 + DSSIM) partitioned over the same ranks and timed after the default one.  configs 4
 and 5 as the main workload are fixed grids => "strong".  torch.distributed (gloo, host side only) carries the barriers,
 the max-over-ranks of the time and the gather of the tiny score lists — no RCCL anywhere (north_star).
@@ -32,7 +38,7 @@ the max-over-ranks of the time and the gather of the tiny score lists — no RCC
 (float64, one entry per pair, pairs sorted by (group, reference, variant, quality index)); the grid is seeded, so two builds
 run with the same arguments can be compared score for score.
 
-Extra JSON objects: "roofline" (the dominant kernel: algorithmic bytes per launch over its HIP-event duration alone on
+Extra JSON objects (--full): "roofline" (the dominant kernel: algorithmic bytes per launch over its HIP-event duration alone on
 the GPU = `frac`, in the timed region = `in_region_*`; the roof that binds it from the SQ counters under profiles/;
 every kernel's row in `kernels`; the step against this round's and round 2's frozen byte model), "per_metric",
 "kodak_only", "per_call" (one blocking call per encode: crates/codec-iter/src/gpu.rs:83-109), "end_to_end"
@@ -94,9 +100,16 @@ def parse():
     ap.add_argument("--inflight", type=int, default=0, help="batches launched and not yet collected (default: 2 * batches - 1 of a small grid, 3 of the sweep)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the scores of the last one to DIR/<metric>.npy (float64, global pair order)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline (solo pass and roofline, per-metric, kodak_only, end_to_end, "
+                         "per_call, CPU baseline and oracle check; N > 1: shard recomputation and the strong leg); the --no-* options "
+                         "switch legs of a --full run off")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run: set up, warm up, time the steps, dump, print the line - every other leg is off
+        for leg in ("no_solo", "no_events", "no_per_metric", "no_end_to_end", "no_per_call", "no_kodak_only", "no_strong", "no_cpu_baseline"):
+            setattr(args, leg, True)
     return args
 
 
@@ -432,14 +445,19 @@ def main():
             col = METRIC_NAMES.index(m)
             np.save(os.path.join(out_dir, f"{m}.npy"), np.array([v[col] for _, v in rows], np.float64))
 
-    def gather_and_check(wk, res, scores):
-        """Scores of the last step in global order on rank 0; one item of every other rank is recomputed there."""
+    def gather_and_check(wk, res, scores, check=True):
+        """Every rank's share of the grid; with `check`, the scores of the last step in global order on rank 0, where one
+        item of every other rank is recomputed."""
         info = [None] * world
         dist.all_gather_object(info, (wk.mp_per_step, wk.pairs_per_step))
+        all_mp, all_pairs = [x[0] for x in info], [x[1] for x in info]
+        shard = {"partition": wk.mode, "pairs_per_rank": all_pairs, "megapixels_per_rank": [round(x, 3) for x in all_mp],
+                 "imbalance_max_over_mean": round(sh.imbalance(all_mp), 4)} if rank == 0 else None
+        if not check:
+            return all_mp, all_pairs, shard
         local = score_rows(wk, res, scores)
         merged = [None] * world if rank == 0 else None
         dist.gather_object(local, merged, dst=0)
-        all_mp, all_pairs = [x[0] for x in info], [x[1] for x in info]
         if rank != 0:
             return all_mp, all_pairs, None
         flat = sorted((t for part in merged for t in part), key=lambda t: t[0])
@@ -454,9 +472,7 @@ def main():
                 got = (m.dssim or 0.0, m.ssimulacra2 or 0.0, m.butteraugli or 0.0, m.psnr or 0.0)
                 max_diff = max(max_diff, max(abs(a - b) for a, b in zip(got, want)))
         assert max_diff == 0.0, f"a gathered score differs from its recomputation on rank 0 ({max_diff})"
-        return all_mp, all_pairs, {"partition": wk.mode, "pairs_per_rank": all_pairs, "megapixels_per_rank": [round(x, 3) for x in all_mp],
-                                   "imbalance_max_over_mean": round(sh.imbalance(all_mp), 4), "gathered_scores": len(flat),
-                                   "recomputed_on_rank0": len(foreign), "recomputed_max_abs_diff": max_diff}
+        return all_mp, all_pairs, dict(shard, gathered_scores=len(flat), recomputed_on_rank0=len(foreign), recomputed_max_abs_diff=max_diff)
 
     # ---- resident batches -----------------------------------------------------------------------------------------------------
     small = wkl.mp_per_step * wkl.n_eval_metrics < 1000.0
@@ -504,7 +520,7 @@ def main():
     if dist is not None:
         secs = [None] * world
         dist.all_gather_object(secs, round(local_elapsed, 4))
-        all_mp, all_pairs, shard = gather_and_check(wkl, res, scores)
+        all_mp, all_pairs, shard = gather_and_check(wkl, res, scores, check=args.full)
         if shard is not None:
             shard["seconds_per_rank"] = secs
     # MP/s = reference pixels x (pair, metric) evaluations / wall time
@@ -513,7 +529,7 @@ def main():
 
     # ---- roofline -----------------------------------------------------------------------------------------------------------------
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         peak = rf.HBM_PEAK_GBPS
         mp_many = sum(g.megapixels for g, _, _ in wkl.launches if len(g.pairs) >= 6 * len(g.references))
         traffic_tbl, sq_tbl, prof_tag = read_profile_tables(many_per_reference=mp_many > 0.5 * wkl.mp_per_step)

@@ -1,4 +1,4 @@
-"""bench.py's output contract, on the device: one JSON line with the required keys (N = 1), and the N = 2 path
+"""bench.py's output contract, on the device: one JSON line with the required keys (N = 1; the extra legs with --full), and the N = 2 path
 (torch.distributed.run, one process per rank, max-over-ranks time, rank 0 prints) rehearsed with both ranks sharing
 this box's single GPU over gloo (CE_BENCH_SHARE_DEVICE=1 - the driver never sets it)."""
 import json
@@ -21,7 +21,7 @@ def _json_lines(out):
 
 def test_single_gpu_line(tmp_path):
     dump = tmp_path / "outputs"
-    out = subprocess.run([sys.executable, "bench.py", "--quick", "--steps", "4", "--warmup", "1", "--dump-outputs", str(dump)], cwd=ROOT,
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--quick", "--steps", "4", "--warmup", "1", "--dump-outputs", str(dump)], cwd=ROOT,
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = _json_lines(out.stdout)
@@ -77,6 +77,30 @@ def test_single_gpu_line(tmp_path):
     assert 0.2 * d["value"] < e["pageable"]["value"] <= e["value"] * 1.6
 
 
+def test_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full the line carries the headline alone: the same keys and meaning, every extra leg null, the scores dumped."""
+    dump = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, "bench.py", "--quick", "--steps", "4", "--warmup", "1", "--dump-outputs", str(dump)], cwd=ROOT,
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = _json_lines(out.stdout)
+    assert len(lines) == 1
+    d = lines[0]
+    assert REQUIRED <= set(d), REQUIRED - set(d)
+    assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "MP/s" and d["scaling"] == "weak"
+    assert d["higher_is_better"] is True and d["vs_baseline"] is None and d["data"] == "synthetic" and d["dtype"] == "f32"
+    assert set(d["config"]["metrics"]) == {"ssimulacra2", "dssim", "butteraugli"} and d["config"]["metric_evaluations_per_pair"] == 3
+    assert d["config"]["pairs_per_step"] == 6 * 3 + 8 * 8
+    # value = reference pixels x (pair, metric) evaluations / wall time of the timed steps
+    assert abs(d["value"] - 3 * d["config"]["megapixels_per_step"] / (d["ms_per_step"] / 1e3)) < 1e-2 * d["value"]
+    for leg in ("roofline", "cpu_baseline", "per_metric", "kodak_only", "per_call", "end_to_end", "shard", "strong", "max_rel_dev_vs_oracle"):
+        assert d[leg] is None, leg
+    assert sorted(os.listdir(dump)) == sorted(f"{m}.npy" for m in d["config"]["metrics"])
+    for m in d["config"]["metrics"]:
+        a = np.load(dump / f"{m}.npy")
+        assert a.dtype == np.float64 and a.shape == (d["config"]["pairs_per_step"],) and np.isfinite(a).all()
+
+
 def _check_two_rank_line(out):
     assert out.returncode == 0, out.stderr[-2000:]
     lines = _json_lines(out.stdout)
@@ -102,7 +126,7 @@ def test_two_rank_path_sharing_one_device():
     """The driver's form: torch.distributed.run starts the ranks."""
     env = dict(os.environ, CE_BENCH_SHARE_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29541", "bench.py", "--gpus", "2", "--quick", "--steps", "4", "--warmup", "1"]
+           "--master-port", "29541", "bench.py", "--gpus", "2", "--full", "--quick", "--steps", "4", "--warmup", "1"]
     _check_two_rank_line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900))
 
 
@@ -111,7 +135,7 @@ def test_two_ranks_from_the_plain_command():
     env = dict(os.environ, CE_BENCH_SHARE_DEVICE="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--quick", "--steps", "4", "--warmup", "1"]
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--full", "--quick", "--steps", "4", "--warmup", "1"]
     _check_two_rank_line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900))
 
 
@@ -119,10 +143,32 @@ def test_two_rank_fixed_grid_strong_scaling_with_unit_fallback():
     """configs[4] (few references): the fixed grid is split by (image, codec-config) when that balances better."""
     env = dict(os.environ, CE_BENCH_SHARE_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29543", "bench.py", "--gpus", "2", "--config", "5", "--refs", "3", "--steps", "2", "--warmup", "1", "--no-solo"]
+           "--master-port", "29543", "bench.py", "--gpus", "2", "--full", "--config", "5", "--refs", "3", "--steps", "2", "--warmup", "1", "--no-solo"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _json_lines(out.stdout)[0]
     assert d["scaling"] == "strong" and d["config"]["pairs_per_step"] == 300
     sh = d["shard"]
     assert sh["partition"] == "image-x-codec-config" and sh["pairs_per_rank"] == [150, 150] and sh["recomputed_max_abs_diff"] == 0.0
+
+
+def test_two_rank_plain_line(tmp_path):
+    """N = 2 without --full: the headline over both ranks and each rank's share of the grid; no recomputation, no strong leg."""
+    env = dict(os.environ, CE_BENCH_SHARE_DEVICE="1")
+    dump = tmp_path / "outputs"
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+           "--master-port", "29545", "bench.py", "--gpus", "2", "--quick", "--steps", "4", "--warmup", "1", "--dump-outputs", str(dump)]
+    out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = _json_lines(out.stdout)
+    assert len(lines) == 1  # rank 0 only
+    d = lines[0]
+    assert d["n_gpus"] == 2 and d["strong"] is None and d["roofline"] is None and d["cpu_baseline"] is None
+    assert abs(d["value"] - 3 * d["config"]["megapixels_per_step"] / (d["ms_per_step"] / 1e3)) < 1e-2 * d["value"]
+    sh = d["shard"]
+    n = 2 * (6 * 3 + 8 * 8)
+    assert sh["partition"] == "reference" and sum(sh["pairs_per_rank"]) == d["config"]["pairs_per_step"] == n
+    assert sh["imbalance_max_over_mean"] == 1.0 and "recomputed_on_rank0" not in sh
+    for m in d["config"]["metrics"]:
+        a = np.load(dump / f"{m}.npy")
+        assert a.shape == (n,) and np.isfinite(a).all()
