@@ -139,6 +139,20 @@ impl HipMetrics {
         self.check(rc, width as u32, height as u32, rgb.len())?;
         Ok(out)
     }
+
+    /// `calculate_butteraugli_with_intensity` returning what `ButteraugliResult` holds (src/metrics/prelude.rs:64-65):
+    /// the score and the per-pixel diffmap, row-major `width * height`, whose maximum is the score.
+    pub fn calculate_butteraugli_with_diffmap(&mut self, reference: &[u8], test: &[u8], width: usize, height: usize,
+                                              intensity_target: f32) -> Result<(f64, Vec<f32>), HipError> {
+        let mut score = 0.0f64;
+        let mut diffmap = vec![0.0f32; width * height];
+        let rc = unsafe {
+            sys::ce_calculate_butteraugli_diffmap(self.ctx, reference.as_ptr(), reference.len(), test.as_ptr(), test.len(), width,
+                                                  height, intensity_target, &mut score, diffmap.as_mut_ptr())
+        };
+        self.check(rc, width as u32, height as u32, test.len())?;
+        Ok((score, diffmap))
+    }
 }
 
 /// Page-locked host bytes (`ce_host_alloc`): a decoder that writes its RGB8 output here lets `evaluate_grid` copy it with

@@ -31,6 +31,7 @@ pub const CE_METRIC_SSIMULACRA2: u32 = 1 << 1;
 pub const CE_METRIC_BUTTERAUGLI: u32 = 1 << 2;
 pub const CE_METRIC_PSNR: u32 = 1 << 3;
 pub const CE_FLAG_XYB_ROUNDTRIP: u32 = 1 << 0;
+pub const CE_FLAG_BUTTERAUGLI_DIFFMAP: u32 = 1 << 1;
 pub const CE_DEFAULT_INTENSITY_TARGET: c_float = 80.0;
 
 pub const CE_PIXEL_RGB8: c_int = 0;
@@ -79,6 +80,9 @@ extern "C" {
                               width: usize, height: usize, out: *mut c_double) -> c_int;
     pub fn ce_calculate_butteraugli(ctx: *mut ce_ctx, reference: *const u8, reference_len: usize, test: *const u8, test_len: usize,
                                     width: usize, height: usize, intensity_target: c_float, out: *mut c_double) -> c_int;
+    pub fn ce_calculate_butteraugli_diffmap(ctx: *mut ce_ctx, reference: *const u8, reference_len: usize, test: *const u8,
+                                            test_len: usize, width: usize, height: usize, intensity_target: c_float,
+                                            score: *mut c_double, diffmap_out: *mut c_float) -> c_int;
     pub fn ce_xyb_roundtrip(ctx: *mut ce_ctx, rgb: *const u8, rgb_len: usize, width: usize, height: usize, out: *mut u8) -> c_int;
     pub fn ce_rgb8_to_dssim_image(ctx: *mut ce_ctx, rgb: *const u8, rgb_len: usize, width: usize, height: usize,
                                   out_rgba_f32: *mut c_float) -> c_int;
@@ -114,6 +118,8 @@ extern "C" {
     pub fn ce_batch_launch(b: *mut ce_batch, n_pairs: u32, metric_mask: u32, flags: u32, intensity_target: c_float) -> c_int;
     pub fn ce_batch_collect(b: *mut ce_batch, n_pairs: u32, out: *mut ce_scores) -> c_int;
     pub fn ce_batch_butteraugli_pnorm3(b: *mut ce_batch, n_pairs: u32, out: *mut c_double) -> c_int;
+    pub fn ce_batch_butteraugli_diffmap(b: *mut ce_batch, first: u32, count: u32, block: u32, out: *mut c_float,
+                                        out_floats: usize) -> c_int;
     pub fn ce_ref_create(ctx: *mut ce_ctx, reference: *const u8, reference_len: usize, width: u32, height: u32, flags: u32,
                          out: *mut *mut ce_ref) -> c_int;
     pub fn ce_ref_compare(r: *mut ce_ref, test: *const u8, test_len: usize, metric_mask: u32, intensity_target: c_float,
@@ -121,6 +127,8 @@ extern "C" {
     pub fn ce_ref_compare_many(r: *mut ce_ref, tests: *const *const u8, test_lens: *const usize, n_tests: u32, metric_mask: u32,
                                intensity_target: c_float, out: *mut ce_scores) -> c_int;
     pub fn ce_ref_stats(r: *const ce_ref, builds: *mut u32) -> c_int;
+    pub fn ce_ref_butteraugli_diffmap(r: *mut ce_ref, first: u32, count: u32, block: u32, out: *mut c_float,
+                                      out_floats: usize) -> c_int;
     pub fn ce_ref_destroy(r: *mut ce_ref);
     pub fn ce_prof_enable(ctx: *mut ce_ctx, on: c_int) -> c_int;
     pub fn ce_prof_filter(ctx: *mut ce_ctx, substring: *const c_char) -> c_int;

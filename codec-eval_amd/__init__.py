@@ -32,6 +32,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 CE_OK, CE_ERR_DIM_MISMATCH, CE_ERR_BAD_LENGTH, CE_ERR_TOO_SMALL, CE_ERR_BACKEND, CE_ERR_INVALID_ARG = range(6)
 METRIC_DSSIM, METRIC_SSIMULACRA2, METRIC_BUTTERAUGLI, METRIC_PSNR = 1, 2, 4, 8
 FLAG_XYB_ROUNDTRIP = 1
+FLAG_BUTTERAUGLI_DIFFMAP = 1 << 1
 PIXEL_RGB8, PIXEL_RGBA8, PIXEL_RGB16_10BIT, PIXEL_RGBA16_10BIT = 0, 1, 2, 3
 DEFAULT_INTENSITY_TARGET = 80.0
 
@@ -116,6 +117,7 @@ _PROTOTYPES = [
     ("ce_calculate_ssimulacra2", _i, [_vp, _u8p, _sz, _u8p, _sz, _sz, _sz, _dp]),
     ("ce_calculate_dssim", _i, [_vp, _u8p, _sz, _u8p, _sz, _sz, _sz, _dp]),
     ("ce_calculate_butteraugli", _i, [_vp, _u8p, _sz, _u8p, _sz, _sz, _sz, _f32, _dp]),
+    ("ce_calculate_butteraugli_diffmap", _i, [_vp, _u8p, _sz, _u8p, _sz, _sz, _sz, _f32, _dp, _vp]),
     ("ce_xyb_roundtrip", _i, [_vp, _u8p, _sz, _sz, _sz, _u8p]),
     ("ce_rgb8_to_dssim_image", _i, [_vp, _u8p, _sz, _sz, _sz, _vp]),
     ("ce_eval_pair", _i, [_vp, _u8p, _sz, _u8p, _sz, _u32, _u32, _u32, _u32, _f32, C.POINTER(CeScores)]),
@@ -142,10 +144,12 @@ _PROTOTYPES = [
     ("ce_batch_launch", _i, [_vp, _u32, _u32, _u32, _f32]),
     ("ce_batch_collect", _i, [_vp, _u32, C.POINTER(CeScores)]),
     ("ce_batch_butteraugli_pnorm3", _i, [_vp, _u32, _dp]),
+    ("ce_batch_butteraugli_diffmap", _i, [_vp, _u32, _u32, _u32, _vp, _sz]),
     ("ce_ref_create", _i, [_vp, _u8p, _sz, _u32, _u32, _u32, C.POINTER(_vp)]),
     ("ce_ref_compare", _i, [_vp, _u8p, _sz, _u32, _f32, C.POINTER(CeScores)]),
     ("ce_ref_compare_many", _i, [_vp, C.POINTER(_u8p), C.POINTER(_sz), _u32, _u32, _f32, C.POINTER(CeScores)]),
     ("ce_ref_stats", _i, [_vp, C.POINTER(_u32 * 3)]),
+    ("ce_ref_butteraugli_diffmap", _i, [_vp, _u32, _u32, _u32, _vp, _sz]),
     ("ce_ref_destroy", None, [_vp]),
     ("ce_prof_enable", _i, [_vp, _i]),
     ("ce_prof_filter", _i, [_vp, C.c_char_p]),
@@ -312,6 +316,22 @@ def perception_from_butteraugli(b: float) -> str:  # mod.rs:223-235
 
 
 @dataclass
+class ButteraugliResult:
+    """ButteraugliResult (src/metrics/prelude.rs:64-65): the score and the per-pixel diffmap, an [h, w] float32 array."""
+    score: float
+    diffmap: np.ndarray
+
+
+def _read_diffmaps(ctx: "Context", fn, handle, width: int, height: int, first: int, count: int, block: int) -> np.ndarray:
+    """[count, ceil(h / block), ceil(w / block)] float32 through ce_batch_butteraugli_diffmap / ce_ref_butteraugli_diffmap."""
+    if block < 1:
+        raise CodecEvalError(CE_ERR_INVALID_ARG, "block must be 1 or a power of two up to 64")
+    out = np.empty((count, -(-height // block), -(-width // block)), np.float32)
+    ctx._check(fn(handle, first, count, block, out.ctypes.data, out.size))
+    return out
+
+
+@dataclass
 class MetricResult:
     dssim: Optional[float] = None
     ssimulacra2: Optional[float] = None
@@ -424,6 +444,17 @@ class Context:
     def calculate_butteraugli_with_intensity(self, reference, test, width: int, height: int, intensity_target: float) -> float:
         """calculate_butteraugli_with_intensity, src/metrics/butteraugli.rs:99."""
         return self._leaf(lib().ce_calculate_butteraugli, reference, test, width, height, float(intensity_target))
+
+    def calculate_butteraugli_diffmap(self, reference, test, width: int, height: int,
+                                      intensity_target: float = DEFAULT_INTENSITY_TARGET) -> ButteraugliResult:
+        """calculate_butteraugli / _with_intensity returning ButteraugliResult{score, diffmap}, src/metrics/butteraugli.rs:45,99
+        and src/metrics/prelude.rs:64-65: diffmap is the [h, w] float32 map whose maximum is the score."""
+        r, t = _buf(reference), _buf(test)
+        score = C.c_double()
+        dm = np.empty((height, width), np.float32)
+        self._check(lib().ce_calculate_butteraugli_diffmap(self._h, r.ctypes.data, r.size, t.ctypes.data, t.size, width, height,
+                                                           float(intensity_target), C.byref(score), dm.ctypes.data))
+        return ButteraugliResult(score.value, dm)
 
     def xyb_roundtrip(self, rgb, width: int, height: int) -> np.ndarray:
         """xyb_roundtrip, src/metrics/xyb.rs:225."""
@@ -589,13 +620,18 @@ class Batch:
     def test_slab(self) -> int:
         return int(lib().ce_batch_test_slab(self._h))
 
-    def run(self, n_pairs: int, config: MetricConfig, intensity_target: float = DEFAULT_INTENSITY_TARGET) -> List[CeScores]:
+    def run(self, n_pairs: int, config: MetricConfig, intensity_target: float = DEFAULT_INTENSITY_TARGET,
+            butteraugli_diffmap: bool = False) -> List[CeScores]:
+        """butteraugli_diffmap=True: also keep every pair's Butteraugli diffmap for butteraugli_diffmaps()."""
         out = (CeScores * n_pairs)()
-        self.ctx._check(lib().ce_batch_run(self._h, n_pairs, config.mask, config.flags, intensity_target, out))
+        flags = config.flags | (FLAG_BUTTERAUGLI_DIFFMAP if butteraugli_diffmap else 0)
+        self.ctx._check(lib().ce_batch_run(self._h, n_pairs, config.mask, flags, intensity_target, out))
         return list(out)
 
-    def launch(self, n_pairs: int, config: MetricConfig, intensity_target: float = DEFAULT_INTENSITY_TARGET):
-        self.ctx._check(lib().ce_batch_launch(self._h, n_pairs, config.mask, config.flags, intensity_target))
+    def launch(self, n_pairs: int, config: MetricConfig, intensity_target: float = DEFAULT_INTENSITY_TARGET,
+               butteraugli_diffmap: bool = False):
+        flags = config.flags | (FLAG_BUTTERAUGLI_DIFFMAP if butteraugli_diffmap else 0)
+        self.ctx._check(lib().ce_batch_launch(self._h, n_pairs, config.mask, flags, intensity_target))
 
     def collect(self, n_pairs: int) -> List[CeScores]:
         out = (CeScores * n_pairs)()
@@ -606,6 +642,12 @@ class Batch:
         out = np.zeros(n_pairs, np.float64)
         self.ctx._check(lib().ce_batch_butteraugli_pnorm3(self._h, n_pairs, out.ctypes.data_as(_dp)))
         return out
+
+    def butteraugli_diffmaps(self, first: int, count: int, block: int = 1) -> np.ndarray:
+        """Diffmaps of pairs [first, first + count) of the last run / launch with butteraugli_diffmap=True, as a
+        [count, ceil(h / block), ceil(w / block)] float32 array: block = 1 is the full map, a power of two up to 64 the
+        maximum over each block x block cell."""
+        return _read_diffmaps(self.ctx, lib().ce_batch_butteraugli_diffmap, self._h, self.width, self.height, first, count, block)
 
     # -- test hooks
     def debug_limit_scales(self, n: int):
@@ -629,12 +671,13 @@ class Batch:
 class ReferenceHandle:
     """Ssimulacra2Reference::{new, compare} (crates/codec-iter/src/eval.rs:138-149, 83-89)."""
 
-    def __init__(self, ctx: Context, reference, width: int, height: int, xyb_roundtrip: bool = False):
-        self.ctx = ctx
+    def __init__(self, ctx: Context, reference, width: int, height: int, xyb_roundtrip: bool = False,
+                 butteraugli_diffmap: bool = False):
+        self.ctx, self.width, self.height = ctx, width, height
         r = _buf(reference)
         self._h = C.c_void_p()
-        ctx._check(lib().ce_ref_create(ctx._h, r.ctypes.data, r.size, width, height,
-                                       FLAG_XYB_ROUNDTRIP if xyb_roundtrip else 0, C.byref(self._h)))
+        flags = (FLAG_XYB_ROUNDTRIP if xyb_roundtrip else 0) | (FLAG_BUTTERAUGLI_DIFFMAP if butteraugli_diffmap else 0)
+        ctx._check(lib().ce_ref_create(ctx._h, r.ctypes.data, r.size, width, height, flags, C.byref(self._h)))
 
     def compare(self, test, config: MetricConfig = None, intensity_target: float = DEFAULT_INTENSITY_TARGET) -> MetricResult:
         config = config or MetricConfig.ssimulacra2_only()
@@ -658,6 +701,11 @@ class ReferenceHandle:
         for s in out:
             res.append(MetricResult.from_c(s) if s.status == 0 else _error_obj(s.status, self.ctx._err()))
         return res
+
+    def butteraugli_diffmaps(self, first: int, count: int, block: int = 1) -> np.ndarray:
+        """Diffmaps of tests [first, first + count) of the last compare / compare_many (handle made with
+        butteraugli_diffmap=True, a config with Butteraugli): see Batch.butteraugli_diffmaps."""
+        return _read_diffmaps(self.ctx, lib().ce_ref_butteraugli_diffmap, self._h, self.width, self.height, first, count, block)
 
     def stats(self):
         """(ssimulacra2, dssim, butteraugli): compares so far that had to build that metric's reference-side state."""

@@ -847,7 +847,10 @@ __device__ __forceinline__ void malta_rows_xy(const ba_f2 *__restrict__ base, ba
 // FINAL (the full-resolution level, launched after the half-resolution one): the pixel's diffmap value takes the
 // half-resolution diffmap (AddSupersampled2x, weight 0.5) and goes straight into the score reductions - max, sum d^3, d^6,
 // d^12 per tile - instead of to memory; !FINAL (the half-resolution level) writes its diffmap.
-template <int MR, int NT, bool FINAL>
+// FINAL && STORE (CE_FLAG_BUTTERAUGLI_DIFFMAP): the same reductions, and the final value of every pixel is also written
+// to `diffmap` ([pair][h][pitch] of the full resolution), one float2 per thread and row - the thread's two columns (0 past
+// the image's right edge, inside the pitch padding).
+template <int MR, int NT, bool FINAL, bool STORE>
 __global__ __launch_bounds__(NT, NT == 256 ? 3 : 4) void k_ba_malta_l2_xy(const float *__restrict__ psy, const uint32_t *__restrict__ pair_ref,
                                                            const float *__restrict__ blurred, const float *__restrict__ mask_vals,
                                                            float *__restrict__ diffmap, geom g, uint32_t max_refs,
@@ -947,7 +950,8 @@ __global__ __launch_bounds__(NT, NT == 256 ? 3 : 4) void k_ba_malta_l2_xy(const 
     float red_m = 0.0f;  // the diffmap is non-negative
     double red_s3 = 0.0, red_s6 = 0.0, red_s12 = 0.0;
 #pragma unroll 1
-    for (int sub = 0; sub < MR / RSTEP; sub++)
+    for (int sub = 0; sub < MR / RSTEP; sub++) {
+    float dmap[2] = {0.0f, 0.0f};  // STORE: the row's two final values of this thread
 #pragma unroll
     for (int r = 0; r < 2; r++) {
         const uint32_t x = bx * MT + 2 * tq + r, y = by * MR + RSTEP * sub + ty;
@@ -998,6 +1002,13 @@ __global__ __launch_bounds__(NT, NT == 256 ? 3 : 4) void k_ba_malta_l2_xy(const 
         red_s6 += d6;
         red_s12 += d6 * d6;
         red_m = fmaxf(red_m, d);
+        if (STORE) dmap[r] = d;
+    }
+    if constexpr (FINAL && STORE) {  // x is even and the pitch a multiple of 32: x < w puts x + 1 inside the row's pitch
+        const uint32_t x = bx * MT + 2 * tq, y = by * MR + RSTEP * sub + ty;
+        if (x < g.w && y < g.h)
+            *reinterpret_cast<float2 *>(diffmap + (size_t)p * g.plane + (size_t)y * g.pitch + x) = make_float2(dmap[0], dmap[1]);
+    }
     }
     if (FINAL) {  // one partial per (pair, tile): thread order, then wave order - fixed, so the sums are reproducible
         __shared__ float s_max[NT / 64];
@@ -1123,6 +1134,25 @@ __global__ __launch_bounds__(TPB) void k_ba_score(const float *__restrict__ blk_
     }
 }
 
+// B x B cell maxima (B = 1 << lb, 2 .. 64) of the stored full-resolution diffmaps of pairs [first, first + count), packed
+// [count][ceil(h / B)][ceil(w / B)].  One thread per column of one cell row: the max down the cell's rows (a wave reads 64
+// adjacent columns of a row), then across the cell's B lanes (B <= 64: a cell never leaves its wave).  Columns at or past
+// w enter as -inf and read nothing, so the pitch padding is never read; the max of the same floats is exact.
+__global__ __launch_bounds__(256) void k_ba_block_max(const float *__restrict__ map, geom g, uint32_t first, uint32_t lb,
+                                                      uint32_t tiles_x, uint32_t bw, uint32_t bh, float *__restrict__ out)
+{
+    const uint32_t t = blockIdx.x % tiles_x, cy = (blockIdx.x / tiles_x) % bh, q = blockIdx.x / tiles_x / bh;
+    const uint32_t B = 1u << lb, x = t * 256 + threadIdx.x;
+    float m = -__builtin_inff();
+    if (x < g.w) {
+        const float *col = map + (size_t)(first + q) * g.plane + x;
+        const uint32_t y1 = min((cy + 1) << lb, g.h);
+        for (uint32_t y = cy << lb; y < y1; y++) m = fmaxf(m, col[(size_t)y * g.pitch]);
+    }
+    for (uint32_t off = 1; off < B; off <<= 1) m = fmaxf(m, __shfl_xor(m, (int)off, 64));
+    if (x < g.w && (x & (B - 1)) == 0) out[((size_t)q * bh + cy) * bw + (x >> lb)] = m;
+}
+
 // debug: div2_shared_rcp against operator/ on pseudo-random operands of the ranges Malta uses (and wider)
 __global__ __launch_bounds__(256) void k_div_sweep(uint64_t seed, uint64_t count, unsigned long long *out)
 {
@@ -1218,6 +1248,11 @@ void ce_butteraugli_free(ce_batch *b)
     hipFree(b->ba_blk_max);
     hipFree(b->ba_blk_sums);
     hipFree(b->ba_pnorm);
+    hipFree(b->ba_map);
+    hipFree(b->ba_cells);
+    b->ba_map = b->ba_cells = nullptr;
+    b->ba_cells_cap = 0;
+    b->ba_map_pairs = 0;
     b->ba_blk_max = nullptr;
     b->ba_blk_sums = nullptr;
     b->ba_pnorm = nullptr;
@@ -1240,7 +1275,7 @@ static int ba_allocate(ce_batch *b)
     const size_t slots = (size_t)b->max_refs + b->max_pairs, P = b->max_pairs, p0 = b->ba[0].plane;
     for (int l = 0; l < b->ba_levels; l++) {
         CE_HIP(ctx, hipMalloc(&b->ba_psy[l], slots * PSY * b->ba[l].plane * sizeof(float)));
-        if (l == 1) CE_HIP(ctx, hipMalloc(&b->ba_diff[l], P * b->ba[l].plane * sizeof(float)));  // the full-resolution diffmap is never stored
+        if (l == 1) CE_HIP(ctx, hipMalloc(&b->ba_diff[l], P * b->ba[l].plane * sizeof(float)));  // the full-resolution diffmap: ba_map, on request
     }
     for (auto &p : b->ba_s) CE_HIP(ctx, hipMalloc(&p, slots * 3 * p0 * sizeof(float)));
     // blurred mask input per image slot and level, the references' two mask-value planes per level (both persist like the
@@ -1280,11 +1315,20 @@ static bool ba_one_stream()  // CE_BA_LEVEL_STREAMS=1: both resolution levels on
     return v;
 }
 
-int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, uint32_t n_pairs, float intensity_target)
+int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, uint32_t n_pairs, float intensity_target,
+                          bool store_map)
 {
     ce_ctx *ctx = b->ctx;
     int rc = ba_prepare(b);
     if (rc != CE_OK) return rc;
+    // CE_FLAG_BUTTERAUGLI_DIFFMAP: the full-resolution diffmaps of all pairs, allocated by the first launch that asks for
+    // them (one allocation: there is nothing to undo if it fails) and kept until the working set is freed
+    if (store_map && !b->ba_map && hipMalloc(&b->ba_map, (size_t)b->max_pairs * b->ba[0].plane * sizeof(float)) != hipSuccess) {
+        b->ba_map = nullptr;
+        (void)hipGetLastError();
+        ctx->err = "out of device memory for the Butteraugli diffmaps";
+        return CE_ERR_BACKEND;
+    }
     const uint32_t n_slots = n_refs_used + n_pairs, mr = b->max_refs;
     // reference handle (ce_ref_*): the references' PsychoImage (both resolutions) of an earlier launch with the same
     // intensity target is still in ba_psy, so only the distorted slots go through the per-image chain
@@ -1421,15 +1465,25 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
         const bool has_sub = b->ba_levels == 2;
         const auto &ds = b->ba[has_sub ? 1 : 0];
         const geom gsub{ds.w, ds.h, ds.pitch, ds.plane};
+#define CE_MALTA_ARGS(FINAL, STORE)                                                                                                \
+    psy, b->d_pair_ref, (const float *)b->ba_mask[l], (const float *)b->ba_mask_vals[l],                                               \
+        STORE ? b->ba_map : FINAL ? (float *)nullptr : b->ba_diff[1], g, mr, mb, (const uint2 *)b->ba_work[l].d, tiles_x,             \
+        FINAL ? (const float *)b->ba_diff[1] : (const float *)nullptr, gsub, has_sub ? 1 : 0, b->ba_blk_max, b->ba_blk_sums, b->ba_blocks
 #define CE_MALTA_LAUNCH(ROWS, THREADS, FINAL)                                                                                      \
-    CE_LAUNCH_ON(ctx, st, "ba_malta_l2", (k_ba_malta_l2_xy<ROWS, THREADS, FINAL>), dim3(b->ba_work[l].len), dim3(THREADS), 0, psy, b->d_pair_ref, \
-              (const float *)b->ba_mask[l], (const float *)b->ba_mask_vals[l], FINAL ? (float *)nullptr : b->ba_diff[1], g, mr, mb,       \
-              (const uint2 *)b->ba_work[l].d, tiles_x, FINAL ? (const float *)b->ba_diff[1] : (const float *)nullptr, gsub,               \
-              has_sub ? 1 : 0, b->ba_blk_max, b->ba_blk_sums, b->ba_blocks)
+    CE_LAUNCH_ON(ctx, st, "ba_malta_l2", (k_ba_malta_l2_xy<ROWS, THREADS, FINAL, false>), dim3(b->ba_work[l].len), dim3(THREADS), 0, \
+                 CE_MALTA_ARGS(FINAL, false))
+#define CE_MALTA_MAP_LAUNCH(ROWS, THREADS)                                                                                         \
+    CE_LAUNCH_ON(ctx, st, "ba_malta_l2_map", (k_ba_malta_l2_xy<ROWS, THREADS, true, true>), dim3(b->ba_work[l].len), dim3(THREADS), \
+                 0, CE_MALTA_ARGS(true, true))
         if (l == 0) {
             final_tiles = tiles_x * tiles_y;
             if (two_streams) CE_HIP(ctx, hipStreamWaitEvent(s_main, b->ev_ba_join, 0));  // the half-resolution diffmap
-            if (malta_rows == 64)
+            if (store_map) {  // the same kernel, also writing the diffmap: a profiler name of its own
+                if (malta_rows == 64)
+                    CE_MALTA_MAP_LAUNCH(64, 512);
+                else
+                    CE_MALTA_MAP_LAUNCH(32, 256);
+            } else if (malta_rows == 64)
                 CE_MALTA_LAUNCH(64, 512, true);
             else
                 CE_MALTA_LAUNCH(32, 256, true);
@@ -1440,6 +1494,8 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
                 CE_MALTA_LAUNCH(32, 256, false);
             if (two_streams) CE_HIP(ctx, hipEventRecord(b->ev_ba_join, s_half));
         }
+#undef CE_MALTA_MAP_LAUNCH
+#undef CE_MALTA_ARGS
 #undef CE_MALTA_LAUNCH
     }
     if (b->keep_ref_pyramid && !cached) {
@@ -1451,5 +1507,43 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
     CE_LAUNCH(ctx, "ba_score", k_ba_score, dim3(n_pairs), dim3(TPB), 0, b->ba_blk_max, b->ba_blk_sums, b->d_scores, b->ba_pnorm,
               b->ba_blocks, final_tiles, (double)d0.w * (double)d0.h);
     CE_HIP(ctx, hipGetLastError());
+    return CE_OK;
+}
+
+// B x B cell maxima (B = 1: the packed map itself) of the stored diffmaps of pairs [first, first + count) into `out` (host,
+// count * ceil(h / B) * ceil(w / B) floats); the caller has checked the range and B.  Enqueued on the context's stream,
+// behind the launch that wrote the maps, and waited for.
+int ce_butteraugli_read_maps(ce_batch *b, uint32_t first, uint32_t count, uint32_t block, float *out)
+{
+    ce_ctx *ctx = b->ctx;
+    const auto &d = b->ba[0];
+    const geom g{d.w, d.h, d.pitch, d.plane};
+    if (block == 1) {  // [pair][h][pitch] rows are contiguous over the pairs: one pitched copy
+        CE_HIP(ctx, hipMemcpy2DAsync(out, (size_t)d.w * sizeof(float), b->ba_map + (size_t)first * d.plane, (size_t)d.pitch * sizeof(float),
+                                     (size_t)d.w * sizeof(float), (size_t)count * d.h, hipMemcpyDeviceToHost, ctx->stream));
+        CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return CE_OK;
+    }
+    uint32_t lb = 0;
+    while ((1u << lb) < block) lb++;
+    const uint32_t bw = (d.w + block - 1) >> lb, bh = (d.h + block - 1) >> lb, tiles_x = (d.w + 255) / 256;
+    const size_t n = (size_t)count * bw * bh;
+    if (b->ba_cells_cap < n) {
+        hipFree(b->ba_cells);
+        b->ba_cells = nullptr;
+        b->ba_cells_cap = 0;
+        CE_HIP(ctx, hipMalloc(&b->ba_cells, n * sizeof(float)));
+        b->ba_cells_cap = n;
+    }
+    const size_t blocks = (size_t)tiles_x * bh * count;
+    if (blocks > 0x7fffffffu) {
+        ctx->err = "diffmap readout too large for one launch";
+        return CE_ERR_INVALID_ARG;
+    }
+    CE_LAUNCH_ON(ctx, ctx->stream, "ba_block_max", k_ba_block_max, dim3((uint32_t)blocks), dim3(256), 0, (const float *)b->ba_map, g, first,
+                 lb, tiles_x, bw, bh, b->ba_cells);
+    CE_HIP(ctx, hipGetLastError());
+    CE_HIP(ctx, hipMemcpyAsync(out, b->ba_cells, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CE_OK;
 }

@@ -44,6 +44,26 @@ int validate_pair(ce_ctx *ctx, size_t ref_len, size_t test_len, size_t w, size_t
 
 constexpr uint32_t kKnownMetrics = CE_METRIC_DSSIM | CE_METRIC_SSIMULACRA2 | CE_METRIC_BUTTERAUGLI | CE_METRIC_PSNR;
 
+// the readouts of CE_FLAG_BUTTERAUGLI_DIFFMAP (ce_batch_butteraugli_diffmap, ce_ref_butteraugli_diffmap): checks, then the
+// device readout (butteraugli.hip)
+int read_diffmaps(ce_batch *b, uint32_t first, uint32_t count, uint32_t block, float *out, size_t out_floats)
+{
+    if (!b || !out) return CE_ERR_INVALID_ARG;
+    ce_ctx *ctx = b->ctx;
+    if (b->ba_map_pairs == 0)
+        return fail(ctx, CE_ERR_INVALID_ARG, "no Butteraugli diffmaps: the last launch did not run Butteraugli with CE_FLAG_BUTTERAUGLI_DIFFMAP");
+    if (count == 0 || first > b->ba_map_pairs || count > b->ba_map_pairs - first)
+        return fail(ctx, CE_ERR_INVALID_ARG, "diffmap pairs [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) +
+                                                 ") outside the " + std::to_string(b->ba_map_pairs) + " stored");
+    if (block == 0 || block > 64 || (block & (block - 1)) != 0)
+        return fail(ctx, CE_ERR_INVALID_ARG, "diffmap block must be 1 or a power of two up to 64");
+    const size_t want = (size_t)count * ((b->w + block - 1) / block) * ((b->h + block - 1) / block);
+    if (out_floats != want)
+        return fail(ctx, CE_ERR_INVALID_ARG, "diffmap readout needs " + std::to_string(want) + " floats, got " + std::to_string(out_floats));
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    return ce_butteraugli_read_maps(b, first, count, block, out);
+}
+
 double psnr_from_sse(unsigned long long sse, size_t w, size_t h)
 {
     // src/metrics/mod.rs:317,324-330
@@ -325,6 +345,8 @@ void ce_ctx_destroy(ce_ctx *ctx)
     prof_drain(ctx);
     for (auto &kv : ctx->shape_pool) ce_batch_destroy(kv.second);
     ctx->shape_pool.clear();
+    ce_batch_destroy(ctx->leaf_map);
+    ctx->leaf_map = nullptr;
     if (ctx->up2_stream) hipStreamSynchronize(ctx->up2_stream), hipStreamDestroy(ctx->up2_stream), hipEventDestroy(ctx->ev_up2);
     for (auto &st : ctx->aux_stream)  // after the last batch that may still drain them
         if (st) hipStreamSynchronize(st), hipStreamDestroy(st), st = nullptr;
@@ -785,6 +807,7 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
     ce_ctx *ctx = b->ctx;
     if (n_pairs == 0 || n_pairs > b->max_pairs) return fail(ctx, CE_ERR_INVALID_ARG, "n_pairs out of range");
     if (metric_mask & ~kKnownMetrics) return fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
+    b->ba_map_pairs = 0;  // whatever happens below, no readout returns the maps of an earlier launch
     CE_HIP(ctx, hipSetDevice(ctx->device));
     {
         int rc = flush_uploads(b);
@@ -830,6 +853,7 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
     const bool run_ssim2 = (metric_mask & CE_METRIC_SSIMULACRA2) && b->w >= 8 && b->h >= 8;
     const bool run_dssim = (metric_mask & CE_METRIC_DSSIM) != 0;
     const bool run_ba = (metric_mask & CE_METRIC_BUTTERAUGLI) && b->w >= 8 && b->h >= 8;
+    const bool store_maps = run_ba && (flags & CE_FLAG_BUTTERAUGLI_DIFFMAP);
     // Side by side or back to back?  Measured (profiles/r02_experiments.md sections 1, 12, 15): a SMALL batch is bound by
     // the latency of its ~130 dependent launches, and three chains side by side hide each other's gaps (one Kodak pair
     // 0.76 -> 0.54 ms, eight 1.37 -> 1.23 ms, one 4K pair 3.65 -> 2.94 ms); a LARGE grid fills the GPU from one chain,
@@ -883,7 +907,7 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
     auto launch_metric = [&](int k) -> int {
         return k == 0   ? ce_launch_ssim2(b, d_refs, n_refs_used, n_pairs)
                : k == 1 ? ce_launch_dssim(b, d_refs, n_refs_used, n_pairs)
-                        : ce_launch_butteraugli(b, d_refs, n_refs_used, n_pairs, intensity_target);
+                        : ce_launch_butteraugli(b, d_refs, n_refs_used, n_pairs, intensity_target, store_maps);
     };
     const bool runs[3] = {run_ssim2, run_dssim, run_ba};
     // launch order of the chains (0 SSIMULACRA2, 1 DSSIM, 2 Butteraugli); CE_FORK_ORDER=<permutation> for A/B runs of
@@ -969,6 +993,7 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
         if (joined & (1u << k)) CE_HIP(ctx, hipStreamWaitEvent(base, b->ev_join[k], 0));
     b->last_n_pairs = n_pairs;
     b->last_mask = metric_mask;
+    b->ba_map_pairs = store_maps ? n_pairs : 0;
     // the scores come back behind the last kernel of THIS launch and ev_run marks them: ce_batch_collect waits for the event,
     // not for the stream (round 2 copied at collect time and drained the context's stream, so collecting one batch waited
     // for every batch launched after it - in ce_eval_batch the next chunk's upload then started only when the device was idle)
@@ -1035,6 +1060,11 @@ int ce_batch_butteraugli_pnorm3(ce_batch *b, uint32_t n_pairs, double *out)
     CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
     CE_HIP(ctx, hipMemcpy(out, b->ba_pnorm, sizeof(double) * n_pairs, hipMemcpyDeviceToHost));
     return CE_OK;
+}
+
+int ce_batch_butteraugli_diffmap(ce_batch *b, uint32_t first, uint32_t count, uint32_t block, float *out, size_t out_floats)
+{
+    return read_diffmaps(b, first, count, block, out, out_floats);
 }
 
 int ce_batch_run(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_t flags, float intensity_target,
@@ -1178,6 +1208,9 @@ int ce_eval_batch_lut(ce_ctx *ctx, size_t n, const ce_pair_desc *pairs, const ce
                       uint32_t flags, float intensity_target, ce_scores *out)
 {
     if (!ctx || (!pairs && n) || (!out && n)) return CE_ERR_INVALID_ARG;
+    // the maps live in the pooled batches, which the next call reuses: they are read from a ce_batch or a ce_ref
+    if (flags & CE_FLAG_BUTTERAUGLI_DIFFMAP)
+        return fail(ctx, CE_ERR_INVALID_ARG, "CE_FLAG_BUTTERAUGLI_DIFFMAP needs a ce_batch or a ce_ref: the pooled batches keep no maps");
     // bucket by shape (Kodak mixes 768x512 and 512x768); invalid items never reach the device
     std::map<std::pair<uint32_t, uint32_t>, std::vector<size_t>> buckets;
     for (size_t i = 0; i < n; i++) {
@@ -1318,6 +1351,38 @@ int ce_calculate_butteraugli(ce_ctx *ctx, const uint8_t *reference, size_t refer
 {
     return leaf(ctx, reference, reference_len, test, test_len, width, height, CE_METRIC_BUTTERAUGLI, intensity_target,
                 out);
+}
+
+int ce_calculate_butteraugli_diffmap(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test,
+                                     size_t test_len, size_t width, size_t height, float intensity_target, double *score,
+                                     float *diffmap_out)
+{
+    if (!ctx || !reference || !test || !score || !diffmap_out) return CE_ERR_INVALID_ARG;
+    if (int rc = validate_pair(ctx, reference_len, test_len, width, height)) return rc;
+    if (width < 8 || height < 8) return fail(ctx, CE_ERR_TOO_SMALL, "minimum 8x8 for butteraugli");  // src/eval/helpers.rs:89
+    if (width > UINT32_MAX || height > UINT32_MAX) return fail(ctx, CE_ERR_INVALID_ARG, "image too large");
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    // a one-pair batch of the context, kept while the shape stays the same (not the pooled ce_eval_batch batches, which
+    // keep no maps)
+    ce_batch *b = ctx->leaf_map;
+    if (!b || b->w != width || b->h != height) {
+        ce_batch_destroy(b);
+        ctx->leaf_map = nullptr;
+        if (int rc = ce_batch_create(ctx, (uint32_t)width, (uint32_t)height, 1, 1, &ctx->leaf_map)) return rc;
+        b = ctx->leaf_map;
+    }
+    b->caller_blocks = true;  // collected before return: page-locked images are read in place (upload())
+    int rc = ce_batch_set_reference(b, 0, reference, reference_len);
+    if (rc == CE_OK) rc = ce_batch_set_test(b, 0, 0, test, test_len);
+    ce_scores s{};
+    if (rc == CE_OK) rc = ce_batch_run(b, 1, CE_METRIC_BUTTERAUGLI, CE_FLAG_BUTTERAUGLI_DIFFMAP, intensity_target, &s);
+    if (rc != CE_OK) drain_batch(b);
+    b->caller_blocks = false;
+    if (rc != CE_OK) return rc;
+    if (s.status != CE_OK) return s.status;
+    if (int r = read_diffmaps(b, 0, 1, 1, diffmap_out, width * height)) return r;
+    *score = s.butteraugli;
+    return CE_OK;
 }
 
 // leaf scratch (ce_internal.h): device buffers of at least in_bytes / out_bytes and a pinned staging buffer of the larger
@@ -1461,6 +1526,12 @@ int ce_ref_compare(ce_ref *ref, const uint8_t *test, size_t test_len, uint32_t m
     int rc = ce_ref_compare_many(ref, &test, &test_len, 1, metric_mask, intensity_target, out);
     if (rc != CE_OK) return rc;
     return out->status;
+}
+
+int ce_ref_butteraugli_diffmap(ce_ref *ref, uint32_t first, uint32_t count, uint32_t block, float *out, size_t out_floats)
+{
+    if (!ref) return CE_ERR_INVALID_ARG;
+    return read_diffmaps(ref->batch, first, count, block, out, out_floats);  // the handle's current batch (compare_many may replace it)
 }
 
 int ce_ref_stats(const ce_ref *ref, uint32_t builds[3])

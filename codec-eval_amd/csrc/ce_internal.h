@@ -84,6 +84,8 @@ struct ce_ctx {
     // ce_rgb8_to_dssim_image): device in / out and a page-locked staging buffer, kept between calls
     uint8_t *leaf_d_in = nullptr, *leaf_d_out = nullptr, *leaf_h = nullptr;
     size_t leaf_in_cap = 0, leaf_out_cap = 0, leaf_h_cap = 0;
+    // the one-pair batch of ce_calculate_butteraugli_diffmap (remade when the shape changes)
+    struct ce_batch *leaf_map = nullptr;
 
     // Auxiliary streams of the context, shared by all its batches (made on first use, destroyed with the context): the
     // three metric chains of a forked batch, SSIMULACRA2's level-0 passes (+ the chunking experiment's second one),
@@ -215,6 +217,13 @@ struct ce_batch {
     hipStream_t ba_half_stream = nullptr;
     hipEvent_t ev_ba_fork = nullptr, ev_ba_join = nullptr;
     float *ba_mask_vals[2] = {};  // [ref][2][plane_l]    maskval / dc_maskval of the references (FuzzyErosion + mask curves)
+    // CE_FLAG_BUTTERAUGLI_DIFFMAP: [pair][plane_0] full-resolution diffmaps (made on the first such launch), how many pairs
+    // of the LAST launch stored theirs (0 after a launch without the flag or without Butteraugli), and the device buffer
+    // of the block-max readouts (grow-only)
+    float *ba_map = nullptr;
+    uint32_t ba_map_pairs = 0;
+    float *ba_cells = nullptr;
+    size_t ba_cells_cap = 0;
     float *ba_blk_max = nullptr;
     double *ba_blk_sums = nullptr;
     double *ba_pnorm = nullptr;  // [pair] libjxl 3-norm of the last run
@@ -299,7 +308,9 @@ int ce_ssim2_cbrt_sweep(ce_ctx *ctx, uint32_t first_bits, uint64_t count, uint64
 int ce_launch_xyb_roundtrip(ce_ctx *ctx, const uint8_t *d_in, uint8_t *d_out, size_t n_pixels);
 int ce_launch_dssim(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, uint32_t n_pairs);
 void ce_dssim_free(ce_batch *b);
-int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, uint32_t n_pairs, float intensity_target);
+int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, uint32_t n_pairs, float intensity_target,
+                          bool store_map);
+int ce_butteraugli_read_maps(ce_batch *b, uint32_t first, uint32_t count, uint32_t block, float *out);
 void ce_butteraugli_free(ce_batch *b);
 int ce_butteraugli_div_sweep(ce_ctx *ctx, uint64_t seed, uint64_t count, uint64_t *mismatches);
 int ce_calibrate_traffic(ce_ctx *ctx, size_t bytes);

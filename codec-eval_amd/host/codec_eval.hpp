@@ -168,6 +168,20 @@ inline double calculate_butteraugli(const HipBackend &be, const Bytes &reference
 {
     return calculate_butteraugli_with_intensity(be, reference, test, width, height, CE_DEFAULT_INTENSITY_TARGET);
 }
+// ButteraugliResult{score, diffmap}, src/metrics/prelude.rs:64-65: diffmap is row-major width * height, its maximum the score
+struct ButteraugliResult {
+    double score;
+    std::vector<float> diffmap;
+};
+inline ButteraugliResult calculate_butteraugli_with_diffmap(const HipBackend &be, const Bytes &reference, const Bytes &test, size_t width,
+                                                            size_t height, float intensity_target = CE_DEFAULT_INTENSITY_TARGET)
+{
+    ButteraugliResult r{0.0, std::vector<float>(width * height)};
+    detail::check(be, ce_calculate_butteraugli_diffmap(be.ctx(), reference.data(), reference.size(), test.data(), test.size(), width, height,
+                                                       intensity_target, &r.score, r.diffmap.data()),
+                  "Butteraugli", width, height, test.size());
+    return r;
+}
 // xyb_roundtrip, src/metrics/xyb.rs:225-253 (asserts on the length, :227)
 inline Bytes xyb_roundtrip(const HipBackend &be, const Bytes &rgb, size_t width, size_t height)
 {

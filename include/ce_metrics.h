@@ -60,7 +60,14 @@ enum ce_metric {
     CE_METRIC_PSNR = 1u << 3
 };
 enum ce_flag {
-    CE_FLAG_XYB_ROUNDTRIP = 1u << 0 /* MetricConfig::xyb_roundtrip: reference side only (session.rs:447-456) */
+    CE_FLAG_XYB_ROUNDTRIP = 1u << 0, /* MetricConfig::xyb_roundtrip: reference side only (session.rs:447-456) */
+    /* ButteraugliResult.diffmap (src/metrics/prelude.rs:64-65): with CE_METRIC_BUTTERAUGLI, ce_batch_launch / ce_batch_run
+     * and the compares of a ce_ref created with it also keep every pair's full-resolution diffmap on the device (4 bytes per
+     * pixel and pair, allocated by the first such launch; not counted by ce_estimate_batch_bytes), to be read with
+     * ce_batch_butteraugli_diffmap / ce_ref_butteraugli_diffmap.  Scores are the same with and without it.
+     * ce_eval_batch, ce_eval_batch_lut and ce_eval_pair return CE_ERR_INVALID_ARG for it: their batches do not outlive the
+     * call. */
+    CE_FLAG_BUTTERAUGLI_DIFFMAP = 1u << 1
 };
 
 #define CE_DEFAULT_INTENSITY_TARGET 80.0f /* src/metrics/butteraugli.rs:94 */
@@ -116,6 +123,10 @@ int ce_calculate_dssim(ce_ctx *ctx, const uint8_t *reference, size_t reference_l
 int ce_calculate_butteraugli(ce_ctx *ctx, const uint8_t *reference, size_t reference_len,
                              const uint8_t *test, size_t test_len, size_t width, size_t height,
                              float intensity_target, double *out);
+/* ButteraugliResult{score, diffmap}: src/metrics/prelude.rs:64-65; butteraugli.rs:45,99.  diffmap_out: w*h floats */
+int ce_calculate_butteraugli_diffmap(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test,
+                                     size_t test_len, size_t width, size_t height, float intensity_target,
+                                     double *score, float *diffmap_out);
 /* xyb_roundtrip                         src/metrics/xyb.rs:225 ; out has rgb_len bytes */
 int ce_xyb_roundtrip(ce_ctx *ctx, const uint8_t *rgb, size_t rgb_len, size_t width, size_t height,
                      uint8_t *out);
@@ -212,6 +223,13 @@ int ce_batch_collect(ce_batch *b, uint32_t n_pairs, ce_scores *out);
  * that asked for CE_METRIC_BUTTERAUGLI.  The reference only ever reads `.score` (the max-norm,
  * src/metrics/butteraugli.rs:80); BASELINE.json's configs[2] also names the 3-norm. */
 int ce_batch_butteraugli_pnorm3(ce_batch *b, uint32_t n_pairs, double *out);
+/* ButteraugliResult.diffmap (src/metrics/prelude.rs:64-65) of a grid, as crates/codec-compare/src/find_outliers.rs:77-118
+ * would look for where a pair is bad: maps of pairs [first, first+count) of the last launch that had
+ * CE_FLAG_BUTTERAUGLI_DIFFMAP and Butteraugli; block = 1 (full map) or a power of two <= 64 (B x B cell maxima, edge cells
+ * clipped to the image); out_floats must be count*ceil(w/B)*ceil(h/B); out is [count][ceil(h/B)][ceil(w/B)].  Waits for
+ * that launch.  CE_ERR_INVALID_ARG for a null pointer, no stored maps, count = 0 or a range past the stored pairs, a bad
+ * block or a wrong out_floats. */
+int ce_batch_butteraugli_diffmap(ce_batch *b, uint32_t first, uint32_t count, uint32_t block, float *out, size_t out_floats);
 
 /* ---- reference handle: Ssimulacra2Reference::{new,compare} ------------------------
  * crates/codec-iter/src/eval.rs:138-149,83-89; crates/codec-compare/src/brute_force_sweep.rs:197-201,256
@@ -235,6 +253,9 @@ int ce_ref_compare_many(ce_ref *ref, const uint8_t *const *tests, const size_t *
 /* builds[k] = number of compares so far that had to (re)build the reference-side state of SSIMULACRA2 (k = 0),
  * DSSIM (1), Butteraugli (2): 1 each after any number of compares of one handle with one intensity target */
 int ce_ref_stats(const ce_ref *ref, uint32_t builds[3]);
+/* the same for a reference handle created with CE_FLAG_BUTTERAUGLI_DIFFMAP: the tests of its last compare / compare_many
+ * (src/metrics/prelude.rs:64-65 per compare of eval.rs:83-89) */
+int ce_ref_butteraugli_diffmap(ce_ref *ref, uint32_t first, uint32_t count, uint32_t block, float *out, size_t out_floats);
 void ce_ref_destroy(ce_ref *ref);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------ */
