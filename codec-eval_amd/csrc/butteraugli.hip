@@ -459,7 +459,7 @@ __device__ __forceinline__ float mask_pre_one(float uhf0, float hf0, float uhf1,
     return sqrtf(kMul * fabsf(m) + bias) - sqrt_bias;
 }
 
-template <int LEN, int EPI, bool HV, int TR = 64>
+template <int LEN, int EPI, bool HV, int TR>
 __global__ __launch_bounds__(TPB) void k_ba_blur_v_split(const float *__restrict__ tmp, const float *__restrict__ xyb,
                                                          float *__restrict__ psy, geom g, blur_kernel bk, float inv_wsum,
                                                          uint32_t n_refs_used, uint32_t max_refs, uint32_t z0,
@@ -842,8 +842,8 @@ __device__ __forceinline__ void malta_rows_xy(const ba_f2 *__restrict__ base, ba
 }
 
 // MR rows of outputs per block, NT threads (32 threads per output row pair-column, NT / 32 rows per step):
-//   <32, 256>: 72 x 40 tile (1.41x halo), 39 KB LDS, four blocks per CU
-//   <64, 512>: 72 x 72 tile (1.27x halo: 10 % fewer pre-scalings), 73 KB LDS, two blocks of eight waves per CU
+//   <32, 256> (the one launched): 72 x 40 tile (1.41x halo), 39 KB LDS, four blocks per CU.  <64, 512> - a 72 x 72 tile,
+//   10 % fewer pre-scalings, 73 KB LDS, two blocks of eight waves per CU - was slower (profiles/r02_experiments.md section 6)
 // FINAL (the full-resolution level, launched after the half-resolution one): the pixel's diffmap value takes the
 // half-resolution diffmap (AddSupersampled2x, weight 0.5) and goes straight into the score reductions - max, sum d^3, d^6,
 // d^12 per tile - instead of to memory; !FINAL (the half-resolution level) writes its diffmap.
@@ -1306,15 +1306,6 @@ static int ba_prepare(ce_batch *b)
     return CE_OK;
 }
 
-static bool ba_one_stream()  // CE_BA_LEVEL_STREAMS=1: both resolution levels on one stream whatever the batch size (A/B knob)
-{
-    static const bool v = [] {
-        const char *e = std::getenv("CE_BA_LEVEL_STREAMS");
-        return e && e[0] == '1';
-    }();
-    return v;
-}
-
 int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, uint32_t n_pairs, float intensity_target,
                           bool store_map)
 {
@@ -1354,7 +1345,7 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
     // resolution levels are independent until the full-resolution Malta kernel, so the half-resolution chain runs on a stream
     // of its own (with its own scratch planes) beside the full-resolution one: two cross-stream events instead of seven
     // launches on the critical path (profiles/r03_experiments.md section 14).
-    const bool two_streams = b->ba_levels == 2 && !ctx->prof_serial && (double)n_pairs * b->w * b->h <= 4e6 && !ba_one_stream();
+    const bool two_streams = b->ba_levels == 2 && !ctx->prof_serial && (double)n_pairs * b->w * b->h <= 4e6;
     hipStream_t s_main = CE_STREAM(ctx), s_half = s_main;
     if (two_streams) {
         if (!b->ba_half_stream) {
@@ -1396,40 +1387,22 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
                 return CE_ERR_BACKEND;
             }
             const dim3 gh3((g.w + 255) / 256, (g.h + 8 * BH_TILES - 1) / (8 * BH_TILES), nz * 3);
-            const dim3 gvs((g.w + 63) / 64, (g.h + 63) / 64, nz);
             float *sB = scr[1];
             // LF: row pass sC -> sA, column pass + split: LF -> psy, raw MF -> sB
             CE_LAUNCH_ON(ctx, st, "ba_blur_h33", k_ba_blur_h<33>, gh3, dim3(TPB), 0, (const float *)sC, sA, g, s3, s3, kLf, inv_weight_sum(kLf),
                       n_refs_used, mr, 1, z0);
-            // rows per block of the column / fused stages: 32 (default; 26 / 21 KB of LDS and ~100 / 56 registers: five blocks per CU)
-            // or 64 (CE_HV_ROWS=64: smaller halo, 45 / 38 KB, three or four blocks).  Measured (profiles/r02_experiments.md
-            // section 18): 32 rows 0.50 + 0.33 ms per step solo against 0.53 + 0.41 (MF, HF), 0.48 against 0.53 (LF); headline
-            // equal, 4K grid +3 %
-            static const int hv_rows = [] {
-                const char *e = std::getenv("CE_HV_ROWS");
-                return e && std::atoi(e) == 64 ? 64 : 32;
-            }();
-            const dim3 gvs32((g.w + 63) / 64, (g.h + 31) / 32, nz);
-            if (hv_rows == 32)
-                CE_LAUNCH_ON(ctx, st, "ba_blur_v_lf", (k_ba_blur_v_split<33, EPI_LF, false, 32>), gvs32, dim3(TPB), 0, (const float *)sA,
-                          (const float *)sC, psy, g, kLf, inv_weight_sum(kLf), n_refs_used, mr, z0, (float *)nullptr, sB);
-            else
-            CE_LAUNCH_ON(ctx, st, "ba_blur_v_lf", (k_ba_blur_v_split<33, EPI_LF, false>), gvs, dim3(TPB), 0, (const float *)sA, (const float *)sC, psy,
-                      g, kLf, inv_weight_sum(kLf), n_refs_used, mr, z0, (float *)nullptr, sB);
+            // 32 rows per block of the column / fused stages (26 / 21 KB of LDS and ~100 / 56 registers: five blocks per
+            // CU).  64 rows (smaller halo, 45 / 38 KB, three or four blocks) measured equal or slower
+            // (profiles/r02_experiments.md section 18, r03_experiments.md section 12).
+            const dim3 gvs((g.w + 63) / 64, (g.h + 31) / 32, nz);
+            CE_LAUNCH_ON(ctx, st, "ba_blur_v_lf", (k_ba_blur_v_split<33, EPI_LF, false, 32>), gvs, dim3(TPB), 0, (const float *)sA,
+                         (const float *)sC, psy, g, kLf, inv_weight_sum(kLf), n_refs_used, mr, z0, (float *)nullptr, sB);
             // MF: row + column pass of raw MF (sB) + split: MF -> psy, raw HF -> sA (its old contents are dead)
-            if (hv_rows == 32)
-                CE_LAUNCH_ON(ctx, st, "ba_blur_hv_mf", (k_ba_blur_v_split<15, EPI_MF, true, 32>), gvs32, dim3(TPB), 0, (const float *)sB,
-                          (const float *)nullptr, psy, g, kHf, inv_weight_sum(kHf), n_refs_used, mr, z0, (float *)nullptr, sA);
-            else
-            CE_LAUNCH_ON(ctx, st, "ba_blur_hv_mf", (k_ba_blur_v_split<15, EPI_MF, true>), gvs, dim3(TPB), 0, (const float *)sB, (const float *)nullptr,
-                      psy, g, kHf, inv_weight_sum(kHf), n_refs_used, mr, z0, (float *)nullptr, sA);
+            CE_LAUNCH_ON(ctx, st, "ba_blur_hv_mf", (k_ba_blur_v_split<15, EPI_MF, true, 32>), gvs, dim3(TPB), 0, (const float *)sB,
+                         (const float *)nullptr, psy, g, kHf, inv_weight_sum(kHf), n_refs_used, mr, z0, (float *)nullptr, sA);
             // HF: row + column pass of raw HF (sA) + split: HF, UHF -> psy, the mask input -> sB (raw MF is dead)
-            if (hv_rows == 32)
-                CE_LAUNCH_ON(ctx, st, "ba_blur_hv_hf", (k_ba_blur_v_split<7, EPI_HF, true, 32>), gvs32, dim3(TPB), 0, (const float *)sA,
-                          (const float *)nullptr, psy, g, kUhf, inv_weight_sum(kUhf), n_refs_used, mr, z0, sB, (float *)nullptr);
-            else
-            CE_LAUNCH_ON(ctx, st, "ba_blur_hv_hf", (k_ba_blur_v_split<7, EPI_HF, true>), gvs, dim3(TPB), 0, (const float *)sA, (const float *)nullptr,
-                      psy, g, kUhf, inv_weight_sum(kUhf), n_refs_used, mr, z0, sB, (float *)nullptr);
+            CE_LAUNCH_ON(ctx, st, "ba_blur_hv_hf", (k_ba_blur_v_split<7, EPI_HF, true, 32>), gvs, dim3(TPB), 0, (const float *)sA,
+                         (const float *)nullptr, psy, g, kUhf, inv_weight_sum(kUhf), n_refs_used, mr, z0, sB, (float *)nullptr);
         }
 
         // mask input: DiffPrecompute of HF + UHF (written by the HF split's epilogue into ba_s[1]), blurred with sigma 2.7 -
@@ -1449,19 +1422,13 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
             CE_LAUNCH_ON(ctx, st, "ba_mask_vals", k_ba_mask_vals, G(n_refs_used), dim3(TPB), 0, (const float *)b->ba_mask[l], b->ba_mask_vals[l], g);
 
         // ---- per pair: Malta + L2 terms + CombineChannelsToDiffmap -> the level's diffmap ----
-        // tile height: 64 rows / 512 threads for images that fill the chip with such tiles, else 32 rows / 256 threads
-        // (CE_MALTA_ROWS=32|64 forces one: measurement knob)
-        static const int forced_rows = [] {
-            const char *e = std::getenv("CE_MALTA_ROWS");
-            const int v = e ? std::atoi(e) : 0;
-            return v == 32 || v == 64 ? v : 0;
-        }();
-        const int malta_rows = forced_rows ? forced_rows : 32;
+        // 32-row tiles, 256 threads: the 64-row / 512-thread tile was slower (profiles/r02_experiments.md section 6,
+        // r03_experiments.md section 12)
         malta_bands mb;
         mb.p[0][0] = mUhfX; mb.p[0][1] = mHfX; mb.p[0][2] = mMfX;
         mb.p[1][0] = mUhfY; mb.p[1][1] = mHfY; mb.p[1][2] = mMfY;
-        const uint32_t tiles_x = (d.w + MT - 1) / MT, tiles_y = (d.h + (uint32_t)malta_rows - 1) / (uint32_t)malta_rows;
-        if ((rc = ce_build_xcd_list(b, n_pairs, tiles_x * tiles_y, &b->ba_work[l])) != CE_OK) return rc;
+        const uint32_t tiles_x = (d.w + MT - 1) / MT, tiles_y = (d.h + 31) / 32;
+        if ((rc = ce_build_xcd_list(b, n_pairs, ce_xcd_keys{1, tiles_x * tiles_y, 1}, &b->ba_work[l])) != CE_OK) return rc;
         const bool has_sub = b->ba_levels == 2;
         const auto &ds = b->ba[has_sub ? 1 : 0];
         const geom gsub{ds.w, ds.h, ds.pitch, ds.plane};
@@ -1469,34 +1436,19 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
     psy, b->d_pair_ref, (const float *)b->ba_mask[l], (const float *)b->ba_mask_vals[l],                                               \
         STORE ? b->ba_map : FINAL ? (float *)nullptr : b->ba_diff[1], g, mr, mb, (const uint2 *)b->ba_work[l].d, tiles_x,             \
         FINAL ? (const float *)b->ba_diff[1] : (const float *)nullptr, gsub, has_sub ? 1 : 0, b->ba_blk_max, b->ba_blk_sums, b->ba_blocks
-#define CE_MALTA_LAUNCH(ROWS, THREADS, FINAL)                                                                                      \
-    CE_LAUNCH_ON(ctx, st, "ba_malta_l2", (k_ba_malta_l2_xy<ROWS, THREADS, FINAL, false>), dim3(b->ba_work[l].len), dim3(THREADS), 0, \
-                 CE_MALTA_ARGS(FINAL, false))
-#define CE_MALTA_MAP_LAUNCH(ROWS, THREADS)                                                                                         \
-    CE_LAUNCH_ON(ctx, st, "ba_malta_l2_map", (k_ba_malta_l2_xy<ROWS, THREADS, true, true>), dim3(b->ba_work[l].len), dim3(THREADS), \
-                 0, CE_MALTA_ARGS(true, true))
+        const dim3 gmalta(b->ba_work[l].len);
         if (l == 0) {
             final_tiles = tiles_x * tiles_y;
             if (two_streams) CE_HIP(ctx, hipStreamWaitEvent(s_main, b->ev_ba_join, 0));  // the half-resolution diffmap
-            if (store_map) {  // the same kernel, also writing the diffmap: a profiler name of its own
-                if (malta_rows == 64)
-                    CE_MALTA_MAP_LAUNCH(64, 512);
-                else
-                    CE_MALTA_MAP_LAUNCH(32, 256);
-            } else if (malta_rows == 64)
-                CE_MALTA_LAUNCH(64, 512, true);
+            if (store_map)  // the same kernel, also writing the diffmap: a profiler name of its own
+                CE_LAUNCH_ON(ctx, st, "ba_malta_l2_map", (k_ba_malta_l2_xy<32, 256, true, true>), gmalta, dim3(256), 0, CE_MALTA_ARGS(true, true));
             else
-                CE_MALTA_LAUNCH(32, 256, true);
+                CE_LAUNCH_ON(ctx, st, "ba_malta_l2", (k_ba_malta_l2_xy<32, 256, true, false>), gmalta, dim3(256), 0, CE_MALTA_ARGS(true, false));
         } else {
-            if (malta_rows == 64)
-                CE_MALTA_LAUNCH(64, 512, false);
-            else
-                CE_MALTA_LAUNCH(32, 256, false);
+            CE_LAUNCH_ON(ctx, st, "ba_malta_l2", (k_ba_malta_l2_xy<32, 256, false, false>), gmalta, dim3(256), 0, CE_MALTA_ARGS(false, false));
             if (two_streams) CE_HIP(ctx, hipEventRecord(b->ev_ba_join, s_half));
         }
-#undef CE_MALTA_MAP_LAUNCH
 #undef CE_MALTA_ARGS
-#undef CE_MALTA_LAUNCH
     }
     if (b->keep_ref_pyramid && !cached) {
         b->ba_ref_src = d_refs;

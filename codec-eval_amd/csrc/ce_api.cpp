@@ -3,7 +3,6 @@
 // kinds, profiling hooks.  All device work is in the .hip files; there is no CPU compute
 // path here — if HIP is unavailable every entry point fails with CE_ERR_BACKEND.
 #include <algorithm>
-#include <array>
 #include <atomic>
 #include <condition_variable>
 #include <functional>
@@ -123,41 +122,14 @@ static void prof_drain(ce_ctx *ctx)
     ctx->pend.clear();
 }
 
-// XCD-aware launch order for kernels whose workgroup = (tile, pair).  Workgroups reach the 8 XCDs round-robin by launch
-// id and every XCD has its own L2, so the workgroups that read the same tile of one REFERENCE for its different
-// distorted images should carry ids that are congruent mod 8 and adjacent: the reference's planes are then fetched into
-// one XCD's L2 once and hit there by the reference's other pairs (the scheme of the SSIMULACRA2 passes, ssim2.hip).
-// Keys (reference, tile) are dealt to the 8 classes in turn, each key followed by all pairs of its reference;
-// entry id = slot * 8 + class; classes are padded with (~0, 0) entries (the kernel returns at once).  Rebuilt only when
-// the pair -> reference table, the pair count or the tile count changes.
-int ce_build_xcd_list(ce_batch *b, uint32_t n_pairs, uint32_t n_tiles, ce_xcd_list *L)
+// The XCD-aware work list (ce_plan.h: ce_plan_xcd_list) of batch b's first n_pairs pairs, on the device.  Rebuilt only
+// when one of its inputs changes: the pair -> reference table, the pair count or the keys.
+int ce_build_xcd_list(ce_batch *b, uint32_t n_pairs, const ce_xcd_keys &keys, ce_xcd_list *L)
 {
-    if (L->d && L->version == b->pair_ref_version && L->pairs == n_pairs && L->tiles == n_tiles) return CE_OK;
+    static_assert(sizeof(ce_plan_entry) == sizeof(uint2) && alignof(ce_plan_entry) <= alignof(uint2), "entries are read as uint2");
+    if (L->d && L->version == b->pair_ref_version && L->pairs == n_pairs && L->keys == keys) return CE_OK;
     ce_ctx *ctx = b->ctx;
-    std::vector<std::vector<uint32_t>> pairs_of(b->max_refs);
-    for (uint32_t p = 0; p < n_pairs; p++) pairs_of[b->h_pair_ref[p]].push_back(p);
-    static const bool natural = [] {  // CE_XCD_ORDER=0: pair-major, tile-minor (what a 3-D grid would do) - A/B knob
-        const char *e = std::getenv("CE_XCD_ORDER");
-        return e && std::atoi(e) == 0;
-    }();
-    std::vector<uint2> flat;
-    if (natural) {
-        for (uint32_t p = 0; p < n_pairs; p++)
-            for (uint32_t t = 0; t < n_tiles; t++) flat.push_back(make_uint2(t, p));
-    } else {
-        std::vector<uint2> cls[8];
-        uint32_t k = 0;
-        for (uint32_t r = 0; r < b->max_refs; r++) {
-            if (pairs_of[r].empty()) continue;
-            for (uint32_t t = 0; t < n_tiles; t++, k++)
-                for (uint32_t p : pairs_of[r]) cls[k & 7].push_back(make_uint2(t, p));
-        }
-        size_t longest = 0;
-        for (auto &v : cls) longest = std::max(longest, v.size());
-        flat.assign(longest * 8, make_uint2(~0u, 0u));
-        for (uint32_t x = 0; x < 8; x++)
-            for (size_t sl = 0; sl < cls[x].size(); sl++) flat[sl * 8 + x] = cls[x][sl];
-    }
+    const std::vector<ce_plan_entry> flat = ce_plan_xcd_list(b->h_pair_ref.data(), n_pairs, b->max_refs, keys);
     if (flat.size() > L->cap) {
         if (L->d) CE_HIP(ctx, hipFree(L->d));
         L->d = nullptr;
@@ -169,7 +141,7 @@ int ce_build_xcd_list(ce_batch *b, uint32_t n_pairs, uint32_t n_tiles, ce_xcd_li
     L->len = (uint32_t)flat.size();
     L->version = b->pair_ref_version;
     L->pairs = n_pairs;
-    L->tiles = n_tiles;
+    L->keys = keys;
     return CE_OK;
 }
 
@@ -467,10 +439,6 @@ void ce_batch_destroy(ce_batch *b)
         if (b->ev_join[l]) hipEventDestroy(b->ev_join[l]);
     }
     ce_ssim2_free(b);
-    hipFree(b->d_work_h);
-    hipFree(b->d_work_v);
-    hipFree(b->d_work_ht);
-    hipFree(b->d_work_vt);
     ce_dssim_free(b);
     ce_butteraugli_free(b);
     delete b;
@@ -909,18 +877,8 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
                : k == 1 ? ce_launch_dssim(b, d_refs, n_refs_used, n_pairs)
                         : ce_launch_butteraugli(b, d_refs, n_refs_used, n_pairs, intensity_target, store_maps);
     };
+    // the chains are enqueued in this order: SSIMULACRA2 first is the fastest start (profiles/r02_experiments.md section 19)
     const bool runs[3] = {run_ssim2, run_dssim, run_ba};
-    // launch order of the chains (0 SSIMULACRA2, 1 DSSIM, 2 Butteraugli); CE_FORK_ORDER=<permutation> for A/B runs of
-    // the forked schedule (profiles/r02_experiments.md section 19)
-    static const std::array<int, 3> fork_order = [] {
-        std::array<int, 3> o{0, 1, 2};
-        const char *e = std::getenv("CE_FORK_ORDER");
-        if (e && std::strlen(e) == 3) {
-            std::array<int, 3> t{e[0] - '0', e[1] - '0', e[2] - '0'};
-            if ((1 << t[0] | 1 << t[1] | 1 << t[2]) == 7 && t[0] >= 0 && t[1] >= 0 && t[2] >= 0) o = t;
-        }
-        return o;
-    }();
     // A forked SMALL batch is bound by the host: the ~50 launches of the three chains take ~0.2 ms to enqueue one after
     // the other, and a chain cannot start before its first launch is enqueued.  So the chains of a fully forked batch are
     // enqueued by one host thread each (the caller's + two helpers; CE_STREAM makes a launch function enqueue on its
@@ -931,11 +889,11 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
         int rcs[3] = {CE_OK, CE_OK, CE_OK};
         std::string errs[3];
         int last = -1;
-        for (int i = 0; i < 3; i++)
-            if (runs[fork_order[i]]) {
-                int rc = prepare_fork(fork_order[i]);
+        for (int k = 0; k < 3; k++)
+            if (runs[k]) {
+                int rc = prepare_fork(k);
                 if (rc != CE_OK) return rc;
-                last = fork_order[i];
+                last = k;
             }
         auto body = [&](int k) {
             ce_tls_stream = b->metric_stream[k];
@@ -951,15 +909,14 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
             }
         }
         int used = 0;
-        for (int i = 0; i < 3; i++) {
-            const int k = fork_order[i];
+        for (int k = 0; k < 3; k++) {
             if (!runs[k] || k == last) continue;
             if (ctx->helpers && used < 2)
                 ctx->helpers->submit(used++, [&body, k] { body(k); });
             else
                 body(k);
         }
-        body(last);  // the caller's thread takes the chain that is enqueued last in the single-threaded order
+        body(last);  // the caller's thread takes the last chain that runs
         for (int i = 0; i < used; i++) ctx->helpers->wait(i);
         for (int k = 0; k < 3; k++) {
             if (!runs[k]) continue;
@@ -967,8 +924,7 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
             joined |= 1u << k;
         }
     } else {
-        for (int i = 0; i < 3; i++) {
-            const int k = fork_mask == 7u ? fork_order[i] : i;
+        for (int k = 0; k < 3; k++) {
             if (!runs[k]) continue;
             if (!(fork_mask & (1u << k))) {
                 int rc = launch_metric(k);

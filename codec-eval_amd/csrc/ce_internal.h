@@ -88,12 +88,11 @@ struct ce_ctx {
     struct ce_batch *leaf_map = nullptr;
 
     // Auxiliary streams of the context, shared by all its batches (made on first use, destroyed with the context): the
-    // three metric chains of a forked batch, SSIMULACRA2's level-0 passes (+ the chunking experiment's second one),
-    // Butteraugli's half-resolution chain.  Rounds 1-2 made them per BATCH: a context with a scratch batch and a reference
-    // handle then held 13 streams, HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues in creation order, and two
+    // three metric chains of a forked batch, SSIMULACRA2's level-0 passes, Butteraugli's half-resolution chain.  Rounds
+    // 1-2 made them per BATCH: a context with a scratch batch and a reference handle then held 13 streams, HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues in creation order, and two
     // chains of one call could land on one queue - the same call took 0.45 or 0.8 ms depending on what had been created
     // before it (profiles/r03_experiments.md section 15).
-    enum { AUX_METRIC0 = 0, AUX_SSIM2_L0 = 3, AUX_SSIM2_L0B = 4, AUX_BA_HALF = 5, AUX_COUNT = 6 };
+    enum { AUX_METRIC0 = 0, AUX_SSIM2_L0 = 3, AUX_BA_HALF = 4, AUX_COUNT = 5 };
     hipStream_t aux_stream[AUX_COUNT] = {};
     hipStream_t up2_stream = nullptr;  // second DMA stream of ce_eval_batch's page-locked uploads (CE_UPLOAD_STREAMS=2)
     hipEvent_t ev_up2 = nullptr;
@@ -103,17 +102,12 @@ struct ce_ctx {
     struct ce_fork_helpers *helpers = nullptr;
 };
 
-// XCD-aware 1-D launch order for per-pair tile kernels (ce_build_xcd_list, ce_api.cpp): entry = (tile, pair)
+// XCD-aware 1-D launch order of a per-pair tile kernel on the device (ce_plan.h, ce_build_xcd_list in ce_api.cpp):
+// entry = (tile, pair), with the inputs it was built from
 struct ce_xcd_list {
     uint2 *d = nullptr;
-    uint32_t len = 0, cap = 0, version = ~0u, pairs = 0, tiles = 0;
-};
-
-// launch order of the streaming per-pair kernels (dssim.hip): one entry per BLOCK = a strip tile and the (up to four)
-// distorted images of one reference that its waves walk side by side
-struct ce_group_list {
-    void *d = nullptr;
-    uint32_t len = 0, cap = 0, version = ~0u, pairs = 0, strips = 0, rows = 0, h = 0;
+    uint32_t len = 0, cap = 0, version = ~0u, pairs = 0;
+    ce_xcd_keys keys{};
 };
 
 struct ce_batch {
@@ -169,13 +163,9 @@ struct ce_batch {
     ce_dev_scores *d_scores = nullptr;
     ce_dev_scores *h_scores = nullptr;  // pinned
     bool ssim2_ready = false;
-    // XCD-aware work lists of the level-0 row / column pass (ssim2.hip): launch id -> (block, channel, pair)
-    uint2 *d_work_h = nullptr, *d_work_v = nullptr;    // level 0
-    uint2 *d_work_ht = nullptr, *d_work_vt = nullptr;  // the merged launch of levels 1..
-    uint32_t work_len_h = 0, work_len_v = 0, work_cap_h = 0, work_cap_v = 0, work_version = ~0u, work_pairs = 0;
-    uint32_t work_len_ht = 0, work_len_vt = 0, work_cap_ht = 0, work_cap_vt = 0, work_version_t = ~0u, work_pairs_t = 0;
-    uint32_t work_blk_ht = 0, work_blk_vt = 0;
-    std::vector<uint2> work_chunks_h, work_chunks_v;  // (offset, length) segments of the level-0 lists (CE_SSIM2_L0_CHUNK experiment)
+    // XCD-aware work lists of the row / column pass (ssim2.hip): launch id -> (block, channel, pair)
+    ce_xcd_list work_h, work_v;    // level 0
+    ce_xcd_list work_ht, work_vt;  // the merged launch of levels 1..
     // reference handles (ce_ref_*): the references' XYB pyramid of the last SSIMULACRA2 run stays valid
     // until a reference is replaced, so later compares only build the distorted side
     bool keep_ref_pyramid = false;
@@ -200,7 +190,7 @@ struct ce_batch {
     double *ds_part = nullptr; // [pairs][levels][2][blocks] partial sums (sum, abs-dev)
     double *ds_level_scores = nullptr;  // [pairs][levels]
     uint32_t ds_blocks = 0;
-    ce_group_list ds_gwork[CE_DSSIM_SCALES];  // k_dssim_compare_stream's launch order, per level
+    ce_xcd_list ds_gwork[CE_DSSIM_SCALES];  // k_dssim_compare_stream's launch order, per level
     bool dssim_ready = false;
 
     // Butteraugli working set (butteraugli.hip): level 0 = full resolution, 1 = 2x-subsampled
@@ -314,7 +304,7 @@ int ce_butteraugli_read_maps(ce_batch *b, uint32_t first, uint32_t count, uint32
 void ce_butteraugli_free(ce_batch *b);
 int ce_butteraugli_div_sweep(ce_ctx *ctx, uint64_t seed, uint64_t count, uint64_t *mismatches);
 int ce_calibrate_traffic(ce_ctx *ctx, size_t bytes);
-int ce_build_xcd_list(ce_batch *b, uint32_t n_pairs, uint32_t n_tiles, ce_xcd_list *list);
+int ce_build_xcd_list(ce_batch *b, uint32_t n_pairs, const ce_xcd_keys &keys, ce_xcd_list *list);
 void ce_free_xcd_list(ce_xcd_list *list);
 int ce_launch_rgb8_to_dssim_image(ce_ctx *ctx, const uint8_t *d_rgb, float *d_rgba, size_t n_pixels);
 

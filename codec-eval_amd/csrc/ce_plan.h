@@ -1,5 +1,6 @@
-// How ce_eval_batch cuts a shape bucket into chunks: plain C++ without device calls, checked on the host by
-// tests/cpp/test_eval_plan.cpp.  The executor (ce_api.cpp) reads the inputs from its context and runs the chunks in order.
+// Host-side launch planning, plain C++ without device calls, checked on the host by tests/cpp/test_eval_plan.cpp: how
+// ce_eval_batch cuts a shape bucket into chunks, and the XCD-aware work lists of the per-pair tile kernels.  The callers
+// (ce_api.cpp and the metrics' launch functions) read the inputs from their context and put the result on the device.
 #pragma once
 
 #include <algorithm>
@@ -68,4 +69,50 @@ inline void ce_plan_bucket(const std::vector<size_t> &items, const std::vector<c
             if (plan[p].slot == c.slot) c.collect_first = p;  // the latest one; the earlier ones it collected itself
         plan.push_back(std::move(c));
     }
+}
+
+// XCD-aware 1-D launch order for per-pair tile kernels.  Workgroups reach the 8 XCDs round-robin by launch id and every
+// XCD has its own L2, so the workgroups that read the same part of one REFERENCE for its different distorted images
+// should carry ids that are congruent mod 8 and adjacent: the reference's data is then fetched into one XCD's L2 once and
+// hit there by the reference's other pairs.  The keys of each reference that has pairs are dealt to the 8 classes in
+// turn; a key is followed by its tiles and each tile by all pairs of its reference.  Entry id = slot * 8 + class; every
+// class is padded to one length, a multiple of round_to, with (~0u, 0) entries (the kernel returns at once).
+struct ce_plan_entry {  // (tile, pair): the layout of HIP's uint2, which the kernels read
+    uint32_t tile, pair;
+};
+
+struct ce_xcd_keys {
+    uint32_t channels;          // a reference has channels * keys_per_channel keys, channel-major
+    uint32_t keys_per_channel;
+    uint32_t tiles_per_key;     // key j of channel c covers the tiles (j * tiles_per_key + sub) | c << 16
+    uint32_t round_to = 1;      // a block takes round_to consecutive entries of one class
+};
+
+inline bool operator==(const ce_xcd_keys &a, const ce_xcd_keys &b)
+{
+    return a.channels == b.channels && a.keys_per_channel == b.keys_per_channel && a.tiles_per_key == b.tiles_per_key &&
+           a.round_to == b.round_to;
+}
+
+// The list of pairs [0, n_pairs); pair_ref[p] < n_refs is the reference of pair p.
+inline std::vector<ce_plan_entry> ce_plan_xcd_list(const uint32_t *pair_ref, uint32_t n_pairs, uint32_t n_refs, const ce_xcd_keys &k)
+{
+    std::vector<std::vector<uint32_t>> pairs_of(n_refs);
+    for (uint32_t p = 0; p < n_pairs; p++) pairs_of[pair_ref[p]].push_back(p);
+    std::vector<ce_plan_entry> cls[8];
+    uint32_t key = 0;
+    for (const auto &pairs : pairs_of) {
+        if (pairs.empty()) continue;
+        for (uint32_t c = 0; c < k.channels; c++)
+            for (uint32_t j = 0; j < k.keys_per_channel; j++, key++)
+                for (uint32_t sub = 0; sub < k.tiles_per_key; sub++)
+                    for (uint32_t p : pairs) cls[key & 7].push_back({(j * k.tiles_per_key + sub) | c << 16, p});
+    }
+    size_t len = 0;
+    for (const auto &v : cls) len = std::max(len, v.size());
+    len = (len + k.round_to - 1) / k.round_to * k.round_to;
+    std::vector<ce_plan_entry> list(len * 8, ce_plan_entry{~0u, 0u});
+    for (uint32_t x = 0; x < 8; x++)
+        for (size_t i = 0; i < cls[x].size(); i++) list[i * 8 + x] = cls[x][i];
+    return list;
 }

@@ -151,8 +151,7 @@ void ce_dssim_free(ce_batch *b)
     for (int l = 0; l < CE_DSSIM_SCALES; l++) {
         hipFree(b->ds_rimg[l]); hipFree(b->ds_rmu[l]); hipFree(b->ds_rsq[l]);
         b->ds_rimg[l] = b->ds_rmu[l] = b->ds_rsq[l] = nullptr;
-        hipFree(b->ds_gwork[l].d);
-        b->ds_gwork[l] = ce_group_list{};
+        ce_free_xcd_list(&b->ds_gwork[l]);
     }
     b->ds_ref_src = nullptr;
     hipFree(b->ds_part); hipFree(b->ds_level_scores);

@@ -401,50 +401,6 @@ __global__ __launch_bounds__(CS_WAVES * 64) void k_dssim_create_stream(const uin
     }
 }
 
-// Launch order of k_dssim_compare_stream: entries (strip tile, pair); a block's CS_WAVES waves take consecutive entries of
-// one XCD class.  Workgroups reach the 8 XCDs round-robin by launch id; all entries of one (reference, row block) - its
-// strips, and on each strip the reference's distorted images one after the other - go to ONE class, so that the
-// 128-byte lines two neighbouring strips share (a strip starts two columns left of a multiple of 60) and the reference's
-// lines are fetched into one L2 (and mostly by one CU) while they are in use.
-int build_stream_list(ce_batch *b, uint32_t n_pairs, uint32_t strips, uint32_t rows, uint32_t h, ce_group_list *L)
-{
-    if (L->d && L->version == b->pair_ref_version && L->pairs == n_pairs && L->strips == strips && L->rows == rows && L->h == h)
-        return CE_OK;
-    ce_ctx *ctx = b->ctx;
-    std::vector<std::vector<uint32_t>> pairs_of(b->max_refs);
-    for (uint32_t p = 0; p < n_pairs; p++) pairs_of[b->h_pair_ref[p]].push_back(p);
-    const uint32_t row_blocks = (h + rows - 1) / rows;
-    std::vector<uint2> cls[8];
-    uint32_t k = 0;
-    for (uint32_t r = 0; r < b->max_refs; r++) {
-        if (pairs_of[r].empty()) continue;
-        for (uint32_t rb = 0; rb < row_blocks; rb++, k++)
-            for (uint32_t s = 0; s < strips; s++)
-                for (uint32_t p : pairs_of[r]) cls[k & 7].push_back(make_uint2(rb * strips + s, p));
-    }
-    size_t longest = 0;
-    for (auto &v : cls) longest = std::max(longest, v.size());
-    longest = (longest + CS_WAVES - 1) / CS_WAVES * CS_WAVES;
-    std::vector<uint2> flat(longest * 8, make_uint2(~0u, 0u));
-    for (uint32_t x = 0; x < 8; x++)
-        for (size_t sl = 0; sl < cls[x].size(); sl++) flat[sl * 8 + x] = cls[x][sl];
-    if (flat.size() > L->cap) {
-        if (L->d) CE_HIP(ctx, hipFree(L->d));
-        L->d = nullptr;
-        L->cap = 0;
-        CE_HIP(ctx, hipMalloc(&L->d, flat.size() * sizeof(uint2)));
-        L->cap = (uint32_t)flat.size();
-    }
-    if (int rc = ce_upload_table(b, L->d, flat.data(), flat.size() * sizeof(uint2))) return rc;  // `flat` is pageable and goes out of scope
-    L->len = (uint32_t)flat.size();
-    L->version = b->pair_ref_version;
-    L->pairs = n_pairs;
-    L->strips = strips;
-    L->rows = rows;
-    L->h = h;
-    return CE_OK;
-}
-
 // rows a wave of the streaming kernels walks: as many as still leave every SIMD a few waves (a wave re-reads 4 rows of halo)
 uint32_t stream_rows(uint32_t strips, uint32_t h, uint32_t n_images)
 {
@@ -491,7 +447,12 @@ int ce_dssim_compare_stream(ce_batch *b, int l, uint32_t n_pairs, float *level_m
     const auto &d = b->ds[l];
     const lvl_geom lg{d.w, d.h, d.pitch, d.plane};
     const uint32_t strips = (d.w + CS_OUT - 1) / CS_OUT, rows = stream_rows(strips, d.h, n_pairs);
-    const int rc = build_stream_list(b, n_pairs, strips, rows, d.h, &b->ds_gwork[l]);
+    // Launch order (ce_plan.h: ce_plan_xcd_list): one key per row block, entries (row block * strips + strip, pair).  A
+    // block's CS_WAVES waves take consecutive entries of one XCD class, and all entries of one (reference, row block) - its
+    // strips, and on each strip the reference's distorted images one after the other - go to ONE class, so that the
+    // 128-byte lines two neighbouring strips share (a strip starts two columns left of a multiple of 60) and the
+    // reference's lines are fetched into one L2 (and mostly by one CU) while they are in use.
+    const int rc = ce_build_xcd_list(b, n_pairs, ce_xcd_keys{1, (d.h + rows - 1) / rows, strips, CS_WAVES}, &b->ds_gwork[l]);
     if (rc != CE_OK) return rc;
     CE_LAUNCH(ctx, "dssim_compare", k_dssim_compare_stream, dim3(b->ds_gwork[l].len / CS_WAVES), dim3(CS_WAVES * 64), 0,
               (const float *)b->ds_img, (const float *)b->ds_rimg[l], (const float *)b->ds_rmu[l], (const float *)b->ds_rsq[l],

@@ -1,7 +1,12 @@
-// The chunk plan of ce_eval_batch (codec-eval_amd/csrc/ce_plan.h) on hand-derived cases: budget cap with ring reuse, the
-// first-chunk ramp, two buckets, a split reference, the pooled-batch hint.  No device.
+// The host-side launch plans of codec-eval_amd/csrc/ce_plan.h on hand-derived cases.  No device.
+// - The chunk plan of ce_eval_batch: budget cap with ring reuse, the first-chunk ramp, two buckets, a split reference, the
+//   pooled-batch hint.
+// - The XCD-aware work lists: one list per tile encoding (Butteraugli's Malta tiles, SSIMULACRA2's channel blocks, DSSIM's
+//   strips with a rounded class length), and properties over a sweep of bindings.
 #include <cstdint>
 #include <cstdio>
+#include <set>
+#include <utility>
 #include <vector>
 
 #include "ce_plan.h"
@@ -60,8 +65,120 @@ static void check_chunks(const std::vector<ce_plan_chunk> &plan, size_t first, c
     }
 }
 
+static const ce_plan_entry kPad{~0u, 0u};
+
+static bool operator==(const ce_plan_entry &a, const ce_plan_entry &b) { return a.tile == b.tile && a.pair == b.pair; }
+
+static void check_list(const std::vector<ce_plan_entry> &got, const std::vector<ce_plan_entry> &want)
+{
+    CHECK(got.size() == want.size());
+    for (size_t i = 0; i < got.size() && i < want.size(); i++)
+        if (!(got[i] == want[i])) {
+            std::printf("entry %zu: (%x, %u), want (%x, %u)\n", i, got[i].tile, got[i].pair, want[i].tile, want[i].pair);
+            g_fail++;
+        }
+}
+
+// the list whose class x holds cls[x] (entry id = slot * 8 + class), padded to `len` slots
+static std::vector<ce_plan_entry> from_classes(const std::vector<std::vector<ce_plan_entry>> &cls, size_t len)
+{
+    std::vector<ce_plan_entry> v(len * 8, kPad);
+    for (size_t x = 0; x < cls.size(); x++)
+        for (size_t i = 0; i < cls[x].size(); i++) v[i * 8 + x] = cls[x][i];
+    return v;
+}
+
+// Properties of any list: every (tile, pair) of a pair below n_pairs appears exactly once; all other entries are padding;
+// key i of the bound references (in reference order) sits in class i % 8; the length is 8 x round_to x k, with no padding
+// group of round_to slots at the end.
+static void check_list_properties(const std::vector<uint32_t> &pair_ref, uint32_t n_pairs, uint32_t n_refs, const ce_xcd_keys &k)
+{
+    const std::vector<ce_plan_entry> list = ce_plan_xcd_list(pair_ref.data(), n_pairs, n_refs, k);
+    std::vector<uint32_t> first_key(n_refs, ~0u);  // global index of each bound reference's first key
+    uint32_t keys = 0;
+    for (uint32_t r = 0; r < n_refs; r++)
+        for (uint32_t p = 0; p < n_pairs; p++)
+            if (pair_ref[p] == r) {
+                first_key[r] = keys;
+                keys += k.channels * k.keys_per_channel;
+                break;
+            }
+    std::set<std::pair<uint32_t, uint32_t>> want, seen;
+    for (uint32_t p = 0; p < n_pairs; p++)
+        for (uint32_t c = 0; c < k.channels; c++)
+            for (uint32_t t = 0; t < k.keys_per_channel * k.tiles_per_key; t++) want.insert({t | c << 16, p});
+    size_t last_used = 0;
+    for (size_t i = 0; i < list.size(); i++) {
+        const ce_plan_entry e = list[i];
+        if (e == kPad) continue;
+        last_used = i / 8 + 1;
+        CHECK(e.pair < n_pairs);
+        if (e.pair >= n_pairs) continue;
+        CHECK(seen.insert({e.tile, e.pair}).second);
+        const uint32_t c = e.tile >> 16, j = (e.tile & 0xffffu) / k.tiles_per_key;
+        CHECK(first_key[pair_ref[e.pair]] != ~0u);
+        CHECK((first_key[pair_ref[e.pair]] + c * k.keys_per_channel + j) % 8 == i % 8);
+    }
+    CHECK(seen == want);
+    CHECK(list.size() % (8 * k.round_to) == 0);
+    CHECK(list.size() / 8 - last_used < k.round_to);
+}
+
+static void xcd_lists()
+{
+    {  // the worked example: references 0 (pairs 0, 2) and 1 (pair 1), three keys each, one tile per key
+        const std::vector<uint32_t> pair_ref{0, 1, 0};
+        check_list(ce_plan_xcd_list(pair_ref.data(), 3, 2, ce_xcd_keys{1, 3, 1}),
+                   {{0, 0}, {1, 0}, {2, 0}, {0, 1}, {1, 1}, {2, 1}, kPad, kPad,  //
+                    {0, 2}, {1, 2}, {2, 2}, kPad, kPad, kPad, kPad, kPad});
+    }
+    {  // SSIMULACRA2 (3 channels x 2 blocks, entry block | channel << 16): pairs bound out of order (reference 2 holds
+       // pairs 0 and 2, reference 0 pair 1), reference 1 unbound, pair 3 past n_pairs.  Reference 0's six keys take
+       // classes 0-5, reference 2's classes 6, 7, 0, 1, 2, 3.
+        const std::vector<uint32_t> pair_ref{2, 0, 2, 1};
+        const uint32_t C1 = 1u << 16, C2 = 2u << 16;
+        check_list(ce_plan_xcd_list(pair_ref.data(), 3, 3, ce_xcd_keys{3, 2, 1}),
+                   from_classes({{{0, 1}, {C1, 0}, {C1, 2}},
+                                 {{1, 1}, {C1 | 1, 0}, {C1 | 1, 2}},
+                                 {{C1, 1}, {C2, 0}, {C2, 2}},
+                                 {{C1 | 1, 1}, {C2 | 1, 0}, {C2 | 1, 2}},
+                                 {{C2, 1}},
+                                 {{C2 | 1, 1}},
+                                 {{0, 0}, {0, 2}},
+                                 {{1, 0}, {1, 2}}},
+                                3));
+    }
+    {  // DSSIM (one key per row block covering its 3 strips, entry row block * 3 + strip; classes rounded to 4 slots):
+       // one reference with pairs 0 and 1, two row blocks
+        const std::vector<uint32_t> pair_ref{0, 0};
+        check_list(ce_plan_xcd_list(pair_ref.data(), 2, 1, ce_xcd_keys{1, 2, 3, 4}),
+                   from_classes({{{0, 0}, {0, 1}, {1, 0}, {1, 1}, {2, 0}, {2, 1}},  //
+                                 {{3, 0}, {3, 1}, {4, 0}, {4, 1}, {5, 0}, {5, 1}}},
+                                8));
+    }
+    {  // no pair: an empty list
+        const std::vector<uint32_t> pair_ref{0};
+        CHECK(ce_plan_xcd_list(pair_ref.data(), 0, 1, ce_xcd_keys{3, 5, 1}).empty());
+    }
+    // properties over a sweep: up to 20 references (some unbound), pairs bound in a scrambled order, n_pairs below the
+    // table's length, key counts that are and are not multiples of 8, round_to 1 and 4
+    uint32_t seed = 1;
+    auto next = [&seed](uint32_t n) {
+        seed = seed * 1664525u + 1013904223u;
+        return (seed >> 8) % n;
+    };
+    for (int it = 0; it < 300; it++) {
+        const uint32_t n_refs = 1 + next(20), max_pairs = 1 + next(40), n_pairs = next(max_pairs + 1);
+        std::vector<uint32_t> pair_ref(max_pairs);
+        for (auto &r : pair_ref) r = next(n_refs) & ~1u;  // odd references stay unbound
+        const ce_xcd_keys k{1 + next(3), 1 + next(24), 1 + next(5), next(2) ? 4u : 1u};
+        check_list_properties(pair_ref, n_pairs, n_refs, k);
+    }
+}
+
 int main()
 {
+    xcd_lists();
     {  // 12 refs x 4 tests, cap 8 pairs, ramp 64: six chunks of two whole references on slots 0,1,2,0,1,2
         bucket b(12, 4);
         std::vector<ce_plan_chunk> plan;

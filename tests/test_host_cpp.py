@@ -34,8 +34,8 @@ def test_host_mirror_on_gpu(ce, tmp_path):
 
 
 def test_eval_batch_chunk_plan(tmp_path):
-    """ce_eval_batch's chunk planner (codec-eval_amd/csrc/ce_plan.h: plain C++) against plans derived by hand from the
-    rules it implements (tests/cpp/test_eval_plan.cpp)."""
+    """The host-side launch plans (codec-eval_amd/csrc/ce_plan.h: plain C++) - ce_eval_batch's chunks and the XCD-aware
+    work lists - against plans derived by hand from the rules they implement (tests/cpp/test_eval_plan.cpp)."""
     exe = str(tmp_path / "test_eval_plan")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "codec-eval_amd", "csrc"),
                            os.path.join(ROOT, "tests", "cpp", "test_eval_plan.cpp"), "-o", exe])
