@@ -153,6 +153,42 @@ impl HipMetrics {
         self.check(rc, width as u32, height as u32, test.len())?;
         Ok((score, diffmap))
     }
+
+    /// `calculate_dssim` with the maps kept, the shape of dssim-core's `Dssim::compare` (`(Val, Vec<SsimMap>)`, which
+    /// src/metrics/dssim.rs:68 drops): the score and one `SsimMap` per scale, level 0 at full resolution.
+    pub fn calculate_dssim_with_ssim_maps(&mut self, reference: &[u8], test: &[u8], width: usize, height: usize)
+                                          -> Result<(f64, Vec<SsimMap>), HipError> {
+        let (mut n, mut lw, mut lh) = (0u32, [0u32; sys::CE_DSSIM_MAX_LEVELS], [0u32; sys::CE_DSSIM_MAX_LEVELS]);
+        if width > 0 && height > 0 && width <= u32::MAX as usize && height <= u32::MAX as usize {
+            unsafe { sys::ce_dssim_levels(width as u32, height as u32, &mut n, lw.as_mut_ptr(), lh.as_mut_ptr()) };
+        }
+        let sizes: Vec<(usize, usize)> = (0..n as usize).map(|l| (lw[l] as usize, lh[l] as usize)).collect();
+        let mut maps = vec![0.0f32; sizes.iter().map(|(w, h)| w * h).sum()];
+        let mut ssim = [0.0f64; sys::CE_DSSIM_MAX_LEVELS];
+        let mut score = 0.0f64;
+        let rc = unsafe {
+            sys::ce_calculate_dssim_ssim_maps(self.ctx, reference.as_ptr(), reference.len(), test.as_ptr(), test.len(), width, height,
+                                              &mut score, ssim.as_mut_ptr(), maps.as_mut_ptr(), maps.len())
+        };
+        self.check(rc, width as u32, height as u32, test.len())?;
+        let mut out = Vec::with_capacity(sizes.len());
+        let mut off = 0;
+        for (l, &(w, h)) in sizes.iter().enumerate() {
+            out.push(SsimMap { width: w, height: h, map: maps[off..off + w * h].to_vec(), ssim: ssim[l] });
+            off += w * h;
+        }
+        Ok((score, out))
+    }
+}
+
+/// dssim-core's `SsimMap` (re-exported at src/metrics/prelude.rs:45): one scale's per-pixel SSIM image, row-major
+/// `width * height`, and that scale's pooled score.
+#[derive(Clone, Debug)]
+pub struct SsimMap {
+    pub width: usize,
+    pub height: usize,
+    pub map: Vec<f32>,
+    pub ssim: f64,
 }
 
 /// Page-locked host bytes (`ce_host_alloc`): a decoder that writes its RGB8 output here lets `evaluate_grid` copy it with

@@ -14,7 +14,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from dataclasses import dataclass
-from typing import Iterable, List, Optional, Sequence
+from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -35,6 +35,7 @@ FLAG_XYB_ROUNDTRIP = 1
 FLAG_BUTTERAUGLI_DIFFMAP = 1 << 1
 PIXEL_RGB8, PIXEL_RGBA8, PIXEL_RGB16_10BIT, PIXEL_RGBA16_10BIT = 0, 1, 2, 3
 DEFAULT_INTENSITY_TARGET = 80.0
+DSSIM_MAX_LEVELS = 5  # CE_DSSIM_MAX_LEVELS
 
 _STATUS_NAMES = {
     CE_ERR_DIM_MISMATCH: "DimensionMismatch",
@@ -118,6 +119,8 @@ _PROTOTYPES = [
     ("ce_calculate_dssim", _i, [_vp, _u8p, _sz, _u8p, _sz, _sz, _sz, _dp]),
     ("ce_calculate_butteraugli", _i, [_vp, _u8p, _sz, _u8p, _sz, _sz, _sz, _f32, _dp]),
     ("ce_calculate_butteraugli_diffmap", _i, [_vp, _u8p, _sz, _u8p, _sz, _sz, _sz, _f32, _dp, _vp]),
+    ("ce_dssim_levels", _i, [_u32, _u32, C.POINTER(_u32), _vp, _vp]),
+    ("ce_calculate_dssim_ssim_maps", _i, [_vp, _u8p, _sz, _u8p, _sz, _sz, _sz, _dp, _vp, _vp, _sz]),
     ("ce_xyb_roundtrip", _i, [_vp, _u8p, _sz, _sz, _sz, _u8p]),
     ("ce_rgb8_to_dssim_image", _i, [_vp, _u8p, _sz, _sz, _sz, _vp]),
     ("ce_eval_pair", _i, [_vp, _u8p, _sz, _u8p, _sz, _u32, _u32, _u32, _u32, _f32, C.POINTER(CeScores)]),
@@ -145,11 +148,13 @@ _PROTOTYPES = [
     ("ce_batch_collect", _i, [_vp, _u32, C.POINTER(CeScores)]),
     ("ce_batch_butteraugli_pnorm3", _i, [_vp, _u32, _dp]),
     ("ce_batch_butteraugli_diffmap", _i, [_vp, _u32, _u32, _u32, _vp, _sz]),
+    ("ce_batch_dssim_ssim_maps", _i, [_vp, _u32, _u32, _u32, _u32, _vp, _sz, _vp]),
     ("ce_ref_create", _i, [_vp, _u8p, _sz, _u32, _u32, _u32, C.POINTER(_vp)]),
     ("ce_ref_compare", _i, [_vp, _u8p, _sz, _u32, _f32, C.POINTER(CeScores)]),
     ("ce_ref_compare_many", _i, [_vp, C.POINTER(_u8p), C.POINTER(_sz), _u32, _u32, _f32, C.POINTER(CeScores)]),
     ("ce_ref_stats", _i, [_vp, C.POINTER(_u32 * 3)]),
     ("ce_ref_butteraugli_diffmap", _i, [_vp, _u32, _u32, _u32, _vp, _sz]),
+    ("ce_ref_dssim_ssim_maps", _i, [_vp, _u32, _u32, _u32, _u32, _vp, _sz, _vp]),
     ("ce_ref_destroy", None, [_vp]),
     ("ce_prof_enable", _i, [_vp, _i]),
     ("ce_prof_filter", _i, [_vp, C.c_char_p]),
@@ -332,6 +337,39 @@ def _read_diffmaps(ctx: "Context", fn, handle, width: int, height: int, first: i
 
 
 @dataclass
+class SsimMap:
+    """dssim-core's SsimMap (re-exported at src/metrics/prelude.rs:45): one scale's per-pixel SSIM image, an [h_l, w_l]
+    float32 array, and that scale's pooled score."""
+    map: np.ndarray
+    ssim: float
+
+
+def dssim_levels(width: int, height: int) -> List[Tuple[int, int]]:
+    """(w_l, h_l) of DSSIM's scales (Dssim::create_image): halved (floor) while at least 8 x 8, at most DSSIM_MAX_LEVELS."""
+    n, lw, lh = _u32(), (_u32 * DSSIM_MAX_LEVELS)(), (_u32 * DSSIM_MAX_LEVELS)()
+    L = lib()
+    rc = L.ce_dssim_levels(width, height, C.byref(n), lw, lh)
+    if rc != CE_OK:
+        _raise(rc, (L.ce_last_error(None) or b"").decode())
+    return [(int(lw[l]), int(lh[l])) for l in range(n.value)]
+
+
+def _read_ssim_maps(ctx: "Context", fn, handle, width: int, height: int, level: int, first: int, count: int, block: int):
+    """(maps float32 [count, ceil(h_l / block), ceil(w_l / block)], ssim float64 [count]) through ce_batch_dssim_ssim_maps /
+    ce_ref_dssim_ssim_maps."""
+    if block < 1:
+        raise CodecEvalError(CE_ERR_INVALID_ARG, "block must be 1 or a power of two up to 64")
+    levels = dssim_levels(width, height)
+    if not 0 <= level < len(levels):
+        raise CodecEvalError(CE_ERR_INVALID_ARG, f"DSSIM level {level} of {len(levels)}")
+    w, h = levels[level]
+    maps = np.empty((count, -(-h // block), -(-w // block)), np.float32)
+    ssim = np.empty(count, np.float64)
+    ctx._check(fn(handle, level, first, count, block, maps.ctypes.data, maps.size, ssim.ctypes.data))
+    return maps, ssim
+
+
+@dataclass
 class MetricResult:
     dssim: Optional[float] = None
     ssimulacra2: Optional[float] = None
@@ -455,6 +493,22 @@ class Context:
         self._check(lib().ce_calculate_butteraugli_diffmap(self._h, r.ctypes.data, r.size, t.ctypes.data, t.size, width, height,
                                                            float(intensity_target), C.byref(score), dm.ctypes.data))
         return ButteraugliResult(score.value, dm)
+
+    def calculate_dssim_with_ssim_maps(self, reference, test, width: int, height: int) -> Tuple[float, List[SsimMap]]:
+        """Dssim::compare with the maps kept (Dssim::set_save_ssim_maps): (the score of calculate_dssim, one SsimMap per
+        scale, level 0 = full resolution)."""
+        r, t = _buf(reference), _buf(test)
+        levels = dssim_levels(width, height) if width and height else []
+        maps = np.empty(sum(w * h for w, h in levels), np.float32)
+        ssim = np.empty(DSSIM_MAX_LEVELS, np.float64)
+        score = C.c_double()
+        self._check(lib().ce_calculate_dssim_ssim_maps(self._h, r.ctypes.data, r.size, t.ctypes.data, t.size, width, height,
+                                                       C.byref(score), ssim.ctypes.data, maps.ctypes.data, maps.size))
+        out, off = [], 0
+        for l, (w, h) in enumerate(levels):
+            out.append(SsimMap(maps[off:off + w * h].reshape(h, w), float(ssim[l])))
+            off += w * h
+        return score.value, out
 
     def xyb_roundtrip(self, rgb, width: int, height: int) -> np.ndarray:
         """xyb_roundtrip, src/metrics/xyb.rs:225."""
@@ -649,6 +703,12 @@ class Batch:
         maximum over each block x block cell."""
         return _read_diffmaps(self.ctx, lib().ce_batch_butteraugli_diffmap, self._h, self.width, self.height, first, count, block)
 
+    def dssim_ssim_maps(self, level: int, first: int, count: int, block: int = 1):
+        """DSSIM's SsimMap at `level` of pairs [first, first + count) of the last run / launch with DSSIM:
+        (maps, float32 [count, ceil(h_l / block), ceil(w_l / block)], ssim, float64 [count]).  block = 1 is the full map, a
+        power of two up to 64 the minimum over each block x block cell."""
+        return _read_ssim_maps(self.ctx, lib().ce_batch_dssim_ssim_maps, self._h, self.width, self.height, level, first, count, block)
+
     # -- test hooks
     def debug_limit_scales(self, n: int):
         self.ctx._check(lib().ce_debug_ssim2_limit_scales(self._h, n))
@@ -706,6 +766,11 @@ class ReferenceHandle:
         """Diffmaps of tests [first, first + count) of the last compare / compare_many (handle made with
         butteraugli_diffmap=True, a config with Butteraugli): see Batch.butteraugli_diffmaps."""
         return _read_diffmaps(self.ctx, lib().ce_ref_butteraugli_diffmap, self._h, self.width, self.height, first, count, block)
+
+    def dssim_ssim_maps(self, level: int, first: int, count: int, block: int = 1):
+        """DSSIM's SsimMap of tests [first, first + count) of the last compare / compare_many with DSSIM: see
+        Batch.dssim_ssim_maps."""
+        return _read_ssim_maps(self.ctx, lib().ce_ref_dssim_ssim_maps, self._h, self.width, self.height, level, first, count, block)
 
     def stats(self):
         """(ssimulacra2, dssim, butteraugli): compares so far that had to build that metric's reference-side state."""

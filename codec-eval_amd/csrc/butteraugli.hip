@@ -1134,25 +1134,6 @@ __global__ __launch_bounds__(TPB) void k_ba_score(const float *__restrict__ blk_
     }
 }
 
-// B x B cell maxima (B = 1 << lb, 2 .. 64) of the stored full-resolution diffmaps of pairs [first, first + count), packed
-// [count][ceil(h / B)][ceil(w / B)].  One thread per column of one cell row: the max down the cell's rows (a wave reads 64
-// adjacent columns of a row), then across the cell's B lanes (B <= 64: a cell never leaves its wave).  Columns at or past
-// w enter as -inf and read nothing, so the pitch padding is never read; the max of the same floats is exact.
-__global__ __launch_bounds__(256) void k_ba_block_max(const float *__restrict__ map, geom g, uint32_t first, uint32_t lb,
-                                                      uint32_t tiles_x, uint32_t bw, uint32_t bh, float *__restrict__ out)
-{
-    const uint32_t t = blockIdx.x % tiles_x, cy = (blockIdx.x / tiles_x) % bh, q = blockIdx.x / tiles_x / bh;
-    const uint32_t B = 1u << lb, x = t * 256 + threadIdx.x;
-    float m = -__builtin_inff();
-    if (x < g.w) {
-        const float *col = map + (size_t)(first + q) * g.plane + x;
-        const uint32_t y1 = min((cy + 1) << lb, g.h);
-        for (uint32_t y = cy << lb; y < y1; y++) m = fmaxf(m, col[(size_t)y * g.pitch]);
-    }
-    for (uint32_t off = 1; off < B; off <<= 1) m = fmaxf(m, __shfl_xor(m, (int)off, 64));
-    if (x < g.w && (x & (B - 1)) == 0) out[((size_t)q * bh + cy) * bw + (x >> lb)] = m;
-}
-
 // debug: div2_shared_rcp against operator/ on pseudo-random operands of the ranges Malta uses (and wider)
 __global__ __launch_bounds__(256) void k_div_sweep(uint64_t seed, uint64_t count, unsigned long long *out)
 {
@@ -1463,39 +1444,10 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
 }
 
 // B x B cell maxima (B = 1: the packed map itself) of the stored diffmaps of pairs [first, first + count) into `out` (host,
-// count * ceil(h / B) * ceil(w / B) floats); the caller has checked the range and B.  Enqueued on the context's stream,
-// behind the launch that wrote the maps, and waited for.
+// count * ceil(h / B) * ceil(w / B) floats); the caller has checked the range and B.  maps.hip: ce_read_map_cells.
 int ce_butteraugli_read_maps(ce_batch *b, uint32_t first, uint32_t count, uint32_t block, float *out)
 {
-    ce_ctx *ctx = b->ctx;
     const auto &d = b->ba[0];
-    const geom g{d.w, d.h, d.pitch, d.plane};
-    if (block == 1) {  // [pair][h][pitch] rows are contiguous over the pairs: one pitched copy
-        CE_HIP(ctx, hipMemcpy2DAsync(out, (size_t)d.w * sizeof(float), b->ba_map + (size_t)first * d.plane, (size_t)d.pitch * sizeof(float),
-                                     (size_t)d.w * sizeof(float), (size_t)count * d.h, hipMemcpyDeviceToHost, ctx->stream));
-        CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return CE_OK;
-    }
-    uint32_t lb = 0;
-    while ((1u << lb) < block) lb++;
-    const uint32_t bw = (d.w + block - 1) >> lb, bh = (d.h + block - 1) >> lb, tiles_x = (d.w + 255) / 256;
-    const size_t n = (size_t)count * bw * bh;
-    if (b->ba_cells_cap < n) {
-        hipFree(b->ba_cells);
-        b->ba_cells = nullptr;
-        b->ba_cells_cap = 0;
-        CE_HIP(ctx, hipMalloc(&b->ba_cells, n * sizeof(float)));
-        b->ba_cells_cap = n;
-    }
-    const size_t blocks = (size_t)tiles_x * bh * count;
-    if (blocks > 0x7fffffffu) {
-        ctx->err = "diffmap readout too large for one launch";
-        return CE_ERR_INVALID_ARG;
-    }
-    CE_LAUNCH_ON(ctx, ctx->stream, "ba_block_max", k_ba_block_max, dim3((uint32_t)blocks), dim3(256), 0, (const float *)b->ba_map, g, first,
-                 lb, tiles_x, bw, bh, b->ba_cells);
-    CE_HIP(ctx, hipGetLastError());
-    CE_HIP(ctx, hipMemcpyAsync(out, b->ba_cells, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CE_OK;
+    return ce_read_map_cells(b, "ba_block_max", b->ba_map, ce_map_geom{d.w, d.h, d.pitch, d.plane}, first, count, block, false,
+                             &b->ba_cells, &b->ba_cells_cap, out);
 }

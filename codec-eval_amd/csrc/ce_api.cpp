@@ -43,6 +43,23 @@ int validate_pair(ce_ctx *ctx, size_t ref_len, size_t test_len, size_t w, size_t
 
 constexpr uint32_t kKnownMetrics = CE_METRIC_DSSIM | CE_METRIC_SSIMULACRA2 | CE_METRIC_BUTTERAUGLI | CE_METRIC_PSNR;
 
+// the argument checks of every map readout (what = "diffmap" / "SSIM map"): pairs [first, first + count) of the `stored`
+// ones of the last launch, block 1 or a power of two up to 64, and out_floats = count * ceil(w / B) * ceil(h / B) floats of
+// a w x h map (0 when there is no map output)
+int check_map_readout(ce_ctx *ctx, const char *what, uint32_t stored, uint32_t first, uint32_t count, uint32_t block, uint32_t w,
+                      uint32_t h, bool has_out, size_t out_floats)
+{
+    if (count == 0 || first > stored || count > stored - first)
+        return fail(ctx, CE_ERR_INVALID_ARG, std::string(what) + " pairs [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) +
+                                                 ") outside the " + std::to_string(stored) + " stored");
+    if (block == 0 || block > 64 || (block & (block - 1)) != 0)
+        return fail(ctx, CE_ERR_INVALID_ARG, std::string(what) + " block must be 1 or a power of two up to 64");
+    const size_t want = has_out ? (size_t)count * ((w + block - 1) / block) * ((h + block - 1) / block) : 0;
+    if (out_floats != want)
+        return fail(ctx, CE_ERR_INVALID_ARG, std::string(what) + " readout needs " + std::to_string(want) + " floats, got " + std::to_string(out_floats));
+    return CE_OK;
+}
+
 // the readouts of CE_FLAG_BUTTERAUGLI_DIFFMAP (ce_batch_butteraugli_diffmap, ce_ref_butteraugli_diffmap): checks, then the
 // device readout (butteraugli.hip)
 int read_diffmaps(ce_batch *b, uint32_t first, uint32_t count, uint32_t block, float *out, size_t out_floats)
@@ -51,16 +68,25 @@ int read_diffmaps(ce_batch *b, uint32_t first, uint32_t count, uint32_t block, f
     ce_ctx *ctx = b->ctx;
     if (b->ba_map_pairs == 0)
         return fail(ctx, CE_ERR_INVALID_ARG, "no Butteraugli diffmaps: the last launch did not run Butteraugli with CE_FLAG_BUTTERAUGLI_DIFFMAP");
-    if (count == 0 || first > b->ba_map_pairs || count > b->ba_map_pairs - first)
-        return fail(ctx, CE_ERR_INVALID_ARG, "diffmap pairs [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) +
-                                                 ") outside the " + std::to_string(b->ba_map_pairs) + " stored");
-    if (block == 0 || block > 64 || (block & (block - 1)) != 0)
-        return fail(ctx, CE_ERR_INVALID_ARG, "diffmap block must be 1 or a power of two up to 64");
-    const size_t want = (size_t)count * ((b->w + block - 1) / block) * ((b->h + block - 1) / block);
-    if (out_floats != want)
-        return fail(ctx, CE_ERR_INVALID_ARG, "diffmap readout needs " + std::to_string(want) + " floats, got " + std::to_string(out_floats));
+    if (int rc = check_map_readout(ctx, "diffmap", b->ba_map_pairs, first, count, block, b->w, b->h, true, out_floats)) return rc;
     CE_HIP(ctx, hipSetDevice(ctx->device));
     return ce_butteraugli_read_maps(b, first, count, block, out);
+}
+
+// the readouts of DSSIM's SsimMap (ce_batch_dssim_ssim_maps, ce_ref_dssim_ssim_maps): checks, then the device readout
+// (dssim.hip)
+int read_ssim_maps(ce_batch *b, uint32_t level, uint32_t first, uint32_t count, uint32_t block, float *maps, size_t maps_floats,
+                   double *ssim)
+{
+    if (!b || (!maps && !ssim)) return CE_ERR_INVALID_ARG;
+    ce_ctx *ctx = b->ctx;
+    if (b->ds_map_pairs == 0) return fail(ctx, CE_ERR_INVALID_ARG, "no DSSIM SSIM maps: the last launch did not run DSSIM");
+    if (level >= (uint32_t)b->ds_levels)
+        return fail(ctx, CE_ERR_INVALID_ARG, "DSSIM level " + std::to_string(level) + " of " + std::to_string(b->ds_levels));
+    const auto &d = b->ds[level];
+    if (int rc = check_map_readout(ctx, "SSIM map", b->ds_map_pairs, first, count, block, d.w, d.h, maps != nullptr, maps_floats)) return rc;
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    return ce_dssim_read_maps(b, level, first, count, block, maps, ssim);
 }
 
 double psnr_from_sse(unsigned long long sse, size_t w, size_t h)
@@ -775,7 +801,7 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
     ce_ctx *ctx = b->ctx;
     if (n_pairs == 0 || n_pairs > b->max_pairs) return fail(ctx, CE_ERR_INVALID_ARG, "n_pairs out of range");
     if (metric_mask & ~kKnownMetrics) return fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
-    b->ba_map_pairs = 0;  // whatever happens below, no readout returns the maps of an earlier launch
+    b->ba_map_pairs = b->ds_map_pairs = 0;  // whatever happens below, no readout returns the maps of an earlier launch
     CE_HIP(ctx, hipSetDevice(ctx->device));
     {
         int rc = flush_uploads(b);
@@ -950,6 +976,7 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
     b->last_n_pairs = n_pairs;
     b->last_mask = metric_mask;
     b->ba_map_pairs = store_maps ? n_pairs : 0;
+    b->ds_map_pairs = run_dssim ? n_pairs : 0;  // DSSIM writes its SSIM maps on every launch
     // the scores come back behind the last kernel of THIS launch and ev_run marks them: ce_batch_collect waits for the event,
     // not for the stream (round 2 copied at collect time and drained the context's stream, so collecting one batch waited
     // for every batch launched after it - in ce_eval_batch the next chunk's upload then started only when the device was idle)
@@ -1021,6 +1048,12 @@ int ce_batch_butteraugli_pnorm3(ce_batch *b, uint32_t n_pairs, double *out)
 int ce_batch_butteraugli_diffmap(ce_batch *b, uint32_t first, uint32_t count, uint32_t block, float *out, size_t out_floats)
 {
     return read_diffmaps(b, first, count, block, out, out_floats);
+}
+
+int ce_batch_dssim_ssim_maps(ce_batch *b, uint32_t level, uint32_t first, uint32_t count, uint32_t block, float *maps,
+                             size_t maps_floats, double *ssim)
+{
+    return read_ssim_maps(b, level, first, count, block, maps, maps_floats, ssim);
 }
 
 int ce_batch_run(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_t flags, float intensity_target,
@@ -1309,17 +1342,13 @@ int ce_calculate_butteraugli(ce_ctx *ctx, const uint8_t *reference, size_t refer
                 out);
 }
 
-int ce_calculate_butteraugli_diffmap(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test,
-                                     size_t test_len, size_t width, size_t height, float intensity_target, double *score,
-                                     float *diffmap_out)
+// The one-pair map calls (ce_calculate_butteraugli_diffmap, ce_calculate_dssim_ssim_maps): the pair through a one-pair batch
+// of the context, kept while the shape stays the same (not the pooled ce_eval_batch batches, whose next call reuses them);
+// *out_b is that batch, with the maps of this run.  The caller has checked the arguments.
+static int leaf_map_run(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test, size_t test_len, size_t width,
+                        size_t height, uint32_t metric, uint32_t flags, float intensity_target, ce_scores *s, ce_batch **out_b)
 {
-    if (!ctx || !reference || !test || !score || !diffmap_out) return CE_ERR_INVALID_ARG;
-    if (int rc = validate_pair(ctx, reference_len, test_len, width, height)) return rc;
-    if (width < 8 || height < 8) return fail(ctx, CE_ERR_TOO_SMALL, "minimum 8x8 for butteraugli");  // src/eval/helpers.rs:89
-    if (width > UINT32_MAX || height > UINT32_MAX) return fail(ctx, CE_ERR_INVALID_ARG, "image too large");
     CE_HIP(ctx, hipSetDevice(ctx->device));
-    // a one-pair batch of the context, kept while the shape stays the same (not the pooled ce_eval_batch batches, which
-    // keep no maps)
     ce_batch *b = ctx->leaf_map;
     if (!b || b->w != width || b->h != height) {
         ce_batch_destroy(b);
@@ -1330,14 +1359,57 @@ int ce_calculate_butteraugli_diffmap(ce_ctx *ctx, const uint8_t *reference, size
     b->caller_blocks = true;  // collected before return: page-locked images are read in place (upload())
     int rc = ce_batch_set_reference(b, 0, reference, reference_len);
     if (rc == CE_OK) rc = ce_batch_set_test(b, 0, 0, test, test_len);
-    ce_scores s{};
-    if (rc == CE_OK) rc = ce_batch_run(b, 1, CE_METRIC_BUTTERAUGLI, CE_FLAG_BUTTERAUGLI_DIFFMAP, intensity_target, &s);
+    if (rc == CE_OK) rc = ce_batch_run(b, 1, metric, flags, intensity_target, s);
     if (rc != CE_OK) drain_batch(b);
     b->caller_blocks = false;
     if (rc != CE_OK) return rc;
-    if (s.status != CE_OK) return s.status;
+    *out_b = b;
+    return s->status;
+}
+
+int ce_calculate_butteraugli_diffmap(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test,
+                                     size_t test_len, size_t width, size_t height, float intensity_target, double *score,
+                                     float *diffmap_out)
+{
+    if (!ctx || !reference || !test || !score || !diffmap_out) return CE_ERR_INVALID_ARG;
+    if (int rc = validate_pair(ctx, reference_len, test_len, width, height)) return rc;
+    if (width < 8 || height < 8) return fail(ctx, CE_ERR_TOO_SMALL, "minimum 8x8 for butteraugli");  // src/eval/helpers.rs:89
+    if (width > UINT32_MAX || height > UINT32_MAX) return fail(ctx, CE_ERR_INVALID_ARG, "image too large");
+    ce_scores s{};
+    ce_batch *b = nullptr;
+    if (int rc = leaf_map_run(ctx, reference, reference_len, test, test_len, width, height, CE_METRIC_BUTTERAUGLI,
+                              CE_FLAG_BUTTERAUGLI_DIFFMAP, intensity_target, &s, &b))
+        return rc;
     if (int r = read_diffmaps(b, 0, 1, 1, diffmap_out, width * height)) return r;
     *score = s.butteraugli;
+    return CE_OK;
+}
+
+int ce_calculate_dssim_ssim_maps(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test, size_t test_len,
+                                 size_t width, size_t height, double *dssim, double *level_ssim, float *maps, size_t maps_floats)
+{
+    if (!ctx || !reference || !test || !dssim || !level_ssim || !maps) return CE_ERR_INVALID_ARG;
+    if (width == 0 || height == 0) return fail(ctx, CE_ERR_INVALID_ARG, "empty image");  // ce_calculate_dssim's order
+    if (int rc = validate_pair(ctx, reference_len, test_len, width, height)) return rc;
+    if (width > UINT32_MAX || height > UINT32_MAX) return fail(ctx, CE_ERR_INVALID_ARG, "image too large");
+    uint32_t lw[CE_DSSIM_MAX_LEVELS], lh[CE_DSSIM_MAX_LEVELS];
+    const uint32_t n = ce_plan_dssim_levels((uint32_t)width, (uint32_t)height, CE_DSSIM_MAX_LEVELS, lw, lh);
+    size_t want = 0;
+    for (uint32_t l = 0; l < n; l++) want += (size_t)lw[l] * lh[l];
+    if (maps_floats != want)
+        return fail(ctx, CE_ERR_INVALID_ARG, "SSIM maps of every level need " + std::to_string(want) + " floats, got " + std::to_string(maps_floats));
+    ce_scores s{};
+    ce_batch *b = nullptr;
+    if (int rc = leaf_map_run(ctx, reference, reference_len, test, test_len, width, height, CE_METRIC_DSSIM, 0, 0.0f, &s, &b))
+        return rc;
+    size_t off = 0;
+    for (uint32_t l = 0; l < CE_DSSIM_MAX_LEVELS; l++) {
+        level_ssim[l] = NAN;
+        if (l >= n) continue;
+        if (int r = read_ssim_maps(b, l, 0, 1, 1, maps + off, (size_t)lw[l] * lh[l], &level_ssim[l])) return r;
+        off += (size_t)lw[l] * lh[l];
+    }
+    *dssim = s.dssim;
     return CE_OK;
 }
 
@@ -1488,6 +1560,21 @@ int ce_ref_butteraugli_diffmap(ce_ref *ref, uint32_t first, uint32_t count, uint
 {
     if (!ref) return CE_ERR_INVALID_ARG;
     return read_diffmaps(ref->batch, first, count, block, out, out_floats);  // the handle's current batch (compare_many may replace it)
+}
+
+int ce_ref_dssim_ssim_maps(ce_ref *ref, uint32_t level, uint32_t first, uint32_t count, uint32_t block, float *maps,
+                           size_t maps_floats, double *ssim)
+{
+    if (!ref) return CE_ERR_INVALID_ARG;
+    return read_ssim_maps(ref->batch, level, first, count, block, maps, maps_floats, ssim);  // the handle's current batch
+}
+
+int ce_dssim_levels(uint32_t width, uint32_t height, uint32_t *n_levels, uint32_t *level_w, uint32_t *level_h)
+{
+    if (!n_levels || !level_w || !level_h) return fail(nullptr, CE_ERR_INVALID_ARG, "null pointer");
+    if (width == 0 || height == 0) return fail(nullptr, CE_ERR_INVALID_ARG, "empty image");
+    *n_levels = ce_plan_dssim_levels(width, height, CE_DSSIM_MAX_LEVELS, level_w, level_h);
+    return CE_OK;
 }
 
 int ce_ref_stats(const ce_ref *ref, uint32_t builds[3])

@@ -84,7 +84,7 @@ struct ce_ctx {
     // ce_rgb8_to_dssim_image): device in / out and a page-locked staging buffer, kept between calls
     uint8_t *leaf_d_in = nullptr, *leaf_d_out = nullptr, *leaf_h = nullptr;
     size_t leaf_in_cap = 0, leaf_out_cap = 0, leaf_h_cap = 0;
-    // the one-pair batch of ce_calculate_butteraugli_diffmap (remade when the shape changes)
+    // the one-pair batch of ce_calculate_butteraugli_diffmap and ce_calculate_dssim_ssim_maps (remade when the shape changes)
     struct ce_batch *leaf_map = nullptr;
 
     // Auxiliary streams of the context, shared by all its batches (made on first use, destroyed with the context): the
@@ -186,9 +186,14 @@ struct ce_batch {
     float *ds_rimg[CE_DSSIM_SCALES] = {}, *ds_rmu[CE_DSSIM_SCALES] = {}, *ds_rsq[CE_DSSIM_SCALES] = {};  // the references' planes, per level: [max_refs][3][plane_l]
     const uint8_t *ds_ref_src = nullptr;  // reference slab those planes were built from (valid while keep_ref_pyramid)
     uint32_t ds_ref_count = 0;
-    float *ds_map = nullptr;   // [pairs][plane] SSIM map
+    float *ds_map = nullptr;   // [level][max_pairs][plane_l] channel-averaged SSIM maps (SsimMap.map)
     double *ds_part = nullptr; // [pairs][levels][2][blocks] partial sums (sum, abs-dev)
-    double *ds_level_scores = nullptr;  // [pairs][levels]
+    double *ds_level_scores = nullptr;  // [pairs][CE_DSSIM_SCALES]: after a launch, every level's score (SsimMap.ssim)
+    // how many pairs of the LAST launch left their SSIM maps in ds_map (every launch with DSSIM does; 0 after one without),
+    // and the device buffer of the block-min readouts (grow-only)
+    uint32_t ds_map_pairs = 0;
+    float *ds_cells = nullptr;
+    size_t ds_cells_cap = 0;
     uint32_t ds_blocks = 0;
     ce_xcd_list ds_gwork[CE_DSSIM_SCALES];  // k_dssim_compare_stream's launch order, per level
     bool dssim_ready = false;
@@ -301,6 +306,14 @@ void ce_dssim_free(ce_batch *b);
 int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, uint32_t n_pairs, float intensity_target,
                           bool store_map);
 int ce_butteraugli_read_maps(ce_batch *b, uint32_t first, uint32_t count, uint32_t block, float *out);
+int ce_dssim_read_maps(ce_batch *b, uint32_t level, uint32_t first, uint32_t count, uint32_t block, float *maps, double *ssim);
+// a pitched per-pair map plane set (maps.hip)
+struct ce_map_geom {
+    uint32_t w, h, pitch;
+    size_t plane;
+};
+int ce_read_map_cells(ce_batch *b, const char *name, const float *map, ce_map_geom g, uint32_t first, uint32_t count, uint32_t block,
+                      bool take_min, float **cells, size_t *cells_cap, float *out);
 void ce_butteraugli_free(ce_batch *b);
 int ce_butteraugli_div_sweep(ce_ctx *ctx, uint64_t seed, uint64_t count, uint64_t *mismatches);
 int ce_calibrate_traffic(ce_ctx *ctx, size_t bytes);

@@ -116,3 +116,21 @@ inline std::vector<ce_plan_entry> ce_plan_xcd_list(const uint32_t *pair_ref, uin
         for (size_t i = 0; i < cls[x].size(); i++) list[i * 8 + x] = cls[x][i];
     return list;
 }
+
+// DSSIM's scale pyramid (Dssim::create_image, make_scales_recursive): level 0 is the image, and a level is halved (floor)
+// into the next only while it is at least 8 x 8, up to max_levels levels.  Writes the level sizes, returns their count (0
+// for an empty image).  The one rule of dssim.hip's working set and of ce_dssim_levels.
+inline uint32_t ce_plan_dssim_levels(uint32_t w, uint32_t h, uint32_t max_levels, uint32_t *level_w, uint32_t *level_h)
+{
+    if (w == 0 || h == 0) return 0;
+    uint32_t n = 0;
+    while (n < max_levels) {
+        level_w[n] = w;
+        level_h[n] = h;
+        n++;
+        if (w < 8 || h < 8) break;
+        w /= 2;
+        h /= 2;
+    }
+    return n;
+}

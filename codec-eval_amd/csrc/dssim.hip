@@ -142,6 +142,14 @@ __global__ __launch_bounds__(64) void k_dssim_finalize_pairs(const double *__res
     if (lane == 0) scores[p].dssim = 1.0 / ssim - 1.0;
 }
 
+// level l's SSIM maps start at ds_map + map_offset(b, l): the levels one after the other, max_pairs planes each
+size_t map_offset(const ce_batch *b, int l)
+{
+    size_t off = 0;
+    for (int k = 0; k < l; k++) off += (size_t)b->max_pairs * b->ds[k].plane;
+    return off;
+}
+
 }  // namespace
 
 void ce_dssim_free(ce_batch *b)
@@ -154,8 +162,10 @@ void ce_dssim_free(ce_batch *b)
         ce_free_xcd_list(&b->ds_gwork[l]);
     }
     b->ds_ref_src = nullptr;
-    hipFree(b->ds_part); hipFree(b->ds_level_scores);
-    b->ds_img = b->ds_map = nullptr;
+    hipFree(b->ds_part); hipFree(b->ds_level_scores); hipFree(b->ds_cells);
+    b->ds_img = b->ds_map = b->ds_cells = nullptr;
+    b->ds_cells_cap = 0;
+    b->ds_map_pairs = 0;
     b->ds_part = b->ds_level_scores = nullptr;
     b->dssim_ready = false;
 }
@@ -163,20 +173,14 @@ void ce_dssim_free(ce_batch *b)
 static int dssim_allocate(ce_batch *b)
 {
     ce_ctx *ctx = b->ctx;
-    uint32_t w = b->w, h = b->h;
-    int n = 0;
-    // make_scales_recursive: a level is halved only while it is at least 8x8
-    for (int l = 0; l < CE_DSSIM_SCALES; l++) {
+    uint32_t lw[CE_DSSIM_SCALES], lh[CE_DSSIM_SCALES];
+    const int n = (int)ce_plan_dssim_levels(b->w, b->h, CE_DSSIM_SCALES, lw, lh);  // make_scales_recursive (ce_plan.h)
+    for (int l = 0; l < n; l++) {
         auto &d = b->ds[l];
-        d.w = w;
-        d.h = h;
-        d.pitch = (w + 31u) & ~31u;
-        d.plane = (size_t)d.pitch * h;
-        n++;
-        if (w < 8 || h < 8) break;
-        w /= 2;
-        h /= 2;
-        if (w == 0 || h == 0) break;
+        d.w = lw[l];
+        d.h = lh[l];
+        d.pitch = (d.w + 31u) & ~31u;
+        d.plane = (size_t)d.pitch * d.h;
     }
     b->ds_levels = n;
     const size_t slots = (size_t)b->max_refs + b->max_pairs, p0 = b->ds[0].plane;
@@ -193,9 +197,8 @@ static int dssim_allocate(ce_batch *b)
         CE_HIP(ctx, hipMalloc(&b->ds_rmu[l], rb));
         CE_HIP(ctx, hipMalloc(&b->ds_rsq[l], rb));
     }
-    size_t map_floats = 0;  // every level's SSIM maps stay until the tail kernels have run
-    for (int l = 0; l < n; l++) map_floats += (size_t)b->max_pairs * b->ds[l].plane;
-    CE_HIP(ctx, hipMalloc(&b->ds_map, map_floats * sizeof(float)));
+    // every level's SSIM maps, kept until the next launch (ce_dssim_read_maps)
+    CE_HIP(ctx, hipMalloc(&b->ds_map, map_offset(b, n) * sizeof(float)));
     // partial sums per (pair, level): the absdev kernel's blocks, or the compare kernel's strip tiles (>= 2 rows each)
     b->ds_blocks = std::max(((b->ds[0].w + 63) / 64) * ((b->ds[0].h + AD_ROWS - 1) / AD_ROWS), ((b->ds[0].w + CE_DSSIM_STRIP - 1) / CE_DSSIM_STRIP) * ((b->ds[0].h + 1) / 2));
     CE_HIP(ctx, hipMalloc(&b->ds_part, (size_t)b->max_pairs * CE_DSSIM_SCALES * 2 * b->ds_blocks * sizeof(double)));
@@ -229,17 +232,15 @@ int ce_launch_dssim(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
     if (!cached) b->ref_builds[1]++;
     ds_geom g{};
     ds_tail tail{};
-    size_t map_off = 0;
     for (int l = 0; l < b->ds_levels; l++) {
         const auto &d = b->ds[l];
         // create_image for every used slot (references once per reference), then compare per pair: dssim_stream.hip
         if ((rc = ce_dssim_create_stream(b, l, d_refs, n_refs_used, n_pairs, z0)) != CE_OK) return rc;
         uint32_t n_part = 0;
-        if ((rc = ce_dssim_compare_stream(b, l, n_pairs, b->ds_map + map_off, &n_part)) != CE_OK) return rc;
+        if ((rc = ce_dssim_compare_stream(b, l, n_pairs, b->ds_map + map_offset(b, l), &n_part)) != CE_OK) return rc;
         tail.w[l] = d.w, tail.h[l] = d.h, tail.pitch[l] = d.pitch, tail.plane[l] = d.plane, tail.n_part[l] = n_part;
         tail.gx[l] = (d.w + 63) / 64;
-        tail.map_off[l] = map_off;
-        map_off += (size_t)b->max_pairs * d.plane;
+        tail.map_off[l] = map_offset(b, l);
         g.npix[l] = d.w * d.h;
         g.nblk[l] = tail.gx[l] * ((d.h + AD_ROWS - 1) / AD_ROWS);
         tail.blk_end[l] = (l ? tail.blk_end[l - 1] : 0u) + g.nblk[l];
@@ -259,6 +260,23 @@ int ce_launch_dssim(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
               b->ds_level_scores, b->d_scores, n_pairs, (uint32_t)b->ds_levels, b->ds_blocks, g);
     CE_HIP(ctx, hipGetLastError());
     return CE_OK;
+}
+
+// SsimMap of pairs [first, first + count) at `level`, from the last launch: the maps (B = 1) or their B x B cell minima
+// into `maps` and the level scores into `ssim`, either of them may be null; the caller has checked the arguments.
+// Enqueued on the context's stream behind that launch (maps.hip: ce_read_map_cells) and waited for.
+int ce_dssim_read_maps(ce_batch *b, uint32_t level, uint32_t first, uint32_t count, uint32_t block, float *maps, double *ssim)
+{
+    ce_ctx *ctx = b->ctx;
+    if (ssim) {  // every pair's score of this level: a strided gather out of [pair][CE_DSSIM_SCALES]
+        CE_HIP(ctx, hipMemcpy2DAsync(ssim, sizeof(double), b->ds_level_scores + (size_t)first * CE_DSSIM_SCALES + level,
+                                     CE_DSSIM_SCALES * sizeof(double), sizeof(double), count, hipMemcpyDeviceToHost, ctx->stream));
+        if (!maps) CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (!maps) return CE_OK;
+    const auto &d = b->ds[level];
+    return ce_read_map_cells(b, "dssim_block_min", b->ds_map + map_offset(b, (int)level), ce_map_geom{d.w, d.h, d.pitch, d.plane},
+                             first, count, block, true, &b->ds_cells, &b->ds_cells_cap, maps);
 }
 
 int ce_launch_rgb8_to_dssim_image(ce_ctx *ctx, const uint8_t *d_rgb, float *d_rgba, size_t n_pixels)

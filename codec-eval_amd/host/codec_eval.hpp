@@ -182,6 +182,37 @@ inline ButteraugliResult calculate_butteraugli_with_diffmap(const HipBackend &be
                   "Butteraugli", width, height, test.size());
     return r;
 }
+// dssim-core's SsimMap (re-exported at src/metrics/prelude.rs:45): one scale's per-pixel SSIM image, row-major
+// width * height, and that scale's pooled score
+struct SsimMap {
+    size_t width, height;
+    std::vector<float> map;
+    double ssim;
+};
+// calculate_dssim with the maps kept, the shape of Dssim::compare ((Val, Vec<SsimMap>), dropped at src/metrics/dssim.rs:68):
+// the score and one SsimMap per scale, level 0 at full resolution
+inline std::pair<double, std::vector<SsimMap>> calculate_dssim_with_ssim_maps(const HipBackend &be, const Bytes &reference,
+                                                                              const Bytes &test, size_t width, size_t height)
+{
+    uint32_t n = 0, lw[CE_DSSIM_MAX_LEVELS] = {}, lh[CE_DSSIM_MAX_LEVELS] = {};
+    if (width > 0 && height > 0 && width <= UINT32_MAX && height <= UINT32_MAX)
+        ce_dssim_levels((uint32_t)width, (uint32_t)height, &n, lw, lh);
+    size_t total = 0;
+    for (uint32_t l = 0; l < n; l++) total += (size_t)lw[l] * lh[l];
+    std::vector<float> maps(total);
+    double score = 0.0, ssim[CE_DSSIM_MAX_LEVELS];
+    detail::check(be, ce_calculate_dssim_ssim_maps(be.ctx(), reference.data(), reference.size(), test.data(), test.size(), width, height,
+                                                   &score, ssim, maps.data(), maps.size()),
+                  "DSSIM", width, height, test.size());
+    std::vector<SsimMap> out;
+    size_t off = 0;
+    for (uint32_t l = 0; l < n; l++) {
+        const size_t m = (size_t)lw[l] * lh[l];
+        out.push_back(SsimMap{lw[l], lh[l], std::vector<float>(maps.begin() + off, maps.begin() + off + m), ssim[l]});
+        off += m;
+    }
+    return {score, std::move(out)};
+}
 // xyb_roundtrip, src/metrics/xyb.rs:225-253 (asserts on the length, :227)
 inline Bytes xyb_roundtrip(const HipBackend &be, const Bytes &rgb, size_t width, size_t height)
 {

@@ -71,6 +71,7 @@ enum ce_flag {
 };
 
 #define CE_DEFAULT_INTENSITY_TARGET 80.0f /* src/metrics/butteraugli.rs:94 */
+#define CE_DSSIM_MAX_LEVELS 5 /* dssim-core's scale weights: at most this many SsimMap per compare */
 
 /* MetricResult (src/metrics/mod.rs:140-149): a score is meaningful iff its bit is
  * set in `valid`; `status` is the ce_status of this pair. */
@@ -127,6 +128,20 @@ int ce_calculate_butteraugli(ce_ctx *ctx, const uint8_t *reference, size_t refer
 int ce_calculate_butteraugli_diffmap(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test,
                                      size_t test_len, size_t width, size_t height, float intensity_target,
                                      double *score, float *diffmap_out);
+/* DSSIM's SsimMap (dssim-core, re-exported at src/metrics/prelude.rs:45; Dssim::compare returns (Val, Vec<SsimMap>),
+ * which src/metrics/dssim.rs:68 drops as _ssim_maps).  An SsimMap is one scale's per-pixel SSIM image of the channel-
+ * averaged statistics (map) and that scale's pooled score (ssim).
+ * Level geometry, the rule of Dssim::create_image: a level is halved (floor) only while it is at least 8 x 8, at most
+ * CE_DSSIM_MAX_LEVELS levels; level_w / level_h have CE_DSSIM_MAX_LEVELS entries.  A pure host function (no context, works
+ * without a device); CE_ERR_INVALID_ARG for width or height 0 or a null pointer. */
+int ce_dssim_levels(uint32_t width, uint32_t height, uint32_t *n_levels, uint32_t *level_w, uint32_t *level_h);
+/* The one-pair call: Dssim::compare with every scale's map kept (Dssim::set_save_ssim_maps).  dssim as ce_calculate_dssim;
+ * level_ssim[CE_DSSIM_MAX_LEVELS] the levels' SsimMap.ssim (NaN past the image's level count); maps every level's full map,
+ * level after level, row-major; maps_floats must be the sum of w_l * h_l over the levels (ce_dssim_levels).  Length and
+ * dimension errors as ce_calculate_dssim. */
+int ce_calculate_dssim_ssim_maps(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test,
+                                 size_t test_len, size_t width, size_t height, double *dssim, double *level_ssim,
+                                 float *maps, size_t maps_floats);
 /* xyb_roundtrip                         src/metrics/xyb.rs:225 ; out has rgb_len bytes */
 int ce_xyb_roundtrip(ce_ctx *ctx, const uint8_t *rgb, size_t rgb_len, size_t width, size_t height,
                      uint8_t *out);
@@ -230,6 +245,14 @@ int ce_batch_butteraugli_pnorm3(ce_batch *b, uint32_t n_pairs, double *out);
  * that launch.  CE_ERR_INVALID_ARG for a null pointer, no stored maps, count = 0 or a range past the stored pairs, a bad
  * block or a wrong out_floats. */
 int ce_batch_butteraugli_diffmap(ce_batch *b, uint32_t first, uint32_t count, uint32_t block, float *out, size_t out_floats);
+/* DSSIM's SsimMap (see ce_dssim_levels) of pairs [first, first+count) at `level`, from the last launch of this batch that
+ * ran CE_METRIC_DSSIM (every such launch keeps its maps on the device, no flag needed).  maps = [count][ceil(h_l/B)]
+ * [ceil(w_l/B)] floats: block B = 1 is the full map, B = a power of two <= 64 the MINIMUM of each B x B cell (the worst
+ * local similarity; edge cells clipped to the level); ssim = [count] doubles (SsimMap.ssim).  Either output may be NULL
+ * (maps_floats then 0), not both.  Waits for that launch.  CE_ERR_INVALID_ARG for a null handle, no stored maps,
+ * level >= the level count, count = 0 or a range past the stored pairs, a bad block or a wrong maps_floats. */
+int ce_batch_dssim_ssim_maps(ce_batch *b, uint32_t level, uint32_t first, uint32_t count, uint32_t block,
+                             float *maps, size_t maps_floats, double *ssim);
 
 /* ---- reference handle: Ssimulacra2Reference::{new,compare} ------------------------
  * crates/codec-iter/src/eval.rs:138-149,83-89; crates/codec-compare/src/brute_force_sweep.rs:197-201,256
@@ -256,6 +279,9 @@ int ce_ref_stats(const ce_ref *ref, uint32_t builds[3]);
 /* the same for a reference handle created with CE_FLAG_BUTTERAUGLI_DIFFMAP: the tests of its last compare / compare_many
  * (src/metrics/prelude.rs:64-65 per compare of eval.rs:83-89) */
 int ce_ref_butteraugli_diffmap(ce_ref *ref, uint32_t first, uint32_t count, uint32_t block, float *out, size_t out_floats);
+/* the same as ce_batch_dssim_ssim_maps for the tests of a reference handle's last compare / compare_many that ran DSSIM */
+int ce_ref_dssim_ssim_maps(ce_ref *ref, uint32_t level, uint32_t first, uint32_t count, uint32_t block,
+                           float *maps, size_t maps_floats, double *ssim);
 void ce_ref_destroy(ce_ref *ref);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------ */
