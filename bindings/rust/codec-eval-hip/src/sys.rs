@@ -154,4 +154,5 @@ extern "C" {
     pub fn ce_debug_cbrt_sweep(ctx: *mut ce_ctx, first_bits: u32, count: u64, mismatches: *mut u64, slow_path: *mut u64) -> c_int;
     pub fn ce_debug_div_sweep(ctx: *mut ce_ctx, seed: u64, count: u64, mismatches: *mut u64) -> c_int;
     pub fn ce_debug_calibrate_traffic(ctx: *mut ce_ctx, bytes: usize) -> c_int;
+    pub fn ce_debug_dssim_walk_rows(b: *mut ce_batch, rows: u32) -> c_int;
 }

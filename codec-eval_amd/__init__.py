@@ -170,6 +170,7 @@ _PROTOTYPES = [
     ("ce_debug_cbrt_sweep", _i, [_vp, _u32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("ce_debug_div_sweep", _i, [_vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("ce_debug_calibrate_traffic", _i, [_vp, _sz]),
+    ("ce_debug_dssim_walk_rows", _i, [_vp, _u32]),
 ]
 ABI_SYMBOLS = [p[0] for p in _PROTOTYPES]
 
@@ -720,6 +721,10 @@ class Batch:
         self.ctx._check(lib().ce_debug_ssim2_planes(self._h, scale, which, channel, buf.ctypes.data, buf.size,
                                                      C.byref(w), C.byref(h)))
         return buf[: nplanes * w.value * h.value].reshape(nplanes, h.value, w.value).copy()
+
+    def debug_dssim_walk_rows(self, rows: int):
+        """Force the rows a wave of DSSIM's streaming kernels walks in later runs (0 = automatic, else 2, 4, .. 64)."""
+        self.ctx._check(lib().ce_debug_dssim_walk_rows(self._h, rows))
 
     def debug_averages(self, pair_index: int) -> np.ndarray:
         avg = np.zeros((6, 3, 6), np.float64)

@@ -1699,6 +1699,14 @@ int ce_debug_ssim2_limit_scales(ce_batch *b, int max_scales)
     return CE_OK;
 }
 
+int ce_debug_dssim_walk_rows(ce_batch *b, uint32_t rows)
+{
+    // ds_part holds a strip's partial sums per 2-row tile (dssim.hip: ds_blocks), so every allowed walk fits
+    if (!b || (rows != 0 && (rows < 2 || rows > 64 || (rows & (rows - 1)) != 0))) return CE_ERR_INVALID_ARG;
+    b->debug_ds_rows = rows;
+    return CE_OK;
+}
+
 int ce_debug_ssim2_averages(ce_batch *b, uint32_t pair_index, double *avg, int *n_scales)
 {
     if (!b || !avg || !b->ssim2_ready || pair_index >= b->max_pairs) return CE_ERR_INVALID_ARG;

@@ -195,6 +195,7 @@ struct ce_batch {
     float *ds_cells = nullptr;
     size_t ds_cells_cap = 0;
     uint32_t ds_blocks = 0;
+    uint32_t debug_ds_rows = 0;  // test hook (ce_debug_dssim_walk_rows): forced walk length of the streaming kernels, 0 = automatic
     ce_xcd_list ds_gwork[CE_DSSIM_SCALES];  // k_dssim_compare_stream's launch order, per level
     bool dssim_ready = false;
 

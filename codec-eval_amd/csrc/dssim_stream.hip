@@ -428,7 +428,7 @@ int ce_dssim_create_stream(ce_batch *b, int l, const uint8_t *d_refs, uint32_t n
     const uint32_t n_slots = n_refs_used + n_pairs;
     if (n_slots <= z0) return CE_OK;
     const uint32_t strips_ref = (d.w + 64 - 2 * CR_HALO_REF - 1) / (64 - 2 * CR_HALO_REF), strips = (d.w + CS_OUT - 1) / CS_OUT;
-    const uint32_t rows = stream_rows(strips, d.h, n_slots - z0);
+    const uint32_t rows = b->debug_ds_rows ? b->debug_ds_rows : stream_rows(strips, d.h, n_slots - z0);
     const uint32_t tiles = std::max(z0 < n_refs_used ? strips_ref : 0u, strips) * ((d.h + rows - 1) / rows);
 #define CE_CREATE_LAUNCH(NAME, U8, GRID, Z0)                                                                                        \
     CE_LAUNCH(ctx, NAME, (k_dssim_create_stream<U8>), GRID, dim3(CS_WAVES * 64), 0, d_refs, (const uint8_t *)b->d_tests,            \
@@ -446,7 +446,7 @@ int ce_dssim_compare_stream(ce_batch *b, int l, uint32_t n_pairs, float *level_m
     ce_ctx *ctx = b->ctx;
     const auto &d = b->ds[l];
     const lvl_geom lg{d.w, d.h, d.pitch, d.plane};
-    const uint32_t strips = (d.w + CS_OUT - 1) / CS_OUT, rows = stream_rows(strips, d.h, n_pairs);
+    const uint32_t strips = (d.w + CS_OUT - 1) / CS_OUT, rows = b->debug_ds_rows ? b->debug_ds_rows : stream_rows(strips, d.h, n_pairs);
     // Launch order (ce_plan.h: ce_plan_xcd_list): one key per row block, entries (row block * strips + strip, pair).  A
     // block's CS_WAVES waves take consecutive entries of one XCD class, and all entries of one (reference, row block) - its
     // strips, and on each strip the reference's distorted images one after the other - go to ONE class, so that the

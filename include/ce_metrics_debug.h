@@ -39,6 +39,10 @@ int ce_debug_div_sweep(ce_ctx *ctx, uint64_t seed, uint64_t count, uint64_t *mis
  * and 16 bytes per lane and writes it with 4 and 16 (kernels k_calib_read<W> / k_calib_write<W>), so a PMC pass can
  * measure FETCH_SIZE's / WRITE_SIZE's correction factor per access width (profiles/make_traffic.py). */
 int ce_debug_calibrate_traffic(ce_ctx *ctx, size_t bytes);
+/* DSSIM's streaming kernels walk `rows` rows per wave, picked from the batch size (dssim_stream.hip: stream_rows).  This
+ * forces the walk length of the create and compare streams of every level in later runs of `b`: rows = 0 is the automatic
+ * choice (the default), otherwise a power of two from 2 to 64; anything else is CE_ERR_INVALID_ARG. */
+int ce_debug_dssim_walk_rows(ce_batch *b, uint32_t rows);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,7 @@ import dssim_map_shim as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "ce_metrics.h")).read()
+DEBUG_HEADER = open(os.path.join(ROOT, "include", "ce_metrics_debug.h")).read()
 SYS = open(os.path.join(ROOT, "bindings", "rust", "codec-eval-hip", "src", "sys.rs")).read()
 NEW = {"ce_dssim_levels": 5, "ce_calculate_dssim_ssim_maps": 11, "ce_batch_dssim_ssim_maps": 8, "ce_ref_dssim_ssim_maps": 8}
 
@@ -31,6 +32,21 @@ def test_declared_everywhere_with_the_same_arity(ce):
     assert ce.DSSIM_MAX_LEVELS == 5 == len(S.WEIGHTS)
 
 
+def test_walk_rows_hook_is_declared_everywhere_with_the_same_arity(ce):
+    """ce_debug_dssim_walk_rows (the test hook that forces the streaming kernels' walk length) in the debug header, the
+    Rust declarations and the ctypes layer, with the Batch method the GPU tests call."""
+    name = "ce_debug_dssim_walk_rows"
+    c = re.search(r"\bint " + name + r"\(([^;]*?)\);", re.sub(r"/\*.*?\*/", "", DEBUG_HEADER, flags=re.S), flags=re.S)
+    r = re.search(r"pub fn " + name + r"\((.*?)\)\s*->\s*c_int;", SYS, flags=re.S)
+    assert c and r
+    assert [a.split()[-1].lstrip("*") for a in c.group(1).split(",")] == ["b", "rows"]
+    assert [a.split(":")[0].strip() for a in r.group(1).split(",")] == ["b", "rows"]
+    assert "uint32_t rows" in c.group(1) and "rows: u32" in r.group(1)
+    assert name in ce.ABI_SYMBOLS and hasattr(ce.lib(), name)
+    assert len(getattr(ce.lib(), name).argtypes) == 2
+    assert callable(getattr(ce.Batch, "debug_dssim_walk_rows", None))
+
+
 def test_null_handles_are_invalid_arguments(ce):
     L = ce.lib()
     a = np.zeros(16 * 16 * 3, np.uint8)
@@ -41,6 +57,8 @@ def test_null_handles_are_invalid_arguments(ce):
                                           maps.ctypes.data, maps.size) == ce.CE_ERR_INVALID_ARG
     assert L.ce_batch_dssim_ssim_maps(None, 0, 0, 1, 1, maps.ctypes.data, 256, lv.ctypes.data) == ce.CE_ERR_INVALID_ARG
     assert L.ce_ref_dssim_ssim_maps(None, 0, 0, 1, 1, maps.ctypes.data, 256, lv.ctypes.data) == ce.CE_ERR_INVALID_ARG
+    for rows in (0, 2, 64, 3, 128):  # a null batch is rejected whatever the walk length
+        assert L.ce_debug_dssim_walk_rows(None, rows) == ce.CE_ERR_INVALID_ARG
 
 
 @pytest.fixture(scope="module")

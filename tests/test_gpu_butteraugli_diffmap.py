@@ -264,3 +264,124 @@ def test_invalid_readouts(gpu_ctx, ce, workloads):
     assert L.ce_eval_batch(gpu_ctx._h, 1, pairs, ce.METRIC_BUTTERAUGLI, flags, 80.0, out) == ce.CE_ERR_INVALID_ARG
     assert L.ce_eval_pair(gpu_ctx._h, r_.ctypes.data, r_.size, t_.ctypes.data, t_.size, w, h, ce.METRIC_BUTTERAUGLI, flags, 80.0,
                           ctypes.byref(out[0])) == ce.CE_ERR_INVALID_ARG
+
+
+# Launch geometry the shapes below sit on (butteraugli.hip): front tiles FT = 32 x 32; the row blur's blocks (gh3 of
+# ce_launch_butteraugli) 256 columns x 8 * BH_TILES = 32 rows; the fused column / blur tiles (k_ba_blur_v_split) 64 x 32;
+# the Malta tiles MT = 64 columns x 32 rows.  The half-resolution level is ((w + 1) / 2, (h + 1) / 2) and exists when it
+# is at least 8 x 8 (ba_levels).  Entries: (w, h, the half level's (w, h) or None for one level) - the test asserts the
+# third field, so that a comment here cannot claim a level that is not built.
+BA_EDGE_SHAPES = [
+    (8, 8, None),  # the 8 x 8 minimum
+    (14, 40, None), (15, 41, (8, 21)), (16, 42, (8, 21)),  # one / two levels in w
+    (40, 14, None), (41, 15, (21, 8)), (42, 16, (21, 8)),  # ... and in h
+    (31, 31, (16, 16)), (32, 32, (16, 16)), (33, 33, (17, 17)),  # the front tiles and the 32-row blocks, both axes
+    (61, 61, (31, 31)),  # half level one under the front tiles and the 32-row blocks
+    (63, 63, (32, 32)), (64, 64, (32, 32)), (65, 65, (33, 33)),  # the 64-column fused-blur and Malta tiles; half level on /
+    # over the front tiles and the 32-row blocks
+    (125, 20, (63, 10)), (127, 16, (64, 8)), (129, 17, (65, 9)),  # half level under / on / over the 64-column tiles
+    (255, 63, (128, 32)), (256, 64, (128, 32)), (257, 65, (129, 33)),  # the row blur's 256-column block, 2 x 32 rows
+    (509, 15, (255, 8)), (511, 16, (256, 8)), (513, 17, (257, 9)),  # half level under / on / over the 256-column block
+    (40, 125, (20, 63)), (70, 129, (35, 65)),  # half level one under / over 64 rows
+    (256, 10, None), (257, 11, None), (100, 12, None), (90, 13, None),  # one level, heights under the 33-tap halo
+    (1000, 9, None),  # a wide one-level strip
+    (9, 700, None),  # a tall one-level strip
+    (768, 512, (384, 256)),  # the headline shape
+]
+
+
+def ba_half_level(w, h):
+    """ce_batch's Butteraugli levels: the half-resolution (w, h), or None where it would be under 8 x 8."""
+    hw, hh = (w + 1) // 2, (h + 1) // 2
+    return (hw, hh) if hw >= 8 and hh >= 8 else None
+
+
+def _first_difference(got, want):
+    bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
+    if bad.size == 0:
+        return None
+    y, x = bad[0].tolist()
+    return {"pixels": len(bad), "first": [y, x], "got": float(got[y, x]), "want": float(want[y, x])}
+
+
+def _edge_batch(workloads, w, h):
+    """2 references x 2 distorted images, the second of each with 4:2:0 chroma."""
+    refs = [workloads.make_reference(w, h, 500 + 7 * w + h + r) for r in range(2)]
+    pairs = [(r, workloads.distort(refs[r], 35 + 40 * k, k == 1)) for r in range(2) for k in range(2)]
+    return refs, pairs
+
+
+def _run_edge_batch(ce, ctx, w, h, refs, pairs):
+    b = ce.Batch(ctx, w, h, len(refs), len(pairs))
+    for r, ref in enumerate(refs):
+        b.set_reference(r, ref)
+    for i, (r, t) in enumerate(pairs):
+        b.set_test(i, r, t)
+    s = b.run(len(pairs), ce.MetricConfig(butteraugli=True), butteraugli_diffmap=True)
+    assert all(x.status == 0 for x in s)
+    out = ([x.butteraugli for x in s], b.butteraugli_pnorm3(len(pairs)), b.butteraugli_diffmaps(0, len(pairs)))
+    b.close()
+    return out
+
+
+@pytest.fixture(scope="module")
+def serial_ctx(ce):
+    """A second context with serial profiling: no second stream for the half level (two_streams) and no metric fork."""
+    ctx = ce.Context(0)
+    ctx.prof_enable(True, serial=True)
+    yield ctx
+    ctx.prof_enable(False)
+    ctx.close()
+
+
+@pytest.mark.parametrize("w,h,half", BA_EDGE_SHAPES)
+def test_edge_shapes_map_is_the_oracle_map_bit_for_bit(gpu_ctx, serial_ctx, ce, workloads, shim, w, h, half):
+    """Every pair's map is the oracle's (device switches on) pixel for pixel, its maximum is the score and its f64 p-norm
+    the device's 3-norm; the serial schedule gives the same maps and scores bit for bit."""
+    assert ba_half_level(w, h) == half, (w, h, ba_half_level(w, h), half)
+    refs, pairs = _edge_batch(workloads, w, h)
+    scores, p3, maps = _run_edge_batch(ce, gpu_ctx, w, h, refs, pairs)
+    assert maps.shape == (len(pairs), h, w) and maps.dtype == np.float32
+    shim.set_device_switches(True)
+    try:
+        want = [shim.diffmap(refs[r], t, w, h) for r, t in pairs]
+    finally:
+        shim.set_device_switches(False)
+    for i in range(len(pairs)):
+        assert _first_difference(maps[i], want[i]) is None, (w, h, i, _first_difference(maps[i], want[i]))
+        assert float(maps[i].max()) == scores[i], (w, h, i)
+        assert abs(S.pnorm3(maps[i]) - p3[i]) <= 1e-12 * p3[i], (w, h, i)
+    s_scores, s_p3, s_maps = _run_edge_batch(ce, serial_ctx, w, h, refs, pairs)
+    for i in range(len(pairs)):
+        assert _first_difference(s_maps[i], maps[i]) is None, ("serial", w, h, i, _first_difference(s_maps[i], maps[i]))
+    assert s_scores == scores and s_p3.tobytes() == p3.tobytes()
+
+
+def test_batch_past_the_two_stream_limit_has_the_one_pair_maps(gpu_ctx, ce, workloads):
+    """257 x 129 x 128 pairs = 4.24e6 pixels, over the 4e6 under which the half level gets a stream of its own: the batch
+    runs both levels on one stream, each pair's map is its one-pair call's (two streams) bit for bit."""
+    w, h, n_refs, per_ref = 257, 129, 4, 32
+    assert n_refs * per_ref * w * h > 4e6
+    b = ce.Batch(gpu_ctx, w, h, n_refs, n_refs * per_ref)
+    refs, pairs = [], []
+    for r in range(n_refs):
+        refs.append(workloads.make_reference(w, h, 620 + r))
+        b.set_reference(r, refs[r])
+        for k in range(per_ref):
+            t = workloads.distort(refs[r], 20 + 2 * k, k % 3 == 0)
+            b.set_test(len(pairs), r, t)
+            pairs.append((r, t))
+    s = b.run(len(pairs), ce.MetricConfig(butteraugli=True), butteraugli_diffmap=True)
+    maps = b.butteraugli_diffmaps(0, len(pairs))
+    b.close()
+    one = ce.Batch(gpu_ctx, w, h, 1, 1)
+    try:
+        for i, (r, t) in enumerate(pairs):
+            one.set_reference(0, refs[r])
+            one.set_test(0, 0, t)
+            s1 = one.run(1, ce.MetricConfig(butteraugli=True), butteraugli_diffmap=True)
+            m1 = one.butteraugli_diffmaps(0, 1)[0]
+            assert _first_difference(maps[i], m1) is None, (i, _first_difference(maps[i], m1))
+            assert s[i].butteraugli == s1[0].butteraugli, i
+    finally:
+        one.close()

@@ -75,8 +75,8 @@ def _grid(ce, ctx, workloads, w, h, n_refs, per_ref, seed=170):
 
 
 def test_batch_maps_are_the_one_pair_maps(ce, gpu_ctx, workloads):
-    """512 x 512, 64 pairs: the compare kernel walks its longest strips; pair i's maps and scores of every level are its
-    one-pair call's."""
+    """512 x 512, 64 pairs: the compare kernel walks 32 rows at level 0 (a one-pair call walks 4); pair i's maps and scores
+    of every level are its one-pair call's bit for bit."""
     w = h = 512
     b, pairs = _grid(ce, gpu_ctx, workloads, w, h, 4, 16)
     s = b.run(64, ce.MetricConfig(dssim=True))
@@ -88,9 +88,8 @@ def test_batch_maps_are_the_one_pair_maps(ce, gpu_ctx, workloads):
         assert len(maps) == len(levels)
         for l, m in enumerate(maps):
             assert got[l][0][i].tobytes() == m.map.tobytes(), (i, l, _first_difference(got[l][0][i], m.map))
-            # the f64 grouping of DSSIM's sums depends on the batch size (out of scope here): ulps, not more
-            assert abs(got[l][1][i] - m.ssim) <= 1e-12, (i, l)
-        assert abs(s[i].dssim - score) <= 1e-9 * max(score, 1e-6), i
+            assert got[l][1][i] == m.ssim, (i, l, got[l][1][i], m.ssim)
+        assert s[i].dssim == score, (i, s[i].dssim, score)
 
 
 @pytest.mark.parametrize("w,h", [(200, 136), (129, 65), (768, 512), (9, 301)])
@@ -281,3 +280,96 @@ def test_cpp_mirror(ce, gpu_ctx, workloads, tmp_path):
         assert (int(lw), int(lh)) == (m.map.shape[1], m.map.shape[0])
         assert float.fromhex(ssim) == m.ssim
         assert (out_dir / f"level{l}.f32").read_bytes() == m.map.tobytes()
+
+
+WALKS = (2, 4, 8, 16, 32, 64)  # every walk length stream_rows can pick (dssim_stream.hip)
+# heights one row under / over one, two and three walks of the longer lengths, at a one-strip and a two-strip width (60
+# output columns per strip): the top block (i0 = -1), the surplus steps at the bottom and a last block of 1 .. r rows
+WALK_SHAPES = sorted({(w, h) for w in (61, 121) for r in (8, 16, 32, 64) for h in (r - 1, r + 1, 2 * r - 1, 3 * r + 1)})
+
+
+def _walk_batch(ce, ctx, workloads, w, h):
+    """2 references x 2 distorted images (the second with 4:2:0 chroma)."""
+    b = ce.Batch(ctx, w, h, 2, 4)
+    pairs = []
+    for r in range(2):
+        ref = workloads.make_reference(w, h, 700 + 3 * w + h + r)
+        b.set_reference(r, ref)
+        for k in range(2):
+            t = workloads.distort(ref, 30 + 45 * k, k == 1)
+            b.set_test(len(pairs), r, t)
+            pairs.append((ref, t))
+    return b, pairs
+
+
+def _set_tests(b, pairs, identical=False):
+    for i, (ref, t) in enumerate(pairs):
+        b.set_test(i, i // 2, ref if identical else t)
+
+
+@pytest.mark.parametrize("w,h", DSSIM_SHAPES + WALK_SHAPES)
+def test_every_walk_length_gives_the_oracle_maps(ce, gpu_ctx, workloads, shim, w, h):
+    """Forced walk lengths (ce_debug_dssim_walk_rows) of the create and compare streams: at every level every pair's map is
+    the oracle's bit for bit, and its per-level ssim and DSSIM score are the same bits for all six walks."""
+    b, pairs = _walk_batch(ce, gpu_ctx, workloads, w, h)
+    want = [shim.maps(ref, t, w, h) for ref, t in pairs]
+    n_levels = len(ce.dssim_levels(w, h))
+    first = None
+    try:
+        for rows in WALKS:
+            b.debug_dssim_walk_rows(rows)
+            # identical pairs first (every map 1.0), so that a pixel the walk does not store cannot keep the last walk's value
+            _set_tests(b, pairs, identical=True)
+            assert all(x.dssim == 0.0 for x in b.run(len(pairs), ce.MetricConfig(dssim=True))), (w, h, rows)
+            _set_tests(b, pairs)
+            s = b.run(len(pairs), ce.MetricConfig(dssim=True))
+            got = [b.dssim_ssim_maps(l, 0, len(pairs)) for l in range(n_levels)]
+            for i, (want_d, want_levels) in enumerate(want):
+                assert len(want_levels) == n_levels
+                for l, (wm, ws) in enumerate(want_levels):
+                    diff = _first_difference(got[l][0][i], wm)
+                    assert diff is None, (w, h, rows, i, l, diff)
+                    assert abs(got[l][1][i] - ws) <= 1e-12, (w, h, rows, i, l, got[l][1][i], ws)
+                assert abs(s[i].dssim - want_d) <= 1e-9 * max(abs(want_d), 1e-6), (w, h, rows, i)
+            bits = ([x.dssim for x in s], [g[1].tobytes() for g in got])
+            if first is None:
+                first = bits
+            assert bits == first, (w, h, rows, "scores differ from the 2-row walk's", [x.dssim for x in s], first[0])
+    finally:
+        b.close()
+
+
+def test_walk_rows_hook_rejects_other_lengths(ce, gpu_ctx, workloads):
+    L = ce.lib()
+    b, pairs = _walk_batch(ce, gpu_ctx, workloads, 61, 33)
+    for rows in (1, 3, 6, 48, 65, 128, 1 << 31):
+        assert L.ce_debug_dssim_walk_rows(b._h, rows) == ce.CE_ERR_INVALID_ARG, rows
+    auto = b.run(4, ce.MetricConfig(dssim=True))
+    b.debug_dssim_walk_rows(64)
+    forced = b.run(4, ce.MetricConfig(dssim=True))
+    b.debug_dssim_walk_rows(0)  # back to the automatic choice
+    again = b.run(4, ce.MetricConfig(dssim=True))
+    b.close()
+    assert [x.dssim for x in auto] == [x.dssim for x in forced] == [x.dssim for x in again]
+
+
+def test_natural_64_row_walk_is_the_one_pair_walk(ce, gpu_ctx, workloads):
+    """Without the hook: at 768 x 512 (13 strips of 60 columns, 8 blocks of 64 rows) 80 pairs make 13 * 8 * 80 = 8320
+    waves, at least the 8192 at which stream_rows keeps 64 rows for level 0, where a one-pair call walks 4.  Every pair's
+    maps, per-level ssim and score are its one-pair call's bit for bit."""
+    # stream_rows' threshold is the A/B knob CE_STREAM_MIN_WAVES (default 8192): set, this batch could walk fewer rows
+    assert "CE_STREAM_MIN_WAVES" not in os.environ, "unset CE_STREAM_MIN_WAVES: this test needs stream_rows' default"
+    w, h, n_refs, per_ref = 768, 512, 4, 20
+    n = n_refs * per_ref
+    assert 13 * 8 * n >= 8192
+    b, pairs = _grid(ce, gpu_ctx, workloads, w, h, n_refs, per_ref, seed=730)
+    s = b.run(n, ce.MetricConfig(dssim=True))
+    levels = ce.dssim_levels(w, h)
+    got = [b.dssim_ssim_maps(l, 0, n) for l in range(len(levels))]
+    b.close()
+    for i, (ref, t) in enumerate(pairs):
+        score, maps = gpu_ctx.calculate_dssim_with_ssim_maps(ref, t, w, h)
+        for l, m in enumerate(maps):
+            assert got[l][0][i].tobytes() == m.map.tobytes(), (i, l, _first_difference(got[l][0][i], m.map))
+            assert got[l][1][i] == m.ssim, (i, l, got[l][1][i], m.ssim)
+        assert s[i].dssim == score, (i, s[i].dssim, score)

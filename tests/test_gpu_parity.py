@@ -124,7 +124,8 @@ def test_ssim2_reference_cases(gpu_ctx, oracle, ce):
 
 
 def test_ssim2_planes_bit_exact(gpu_ctx, oracle, ce, workloads):
-    """Stage outputs of level 0 against the oracle's building blocks: every plane identical."""
+    """Stage outputs of levels 0 and 1 against the oracle's building blocks: every linear RGB and XYB plane identical.  The
+    row-blurred streams (debug_planes(scale, 4, c)) of every scale are test_gpu_ssim2_row_streams.py's."""
     w, h = 200, 136
     ref = workloads.make_reference(w, h, 11)
     test = workloads.distort(ref, 70)
@@ -137,7 +138,7 @@ def test_ssim2_planes_bit_exact(gpu_ctx, oracle, ce, workloads):
     b.run(1, ce.MetricConfig.ssimulacra2_only())
     assert np.array_equal(b.debug_planes(0, 2), oracle.ssim2_xyb_positive(lin_r))
     assert np.array_equal(b.debug_planes(0, 3), oracle.ssim2_xyb_positive(lin_t))
-    # level 1: the 2x2 box of linear RGB, its XYB planes, and the five row-blurred streams of channel Y
+    # level 1: the 2x2 box of linear RGB and its XYB planes
     b.debug_limit_scales(2)
     b.run(1, ce.MetricConfig.ssimulacra2_only())
     lin1_r, lin1_t = oracle.ssim2_downscale(lin_r), oracle.ssim2_downscale(lin_t)
@@ -407,7 +408,9 @@ def test_dssim_reference_cases(gpu_ctx, oracle, ce):
 DSSIM_SHAPES = [(1, 1), (3, 2), (7, 9), (8, 8), (15, 17), (20, 20), (64, 64), (100, 100), (101, 77), (255, 129), (768, 512), (512, 768),
                 (33, 33), (65, 31), (32, 96),  # one pixel over / under the 32 x 32 tile (CE_DSSIM_*=tile kernels)
                 # the streaming kernels' strips: 60 output columns per wave for a distorted image / a pair, 56 for a reference,
-                # walks of 2 .. 64 rows - one column / row under, on and over their edges, and degenerate strips
+                # one column / row under, on and over their edges, and degenerate strips.  A one-pair call's compare stream
+                # walks 2 rows per wave at these shapes (4 at 768 x 512 / 512 x 768): test_gpu_dssim_ssim_maps.py forces
+                # every walk length from 2 to 64 rows
                 (59, 9), (60, 10), (61, 33), (62, 3), (119, 66), (120, 64), (121, 65), (56, 8), (57, 130), (112, 5), (113, 17),
                 (300, 2), (2, 300), (1, 70), (70, 1), (4, 4), (5, 63)]
 
