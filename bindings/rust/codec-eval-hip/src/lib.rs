@@ -179,6 +179,43 @@ impl HipMetrics {
         }
         Ok((score, out))
     }
+
+    /// `calculate_ssimulacra2` (src/metrics/ssimulacra2.rs:59) with everything the score pools kept: the score, the 108
+    /// pooled features (`[scale][channel][6]`: mean and 4-norm of the SSIM, artifact and detail-lost maps; NaN past the
+    /// image's scales) and one `Ssim2Maps` per scale, scale 0 at full resolution.
+    pub fn calculate_ssimulacra2_with_maps(&mut self, reference: &[u8], test: &[u8], width: usize, height: usize)
+                                           -> Result<(f64, [f64; sys::CE_SSIM2_MAX_SCALES * 18], Vec<Ssim2Maps>), HipError> {
+        let (mut n, mut sw, mut sh) = (0u32, [0u32; sys::CE_SSIM2_MAX_SCALES], [0u32; sys::CE_SSIM2_MAX_SCALES]);
+        if width > 0 && height > 0 && width <= u32::MAX as usize && height <= u32::MAX as usize {
+            unsafe { sys::ce_ssimulacra2_scales(width as u32, height as u32, &mut n, sw.as_mut_ptr(), sh.as_mut_ptr()) };
+        }
+        let sizes: Vec<(usize, usize)> = (0..n as usize).map(|s| (sw[s] as usize, sh[s] as usize)).collect();
+        let mut maps = vec![0.0f32; sizes.iter().map(|(w, h)| 9 * w * h).sum()];
+        let mut features = [0.0f64; sys::CE_SSIM2_MAX_SCALES * 18];
+        let mut score = 0.0f64;
+        let rc = unsafe {
+            sys::ce_calculate_ssimulacra2_maps(self.ctx, reference.as_ptr(), reference.len(), test.as_ptr(), test.len(), width,
+                                               height, &mut score, features.as_mut_ptr(), maps.as_mut_ptr(), maps.len())
+        };
+        self.check(rc, width as u32, height as u32, test.len())?;
+        let mut out = Vec::with_capacity(sizes.len());
+        let mut off = 0;
+        for &(w, h) in &sizes {
+            out.push(Ssim2Maps { width: w, height: h, maps: maps[off..off + 9 * w * h].to_vec() });
+            off += 9 * w * h;
+        }
+        Ok((score, features, out))
+    }
+}
+
+/// One scale of SSIMULACRA2's per-pixel error terms (ssim_map / edge_diff_map of the lineage behind
+/// src/metrics/ssimulacra2.rs:96): `maps` is `[channel 3][kind 3][height][width]`, kinds `CE_SSIM2_MAP_SSIM`,
+/// `CE_SSIM2_MAP_ARTIFACT`, `CE_SSIM2_MAP_DETAIL_LOST`.
+#[derive(Clone, Debug)]
+pub struct Ssim2Maps {
+    pub width: usize,
+    pub height: usize,
+    pub maps: Vec<f32>,
 }
 
 /// dssim-core's `SsimMap` (re-exported at src/metrics/prelude.rs:45): one scale's per-pixel SSIM image, row-major

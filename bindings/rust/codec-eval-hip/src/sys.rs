@@ -32,8 +32,13 @@ pub const CE_METRIC_BUTTERAUGLI: u32 = 1 << 2;
 pub const CE_METRIC_PSNR: u32 = 1 << 3;
 pub const CE_FLAG_XYB_ROUNDTRIP: u32 = 1 << 0;
 pub const CE_FLAG_BUTTERAUGLI_DIFFMAP: u32 = 1 << 1;
+pub const CE_FLAG_SSIMULACRA2_MAPS: u32 = 1 << 2;
 pub const CE_DEFAULT_INTENSITY_TARGET: c_float = 80.0;
 pub const CE_DSSIM_MAX_LEVELS: usize = 5;
+pub const CE_SSIM2_MAX_SCALES: usize = 6;
+pub const CE_SSIM2_MAP_SSIM: u32 = 0;
+pub const CE_SSIM2_MAP_ARTIFACT: u32 = 1;
+pub const CE_SSIM2_MAP_DETAIL_LOST: u32 = 2;
 
 pub const CE_PIXEL_RGB8: c_int = 0;
 pub const CE_PIXEL_RGBA8: c_int = 1;
@@ -88,6 +93,10 @@ extern "C" {
     pub fn ce_calculate_dssim_ssim_maps(ctx: *mut ce_ctx, reference: *const u8, reference_len: usize, test: *const u8, test_len: usize,
                                         width: usize, height: usize, dssim: *mut c_double, level_ssim: *mut c_double,
                                         maps: *mut c_float, maps_floats: usize) -> c_int;
+    pub fn ce_ssimulacra2_scales(width: u32, height: u32, n_scales: *mut u32, scale_w: *mut u32, scale_h: *mut u32) -> c_int;
+    pub fn ce_calculate_ssimulacra2_maps(ctx: *mut ce_ctx, reference: *const u8, reference_len: usize, test: *const u8, test_len: usize,
+                                         width: usize, height: usize, score: *mut c_double, features: *mut c_double,
+                                         maps: *mut c_float, maps_floats: usize) -> c_int;
     pub fn ce_xyb_roundtrip(ctx: *mut ce_ctx, rgb: *const u8, rgb_len: usize, width: usize, height: usize, out: *mut u8) -> c_int;
     pub fn ce_rgb8_to_dssim_image(ctx: *mut ce_ctx, rgb: *const u8, rgb_len: usize, width: usize, height: usize,
                                   out_rgba_f32: *mut c_float) -> c_int;
@@ -127,6 +136,8 @@ extern "C" {
                                         out_floats: usize) -> c_int;
     pub fn ce_batch_dssim_ssim_maps(b: *mut ce_batch, level: u32, first: u32, count: u32, block: u32, maps: *mut c_float,
                                     maps_floats: usize, ssim: *mut c_double) -> c_int;
+    pub fn ce_batch_ssimulacra2_maps(b: *mut ce_batch, scale: u32, channel: u32, kind: u32, first: u32, count: u32, block: u32,
+                                     maps: *mut c_float, maps_floats: usize, norms: *mut c_double) -> c_int;
     pub fn ce_ref_create(ctx: *mut ce_ctx, reference: *const u8, reference_len: usize, width: u32, height: u32, flags: u32,
                          out: *mut *mut ce_ref) -> c_int;
     pub fn ce_ref_compare(r: *mut ce_ref, test: *const u8, test_len: usize, metric_mask: u32, intensity_target: c_float,
@@ -138,6 +149,8 @@ extern "C" {
                                       out_floats: usize) -> c_int;
     pub fn ce_ref_dssim_ssim_maps(r: *mut ce_ref, level: u32, first: u32, count: u32, block: u32, maps: *mut c_float,
                                   maps_floats: usize, ssim: *mut c_double) -> c_int;
+    pub fn ce_ref_ssimulacra2_maps(r: *mut ce_ref, scale: u32, channel: u32, kind: u32, first: u32, count: u32, block: u32,
+                                   maps: *mut c_float, maps_floats: usize, norms: *mut c_double) -> c_int;
     pub fn ce_ref_destroy(r: *mut ce_ref);
     pub fn ce_prof_enable(ctx: *mut ce_ctx, on: c_int) -> c_int;
     pub fn ce_prof_filter(ctx: *mut ce_ctx, substring: *const c_char) -> c_int;

@@ -33,9 +33,12 @@ CE_OK, CE_ERR_DIM_MISMATCH, CE_ERR_BAD_LENGTH, CE_ERR_TOO_SMALL, CE_ERR_BACKEND,
 METRIC_DSSIM, METRIC_SSIMULACRA2, METRIC_BUTTERAUGLI, METRIC_PSNR = 1, 2, 4, 8
 FLAG_XYB_ROUNDTRIP = 1
 FLAG_BUTTERAUGLI_DIFFMAP = 1 << 1
+FLAG_SSIMULACRA2_MAPS = 1 << 2
 PIXEL_RGB8, PIXEL_RGBA8, PIXEL_RGB16_10BIT, PIXEL_RGBA16_10BIT = 0, 1, 2, 3
 DEFAULT_INTENSITY_TARGET = 80.0
 DSSIM_MAX_LEVELS = 5  # CE_DSSIM_MAX_LEVELS
+SSIM2_MAX_SCALES = 6  # CE_SSIM2_MAX_SCALES
+SSIM2_MAP_SSIM, SSIM2_MAP_ARTIFACT, SSIM2_MAP_DETAIL_LOST = 0, 1, 2  # enum ce_ssim2_map
 
 _STATUS_NAMES = {
     CE_ERR_DIM_MISMATCH: "DimensionMismatch",
@@ -121,6 +124,8 @@ _PROTOTYPES = [
     ("ce_calculate_butteraugli_diffmap", _i, [_vp, _u8p, _sz, _u8p, _sz, _sz, _sz, _f32, _dp, _vp]),
     ("ce_dssim_levels", _i, [_u32, _u32, C.POINTER(_u32), _vp, _vp]),
     ("ce_calculate_dssim_ssim_maps", _i, [_vp, _u8p, _sz, _u8p, _sz, _sz, _sz, _dp, _vp, _vp, _sz]),
+    ("ce_ssimulacra2_scales", _i, [_u32, _u32, C.POINTER(_u32), _vp, _vp]),
+    ("ce_calculate_ssimulacra2_maps", _i, [_vp, _u8p, _sz, _u8p, _sz, _sz, _sz, _dp, _vp, _vp, _sz]),
     ("ce_xyb_roundtrip", _i, [_vp, _u8p, _sz, _sz, _sz, _u8p]),
     ("ce_rgb8_to_dssim_image", _i, [_vp, _u8p, _sz, _sz, _sz, _vp]),
     ("ce_eval_pair", _i, [_vp, _u8p, _sz, _u8p, _sz, _u32, _u32, _u32, _u32, _f32, C.POINTER(CeScores)]),
@@ -149,12 +154,14 @@ _PROTOTYPES = [
     ("ce_batch_butteraugli_pnorm3", _i, [_vp, _u32, _dp]),
     ("ce_batch_butteraugli_diffmap", _i, [_vp, _u32, _u32, _u32, _vp, _sz]),
     ("ce_batch_dssim_ssim_maps", _i, [_vp, _u32, _u32, _u32, _u32, _vp, _sz, _vp]),
+    ("ce_batch_ssimulacra2_maps", _i, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp]),
     ("ce_ref_create", _i, [_vp, _u8p, _sz, _u32, _u32, _u32, C.POINTER(_vp)]),
     ("ce_ref_compare", _i, [_vp, _u8p, _sz, _u32, _f32, C.POINTER(CeScores)]),
     ("ce_ref_compare_many", _i, [_vp, C.POINTER(_u8p), C.POINTER(_sz), _u32, _u32, _f32, C.POINTER(CeScores)]),
     ("ce_ref_stats", _i, [_vp, C.POINTER(_u32 * 3)]),
     ("ce_ref_butteraugli_diffmap", _i, [_vp, _u32, _u32, _u32, _vp, _sz]),
     ("ce_ref_dssim_ssim_maps", _i, [_vp, _u32, _u32, _u32, _u32, _vp, _sz, _vp]),
+    ("ce_ref_ssimulacra2_maps", _i, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp]),
     ("ce_ref_destroy", None, [_vp]),
     ("ce_prof_enable", _i, [_vp, _i]),
     ("ce_prof_filter", _i, [_vp, C.c_char_p]),
@@ -370,6 +377,34 @@ def _read_ssim_maps(ctx: "Context", fn, handle, width: int, height: int, level: 
     return maps, ssim
 
 
+def ssimulacra2_scales(width: int, height: int) -> List[Tuple[int, int]]:
+    """(w_s, h_s) of SSIMULACRA2's scales: a scale exists while its parent is at least 8 x 8 and is the parent halved with
+    ceiling, at most SSIM2_MAX_SCALES (none below 8 x 8)."""
+    n, sw, sh = _u32(), (_u32 * SSIM2_MAX_SCALES)(), (_u32 * SSIM2_MAX_SCALES)()
+    L = lib()
+    rc = L.ce_ssimulacra2_scales(width, height, C.byref(n), sw, sh)
+    if rc != CE_OK:
+        _raise(rc, (L.ce_last_error(None) or b"").decode())
+    return [(int(sw[s]), int(sh[s])) for s in range(n.value)]
+
+
+def _read_ssim2_maps(ctx: "Context", fn, handle, width: int, height: int, scale: int, channel: int, kind: int, first: int,
+                     count: int, block: int, maps: bool = True):
+    """(maps float32 [count, ceil(h_s / block), ceil(w_s / block)] or None, norms float64 [count, 2]) through
+    ce_batch_ssimulacra2_maps / ce_ref_ssimulacra2_maps."""
+    if block < 1:
+        raise CodecEvalError(CE_ERR_INVALID_ARG, "block must be 1 or a power of two up to 64")
+    scales = ssimulacra2_scales(width, height) if width and height else []
+    if not 0 <= scale < len(scales):
+        raise CodecEvalError(CE_ERR_INVALID_ARG, f"SSIMULACRA2 scale {scale} of {len(scales)}")
+    w, h = scales[scale]
+    m = np.empty((count, -(-h // block), -(-w // block)), np.float32) if maps else None
+    norms = np.empty((count, 2), np.float64)
+    ctx._check(fn(handle, scale, channel, kind, first, count, block, m.ctypes.data if maps else None, m.size if maps else 0,
+                  norms.ctypes.data))
+    return m, norms
+
+
 @dataclass
 class MetricResult:
     dssim: Optional[float] = None
@@ -510,6 +545,23 @@ class Context:
             out.append(SsimMap(maps[off:off + w * h].reshape(h, w), float(ssim[l])))
             off += w * h
         return score.value, out
+
+    def calculate_ssimulacra2_with_maps(self, reference, test, width: int, height: int):
+        """calculate_ssimulacra2 with everything the score pools kept: (the score, features float64 [6, 3, 6] - per scale
+        and XYB channel the means and 4-norms of the SSIM, artifact and detail-lost maps, NaN past the image's scales -,
+        one float32 [3 channels, 3 kinds, h_s, w_s] array per scale, kinds in SSIM2_MAP_* order)."""
+        r, t = _buf(reference), _buf(test)
+        scales = ssimulacra2_scales(width, height) if width and height else []
+        maps = np.empty(9 * sum(w * h for w, h in scales), np.float32)
+        features = np.empty((SSIM2_MAX_SCALES, 3, 6), np.float64)
+        score = C.c_double()
+        self._check(lib().ce_calculate_ssimulacra2_maps(self._h, r.ctypes.data, r.size, t.ctypes.data, t.size, width, height,
+                                                        C.byref(score), features.ctypes.data, maps.ctypes.data, maps.size))
+        out, off = [], 0
+        for w, h in scales:
+            out.append(maps[off:off + 9 * w * h].reshape(3, 3, h, w))
+            off += 9 * w * h
+        return score.value, features, out
 
     def xyb_roundtrip(self, rgb, width: int, height: int) -> np.ndarray:
         """xyb_roundtrip, src/metrics/xyb.rs:225."""
@@ -676,16 +728,17 @@ class Batch:
         return int(lib().ce_batch_test_slab(self._h))
 
     def run(self, n_pairs: int, config: MetricConfig, intensity_target: float = DEFAULT_INTENSITY_TARGET,
-            butteraugli_diffmap: bool = False) -> List[CeScores]:
-        """butteraugli_diffmap=True: also keep every pair's Butteraugli diffmap for butteraugli_diffmaps()."""
+            butteraugli_diffmap: bool = False, ssimulacra2_maps: bool = False) -> List[CeScores]:
+        """butteraugli_diffmap=True: also keep every pair's Butteraugli diffmap for butteraugli_diffmaps();
+        ssimulacra2_maps=True: every pair's SSIMULACRA2 error maps for ssimulacra2_maps()."""
         out = (CeScores * n_pairs)()
-        flags = config.flags | (FLAG_BUTTERAUGLI_DIFFMAP if butteraugli_diffmap else 0)
+        flags = config.flags | (FLAG_BUTTERAUGLI_DIFFMAP if butteraugli_diffmap else 0) | (FLAG_SSIMULACRA2_MAPS if ssimulacra2_maps else 0)
         self.ctx._check(lib().ce_batch_run(self._h, n_pairs, config.mask, flags, intensity_target, out))
         return list(out)
 
     def launch(self, n_pairs: int, config: MetricConfig, intensity_target: float = DEFAULT_INTENSITY_TARGET,
-               butteraugli_diffmap: bool = False):
-        flags = config.flags | (FLAG_BUTTERAUGLI_DIFFMAP if butteraugli_diffmap else 0)
+               butteraugli_diffmap: bool = False, ssimulacra2_maps: bool = False):
+        flags = config.flags | (FLAG_BUTTERAUGLI_DIFFMAP if butteraugli_diffmap else 0) | (FLAG_SSIMULACRA2_MAPS if ssimulacra2_maps else 0)
         self.ctx._check(lib().ce_batch_launch(self._h, n_pairs, config.mask, flags, intensity_target))
 
     def collect(self, n_pairs: int) -> List[CeScores]:
@@ -709,6 +762,15 @@ class Batch:
         (maps, float32 [count, ceil(h_l / block), ceil(w_l / block)], ssim, float64 [count]).  block = 1 is the full map, a
         power of two up to 64 the minimum over each block x block cell."""
         return _read_ssim_maps(self.ctx, lib().ce_batch_dssim_ssim_maps, self._h, self.width, self.height, level, first, count, block)
+
+    def ssimulacra2_maps(self, scale: int, channel: int, kind: int, first: int, count: int, block: int = 1, maps: bool = True):
+        """SSIMULACRA2's map `kind` (SSIM2_MAP_*) of XYB `channel` at `scale` for pairs [first, first + count) of the last
+        run / launch: (maps, float32 [count, ceil(h_s / block), ceil(w_s / block)], norms, float64 [count, 2] - the map's
+        mean and 4-norm as the score pooled them).  block = 1 is the full map, a power of two up to 64 the maximum over each
+        block x block cell.  The maps need ssimulacra2_maps=True at launch; maps=False reads the norms alone (maps None),
+        which every launch with SSIMULACRA2 leaves."""
+        return _read_ssim2_maps(self.ctx, lib().ce_batch_ssimulacra2_maps, self._h, self.width, self.height, scale, channel, kind,
+                                first, count, block, maps)
 
     # -- test hooks
     def debug_limit_scales(self, n: int):
@@ -737,11 +799,12 @@ class ReferenceHandle:
     """Ssimulacra2Reference::{new, compare} (crates/codec-iter/src/eval.rs:138-149, 83-89)."""
 
     def __init__(self, ctx: Context, reference, width: int, height: int, xyb_roundtrip: bool = False,
-                 butteraugli_diffmap: bool = False):
+                 butteraugli_diffmap: bool = False, ssimulacra2_maps: bool = False):
         self.ctx, self.width, self.height = ctx, width, height
         r = _buf(reference)
         self._h = C.c_void_p()
-        flags = (FLAG_XYB_ROUNDTRIP if xyb_roundtrip else 0) | (FLAG_BUTTERAUGLI_DIFFMAP if butteraugli_diffmap else 0)
+        flags = ((FLAG_XYB_ROUNDTRIP if xyb_roundtrip else 0) | (FLAG_BUTTERAUGLI_DIFFMAP if butteraugli_diffmap else 0) |
+                 (FLAG_SSIMULACRA2_MAPS if ssimulacra2_maps else 0))
         ctx._check(lib().ce_ref_create(ctx._h, r.ctypes.data, r.size, width, height, flags, C.byref(self._h)))
 
     def compare(self, test, config: MetricConfig = None, intensity_target: float = DEFAULT_INTENSITY_TARGET) -> MetricResult:
@@ -776,6 +839,12 @@ class ReferenceHandle:
         """DSSIM's SsimMap of tests [first, first + count) of the last compare / compare_many with DSSIM: see
         Batch.dssim_ssim_maps."""
         return _read_ssim_maps(self.ctx, lib().ce_ref_dssim_ssim_maps, self._h, self.width, self.height, level, first, count, block)
+
+    def ssimulacra2_maps(self, scale: int, channel: int, kind: int, first: int, count: int, block: int = 1, maps: bool = True):
+        """SSIMULACRA2's maps of tests [first, first + count) of the last compare / compare_many (maps: a handle made with
+        ssimulacra2_maps=True): see Batch.ssimulacra2_maps."""
+        return _read_ssim2_maps(self.ctx, lib().ce_ref_ssimulacra2_maps, self._h, self.width, self.height, scale, channel, kind,
+                                first, count, block, maps)
 
     def stats(self):
         """(ssimulacra2, dssim, butteraugli): compares so far that had to build that metric's reference-side state."""

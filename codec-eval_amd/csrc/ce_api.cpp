@@ -89,6 +89,30 @@ int read_ssim_maps(ce_batch *b, uint32_t level, uint32_t first, uint32_t count, 
     return ce_dssim_read_maps(b, level, first, count, block, maps, ssim);
 }
 
+// the readouts of SSIMULACRA2's maps and their norms (ce_batch_ssimulacra2_maps, ce_ref_ssimulacra2_maps): checks, then the
+// device readout (ssim2.hip).  Norms need a last launch with SSIMULACRA2, maps one with CE_FLAG_SSIMULACRA2_MAPS too.
+int read_ssim2_maps(ce_batch *b, uint32_t scale, uint32_t channel, uint32_t kind, uint32_t first, uint32_t count, uint32_t block,
+                    float *maps, size_t maps_floats, double *norms)
+{
+    if (!b) return fail(nullptr, CE_ERR_INVALID_ARG, "null handle");
+    ce_ctx *ctx = b->ctx;
+    if (!maps && !norms) return fail(ctx, CE_ERR_INVALID_ARG, "SSIMULACRA2 maps readout without an output");
+    if (b->s2_norm_pairs == 0)
+        return fail(ctx, CE_ERR_INVALID_ARG, "no SSIMULACRA2 maps or norms: the last launch did not run SSIMULACRA2");
+    if (maps && b->s2_map_pairs == 0)
+        return fail(ctx, CE_ERR_INVALID_ARG, "no SSIMULACRA2 maps: the last launch did not run SSIMULACRA2 with CE_FLAG_SSIMULACRA2_MAPS");
+    if (scale >= b->s2_scales_run)
+        return fail(ctx, CE_ERR_INVALID_ARG, "SSIMULACRA2 scale " + std::to_string(scale) + " of " + std::to_string(b->s2_scales_run) + " that ran");
+    if (channel >= 3) return fail(ctx, CE_ERR_INVALID_ARG, "SSIMULACRA2 channel " + std::to_string(channel) + " of 3");
+    if (kind >= 3) return fail(ctx, CE_ERR_INVALID_ARG, "SSIMULACRA2 map kind " + std::to_string(kind) + " of 3");
+    const ce_scale_dims &d = b->sd[scale];
+    if (int rc = check_map_readout(ctx, "SSIMULACRA2 map", maps ? b->s2_map_pairs : b->s2_norm_pairs, first, count, block, d.w, d.h,
+                                   maps != nullptr, maps_floats))
+        return rc;
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    return ce_ssim2_read_maps(b, scale, channel, kind, first, count, block, maps, norms);
+}
+
 double psnr_from_sse(unsigned long long sse, size_t w, size_t h)
 {
     // src/metrics/mod.rs:317,324-330
@@ -802,6 +826,7 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
     if (n_pairs == 0 || n_pairs > b->max_pairs) return fail(ctx, CE_ERR_INVALID_ARG, "n_pairs out of range");
     if (metric_mask & ~kKnownMetrics) return fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
     b->ba_map_pairs = b->ds_map_pairs = 0;  // whatever happens below, no readout returns the maps of an earlier launch
+    b->s2_map_pairs = b->s2_norm_pairs = 0;
     CE_HIP(ctx, hipSetDevice(ctx->device));
     {
         int rc = flush_uploads(b);
@@ -848,6 +873,7 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
     const bool run_dssim = (metric_mask & CE_METRIC_DSSIM) != 0;
     const bool run_ba = (metric_mask & CE_METRIC_BUTTERAUGLI) && b->w >= 8 && b->h >= 8;
     const bool store_maps = run_ba && (flags & CE_FLAG_BUTTERAUGLI_DIFFMAP);
+    const bool store_ssim2_maps = run_ssim2 && (flags & CE_FLAG_SSIMULACRA2_MAPS);
     // Side by side or back to back?  Measured (profiles/r02_experiments.md sections 1, 12, 15): a SMALL batch is bound by
     // the latency of its ~130 dependent launches, and three chains side by side hide each other's gaps (one Kodak pair
     // 0.76 -> 0.54 ms, eight 1.37 -> 1.23 ms, one 4K pair 3.65 -> 2.94 ms); a LARGE grid fills the GPU from one chain,
@@ -899,7 +925,7 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
         return CE_OK;
     };
     auto launch_metric = [&](int k) -> int {
-        return k == 0   ? ce_launch_ssim2(b, d_refs, n_refs_used, n_pairs)
+        return k == 0   ? ce_launch_ssim2(b, d_refs, n_refs_used, n_pairs, store_ssim2_maps)
                : k == 1 ? ce_launch_dssim(b, d_refs, n_refs_used, n_pairs)
                         : ce_launch_butteraugli(b, d_refs, n_refs_used, n_pairs, intensity_target, store_maps);
     };
@@ -977,6 +1003,9 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
     b->last_mask = metric_mask;
     b->ba_map_pairs = store_maps ? n_pairs : 0;
     b->ds_map_pairs = run_dssim ? n_pairs : 0;  // DSSIM writes its SSIM maps on every launch
+    b->s2_norm_pairs = run_ssim2 ? n_pairs : 0;  // ... and SSIMULACRA2 its pooled norms (d_avg)
+    b->s2_map_pairs = store_ssim2_maps ? n_pairs : 0;
+    b->s2_scales_run = run_ssim2 ? (uint32_t)std::min(b->n_scales, b->debug_max_scales) : 0;
     // the scores come back behind the last kernel of THIS launch and ev_run marks them: ce_batch_collect waits for the event,
     // not for the stream (round 2 copied at collect time and drained the context's stream, so collecting one batch waited
     // for every batch launched after it - in ce_eval_batch the next chunk's upload then started only when the device was idle)
@@ -1054,6 +1083,12 @@ int ce_batch_dssim_ssim_maps(ce_batch *b, uint32_t level, uint32_t first, uint32
                              size_t maps_floats, double *ssim)
 {
     return read_ssim_maps(b, level, first, count, block, maps, maps_floats, ssim);
+}
+
+int ce_batch_ssimulacra2_maps(ce_batch *b, uint32_t scale, uint32_t channel, uint32_t kind, uint32_t first, uint32_t count,
+                              uint32_t block, float *maps, size_t maps_floats, double *norms)
+{
+    return read_ssim2_maps(b, scale, channel, kind, first, count, block, maps, maps_floats, norms);
 }
 
 int ce_batch_run(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_t flags, float intensity_target,
@@ -1200,6 +1235,8 @@ int ce_eval_batch_lut(ce_ctx *ctx, size_t n, const ce_pair_desc *pairs, const ce
     // the maps live in the pooled batches, which the next call reuses: they are read from a ce_batch or a ce_ref
     if (flags & CE_FLAG_BUTTERAUGLI_DIFFMAP)
         return fail(ctx, CE_ERR_INVALID_ARG, "CE_FLAG_BUTTERAUGLI_DIFFMAP needs a ce_batch or a ce_ref: the pooled batches keep no maps");
+    if (flags & CE_FLAG_SSIMULACRA2_MAPS)
+        return fail(ctx, CE_ERR_INVALID_ARG, "CE_FLAG_SSIMULACRA2_MAPS needs a ce_batch or a ce_ref: the pooled batches keep no maps");
     // bucket by shape (Kodak mixes 768x512 and 512x768); invalid items never reach the device
     std::map<std::pair<uint32_t, uint32_t>, std::vector<size_t>> buckets;
     for (size_t i = 0; i < n; i++) {
@@ -1413,6 +1450,41 @@ int ce_calculate_dssim_ssim_maps(ce_ctx *ctx, const uint8_t *reference, size_t r
     return CE_OK;
 }
 
+int ce_calculate_ssimulacra2_maps(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test, size_t test_len,
+                                  size_t width, size_t height, double *score, double *features, float *maps, size_t maps_floats)
+{
+    if (!ctx || !reference || !test || !score || !features || !maps) return CE_ERR_INVALID_ARG;
+    if (width == 0 || height == 0) return fail(ctx, CE_ERR_INVALID_ARG, "empty image");  // ce_calculate_ssimulacra2's order
+    if (int rc = validate_pair(ctx, reference_len, test_len, width, height)) return rc;
+    if (width > UINT32_MAX || height > UINT32_MAX) return fail(ctx, CE_ERR_INVALID_ARG, "image too large");
+    if (width < 8 || height < 8) return fail(ctx, CE_ERR_TOO_SMALL, "minimum 8x8 for ssimulacra2");
+    uint32_t sw[CE_SSIM2_MAX_SCALES], sh[CE_SSIM2_MAX_SCALES];
+    const uint32_t n = ce_plan_ssim2_scales((uint32_t)width, (uint32_t)height, CE_SSIM2_MAX_SCALES, sw, sh);
+    size_t want = 0;
+    for (uint32_t s = 0; s < n; s++) want += 9 * (size_t)sw[s] * sh[s];
+    if (maps_floats != want)
+        return fail(ctx, CE_ERR_INVALID_ARG, "SSIMULACRA2 maps of every scale need " + std::to_string(want) + " floats, got " + std::to_string(maps_floats));
+    ce_scores s{};
+    ce_batch *b = nullptr;
+    if (int rc = leaf_map_run(ctx, reference, reference_len, test, test_len, width, height, CE_METRIC_SSIMULACRA2,
+                              CE_FLAG_SSIMULACRA2_MAPS, 0.0f, &s, &b))
+        return rc;
+    double avg[CE_SSIM2_MAX_SCALES * 18];
+    CE_HIP(ctx, hipMemcpyAsync(avg, b->d_avg, sizeof(avg), hipMemcpyDeviceToHost, ctx->stream));
+    CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t i = 0; i < CE_SSIM2_MAX_SCALES * 18; i++) features[i] = i < b->s2_scales_run * 18 ? avg[i] : NAN;
+    size_t off = 0;
+    for (uint32_t sc = 0; sc < b->s2_scales_run; sc++)
+        for (uint32_t c = 0; c < 3; c++)
+            for (uint32_t k = 0; k < 3; k++) {
+                const size_t np = (size_t)sw[sc] * sh[sc];
+                if (int r = read_ssim2_maps(b, sc, c, k, 0, 1, 1, maps + off, np, nullptr)) return r;
+                off += np;
+            }
+    *score = s.ssimulacra2;
+    return CE_OK;
+}
+
 // leaf scratch (ce_internal.h): device buffers of at least in_bytes / out_bytes and a pinned staging buffer of the larger
 static int leaf_scratch(ce_ctx *ctx, size_t in_bytes, size_t out_bytes)
 {
@@ -1567,6 +1639,21 @@ int ce_ref_dssim_ssim_maps(ce_ref *ref, uint32_t level, uint32_t first, uint32_t
 {
     if (!ref) return CE_ERR_INVALID_ARG;
     return read_ssim_maps(ref->batch, level, first, count, block, maps, maps_floats, ssim);  // the handle's current batch
+}
+
+int ce_ref_ssimulacra2_maps(ce_ref *ref, uint32_t scale, uint32_t channel, uint32_t kind, uint32_t first, uint32_t count, uint32_t block,
+                            float *maps, size_t maps_floats, double *norms)
+{
+    if (!ref) return fail(nullptr, CE_ERR_INVALID_ARG, "null handle");
+    return read_ssim2_maps(ref->batch, scale, channel, kind, first, count, block, maps, maps_floats, norms);  // the handle's current batch
+}
+
+int ce_ssimulacra2_scales(uint32_t width, uint32_t height, uint32_t *n_scales, uint32_t *scale_w, uint32_t *scale_h)
+{
+    if (!n_scales || !scale_w || !scale_h) return fail(nullptr, CE_ERR_INVALID_ARG, "null pointer");
+    if (width == 0 || height == 0) return fail(nullptr, CE_ERR_INVALID_ARG, "empty image");
+    *n_scales = ce_plan_ssim2_scales(width, height, CE_SSIM2_MAX_SCALES, scale_w, scale_h);
+    return CE_OK;
 }
 
 int ce_dssim_levels(uint32_t width, uint32_t height, uint32_t *n_levels, uint32_t *level_w, uint32_t *level_h)

@@ -19,6 +19,7 @@
 #define CE_MAX_SCALES 6      // SSIMULACRA2 pyramid depth
 #define CE_SSIM2_STREAMS 5   // blur(a), blur(b), blur(a*a), blur(b*b), blur(a*b)
 #define CE_DSSIM_SCALES 5    // dssim-core DEFAULT_WEIGHTS.len()
+static_assert(CE_MAX_SCALES == CE_SSIM2_MAX_SCALES, "the ABI's scale count is the pyramid's");
 
 struct ce_scale_dims {
     uint32_t w, h, pitch;  // pitch in floats, multiple of 32 (128-byte rows)
@@ -84,7 +85,8 @@ struct ce_ctx {
     // ce_rgb8_to_dssim_image): device in / out and a page-locked staging buffer, kept between calls
     uint8_t *leaf_d_in = nullptr, *leaf_d_out = nullptr, *leaf_h = nullptr;
     size_t leaf_in_cap = 0, leaf_out_cap = 0, leaf_h_cap = 0;
-    // the one-pair batch of ce_calculate_butteraugli_diffmap and ce_calculate_dssim_ssim_maps (remade when the shape changes)
+    // the one-pair batch of ce_calculate_butteraugli_diffmap, ce_calculate_dssim_ssim_maps and ce_calculate_ssimulacra2_maps
+    // (remade when the shape changes)
     struct ce_batch *leaf_map = nullptr;
 
     // Auxiliary streams of the context, shared by all its batches (made on first use, destroyed with the context): the
@@ -160,6 +162,15 @@ struct ce_batch {
     double *d_partials = nullptr;      // [pairs][scales][3][max_blocks][6]
     uint32_t max_vblocks = 0;
     double *d_avg = nullptr;           // [pairs][6][3][6]
+    // CE_FLAG_SSIMULACRA2_MAPS: per scale s, [max_pairs][channel 3][kind 3][plane_s] per-pixel error maps (d, artifact,
+    // detail lost; one allocation s2_map made by the first such launch, s2_map_lvl[s] = scale s's part); how many pairs of
+    // the LAST launch stored their maps (0 after a launch without the flag or without SSIMULACRA2) and left their pooled
+    // norms in d_avg (every launch with SSIMULACRA2), the scales it ran; the device buffer of the block-max readouts (grow-only)
+    float *s2_map = nullptr;
+    float *s2_map_lvl[CE_MAX_SCALES] = {};
+    uint32_t s2_map_pairs = 0, s2_norm_pairs = 0, s2_scales_run = 0;
+    float *s2_cells = nullptr;
+    size_t s2_cells_cap = 0;
     ce_dev_scores *d_scores = nullptr;
     ce_dev_scores *h_scores = nullptr;  // pinned
     bool ssim2_ready = false;
@@ -298,7 +309,9 @@ int ce_launch_lut_expand(ce_ctx *ctx, hipStream_t stream, const uint8_t *d_packe
 int ce_launch_lut_apply(ce_ctx *ctx, hipStream_t stream, uint8_t *d_rgb, const uint32_t *d_table, size_t n_pixels);
 int ce_ssim2_prepare(ce_batch *b);
 void ce_ssim2_free(ce_batch *b);
-int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, uint32_t n_pairs);
+int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, uint32_t n_pairs, bool store_maps);
+int ce_ssim2_read_maps(ce_batch *b, uint32_t scale, uint32_t channel, uint32_t kind, uint32_t first, uint32_t count,
+                       uint32_t block, float *maps, double *norms);
 int ce_ssim2_occupancy(int which);
 int ce_ssim2_cbrt_sweep(ce_ctx *ctx, uint32_t first_bits, uint64_t count, uint64_t *mismatches, uint64_t *slow_path);
 int ce_launch_xyb_roundtrip(ce_ctx *ctx, const uint8_t *d_in, uint8_t *d_out, size_t n_pixels);

@@ -134,3 +134,23 @@ inline uint32_t ce_plan_dssim_levels(uint32_t w, uint32_t h, uint32_t max_levels
     }
     return n;
 }
+
+// SSIMULACRA2's scale pyramid (Msssim's loop in the lineage): `if w < 8 || h < 8 {break}; if scale > 0 {downscale}` - the
+// size is tested BEFORE halving (with ceiling), so a scale smaller than 8 px exists whenever its parent was >= 8; at most
+// max_scales scales.  Writes the scale sizes, returns their count (0 below 8 x 8).  The one rule of ssim2.hip's working set
+// and of ce_ssimulacra2_scales.
+inline uint32_t ce_plan_ssim2_scales(uint32_t w, uint32_t h, uint32_t max_scales, uint32_t *scale_w, uint32_t *scale_h)
+{
+    uint32_t n = 0;
+    for (uint32_t s = 0; s < max_scales; s++) {
+        if (w < 8 || h < 8) break;
+        if (s > 0) {
+            w = w / 2 + (w & 1);
+            h = h / 2 + (h & 1);
+        }
+        scale_w[n] = w;
+        scale_h[n] = h;
+        n++;
+    }
+    return n;
+}

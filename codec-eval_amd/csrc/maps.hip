@@ -1,5 +1,6 @@
-// Readout of per-pair maps kept on the device: Butteraugli's diffmaps (CE_FLAG_BUTTERAUGLI_DIFFMAP, butteraugli.hip) and
-// DSSIM's per-level SSIM maps (dssim.hip).  Both are [pair][h][pitch] float planes; a readout packs pairs
+// Readout of per-pair maps kept on the device: Butteraugli's diffmaps (CE_FLAG_BUTTERAUGLI_DIFFMAP, butteraugli.hip),
+// DSSIM's per-level SSIM maps (dssim.hip) and SSIMULACRA2's per-scale error maps (CE_FLAG_SSIMULACRA2_MAPS, ssim2.hip).
+// All are [pair][h][pitch] float planes, a pair's plane `plane` floats after the previous one's; a readout packs pairs
 // [first, first + count) to the host, whole (B = 1) or as the max / min of every B x B cell.
 #include "ce_internal.h"
 
@@ -45,9 +46,17 @@ int ce_read_map_cells(ce_batch *b, const char *name, const float *map, ce_map_ge
                       bool take_min, float **cells, size_t *cells_cap, float *out)
 {
     ce_ctx *ctx = b->ctx;
-    if (block == 1) {  // [pair][h][pitch] rows are contiguous over the pairs: one pitched copy
+    if (block == 1 && g.plane == (size_t)g.pitch * g.h) {  // [pair][h][pitch] rows are contiguous over the pairs: one pitched copy
         CE_HIP(ctx, hipMemcpy2DAsync(out, (size_t)g.w * sizeof(float), map + (size_t)first * g.plane, (size_t)g.pitch * sizeof(float),
                                      (size_t)g.w * sizeof(float), (size_t)count * g.h, hipMemcpyDeviceToHost, ctx->stream));
+        CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return CE_OK;
+    }
+    if (block == 1) {  // padded rows or other planes between the pairs' maps (SSIMULACRA2): one pitched copy per pair
+        for (uint32_t q = 0; q < count; q++)
+            CE_HIP(ctx, hipMemcpy2DAsync(out + (size_t)q * g.w * g.h, (size_t)g.w * sizeof(float), map + (size_t)(first + q) * g.plane,
+                                         (size_t)g.pitch * sizeof(float), (size_t)g.w * sizeof(float), g.h, hipMemcpyDeviceToHost,
+                                         ctx->stream));
         CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return CE_OK;
     }

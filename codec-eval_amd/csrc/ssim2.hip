@@ -479,9 +479,13 @@ struct vblur_state {
 // The four filter steps of DMA group g (ring phase GG = g mod 4, so every register-ring index is static).
 // CHECKED = false is the steady state: all four rows lie in [4, h), so nothing is masked and nothing
 // branches; CHECKED = true handles the first group (rows 0..3 only prime the filter) and the tail.
-template <int GG, bool CHECKED>
+// STORE = true (CE_FLAG_SSIMULACRA2_MAPS) also writes the three per-pixel terms the pool sums - d, artifact, detail - of
+// output row i - 4 to column `lane` of the wave's strip of `map` (planes kind * plane apart), one 256-byte row store per term
+// and wave.  `map` and the row offsets are wave-uniform: the addresses are scalar bases plus the lane's offset.
+template <int GG, bool CHECKED, bool STORE>
 __device__ __forceinline__ void vblur_group(vblur_state &st, const float *__restrict__ slot, int g, uint32_t h,
-                                            const rg_consts &rg)
+                                            const rg_consts &rg, float *__restrict__ map, uint32_t pitch, size_t plane,
+                                            uint32_t lane, bool active)
 {
     const float C2 = 0.0009f;
     float gacc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -519,6 +523,12 @@ __device__ __forceinline__ void vblur_group(vblur_state &st, const float *__rest
             const float artifact = d1 > 0.0f ? d1 : 0.0f;
             const float detail = d1 < 0.0f ? -d1 : 0.0f;
             const float aa = artifact * artifact, ll = detail * detail;
+            if (STORE && active) {
+                float *row = map + (size_t)(i - 4) * pitch;
+                row[lane] = d;
+                (row + plane)[lane] = artifact;
+                (row + 2 * plane)[lane] = detail;
+            }
             gacc[0] += d;
             gacc[1] += dd * dd;
             gacc[2] += artifact;
@@ -531,13 +541,21 @@ __device__ __forceinline__ void vblur_group(vblur_state &st, const float *__rest
     for (int q = 0; q < 6; q++) st.acc[q] += (double)gacc[q];
 }
 
-template <int LEVEL>
+// STORE = true: the same pass, also writing every pixel's three map terms (vblur_group) to maps.lvl[scale], laid out
+// [pair][channel][kind][plane of the scale] (ce_batch::s2_map).  The last argument comes after all the others, so the
+// STORE = false instances read their arguments at the offsets they always had.
+struct ssim2_map_table {
+    float *lvl[CE_MAX_SCALES];
+};
+
+template <int LEVEL, bool STORE>
 __global__ __launch_bounds__(64) void k_ssim2_vblur_dma(const float *__restrict__ hbuf, const float *__restrict__ xyb,
                                                         const uint32_t *__restrict__ pair_ref,
                                                         double *__restrict__ partials, uint32_t w, uint32_t h,
                                                         uint32_t pitch, size_t plane, uint32_t max_refs, uint32_t scale,
                                                         uint32_t max_vblocks, rg_consts rg, lvl_table tab,
-                                                        const uint2 *__restrict__ work, const uint32_t *__restrict__ pair_first)
+                                                        const uint2 *__restrict__ work, const uint32_t *__restrict__ pair_first,
+                                                        ssim2_map_table maps)
 {
     __shared__ __attribute__((aligned(16))) float ring[2 * VB_GROUP];
     uint32_t bx = blockIdx.x, c = blockIdx.y, p = blockIdx.z;
@@ -562,6 +580,7 @@ __global__ __launch_bounds__(64) void k_ssim2_vblur_dma(const float *__restrict_
     const float *xa = xyb + ((size_t)pair_ref[p] * 3 + c) * plane + x0;
     const float *xb = xyb + ((size_t)(max_refs + p) * 3 + c) * plane + x0;
     const uint32_t dr = lane >> 4, dc = (lane & 15) * 4;  // DMA: 16 lanes x 16 B per row, 4 rows per instruction
+    float *map = STORE ? maps.lvl[scale] + ((size_t)p * 9 + (size_t)c * 3) * plane + x0 : nullptr;  // the strip, wave-uniform
 
     using gptr = const __attribute__((address_space(1))) void *;
     using lptr = __attribute__((address_space(3))) void *;
@@ -598,9 +617,11 @@ __global__ __launch_bounds__(64) void k_ssim2_vblur_dma(const float *__restrict_
     // one turn of the loop = 4 groups = 16 rows = one turn of the register ring
 #define CE_VGROUP(GG, CHECKED)                                                                         \
     do {                                                                                               \
-        /* group g has landed once at most the 7 requests of group g+1 are outstanding */              \
+        /* group g has landed once at most the 7 requests of group g+1 are outstanding (STORE: the     \
+           map stores of group g-1 count too and are older, so this also waits for them) */            \
         asm volatile("s_waitcnt vmcnt(7)" ::: "memory");                                               \
-        vblur_group<GG, CHECKED>(st, ring + ((GG) & 1) * VB_GROUP + lane, g0 + (GG), h, rg);           \
+        vblur_group<GG, CHECKED, STORE>(st, ring + ((GG) & 1) * VB_GROUP + lane, g0 + (GG), h, rg, map, \
+                                        pitch, plane, lane, active);                                   \
         /* the slot is free once its LDS reads have returned; refill it with group g+2 */              \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                             \
         issue_group(g0 + (GG) + 2);                                                                    \
@@ -730,8 +751,14 @@ void ce_ssim2_free(ce_batch *b)
     }
     hipFree(b->d_partials);
     hipFree(b->d_avg);
+    hipFree(b->s2_map);
+    hipFree(b->s2_cells);
     b->d_partials = nullptr;
     b->d_avg = nullptr;
+    b->s2_map = b->s2_cells = nullptr;
+    for (int s = 0; s < CE_MAX_SCALES; s++) b->s2_map_lvl[s] = nullptr;
+    b->s2_cells_cap = 0;
+    b->s2_map_pairs = b->s2_norm_pairs = 0;
     for (ce_xcd_list *L : {&b->work_h, &b->work_v, &b->work_ht, &b->work_vt}) ce_free_xcd_list(L);
     b->ssim2_ready = false;
 }
@@ -759,16 +786,10 @@ static int ssim2_allocate(ce_batch *b)
 int ce_ssim2_prepare(ce_batch *b)
 {
     if (b->ssim2_ready) return CE_OK;
-    uint32_t w = b->w, h = b->h;
-    int ns = 0;
-    // The lineage tests the size BEFORE halving (`if w < 8 || h < 8 {break}; if scale > 0
-    // {downscale}`), so a level smaller than 8 px exists whenever its parent was >= 8.
-    for (int s = 0; s < CE_MAX_SCALES; s++) {
-        if (w < 8 || h < 8) break;
-        if (s > 0) {
-            w = (w + 1) / 2;
-            h = (h + 1) / 2;
-        }
+    uint32_t sw[CE_MAX_SCALES], sh[CE_MAX_SCALES];
+    const int ns = (int)ce_plan_ssim2_scales(b->w, b->h, CE_MAX_SCALES, sw, sh);
+    for (int s = 0; s < ns; s++) {
+        const uint32_t w = sw[s], h = sh[s];
         ce_scale_dims &d = b->sd[s];
         d.w = w;
         d.h = h;
@@ -776,7 +797,6 @@ int ce_ssim2_prepare(ce_batch *b)
         d.plane = (size_t)d.pitch * (((size_t)h + HB_ROWS - 1) / HB_ROWS * HB_ROWS);
         d.hpitch = d.pitch;
         d.hplane = d.plane;
-        ns++;
     }
     b->n_scales = ns;
     if (ns == 0) return CE_OK;
@@ -807,11 +827,32 @@ static int build_pass_list(ce_batch *b, uint32_t n_pairs, uint32_t n_blocks, ce_
     return ce_build_xcd_list(b, n_pairs, ce_xcd_keys{3, n_blocks, 1}, L);
 }
 
-int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, uint32_t n_pairs)
+int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, uint32_t n_pairs, bool store_maps)
 {
     ce_ctx *ctx = b->ctx;
     int rc = ce_ssim2_prepare(b);
     if (rc != CE_OK) return rc;
+    // CE_FLAG_SSIMULACRA2_MAPS: every scale's nine maps of all pairs, allocated by the first launch that asks for them (one
+    // allocation: there is nothing to undo if it fails) and kept until the working set is freed
+    ssim2_map_table maps{};
+    if (store_maps) {
+        if (!b->s2_map) {
+            size_t total = 0;
+            for (int s = 0; s < b->n_scales; s++) total += (size_t)b->max_pairs * 9 * b->sd[s].plane;
+            if (hipMalloc(&b->s2_map, total * sizeof(float)) != hipSuccess) {
+                b->s2_map = nullptr;
+                (void)hipGetLastError();
+                ctx->err = "out of device memory for the SSIMULACRA2 maps";
+                return CE_ERR_BACKEND;
+            }
+            size_t off = 0;
+            for (int s = 0; s < b->n_scales; s++) {
+                b->s2_map_lvl[s] = b->s2_map + off;
+                off += (size_t)b->max_pairs * 9 * b->sd[s].plane;
+            }
+        }
+        for (int s = 0; s < b->n_scales; s++) maps.lvl[s] = b->s2_map_lvl[s];
+    }
     rg_consts rg;
     ce_ssim2_recursive_gaussian(rg.mul_in, rg.mul_prev);
     const uint32_t n_slots = n_refs_used + n_pairs;
@@ -824,9 +865,11 @@ int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
     using hblur_fn = void (*)(const float *, const uint32_t *, float *, uint32_t, uint32_t, uint32_t, size_t, uint32_t,
                               rg_consts, lvl_table, const uint2 *, const uint32_t *);
     using vblur_fn = void (*)(const float *, const float *, const uint32_t *, double *, uint32_t, uint32_t, uint32_t,
-                              size_t, uint32_t, uint32_t, uint32_t, rg_consts, lvl_table, const uint2 *, const uint32_t *);
+                              size_t, uint32_t, uint32_t, uint32_t, rg_consts, lvl_table, const uint2 *, const uint32_t *,
+                              ssim2_map_table);
     const hblur_fn h_l0 = k_ssim2_hblur_lds<0>, h_tail = k_ssim2_hblur_lds<-1>;
-    const vblur_fn v_l0 = k_ssim2_vblur_dma<0>, v_tail = k_ssim2_vblur_dma<-1>;
+    const vblur_fn v_l0 = k_ssim2_vblur_dma<0, false>, v_tail = k_ssim2_vblur_dma<-1, false>;
+    const vblur_fn v_l0_map = k_ssim2_vblur_dma<0, true>, v_tail_map = k_ssim2_vblur_dma<-1, true>;
     scale_geom g{};
     const int levels = std::min(b->n_scales, b->debug_max_scales);
     // Front end on the context's stream, level by level (level s+1 needs level s's linear planes).  Level 0's row
@@ -866,9 +909,14 @@ int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
             CE_LAUNCH_ON(ctx, s0, "ssim2_hblur_L0", h_l0, dim3(b->work_h.len), dim3(HB_THREADS), 0, b->d_xyb[0], b->d_pair_ref,
                          b->d_hbuf[0], d.w, d.h, d.pitch, d.plane, b->max_refs, rg, tab, (const uint2 *)b->work_h.d,
                          (const uint32_t *)b->d_pair_first);
-            CE_LAUNCH_ON(ctx, s0, "ssim2_vblur_ssim_L0", v_l0, dim3(b->work_v.len), dim3(64), 0, b->d_hbuf[0], b->d_xyb[0],
-                         b->d_pair_ref, b->d_partials, d.w, d.h, d.pitch, d.plane, b->max_refs, 0u, b->max_vblocks, rg, tab,
-                         (const uint2 *)b->work_v.d, (const uint32_t *)b->d_pair_first);
+#define CE_VBLUR_L0_ARGS                                                                                                   \
+    b->d_hbuf[0], b->d_xyb[0], b->d_pair_ref, b->d_partials, d.w, d.h, d.pitch, d.plane, b->max_refs, 0u, b->max_vblocks, rg, tab, \
+        (const uint2 *)b->work_v.d, (const uint32_t *)b->d_pair_first, maps
+            if (store_maps)  // the same pass, also writing the maps: a profiler name of its own
+                CE_LAUNCH_ON(ctx, s0, "ssim2_vblur_ssim_map_L0", v_l0_map, dim3(b->work_v.len), dim3(64), 0, CE_VBLUR_L0_ARGS);
+            else
+                CE_LAUNCH_ON(ctx, s0, "ssim2_vblur_ssim_L0", v_l0, dim3(b->work_v.len), dim3(64), 0, CE_VBLUR_L0_ARGS);
+#undef CE_VBLUR_L0_ARGS
             if (s0 != CE_STREAM(ctx)) CE_HIP(ctx, hipEventRecord(b->ev_done[0], s0));
         } else {
             const uint32_t l = tab.n++;
@@ -894,9 +942,14 @@ int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
         CE_LAUNCH_ON(ctx, s1, "ssim2_hblur_L1-5", h_tail, dim3(b->work_ht.len), dim3(HB_THREADS), 0,
                      (const float *)nullptr, b->d_pair_ref, (float *)nullptr, 0u, 0u, 0u, (size_t)0, b->max_refs, rg, tab,
                      (const uint2 *)b->work_ht.d, (const uint32_t *)b->d_pair_first);
-        CE_LAUNCH_ON(ctx, s1, "ssim2_vblur_ssim_L1-5", v_tail, dim3(b->work_vt.len), dim3(64), 0,
-                     (const float *)nullptr, (const float *)nullptr, b->d_pair_ref, b->d_partials, 0u, 0u, 0u, (size_t)0, b->max_refs,
-                     0u, b->max_vblocks, rg, tab_v, (const uint2 *)b->work_vt.d, (const uint32_t *)b->d_pair_first);
+#define CE_VBLUR_TAIL_ARGS                                                                                                  \
+    (const float *)nullptr, (const float *)nullptr, b->d_pair_ref, b->d_partials, 0u, 0u, 0u, (size_t)0, b->max_refs, 0u,        \
+        b->max_vblocks, rg, tab_v, (const uint2 *)b->work_vt.d, (const uint32_t *)b->d_pair_first, maps
+        if (store_maps)
+            CE_LAUNCH_ON(ctx, s1, "ssim2_vblur_ssim_map_L1-5", v_tail_map, dim3(b->work_vt.len), dim3(64), 0, CE_VBLUR_TAIL_ARGS);
+        else
+            CE_LAUNCH_ON(ctx, s1, "ssim2_vblur_ssim_L1-5", v_tail, dim3(b->work_vt.len), dim3(64), 0, CE_VBLUR_TAIL_ARGS);
+#undef CE_VBLUR_TAIL_ARGS
         if (s1 != CE_STREAM(ctx)) CE_HIP(ctx, hipEventRecord(b->ev_done[1], s1));
     }
     if (s0 != CE_STREAM(ctx)) {
@@ -928,6 +981,26 @@ int ce_ssim2_cbrt_sweep(ce_ctx *ctx, uint32_t first_bits, uint64_t count, uint64
     return CE_OK;
 }
 
+// SSIMULACRA2's maps of pairs [first, first + count) at (scale, channel, kind), from the last launch: the maps (B = 1) or
+// their B x B cell maxima into `maps` and that map's (mean, 4-norm) pool out of d_avg into `norms`, either may be null; the
+// caller has checked the arguments.  Enqueued on the context's stream behind that launch (maps.hip: ce_read_map_cells) and
+// waited for.
+int ce_ssim2_read_maps(ce_batch *b, uint32_t scale, uint32_t channel, uint32_t kind, uint32_t first, uint32_t count,
+                       uint32_t block, float *maps, double *norms)
+{
+    ce_ctx *ctx = b->ctx;
+    if (norms) {  // d_avg is [pair][scale][channel][6]; the kind's (mean, 4-norm) are entries 2 kind, 2 kind + 1
+        CE_HIP(ctx, hipMemcpy2DAsync(norms, 2 * sizeof(double), b->d_avg + (size_t)first * CE_MAX_SCALES * 18 + scale * 18 + channel * 6 + 2 * kind,
+                                     CE_MAX_SCALES * 18 * sizeof(double), 2 * sizeof(double), count, hipMemcpyDeviceToHost, ctx->stream));
+        if (!maps) CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (!maps) return CE_OK;
+    const ce_scale_dims &d = b->sd[scale];
+    return ce_read_map_cells(b, "ssim2_block_max", b->s2_map_lvl[scale] + (size_t)(channel * 3 + kind) * d.plane,
+                             ce_map_geom{d.w, d.h, d.pitch, 9 * d.plane}, first, count, block, false, &b->s2_cells, &b->s2_cells_cap,
+                             maps);
+}
+
 // debug: resident blocks per CU the runtime computes for the two blur kernels (which: 0 = row pass, 1 = column pass)
 int ce_ssim2_occupancy(int which)
 {
@@ -935,6 +1008,6 @@ int ce_ssim2_occupancy(int which)
     if (which == 0)
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_ssim2_hblur_lds<0>, HB_THREADS, 0);
     else
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_ssim2_vblur_dma<0>, 64, 0);
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_ssim2_vblur_dma<0, false>, 64, 0);
     return n;
 }

@@ -213,6 +213,39 @@ inline std::pair<double, std::vector<SsimMap>> calculate_dssim_with_ssim_maps(co
     }
     return {score, std::move(out)};
 }
+// One scale of SSIMULACRA2's per-pixel error terms (ssim_map / edge_diff_map of the lineage behind src/metrics/ssimulacra2.rs:96):
+// maps is [channel 3][kind 3][height][width], kinds in enum ce_ssim2_map order (SSIM, artifact, detail lost)
+struct Ssim2Maps {
+    size_t width, height;
+    std::vector<float> maps;
+};
+struct Ssim2WithMaps {
+    double score;
+    double features[CE_SSIM2_MAX_SCALES * 18];  // [scale][channel][6]: the means and 4-norms the score weighs, NaN past the scales
+    std::vector<Ssim2Maps> scales;              // scale 0 at full resolution
+};
+// calculate_ssimulacra2 (src/metrics/ssimulacra2.rs:59) with everything the score pools kept
+inline Ssim2WithMaps calculate_ssimulacra2_with_maps(const HipBackend &be, const Bytes &reference, const Bytes &test, size_t width,
+                                                     size_t height)
+{
+    uint32_t n = 0, sw[CE_SSIM2_MAX_SCALES] = {}, sh[CE_SSIM2_MAX_SCALES] = {};
+    if (width > 0 && height > 0 && width <= UINT32_MAX && height <= UINT32_MAX)
+        ce_ssimulacra2_scales((uint32_t)width, (uint32_t)height, &n, sw, sh);
+    size_t total = 0;
+    for (uint32_t s = 0; s < n; s++) total += 9 * (size_t)sw[s] * sh[s];
+    std::vector<float> maps(total);
+    Ssim2WithMaps r{};
+    detail::check(be, ce_calculate_ssimulacra2_maps(be.ctx(), reference.data(), reference.size(), test.data(), test.size(), width, height,
+                                                    &r.score, r.features, maps.data(), maps.size()),
+                  "SSIMULACRA2", width, height, test.size());
+    size_t off = 0;
+    for (uint32_t s = 0; s < n; s++) {
+        const size_t m = 9 * (size_t)sw[s] * sh[s];
+        r.scales.push_back(Ssim2Maps{sw[s], sh[s], std::vector<float>(maps.begin() + off, maps.begin() + off + m)});
+        off += m;
+    }
+    return r;
+}
 // xyb_roundtrip, src/metrics/xyb.rs:225-253 (asserts on the length, :227)
 inline Bytes xyb_roundtrip(const HipBackend &be, const Bytes &rgb, size_t width, size_t height)
 {

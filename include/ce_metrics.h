@@ -67,11 +67,26 @@ enum ce_flag {
      * ce_batch_butteraugli_diffmap / ce_ref_butteraugli_diffmap.  Scores are the same with and without it.
      * ce_eval_batch, ce_eval_batch_lut and ce_eval_pair return CE_ERR_INVALID_ARG for it: their batches do not outlive the
      * call. */
-    CE_FLAG_BUTTERAUGLI_DIFFMAP = 1u << 1
+    CE_FLAG_BUTTERAUGLI_DIFFMAP = 1u << 1,
+    /* The per-pixel terms SSIMULACRA2 pools (ssim_map / edge_diff_map of the lineage behind src/metrics/ssimulacra2.rs:96):
+     * with CE_METRIC_SSIMULACRA2, ce_batch_launch / ce_batch_run and the compares of a ce_ref created with it also keep
+     * every pair's nine maps per scale (ce_ssim2_map x 3 XYB channels) on the device (36 bytes per pixel of every scale and
+     * pair, about 20 MB per 768x512 pair; allocated by the first such launch, not counted by ce_estimate_batch_bytes), to
+     * be read with ce_batch_ssimulacra2_maps / ce_ref_ssimulacra2_maps.  Scores are the same with and without it.
+     * ce_eval_batch, ce_eval_batch_lut and ce_eval_pair return CE_ERR_INVALID_ARG for it. */
+    CE_FLAG_SSIMULACRA2_MAPS = 1u << 2
 };
 
 #define CE_DEFAULT_INTENSITY_TARGET 80.0f /* src/metrics/butteraugli.rs:94 */
 #define CE_DSSIM_MAX_LEVELS 5 /* dssim-core's scale weights: at most this many SsimMap per compare */
+#define CE_SSIM2_MAX_SCALES 6 /* Msssim's NUM_SCALES (lineage of src/metrics/ssimulacra2.rs:96) */
+
+/* SSIMULACRA2's three per-pixel error terms of one XYB channel at one scale, each >= 0 (ssim_map and edge_diff_map of
+ * the lineage).  The score pools each one's mean and 4-norm.
+ *   SSIM         1 - SSIM of the blurred statistics, clamped at 0: structural error
+ *   ARTIFACT     max((1 + |test - mu_test|) / (1 + |ref - mu_ref|) - 1, 0): edges or texture the test adds (ringing, blocking)
+ *   DETAIL_LOST  max(1 - (1 + |test - mu_test|) / (1 + |ref - mu_ref|), 0): edges or texture the test lost (blur) */
+enum ce_ssim2_map { CE_SSIM2_MAP_SSIM = 0, CE_SSIM2_MAP_ARTIFACT = 1, CE_SSIM2_MAP_DETAIL_LOST = 2 };
 
 /* MetricResult (src/metrics/mod.rs:140-149): a score is meaningful iff its bit is
  * set in `valid`; `status` is the ce_status of this pair. */
@@ -142,6 +157,19 @@ int ce_dssim_levels(uint32_t width, uint32_t height, uint32_t *n_levels, uint32_
 int ce_calculate_dssim_ssim_maps(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test,
                                  size_t test_len, size_t width, size_t height, double *dssim, double *level_ssim,
                                  float *maps, size_t maps_floats);
+/* SSIMULACRA2's scale geometry (Msssim's loop behind src/metrics/ssimulacra2.rs:96): scale 0 is the image; a scale exists
+ * while its parent is at least 8 x 8 and is the parent halved with ceiling, at most CE_SSIM2_MAX_SCALES scales (0 below
+ * 8 x 8).  scale_w / scale_h have CE_SSIM2_MAX_SCALES entries.  A pure host function (no context, works without a
+ * device); CE_ERR_INVALID_ARG for width or height 0 or a null pointer. */
+int ce_ssimulacra2_scales(uint32_t width, uint32_t height, uint32_t *n_scales, uint32_t *scale_w, uint32_t *scale_h);
+/* The one-pair call: calculate_ssimulacra2 (src/metrics/ssimulacra2.rs:59) with everything it pools kept.  score as
+ * ce_calculate_ssimulacra2; features = [CE_SSIM2_MAX_SCALES][3][6] doubles, the 108 pooled values the score weighs
+ * ([scale][channel]{ssim mean, ssim 4-norm, artifact mean, artifact 4-norm, detail mean, detail 4-norm}; NaN past the
+ * image's scales); maps = every scale's [channel][kind][h_s][w_s] floats, scale after scale; maps_floats must be
+ * 9 * the sum of w_s * h_s (ce_ssimulacra2_scales).  Length and dimension errors as ce_calculate_ssimulacra2. */
+int ce_calculate_ssimulacra2_maps(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test,
+                                  size_t test_len, size_t width, size_t height, double *score, double *features,
+                                  float *maps, size_t maps_floats);
 /* xyb_roundtrip                         src/metrics/xyb.rs:225 ; out has rgb_len bytes */
 int ce_xyb_roundtrip(ce_ctx *ctx, const uint8_t *rgb, size_t rgb_len, size_t width, size_t height,
                      uint8_t *out);
@@ -253,6 +281,16 @@ int ce_batch_butteraugli_diffmap(ce_batch *b, uint32_t first, uint32_t count, ui
  * level >= the level count, count = 0 or a range past the stored pairs, a bad block or a wrong maps_floats. */
 int ce_batch_dssim_ssim_maps(ce_batch *b, uint32_t level, uint32_t first, uint32_t count, uint32_t block,
                              float *maps, size_t maps_floats, double *ssim);
+/* SSIMULACRA2's error maps (ce_ssim2_map) of pairs [first, first+count) of the last launch: map `kind` of XYB channel
+ * `channel` at `scale` (see ce_ssimulacra2_scales).  maps = [count][ceil(h_s/B)][ceil(w_s/B)] floats: block B = 1 is the
+ * full map, B = a power of two <= 64 the MAXIMUM of each B x B cell (the worst local error; edge cells clipped to the
+ * scale); needs a last launch with CE_FLAG_SSIMULACRA2_MAPS.  norms = [count][2] doubles: that map's mean and 4-norm
+ * exactly as the score pooled them; needs only a last launch with CE_METRIC_SSIMULACRA2.  Either output may be NULL
+ * (maps_floats then 0), not both.  Waits for that launch.  CE_ERR_INVALID_ARG for a null handle, no stored maps or norms,
+ * scale >= the scales that ran, channel or kind >= 3, count = 0 or a range past the stored pairs, a bad block or a
+ * wrong maps_floats. */
+int ce_batch_ssimulacra2_maps(ce_batch *b, uint32_t scale, uint32_t channel, uint32_t kind, uint32_t first,
+                              uint32_t count, uint32_t block, float *maps, size_t maps_floats, double *norms);
 
 /* ---- reference handle: Ssimulacra2Reference::{new,compare} ------------------------
  * crates/codec-iter/src/eval.rs:138-149,83-89; crates/codec-compare/src/brute_force_sweep.rs:197-201,256
@@ -282,6 +320,10 @@ int ce_ref_butteraugli_diffmap(ce_ref *ref, uint32_t first, uint32_t count, uint
 /* the same as ce_batch_dssim_ssim_maps for the tests of a reference handle's last compare / compare_many that ran DSSIM */
 int ce_ref_dssim_ssim_maps(ce_ref *ref, uint32_t level, uint32_t first, uint32_t count, uint32_t block,
                            float *maps, size_t maps_floats, double *ssim);
+/* the same as ce_batch_ssimulacra2_maps for the tests of a reference handle's last compare / compare_many (maps: a handle
+ * created with CE_FLAG_SSIMULACRA2_MAPS; crates/codec-iter/src/eval.rs:83-89) */
+int ce_ref_ssimulacra2_maps(ce_ref *ref, uint32_t scale, uint32_t channel, uint32_t kind, uint32_t first, uint32_t count,
+                            uint32_t block, float *maps, size_t maps_floats, double *norms);
 void ce_ref_destroy(ce_ref *ref);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------ */
