@@ -140,6 +140,15 @@ impl HipMetrics {
         Ok(out)
     }
 
+    /// `compute_heuristics(rgb, width, height, _)` (crates/codec-compare/src/image_heuristics.rs:76-305) on the device;
+    /// images under 3 x 3 are an error (the reference panics).
+    pub fn compute_heuristics(&mut self, rgb: &[u8], width: usize, height: usize) -> Result<sys::ce_image_heuristics, HipError> {
+        let mut out = sys::ce_image_heuristics::default();
+        let rc = unsafe { sys::ce_image_heuristics_rgb8(self.ctx, rgb.as_ptr(), rgb.len(), width, height, &mut out) };
+        self.check(rc, width as u32, height as u32, rgb.len())?;
+        Ok(out)
+    }
+
     /// `calculate_butteraugli_with_intensity` returning what `ButteraugliResult` holds (src/metrics/prelude.rs:64-65):
     /// the score and the per-pixel diffmap, row-major `width * height`, whose maximum is the score.
     pub fn calculate_butteraugli_with_diffmap(&mut self, reference: &[u8], test: &[u8], width: usize, height: usize,
@@ -327,6 +336,14 @@ impl HipSsim2Reference<'_> {
         let rc = unsafe {
             sys::ce_ref_compare_many(self.handle, ptrs.as_ptr(), lens.as_ptr(), distorted.len() as u32, mask, intensity_target, out.as_mut_ptr())
         };
+        self.owner.check(rc, self.width, self.height, 0)?;
+        Ok(out)
+    }
+
+    /// `compute_heuristics` of the resident reference image: the heuristics CSV of a sweep without a second decode.
+    pub fn heuristics(&mut self) -> Result<sys::ce_image_heuristics, HipError> {
+        let mut out = sys::ce_image_heuristics::default();
+        let rc = unsafe { sys::ce_ref_image_heuristics(self.handle, &mut out) };
         self.owner.check(rc, self.width, self.height, 0)?;
         Ok(out)
     }

@@ -57,6 +57,43 @@ pub struct ce_scores {
     pub status: i32,
 }
 
+/// `ce_image_heuristics` (128 bytes): `ImageHeuristics` of crates/codec-compare/src/image_heuristics.rs:22-63 without the
+/// name, plus analyze-image's `detail_block_pct` (variance > 1000).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct ce_image_heuristics {
+    pub width: u64,
+    pub height: u64,
+    pub pixels: u64,
+    pub mean_luminance: c_float,
+    pub luminance_variance: c_float,
+    pub luminance_std: c_float,
+    pub edge_strength_mean: c_float,
+    pub edge_strength_max: c_float,
+    pub edge_density: c_float,
+    pub flat_block_pct: c_float,
+    pub low_var_block_pct: c_float,
+    pub mid_var_block_pct: c_float,
+    pub high_var_block_pct: c_float,
+    pub detail_block_pct: c_float,
+    pub block_variance_mean: c_float,
+    pub block_variance_std: c_float,
+    pub color_variance: c_float,
+    pub saturation_mean: c_float,
+    pub saturation_std: c_float,
+    pub high_freq_energy: c_float,
+    pub low_freq_energy: c_float,
+    pub freq_ratio: c_float,
+    pub local_contrast_mean: c_float,
+    pub local_contrast_std: c_float,
+    pub horizontal_complexity: c_float,
+    pub vertical_complexity: c_float,
+    pub diagonal_complexity: c_float,
+    pub analyze_detail_block_pct: c_float,
+}
+pub const CE_BATCH_REFERENCES: u32 = 0;
+pub const CE_BATCH_TESTS: u32 = 1;
+
 /// `ce_pair_desc` (40 bytes): one item of the (image x codec x quality) grid, host pointers.
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -152,6 +189,10 @@ extern "C" {
     pub fn ce_ref_ssimulacra2_maps(r: *mut ce_ref, scale: u32, channel: u32, kind: u32, first: u32, count: u32, block: u32,
                                    maps: *mut c_float, maps_floats: usize, norms: *mut c_double) -> c_int;
     pub fn ce_ref_destroy(r: *mut ce_ref);
+    pub fn ce_image_heuristics_rgb8(ctx: *mut ce_ctx, rgb: *const u8, len: usize, width: usize, height: usize,
+                                    out: *mut ce_image_heuristics) -> c_int;
+    pub fn ce_batch_image_heuristics(b: *mut ce_batch, which: u32, first: u32, count: u32, out: *mut ce_image_heuristics) -> c_int;
+    pub fn ce_ref_image_heuristics(r: *mut ce_ref, out: *mut ce_image_heuristics) -> c_int;
     pub fn ce_prof_enable(ctx: *mut ce_ctx, on: c_int) -> c_int;
     pub fn ce_prof_filter(ctx: *mut ce_ctx, substring: *const c_char) -> c_int;
     pub fn ce_prof_reset(ctx: *mut ce_ctx) -> c_int;

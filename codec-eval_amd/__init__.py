@@ -35,6 +35,7 @@ FLAG_XYB_ROUNDTRIP = 1
 FLAG_BUTTERAUGLI_DIFFMAP = 1 << 1
 FLAG_SSIMULACRA2_MAPS = 1 << 2
 PIXEL_RGB8, PIXEL_RGBA8, PIXEL_RGB16_10BIT, PIXEL_RGBA16_10BIT = 0, 1, 2, 3
+BATCH_REFERENCES, BATCH_TESTS = 0, 1  # enum ce_batch_images
 DEFAULT_INTENSITY_TARGET = 80.0
 DSSIM_MAX_LEVELS = 5  # CE_DSSIM_MAX_LEVELS
 SSIM2_MAX_SCALES = 6  # CE_SSIM2_MAX_SCALES
@@ -69,6 +70,26 @@ class CePairDesc(C.Structure):
         ("width", C.c_uint32),
         ("height", C.c_uint32),
     ]
+
+
+# ImageHeuristics of crates/codec-compare/src/image_heuristics.rs:22-63 without the name, plus analyze-image's
+# "variance > 1000" block percentage (analyze_image.rs:94-96): the fields of ce_image_heuristics, in order
+HEURISTICS_FIELDS = (
+    "width", "height", "pixels",
+    "mean_luminance", "luminance_variance", "luminance_std",
+    "edge_strength_mean", "edge_strength_max", "edge_density",
+    "flat_block_pct", "low_var_block_pct", "mid_var_block_pct", "high_var_block_pct", "detail_block_pct",
+    "block_variance_mean", "block_variance_std",
+    "color_variance", "saturation_mean", "saturation_std",
+    "high_freq_energy", "low_freq_energy", "freq_ratio",
+    "local_contrast_mean", "local_contrast_std",
+    "horizontal_complexity", "vertical_complexity", "diagonal_complexity",
+    "analyze_detail_block_pct",
+)
+
+
+class CeImageHeuristics(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in HEURISTICS_FIELDS[:3]] + [(f, C.c_float) for f in HEURISTICS_FIELDS[3:]]
 
 
 class CodecEvalError(RuntimeError):
@@ -163,6 +184,9 @@ _PROTOTYPES = [
     ("ce_ref_dssim_ssim_maps", _i, [_vp, _u32, _u32, _u32, _u32, _vp, _sz, _vp]),
     ("ce_ref_ssimulacra2_maps", _i, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp]),
     ("ce_ref_destroy", None, [_vp]),
+    ("ce_image_heuristics_rgb8", _i, [_vp, _u8p, _sz, _sz, _sz, C.POINTER(CeImageHeuristics)]),
+    ("ce_batch_image_heuristics", _i, [_vp, _u32, _u32, _u32, C.POINTER(CeImageHeuristics)]),
+    ("ce_ref_image_heuristics", _i, [_vp, C.POINTER(CeImageHeuristics)]),
     ("ce_prof_enable", _i, [_vp, _i]),
     ("ce_prof_filter", _i, [_vp, C.c_char_p]),
     ("ce_prof_reset", _i, [_vp]),
@@ -406,6 +430,47 @@ def _read_ssim2_maps(ctx: "Context", fn, handle, width: int, height: int, scale:
 
 
 @dataclass
+class ImageHeuristics:
+    """ImageHeuristics (crates/codec-compare/src/image_heuristics.rs:22-63) of one image, computed on the device: the
+    reference's fields and order, image name included (empty unless the caller sets it), plus analyze-image's
+    detail_block_pct (blocks with variance > 1000, analyze_image.rs:94-96).  The f32 fields are Python floats holding the
+    exact f32 values."""
+    image: str
+    width: int
+    height: int
+    pixels: int
+    mean_luminance: float
+    luminance_variance: float
+    luminance_std: float
+    edge_strength_mean: float
+    edge_strength_max: float
+    edge_density: float
+    flat_block_pct: float
+    low_var_block_pct: float
+    mid_var_block_pct: float
+    high_var_block_pct: float
+    detail_block_pct: float
+    block_variance_mean: float
+    block_variance_std: float
+    color_variance: float
+    saturation_mean: float
+    saturation_std: float
+    high_freq_energy: float
+    low_freq_energy: float
+    freq_ratio: float
+    local_contrast_mean: float
+    local_contrast_std: float
+    horizontal_complexity: float
+    vertical_complexity: float
+    diagonal_complexity: float
+    analyze_detail_block_pct: float
+
+    @staticmethod
+    def from_c(h: CeImageHeuristics, image: str = "") -> "ImageHeuristics":
+        return ImageHeuristics(image, *[getattr(h, f) for f in HEURISTICS_FIELDS])
+
+
+@dataclass
 class MetricResult:
     dssim: Optional[float] = None
     ssimulacra2: Optional[float] = None
@@ -576,6 +641,13 @@ class Context:
         out = np.empty((height, width, 4), np.float32)
         self._check(lib().ce_rgb8_to_dssim_image(self._h, r.ctypes.data, r.size, width, height, out.ctypes.data))
         return out
+
+    def image_heuristics(self, rgb, width: int, height: int, image: str = "") -> ImageHeuristics:
+        """compute_heuristics, crates/codec-compare/src/image_heuristics.rs:76 (images under 3 x 3 raise)."""
+        r = _buf(rgb)
+        out = CeImageHeuristics()
+        self._check(lib().ce_image_heuristics_rgb8(self._h, r.ctypes.data, r.size, width, height, C.byref(out)))
+        return ImageHeuristics.from_c(out, image)
 
     # -- dispatcher
     def calculate_metrics(self, reference, test, width: int, height: int, config: MetricConfig,
@@ -772,6 +844,13 @@ class Batch:
         return _read_ssim2_maps(self.ctx, lib().ce_batch_ssimulacra2_maps, self._h, self.width, self.height, scale, channel, kind,
                                 first, count, block, maps)
 
+    def image_heuristics(self, first: int, count: int, tests: bool = False) -> List[ImageHeuristics]:
+        """compute_heuristics of references (tests=True: test images) [first, first + count) as they sit in the batch,
+        after every set_* / bind_pair so far; the last run's scores and maps stay as they are."""
+        out = (CeImageHeuristics * max(count, 1))()
+        self.ctx._check(lib().ce_batch_image_heuristics(self._h, BATCH_TESTS if tests else BATCH_REFERENCES, first, count, out))
+        return [ImageHeuristics.from_c(out[i]) for i in range(count)]
+
     # -- test hooks
     def debug_limit_scales(self, n: int):
         self.ctx._check(lib().ce_debug_ssim2_limit_scales(self._h, n))
@@ -845,6 +924,12 @@ class ReferenceHandle:
         ssimulacra2_maps=True): see Batch.ssimulacra2_maps."""
         return _read_ssim2_maps(self.ctx, lib().ce_ref_ssimulacra2_maps, self._h, self.width, self.height, scale, channel, kind,
                                 first, count, block, maps)
+
+    def image_heuristics(self, image: str = "") -> ImageHeuristics:
+        """compute_heuristics of the handle's reference image."""
+        out = CeImageHeuristics()
+        self.ctx._check(lib().ce_ref_image_heuristics(self._h, C.byref(out)))
+        return ImageHeuristics.from_c(out, image)
 
     def stats(self):
         """(ssimulacra2, dssim, butteraugli): compares so far that had to build that metric's reference-side state."""

@@ -378,6 +378,8 @@ void ce_ctx_destroy(ce_ctx *ctx)
     hipFree(ctx->leaf_d_in);
     hipFree(ctx->leaf_d_out);
     if (ctx->leaf_h) hipHostFree(ctx->leaf_h);
+    hipFree(ctx->heur_d);
+    if (ctx->heur_h) hipHostFree(ctx->heur_h);
     hipFree(ctx->d_lut_ssim2);
     hipFree(ctx->d_lut_powf);
     hipFree(ctx->d_xyb_thresh);
@@ -1543,6 +1545,47 @@ int ce_rgb8_to_dssim_image(ce_ctx *ctx, const uint8_t *rgb, size_t rgb_len, size
     });
 }
 
+// ---- image heuristics (heuristics.hip) ---------------------------------------------------------
+
+int ce_image_heuristics_rgb8(ce_ctx *ctx, const uint8_t *rgb, size_t len, size_t width, size_t height, ce_image_heuristics *out)
+{
+    if (!ctx || !rgb || !out) return CE_ERR_INVALID_ARG;
+    if (width > UINT32_MAX || height > UINT32_MAX || (height && width > SIZE_MAX / 3 / height))
+        return fail(ctx, CE_ERR_INVALID_ARG, "image heuristics: image dimensions out of range");
+    if (len != width * height * 3) return bad_length(ctx, width * height * 3, len);
+    if (width < 3 || height < 3)
+        return fail(ctx, CE_ERR_TOO_SMALL, "image heuristics need at least 3 x 3 pixels, got " + std::to_string(width) + " x " +
+                                               std::to_string(height));
+    int rc = leaf_scratch(ctx, len, 0);
+    if (rc != CE_OK) return rc;
+    std::memcpy(ctx->leaf_h, rgb, len);
+    const hipError_t e = hipMemcpyAsync(ctx->leaf_d_in, ctx->leaf_h, len, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) return fail(ctx, CE_ERR_BACKEND, std::string("image heuristics upload: ") + hipGetErrorString(e));
+    return ce_image_heuristics_run(ctx, ctx->leaf_d_in, len, (uint32_t)width, (uint32_t)height, 1, out);
+}
+
+int ce_batch_image_heuristics(ce_batch *b, uint32_t which, uint32_t first, uint32_t count, ce_image_heuristics *out)
+{
+    if (!b || !out) return CE_ERR_INVALID_ARG;
+    ce_ctx *ctx = b->ctx;
+    if (which != CE_BATCH_REFERENCES && which != CE_BATCH_TESTS)
+        return fail(ctx, CE_ERR_INVALID_ARG, "image heuristics: unknown slab " + std::to_string(which));
+    const uint32_t slots = which == CE_BATCH_TESTS ? b->max_pairs : b->max_refs;
+    if (count == 0 || first > slots || count > slots - first)
+        return fail(ctx, CE_ERR_INVALID_ARG, "image heuristics: images [" + std::to_string(first) + ", " +
+                                                 std::to_string((uint64_t)first + count) + ") outside the " + std::to_string(slots) +
+                                                 " slots");
+    if (b->w < 3 || b->h < 3)
+        return fail(ctx, CE_ERR_TOO_SMALL, "image heuristics need at least 3 x 3 pixels, got " + std::to_string(b->w) + " x " +
+                                               std::to_string(b->h));
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    // the kernels run on the context's stream: behind the inline route's copies already, behind the upload stream's
+    // copies, conversions and colour tables from here (the ordering of a launch, order_write)
+    if (int rc = flush_uploads(b)) return rc;
+    const uint8_t *slab = which == CE_BATCH_TESTS ? b->d_tests : b->d_refs;
+    return ce_image_heuristics_run(ctx, slab + (size_t)first * b->img_bytes, b->img_bytes, b->w, b->h, count, out);
+}
+
 // ---- reference handle -------------------------------------------------------------------------
 
 struct ce_ref {
@@ -1646,6 +1689,12 @@ int ce_ref_ssimulacra2_maps(ce_ref *ref, uint32_t scale, uint32_t channel, uint3
 {
     if (!ref) return fail(nullptr, CE_ERR_INVALID_ARG, "null handle");
     return read_ssim2_maps(ref->batch, scale, channel, kind, first, count, block, maps, maps_floats, norms);  // the handle's current batch
+}
+
+int ce_ref_image_heuristics(ce_ref *ref, ce_image_heuristics *out)
+{
+    if (!ref || !out) return CE_ERR_INVALID_ARG;
+    return ce_batch_image_heuristics(ref->batch, CE_BATCH_REFERENCES, 0, 1, out);  // the handle's current batch holds its image
 }
 
 int ce_ssimulacra2_scales(uint32_t width, uint32_t height, uint32_t *n_scales, uint32_t *scale_w, uint32_t *scale_h)

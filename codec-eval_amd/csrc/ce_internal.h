@@ -88,6 +88,10 @@ struct ce_ctx {
     // the one-pair batch of ce_calculate_butteraugli_diffmap, ce_calculate_dssim_ssim_maps and ce_calculate_ssimulacra2_maps
     // (remade when the shape changes)
     struct ce_batch *leaf_map = nullptr;
+    // grow-only device scratch of the image heuristics (heuristics.hip: per-tile partial sums, per-image means and results)
+    // and the page-locked buffer their results come back through
+    uint8_t *heur_d = nullptr, *heur_h = nullptr;
+    size_t heur_d_cap = 0, heur_h_cap = 0;
 
     // Auxiliary streams of the context, shared by all its batches (made on first use, destroyed with the context): the
     // three metric chains of a forked batch, SSIMULACRA2's level-0 passes, Butteraugli's half-resolution chain.  Rounds
@@ -334,6 +338,10 @@ int ce_calibrate_traffic(ce_ctx *ctx, size_t bytes);
 int ce_build_xcd_list(ce_batch *b, uint32_t n_pairs, const ce_xcd_keys &keys, ce_xcd_list *list);
 void ce_free_xcd_list(ce_xcd_list *list);
 int ce_launch_rgb8_to_dssim_image(ce_ctx *ctx, const uint8_t *d_rgb, float *d_rgba, size_t n_pixels);
+// compute_heuristics of n packed RGB8 images of one shape, img_stride bytes apart on the device, on the context's stream;
+// returns after the results are in out (heuristics.hip)
+int ce_image_heuristics_run(ce_ctx *ctx, const uint8_t *d_imgs, size_t img_stride, uint32_t w, uint32_t h, uint32_t n,
+                            ce_image_heuristics *out);
 
 // host-side constant builders (ce_tables.cpp)
 void ce_build_srgb_lut_f64(float lut[256]);

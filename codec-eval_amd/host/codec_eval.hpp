@@ -261,6 +261,15 @@ inline std::vector<float> rgb8_to_dssim_image(const HipBackend &be, const Bytes 
     detail::check(be, ce_rgb8_to_dssim_image(be.ctx(), rgb.data(), rgb.size(), width, height, out.data()), "DSSIM", width, height, rgb.size());
     return out;
 }
+// compute_heuristics (crates/codec-compare/src/image_heuristics.rs:76-305) of packed RGB8; under 3 x 3 is an error (the
+// reference panics there)
+inline ce_image_heuristics compute_heuristics(const HipBackend &be, const Bytes &rgb, size_t width, size_t height)
+{
+    ce_image_heuristics h{};
+    detail::check(be, ce_image_heuristics_rgb8(be.ctx(), rgb.data(), rgb.size(), width, height, &h), "image heuristics", width, height,
+                  rgb.size());
+    return h;
+}
 }  // namespace metrics
 
 namespace eval {
@@ -484,6 +493,14 @@ public:
             out.push_back(s[i].ssimulacra2);
         }
         return out;
+    }
+
+    // compute_heuristics of the resident source image (no second upload)
+    ce_image_heuristics heuristics() const
+    {
+        ce_image_heuristics h{};
+        detail::check(*be_, ce_ref_image_heuristics(ref_, &h), "image heuristics", w_, h_, 0);
+        return h;
     }
 
 private:

@@ -182,5 +182,34 @@ inline std::string csv_summary(const std::vector<eval::ImageReport> &images)
     return o;
 }
 
+// codec-compare's image-heuristics CSV (crates/codec-compare/src/image_heuristics.rs:358-400): written with writeln!, so
+// the name goes out unquoted and each f32 at its exact binary value with {:.2} / {:.4}
+struct NamedHeuristics {
+    std::string image;
+    ce_image_heuristics h;
+};
+inline std::string heuristics_csv(const std::vector<NamedHeuristics> &rows)
+{
+    std::string o =
+        "image,width,height,pixels,mean_luminance,luminance_variance,luminance_std,edge_strength_mean,edge_strength_max,edge_density,"
+        "flat_block_pct,low_var_block_pct,mid_var_block_pct,high_var_block_pct,detail_block_pct,block_variance_mean,block_variance_std,"
+        "color_variance,saturation_mean,saturation_std,high_freq_energy,low_freq_energy,freq_ratio,local_contrast_mean,local_contrast_std,"
+        "horizontal_complexity,vertical_complexity,diagonal_complexity\n";
+    for (const auto &r : rows) {
+        const ce_image_heuristics &h = r.h;
+        const std::pair<float, int> cols[24] = {
+            {h.mean_luminance, 2}, {h.luminance_variance, 2}, {h.luminance_std, 2}, {h.edge_strength_mean, 2},
+            {h.edge_strength_max, 2}, {h.edge_density, 4}, {h.flat_block_pct, 2}, {h.low_var_block_pct, 2},
+            {h.mid_var_block_pct, 2}, {h.high_var_block_pct, 2}, {h.detail_block_pct, 2}, {h.block_variance_mean, 2},
+            {h.block_variance_std, 2}, {h.color_variance, 2}, {h.saturation_mean, 4}, {h.saturation_std, 4},
+            {h.high_freq_energy, 4}, {h.low_freq_energy, 4}, {h.freq_ratio, 4}, {h.local_contrast_mean, 2},
+            {h.local_contrast_std, 2}, {h.horizontal_complexity, 2}, {h.vertical_complexity, 2}, {h.diagonal_complexity, 2}};
+        o += r.image + "," + std::to_string(h.width) + "," + std::to_string(h.height) + "," + std::to_string(h.pixels);
+        for (const auto &c : cols) o += "," + fixed((double)c.first, c.second);
+        o += "\n";
+    }
+    return o;
+}
+
 }  // namespace report
 }  // namespace codec_eval

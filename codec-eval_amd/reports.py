@@ -5,7 +5,9 @@ What downstream tools (`pareto`, `stats`, `rd_knee`, codec-iter's baseline compa
 * `ImageReport` / `CorpusReport` JSON  — `serde_json::to_string_pretty` of the structs in
   src/eval/report.rs:14-166 (written by src/eval/session.rs:500-523);
 * the 13-column CSV summary       — src/eval/session.rs:526-584 (`csv` crate, default writer);
-* `Baseline` / `EvalPoint` JSON       — crates/codec-iter/src/baseline.rs:11-47, eval.rs:21-29.
+* `Baseline` / `EvalPoint` JSON       — crates/codec-iter/src/baseline.rs:11-47, eval.rs:21-29;
+* the image-heuristics CSV            — crates/codec-compare/src/image_heuristics.rs:358-400, read back by
+  build-predictor (crates/codec-compare/src/build_predictor.rs:75-100).
 
 Everything here is host-side formatting of scores the device path produced; there is no arithmetic
 on pixels.  serde_json prints f64 with ryu (shortest digits that round-trip, its own exponent
@@ -24,7 +26,8 @@ from typing import Dict, List, Optional
 __all__ = [
     "format_f64", "to_string_pretty", "rust_f64_display", "CodecResult", "ImageReport", "CorpusReport",
     "EvalPoint", "Baseline", "write_image_report", "write_corpus_report", "csv_summary", "save_baseline",
-    "load_baseline", "rfc3339", "chrono_utc_default",
+    "load_baseline", "rfc3339", "chrono_utc_default", "HEURISTICS_CSV_HEADER", "heuristics_csv", "HeuristicRow",
+    "read_heuristics_csv",
 ]
 
 
@@ -428,3 +431,79 @@ def compare_with_baseline(points: List[EvalPoint], baseline: Baseline) -> List[C
         d_bpp, d_s2 = (bpp - base[q][0], s2 - base[q][1]) if q in base else (0.0, 0.0)
         rows.append(ComparisonRow(q, bpp, s2, d_bpp, d_s2, d_s2 - d_bpp * 10.0))
     return rows
+
+
+# ---- codec-compare's image heuristics (crates/codec-compare/src/image_heuristics.rs:358-400) -----------------------
+HEURISTICS_CSV_HEADER = [
+    "image", "width", "height", "pixels",
+    "mean_luminance", "luminance_variance", "luminance_std",
+    "edge_strength_mean", "edge_strength_max", "edge_density",
+    "flat_block_pct", "low_var_block_pct", "mid_var_block_pct", "high_var_block_pct", "detail_block_pct",
+    "block_variance_mean", "block_variance_std",
+    "color_variance", "saturation_mean", "saturation_std",
+    "high_freq_energy", "low_freq_energy", "freq_ratio",
+    "local_contrast_mean", "local_contrast_std",
+    "horizontal_complexity", "vertical_complexity", "diagonal_complexity",
+]
+# decimal places of each f32 column after `pixels`, from the writeln! format string at image_heuristics.rs:376
+_HEURISTICS_PLACES = [2, 2, 2, 2, 2, 4, 2, 2, 2, 2, 2, 2, 2, 2, 4, 4, 4, 4, 4, 2, 2, 2, 2, 2]
+
+
+def heuristics_csv(rows) -> str:
+    """The image-heuristics CSV byte for byte: the header, then one line per row (objects with the ImageHeuristics
+    fields, e.g. codec_eval_amd.ImageHeuristics).  The reference writes with writeln! rather than the csv crate: the
+    image name goes out unquoted, and each f32 at its exact binary value with {:.2} / {:.4}."""
+    out = io.StringIO()
+    out.write(",".join(HEURISTICS_CSV_HEADER) + "\n")
+    for r in rows:
+        cells = [str(r.image), str(int(r.width)), str(int(r.height)), str(int(r.pixels))]
+        cells += [_fixed(float(getattr(r, f)), p) for f, p in zip(HEURISTICS_CSV_HEADER[4:], _HEURISTICS_PLACES)]
+        out.write(",".join(cells) + "\n")
+    return out.getvalue()
+
+
+@dataclass
+class HeuristicRow:
+    """HeuristicRow, crates/codec-compare/src/build_predictor.rs:42-54."""
+    image: str
+    flat_block_pct: float
+    edge_strength_mean: float
+    edge_density: float
+    detail_block_pct: float
+    block_variance_mean: float
+    high_freq_energy: float
+    freq_ratio: float
+    local_contrast_mean: float
+    saturation_mean: float
+    luminance_std: float
+
+
+# HeuristicRow field -> CSV column, parse_heuristics_csv (build_predictor.rs:86-95)
+_PREDICTOR_COLUMNS = {"flat_block_pct": 10, "edge_strength_mean": 7, "edge_density": 9, "detail_block_pct": 14,
+                      "block_variance_mean": 15, "high_freq_energy": 20, "freq_ratio": 22, "local_contrast_mean": 23,
+                      "saturation_mean": 18, "luminance_std": 6}
+
+
+def _parse_f64_or_zero(s: str) -> float:
+    """`record[i].parse::<f64>().unwrap_or(0.0)`: Rust's parser takes no surrounding whitespace, no underscores."""
+    if s != s.strip() or "_" in s:
+        return 0.0
+    try:
+        return float(s)
+    except ValueError:
+        return 0.0
+
+
+def read_heuristics_csv(source) -> Dict[str, HeuristicRow]:
+    """parse_heuristics_csv (build_predictor.rs:75-100): image -> HeuristicRow from the columns build-predictor uses; a
+    later row of the same image replaces an earlier one.  `source` is a path or the CSV text (anything with a comma)."""
+    import csv
+
+    text = source if "," in source else open(source, encoding="utf-8", newline="").read()
+    rows = list(csv.reader(io.StringIO(text, newline="")))
+    out: Dict[str, HeuristicRow] = {}
+    for rec in rows[1:]:  # csv::Reader has headers by default
+        if not rec:
+            continue
+        out[rec[0]] = HeuristicRow(rec[0], **{f: _parse_f64_or_zero(rec[i]) for f, i in _PREDICTOR_COLUMNS.items()})
+    return out

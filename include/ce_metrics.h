@@ -326,6 +326,67 @@ int ce_ref_ssimulacra2_maps(ce_ref *ref, uint32_t scale, uint32_t channel, uint3
                             uint32_t block, float *maps, size_t maps_floats, double *norms);
 void ce_ref_destroy(ce_ref *ref);
 
+/* ---- image heuristics: ImageHeuristics of crates/codec-compare/src/image_heuristics.rs:22-63 ----------------------
+ * compute_heuristics (image_heuristics.rs:76-305), whose CSV (:358-400) build-predictor reads to pick an encoder
+ * (crates/codec-compare/src/build_predictor.rs:75-100).  Same field names and order; the image name stays with the caller.
+ * Every per-pixel and per-block value (gray, gradients, 3x3 contrast, saturation, adjacent differences, each 8x8 block's
+ * sequential f32 mean and variance) is the reference's f32 arithmetic, so width .. pixels, edge_strength_max,
+ * edge_density, the five *_block_pct, analyze_detail_block_pct, high/low_freq_energy and freq_ratio equal the
+ * reference's bit for bit.  The whole-image sums behind the other fields (means, variances, standard deviations, the
+ * complexities) take the reference's f32 terms (a variance's (v - mean)^2 with the f32 mean), add them in f64 in an
+ * order fixed by the image's shape alone, round once to f32 and divide by the reference's f32 divisor: deterministic,
+ * but not the reference's sequential f32 accumulation (DESIGN.md section 2 gives the measured gap).  Images under 8 x 8
+ * have no blocks: their block fields are 0 (num_blocks.max(1), image_heuristics.rs:136).  Images under 3 x 3 return
+ * CE_ERR_TOO_SMALL (the reference underflows width - 2 there). */
+typedef struct ce_image_heuristics {
+    uint64_t width;
+    uint64_t height;
+    uint64_t pixels;
+    float mean_luminance;
+    float luminance_variance;
+    float luminance_std;
+    float edge_strength_mean;
+    float edge_strength_max;
+    float edge_density;
+    float flat_block_pct;
+    float low_var_block_pct;
+    float mid_var_block_pct;
+    float high_var_block_pct;
+    float detail_block_pct;
+    float block_variance_mean;
+    float block_variance_std;
+    float color_variance;
+    float saturation_mean;
+    float saturation_std;
+    float high_freq_energy;
+    float low_freq_energy;
+    float freq_ratio;
+    float local_contrast_mean;
+    float local_contrast_std;
+    float horizontal_complexity;
+    float vertical_complexity;
+    float diagonal_complexity;
+    /* analyze-image's detail_block_pct (crates/codec-compare/src/analyze_image.rs:94-96): blocks with variance > 1000,
+     * over num_blocks.max(1) like the fields above (0, not analyze-image's NaN, without blocks) */
+    float analyze_detail_block_pct;
+} ce_image_heuristics;
+
+/* which slab ce_batch_image_heuristics reads */
+enum ce_batch_images { CE_BATCH_REFERENCES = 0, CE_BATCH_TESTS = 1 };
+
+/* compute_heuristics (image_heuristics.rs:76) of one packed RGB8 image.  CE_ERR_BAD_LENGTH unless len = w * h * 3,
+ * then CE_ERR_TOO_SMALL for a width or height under 3. */
+int ce_image_heuristics_rgb8(ce_ctx *ctx, const uint8_t *rgb, size_t len, size_t width, size_t height, ce_image_heuristics *out);
+/* compute_heuristics of images [first, first + count) already resident in a batch's references (which =
+ * CE_BATCH_REFERENCES) or tests (CE_BATCH_TESTS) slab - the source images of a corpus sweep, with no second upload
+ * (full_comparison.rs uploads every source image; image_heuristics.rs:334-345 decodes it again).  Sees every image
+ * written by ce_batch_set_* / bind_pair before the call; launches nothing of the metrics and leaves the last launch's
+ * scores and maps as they were.  out has count entries.  CE_ERR_INVALID_ARG for an unknown slab, count = 0 or a range
+ * past the slab, CE_ERR_TOO_SMALL for a batch under 3 x 3. */
+int ce_batch_image_heuristics(ce_batch *b, uint32_t which, uint32_t first, uint32_t count, ce_image_heuristics *out);
+/* the same for the image of a reference handle (Ssimulacra2Reference::new, crates/codec-iter/src/eval.rs:138-149) */
+int ce_ref_image_heuristics(ce_ref *ref, ce_image_heuristics *out);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------ */
 /* Bracket every kernel launch with a HIP event pair, recorded on the stream the kernel is launched on,
  * and accumulate per-kernel time.  on = 0: off (default).  on = 2: events only; the batch keeps its
