@@ -114,6 +114,20 @@ impl HipMetrics {
         Ok(s.into())
     }
 
+    /// One pair of packed 16-bit RGB at its own precision (`ce_eval_pair_deep`): what a decoder hands over as
+    /// `PixelData::Rgb16`, scored without `to_8bit`.  Sample `v` of a side of depth `d` (8, 10, 12 or 16) means the sRGB
+    /// value `v / (2^d - 1)`; an 8-bit source widened to u16 goes in as depth 8.  PSNR is reported for equal depths only.
+    pub fn calculate_metrics_deep(&mut self, reference: &[u16], ref_depth: u32, test: &[u16], test_depth: u32, width: u32,
+                                  height: u32, m: Metrics) -> Result<Scores, HipError> {
+        let mut s = sys::ce_scores::default();
+        let rc = unsafe {
+            sys::ce_eval_pair_deep(self.ctx, reference.as_ptr(), reference.len() * 2, ref_depth, test.as_ptr(), test.len() * 2,
+                                   test_depth, width, height, m.mask(), m.flags(), sys::CE_DEFAULT_INTENSITY_TARGET, &mut s)
+        };
+        self.check(rc, width, height, test.len())?;  // three samples per pixel, as the bytes of an RGB8 image
+        Ok(s.into())
+    }
+
     /// The whole `(codec, quality)` grid of `evaluate_image` (session.rs:375-376) in one call: decode every cell
     /// first, then pass `(reference, decoded, width, height)` per cell.  Cells that share a reference slice share
     /// one device slot.  Per-cell failures come back as `Err` in their position.

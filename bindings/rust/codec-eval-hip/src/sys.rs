@@ -44,6 +44,9 @@ pub const CE_PIXEL_RGB8: c_int = 0;
 pub const CE_PIXEL_RGBA8: c_int = 1;
 pub const CE_PIXEL_RGB16_10BIT: c_int = 2;
 pub const CE_PIXEL_RGBA16_10BIT: c_int = 3;
+/// deep batches only (`ce_batch_create_deep`): u16 samples at the side's own depth
+pub const CE_PIXEL_RGB16: c_int = 4;
+pub const CE_PIXEL_RGBA16: c_int = 5;
 
 /// `ce_scores` (40 bytes): a score is meaningful iff its bit is set in `valid`.
 #[repr(C)]
@@ -150,6 +153,14 @@ extern "C" {
                              flags: u32, intensity_target: c_float, out: *mut ce_scores) -> c_int;
     pub fn ce_batch_create(ctx: *mut ce_ctx, width: u32, height: u32, max_refs: u32, max_pairs: u32, out: *mut *mut ce_batch) -> c_int;
     pub fn ce_batch_destroy(b: *mut ce_batch);
+    pub fn ce_pixel_bytes(format: c_int) -> usize;
+    pub fn ce_batch_create_deep(ctx: *mut ce_ctx, width: u32, height: u32, max_refs: u32, max_pairs: u32, ref_depth: u32,
+                                test_depth: u32, out: *mut *mut ce_batch) -> c_int;
+    pub fn ce_estimate_batch_bytes_deep(width: u32, height: u32, n_refs: u32, n_pairs: u32, metric_mask: u32, ref_depth: u32,
+                                        test_depth: u32) -> usize;
+    pub fn ce_eval_pair_deep(ctx: *mut ce_ctx, reference: *const u16, reference_len: usize, ref_depth: u32, test: *const u16,
+                             test_len: usize, test_depth: u32, width: u32, height: u32, metric_mask: u32, flags: u32,
+                             intensity_target: c_float, out: *mut ce_scores) -> c_int;
     pub fn ce_batch_set_reference(b: *mut ce_batch, ref_index: u32, rgb: *const u8, len: usize) -> c_int;
     pub fn ce_batch_set_test(b: *mut ce_batch, pair_index: u32, ref_index: u32, rgb: *const u8, len: usize) -> c_int;
     pub fn ce_batch_set_reference_fmt(b: *mut ce_batch, ref_index: u32, pixels: *const c_void, len: usize, format: c_int) -> c_int;

@@ -35,6 +35,8 @@ FLAG_XYB_ROUNDTRIP = 1
 FLAG_BUTTERAUGLI_DIFFMAP = 1 << 1
 FLAG_SSIMULACRA2_MAPS = 1 << 2
 PIXEL_RGB8, PIXEL_RGBA8, PIXEL_RGB16_10BIT, PIXEL_RGBA16_10BIT = 0, 1, 2, 3
+PIXEL_RGB16, PIXEL_RGBA16 = 4, 5  # deep batches only (Context.batch_deep): u16 samples at the side's own depth
+DEEP_DEPTHS = (8, 10, 12, 16)
 BATCH_REFERENCES, BATCH_TESTS = 0, 1  # enum ce_batch_images
 DEFAULT_INTENSITY_TARGET = 80.0
 DSSIM_MAX_LEVELS = 5  # CE_DSSIM_MAX_LEVELS
@@ -158,6 +160,10 @@ _PROTOTYPES = [
     ("ce_eval_batch_lut", _i, [_vp, _sz, C.POINTER(CePairDesc), C.POINTER(_vp), _u32, _u32, _f32, C.POINTER(CeScores)]),
     ("ce_batch_create", _i, [_vp, _u32, _u32, _u32, _u32, C.POINTER(_vp)]),
     ("ce_batch_destroy", None, [_vp]),
+    ("ce_pixel_bytes", _sz, [_i]),
+    ("ce_batch_create_deep", _i, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, C.POINTER(_vp)]),
+    ("ce_estimate_batch_bytes_deep", _sz, [_u32, _u32, _u32, _u32, _u32, _u32, _u32]),
+    ("ce_eval_pair_deep", _i, [_vp, _vp, _sz, _u32, _vp, _sz, _u32, _u32, _u32, _u32, _u32, _f32, C.POINTER(CeScores)]),
     ("ce_batch_set_reference", _i, [_vp, _u32, _u8p, _sz]),
     ("ce_batch_set_test", _i, [_vp, _u32, _u32, _u8p, _sz]),
     ("ce_batch_set_reference_fmt", _i, [_vp, _u32, _vp, _sz, _i]),
@@ -226,6 +232,20 @@ def lib() -> C.CDLL:
 def estimate_batch_bytes(width: int, height: int, n_refs: int, n_pairs: int, config: "MetricConfig") -> int:
     """Upper estimate of the device bytes a Batch of this shape holds once `config`'s metrics have run."""
     return int(lib().ce_estimate_batch_bytes(width, height, n_refs, n_pairs, config.mask))
+
+
+def estimate_batch_bytes_deep(width: int, height: int, n_refs: int, n_pairs: int, config: "MetricConfig", ref_depth: int,
+                              test_depth: int) -> int:
+    """estimate_batch_bytes for a deep batch (Context.batch_deep) of these depths."""
+    return int(lib().ce_estimate_batch_bytes_deep(width, height, n_refs, n_pairs, config.mask, ref_depth, test_depth))
+
+
+def _buf16(a) -> np.ndarray:
+    """Borrowed view as a flat contiguous u16 array (the packed samples of a deep image)."""
+    arr = np.asarray(a)
+    if arr.dtype != np.uint16:
+        raise TypeError("deep pixel buffers must be uint16")
+    return np.ascontiguousarray(arr).reshape(-1)
 
 
 def version() -> str:
@@ -659,6 +679,20 @@ class Context:
                                        config.mask, config.flags, intensity_target, C.byref(s)))
         return MetricResult.from_c(s)
 
+    def eval_pair_deep(self, reference, ref_depth: int, test, test_depth: int, width: int, height: int, config: MetricConfig,
+                       intensity_target: float = DEFAULT_INTENSITY_TARGET) -> MetricResult:
+        """calculate_metrics over packed uint16 RGB at its own precision (ce_eval_pair_deep): sample v of a side of depth d
+        means the sRGB value v / (2^d - 1).  PSNR is reported only for equal depths."""
+        r, t = _buf16(reference), _buf16(test)
+        s = CeScores()
+        self._check(lib().ce_eval_pair_deep(self._h, r.ctypes.data, r.nbytes, ref_depth, t.ctypes.data, t.nbytes, test_depth, width,
+                                            height, config.mask, config.flags, intensity_target, C.byref(s)))
+        return MetricResult.from_c(s)
+
+    def batch_deep(self, width: int, height: int, max_refs: int, max_pairs: int, ref_depth: int, test_depth: int) -> "Batch":
+        """A Batch whose slabs hold uint16 samples of the given depths (8, 10, 12 or 16 bits per side)."""
+        return Batch(self, width, height, max_refs, max_pairs, depths=(ref_depth, test_depth))
+
     def host_buffer(self, nbytes: int) -> np.ndarray:
         """`nbytes` of page-locked host memory as a flat uint8 array (ce_host_alloc; freed when the array and every view of
         it are gone): images placed here are uploaded by DMA straight from the buffer, overlapped with the kernels."""
@@ -745,11 +779,23 @@ class ColorTable:
 class Batch:
     """HBM-resident grid of (reference, test) pairs of one shape (ce_batch_*)."""
 
-    def __init__(self, ctx: Context, width: int, height: int, max_refs: int, max_pairs: int):
+    def __init__(self, ctx: Context, width: int, height: int, max_refs: int, max_pairs: int,
+                 depths: Optional[Tuple[int, int]] = None):
+        """depths=(reference depth, test depth): a deep batch (ce_batch_create_deep) - set_reference / set_test then also
+        take uint16 arrays ([h, w, 3] or flat RGB, [h, w, 4] RGBA) of that side's depth."""
         self.ctx, self.width, self.height = ctx, width, height
         self.max_refs, self.max_pairs = max_refs, max_pairs
+        self.depths = tuple(depths) if depths is not None else None
         self._h = C.c_void_p()
-        ctx._check(lib().ce_batch_create(ctx._h, width, height, max_refs, max_pairs, C.byref(self._h)))
+        if self.depths is None:
+            ctx._check(lib().ce_batch_create(ctx._h, width, height, max_refs, max_pairs, C.byref(self._h)))
+        else:
+            ctx._check(lib().ce_batch_create_deep(ctx._h, width, height, max_refs, max_pairs, self.depths[0], self.depths[1],
+                                                  C.byref(self._h)))
+
+    @staticmethod
+    def _deep_fmt(a: np.ndarray) -> int:
+        return PIXEL_RGBA16 if a.ndim == 3 and a.shape[-1] == 4 else PIXEL_RGB16
 
     def close(self):
         if self._h and self.ctx._h:
@@ -763,10 +809,14 @@ class Batch:
             pass
 
     def set_reference(self, ref_index: int, rgb):
+        if np.asarray(rgb).dtype == np.uint16:
+            return self.set_reference_fmt(ref_index, rgb, self._deep_fmt(np.asarray(rgb)))
         r = _buf(rgb)
         self.ctx._check(lib().ce_batch_set_reference(self._h, ref_index, r.ctypes.data, r.size))
 
     def set_test(self, pair_index: int, ref_index: int, rgb):
+        if np.asarray(rgb).dtype == np.uint16:
+            return self.set_test_fmt(pair_index, ref_index, rgb, self._deep_fmt(np.asarray(rgb)))
         t = _buf(rgb)
         self.ctx._check(lib().ce_batch_set_test(self._h, pair_index, ref_index, t.ctypes.data, t.size))
 

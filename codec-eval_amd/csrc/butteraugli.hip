@@ -265,20 +265,26 @@ constexpr int FT = 32, FR = FT + 4;
 // HALF: the half-resolution level - its linear RGB is the 2x2 average of the full-resolution image's (Subsample2x: the
 // four quarter-weighted samples added in row-major order, the last odd row / column doubled), formed here from the u8
 // source instead of in a pass of its own; gi = the full-resolution geometry.
-template <bool HALF>
+// T: the sample type - uint8_t (the 256-entry table in LDS, packed loads on interior tiles) or the uint16_t of a deep batch
+// (2^depth entries per side in global memory, lut for the references and lut_test for the distorted images; every tile
+// takes the per-sample loads of the border path)
+template <bool HALF, typename T>
 __global__ __launch_bounds__(TPB) void k_ba_front(const uint8_t *__restrict__ refs, const uint8_t *__restrict__ tests,
-                                                  const float *__restrict__ lut, geom gi,
+                                                  const float *__restrict__ lut, const float *__restrict__ lut_test, geom gi,
                                                   float *__restrict__ xyb, geom g, float w0, float w1, float w2,
                                                   float intensity_target, size_t img_bytes, uint32_t n_refs_used, uint32_t max_refs,
                                                   uint32_t z0)
 {
     __shared__ float L[3][FR * FR];   // linear, region = tile + 2
     __shared__ float H[3][FR * FT];   // row-blurred: FR rows x FT columns
+    constexpr bool U8 = sizeof(T) == 1;
     __shared__ float s_lut[256];
-    s_lut[threadIdx.x] = lut[threadIdx.x];
+    if (U8) s_lut[threadIdx.x] = lut[threadIdx.x];
     const uint32_t z = blockIdx.z + z0, slot = slot_of(z, n_refs_used, max_refs);
     const int w = (int)g.w, h = (int)g.h, x0 = blockIdx.x * FT, y0 = blockIdx.y * FT, gx0 = x0 - 2, gy0 = y0 - 2;
     const uint8_t *src8 = z < n_refs_used ? refs + (size_t)z * img_bytes : tests + (size_t)(z - n_refs_used) * img_bytes;
+    const T *srcT = reinterpret_cast<const T *>(src8);
+    const float *tab = U8 ? s_lut : (z < n_refs_used ? lut : lut_test);
     const int W8 = HALF ? (int)gi.w : w, H8 = HALF ? (int)gi.h : h;  // the u8 image
     __syncthreads();
     const bool interior = gx0 >= 0 && gy0 >= 0 && gx0 + FR <= w && gy0 + FR <= h;
@@ -289,7 +295,7 @@ __global__ __launch_bounds__(TPB) void k_ba_front(const uint8_t *__restrict__ re
         const uint32_t d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3], sh = (uint32_t)(a & 3);
         v0 = __builtin_amdgcn_alignbyte(d1, d0, sh), v1 = __builtin_amdgcn_alignbyte(d2, d1, sh), v2 = __builtin_amdgcn_alignbyte(d3, d2, sh);
     };
-    if (!HALF && interior) {
+    if (U8 && !HALF && interior) {
         // four pixels per task; nine tasks per row of the region
         for (int i = threadIdx.x; i < FR * (FR / 4); i += TPB) {
             const int ly = i / (FR / 4), lx = 4 * (i % (FR / 4));
@@ -301,7 +307,7 @@ __global__ __launch_bounds__(TPB) void k_ba_front(const uint8_t *__restrict__ re
             L[0][o + 2] = s_lut[(v1 >> 16) & 255u], L[1][o + 2] = s_lut[v1 >> 24], L[2][o + 2] = s_lut[v2 & 255u];
             L[0][o + 3] = s_lut[(v2 >> 8) & 255u], L[1][o + 3] = s_lut[(v2 >> 16) & 255u], L[2][o + 3] = s_lut[v2 >> 24];
         }
-    } else if (HALF && interior && 2 * (gx0 + FR) <= W8 && 2 * (gy0 + FR) <= H8) {
+    } else if (U8 && HALF && interior && 2 * (gx0 + FR) <= W8 && 2 * (gy0 + FR) <= H8) {
         // two half-resolution elements (2 x 4 u8 pixels) per task: ((0 + q00) + q01) + q10) + q11, q = 0.25 * linear
         for (int i = threadIdx.x; i < FR * (FR / 2); i += TPB) {
             const int ly = i / (FR / 2), lx = 2 * (i % (FR / 2));
@@ -325,10 +331,10 @@ __global__ __launch_bounds__(TPB) void k_ba_front(const uint8_t *__restrict__ re
         const int lx = i % FR, ly = i / FR, X = gx0 + lx, Y = gy0 + ly;
         if (X >= 0 && X < w && Y >= 0 && Y < h) {
             if (!HALF) {
-                const uint8_t *px = src8 + ((size_t)Y * w + X) * 3;
-                L[0][i] = s_lut[px[0]];
-                L[1][i] = s_lut[px[1]];
-                L[2][i] = s_lut[px[2]];
+                const T *px = srcT + ((size_t)Y * w + X) * 3;
+                L[0][i] = tab[px[0]];
+                L[1][i] = tab[px[1]];
+                L[2][i] = tab[px[2]];
             } else {
                 float acc[3] = {0.0f, 0.0f, 0.0f};
 #pragma unroll
@@ -337,9 +343,9 @@ __global__ __launch_bounds__(TPB) void k_ba_front(const uint8_t *__restrict__ re
                     for (int dx = 0; dx < 2; dx++) {
                         const int ix = 2 * X + dx, iy = 2 * Y + dy;
                         if (ix < W8 && iy < H8) {
-                            const uint8_t *px = src8 + ((size_t)iy * W8 + ix) * 3;
+                            const T *px = srcT + ((size_t)iy * W8 + ix) * 3;
 #pragma unroll
-                            for (int c = 0; c < 3; c++) acc[c] += 0.25f * s_lut[px[c]];
+                            for (int c = 0; c < 3; c++) acc[c] += 0.25f * tab[px[c]];
                         }
                     }
 #pragma unroll
@@ -1352,13 +1358,22 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
         // ---- per image slot: PsychoImage ----
         const plane_sel s3{3, 0, 3};
         const dim3 ft((d.w + FT - 1) / FT, (d.h + FT - 1) / FT, nz);
-        if (l == 0) {
-            CE_LAUNCH_ON(ctx, st, "ba_front_u8", k_ba_front<false>, ft, dim3(TPB), 0, d_refs, b->d_tests, ctx->d_lut_ssim2, g, sC, g, w0, w1, w2,
-                      intensity_target, b->img_bytes, n_refs_used, mr, z0);
+        const auto &pd = b->ba[0];
+        const geom gfull{pd.w, pd.h, pd.pitch, pd.plane};
+        if (b->depth[0]) {  // a deep batch: u16 samples, one table per side (rule 0, the f64 curve)
+            const float *lr = b->deep_lut[0][0], *lt = b->deep_lut[0][1];
+            if (l == 0)
+                CE_LAUNCH_ON(ctx, st, "ba_front_u16", (k_ba_front<false, uint16_t>), ft, dim3(TPB), 0, d_refs, b->d_tests, lr, lt, g, sC, g,
+                             w0, w1, w2, intensity_target, b->img_bytes, n_refs_used, mr, z0);
+            else
+                CE_LAUNCH_ON(ctx, st, "ba_front_half_u16", (k_ba_front<true, uint16_t>), ft, dim3(TPB), 0, d_refs, b->d_tests, lr, lt, gfull,
+                             sC, g, w0, w1, w2, intensity_target, b->img_bytes, n_refs_used, mr, z0);
+        } else if (l == 0) {
+            CE_LAUNCH_ON(ctx, st, "ba_front_u8", (k_ba_front<false, uint8_t>), ft, dim3(TPB), 0, d_refs, b->d_tests, ctx->d_lut_ssim2,
+                         ctx->d_lut_ssim2, g, sC, g, w0, w1, w2, intensity_target, b->img_bytes, n_refs_used, mr, z0);
         } else {
-            const auto &pd = b->ba[0];
-            CE_LAUNCH_ON(ctx, st, "ba_front_half", k_ba_front<true>, ft, dim3(TPB), 0, d_refs, b->d_tests, ctx->d_lut_ssim2,
-                      geom{pd.w, pd.h, pd.pitch, pd.plane}, sC, g, w0, w1, w2, intensity_target, b->img_bytes, n_refs_used, mr, z0);
+            CE_LAUNCH_ON(ctx, st, "ba_front_half", (k_ba_front<true, uint8_t>), ft, dim3(TPB), 0, d_refs, b->d_tests, ctx->d_lut_ssim2,
+                         ctx->d_lut_ssim2, gfull, sC, g, w0, w1, w2, intensity_target, b->img_bytes, n_refs_used, mr, z0);
         }
         // LF = blur(xyb, 7.156) -> psy[LF0..2]
         // SeparateFrequencies: row blur of a band, then column blur fused with the pointwise split (k_ba_blur_v_split)

@@ -113,13 +113,37 @@ int read_ssim2_maps(ce_batch *b, uint32_t scale, uint32_t channel, uint32_t kind
     return ce_ssim2_read_maps(b, scale, channel, kind, first, count, block, maps, norms);
 }
 
-double psnr_from_sse(unsigned long long sse, size_t w, size_t h)
+double psnr_from_sse(unsigned long long sse, size_t w, size_t h, double maxv = 255.0)
 {
-    // src/metrics/mod.rs:317,324-330
+    // src/metrics/mod.rs:317,324-330 (a deep batch: 255 replaced by its 2^depth - 1)
     const double pixel_count = (double)(w * h * 3);
     const double mse = (double)sse / pixel_count;
     if (mse == 0.0) return INFINITY;
-    return 10.0 * std::log10(255.0 * 255.0 / mse);
+    return 10.0 * std::log10(maxv * maxv / mse);
+}
+
+bool deep_depth_ok(uint32_t d) { return d == 8 || d == 10 || d == 12 || d == 16; }
+
+// The sRGB -> linear table of a deep batch's side on the device: 2^depth entries by `rule` (0: ce_build_srgb_table_f64,
+// 1: ce_build_srgb_table_powf), built once per context and kept (ce_ctx::deep_tables).
+int ce_deep_table(ce_ctx *ctx, uint32_t depth, int rule, const float **out)
+{
+    const auto key = std::make_pair(depth, rule);
+    auto it = ctx->deep_tables.find(key);
+    if (it == ctx->deep_tables.end()) {
+        const uint32_t maxv = (1u << depth) - 1u;
+        std::vector<float> host((size_t)maxv + 1);
+        if (rule == 0) ce_build_srgb_table_f64(host.data(), maxv); else ce_build_srgb_table_powf(host.data(), maxv);
+        float *d = nullptr;
+        CE_HIP(ctx, hipMalloc(&d, host.size() * sizeof(float)));
+        if (hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+            hipFree(d);
+            return fail(ctx, CE_ERR_BACKEND, "H2D failed (deep sRGB table)");
+        }
+        it = ctx->deep_tables.emplace(key, d).first;
+    }
+    *out = it->second;
+    return CE_OK;
 }
 
 }  // namespace
@@ -369,6 +393,10 @@ void ce_ctx_destroy(ce_ctx *ctx)
     ctx->shape_pool.clear();
     ce_batch_destroy(ctx->leaf_map);
     ctx->leaf_map = nullptr;
+    ce_batch_destroy(ctx->leaf_deep);
+    ctx->leaf_deep = nullptr;
+    for (auto &kv : ctx->deep_tables) hipFree(kv.second);
+    ctx->deep_tables.clear();
     if (ctx->up2_stream) hipStreamSynchronize(ctx->up2_stream), hipStreamDestroy(ctx->up2_stream), hipEventDestroy(ctx->ev_up2);
     for (auto &st : ctx->aux_stream)  // after the last batch that may still drain them
         if (st) hipStreamSynchronize(st), hipStreamDestroy(st), st = nullptr;
@@ -413,12 +441,18 @@ const char *ce_last_error(const ce_ctx *ctx) { return ctx ? ctx->err.c_str() : g
 
 // ---- resident batch ------------------------------------------------------------------------
 
-int ce_batch_create(ce_ctx *ctx, uint32_t width, uint32_t height, uint32_t max_refs, uint32_t max_pairs,
-                    ce_batch **out)
+// ref_depth = test_depth = 0: an RGB8 batch; otherwise a deep one (checked by the caller)
+static int batch_create(ce_ctx *ctx, uint32_t width, uint32_t height, uint32_t max_refs, uint32_t max_pairs, uint32_t ref_depth,
+                        uint32_t test_depth, ce_batch **out)
 {
     if (!ctx || !out || width == 0 || height == 0 || max_refs == 0 || max_pairs == 0) return CE_ERR_INVALID_ARG;
     *out = nullptr;
     CE_HIP(ctx, hipSetDevice(ctx->device));
+    const float *deep_lut[2][2] = {};
+    if (ref_depth)
+        for (int rule = 0; rule < 2; rule++)
+            for (int side = 0; side < 2; side++)
+                if (int rc = ce_deep_table(ctx, side ? test_depth : ref_depth, rule, &deep_lut[rule][side])) return rc;
     ce_batch *b = new (std::nothrow) ce_batch();
     if (!b) return CE_ERR_BACKEND;
     b->ctx = ctx;
@@ -426,7 +460,9 @@ int ce_batch_create(ce_ctx *ctx, uint32_t width, uint32_t height, uint32_t max_r
     b->h = height;
     b->max_refs = max_refs;
     b->max_pairs = max_pairs;
-    b->img_bytes = (size_t)width * height * 3;
+    b->img_bytes = (size_t)width * height * (ref_depth ? 6 : 3);
+    b->depth[0] = ref_depth, b->depth[1] = test_depth;
+    std::memcpy(b->deep_lut, deep_lut, sizeof(deep_lut));
     b->h_pair_ref.assign(max_pairs, 0);
     int rc = CE_OK;
     auto chk = [&](hipError_t e, const char *what) {
@@ -459,6 +495,22 @@ int ce_batch_create(ce_ctx *ctx, uint32_t width, uint32_t height, uint32_t max_r
     }
     *out = b;
     return CE_OK;
+}
+
+int ce_batch_create(ce_ctx *ctx, uint32_t width, uint32_t height, uint32_t max_refs, uint32_t max_pairs, ce_batch **out)
+{
+    return batch_create(ctx, width, height, max_refs, max_pairs, 0, 0, out);
+}
+
+int ce_batch_create_deep(ce_ctx *ctx, uint32_t width, uint32_t height, uint32_t max_refs, uint32_t max_pairs, uint32_t ref_depth,
+                         uint32_t test_depth, ce_batch **out)
+{
+    if (!ctx || !out) return CE_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (!deep_depth_ok(ref_depth) || !deep_depth_ok(test_depth))
+        return fail(ctx, CE_ERR_INVALID_ARG, "a deep batch's depths must be 8, 10, 12 or 16 bits, got " + std::to_string(ref_depth) +
+                                                 " / " + std::to_string(test_depth));
+    return batch_create(ctx, width, height, max_refs, max_pairs, ref_depth, test_depth, out);
 }
 
 void ce_batch_destroy(ce_batch *b)
@@ -679,19 +731,27 @@ int ce_batch_set_reference(ce_batch *b, uint32_t ref_index, const uint8_t *rgb, 
 {
     if (!b || !rgb) return CE_ERR_INVALID_ARG;
     if (ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "ref_index out of range");
+    if (b->depth[0]) return ce_batch_set_reference_fmt(b, ref_index, rgb, len, CE_PIXEL_RGB8);  // a deep batch: widened on the device
     if (len != b->img_bytes) return bad_length(b->ctx, b->img_bytes, len);
     invalidate_reference_state(b);  // cached reference-side planes are stale
     return upload(b, b->d_refs + (size_t)ref_index * b->img_bytes, rgb);
 }
 
 // pixels in a decoder's format -> wide staging -> device -> ingest kernel writes the RGB8 slab slot
-static int upload_fmt(ce_batch *b, uint8_t *dst, const void *pixels, size_t len, int format)
+// (a deep batch: -> the ingest kernel that writes the u16 slab slot of that side, depth `depth`; 0 = an RGB8 batch)
+static int upload_fmt(ce_batch *b, uint8_t *dst, const void *pixels, size_t len, int format, uint32_t depth)
 {
     ce_ctx *ctx = b->ctx;
     const size_t bpp = ce_pixel_bytes(format), n_px = (size_t)b->w * b->h;
     if (bpp == 0) return fail(ctx, CE_ERR_INVALID_ARG, "unknown pixel format");
+    const bool fmt16 = format == CE_PIXEL_RGB16 || format == CE_PIXEL_RGBA16, fmt8 = format == CE_PIXEL_RGB8 || format == CE_PIXEL_RGBA8;
+    if (!depth && fmt16) return fail(ctx, CE_ERR_INVALID_ARG, "CE_PIXEL_RGB16 / CE_PIXEL_RGBA16 need a deep batch (ce_batch_create_deep)");
+    if (depth && !fmt16 && !fmt8)
+        return fail(ctx, CE_ERR_INVALID_ARG, "the *_10BIT formats round to 8 bits: a deep batch takes CE_PIXEL_RGB16 / CE_PIXEL_RGBA16");
+    if (depth && fmt8 && depth != 8)
+        return fail(ctx, CE_ERR_INVALID_ARG, "an 8-bit image needs a side of depth 8, this one has " + std::to_string(depth));
     if (len != n_px * bpp) return bad_length(ctx, n_px * bpp, len);
-    if (format == CE_PIXEL_RGB8) return upload(b, dst, static_cast<const uint8_t *>(pixels), false);
+    if (format == CE_PIXEL_RGB8 && !depth) return upload(b, dst, static_cast<const uint8_t *>(pixels), false);
     CE_HIP(ctx, hipSetDevice(ctx->device));  // the staging allocations and the ingest launch below go to the context's device
     const int k = b->next_wide;
     b->next_wide ^= 1;
@@ -704,7 +764,8 @@ static int upload_fmt(ce_batch *b, uint8_t *dst, const void *pixels, size_t len,
     if (b->wide_busy[k]) CE_HIP(ctx, hipEventSynchronize(b->ev_wide[k]));  // this staging pair's previous image has been converted
     std::memcpy(b->h_wide[k], pixels, len);
     CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], len, hipMemcpyHostToDevice, b->up_stream));
-    int rc = ce_launch_ingest(ctx, b->up_stream, format, b->d_wide[k], dst, n_px);
+    int rc = depth ? ce_launch_ingest_deep(ctx, b->up_stream, format, depth, b->d_wide[k], reinterpret_cast<uint16_t *>(dst), n_px)
+                   : ce_launch_ingest(ctx, b->up_stream, format, b->d_wide[k], dst, n_px);
     if (rc != CE_OK) return rc;
     CE_HIP(ctx, hipEventRecord(b->ev_wide[k], b->up_stream));
     b->wide_busy[k] = true;
@@ -717,7 +778,7 @@ int ce_batch_set_reference_fmt(ce_batch *b, uint32_t ref_index, const void *pixe
     if (!b || !pixels) return CE_ERR_INVALID_ARG;
     if (ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "ref_index out of range");
     invalidate_reference_state(b);
-    return upload_fmt(b, b->d_refs + (size_t)ref_index * b->img_bytes, pixels, len, format);
+    return upload_fmt(b, b->d_refs + (size_t)ref_index * b->img_bytes, pixels, len, format, b->depth[0]);
 }
 
 // ---- ICC -> sRGB colour tables ----------------------------------------------------------------------------------------
@@ -774,6 +835,7 @@ static int apply_lut(ce_batch *b, uint8_t *slot, const ce_lut *lut)
 
 int ce_batch_set_reference_lut(ce_batch *b, uint32_t ref_index, const void *pixels, size_t len, int format, const ce_lut *lut)
 {
+    if (b && lut && b->depth[0]) return fail(b->ctx, CE_ERR_INVALID_ARG, "a colour table is 2^24 8-bit colours: not for a deep batch");
     if (int rc = ce_batch_set_reference_fmt(b, ref_index, pixels, len, format)) return rc;
     return apply_lut(b, b->d_refs + (size_t)ref_index * b->img_bytes, lut);
 }
@@ -781,6 +843,7 @@ int ce_batch_set_reference_lut(ce_batch *b, uint32_t ref_index, const void *pixe
 int ce_batch_set_test_lut(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format,
                           const ce_lut *lut)
 {
+    if (b && lut && b->depth[0]) return fail(b->ctx, CE_ERR_INVALID_ARG, "a colour table is 2^24 8-bit colours: not for a deep batch");
     if (int rc = ce_batch_set_test_fmt(b, pair_index, ref_index, pixels, len, format)) return rc;
     return apply_lut(b, b->d_tests + (size_t)pair_index * b->img_bytes, lut);
 }
@@ -801,6 +864,7 @@ int ce_batch_bind_pair(ce_batch *b, uint32_t pair_index, uint32_t ref_index)
 int ce_batch_set_test(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const uint8_t *rgb, size_t len)
 {
     if (!b || !rgb) return CE_ERR_INVALID_ARG;
+    if (b->depth[0]) return ce_batch_set_test_fmt(b, pair_index, ref_index, rgb, len, CE_PIXEL_RGB8);
     if (int rc = ce_batch_bind_pair(b, pair_index, ref_index)) return rc;
     if (len != b->img_bytes) return bad_length(b->ctx, b->img_bytes, len);
     return upload(b, b->d_tests + (size_t)pair_index * b->img_bytes, rgb);
@@ -810,7 +874,7 @@ int ce_batch_set_test_fmt(ce_batch *b, uint32_t pair_index, uint32_t ref_index, 
 {
     if (!b || !pixels) return CE_ERR_INVALID_ARG;
     if (int rc = ce_batch_bind_pair(b, pair_index, ref_index)) return rc;
-    return upload_fmt(b, b->d_tests + (size_t)pair_index * b->img_bytes, pixels, len, format);
+    return upload_fmt(b, b->d_tests + (size_t)pair_index * b->img_bytes, pixels, len, format, b->depth[1]);
 }
 
 void *ce_batch_reference_slab(ce_batch *b)
@@ -827,6 +891,8 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
     ce_ctx *ctx = b->ctx;
     if (n_pairs == 0 || n_pairs > b->max_pairs) return fail(ctx, CE_ERR_INVALID_ARG, "n_pairs out of range");
     if (metric_mask & ~kKnownMetrics) return fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
+    if (b->depth[0] && (flags & CE_FLAG_XYB_ROUNDTRIP))
+        return fail(ctx, CE_ERR_INVALID_ARG, "CE_FLAG_XYB_ROUNDTRIP quantises to 8 bits by definition: not for a deep batch");
     b->ba_map_pairs = b->ds_map_pairs = 0;  // whatever happens below, no readout returns the maps of an earlier launch
     b->s2_map_pairs = b->s2_norm_pairs = 0;
     CE_HIP(ctx, hipSetDevice(ctx->device));
@@ -995,7 +1061,7 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
             joined |= 1u << k;  // the context's stream waits for it after every chain has been launched
         }
     }
-    if (metric_mask & CE_METRIC_PSNR) {
+    if ((metric_mask & CE_METRIC_PSNR) && b->depth[0] == b->depth[1]) {  // sides of two depths share no integer grid: no PSNR
         int rc = ce_launch_psnr(b, d_refs, n_pairs);
         if (rc != CE_OK) return rc;
     }
@@ -1037,8 +1103,8 @@ int ce_batch_collect(ce_batch *b, uint32_t n_pairs, ce_scores *out)
         ce_scores s{};
         s.status = CE_OK;
         const ce_dev_scores &d = b->h_scores[i];
-        if (mask & CE_METRIC_PSNR) {
-            s.psnr = psnr_from_sse(d.sse, b->w, b->h);
+        if ((mask & CE_METRIC_PSNR) && b->depth[0] == b->depth[1]) {
+            s.psnr = psnr_from_sse(d.sse, b->w, b->h, b->depth[0] ? (double)((1u << b->depth[0]) - 1u) : 255.0);
             s.valid |= CE_METRIC_PSNR;
         }
         if (mask & CE_METRIC_DSSIM) {
@@ -1123,6 +1189,16 @@ size_t ce_estimate_batch_bytes(uint32_t w, uint32_t h, uint32_t n_refs, uint32_t
     }
     if (metric_mask & CE_METRIC_PSNR) bytes += 8.0 * pairs;
     return (size_t)(bytes * 1.2) + (size_t)(allocations * (256u << 10)) + (8u << 20);  // row / pitch padding of the planar buffers
+}
+
+// the u16 slabs hold 6 bytes per pixel instead of 3, and the tables 4 * 2^depth bytes per side and rule; the working sets
+// behind the front ends are the same
+size_t ce_estimate_batch_bytes_deep(uint32_t w, uint32_t h, uint32_t n_refs, uint32_t n_pairs, uint32_t metric_mask, uint32_t ref_depth,
+                                    uint32_t test_depth)
+{
+    if (!deep_depth_ok(ref_depth) || !deep_depth_ok(test_depth)) return 0;
+    const size_t slabs = (size_t)3 * w * h * ((size_t)n_refs + n_pairs);
+    return ce_estimate_batch_bytes(w, h, n_refs, n_pairs, metric_mask) + slabs + (((size_t)8 << ref_depth) + ((size_t)8 << test_depth));
 }
 
 int ce_ctx_memory_info(ce_ctx *ctx, size_t *free_bytes, size_t *total_bytes)
@@ -1338,6 +1414,44 @@ int ce_eval_pair(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, co
     ce_pair_desc d{reference, reference_len, test, test_len, width, height};
     int rc = ce_eval_batch(ctx, 1, &d, metric_mask, flags, intensity_target, out);
     if (rc != CE_OK) return rc;
+    return out->status;
+}
+
+// One pair of packed u16 RGB through the context's one-pair deep batch (kept while shape and depths stay the same).
+// Validation in ce_eval_pair's order: null pointers, empty image, length mismatch, wrong length; then the flags.
+int ce_eval_pair_deep(ce_ctx *ctx, const uint16_t *reference, size_t reference_len, uint32_t ref_depth, const uint16_t *test,
+                      size_t test_len, uint32_t test_depth, uint32_t width, uint32_t height, uint32_t metric_mask, uint32_t flags,
+                      float intensity_target, ce_scores *out)
+{
+    if (!ctx || !out || !reference || !test) return CE_ERR_INVALID_ARG;
+    *out = ce_scores{};
+    if (!deep_depth_ok(ref_depth) || !deep_depth_ok(test_depth))
+        return out->status = fail(ctx, CE_ERR_INVALID_ARG, "depths must be 8, 10, 12 or 16 bits, got " + std::to_string(ref_depth) + " / " +
+                                                               std::to_string(test_depth));
+    if (width == 0 || height == 0) return out->status = CE_ERR_INVALID_ARG;
+    if (reference_len != test_len)
+        return out->status = fail(ctx, CE_ERR_DIM_MISMATCH, "Dimension mismatch: reference " + std::to_string(reference_len) +
+                                                                " bytes, test " + std::to_string(test_len) + " bytes");
+    const size_t want = (size_t)width * height * 6;
+    if (reference_len != want) return out->status = bad_length(ctx, want, reference_len);
+    if (flags & (CE_FLAG_BUTTERAUGLI_DIFFMAP | CE_FLAG_SSIMULACRA2_MAPS))
+        return out->status = fail(ctx, CE_ERR_INVALID_ARG, "map flags need a ce_batch: this call's batch does not outlive it");
+    if (metric_mask & ~kKnownMetrics) return out->status = fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    ce_batch *b = ctx->leaf_deep;
+    if (!b || b->w != width || b->h != height || b->depth[0] != ref_depth || b->depth[1] != test_depth) {
+        ce_batch_destroy(b);
+        ctx->leaf_deep = nullptr;
+        if (int rc = ce_batch_create_deep(ctx, width, height, 1, 1, ref_depth, test_depth, &ctx->leaf_deep)) return out->status = rc;
+        b = ctx->leaf_deep;
+    }
+    int rc = ce_batch_set_reference_fmt(b, 0, reference, reference_len, CE_PIXEL_RGB16);
+    if (rc == CE_OK) rc = ce_batch_set_test_fmt(b, 0, 0, test, test_len, CE_PIXEL_RGB16);
+    if (rc == CE_OK) rc = ce_batch_run(b, 1, metric_mask, flags, intensity_target, out);
+    if (rc != CE_OK) {
+        drain_batch(b);
+        return out->status = rc;
+    }
     return out->status;
 }
 
@@ -1568,6 +1682,7 @@ int ce_batch_image_heuristics(ce_batch *b, uint32_t which, uint32_t first, uint3
 {
     if (!b || !out) return CE_ERR_INVALID_ARG;
     ce_ctx *ctx = b->ctx;
+    if (b->depth[0]) return fail(ctx, CE_ERR_INVALID_ARG, "image heuristics are defined on u8 gray levels: not for a deep batch");
     if (which != CE_BATCH_REFERENCES && which != CE_BATCH_TESTS)
         return fail(ctx, CE_ERR_INVALID_ARG, "image heuristics: unknown slab " + std::to_string(which));
     const uint32_t slots = which == CE_BATCH_TESTS ? b->max_pairs : b->max_refs;

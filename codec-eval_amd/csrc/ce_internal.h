@@ -19,6 +19,9 @@
 #define CE_MAX_SCALES 6      // SSIMULACRA2 pyramid depth
 #define CE_SSIM2_STREAMS 5   // blur(a), blur(b), blur(a*a), blur(b*b), blur(a*b)
 #define CE_DSSIM_SCALES 5    // dssim-core DEFAULT_WEIGHTS.len()
+// where a front end's level 0 comes from: the linear planes of the level below (levels above 0), packed RGB8, or the packed
+// u16 RGB of a deep batch (ce_batch_create_deep)
+enum { CE_SRC_F32 = 0, CE_SRC_U8 = 1, CE_SRC_U16 = 2 };
 static_assert(CE_MAX_SCALES == CE_SSIM2_MAX_SCALES, "the ABI's scale count is the pyramid's");
 
 struct ce_scale_dims {
@@ -62,6 +65,10 @@ struct ce_ctx {
     float *d_lut_ssim2 = nullptr;  // sRGB->linear, f64 formula rounded to f32 (SSIMULACRA2 front end)
     float *d_lut_powf = nullptr;   // sRGB->linear via f32 powf(2.4) (dssim.rs:78-85, xyb.rs:60-66)
     float *d_xyb_thresh = nullptr; // linear->sRGB u8 decision thresholds (xyb.rs:86-88)
+    // sRGB->linear tables of the deep batches, 2^depth entries each, keyed by (depth, rule: 0 = the f64 curve, 1 = f32 powf);
+    // built by the first deep batch that needs one and kept until the context goes (ce_api.cpp: ce_deep_table)
+    std::map<std::pair<uint32_t, int>, float *> deep_tables;
+    struct ce_batch *leaf_deep = nullptr;  // the one-pair deep batch of ce_eval_pair_deep (remade when shape or depths change)
 
     // profiling
     bool prof = false;         // record a HIP event pair around every launch (on the launch's own stream)
@@ -119,7 +126,12 @@ struct ce_xcd_list {
 struct ce_batch {
     ce_ctx *ctx = nullptr;
     uint32_t w = 0, h = 0, max_refs = 0, max_pairs = 0;
-    size_t img_bytes = 0;  // w*h*3
+    size_t img_bytes = 0;  // w*h*3; w*h*6 in a deep batch
+    // A deep batch (ce_batch_create_deep): depth[0] / depth[1] = bits per sample of the reference / test side (8, 10, 12 or
+    // 16), the slabs hold packed u16 RGB and the front ends read them through deep_lut[rule][side] (ce_ctx::deep_tables).
+    // 0 / 0: an RGB8 batch.
+    uint32_t depth[2] = {0, 0};
+    const float *deep_lut[2][2] = {};
 
     uint8_t *d_refs = nullptr;     // [max_refs][h][w][3]
     uint8_t *d_refs_rt = nullptr;  // XYB-roundtripped references (lazily allocated)
@@ -307,8 +319,8 @@ __device__ __forceinline__ float ce_div_noscale(float a, float b) { return ce_di
 
 // ---- kernel launchers (one .hip file per metric) ---------------------------------------
 int ce_launch_psnr(ce_batch *b, const uint8_t *d_refs, uint32_t n_pairs);
-size_t ce_pixel_bytes(int format);
 int ce_launch_ingest(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, uint8_t *d_dst, size_t n_pixels);
+int ce_launch_ingest_deep(ce_ctx *ctx, hipStream_t stream, int format, uint32_t depth, const void *d_src, uint16_t *d_dst, size_t n_pixels);
 int ce_launch_lut_expand(ce_ctx *ctx, hipStream_t stream, const uint8_t *d_packed, uint32_t *d_table);
 int ce_launch_lut_apply(ce_ctx *ctx, hipStream_t stream, uint8_t *d_rgb, const uint32_t *d_table, size_t n_pixels);
 int ce_ssim2_prepare(ce_batch *b);
@@ -346,5 +358,8 @@ int ce_image_heuristics_run(ce_ctx *ctx, const uint8_t *d_imgs, size_t img_strid
 // host-side constant builders (ce_tables.cpp)
 void ce_build_srgb_lut_f64(float lut[256]);
 void ce_build_srgb_lut_powf(float lut[256]);
+// the same two rules for samples 0 .. maxv meaning v / maxv: lut has maxv + 1 entries
+void ce_build_srgb_table_f64(float *lut, uint32_t maxv);
+void ce_build_srgb_table_powf(float *lut, uint32_t maxv);
 void ce_ssim2_recursive_gaussian(float mul_in[3], float mul_prev[3]);
 bool ce_build_xyb_srgb_thresholds(float thresh[256]);

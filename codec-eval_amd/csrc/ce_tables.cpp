@@ -26,6 +26,25 @@ void ce_build_srgb_lut_powf(float lut[256])
     }
 }
 
+// The same two rules with 255 replaced by maxv = 2^depth - 1 (deep batches): sample v means the sRGB
+// value v / maxv.  With maxv = 255 these are the two tables above, entry for entry; with maxv = 65535 entry 257 * i is entry
+// i of them (257 i / 65535 and i / 255 are the same real number and the division is correctly rounded).
+void ce_build_srgb_table_f64(float *lut, uint32_t maxv)
+{
+    for (uint32_t i = 0; i <= maxv; i++) {
+        const double v = (double)i / (double)maxv;
+        lut[i] = (float)(v <= 0.04045 ? v / 12.92 : std::pow((v + 0.055) / 1.055, 2.4));
+    }
+}
+
+void ce_build_srgb_table_powf(float *lut, uint32_t maxv)
+{
+    for (uint32_t i = 0; i <= maxv; i++) {
+        const float s = (float)i / (float)maxv;
+        lut[i] = s <= 0.04045f ? s / 12.92f : powf((s + 0.055f) / 1.055f, 2.4f);
+    }
+}
+
 // Coefficients of the sigma = 1.5 recursive Gaussian (Charalampidis 2016 truncated-cosine
 // form as derived in libjxl's CreateRecursiveGaussian):
 // three second-order sections k = 1,3,5 with   out_k[n] = n2_k (in[n-N-1] + in[n+N-1])

@@ -213,12 +213,15 @@ __global__ __launch_bounds__(CS_WAVES * 64) __attribute__((amdgpu_waves_per_eu(3
 // neighbour's value and the rows above / below it the first / last row's (replicate that pass's input), as in the compare.
 constexpr int CR_HALO_REF = 4, CR_HALO_DIST = 2;
 
-template <bool FROM_U8, bool REF, bool EDGE>
+// SRC (ce_internal.h: CE_SRC_*): level 0 reads sRGB samples through a table - u8 through the 256 entries in LDS, the u16 of a
+// deep batch through its side's 2^depth entries in global memory (s_lut is that table then) - the levels above read floats
+template <int SRC, bool REF, bool EDGE>
 __device__ __forceinline__ void dssim_create_strip(const uint8_t *__restrict__ src8, const float *const (&srcf)[3], const float *s_lut,
                                                    float *const (&lin_out)[3], float *const (&oimg)[3], float *const (&omu)[3],
                                                    float *const (&osq)[3], const lvl_geom &g, const lvl_geom &gn, int has_next, int xs,
                                                    int y0, int y1)
 {
+    constexpr bool FROM_U8 = SRC == CE_SRC_U8, FROM_U16 = SRC == CE_SRC_U16;
     constexpr int H = REF ? CR_HALO_REF : CR_HALO_DIST, OUT = 64 - 2 * H;
     const int w = (int)g.w, h = (int)g.h, lane = (int)(threadIdx.x & 63);
     const uint32_t pitch = g.pitch;
@@ -241,6 +244,9 @@ __device__ __forceinline__ void dssim_create_strip(const uint8_t *__restrict__ s
             // 32-bit: DSSIM keeps > 300 B per pixel resident, so an image that fits the device is far below 2^32 / 3 pixels
             const uint8_t *px = src8 + (yc * (uint32_t)w + Xc) * 3u;
             o.v[0] = px[0], o.v[1] = px[1], o.v[2] = px[2];
+        } else if (FROM_U16) {
+            const uint16_t *px = reinterpret_cast<const uint16_t *>(src8) + (yc * (uint32_t)w + Xc) * 3u;
+            o.v[0] = px[0], o.v[1] = px[1], o.v[2] = px[2];
         } else {
             const uint32_t ob = (yc * pitch + Xc) * 4u;
 #pragma unroll
@@ -249,7 +255,7 @@ __device__ __forceinline__ void dssim_create_strip(const uint8_t *__restrict__ s
     };
     auto linear = [&](const raw3 &r, rgb &o) {
 #pragma unroll
-        for (int c = 0; c < 3; c++) o.v[c] = FROM_U8 ? s_lut[r.v[c]] : __uint_as_float(r.v[c]);
+        for (int c = 0; c < 3; c++) o.v[c] = (FROM_U8 || FROM_U16) ? s_lut[r.v[c]] : __uint_as_float(r.v[c]);
     };
     constexpr int NS = REF ? 6 : 1;  // planes of the mu / sq passes (a distorted image has none; 1 keeps the types well-formed)
     // a pass after the first at input row r: rows outside the image replicate the first / last row of ITS input
@@ -354,15 +360,17 @@ __device__ __forceinline__ void dssim_create_strip(const uint8_t *__restrict__ s
 }
 
 // grid (tile groups of CS_WAVES, image slots z0 ..): a block's waves are neighbouring strip tiles of ONE slot
-template <bool FROM_U8>
+template <int SRC>
 __global__ __launch_bounds__(CS_WAVES * 64) void k_dssim_create_stream(const uint8_t *__restrict__ refs, const uint8_t *__restrict__ tests,
-                                                                       const float *__restrict__ lut, const float *__restrict__ lin_in,
+                                                                       const float *__restrict__ lut, const float *__restrict__ lut_test,
+                                                                       const float *__restrict__ lin_in,
                                                                        float *__restrict__ lin_out, float *__restrict__ img,
                                                                        float *__restrict__ rimg, float *__restrict__ rmu,
                                                                        float *__restrict__ rsq, lvl_geom g, lvl_geom gn, int has_next,
                                                                        size_t img_bytes, uint32_t n_refs_used, uint32_t max_refs, uint32_t z0,
                                                                        uint32_t rows)
 {
+    constexpr bool FROM_U8 = SRC == CE_SRC_U8, FROM_U16 = SRC == CE_SRC_U16;
     __shared__ float s_lut[256];
     if (FROM_U8) {
         s_lut[threadIdx.x] = lut[threadIdx.x];
@@ -376,7 +384,7 @@ __global__ __launch_bounds__(CS_WAVES * 64) void k_dssim_create_stream(const uin
     const uint32_t tile = blockIdx.x * CS_WAVES + wv;
     if (tile >= strips * ((g.h + rows - 1) / rows)) return;
     const int xs = (int)((tile % strips) * out_cols), y0 = (int)((tile / strips) * rows), y1 = min(y0 + (int)rows, (int)g.h);
-    const uint8_t *src8 = FROM_U8 ? (is_ref ? refs + (size_t)z * img_bytes : tests + (size_t)(z - n_refs_used) * img_bytes) : nullptr;
+    const uint8_t *src8 = (FROM_U8 || FROM_U16) ? (is_ref ? refs + (size_t)z * img_bytes : tests + (size_t)(z - n_refs_used) * img_bytes) : nullptr;
     const float *srcf[3];
     float *lo[3], *oi[3], *om[3], *oq[3];
 #pragma unroll
@@ -387,17 +395,18 @@ __global__ __launch_bounds__(CS_WAVES * 64) void k_dssim_create_stream(const uin
         om[c] = rmu + ((size_t)oslot * 3 + c) * g.plane;
         oq[c] = rsq + ((size_t)oslot * 3 + c) * g.plane;
     }
+    const float *tab = FROM_U16 ? (is_ref ? lut : lut_test) : s_lut;
     const bool edge = xs == 0 || xs + (int)out_cols + (is_ref ? CR_HALO_REF : CR_HALO_DIST) >= (int)g.w;
     if (is_ref) {
         if (edge)
-            dssim_create_strip<FROM_U8, true, true>(src8, srcf, s_lut, lo, oi, om, oq, g, gn, has_next, xs, y0, y1);
+            dssim_create_strip<SRC, true, true>(src8, srcf, tab, lo, oi, om, oq, g, gn, has_next, xs, y0, y1);
         else
-            dssim_create_strip<FROM_U8, true, false>(src8, srcf, s_lut, lo, oi, om, oq, g, gn, has_next, xs, y0, y1);
+            dssim_create_strip<SRC, true, false>(src8, srcf, tab, lo, oi, om, oq, g, gn, has_next, xs, y0, y1);
     } else {
         if (edge)
-            dssim_create_strip<FROM_U8, false, true>(src8, srcf, s_lut, lo, oi, om, oq, g, gn, has_next, xs, y0, y1);
+            dssim_create_strip<SRC, false, true>(src8, srcf, tab, lo, oi, om, oq, g, gn, has_next, xs, y0, y1);
         else
-            dssim_create_strip<FROM_U8, false, false>(src8, srcf, s_lut, lo, oi, om, oq, g, gn, has_next, xs, y0, y1);
+            dssim_create_strip<SRC, false, false>(src8, srcf, tab, lo, oi, om, oq, g, gn, has_next, xs, y0, y1);
     }
 }
 
@@ -430,13 +439,14 @@ int ce_dssim_create_stream(ce_batch *b, int l, const uint8_t *d_refs, uint32_t n
     const uint32_t strips_ref = (d.w + 64 - 2 * CR_HALO_REF - 1) / (64 - 2 * CR_HALO_REF), strips = (d.w + CS_OUT - 1) / CS_OUT;
     const uint32_t rows = b->debug_ds_rows ? b->debug_ds_rows : stream_rows(strips, d.h, n_slots - z0);
     const uint32_t tiles = std::max(z0 < n_refs_used ? strips_ref : 0u, strips) * ((d.h + rows - 1) / rows);
-#define CE_CREATE_LAUNCH(NAME, U8, GRID, Z0)                                                                                        \
+#define CE_CREATE_LAUNCH(NAME, U8, GRID, Z0, LUT_R, LUT_T)                                                                                      \
     CE_LAUNCH(ctx, NAME, (k_dssim_create_stream<U8>), GRID, dim3(CS_WAVES * 64), 0, d_refs, (const uint8_t *)b->d_tests,            \
-              (const float *)ctx->d_lut_powf, (const float *)(l == 0 ? nullptr : b->ds_lin[l & 1]), b->ds_lin[(l + 1) & 1], b->ds_img,      \
+              (const float *)LUT_R, (const float *)LUT_T, (const float *)(l == 0 ? nullptr : b->ds_lin[l & 1]), b->ds_lin[(l + 1) & 1], b->ds_img,      \
               b->ds_rimg[l], b->ds_rmu[l], b->ds_rsq[l], lg, ng, has_next ? 1 : 0, b->img_bytes, n_refs_used, b->max_refs, Z0, rows)
     const dim3 grid((tiles + CS_WAVES - 1) / CS_WAVES, n_slots - z0);
-    if (l == 0) CE_CREATE_LAUNCH("dssim_create_u8", true, grid, z0);
-    else CE_CREATE_LAUNCH("dssim_create", false, grid, z0);
+    if (l == 0 && b->depth[0]) CE_CREATE_LAUNCH("dssim_create_u16", CE_SRC_U16, grid, z0, b->deep_lut[1][0], b->deep_lut[1][1]);
+    else if (l == 0) CE_CREATE_LAUNCH("dssim_create_u8", CE_SRC_U8, grid, z0, ctx->d_lut_powf, ctx->d_lut_powf);
+    else CE_CREATE_LAUNCH("dssim_create", CE_SRC_F32, grid, z0, ctx->d_lut_powf, ctx->d_lut_powf);
 #undef CE_CREATE_LAUNCH
     return CE_OK;
 }

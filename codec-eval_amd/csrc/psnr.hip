@@ -75,6 +75,49 @@ __global__ __launch_bounds__(kThreads) void k_psnr_sse(const uint8_t *__restrict
     }
 }
 
+// The deep batch's u16 samples (both sides of one depth): eight samples per 16-byte load, each squared difference below
+// 2^32 and added in u64.
+__global__ __launch_bounds__(kThreads) void k_psnr_sse_u16(const uint8_t *__restrict__ refs, const uint8_t *__restrict__ tests,
+                                                           const uint32_t *__restrict__ pair_ref, ce_dev_scores *__restrict__ scores,
+                                                           size_t img_bytes)
+{
+    const uint32_t p = blockIdx.y;
+    const uint8_t *a = refs + (size_t)pair_ref[p] * img_bytes;
+    const uint8_t *b = tests + (size_t)p * img_bytes;
+    unsigned long long sse = 0;
+    const size_t tid = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    const size_t nthreads = (size_t)gridDim.x * kThreads;
+    auto sq = [](uint32_t x, uint32_t y) {
+        const uint32_t d = x > y ? x - y : y - x;
+        return (unsigned long long)d * d;
+    };
+    if ((img_bytes & 15) == 0) {  // every image of the slab then starts 16-byte aligned
+        const uint4 *a4 = reinterpret_cast<const uint4 *>(a);
+        const uint4 *b4 = reinterpret_cast<const uint4 *>(b);
+        const size_t n16 = img_bytes >> 4;
+        for (size_t i = tid; i < n16; i += nthreads) {
+            const uint4 va = a4[i], vb = b4[i];
+            const uint32_t wa[4] = {va.x, va.y, va.z, va.w}, wb[4] = {vb.x, vb.y, vb.z, vb.w};
+#pragma unroll
+            for (int k = 0; k < 4; k++) sse += sq(wa[k] & 0xffffu, wb[k] & 0xffffu) + sq(wa[k] >> 16, wb[k] >> 16);
+        }
+    } else {
+        const uint16_t *a2 = reinterpret_cast<const uint16_t *>(a);
+        const uint16_t *b2 = reinterpret_cast<const uint16_t *>(b);
+        for (size_t i = tid; i < (img_bytes >> 1); i += nthreads) sse += sq(a2[i], b2[i]);
+    }
+    __shared__ unsigned long long s_part[kThreads / 64];
+    sse = wave_sum_u64(sse);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = sse;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long t = 0;
+#pragma unroll
+        for (int k = 0; k < kThreads / 64; k++) t += s_part[k];
+        atomicAdd(&scores[p].sse, t);
+    }
+}
+
 __global__ void k_psnr_clear(ce_dev_scores *scores, uint32_t n)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -94,8 +137,12 @@ int ce_launch_psnr(ce_batch *b, const uint8_t *d_refs, uint32_t n_pairs)
     const uint32_t cap = std::max<uint32_t>(kBlocksPerPair, 4096u / n_pairs);
     if (blocks > cap) blocks = cap;
     if (blocks == 0) blocks = 1;
-    CE_LAUNCH(ctx, "psnr_sse", k_psnr_sse, dim3(blocks, n_pairs), dim3(kThreads), 0, d_refs, b->d_tests, b->d_pair_ref,
-              b->d_scores, b->img_bytes);
+    if (b->depth[0])
+        CE_LAUNCH(ctx, "psnr_sse_u16", k_psnr_sse_u16, dim3(blocks, n_pairs), dim3(kThreads), 0, d_refs, b->d_tests, b->d_pair_ref,
+                  b->d_scores, b->img_bytes);
+    else
+        CE_LAUNCH(ctx, "psnr_sse", k_psnr_sse, dim3(blocks, n_pairs), dim3(kThreads), 0, d_refs, b->d_tests, b->d_pair_ref,
+                  b->d_scores, b->img_bytes);
     CE_HIP(ctx, hipGetLastError());
     return CE_OK;
 }

@@ -570,6 +570,30 @@ inline MetricResult evaluate_single(const HipBackend &be, const ImageData &refer
     detail::check(be, rc, "evaluate_single", reference.width, reference.height, e.size());
     return MetricResult::from_c(s);
 }
+// ---- deep input (include/ce_metrics.h: ce_batch_create_deep; no reference item - the reference rounds PixelData::Rgb16 to
+// 8 bits with to_8bit before it measures) -------------------------------------------------------------------------------
+// One pair of packed u16 RGB at its own precision: sample v of a side of depth d (8, 10, 12, 16) is the sRGB value
+// v / (2^d - 1).  PSNR is reported for equal depths only.
+inline MetricResult evaluate_pair_deep(const HipBackend &be, const std::vector<uint16_t> &reference, uint32_t ref_depth,
+                                       const std::vector<uint16_t> &test, uint32_t test_depth, size_t width, size_t height,
+                                       const MetricConfig &config)
+{
+    ce_scores s{};
+    const int rc = ce_eval_pair_deep(be.ctx(), reference.data(), reference.size() * 2, ref_depth, test.data(), test.size() * 2, test_depth,
+                                     (uint32_t)width, (uint32_t)height, config.mask(), config.flags(), CE_DEFAULT_INTENSITY_TARGET, &s);
+    detail::check(be, rc, "evaluate_pair_deep", width, height, test.size());
+    return MetricResult::from_c(s);
+}
+// A deep HBM-resident grid, filled with ce_batch_set_*_fmt(CE_PIXEL_RGB16 / CE_PIXEL_RGBA16) and run like any batch; the
+// caller destroys it with ce_batch_destroy.
+inline ce_batch *batch_deep(const HipBackend &be, uint32_t width, uint32_t height, uint32_t max_refs, uint32_t max_pairs,
+                            uint32_t ref_depth, uint32_t test_depth)
+{
+    ce_batch *b = nullptr;
+    const int rc = ce_batch_create_deep(be.ctx(), width, height, max_refs, max_pairs, ref_depth, test_depth, &b);
+    detail::check(be, rc, "batch_deep", width, height, (size_t)width * height * 3);
+    return b;
+}
 // assert_quality, helpers.rs:212-255
 inline void assert_quality(const HipBackend &be, const ImageData &reference, const ImageData &encoded,
                            std::optional<double> min_ssimulacra2, std::optional<double> max_dssim)

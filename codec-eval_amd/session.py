@@ -16,7 +16,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import (PIXEL_RGB8, PIXEL_RGBA8, Batch, CodecEvalError, ColorTable, Context, DimensionMismatch, MetricCalculation,
+from . import (DEEP_DEPTHS, PIXEL_RGB8, PIXEL_RGB16, PIXEL_RGBA8, PIXEL_RGBA16, Batch, CodecEvalError, ColorTable, Context, DimensionMismatch, MetricCalculation,
                MetricConfig, MetricResult, _error_obj, estimate_batch_bytes, CE_ERR_BACKEND)
 from . import reports as R
 
@@ -26,11 +26,12 @@ __all__ = ["ImageData", "EncodeRequest", "EvalConfig", "EvalConfigBuilder", "Eva
 @dataclass
 class ImageData:
     """session.rs:25-149.  `RgbSlice`, `RgbaSlice`, `RgbSliceWithIcc` (the imgref variants carry the same bytes)."""
-    data: np.ndarray  # packed u8, RGB or RGBA
+    data: np.ndarray  # packed u8, RGB or RGBA (depth 0); packed u16 of `depth` bits per sample for a deep image
     width: int
     height: int
     channels: int = 3
     icc_profile: Optional[bytes] = None
+    depth: int = 0  # 0: 8-bit samples in u8; 8, 10, 12 or 16: a deep image (rgb16 / rgba16), scored at its own precision
 
     @staticmethod
     def rgb(data, width: int, height: int) -> "ImageData":
@@ -44,10 +45,26 @@ class ImageData:
     def rgb_with_icc(data, width: int, height: int, icc_profile: bytes) -> "ImageData":
         return ImageData(np.ascontiguousarray(data, dtype=np.uint8).reshape(-1), int(width), int(height), 3, bytes(icc_profile))
 
+    @staticmethod
+    def rgb16(data, width: int, height: int, depth: int) -> "ImageData":
+        """A decoder's PixelData::Rgb16 (crates/codec-iter/src/avif_config.rs:122-170) kept as it is: packed uint16
+        samples of `depth` bits, each meaning the sRGB value v / (2^depth - 1).  A session scores it through a deep batch."""
+        if depth not in DEEP_DEPTHS:
+            raise ValueError(f"depth must be one of {DEEP_DEPTHS}, got {depth}")
+        return ImageData(np.ascontiguousarray(data, dtype=np.uint16).reshape(-1), int(width), int(height), 3, None, int(depth))
+
+    @staticmethod
+    def rgba16(data, width: int, height: int, depth: int) -> "ImageData":
+        if depth not in DEEP_DEPTHS:
+            raise ValueError(f"depth must be one of {DEEP_DEPTHS}, got {depth}")
+        return ImageData(np.ascontiguousarray(data, dtype=np.uint16).reshape(-1), int(width), int(height), 4, None, int(depth))
+
     def to_rgb8_vec(self) -> np.ndarray:  # session.rs:98-117 (host copy; the session itself strips alpha on the device)
-        if self.channels == 3:
-            return self.data
-        return np.ascontiguousarray(self.data.reshape(-1, 4)[:, :3]).reshape(-1)
+        data = self.data if self.channels == 3 else np.ascontiguousarray(self.data.reshape(-1, 4)[:, :3]).reshape(-1)
+        if self.depth:  # to_8bit's rule for any depth: what the reference does to a 10-bit decode before it measures
+            maxv = (1 << self.depth) - 1
+            return np.minimum((np.minimum(data, maxv).astype(np.uint64) * 255 + maxv // 2) // maxv, 255).astype(np.uint8)
+        return data
 
     def to_rgb8_srgb(self, cms: Optional[Callable[[bytes, np.ndarray], np.ndarray]] = None) -> np.ndarray:
         """session.rs:143-147 -> transform_to_srgb, metrics/icc.rs:69-113: on the HOST (the session itself applies the
@@ -67,6 +84,8 @@ class ImageData:
 
     @property
     def pixel_format(self) -> int:
+        if self.depth:
+            return PIXEL_RGB16 if self.channels == 3 else PIXEL_RGBA16
         return PIXEL_RGB8 if self.channels == 3 else PIXEL_RGBA8
 
 
@@ -247,9 +266,22 @@ class EvalSession:
                 self._score_part(w, h, part, cfg)
 
     def _score_part(self, w: int, h: int, group, cfg: MetricConfig):
+        """Cells whose decode is 8-bit go through an RGB8 batch as ever; the cells of deep decodes (ImageData.rgb16 /
+        rgba16) through one deep batch per (source depth, decode depth), the 8-bit source as depth 8, neither side rescaled."""
+        kinds: Dict[Tuple[int, int], list] = {}
+        for image, report, pending in group:
+            by_depth: Dict[int, list] = {}
+            for cell in pending:
+                by_depth.setdefault(cell[1].depth, []).append(cell)
+            for d, cells in by_depth.items():
+                kinds.setdefault((image.depth or 8, d) if (d or image.depth) else (0, 0), []).append((image, report, cells))
+        for depths, sub in kinds.items():
+            self._score_cells(w, h, sub, cfg, None if depths == (0, 0) else (depths[0], depths[1] or 8))
+
+    def _score_cells(self, w: int, h: int, group, cfg: MetricConfig, depths: Optional[Tuple[int, int]]):
         n_refs = len(group)
         n_pairs = sum(len(p) for _, _, p in group)
-        batch = Batch(self.ctx, w, h, n_refs, n_pairs)
+        batch = Batch(self.ctx, w, h, n_refs, n_pairs, depths=depths)
         try:
             rows = []
             k = 0

@@ -292,6 +292,49 @@ int ce_batch_dssim_ssim_maps(ce_batch *b, uint32_t level, uint32_t first, uint32
 int ce_batch_ssimulacra2_maps(ce_batch *b, uint32_t scale, uint32_t channel, uint32_t kind, uint32_t first,
                               uint32_t count, uint32_t block, float *maps, size_t maps_floats, double *norms);
 
+/* ---- deep batches: 10-, 12- and 16-bit images at their own precision --------------------------
+ * CE_PIXEL_RGB16_10BIT above restates to_8bit (crates/codec-iter/src/avif_config.rs:122-170): every 10-bit sample of a
+ * decode is rounded to 8 bits before anything is measured.  A deep batch keeps the samples: its slabs are packed
+ * interleaved RGB in uint16_t (little endian) with a declared depth d in {8, 10, 12, 16} per side; sample v (larger values
+ * are clamped to 2^d - 1 on ingest, as to_8bit's .min does) means the sRGB-encoded value v / (2^d - 1), and each metric
+ * turns it into linear light by its own 8-bit rule with 255 replaced by 2^d - 1 (SSIMULACRA2 and Butteraugli: the curve in
+ * f64 rounded once to f32; DSSIM: f32 with powf, src/metrics/dssim.rs:78-85; PSNR: the exact integer sum of squared sample
+ * differences, then calculate_psnr's expression, src/metrics/mod.rs:324-330, with 255 replaced by 2^d - 1).  The two sides
+ * have their own depths - an 8-bit source against a 10-bit decode, neither rescaled; PSNR needs equal depths and with
+ * unequal ones its bit stays clear in `valid` while the other metrics run.  A deep batch of depths 8 / 8 scores an image
+ * bit for bit as an RGB8 batch does, and so does one of depth 16 holding v8 * 257.
+ * Not part of this: linear-f32 input, PQ / HLG transfer curves, wide-gamut primaries, deep ce_ref handles, deep
+ * ce_eval_batch.
+ * Pixel formats of a deep batch only (their depth is that side's): packed u16 RGB / RGBA (alpha dropped). */
+enum {
+    CE_PIXEL_RGB16 = 4,
+    CE_PIXEL_RGBA16 = 5
+};
+/* bytes per pixel of a CE_PIXEL_* format, 0 for an unknown one (pure host function) */
+size_t ce_pixel_bytes(int format);
+/* ce_batch_create with a depth per side; CE_ERR_INVALID_ARG for a depth outside {8, 10, 12, 16}.  On such a batch
+ *   ce_batch_set_reference_fmt / ce_batch_set_test_fmt take CE_PIXEL_RGB16 and CE_PIXEL_RGBA16, and CE_PIXEL_RGB8 /
+ *     CE_PIXEL_RGBA8 where that side's depth is 8 (the *_10BIT formats: CE_ERR_INVALID_ARG); ce_batch_set_reference /
+ *     ce_batch_set_test are the CE_PIXEL_RGB8 form;
+ *   ce_batch_reference_slab / ce_batch_test_slab are the u16 slabs ([max_refs][h][w][3], [max_pairs][h][w][3]; values
+ *     written in place must not exceed 2^d - 1);
+ *   ce_batch_bind_pair, ce_batch_run, ce_batch_launch, ce_batch_collect, ce_batch_butteraugli_pnorm3 and the three map
+ *     readers work as on any batch;
+ *   CE_ERR_INVALID_ARG, with the reason in ce_last_error: CE_FLAG_XYB_ROUNDTRIP (by definition an 8-bit quantisation,
+ *     src/metrics/xyb.rs:185-199), ce_batch_image_heuristics (defined on u8 gray levels), ce_batch_set_*_lut with a table
+ *     (the table is 2^24 8-bit colours).
+ * (No reference item: the reference scores PixelData::Rgb16 only after to_8bit.) */
+int ce_batch_create_deep(ce_ctx *ctx, uint32_t width, uint32_t height, uint32_t max_refs, uint32_t max_pairs,
+                         uint32_t ref_depth, uint32_t test_depth, ce_batch **out);
+/* ce_estimate_batch_bytes for a deep batch (0 for a depth outside {8, 10, 12, 16}) */
+size_t ce_estimate_batch_bytes_deep(uint32_t width, uint32_t height, uint32_t n_refs, uint32_t n_pairs, uint32_t metric_mask,
+                                    uint32_t ref_depth, uint32_t test_depth);
+/* ce_eval_pair over packed u16 RGB of the given depths (lengths in bytes: width * height * 6; samples above 2^d - 1 are
+ * clamped); the same error kinds in the same order, CE_ERR_INVALID_ARG for a bad depth, CE_FLAG_XYB_ROUNDTRIP or a map flag */
+int ce_eval_pair_deep(ce_ctx *ctx, const uint16_t *reference, size_t reference_len, uint32_t ref_depth, const uint16_t *test,
+                      size_t test_len, uint32_t test_depth, uint32_t width, uint32_t height, uint32_t metric_mask,
+                      uint32_t flags, float intensity_target, ce_scores *out);
+
 /* ---- reference handle: Ssimulacra2Reference::{new,compare} ------------------------
  * crates/codec-iter/src/eval.rs:138-149,83-89; crates/codec-compare/src/brute_force_sweep.rs:197-201,256
  * The handle keeps the reference resident in HBM together with its reference-side state for EVERY metric: the XYB
