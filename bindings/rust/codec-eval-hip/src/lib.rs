@@ -163,6 +163,28 @@ impl HipMetrics {
         Ok(out)
     }
 
+    /// One packed RGB8 image at the size a `ViewingCondition` displays it (`SimulationParams`, src/viewing.rs:308-331;
+    /// `ce_resample_rgb8`): the fixed-point separable convolution of Pillow's `Image.resize`, bit for bit, on the device.
+    pub fn resample_rgb8(&mut self, rgb: &[u8], width: u32, height: u32, out_width: u32, out_height: u32, filter: ResampleFilter)
+                         -> Result<Vec<u8>, HipError> {
+        let mut out = vec![0u8; out_width as usize * out_height as usize * 3];
+        let rc = unsafe {
+            sys::ce_resample_rgb8(self.ctx, rgb.as_ptr(), rgb.len(), width, height, out_width, out_height, filter as i32,
+                                  out.as_mut_ptr(), out.len())
+        };
+        self.check(rc, width, height, rgb.len())?;
+        Ok(out)
+    }
+
+    /// A resident grid of `(reference, test)` pairs of one shape (`ce_batch_create`); `&self`, so that a source grid and
+    /// the grids it is resampled into can live side by side (one call at a time per context, as everywhere).
+    pub fn batch(&self, width: u32, height: u32, max_refs: u32, max_pairs: u32) -> Result<HipBatch<'_>, HipError> {
+        let mut handle = std::ptr::null_mut();
+        let rc = unsafe { sys::ce_batch_create(self.ctx, width, height, max_refs, max_pairs, &mut handle) };
+        self.check(rc, width, height, 0)?;
+        Ok(HipBatch { owner: self, handle, width, height })
+    }
+
     /// `calculate_butteraugli_with_intensity` returning what `ButteraugliResult` holds (src/metrics/prelude.rs:64-65):
     /// the score and the per-pixel diffmap, row-major `width * height`, whose maximum is the score.
     pub fn calculate_butteraugli_with_diffmap(&mut self, reference: &[u8], test: &[u8], width: usize, height: usize,
@@ -409,4 +431,72 @@ impl HipSsim2 {
 fn last_error(ctx: *const sys::ce_ctx) -> String {
     let p = unsafe { sys::ce_last_error(ctx) };
     if p.is_null() { String::new() } else { unsafe { CStr::from_ptr(p) }.to_string_lossy().into_owned() }
+}
+
+/// `enum ce_resample_filter`: the kernel of `resample_rgb8` / `HipBatch::resample_pairs_into`.
+#[derive(Debug, Clone, Copy, PartialEq, Eq, Default)]
+#[repr(i32)]
+pub enum ResampleFilter {
+    Box = 0,
+    Bilinear = 1,
+    Bicubic = 2,
+    #[default]
+    Lanczos3 = 3,
+}
+
+/// `ce_batch`: images of one shape resident on the device, scored in one launch.  Resampling one grid into another
+/// (`resample_pairs_into`) scores a sweep at the size a `ViewingCondition` displays it (src/viewing.rs:244-301) without
+/// another upload.
+pub struct HipBatch<'a> {
+    owner: &'a HipMetrics,
+    handle: *mut sys::ce_batch,
+    width: u32,
+    height: u32,
+}
+
+impl HipBatch<'_> {
+    fn check(&self, rc: i32, len: usize) -> Result<(), HipError> {
+        self.owner.check(rc, self.width, self.height, len)
+    }
+
+    pub fn set_reference(&mut self, ref_index: u32, rgb: &[u8]) -> Result<(), HipError> {
+        let rc = unsafe { sys::ce_batch_set_reference(self.handle, ref_index, rgb.as_ptr(), rgb.len()) };
+        self.check(rc, rgb.len())
+    }
+
+    pub fn set_test(&mut self, pair_index: u32, ref_index: u32, rgb: &[u8]) -> Result<(), HipError> {
+        let rc = unsafe { sys::ce_batch_set_test(self.handle, pair_index, ref_index, rgb.as_ptr(), rgb.len()) };
+        self.check(rc, rgb.len())
+    }
+
+    /// `ce_batch_resample`: references (`tests`: test images) `[first, first + count)` into the same indices of `dst`.
+    pub fn resample_into(&mut self, dst: &mut HipBatch<'_>, tests: bool, first: u32, count: u32, filter: ResampleFilter)
+                         -> Result<(), HipError> {
+        let which = if tests { sys::CE_BATCH_TESTS } else { sys::CE_BATCH_REFERENCES };
+        let rc = unsafe { sys::ce_batch_resample(self.handle, dst.handle, which, first, count, filter as i32) };
+        self.check(rc, 0)
+    }
+
+    /// `ce_batch_resample_pairs`: both slabs and the pair bindings; `dst.run(n_pairs, ..)` follows directly.
+    pub fn resample_pairs_into(&mut self, dst: &mut HipBatch<'_>, n_refs: u32, n_pairs: u32, filter: ResampleFilter)
+                               -> Result<(), HipError> {
+        let rc = unsafe { sys::ce_batch_resample_pairs(self.handle, dst.handle, n_refs, n_pairs, filter as i32) };
+        self.check(rc, 0)
+    }
+
+    /// `ce_batch_run` over pairs `[0, n_pairs)`.
+    pub fn run(&mut self, n_pairs: u32, m: Metrics) -> Result<Vec<Scores>, HipError> {
+        let mut out = vec![sys::ce_scores::default(); n_pairs as usize];
+        let rc = unsafe {
+            sys::ce_batch_run(self.handle, n_pairs, m.mask(), m.flags(), sys::CE_DEFAULT_INTENSITY_TARGET, out.as_mut_ptr())
+        };
+        self.check(rc, 0)?;
+        Ok(out.into_iter().map(Into::into).collect())
+    }
+}
+
+impl Drop for HipBatch<'_> {
+    fn drop(&mut self) {
+        unsafe { sys::ce_batch_destroy(self.handle) }
+    }
 }

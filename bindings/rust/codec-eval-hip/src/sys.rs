@@ -204,6 +204,10 @@ extern "C" {
                                     out: *mut ce_image_heuristics) -> c_int;
     pub fn ce_batch_image_heuristics(b: *mut ce_batch, which: u32, first: u32, count: u32, out: *mut ce_image_heuristics) -> c_int;
     pub fn ce_ref_image_heuristics(r: *mut ce_ref, out: *mut ce_image_heuristics) -> c_int;
+    pub fn ce_resample_rgb8(ctx: *mut ce_ctx, rgb: *const u8, len: usize, w: u32, h: u32, out_w: u32, out_h: u32, filter: c_int,
+                            out: *mut u8, out_len: usize) -> c_int;
+    pub fn ce_batch_resample(src: *mut ce_batch, dst: *mut ce_batch, which: u32, first: u32, count: u32, filter: c_int) -> c_int;
+    pub fn ce_batch_resample_pairs(src: *mut ce_batch, dst: *mut ce_batch, n_refs: u32, n_pairs: u32, filter: c_int) -> c_int;
     pub fn ce_prof_enable(ctx: *mut ce_ctx, on: c_int) -> c_int;
     pub fn ce_prof_filter(ctx: *mut ce_ctx, substring: *const c_char) -> c_int;
     pub fn ce_prof_reset(ctx: *mut ce_ctx) -> c_int;

@@ -42,6 +42,7 @@ DEFAULT_INTENSITY_TARGET = 80.0
 DSSIM_MAX_LEVELS = 5  # CE_DSSIM_MAX_LEVELS
 SSIM2_MAX_SCALES = 6  # CE_SSIM2_MAX_SCALES
 SSIM2_MAP_SSIM, SSIM2_MAP_ARTIFACT, SSIM2_MAP_DETAIL_LOST = 0, 1, 2  # enum ce_ssim2_map
+RESAMPLE_BOX, RESAMPLE_BILINEAR, RESAMPLE_BICUBIC, RESAMPLE_LANCZOS3 = 0, 1, 2, 3  # enum ce_resample_filter
 
 _STATUS_NAMES = {
     CE_ERR_DIM_MISMATCH: "DimensionMismatch",
@@ -193,6 +194,9 @@ _PROTOTYPES = [
     ("ce_image_heuristics_rgb8", _i, [_vp, _u8p, _sz, _sz, _sz, C.POINTER(CeImageHeuristics)]),
     ("ce_batch_image_heuristics", _i, [_vp, _u32, _u32, _u32, C.POINTER(CeImageHeuristics)]),
     ("ce_ref_image_heuristics", _i, [_vp, C.POINTER(CeImageHeuristics)]),
+    ("ce_resample_rgb8", _i, [_vp, _u8p, _sz, _u32, _u32, _u32, _u32, _i, _u8p, _sz]),
+    ("ce_batch_resample", _i, [_vp, _vp, _u32, _u32, _u32, _i]),
+    ("ce_batch_resample_pairs", _i, [_vp, _vp, _u32, _u32, _i]),
     ("ce_prof_enable", _i, [_vp, _i]),
     ("ce_prof_filter", _i, [_vp, C.c_char_p]),
     ("ce_prof_reset", _i, [_vp]),
@@ -669,6 +673,17 @@ class Context:
         self._check(lib().ce_image_heuristics_rgb8(self._h, r.ctypes.data, r.size, width, height, C.byref(out)))
         return ImageHeuristics.from_c(out, image)
 
+    def resample_rgb8(self, rgb, width: int, height: int, out_width: int, out_height: int,
+                      filter: int = RESAMPLE_LANCZOS3) -> np.ndarray:
+        """One packed RGB8 image at another size (ce_resample_rgb8): the image SimulationParams (src/viewing.rs:308-331)
+        describes, by the fixed-point separable convolution of Pillow's Image.resize, bit for bit -> (out_height,
+        out_width, 3) uint8."""
+        r = _buf(rgb)
+        out = np.empty((max(out_height, 0), max(out_width, 0), 3), np.uint8)
+        self._check(lib().ce_resample_rgb8(self._h, r.ctypes.data, r.size, width, height, out_width, out_height, filter,
+                                           out.ctypes.data, out.size))
+        return out
+
     # -- dispatcher
     def calculate_metrics(self, reference, test, width: int, height: int, config: MetricConfig,
                           intensity_target: float = DEFAULT_INTENSITY_TARGET) -> MetricResult:
@@ -692,6 +707,13 @@ class Context:
     def batch_deep(self, width: int, height: int, max_refs: int, max_pairs: int, ref_depth: int, test_depth: int) -> "Batch":
         """A Batch whose slabs hold uint16 samples of the given depths (8, 10, 12 or 16 bits per side)."""
         return Batch(self, width, height, max_refs, max_pairs, depths=(ref_depth, test_depth))
+
+    def copy_device(self, dst: int, src: int, nbytes: int):
+        """`nbytes` from one device address to another on the context's stream (for callers that move images between the
+        slabs Batch.reference_slab / test_slab expose): ordered like a kernel of this context."""
+        rc = lib().hipMemcpyAsync(C.c_void_p(dst), C.c_void_p(src), C.c_size_t(nbytes), 3, C.c_void_p(self.stream))  # 3: device to device
+        if rc != 0:
+            raise MetricCalculation(CE_ERR_BACKEND, f"hipMemcpyAsync failed with {rc}")
 
     def host_buffer(self, nbytes: int) -> np.ndarray:
         """`nbytes` of page-locked host memory as a flat uint8 array (ce_host_alloc; freed when the array and every view of
@@ -786,6 +808,7 @@ class Batch:
         self.ctx, self.width, self.height = ctx, width, height
         self.max_refs, self.max_pairs = max_refs, max_pairs
         self.depths = tuple(depths) if depths is not None else None
+        self._pair_ref = [0] * max_pairs  # the pair -> reference bindings, as the library holds them
         self._h = C.c_void_p()
         if self.depths is None:
             ctx._check(lib().ce_batch_create(ctx._h, width, height, max_refs, max_pairs, C.byref(self._h)))
@@ -819,6 +842,7 @@ class Batch:
             return self.set_test_fmt(pair_index, ref_index, rgb, self._deep_fmt(np.asarray(rgb)))
         t = _buf(rgb)
         self.ctx._check(lib().ce_batch_set_test(self._h, pair_index, ref_index, t.ctypes.data, t.size))
+        self._pair_ref[pair_index] = ref_index
 
     # decoded-image ingest: pixels as a decoder hands them over, converted to RGB8 on the device
     def set_reference_fmt(self, ref_index: int, pixels, fmt: int):
@@ -828,6 +852,7 @@ class Batch:
     def set_test_fmt(self, pair_index: int, ref_index: int, pixels, fmt: int):
         a = np.ascontiguousarray(pixels)
         self.ctx._check(lib().ce_batch_set_test_fmt(self._h, pair_index, ref_index, a.ctypes.data, a.nbytes, fmt))
+        self._pair_ref[pair_index] = ref_index
 
     # ... and through a colour table (ICC -> sRGB on the device)
     def set_reference_lut(self, ref_index: int, pixels, fmt: int, table: Optional["ColorTable"]):
@@ -837,9 +862,15 @@ class Batch:
     def set_test_lut(self, pair_index: int, ref_index: int, pixels, fmt: int, table: Optional["ColorTable"]):
         a = np.ascontiguousarray(pixels)
         self.ctx._check(lib().ce_batch_set_test_lut(self._h, pair_index, ref_index, a.ctypes.data, a.nbytes, fmt, table._h if table else None))
+        self._pair_ref[pair_index] = ref_index
 
     def bind_pair(self, pair_index: int, ref_index: int):
         self.ctx._check(lib().ce_batch_bind_pair(self._h, pair_index, ref_index))
+        self._pair_ref[pair_index] = ref_index
+
+    def pair_reference(self, pair_index: int) -> int:
+        """The reference pair `pair_index` is bound to (0 until a set_test* / bind_pair names another)."""
+        return self._pair_ref[pair_index]
 
     @property
     def reference_slab(self) -> int:
@@ -900,6 +931,18 @@ class Batch:
         out = (CeImageHeuristics * max(count, 1))()
         self.ctx._check(lib().ce_batch_image_heuristics(self._h, BATCH_TESTS if tests else BATCH_REFERENCES, first, count, out))
         return [ImageHeuristics.from_c(out[i]) for i in range(count)]
+
+    def resample_into(self, dst: "Batch", first: int, count: int, tests: bool = False, filter: int = RESAMPLE_LANCZOS3):
+        """References (tests=True: test images) [first, first + count) of this batch resampled to `dst`'s shape into the
+        same indices of `dst`, a batch of the same context (ce_batch_resample): on the device, behind this batch's
+        uploads and ahead of dst's next launch; no scores or maps of either batch change."""
+        self.ctx._check(lib().ce_batch_resample(self._h, dst._h, BATCH_TESTS if tests else BATCH_REFERENCES, first, count, filter))
+
+    def resample_pairs_into(self, dst: "Batch", n_refs: int, n_pairs: int, filter: int = RESAMPLE_LANCZOS3):
+        """References [0, n_refs) and tests [0, n_pairs) resampled into `dst` together with the pairs' reference
+        bindings (ce_batch_resample_pairs): `dst.run(n_pairs, ...)` follows directly."""
+        self.ctx._check(lib().ce_batch_resample_pairs(self._h, dst._h, n_refs, n_pairs, filter))
+        dst._pair_ref[:n_pairs] = self._pair_ref[:n_pairs]
 
     # -- test hooks
     def debug_limit_scales(self, n: int):

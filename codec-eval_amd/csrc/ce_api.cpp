@@ -408,6 +408,9 @@ void ce_ctx_destroy(ce_ctx *ctx)
     if (ctx->leaf_h) hipHostFree(ctx->leaf_h);
     hipFree(ctx->heur_d);
     if (ctx->heur_h) hipHostFree(ctx->heur_h);
+    hipFree(ctx->rs_mid);
+    for (auto &kv : ctx->rs_tables) hipFree(kv.second.d);
+    ctx->rs_tables.clear();
     hipFree(ctx->d_lut_ssim2);
     hipFree(ctx->d_lut_powf);
     hipFree(ctx->d_xyb_thresh);
@@ -1699,6 +1702,145 @@ int ce_batch_image_heuristics(ce_batch *b, uint32_t which, uint32_t first, uint3
     if (int rc = flush_uploads(b)) return rc;
     const uint8_t *slab = which == CE_BATCH_TESTS ? b->d_tests : b->d_refs;
     return ce_image_heuristics_run(ctx, slab + (size_t)first * b->img_bytes, b->img_bytes, b->w, b->h, count, out);
+}
+
+// ---- viewing simulation: resampling (resample.hip) ----------------------------------------------
+
+// the taps of one axis on the device, built on first use and kept with the context (ce_ctx::rs_tables)
+static int resample_table(ce_ctx *ctx, uint32_t n_in, uint32_t n_out, int filter, const ce_resample_axis **out)
+{
+    const auto key = std::make_tuple(n_in, n_out, filter);
+    auto it = ctx->rs_tables.find(key);
+    if (it == ctx->rs_tables.end()) {
+        std::vector<int32_t> host;
+        ce_resample_axis a;
+        a.n_in = n_in, a.n_out = n_out;
+        if (!ce_build_resample_table(n_in, n_out, filter, host, &a.ksize)) return fail(ctx, CE_ERR_INVALID_ARG, "resample: bad axis");
+        CE_HIP(ctx, hipMalloc((void **)&a.d, host.size() * sizeof(int32_t)));
+        if (hipMemcpy(a.d, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+            hipFree(a.d);
+            return fail(ctx, CE_ERR_BACKEND, "H2D failed (resample taps)");
+        }
+        it = ctx->rs_tables.emplace(key, a).first;
+    }
+    *out = &it->second;
+    return CE_OK;
+}
+
+static bool resample_filter_ok(int filter) { return filter >= CE_RESAMPLE_BOX && filter <= CE_RESAMPLE_LANCZOS3; }
+
+// n images of w x h at d_src (src_stride apart) to out_w x out_h at d_dst, queued on the context's stream
+static int resample_images(ce_ctx *ctx, const uint8_t *d_src, size_t src_stride, uint8_t *d_dst, size_t dst_stride, uint32_t w, uint32_t h,
+                           uint32_t out_w, uint32_t out_h, uint32_t n, int filter)
+{
+    if (w == out_w && h == out_h) {  // no pass changes a size: the bytes themselves
+        const size_t img = (size_t)w * h * 3;
+        if (src_stride == img && dst_stride == img) {
+            CE_HIP(ctx, hipMemcpyAsync(d_dst, d_src, img * n, hipMemcpyDeviceToDevice, ctx->stream));
+        } else {
+            for (uint32_t i = 0; i < n; i++)
+                CE_HIP(ctx, hipMemcpyAsync(d_dst + i * dst_stride, d_src + i * src_stride, img, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        return CE_OK;
+    }
+    const ce_resample_axis *horiz = nullptr, *vert = nullptr;
+    if (w != out_w)
+        if (int rc = resample_table(ctx, w, out_w, filter, &horiz)) return rc;
+    if (h != out_h)
+        if (int rc = resample_table(ctx, h, out_h, filter, &vert)) return rc;
+    if (horiz && vert) {
+        const size_t need = (size_t)n * h * out_w * 3;
+        if (ctx->rs_mid_cap < need) {
+            CE_HIP(ctx, hipStreamSynchronize(ctx->stream));  // an earlier resample may still be between its passes
+            CE_HIP(ctx, hipFree(ctx->rs_mid));
+            ctx->rs_mid = nullptr;
+            ctx->rs_mid_cap = 0;
+            CE_HIP(ctx, hipMalloc((void **)&ctx->rs_mid, need + need / 4));
+            ctx->rs_mid_cap = need + need / 4;
+        }
+    }
+    return ce_launch_resample(ctx, ctx->stream, d_src, src_stride, d_dst, dst_stride, w, h, out_w, out_h, n, horiz, vert, ctx->rs_mid);
+}
+
+int ce_resample_rgb8(ce_ctx *ctx, const uint8_t *rgb, size_t len, uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h, int filter,
+                     uint8_t *out, size_t out_len)
+{
+    if (!ctx || !rgb || !out) return fail(ctx, CE_ERR_INVALID_ARG, "resample: null pointer");
+    if (!resample_filter_ok(filter)) return fail(ctx, CE_ERR_INVALID_ARG, "resample: unknown filter " + std::to_string(filter));
+    if (w == 0 || h == 0 || out_w == 0 || out_h == 0)
+        return fail(ctx, CE_ERR_INVALID_ARG, "resample: " + std::to_string(w) + " x " + std::to_string(h) + " to " + std::to_string(out_w) +
+                                                 " x " + std::to_string(out_h) + " has an empty side");
+    const size_t want_in = (size_t)w * h * 3, want_out = (size_t)out_w * out_h * 3;
+    if (len != want_in) return bad_length(ctx, want_in, len);
+    if (out_len != want_out) return bad_length(ctx, want_out, out_len);
+    return leaf_roundtrip(ctx, rgb, len, out, out_len, [&](uint8_t *d_in, uint8_t *d_out) {
+        return resample_images(ctx, d_in, want_in, d_out, want_out, w, h, out_w, out_h, 1, filter);
+    });
+}
+
+// the checks two batches must pass before anything moves between them
+static int resample_check(ce_batch *src, ce_batch *dst, int filter)
+{
+    if (!src || !dst) return fail(src ? src->ctx : dst ? dst->ctx : nullptr, CE_ERR_INVALID_ARG, "resample: null batch");
+    ce_ctx *ctx = src->ctx;
+    if (dst->ctx != ctx) return fail(ctx, CE_ERR_INVALID_ARG, "resample: the two batches belong to different contexts");
+    if (src == dst) return fail(ctx, CE_ERR_INVALID_ARG, "resample: source and destination are the same batch");
+    if (!resample_filter_ok(filter)) return fail(ctx, CE_ERR_INVALID_ARG, "resample: unknown filter " + std::to_string(filter));
+    if (src->depth[0] || dst->depth[0])
+        return fail(ctx, CE_ERR_INVALID_ARG, "resample works on RGB8 batches: a deep batch is out of its scope");
+    return CE_OK;
+}
+
+static int resample_slab(ce_batch *src, ce_batch *dst, uint32_t which, uint32_t first, uint32_t count, int filter)
+{
+    ce_ctx *ctx = src->ctx;
+    const bool tests = which == CE_BATCH_TESTS;
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    // the kernels run on the context's stream: behind src's uploads (the ordering of a launch), and as an inline write of
+    // dst (order_write: behind dst's own uploads, ahead of its next launch and of its later uploads)
+    if (int rc = flush_uploads(src)) return rc;
+    if (int rc = order_write(dst, true)) return rc;
+    if (!tests) invalidate_reference_state(dst);
+    const uint8_t *s = (tests ? src->d_tests : src->d_refs) + (size_t)first * src->img_bytes;
+    uint8_t *d = (tests ? dst->d_tests : dst->d_refs) + (size_t)first * dst->img_bytes;
+    const int rc = resample_images(ctx, s, src->img_bytes, d, dst->img_bytes, src->w, src->h, dst->w, dst->h, count, filter);
+    src->inline_pending = true;  // a later upload into src waits for these reads (order_write)
+    return rc;
+}
+
+static int resample_range_check(ce_batch *src, ce_batch *dst, bool tests, uint32_t first, uint32_t count)
+{
+    const uint32_t slots = tests ? std::min(src->max_pairs, dst->max_pairs) : std::min(src->max_refs, dst->max_refs);
+    if (count == 0 || first > slots || count > slots - first)
+        return fail(src->ctx, CE_ERR_INVALID_ARG, std::string("resample: ") + (tests ? "tests [" : "references [") + std::to_string(first) + ", " +
+                                                      std::to_string((uint64_t)first + count) + ") outside the " + std::to_string(slots) +
+                                                      " slots both batches have");
+    return CE_OK;
+}
+
+int ce_batch_resample(ce_batch *src, ce_batch *dst, uint32_t which, uint32_t first, uint32_t count, int filter)
+{
+    if (int rc = resample_check(src, dst, filter)) return rc;
+    if (which != CE_BATCH_REFERENCES && which != CE_BATCH_TESTS)
+        return fail(src->ctx, CE_ERR_INVALID_ARG, "resample: unknown slab " + std::to_string(which));
+    if (int rc = resample_range_check(src, dst, which == CE_BATCH_TESTS, first, count)) return rc;
+    return resample_slab(src, dst, which, first, count, filter);
+}
+
+int ce_batch_resample_pairs(ce_batch *src, ce_batch *dst, uint32_t n_refs, uint32_t n_pairs, int filter)
+{
+    if (int rc = resample_check(src, dst, filter)) return rc;
+    if (int rc = resample_range_check(src, dst, false, 0, n_refs)) return rc;
+    if (int rc = resample_range_check(src, dst, true, 0, n_pairs)) return rc;
+    for (uint32_t i = 0; i < n_pairs; i++)
+        if (src->h_pair_ref[i] >= n_refs)
+            return fail(src->ctx, CE_ERR_INVALID_ARG, "resample: pair " + std::to_string(i) + " is bound to reference " +
+                                                          std::to_string(src->h_pair_ref[i]) + ", outside the " + std::to_string(n_refs) + " resampled");
+    if (int rc = resample_slab(src, dst, CE_BATCH_REFERENCES, 0, n_refs, filter)) return rc;
+    if (int rc = resample_slab(src, dst, CE_BATCH_TESTS, 0, n_pairs, filter)) return rc;
+    for (uint32_t i = 0; i < n_pairs; i++)
+        if (int rc = ce_batch_bind_pair(dst, i, src->h_pair_ref[i])) return rc;
+    return CE_OK;
 }
 
 // ---- reference handle -------------------------------------------------------------------------

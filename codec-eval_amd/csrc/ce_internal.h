@@ -55,6 +55,12 @@ struct ce_kernel_stat {
 #define CE_DEFAULT_FORK_ALONE_BELOW_MP 64.0
 #endif
 
+// One axis of a resample on the device: int32 [n_out] first tap | [n_out] tap count | [n_out][ksize] weights (22-bit fixed point)
+struct ce_resample_axis {
+    int32_t *d = nullptr;
+    uint32_t n_in = 0, n_out = 0, ksize = 0;
+};
+
 struct ce_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -99,6 +105,11 @@ struct ce_ctx {
     // and the page-locked buffer their results come back through
     uint8_t *heur_d = nullptr, *heur_h = nullptr;
     size_t heur_d_cap = 0, heur_h_cap = 0;
+    // grow-only device scratch of the resampler (resample.hip): the u8 image between its two passes, and the tap tables of
+    // the (in, out, filter) pairs used so far, keyed by them and kept until the context goes (ce_api.cpp: resample_table)
+    uint8_t *rs_mid = nullptr;
+    size_t rs_mid_cap = 0;
+    std::map<std::tuple<uint32_t, uint32_t, int>, struct ce_resample_axis> rs_tables;
 
     // Auxiliary streams of the context, shared by all its batches (made on first use, destroyed with the context): the
     // three metric chains of a forked batch, SSIMULACRA2's level-0 passes, Butteraugli's half-resolution chain.  Rounds
@@ -355,7 +366,17 @@ int ce_launch_rgb8_to_dssim_image(ce_ctx *ctx, const uint8_t *d_rgb, float *d_rg
 int ce_image_heuristics_run(ce_ctx *ctx, const uint8_t *d_imgs, size_t img_stride, uint32_t w, uint32_t h, uint32_t n,
                             ce_image_heuristics *out);
 
+// n images of w x h packed RGB8, src_stride bytes apart, to out_w x out_h, dst_stride apart, on `stream` (resample.hip):
+// `horiz` / `vert` are the axes whose size changes (nullptr: that pass is skipped; both nullptr is the caller's byte copy),
+// `mid` holds the n x h x out_w x 3 bytes between the passes when both run
+int ce_launch_resample(ce_ctx *ctx, hipStream_t stream, const uint8_t *d_src, size_t src_stride, uint8_t *d_dst, size_t dst_stride,
+                       uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h, uint32_t n, const ce_resample_axis *horiz,
+                       const ce_resample_axis *vert, uint8_t *mid);
+
 // host-side constant builders (ce_tables.cpp)
+// the resampler's taps of one axis, n_in -> n_out samples (include/ce_metrics.h, enum ce_resample_filter): table = [n_out]
+// first tap | [n_out] tap count | [n_out][ksize] weights; false for an unknown filter or an empty axis
+bool ce_build_resample_table(uint32_t n_in, uint32_t n_out, int filter, std::vector<int32_t> &table, uint32_t *ksize);
 void ce_build_srgb_lut_f64(float lut[256]);
 void ce_build_srgb_lut_powf(float lut[256]);
 // the same two rules for samples 0 .. maxv meaning v / maxv: lut has maxv + 1 entries

@@ -135,3 +135,64 @@ bool ce_build_xyb_srgb_thresholds(float thresh[256])
     }
     return ok;
 }
+
+// The taps of one axis of the resampler (include/ce_metrics.h, enum ce_resample_filter), all in f64
+// with the host libm as the sRGB tables above: Pillow's precompute_coeffs + normalize_coeffs_8bpc.
+static double resample_sinc(double x)
+{
+    if (x == 0.0) return 1.0;
+    x *= M_PI;
+    return std::sin(x) / x;
+}
+
+static double resample_weight(int filter, double x)
+{
+    switch (filter) {
+    case CE_RESAMPLE_BOX: return x > -0.5 && x <= 0.5 ? 1.0 : 0.0;
+    case CE_RESAMPLE_BILINEAR:
+        if (x < 0.0) x = -x;
+        return x < 1.0 ? 1.0 - x : 0.0;
+    case CE_RESAMPLE_BICUBIC: {
+        const double a = -0.5;
+        if (x < 0.0) x = -x;
+        if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+        if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+        return 0.0;
+    }
+    default: return -3.0 <= x && x < 3.0 ? resample_sinc(x) * resample_sinc(x / 3) : 0.0;
+    }
+}
+
+bool ce_build_resample_table(uint32_t n_in, uint32_t n_out, int filter, std::vector<int32_t> &table, uint32_t *ksize_out)
+{
+    static const double supports[4] = {0.5, 1.0, 2.0, 3.0};
+    if (filter < 0 || filter > 3 || n_in == 0 || n_out == 0) return false;
+    const double scale = (double)n_in / (double)n_out;
+    const double fs = scale < 1.0 ? 1.0 : scale;
+    const double support = supports[filter] * fs;
+    const uint32_t ksize = (uint32_t)std::ceil(support) * 2 + 1;
+    table.assign((size_t)n_out * (2 + (size_t)ksize), 0);
+    std::vector<double> k(ksize);
+    for (uint32_t xx = 0; xx < n_out; xx++) {
+        const double center = (xx + 0.5) * scale;
+        int64_t xmin = (int64_t)(center - support + 0.5);
+        if (xmin < 0) xmin = 0;
+        int64_t xmax = (int64_t)(center + support + 0.5);
+        if (xmax > (int64_t)n_in) xmax = n_in;
+        const int64_t n = xmax - xmin;
+        double ww = 0.0;
+        for (int64_t x = 0; x < n; x++) {
+            k[x] = resample_weight(filter, (x + xmin - center + 0.5) / fs);
+            ww += k[x];
+        }
+        table[xx] = (int32_t)xmin;
+        table[(size_t)n_out + xx] = (int32_t)n;
+        int32_t *out = &table[2 * (size_t)n_out + (size_t)xx * ksize];
+        for (int64_t x = 0; x < n; x++) {
+            const double v = ww != 0.0 ? k[x] / ww : k[x];
+            out[x] = v < 0 ? (int32_t)(-0.5 + v * (double)(1 << 22)) : (int32_t)(0.5 + v * (double)(1 << 22));
+        }
+    }
+    *ksize_out = ksize;
+    return true;
+}

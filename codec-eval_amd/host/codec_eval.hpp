@@ -12,6 +12,7 @@
 // loop, session.rs:375-410); results are emitted in the reference's loop order.
 #pragma once
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -272,6 +273,133 @@ inline ce_image_heuristics compute_heuristics(const HipBackend &be, const Bytes 
 }
 }  // namespace metrics
 
+// ---- src/viewing.rs: viewing conditions ------------------------------------------------------------------------------
+// ViewingCondition, SimulationMode, SimulationParams, REFERENCE_PPD and the presets, item for item (every formula f64,
+// std::round = f64::round: half away from zero).  The reference stops at the parameters; displayed_size() and
+// metrics::resample_rgb8 / ce_batch_resample go on to the image a viewer sees.
+namespace viewing {
+
+constexpr double REFERENCE_PPD = 40.0;  // viewing.rs:337
+
+enum class SimulationMode { Accurate, DownsampleOnly };  // viewing.rs:33-53
+
+namespace detail {
+inline uint32_t round_u32(double x)  // `x.round() as u32`: the cast saturates
+{
+    const double r = std::round(x);
+    if (!(r > 0.0)) return 0;
+    return r >= 4294967295.0 ? 4294967295u : (uint32_t)r;
+}
+}  // namespace detail
+
+struct SimulationParams {  // viewing.rs:308-331
+    double scale_factor = 1.0;
+    uint32_t target_width = 0, target_height = 0;
+    double adjusted_ppd = REFERENCE_PPD;
+    bool requires_upscale = false, requires_downscale = false;
+
+    bool requires_scaling() const { return requires_upscale || requires_downscale; }
+    double downscale_only_factor() const { return std::min(scale_factor, 1.0); }
+    double threshold_multiplier() const { return adjusted_ppd / REFERENCE_PPD; }
+    double adjust_dssim_threshold(double base) const { return base * threshold_multiplier(); }
+    double adjust_butteraugli_threshold(double base) const { return base * threshold_multiplier(); }
+    double adjust_ssimulacra2_threshold(double base) const  // viewing.rs:431-445
+    {
+        const double m = threshold_multiplier();
+        const double v = m >= 1.0 ? base - (100.0 - base) * (1.0 - 1.0 / m) : base + (100.0 - base) * (1.0 / m - 1.0);
+        return std::min(std::max(v, 0.0), 100.0);
+    }
+    bool dssim_acceptable(double dssim, double base) const { return dssim < adjust_dssim_threshold(base); }
+    bool butteraugli_acceptable(double b, double base) const { return b < adjust_butteraugli_threshold(base); }
+    bool ssimulacra2_acceptable(double s, double base) const { return s > adjust_ssimulacra2_threshold(base); }
+    // Not in the reference: the device pixels a width x height image occupies, round(n / scale_factor) per side and at
+    // least 1 - the size it is resampled to (target_width multiplies where a browser divides; the reference's tests pin it)
+    std::pair<uint32_t, uint32_t> displayed_size(uint32_t width, uint32_t height) const
+    {
+        if (scale_factor == 1.0) return {width, height};
+        return {std::max(1u, detail::round_u32((double)width / scale_factor)), std::max(1u, detail::round_u32((double)height / scale_factor))};
+    }
+};
+
+struct ViewingCondition {  // viewing.rs:74-104
+    double acuity_ppd = 40.0;  // Default = desktop(), viewing.rs:471-475
+    std::optional<double> browser_dppx, image_intrinsic_dppx, ppd;
+
+    static ViewingCondition make(double acuity_ppd) { return {acuity_ppd, std::nullopt, std::nullopt, std::nullopt}; }  // ::new
+    static ViewingCondition desktop() { return make(40.0); }
+    static ViewingCondition laptop() { return make(60.0); }
+    static ViewingCondition smartphone() { return make(90.0); }
+    ViewingCondition with_browser_dppx(double dppx) const
+    {
+        ViewingCondition v = *this;
+        v.browser_dppx = dppx;
+        return v;
+    }
+    ViewingCondition with_image_intrinsic_dppx(double dppx) const
+    {
+        ViewingCondition v = *this;
+        v.image_intrinsic_dppx = dppx;
+        return v;
+    }
+    ViewingCondition with_ppd_override(double p) const
+    {
+        ViewingCondition v = *this;
+        v.ppd = p;
+        return v;
+    }
+    double srcset_ratio() const { return image_intrinsic_dppx.value_or(1.0) / browser_dppx.value_or(1.0); }
+    double effective_ppd() const { return ppd ? *ppd : acuity_ppd * srcset_ratio(); }
+    SimulationParams simulation_params(uint32_t w, uint32_t h, SimulationMode mode) const  // viewing.rs:244-301
+    {
+        const double ratio = srcset_ratio();
+        if (mode == SimulationMode::Accurate || ratio >= 1.0)
+            return {ratio, detail::round_u32((double)w * ratio), detail::round_u32((double)h * ratio), effective_ppd(),
+                    mode == SimulationMode::Accurate && ratio < 1.0, ratio > 1.0};
+        return {1.0, w, h, acuity_ppd * ratio, false, false};
+    }
+    bool operator==(const ViewingCondition &o) const
+    {
+        return acuity_ppd == o.acuity_ppd && browser_dppx == o.browser_dppx && image_intrinsic_dppx == o.image_intrinsic_dppx && ppd == o.ppd;
+    }
+};
+
+namespace presets {  // viewing.rs:495-656
+inline ViewingCondition of(double acuity, double browser, double intrinsic)
+{
+    return ViewingCondition::make(acuity).with_browser_dppx(browser).with_image_intrinsic_dppx(intrinsic);
+}
+inline ViewingCondition native_desktop() { return of(40.0, 1.0, 1.0); }
+inline ViewingCondition native_laptop() { return of(70.0, 2.0, 2.0); }
+inline ViewingCondition native_phone() { return of(95.0, 3.0, 3.0); }
+inline ViewingCondition srcset_1x_on_phone() { return of(95.0, 3.0, 1.0); }
+inline ViewingCondition srcset_1x_on_laptop() { return of(70.0, 2.0, 1.0); }
+inline ViewingCondition srcset_2x_on_phone() { return of(95.0, 3.0, 2.0); }
+inline ViewingCondition srcset_2x_on_desktop() { return of(40.0, 1.0, 2.0); }
+inline ViewingCondition srcset_2x_on_laptop_1_5x() { return of(70.0, 1.5, 2.0); }
+inline ViewingCondition srcset_3x_on_phone() { return native_phone(); }
+inline std::vector<ViewingCondition> all()  // most demanding first
+{
+    return {srcset_1x_on_phone(), srcset_1x_on_laptop(), native_desktop(),           srcset_2x_on_phone(),
+            native_laptop(),      srcset_2x_on_desktop(), srcset_2x_on_laptop_1_5x(), native_phone()};
+}
+inline std::vector<ViewingCondition> key() { return {native_desktop(), native_laptop(), native_phone()}; }
+inline ViewingCondition baseline() { return native_laptop(); }
+inline ViewingCondition demanding() { return native_desktop(); }
+}  // namespace presets
+}  // namespace viewing
+
+namespace metrics {
+// One packed RGB8 image at another size (ce_resample_rgb8): what SimulationParams (viewing.rs:308-331) describes
+inline Bytes resample_rgb8(const HipBackend &be, const Bytes &rgb, uint32_t width, uint32_t height, uint32_t out_width, uint32_t out_height,
+                           int filter = CE_RESAMPLE_LANCZOS3)
+{
+    Bytes out((size_t)out_width * out_height * 3);
+    detail::check(be, ce_resample_rgb8(be.ctx(), rgb.data(), rgb.size(), width, height, out_width, out_height, filter, out.data(), out.size()),
+                  "resample", width, height, rgb.size());
+    return out;
+}
+}  // namespace metrics
+
 namespace eval {
 
 // ---- src/eval/session.rs:25-147 (the slice variants; imgref variants collapse to them in C++) ----------
@@ -336,6 +464,12 @@ struct EvalConfig {  // session.rs:190-279; the default quality sweep is :273-27
     MetricConfig metrics = MetricConfig::all();
     std::vector<double> quality_levels = {50.0, 60.0, 70.0, 80.0, 85.0, 90.0, 95.0};
     float intensity_target = CE_DEFAULT_INTENSITY_TARGET;
+    // session.rs:196 carries the condition and nothing reads it.  simulate_viewing unset: every score is what it always was.
+    // Set: the source and every decode are resampled on the device to the size `viewing` displays them at
+    // (SimulationParams::displayed_size) and scored there; untagged (sRGB) decodes only.
+    viewing::ViewingCondition viewing;
+    std::optional<viewing::SimulationMode> simulate_viewing;
+    int resample_filter = CE_RESAMPLE_LANCZOS3;
 };
 
 struct CodecResult {  // src/eval/report.rs:16-52
@@ -411,10 +545,26 @@ public:
                 report.results.push_back(std::move(r));
             }
         if (!decoded.empty()) {
+            uint32_t sw = (uint32_t)image.width, sh = (uint32_t)image.height;
+            std::vector<uint8_t> shown_reference;
+            const std::vector<uint8_t> *ref = &reference_rgb;
+            if (config_.simulate_viewing) {
+                const auto shown = config_.viewing.simulation_params(sw, sh, *config_.simulate_viewing).displayed_size(sw, sh);
+                if (shown != std::make_pair(sw, sh)) {
+                    for (const ce_lut *lut : luts)
+                        if (lut) throw Error(Error::Kind::MetricCalculation, "Metric calculation failed: viewing simulation takes untagged (sRGB) decodes only");
+                    shown_reference = metrics::resample_rgb8(*be_, reference_rgb, sw, sh, shown.first, shown.second, config_.resample_filter);
+                    ref = &shown_reference;
+                    for (auto &d : decoded) {
+                        detail::check(*be_, d.size() == reference_rgb.size() ? CE_OK : CE_ERR_DIM_MISMATCH, "metric", sw, sh, d.size());
+                        d = metrics::resample_rgb8(*be_, d, sw, sh, shown.first, shown.second, config_.resample_filter);
+                    }
+                    sw = shown.first, sh = shown.second;
+                }
+            }
             std::vector<ce_pair_desc> pairs(decoded.size());
             for (size_t i = 0; i < decoded.size(); i++)
-                pairs[i] = {reference_rgb.data(), reference_rgb.size(), decoded[i].data(), decoded[i].size(), (uint32_t)image.width,
-                            (uint32_t)image.height};
+                pairs[i] = {ref->data(), ref->size(), decoded[i].data(), decoded[i].size(), sw, sh};
             std::vector<ce_scores> scores(decoded.size());
             const int rc = ce_eval_batch_lut(be_->ctx(), pairs.size(), pairs.data(), luts.data(), config_.metrics.mask(),
                                              config_.metrics.flags(), config_.intensity_target, scores.data());

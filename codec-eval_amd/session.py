@@ -18,7 +18,9 @@ import numpy as np
 
 from . import (DEEP_DEPTHS, PIXEL_RGB8, PIXEL_RGB16, PIXEL_RGBA8, PIXEL_RGBA16, Batch, CodecEvalError, ColorTable, Context, DimensionMismatch, MetricCalculation,
                MetricConfig, MetricResult, _error_obj, estimate_batch_bytes, CE_ERR_BACKEND)
+from . import RESAMPLE_LANCZOS3
 from . import reports as R
+from .viewing import SimulationMode, ViewingCondition
 
 __all__ = ["ImageData", "EncodeRequest", "EvalConfig", "EvalConfigBuilder", "EvalSession"]
 
@@ -107,9 +109,14 @@ DecodeFn = Callable[[bytes], ImageData]
 class EvalConfig:  # session.rs:188-279
     report_dir: str
     cache_dir: Optional[str] = None
-    viewing: Optional[object] = None  # ViewingCondition: carried, not used by any metric (dssim.rs:40 ignores it too)
+    viewing: Optional[ViewingCondition] = None  # carried; no metric reads it (dssim.rs:43 ignores it too) unless simulate_viewing is set
     metrics: MetricConfig = field(default_factory=MetricConfig.all)
     quality_levels: List[float] = field(default_factory=lambda: [50.0, 60.0, 70.0, 80.0, 85.0, 90.0, 95.0])
+    # Not in the reference, whose simulation_params (src/viewing.rs:244-301) nothing consumes.  None: every score is what it
+    # always was.  A SimulationMode: each decode and its source are resampled on the device to the size `viewing` displays
+    # them at (SimulationParams.displayed_size, viewing.py) and scored there; 8-bit decodes only.
+    simulate_viewing: Optional[SimulationMode] = None
+    resample_filter: int = RESAMPLE_LANCZOS3
 
     @staticmethod
     def builder() -> "EvalConfigBuilder":
@@ -118,7 +125,7 @@ class EvalConfig:  # session.rs:188-279
 
 class EvalConfigBuilder:
     def __init__(self):
-        self._report_dir = self._cache_dir = self._viewing = self._metrics = self._levels = None
+        self._report_dir = self._cache_dir = self._viewing = self._metrics = self._levels = self._simulate = None
 
     def report_dir(self, path):
         self._report_dir = str(path)
@@ -130,6 +137,10 @@ class EvalConfigBuilder:
 
     def viewing(self, viewing):
         self._viewing = viewing
+        return self
+
+    def simulate_viewing(self, mode: Optional[SimulationMode]):
+        self._simulate = mode
         return self
 
     def metrics(self, metrics: MetricConfig):
@@ -148,6 +159,7 @@ class EvalConfigBuilder:
             cfg.metrics = self._metrics
         if self._levels is not None:
             cfg.quality_levels = self._levels
+        cfg.simulate_viewing = self._simulate
         return cfg
 
 
@@ -235,6 +247,13 @@ class EvalSession:
                 report.results.append(row)
         return report, pending
 
+    def _displayed(self, w: int, h: int) -> Tuple[int, int]:
+        """The size a w x h image is scored at: its own, unless config.simulate_viewing asks for the displayed one."""
+        if self.config.simulate_viewing is None:
+            return w, h
+        cond = self.config.viewing or ViewingCondition.default()
+        return cond.simulation_params(w, h, self.config.simulate_viewing).displayed_size(w, h)
+
     def _score(self, jobs: List[Tuple[ImageData, R.ImageReport, List[Tuple[int, ImageData]]]]):
         """All cells of all images, one device batch per shape; references uploaded once per image."""
         cfg = self.config.metrics
@@ -247,9 +266,11 @@ class EvalSession:
             # more cells than one batch holds is split (its reference is uploaded once per part)
             free, _total = self.ctx.memory_info()
             budget = int(os.environ.get("CE_SESSION_BATCH_BYTES", 0)) or int(free * 0.6)
-            fixed = estimate_batch_bytes(w, h, 0, 0, cfg)
-            per_ref = estimate_batch_bytes(w, h, 1, 0, cfg) - fixed
-            per_pair = estimate_batch_bytes(w, h, 0, 1, cfg) - fixed
+            sw, sh = self._displayed(w, h)  # the metrics' working set is the displayed shape's; the source slabs come on top
+            extra = 3 * w * h if (sw, sh) != (w, h) else 0
+            fixed = estimate_batch_bytes(sw, sh, 0, 0, cfg)
+            per_ref = estimate_batch_bytes(sw, sh, 1, 0, cfg) - fixed + extra
+            per_pair = estimate_batch_bytes(sw, sh, 0, 1, cfg) - fixed + extra
             max_pairs = max(1, (budget - fixed - per_ref) // max(per_pair, 1))
             parts: List[list] = [[]]  # each part: [(image, report, cells)]
             used = fixed
@@ -293,7 +314,16 @@ class EvalSession:
                     batch.set_test_lut(k, ri, decoded.data, decoded.pixel_format, self._table_for(decoded))  # to_rgb8_srgb, session.rs:394
                     rows.append((report, row_index))
                     k += 1
-            scores = batch.run(n_pairs, cfg)
+            shown = self._displayed(w, h)
+            if shown != (w, h):
+                dst = Batch(self.ctx, shown[0], shown[1], n_refs, n_pairs)
+                try:
+                    batch.resample_pairs_into(dst, n_refs, n_pairs, self.config.resample_filter)
+                    scores = dst.run(n_pairs, cfg)
+                finally:
+                    dst.close()
+            else:
+                scores = batch.run(n_pairs, cfg)
         finally:
             batch.close()
         for (report, row_index), s in zip(rows, scores):

@@ -430,6 +430,43 @@ int ce_batch_image_heuristics(ce_batch *b, uint32_t which, uint32_t first, uint3
 /* the same for the image of a reference handle (Ssimulacra2Reference::new, crates/codec-iter/src/eval.rs:138-149) */
 int ce_ref_image_heuristics(ce_ref *ref, ce_image_heuristics *out);
 
+/* ---- viewing simulation: the resampling ViewingCondition::simulation_params asks for (src/viewing.rs:244-301) -----------
+ * SimulationParams (src/viewing.rs:308-331) says at which size an image has to be looked at under a ViewingCondition
+ * ("simulate browser behavior exactly", src/viewing.rs:18-19, 33-53); the reference has no resampler and its metrics ignore
+ * the condition (src/metrics/dssim.rs:43).  These calls change an image's size on the device.  The resampler is the
+ * separable fixed-point convolution Pillow's Image.resize runs on 8-bit images, on the sRGB-encoded bytes as a browser
+ * does, bit for bit: per axis with scale = in / out, fs = max(scale, 1) and support = S * fs, output
+ * sample xx has center = (xx + 0.5) * scale, taps [xmin, xmax) = [max(0, (int)(center - support + 0.5)),
+ * min(in, (int)(center + support + 0.5))), weights f((x + xmin - center + 0.5) / fs) normalised by their left-to-right f64
+ * sum, each turned into (int)(+-0.5 + k * 2^22), and is clip_0_255((2^21 + sum k_i * sample_i) >> 22) in int32.  The
+ * horizontal pass runs first and writes u8, the vertical pass runs on that; a pass whose size does not change is skipped
+ * (equal sizes: a byte copy).  The weights are built on the host in f64.
+ *   BOX       f = 1 on (-0.5, 0.5], S = 0.5      BILINEAR  f = 1 - |x| on (-1, 1), S = 1
+ *   BICUBIC   Keys' cubic with a = -0.5, S = 2    LANCZOS3  sinc(x) sinc(x / 3) on [-3, 3), S = 3 */
+enum ce_resample_filter {
+    CE_RESAMPLE_BOX = 0,
+    CE_RESAMPLE_BILINEAR = 1,
+    CE_RESAMPLE_BICUBIC = 2,
+    CE_RESAMPLE_LANCZOS3 = 3
+};
+/* One packed RGB8 image of w x h to out_w x out_h (the image SimulationParams::target_width / target_height describe,
+ * src/viewing.rs:312-316).  CE_ERR_INVALID_ARG for a null pointer, an unknown filter or a zero size; CE_ERR_BAD_LENGTH
+ * unless len = w * h * 3 and out_len = out_w * out_h * 3. */
+int ce_resample_rgb8(ce_ctx *ctx, const uint8_t *rgb, size_t len, uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h,
+                     int filter, uint8_t *out, size_t out_len);
+/* Images [first, first + count) of src's reference or test slab (which: enum ce_batch_images) resampled into the same
+ * indices of dst, a batch of another (or the same) shape on the same context - the images of a resident sweep at the
+ * size a condition displays them (src/viewing.rs:244-301), with no upload and no host pixel pass.  Runs behind every
+ * ce_batch_set_* of src so far and before any later launch on dst; touches no metric buffer and no stored scores or maps
+ * of either batch; returns without waiting.  CE_ERR_INVALID_ARG, with the reason in ce_last_error, for a null handle,
+ * batches of different contexts, src = dst, an unknown slab or filter, count = 0, a range past either batch's slots, or a
+ * deep batch on either side (resampling u16 samples is not part of this). */
+int ce_batch_resample(ce_batch *src, ce_batch *dst, uint32_t which, uint32_t first, uint32_t count, int filter);
+/* Both slabs - references [0, n_refs) and tests [0, n_pairs) - and src's pair -> reference bindings of those pairs, so
+ * that ce_batch_run(dst, n_pairs, ...) follows directly (src/viewing.rs:244-301 applied to a whole grid).  Errors as
+ * ce_batch_resample. */
+int ce_batch_resample_pairs(ce_batch *src, ce_batch *dst, uint32_t n_refs, uint32_t n_pairs, int filter);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------ */
 /* Bracket every kernel launch with a HIP event pair, recorded on the stream the kernel is launched on,
  * and accumulate per-kernel time.  on = 0: off (default).  on = 2: events only; the batch keeps its
