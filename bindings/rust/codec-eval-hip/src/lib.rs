@@ -444,6 +444,75 @@ pub enum ResampleFilter {
     Lanczos3 = 3,
 }
 
+/// A decoder's Y'CbCr planes in HOST memory (`ce_yuv_image` with `CE_MEM_HOST`): what a JPEG decoder in raw mode or dav1d
+/// hands over.  `planes`: (Y, Cb, Cr), (Y, interleaved CbCr) with `semiplanar`, or (Y) for 4:0:0, each with its pitch in
+/// bytes; bytes are u8 samples at depth 8 and little-endian u16 above.  The enum fields take the `sys::CE_YUV_*` /
+/// `sys::CE_CHROMA_*` constants.  Device surfaces (rocJPEG / rocDecode) go through `sys::ce_yuv_image` directly.
+#[derive(Debug, Clone, Copy)]
+pub struct YuvPlanes<'p> {
+    pub planes: [Option<(&'p [u8], usize)>; 3],
+    pub subsampling: i32,
+    pub semiplanar: bool,
+    pub matrix: i32,
+    pub range: i32,
+    pub upsample: i32,
+    pub depth: i32,
+    pub msb_aligned: bool,
+}
+
+impl YuvPlanes<'_> {
+    /// The C struct, after checking that every plane given holds `rows` rows of its pitch (the library checks the rest).
+    fn to_sys(&self, width: u32, height: u32) -> Result<sys::ce_yuv_image, HipError> {
+        let ch = if self.subsampling == sys::CE_YUV_420 { (height as usize + 1) / 2 } else { height as usize };
+        let mut plane = [ptr::null::<std::os::raw::c_void>(); 3];
+        let mut pitch = [0usize; 3];
+        for (i, p) in self.planes.iter().enumerate() {
+            if let Some((bytes, stride)) = p {
+                let rows = if i == 0 { height as usize } else { ch };
+                let bps = if self.depth == 8 { 1 } else { 2 };
+                let cw = if self.subsampling == sys::CE_YUV_444 { width as usize } else { (width as usize + 1) / 2 };
+                let row = bps * if i == 0 { width as usize } else if self.semiplanar { 2 * cw } else { cw };
+                if rows > 0 && bytes.len() < (rows - 1) * stride + row {
+                    return Err(HipError::MetricCalculation { metric: "hip".into(), reason: format!("Y'CbCr plane {i} is shorter than its rows") });
+                }
+                plane[i] = bytes.as_ptr().cast();
+                pitch[i] = *stride;
+            }
+        }
+        Ok(sys::ce_yuv_image {
+            plane,
+            pitch,
+            subsampling: self.subsampling,
+            layout: if self.semiplanar { sys::CE_YUV_SEMIPLANAR } else { sys::CE_YUV_PLANAR },
+            matrix: self.matrix,
+            range: self.range,
+            upsample: self.upsample,
+            depth: self.depth,
+            msb_aligned: self.msb_aligned as i32,
+            memory: sys::CE_MEM_HOST,
+            lut: ptr::null(),
+        })
+    }
+}
+
+/// `ce_yuv_coefficients`: {KY, KRV, KGU, KGV, KBU, y0, c0} of the fixed-point conversion; `None` for a bad argument.
+pub fn yuv_coefficients(matrix: i32, range: i32, depth_in: u32, depth_out: u32) -> Option<[i64; 7]> {
+    let mut out = [0i64; 7];
+    let rc = unsafe { sys::ce_yuv_coefficients(matrix, range, depth_in, depth_out, out.as_mut_ptr()) };
+    (rc == sys::CE_OK).then_some(out)
+}
+
+impl HipMetrics {
+    /// `ce_yuv_to_rgb8`: one image's planes -> packed RGB8, upsampled and converted on the device.
+    pub fn yuv_to_rgb8(&mut self, image: &YuvPlanes<'_>, width: u32, height: u32) -> Result<Vec<u8>, HipError> {
+        let c = image.to_sys(width, height)?;
+        let mut out = vec![0u8; width as usize * height as usize * 3];
+        let rc = unsafe { sys::ce_yuv_to_rgb8(self.ctx, &c, width, height, out.as_mut_ptr(), out.len()) };
+        self.check(rc, width, height, out.len())?;
+        Ok(out)
+    }
+}
+
 /// `ce_batch`: images of one shape resident on the device, scored in one launch.  Resampling one grid into another
 /// (`resample_pairs_into`) scores a sweep at the size a `ViewingCondition` displays it (src/viewing.rs:244-301) without
 /// another upload.
@@ -467,6 +536,20 @@ impl HipBatch<'_> {
     pub fn set_test(&mut self, pair_index: u32, ref_index: u32, rgb: &[u8]) -> Result<(), HipError> {
         let rc = unsafe { sys::ce_batch_set_test(self.handle, pair_index, ref_index, rgb.as_ptr(), rgb.len()) };
         self.check(rc, rgb.len())
+    }
+
+    /// `ce_batch_set_reference_yuv`: a decoder's planes straight into a reference slot.
+    pub fn set_reference_yuv(&mut self, ref_index: u32, image: &YuvPlanes<'_>) -> Result<(), HipError> {
+        let c = image.to_sys(self.width, self.height)?;
+        let rc = unsafe { sys::ce_batch_set_reference_yuv(self.handle, ref_index, &c) };
+        self.check(rc, 0)
+    }
+
+    /// `ce_batch_set_test_yuv`: the same for the test image of pair `pair_index`, bound to reference `ref_index`.
+    pub fn set_test_yuv(&mut self, pair_index: u32, ref_index: u32, image: &YuvPlanes<'_>) -> Result<(), HipError> {
+        let c = image.to_sys(self.width, self.height)?;
+        let rc = unsafe { sys::ce_batch_set_test_yuv(self.handle, pair_index, ref_index, &c) };
+        self.check(rc, 0)
     }
 
     /// `ce_batch_resample`: references (`tests`: test images) `[first, first + count)` into the same indices of `dst`.

@@ -109,6 +109,40 @@ pub struct ce_pair_desc {
     pub height: u32,
 }
 
+// planar Y'CbCr ingest
+pub const CE_YUV_444: c_int = 0;
+pub const CE_YUV_422: c_int = 1;
+pub const CE_YUV_420: c_int = 2;
+pub const CE_YUV_400: c_int = 3;
+pub const CE_YUV_PLANAR: c_int = 0;
+pub const CE_YUV_SEMIPLANAR: c_int = 1;
+pub const CE_YUV_BT601: c_int = 0;
+pub const CE_YUV_BT709: c_int = 1;
+pub const CE_YUV_BT2020: c_int = 2;
+pub const CE_YUV_FULL: c_int = 0;
+pub const CE_YUV_LIMITED: c_int = 1;
+pub const CE_CHROMA_NEAREST: c_int = 0;
+pub const CE_CHROMA_TRIANGLE: c_int = 1;
+pub const CE_MEM_HOST: c_int = 0;
+pub const CE_MEM_DEVICE: c_int = 1;
+
+/// `ce_yuv_image` (88 bytes): a decoder's Y'CbCr planes, in host or device memory.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ce_yuv_image {
+    pub plane: [*const c_void; 3],
+    pub pitch: [usize; 3],
+    pub subsampling: c_int,
+    pub layout: c_int,
+    pub matrix: c_int,
+    pub range: c_int,
+    pub upsample: c_int,
+    pub depth: c_int,
+    pub msb_aligned: c_int,
+    pub memory: c_int,
+    pub lut: *const ce_lut,
+}
+
 extern "C" {
     pub fn ce_version() -> *const c_char;
     pub fn ce_device_count() -> c_int;
@@ -208,6 +242,12 @@ extern "C" {
                             out: *mut u8, out_len: usize) -> c_int;
     pub fn ce_batch_resample(src: *mut ce_batch, dst: *mut ce_batch, which: u32, first: u32, count: u32, filter: c_int) -> c_int;
     pub fn ce_batch_resample_pairs(src: *mut ce_batch, dst: *mut ce_batch, n_refs: u32, n_pairs: u32, filter: c_int) -> c_int;
+    pub fn ce_yuv_coefficients(matrix: c_int, range: c_int, depth_in: u32, depth_out: u32, out: *mut i64) -> c_int;
+    pub fn ce_batch_set_reference_yuv(b: *mut ce_batch, ref_index: u32, image: *const ce_yuv_image) -> c_int;
+    pub fn ce_batch_set_test_yuv(b: *mut ce_batch, pair_index: u32, ref_index: u32, image: *const ce_yuv_image) -> c_int;
+    pub fn ce_yuv_to_rgb8(ctx: *mut ce_ctx, image: *const ce_yuv_image, width: u32, height: u32, out: *mut u8, out_len: usize) -> c_int;
+    pub fn ce_yuv_to_rgb16(ctx: *mut ce_ctx, image: *const ce_yuv_image, width: u32, height: u32, depth_out: u32, out: *mut u16,
+                           out_len: usize) -> c_int;
     pub fn ce_prof_enable(ctx: *mut ce_ctx, on: c_int) -> c_int;
     pub fn ce_prof_filter(ctx: *mut ce_ctx, substring: *const c_char) -> c_int;
     pub fn ce_prof_reset(ctx: *mut ce_ctx) -> c_int;

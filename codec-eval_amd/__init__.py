@@ -43,6 +43,13 @@ DSSIM_MAX_LEVELS = 5  # CE_DSSIM_MAX_LEVELS
 SSIM2_MAX_SCALES = 6  # CE_SSIM2_MAX_SCALES
 SSIM2_MAP_SSIM, SSIM2_MAP_ARTIFACT, SSIM2_MAP_DETAIL_LOST = 0, 1, 2  # enum ce_ssim2_map
 RESAMPLE_BOX, RESAMPLE_BILINEAR, RESAMPLE_BICUBIC, RESAMPLE_LANCZOS3 = 0, 1, 2, 3  # enum ce_resample_filter
+# planar Y'CbCr ingest (include/ce_metrics.h)
+YUV_444, YUV_422, YUV_420, YUV_400 = 0, 1, 2, 3  # enum ce_yuv_subsampling
+YUV_PLANAR, YUV_SEMIPLANAR = 0, 1  # enum ce_yuv_layout
+YUV_BT601, YUV_BT709, YUV_BT2020 = 0, 1, 2  # enum ce_yuv_matrix
+YUV_FULL, YUV_LIMITED = 0, 1  # enum ce_yuv_range
+CHROMA_NEAREST, CHROMA_TRIANGLE = 0, 1  # enum ce_chroma_upsample
+MEM_HOST, MEM_DEVICE = 0, 1  # enum ce_mem
 
 _STATUS_NAMES = {
     CE_ERR_DIM_MISMATCH: "DimensionMismatch",
@@ -93,6 +100,22 @@ HEURISTICS_FIELDS = (
 
 class CeImageHeuristics(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in HEURISTICS_FIELDS[:3]] + [(f, C.c_float) for f in HEURISTICS_FIELDS[3:]]
+
+
+class CeYuvImage(C.Structure):
+    _fields_ = [
+        ("plane", C.c_void_p * 3),
+        ("pitch", C.c_size_t * 3),
+        ("subsampling", C.c_int),
+        ("layout", C.c_int),
+        ("matrix", C.c_int),
+        ("range", C.c_int),
+        ("upsample", C.c_int),
+        ("depth", C.c_int),
+        ("msb_aligned", C.c_int),
+        ("memory", C.c_int),
+        ("lut", C.c_void_p),
+    ]
 
 
 class CodecEvalError(RuntimeError):
@@ -197,6 +220,11 @@ _PROTOTYPES = [
     ("ce_resample_rgb8", _i, [_vp, _u8p, _sz, _u32, _u32, _u32, _u32, _i, _u8p, _sz]),
     ("ce_batch_resample", _i, [_vp, _vp, _u32, _u32, _u32, _i]),
     ("ce_batch_resample_pairs", _i, [_vp, _vp, _u32, _u32, _i]),
+    ("ce_yuv_coefficients", _i, [_i, _i, _u32, _u32, C.POINTER(C.c_int64 * 7)]),
+    ("ce_batch_set_reference_yuv", _i, [_vp, _u32, C.POINTER(CeYuvImage)]),
+    ("ce_batch_set_test_yuv", _i, [_vp, _u32, _u32, C.POINTER(CeYuvImage)]),
+    ("ce_yuv_to_rgb8", _i, [_vp, C.POINTER(CeYuvImage), _u32, _u32, _vp, _sz]),
+    ("ce_yuv_to_rgb16", _i, [_vp, C.POINTER(CeYuvImage), _u32, _u32, _u32, _vp, _sz]),
     ("ce_prof_enable", _i, [_vp, _i]),
     ("ce_prof_filter", _i, [_vp, C.c_char_p]),
     ("ce_prof_reset", _i, [_vp]),
@@ -250,6 +278,57 @@ def _buf16(a) -> np.ndarray:
     if arr.dtype != np.uint16:
         raise TypeError("deep pixel buffers must be uint16")
     return np.ascontiguousarray(arr).reshape(-1)
+
+
+def yuv_coefficients(matrix: int, range: int, depth_in: int, depth_out: int) -> Tuple[int, ...]:
+    """(KY, KRV, KGU, KGV, KBU, y0, c0): the fixed-point Y'CbCr -> RGB coefficients of ce_yuv_coefficients (a pure host
+    function, works without a device); raises for an unknown matrix / range or a depth outside the supported ones."""
+    out = (C.c_int64 * 7)()
+    rc = lib().ce_yuv_coefficients(matrix, range, depth_in, depth_out, C.byref(out))
+    if rc != CE_OK:
+        _raise(rc, f"yuv_coefficients: bad matrix {matrix}, range {range} or depths {depth_in} -> {depth_out}")
+    return tuple(int(v) for v in out)
+
+
+@dataclass
+class YuvImage:
+    """A decoder's Y'CbCr planes (struct ce_yuv_image).  `planes`: 2-D numpy arrays (uint8 at depth 8, uint16 above; a row
+    stride beyond the row is kept as the pitch), or integer device addresses with `pitches` in bytes and
+    memory=MEM_DEVICE.  PLANAR: (Y, Cb, Cr); SEMIPLANAR: (Y, interleaved CbCr); 4:0:0: (Y,)."""
+    planes: Sequence
+    subsampling: int = YUV_420
+    layout: int = YUV_PLANAR
+    matrix: int = YUV_BT601
+    range: int = YUV_FULL
+    upsample: int = CHROMA_TRIANGLE
+    depth: int = 8
+    msb_aligned: bool = False
+    memory: int = MEM_HOST
+    pitches: Optional[Sequence[int]] = None
+
+    def _c(self):
+        """(CeYuvImage, the arrays it borrows)"""
+        c = CeYuvImage()
+        keep = []
+        for i, p in enumerate(list(self.planes)[:3]):
+            if p is None:
+                continue
+            if isinstance(p, (int, np.integer)):
+                c.plane[i] = int(p)
+                c.pitch[i] = int(self.pitches[i]) if self.pitches is not None else 0
+                continue
+            a = np.asarray(p)
+            if a.ndim != 2 or a.dtype not in (np.uint8, np.uint16):
+                raise TypeError("a Y'CbCr plane is a 2-D uint8 or uint16 array")
+            if a.shape[1] > 1 and a.strides[1] != a.itemsize:
+                a = np.ascontiguousarray(a)
+            keep.append(a)
+            c.plane[i] = a.ctypes.data
+            c.pitch[i] = int(self.pitches[i]) if self.pitches is not None else (a.strides[0] if a.shape[0] > 1 else a.shape[1] * a.itemsize)
+        c.subsampling, c.layout, c.matrix, c.range = self.subsampling, self.layout, self.matrix, self.range
+        c.upsample, c.depth, c.msb_aligned, c.memory = self.upsample, self.depth, int(bool(self.msb_aligned)), self.memory
+        c.lut = None
+        return c, keep
 
 
 def version() -> str:
@@ -684,6 +763,21 @@ class Context:
                                            out.ctypes.data, out.size))
         return out
 
+    def yuv_to_rgb8(self, image: "YuvImage", width: int, height: int) -> np.ndarray:
+        """A decoder's Y'CbCr planes -> (height, width, 3) uint8 by the device's chroma upsampling and colour matrix
+        (ce_yuv_to_rgb8; the definition is in include/ce_metrics.h)."""
+        c, _keep = image._c()
+        out = np.empty((height, width, 3), np.uint8)
+        self._check(lib().ce_yuv_to_rgb8(self._h, C.byref(c), width, height, out.ctypes.data, out.size))
+        return out
+
+    def yuv_to_rgb16(self, image: "YuvImage", width: int, height: int, depth_out: int) -> np.ndarray:
+        """The same to (height, width, 3) uint16 samples of `depth_out` bits (8, 10, 12 or 16)."""
+        c, _keep = image._c()
+        out = np.empty((height, width, 3), np.uint16)
+        self._check(lib().ce_yuv_to_rgb16(self._h, C.byref(c), width, height, depth_out, out.ctypes.data, out.size))
+        return out
+
     # -- dispatcher
     def calculate_metrics(self, reference, test, width: int, height: int, config: MetricConfig,
                           intensity_target: float = DEFAULT_INTENSITY_TARGET) -> MetricResult:
@@ -852,6 +946,16 @@ class Batch:
     def set_test_fmt(self, pair_index: int, ref_index: int, pixels, fmt: int):
         a = np.ascontiguousarray(pixels)
         self.ctx._check(lib().ce_batch_set_test_fmt(self._h, pair_index, ref_index, a.ctypes.data, a.nbytes, fmt))
+        self._pair_ref[pair_index] = ref_index
+
+    # a decoder's Y'CbCr planes, host or device: upsampled and converted on the device, straight into the slot
+    def set_reference_yuv(self, ref_index: int, image: "YuvImage"):
+        c, _keep = image._c()
+        self.ctx._check(lib().ce_batch_set_reference_yuv(self._h, ref_index, C.byref(c)))
+
+    def set_test_yuv(self, pair_index: int, ref_index: int, image: "YuvImage"):
+        c, _keep = image._c()
+        self.ctx._check(lib().ce_batch_set_test_yuv(self._h, pair_index, ref_index, C.byref(c)))
         self._pair_ref[pair_index] = ref_index
 
     # ... and through a colour table (ICC -> sRGB on the device)

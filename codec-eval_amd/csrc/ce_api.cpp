@@ -1704,6 +1704,160 @@ int ce_batch_image_heuristics(ce_batch *b, uint32_t which, uint32_t first, uint3
     return ce_image_heuristics_run(ctx, slab + (size_t)first * b->img_bytes, b->img_bytes, b->w, b->h, count, out);
 }
 
+// ---- planar Y'CbCr ingest (yuv.hip) --------------------------------------------------------------
+
+// a checked ce_yuv_image: what the kernel reads, and each plane's rows for the host copy
+struct yuv_plan {
+    ce_yuv_dev dev{};
+    int n_planes = 0;
+    size_t rows[3] = {}, row_bytes[3] = {};
+    size_t offset[3] = {}, total = 0;  // the planes packed without pitch padding, each at an even offset
+};
+
+static int yuv_check(ce_ctx *ctx, const ce_yuv_image *img, uint32_t w, uint32_t h, uint32_t depth_out, yuv_plan *plan)
+{
+    if (!img) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: null image");
+    if (img->subsampling < CE_YUV_444 || img->subsampling > CE_YUV_400)
+        return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: unknown subsampling " + std::to_string(img->subsampling));
+    if (img->layout != CE_YUV_PLANAR && img->layout != CE_YUV_SEMIPLANAR)
+        return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: unknown layout " + std::to_string(img->layout));
+    if (img->upsample != CE_CHROMA_NEAREST && img->upsample != CE_CHROMA_TRIANGLE)
+        return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: unknown chroma upsampling " + std::to_string(img->upsample));
+    if (img->memory != CE_MEM_HOST && img->memory != CE_MEM_DEVICE)
+        return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: unknown memory kind " + std::to_string(img->memory));
+    if (img->depth != 8 && img->depth != 10 && img->depth != 12)
+        return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: depth must be 8, 10 or 12 bits, got " + std::to_string(img->depth));
+    if (img->msb_aligned && img->depth == 8) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: msb_aligned is for u16 samples, not depth 8");
+    if (img->lut) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: a colour table is 2^24 RGB colours and is not offered for YUV");
+    ce_yuv_dev &d = plan->dev;
+    if (ce_yuv_coefficients(img->matrix, img->range, (uint32_t)img->depth, depth_out, d.k) != CE_OK)
+        return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: unknown matrix " + std::to_string(img->matrix) + " or range " + std::to_string(img->range));
+    const size_t bps = img->depth == 8 ? 1 : 2;
+    const size_t cw = img->subsampling == CE_YUV_444 ? w : ((size_t)w + 1) / 2, ch = img->subsampling == CE_YUV_420 ? ((size_t)h + 1) / 2 : h;
+    const bool semi = img->layout == CE_YUV_SEMIPLANAR;
+    plan->n_planes = img->subsampling == CE_YUV_400 ? 1 : semi ? 2 : 3;
+    for (int p = 0; p < plan->n_planes; p++) {
+        plan->rows[p] = p == 0 ? h : ch;
+        plan->row_bytes[p] = (p == 0 ? (size_t)w : semi ? 2 * cw : cw) * bps;
+        if (!img->plane[p]) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: plane " + std::to_string(p) + " is missing");
+        if (img->pitch[p] < plan->row_bytes[p])
+            return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: pitch " + std::to_string(img->pitch[p]) + " of plane " + std::to_string(p) +
+                                                     " is under its row's " + std::to_string(plan->row_bytes[p]) + " bytes");
+        if (bps == 2 && ((reinterpret_cast<uintptr_t>(img->plane[p]) | img->pitch[p]) & 1))
+            return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: the pointer and pitch of u16 plane " + std::to_string(p) + " must be 2-byte aligned");
+        plan->offset[p] = plan->total;
+        plan->total += (plan->rows[p] * plan->row_bytes[p] + 1) & ~(size_t)1;
+        d.plane[p] = static_cast<const uint8_t *>(img->plane[p]);
+        d.pitch[p] = img->pitch[p];
+    }
+    d.subsampling = img->subsampling, d.layout = img->layout, d.upsample = img->upsample;
+    d.depth = (uint32_t)img->depth;
+    d.shift = img->msb_aligned ? 16u - (uint32_t)img->depth : 0u;
+    return CE_OK;
+}
+
+// host planes -> `h_stage` without their pitch padding; the device copy at d_stage is what the kernel then reads
+static void yuv_pack(const ce_yuv_image *img, yuv_plan *plan, uint8_t *h_stage, const uint8_t *d_stage)
+{
+    for (int p = 0; p < plan->n_planes; p++) {
+        const uint8_t *src = static_cast<const uint8_t *>(img->plane[p]);
+        uint8_t *dst = h_stage + plan->offset[p];
+        for (size_t r = 0; r < plan->rows[p]; r++) std::memcpy(dst + r * plan->row_bytes[p], src + r * img->pitch[p], plan->row_bytes[p]);
+        plan->dev.plane[p] = d_stage + plan->offset[p];
+        plan->dev.pitch[p] = plan->row_bytes[p];
+    }
+}
+
+// one Y'CbCr image into a slab slot on the batch's upload stream: device planes are read in place, host planes go
+// through the wide staging pair of upload_fmt (8 bytes per pixel: the packed planes are at most 6 and a few bytes)
+static int upload_yuv(ce_batch *b, uint8_t *dst, const ce_yuv_image *img, yuv_plan &plan, uint32_t depth)
+{
+    ce_ctx *ctx = b->ctx;
+    const size_t n_px = (size_t)b->w * b->h;
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    if (img->memory == CE_MEM_DEVICE) {
+        if (int rc = order_write(b, false)) return rc;
+        if (int rc = ce_launch_yuv(ctx, b->up_stream, plan.dev, b->w, b->h, dst, depth != 0, depth ? depth : 8)) return rc;
+        b->uploads_pending = true;
+        return CE_OK;
+    }
+    if (plan.total > n_px * 8) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: the packed planes do not fit the staging buffer");
+    const int k = b->next_wide;
+    b->next_wide ^= 1;
+    if (!b->h_wide[k]) {
+        CE_HIP(ctx, hipHostMalloc((void **)&b->h_wide[k], n_px * 8, hipHostMallocDefault));
+        CE_HIP(ctx, hipMalloc((void **)&b->d_wide[k], n_px * 8));
+        CE_HIP(ctx, hipEventCreateWithFlags(&b->ev_wide[k], hipEventDisableTiming));
+    }
+    if (int rc = order_write(b, false)) return rc;
+    if (b->wide_busy[k]) CE_HIP(ctx, hipEventSynchronize(b->ev_wide[k]));
+    yuv_pack(img, &plan, b->h_wide[k], b->d_wide[k]);
+    CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], plan.total, hipMemcpyHostToDevice, b->up_stream));
+    if (int rc = ce_launch_yuv(ctx, b->up_stream, plan.dev, b->w, b->h, dst, depth != 0, depth ? depth : 8)) return rc;
+    CE_HIP(ctx, hipEventRecord(b->ev_wide[k], b->up_stream));
+    b->wide_busy[k] = true;
+    b->uploads_pending = true;
+    return CE_OK;
+}
+
+int ce_batch_set_reference_yuv(ce_batch *b, uint32_t ref_index, const ce_yuv_image *image)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    if (ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "ref_index out of range");
+    yuv_plan plan;
+    if (int rc = yuv_check(b->ctx, image, b->w, b->h, b->depth[0] ? b->depth[0] : 8, &plan)) return rc;
+    invalidate_reference_state(b);
+    return upload_yuv(b, b->d_refs + (size_t)ref_index * b->img_bytes, image, plan, b->depth[0]);
+}
+
+int ce_batch_set_test_yuv(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const ce_yuv_image *image)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    if (pair_index >= b->max_pairs || ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "pair/ref index out of range");
+    yuv_plan plan;
+    if (int rc = yuv_check(b->ctx, image, b->w, b->h, b->depth[1] ? b->depth[1] : 8, &plan)) return rc;
+    if (int rc = ce_batch_bind_pair(b, pair_index, ref_index)) return rc;
+    return upload_yuv(b, b->d_tests + (size_t)pair_index * b->img_bytes, image, plan, b->depth[1]);
+}
+
+// one image -> host memory through the leaf scratch, on the context's stream
+static int yuv_to_host(ce_ctx *ctx, const ce_yuv_image *image, uint32_t w, uint32_t h, bool out16, uint32_t depth_out, void *out,
+                       size_t out_len)
+{
+    if (!ctx) return CE_ERR_INVALID_ARG;
+    if (!out) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: null output");
+    if (w == 0 || h == 0) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: empty image");
+    if (out16 && !deep_depth_ok(depth_out))
+        return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: the output depth must be 8, 10, 12 or 16 bits, got " + std::to_string(depth_out));
+    yuv_plan plan;
+    if (int rc = yuv_check(ctx, image, w, h, depth_out, &plan)) return rc;
+    const size_t samples = (size_t)w * h * 3, out_bytes = samples * (out16 ? 2 : 1);
+    if (out_len != samples)
+        return fail(ctx, CE_ERR_BAD_LENGTH, "Invalid image size: expected " + std::to_string(samples) + " samples, got " + std::to_string(out_len));
+    const bool host = image->memory == CE_MEM_HOST;
+    if (int rc = leaf_scratch(ctx, host ? plan.total : 1, out_bytes)) return rc;
+    if (host) {
+        yuv_pack(image, &plan, ctx->leaf_h, ctx->leaf_d_in);
+        CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_d_in, ctx->leaf_h, plan.total, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (int rc = ce_launch_yuv(ctx, ctx->stream, plan.dev, w, h, ctx->leaf_d_out, out16, depth_out)) return rc;
+    CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_h, ctx->leaf_d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(out, ctx->leaf_h, out_bytes);
+    return CE_OK;
+}
+
+int ce_yuv_to_rgb8(ce_ctx *ctx, const ce_yuv_image *image, uint32_t width, uint32_t height, uint8_t *out, size_t out_len)
+{
+    return yuv_to_host(ctx, image, width, height, false, 8, out, out_len);
+}
+
+int ce_yuv_to_rgb16(ce_ctx *ctx, const ce_yuv_image *image, uint32_t width, uint32_t height, uint32_t depth_out, uint16_t *out,
+                    size_t out_len)
+{
+    return yuv_to_host(ctx, image, width, height, true, depth_out, out, out_len);
+}
+
 // ---- viewing simulation: resampling (resample.hip) ----------------------------------------------
 
 // the taps of one axis on the device, built on first use and kept with the context (ce_ctx::rs_tables)

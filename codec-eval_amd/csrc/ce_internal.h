@@ -373,6 +373,17 @@ int ce_launch_resample(ce_ctx *ctx, hipStream_t stream, const uint8_t *d_src, si
                        uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h, uint32_t n, const ce_resample_axis *horiz,
                        const ce_resample_axis *vert, uint8_t *mid);
 
+// One Y'CbCr image on the device as yuv.hip reads it: checked by ce_api.cpp (yuv_check), planes in device memory
+struct ce_yuv_dev {
+    const uint8_t *plane[3];
+    size_t pitch[3];         // bytes
+    int subsampling, layout, upsample;
+    uint32_t depth, shift;   // bits per sample; right shift of an MSB-aligned u16 sample (0: low-aligned)
+    int64_t k[7];            // ce_yuv_coefficients for (matrix, range, depth, depth_out)
+};
+// w x h pixels of `src` -> packed RGB at d_dst: u8 (depth_out = 8, out16 = false) or u16 of depth_out, one launch (yuv.hip)
+int ce_launch_yuv(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32_t w, uint32_t h, void *d_dst, bool out16, uint32_t depth_out);
+
 // host-side constant builders (ce_tables.cpp)
 // the resampler's taps of one axis, n_in -> n_out samples (include/ce_metrics.h, enum ce_resample_filter): table = [n_out]
 // first tap | [n_out] tap count | [n_out][ksize] weights; false for an unknown filter or an empty axis

@@ -196,3 +196,43 @@ bool ce_build_resample_table(uint32_t n_in, uint32_t n_out, int filter, std::vec
     *ksize_out = ksize;
     return true;
 }
+
+// ---- Y'CbCr -> RGB fixed-point coefficients (include/ce_metrics.h: ce_yuv_coefficients; yuv.hip) ------------------------
+// {KY, KRV, KGU, KGV, KBU, y0, c0}, every product in f64 and rounded once with rint.  BT601 uses libjpeg's literals
+// (jdcolor.c), which are not the Kr / Kb quotients to the last digit: they are what makes d = D = 8 full range its table.
+int ce_yuv_coefficients(int matrix, int range, uint32_t depth_in, uint32_t depth_out, int64_t out[7])
+{
+    if (!out) return CE_ERR_INVALID_ARG;
+    if (depth_in != 8 && depth_in != 10 && depth_in != 12) return CE_ERR_INVALID_ARG;
+    if (depth_out != 8 && depth_out != 10 && depth_out != 12 && depth_out != 16) return CE_ERR_INVALID_ARG;
+    double a, b, c, e;
+    if (matrix == CE_YUV_BT601) {
+        a = 1.40200, b = 0.34414, c = 0.71414, e = 1.77200;
+    } else if (matrix == CE_YUV_BT709 || matrix == CE_YUV_BT2020) {
+        const double kr = matrix == CE_YUV_BT709 ? 0.2126 : 0.2627, kb = matrix == CE_YUV_BT709 ? 0.0722 : 0.0593;
+        const double kg = 1.0 - kr - kb;
+        a = 2.0 * (1.0 - kr), e = 2.0 * (1.0 - kb);
+        b = kb * e / kg, c = kr * a / kg;
+    } else {
+        return CE_ERR_INVALID_ARG;
+    }
+    const double m = (double)((1u << depth_out) - 1u), u = (double)(1u << (depth_in - 8));
+    double sy, sc;
+    int64_t y0, c0;
+    if (range == CE_YUV_FULL) {
+        y0 = 0, c0 = (int64_t)1 << (depth_in - 1);
+        sy = sc = m / (double)((1u << depth_in) - 1u);
+    } else if (range == CE_YUV_LIMITED) {
+        y0 = 16 << (depth_in - 8), c0 = 128 << (depth_in - 8);
+        sy = m / (219.0 * u), sc = m / (224.0 * u);
+    } else {
+        return CE_ERR_INVALID_ARG;
+    }
+    out[0] = (int64_t)std::rint(sy * 65536.0);
+    out[1] = (int64_t)std::rint(sc * a * 65536.0);
+    out[2] = (int64_t)std::rint(sc * b * 65536.0);
+    out[3] = (int64_t)std::rint(sc * c * 65536.0);
+    out[4] = (int64_t)std::rint(sc * e * 65536.0);
+    out[5] = y0, out[6] = c0;
+    return CE_OK;
+}

@@ -398,6 +398,42 @@ inline Bytes resample_rgb8(const HipBackend &be, const Bytes &rgb, uint32_t widt
                   "resample", width, height, rgb.size());
     return out;
 }
+
+// ---- planar Y'CbCr ingest: a decoder's planes, upsampled and converted on the device -------------
+// The struct is the ABI's; yuv_image() fills the common case (8-bit 4:2:0 planar, BT.601 full range, triangle upsampling:
+// what a JPEG decoder in raw mode hands over) and the caller changes what differs.
+using YuvImage = ce_yuv_image;
+inline YuvImage yuv_image(const void *y, size_t y_pitch, const void *cb, size_t cb_pitch, const void *cr, size_t cr_pitch,
+                          int memory = CE_MEM_HOST)
+{
+    YuvImage img{};
+    img.plane[0] = y, img.plane[1] = cb, img.plane[2] = cr;
+    img.pitch[0] = y_pitch, img.pitch[1] = cb_pitch, img.pitch[2] = cr_pitch;
+    img.subsampling = CE_YUV_420, img.layout = CE_YUV_PLANAR, img.matrix = CE_YUV_BT601, img.range = CE_YUV_FULL;
+    img.upsample = CE_CHROMA_TRIANGLE, img.depth = 8, img.msb_aligned = 0, img.memory = memory, img.lut = nullptr;
+    return img;
+}
+inline Bytes yuv_to_rgb8(const HipBackend &be, const YuvImage &image, uint32_t width, uint32_t height)
+{
+    Bytes out((size_t)width * height * 3);
+    detail::check(be, ce_yuv_to_rgb8(be.ctx(), &image, width, height, out.data(), out.size()), "yuv", width, height, out.size());
+    return out;
+}
+inline std::vector<uint16_t> yuv_to_rgb16(const HipBackend &be, const YuvImage &image, uint32_t width, uint32_t height, uint32_t depth_out)
+{
+    std::vector<uint16_t> out((size_t)width * height * 3);
+    detail::check(be, ce_yuv_to_rgb16(be.ctx(), &image, width, height, depth_out, out.data(), out.size()), "yuv", width, height, out.size());
+    return out;
+}
+// straight into a slot of a resident batch (RGB8 or deep), host or device planes
+inline void batch_set_reference_yuv(const HipBackend &be, ce_batch *batch, uint32_t ref_index, const YuvImage &image)
+{
+    detail::check(be, ce_batch_set_reference_yuv(batch, ref_index, &image), "yuv", 0, 0, 0);
+}
+inline void batch_set_test_yuv(const HipBackend &be, ce_batch *batch, uint32_t pair_index, uint32_t ref_index, const YuvImage &image)
+{
+    detail::check(be, ce_batch_set_test_yuv(batch, pair_index, ref_index, &image), "yuv", 0, 0, 0);
+}
 }  // namespace metrics
 
 namespace eval {

@@ -19,6 +19,7 @@ import numpy as np
 from . import (DEEP_DEPTHS, PIXEL_RGB8, PIXEL_RGB16, PIXEL_RGBA8, PIXEL_RGBA16, Batch, CodecEvalError, ColorTable, Context, DimensionMismatch, MetricCalculation,
                MetricConfig, MetricResult, _error_obj, estimate_batch_bytes, CE_ERR_BACKEND)
 from . import RESAMPLE_LANCZOS3
+from . import CHROMA_TRIANGLE, MEM_HOST, YUV_400, YUV_420, YUV_444, YUV_BT601, YUV_FULL, YUV_PLANAR, YUV_SEMIPLANAR, YuvImage, yuv_coefficients
 from . import reports as R
 from .viewing import SimulationMode, ViewingCondition
 
@@ -34,6 +35,7 @@ class ImageData:
     channels: int = 3
     icc_profile: Optional[bytes] = None
     depth: int = 0  # 0: 8-bit samples in u8; 8, 10, 12 or 16: a deep image (rgb16 / rgba16), scored at its own precision
+    yuv_image: Optional[YuvImage] = None  # an 8-bit decode still in its Y'CbCr planes (ImageData.yuv); `data` is then empty
 
     @staticmethod
     def rgb(data, width: int, height: int) -> "ImageData":
@@ -61,7 +63,56 @@ class ImageData:
             raise ValueError(f"depth must be one of {DEEP_DEPTHS}, got {depth}")
         return ImageData(np.ascontiguousarray(data, dtype=np.uint16).reshape(-1), int(width), int(height), 4, None, int(depth))
 
+    @staticmethod
+    def yuv(planes, width: int, height: int, subsampling: int = YUV_420, layout: int = YUV_PLANAR, matrix: int = YUV_BT601,
+            range: int = YUV_FULL, upsample: int = CHROMA_TRIANGLE) -> "ImageData":
+        """A decoder's 8-bit Y'CbCr planes in host memory (a JPEG decoder in raw mode, dav1d: 2-D uint8 arrays, Y, Cb, Cr or
+        Y, interleaved CbCr) as they are: the session upsamples and converts them on the device, straight into the batch
+        slot (Batch.set_*_yuv, the definition of include/ce_metrics.h), and scores the result as RGB8; the multi-device
+        session converts them on the host with to_rgb8_vec, the same definition.  Deeper planes go through
+        Batch.set_*_yuv."""
+        img = YuvImage([np.asarray(p) for p in planes], subsampling, layout, matrix, range, upsample, 8, False, MEM_HOST)
+        for p in img.planes:
+            if p.dtype != np.uint8 or p.ndim != 2:
+                raise TypeError("ImageData.yuv takes 2-D uint8 planes")
+        return ImageData(np.empty(0, np.uint8), int(width), int(height), 3, None, 0, img)
+
+    def _yuv_to_rgb8_host(self) -> np.ndarray:
+        """The device's conversion restated on the host for to_rgb8_vec (int64, the definition of include/ce_metrics.h)."""
+        y, w, h = self.yuv_image, self.width, self.height
+        ky, krv, kgu, kgv, kbu, y0, c0 = yuv_coefficients(y.matrix, y.range, 8, 8)
+        luma = y.planes[0].astype(np.int64)[:h, :w]
+        if y.subsampling == YUV_400:
+            cb = cr = np.full((h, w), c0, np.int64)
+        else:
+            if y.layout == YUV_SEMIPLANAR:
+                cb, cr = y.planes[1][:, 0::2].astype(np.int64), y.planes[1][:, 1::2].astype(np.int64)
+            else:
+                cb, cr = y.planes[1].astype(np.int64), y.planes[2].astype(np.int64)
+            cb, cr = (self._upsample_chroma(c, y.subsampling, y.upsample == CHROMA_TRIANGLE)[:h, :w] for c in (cb, cr))
+        yy = ky * (luma - y0) + 32768
+        rgb = np.stack([(yy + krv * (cr - c0)) >> 16, (yy - kgu * (cb - c0) - kgv * (cr - c0)) >> 16, (yy + kbu * (cb - c0)) >> 16], -1)
+        return np.clip(rgb, 0, 255).astype(np.uint8).reshape(-1)
+
+    @staticmethod
+    def _upsample_chroma(c: np.ndarray, subsampling: int, triangle: bool) -> np.ndarray:
+        if subsampling == YUV_444:
+            return c
+        shift = lambda a, k, axis: np.take(a, np.clip(np.arange(a.shape[axis]) + k, 0, a.shape[axis] - 1), axis=axis)
+        nb = (lambda a, k, axis: shift(a, k, axis)) if triangle else (lambda a, k, axis: a)
+        if subsampling == YUV_420:
+            t = np.empty((2 * c.shape[0], c.shape[1]), np.int64)
+            t[0::2], t[1::2] = 3 * c + nb(c, -1, 0), 3 * c + nb(c, 1, 0)
+            even, odd, sh = 8, 7, 4
+        else:
+            t, even, odd, sh = c, 1, 2, 2
+        out = np.empty((t.shape[0], 2 * t.shape[1]), np.int64)
+        out[:, 0::2], out[:, 1::2] = (3 * t + nb(t, -1, 1) + even) >> sh, (3 * t + nb(t, 1, 1) + odd) >> sh
+        return out
+
     def to_rgb8_vec(self) -> np.ndarray:  # session.rs:98-117 (host copy; the session itself strips alpha on the device)
+        if self.yuv_image is not None:
+            return self._yuv_to_rgb8_host()
         data = self.data if self.channels == 3 else np.ascontiguousarray(self.data.reshape(-1, 4)[:, :3]).reshape(-1)
         if self.depth:  # to_8bit's rule for any depth: what the reference does to a 10-bit decode before it measures
             maxv = (1 << self.depth) - 1
@@ -307,11 +358,17 @@ class EvalSession:
             rows = []
             k = 0
             for ri, (image, report, pending) in enumerate(group):
-                batch.set_reference_fmt(ri, image.data, image.pixel_format)
+                if image.yuv_image is not None:
+                    batch.set_reference_yuv(ri, image.yuv_image)
+                else:
+                    batch.set_reference_fmt(ri, image.data, image.pixel_format)
                 for row_index, decoded in pending:
                     if (decoded.width, decoded.height) != (w, h):  # calculate_metrics' length check, ssimulacra2.rs:65-70
                         raise DimensionMismatch(1, f"Dimension mismatch: expected ({w}, {h}), got ({decoded.width}, {decoded.height})")
-                    batch.set_test_lut(k, ri, decoded.data, decoded.pixel_format, self._table_for(decoded))  # to_rgb8_srgb, session.rs:394
+                    if decoded.yuv_image is not None:  # a decoder's Y'CbCr planes: upsampled and converted on the device, into the slot
+                        batch.set_test_yuv(k, ri, decoded.yuv_image)
+                    else:
+                        batch.set_test_lut(k, ri, decoded.data, decoded.pixel_format, self._table_for(decoded))  # to_rgb8_srgb, session.rs:394
                     rows.append((report, row_index))
                     k += 1
             shown = self._displayed(w, h)

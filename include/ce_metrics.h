@@ -467,6 +467,80 @@ int ce_batch_resample(ce_batch *src, ce_batch *dst, uint32_t which, uint32_t fir
  * ce_batch_resample. */
 int ce_batch_resample_pairs(ce_batch *src, ce_batch *dst, uint32_t n_refs, uint32_t n_pairs, int filter);
 
+/* ---- planar Y'CbCr ingest: a decoder's planes straight into a slot of a resident batch ----------
+ * A decoder works in Y'CbCr planes, usually 4:2:0 (a JPEG decoder in raw mode, dav1d / libavif, rocJPEG and rocDecode,
+ * whose surfaces are already in device memory); crates/codec-iter/src/avif_config.rs:163-169 bails on every PixelData
+ * variant that is not RGB.  These calls run the chroma upsampling and the colour matrix on the device, in integers, and
+ * write packed RGB into the slot: u8 on an RGB8 batch (output depth D = 8), u16 of that side's depth D on a deep batch.
+ *   samples   depth d in {8, 10, 12}: u8 at 8 bits, u16 little endian above, low-aligned (values above 2^d - 1 are
+ *             clamped to it, as deep ingest does) or MSB-aligned (P010: v >> (16 - d)).  m = 2^D - 1, u = 2^(d - 8).
+ *   chroma    planes are ceil(w / 2) wide for 4:2:0 and 4:2:2 and ceil(h / 2) tall for 4:2:0; they are upsampled to
+ *             2 cw x 2 ch (4:2:0) or 2 cw x h (4:2:2) and cropped to w x h.
+ *             CE_CHROMA_NEAREST   replication
+ *             CE_CHROMA_TRIANGLE  libjpeg's "fancy" upsampling, centre-sited, in integers (>> is a floor):
+ *               h2v2, chroma row r:  even output row  t[i] = 3 c[r][i] + c[max(r - 1, 0)][i]
+ *                                    odd output row   t[i] = 3 c[r][i] + c[min(r + 1, ch - 1)][i]
+ *                                    out[2i] = (3 t[i] + t[max(i - 1, 0)] + 8) >> 4
+ *                                    out[2i + 1] = (3 t[i] + t[min(i + 1, cw - 1)] + 7) >> 4
+ *               h2v1:                out[2i] = (3 c[i] + c[max(i - 1, 0)] + 1) >> 2
+ *                                    out[2i + 1] = (3 c[i] + c[min(i + 1, cw - 1)] + 2) >> 2
+ *   matrix    a (Cr -> R), b (Cb -> G), c (Cr -> G), e (Cb -> B).  BT601: the literals 1.40200, 0.34414, 0.71414, 1.77200
+ *             (libjpeg's jdcolor.c).  BT709 (Kr = 0.2126, Kb = 0.0722) and BT2020 (Kr = 0.2627, Kb = 0.0593): in f64,
+ *             a = 2 (1 - Kr), e = 2 (1 - Kb), b = Kb e / Kg, c = Kr a / Kg with Kg = 1 - Kr - Kb.
+ *   range     FULL: y0 = 0, c0 = 2^(d - 1), sy = sc = m / (2^d - 1).  LIMITED: y0 = 16 u, c0 = 128 u, sy = m / (219 u),
+ *             sc = m / (224 u).
+ *   fixed point, built on the host in f64, int64 on the device:
+ *             KY = rint(sy 2^16), KRV = rint(sc a 2^16), KGU = rint(sc b 2^16), KGV = rint(sc c 2^16), KBU = rint(sc e 2^16)
+ *             R = clamp((KY (y - y0) + KRV (cr - c0) + 2^15) >> 16, 0, m)
+ *             G = clamp((KY (y - y0) - KGU (cb - c0) - KGV (cr - c0) + 2^15) >> 16, 0, m)
+ *             B = clamp((KY (y - y0) + KBU (cb - c0) + 2^15) >> 16, 0, m)
+ *             BT601 / FULL / d = D = 8 gives 65536, 91881, 22554, 46802, 116130: libjpeg-turbo's decoder, bit for bit.
+ *             4:0:0 (gray): R = G = B from the Y term alone.
+ * Not part of this: left-cosited (MPEG-2 / H.264 default) and other chroma sitings, 4:1:1 / 4:4:0, packed YUYV, 16-bit
+ * YUV, PQ / HLG, identity / YCgCo matrices, YUV through ce_eval_batch, ce_ref_* and ce_batch_resample*, alpha planes. */
+enum ce_yuv_subsampling { CE_YUV_444 = 0, CE_YUV_422 = 1, CE_YUV_420 = 2, CE_YUV_400 = 3 };
+/* PLANAR: plane[0..2] = Y, Cb, Cr (I420 and its kin).  SEMIPLANAR: plane[0] = Y, plane[1] = interleaved Cb Cr pairs
+ * (NV12 / NV16 / P010), plane[2] unused.  4:0:0 reads plane[0] only under either layout. */
+enum ce_yuv_layout { CE_YUV_PLANAR = 0, CE_YUV_SEMIPLANAR = 1 };
+enum ce_yuv_matrix { CE_YUV_BT601 = 0, CE_YUV_BT709 = 1, CE_YUV_BT2020 = 2 };
+enum ce_yuv_range { CE_YUV_FULL = 0, CE_YUV_LIMITED = 1 };
+enum ce_chroma_upsample { CE_CHROMA_NEAREST = 0, CE_CHROMA_TRIANGLE = 1 };
+enum ce_mem { CE_MEM_HOST = 0, CE_MEM_DEVICE = 1 };
+typedef struct ce_yuv_image {
+    const void *plane[3];
+    size_t pitch[3];      /* bytes from one row to the next; may exceed the row */
+    int subsampling;      /* enum ce_yuv_subsampling */
+    int layout;           /* enum ce_yuv_layout */
+    int matrix;           /* enum ce_yuv_matrix */
+    int range;            /* enum ce_yuv_range */
+    int upsample;         /* enum ce_chroma_upsample */
+    int depth;            /* 8, 10 or 12 */
+    int msb_aligned;      /* u16 samples hold their value in the top bits (P010); depth 8: must be 0 */
+    int memory;           /* enum ce_mem: where the planes are */
+    const ce_lut *lut;    /* reserved, must be NULL: a colour table is 2^24 RGB colours and is not offered for YUV; a
+                           * non-NULL value is refused with CE_ERR_INVALID_ARG rather than ignored */
+} ce_yuv_image;
+/* {KY, KRV, KGU, KGV, KBU, y0, c0} as defined above.  A pure host function (no context, works without a device);
+ * CE_ERR_INVALID_ARG for an unknown matrix or range, depth_in outside {8, 10, 12}, depth_out outside {8, 10, 12, 16} or
+ * a null pointer. */
+int ce_yuv_coefficients(int matrix, int range, uint32_t depth_in, uint32_t depth_out, int64_t out[7]);
+/* One image of the batch's shape into a reference / test slot, on an RGB8 or a deep batch, on the same stream and with
+ * the same ordering as ce_batch_set_*_fmt.  CE_MEM_HOST planes are copied row by row (not the pitch padding) through the
+ * batch's page-locked staging and are consumed on return.  CE_MEM_DEVICE planes are read in place by the kernel, on the
+ * context's device: the caller must have finished writing them before the call and must keep them until the batch's next
+ * launch has been collected; the call returns without waiting.  CE_ERR_INVALID_ARG, with the reason in ce_last_error and
+ * the batch still usable, for a null struct, a missing plane of the layout, an unknown enum, a depth outside {8, 10, 12},
+ * a pitch under the row's bytes, a u16 plane pointer or pitch that is not 2-byte aligned, msb_aligned with depth 8, or a
+ * colour table. */
+int ce_batch_set_reference_yuv(ce_batch *b, uint32_t ref_index, const ce_yuv_image *image);
+int ce_batch_set_test_yuv(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const ce_yuv_image *image);
+/* One image of width x height to packed RGB8 (out_len = width * height * 3 bytes) or to packed u16 RGB of depth_out in
+ * {8, 10, 12, 16} (out_len = width * height * 3 samples) in host memory.  Errors as above; CE_ERR_BAD_LENGTH for a
+ * wrong out_len. */
+int ce_yuv_to_rgb8(ce_ctx *ctx, const ce_yuv_image *image, uint32_t width, uint32_t height, uint8_t *out, size_t out_len);
+int ce_yuv_to_rgb16(ce_ctx *ctx, const ce_yuv_image *image, uint32_t width, uint32_t height, uint32_t depth_out, uint16_t *out,
+                    size_t out_len);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------ */
 /* Bracket every kernel launch with a HIP event pair, recorded on the stream the kernel is launched on,
  * and accumulate per-kernel time.  on = 0: off (default).  on = 2: events only; the batch keeps its
