@@ -503,6 +503,24 @@ pub fn yuv_coefficients(matrix: i32, range: i32, depth_in: u32, depth_out: u32) 
 }
 
 impl HipMetrics {
+    /// `ce_composite_rgba8`: straight-alpha RGBA8 source-over onto the opaque colour `bg` -> packed RGB8, on the device.
+    pub fn composite_rgba8(&mut self, rgba: &[u8], width: u32, height: u32, bg: [u8; 3]) -> Result<Vec<u8>, HipError> {
+        let mut out = vec![0u8; width as usize * height as usize * 3];
+        let rc = unsafe { sys::ce_composite_rgba8(self.ctx, rgba.as_ptr(), rgba.len(), width, height, bg.as_ptr(), out.as_mut_ptr(), out.len()) };
+        self.check(rc, width, height, rgba.len())?;
+        Ok(out)
+    }
+
+    /// `ce_composite_rgba16`: the same for u16 samples of `depth` bits (8, 10, 12 or 16) and a background at that depth.
+    pub fn composite_rgba16(&mut self, rgba: &[u16], width: u32, height: u32, depth: u32, bg: [u16; 3]) -> Result<Vec<u16>, HipError> {
+        let mut out = vec![0u16; width as usize * height as usize * 3];
+        let rc = unsafe {
+            sys::ce_composite_rgba16(self.ctx, rgba.as_ptr(), rgba.len(), width, height, depth, bg.as_ptr(), out.as_mut_ptr(), out.len())
+        };
+        self.check(rc, width, height, rgba.len())?;
+        Ok(out)
+    }
+
     /// `ce_yuv_to_rgb8`: one image's planes -> packed RGB8, upsampled and converted on the device.
     pub fn yuv_to_rgb8(&mut self, image: &YuvPlanes<'_>, width: u32, height: u32) -> Result<Vec<u8>, HipError> {
         let c = image.to_sys(width, height)?;
@@ -536,6 +554,30 @@ impl HipBatch<'_> {
     pub fn set_test(&mut self, pair_index: u32, ref_index: u32, rgb: &[u8]) -> Result<(), HipError> {
         let rc = unsafe { sys::ce_batch_set_test(self.handle, pair_index, ref_index, rgb.as_ptr(), rgb.len()) };
         self.check(rc, rgb.len())
+    }
+
+    /// `ce_batch_set_reference_over`: one straight-alpha RGBA image (`format`: `sys::CE_PIXEL_RGBA8`, or
+    /// `sys::CE_PIXEL_RGBA16` on a deep batch; `pixels` are its bytes) composited on the device over each of `backgrounds`
+    /// (samples at the side's depth) into reference slots `first_ref ..`: the pixel is read once.
+    pub fn set_reference_over(&mut self, first_ref: u32, pixels: &[u8], format: i32, backgrounds: &[[u16; 3]]) -> Result<(), HipError> {
+        let rc = unsafe {
+            sys::ce_batch_set_reference_over(self.handle, first_ref, pixels.as_ptr().cast(), pixels.len(), format,
+                                             backgrounds.len() as u32, backgrounds.as_ptr().cast())
+        };
+        self.check(rc, pixels.len())
+    }
+
+    /// `ce_batch_set_test_over`: the same into test slots `first_pair ..`, pair `first_pair + k` bound to `ref_indices[k]`.
+    pub fn set_test_over(&mut self, first_pair: u32, ref_indices: &[u32], pixels: &[u8], format: i32, backgrounds: &[[u16; 3]])
+                         -> Result<(), HipError> {
+        if ref_indices.len() != backgrounds.len() {
+            return Err(HipError::MetricCalculation { metric: "hip".into(), reason: "one reference index per background".into() });
+        }
+        let rc = unsafe {
+            sys::ce_batch_set_test_over(self.handle, first_pair, ref_indices.as_ptr(), pixels.as_ptr().cast(), pixels.len(), format,
+                                        backgrounds.len() as u32, backgrounds.as_ptr().cast())
+        };
+        self.check(rc, pixels.len())
     }
 
     /// `ce_batch_set_reference_yuv`: a decoder's planes straight into a reference slot.

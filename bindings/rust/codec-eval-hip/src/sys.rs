@@ -126,6 +126,9 @@ pub const CE_CHROMA_TRIANGLE: c_int = 1;
 pub const CE_MEM_HOST: c_int = 0;
 pub const CE_MEM_DEVICE: c_int = 1;
 
+/// `CE_MAX_BACKGROUNDS`: solid colours one upload is composited over
+pub const CE_MAX_BACKGROUNDS: usize = 8;
+
 /// `ce_yuv_image` (88 bytes): a decoder's Y'CbCr planes, in host or device memory.
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -248,6 +251,14 @@ extern "C" {
     pub fn ce_yuv_to_rgb8(ctx: *mut ce_ctx, image: *const ce_yuv_image, width: u32, height: u32, out: *mut u8, out_len: usize) -> c_int;
     pub fn ce_yuv_to_rgb16(ctx: *mut ce_ctx, image: *const ce_yuv_image, width: u32, height: u32, depth_out: u32, out: *mut u16,
                            out_len: usize) -> c_int;
+    pub fn ce_batch_set_reference_over(b: *mut ce_batch, first_ref: u32, pixels: *const c_void, len: usize, format: c_int, n_bg: u32,
+                                       backgrounds: *const u16) -> c_int;
+    pub fn ce_batch_set_test_over(b: *mut ce_batch, first_pair: u32, ref_indices: *const u32, pixels: *const c_void, len: usize,
+                                  format: c_int, n_bg: u32, backgrounds: *const u16) -> c_int;
+    pub fn ce_composite_rgba8(ctx: *mut ce_ctx, rgba: *const u8, len: usize, w: u32, h: u32, bg: *const u8, out: *mut u8,
+                              out_len: usize) -> c_int;
+    pub fn ce_composite_rgba16(ctx: *mut ce_ctx, rgba: *const u16, len: usize, w: u32, h: u32, depth: u32, bg: *const u16,
+                               out: *mut u16, out_len: usize) -> c_int;
     pub fn ce_prof_enable(ctx: *mut ce_ctx, on: c_int) -> c_int;
     pub fn ce_prof_filter(ctx: *mut ce_ctx, substring: *const c_char) -> c_int;
     pub fn ce_prof_reset(ctx: *mut ce_ctx) -> c_int;

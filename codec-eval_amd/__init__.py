@@ -50,6 +50,8 @@ YUV_BT601, YUV_BT709, YUV_BT2020 = 0, 1, 2  # enum ce_yuv_matrix
 YUV_FULL, YUV_LIMITED = 0, 1  # enum ce_yuv_range
 CHROMA_NEAREST, CHROMA_TRIANGLE = 0, 1  # enum ce_chroma_upsample
 MEM_HOST, MEM_DEVICE = 0, 1  # enum ce_mem
+MAX_BACKGROUNDS = 8  # CE_MAX_BACKGROUNDS: solid colours one upload is composited over
+ALPHA_BLACK_WHITE = ((0, 0, 0), (255, 255, 255))  # the two page colours a transparent image is most often seen on, 8-bit
 
 _STATUS_NAMES = {
     CE_ERR_DIM_MISMATCH: "DimensionMismatch",
@@ -225,6 +227,10 @@ _PROTOTYPES = [
     ("ce_batch_set_test_yuv", _i, [_vp, _u32, _u32, C.POINTER(CeYuvImage)]),
     ("ce_yuv_to_rgb8", _i, [_vp, C.POINTER(CeYuvImage), _u32, _u32, _vp, _sz]),
     ("ce_yuv_to_rgb16", _i, [_vp, C.POINTER(CeYuvImage), _u32, _u32, _u32, _vp, _sz]),
+    ("ce_batch_set_reference_over", _i, [_vp, _u32, _vp, _sz, _i, _u32, _vp]),
+    ("ce_batch_set_test_over", _i, [_vp, _u32, _vp, _vp, _sz, _i, _u32, _vp]),
+    ("ce_composite_rgba8", _i, [_vp, _vp, _sz, _u32, _u32, _vp, _vp, _sz]),
+    ("ce_composite_rgba16", _i, [_vp, _vp, _sz, _u32, _u32, _u32, _vp, _vp, _sz]),
     ("ce_prof_enable", _i, [_vp, _i]),
     ("ce_prof_filter", _i, [_vp, C.c_char_p]),
     ("ce_prof_reset", _i, [_vp]),
@@ -278,6 +284,41 @@ def _buf16(a) -> np.ndarray:
     if arr.dtype != np.uint16:
         raise TypeError("deep pixel buffers must be uint16")
     return np.ascontiguousarray(arr).reshape(-1)
+
+
+def scale_background(rgb8: Sequence[int], depth: int) -> Tuple[int, ...]:
+    """An 8-bit background colour at `depth` bits: (v * m + 127) // 255 per sample, m = 2^depth - 1."""
+    m = (1 << depth) - 1
+    if any(not 0 <= int(v) <= 255 for v in rgb8) or len(rgb8) != 3:
+        raise ValueError(f"a background is three 8-bit values, got {tuple(rgb8)}")
+    return tuple((int(v) * m + 127) // 255 for v in rgb8)
+
+
+def composite_over(rgba, background: Sequence[int], depth: int = 8) -> np.ndarray:
+    """The device's alpha compositing on the host (include/ce_metrics.h: ce_batch_set_*_over), for the paths that have no
+    device: straight alpha, source-over onto the opaque colour `background` (three samples of `depth` bits), on the encoded
+    values, (c a + bg (m - a) + (m >> 1)) // m in exact integers.  rgba: (..., 4) uint8 (depth 8) or uint16; returns
+    (..., 3) of the same type."""
+    a = np.asarray(rgba)
+    if a.dtype not in (np.uint8, np.uint16) or a.shape[-1] != 4:
+        raise TypeError("composite_over takes (..., 4) uint8 or uint16 samples")
+    if a.dtype == np.uint8 and depth != 8:
+        raise ValueError("uint8 samples are depth 8")
+    m = (1 << depth) - 1
+    bg = np.asarray([int(v) for v in background], np.uint64)
+    if bg.shape != (3,) or int(bg.max()) > m:
+        raise ValueError(f"a background is three samples of at most {m}, got {tuple(background)}")
+    v = np.minimum(a.astype(np.uint64), m)
+    c, al = v[..., :3], v[..., 3:4]
+    return ((c * al + bg * (m - al) + (m >> 1)) // m).astype(a.dtype)
+
+
+def _backgrounds(backgrounds) -> np.ndarray:
+    """[n_bg][3] background samples as the contiguous u16 array the ABI takes"""
+    b = np.asarray(backgrounds)
+    if b.ndim != 2 or b.shape[1] != 3 or b.min(initial=0) < 0 or b.max(initial=0) > 0xffff:
+        raise ValueError("backgrounds are rows of three samples")
+    return np.ascontiguousarray(b, dtype=np.uint16)
 
 
 def yuv_coefficients(matrix: int, range: int, depth_in: int, depth_out: int) -> Tuple[int, ...]:
@@ -778,6 +819,26 @@ class Context:
         self._check(lib().ce_yuv_to_rgb16(self._h, C.byref(c), width, height, depth_out, out.ctypes.data, out.size))
         return out
 
+    def composite_rgba8(self, rgba, width: int, height: int, background: Sequence[int]) -> np.ndarray:
+        """Straight-alpha RGBA8 source-over onto the opaque 8-bit colour `background` -> (height, width, 3) uint8, on the
+        device (ce_composite_rgba8; the definition is in include/ce_metrics.h)."""
+        a = _buf(rgba)
+        bg = _backgrounds([background])
+        if int(bg.max()) > 255:
+            raise ValueError("an 8-bit background sample is at most 255")
+        bg8 = bg.astype(np.uint8)
+        out = np.empty((height, width, 3), np.uint8)
+        self._check(lib().ce_composite_rgba8(self._h, a.ctypes.data, a.size, width, height, bg8.ctypes.data, out.ctypes.data, out.size))
+        return out
+
+    def composite_rgba16(self, rgba, width: int, height: int, depth: int, background: Sequence[int]) -> np.ndarray:
+        """The same for u16 RGBA samples of `depth` bits (8, 10, 12 or 16) and a background at that depth."""
+        a = _buf16(rgba)
+        bg = _backgrounds([background])
+        out = np.empty((height, width, 3), np.uint16)
+        self._check(lib().ce_composite_rgba16(self._h, a.ctypes.data, a.size, width, height, depth, bg.ctypes.data, out.ctypes.data, out.size))
+        return out
+
     # -- dispatcher
     def calculate_metrics(self, reference, test, width: int, height: int, config: MetricConfig,
                           intensity_target: float = DEFAULT_INTENSITY_TARGET) -> MetricResult:
@@ -957,6 +1018,20 @@ class Batch:
         c, _keep = image._c()
         self.ctx._check(lib().ce_batch_set_test_yuv(self._h, pair_index, ref_index, C.byref(c)))
         self._pair_ref[pair_index] = ref_index
+
+    # a transparent image composited over solid colours on the device: one upload fills len(backgrounds) consecutive slots
+    def set_reference_over(self, first_ref: int, pixels, fmt: int, backgrounds):
+        a, bg = np.ascontiguousarray(pixels), _backgrounds(backgrounds)
+        self.ctx._check(lib().ce_batch_set_reference_over(self._h, first_ref, a.ctypes.data, a.nbytes, fmt, len(bg), bg.ctypes.data))
+
+    def set_test_over(self, first_pair: int, ref_indices: Sequence[int], pixels, fmt: int, backgrounds):
+        a, bg = np.ascontiguousarray(pixels), _backgrounds(backgrounds)
+        refs = np.ascontiguousarray(ref_indices, dtype=np.uint32)
+        if refs.shape != (len(bg),):
+            raise ValueError("set_test_over takes one reference index per background")
+        self.ctx._check(lib().ce_batch_set_test_over(self._h, first_pair, refs.ctypes.data, a.ctypes.data, a.nbytes, fmt, len(bg), bg.ctypes.data))
+        for k, r in enumerate(refs):
+            self._pair_ref[first_pair + k] = int(r)
 
     # ... and through a colour table (ICC -> sRGB on the device)
     def set_reference_lut(self, ref_index: int, pixels, fmt: int, table: Optional["ColorTable"]):

@@ -1858,6 +1858,123 @@ int ce_yuv_to_rgb16(ce_ctx *ctx, const ce_yuv_image *image, uint32_t width, uint
     return yuv_to_host(ctx, image, width, height, true, depth_out, out, out_len);
 }
 
+// ---- alpha: composited over solid backgrounds (alpha.hip) ----------------------------------------
+
+static int alpha_backgrounds_ok(ce_ctx *ctx, uint32_t n_bg, const uint16_t *backgrounds, uint32_t depth)
+{
+    if (n_bg == 0 || n_bg > CE_MAX_BACKGROUNDS)
+        return fail(ctx, CE_ERR_INVALID_ARG, "alpha compositing: 1 to " + std::to_string(CE_MAX_BACKGROUNDS) + " backgrounds, got " + std::to_string(n_bg));
+    const uint32_t m = (1u << depth) - 1u;
+    for (uint32_t i = 0; i < 3 * n_bg; i++)
+        if (backgrounds[i] > m)
+            return fail(ctx, CE_ERR_INVALID_ARG, "alpha compositing: background sample " + std::to_string(backgrounds[i]) + " is above " + std::to_string(m));
+    return CE_OK;
+}
+
+// the checks of one ce_batch_set_*_over call that do not depend on the slots; depth = that side's (0: an RGB8 batch)
+static int alpha_check(ce_batch *b, size_t len, int format, uint32_t n_bg, const uint16_t *backgrounds, uint32_t depth)
+{
+    ce_ctx *ctx = b->ctx;
+    if (format != CE_PIXEL_RGBA8 && format != CE_PIXEL_RGBA16)
+        return fail(ctx, CE_ERR_INVALID_ARG, format == CE_PIXEL_RGBA16_10BIT ? "alpha compositing: CE_PIXEL_RGBA16_10BIT rounds to 8 bits; a deep batch takes 10-bit alpha as CE_PIXEL_RGBA16"
+                                                                              : "alpha compositing: the format must be CE_PIXEL_RGBA8 or CE_PIXEL_RGBA16");
+    if (!depth && format == CE_PIXEL_RGBA16) return fail(ctx, CE_ERR_INVALID_ARG, "alpha compositing: CE_PIXEL_RGBA16 needs a deep batch (ce_batch_create_deep)");
+    if (depth && depth != 8 && format == CE_PIXEL_RGBA8)
+        return fail(ctx, CE_ERR_INVALID_ARG, "alpha compositing: an 8-bit image needs a side of depth 8, this one has " + std::to_string(depth));
+    const size_t want = (size_t)b->w * b->h * ce_pixel_bytes(format);
+    if (len != want)
+        return fail(ctx, CE_ERR_INVALID_ARG, "alpha compositing: expected " + std::to_string(want) + " bytes, got " + std::to_string(len));
+    return alpha_backgrounds_ok(ctx, n_bg, backgrounds, depth ? depth : 8);
+}
+
+// one RGBA image through the wide staging pair of upload_fmt into n_bg consecutive slots from dst on
+static int upload_over(ce_batch *b, uint8_t *dst, const void *pixels, size_t len, int format, uint32_t depth, uint32_t n_bg,
+                       const uint16_t *backgrounds)
+{
+    ce_ctx *ctx = b->ctx;
+    const size_t n_px = (size_t)b->w * b->h;
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    const int k = b->next_wide;
+    b->next_wide ^= 1;
+    if (!b->h_wide[k]) {
+        CE_HIP(ctx, hipHostMalloc((void **)&b->h_wide[k], n_px * 8, hipHostMallocDefault));
+        CE_HIP(ctx, hipMalloc((void **)&b->d_wide[k], n_px * 8));
+        CE_HIP(ctx, hipEventCreateWithFlags(&b->ev_wide[k], hipEventDisableTiming));
+    }
+    if (int rc = order_write(b, false)) return rc;
+    if (b->wide_busy[k]) CE_HIP(ctx, hipEventSynchronize(b->ev_wide[k]));
+    std::memcpy(b->h_wide[k], pixels, len);
+    CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], len, hipMemcpyHostToDevice, b->up_stream));
+    if (int rc = ce_launch_alpha(ctx, b->up_stream, b->d_wide[k], format == CE_PIXEL_RGBA16, dst, depth != 0, depth ? depth : 8, n_px, n_bg, backgrounds))
+        return rc;
+    CE_HIP(ctx, hipEventRecord(b->ev_wide[k], b->up_stream));
+    b->wide_busy[k] = true;
+    b->uploads_pending = true;
+    return CE_OK;
+}
+
+int ce_batch_set_reference_over(ce_batch *b, uint32_t first_ref, const void *pixels, size_t len, int format, uint32_t n_bg,
+                                const uint16_t *backgrounds)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    if (!pixels || !backgrounds) return fail(b->ctx, CE_ERR_INVALID_ARG, "alpha compositing: null pointer");
+    if (int rc = alpha_check(b, len, format, n_bg, backgrounds, b->depth[0])) return rc;
+    if (first_ref > b->max_refs || n_bg > b->max_refs - first_ref)
+        return fail(b->ctx, CE_ERR_INVALID_ARG, "alpha compositing: reference slots [" + std::to_string(first_ref) + ", " + std::to_string((uint64_t)first_ref + n_bg) +
+                                                    ") outside the " + std::to_string(b->max_refs) + " slots");
+    invalidate_reference_state(b);
+    return upload_over(b, b->d_refs + (size_t)first_ref * b->img_bytes, pixels, len, format, b->depth[0], n_bg, backgrounds);
+}
+
+int ce_batch_set_test_over(ce_batch *b, uint32_t first_pair, const uint32_t *ref_indices, const void *pixels, size_t len,
+                           int format, uint32_t n_bg, const uint16_t *backgrounds)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    if (!ref_indices || !pixels || !backgrounds) return fail(b->ctx, CE_ERR_INVALID_ARG, "alpha compositing: null pointer");
+    if (int rc = alpha_check(b, len, format, n_bg, backgrounds, b->depth[1])) return rc;
+    if (first_pair > b->max_pairs || n_bg > b->max_pairs - first_pair)
+        return fail(b->ctx, CE_ERR_INVALID_ARG, "alpha compositing: test slots [" + std::to_string(first_pair) + ", " + std::to_string((uint64_t)first_pair + n_bg) +
+                                                    ") outside the " + std::to_string(b->max_pairs) + " slots");
+    for (uint32_t k = 0; k < n_bg; k++)
+        if (ref_indices[k] >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "alpha compositing: ref index " + std::to_string(ref_indices[k]) + " out of range");
+    for (uint32_t k = 0; k < n_bg; k++)
+        if (int rc = ce_batch_bind_pair(b, first_pair + k, ref_indices[k])) return rc;
+    return upload_over(b, b->d_tests + (size_t)first_pair * b->img_bytes, pixels, len, format, b->depth[1], n_bg, backgrounds);
+}
+
+// one image over one colour -> host memory through the leaf scratch, on the context's stream
+static int composite_to_host(ce_ctx *ctx, const void *rgba, size_t len, uint32_t w, uint32_t h, bool deep, uint32_t depth,
+                             const uint16_t bg[3], void *out, size_t out_len)
+{
+    if (!ctx) return CE_ERR_INVALID_ARG;
+    if (!rgba || !bg || !out) return fail(ctx, CE_ERR_INVALID_ARG, "alpha compositing: null pointer");
+    if (!deep_depth_ok(depth)) return fail(ctx, CE_ERR_INVALID_ARG, "alpha compositing: depth must be 8, 10, 12 or 16 bits, got " + std::to_string(depth));
+    const size_t n_px = (size_t)w * h;
+    if (len != n_px * 4 || out_len != n_px * 3)
+        return fail(ctx, CE_ERR_INVALID_ARG, "alpha compositing: expected " + std::to_string(n_px * 4) + " samples in and " + std::to_string(n_px * 3) +
+                                                 " out, got " + std::to_string(len) + " and " + std::to_string(out_len));
+    if (int rc = alpha_backgrounds_ok(ctx, 1, bg, depth)) return rc;
+    if (n_px == 0) return CE_OK;
+    const size_t bps = deep ? 2 : 1;
+    return leaf_roundtrip(ctx, rgba, len * bps, out, out_len * bps, [&](uint8_t *d_in, uint8_t *d_out) {
+        return ce_launch_alpha(ctx, ctx->stream, d_in, deep, d_out, deep, depth, n_px, 1, bg);
+    });
+}
+
+int ce_composite_rgba8(ce_ctx *ctx, const uint8_t *rgba, size_t len, uint32_t w, uint32_t h, const uint8_t bg[3], uint8_t *out,
+                       size_t out_len)
+{
+    uint16_t bg16[3] = {};
+    for (int c = 0; bg && c < 3; c++) bg16[c] = bg[c];
+    return composite_to_host(ctx, rgba, len, w, h, false, 8, bg ? bg16 : nullptr, out, out_len);
+}
+
+int ce_composite_rgba16(ce_ctx *ctx, const uint16_t *rgba, size_t len, uint32_t w, uint32_t h, uint32_t depth, const uint16_t bg[3],
+                        uint16_t *out, size_t out_len)
+{
+    return composite_to_host(ctx, rgba, len, w, h, true, depth, bg, out, out_len);
+}
+
 // ---- viewing simulation: resampling (resample.hip) ----------------------------------------------
 
 // the taps of one axis on the device, built on first use and kept with the context (ce_ctx::rs_tables)

@@ -384,6 +384,12 @@ struct ce_yuv_dev {
 // w x h pixels of `src` -> packed RGB at d_dst: u8 (depth_out = 8, out16 = false) or u16 of depth_out, one launch (yuv.hip)
 int ce_launch_yuv(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32_t w, uint32_t h, void *d_dst, bool out16, uint32_t depth_out);
 
+// n_pixels RGBA pixels at d_src (u8, or u16 of `depth` bits: src16) source-over onto each of n_bg solid colours
+// (backgrounds[n_bg][3], <= 2^depth - 1) -> n_bg consecutive packed RGB images from d_dst on, u8 or u16 (dst16; u8
+// samples: depth 8), one launch (alpha.hip)
+int ce_launch_alpha(ce_ctx *ctx, hipStream_t stream, const void *d_src, bool src16, void *d_dst, bool dst16, uint32_t depth,
+                    size_t n_pixels, uint32_t n_bg, const uint16_t *backgrounds);
+
 // host-side constant builders (ce_tables.cpp)
 // the resampler's taps of one axis, n_in -> n_out samples (include/ce_metrics.h, enum ce_resample_filter): table = [n_out]
 // first tap | [n_out] tap count | [n_out][ksize] weights; false for an unknown filter or an empty axis

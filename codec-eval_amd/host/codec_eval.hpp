@@ -13,6 +13,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -434,6 +435,39 @@ inline void batch_set_test_yuv(const HipBackend &be, ce_batch *batch, uint32_t p
 {
     detail::check(be, ce_batch_set_test_yuv(batch, pair_index, ref_index, &image), "yuv", 0, 0, 0);
 }
+
+// ---- alpha: a transparent image composited over solid backgrounds on the device -----------------
+// straight alpha, source-over onto an opaque colour, on the encoded values: (c a + bg (m - a) + (m >> 1)) / m
+using Background = std::array<uint16_t, 3>;  // samples at the destination's depth (8-bit: <= 255)
+inline Bytes composite_rgba8(const HipBackend &be, const Bytes &rgba, uint32_t width, uint32_t height, const std::array<uint8_t, 3> &background)
+{
+    Bytes out((size_t)width * height * 3);
+    detail::check(be, ce_composite_rgba8(be.ctx(), rgba.data(), rgba.size(), width, height, background.data(), out.data(), out.size()),
+                  "alpha", width, height, rgba.size());
+    return out;
+}
+inline std::vector<uint16_t> composite_rgba16(const HipBackend &be, const std::vector<uint16_t> &rgba, uint32_t width, uint32_t height,
+                                              uint32_t depth, const Background &background)
+{
+    std::vector<uint16_t> out((size_t)width * height * 3);
+    detail::check(be, ce_composite_rgba16(be.ctx(), rgba.data(), rgba.size(), width, height, depth, background.data(), out.data(), out.size()),
+                  "alpha", width, height, rgba.size());
+    return out;
+}
+// one upload into backgrounds.size() consecutive slots of a resident batch (RGB8 or deep), slot k over backgrounds[k]
+inline void batch_set_reference_over(const HipBackend &be, ce_batch *batch, uint32_t first_ref, const void *pixels, size_t len, int format,
+                                     const std::vector<Background> &backgrounds)
+{
+    detail::check(be, ce_batch_set_reference_over(batch, first_ref, pixels, len, format, (uint32_t)backgrounds.size(),
+                                                  backgrounds.empty() ? nullptr : backgrounds[0].data()), "alpha", 0, 0, len);
+}
+inline void batch_set_test_over(const HipBackend &be, ce_batch *batch, uint32_t first_pair, const std::vector<uint32_t> &ref_indices,
+                                const void *pixels, size_t len, int format, const std::vector<Background> &backgrounds)
+{
+    if (ref_indices.size() != backgrounds.size()) throw Error(Error::Kind::MetricCalculation, "alpha: one reference index per background");
+    detail::check(be, ce_batch_set_test_over(batch, first_pair, ref_indices.data(), pixels, len, format, (uint32_t)backgrounds.size(),
+                                             backgrounds.empty() ? nullptr : backgrounds[0].data()), "alpha", 0, 0, len);
+}
 }  // namespace metrics
 
 namespace eval {
@@ -506,7 +540,26 @@ struct EvalConfig {  // session.rs:190-279; the default quality sweep is :273-27
     viewing::ViewingCondition viewing;
     std::optional<viewing::SimulationMode> simulate_viewing;
     int resample_filter = CE_RESAMPLE_LANCZOS3;
+    // Not in the reference, which drops alpha (session.rs:98-117).  Empty: every score is what it always was.  8-bit colours
+    // (kAlphaBlackWhite): a pair whose source or decode is Rgba8 is composited over each on the device and scored over each;
+    // CodecResult::metrics carries the worst value per metric, ImageReport::alpha_scores the per-background ones.
+    std::vector<std::array<uint8_t, 3>> alpha_backgrounds;
 };
+inline const std::vector<std::array<uint8_t, 3>> kAlphaBlackWhite = {{0, 0, 0}, {255, 255, 255}};
+
+// one pair's scores over each background -> the worst value per metric: max DSSIM, max Butteraugli, min SSIMULACRA2, min PSNR
+inline MetricResult worst_over_backgrounds(const std::vector<MetricResult> &per_bg)
+{
+    MetricResult w = per_bg.at(0);
+    for (size_t k = 1; k < per_bg.size(); k++) {
+        const MetricResult &m = per_bg[k];
+        w.dssim = w.dssim && m.dssim ? std::optional<double>(std::max(*w.dssim, *m.dssim)) : std::nullopt;
+        w.butteraugli = w.butteraugli && m.butteraugli ? std::optional<double>(std::max(*w.butteraugli, *m.butteraugli)) : std::nullopt;
+        w.ssimulacra2 = w.ssimulacra2 && m.ssimulacra2 ? std::optional<double>(std::min(*w.ssimulacra2, *m.ssimulacra2)) : std::nullopt;
+        w.psnr = w.psnr && m.psnr ? std::optional<double>(std::min(*w.psnr, *m.psnr)) : std::nullopt;
+    }
+    return w;
+}
 
 struct CodecResult {  // src/eval/report.rs:16-52
     std::string codec_id, codec_version;
@@ -523,6 +576,8 @@ struct ImageReport {  // report.rs:68-136
     std::string name;
     uint32_t width = 0, height = 0;
     std::vector<CodecResult> results;
+    // EvalConfig::alpha_backgrounds: result index -> its scores over each background, for the results that were composited
+    std::map<size_t, std::vector<MetricResult>> alpha_scores;
 };
 
 class EvalSession {  // session.rs:281-497
@@ -551,7 +606,8 @@ public:
     ImageReport evaluate_image(const std::string &name, const ImageData &image) const
     {
         std::vector<const ce_lut *> luts;
-        ImageReport report{name, (uint32_t)image.width, (uint32_t)image.height, {}};
+        ImageReport report{name, (uint32_t)image.width, (uint32_t)image.height, {}, {}};
+        if (!config_.alpha_backgrounds.empty()) return evaluate_image_over(std::move(report), image);
         const std::vector<uint8_t> reference_rgb = image.to_rgb8_vec();
         std::vector<std::vector<uint8_t>> decoded;  // kept alive until the batch has run
         std::vector<size_t> result_of_pair;
@@ -621,6 +677,79 @@ private:
         EncodeFn encode;
         DecodeFn decode;
     };
+    // `image` seen over `bg`: composited on the device (ce_composite_rgba8) if it has alpha, to_rgb8_vec otherwise
+    std::vector<uint8_t> seen_over(const ImageData &image, const std::array<uint8_t, 3> &bg) const
+    {
+        if (image.format != ImageData::Format::Rgba8) return image.to_rgb8_vec();
+        return metrics::composite_rgba8(*be_, image.data, (uint32_t)image.width, (uint32_t)image.height, bg);
+    }
+    // evaluate_image with EvalConfig::alpha_backgrounds set: the sweep as ever; a pair with alpha on either side becomes one
+    // pair per background of the pooled batch call, a pair without stays one
+    ImageReport evaluate_image_over(ImageReport report, const ImageData &image) const
+    {
+        if (config_.simulate_viewing) throw Error(Error::Kind::MetricCalculation, "Metric calculation failed: alpha_backgrounds with simulate_viewing is not offered here");
+        const auto &bgs = config_.alpha_backgrounds;
+        const bool src_alpha = image.format == ImageData::Format::Rgba8;
+        std::vector<std::vector<uint8_t>> refs;  // the source over each background (one entry if it has no alpha)
+        for (size_t k = 0; k < (src_alpha ? bgs.size() : 1); k++) refs.push_back(seen_over(image, bgs[k]));
+        std::vector<std::vector<uint8_t>> tests;
+        std::vector<const ce_lut *> luts;
+        std::vector<size_t> ref_of_pair, result_of_pair;
+        for (const auto &codec : codecs_)
+            for (double quality : config_.quality_levels) {
+                EncodeRequest request{quality, {}};
+                const auto t0 = std::chrono::steady_clock::now();
+                const std::vector<uint8_t> encoded = codec.encode(image, request);
+                const auto t1 = std::chrono::steady_clock::now();
+                CodecResult r;
+                r.codec_id = codec.id;
+                r.codec_version = codec.version;
+                r.quality = quality;
+                r.file_size = encoded.size();
+                r.bits_per_pixel = (double)(encoded.size() * 8) / ((double)image.width * (double)image.height);
+                r.encode_time = t1 - t0;
+                r.codec_params = request.params;
+                if (codec.decode) {
+                    const auto d0 = std::chrono::steady_clock::now();
+                    const ImageData dec = codec.decode(encoded);
+                    r.decode_time = std::chrono::steady_clock::now() - d0;
+                    const bool dec_alpha = dec.format == ImageData::Format::Rgba8;
+                    const ce_lut *lut = table_for(dec);
+                    if (dec_alpha && lut) throw Error(Error::Kind::MetricCalculation, "Metric calculation failed: alpha_backgrounds: a decode with alpha and an ICC profile is not supported");
+                    if (dec_alpha && (dec.width != image.width || dec.height != image.height))
+                        detail::check(*be_, CE_ERR_DIM_MISMATCH, "metric", image.width, image.height, dec.data.size());
+                    for (size_t k = 0; k < (src_alpha || dec_alpha ? bgs.size() : 1); k++) {
+                        tests.push_back(seen_over(dec, bgs[k]));
+                        luts.push_back(lut);
+                        ref_of_pair.push_back(src_alpha ? k : 0);
+                        result_of_pair.push_back(report.results.size());
+                    }
+                }
+                report.results.push_back(std::move(r));
+            }
+        if (tests.empty()) return report;
+        std::vector<ce_pair_desc> pairs(tests.size());
+        for (size_t i = 0; i < tests.size(); i++) {
+            const auto &ref = refs[ref_of_pair[i]];
+            pairs[i] = {ref.data(), ref.size(), tests[i].data(), tests[i].size(), (uint32_t)image.width, (uint32_t)image.height};
+        }
+        std::vector<ce_scores> scores(tests.size());
+        const int rc = ce_eval_batch_lut(be_->ctx(), pairs.size(), pairs.data(), luts.data(), config_.metrics.mask(), config_.metrics.flags(),
+                                         config_.intensity_target, scores.data());
+        detail::check(*be_, rc, "batch", image.width, image.height, refs[0].size());
+        std::map<size_t, std::vector<MetricResult>> per_result;
+        for (size_t i = 0; i < tests.size(); i++) {
+            detail::check(*be_, scores[i].status, "metric", image.width, image.height, tests[i].size());
+            per_result[result_of_pair[i]].push_back(MetricResult::from_c(scores[i]));
+        }
+        for (auto &[index, per_bg] : per_result) {
+            CodecResult &r = report.results[index];
+            r.metrics = worst_over_backgrounds(per_bg);
+            r.perception = r.metrics.perception_level();  // session.rs:407
+            if (per_bg.size() > 1) report.alpha_scores[index] = std::move(per_bg);
+        }
+        return report;
+    }
     const ce_lut *table_for(const ImageData &decoded) const
     {
         if (!decoded.icc_profile) return nullptr;  // ColorProfile::Srgb: a plain copy (icc.rs:73)

@@ -245,6 +245,8 @@ public:
 
     std::vector<ImageReport> evaluate_corpus(const std::vector<std::pair<std::string, ImageData>> &images, MultiDeviceStats *stats = nullptr) const
     {
+        if (!config_.alpha_backgrounds.empty())  // not silently dropped: EvalSession (one device) is the route for it
+            throw Error(Error::Kind::MetricCalculation, "Metric calculation failed: alpha_backgrounds is not offered by the multi-device session");
         std::vector<ImageReport> reports(images.size());
         std::vector<std::vector<uint8_t>> references(images.size());
         std::vector<std::vector<std::vector<uint8_t>>> decoded(images.size());
@@ -253,7 +255,7 @@ public:
         std::vector<std::vector<uint8_t>> profiles;  // distinct ICC profiles met among the decoded images
         for (size_t i = 0; i < images.size(); i++) {
             const ImageData &image = images[i].second;
-            reports[i] = ImageReport{images[i].first, (uint32_t)image.width, (uint32_t)image.height, {}};
+            reports[i] = ImageReport{images[i].first, (uint32_t)image.width, (uint32_t)image.height, {}, {}};
             references[i] = image.to_rgb8_vec();
             for (const auto &codec : codecs_)
                 for (double quality : config_.quality_levels) {

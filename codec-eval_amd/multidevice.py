@@ -22,7 +22,7 @@ import numpy as np
 from . import (CE_ERR_BACKEND, ColorTable, Context, MetricCalculation, MetricConfig, MetricResult, _error_obj, device_count,
                estimate_batch_bytes)
 from . import reports as R
-from .session import EvalConfig, EvalSession, ImageData
+from .session import EvalConfig, EvalSession, ImageData, worst_over_backgrounds
 
 __all__ = ["GuidedQueue", "ReferenceJob", "DevicePool", "MultiDeviceEvalSession", "largest_first"]
 
@@ -203,25 +203,41 @@ class MultiDeviceEvalSession:
 
     def evaluate_corpus(self, name: str, images: Sequence[Tuple[str, ImageData]]) -> Tuple[R.CorpusReport, dict]:
         corpus = R.CorpusReport(name, config_summary=f"metrics: {self.config.metrics}")
+        # EvalConfig.alpha_backgrounds: there is no device on this thread, so a pair with alpha is composited on the host
+        # (ImageData.composited_rgb8_vec -> composite_over, the device's definition) and becomes one job per background;
+        # job 0 of an image also holds its pairs without alpha, which are scored once
+        bgs = self.config.alpha_backgrounds or ()
         jobs, rows = [], []
         for img_name, image in images:
             report, pending = EvalSession._sweep(self._sweeper, img_name, image)
             corpus.images.append(report)
-            job = ReferenceJob(image.to_rgb8_vec(), image.width, image.height)
             for row_index, decoded in pending:
                 if (decoded.width, decoded.height) != (image.width, image.height):
                     raise _error_obj(1, f"Dimension mismatch: expected ({image.width}, {image.height}), got ({decoded.width}, {decoded.height})")
-                job.tests.append(decoded.to_rgb8_vec())
-                job.test_profiles.append(decoded.icc_profile)
-            jobs.append(job)
-            rows.append((report, [ri for ri, _ in pending]))
+            for k in range(max(len(bgs), 1)):
+                cells = [(ri, d) for ri, d in pending if k == 0 or image.has_alpha or d.has_alpha]
+                if k > 0 and not cells:
+                    continue
+                job = ReferenceJob(image.composited_rgb8_vec(bgs[k]) if bgs else image.to_rgb8_vec(), image.width, image.height)
+                for row_index, decoded in cells:
+                    if bgs and decoded.has_alpha and decoded.icc_profile is not None:
+                        raise _error_obj(CE_ERR_BACKEND, "Metric calculation failed: alpha_backgrounds: a decode with alpha and an ICC profile is not supported")
+                    job.tests.append(decoded.composited_rgb8_vec(bgs[k]) if bgs else decoded.to_rgb8_vec())
+                    job.test_profiles.append(decoded.icc_profile)
+                jobs.append(job)
+                rows.append((report, [ri for ri, _ in cells]))
         stats = self.pool.run(jobs, self.config.metrics)
+        per_row: dict = {}
         for job, (report, row_indices) in zip(jobs, rows):
             for s, ri in zip(job.scores, row_indices):
                 if s.status != 0:
                     raise _error_obj(s.status, f"{report.name}: status {s.status}")
-                m = MetricResult.from_c(s)
-                row = report.results[ri]
-                row.dssim, row.ssimulacra2, row.butteraugli, row.psnr = m.dssim, m.ssimulacra2, m.butteraugli, m.psnr
-                row.perception = m.perception_level()  # session.rs:407
+                per_row.setdefault((id(report), ri), (report, ri, []))[2].append(MetricResult.from_c(s))
+        for report, ri, per_bg in per_row.values():
+            m = worst_over_backgrounds(per_bg)
+            row = report.results[ri]
+            row.dssim, row.ssimulacra2, row.butteraugli, row.psnr = m.dssim, m.ssimulacra2, m.butteraugli, m.psnr
+            row.perception = m.perception_level()  # session.rs:407
+            if len(per_bg) > 1:
+                report.alpha_scores[ri] = per_bg
         return corpus, stats

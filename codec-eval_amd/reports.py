@@ -246,6 +246,9 @@ class ImageReport:  # report.rs:66-107
     results: List[CodecResult] = field(default_factory=list)
     source_path: Optional[str] = None
     timestamp: _dt.datetime = field(default_factory=_now)
+    # EvalConfig.alpha_backgrounds: row index -> that row's MetricResult over each background, in the config's order, for
+    # the rows that were composited (the row itself carries the worst value per metric).  Not part of the JSON / CSV.
+    alpha_scores: Dict[int, list] = field(default_factory=dict, repr=False, compare=False)
 
     @property
     def uncompressed_size(self) -> int:

@@ -20,10 +20,11 @@ from . import (DEEP_DEPTHS, PIXEL_RGB8, PIXEL_RGB16, PIXEL_RGBA8, PIXEL_RGBA16, 
                MetricConfig, MetricResult, _error_obj, estimate_batch_bytes, CE_ERR_BACKEND)
 from . import RESAMPLE_LANCZOS3
 from . import CHROMA_TRIANGLE, MEM_HOST, YUV_400, YUV_420, YUV_444, YUV_BT601, YUV_FULL, YUV_PLANAR, YUV_SEMIPLANAR, YuvImage, yuv_coefficients
+from . import ALPHA_BLACK_WHITE, MAX_BACKGROUNDS, composite_over, scale_background
 from . import reports as R
 from .viewing import SimulationMode, ViewingCondition
 
-__all__ = ["ImageData", "EncodeRequest", "EvalConfig", "EvalConfigBuilder", "EvalSession"]
+__all__ = ["ImageData", "EncodeRequest", "EvalConfig", "EvalConfigBuilder", "EvalSession", "ALPHA_BLACK_WHITE"]
 
 
 @dataclass
@@ -119,6 +120,22 @@ class ImageData:
             return np.minimum((np.minimum(data, maxv).astype(np.uint64) * 255 + maxv // 2) // maxv, 255).astype(np.uint8)
         return data
 
+    @property
+    def has_alpha(self) -> bool:
+        return self.channels == 4 and self.yuv_image is None
+
+    def composited_rgb8_vec(self, background: Sequence[int]) -> np.ndarray:
+        """to_rgb8_vec of this image seen over the opaque 8-bit colour `background` (EvalConfig.alpha_backgrounds), on the
+        host: composite_over at the image's own depth, then to_8bit's rule.  An image without alpha is to_rgb8_vec."""
+        if not self.has_alpha:
+            return self.to_rgb8_vec()
+        d = self.depth or 8
+        rgb = composite_over(self.data.reshape(-1, 4), scale_background(background, d), d).reshape(-1)
+        if self.depth:
+            maxv = (1 << d) - 1
+            return np.minimum((rgb.astype(np.uint64) * 255 + maxv // 2) // maxv, 255).astype(np.uint8)
+        return rgb
+
     def to_rgb8_srgb(self, cms: Optional[Callable[[bytes, np.ndarray], np.ndarray]] = None) -> np.ndarray:
         """session.rs:143-147 -> transform_to_srgb, metrics/icc.rs:69-113: on the HOST (the session itself applies the
         profile on the device through a colour table).  `cms(profile_bytes, rgb_nx3_u8) -> rgb_nx3_u8` is the colour
@@ -168,6 +185,11 @@ class EvalConfig:  # session.rs:188-279
     # them at (SimulationParams.displayed_size, viewing.py) and scored there; 8-bit decodes only.
     simulate_viewing: Optional[SimulationMode] = None
     resample_filter: int = RESAMPLE_LANCZOS3
+    # Not in the reference, which drops alpha (session.rs:98-117).  None: every score and every upload is what it always was.
+    # A sequence of 8-bit (r, g, b) colours (ALPHA_BLACK_WHITE: black and white): a pair whose source or decode has alpha is
+    # composited over each on the device (Batch.set_*_over) and scored over each; the row carries the
+    # worst value per metric and the report keeps the per-background scores (ImageReport.alpha_scores).
+    alpha_backgrounds: Optional[Sequence[Tuple[int, int, int]]] = None
 
     @staticmethod
     def builder() -> "EvalConfigBuilder":
@@ -177,6 +199,7 @@ class EvalConfig:  # session.rs:188-279
 class EvalConfigBuilder:
     def __init__(self):
         self._report_dir = self._cache_dir = self._viewing = self._metrics = self._levels = self._simulate = None
+        self._alpha = None
 
     def report_dir(self, path):
         self._report_dir = str(path)
@@ -198,6 +221,15 @@ class EvalConfigBuilder:
         self._metrics = metrics
         return self
 
+    def alpha_backgrounds(self, backgrounds: Optional[Sequence[Tuple[int, int, int]]]):
+        """8-bit (r, g, b) colours to composite transparent images over (ALPHA_BLACK_WHITE); None: alpha is dropped"""
+        if backgrounds is not None:
+            backgrounds = tuple(tuple(int(v) for v in bg) for bg in backgrounds)
+            if not 1 <= len(backgrounds) <= MAX_BACKGROUNDS or any(len(bg) != 3 or min(bg) < 0 or max(bg) > 255 for bg in backgrounds):
+                raise ValueError(f"alpha_backgrounds: 1 to {MAX_BACKGROUNDS} colours of three 8-bit values")
+        self._alpha = backgrounds
+        return self
+
     def quality_levels(self, levels: Sequence[float]):
         self._levels = [float(q) for q in levels]
         return self
@@ -211,7 +243,18 @@ class EvalConfigBuilder:
         if self._levels is not None:
             cfg.quality_levels = self._levels
         cfg.simulate_viewing = self._simulate
+        cfg.alpha_backgrounds = self._alpha
         return cfg
+
+
+def worst_over_backgrounds(per_bg: Sequence[MetricResult]) -> MetricResult:
+    """One pair's scores over each background -> the worst value per metric: max DSSIM, max Butteraugli, min SSIMULACRA2,
+    min PSNR.  A single entry is returned as it is."""
+    if len(per_bg) == 1:
+        return per_bg[0]
+    pick = lambda vals, f: None if any(v is None for v in vals) else f(vals)
+    return MetricResult(dssim=pick([m.dssim for m in per_bg], max), ssimulacra2=pick([m.ssimulacra2 for m in per_bg], min),
+                        butteraugli=pick([m.butteraugli for m in per_bg], max), psnr=pick([m.psnr for m in per_bg], min))
 
 
 @dataclass
@@ -322,6 +365,9 @@ class EvalSession:
             fixed = estimate_batch_bytes(sw, sh, 0, 0, cfg)
             per_ref = estimate_batch_bytes(sw, sh, 1, 0, cfg) - fixed + extra
             per_pair = estimate_batch_bytes(sw, sh, 0, 1, cfg) - fixed + extra
+            # with alpha_backgrounds a pair may take one slot per background on either side: budget for that
+            fan = len(self.config.alpha_backgrounds) if self.config.alpha_backgrounds else 1
+            per_ref, per_pair = per_ref * fan, per_pair * fan
             max_pairs = max(1, (budget - fixed - per_ref) // max(per_pair, 1))
             parts: List[list] = [[]]  # each part: [(image, report, cells)]
             used = fixed
@@ -351,26 +397,44 @@ class EvalSession:
             self._score_cells(w, h, sub, cfg, None if depths == (0, 0) else (depths[0], depths[1] or 8))
 
     def _score_cells(self, w: int, h: int, group, cfg: MetricConfig, depths: Optional[Tuple[int, int]]):
-        n_refs = len(group)
-        n_pairs = sum(len(p) for _, _, p in group)
+        # a pair whose source or decode has alpha takes one test slot per background (config.alpha_backgrounds); a source
+        # with alpha takes one reference slot per background, an opaque one a single slot that all of them read
+        bgs = self.config.alpha_backgrounds or ()
+        fan = lambda image, decoded: len(bgs) if bgs and (image.has_alpha or decoded.has_alpha) else 1
+        n_refs = sum(len(bgs) if bgs and image.has_alpha else 1 for image, _, _ in group)
+        n_pairs = sum(fan(image, decoded) for image, _, p in group for _, decoded in p)
+        bg_side = [[scale_background(bg, d or 8) for bg in bgs] for d in (depths or (8, 8))]  # at each side's depth
         batch = Batch(self.ctx, w, h, n_refs, n_pairs, depths=depths)
         try:
             rows = []
-            k = 0
-            for ri, (image, report, pending) in enumerate(group):
-                if image.yuv_image is not None:
-                    batch.set_reference_yuv(ri, image.yuv_image)
+            k = ri = 0
+            for image, report, pending in group:
+                if bgs and image.has_alpha:
+                    batch.set_reference_over(ri, image.data, image.pixel_format, bg_side[0])
+                    ref_of = list(range(ri, ri + len(bgs)))
                 else:
-                    batch.set_reference_fmt(ri, image.data, image.pixel_format)
+                    if image.yuv_image is not None:
+                        batch.set_reference_yuv(ri, image.yuv_image)
+                    else:
+                        batch.set_reference_fmt(ri, image.data, image.pixel_format)
+                    ref_of = [ri] * max(len(bgs), 1)
+                ri = ref_of[-1] + 1
                 for row_index, decoded in pending:
                     if (decoded.width, decoded.height) != (w, h):  # calculate_metrics' length check, ssimulacra2.rs:65-70
                         raise DimensionMismatch(1, f"Dimension mismatch: expected ({w}, {h}), got ({decoded.width}, {decoded.height})")
-                    if decoded.yuv_image is not None:  # a decoder's Y'CbCr planes: upsampled and converted on the device, into the slot
-                        batch.set_test_yuv(k, ri, decoded.yuv_image)
+                    n = fan(image, decoded)
+                    if bgs and decoded.has_alpha:
+                        if self._table_for(decoded) is not None:
+                            raise MetricCalculation(CE_ERR_BACKEND, "Metric calculation failed: alpha_backgrounds: a decode with alpha and an ICC profile is not supported")
+                        batch.set_test_over(k, ref_of, decoded.data, decoded.pixel_format, bg_side[1])
                     else:
-                        batch.set_test_lut(k, ri, decoded.data, decoded.pixel_format, self._table_for(decoded))  # to_rgb8_srgb, session.rs:394
-                    rows.append((report, row_index))
-                    k += 1
+                        for j in range(n):  # an opaque decode against a source with alpha: the same image over every background
+                            if decoded.yuv_image is not None:  # a decoder's Y'CbCr planes: upsampled and converted on the device, into the slot
+                                batch.set_test_yuv(k + j, ref_of[j], decoded.yuv_image)
+                            else:
+                                batch.set_test_lut(k + j, ref_of[j], decoded.data, decoded.pixel_format, self._table_for(decoded))  # to_rgb8_srgb, session.rs:394
+                    rows.append((report, row_index, k, n))
+                    k += n
             shown = self._displayed(w, h)
             if shown != (w, h):
                 dst = Batch(self.ctx, shown[0], shown[1], n_refs, n_pairs)
@@ -383,13 +447,18 @@ class EvalSession:
                 scores = batch.run(n_pairs, cfg)
         finally:
             batch.close()
-        for (report, row_index), s in zip(rows, scores):
-            if s.status != 0:
-                raise _error_obj(s.status, self.ctx._err())
-            m = MetricResult.from_c(s)
+        for report, row_index, first, n in rows:
+            per_bg = []
+            for s in scores[first:first + n]:
+                if s.status != 0:
+                    raise _error_obj(s.status, self.ctx._err())
+                per_bg.append(MetricResult.from_c(s))
+            m = worst_over_backgrounds(per_bg)
             row = report.results[row_index]
             row.dssim, row.ssimulacra2, row.butteraugli, row.psnr = m.dssim, m.ssimulacra2, m.butteraugli, m.psnr
             row.perception = m.perception_level()  # session.rs:407
+            if n > 1:
+                report.alpha_scores[row_index] = per_bg
 
     def evaluate_image(self, name: str, image: ImageData) -> R.ImageReport:  # session.rs:368-434
         # the source image enters as to_rgb8_vec() (session.rs:373): its own profile, if any, is NOT applied

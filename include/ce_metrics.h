@@ -541,6 +541,43 @@ int ce_yuv_to_rgb8(ce_ctx *ctx, const ce_yuv_image *image, uint32_t width, uint3
 int ce_yuv_to_rgb16(ce_ctx *ctx, const ce_yuv_image *image, uint32_t width, uint32_t height, uint32_t depth_out, uint16_t *out,
                     size_t out_len);
 
+/* ---- alpha: a transparent image composited over solid backgrounds on the device -----------------
+ * CE_PIXEL_RGBA8 / CE_PIXEL_RGBA16 above drop alpha (ImageData::to_rgb8_vec, src/eval/session.rs:98-117), so the colour an
+ * encoder left under alpha = 0 is scored although nobody sees it, and damage to the alpha plane is not scored although it
+ * shows over every background but one.  These calls composite instead: source-over of STRAIGHT (non-premultiplied) alpha
+ * onto an opaque solid colour, on the ENCODED sample values (what a browser's compositor does with an sRGB page), in
+ * unsigned 32-bit integers.  With m = 2^d - 1 (255 for 8-bit samples), per channel,
+ *     out = (c * a + bg * (m - a) + (m >> 1)) / m        (integer division; c and a clamped to m first)
+ * c * a + bg * (m - a) <= m * m, so with the rounding term the sum stays below 2^32 at every depth; the division is exact.
+ * For m = 255 this is Pillow's Image.alpha_composite over an opaque background on all 2^24 (c, a, bg) triples.  a = m
+ * gives c, a = 0 gives bg, and the result is monotone in c.
+ * One upload of the image fills n_bg consecutive slots, slot k over backgrounds[k] (1 <= n_bg <= CE_MAX_BACKGROUNDS): the
+ * pixel is read once on the device.  format: CE_PIXEL_RGBA8 on an RGB8 batch or on a side of depth 8 of a deep batch,
+ * CE_PIXEL_RGBA16 on a deep batch (samples of that side's depth d).  backgrounds: [n_bg][3] samples at the destination
+ * side's depth (an RGB8 batch: <= 255).
+ * Not part of this: premultiplied alpha, linear-light blending (the convention of libjxl's command-line tools), patterned
+ * (checkerboard) backgrounds, dssim-core's own alpha handling, CE_PIXEL_RGBA16_10BIT (refused; a deep batch is the route
+ * for 10-bit alpha), device-resident sources, ce_ref_* handles, ce_eval_batch, ce_eval_batch_lut and ce_batch_resample*. */
+#define CE_MAX_BACKGROUNDS 8
+/* Reference slots first_ref .. first_ref + n_bg - 1 / test slots first_pair .. first_pair + n_bg - 1, pair first_pair + k
+ * bound to reference ref_indices[k]; on the same stream and with the same ordering as ce_batch_set_*_fmt, the pixels
+ * consumed on return.  CE_ERR_INVALID_ARG, with the reason in ce_last_error and the batch still usable, for a null handle
+ * or pointer, a format without alpha or a *_10BIT format, CE_PIXEL_RGBA16 on an RGB8 batch, CE_PIXEL_RGBA8 on a deep side
+ * whose depth is not 8, a wrong len, n_bg = 0 or n_bg > CE_MAX_BACKGROUNDS, a background sample above m, a slot range or a
+ * ref_indices entry past the batch. */
+int ce_batch_set_reference_over(ce_batch *b, uint32_t first_ref, const void *pixels, size_t len, int format, uint32_t n_bg,
+                                const uint16_t *backgrounds);
+int ce_batch_set_test_over(ce_batch *b, uint32_t first_pair, const uint32_t *ref_indices, const void *pixels, size_t len,
+                           int format, uint32_t n_bg, const uint16_t *backgrounds);
+/* One image over one colour to host memory: w x h RGBA8 (len = w * h * 4 bytes) -> packed RGB8 (out_len = w * h * 3
+ * bytes); w x h u16 RGBA of `depth` bits in {8, 10, 12, 16} (len = w * h * 4 samples) -> packed u16 RGB (out_len =
+ * w * h * 3 samples).  CE_ERR_INVALID_ARG for a null handle or pointer, a wrong len or out_len, a background sample above
+ * m, or a depth outside {8, 10, 12, 16}. */
+int ce_composite_rgba8(ce_ctx *ctx, const uint8_t *rgba, size_t len, uint32_t w, uint32_t h, const uint8_t bg[3], uint8_t *out,
+                       size_t out_len);
+int ce_composite_rgba16(ce_ctx *ctx, const uint16_t *rgba, size_t len, uint32_t w, uint32_t h, uint32_t depth, const uint16_t bg[3],
+                        uint16_t *out, size_t out_len);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------ */
 /* Bracket every kernel launch with a HIP event pair, recorded on the stream the kernel is launched on,
  * and accumulate per-kernel time.  on = 0: off (default).  on = 2: events only; the batch keeps its
