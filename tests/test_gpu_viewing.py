@@ -333,3 +333,60 @@ def test_every_refusal_leaves_both_batches_usable(gpu_ctx, ce, workloads):
         for b in (src, dst, deep, foreign):
             b.close()
         other.close()
+
+
+# ---- the smallest shapes that reach the kernels' edges (the host-compiled run of the same text under sanitizers is
+# tests/test_resample_kernel_host_cpu.py; these are exact integers, so everything is array_equal) -------------------------
+
+@pytest.mark.parametrize("ow,oh", [(341, 3), (342, 3)])
+def test_slots_at_every_dword_phase(gpu_ctx, ce, ow, oh):
+    """A tile is 1024 row bytes counted from the aligned dword that holds the row's first byte.  341 x 3 is 1023 bytes a row
+    and 3069 a slot, so four consecutive slots start at all four phases (342 x 3: 1026 and 3078, phases 0 and 2) and the rows
+    within a slot move on by 3 (2).  From a two-pass source and a horizontal-only one, with sentinel slots on either side."""
+    slot = ow * oh * 3
+    assert {(k * slot) % 4 for k in range(1, 5)} == ({0, 1, 2, 3} if ow == 341 else {0, 2})
+    sentinel = np.full(slot, 0xA5, np.uint8)
+    for w, h in ((682, 6), (171, 3)):
+        imgs = [R.content(w, h, "noise", seed=60 + i) for i in range(4)]
+        src, dst = ce.Batch(gpu_ctx, w, h, 1, 5), ce.Batch(gpu_ctx, ow, oh, 1, 6)
+        try:
+            for i, im in enumerate(imgs):
+                src.set_test(1 + i, 0, im)
+            for filt in R.FILTERS:
+                for i in range(6):
+                    dst.set_test(i, 0, sentinel)
+                src.resample_into(dst, 1, 4, tests=True, filter=filt)
+                got = read_slab(ce, gpu_ctx, dst.test_slab, slot * 6).reshape(6, oh, ow, 3)
+                for i, im in enumerate(imgs):
+                    assert np.array_equal(got[1 + i], R.resample(im, ow, oh, filt)), (w, h, ow, oh, filt, "slot", 1 + i)
+                for i in (0, 5):
+                    assert np.array_equal(got[i].reshape(-1), sentinel), (w, h, ow, oh, filt, "sentinel", i)
+        finally:
+            src.close(), dst.close()
+
+
+@pytest.mark.parametrize("w,h,oh", [(1840, 4, 4), (1841, 4, 4), (1841, 4, 2)])
+def test_route_boundary_of_the_horizontal_taps(gpu_ctx, ce, w, h, oh):
+    """Lanczos3 to 345 pixels: from 1840 a pixel has 33 taps and a tile's tables are 48 020 bytes, the last that are staged in
+    LDS; from 1841 it has 35 and they are read from the global table.  345 pixels are 1035 row bytes: two tiles, three
+    images."""
+    ow, n = 345, 3
+    imgs = [R.content(w, h, "noise", seed=70 + i) for i in range(n)]
+    src, dst = ce.Batch(gpu_ctx, w, h, 1, n), ce.Batch(gpu_ctx, ow, oh, 1, n)
+    try:
+        for i, im in enumerate(imgs):
+            src.set_test(i, 0, im)
+        src.resample_into(dst, 0, n, tests=True)
+        got = read_slab(ce, gpu_ctx, dst.test_slab, ow * oh * 3 * n).reshape(n, oh, ow, 3)
+        for i, im in enumerate(imgs):
+            assert np.array_equal(got[i], R.resample(im, ow, oh, R.LANCZOS3)), (w, h, ow, oh, i)
+    finally:
+        src.close(), dst.close()
+
+
+@pytest.mark.parametrize("h", [1, 5])
+def test_leaf_widths_within_a_dword_of_a_tile_boundary(gpu_ctx, ce, h):
+    for ow in (340, 341, 342, 343, 682, 683, 684):  # 1020 .. 1029 and 2046 .. 2052 row bytes
+        for w in (2 * ow, (ow + 1) // 2):
+            img = R.content(w, h, "noise", seed=80)
+            assert np.array_equal(gpu_ctx.resample_rgb8(img, w, h, ow, h), R.resample(img, ow, h, R.LANCZOS3)), (w, h, ow)
