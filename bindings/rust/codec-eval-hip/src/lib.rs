@@ -128,6 +128,20 @@ impl HipMetrics {
         Ok(s.into())
     }
 
+    /// One pair of packed f32 RGB in linear light with BT.709 / sRGB primaries (`ce_eval_pair_linear`): 1.0 is the white an
+    /// 8-bit 255 maps to, values below 0 and above 1 are scored (HDR highlights, colours outside the sRGB gamut).  PSNR is not
+    /// reported.  `intensity_target` is Butteraugli's: nits at 1.0.
+    pub fn calculate_metrics_linear(&mut self, reference: &[f32], test: &[f32], width: u32, height: u32, m: Metrics,
+                                    intensity_target: f32) -> Result<Scores, HipError> {
+        let mut s = sys::ce_scores::default();
+        let rc = unsafe {
+            sys::ce_eval_pair_linear(self.ctx, reference.as_ptr(), reference.len() * 4, test.as_ptr(), test.len() * 4, width, height,
+                                     m.mask(), m.flags(), intensity_target, &mut s)
+        };
+        self.check(rc, width, height, test.len())?;  // three samples per pixel, as the bytes of an RGB8 image
+        Ok(s.into())
+    }
+
     /// The whole `(codec, quality)` grid of `evaluate_image` (session.rs:375-376) in one call: decode every cell
     /// first, then pass `(reference, decoded, width, height)` per cell.  Cells that share a reference slice share
     /// one device slot.  Per-cell failures come back as `Err` in their position.

@@ -47,6 +47,20 @@ pub const CE_PIXEL_RGBA16_10BIT: c_int = 3;
 /// deep batches only (`ce_batch_create_deep`): u16 samples at the side's own depth
 pub const CE_PIXEL_RGB16: c_int = 4;
 pub const CE_PIXEL_RGBA16: c_int = 5;
+/// linear batches only (`ce_batch_create_linear`): packed f32 RGB, linear light with BT.709 / sRGB primaries
+pub const CE_PIXEL_RGB_F32: c_int = 7;
+/// `CE_LINEAR_MAX`: the clamp of a linear image's samples on ingest
+pub const CE_LINEAR_MAX: c_float = 1024.0;
+
+/// `ce_colour` (16 bytes): how integer RGB code values are to be read (ITU-T H.273 code points).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ce_colour {
+    pub primaries: c_int,
+    pub transfer: c_int,
+    pub depth: u32,
+    pub white_nits: c_float,
+}
 
 /// `ce_scores` (40 bytes): a score is meaningful iff its bit is set in `valid`.
 #[repr(C)]
@@ -198,6 +212,20 @@ extern "C" {
     pub fn ce_eval_pair_deep(ctx: *mut ce_ctx, reference: *const u16, reference_len: usize, ref_depth: u32, test: *const u16,
                              test_len: usize, test_depth: u32, width: u32, height: u32, metric_mask: u32, flags: u32,
                              intensity_target: c_float, out: *mut ce_scores) -> c_int;
+    pub fn ce_batch_create_linear(ctx: *mut ce_ctx, width: u32, height: u32, max_refs: u32, max_pairs: u32, out: *mut *mut ce_batch) -> c_int;
+    pub fn ce_estimate_batch_bytes_linear(width: u32, height: u32, n_refs: u32, n_pairs: u32, metric_mask: u32) -> usize;
+    pub fn ce_eval_pair_linear(ctx: *mut ce_ctx, reference: *const c_float, reference_len: usize, test: *const c_float, test_len: usize,
+                               width: u32, height: u32, metric_mask: u32, flags: u32, intensity_target: c_float,
+                               out: *mut ce_scores) -> c_int;
+    pub fn ce_srgb_table(depth: u32, rule: c_int, out: *mut c_float, n: usize) -> c_int;
+    pub fn ce_batch_set_reference_cicp(b: *mut ce_batch, ref_index: u32, pixels: *const c_void, len: usize, format: c_int,
+                                       c: *const ce_colour) -> c_int;
+    pub fn ce_batch_set_test_cicp(b: *mut ce_batch, pair_index: u32, ref_index: u32, pixels: *const c_void, len: usize, format: c_int,
+                                  c: *const ce_colour) -> c_int;
+    pub fn ce_cicp_to_linear(ctx: *mut ce_ctx, pixels: *const c_void, len: usize, format: c_int, c: *const ce_colour, w: u32, h: u32,
+                             out: *mut c_float, out_len: usize) -> c_int;
+    pub fn ce_transfer_table(transfer: c_int, depth: u32, white_nits: c_float, out: *mut c_float, n: usize) -> c_int;
+    pub fn ce_colour_matrix(primaries: c_int, out: *mut c_float) -> c_int;
     pub fn ce_batch_set_reference(b: *mut ce_batch, ref_index: u32, rgb: *const u8, len: usize) -> c_int;
     pub fn ce_batch_set_test(b: *mut ce_batch, pair_index: u32, ref_index: u32, rgb: *const u8, len: usize) -> c_int;
     pub fn ce_batch_set_reference_fmt(b: *mut ce_batch, ref_index: u32, pixels: *const c_void, len: usize, format: c_int) -> c_int;

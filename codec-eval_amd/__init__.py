@@ -36,7 +36,12 @@ FLAG_BUTTERAUGLI_DIFFMAP = 1 << 1
 FLAG_SSIMULACRA2_MAPS = 1 << 2
 PIXEL_RGB8, PIXEL_RGBA8, PIXEL_RGB16_10BIT, PIXEL_RGBA16_10BIT = 0, 1, 2, 3
 PIXEL_RGB16, PIXEL_RGBA16 = 4, 5  # deep batches only (Context.batch_deep): u16 samples at the side's own depth
+PIXEL_RGB_F32 = 7  # linear batches only (Context.batch_linear): packed float RGB, linear light with sRGB primaries
+LINEAR_MAX = 1024.0  # CE_LINEAR_MAX: the clamp of a linear image's samples on ingest
 DEEP_DEPTHS = (8, 10, 12, 16)
+# ITU-T H.273 code points the CICP ingest takes (include/ce_metrics.h)
+PRIMARIES_BT709, PRIMARIES_BT2020, PRIMARIES_P3_D65 = 1, 9, 12
+TRANSFER_SRGB, TRANSFER_LINEAR, TRANSFER_PQ = 13, 8, 16
 BATCH_REFERENCES, BATCH_TESTS = 0, 1  # enum ce_batch_images
 DEFAULT_INTENSITY_TARGET = 80.0
 DSSIM_MAX_LEVELS = 5  # CE_DSSIM_MAX_LEVELS
@@ -120,6 +125,10 @@ class CeYuvImage(C.Structure):
     ]
 
 
+class CeColour(C.Structure):
+    _fields_ = [("primaries", C.c_int), ("transfer", C.c_int), ("depth", C.c_uint32), ("white_nits", C.c_float)]
+
+
 class CodecEvalError(RuntimeError):
     """Mirrors codec_eval::Error for this path (src/error.rs:31-49)."""
 
@@ -190,6 +199,15 @@ _PROTOTYPES = [
     ("ce_batch_create_deep", _i, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, C.POINTER(_vp)]),
     ("ce_estimate_batch_bytes_deep", _sz, [_u32, _u32, _u32, _u32, _u32, _u32, _u32]),
     ("ce_eval_pair_deep", _i, [_vp, _vp, _sz, _u32, _vp, _sz, _u32, _u32, _u32, _u32, _u32, _f32, C.POINTER(CeScores)]),
+    ("ce_batch_create_linear", _i, [_vp, _u32, _u32, _u32, _u32, C.POINTER(_vp)]),
+    ("ce_estimate_batch_bytes_linear", _sz, [_u32, _u32, _u32, _u32, _u32]),
+    ("ce_eval_pair_linear", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, _f32, C.POINTER(CeScores)]),
+    ("ce_srgb_table", _i, [_u32, _i, _vp, _sz]),
+    ("ce_batch_set_reference_cicp", _i, [_vp, _u32, _vp, _sz, _i, C.POINTER(CeColour)]),
+    ("ce_batch_set_test_cicp", _i, [_vp, _u32, _u32, _vp, _sz, _i, C.POINTER(CeColour)]),
+    ("ce_cicp_to_linear", _i, [_vp, _vp, _sz, _i, C.POINTER(CeColour), _u32, _u32, _vp, _sz]),
+    ("ce_transfer_table", _i, [_i, _u32, _f32, _vp, _sz]),
+    ("ce_colour_matrix", _i, [_i, _vp]),
     ("ce_batch_set_reference", _i, [_vp, _u32, _u8p, _sz]),
     ("ce_batch_set_test", _i, [_vp, _u32, _u32, _u8p, _sz]),
     ("ce_batch_set_reference_fmt", _i, [_vp, _u32, _vp, _sz, _i]),
@@ -276,6 +294,81 @@ def estimate_batch_bytes_deep(width: int, height: int, n_refs: int, n_pairs: int
                               test_depth: int) -> int:
     """estimate_batch_bytes for a deep batch (Context.batch_deep) of these depths."""
     return int(lib().ce_estimate_batch_bytes_deep(width, height, n_refs, n_pairs, config.mask, ref_depth, test_depth))
+
+
+def estimate_batch_bytes_linear(width: int, height: int, n_refs: int, n_pairs: int, config: "MetricConfig") -> int:
+    """estimate_batch_bytes for a linear batch (Context.batch_linear)."""
+    return int(lib().ce_estimate_batch_bytes_linear(width, height, n_refs, n_pairs, config.mask))
+
+
+def _host_check(rc: int):
+    if rc != CE_OK:
+        _raise(rc, (lib().ce_last_error(None) or b"").decode())
+
+
+def srgb_table(depth: int, rule: int = 0) -> np.ndarray:
+    """The library's own sRGB -> linear table of `depth` bits (ce_srgb_table): rule 0 the f64 curve rounded once to f32
+    (SSIMULACRA2, Butteraugli), rule 1 f32 powf (DSSIM) - exactly the floats the RGB8 and deep batches read."""
+    out = np.empty(1 << depth if 0 < depth <= 16 else 1, np.float32)
+    _host_check(lib().ce_srgb_table(depth, rule, out.ctypes.data, out.size))
+    return out
+
+
+def transfer_table(transfer: int, depth: int, white_nits: float = 203.0) -> np.ndarray:
+    """The CICP ingest's table of code value -> linear light (ce_transfer_table); white_nits is read for PQ only."""
+    out = np.empty(1 << depth if 0 < depth <= 16 else 1, np.float32)
+    _host_check(lib().ce_transfer_table(transfer, depth, white_nits, out.ctypes.data, out.size))
+    return out
+
+
+def colour_matrix(primaries: int) -> np.ndarray:
+    """The CICP ingest's 3 x 3 matrix from `primaries` to BT.709 / sRGB primaries (ce_colour_matrix), float32."""
+    out = np.empty((3, 3), np.float32)
+    _host_check(lib().ce_colour_matrix(primaries, out.ctypes.data))
+    return out
+
+
+@dataclass(frozen=True)
+class ColourDescription:
+    """How integer RGB code values are to be read (ce_colour): H.273 colour primaries (1 BT.709, 9 BT.2020, 12 Display P3)
+    and transfer characteristics (13 sRGB, 8 linear, 16 PQ), bits per sample, and for PQ the luminance that becomes 1.0."""
+    primaries: int = PRIMARIES_BT709
+    transfer: int = TRANSFER_SRGB
+    depth: int = 8
+    white_nits: float = 203.0
+
+    def with_depth(self, depth: int) -> "ColourDescription":
+        return ColourDescription(self.primaries, self.transfer, depth, self.white_nits)
+
+    @property
+    def is_srgb(self) -> bool:
+        return self.primaries == PRIMARIES_BT709 and self.transfer == TRANSFER_SRGB
+
+    def _c(self) -> CeColour:
+        return CeColour(self.primaries, self.transfer, self.depth, self.white_nits)
+
+
+ColourDescription.SRGB = ColourDescription(PRIMARIES_BT709, TRANSFER_SRGB, 8)
+ColourDescription.DISPLAY_P3 = ColourDescription(PRIMARIES_P3_D65, TRANSFER_SRGB, 8)
+ColourDescription.BT2020_PQ = ColourDescription(PRIMARIES_BT2020, TRANSFER_PQ, 10, 203.0)
+
+
+def _cicp_fmt(a: np.ndarray) -> int:
+    """The CE_PIXEL_* format of an [h, w, 3 or 4] (or flat RGB) uint8 / uint16 array."""
+    alpha = a.ndim == 3 and a.shape[-1] == 4
+    if a.dtype == np.uint8:
+        return PIXEL_RGBA8 if alpha else PIXEL_RGB8
+    if a.dtype == np.uint16:
+        return PIXEL_RGBA16 if alpha else PIXEL_RGB16
+    raise TypeError("CICP ingest takes uint8 or uint16 samples")
+
+
+def _buf_f32(a) -> np.ndarray:
+    """Borrowed view as a flat contiguous float32 array (the packed samples of a linear image)."""
+    arr = np.asarray(a)
+    if arr.dtype != np.float32:
+        raise TypeError("linear pixel buffers must be float32")
+    return np.ascontiguousarray(arr).reshape(-1)
 
 
 def _buf16(a) -> np.ndarray:
@@ -859,6 +952,31 @@ class Context:
                                             height, config.mask, config.flags, intensity_target, C.byref(s)))
         return MetricResult.from_c(s)
 
+    def eval_pair_linear(self, reference, test, width: int, height: int, config: MetricConfig,
+                         intensity_target: float = DEFAULT_INTENSITY_TARGET) -> MetricResult:
+        """calculate_metrics over packed float32 RGB, linear light with sRGB primaries, 1.0 = the white of an 8-bit 255
+        (ce_eval_pair_linear).  PSNR is not reported."""
+        r, t = _buf_f32(reference), _buf_f32(test)
+        s = CeScores()
+        self._check(lib().ce_eval_pair_linear(self._h, r.ctypes.data, r.nbytes, t.ctypes.data, t.nbytes, width, height, config.mask,
+                                              config.flags, intensity_target, C.byref(s)))
+        return MetricResult.from_c(s)
+
+    def batch_linear(self, width: int, height: int, max_refs: int, max_pairs: int) -> "Batch":
+        """A Batch whose slabs hold packed float32 RGB in linear light (ce_batch_create_linear): loaded with float32 arrays
+        through set_reference / set_test, or with tagged code values through set_reference_cicp / set_test_cicp."""
+        return Batch(self, width, height, max_refs, max_pairs, linear=True)
+
+    def cicp_to_linear(self, pixels, width: int, height: int, colour: "ColourDescription") -> np.ndarray:
+        """One image of uint8 / uint16 RGB(A) code values read by `colour` -> [h, w, 3] float32 linear light with sRGB
+        primaries, on the device (ce_cicp_to_linear)."""
+        a = np.ascontiguousarray(pixels)
+        out = np.empty((height, width, 3), np.float32)
+        c = colour._c()
+        self._check(lib().ce_cicp_to_linear(self._h, a.ctypes.data, a.nbytes, _cicp_fmt(a), C.byref(c), width, height, out.ctypes.data,
+                                            out.size))
+        return out
+
     def batch_deep(self, width: int, height: int, max_refs: int, max_pairs: int, ref_depth: int, test_depth: int) -> "Batch":
         """A Batch whose slabs hold uint16 samples of the given depths (8, 10, 12 or 16 bits per side)."""
         return Batch(self, width, height, max_refs, max_pairs, depths=(ref_depth, test_depth))
@@ -957,15 +1075,21 @@ class Batch:
     """HBM-resident grid of (reference, test) pairs of one shape (ce_batch_*)."""
 
     def __init__(self, ctx: Context, width: int, height: int, max_refs: int, max_pairs: int,
-                 depths: Optional[Tuple[int, int]] = None):
+                 depths: Optional[Tuple[int, int]] = None, linear: bool = False):
         """depths=(reference depth, test depth): a deep batch (ce_batch_create_deep) - set_reference / set_test then also
-        take uint16 arrays ([h, w, 3] or flat RGB, [h, w, 4] RGBA) of that side's depth."""
+        take uint16 arrays ([h, w, 3] or flat RGB, [h, w, 4] RGBA) of that side's depth.  linear=True: a linear batch
+        (ce_batch_create_linear) - set_reference / set_test take float32 arrays, set_*_cicp tagged code values."""
+        if linear and depths is not None:
+            raise ValueError("a batch is deep or linear, not both")
+        self.linear = linear
         self.ctx, self.width, self.height = ctx, width, height
         self.max_refs, self.max_pairs = max_refs, max_pairs
         self.depths = tuple(depths) if depths is not None else None
         self._pair_ref = [0] * max_pairs  # the pair -> reference bindings, as the library holds them
         self._h = C.c_void_p()
-        if self.depths is None:
+        if linear:
+            ctx._check(lib().ce_batch_create_linear(ctx._h, width, height, max_refs, max_pairs, C.byref(self._h)))
+        elif self.depths is None:
             ctx._check(lib().ce_batch_create(ctx._h, width, height, max_refs, max_pairs, C.byref(self._h)))
         else:
             ctx._check(lib().ce_batch_create_deep(ctx._h, width, height, max_refs, max_pairs, self.depths[0], self.depths[1],
@@ -987,12 +1111,16 @@ class Batch:
             pass
 
     def set_reference(self, ref_index: int, rgb):
+        if np.asarray(rgb).dtype == np.float32:
+            return self.set_reference_fmt(ref_index, rgb, PIXEL_RGB_F32)
         if np.asarray(rgb).dtype == np.uint16:
             return self.set_reference_fmt(ref_index, rgb, self._deep_fmt(np.asarray(rgb)))
         r = _buf(rgb)
         self.ctx._check(lib().ce_batch_set_reference(self._h, ref_index, r.ctypes.data, r.size))
 
     def set_test(self, pair_index: int, ref_index: int, rgb):
+        if np.asarray(rgb).dtype == np.float32:
+            return self.set_test_fmt(pair_index, ref_index, rgb, PIXEL_RGB_F32)
         if np.asarray(rgb).dtype == np.uint16:
             return self.set_test_fmt(pair_index, ref_index, rgb, self._deep_fmt(np.asarray(rgb)))
         t = _buf(rgb)
@@ -1007,6 +1135,16 @@ class Batch:
     def set_test_fmt(self, pair_index: int, ref_index: int, pixels, fmt: int):
         a = np.ascontiguousarray(pixels)
         self.ctx._check(lib().ce_batch_set_test_fmt(self._h, pair_index, ref_index, a.ctypes.data, a.nbytes, fmt))
+        self._pair_ref[pair_index] = ref_index
+
+    # tagged code values (H.273 primaries / transfer) -> linear light on the device, into a slot of a linear batch
+    def set_reference_cicp(self, ref_index: int, pixels, colour: "ColourDescription"):
+        a, c = np.ascontiguousarray(pixels), colour._c()
+        self.ctx._check(lib().ce_batch_set_reference_cicp(self._h, ref_index, a.ctypes.data, a.nbytes, _cicp_fmt(a), C.byref(c)))
+
+    def set_test_cicp(self, pair_index: int, ref_index: int, pixels, colour: "ColourDescription"):
+        a, c = np.ascontiguousarray(pixels), colour._c()
+        self.ctx._check(lib().ce_batch_set_test_cicp(self._h, pair_index, ref_index, a.ctypes.data, a.nbytes, _cicp_fmt(a), C.byref(c)))
         self._pair_ref[pair_index] = ref_index
 
     # a decoder's Y'CbCr planes, host or device: upsampled and converted on the device, straight into the slot

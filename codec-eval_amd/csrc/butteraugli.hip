@@ -267,7 +267,13 @@ constexpr int FT = 32, FR = FT + 4;
 // source instead of in a pass of its own; gi = the full-resolution geometry.
 // T: the sample type - uint8_t (the 256-entry table in LDS, packed loads on interior tiles) or the uint16_t of a deep batch
 // (2^depth entries per side in global memory, lut for the references and lut_test for the distorted images; every tile
-// takes the per-sample loads of the border path)
+// takes the per-sample loads of the border path) or the float of a linear batch (the sample is the
+// linear value: no table, the same per-sample path)
+template <typename T>
+__device__ __forceinline__ float ba_linear_of(const float *tab, T v) { return tab[v]; }
+template <>
+__device__ __forceinline__ float ba_linear_of<float>(const float *, float v) { return v; }
+
 template <bool HALF, typename T>
 __global__ __launch_bounds__(TPB) void k_ba_front(const uint8_t *__restrict__ refs, const uint8_t *__restrict__ tests,
                                                   const float *__restrict__ lut, const float *__restrict__ lut_test, geom gi,
@@ -332,9 +338,9 @@ __global__ __launch_bounds__(TPB) void k_ba_front(const uint8_t *__restrict__ re
         if (X >= 0 && X < w && Y >= 0 && Y < h) {
             if (!HALF) {
                 const T *px = srcT + ((size_t)Y * w + X) * 3;
-                L[0][i] = tab[px[0]];
-                L[1][i] = tab[px[1]];
-                L[2][i] = tab[px[2]];
+                L[0][i] = ba_linear_of<T>(tab, px[0]);
+                L[1][i] = ba_linear_of<T>(tab, px[1]);
+                L[2][i] = ba_linear_of<T>(tab, px[2]);
             } else {
                 float acc[3] = {0.0f, 0.0f, 0.0f};
 #pragma unroll
@@ -345,7 +351,7 @@ __global__ __launch_bounds__(TPB) void k_ba_front(const uint8_t *__restrict__ re
                         if (ix < W8 && iy < H8) {
                             const T *px = srcT + ((size_t)iy * W8 + ix) * 3;
 #pragma unroll
-                            for (int c = 0; c < 3; c++) acc[c] += 0.25f * tab[px[c]];
+                            for (int c = 0; c < 3; c++) acc[c] += 0.25f * ba_linear_of<T>(tab, px[c]);
                         }
                     }
 #pragma unroll
@@ -1360,7 +1366,15 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
         const dim3 ft((d.w + FT - 1) / FT, (d.h + FT - 1) / FT, nz);
         const auto &pd = b->ba[0];
         const geom gfull{pd.w, pd.h, pd.pitch, pd.plane};
-        if (b->depth[0]) {  // a deep batch: u16 samples, one table per side (rule 0, the f64 curve)
+        if (b->linear) {  // a linear batch: f32 samples, no table
+            const float *none = nullptr;
+            if (l == 0)
+                CE_LAUNCH_ON(ctx, st, "ba_front_lin", (k_ba_front<false, float>), ft, dim3(TPB), 0, d_refs, b->d_tests, none, none, g, sC, g,
+                             w0, w1, w2, intensity_target, b->img_bytes, n_refs_used, mr, z0);
+            else
+                CE_LAUNCH_ON(ctx, st, "ba_front_half_lin", (k_ba_front<true, float>), ft, dim3(TPB), 0, d_refs, b->d_tests, none, none, gfull,
+                             sC, g, w0, w1, w2, intensity_target, b->img_bytes, n_refs_used, mr, z0);
+        } else if (b->depth[0]) {  // a deep batch: u16 samples, one table per side (rule 0, the f64 curve)
             const float *lr = b->deep_lut[0][0], *lt = b->deep_lut[0][1];
             if (l == 0)
                 CE_LAUNCH_ON(ctx, st, "ba_front_u16", (k_ba_front<false, uint16_t>), ft, dim3(TPB), 0, d_refs, b->d_tests, lr, lt, g, sC, g,

@@ -395,8 +395,12 @@ void ce_ctx_destroy(ce_ctx *ctx)
     ctx->leaf_map = nullptr;
     ce_batch_destroy(ctx->leaf_deep);
     ctx->leaf_deep = nullptr;
+    ce_batch_destroy(ctx->leaf_linear);
+    ctx->leaf_linear = nullptr;
     for (auto &kv : ctx->deep_tables) hipFree(kv.second);
     ctx->deep_tables.clear();
+    for (auto &kv : ctx->cicp_tables) hipFree(kv.second);
+    ctx->cicp_tables.clear();
     if (ctx->up2_stream) hipStreamSynchronize(ctx->up2_stream), hipStreamDestroy(ctx->up2_stream), hipEventDestroy(ctx->ev_up2);
     for (auto &st : ctx->aux_stream)  // after the last batch that may still drain them
         if (st) hipStreamSynchronize(st), hipStreamDestroy(st), st = nullptr;
@@ -445,8 +449,9 @@ const char *ce_last_error(const ce_ctx *ctx) { return ctx ? ctx->err.c_str() : g
 // ---- resident batch ------------------------------------------------------------------------
 
 // ref_depth = test_depth = 0: an RGB8 batch; otherwise a deep one (checked by the caller)
+// linear: packed f32 RGB slabs (ce_batch_create_linear; depths 0 / 0)
 static int batch_create(ce_ctx *ctx, uint32_t width, uint32_t height, uint32_t max_refs, uint32_t max_pairs, uint32_t ref_depth,
-                        uint32_t test_depth, ce_batch **out)
+                        uint32_t test_depth, ce_batch **out, bool linear = false)
 {
     if (!ctx || !out || width == 0 || height == 0 || max_refs == 0 || max_pairs == 0) return CE_ERR_INVALID_ARG;
     *out = nullptr;
@@ -463,7 +468,8 @@ static int batch_create(ce_ctx *ctx, uint32_t width, uint32_t height, uint32_t m
     b->h = height;
     b->max_refs = max_refs;
     b->max_pairs = max_pairs;
-    b->img_bytes = (size_t)width * height * (ref_depth ? 6 : 3);
+    b->img_bytes = (size_t)width * height * (linear ? 12 : ref_depth ? 6 : 3);
+    b->linear = linear;
     b->depth[0] = ref_depth, b->depth[1] = test_depth;
     std::memcpy(b->deep_lut, deep_lut, sizeof(deep_lut));
     b->h_pair_ref.assign(max_pairs, 0);
@@ -514,6 +520,11 @@ int ce_batch_create_deep(ce_ctx *ctx, uint32_t width, uint32_t height, uint32_t 
         return fail(ctx, CE_ERR_INVALID_ARG, "a deep batch's depths must be 8, 10, 12 or 16 bits, got " + std::to_string(ref_depth) +
                                                  " / " + std::to_string(test_depth));
     return batch_create(ctx, width, height, max_refs, max_pairs, ref_depth, test_depth, out);
+}
+
+int ce_batch_create_linear(ce_ctx *ctx, uint32_t width, uint32_t height, uint32_t max_refs, uint32_t max_pairs, ce_batch **out)
+{
+    return batch_create(ctx, width, height, max_refs, max_pairs, 0, 0, out, true);
 }
 
 void ce_batch_destroy(ce_batch *b)
@@ -730,14 +741,36 @@ static int upload_many(ce_batch *b, const std::vector<upload_job> &jobs)
     return CE_OK;
 }
 
+static const char *const kLinearWants =
+    "a linear batch takes CE_PIXEL_RGB_F32 through ce_batch_set_*_fmt and tagged code values through ce_batch_set_*_cicp";
+
 int ce_batch_set_reference(ce_batch *b, uint32_t ref_index, const uint8_t *rgb, size_t len)
 {
     if (!b || !rgb) return CE_ERR_INVALID_ARG;
     if (ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "ref_index out of range");
     if (b->depth[0]) return ce_batch_set_reference_fmt(b, ref_index, rgb, len, CE_PIXEL_RGB8);  // a deep batch: widened on the device
+    if (b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kLinearWants);
     if (len != b->img_bytes) return bad_length(b->ctx, b->img_bytes, len);
     invalidate_reference_state(b);  // cached reference-side planes are stale
     return upload(b, b->d_refs + (size_t)ref_index * b->img_bytes, rgb);
+}
+
+// `len` bytes of a decoder's image -> wide staging pair k -> its device half, on the batch's upload stream (the caller
+// launches the conversion behind it, records ev_wide[k] and marks the pair busy)
+static int wide_stage(ce_batch *b, int k, const void *pixels, size_t len)
+{
+    ce_ctx *ctx = b->ctx;
+    const size_t cap = (size_t)b->w * b->h * (b->linear ? 12 : 8);
+    if (!b->h_wide[k]) {
+        CE_HIP(ctx, hipHostMalloc((void **)&b->h_wide[k], cap, hipHostMallocDefault));
+        CE_HIP(ctx, hipMalloc((void **)&b->d_wide[k], cap));
+        CE_HIP(ctx, hipEventCreateWithFlags(&b->ev_wide[k], hipEventDisableTiming));
+    }
+    if (int rc = order_write(b, false)) return rc;
+    if (b->wide_busy[k]) CE_HIP(ctx, hipEventSynchronize(b->ev_wide[k]));  // this staging pair's previous image has been converted
+    std::memcpy(b->h_wide[k], pixels, len);
+    CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], len, hipMemcpyHostToDevice, b->up_stream));
+    return CE_OK;
 }
 
 // pixels in a decoder's format -> wide staging -> device -> ingest kernel writes the RGB8 slab slot
@@ -747,6 +780,8 @@ static int upload_fmt(ce_batch *b, uint8_t *dst, const void *pixels, size_t len,
     ce_ctx *ctx = b->ctx;
     const size_t bpp = ce_pixel_bytes(format), n_px = (size_t)b->w * b->h;
     if (bpp == 0) return fail(ctx, CE_ERR_INVALID_ARG, "unknown pixel format");
+    if (b->linear != (format == CE_PIXEL_RGB_F32))
+        return fail(ctx, CE_ERR_INVALID_ARG, b->linear ? kLinearWants : "CE_PIXEL_RGB_F32 needs a linear batch (ce_batch_create_linear)");
     const bool fmt16 = format == CE_PIXEL_RGB16 || format == CE_PIXEL_RGBA16, fmt8 = format == CE_PIXEL_RGB8 || format == CE_PIXEL_RGBA8;
     if (!depth && fmt16) return fail(ctx, CE_ERR_INVALID_ARG, "CE_PIXEL_RGB16 / CE_PIXEL_RGBA16 need a deep batch (ce_batch_create_deep)");
     if (depth && !fmt16 && !fmt8)
@@ -758,16 +793,9 @@ static int upload_fmt(ce_batch *b, uint8_t *dst, const void *pixels, size_t len,
     CE_HIP(ctx, hipSetDevice(ctx->device));  // the staging allocations and the ingest launch below go to the context's device
     const int k = b->next_wide;
     b->next_wide ^= 1;
-    if (!b->h_wide[k]) {
-        CE_HIP(ctx, hipHostMalloc((void **)&b->h_wide[k], n_px * 8, hipHostMallocDefault));
-        CE_HIP(ctx, hipMalloc((void **)&b->d_wide[k], n_px * 8));
-        CE_HIP(ctx, hipEventCreateWithFlags(&b->ev_wide[k], hipEventDisableTiming));
-    }
-    if (int rc = order_write(b, false)) return rc;
-    if (b->wide_busy[k]) CE_HIP(ctx, hipEventSynchronize(b->ev_wide[k]));  // this staging pair's previous image has been converted
-    std::memcpy(b->h_wide[k], pixels, len);
-    CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], len, hipMemcpyHostToDevice, b->up_stream));
-    int rc = depth ? ce_launch_ingest_deep(ctx, b->up_stream, format, depth, b->d_wide[k], reinterpret_cast<uint16_t *>(dst), n_px)
+    if (int rc = wide_stage(b, k, pixels, len)) return rc;
+    int rc = b->linear ? ce_launch_linear_sanitise(ctx, b->up_stream, reinterpret_cast<const float *>(b->d_wide[k]), reinterpret_cast<float *>(dst), n_px * 3)
+             : depth ? ce_launch_ingest_deep(ctx, b->up_stream, format, depth, b->d_wide[k], reinterpret_cast<uint16_t *>(dst), n_px)
                    : ce_launch_ingest(ctx, b->up_stream, format, b->d_wide[k], dst, n_px);
     if (rc != CE_OK) return rc;
     CE_HIP(ctx, hipEventRecord(b->ev_wide[k], b->up_stream));
@@ -839,6 +867,7 @@ static int apply_lut(ce_batch *b, uint8_t *slot, const ce_lut *lut)
 int ce_batch_set_reference_lut(ce_batch *b, uint32_t ref_index, const void *pixels, size_t len, int format, const ce_lut *lut)
 {
     if (b && lut && b->depth[0]) return fail(b->ctx, CE_ERR_INVALID_ARG, "a colour table is 2^24 8-bit colours: not for a deep batch");
+    if (b && lut && b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, "a colour table is 2^24 8-bit colours: not for a linear batch");
     if (int rc = ce_batch_set_reference_fmt(b, ref_index, pixels, len, format)) return rc;
     return apply_lut(b, b->d_refs + (size_t)ref_index * b->img_bytes, lut);
 }
@@ -847,6 +876,7 @@ int ce_batch_set_test_lut(ce_batch *b, uint32_t pair_index, uint32_t ref_index, 
                           const ce_lut *lut)
 {
     if (b && lut && b->depth[0]) return fail(b->ctx, CE_ERR_INVALID_ARG, "a colour table is 2^24 8-bit colours: not for a deep batch");
+    if (b && lut && b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, "a colour table is 2^24 8-bit colours: not for a linear batch");
     if (int rc = ce_batch_set_test_fmt(b, pair_index, ref_index, pixels, len, format)) return rc;
     return apply_lut(b, b->d_tests + (size_t)pair_index * b->img_bytes, lut);
 }
@@ -868,6 +898,7 @@ int ce_batch_set_test(ce_batch *b, uint32_t pair_index, uint32_t ref_index, cons
 {
     if (!b || !rgb) return CE_ERR_INVALID_ARG;
     if (b->depth[0]) return ce_batch_set_test_fmt(b, pair_index, ref_index, rgb, len, CE_PIXEL_RGB8);
+    if (b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kLinearWants);
     if (int rc = ce_batch_bind_pair(b, pair_index, ref_index)) return rc;
     if (len != b->img_bytes) return bad_length(b->ctx, b->img_bytes, len);
     return upload(b, b->d_tests + (size_t)pair_index * b->img_bytes, rgb);
@@ -896,6 +927,8 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
     if (metric_mask & ~kKnownMetrics) return fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
     if (b->depth[0] && (flags & CE_FLAG_XYB_ROUNDTRIP))
         return fail(ctx, CE_ERR_INVALID_ARG, "CE_FLAG_XYB_ROUNDTRIP quantises to 8 bits by definition: not for a deep batch");
+    if (b->linear && (flags & CE_FLAG_XYB_ROUNDTRIP))
+        return fail(ctx, CE_ERR_INVALID_ARG, "CE_FLAG_XYB_ROUNDTRIP quantises to 8 bits by definition: not for a linear batch");
     b->ba_map_pairs = b->ds_map_pairs = 0;  // whatever happens below, no readout returns the maps of an earlier launch
     b->s2_map_pairs = b->s2_norm_pairs = 0;
     CE_HIP(ctx, hipSetDevice(ctx->device));
@@ -1064,7 +1097,7 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
             joined |= 1u << k;  // the context's stream waits for it after every chain has been launched
         }
     }
-    if ((metric_mask & CE_METRIC_PSNR) && b->depth[0] == b->depth[1]) {  // sides of two depths share no integer grid: no PSNR
+    if ((metric_mask & CE_METRIC_PSNR) && b->depth[0] == b->depth[1] && !b->linear) {  // sides of two depths, or floats, share no integer grid: no PSNR
         int rc = ce_launch_psnr(b, d_refs, n_pairs);
         if (rc != CE_OK) return rc;
     }
@@ -1106,7 +1139,7 @@ int ce_batch_collect(ce_batch *b, uint32_t n_pairs, ce_scores *out)
         ce_scores s{};
         s.status = CE_OK;
         const ce_dev_scores &d = b->h_scores[i];
-        if ((mask & CE_METRIC_PSNR) && b->depth[0] == b->depth[1]) {
+        if ((mask & CE_METRIC_PSNR) && b->depth[0] == b->depth[1] && !b->linear) {
             s.psnr = psnr_from_sse(d.sse, b->w, b->h, b->depth[0] ? (double)((1u << b->depth[0]) - 1u) : 255.0);
             s.valid |= CE_METRIC_PSNR;
         }
@@ -1202,6 +1235,12 @@ size_t ce_estimate_batch_bytes_deep(uint32_t w, uint32_t h, uint32_t n_refs, uin
     if (!deep_depth_ok(ref_depth) || !deep_depth_ok(test_depth)) return 0;
     const size_t slabs = (size_t)3 * w * h * ((size_t)n_refs + n_pairs);
     return ce_estimate_batch_bytes(w, h, n_refs, n_pairs, metric_mask) + slabs + (((size_t)8 << ref_depth) + ((size_t)8 << test_depth));
+}
+
+// the f32 slabs hold 12 bytes per pixel instead of 3; the working sets behind the front ends are the same
+size_t ce_estimate_batch_bytes_linear(uint32_t w, uint32_t h, uint32_t n_refs, uint32_t n_pairs, uint32_t metric_mask)
+{
+    return ce_estimate_batch_bytes(w, h, n_refs, n_pairs, metric_mask) + (size_t)9 * w * h * ((size_t)n_refs + n_pairs);
 }
 
 int ce_ctx_memory_info(ce_ctx *ctx, size_t *free_bytes, size_t *total_bytes)
@@ -1458,6 +1497,180 @@ int ce_eval_pair_deep(ce_ctx *ctx, const uint16_t *reference, size_t reference_l
     return out->status;
 }
 
+// One pair of packed f32 RGB through the context's one-pair linear batch (kept while the shape stays the same); validation
+// as ce_eval_pair_deep
+int ce_eval_pair_linear(ce_ctx *ctx, const float *reference, size_t reference_len, const float *test, size_t test_len, uint32_t width,
+                        uint32_t height, uint32_t metric_mask, uint32_t flags, float intensity_target, ce_scores *out)
+{
+    if (!ctx || !out || !reference || !test) return CE_ERR_INVALID_ARG;
+    *out = ce_scores{};
+    if (width == 0 || height == 0) return out->status = CE_ERR_INVALID_ARG;
+    if (reference_len != test_len)
+        return out->status = fail(ctx, CE_ERR_DIM_MISMATCH, "Dimension mismatch: reference " + std::to_string(reference_len) +
+                                                                " bytes, test " + std::to_string(test_len) + " bytes");
+    const size_t want = (size_t)width * height * 12;
+    if (reference_len != want) return out->status = bad_length(ctx, want, reference_len);
+    if (flags & (CE_FLAG_BUTTERAUGLI_DIFFMAP | CE_FLAG_SSIMULACRA2_MAPS))
+        return out->status = fail(ctx, CE_ERR_INVALID_ARG, "map flags need a ce_batch: this call's batch does not outlive it");
+    if (metric_mask & ~kKnownMetrics) return out->status = fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    ce_batch *b = ctx->leaf_linear;
+    if (!b || b->w != width || b->h != height) {
+        ce_batch_destroy(b);
+        ctx->leaf_linear = nullptr;
+        if (int rc = ce_batch_create_linear(ctx, width, height, 1, 1, &ctx->leaf_linear)) return out->status = rc;
+        b = ctx->leaf_linear;
+    }
+    int rc = ce_batch_set_reference_fmt(b, 0, reference, reference_len, CE_PIXEL_RGB_F32);
+    if (rc == CE_OK) rc = ce_batch_set_test_fmt(b, 0, 0, test, test_len, CE_PIXEL_RGB_F32);
+    if (rc == CE_OK) rc = ce_batch_run(b, 1, metric_mask, flags, intensity_target, out);
+    if (rc != CE_OK) {
+        drain_batch(b);
+        return out->status = rc;
+    }
+    return out->status;
+}
+
+// ---- CICP ingest (cicp.hip) --------------------------------------------------------------------------
+int ce_srgb_table(uint32_t depth, int rule, float *out, size_t n)
+{
+    if (!out || !deep_depth_ok(depth) || (rule != 0 && rule != 1) || n != ((size_t)1 << depth))
+        return fail(nullptr, CE_ERR_INVALID_ARG, "ce_srgb_table: depth 8, 10, 12 or 16, rule 0 or 1, n = 2^depth");
+    if (rule == 0) ce_build_srgb_table_f64(out, (1u << depth) - 1u); else ce_build_srgb_table_powf(out, (1u << depth) - 1u);
+    return CE_OK;
+}
+
+int ce_transfer_table(int transfer, uint32_t depth, float white_nits, float *out, size_t n)
+{
+    if (!out || !deep_depth_ok(depth) || n != ((size_t)1 << depth))
+        return fail(nullptr, CE_ERR_INVALID_ARG, "ce_transfer_table: depth 8, 10, 12 or 16 and n = 2^depth");
+    if (!ce_build_transfer_table(transfer, (1u << depth) - 1u, (double)white_nits, out))
+        return fail(nullptr, CE_ERR_INVALID_ARG, "ce_transfer_table: transfer 13 (sRGB), 8 (linear) or 16 (PQ, white_nits > 0)");
+    return CE_OK;
+}
+
+int ce_colour_matrix(int primaries, float out[9])
+{
+    if (!out || !ce_build_colour_matrix(primaries, out))
+        return fail(nullptr, CE_ERR_INVALID_ARG, "ce_colour_matrix: primaries 1 (BT.709), 9 (BT.2020) or 12 (Display P3)");
+    return CE_OK;
+}
+
+namespace {
+// what one CICP ingest runs with: the device table of (transfer, depth, white_nits) and the matrix (has_matrix: primaries != 1)
+struct cicp_plan {
+    const float *d_table;
+    uint32_t maxv;
+    bool has_matrix;
+    float m[9];
+};
+
+int cicp_check(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_colour *c, size_t n_px, cicp_plan *plan)
+{
+    if (!pixels || !c) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: null pointer");
+    const bool fmt8 = format == CE_PIXEL_RGB8 || format == CE_PIXEL_RGBA8, fmt16 = format == CE_PIXEL_RGB16 || format == CE_PIXEL_RGBA16;
+    if (!fmt8 && !fmt16) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: format must be CE_PIXEL_RGB8, RGBA8, RGB16 or RGBA16");
+    if (!deep_depth_ok(c->depth)) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: depth must be 8, 10, 12 or 16, got " + std::to_string(c->depth));
+    if (fmt8 && c->depth != 8) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: an 8-bit format needs depth 8, got " + std::to_string(c->depth));
+    if (c->transfer != 13 && c->transfer != 8 && c->transfer != 16)
+        return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: transfer must be 13 (sRGB), 8 (linear) or 16 (PQ), got " + std::to_string(c->transfer));
+    if (c->transfer == 16 && !(c->white_nits > 0.0f && std::isfinite(c->white_nits)))
+        return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: PQ needs white_nits > 0");
+    if (!ce_build_colour_matrix(c->primaries, plan->m))
+        return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: primaries must be 1 (BT.709), 9 (BT.2020) or 12 (Display P3), got " + std::to_string(c->primaries));
+    if (len != n_px * ce_pixel_bytes(format)) return bad_length(ctx, n_px * ce_pixel_bytes(format), len);
+    plan->has_matrix = c->primaries != 1;
+    plan->maxv = (1u << c->depth) - 1u;
+    // the table on the device, built once per context and (transfer, depth, white) and kept; white only matters to PQ
+    const float white = c->transfer == 16 ? c->white_nits : 0.0f;
+    uint32_t white_bits;
+    std::memcpy(&white_bits, &white, 4);
+    const auto key = std::make_tuple(c->transfer, c->depth, white_bits);
+    auto it = ctx->cicp_tables.find(key);
+    if (it == ctx->cicp_tables.end()) {
+        std::vector<float> host((size_t)plan->maxv + 1);
+        ce_build_transfer_table(c->transfer, plan->maxv, (double)white, host.data());
+        CE_HIP(ctx, hipSetDevice(ctx->device));
+        float *d = nullptr;
+        CE_HIP(ctx, hipMalloc(&d, host.size() * sizeof(float)));
+        if (hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+            hipFree(d);
+            return fail(ctx, CE_ERR_BACKEND, "H2D failed (transfer table)");
+        }
+        it = ctx->cicp_tables.emplace(key, d).first;
+    }
+    plan->d_table = it->second;
+    return CE_OK;
+}
+
+// one tagged image through the wide staging pair of upload_fmt into the slot at dst, on the batch's upload stream
+int upload_cicp(ce_batch *b, uint8_t *dst, const void *pixels, size_t len, int format, const cicp_plan &plan)
+{
+    ce_ctx *ctx = b->ctx;
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    const int k = b->next_wide;
+    b->next_wide ^= 1;
+    if (int rc = wide_stage(b, k, pixels, len)) return rc;
+    if (int rc = ce_launch_cicp(ctx, b->up_stream, format, b->d_wide[k], reinterpret_cast<float *>(dst), (size_t)b->w * b->h, plan.d_table,
+                                plan.maxv, plan.has_matrix ? plan.m : nullptr))
+        return rc;
+    CE_HIP(ctx, hipEventRecord(b->ev_wide[k], b->up_stream));
+    b->wide_busy[k] = true;
+    b->uploads_pending = true;
+    return CE_OK;
+}
+}  // namespace
+
+int ce_batch_set_reference_cicp(ce_batch *b, uint32_t ref_index, const void *pixels, size_t len, int format, const ce_colour *c)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    if (!b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, "CICP ingest writes linear light: it needs a linear batch (ce_batch_create_linear)");
+    if (ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "ref_index out of range");
+    cicp_plan plan;
+    if (int rc = cicp_check(b->ctx, pixels, len, format, c, (size_t)b->w * b->h, &plan)) return rc;
+    invalidate_reference_state(b);
+    return upload_cicp(b, b->d_refs + (size_t)ref_index * b->img_bytes, pixels, len, format, plan);
+}
+
+int ce_batch_set_test_cicp(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format,
+                           const ce_colour *c)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    if (!b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, "CICP ingest writes linear light: it needs a linear batch (ce_batch_create_linear)");
+    if (pair_index >= b->max_pairs || ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "pair/ref index out of range");
+    cicp_plan plan;
+    if (int rc = cicp_check(b->ctx, pixels, len, format, c, (size_t)b->w * b->h, &plan)) return rc;
+    if (int rc = ce_batch_bind_pair(b, pair_index, ref_index)) return rc;
+    return upload_cicp(b, b->d_tests + (size_t)pair_index * b->img_bytes, pixels, len, format, plan);
+}
+
+int ce_cicp_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_colour *c, uint32_t w, uint32_t h, float *out,
+                      size_t out_len)
+{
+    if (!ctx || !out) return CE_ERR_INVALID_ARG;
+    if (w == 0 || h == 0) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: empty image");
+    const size_t n_px = (size_t)w * h;
+    cicp_plan plan;
+    if (int rc = cicp_check(ctx, pixels, len, format, c, n_px, &plan)) return rc;
+    if (out_len != n_px * 3) return fail(ctx, CE_ERR_BAD_LENGTH, "CICP ingest: out_len must be " + std::to_string(n_px * 3) + " floats, got " + std::to_string(out_len));
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    void *d_in = nullptr;
+    float *d_out = nullptr;
+    CE_HIP(ctx, hipMalloc(&d_in, len));
+    if (hipMalloc(&d_out, n_px * 12) != hipSuccess) {
+        hipFree(d_in);
+        return fail(ctx, CE_ERR_BACKEND, "hipMalloc failed (CICP ingest)");
+    }
+    int rc = CE_OK;
+    if (hipMemcpyAsync(d_in, pixels, len, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = fail(ctx, CE_ERR_BACKEND, "H2D failed (CICP ingest)");
+    if (rc == CE_OK) rc = ce_launch_cicp(ctx, ctx->stream, format, d_in, d_out, n_px, plan.d_table, plan.maxv, plan.has_matrix ? plan.m : nullptr);
+    if (rc == CE_OK && hipMemcpyAsync(out, d_out, n_px * 12, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, CE_ERR_BACKEND, "D2H failed (CICP ingest)");
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == CE_OK) rc = fail(ctx, CE_ERR_BACKEND, "sync failed (CICP ingest)");
+    hipFree(d_in);
+    hipFree(d_out);
+    return rc;
+}
+
 static int leaf(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test, size_t test_len,
                 size_t width, size_t height, uint32_t metric, float intensity, double *out)
 {
@@ -1686,6 +1899,7 @@ int ce_batch_image_heuristics(ce_batch *b, uint32_t which, uint32_t first, uint3
     if (!b || !out) return CE_ERR_INVALID_ARG;
     ce_ctx *ctx = b->ctx;
     if (b->depth[0]) return fail(ctx, CE_ERR_INVALID_ARG, "image heuristics are defined on u8 gray levels: not for a deep batch");
+    if (b->linear) return fail(ctx, CE_ERR_INVALID_ARG, "image heuristics are defined on u8 gray levels: not for a linear batch");
     if (which != CE_BATCH_REFERENCES && which != CE_BATCH_TESTS)
         return fail(ctx, CE_ERR_INVALID_ARG, "image heuristics: unknown slab " + std::to_string(which));
     const uint32_t slots = which == CE_BATCH_TESTS ? b->max_pairs : b->max_refs;
@@ -1800,10 +2014,13 @@ static int upload_yuv(ce_batch *b, uint8_t *dst, const ce_yuv_image *img, yuv_pl
     return CE_OK;
 }
 
+static const char *const kYuvLinear = "Y'CbCr ingest writes integer RGB: for a linear batch chain ce_yuv_to_rgb16 into ce_batch_set_*_cicp";
+
 int ce_batch_set_reference_yuv(ce_batch *b, uint32_t ref_index, const ce_yuv_image *image)
 {
     if (!b) return CE_ERR_INVALID_ARG;
     if (ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "ref_index out of range");
+    if (b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kYuvLinear);
     yuv_plan plan;
     if (int rc = yuv_check(b->ctx, image, b->w, b->h, b->depth[0] ? b->depth[0] : 8, &plan)) return rc;
     invalidate_reference_state(b);
@@ -1814,6 +2031,7 @@ int ce_batch_set_test_yuv(ce_batch *b, uint32_t pair_index, uint32_t ref_index, 
 {
     if (!b) return CE_ERR_INVALID_ARG;
     if (pair_index >= b->max_pairs || ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "pair/ref index out of range");
+    if (b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kYuvLinear);
     yuv_plan plan;
     if (int rc = yuv_check(b->ctx, image, b->w, b->h, b->depth[1] ? b->depth[1] : 8, &plan)) return rc;
     if (int rc = ce_batch_bind_pair(b, pair_index, ref_index)) return rc;
@@ -1875,6 +2093,7 @@ static int alpha_backgrounds_ok(ce_ctx *ctx, uint32_t n_bg, const uint16_t *back
 static int alpha_check(ce_batch *b, size_t len, int format, uint32_t n_bg, const uint16_t *backgrounds, uint32_t depth)
 {
     ce_ctx *ctx = b->ctx;
+    if (b->linear) return fail(ctx, CE_ERR_INVALID_ARG, "alpha compositing works on encoded integer samples: not for a linear batch");
     if (format != CE_PIXEL_RGBA8 && format != CE_PIXEL_RGBA16)
         return fail(ctx, CE_ERR_INVALID_ARG, format == CE_PIXEL_RGBA16_10BIT ? "alpha compositing: CE_PIXEL_RGBA16_10BIT rounds to 8 bits; a deep batch takes 10-bit alpha as CE_PIXEL_RGBA16"
                                                                               : "alpha compositing: the format must be CE_PIXEL_RGBA8 or CE_PIXEL_RGBA16");
@@ -2059,6 +2278,8 @@ static int resample_check(ce_batch *src, ce_batch *dst, int filter)
     if (!resample_filter_ok(filter)) return fail(ctx, CE_ERR_INVALID_ARG, "resample: unknown filter " + std::to_string(filter));
     if (src->depth[0] || dst->depth[0])
         return fail(ctx, CE_ERR_INVALID_ARG, "resample works on RGB8 batches: a deep batch is out of its scope");
+    if (src->linear || dst->linear)
+        return fail(ctx, CE_ERR_INVALID_ARG, "resample works on RGB8 batches: a linear batch is out of its scope");
     return CE_OK;
 }
 

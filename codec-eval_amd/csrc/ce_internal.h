@@ -20,8 +20,9 @@
 #define CE_SSIM2_STREAMS 5   // blur(a), blur(b), blur(a*a), blur(b*b), blur(a*b)
 #define CE_DSSIM_SCALES 5    // dssim-core DEFAULT_WEIGHTS.len()
 // where a front end's level 0 comes from: the linear planes of the level below (levels above 0), packed RGB8, or the packed
-// u16 RGB of a deep batch (ce_batch_create_deep)
-enum { CE_SRC_F32 = 0, CE_SRC_U8 = 1, CE_SRC_U16 = 2 };
+// u16 RGB of a deep batch (ce_batch_create_deep), or the packed f32 RGB of a linear batch (ce_batch_create_linear: the sample
+// is the linear value, no table)
+enum { CE_SRC_F32 = 0, CE_SRC_U8 = 1, CE_SRC_U16 = 2, CE_SRC_LIN = 3 };
 static_assert(CE_MAX_SCALES == CE_SSIM2_MAX_SCALES, "the ABI's scale count is the pyramid's");
 
 struct ce_scale_dims {
@@ -75,6 +76,10 @@ struct ce_ctx {
     // built by the first deep batch that needs one and kept until the context goes (ce_api.cpp: ce_deep_table)
     std::map<std::pair<uint32_t, int>, float *> deep_tables;
     struct ce_batch *leaf_deep = nullptr;  // the one-pair deep batch of ce_eval_pair_deep (remade when shape or depths change)
+    struct ce_batch *leaf_linear = nullptr;  // the one-pair linear batch of ce_eval_pair_linear (remade when the shape changes)
+    // transfer tables of the CICP ingest (cicp.hip), 2^depth entries each, keyed by (transfer, depth, bits of white_nits);
+    // built by the first ingest that needs one and kept until the context goes (ce_api.cpp: cicp_table)
+    std::map<std::tuple<int, uint32_t, uint32_t>, float *> cicp_tables;
 
     // profiling
     bool prof = false;         // record a HIP event pair around every launch (on the launch's own stream)
@@ -137,7 +142,8 @@ struct ce_xcd_list {
 struct ce_batch {
     ce_ctx *ctx = nullptr;
     uint32_t w = 0, h = 0, max_refs = 0, max_pairs = 0;
-    size_t img_bytes = 0;  // w*h*3; w*h*6 in a deep batch
+    size_t img_bytes = 0;  // w*h*3; w*h*6 in a deep batch; w*h*12 in a linear batch
+    bool linear = false;   // a linear batch (ce_batch_create_linear): the slabs hold packed f32 RGB, linear light; depth = 0 / 0
     // A deep batch (ce_batch_create_deep): depth[0] / depth[1] = bits per sample of the reference / test side (8, 10, 12 or
     // 16), the slabs hold packed u16 RGB and the front ends read them through deep_lut[rule][side] (ce_ctx::deep_tables).
     // 0 / 0: an RGB8 batch.
@@ -390,7 +396,19 @@ int ce_launch_yuv(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32
 int ce_launch_alpha(ce_ctx *ctx, hipStream_t stream, const void *d_src, bool src16, void *d_dst, bool dst16, uint32_t depth,
                     size_t n_pixels, uint32_t n_bg, const uint16_t *backgrounds);
 
+// n_samples floats at d_src (16-byte aligned staging) -> d_dst with NaN -> 0 and the clamp to +-CE_LINEAR_MAX (cicp.hip)
+int ce_launch_linear_sanitise(ce_ctx *ctx, hipStream_t stream, const float *d_src, float *d_dst, size_t n_samples);
+// n_pixels RGB(A) pixels of u8 / u16 samples at d_src (16-byte aligned staging; format: CE_PIXEL_RGB8 / RGBA8 / RGB16 /
+// RGBA16) -> packed f32 RGB at d_dst: table[min(v, maxv)] per channel, then, with a matrix (nullptr: none), the 3 x 3
+// product in separately rounded f32 operations, then the clamp of a linear image (cicp.hip)
+int ce_launch_cicp(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, float *d_dst, size_t n_pixels, const float *d_table,
+                   uint32_t maxv, const float *matrix);
+
 // host-side constant builders (ce_tables.cpp)
+// the CICP ingest's transfer table (include/ce_metrics.h: ce_transfer_table) and primaries matrix (ce_colour_matrix); false
+// for a code point that is not offered
+bool ce_build_transfer_table(int transfer, uint32_t maxv, double white_nits, float *lut);
+bool ce_build_colour_matrix(int primaries, float m[9]);
 // the resampler's taps of one axis, n_in -> n_out samples (include/ce_metrics.h, enum ce_resample_filter): table = [n_out]
 // first tap | [n_out] tap count | [n_out][ksize] weights; false for an unknown filter or an empty axis
 bool ce_build_resample_table(uint32_t n_in, uint32_t n_out, int filter, std::vector<int32_t> &table, uint32_t *ksize);

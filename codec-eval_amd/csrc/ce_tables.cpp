@@ -236,3 +236,90 @@ int ce_yuv_coefficients(int matrix, int range, uint32_t depth_in, uint32_t depth
     out[5] = y0, out[6] = c0;
     return CE_OK;
 }
+
+// ---- CICP ingest (include/ce_metrics.h: ce_transfer_table, ce_colour_matrix) --------------------------
+// Transfer characteristics 13 (sRGB: the rule-0 table above), 8 (linear: v / maxv) and 16 (PQ, SMPTE ST 2084 with its
+// rational constants: nits / white_nits), each in f64 per code point and rounded once to f32.
+bool ce_build_transfer_table(int transfer, uint32_t maxv, double white_nits, float *lut)
+{
+    if (transfer == 13) {
+        ce_build_srgb_table_f64(lut, maxv);
+        return true;
+    }
+    if (transfer == 8) {
+        for (uint32_t i = 0; i <= maxv; i++) lut[i] = (float)((double)i / (double)maxv);
+        return true;
+    }
+    if (transfer == 16) {
+        if (!(white_nits > 0.0) || !std::isfinite(white_nits)) return false;
+        const double m1 = 2610.0 / 16384.0, m2 = 2523.0 / 4096.0 * 128.0;
+        const double c1 = 3424.0 / 4096.0, c2 = 2413.0 / 4096.0 * 32.0, c3 = 2392.0 / 4096.0 * 32.0;
+        for (uint32_t i = 0; i <= maxv; i++) {
+            const double e = (double)i / (double)maxv;
+            const double p = std::pow(e, 1.0 / m2);
+            const double num = std::fmax(p - c1, 0.0), den = c2 - c3 * p;
+            const double y = std::pow(num / den, 1.0 / m1);
+            lut[i] = (float)(10000.0 * y / white_nits);
+        }
+        return true;
+    }
+    return false;
+}
+
+namespace {
+// inverse of a 3 x 3 matrix by its adjugate, every operation written out (the restatement in tests/cicp_restatement.py
+// performs the same f64 operations in the same order)
+void inv3(const double a[9], double o[9])
+{
+    const double c00 = a[4] * a[8] - a[5] * a[7], c01 = a[5] * a[6] - a[3] * a[8], c02 = a[3] * a[7] - a[4] * a[6];
+    const double det = (a[0] * c00 + a[1] * c01) + a[2] * c02;
+    o[0] = c00 / det;
+    o[1] = (a[2] * a[7] - a[1] * a[8]) / det;
+    o[2] = (a[1] * a[5] - a[2] * a[4]) / det;
+    o[3] = c01 / det;
+    o[4] = (a[0] * a[8] - a[2] * a[6]) / det;
+    o[5] = (a[2] * a[3] - a[0] * a[5]) / det;
+    o[6] = c02 / det;
+    o[7] = (a[1] * a[6] - a[0] * a[7]) / det;
+    o[8] = (a[0] * a[4] - a[1] * a[3]) / det;
+}
+
+// XYZ <- RGB of a set of chromaticities (x, y of red, green, blue, white): columns (x / y, 1, (1 - x - y) / y) scaled so
+// that RGB = (1, 1, 1) gives the white point with Y = 1
+void rgb_to_xyz(const double xy[8], double m[9])
+{
+    double p[9], pi[9];
+    for (int c = 0; c < 3; c++) {
+        const double x = xy[2 * c], y = xy[2 * c + 1];
+        p[c] = x / y, p[3 + c] = 1.0, p[6 + c] = ((1.0 - x) - y) / y;
+    }
+    const double wx = xy[6] / xy[7], wy = 1.0, wz = ((1.0 - xy[6]) - xy[7]) / xy[7];
+    inv3(p, pi);
+    for (int c = 0; c < 3; c++) {
+        const double s = (pi[3 * c] * wx + pi[3 * c + 1] * wy) + pi[3 * c + 2] * wz;
+        for (int r = 0; r < 3; r++) m[3 * r + c] = p[3 * r + c] * s;
+    }
+}
+}  // namespace
+
+// Colour primaries 1 (BT.709), 9 (BT.2020) and 12 (Display P3, D65), H.273's chromaticities: M = inv(XYZ <- sRGB) * (XYZ <-
+// src) in f64, rounded once to f32; primaries 1 gives the identity (the ingest does not multiply then).
+bool ce_build_colour_matrix(int primaries, float m[9])
+{
+    static const double k709[8] = {0.640, 0.330, 0.300, 0.600, 0.150, 0.060, 0.3127, 0.3290};
+    static const double k2020[8] = {0.708, 0.292, 0.170, 0.797, 0.131, 0.046, 0.3127, 0.3290};
+    static const double kP3[8] = {0.680, 0.320, 0.265, 0.690, 0.150, 0.060, 0.3127, 0.3290};
+    if (primaries == 1) {
+        for (int i = 0; i < 9; i++) m[i] = (i % 4 == 0) ? 1.0f : 0.0f;
+        return true;
+    }
+    const double *src = primaries == 9 ? k2020 : primaries == 12 ? kP3 : nullptr;
+    if (!src) return false;
+    double a[9], ai[9], s[9];
+    rgb_to_xyz(k709, a);
+    inv3(a, ai);
+    rgb_to_xyz(src, s);
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) m[3 * r + c] = (float)((ai[3 * r] * s[c] + ai[3 * r + 1] * s[3 + c]) + ai[3 * r + 2] * s[6 + c]);
+    return true;
+}

@@ -1,0 +1,149 @@
+// The device code of the CICP ingest and of the linear-f32 upload (cicp.hip), kept free of anything but the HIP keywords,
+// uint2 / uint4 / float4 and blockIdx / threadIdx, so that tests/cpp/cicp_kernel_host.cpp can compile the same text for the
+// host - thread and block indices as loop variables - and run it under the host sanitizers against a source and a slot
+// allocated at exactly their size.  Every product and every sum of the matrix is a separately rounded f32 operation: this
+// text is compiled with -ffp-contract=off on the device and on the host, and its expressions are written so that no
+// other evaluation order is allowed (include/ce_metrics.h: the definition of ce_batch_set_*_cicp).
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+#include "ce_metrics.h"
+
+namespace {
+
+constexpr int kCicpBlock = 256;  // threads per block; a thread owns 4 pixels: a 768 x 512 image is 384 blocks
+
+struct cicp_args {
+    const void *src;     // packed RGB / RGBA, u8 or u16 samples, 16-byte aligned
+    float *dst;          // the slot: packed f32 RGB, 4-byte aligned (16 where the slot's offset allows)
+    size_t n_pixels;
+    const float *table;  // maxv + 1 entries
+    uint32_t maxv;
+    float m[9];          // row-major; unused without MATRIX
+};
+
+// a linear image's sample: NaN -> 0, then the clamp to [-CE_LINEAR_MAX, CE_LINEAR_MAX]
+__device__ __forceinline__ float linear_clamp(float v)
+{
+    if (v != v) return 0.0f;
+    return v > CE_LINEAR_MAX ? CE_LINEAR_MAX : (v < -CE_LINEAR_MAX ? -CE_LINEAR_MAX : v);
+}
+
+template <bool MATRIX>
+__device__ __forceinline__ void cicp_pixel(const cicp_args &a, uint32_t r, uint32_t g, uint32_t b, float (&o)[3])
+{
+    const float tr = a.table[r < a.maxv ? r : a.maxv], tg = a.table[g < a.maxv ? g : a.maxv], tb = a.table[b < a.maxv ? b : a.maxv];
+    if constexpr (MATRIX) {
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            const float p0 = a.m[3 * i] * tr, p1 = a.m[3 * i + 1] * tg, p2 = a.m[3 * i + 2] * tb;
+            const float s01 = p0 + p1;
+            o[i] = linear_clamp(s01 + p2);
+        }
+    } else {
+        o[0] = linear_clamp(tr), o[1] = linear_clamp(tg), o[2] = linear_clamp(tb);
+    }
+}
+
+// 12 floats (four pixels) to p: three 16-byte stores where the address allows, twelve 4-byte stores otherwise; the same
+// choice for every thread of a launch, since a group starts a multiple of 48 bytes into its slot
+__device__ __forceinline__ void store12(float *p, const float (&o)[12])
+{
+    if ((reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+#pragma unroll
+        for (int i = 0; i < 3; i++) reinterpret_cast<float4 *>(p)[i] = make_float4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 12; i++) p[i] = o[i];
+    }
+}
+
+// FMT: CE_PIXEL_RGB8 / RGBA8 / RGB16 / RGBA16 (alpha dropped).  A thread converts one group of four pixels from the
+// registers its aligned loads filled (12 bytes: three dwords; 16: one uint4; 24: three uint2; 32: two uint4) and stores 48
+// bytes; the last n_pixels % 4 pixels go sample by sample, one pixel to a thread of block 0.  The table is gathered from
+// global memory at every depth: 1, 4 and 16 KB stay in the vector L1 and the 256 KB of depth 16 in L2, one code path.
+template <int FMT, bool MATRIX>
+__global__ __launch_bounds__(kCicpBlock) void k_cicp(const cicp_args a)
+{
+    constexpr bool S16 = FMT == CE_PIXEL_RGB16 || FMT == CE_PIXEL_RGBA16, ALPHA = FMT == CE_PIXEL_RGBA8 || FMT == CE_PIXEL_RGBA16;
+    constexpr int NC = ALPHA ? 4 : 3;
+    const size_t n_groups = a.n_pixels / 4;
+    const size_t tid = (size_t)blockIdx.x * kCicpBlock + threadIdx.x;
+    if (tid < n_groups) {
+        uint32_t s[4 * NC];  // the group's samples, in memory order
+        if constexpr (!S16) {
+            uint32_t d[NC];
+            if constexpr (ALPHA) {
+                const uint4 v = reinterpret_cast<const uint4 *>(a.src)[tid];
+                d[0] = v.x, d[1] = v.y, d[2] = v.z, d[NC - 1] = v.w;
+            } else {
+#pragma unroll
+                for (int i = 0; i < NC; i++) d[i] = reinterpret_cast<const uint32_t *>(a.src)[tid * NC + i];
+            }
+#pragma unroll
+            for (int i = 0; i < 4 * NC; i++) s[i] = (d[i / 4] >> (8 * (i % 4))) & 255u;
+        } else {
+            uint32_t d[2 * NC];
+            if constexpr (ALPHA) {
+#pragma unroll
+                for (int i = 0; i < 2; i++) {
+                    const uint4 v = reinterpret_cast<const uint4 *>(a.src)[tid * 2 + i];
+                    d[4 * i] = v.x, d[4 * i + 1] = v.y, d[4 * i + 2] = v.z, d[4 * i + 3] = v.w;
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 3; i++) {
+                    const uint2 v = reinterpret_cast<const uint2 *>(a.src)[tid * 3 + i];
+                    d[2 * i] = v.x, d[2 * i + 1] = v.y;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 4 * NC; i++) s[i] = (d[i / 2] >> (16 * (i % 2))) & 0xffffu;
+        }
+        float o[12];
+#pragma unroll
+        for (int p = 0; p < 4; p++) {
+            float px[3];
+            cicp_pixel<MATRIX>(a, s[NC * p], s[NC * p + 1], s[NC * p + 2], px);
+            o[3 * p] = px[0], o[3 * p + 1] = px[1], o[3 * p + 2] = px[2];
+        }
+        store12(a.dst + tid * 12, o);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < a.n_pixels % 4) {
+        const size_t p = n_groups * 4 + threadIdx.x;
+        uint32_t v[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+            v[c] = S16 ? static_cast<const uint16_t *>(a.src)[p * NC + c] : static_cast<const uint8_t *>(a.src)[p * NC + c];
+        float px[3];
+        cicp_pixel<MATRIX>(a, v[0], v[1], v[2], px);
+#pragma unroll
+        for (int c = 0; c < 3; c++) a.dst[p * 3 + c] = px[c];
+    }
+}
+
+// The CE_PIXEL_RGB_F32 upload: n_samples floats from 16-byte aligned staging into the slot through linear_clamp, four to a
+// thread (one 16-byte load; one 16-byte store where the slot's address allows), the last n_samples % 4 one to a thread of
+// block 0.
+__global__ __launch_bounds__(kCicpBlock) void k_linear_sanitise(const float *__restrict__ src, float *__restrict__ dst, size_t n_samples)
+{
+    const size_t n_groups = n_samples / 4;
+    const size_t tid = (size_t)blockIdx.x * kCicpBlock + threadIdx.x;
+    if (tid < n_groups) {
+        const float4 v = reinterpret_cast<const float4 *>(src)[tid];
+        const float o0 = linear_clamp(v.x), o1 = linear_clamp(v.y), o2 = linear_clamp(v.z), o3 = linear_clamp(v.w);
+        float *p = dst + tid * 4;
+        if ((reinterpret_cast<uintptr_t>(p) & 15) == 0)
+            *reinterpret_cast<float4 *>(p) = make_float4(o0, o1, o2, o3);
+        else
+            p[0] = o0, p[1] = o1, p[2] = o2, p[3] = o3;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < n_samples % 4) {
+        const size_t i = n_groups * 4 + threadIdx.x;
+        dst[i] = linear_clamp(src[i]);
+    }
+}
+
+}  // namespace

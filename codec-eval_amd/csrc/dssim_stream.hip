@@ -214,7 +214,8 @@ __global__ __launch_bounds__(CS_WAVES * 64) __attribute__((amdgpu_waves_per_eu(3
 constexpr int CR_HALO_REF = 4, CR_HALO_DIST = 2;
 
 // SRC (ce_internal.h: CE_SRC_*): level 0 reads sRGB samples through a table - u8 through the 256 entries in LDS, the u16 of a
-// deep batch through its side's 2^depth entries in global memory (s_lut is that table then) - the levels above read floats
+// deep batch through its side's 2^depth entries in global memory (s_lut is that table then), the packed f32 of a linear batch
+// as it is (CE_SRC_LIN) - the levels above read floats
 template <int SRC, bool REF, bool EDGE>
 __device__ __forceinline__ void dssim_create_strip(const uint8_t *__restrict__ src8, const float *const (&srcf)[3], const float *s_lut,
                                                    float *const (&lin_out)[3], float *const (&oimg)[3], float *const (&omu)[3],
@@ -247,6 +248,10 @@ __device__ __forceinline__ void dssim_create_strip(const uint8_t *__restrict__ s
         } else if (FROM_U16) {
             const uint16_t *px = reinterpret_cast<const uint16_t *>(src8) + (yc * (uint32_t)w + Xc) * 3u;
             o.v[0] = px[0], o.v[1] = px[1], o.v[2] = px[2];
+        } else if (SRC == CE_SRC_LIN) {
+            const float *px = reinterpret_cast<const float *>(src8) + (yc * (uint32_t)w + Xc) * 3u;
+#pragma unroll
+            for (int c = 0; c < 3; c++) o.v[c] = __float_as_uint(px[c]);
         } else {
             const uint32_t ob = (yc * pitch + Xc) * 4u;
 #pragma unroll
@@ -384,7 +389,7 @@ __global__ __launch_bounds__(CS_WAVES * 64) void k_dssim_create_stream(const uin
     const uint32_t tile = blockIdx.x * CS_WAVES + wv;
     if (tile >= strips * ((g.h + rows - 1) / rows)) return;
     const int xs = (int)((tile % strips) * out_cols), y0 = (int)((tile / strips) * rows), y1 = min(y0 + (int)rows, (int)g.h);
-    const uint8_t *src8 = (FROM_U8 || FROM_U16) ? (is_ref ? refs + (size_t)z * img_bytes : tests + (size_t)(z - n_refs_used) * img_bytes) : nullptr;
+    const uint8_t *src8 = (FROM_U8 || FROM_U16 || SRC == CE_SRC_LIN) ? (is_ref ? refs + (size_t)z * img_bytes : tests + (size_t)(z - n_refs_used) * img_bytes) : nullptr;
     const float *srcf[3];
     float *lo[3], *oi[3], *om[3], *oq[3];
 #pragma unroll
@@ -444,7 +449,8 @@ int ce_dssim_create_stream(ce_batch *b, int l, const uint8_t *d_refs, uint32_t n
               (const float *)LUT_R, (const float *)LUT_T, (const float *)(l == 0 ? nullptr : b->ds_lin[l & 1]), b->ds_lin[(l + 1) & 1], b->ds_img,      \
               b->ds_rimg[l], b->ds_rmu[l], b->ds_rsq[l], lg, ng, has_next ? 1 : 0, b->img_bytes, n_refs_used, b->max_refs, Z0, rows)
     const dim3 grid((tiles + CS_WAVES - 1) / CS_WAVES, n_slots - z0);
-    if (l == 0 && b->depth[0]) CE_CREATE_LAUNCH("dssim_create_u16", CE_SRC_U16, grid, z0, b->deep_lut[1][0], b->deep_lut[1][1]);
+    if (l == 0 && b->linear) CE_CREATE_LAUNCH("dssim_create_lin", CE_SRC_LIN, grid, z0, nullptr, nullptr);
+    else if (l == 0 && b->depth[0]) CE_CREATE_LAUNCH("dssim_create_u16", CE_SRC_U16, grid, z0, b->deep_lut[1][0], b->deep_lut[1][1]);
     else if (l == 0) CE_CREATE_LAUNCH("dssim_create_u8", CE_SRC_U8, grid, z0, ctx->d_lut_powf, ctx->d_lut_powf);
     else CE_CREATE_LAUNCH("dssim_create", CE_SRC_F32, grid, z0, ctx->d_lut_powf, ctx->d_lut_powf);
 #undef CE_CREATE_LAUNCH

@@ -157,6 +157,7 @@ size_t ce_pixel_bytes(int format)
         case CE_PIXEL_RGBA16_10BIT: return 8;
         case CE_PIXEL_RGB16: return 6;
         case CE_PIXEL_RGBA16: return 8;
+        case CE_PIXEL_RGB_F32: return 12;
         default: return 0;
     }
 }

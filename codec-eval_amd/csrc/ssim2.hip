@@ -134,7 +134,7 @@ __device__ __forceinline__ void linear_to_xyb_positive(float r, float g, float b
 // linear RGB (2x2 box average, edge-clamped, ceil sizes; summed in the lineage's (y, x) order).
 // SRC: where level 0 comes from - CE_SRC_U8 (the 256-entry table, held in LDS) or CE_SRC_U16 (a deep batch: 2^depth entries
 // per side, lut for the references and lut_test for the distorted images, gathered from global memory);
-// CE_SRC_F32 = a level above 0, from the linear planes
+// CE_SRC_LIN (a linear batch: the packed f32 sample is the linear value); CE_SRC_F32 = a level above 0, from the linear planes
 template <int SRC>
 __global__ __launch_bounds__(256) void k_ssim2_prep(const uint8_t *__restrict__ refs, const uint8_t *__restrict__ tests,
                                                     const float *__restrict__ lut, const float *__restrict__ lut_test,
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256) void k_ssim2_prep(const uint8_t *__restrict__ 
                                                     size_t oplane, int has_next, size_t img_bytes, uint32_t n_refs_used,
                                                     uint32_t max_refs, uint32_t z0)
 {
-    constexpr bool FROM_U8 = SRC == CE_SRC_U8, FROM_U16 = SRC == CE_SRC_U16;
+    constexpr bool FROM_U8 = SRC == CE_SRC_U8, FROM_U16 = SRC == CE_SRC_U16, FROM_LIN = SRC == CE_SRC_LIN;
     __shared__ float s_lut[256];
     if (FROM_U8) {
         s_lut[threadIdx.x] = lut[threadIdx.x];
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256) void k_ssim2_prep(const uint8_t *__restrict__ 
     const uint32_t qx = blockIdx.x * 64 + (threadIdx.x & 63), qy = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (qx >= (w + 1) / 2 || qy >= (h + 1) / 2) return;
     const uint8_t *src8 = nullptr;
-    if (FROM_U8 || FROM_U16) src8 = z < n_refs_used ? refs + (size_t)z * img_bytes : tests + (size_t)(z - n_refs_used) * img_bytes;
+    if (FROM_U8 || FROM_U16 || FROM_LIN) src8 = z < n_refs_used ? refs + (size_t)z * img_bytes : tests + (size_t)(z - n_refs_used) * img_bytes;
     const uint16_t *src16 = reinterpret_cast<const uint16_t *>(src8);
     const float *tab16 = z < n_refs_used ? lut : lut_test;
     const float *srcf = lin_in + (size_t)slot * 3 * plane;
@@ -191,6 +191,11 @@ __global__ __launch_bounds__(256) void k_ssim2_prep(const uint8_t *__restrict__ 
                 r = tab16[px[0]];
                 g = tab16[px[1]];
                 bl = tab16[px[2]];
+            } else if (FROM_LIN) {
+                const float *px = reinterpret_cast<const float *>(src8) + ((size_t)y * w + x) * 3;  // x, y clamped: inside the image
+                r = px[0];
+                g = px[1];
+                bl = px[2];
             } else {
                 const size_t o = (size_t)y * pitch + x;
                 r = srcf[o];
@@ -900,7 +905,11 @@ int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
         const bool has_next = s + 1 < levels;
         const ce_scale_dims &nd = b->sd[has_next ? s + 1 : s];
         const dim3 quad_grid(((d.w + 1) / 2 + 63) / 64, ((d.h + 1) / 2 + 3) / 4, n_slots - z0);
-        if (s == 0 && b->depth[0])
+        if (s == 0 && b->linear)
+            CE_LAUNCH(ctx, "ssim2_prep_lin", k_ssim2_prep<CE_SRC_LIN>, quad_grid, dim3(256), 0, d_refs, b->d_tests, (const float *)nullptr,
+                      (const float *)nullptr, (const float *)nullptr, b->d_xyb[0], b->d_lin[1], d.w, d.h, d.pitch, d.plane, nd.pitch,
+                      nd.plane, has_next ? 1 : 0, b->img_bytes, n_refs_used, b->max_refs, z0);
+        else if (s == 0 && b->depth[0])
             CE_LAUNCH(ctx, "ssim2_prep_u16", k_ssim2_prep<CE_SRC_U16>, quad_grid, dim3(256), 0, d_refs, b->d_tests, b->deep_lut[0][0],
                       b->deep_lut[0][1], (const float *)nullptr, b->d_xyb[0], b->d_lin[1], d.w, d.h, d.pitch, d.plane, nd.pitch,
                       nd.plane, has_next ? 1 : 0, b->img_bytes, n_refs_used, b->max_refs, z0);

@@ -426,6 +426,32 @@ inline std::vector<uint16_t> yuv_to_rgb16(const HipBackend &be, const YuvImage &
     detail::check(be, ce_yuv_to_rgb16(be.ctx(), &image, width, height, depth_out, out.data(), out.size()), "yuv", width, height, out.size());
     return out;
 }
+// ---- CICP ingest (include/ce_metrics.h: ce_cicp_to_linear) ---------------------------------------
+// H.273 code points a decoder reports; presets for the common three
+using ColourDescription = ce_colour;
+inline ColourDescription colour_srgb(uint32_t depth = 8) { return ColourDescription{1, 13, depth, 0.0f}; }
+inline ColourDescription colour_display_p3(uint32_t depth = 8) { return ColourDescription{12, 13, depth, 0.0f}; }
+inline ColourDescription colour_bt2020_pq(uint32_t depth = 10, float white_nits = 203.0f) { return ColourDescription{9, 16, depth, white_nits}; }
+// One image of integer RGB(A) code values (format: CE_PIXEL_RGB8 / RGBA8 / RGB16 / RGBA16; len in bytes) read by `colour`
+// -> packed float RGB, linear light with BT.709 / sRGB primaries, on the device
+inline std::vector<float> cicp_to_linear(const HipBackend &be, const void *pixels, size_t len, int format, const ColourDescription &colour,
+                                         uint32_t width, uint32_t height)
+{
+    std::vector<float> out((size_t)width * height * 3);
+    detail::check(be, ce_cicp_to_linear(be.ctx(), pixels, len, format, &colour, width, height, out.data(), out.size()), "cicp", width, height, len);
+    return out;
+}
+// straight into a slot of a linear batch (eval::batch_linear)
+inline void batch_set_reference_cicp(const HipBackend &be, ce_batch *batch, uint32_t ref_index, const void *pixels, size_t len, int format,
+                                     const ColourDescription &colour)
+{
+    detail::check(be, ce_batch_set_reference_cicp(batch, ref_index, pixels, len, format, &colour), "cicp", 0, 0, 0);
+}
+inline void batch_set_test_cicp(const HipBackend &be, ce_batch *batch, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len,
+                                int format, const ColourDescription &colour)
+{
+    detail::check(be, ce_batch_set_test_cicp(batch, pair_index, ref_index, pixels, len, format, &colour), "cicp", 0, 0, 0);
+}
 // straight into a slot of a resident batch (RGB8 or deep), host or device planes
 inline void batch_set_reference_yuv(const HipBackend &be, ce_batch *batch, uint32_t ref_index, const YuvImage &image)
 {
@@ -907,6 +933,28 @@ inline ce_batch *batch_deep(const HipBackend &be, uint32_t width, uint32_t heigh
     ce_batch *b = nullptr;
     const int rc = ce_batch_create_deep(be.ctx(), width, height, max_refs, max_pairs, ref_depth, test_depth, &b);
     detail::check(be, rc, "batch_deep", width, height, (size_t)width * height * 3);
+    return b;
+}
+// ---- linear input (include/ce_metrics.h: ce_batch_create_linear) --------------------------------
+// One pair of packed float RGB in linear light with BT.709 / sRGB primaries: 1.0 is the white an 8-bit 255 maps to, values
+// below 0 and above 1 are scored.  PSNR is not reported.  intensity_target is Butteraugli's: nits at 1.0.
+inline MetricResult evaluate_pair_linear(const HipBackend &be, const std::vector<float> &reference, const std::vector<float> &test,
+                                         size_t width, size_t height, const MetricConfig &config,
+                                         float intensity_target = CE_DEFAULT_INTENSITY_TARGET)
+{
+    ce_scores s{};
+    const int rc = ce_eval_pair_linear(be.ctx(), reference.data(), reference.size() * 4, test.data(), test.size() * 4, (uint32_t)width,
+                                       (uint32_t)height, config.mask(), config.flags(), intensity_target, &s);
+    detail::check(be, rc, "evaluate_pair_linear", width, height, test.size());
+    return MetricResult::from_c(s);
+}
+// A linear HBM-resident grid, filled with ce_batch_set_*_fmt(CE_PIXEL_RGB_F32) or metrics::batch_set_*_cicp and run like
+// any batch; the caller destroys it with ce_batch_destroy.
+inline ce_batch *batch_linear(const HipBackend &be, uint32_t width, uint32_t height, uint32_t max_refs, uint32_t max_pairs)
+{
+    ce_batch *b = nullptr;
+    const int rc = ce_batch_create_linear(be.ctx(), width, height, max_refs, max_pairs, &b);
+    detail::check(be, rc, "batch_linear", width, height, (size_t)width * height * 3);
     return b;
 }
 // assert_quality, helpers.rs:212-255

@@ -16,7 +16,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import (DEEP_DEPTHS, PIXEL_RGB8, PIXEL_RGB16, PIXEL_RGBA8, PIXEL_RGBA16, Batch, CodecEvalError, ColorTable, Context, DimensionMismatch, MetricCalculation,
+from . import (ColourDescription, DEEP_DEPTHS, PIXEL_RGB_F32, PIXEL_RGB8, PIXEL_RGB16, PIXEL_RGBA8, PIXEL_RGBA16, Batch, CodecEvalError, ColorTable, Context, DimensionMismatch, MetricCalculation,
                MetricConfig, MetricResult, _error_obj, estimate_batch_bytes, CE_ERR_BACKEND)
 from . import RESAMPLE_LANCZOS3
 from . import CHROMA_TRIANGLE, MEM_HOST, YUV_400, YUV_420, YUV_444, YUV_BT601, YUV_FULL, YUV_PLANAR, YUV_SEMIPLANAR, YuvImage, yuv_coefficients
@@ -25,6 +25,11 @@ from . import reports as R
 from .viewing import SimulationMode, ViewingCondition
 
 __all__ = ["ImageData", "EncodeRequest", "EvalConfig", "EvalConfigBuilder", "EvalSession", "ALPHA_BLACK_WHITE"]
+
+
+def _colour_at(colour: Optional[ColourDescription], depth: int) -> Optional[ColourDescription]:
+    """A constructor's colour= at the image's own depth (a preset names primaries and transfer; the samples say the depth)."""
+    return None if colour is None else colour.with_depth(int(depth))
 
 
 @dataclass
@@ -37,32 +42,47 @@ class ImageData:
     icc_profile: Optional[bytes] = None
     depth: int = 0  # 0: 8-bit samples in u8; 8, 10, 12 or 16: a deep image (rgb16 / rgba16), scored at its own precision
     yuv_image: Optional[YuvImage] = None  # an 8-bit decode still in its Y'CbCr planes (ImageData.yuv); `data` is then empty
+    # How the code values are to be read (H.273 primaries / transfer; its depth is this image's): None = sRGB, as ever.  A
+    # decode with a non-sRGB description is scored in linear light through a linear batch.
+    colour: Optional[ColourDescription] = None
+    linear: bool = False  # `data` is packed float32 RGB, linear light with sRGB primaries (ImageData.linear_f32)
 
     @staticmethod
-    def rgb(data, width: int, height: int) -> "ImageData":
-        return ImageData(np.ascontiguousarray(data, dtype=np.uint8).reshape(-1), int(width), int(height), 3)
+    def rgb(data, width: int, height: int, colour: Optional[ColourDescription] = None) -> "ImageData":
+        return ImageData(np.ascontiguousarray(data, dtype=np.uint8).reshape(-1), int(width), int(height), 3, colour=_colour_at(colour, 8))
 
     @staticmethod
-    def rgba(data, width: int, height: int) -> "ImageData":
-        return ImageData(np.ascontiguousarray(data, dtype=np.uint8).reshape(-1), int(width), int(height), 4)
+    def rgba(data, width: int, height: int, colour: Optional[ColourDescription] = None) -> "ImageData":
+        return ImageData(np.ascontiguousarray(data, dtype=np.uint8).reshape(-1), int(width), int(height), 4, colour=_colour_at(colour, 8))
+
+    @staticmethod
+    def linear_f32(data, width: int, height: int) -> "ImageData":
+        """Packed float32 RGB in linear light with BT.709 / sRGB primaries, 1.0 = the white an 8-bit 255 maps to; values
+        below 0 and above 1 are scored.  A session scores it through a linear batch."""
+        a = np.ascontiguousarray(data, dtype=np.float32).reshape(-1)
+        if a.size != int(width) * int(height) * 3:
+            raise ValueError(f"a linear image is width * height * 3 floats, got {a.size}")
+        return ImageData(a, int(width), int(height), 3, linear=True)
 
     @staticmethod
     def rgb_with_icc(data, width: int, height: int, icc_profile: bytes) -> "ImageData":
         return ImageData(np.ascontiguousarray(data, dtype=np.uint8).reshape(-1), int(width), int(height), 3, bytes(icc_profile))
 
     @staticmethod
-    def rgb16(data, width: int, height: int, depth: int) -> "ImageData":
+    def rgb16(data, width: int, height: int, depth: int, colour: Optional[ColourDescription] = None) -> "ImageData":
         """A decoder's PixelData::Rgb16 (crates/codec-iter/src/avif_config.rs:122-170) kept as it is: packed uint16
         samples of `depth` bits, each meaning the sRGB value v / (2^depth - 1).  A session scores it through a deep batch."""
         if depth not in DEEP_DEPTHS:
             raise ValueError(f"depth must be one of {DEEP_DEPTHS}, got {depth}")
-        return ImageData(np.ascontiguousarray(data, dtype=np.uint16).reshape(-1), int(width), int(height), 3, None, int(depth))
+        return ImageData(np.ascontiguousarray(data, dtype=np.uint16).reshape(-1), int(width), int(height), 3, None, int(depth),
+                         colour=_colour_at(colour, depth))
 
     @staticmethod
-    def rgba16(data, width: int, height: int, depth: int) -> "ImageData":
+    def rgba16(data, width: int, height: int, depth: int, colour: Optional[ColourDescription] = None) -> "ImageData":
         if depth not in DEEP_DEPTHS:
             raise ValueError(f"depth must be one of {DEEP_DEPTHS}, got {depth}")
-        return ImageData(np.ascontiguousarray(data, dtype=np.uint16).reshape(-1), int(width), int(height), 4, None, int(depth))
+        return ImageData(np.ascontiguousarray(data, dtype=np.uint16).reshape(-1), int(width), int(height), 4, None, int(depth),
+                         colour=_colour_at(colour, depth))
 
     @staticmethod
     def yuv(planes, width: int, height: int, subsampling: int = YUV_420, layout: int = YUV_PLANAR, matrix: int = YUV_BT601,
@@ -114,11 +134,18 @@ class ImageData:
     def to_rgb8_vec(self) -> np.ndarray:  # session.rs:98-117 (host copy; the session itself strips alpha on the device)
         if self.yuv_image is not None:
             return self._yuv_to_rgb8_host()
+        if self.in_linear_light:  # no reference rule turns HDR or wide-gamut content into sRGB bytes: it is scored in linear light
+            raise MetricCalculation(CE_ERR_BACKEND, "Metric calculation failed: an image in linear light or with a non-sRGB colour description has no RGB8 form")
         data = self.data if self.channels == 3 else np.ascontiguousarray(self.data.reshape(-1, 4)[:, :3]).reshape(-1)
         if self.depth:  # to_8bit's rule for any depth: what the reference does to a 10-bit decode before it measures
             maxv = (1 << self.depth) - 1
             return np.minimum((np.minimum(data, maxv).astype(np.uint64) * 255 + maxv // 2) // maxv, 255).astype(np.uint8)
         return data
+
+    @property
+    def in_linear_light(self) -> bool:
+        """Scored through a linear batch: linear float32, or code values with a description other than sRGB's."""
+        return self.linear or (self.colour is not None and not self.colour.is_srgb)
 
     @property
     def has_alpha(self) -> bool:
@@ -154,6 +181,8 @@ class ImageData:
 
     @property
     def pixel_format(self) -> int:
+        if self.linear:
+            return PIXEL_RGB_F32
         if self.depth:
             return PIXEL_RGB16 if self.channels == 3 else PIXEL_RGBA16
         return PIXEL_RGB8 if self.channels == 3 else PIXEL_RGBA8
@@ -387,14 +416,74 @@ class EvalSession:
         """Cells whose decode is 8-bit go through an RGB8 batch as ever; the cells of deep decodes (ImageData.rgb16 /
         rgba16) through one deep batch per (source depth, decode depth), the 8-bit source as depth 8, neither side rescaled."""
         kinds: Dict[Tuple[int, int], list] = {}
+        linear_group = []
         for image, report, pending in group:
             by_depth: Dict[int, list] = {}
+            lin = [cell for cell in pending if image.in_linear_light or cell[1].in_linear_light]
+            if lin:
+                linear_group.append((image, report, lin))
+                pending = [cell for cell in pending if not (image.in_linear_light or cell[1].in_linear_light)]
             for cell in pending:
                 by_depth.setdefault(cell[1].depth, []).append(cell)
             for d, cells in by_depth.items():
                 kinds.setdefault((image.depth or 8, d) if (d or image.depth) else (0, 0), []).append((image, report, cells))
         for depths, sub in kinds.items():
             self._score_cells(w, h, sub, cfg, None if depths == (0, 0) else (depths[0], depths[1] or 8))
+        if linear_group:
+            self._score_cells_linear(w, h, linear_group, cfg)
+
+    def _set_linear(self, batch: Batch, image: ImageData, ref_index: int, pair_index: Optional[int]):
+        """One image into a slot of a linear batch: float32 as it is, code values through the CICP ingest - by their own
+        description, an untagged image as sRGB (1, 13) at its own depth."""
+        def refuse(what):
+            raise MetricCalculation(CE_ERR_BACKEND, f"Metric calculation failed: linear-light scoring: {what}")
+        if image.yuv_image is not None:
+            refuse("Y'CbCr planes do not enter a linear batch (convert with yuv_to_rgb16 and tag the result)")
+        if image.colour is not None and image.icc_profile is not None:
+            refuse("an image with both a colour description and an ICC profile is not supported")
+        if image.icc_profile is not None and pair_index is not None:  # the source's own profile is not applied, as ever
+            refuse("an ICC profile is not applied in linear light")
+        if image.has_alpha and self.config.alpha_backgrounds:
+            refuse("alpha_backgrounds with a colour description is not supported")
+        if image.linear:
+            return batch.set_reference(ref_index, image.data) if pair_index is None else batch.set_test(pair_index, ref_index, image.data)
+        colour = image.colour or ColourDescription.SRGB.with_depth(image.depth or 8)
+        px = image.data.reshape(image.height, image.width, image.channels)
+        if pair_index is None:
+            batch.set_reference_cicp(ref_index, px, colour)
+        else:
+            batch.set_test_cicp(pair_index, ref_index, px, colour)
+
+    def _score_cells_linear(self, w: int, h: int, group, cfg: MetricConfig):
+        """The cells scored in linear light: one linear batch, a reference slot per image, a test slot
+        per cell; PSNR is not defined there and stays None."""
+        if self._displayed(w, h) != (w, h):
+            raise MetricCalculation(CE_ERR_BACKEND, "Metric calculation failed: linear-light scoring: simulate_viewing resamples 8-bit images only")
+        if cfg.flags & 1:  # CE_FLAG_XYB_ROUNDTRIP
+            raise MetricCalculation(CE_ERR_BACKEND, "Metric calculation failed: linear-light scoring: xyb_roundtrip is an 8-bit quantisation")
+        n_pairs = sum(len(p) for _, _, p in group)
+        batch = Batch(self.ctx, w, h, len(group), n_pairs, linear=True)
+        try:
+            rows = []
+            k = 0
+            for ri, (image, report, pending) in enumerate(group):
+                self._set_linear(batch, image, ri, None)
+                for row_index, decoded in pending:
+                    if (decoded.width, decoded.height) != (w, h):
+                        raise DimensionMismatch(1, f"Dimension mismatch: expected ({w}, {h}), got ({decoded.width}, {decoded.height})")
+                    self._set_linear(batch, decoded, ri, k)
+                    rows.append((report, row_index, k))
+                    k += 1
+            scores = batch.run(n_pairs, cfg)
+        finally:
+            batch.close()
+        for report, row_index, k in rows:
+            if scores[k].status != 0:
+                raise _error_obj(scores[k].status, self.ctx._err())
+            m = MetricResult.from_c(scores[k])
+            row = report.results[row_index]
+            row.dssim, row.ssimulacra2, row.butteraugli, row.psnr = m.dssim, m.ssimulacra2, m.butteraugli, m.psnr
+            row.perception = m.perception_level()
 
     def _score_cells(self, w: int, h: int, group, cfg: MetricConfig, depths: Optional[Tuple[int, int]]):
         # a pair whose source or decode has alpha takes one test slot per background (config.alpha_backgrounds); a source

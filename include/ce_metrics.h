@@ -303,8 +303,8 @@ int ce_batch_ssimulacra2_maps(ce_batch *b, uint32_t scale, uint32_t channel, uin
  * have their own depths - an 8-bit source against a 10-bit decode, neither rescaled; PSNR needs equal depths and with
  * unequal ones its bit stays clear in `valid` while the other metrics run.  A deep batch of depths 8 / 8 scores an image
  * bit for bit as an RGB8 batch does, and so does one of depth 16 holding v8 * 257.
- * Not part of this: linear-f32 input, PQ / HLG transfer curves, wide-gamut primaries, deep ce_ref handles, deep
- * ce_eval_batch.
+ * Not part of this: deep ce_ref handles, deep ce_eval_batch (linear-f32 input, PQ and wide-gamut primaries: linear batches,
+ * below; HLG: not offered).
  * Pixel formats of a deep batch only (their depth is that side's): packed u16 RGB / RGBA (alpha dropped). */
 enum {
     CE_PIXEL_RGB16 = 4,
@@ -577,6 +577,86 @@ int ce_composite_rgba8(ce_ctx *ctx, const uint8_t *rgba, size_t len, uint32_t w,
                        size_t out_len);
 int ce_composite_rgba16(ce_ctx *ctx, const uint16_t *rgba, size_t len, uint32_t w, uint32_t h, uint32_t depth, const uint16_t bg[3],
                         uint16_t *out, size_t out_len);
+
+/* ---- linear batches and CICP ingest: HDR and wide-gamut images -----------------------------------
+ * Every batch above reads its samples as sRGB-encoded values with BT.709 primaries.  A LINEAR batch holds linear light
+ * instead: its slabs are packed interleaved RGB float, linear light with BT.709 / sRGB primaries and D65 white, 1.0 the
+ * white an 8-bit 255 maps to; values below 0 (colours outside the sRGB gamut) and above 1 (highlights) are legal and are
+ * scored.  On ingest NaN becomes 0 and every sample is clamped to [-CE_LINEAR_MAX, CE_LINEAR_MAX] (PQ's 10 000 nits at an
+ * 80-nit white is 125).  Slot k of a slab starts at byte k * width * height * 12 (ce_batch_reference_slab /
+ * ce_batch_test_slab; one copy of the image per slot, read by every metric).
+ * SSIMULACRA2, DSSIM and Butteraugli take the sample as their level-0 linear value, with no table; everything behind that
+ * - the diffmap, DSSIM's SSIM maps, CE_FLAG_SSIMULACRA2_MAPS included - is the code every batch runs, so a linear batch
+ * loaded with ce_srgb_table(8, 0)[v] scores SSIMULACRA2 and Butteraugli bit for bit as the RGB8 batch of the bytes v does,
+ * and one loaded with ce_srgb_table(8, 1)[v] DSSIM.  PSNR has no integer grid here: its bit stays clear in `valid` and the
+ * other metrics run.  Butteraugli's intensity_target keeps its meaning: nits at 1.0.
+ * On a linear batch
+ *   ce_batch_set_reference_fmt / ce_batch_set_test_fmt take CE_PIXEL_RGB_F32 only (len = width * height * 12);
+ *   ce_batch_set_reference_cicp / ce_batch_set_test_cicp take tagged integer code values (below);
+ *   ce_batch_bind_pair, ce_batch_run, ce_batch_launch, ce_batch_collect, ce_batch_butteraugli_pnorm3 and the three map
+ *     readers work as on any batch;
+ *   CE_ERR_INVALID_ARG, with the reason in ce_last_error and the batch still usable: CE_FLAG_XYB_ROUNDTRIP,
+ *     ce_batch_image_heuristics, ce_batch_set_*_lut with a table, ce_batch_set_reference / ce_batch_set_test and every
+ *     8- / 16-bit format (the *_10BIT ones included) through *_fmt, ce_batch_resample* from or into it, *_over, *_yuv.
+ *   CE_PIXEL_RGB_F32 on a batch that is not linear is refused the same way.
+ * Not part of this: HLG (its OOTF couples the channels and needs a device powf), the BT.709 / BT.1886 gamma transfers,
+ * primaries with a non-D65 white, limited-range RGB, ce_ref_* handles on linear batches and the pooled ce_eval_batch on
+ * them, Y'CbCr straight into a linear batch (chain ce_yuv_to_rgb16 into *_cicp).
+ * (No reference item: the reference scores every PixelData variant only after to_8bit / to_rgb8_vec.) */
+enum {
+    CE_PIXEL_RGB_F32 = 7 /* packed float RGB, 12 bytes per pixel: linear batches only (6 is not a format) */
+};
+#define CE_LINEAR_MAX 1024.0f
+int ce_batch_create_linear(ce_ctx *ctx, uint32_t width, uint32_t height, uint32_t max_refs, uint32_t max_pairs, ce_batch **out);
+/* ce_estimate_batch_bytes for a linear batch */
+size_t ce_estimate_batch_bytes_linear(uint32_t width, uint32_t height, uint32_t n_refs, uint32_t n_pairs, uint32_t metric_mask);
+/* ce_eval_pair over packed float RGB (lengths in bytes: width * height * 12); the same error kinds in the same order,
+ * CE_ERR_INVALID_ARG for CE_FLAG_XYB_ROUNDTRIP or a map flag */
+int ce_eval_pair_linear(ce_ctx *ctx, const float *reference, size_t reference_len, const float *test, size_t test_len, uint32_t width,
+                        uint32_t height, uint32_t metric_mask, uint32_t flags, float intensity_target, ce_scores *out);
+/* The library's own sRGB -> linear table of `depth` bits (8, 10, 12 or 16; n = 2^depth entries): rule 0 the f64 curve
+ * rounded once to f32 (SSIMULACRA2, Butteraugli), rule 1 f32 powf (DSSIM, src/metrics/dssim.rs:78-85) - exactly the floats
+ * the RGB8 and deep batches read.  A pure host function. */
+int ce_srgb_table(uint32_t depth, int rule, float *out, size_t n);
+
+/* CICP ingest: integer RGB code values tagged with ITU-T H.273 code points -> a slot of a linear batch, on the device.
+ *   primaries  1 BT.709 (x, y: R 0.640 0.330, G 0.300 0.600, B 0.150 0.060), 9 BT.2020 (R 0.708 0.292, G 0.170 0.797,
+ *              B 0.131 0.046), 12 Display P3 (R 0.680 0.320, G 0.265 0.690, B 0.150 0.060); white D65 (0.3127, 0.3290) each
+ *   transfer   13 sRGB; 8 linear: v / maxv; 16 PQ (SMPTE ST 2084): nits / white_nits with white_nits > 0 (203 is the usual
+ *              suggestion; pass Butteraugli's intensity target to keep absolute nits)
+ *   depth      8, 10, 12 or 16; maxv = 2^depth - 1; 8-bit formats require depth 8
+ * Definition, per pixel of a CE_PIXEL_RGB8 / RGBA8 / RGB16 / RGBA16 image (alpha dropped, as to_rgb8_vec drops it):
+ *   1. t = table[min(v, maxv)] per channel.  The table is built on the host in f64 per code point e = v / maxv and rounded
+ *      once to f32; the curve is never evaluated on the device.  sRGB: exactly ce_srgb_table(depth, 0).  PQ, with
+ *      m1 = 2610/16384, m2 = 2523/4096 * 128, c1 = 3424/4096, c2 = 2413/4096 * 32, c3 = 2392/4096 * 32:
+ *      p = e^(1/m2), nits = 10000 * (max(p - c1, 0) / (c2 - c3 p))^(1/m1), t = nits / white_nits.
+ *   2. primaries 1: nothing further, the result is the table value bit for bit.
+ *   3. otherwise o_i = (M[i][0] * r + M[i][1] * g) + M[i][2] * b in f32, every product and sum rounded separately (no
+ *      fused multiply-add), with M = inv(XYZ <- sRGB) * (XYZ <- src) built on the host in f64 from the chromaticities above
+ *      and rounded once to f32 (ce_colour_matrix, row-major).
+ *   4. the clamp of a linear image: NaN -> 0, then [-CE_LINEAR_MAX, CE_LINEAR_MAX].
+ * tests/cicp_restatement.py restates this in numpy; the device equals it bit for bit. */
+typedef struct ce_colour {
+    int primaries;     /* H.273 ColourPrimaries: 1, 9 or 12 */
+    int transfer;      /* H.273 TransferCharacteristics: 13, 8 or 16 */
+    uint32_t depth;    /* 8, 10, 12 or 16; samples above 2^depth - 1 are clamped */
+    float white_nits;  /* PQ only: the luminance that becomes 1.0 */
+} ce_colour;
+/* One image of the batch's shape into a reference / test slot of a LINEAR batch, on the same stream and with the same
+ * staging and ordering as ce_batch_set_*_fmt; the pixels are consumed on return.  CE_ERR_INVALID_ARG, with the reason in
+ * ce_last_error and the batch still usable, for a batch that is not linear, a null pointer, another format, a depth,
+ * primaries or transfer outside the lists above, an 8-bit format with depth != 8, PQ without white_nits > 0;
+ * CE_ERR_BAD_LENGTH for a wrong len. */
+int ce_batch_set_reference_cicp(ce_batch *b, uint32_t ref_index, const void *pixels, size_t len, int format, const ce_colour *c);
+int ce_batch_set_test_cicp(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format,
+                           const ce_colour *c);
+/* One image of w x h to packed float RGB in host memory (out_len = w * h * 3 floats).  Errors as above. */
+int ce_cicp_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_colour *c, uint32_t w, uint32_t h, float *out,
+                      size_t out_len);
+/* The ingest's transfer table (n = 2^depth entries; white_nits is read for PQ only) and its primaries matrix (row-major;
+ * primaries 1: the identity).  Pure host functions; CE_ERR_INVALID_ARG for a code point outside the lists above. */
+int ce_transfer_table(int transfer, uint32_t depth, float white_nits, float *out, size_t n);
+int ce_colour_matrix(int primaries, float out[9]);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------ */
 /* Bracket every kernel launch with a HIP event pair, recorded on the stream the kernel is launched on,
