@@ -543,6 +543,16 @@ impl HipMetrics {
         self.check(rc, width, height, out.len())?;
         Ok(out)
     }
+
+    /// `ce_yuv_to_linear`: one image's planes read by the colour description `colour` (H.273 primaries / transfer, the depth
+    /// of the integer RGB grid, PQ's white) -> packed f32 RGB, linear light with sRGB primaries, in one kernel.
+    pub fn yuv_to_linear(&mut self, image: &YuvPlanes<'_>, colour: &sys::ce_colour, width: u32, height: u32) -> Result<Vec<f32>, HipError> {
+        let c = image.to_sys(width, height)?;
+        let mut out = vec![0f32; width as usize * height as usize * 3];
+        let rc = unsafe { sys::ce_yuv_to_linear(self.ctx, &c, colour, width, height, out.as_mut_ptr(), out.len()) };
+        self.check(rc, width, height, out.len())?;
+        Ok(out)
+    }
 }
 
 /// `ce_batch`: images of one shape resident on the device, scored in one launch.  Resampling one grid into another
@@ -605,6 +615,21 @@ impl HipBatch<'_> {
     pub fn set_test_yuv(&mut self, pair_index: u32, ref_index: u32, image: &YuvPlanes<'_>) -> Result<(), HipError> {
         let c = image.to_sys(self.width, self.height)?;
         let rc = unsafe { sys::ce_batch_set_test_yuv(self.handle, pair_index, ref_index, &c) };
+        self.check(rc, 0)
+    }
+
+    /// `ce_batch_set_reference_yuv_cicp`: a decoder's planes read by `colour` into a reference slot of a LINEAR batch.
+    pub fn set_reference_yuv_cicp(&mut self, ref_index: u32, image: &YuvPlanes<'_>, colour: &sys::ce_colour) -> Result<(), HipError> {
+        let c = image.to_sys(self.width, self.height)?;
+        let rc = unsafe { sys::ce_batch_set_reference_yuv_cicp(self.handle, ref_index, &c, colour) };
+        self.check(rc, 0)
+    }
+
+    /// `ce_batch_set_test_yuv_cicp`: the same for the test image of pair `pair_index`, bound to reference `ref_index`.
+    pub fn set_test_yuv_cicp(&mut self, pair_index: u32, ref_index: u32, image: &YuvPlanes<'_>, colour: &sys::ce_colour)
+                             -> Result<(), HipError> {
+        let c = image.to_sys(self.width, self.height)?;
+        let rc = unsafe { sys::ce_batch_set_test_yuv_cicp(self.handle, pair_index, ref_index, &c, colour) };
         self.check(rc, 0)
     }
 

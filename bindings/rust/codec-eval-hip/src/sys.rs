@@ -279,6 +279,11 @@ extern "C" {
     pub fn ce_yuv_to_rgb8(ctx: *mut ce_ctx, image: *const ce_yuv_image, width: u32, height: u32, out: *mut u8, out_len: usize) -> c_int;
     pub fn ce_yuv_to_rgb16(ctx: *mut ce_ctx, image: *const ce_yuv_image, width: u32, height: u32, depth_out: u32, out: *mut u16,
                            out_len: usize) -> c_int;
+    pub fn ce_batch_set_reference_yuv_cicp(b: *mut ce_batch, ref_index: u32, image: *const ce_yuv_image, c: *const ce_colour) -> c_int;
+    pub fn ce_batch_set_test_yuv_cicp(b: *mut ce_batch, pair_index: u32, ref_index: u32, image: *const ce_yuv_image,
+                                      c: *const ce_colour) -> c_int;
+    pub fn ce_yuv_to_linear(ctx: *mut ce_ctx, image: *const ce_yuv_image, c: *const ce_colour, width: u32, height: u32, out: *mut c_float,
+                            out_len: usize) -> c_int;
     pub fn ce_batch_set_reference_over(b: *mut ce_batch, first_ref: u32, pixels: *const c_void, len: usize, format: c_int, n_bg: u32,
                                        backgrounds: *const u16) -> c_int;
     pub fn ce_batch_set_test_over(b: *mut ce_batch, first_pair: u32, ref_indices: *const u32, pixels: *const c_void, len: usize,

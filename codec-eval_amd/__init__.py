@@ -245,6 +245,9 @@ _PROTOTYPES = [
     ("ce_batch_set_test_yuv", _i, [_vp, _u32, _u32, C.POINTER(CeYuvImage)]),
     ("ce_yuv_to_rgb8", _i, [_vp, C.POINTER(CeYuvImage), _u32, _u32, _vp, _sz]),
     ("ce_yuv_to_rgb16", _i, [_vp, C.POINTER(CeYuvImage), _u32, _u32, _u32, _vp, _sz]),
+    ("ce_batch_set_reference_yuv_cicp", _i, [_vp, _u32, C.POINTER(CeYuvImage), C.POINTER(CeColour)]),
+    ("ce_batch_set_test_yuv_cicp", _i, [_vp, _u32, _u32, C.POINTER(CeYuvImage), C.POINTER(CeColour)]),
+    ("ce_yuv_to_linear", _i, [_vp, C.POINTER(CeYuvImage), C.POINTER(CeColour), _u32, _u32, _vp, _sz]),
     ("ce_batch_set_reference_over", _i, [_vp, _u32, _vp, _sz, _i, _u32, _vp]),
     ("ce_batch_set_test_over", _i, [_vp, _u32, _vp, _vp, _sz, _i, _u32, _vp]),
     ("ce_composite_rgba8", _i, [_vp, _vp, _sz, _u32, _u32, _vp, _vp, _sz]),
@@ -912,6 +915,15 @@ class Context:
         self._check(lib().ce_yuv_to_rgb16(self._h, C.byref(c), width, height, depth_out, out.ctypes.data, out.size))
         return out
 
+    def yuv_to_linear(self, image: "YuvImage", width: int, height: int, colour: "ColourDescription") -> np.ndarray:
+        """A decoder's Y'CbCr planes read by `colour` -> (height, width, 3) float32 linear light with sRGB primaries, in one
+        kernel (ce_yuv_to_linear): yuv_to_rgb16 at depth_out = colour.depth followed by cicp_to_linear, bit for bit."""
+        c, _keep = image._c()
+        col = colour._c()
+        out = np.empty((height, width, 3), np.float32)
+        self._check(lib().ce_yuv_to_linear(self._h, C.byref(c), C.byref(col), width, height, out.ctypes.data, out.size))
+        return out
+
     def composite_rgba8(self, rgba, width: int, height: int, background: Sequence[int]) -> np.ndarray:
         """Straight-alpha RGBA8 source-over onto the opaque 8-bit colour `background` -> (height, width, 3) uint8, on the
         device (ce_composite_rgba8; the definition is in include/ce_metrics.h)."""
@@ -1155,6 +1167,18 @@ class Batch:
     def set_test_yuv(self, pair_index: int, ref_index: int, image: "YuvImage"):
         c, _keep = image._c()
         self.ctx._check(lib().ce_batch_set_test_yuv(self._h, pair_index, ref_index, C.byref(c)))
+        self._pair_ref[pair_index] = ref_index
+
+    # the same planes with a colour description -> linear light in one kernel, into a slot of a linear batch
+    def set_reference_yuv_cicp(self, ref_index: int, image: "YuvImage", colour: "ColourDescription"):
+        c, _keep = image._c()
+        col = colour._c()
+        self.ctx._check(lib().ce_batch_set_reference_yuv_cicp(self._h, ref_index, C.byref(c), C.byref(col)))
+
+    def set_test_yuv_cicp(self, pair_index: int, ref_index: int, image: "YuvImage", colour: "ColourDescription"):
+        c, _keep = image._c()
+        col = colour._c()
+        self.ctx._check(lib().ce_batch_set_test_yuv_cicp(self._h, pair_index, ref_index, C.byref(c), C.byref(col)))
         self._pair_ref[pair_index] = ref_index
 
     # a transparent image composited over solid colours on the device: one upload fills len(backgrounds) consecutive slots

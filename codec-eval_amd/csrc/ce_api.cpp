@@ -1565,23 +1565,26 @@ struct cicp_plan {
     float m[9];
 };
 
-int cicp_check(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_colour *c, size_t n_px, cicp_plan *plan)
+// the colour description alone: depth, transfer and primaries from the lists of the header; fills maxv and the matrix
+int cicp_colour_check(ce_ctx *ctx, const ce_colour *c, cicp_plan *plan)
 {
-    if (!pixels || !c) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: null pointer");
-    const bool fmt8 = format == CE_PIXEL_RGB8 || format == CE_PIXEL_RGBA8, fmt16 = format == CE_PIXEL_RGB16 || format == CE_PIXEL_RGBA16;
-    if (!fmt8 && !fmt16) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: format must be CE_PIXEL_RGB8, RGBA8, RGB16 or RGBA16");
     if (!deep_depth_ok(c->depth)) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: depth must be 8, 10, 12 or 16, got " + std::to_string(c->depth));
-    if (fmt8 && c->depth != 8) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: an 8-bit format needs depth 8, got " + std::to_string(c->depth));
     if (c->transfer != 13 && c->transfer != 8 && c->transfer != 16)
         return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: transfer must be 13 (sRGB), 8 (linear) or 16 (PQ), got " + std::to_string(c->transfer));
     if (c->transfer == 16 && !(c->white_nits > 0.0f && std::isfinite(c->white_nits)))
         return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: PQ needs white_nits > 0");
     if (!ce_build_colour_matrix(c->primaries, plan->m))
         return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: primaries must be 1 (BT.709), 9 (BT.2020) or 12 (Display P3), got " + std::to_string(c->primaries));
-    if (len != n_px * ce_pixel_bytes(format)) return bad_length(ctx, n_px * ce_pixel_bytes(format), len);
     plan->has_matrix = c->primaries != 1;
     plan->maxv = (1u << c->depth) - 1u;
-    // the table on the device, built once per context and (transfer, depth, white) and kept; white only matters to PQ
+    plan->d_table = nullptr;
+    return CE_OK;
+}
+
+// the table of a checked description on the device, built once per context and (transfer, depth, white) and kept; white
+// only matters to PQ
+int cicp_table(ce_ctx *ctx, const ce_colour *c, cicp_plan *plan)
+{
     const float white = c->transfer == 16 ? c->white_nits : 0.0f;
     uint32_t white_bits;
     std::memcpy(&white_bits, &white, 4);
@@ -1601,6 +1604,18 @@ int cicp_check(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce
     }
     plan->d_table = it->second;
     return CE_OK;
+}
+
+int cicp_check(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_colour *c, size_t n_px, cicp_plan *plan)
+{
+    if (!pixels || !c) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: null pointer");
+    const bool fmt8 = format == CE_PIXEL_RGB8 || format == CE_PIXEL_RGBA8, fmt16 = format == CE_PIXEL_RGB16 || format == CE_PIXEL_RGBA16;
+    if (!fmt8 && !fmt16) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: format must be CE_PIXEL_RGB8, RGBA8, RGB16 or RGBA16");
+    if (fmt8 && deep_depth_ok(c->depth) && c->depth != 8)
+        return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: an 8-bit format needs depth 8, got " + std::to_string(c->depth));
+    if (int rc = cicp_colour_check(ctx, c, plan)) return rc;
+    if (len != n_px * ce_pixel_bytes(format)) return bad_length(ctx, n_px * ce_pixel_bytes(format), len);
+    return cicp_table(ctx, c, plan);
 }
 
 // one tagged image through the wide staging pair of upload_fmt into the slot at dst, on the batch's upload stream
@@ -1982,16 +1997,27 @@ static void yuv_pack(const ce_yuv_image *img, yuv_plan *plan, uint8_t *h_stage, 
     }
 }
 
+// the conversion of one checked image into dst: integer RGB (u8, or u16 of `depth`), or with `lin` the fused linear-light
+// ingest of a linear batch (yuv_cicp.hip), whose integer grid is the one plan.dev.k was built for
+static int launch_yuv_into(ce_ctx *ctx, hipStream_t stream, const yuv_plan &plan, uint32_t w, uint32_t h, uint8_t *dst, uint32_t depth,
+                           const cicp_plan *lin)
+{
+    if (lin)
+        return ce_launch_yuv_cicp(ctx, stream, plan.dev, w, h, reinterpret_cast<float *>(dst), lin->d_table, lin->maxv, lin->has_matrix ? lin->m : nullptr);
+    return ce_launch_yuv(ctx, stream, plan.dev, w, h, dst, depth != 0, depth ? depth : 8);
+}
+
 // one Y'CbCr image into a slab slot on the batch's upload stream: device planes are read in place, host planes go
-// through the wide staging pair of upload_fmt (8 bytes per pixel: the packed planes are at most 6 and a few bytes)
-static int upload_yuv(ce_batch *b, uint8_t *dst, const ce_yuv_image *img, yuv_plan &plan, uint32_t depth)
+// through the wide staging pair of upload_fmt (8 bytes per pixel, 12 on a linear batch: the packed planes are at most 6 and
+// a few bytes)
+static int upload_yuv(ce_batch *b, uint8_t *dst, const ce_yuv_image *img, yuv_plan &plan, uint32_t depth, const cicp_plan *lin = nullptr)
 {
     ce_ctx *ctx = b->ctx;
     const size_t n_px = (size_t)b->w * b->h;
     CE_HIP(ctx, hipSetDevice(ctx->device));
     if (img->memory == CE_MEM_DEVICE) {
         if (int rc = order_write(b, false)) return rc;
-        if (int rc = ce_launch_yuv(ctx, b->up_stream, plan.dev, b->w, b->h, dst, depth != 0, depth ? depth : 8)) return rc;
+        if (int rc = launch_yuv_into(ctx, b->up_stream, plan, b->w, b->h, dst, depth, lin)) return rc;
         b->uploads_pending = true;
         return CE_OK;
     }
@@ -1999,22 +2025,23 @@ static int upload_yuv(ce_batch *b, uint8_t *dst, const ce_yuv_image *img, yuv_pl
     const int k = b->next_wide;
     b->next_wide ^= 1;
     if (!b->h_wide[k]) {
-        CE_HIP(ctx, hipHostMalloc((void **)&b->h_wide[k], n_px * 8, hipHostMallocDefault));
-        CE_HIP(ctx, hipMalloc((void **)&b->d_wide[k], n_px * 8));
+        const size_t cap = n_px * (b->linear ? 12 : 8);  // wide_stage's size: the pair is shared with *_fmt and *_cicp
+        CE_HIP(ctx, hipHostMalloc((void **)&b->h_wide[k], cap, hipHostMallocDefault));
+        CE_HIP(ctx, hipMalloc((void **)&b->d_wide[k], cap));
         CE_HIP(ctx, hipEventCreateWithFlags(&b->ev_wide[k], hipEventDisableTiming));
     }
     if (int rc = order_write(b, false)) return rc;
     if (b->wide_busy[k]) CE_HIP(ctx, hipEventSynchronize(b->ev_wide[k]));
     yuv_pack(img, &plan, b->h_wide[k], b->d_wide[k]);
     CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], plan.total, hipMemcpyHostToDevice, b->up_stream));
-    if (int rc = ce_launch_yuv(ctx, b->up_stream, plan.dev, b->w, b->h, dst, depth != 0, depth ? depth : 8)) return rc;
+    if (int rc = launch_yuv_into(ctx, b->up_stream, plan, b->w, b->h, dst, depth, lin)) return rc;
     CE_HIP(ctx, hipEventRecord(b->ev_wide[k], b->up_stream));
     b->wide_busy[k] = true;
     b->uploads_pending = true;
     return CE_OK;
 }
 
-static const char *const kYuvLinear = "Y'CbCr ingest writes integer RGB: for a linear batch chain ce_yuv_to_rgb16 into ce_batch_set_*_cicp";
+static const char *const kYuvLinear = "Y'CbCr ingest writes integer RGB: a linear batch takes planes through ce_batch_set_*_yuv_cicp";
 
 int ce_batch_set_reference_yuv(ce_batch *b, uint32_t ref_index, const ce_yuv_image *image)
 {
@@ -2074,6 +2101,74 @@ int ce_yuv_to_rgb16(ce_ctx *ctx, const ce_yuv_image *image, uint32_t width, uint
                     size_t out_len)
 {
     return yuv_to_host(ctx, image, width, height, true, depth_out, out, out_len);
+}
+
+// ---- Y'CbCr planes with a CICP description into a linear batch (yuv_cicp.hip) ----------------
+
+// everything *_yuv refuses about the image and *_cicp about the description, and their one joint rule: the integer RGB
+// grid between the two halves (c->depth) is no coarser than the samples
+static int yuv_cicp_check(ce_ctx *ctx, const ce_yuv_image *img, const ce_colour *c, uint32_t w, uint32_t h, yuv_plan *plan, cicp_plan *lin)
+{
+    if (!img) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: null image");
+    if (!c) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: null pointer");
+    if (int rc = cicp_colour_check(ctx, c, lin)) return rc;
+    if (int rc = yuv_check(ctx, img, w, h, c->depth, plan)) return rc;
+    if (c->depth < (uint32_t)img->depth)
+        return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr CICP ingest: the colour description's depth " + std::to_string(c->depth) +
+                                                 " is under the samples' " + std::to_string(img->depth) + " bits");
+    return cicp_table(ctx, c, lin);
+}
+
+static const char *const kYuvCicpWantsLinear =
+    "Y'CbCr CICP ingest writes linear light: it needs a linear batch (ce_batch_create_linear); ce_batch_set_*_yuv serves the others";
+
+int ce_batch_set_reference_yuv_cicp(ce_batch *b, uint32_t ref_index, const ce_yuv_image *image, const ce_colour *c)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    if (!b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kYuvCicpWantsLinear);
+    if (ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "ref_index out of range");
+    yuv_plan plan;
+    cicp_plan lin;
+    if (int rc = yuv_cicp_check(b->ctx, image, c, b->w, b->h, &plan, &lin)) return rc;
+    invalidate_reference_state(b);
+    return upload_yuv(b, b->d_refs + (size_t)ref_index * b->img_bytes, image, plan, 0, &lin);
+}
+
+int ce_batch_set_test_yuv_cicp(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const ce_yuv_image *image, const ce_colour *c)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    if (!b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kYuvCicpWantsLinear);
+    if (pair_index >= b->max_pairs || ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "pair/ref index out of range");
+    yuv_plan plan;
+    cicp_plan lin;
+    if (int rc = yuv_cicp_check(b->ctx, image, c, b->w, b->h, &plan, &lin)) return rc;
+    if (int rc = ce_batch_bind_pair(b, pair_index, ref_index)) return rc;
+    return upload_yuv(b, b->d_tests + (size_t)pair_index * b->img_bytes, image, plan, 0, &lin);
+}
+
+// one image -> packed f32 RGB in host memory through the leaf scratch, on the context's stream (as yuv_to_host)
+int ce_yuv_to_linear(ce_ctx *ctx, const ce_yuv_image *image, const ce_colour *c, uint32_t w, uint32_t h, float *out, size_t out_len)
+{
+    if (!ctx) return CE_ERR_INVALID_ARG;
+    if (!out) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: null output");
+    if (w == 0 || h == 0) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: empty image");
+    yuv_plan plan;
+    cicp_plan lin;
+    if (int rc = yuv_cicp_check(ctx, image, c, w, h, &plan, &lin)) return rc;
+    const size_t samples = (size_t)w * h * 3, out_bytes = samples * sizeof(float);
+    if (out_len != samples)
+        return fail(ctx, CE_ERR_BAD_LENGTH, "Y'CbCr CICP ingest: out_len must be " + std::to_string(samples) + " floats, got " + std::to_string(out_len));
+    const bool host = image->memory == CE_MEM_HOST;
+    if (int rc = leaf_scratch(ctx, host ? plan.total : 1, out_bytes)) return rc;
+    if (host) {
+        yuv_pack(image, &plan, ctx->leaf_h, ctx->leaf_d_in);
+        CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_d_in, ctx->leaf_h, plan.total, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (int rc = launch_yuv_into(ctx, ctx->stream, plan, w, h, ctx->leaf_d_out, 0, &lin)) return rc;
+    CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_h, ctx->leaf_d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(out, ctx->leaf_h, out_bytes);
+    return CE_OK;
 }
 
 // ---- alpha: composited over solid backgrounds (alpha.hip) ----------------------------------------

@@ -404,6 +404,11 @@ int ce_launch_linear_sanitise(ce_ctx *ctx, hipStream_t stream, const float *d_sr
 int ce_launch_cicp(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, float *d_dst, size_t n_pixels, const float *d_table,
                    uint32_t maxv, const float *matrix);
 
+// w x h pixels of `src`, whose k was built for depth_out = log2(maxv + 1), -> packed f32 RGB at d_dst: ce_launch_yuv's integer
+// RGB in [0, maxv] handed pixel by pixel to ce_launch_cicp's table, matrix (nullptr: none) and clamp, one launch (yuv_cicp.hip)
+int ce_launch_yuv_cicp(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32_t w, uint32_t h, float *d_dst, const float *d_table,
+                       uint32_t maxv, const float *matrix);
+
 // host-side constant builders (ce_tables.cpp)
 // the CICP ingest's transfer table (include/ce_metrics.h: ce_transfer_table) and primaries matrix (ce_colour_matrix); false
 // for a code point that is not offered

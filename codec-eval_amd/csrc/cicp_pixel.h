@@ -1,0 +1,45 @@
+// One pixel of the CICP ingest (cicp_kernel.h: k_cicp; yuv_cicp_kernel.h: k_yuv_cicp): the arguments, the clamp of a linear
+// image and the table gather with the separately rounded f32 matrix, apart from the kernels so that a file that needs the
+// pixel does not emit them.  Host-compilable like the headers that include it, and compiled with -ffp-contract=off.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+#include "ce_metrics.h"
+
+namespace {
+
+struct cicp_args {
+    const void *src;     // packed RGB / RGBA, u8 or u16 samples, 16-byte aligned
+    float *dst;          // the slot: packed f32 RGB, 4-byte aligned (16 where the slot's offset allows)
+    size_t n_pixels;
+    const float *table;  // maxv + 1 entries
+    uint32_t maxv;
+    float m[9];          // row-major; unused without MATRIX
+};
+
+// a linear image's sample: NaN -> 0, then the clamp to [-CE_LINEAR_MAX, CE_LINEAR_MAX]
+__device__ __forceinline__ float linear_clamp(float v)
+{
+    if (v != v) return 0.0f;
+    return v > CE_LINEAR_MAX ? CE_LINEAR_MAX : (v < -CE_LINEAR_MAX ? -CE_LINEAR_MAX : v);
+}
+
+template <bool MATRIX>
+__device__ __forceinline__ void cicp_pixel(const cicp_args &a, uint32_t r, uint32_t g, uint32_t b, float (&o)[3])
+{
+    const float tr = a.table[r < a.maxv ? r : a.maxv], tg = a.table[g < a.maxv ? g : a.maxv], tb = a.table[b < a.maxv ? b : a.maxv];
+    if constexpr (MATRIX) {
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            const float p0 = a.m[3 * i] * tr, p1 = a.m[3 * i + 1] * tg, p2 = a.m[3 * i + 2] * tb;
+            const float s01 = p0 + p1;
+            o[i] = linear_clamp(s01 + p2);
+        }
+    } else {
+        o[0] = linear_clamp(tr), o[1] = linear_clamp(tg), o[2] = linear_clamp(tb);
+    }
+}
+
+}  // namespace

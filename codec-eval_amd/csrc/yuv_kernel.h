@@ -1,6 +1,7 @@
 // The device code of the Y'CbCr ingest (yuv.hip), kept free of anything but the HIP keywords, min / max, uint2 / uint4 and
 // blockIdx / threadIdx, so that tests/cpp/yuv_kernel_host.cpp can compile the same text for the host - thread and block
-// indices as loop variables - and run it under the host sanitizers against planes allocated at exactly their size.
+// indices as loop variables - and run it under the host sanitizers against planes allocated at exactly their size.  Its
+// loads, upsampling and matrix (yuv_block, yuv_matrix_px) also serve the fused linear-light ingest, yuv_cicp_kernel.h.
 #pragma once
 
 #include <cstddef>
@@ -95,23 +96,17 @@ __device__ __forceinline__ void ld_luma(const yuv_args &a, uint32_t y, uint32_t 
 
 __device__ __forceinline__ uint32_t clamp_m(int64_t v, int64_t m) { return (uint32_t)(v < 0 ? 0 : v > m ? m : v); }
 
-// BPS: bytes per input sample; OUT16: u16 output (a deep batch); SUB: enum ce_yuv_subsampling; SEMI: interleaved CbCr
-template <int BPS, bool OUT16, int SUB, bool SEMI>
-__global__ __launch_bounds__(64) void k_yuv(const yuv_args a, uint8_t *__restrict__ dst)
+// The block of group (gx, gy) before the matrix: its 2 x 8 luma samples and its chroma at full resolution (the upsampling of
+// include/ce_metrics.h).  Every load goes through ld_luma / ld_chroma, whose clamped indices keep it inside the planes.
+// Shared by k_yuv and k_yuv_cicp (yuv_cicp_kernel.h).
+template <int BPS, int SUB, bool SEMI>
+__device__ __forceinline__ void yuv_block(const yuv_args &a, uint32_t gx, uint32_t gy, int (&Y)[2][8], int (&CB)[2][8], int (&CR)[2][8])
 {
-    const uint32_t gw = (a.w + 7) / 8, gh = (a.h + 1) / 2;
-    const size_t tid = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (tid >= (size_t)gw * gh) return;
-    const uint32_t gy = (uint32_t)(tid / gw), gx = (uint32_t)(tid - (size_t)gy * gw);
     const uint32_t x0 = gx * 8, y0 = gy * 2;
     const uint32_t y1 = min(y0 + 1, a.h - 1);  // odd height: the second row repeats the first's loads and is not stored
-
-    int Y[2][8];
     ld_luma<BPS>(a, y0, x0, Y[0]);
     ld_luma<BPS>(a, y1, x0, Y[1]);
 
-    // full-resolution chroma of the block, minus c0
-    int CB[2][8], CR[2][8];
     if (SUB == CE_YUV_400) {
 #pragma unroll
         for (int j = 0; j < 2; j++)
@@ -158,6 +153,30 @@ __global__ __launch_bounds__(64) void k_yuv(const yuv_args a, uint8_t *__restric
             }
         }
     }
+}
+
+// one pixel through the fixed-point matrix: R, G, B in [0, a.m]
+__device__ __forceinline__ void yuv_matrix_px(const yuv_args &a, int y, int cb, int cr, uint32_t &r, uint32_t &g, uint32_t &b)
+{
+    const int64_t yy = a.ky * ((int64_t)y - a.y0) + 32768;
+    const int64_t u = (int64_t)cb - a.c0, v = (int64_t)cr - a.c0;
+    r = clamp_m((yy + a.krv * v) >> 16, a.m);
+    g = clamp_m((yy - a.kgu * u - a.kgv * v) >> 16, a.m);
+    b = clamp_m((yy + a.kbu * u) >> 16, a.m);
+}
+
+// BPS: bytes per input sample; OUT16: u16 output (a deep batch); SUB: enum ce_yuv_subsampling; SEMI: interleaved CbCr
+template <int BPS, bool OUT16, int SUB, bool SEMI>
+__global__ __launch_bounds__(64) void k_yuv(const yuv_args a, uint8_t *__restrict__ dst)
+{
+    const uint32_t gw = (a.w + 7) / 8, gh = (a.h + 1) / 2;
+    const size_t tid = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (tid >= (size_t)gw * gh) return;
+    const uint32_t gy = (uint32_t)(tid / gw), gx = (uint32_t)(tid - (size_t)gy * gw);
+    const uint32_t x0 = gx * 8, y0 = gy * 2;
+
+    int Y[2][8], CB[2][8], CR[2][8];
+    yuv_block<BPS, SUB, SEMI>(a, gx, gy, Y, CB, CR);
 
     constexpr int OB = OUT16 ? 2 : 1;        // bytes per output sample
     constexpr int NW = 24 * OB / 4;          // dwords per block row
@@ -166,13 +185,7 @@ __global__ __launch_bounds__(64) void k_yuv(const yuv_args a, uint8_t *__restric
     for (int j = 0; j < 2; j++) {
         uint32_t smp[24];
 #pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const int64_t yy = a.ky * ((int64_t)Y[j][k] - a.y0) + 32768;
-            const int64_t u = (int64_t)CB[j][k] - a.c0, v = (int64_t)CR[j][k] - a.c0;
-            smp[3 * k] = clamp_m((yy + a.krv * v) >> 16, a.m);
-            smp[3 * k + 1] = clamp_m((yy - a.kgu * u - a.kgv * v) >> 16, a.m);
-            smp[3 * k + 2] = clamp_m((yy + a.kbu * u) >> 16, a.m);
-        }
+        for (int k = 0; k < 8; k++) yuv_matrix_px(a, Y[j][k], CB[j][k], CR[j][k], smp[3 * k], smp[3 * k + 1], smp[3 * k + 2]);
         const uint32_t y = y0 + j;
         if (y >= a.h) break;
         uint8_t *p = dst + ((size_t)y * a.w + x0) * (3 * OB);

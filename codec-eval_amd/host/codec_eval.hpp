@@ -452,6 +452,24 @@ inline void batch_set_test_cicp(const HipBackend &be, ce_batch *batch, uint32_t 
 {
     detail::check(be, ce_batch_set_test_cicp(batch, pair_index, ref_index, pixels, len, format, &colour), "cicp", 0, 0, 0);
 }
+// ---- Y'CbCr planes with a colour description -> linear light in one kernel ---------------------------
+// yuv_to_rgb16 at depth_out = colour.depth followed by cicp_to_linear, bit for bit; colour.depth >= image.depth
+inline std::vector<float> yuv_to_linear(const HipBackend &be, const YuvImage &image, const ColourDescription &colour, uint32_t width, uint32_t height)
+{
+    std::vector<float> out((size_t)width * height * 3);
+    detail::check(be, ce_yuv_to_linear(be.ctx(), &image, &colour, width, height, out.data(), out.size()), "yuv_cicp", width, height, out.size());
+    return out;
+}
+// straight into a slot of a linear batch (eval::batch_linear), host or device planes
+inline void batch_set_reference_yuv_cicp(const HipBackend &be, ce_batch *batch, uint32_t ref_index, const YuvImage &image, const ColourDescription &colour)
+{
+    detail::check(be, ce_batch_set_reference_yuv_cicp(batch, ref_index, &image, &colour), "yuv_cicp", 0, 0, 0);
+}
+inline void batch_set_test_yuv_cicp(const HipBackend &be, ce_batch *batch, uint32_t pair_index, uint32_t ref_index, const YuvImage &image,
+                                    const ColourDescription &colour)
+{
+    detail::check(be, ce_batch_set_test_yuv_cicp(batch, pair_index, ref_index, &image, &colour), "yuv_cicp", 0, 0, 0);
+}
 // straight into a slot of a resident batch (RGB8 or deep), host or device planes
 inline void batch_set_reference_yuv(const HipBackend &be, ce_batch *batch, uint32_t ref_index, const YuvImage &image)
 {

@@ -41,7 +41,7 @@ class ImageData:
     channels: int = 3
     icc_profile: Optional[bytes] = None
     depth: int = 0  # 0: 8-bit samples in u8; 8, 10, 12 or 16: a deep image (rgb16 / rgba16), scored at its own precision
-    yuv_image: Optional[YuvImage] = None  # an 8-bit decode still in its Y'CbCr planes (ImageData.yuv); `data` is then empty
+    yuv_image: Optional[YuvImage] = None  # a decode still in its Y'CbCr planes (ImageData.yuv); `data` is then empty
     # How the code values are to be read (H.273 primaries / transfer; its depth is this image's): None = sRGB, as ever.  A
     # decode with a non-sRGB description is scored in linear light through a linear batch.
     colour: Optional[ColourDescription] = None
@@ -86,30 +86,37 @@ class ImageData:
 
     @staticmethod
     def yuv(planes, width: int, height: int, subsampling: int = YUV_420, layout: int = YUV_PLANAR, matrix: int = YUV_BT601,
-            range: int = YUV_FULL, upsample: int = CHROMA_TRIANGLE) -> "ImageData":
-        """A decoder's 8-bit Y'CbCr planes in host memory (a JPEG decoder in raw mode, dav1d: 2-D uint8 arrays, Y, Cb, Cr or
-        Y, interleaved CbCr) as they are: the session upsamples and converts them on the device, straight into the batch
-        slot (Batch.set_*_yuv, the definition of include/ce_metrics.h), and scores the result as RGB8; the multi-device
-        session converts them on the host with to_rgb8_vec, the same definition.  Deeper planes go through
-        Batch.set_*_yuv."""
-        img = YuvImage([np.asarray(p) for p in planes], subsampling, layout, matrix, range, upsample, 8, False, MEM_HOST)
+            range: int = YUV_FULL, upsample: int = CHROMA_TRIANGLE, *, depth: int = 8, msb_aligned: bool = False,
+            colour: Optional[ColourDescription] = None) -> "ImageData":
+        """A decoder's Y'CbCr planes in host memory (a JPEG decoder in raw mode, dav1d: 2-D arrays, Y, Cb, Cr or Y,
+        interleaved CbCr; uint8 at depth 8, uint16 at 10 and 12, low- or MSB-aligned as P010 is) as they are: the session
+        upsamples and converts them on the device, straight into the batch slot (Batch.set_*_yuv, the definition of
+        include/ce_metrics.h), and scores the result as RGB8; the multi-device session converts them on the host with
+        to_rgb8_vec, the same definition.  With a `colour` other than sRGB's (an HDR10 frame: BT2020_PQ) the image is
+        scored in linear light, its planes going through Batch.set_*_yuv_cicp."""
+        if depth not in (8, 10, 12):
+            raise ValueError(f"Y'CbCr samples are 8, 10 or 12 bits, got {depth}")
+        img = YuvImage([np.asarray(p) for p in planes], subsampling, layout, matrix, range, upsample, int(depth), bool(msb_aligned), MEM_HOST)
+        want = np.uint8 if depth == 8 else np.uint16
         for p in img.planes:
-            if p.dtype != np.uint8 or p.ndim != 2:
-                raise TypeError("ImageData.yuv takes 2-D uint8 planes")
-        return ImageData(np.empty(0, np.uint8), int(width), int(height), 3, None, 0, img)
+            if p.dtype != want or p.ndim != 2:
+                raise TypeError("ImageData.yuv takes 2-D uint8 planes" if depth == 8 else f"ImageData.yuv at depth {depth} takes 2-D uint16 planes")
+        return ImageData(np.empty(0, np.uint8), int(width), int(height), 3, None, 0, img, colour=_colour_at(colour, depth))
 
     def _yuv_to_rgb8_host(self) -> np.ndarray:
         """The device's conversion restated on the host for to_rgb8_vec (int64, the definition of include/ce_metrics.h)."""
         y, w, h = self.yuv_image, self.width, self.height
-        ky, krv, kgu, kgv, kbu, y0, c0 = yuv_coefficients(y.matrix, y.range, 8, 8)
-        luma = y.planes[0].astype(np.int64)[:h, :w]
+        ky, krv, kgu, kgv, kbu, y0, c0 = yuv_coefficients(y.matrix, y.range, y.depth, 8)
+        shift, maxv = (16 - y.depth if y.msb_aligned else 0), (1 << y.depth) - 1
+        sample = lambda p: np.minimum(p.astype(np.int64) >> shift, maxv)
+        luma = sample(y.planes[0])[:h, :w]
         if y.subsampling == YUV_400:
             cb = cr = np.full((h, w), c0, np.int64)
         else:
             if y.layout == YUV_SEMIPLANAR:
-                cb, cr = y.planes[1][:, 0::2].astype(np.int64), y.planes[1][:, 1::2].astype(np.int64)
+                cb, cr = sample(y.planes[1][:, 0::2]), sample(y.planes[1][:, 1::2])
             else:
-                cb, cr = y.planes[1].astype(np.int64), y.planes[2].astype(np.int64)
+                cb, cr = sample(y.planes[1]), sample(y.planes[2])
             cb, cr = (self._upsample_chroma(c, y.subsampling, y.upsample == CHROMA_TRIANGLE)[:h, :w] for c in (cb, cr))
         yy = ky * (luma - y0) + 32768
         rgb = np.stack([(yy + krv * (cr - c0)) >> 16, (yy - kgu * (cb - c0) - kgv * (cr - c0)) >> 16, (yy + kbu * (cb - c0)) >> 16], -1)
@@ -132,10 +139,10 @@ class ImageData:
         return out
 
     def to_rgb8_vec(self) -> np.ndarray:  # session.rs:98-117 (host copy; the session itself strips alpha on the device)
-        if self.yuv_image is not None:
-            return self._yuv_to_rgb8_host()
         if self.in_linear_light:  # no reference rule turns HDR or wide-gamut content into sRGB bytes: it is scored in linear light
             raise MetricCalculation(CE_ERR_BACKEND, "Metric calculation failed: an image in linear light or with a non-sRGB colour description has no RGB8 form")
+        if self.yuv_image is not None:
+            return self._yuv_to_rgb8_host()
         data = self.data if self.channels == 3 else np.ascontiguousarray(self.data.reshape(-1, 4)[:, :3]).reshape(-1)
         if self.depth:  # to_8bit's rule for any depth: what the reference does to a 10-bit decode before it measures
             maxv = (1 << self.depth) - 1
@@ -434,11 +441,14 @@ class EvalSession:
 
     def _set_linear(self, batch: Batch, image: ImageData, ref_index: int, pair_index: Optional[int]):
         """One image into a slot of a linear batch: float32 as it is, code values through the CICP ingest - by their own
-        description, an untagged image as sRGB (1, 13) at its own depth."""
+        description, an untagged image as sRGB (1, 13) at its own depth - and Y'CbCr planes through the fused ingest."""
         def refuse(what):
             raise MetricCalculation(CE_ERR_BACKEND, f"Metric calculation failed: linear-light scoring: {what}")
-        if image.yuv_image is not None:
-            refuse("Y'CbCr planes do not enter a linear batch (convert with yuv_to_rgb16 and tag the result)")
+        if image.yuv_image is not None:  # the planes' own tag, an untagged image as sRGB; depth 16 keeps what the matrix gives between code points
+            colour = (image.colour or ColourDescription.SRGB).with_depth(16)
+            if pair_index is None:
+                return batch.set_reference_yuv_cicp(ref_index, image.yuv_image, colour)
+            return batch.set_test_yuv_cicp(pair_index, ref_index, image.yuv_image, colour)
         if image.colour is not None and image.icc_profile is not None:
             refuse("an image with both a colour description and an ICC profile is not supported")
         if image.icc_profile is not None and pair_index is not None:  # the source's own profile is not applied, as ever

@@ -497,7 +497,7 @@ int ce_batch_resample_pairs(ce_batch *src, ce_batch *dst, uint32_t n_refs, uint3
  *             BT601 / FULL / d = D = 8 gives 65536, 91881, 22554, 46802, 116130: libjpeg-turbo's decoder, bit for bit.
  *             4:0:0 (gray): R = G = B from the Y term alone.
  * Not part of this: left-cosited (MPEG-2 / H.264 default) and other chroma sitings, 4:1:1 / 4:4:0, packed YUYV, 16-bit
- * YUV, PQ / HLG, identity / YCgCo matrices, YUV through ce_eval_batch, ce_ref_* and ce_batch_resample*, alpha planes. */
+ * YUV, HLG (PQ: ce_batch_set_*_yuv_cicp below), identity / YCgCo matrices, YUV through ce_eval_batch, ce_ref_* and ce_batch_resample*, alpha planes. */
 enum ce_yuv_subsampling { CE_YUV_444 = 0, CE_YUV_422 = 1, CE_YUV_420 = 2, CE_YUV_400 = 3 };
 /* PLANAR: plane[0..2] = Y, Cb, Cr (I420 and its kin).  SEMIPLANAR: plane[0] = Y, plane[1] = interleaved Cb Cr pairs
  * (NV12 / NV16 / P010), plane[2] unused.  4:0:0 reads plane[0] only under either layout. */
@@ -593,6 +593,7 @@ int ce_composite_rgba16(ce_ctx *ctx, const uint16_t *rgba, size_t len, uint32_t 
  * On a linear batch
  *   ce_batch_set_reference_fmt / ce_batch_set_test_fmt take CE_PIXEL_RGB_F32 only (len = width * height * 12);
  *   ce_batch_set_reference_cicp / ce_batch_set_test_cicp take tagged integer code values (below);
+ *   ce_batch_set_reference_yuv_cicp / ce_batch_set_test_yuv_cicp take Y'CbCr planes with such a tag (below);
  *   ce_batch_bind_pair, ce_batch_run, ce_batch_launch, ce_batch_collect, ce_batch_butteraugli_pnorm3 and the three map
  *     readers work as on any batch;
  *   CE_ERR_INVALID_ARG, with the reason in ce_last_error and the batch still usable: CE_FLAG_XYB_ROUNDTRIP,
@@ -601,7 +602,7 @@ int ce_composite_rgba16(ce_ctx *ctx, const uint16_t *rgba, size_t len, uint32_t 
  *   CE_PIXEL_RGB_F32 on a batch that is not linear is refused the same way.
  * Not part of this: HLG (its OOTF couples the channels and needs a device powf), the BT.709 / BT.1886 gamma transfers,
  * primaries with a non-D65 white, limited-range RGB, ce_ref_* handles on linear batches and the pooled ce_eval_batch on
- * them, Y'CbCr straight into a linear batch (chain ce_yuv_to_rgb16 into *_cicp).
+ * them.
  * (No reference item: the reference scores every PixelData variant only after to_8bit / to_rgb8_vec.) */
 enum {
     CE_PIXEL_RGB_F32 = 7 /* packed float RGB, 12 bytes per pixel: linear batches only (6 is not a format) */
@@ -657,6 +658,32 @@ int ce_cicp_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, c
  * primaries 1: the identity).  Pure host functions; CE_ERR_INVALID_ARG for a code point outside the lists above. */
 int ce_transfer_table(int transfer, uint32_t depth, float white_nits, float *out, size_t n);
 int ce_colour_matrix(int primaries, float out[9]);
+
+/* Y'CbCr planes with a CICP description -> a slot of a linear batch, on the device, in one kernel:
+ * what an HDR10 frame, an AVIF-HDR still from dav1d / libavif or a rocDecode / rocJPEG surface is.  The definition is the
+ * composition of the two above and adds no arithmetic.  For an image img and a colour description c,
+ *     rgb = the integer RGB that ce_yuv_to_rgb16(img, depth_out = c.depth) defines (samples, chroma upsampling, fixed-point
+ *           matrix, clamp to 2^c.depth - 1)
+ *     out = what ce_cicp_to_linear(rgb as CE_PIXEL_RGB16, c) defines (table gather, separately rounded f32 3 x 3 for
+ *           primaries != 1, the clamp of a linear image)
+ * img.depth (8, 10 or 12) is the depth of the Y'CbCr samples; c.depth (8, 10, 12 or 16) is the depth of the integer RGB
+ * grid between the two steps and the size of the transfer table, and must not be under img.depth.  c.depth = 16 keeps what
+ * the matrix produces between the samples' code points; c.depth = img.depth is what a decoder's own RGB output would have
+ * been.  The composition of tests/yuv_restatement.py (yuv_to_rgb with D = c.depth) and tests/cicp_restatement.py (to_linear)
+ * restates it in numpy; the device equals it bit for bit, on every float.
+ * ce_batch_set_*_yuv_cicp: one image of the batch's shape into a reference / test slot of a LINEAR batch, with the staging,
+ * the stream and the ordering of ce_batch_set_*_yuv; CE_MEM_HOST planes are consumed on return, CE_MEM_DEVICE planes are
+ * read in place under the lifetime rule given there.  CE_ERR_INVALID_ARG, with the reason in ce_last_error and the batch
+ * still usable, for everything ce_batch_set_*_yuv refuses about the image, everything ce_batch_set_*_cicp refuses about c,
+ * c.depth < img.depth, a null pointer, and a batch that is not linear.  (ce_batch_set_*_yuv on a linear batch stays refused:
+ * it has no colour description to go by.)
+ * ce_yuv_to_linear: one image of width x height to packed float RGB in host memory (out_len = width * height * 3 floats);
+ * errors as above, CE_ERR_BAD_LENGTH for a wrong out_len.
+ * Not part of this: HLG and the BT.709 / BT.1886 transfers, identity / YCgCo matrices, chroma sitings other than the centred
+ * one, ce_ref_* handles and the pooled ce_eval_batch on linear batches, resampling of linear batches. */
+int ce_batch_set_reference_yuv_cicp(ce_batch *b, uint32_t ref_index, const ce_yuv_image *image, const ce_colour *c);
+int ce_batch_set_test_yuv_cicp(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const ce_yuv_image *image, const ce_colour *c);
+int ce_yuv_to_linear(ce_ctx *ctx, const ce_yuv_image *image, const ce_colour *c, uint32_t width, uint32_t height, float *out, size_t out_len);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------ */
 /* Bracket every kernel launch with a HIP event pair, recorded on the stream the kernel is launched on,

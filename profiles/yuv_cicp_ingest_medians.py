@@ -1,0 +1,46 @@
+"""Per-dispatch medians of profiles/yuv_cicp_ingest_timing.py's phases from rocprofv3's kernel trace.
+usage: yuv_cicp_ingest_medians.py TRACE_DIR PLAN.txt - TRACE_DIR is searched for *kernel_trace.csv; PLAN.txt is the timing
+script's output, whose last line is the plan: the phases in order, each with the kernel it dispatches and how often.  The
+dispatches of a kernel are taken in start order and dealt to the phases in plan order, the warm-up ones dropped.  Prints
+one line per phase (median microseconds, GB/s against the bytes the script printed) and the fused-to-yardstick ratios."""
+import csv
+import glob
+import json
+import os
+import statistics
+import sys
+
+trace_dir, plan_path = sys.argv[1], sys.argv[2]
+plan = json.loads(open(plan_path).read().strip().splitlines()[-1])
+rows = []
+for path in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True):
+    with open(path, newline="") as f:
+        for r in csv.DictReader(f):
+            rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
+rows.sort()
+queues = {}
+for phase in plan:
+    k = phase["kernel"]
+    if k not in queues:
+        queues[k] = [(s, e) for s, e, name in rows if k in name]
+medians = {}
+for phase in plan:
+    q = queues[phase["kernel"]]
+    mine, queues[phase["kernel"]] = q[:phase["dispatches"]], q[phase["dispatches"]:]
+    assert len(mine) == phase["dispatches"], (phase, len(mine))
+    us = [(e - s) / 1e3 for s, e in mine[phase["warmup"]:]]
+    if not us:
+        continue
+    med = statistics.median(us)
+    medians[phase["label"]] = med
+    print(f"{phase['label']}: median {med:.2f} us over {len(us)} dispatches (min {min(us):.2f}, max {max(us):.2f}), "
+          f"{phase['mb'] / med * 1e3:.1f} GB/s of {phase['mb']:.3f} MB")
+for k, left in queues.items():
+    assert not left, (k, len(left))
+for size in ("768x512", "3840x2160"):
+    pick = lambda part: next(v for k, v in medians.items() if k.startswith(size) and part in k)
+    deep = pick("yuv420_16_deep") + pick("cicp_rgb16_m")
+    eight = pick("yuv420_8)") + pick("cicp_rgb8)")
+    print(f"{size}: fused P010 depth 16 / (yuv420_16_deep + cicp_rgb16_m) = {pick('fused P010 (9, 16, 16)'):.2f} / {deep:.2f} = "
+          f"{pick('fused P010 (9, 16, 16)') / deep:.3f} (byte count: 15 / 27 = 0.556); depth 10 table: {pick('fused P010 (9, 16, 10)') / deep:.3f}; "
+          f"fused I420 / (yuv420_8 + cicp_rgb8) = {pick('fused I420') / eight:.3f} (13.5 / 19.5 = 0.692)")
