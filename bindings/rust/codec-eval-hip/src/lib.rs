@@ -190,6 +190,20 @@ impl HipMetrics {
         Ok(out)
     }
 
+    /// One packed `f32` RGB image in linear light at another size (`ce_resample_linear`): the convolution of Pillow's
+    /// `Image.resize` on mode "F" images - f64 weights and accumulator, one rounding to f32 per pass - bit for bit, on the
+    /// device, clamped to +-`CE_LINEAR_MAX`.  The lengths the library checks are in bytes.
+    pub fn resample_linear(&mut self, rgb: &[f32], width: u32, height: u32, out_width: u32, out_height: u32, filter: ResampleFilter)
+                           -> Result<Vec<f32>, HipError> {
+        let mut out = vec![0f32; out_width as usize * out_height as usize * 3];
+        let rc = unsafe {
+            sys::ce_resample_linear(self.ctx, rgb.as_ptr(), rgb.len() * 4, width, height, out_width, out_height, filter as i32,
+                                    out.as_mut_ptr(), out.len() * 4)
+        };
+        self.check(rc, width, height, rgb.len())?;
+        Ok(out)
+    }
+
     /// A resident grid of `(reference, test)` pairs of one shape (`ce_batch_create`); `&self`, so that a source grid and
     /// the grids it is resampled into can live side by side (one call at a time per context, as everywhere).
     pub fn batch(&self, width: u32, height: u32, max_refs: u32, max_pairs: u32) -> Result<HipBatch<'_>, HipError> {

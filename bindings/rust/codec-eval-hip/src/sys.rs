@@ -271,6 +271,8 @@ extern "C" {
     pub fn ce_ref_image_heuristics(r: *mut ce_ref, out: *mut ce_image_heuristics) -> c_int;
     pub fn ce_resample_rgb8(ctx: *mut ce_ctx, rgb: *const u8, len: usize, w: u32, h: u32, out_w: u32, out_h: u32, filter: c_int,
                             out: *mut u8, out_len: usize) -> c_int;
+    pub fn ce_resample_linear(ctx: *mut ce_ctx, rgb: *const c_float, len: usize, w: u32, h: u32, out_w: u32, out_h: u32, filter: c_int,
+                              out: *mut c_float, out_len: usize) -> c_int;
     pub fn ce_batch_resample(src: *mut ce_batch, dst: *mut ce_batch, which: u32, first: u32, count: u32, filter: c_int) -> c_int;
     pub fn ce_batch_resample_pairs(src: *mut ce_batch, dst: *mut ce_batch, n_refs: u32, n_pairs: u32, filter: c_int) -> c_int;
     pub fn ce_yuv_coefficients(matrix: c_int, range: c_int, depth_in: u32, depth_out: u32, out: *mut i64) -> c_int;

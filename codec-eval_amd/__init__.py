@@ -238,6 +238,7 @@ _PROTOTYPES = [
     ("ce_batch_image_heuristics", _i, [_vp, _u32, _u32, _u32, C.POINTER(CeImageHeuristics)]),
     ("ce_ref_image_heuristics", _i, [_vp, C.POINTER(CeImageHeuristics)]),
     ("ce_resample_rgb8", _i, [_vp, _u8p, _sz, _u32, _u32, _u32, _u32, _i, _u8p, _sz]),
+    ("ce_resample_linear", _i, [_vp, _vp, _sz, _u32, _u32, _u32, _u32, _i, _vp, _sz]),
     ("ce_batch_resample", _i, [_vp, _vp, _u32, _u32, _u32, _i]),
     ("ce_batch_resample_pairs", _i, [_vp, _vp, _u32, _u32, _i]),
     ("ce_yuv_coefficients", _i, [_i, _i, _u32, _u32, C.POINTER(C.c_int64 * 7)]),
@@ -900,6 +901,17 @@ class Context:
                                            out.ctypes.data, out.size))
         return out
 
+    def resample_linear(self, rgb, width: int, height: int, out_width: int, out_height: int,
+                        filter: int = RESAMPLE_LANCZOS3) -> np.ndarray:
+        """One packed float32 RGB image in linear light at another size (ce_resample_linear): the convolution of Pillow's
+        Image.resize on mode "F" images - f64 weights and accumulator, one rounding to f32 per pass - bit for bit, clamped
+        to +-LINEAR_MAX -> (out_height, out_width, 3) float32."""
+        r = _buf_f32(rgb)
+        out = np.empty((max(out_height, 0), max(out_width, 0), 3), np.float32)
+        self._check(lib().ce_resample_linear(self._h, r.ctypes.data, r.nbytes, width, height, out_width, out_height, filter,
+                                             out.ctypes.data, out.nbytes))
+        return out
+
     def yuv_to_rgb8(self, image: "YuvImage", width: int, height: int) -> np.ndarray:
         """A decoder's Y'CbCr planes -> (height, width, 3) uint8 by the device's chroma upsampling and colour matrix
         (ce_yuv_to_rgb8; the definition is in include/ce_metrics.h)."""
@@ -1275,7 +1287,8 @@ class Batch:
 
     def resample_into(self, dst: "Batch", first: int, count: int, tests: bool = False, filter: int = RESAMPLE_LANCZOS3):
         """References (tests=True: test images) [first, first + count) of this batch resampled to `dst`'s shape into the
-        same indices of `dst`, a batch of the same context (ce_batch_resample): on the device, behind this batch's
+        same indices of `dst`, a batch of the same context and the same kind - RGB8 into RGB8 by the fixed-point resampler,
+        linear into linear by the float one (ce_batch_resample): on the device, behind this batch's
         uploads and ahead of dst's next launch; no scores or maps of either batch change."""
         self.ctx._check(lib().ce_batch_resample(self._h, dst._h, BATCH_TESTS if tests else BATCH_REFERENCES, first, count, filter))
 

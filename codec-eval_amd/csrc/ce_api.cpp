@@ -415,6 +415,8 @@ void ce_ctx_destroy(ce_ctx *ctx)
     hipFree(ctx->rs_mid);
     for (auto &kv : ctx->rs_tables) hipFree(kv.second.d);
     ctx->rs_tables.clear();
+    for (auto &kv : ctx->rs_tables_f64) hipFree(kv.second.d);
+    ctx->rs_tables_f64.clear();
     hipFree(ctx->d_lut_ssim2);
     hipFree(ctx->d_lut_powf);
     hipFree(ctx->d_xyb_thresh);
@@ -2312,7 +2314,42 @@ static int resample_table(ce_ctx *ctx, uint32_t n_in, uint32_t n_out, int filter
     return CE_OK;
 }
 
+// the same for the float resampler (ce_ctx::rs_tables_f64)
+static int resample_table_f64(ce_ctx *ctx, uint32_t n_in, uint32_t n_out, int filter, const ce_resample_axis_f64 **out)
+{
+    const auto key = std::make_tuple(n_in, n_out, filter);
+    auto it = ctx->rs_tables_f64.find(key);
+    if (it == ctx->rs_tables_f64.end()) {
+        std::vector<double> host;
+        ce_resample_axis_f64 a;
+        a.n_in = n_in, a.n_out = n_out;
+        if (!ce_build_resample_table_f64(n_in, n_out, filter, host, &a.ksize)) return fail(ctx, CE_ERR_INVALID_ARG, "resample: bad axis");
+        CE_HIP(ctx, hipMalloc((void **)&a.d, host.size() * sizeof(double)));
+        if (hipMemcpy(a.d, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+            hipFree(a.d);
+            return fail(ctx, CE_ERR_BACKEND, "H2D failed (resample taps)");
+        }
+        it = ctx->rs_tables_f64.emplace(key, a).first;
+    }
+    *out = &it->second;
+    return CE_OK;
+}
+
 static bool resample_filter_ok(int filter) { return filter >= CE_RESAMPLE_BOX && filter <= CE_RESAMPLE_LANCZOS3; }
+
+// the image between the two passes: at least `need` bytes of ce_ctx::rs_mid
+static int resample_mid(ce_ctx *ctx, size_t need)
+{
+    if (ctx->rs_mid_cap < need) {
+        CE_HIP(ctx, hipStreamSynchronize(ctx->stream));  // an earlier resample may still be between its passes
+        CE_HIP(ctx, hipFree(ctx->rs_mid));
+        ctx->rs_mid = nullptr;
+        ctx->rs_mid_cap = 0;
+        CE_HIP(ctx, hipMalloc((void **)&ctx->rs_mid, need + need / 4));
+        ctx->rs_mid_cap = need + need / 4;
+    }
+    return CE_OK;
+}
 
 // n images of w x h at d_src (src_stride apart) to out_w x out_h at d_dst, queued on the context's stream
 static int resample_images(ce_ctx *ctx, const uint8_t *d_src, size_t src_stride, uint8_t *d_dst, size_t dst_stride, uint32_t w, uint32_t h,
@@ -2333,18 +2370,34 @@ static int resample_images(ce_ctx *ctx, const uint8_t *d_src, size_t src_stride,
         if (int rc = resample_table(ctx, w, out_w, filter, &horiz)) return rc;
     if (h != out_h)
         if (int rc = resample_table(ctx, h, out_h, filter, &vert)) return rc;
-    if (horiz && vert) {
-        const size_t need = (size_t)n * h * out_w * 3;
-        if (ctx->rs_mid_cap < need) {
-            CE_HIP(ctx, hipStreamSynchronize(ctx->stream));  // an earlier resample may still be between its passes
-            CE_HIP(ctx, hipFree(ctx->rs_mid));
-            ctx->rs_mid = nullptr;
-            ctx->rs_mid_cap = 0;
-            CE_HIP(ctx, hipMalloc((void **)&ctx->rs_mid, need + need / 4));
-            ctx->rs_mid_cap = need + need / 4;
-        }
-    }
+    if (horiz && vert)
+        if (int rc = resample_mid(ctx, (size_t)n * h * out_w * 3)) return rc;
     return ce_launch_resample(ctx, ctx->stream, d_src, src_stride, d_dst, dst_stride, w, h, out_w, out_h, n, horiz, vert, ctx->rs_mid);
+}
+
+// the same for packed f32 RGB (strides in bytes, multiples of 4): resample_f32.hip; equal sizes are a byte copy, unclamped
+static int resample_images_linear(ce_ctx *ctx, const uint8_t *d_src, size_t src_stride, uint8_t *d_dst, size_t dst_stride, uint32_t w,
+                                  uint32_t h, uint32_t out_w, uint32_t out_h, uint32_t n, int filter)
+{
+    if (w == out_w && h == out_h) {
+        const size_t img = (size_t)w * h * 12;
+        if (src_stride == img && dst_stride == img) {
+            CE_HIP(ctx, hipMemcpyAsync(d_dst, d_src, img * n, hipMemcpyDeviceToDevice, ctx->stream));
+        } else {
+            for (uint32_t i = 0; i < n; i++)
+                CE_HIP(ctx, hipMemcpyAsync(d_dst + i * dst_stride, d_src + i * src_stride, img, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        return CE_OK;
+    }
+    const ce_resample_axis_f64 *horiz = nullptr, *vert = nullptr;
+    if (w != out_w)
+        if (int rc = resample_table_f64(ctx, w, out_w, filter, &horiz)) return rc;
+    if (h != out_h)
+        if (int rc = resample_table_f64(ctx, h, out_h, filter, &vert)) return rc;
+    if (horiz && vert)
+        if (int rc = resample_mid(ctx, (size_t)n * h * out_w * 12)) return rc;
+    return ce_launch_resample_f32(ctx, ctx->stream, reinterpret_cast<const float *>(d_src), src_stride / 4, reinterpret_cast<float *>(d_dst),
+                                  dst_stride / 4, w, h, out_w, out_h, n, horiz, vert, reinterpret_cast<float *>(ctx->rs_mid));
 }
 
 int ce_resample_rgb8(ce_ctx *ctx, const uint8_t *rgb, size_t len, uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h, int filter,
@@ -2363,6 +2416,22 @@ int ce_resample_rgb8(ce_ctx *ctx, const uint8_t *rgb, size_t len, uint32_t w, ui
     });
 }
 
+int ce_resample_linear(ce_ctx *ctx, const float *rgb, size_t len, uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h, int filter, float *out,
+                       size_t out_len)
+{
+    if (!ctx || !rgb || !out) return fail(ctx, CE_ERR_INVALID_ARG, "resample: null pointer");
+    if (!resample_filter_ok(filter)) return fail(ctx, CE_ERR_INVALID_ARG, "resample: unknown filter " + std::to_string(filter));
+    if (w == 0 || h == 0 || out_w == 0 || out_h == 0)
+        return fail(ctx, CE_ERR_INVALID_ARG, "resample: " + std::to_string(w) + " x " + std::to_string(h) + " to " + std::to_string(out_w) +
+                                                 " x " + std::to_string(out_h) + " has an empty side");
+    const size_t want_in = (size_t)w * h * 12, want_out = (size_t)out_w * out_h * 12;
+    if (len != want_in) return bad_length(ctx, want_in, len);
+    if (out_len != want_out) return bad_length(ctx, want_out, out_len);
+    return leaf_roundtrip(ctx, rgb, len, out, out_len, [&](uint8_t *d_in, uint8_t *d_out) {
+        return resample_images_linear(ctx, d_in, want_in, d_out, want_out, w, h, out_w, out_h, 1, filter);
+    });
+}
+
 // the checks two batches must pass before anything moves between them
 static int resample_check(ce_batch *src, ce_batch *dst, int filter)
 {
@@ -2372,9 +2441,11 @@ static int resample_check(ce_batch *src, ce_batch *dst, int filter)
     if (src == dst) return fail(ctx, CE_ERR_INVALID_ARG, "resample: source and destination are the same batch");
     if (!resample_filter_ok(filter)) return fail(ctx, CE_ERR_INVALID_ARG, "resample: unknown filter " + std::to_string(filter));
     if (src->depth[0] || dst->depth[0])
-        return fail(ctx, CE_ERR_INVALID_ARG, "resample works on RGB8 batches: a deep batch is out of its scope");
-    if (src->linear || dst->linear)
-        return fail(ctx, CE_ERR_INVALID_ARG, "resample works on RGB8 batches: a linear batch is out of its scope");
+        return fail(ctx, CE_ERR_INVALID_ARG, src->linear || dst->linear
+                                                 ? "resample: a linear batch resamples into a linear batch only, and a deep batch is out of its scope"
+                                                 : "resample works on RGB8 and linear batches: a deep batch is out of its scope");
+    if (src->linear != dst->linear)
+        return fail(ctx, CE_ERR_INVALID_ARG, "resample: a linear batch resamples into a linear batch only, an RGB8 batch into an RGB8 one");
     return CE_OK;
 }
 
@@ -2390,7 +2461,8 @@ static int resample_slab(ce_batch *src, ce_batch *dst, uint32_t which, uint32_t 
     if (!tests) invalidate_reference_state(dst);
     const uint8_t *s = (tests ? src->d_tests : src->d_refs) + (size_t)first * src->img_bytes;
     uint8_t *d = (tests ? dst->d_tests : dst->d_refs) + (size_t)first * dst->img_bytes;
-    const int rc = resample_images(ctx, s, src->img_bytes, d, dst->img_bytes, src->w, src->h, dst->w, dst->h, count, filter);
+    const int rc = (src->linear ? resample_images_linear : resample_images)(ctx, s, src->img_bytes, d, dst->img_bytes, src->w, src->h, dst->w,
+                                                                            dst->h, count, filter);
     src->inline_pending = true;  // a later upload into src waits for these reads (order_write)
     return rc;
 }

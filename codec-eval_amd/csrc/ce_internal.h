@@ -62,6 +62,13 @@ struct ce_resample_axis {
     uint32_t n_in = 0, n_out = 0, ksize = 0;
 };
 
+// One axis of a float resample (resample_f32.hip): n_out * (1 + ksize) doubles, the first n_out of them holding, as int32,
+// [n_out] first tap | [n_out] tap count; then [n_out][ksize] f64 weights
+struct ce_resample_axis_f64 {
+    double *d = nullptr;
+    uint32_t n_in = 0, n_out = 0, ksize = 0;
+};
+
 struct ce_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -110,11 +117,13 @@ struct ce_ctx {
     // and the page-locked buffer their results come back through
     uint8_t *heur_d = nullptr, *heur_h = nullptr;
     size_t heur_d_cap = 0, heur_h_cap = 0;
-    // grow-only device scratch of the resampler (resample.hip): the u8 image between its two passes, and the tap tables of
+    // grow-only device scratch of the resamplers (resample.hip, resample_f32.hip): the image between the two passes - u8, or
+    // f32 for a linear batch; both resamplers run on the context's stream, so one buffer serves them - and the tap tables of
     // the (in, out, filter) pairs used so far, keyed by them and kept until the context goes (ce_api.cpp: resample_table)
     uint8_t *rs_mid = nullptr;
     size_t rs_mid_cap = 0;
     std::map<std::tuple<uint32_t, uint32_t, int>, struct ce_resample_axis> rs_tables;
+    std::map<std::tuple<uint32_t, uint32_t, int>, struct ce_resample_axis_f64> rs_tables_f64;
 
     // Auxiliary streams of the context, shared by all its batches (made on first use, destroyed with the context): the
     // three metric chains of a forked batch, SSIMULACRA2's level-0 passes, Butteraugli's half-resolution chain.  Rounds
@@ -379,6 +388,12 @@ int ce_launch_resample(ce_ctx *ctx, hipStream_t stream, const uint8_t *d_src, si
                        uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h, uint32_t n, const ce_resample_axis *horiz,
                        const ce_resample_axis *vert, uint8_t *mid);
 
+// The same for packed f32 RGB (a linear batch's slabs; resample_f32.hip): strides in floats, `mid` the n x h x out_w x 3 floats
+// between the passes; the last pass that runs clamps its store to +-CE_LINEAR_MAX
+int ce_launch_resample_f32(ce_ctx *ctx, hipStream_t stream, const float *d_src, size_t src_stride, float *d_dst, size_t dst_stride,
+                           uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h, uint32_t n, const ce_resample_axis_f64 *horiz,
+                           const ce_resample_axis_f64 *vert, float *mid);
+
 // One Y'CbCr image on the device as yuv.hip reads it: checked by ce_api.cpp (yuv_check), planes in device memory
 struct ce_yuv_dev {
     const uint8_t *plane[3];
@@ -417,6 +432,8 @@ bool ce_build_colour_matrix(int primaries, float m[9]);
 // the resampler's taps of one axis, n_in -> n_out samples (include/ce_metrics.h, enum ce_resample_filter): table = [n_out]
 // first tap | [n_out] tap count | [n_out][ksize] weights; false for an unknown filter or an empty axis
 bool ce_build_resample_table(uint32_t n_in, uint32_t n_out, int filter, std::vector<int32_t> &table, uint32_t *ksize);
+// the float resampler's: the same geometry with the normalised f64 weights themselves, in ce_resample_axis_f64's layout
+bool ce_build_resample_table_f64(uint32_t n_in, uint32_t n_out, int filter, std::vector<double> &table, uint32_t *ksize);
 void ce_build_srgb_lut_f64(float lut[256]);
 void ce_build_srgb_lut_powf(float lut[256]);
 // the same two rules for samples 0 .. maxv meaning v / maxv: lut has maxv + 1 entries

@@ -197,6 +197,45 @@ bool ce_build_resample_table(uint32_t n_in, uint32_t n_out, int filter, std::vec
     return true;
 }
 
+// The taps of one axis of the float resampler (ce_resample_linear): Pillow's precompute_coeffs alone,
+// the weights kept as the normalised doubles.  Same geometry and ksize as above; the filter's argument is scaled by the
+// reciprocal 1.0 / fs as Pillow writes it, which differs from the division above in the last bits of some bilinear taps -
+// invisible after the rounding to 22 bits there, visible here.  table = n_out * (1 + ksize) doubles: the first n_out hold,
+// as 2 * n_out int32, [n_out] first tap | [n_out] tap count; then [n_out][ksize] weights, zero past a sample's count.
+bool ce_build_resample_table_f64(uint32_t n_in, uint32_t n_out, int filter, std::vector<double> &table, uint32_t *ksize_out)
+{
+    static const double supports[4] = {0.5, 1.0, 2.0, 3.0};
+    if (filter < 0 || filter > 3 || n_in == 0 || n_out == 0) return false;
+    const double scale = (double)n_in / (double)n_out;
+    const double fs = scale < 1.0 ? 1.0 : scale;
+    const double support = supports[filter] * fs;
+    const double ss = 1.0 / fs;
+    const uint32_t ksize = (uint32_t)std::ceil(support) * 2 + 1;
+    table.assign((size_t)n_out * (1 + (size_t)ksize), 0.0);
+    std::vector<int32_t> head(2 * (size_t)n_out);
+    for (uint32_t xx = 0; xx < n_out; xx++) {
+        const double center = (xx + 0.5) * scale;
+        int64_t xmin = (int64_t)(center - support + 0.5);
+        if (xmin < 0) xmin = 0;
+        int64_t xmax = (int64_t)(center + support + 0.5);
+        if (xmax > (int64_t)n_in) xmax = n_in;
+        const int64_t n = xmax - xmin;
+        double *k = &table[(size_t)n_out + (size_t)xx * ksize];
+        double ww = 0.0;
+        for (int64_t x = 0; x < n; x++) {
+            k[x] = resample_weight(filter, (x + xmin - center + 0.5) * ss);
+            ww += k[x];
+        }
+        if (ww != 0.0)
+            for (int64_t x = 0; x < n; x++) k[x] /= ww;
+        head[xx] = (int32_t)xmin;
+        head[(size_t)n_out + xx] = (int32_t)n;
+    }
+    memcpy(table.data(), head.data(), head.size() * sizeof(int32_t));
+    *ksize_out = ksize;
+    return true;
+}
+
 // ---- Y'CbCr -> RGB fixed-point coefficients (include/ce_metrics.h: ce_yuv_coefficients; yuv.hip) ------------------------
 // {KY, KRV, KGU, KGV, KBU, y0, c0}, every product in f64 and rounded once with rint.  BT601 uses libjpeg's literals
 // (jdcolor.c), which are not the Kr / Kb quotients to the last digit: they are what makes d = D = 8 full range its table.

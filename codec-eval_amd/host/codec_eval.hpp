@@ -400,6 +400,17 @@ inline Bytes resample_rgb8(const HipBackend &be, const Bytes &rgb, uint32_t widt
     return out;
 }
 
+// One packed float RGB image in linear light at another size (ce_resample_linear): the convolution
+// of Pillow's Image.resize on mode "F" images, bit for bit, clamped to +-CE_LINEAR_MAX
+inline std::vector<float> resample_linear(const HipBackend &be, const std::vector<float> &rgb, uint32_t width, uint32_t height, uint32_t out_width,
+                                          uint32_t out_height, int filter = CE_RESAMPLE_LANCZOS3)
+{
+    std::vector<float> out((size_t)out_width * out_height * 3);
+    detail::check(be, ce_resample_linear(be.ctx(), rgb.data(), rgb.size() * 4, width, height, out_width, out_height, filter, out.data(), out.size() * 4),
+                  "resample", width, height, rgb.size());
+    return out;
+}
+
 // ---- planar Y'CbCr ingest: a decoder's planes, upsampled and converted on the device -------------
 // The struct is the ABI's; yuv_image() fills the common case (8-bit 4:2:0 planar, BT.601 full range, triangle upsampling:
 // what a JPEG decoder in raw mode hands over) and the caller changes what differs.
@@ -965,6 +976,21 @@ inline MetricResult evaluate_pair_linear(const HipBackend &be, const std::vector
                                        (uint32_t)height, config.mask(), config.flags(), intensity_target, &s);
     detail::check(be, rc, "evaluate_pair_linear", width, height, test.size());
     return MetricResult::from_c(s);
+}
+// The same pair at the size `condition` displays it (viewing::SimulationParams::displayed_size): both images resampled in
+// linear light on the device (metrics::resample_linear), then scored; a condition that displays them as they are scores them
+// as they are.  A resident grid takes the same route without a host copy: ce_batch_resample_pairs from one batch_linear into
+// another of the displayed shape.
+inline MetricResult evaluate_pair_linear_under(const HipBackend &be, const std::vector<float> &reference, const std::vector<float> &test,
+                                               size_t width, size_t height, const viewing::ViewingCondition &condition,
+                                               viewing::SimulationMode mode, const MetricConfig &config, int filter = CE_RESAMPLE_LANCZOS3,
+                                               float intensity_target = CE_DEFAULT_INTENSITY_TARGET)
+{
+    const auto shown = condition.simulation_params((uint32_t)width, (uint32_t)height, mode).displayed_size((uint32_t)width, (uint32_t)height);
+    if (shown == std::make_pair((uint32_t)width, (uint32_t)height)) return evaluate_pair_linear(be, reference, test, width, height, config, intensity_target);
+    return evaluate_pair_linear(be, metrics::resample_linear(be, reference, (uint32_t)width, (uint32_t)height, shown.first, shown.second, filter),
+                                metrics::resample_linear(be, test, (uint32_t)width, (uint32_t)height, shown.first, shown.second, filter), shown.first,
+                                shown.second, config, intensity_target);
 }
 // A linear HBM-resident grid, filled with ce_batch_set_*_fmt(CE_PIXEL_RGB_F32) or metrics::batch_set_*_cicp and run like
 // any batch; the caller destroys it with ce_batch_destroy.

@@ -397,7 +397,8 @@ class EvalSession:
             free, _total = self.ctx.memory_info()
             budget = int(os.environ.get("CE_SESSION_BATCH_BYTES", 0)) or int(free * 0.6)
             sw, sh = self._displayed(w, h)  # the metrics' working set is the displayed shape's; the source slabs come on top
-            extra = 3 * w * h if (sw, sh) != (w, h) else 0
+            in_linear = any(image.in_linear_light or any(d.in_linear_light for _, d in pending) for image, _, pending in group)
+            extra = (12 if in_linear else 3) * w * h if (sw, sh) != (w, h) else 0  # a linear source slab holds 12 bytes a pixel
             fixed = estimate_batch_bytes(sw, sh, 0, 0, cfg)
             per_ref = estimate_batch_bytes(sw, sh, 1, 0, cfg) - fixed + extra
             per_pair = estimate_batch_bytes(sw, sh, 0, 1, cfg) - fixed + extra
@@ -466,9 +467,8 @@ class EvalSession:
 
     def _score_cells_linear(self, w: int, h: int, group, cfg: MetricConfig):
         """The cells scored in linear light: one linear batch, a reference slot per image, a test slot
-        per cell; PSNR is not defined there and stays None."""
-        if self._displayed(w, h) != (w, h):
-            raise MetricCalculation(CE_ERR_BACKEND, "Metric calculation failed: linear-light scoring: simulate_viewing resamples 8-bit images only")
+        per cell; PSNR is not defined there and stays None.  With simulate_viewing they are scored at the displayed size: the
+        batch of the uploads is resampled in linear light into a linear batch of that shape."""
         if cfg.flags & 1:  # CE_FLAG_XYB_ROUNDTRIP
             raise MetricCalculation(CE_ERR_BACKEND, "Metric calculation failed: linear-light scoring: xyb_roundtrip is an 8-bit quantisation")
         n_pairs = sum(len(p) for _, _, p in group)
@@ -484,7 +484,16 @@ class EvalSession:
                     self._set_linear(batch, decoded, ri, k)
                     rows.append((report, row_index, k))
                     k += 1
-            scores = batch.run(n_pairs, cfg)
+            shown = self._displayed(w, h)
+            if shown != (w, h):
+                dst = Batch(self.ctx, shown[0], shown[1], len(group), n_pairs, linear=True)
+                try:
+                    batch.resample_pairs_into(dst, len(group), n_pairs, self.config.resample_filter)
+                    scores = dst.run(n_pairs, cfg)
+                finally:
+                    dst.close()
+            else:
+                scores = batch.run(n_pairs, cfg)
         finally:
             batch.close()
         for report, row_index, k in rows:

@@ -223,16 +223,19 @@ class ConditionScores:
 
 def score_under(ctx, batch, n_refs: int, n_pairs: int, conditions: Sequence[ViewingCondition],
                 mode: SimulationMode = SimulationMode.Accurate, config=None, filter: Optional[int] = None) -> List[ConditionScores]:
-    """Score the resident RGB8 `batch` (references [0, n_refs), pairs [0, n_pairs)) under every condition, each at the
-    size that condition displays the images: one device-side resample and one launch per distinct displayed shape, no
-    upload.  A shape's destination batch is sized with estimate_batch_bytes against a third of the free device memory;
+    """Score the resident RGB8 or linear `batch` (references [0, n_refs), pairs [0, n_pairs)) under every condition, each
+    at the size that condition displays the images: one device-side resample and one launch per distinct displayed shape,
+    no upload.  A linear batch is resampled in linear light into linear batches.  A shape's
+    destination batch is sized with estimate_batch_bytes (_linear for a linear batch) against a third of the free device memory;
     when the whole grid does not fit, the pairs go through it in chunks (every chunk carries all n_refs references).
     Conditions that display the images as they are score `batch` itself."""
-    from . import (RESAMPLE_LANCZOS3, Batch, MetricConfig, MetricResult, _error_obj, estimate_batch_bytes)
+    from . import (RESAMPLE_LANCZOS3, Batch, MetricConfig, MetricResult, _error_obj, estimate_batch_bytes, estimate_batch_bytes_linear)
 
     config = config or MetricConfig.all()
     filter = RESAMPLE_LANCZOS3 if filter is None else filter
     w, h = batch.width, batch.height
+    linear = bool(getattr(batch, "linear", False))
+    estimate = estimate_batch_bytes_linear if linear else estimate_batch_bytes
     params = [c.simulation_params(w, h, mode) for c in conditions]
     by_shape = {}
 
@@ -254,12 +257,12 @@ def score_under(ctx, batch, n_refs: int, n_pairs: int, conditions: Sequence[View
         ow, oh = shape
         free, _total = ctx.memory_info()
         budget = int(os.environ.get("CE_VIEWING_BATCH_BYTES", 0)) or free // 3
-        fixed = estimate_batch_bytes(ow, oh, n_refs, 0, config)
-        per_pair = max(estimate_batch_bytes(ow, oh, n_refs, 1, config) - fixed, 1)
+        fixed = estimate(ow, oh, n_refs, 0, config)
+        per_pair = max(estimate(ow, oh, n_refs, 1, config) - fixed, 1)
         chunk = int(min(n_pairs, max(1, (budget - fixed) // per_pair)))
         results = []
         if chunk >= n_pairs:
-            dst = Batch(ctx, ow, oh, n_refs, n_pairs)
+            dst = Batch(ctx, ow, oh, n_refs, n_pairs, linear=linear)
             try:
                 batch.resample_pairs_into(dst, n_refs, n_pairs, filter)
                 results = collect(dst.run(n_pairs, config))
@@ -268,12 +271,12 @@ def score_under(ctx, batch, n_refs: int, n_pairs: int, conditions: Sequence[View
         else:
             # every pair is resampled once into `shown`, a batch that is never launched and so holds its slabs only; its
             # tests then go chunk by chunk (device copies on the context's stream) through `dst`, which holds the references
-            shown = Batch(ctx, ow, oh, n_refs, n_pairs)
-            dst = Batch(ctx, ow, oh, n_refs, chunk)
+            shown = Batch(ctx, ow, oh, n_refs, n_pairs, linear=linear)
+            dst = Batch(ctx, ow, oh, n_refs, chunk, linear=linear)
             try:
                 batch.resample_into(dst, 0, n_refs, False, filter)
                 batch.resample_into(shown, 0, n_pairs, True, filter)
-                img = ow * oh * 3
+                img = ow * oh * (12 if linear else 3)
                 for o in range(0, n_pairs, chunk):
                     m = min(chunk, n_pairs - o)
                     ctx.copy_device(dst.test_slab, shown.test_slab + o * img, m * img)

@@ -441,6 +441,14 @@ int ce_ref_image_heuristics(ce_ref *ref, ce_image_heuristics *out);
  * sum, each turned into (int)(+-0.5 + k * 2^22), and is clip_0_255((2^21 + sum k_i * sample_i) >> 22) in int32.  The
  * horizontal pass runs first and writes u8, the vertical pass runs on that; a pass whose size does not change is skipped
  * (equal sizes: a byte copy).  The weights are built on the host in f64.
+ * A LINEAR batch (below) is resampled in linear light, where averaging light is physically right, by
+ * the same convolution as Pillow runs it on mode "F" images, bit for bit: the same taps [xmin, xmax), ss = 1.0 / fs, weights
+ * w_x = f((x + xmin - center + 0.5) * ss) divided by their left-to-right f64 sum when that is not zero and kept as doubles;
+ * acc = 0.0, then acc = acc + (double)sample[xmin + x] * w_x for x ascending, the product and the sum each rounded to f64 (no
+ * fused multiply-add); out = (float)acc.  Horizontal pass first, f32 between the passes, a pass whose size does not change
+ * skipped, equal sizes a byte copy, the three channels independent.  The last pass that runs clamps what it stores to
+ * [-CE_LINEAR_MAX, CE_LINEAR_MAX], the invariant of a linear slab (a filter with negative lobes overshoots); the byte copy
+ * does not clamp.  tests/resample_linear_restatement.py restates this in numpy.
  *   BOX       f = 1 on (-0.5, 0.5], S = 0.5      BILINEAR  f = 1 - |x| on (-1, 1), S = 1
  *   BICUBIC   Keys' cubic with a = -0.5, S = 2    LANCZOS3  sinc(x) sinc(x / 3) on [-3, 3), S = 3 */
 enum ce_resample_filter {
@@ -454,13 +462,20 @@ enum ce_resample_filter {
  * unless len = w * h * 3 and out_len = out_w * out_h * 3. */
 int ce_resample_rgb8(ce_ctx *ctx, const uint8_t *rgb, size_t len, uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h,
                      int filter, uint8_t *out, size_t out_len);
+/* One packed float RGB image in linear light to another size, by the float resampler above.  Errors as ce_resample_rgb8, in
+ * the same order, with the lengths in bytes: len = w * h * 12, out_len = out_w * out_h * 12.  The input is taken as it is
+ * (a NaN spreads to the outputs whose taps cover it); the output is clamped as stated above. */
+int ce_resample_linear(ce_ctx *ctx, const float *rgb, size_t len, uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h, int filter,
+                       float *out, size_t out_len);
 /* Images [first, first + count) of src's reference or test slab (which: enum ce_batch_images) resampled into the same
  * indices of dst, a batch of another (or the same) shape on the same context - the images of a resident sweep at the
  * size a condition displays them (src/viewing.rs:244-301), with no upload and no host pixel pass.  Runs behind every
  * ce_batch_set_* of src so far and before any later launch on dst; touches no metric buffer and no stored scores or maps
  * of either batch; returns without waiting.  CE_ERR_INVALID_ARG, with the reason in ce_last_error, for a null handle,
- * batches of different contexts, src = dst, an unknown slab or filter, count = 0, a range past either batch's slots, or a
- * deep batch on either side (resampling u16 samples is not part of this). */
+ * batches of different contexts, src = dst, an unknown slab or filter, count = 0, a range past either batch's slots, a
+ * deep batch on either side (resampling u16 samples is not part of this: nothing outside the project defines its result,
+ * DESIGN.md section 17), or a linear batch paired with one that is not.  RGB8 -> RGB8 runs the fixed-point resampler,
+ * linear -> linear the float one; stream ordering and bindings are the same for both. */
 int ce_batch_resample(ce_batch *src, ce_batch *dst, uint32_t which, uint32_t first, uint32_t count, int filter);
 /* Both slabs - references [0, n_refs) and tests [0, n_pairs) - and src's pair -> reference bindings of those pairs, so
  * that ce_batch_run(dst, n_pairs, ...) follows directly (src/viewing.rs:244-301 applied to a whole grid).  Errors as
@@ -598,7 +613,9 @@ int ce_composite_rgba16(ce_ctx *ctx, const uint16_t *rgba, size_t len, uint32_t 
  *     readers work as on any batch;
  *   CE_ERR_INVALID_ARG, with the reason in ce_last_error and the batch still usable: CE_FLAG_XYB_ROUNDTRIP,
  *     ce_batch_image_heuristics, ce_batch_set_*_lut with a table, ce_batch_set_reference / ce_batch_set_test and every
- *     8- / 16-bit format (the *_10BIT ones included) through *_fmt, ce_batch_resample* from or into it, *_over, *_yuv.
+ *     8- / 16-bit format (the *_10BIT ones included) through *_fmt, ce_batch_resample* between it and a batch that is not linear, *_over, *_yuv.
+ *   ce_batch_resample / ce_batch_resample_pairs from a linear batch into a linear batch run the float resampler of the
+ *     viewing-simulation section above.
  *   CE_PIXEL_RGB_F32 on a batch that is not linear is refused the same way.
  * Not part of this: HLG (its OOTF couples the channels and needs a device powf), the BT.709 / BT.1886 gamma transfers,
  * primaries with a non-D65 white, limited-range RGB, ce_ref_* handles on linear batches and the pooled ce_eval_batch on
@@ -680,7 +697,7 @@ int ce_colour_matrix(int primaries, float out[9]);
  * ce_yuv_to_linear: one image of width x height to packed float RGB in host memory (out_len = width * height * 3 floats);
  * errors as above, CE_ERR_BAD_LENGTH for a wrong out_len.
  * Not part of this: HLG and the BT.709 / BT.1886 transfers, identity / YCgCo matrices, chroma sitings other than the centred
- * one, ce_ref_* handles and the pooled ce_eval_batch on linear batches, resampling of linear batches. */
+ * one, ce_ref_* handles and the pooled ce_eval_batch on linear batches. */
 int ce_batch_set_reference_yuv_cicp(ce_batch *b, uint32_t ref_index, const ce_yuv_image *image, const ce_colour *c);
 int ce_batch_set_test_yuv_cicp(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const ce_yuv_image *image, const ce_colour *c);
 int ce_yuv_to_linear(ce_ctx *ctx, const ce_yuv_image *image, const ce_colour *c, uint32_t width, uint32_t height, float *out, size_t out_len);
