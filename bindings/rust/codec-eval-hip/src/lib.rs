@@ -567,6 +567,27 @@ impl HipMetrics {
         self.check(rc, width, height, out.len())?;
         Ok(out)
     }
+
+    /// `ce_hlg_to_linear`: one image of BT.2100 HLG code values (`format`: `sys::CE_PIXEL_RGB8` / `RGBA8` / `RGB16` / `RGBA16`;
+    /// `pixels` are its bytes) read by `hlg` - primaries, depth, the display's peak and system gamma, the white that becomes
+    /// 1.0 - -> packed f32 RGB, display light with sRGB primaries.
+    pub fn hlg_to_linear(&mut self, pixels: &[u8], format: i32, hlg: &sys::ce_hlg, width: u32, height: u32) -> Result<Vec<f32>, HipError> {
+        let mut out = vec![0f32; width as usize * height as usize * 3];
+        let rc = unsafe {
+            sys::ce_hlg_to_linear(self.ctx, pixels.as_ptr().cast(), pixels.len(), format, hlg, width, height, out.as_mut_ptr(), out.len())
+        };
+        self.check(rc, width, height, pixels.len())?;
+        Ok(out)
+    }
+
+    /// `ce_yuv_hlg_to_linear`: one image's planes in HLG, in one kernel (`hlg.depth` is the integer RGB grid's, >= the samples').
+    pub fn yuv_hlg_to_linear(&mut self, image: &YuvPlanes<'_>, hlg: &sys::ce_hlg, width: u32, height: u32) -> Result<Vec<f32>, HipError> {
+        let c = image.to_sys(width, height)?;
+        let mut out = vec![0f32; width as usize * height as usize * 3];
+        let rc = unsafe { sys::ce_yuv_hlg_to_linear(self.ctx, &c, hlg, width, height, out.as_mut_ptr(), out.len()) };
+        self.check(rc, width, height, out.len())?;
+        Ok(out)
+    }
 }
 
 /// `ce_batch`: images of one shape resident on the device, scored in one launch.  Resampling one grid into another
@@ -644,6 +665,33 @@ impl HipBatch<'_> {
                              -> Result<(), HipError> {
         let c = image.to_sys(self.width, self.height)?;
         let rc = unsafe { sys::ce_batch_set_test_yuv_cicp(self.handle, pair_index, ref_index, &c, colour) };
+        self.check(rc, 0)
+    }
+
+    /// `ce_batch_set_reference_hlg`: BT.2100 HLG code values (`format` and `pixels` as `hlg_to_linear`) into a reference slot
+    /// of a LINEAR batch.
+    pub fn set_reference_hlg(&mut self, ref_index: u32, pixels: &[u8], format: i32, hlg: &sys::ce_hlg) -> Result<(), HipError> {
+        let rc = unsafe { sys::ce_batch_set_reference_hlg(self.handle, ref_index, pixels.as_ptr().cast(), pixels.len(), format, hlg) };
+        self.check(rc, pixels.len())
+    }
+
+    /// `ce_batch_set_test_hlg`: the same for the test image of pair `pair_index`, bound to reference `ref_index`.
+    pub fn set_test_hlg(&mut self, pair_index: u32, ref_index: u32, pixels: &[u8], format: i32, hlg: &sys::ce_hlg) -> Result<(), HipError> {
+        let rc = unsafe { sys::ce_batch_set_test_hlg(self.handle, pair_index, ref_index, pixels.as_ptr().cast(), pixels.len(), format, hlg) };
+        self.check(rc, pixels.len())
+    }
+
+    /// `ce_batch_set_reference_yuv_hlg`: a decoder's planes in HLG into a reference slot of a LINEAR batch.
+    pub fn set_reference_yuv_hlg(&mut self, ref_index: u32, image: &YuvPlanes<'_>, hlg: &sys::ce_hlg) -> Result<(), HipError> {
+        let c = image.to_sys(self.width, self.height)?;
+        let rc = unsafe { sys::ce_batch_set_reference_yuv_hlg(self.handle, ref_index, &c, hlg) };
+        self.check(rc, 0)
+    }
+
+    /// `ce_batch_set_test_yuv_hlg`: the same for the test image of pair `pair_index`, bound to reference `ref_index`.
+    pub fn set_test_yuv_hlg(&mut self, pair_index: u32, ref_index: u32, image: &YuvPlanes<'_>, hlg: &sys::ce_hlg) -> Result<(), HipError> {
+        let c = image.to_sys(self.width, self.height)?;
+        let rc = unsafe { sys::ce_batch_set_test_yuv_hlg(self.handle, pair_index, ref_index, &c, hlg) };
         self.check(rc, 0)
     }
 

@@ -62,6 +62,18 @@ pub struct ce_colour {
     pub white_nits: c_float,
 }
 
+/// `ce_hlg` (20 bytes): how BT.2100 HLG code values are to be read, with the display they are shown on.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ce_hlg {
+    pub primaries: c_int,
+    pub depth: u32,
+    pub peak_nits: c_float,
+    /// 0: BT.2100's rule from `peak_nits`
+    pub system_gamma: c_float,
+    pub white_nits: c_float,
+}
+
 /// `ce_scores` (40 bytes): a score is meaningful iff its bit is set in `valid`.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -286,6 +298,19 @@ extern "C" {
                                       c: *const ce_colour) -> c_int;
     pub fn ce_yuv_to_linear(ctx: *mut ce_ctx, image: *const ce_yuv_image, c: *const ce_colour, width: u32, height: u32, out: *mut c_float,
                             out_len: usize) -> c_int;
+    pub fn ce_batch_set_reference_hlg(b: *mut ce_batch, ref_index: u32, pixels: *const c_void, len: usize, format: c_int,
+                                      h: *const ce_hlg) -> c_int;
+    pub fn ce_batch_set_test_hlg(b: *mut ce_batch, pair_index: u32, ref_index: u32, pixels: *const c_void, len: usize, format: c_int,
+                                 h: *const ce_hlg) -> c_int;
+    pub fn ce_hlg_to_linear(ctx: *mut ce_ctx, pixels: *const c_void, len: usize, format: c_int, h: *const ce_hlg, w: u32, height: u32,
+                            out: *mut c_float, out_len: usize) -> c_int;
+    pub fn ce_batch_set_reference_yuv_hlg(b: *mut ce_batch, ref_index: u32, image: *const ce_yuv_image, h: *const ce_hlg) -> c_int;
+    pub fn ce_batch_set_test_yuv_hlg(b: *mut ce_batch, pair_index: u32, ref_index: u32, image: *const ce_yuv_image,
+                                     h: *const ce_hlg) -> c_int;
+    pub fn ce_yuv_hlg_to_linear(ctx: *mut ce_ctx, image: *const ce_yuv_image, h: *const ce_hlg, width: u32, height: u32, out: *mut c_float,
+                                out_len: usize) -> c_int;
+    pub fn ce_hlg_table(depth: u32, out: *mut c_float, n: usize) -> c_int;
+    pub fn ce_hlg_params(h: *const ce_hlg, out: *mut c_double) -> c_int;
     pub fn ce_batch_set_reference_over(b: *mut ce_batch, first_ref: u32, pixels: *const c_void, len: usize, format: c_int, n_bg: u32,
                                        backgrounds: *const u16) -> c_int;
     pub fn ce_batch_set_test_over(b: *mut ce_batch, first_pair: u32, ref_indices: *const u32, pixels: *const c_void, len: usize,

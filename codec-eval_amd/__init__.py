@@ -42,6 +42,7 @@ DEEP_DEPTHS = (8, 10, 12, 16)
 # ITU-T H.273 code points the CICP ingest takes (include/ce_metrics.h)
 PRIMARIES_BT709, PRIMARIES_BT2020, PRIMARIES_P3_D65 = 1, 9, 12
 TRANSFER_SRGB, TRANSFER_LINEAR, TRANSFER_PQ = 13, 8, 16
+TRANSFER_HLG = 18  # not a ce_colour transfer: HLG carries a display description of its own (HlgDescription)
 BATCH_REFERENCES, BATCH_TESTS = 0, 1  # enum ce_batch_images
 DEFAULT_INTENSITY_TARGET = 80.0
 DSSIM_MAX_LEVELS = 5  # CE_DSSIM_MAX_LEVELS
@@ -127,6 +128,10 @@ class CeYuvImage(C.Structure):
 
 class CeColour(C.Structure):
     _fields_ = [("primaries", C.c_int), ("transfer", C.c_int), ("depth", C.c_uint32), ("white_nits", C.c_float)]
+
+
+class CeHlg(C.Structure):
+    _fields_ = [("primaries", C.c_int), ("depth", C.c_uint32), ("peak_nits", C.c_float), ("system_gamma", C.c_float), ("white_nits", C.c_float)]
 
 
 class CodecEvalError(RuntimeError):
@@ -249,6 +254,14 @@ _PROTOTYPES = [
     ("ce_batch_set_reference_yuv_cicp", _i, [_vp, _u32, C.POINTER(CeYuvImage), C.POINTER(CeColour)]),
     ("ce_batch_set_test_yuv_cicp", _i, [_vp, _u32, _u32, C.POINTER(CeYuvImage), C.POINTER(CeColour)]),
     ("ce_yuv_to_linear", _i, [_vp, C.POINTER(CeYuvImage), C.POINTER(CeColour), _u32, _u32, _vp, _sz]),
+    ("ce_batch_set_reference_hlg", _i, [_vp, _u32, _vp, _sz, _i, C.POINTER(CeHlg)]),
+    ("ce_batch_set_test_hlg", _i, [_vp, _u32, _u32, _vp, _sz, _i, C.POINTER(CeHlg)]),
+    ("ce_hlg_to_linear", _i, [_vp, _vp, _sz, _i, C.POINTER(CeHlg), _u32, _u32, _vp, _sz]),
+    ("ce_batch_set_reference_yuv_hlg", _i, [_vp, _u32, C.POINTER(CeYuvImage), C.POINTER(CeHlg)]),
+    ("ce_batch_set_test_yuv_hlg", _i, [_vp, _u32, _u32, C.POINTER(CeYuvImage), C.POINTER(CeHlg)]),
+    ("ce_yuv_hlg_to_linear", _i, [_vp, C.POINTER(CeYuvImage), C.POINTER(CeHlg), _u32, _u32, _vp, _sz]),
+    ("ce_hlg_table", _i, [_u32, _vp, _sz]),
+    ("ce_hlg_params", _i, [C.POINTER(CeHlg), _dp]),
     ("ce_batch_set_reference_over", _i, [_vp, _u32, _vp, _sz, _i, _u32, _vp]),
     ("ce_batch_set_test_over", _i, [_vp, _u32, _vp, _vp, _sz, _i, _u32, _vp]),
     ("ce_composite_rgba8", _i, [_vp, _vp, _sz, _u32, _u32, _vp, _vp, _sz]),
@@ -355,6 +368,47 @@ class ColourDescription:
 ColourDescription.SRGB = ColourDescription(PRIMARIES_BT709, TRANSFER_SRGB, 8)
 ColourDescription.DISPLAY_P3 = ColourDescription(PRIMARIES_P3_D65, TRANSFER_SRGB, 8)
 ColourDescription.BT2020_PQ = ColourDescription(PRIMARIES_BT2020, TRANSFER_PQ, 10, 203.0)
+
+
+@dataclass(frozen=True)
+class HlgDescription:
+    """How BT.2100 HLG code values are to be read (ce_hlg): H.273 colour primaries (BT.2100 itself: 9), bits per sample, the
+    display's nominal peak luminance L_W, the system gamma (0: BT.2100's rule from the peak) and the luminance that becomes
+    1.0.  Accepted wherever a ColourDescription is; the image is scored in linear light."""
+    primaries: int = PRIMARIES_BT2020
+    depth: int = 10
+    peak_nits: float = 1000.0
+    system_gamma: float = 0.0
+    white_nits: float = 203.0
+
+    def with_depth(self, depth: int) -> "HlgDescription":
+        return HlgDescription(self.primaries, depth, self.peak_nits, self.system_gamma, self.white_nits)
+
+    @property
+    def is_srgb(self) -> bool:
+        return False
+
+    def _c(self) -> CeHlg:
+        return CeHlg(self.primaries, self.depth, self.peak_nits, self.system_gamma, self.white_nits)
+
+
+HlgDescription.BT2100_HLG = HlgDescription()
+
+
+def hlg_table(depth: int) -> np.ndarray:
+    """The HLG ingest's inverse-OETF table of code value -> scene light in [0, 1] (ce_hlg_table), float32."""
+    out = np.empty(1 << depth if 0 < depth <= 16 else 1, np.float32)
+    _host_check(lib().ce_hlg_table(depth, out.ctypes.data, out.size))
+    return out
+
+
+def hlg_params(description: "HlgDescription") -> np.ndarray:
+    """kR, kG, kB, gamma - 1 and A = peak_nits / white_nits of a description (ce_hlg_params), float64: exactly what the
+    kernel is handed."""
+    out = np.empty(5, np.float64)
+    c = description._c()
+    _host_check(lib().ce_hlg_params(C.byref(c), out.ctypes.data_as(_dp)))
+    return out
 
 
 def _cicp_fmt(a: np.ndarray) -> int:
@@ -1001,6 +1055,25 @@ class Context:
                                             out.size))
         return out
 
+    def hlg_to_linear(self, pixels, width: int, height: int, description: "HlgDescription") -> np.ndarray:
+        """One image of uint8 / uint16 RGB(A) HLG code values read by `description` -> [h, w, 3] float32 display light with
+        sRGB primaries, 1.0 = white_nits, on the device (ce_hlg_to_linear)."""
+        a = np.ascontiguousarray(pixels)
+        out = np.empty((height, width, 3), np.float32)
+        c = description._c()
+        self._check(lib().ce_hlg_to_linear(self._h, a.ctypes.data, a.nbytes, _cicp_fmt(a), C.byref(c), width, height, out.ctypes.data,
+                                           out.size))
+        return out
+
+    def yuv_hlg_to_linear(self, image: "YuvImage", width: int, height: int, description: "HlgDescription") -> np.ndarray:
+        """A decoder's Y'CbCr planes in HLG -> (height, width, 3) float32, in one kernel (ce_yuv_hlg_to_linear): yuv_to_rgb16
+        at depth_out = description.depth followed by hlg_to_linear, bit for bit."""
+        c, _keep = image._c()
+        d = description._c()
+        out = np.empty((height, width, 3), np.float32)
+        self._check(lib().ce_yuv_hlg_to_linear(self._h, C.byref(c), C.byref(d), width, height, out.ctypes.data, out.size))
+        return out
+
     def batch_deep(self, width: int, height: int, max_refs: int, max_pairs: int, ref_depth: int, test_depth: int) -> "Batch":
         """A Batch whose slabs hold uint16 samples of the given depths (8, 10, 12 or 16 bits per side)."""
         return Batch(self, width, height, max_refs, max_pairs, depths=(ref_depth, test_depth))
@@ -1191,6 +1264,27 @@ class Batch:
         c, _keep = image._c()
         col = colour._c()
         self.ctx._check(lib().ce_batch_set_test_yuv_cicp(self._h, pair_index, ref_index, C.byref(c), C.byref(col)))
+        self._pair_ref[pair_index] = ref_index
+
+    # BT.2100 HLG code values, and planes, -> display light on the device, into a slot of a linear batch
+    def set_reference_hlg(self, ref_index: int, pixels, description: "HlgDescription"):
+        a, c = np.ascontiguousarray(pixels), description._c()
+        self.ctx._check(lib().ce_batch_set_reference_hlg(self._h, ref_index, a.ctypes.data, a.nbytes, _cicp_fmt(a), C.byref(c)))
+
+    def set_test_hlg(self, pair_index: int, ref_index: int, pixels, description: "HlgDescription"):
+        a, c = np.ascontiguousarray(pixels), description._c()
+        self.ctx._check(lib().ce_batch_set_test_hlg(self._h, pair_index, ref_index, a.ctypes.data, a.nbytes, _cicp_fmt(a), C.byref(c)))
+        self._pair_ref[pair_index] = ref_index
+
+    def set_reference_yuv_hlg(self, ref_index: int, image: "YuvImage", description: "HlgDescription"):
+        c, _keep = image._c()
+        d = description._c()
+        self.ctx._check(lib().ce_batch_set_reference_yuv_hlg(self._h, ref_index, C.byref(c), C.byref(d)))
+
+    def set_test_yuv_hlg(self, pair_index: int, ref_index: int, image: "YuvImage", description: "HlgDescription"):
+        c, _keep = image._c()
+        d = description._c()
+        self.ctx._check(lib().ce_batch_set_test_yuv_hlg(self._h, pair_index, ref_index, C.byref(c), C.byref(d)))
         self._pair_ref[pair_index] = ref_index
 
     # a transparent image composited over solid colours on the device: one upload fills len(backgrounds) consecutive slots

@@ -1559,12 +1559,15 @@ int ce_colour_matrix(int primaries, float out[9])
 }
 
 namespace {
-// what one CICP ingest runs with: the device table of (transfer, depth, white_nits) and the matrix (has_matrix: primaries != 1)
+// what one CICP ingest runs with: the device table of (transfer, depth, white_nits) and the matrix (has_matrix: primaries != 1);
+// an HLG ingest (hlg_colour_check) runs with the same and with ce_hlg_params' five doubles
 struct cicp_plan {
     const float *d_table;
     uint32_t maxv;
     bool has_matrix;
     float m[9];
+    bool hlg = false;
+    double hlg_params[5];
 };
 
 // the colour description alone: depth, transfer and primaries from the lists of the header; fills maxv and the matrix
@@ -1572,7 +1575,8 @@ int cicp_colour_check(ce_ctx *ctx, const ce_colour *c, cicp_plan *plan)
 {
     if (!deep_depth_ok(c->depth)) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: depth must be 8, 10, 12 or 16, got " + std::to_string(c->depth));
     if (c->transfer != 13 && c->transfer != 8 && c->transfer != 16)
-        return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: transfer must be 13 (sRGB), 8 (linear) or 16 (PQ), got " + std::to_string(c->transfer));
+        return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: transfer must be 13 (sRGB), 8 (linear) or 16 (PQ), got " + std::to_string(c->transfer) +
+                                                 (c->transfer == 18 ? " (HLG carries a display description: ce_batch_set_*_hlg)" : ""));
     if (c->transfer == 16 && !(c->white_nits > 0.0f && std::isfinite(c->white_nits)))
         return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: PQ needs white_nits > 0");
     if (!ce_build_colour_matrix(c->primaries, plan->m))
@@ -1620,6 +1624,14 @@ int cicp_check(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce
     return cicp_table(ctx, c, plan);
 }
 
+// the conversion of one checked image of code values at d_src into d_dst: the CICP pixel, or with plan.hlg the HLG pixel
+int launch_cicp_into(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, float *d_dst, size_t n_px, const cicp_plan &plan)
+{
+    const float *m = plan.has_matrix ? plan.m : nullptr;
+    if (plan.hlg) return ce_launch_hlg(ctx, stream, format, d_src, d_dst, n_px, plan.d_table, plan.maxv, m, plan.hlg_params);
+    return ce_launch_cicp(ctx, stream, format, d_src, d_dst, n_px, plan.d_table, plan.maxv, m);
+}
+
 // one tagged image through the wide staging pair of upload_fmt into the slot at dst, on the batch's upload stream
 int upload_cicp(ce_batch *b, uint8_t *dst, const void *pixels, size_t len, int format, const cicp_plan &plan)
 {
@@ -1628,9 +1640,7 @@ int upload_cicp(ce_batch *b, uint8_t *dst, const void *pixels, size_t len, int f
     const int k = b->next_wide;
     b->next_wide ^= 1;
     if (int rc = wide_stage(b, k, pixels, len)) return rc;
-    if (int rc = ce_launch_cicp(ctx, b->up_stream, format, b->d_wide[k], reinterpret_cast<float *>(dst), (size_t)b->w * b->h, plan.d_table,
-                                plan.maxv, plan.has_matrix ? plan.m : nullptr))
-        return rc;
+    if (int rc = launch_cicp_into(ctx, b->up_stream, format, b->d_wide[k], reinterpret_cast<float *>(dst), (size_t)b->w * b->h, plan)) return rc;
     CE_HIP(ctx, hipEventRecord(b->ev_wide[k], b->up_stream));
     b->wide_busy[k] = true;
     b->uploads_pending = true;
@@ -1661,15 +1671,9 @@ int ce_batch_set_test_cicp(ce_batch *b, uint32_t pair_index, uint32_t ref_index,
     return upload_cicp(b, b->d_tests + (size_t)pair_index * b->img_bytes, pixels, len, format, plan);
 }
 
-int ce_cicp_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_colour *c, uint32_t w, uint32_t h, float *out,
-                      size_t out_len)
+// one checked image of code values -> packed f32 RGB in host memory, on the context's stream
+static int cicp_to_host(ce_ctx *ctx, const void *pixels, size_t len, int format, const cicp_plan &plan, size_t n_px, float *out)
 {
-    if (!ctx || !out) return CE_ERR_INVALID_ARG;
-    if (w == 0 || h == 0) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: empty image");
-    const size_t n_px = (size_t)w * h;
-    cicp_plan plan;
-    if (int rc = cicp_check(ctx, pixels, len, format, c, n_px, &plan)) return rc;
-    if (out_len != n_px * 3) return fail(ctx, CE_ERR_BAD_LENGTH, "CICP ingest: out_len must be " + std::to_string(n_px * 3) + " floats, got " + std::to_string(out_len));
     CE_HIP(ctx, hipSetDevice(ctx->device));
     void *d_in = nullptr;
     float *d_out = nullptr;
@@ -1680,12 +1684,137 @@ int ce_cicp_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, c
     }
     int rc = CE_OK;
     if (hipMemcpyAsync(d_in, pixels, len, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = fail(ctx, CE_ERR_BACKEND, "H2D failed (CICP ingest)");
-    if (rc == CE_OK) rc = ce_launch_cicp(ctx, ctx->stream, format, d_in, d_out, n_px, plan.d_table, plan.maxv, plan.has_matrix ? plan.m : nullptr);
+    if (rc == CE_OK) rc = launch_cicp_into(ctx, ctx->stream, format, d_in, d_out, n_px, plan);
     if (rc == CE_OK && hipMemcpyAsync(out, d_out, n_px * 12, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, CE_ERR_BACKEND, "D2H failed (CICP ingest)");
     if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == CE_OK) rc = fail(ctx, CE_ERR_BACKEND, "sync failed (CICP ingest)");
     hipFree(d_in);
     hipFree(d_out);
     return rc;
+}
+
+int ce_cicp_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_colour *c, uint32_t w, uint32_t h, float *out,
+                      size_t out_len)
+{
+    if (!ctx || !out) return CE_ERR_INVALID_ARG;
+    if (w == 0 || h == 0) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: empty image");
+    const size_t n_px = (size_t)w * h;
+    cicp_plan plan;
+    if (int rc = cicp_check(ctx, pixels, len, format, c, n_px, &plan)) return rc;
+    if (out_len != n_px * 3) return fail(ctx, CE_ERR_BAD_LENGTH, "CICP ingest: out_len must be " + std::to_string(n_px * 3) + " floats, got " + std::to_string(out_len));
+    return cicp_to_host(ctx, pixels, len, format, plan, n_px, out);
+}
+
+// ---- HLG ingest (hlg.hip) ------------------------------------------------------------------------
+int ce_hlg_table(uint32_t depth, float *out, size_t n)
+{
+    if (!out || !deep_depth_ok(depth) || n != ((size_t)1 << depth))
+        return fail(nullptr, CE_ERR_INVALID_ARG, "ce_hlg_table: depth 8, 10, 12 or 16 and n = 2^depth");
+    ce_build_hlg_table((1u << depth) - 1u, out);
+    return CE_OK;
+}
+
+// the description alone: primaries and depth from the header's lists, the two luminances finite and > 0, the system gamma
+// - given, or BT.2100's rule from the peak - in [0.8, 1.6]; out = {kR, kG, kB, gamma - 1, A}
+static int hlg_describe(ce_ctx *ctx, const ce_hlg *h, double out[5])
+{
+    if (!deep_depth_ok(h->depth)) return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: depth must be 8, 10, 12 or 16, got " + std::to_string(h->depth));
+    if (!ce_build_luminance_row(h->primaries, out))
+        return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: primaries must be 1 (BT.709), 9 (BT.2020) or 12 (Display P3), got " + std::to_string(h->primaries));
+    if (!(h->peak_nits > 0.0f && std::isfinite(h->peak_nits))) return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: peak_nits must be finite and > 0");
+    if (!(h->white_nits > 0.0f && std::isfinite(h->white_nits))) return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: white_nits must be finite and > 0");
+    const double gamma = h->system_gamma != 0.0f ? (double)h->system_gamma : 1.2 + 0.42 * std::log10((double)h->peak_nits / 1000.0);
+    if (!(gamma >= 0.8 && gamma <= 1.6))
+        return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: the system gamma must lie in [0.8, 1.6], got " + std::to_string(gamma));
+    out[3] = gamma - 1.0;
+    out[4] = (double)h->peak_nits / (double)h->white_nits;
+    return CE_OK;
+}
+
+int ce_hlg_params(const ce_hlg *h, double out[5])
+{
+    if (!h || !out) return fail(nullptr, CE_ERR_INVALID_ARG, "ce_hlg_params: null pointer");
+    return hlg_describe(nullptr, h, out);
+}
+
+// a checked description as an ingest's plan: maxv, the primaries matrix and the five doubles
+static int hlg_colour_check(ce_ctx *ctx, const ce_hlg *h, cicp_plan *plan)
+{
+    if (int rc = hlg_describe(ctx, h, plan->hlg_params)) return rc;
+    ce_build_colour_matrix(h->primaries, plan->m);
+    plan->hlg = true;
+    plan->has_matrix = h->primaries != 1;
+    plan->maxv = (1u << h->depth) - 1u;
+    plan->d_table = nullptr;
+    return CE_OK;
+}
+
+// the inverse-OETF table of a checked description on the device, one per context and depth, kept next to the CICP tables
+static int hlg_table_dev(ce_ctx *ctx, const ce_hlg *h, cicp_plan *plan)
+{
+    const auto key = std::make_tuple(18, h->depth, 0u);
+    auto it = ctx->cicp_tables.find(key);
+    if (it == ctx->cicp_tables.end()) {
+        std::vector<float> host((size_t)plan->maxv + 1);
+        ce_build_hlg_table(plan->maxv, host.data());
+        CE_HIP(ctx, hipSetDevice(ctx->device));
+        float *d = nullptr;
+        CE_HIP(ctx, hipMalloc(&d, host.size() * sizeof(float)));
+        if (hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+            hipFree(d);
+            return fail(ctx, CE_ERR_BACKEND, "H2D failed (HLG table)");
+        }
+        it = ctx->cicp_tables.emplace(key, d).first;
+    }
+    plan->d_table = it->second;
+    return CE_OK;
+}
+
+static int hlg_check(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_hlg *h, size_t n_px, cicp_plan *plan)
+{
+    if (!pixels || !h) return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: null pointer");
+    const bool fmt8 = format == CE_PIXEL_RGB8 || format == CE_PIXEL_RGBA8, fmt16 = format == CE_PIXEL_RGB16 || format == CE_PIXEL_RGBA16;
+    if (!fmt8 && !fmt16) return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: format must be CE_PIXEL_RGB8, RGBA8, RGB16 or RGBA16");
+    if (fmt8 && deep_depth_ok(h->depth) && h->depth != 8)
+        return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: an 8-bit format needs depth 8, got " + std::to_string(h->depth));
+    if (int rc = hlg_colour_check(ctx, h, plan)) return rc;
+    if (len != n_px * ce_pixel_bytes(format)) return bad_length(ctx, n_px * ce_pixel_bytes(format), len);
+    return hlg_table_dev(ctx, h, plan);
+}
+
+static const char *const kHlgWantsLinear = "HLG ingest writes linear light: it needs a linear batch (ce_batch_create_linear)";
+
+int ce_batch_set_reference_hlg(ce_batch *b, uint32_t ref_index, const void *pixels, size_t len, int format, const ce_hlg *h)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    if (!b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kHlgWantsLinear);
+    if (ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "ref_index out of range");
+    cicp_plan plan;
+    if (int rc = hlg_check(b->ctx, pixels, len, format, h, (size_t)b->w * b->h, &plan)) return rc;
+    invalidate_reference_state(b);
+    return upload_cicp(b, b->d_refs + (size_t)ref_index * b->img_bytes, pixels, len, format, plan);
+}
+
+int ce_batch_set_test_hlg(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format, const ce_hlg *h)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    if (!b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kHlgWantsLinear);
+    if (pair_index >= b->max_pairs || ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "pair/ref index out of range");
+    cicp_plan plan;
+    if (int rc = hlg_check(b->ctx, pixels, len, format, h, (size_t)b->w * b->h, &plan)) return rc;
+    if (int rc = ce_batch_bind_pair(b, pair_index, ref_index)) return rc;
+    return upload_cicp(b, b->d_tests + (size_t)pair_index * b->img_bytes, pixels, len, format, plan);
+}
+
+int ce_hlg_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_hlg *h, uint32_t w, uint32_t height, float *out,
+                     size_t out_len)
+{
+    if (!ctx || !out) return CE_ERR_INVALID_ARG;
+    if (w == 0 || height == 0) return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: empty image");
+    const size_t n_px = (size_t)w * height;
+    cicp_plan plan;
+    if (int rc = hlg_check(ctx, pixels, len, format, h, n_px, &plan)) return rc;
+    if (out_len != n_px * 3) return fail(ctx, CE_ERR_BAD_LENGTH, "HLG ingest: out_len must be " + std::to_string(n_px * 3) + " floats, got " + std::to_string(out_len));
+    return cicp_to_host(ctx, pixels, len, format, plan, n_px, out);
 }
 
 static int leaf(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test, size_t test_len,
@@ -2000,10 +2129,13 @@ static void yuv_pack(const ce_yuv_image *img, yuv_plan *plan, uint8_t *h_stage, 
 }
 
 // the conversion of one checked image into dst: integer RGB (u8, or u16 of `depth`), or with `lin` the fused linear-light
-// ingest of a linear batch (yuv_cicp.hip), whose integer grid is the one plan.dev.k was built for
+// ingest of a linear batch (yuv_cicp.hip; yuv_hlg.hip for an HLG plan), whose integer grid is the one plan.dev.k was built for
 static int launch_yuv_into(ce_ctx *ctx, hipStream_t stream, const yuv_plan &plan, uint32_t w, uint32_t h, uint8_t *dst, uint32_t depth,
                            const cicp_plan *lin)
 {
+    if (lin && lin->hlg)
+        return ce_launch_yuv_hlg(ctx, stream, plan.dev, w, h, reinterpret_cast<float *>(dst), lin->d_table, lin->maxv, lin->has_matrix ? lin->m : nullptr,
+                                 lin->hlg_params);
     if (lin)
         return ce_launch_yuv_cicp(ctx, stream, plan.dev, w, h, reinterpret_cast<float *>(dst), lin->d_table, lin->maxv, lin->has_matrix ? lin->m : nullptr);
     return ce_launch_yuv(ctx, stream, plan.dev, w, h, dst, depth != 0, depth ? depth : 8);
@@ -2148,18 +2280,13 @@ int ce_batch_set_test_yuv_cicp(ce_batch *b, uint32_t pair_index, uint32_t ref_in
     return upload_yuv(b, b->d_tests + (size_t)pair_index * b->img_bytes, image, plan, 0, &lin);
 }
 
-// one image -> packed f32 RGB in host memory through the leaf scratch, on the context's stream (as yuv_to_host)
-int ce_yuv_to_linear(ce_ctx *ctx, const ce_yuv_image *image, const ce_colour *c, uint32_t w, uint32_t h, float *out, size_t out_len)
+// one checked image -> packed f32 RGB in host memory through the leaf scratch, on the context's stream (as yuv_to_host)
+static int yuv_linear_to_host(ce_ctx *ctx, const ce_yuv_image *image, yuv_plan &plan, const cicp_plan &lin, uint32_t w, uint32_t h, float *out,
+                              size_t out_len, const char *what)
 {
-    if (!ctx) return CE_ERR_INVALID_ARG;
-    if (!out) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: null output");
-    if (w == 0 || h == 0) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: empty image");
-    yuv_plan plan;
-    cicp_plan lin;
-    if (int rc = yuv_cicp_check(ctx, image, c, w, h, &plan, &lin)) return rc;
     const size_t samples = (size_t)w * h * 3, out_bytes = samples * sizeof(float);
     if (out_len != samples)
-        return fail(ctx, CE_ERR_BAD_LENGTH, "Y'CbCr CICP ingest: out_len must be " + std::to_string(samples) + " floats, got " + std::to_string(out_len));
+        return fail(ctx, CE_ERR_BAD_LENGTH, std::string(what) + ": out_len must be " + std::to_string(samples) + " floats, got " + std::to_string(out_len));
     const bool host = image->memory == CE_MEM_HOST;
     if (int rc = leaf_scratch(ctx, host ? plan.total : 1, out_bytes)) return rc;
     if (host) {
@@ -2171,6 +2298,68 @@ int ce_yuv_to_linear(ce_ctx *ctx, const ce_yuv_image *image, const ce_colour *c,
     CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
     std::memcpy(out, ctx->leaf_h, out_bytes);
     return CE_OK;
+}
+
+int ce_yuv_to_linear(ce_ctx *ctx, const ce_yuv_image *image, const ce_colour *c, uint32_t w, uint32_t h, float *out, size_t out_len)
+{
+    if (!ctx) return CE_ERR_INVALID_ARG;
+    if (!out) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: null output");
+    if (w == 0 || h == 0) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: empty image");
+    yuv_plan plan;
+    cicp_plan lin;
+    if (int rc = yuv_cicp_check(ctx, image, c, w, h, &plan, &lin)) return rc;
+    return yuv_linear_to_host(ctx, image, plan, lin, w, h, out, out_len, "Y'CbCr CICP ingest");
+}
+
+// ---- Y'CbCr planes in HLG into a linear batch (yuv_hlg.hip) -----------------------------------
+
+// everything *_yuv refuses about the image and *_hlg about the description, and their one joint rule: the integer RGB grid
+// between the two halves (h->depth) is no coarser than the samples
+static int yuv_hlg_check(ce_ctx *ctx, const ce_yuv_image *img, const ce_hlg *hd, uint32_t w, uint32_t h, yuv_plan *plan, cicp_plan *lin)
+{
+    if (!img) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: null image");
+    if (!hd) return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: null pointer");
+    if (int rc = hlg_colour_check(ctx, hd, lin)) return rc;
+    if (int rc = yuv_check(ctx, img, w, h, hd->depth, plan)) return rc;
+    if (hd->depth < (uint32_t)img->depth)
+        return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr HLG ingest: the description's depth " + std::to_string(hd->depth) + " is under the samples' " +
+                                                 std::to_string(img->depth) + " bits");
+    return hlg_table_dev(ctx, hd, lin);
+}
+
+int ce_batch_set_reference_yuv_hlg(ce_batch *b, uint32_t ref_index, const ce_yuv_image *image, const ce_hlg *h)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    if (!b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kHlgWantsLinear);
+    if (ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "ref_index out of range");
+    yuv_plan plan;
+    cicp_plan lin;
+    if (int rc = yuv_hlg_check(b->ctx, image, h, b->w, b->h, &plan, &lin)) return rc;
+    invalidate_reference_state(b);
+    return upload_yuv(b, b->d_refs + (size_t)ref_index * b->img_bytes, image, plan, 0, &lin);
+}
+
+int ce_batch_set_test_yuv_hlg(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const ce_yuv_image *image, const ce_hlg *h)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    if (!b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kHlgWantsLinear);
+    if (pair_index >= b->max_pairs || ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "pair/ref index out of range");
+    yuv_plan plan;
+    cicp_plan lin;
+    if (int rc = yuv_hlg_check(b->ctx, image, h, b->w, b->h, &plan, &lin)) return rc;
+    if (int rc = ce_batch_bind_pair(b, pair_index, ref_index)) return rc;
+    return upload_yuv(b, b->d_tests + (size_t)pair_index * b->img_bytes, image, plan, 0, &lin);
+}
+
+int ce_yuv_hlg_to_linear(ce_ctx *ctx, const ce_yuv_image *image, const ce_hlg *hd, uint32_t w, uint32_t h, float *out, size_t out_len)
+{
+    if (!ctx) return CE_ERR_INVALID_ARG;
+    if (!out) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: null output");
+    if (w == 0 || h == 0) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: empty image");
+    yuv_plan plan;
+    cicp_plan lin;
+    if (int rc = yuv_hlg_check(ctx, image, hd, w, h, &plan, &lin)) return rc;
+    return yuv_linear_to_host(ctx, image, plan, lin, w, h, out, out_len, "Y'CbCr HLG ingest");
 }
 
 // ---- alpha: composited over solid backgrounds (alpha.hip) ----------------------------------------

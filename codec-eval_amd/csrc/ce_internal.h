@@ -85,7 +85,8 @@ struct ce_ctx {
     struct ce_batch *leaf_deep = nullptr;  // the one-pair deep batch of ce_eval_pair_deep (remade when shape or depths change)
     struct ce_batch *leaf_linear = nullptr;  // the one-pair linear batch of ce_eval_pair_linear (remade when the shape changes)
     // transfer tables of the CICP ingest (cicp.hip), 2^depth entries each, keyed by (transfer, depth, bits of white_nits);
-    // built by the first ingest that needs one and kept until the context goes (ce_api.cpp: cicp_table)
+    // built by the first ingest that needs one and kept until the context goes (ce_api.cpp: cicp_table).  The HLG ingest's
+    // inverse-OETF tables (hlg.hip) live here too, one per depth, under H.273's code for HLG: (18, depth, 0) (hlg_table_dev)
     std::map<std::tuple<int, uint32_t, uint32_t>, float *> cicp_tables;
 
     // profiling
@@ -424,7 +425,19 @@ int ce_launch_cicp(ce_ctx *ctx, hipStream_t stream, int format, const void *d_sr
 int ce_launch_yuv_cicp(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32_t w, uint32_t h, float *d_dst, const float *d_table,
                        uint32_t maxv, const float *matrix);
 
+// ce_launch_cicp with the HLG pixel (hlg.hip): d_table is the inverse-OETF table, params = {kR, kG, kB, gamma - 1, A} as
+// ce_hlg_params returns them; between the gather and the matrix, k = (float)(A * hlg_pow(ys, gamma - 1)) scales the three
+int ce_launch_hlg(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, float *d_dst, size_t n_pixels, const float *d_table,
+                  uint32_t maxv, const float *matrix, const double params[5]);
+// ce_launch_yuv_cicp with the HLG pixel, one launch (yuv_hlg.hip)
+int ce_launch_yuv_hlg(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32_t w, uint32_t h, float *d_dst, const float *d_table,
+                      uint32_t maxv, const float *matrix, const double params[5]);
+
 // host-side constant builders (ce_tables.cpp)
+// the HLG ingest's inverse-OETF table (include/ce_metrics.h: ce_hlg_table) and the Y row of the f64 XYZ <- src matrix of
+// `primaries` (ce_hlg_params' kR, kG, kB); false for primaries that are not offered
+void ce_build_hlg_table(uint32_t maxv, float *lut);
+bool ce_build_luminance_row(int primaries, double k[3]);
 // the CICP ingest's transfer table (include/ce_metrics.h: ce_transfer_table) and primaries matrix (ce_colour_matrix); false
 // for a code point that is not offered
 bool ce_build_transfer_table(int transfer, uint32_t maxv, double white_nits, float *lut);

@@ -343,11 +343,12 @@ void rgb_to_xyz(const double xy[8], double m[9])
 
 // Colour primaries 1 (BT.709), 9 (BT.2020) and 12 (Display P3, D65), H.273's chromaticities: M = inv(XYZ <- sRGB) * (XYZ <-
 // src) in f64, rounded once to f32; primaries 1 gives the identity (the ingest does not multiply then).
+static const double k709[8] = {0.640, 0.330, 0.300, 0.600, 0.150, 0.060, 0.3127, 0.3290};
+static const double k2020[8] = {0.708, 0.292, 0.170, 0.797, 0.131, 0.046, 0.3127, 0.3290};
+static const double kP3[8] = {0.680, 0.320, 0.265, 0.690, 0.150, 0.060, 0.3127, 0.3290};
+
 bool ce_build_colour_matrix(int primaries, float m[9])
 {
-    static const double k709[8] = {0.640, 0.330, 0.300, 0.600, 0.150, 0.060, 0.3127, 0.3290};
-    static const double k2020[8] = {0.708, 0.292, 0.170, 0.797, 0.131, 0.046, 0.3127, 0.3290};
-    static const double kP3[8] = {0.680, 0.320, 0.265, 0.690, 0.150, 0.060, 0.3127, 0.3290};
     if (primaries == 1) {
         for (int i = 0; i < 9; i++) m[i] = (i % 4 == 0) ? 1.0f : 0.0f;
         return true;
@@ -360,5 +361,29 @@ bool ce_build_colour_matrix(int primaries, float m[9])
     rgb_to_xyz(src, s);
     for (int r = 0; r < 3; r++)
         for (int c = 0; c < 3; c++) m[3 * r + c] = (float)((ai[3 * r] * s[c] + ai[3 * r + 1] * s[3 + c]) + ai[3 * r + 2] * s[6 + c]);
+    return true;
+}
+
+// ---- HLG ingest (include/ce_metrics.h: ce_hlg_table, ce_hlg_params) --------------------------------
+// BT.2100's HLG inverse OETF with its published constants, in f64 per code point x = v / maxv and rounded once to f32:
+// scene light in [0, 1].  The f64 value at x = 1 is 1.00000003, which rounds to 1.0f.
+void ce_build_hlg_table(uint32_t maxv, float *lut)
+{
+    const double a = 0.17883277, b = 0.28466892, c = 0.55991073;
+    for (uint32_t i = 0; i <= maxv; i++) {
+        const double x = (double)i / (double)maxv;
+        lut[i] = (float)(x <= 0.5 ? x * x / 3.0 : (std::exp((x - c) / a) + b) / 12.0);
+    }
+}
+
+// The luminance coefficients of the tagged primaries: the Y row of the f64 XYZ <- src matrix ce_build_colour_matrix starts
+// from (BT.2020: 0.2627, 0.6780, 0.0593 at four decimals).
+bool ce_build_luminance_row(int primaries, double k[3])
+{
+    const double *src = primaries == 1 ? k709 : primaries == 9 ? k2020 : primaries == 12 ? kP3 : nullptr;
+    if (!src) return false;
+    double m[9];
+    rgb_to_xyz(src, m);
+    k[0] = m[3], k[1] = m[4], k[2] = m[5];
     return true;
 }

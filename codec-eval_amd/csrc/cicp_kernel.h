@@ -30,48 +30,68 @@ __device__ __forceinline__ void store12(float *p, const float (&o)[12])
     }
 }
 
-// FMT: CE_PIXEL_RGB8 / RGBA8 / RGB16 / RGBA16 (alpha dropped).  A thread converts one group of four pixels from the
-// registers its aligned loads filled (12 bytes: three dwords; 16: one uint4; 24: three uint2; 32: two uint4) and stores 48
-// bytes; the last n_pixels % 4 pixels go sample by sample, one pixel to a thread of block 0.  The table is gathered from
-// global memory at every depth: 1, 4 and 16 KB stay in the vector L1 and the 256 KB of depth 16 in L2, one code path.
-template <int FMT, bool MATRIX>
-__global__ __launch_bounds__(kCicpBlock) void k_cicp(const cicp_args a)
+// The samples of group `tid` (four pixels) of a packed FMT image at src, in memory order, from aligned loads (12 bytes: three
+// dwords; 16: one uint4; 24: three uint2; 32: two uint4).  k_cicp's and, in hlg_kernel.h, k_hlg's.
+template <int FMT>
+__device__ __forceinline__ void cicp_load_group(const void *src, size_t tid,
+                                                uint32_t (&s)[4 * ((FMT == CE_PIXEL_RGBA8 || FMT == CE_PIXEL_RGBA16) ? 4 : 3)])
 {
     constexpr bool S16 = FMT == CE_PIXEL_RGB16 || FMT == CE_PIXEL_RGBA16, ALPHA = FMT == CE_PIXEL_RGBA8 || FMT == CE_PIXEL_RGBA16;
     constexpr int NC = ALPHA ? 4 : 3;
+    if constexpr (!S16) {
+        uint32_t d[NC];
+        if constexpr (ALPHA) {
+            const uint4 v = reinterpret_cast<const uint4 *>(src)[tid];
+            d[0] = v.x, d[1] = v.y, d[2] = v.z, d[NC - 1] = v.w;
+        } else {
+#pragma unroll
+            for (int i = 0; i < NC; i++) d[i] = reinterpret_cast<const uint32_t *>(src)[tid * NC + i];
+        }
+#pragma unroll
+        for (int i = 0; i < 4 * NC; i++) s[i] = (d[i / 4] >> (8 * (i % 4))) & 255u;
+    } else {
+        uint32_t d[2 * NC];
+        if constexpr (ALPHA) {
+#pragma unroll
+            for (int i = 0; i < 2; i++) {
+                const uint4 v = reinterpret_cast<const uint4 *>(src)[tid * 2 + i];
+                d[4 * i] = v.x, d[4 * i + 1] = v.y, d[4 * i + 2] = v.z, d[4 * i + 3] = v.w;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                const uint2 v = reinterpret_cast<const uint2 *>(src)[tid * 3 + i];
+                d[2 * i] = v.x, d[2 * i + 1] = v.y;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4 * NC; i++) s[i] = (d[i / 2] >> (16 * (i % 2))) & 0xffffu;
+    }
+}
+
+// the three colour samples of pixel p, sample by sample (the tail)
+template <int FMT>
+__device__ __forceinline__ void cicp_load_pixel(const void *src, size_t p, uint32_t (&v)[3])
+{
+    constexpr bool S16 = FMT == CE_PIXEL_RGB16 || FMT == CE_PIXEL_RGBA16, ALPHA = FMT == CE_PIXEL_RGBA8 || FMT == CE_PIXEL_RGBA16;
+    constexpr int NC = ALPHA ? 4 : 3;
+#pragma unroll
+    for (int c = 0; c < 3; c++) v[c] = S16 ? static_cast<const uint16_t *>(src)[p * NC + c] : static_cast<const uint8_t *>(src)[p * NC + c];
+}
+
+// FMT: CE_PIXEL_RGB8 / RGBA8 / RGB16 / RGBA16 (alpha dropped).  A thread converts one group of four pixels from the
+// registers its aligned loads filled and stores 48 bytes; the last n_pixels % 4 pixels go sample by sample, one pixel to a
+// thread of block 0.  The table is gathered from global memory at every depth: 1, 4 and 16 KB stay in the vector L1 and the
+// 256 KB of depth 16 in L2, one code path.
+template <int FMT, bool MATRIX>
+__global__ __launch_bounds__(kCicpBlock) void k_cicp(const cicp_args a)
+{
+    constexpr int NC = (FMT == CE_PIXEL_RGBA8 || FMT == CE_PIXEL_RGBA16) ? 4 : 3;
     const size_t n_groups = a.n_pixels / 4;
     const size_t tid = (size_t)blockIdx.x * kCicpBlock + threadIdx.x;
     if (tid < n_groups) {
         uint32_t s[4 * NC];  // the group's samples, in memory order
-        if constexpr (!S16) {
-            uint32_t d[NC];
-            if constexpr (ALPHA) {
-                const uint4 v = reinterpret_cast<const uint4 *>(a.src)[tid];
-                d[0] = v.x, d[1] = v.y, d[2] = v.z, d[NC - 1] = v.w;
-            } else {
-#pragma unroll
-                for (int i = 0; i < NC; i++) d[i] = reinterpret_cast<const uint32_t *>(a.src)[tid * NC + i];
-            }
-#pragma unroll
-            for (int i = 0; i < 4 * NC; i++) s[i] = (d[i / 4] >> (8 * (i % 4))) & 255u;
-        } else {
-            uint32_t d[2 * NC];
-            if constexpr (ALPHA) {
-#pragma unroll
-                for (int i = 0; i < 2; i++) {
-                    const uint4 v = reinterpret_cast<const uint4 *>(a.src)[tid * 2 + i];
-                    d[4 * i] = v.x, d[4 * i + 1] = v.y, d[4 * i + 2] = v.z, d[4 * i + 3] = v.w;
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 3; i++) {
-                    const uint2 v = reinterpret_cast<const uint2 *>(a.src)[tid * 3 + i];
-                    d[2 * i] = v.x, d[2 * i + 1] = v.y;
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 4 * NC; i++) s[i] = (d[i / 2] >> (16 * (i % 2))) & 0xffffu;
-        }
+        cicp_load_group<FMT>(a.src, tid, s);
         float o[12];
 #pragma unroll
         for (int p = 0; p < 4; p++) {
@@ -84,9 +104,7 @@ __global__ __launch_bounds__(kCicpBlock) void k_cicp(const cicp_args a)
     if (blockIdx.x == 0 && threadIdx.x < a.n_pixels % 4) {
         const size_t p = n_groups * 4 + threadIdx.x;
         uint32_t v[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++)
-            v[c] = S16 ? static_cast<const uint16_t *>(a.src)[p * NC + c] : static_cast<const uint8_t *>(a.src)[p * NC + c];
+        cicp_load_pixel<FMT>(a.src, p, v);
         float px[3];
         cicp_pixel<MATRIX>(a, v[0], v[1], v[2], px);
 #pragma unroll

@@ -1,6 +1,6 @@
 // One pixel of the CICP ingest (cicp_kernel.h: k_cicp; yuv_cicp_kernel.h: k_yuv_cicp): the arguments, the clamp of a linear
 // image and the table gather with the separately rounded f32 matrix, apart from the kernels so that a file that needs the
-// pixel does not emit them.  Host-compilable like the headers that include it, and compiled with -ffp-contract=off.
+// pixel does not emit them.  hlg_pixel.h builds its pixel on the same arguments, matrix and clamp.  Host-compilable like the headers that include it, and compiled with -ffp-contract=off.
 #pragma once
 
 #include <cstddef>
@@ -26,10 +26,11 @@ __device__ __forceinline__ float linear_clamp(float v)
     return v > CE_LINEAR_MAX ? CE_LINEAR_MAX : (v < -CE_LINEAR_MAX ? -CE_LINEAR_MAX : v);
 }
 
+// steps 3 and 4 of the definition on one pixel's three linear-light values: the separately rounded f32 3 x 3 for primaries
+// other than 1, then the clamp of a linear image (shared with hlg_pixel.h, whose values are display light)
 template <bool MATRIX>
-__device__ __forceinline__ void cicp_pixel(const cicp_args &a, uint32_t r, uint32_t g, uint32_t b, float (&o)[3])
+__device__ __forceinline__ void cicp_matrix_clamp(const cicp_args &a, float tr, float tg, float tb, float (&o)[3])
 {
-    const float tr = a.table[r < a.maxv ? r : a.maxv], tg = a.table[g < a.maxv ? g : a.maxv], tb = a.table[b < a.maxv ? b : a.maxv];
     if constexpr (MATRIX) {
 #pragma unroll
         for (int i = 0; i < 3; i++) {
@@ -40,6 +41,13 @@ __device__ __forceinline__ void cicp_pixel(const cicp_args &a, uint32_t r, uint3
     } else {
         o[0] = linear_clamp(tr), o[1] = linear_clamp(tg), o[2] = linear_clamp(tb);
     }
+}
+
+template <bool MATRIX>
+__device__ __forceinline__ void cicp_pixel(const cicp_args &a, uint32_t r, uint32_t g, uint32_t b, float (&o)[3])
+{
+    const float tr = a.table[r < a.maxv ? r : a.maxv], tg = a.table[g < a.maxv ? g : a.maxv], tb = a.table[b < a.maxv ? b : a.maxv];
+    cicp_matrix_clamp<MATRIX>(a, tr, tg, tb, o);
 }
 
 }  // namespace

@@ -481,6 +481,49 @@ inline void batch_set_test_yuv_cicp(const HipBackend &be, ce_batch *batch, uint3
 {
     detail::check(be, ce_batch_set_test_yuv_cicp(batch, pair_index, ref_index, &image, &colour), "yuv_cicp", 0, 0, 0);
 }
+// ---- BT.2100 HLG -> display light, linear, with sRGB primaries (include/ce_metrics.h: ce_hlg_to_linear) ----
+// HLG carries the display it is shown on - peak luminance and system gamma (0: BT.2100's rule from the peak) - besides the
+// primaries, the depth and the luminance that becomes 1.0
+using HlgDescription = ce_hlg;
+inline HlgDescription hlg_bt2100(uint32_t depth = 10, float peak_nits = 1000.0f, float white_nits = 203.0f)
+{
+    return HlgDescription{9, depth, peak_nits, 0.0f, white_nits};
+}
+// One image of integer RGB(A) HLG code values (format: CE_PIXEL_RGB8 / RGBA8 / RGB16 / RGBA16; len in bytes) -> packed float RGB
+inline std::vector<float> hlg_to_linear(const HipBackend &be, const void *pixels, size_t len, int format, const HlgDescription &hlg,
+                                        uint32_t width, uint32_t height)
+{
+    std::vector<float> out((size_t)width * height * 3);
+    detail::check(be, ce_hlg_to_linear(be.ctx(), pixels, len, format, &hlg, width, height, out.data(), out.size()), "hlg", width, height, len);
+    return out;
+}
+// straight into a slot of a linear batch (eval::batch_linear)
+inline void batch_set_reference_hlg(const HipBackend &be, ce_batch *batch, uint32_t ref_index, const void *pixels, size_t len, int format,
+                                    const HlgDescription &hlg)
+{
+    detail::check(be, ce_batch_set_reference_hlg(batch, ref_index, pixels, len, format, &hlg), "hlg", 0, 0, 0);
+}
+inline void batch_set_test_hlg(const HipBackend &be, ce_batch *batch, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len,
+                               int format, const HlgDescription &hlg)
+{
+    detail::check(be, ce_batch_set_test_hlg(batch, pair_index, ref_index, pixels, len, format, &hlg), "hlg", 0, 0, 0);
+}
+// Y'CbCr planes in HLG, one kernel: yuv_to_rgb16 at depth_out = hlg.depth followed by hlg_to_linear, bit for bit; hlg.depth >= image.depth
+inline std::vector<float> yuv_hlg_to_linear(const HipBackend &be, const YuvImage &image, const HlgDescription &hlg, uint32_t width, uint32_t height)
+{
+    std::vector<float> out((size_t)width * height * 3);
+    detail::check(be, ce_yuv_hlg_to_linear(be.ctx(), &image, &hlg, width, height, out.data(), out.size()), "yuv_hlg", width, height, out.size());
+    return out;
+}
+inline void batch_set_reference_yuv_hlg(const HipBackend &be, ce_batch *batch, uint32_t ref_index, const YuvImage &image, const HlgDescription &hlg)
+{
+    detail::check(be, ce_batch_set_reference_yuv_hlg(batch, ref_index, &image, &hlg), "yuv_hlg", 0, 0, 0);
+}
+inline void batch_set_test_yuv_hlg(const HipBackend &be, ce_batch *batch, uint32_t pair_index, uint32_t ref_index, const YuvImage &image,
+                                   const HlgDescription &hlg)
+{
+    detail::check(be, ce_batch_set_test_yuv_hlg(batch, pair_index, ref_index, &image, &hlg), "yuv_hlg", 0, 0, 0);
+}
 // straight into a slot of a resident batch (RGB8 or deep), host or device planes
 inline void batch_set_reference_yuv(const HipBackend &be, ce_batch *batch, uint32_t ref_index, const YuvImage &image)
 {

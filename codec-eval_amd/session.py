@@ -12,11 +12,11 @@ from __future__ import annotations
 import os
 import time
 from dataclasses import dataclass, field
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from . import (ColourDescription, DEEP_DEPTHS, PIXEL_RGB_F32, PIXEL_RGB8, PIXEL_RGB16, PIXEL_RGBA8, PIXEL_RGBA16, Batch, CodecEvalError, ColorTable, Context, DimensionMismatch, MetricCalculation,
+from . import (ColourDescription, HlgDescription, DEEP_DEPTHS, PIXEL_RGB_F32, PIXEL_RGB8, PIXEL_RGB16, PIXEL_RGBA8, PIXEL_RGBA16, Batch, CodecEvalError, ColorTable, Context, DimensionMismatch, MetricCalculation,
                MetricConfig, MetricResult, _error_obj, estimate_batch_bytes, CE_ERR_BACKEND)
 from . import RESAMPLE_LANCZOS3
 from . import CHROMA_TRIANGLE, MEM_HOST, YUV_400, YUV_420, YUV_444, YUV_BT601, YUV_FULL, YUV_PLANAR, YUV_SEMIPLANAR, YuvImage, yuv_coefficients
@@ -27,7 +27,10 @@ from .viewing import SimulationMode, ViewingCondition
 __all__ = ["ImageData", "EncodeRequest", "EvalConfig", "EvalConfigBuilder", "EvalSession", "ALPHA_BLACK_WHITE"]
 
 
-def _colour_at(colour: Optional[ColourDescription], depth: int) -> Optional[ColourDescription]:
+Colour = Union[ColourDescription, HlgDescription]  # what colour= takes: H.273 code points, or BT.2100 HLG with its display
+
+
+def _colour_at(colour: Optional[Colour], depth: int) -> Optional[Colour]:
     """A constructor's colour= at the image's own depth (a preset names primaries and transfer; the samples say the depth)."""
     return None if colour is None else colour.with_depth(int(depth))
 
@@ -44,15 +47,15 @@ class ImageData:
     yuv_image: Optional[YuvImage] = None  # a decode still in its Y'CbCr planes (ImageData.yuv); `data` is then empty
     # How the code values are to be read (H.273 primaries / transfer; its depth is this image's): None = sRGB, as ever.  A
     # decode with a non-sRGB description is scored in linear light through a linear batch.
-    colour: Optional[ColourDescription] = None
+    colour: Optional[Colour] = None
     linear: bool = False  # `data` is packed float32 RGB, linear light with sRGB primaries (ImageData.linear_f32)
 
     @staticmethod
-    def rgb(data, width: int, height: int, colour: Optional[ColourDescription] = None) -> "ImageData":
+    def rgb(data, width: int, height: int, colour: Optional[Colour] = None) -> "ImageData":
         return ImageData(np.ascontiguousarray(data, dtype=np.uint8).reshape(-1), int(width), int(height), 3, colour=_colour_at(colour, 8))
 
     @staticmethod
-    def rgba(data, width: int, height: int, colour: Optional[ColourDescription] = None) -> "ImageData":
+    def rgba(data, width: int, height: int, colour: Optional[Colour] = None) -> "ImageData":
         return ImageData(np.ascontiguousarray(data, dtype=np.uint8).reshape(-1), int(width), int(height), 4, colour=_colour_at(colour, 8))
 
     @staticmethod
@@ -69,7 +72,7 @@ class ImageData:
         return ImageData(np.ascontiguousarray(data, dtype=np.uint8).reshape(-1), int(width), int(height), 3, bytes(icc_profile))
 
     @staticmethod
-    def rgb16(data, width: int, height: int, depth: int, colour: Optional[ColourDescription] = None) -> "ImageData":
+    def rgb16(data, width: int, height: int, depth: int, colour: Optional[Colour] = None) -> "ImageData":
         """A decoder's PixelData::Rgb16 (crates/codec-iter/src/avif_config.rs:122-170) kept as it is: packed uint16
         samples of `depth` bits, each meaning the sRGB value v / (2^depth - 1).  A session scores it through a deep batch."""
         if depth not in DEEP_DEPTHS:
@@ -78,7 +81,7 @@ class ImageData:
                          colour=_colour_at(colour, depth))
 
     @staticmethod
-    def rgba16(data, width: int, height: int, depth: int, colour: Optional[ColourDescription] = None) -> "ImageData":
+    def rgba16(data, width: int, height: int, depth: int, colour: Optional[Colour] = None) -> "ImageData":
         if depth not in DEEP_DEPTHS:
             raise ValueError(f"depth must be one of {DEEP_DEPTHS}, got {depth}")
         return ImageData(np.ascontiguousarray(data, dtype=np.uint16).reshape(-1), int(width), int(height), 4, None, int(depth),
@@ -87,13 +90,14 @@ class ImageData:
     @staticmethod
     def yuv(planes, width: int, height: int, subsampling: int = YUV_420, layout: int = YUV_PLANAR, matrix: int = YUV_BT601,
             range: int = YUV_FULL, upsample: int = CHROMA_TRIANGLE, *, depth: int = 8, msb_aligned: bool = False,
-            colour: Optional[ColourDescription] = None) -> "ImageData":
+            colour: Optional[Colour] = None) -> "ImageData":
         """A decoder's Y'CbCr planes in host memory (a JPEG decoder in raw mode, dav1d: 2-D arrays, Y, Cb, Cr or Y,
         interleaved CbCr; uint8 at depth 8, uint16 at 10 and 12, low- or MSB-aligned as P010 is) as they are: the session
         upsamples and converts them on the device, straight into the batch slot (Batch.set_*_yuv, the definition of
         include/ce_metrics.h), and scores the result as RGB8; the multi-device session converts them on the host with
         to_rgb8_vec, the same definition.  With a `colour` other than sRGB's (an HDR10 frame: BT2020_PQ) the image is
-        scored in linear light, its planes going through Batch.set_*_yuv_cicp."""
+        scored in linear light, its planes going through Batch.set_*_yuv_cicp, or through
+        Batch.set_*_yuv_hlg for an HlgDescription (section 18)."""
         if depth not in (8, 10, 12):
             raise ValueError(f"Y'CbCr samples are 8, 10 or 12 bits, got {depth}")
         img = YuvImage([np.asarray(p) for p in planes], subsampling, layout, matrix, range, upsample, int(depth), bool(msb_aligned), MEM_HOST)
@@ -442,11 +446,16 @@ class EvalSession:
 
     def _set_linear(self, batch: Batch, image: ImageData, ref_index: int, pair_index: Optional[int]):
         """One image into a slot of a linear batch: float32 as it is, code values through the CICP ingest - by their own
-        description, an untagged image as sRGB (1, 13) at its own depth - and Y'CbCr planes through the fused ingest."""
+        description, an untagged image as sRGB (1, 13) at its own depth - and Y'CbCr planes through the fused ingest; an
+        HlgDescription takes the HLG calls of the same shape."""
         def refuse(what):
             raise MetricCalculation(CE_ERR_BACKEND, f"Metric calculation failed: linear-light scoring: {what}")
         if image.yuv_image is not None:  # the planes' own tag, an untagged image as sRGB; depth 16 keeps what the matrix gives between code points
             colour = (image.colour or ColourDescription.SRGB).with_depth(16)
+            if isinstance(colour, HlgDescription):
+                if pair_index is None:
+                    return batch.set_reference_yuv_hlg(ref_index, image.yuv_image, colour)
+                return batch.set_test_yuv_hlg(pair_index, ref_index, image.yuv_image, colour)
             if pair_index is None:
                 return batch.set_reference_yuv_cicp(ref_index, image.yuv_image, colour)
             return batch.set_test_yuv_cicp(pair_index, ref_index, image.yuv_image, colour)
@@ -460,7 +469,12 @@ class EvalSession:
             return batch.set_reference(ref_index, image.data) if pair_index is None else batch.set_test(pair_index, ref_index, image.data)
         colour = image.colour or ColourDescription.SRGB.with_depth(image.depth or 8)
         px = image.data.reshape(image.height, image.width, image.channels)
-        if pair_index is None:
+        if isinstance(colour, HlgDescription):
+            if pair_index is None:
+                batch.set_reference_hlg(ref_index, px, colour)
+            else:
+                batch.set_test_hlg(pair_index, ref_index, px, colour)
+        elif pair_index is None:
             batch.set_reference_cicp(ref_index, px, colour)
         else:
             batch.set_test_cicp(pair_index, ref_index, px, colour)

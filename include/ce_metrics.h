@@ -304,7 +304,7 @@ int ce_batch_ssimulacra2_maps(ce_batch *b, uint32_t scale, uint32_t channel, uin
  * unequal ones its bit stays clear in `valid` while the other metrics run.  A deep batch of depths 8 / 8 scores an image
  * bit for bit as an RGB8 batch does, and so does one of depth 16 holding v8 * 257.
  * Not part of this: deep ce_ref handles, deep ce_eval_batch (linear-f32 input, PQ and wide-gamut primaries: linear batches,
- * below; HLG: not offered).
+ * below; HLG: ce_batch_set_*_hlg on linear batches, further below).
  * Pixel formats of a deep batch only (their depth is that side's): packed u16 RGB / RGBA (alpha dropped). */
 enum {
     CE_PIXEL_RGB16 = 4,
@@ -512,7 +512,7 @@ int ce_batch_resample_pairs(ce_batch *src, ce_batch *dst, uint32_t n_refs, uint3
  *             BT601 / FULL / d = D = 8 gives 65536, 91881, 22554, 46802, 116130: libjpeg-turbo's decoder, bit for bit.
  *             4:0:0 (gray): R = G = B from the Y term alone.
  * Not part of this: left-cosited (MPEG-2 / H.264 default) and other chroma sitings, 4:1:1 / 4:4:0, packed YUYV, 16-bit
- * YUV, HLG (PQ: ce_batch_set_*_yuv_cicp below), identity / YCgCo matrices, YUV through ce_eval_batch, ce_ref_* and ce_batch_resample*, alpha planes. */
+ * YUV (PQ: ce_batch_set_*_yuv_cicp below; HLG: ce_batch_set_*_yuv_hlg), identity / YCgCo matrices, YUV through ce_eval_batch, ce_ref_* and ce_batch_resample*, alpha planes. */
 enum ce_yuv_subsampling { CE_YUV_444 = 0, CE_YUV_422 = 1, CE_YUV_420 = 2, CE_YUV_400 = 3 };
 /* PLANAR: plane[0..2] = Y, Cb, Cr (I420 and its kin).  SEMIPLANAR: plane[0] = Y, plane[1] = interleaved Cb Cr pairs
  * (NV12 / NV16 / P010), plane[2] unused.  4:0:0 reads plane[0] only under either layout. */
@@ -609,6 +609,7 @@ int ce_composite_rgba16(ce_ctx *ctx, const uint16_t *rgba, size_t len, uint32_t 
  *   ce_batch_set_reference_fmt / ce_batch_set_test_fmt take CE_PIXEL_RGB_F32 only (len = width * height * 12);
  *   ce_batch_set_reference_cicp / ce_batch_set_test_cicp take tagged integer code values (below);
  *   ce_batch_set_reference_yuv_cicp / ce_batch_set_test_yuv_cicp take Y'CbCr planes with such a tag (below);
+ *   ce_batch_set_reference_hlg / ce_batch_set_test_hlg and their *_yuv_hlg forms take BT.2100 HLG (below);
  *   ce_batch_bind_pair, ce_batch_run, ce_batch_launch, ce_batch_collect, ce_batch_butteraugli_pnorm3 and the three map
  *     readers work as on any batch;
  *   CE_ERR_INVALID_ARG, with the reason in ce_last_error and the batch still usable: CE_FLAG_XYB_ROUNDTRIP,
@@ -617,7 +618,7 @@ int ce_composite_rgba16(ce_ctx *ctx, const uint16_t *rgba, size_t len, uint32_t 
  *   ce_batch_resample / ce_batch_resample_pairs from a linear batch into a linear batch run the float resampler of the
  *     viewing-simulation section above.
  *   CE_PIXEL_RGB_F32 on a batch that is not linear is refused the same way.
- * Not part of this: HLG (its OOTF couples the channels and needs a device powf), the BT.709 / BT.1886 gamma transfers,
+ * Not part of this: the BT.709 / BT.1886 gamma transfers (HLG, whose OOTF couples the channels, has calls of its own below),
  * primaries with a non-D65 white, limited-range RGB, ce_ref_* handles on linear batches and the pooled ce_eval_batch on
  * them.
  * (No reference item: the reference scores every PixelData variant only after to_8bit / to_rgb8_vec.) */
@@ -696,11 +697,74 @@ int ce_colour_matrix(int primaries, float out[9]);
  * it has no colour description to go by.)
  * ce_yuv_to_linear: one image of width x height to packed float RGB in host memory (out_len = width * height * 3 floats);
  * errors as above, CE_ERR_BAD_LENGTH for a wrong out_len.
- * Not part of this: HLG and the BT.709 / BT.1886 transfers, identity / YCgCo matrices, chroma sitings other than the centred
+ * Not part of this: the BT.709 / BT.1886 transfers (HLG: ce_batch_set_*_yuv_hlg below), identity / YCgCo matrices, chroma sitings other than the centred
  * one, ce_ref_* handles and the pooled ce_eval_batch on linear batches. */
 int ce_batch_set_reference_yuv_cicp(ce_batch *b, uint32_t ref_index, const ce_yuv_image *image, const ce_colour *c);
 int ce_batch_set_test_yuv_cicp(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const ce_yuv_image *image, const ce_colour *c);
 int ce_yuv_to_linear(ce_ctx *ctx, const ce_yuv_image *image, const ce_colour *c, uint32_t width, uint32_t height, float *out, size_t out_len);
+
+/* HLG ingest: integer RGB code values, or Y'CbCr planes, in BT.2100 Hybrid Log-Gamma (H.273 transfer
+ * 18) -> a slot of a linear batch, on the device.  HLG is scene-referred: the inverse OETF is per channel, but the OOTF that
+ * turns scene light into display light scales all three channels by Ys^(gamma - 1), Ys the pixel's scene luminance and gamma
+ * a function of the display's peak luminance.  So HLG is no per-channel table and ce_colour has no field for the display: it
+ * has a description and calls of its own, and transfer 18 through ce_transfer_table and the *_cicp calls stays refused.
+ * Definition, per pixel of a CE_PIXEL_RGB8 / RGBA8 / RGB16 / RGBA16 image (alpha dropped; 8-bit formats require depth 8;
+ * maxv = 2^depth - 1):
+ *   1. e_c = hlg_table[min(v_c, maxv)] per channel.  The table is built on the host in f64 per code point x = v / maxv and
+ *      rounded once to f32: E = x^2 / 3 for x <= 1/2, E = (exp((x - c) / a) + b) / 12 otherwise, with BT.2100's a = 0.17883277,
+ *      b = 0.28466892, c = 0.55991073 (ce_hlg_table).  hlg_table[0] = 0, hlg_table[maxv] = 1.0f exactly (the f64 value
+ *      1.00000003 rounds there).  The curve is never evaluated on the device.
+ *   2. ys = (kR * (double)e_r + kG * (double)e_g) + kB * (double)e_b in f64, every product and sum rounded separately; kR, kG,
+ *      kB are the Y row of the f64 XYZ <- src matrix of the tagged primaries, the one ce_colour_matrix starts from (BT.2020:
+ *      0.2627, 0.6780, 0.0593 at four decimals).
+ *   3. s = ys > 0 ? hlg_pow(ys, gamma - 1) : 0;  k = (float)(A * s) with A = (double)peak_nits / (double)white_nits: one f64
+ *      product, one rounding to f32.  Black level L_B = 0.
+ *   4. d_c = k * e_c in f32, one product per channel: display light, 1.0 = white_nits.
+ *   5. primaries other than 1: the separately rounded f32 3 x 3 of the CICP definition's step 3; then its step 4, the clamp of
+ *      a linear image.
+ * gamma = system_gamma if that is non-zero, else BT.2100's 1.2 + 0.42 * log10(peak_nits / 1000) evaluated on the host in f64
+ * (1000 nits: 1.2); it must lie in [0.8, 1.6].  system_gamma = 1 with peak_nits = white_nits makes k exactly 1.0f: the output
+ * for primaries 1 is then the table, bit for bit.
+ * hlg_pow(x, g) is part of the definition, not a library call: no two libraries' pow agree to the last bit.  It is a fixed
+ * sequence of IEEE f64 operations - add, multiply, divide, integer work on the exponent bits, one round-to-nearest-integer -
+ * each correctly rounded on the device and on a host alike (codec-eval_amd/csrc/hlg_pixel.h; tests/hlg_restatement.py runs the
+ * same sequence on numpy f64 arrays):
+ *   x = m * 2^e with m in [sqrt(1/2), sqrt(2)) (bits; m >= 1.4142135623730951 is halved);  t = (m - 1) / (m + 1);
+ *   ln m = (2 t) * P(t^2), P = 1 + t^2 (1/3 + t^2 (1/5 + ... + t^2 / 21)) in Horner form from 1/21 down;
+ *   y = g * (ln m + e * ln2), ln2 = 0.6931471805599453;  n = rint(y / ln2);  f = y - n * ln2;
+ *   exp f = 1 + f (1 + f (1/2 + f (1/6 + ... + f / 14!))) in Horner form from 1/14! down;  result = exp f * 2^n (bits).
+ * It stays within 1e-13 relative of the real power (measured: 5e-15) for x in [2^-40, 2] and g in [-0.2, 0.6] - six orders
+ * under an f32 half-ulp - and hlg_pow(x, 0) = 1 exactly.
+ * tests/hlg_restatement.py restates all of this in numpy; the device equals it bit for bit, on every float.
+ * ce_batch_set_*_hlg / ce_hlg_to_linear take exactly what ce_batch_set_*_cicp / ce_cicp_to_linear take, with their staging,
+ * stream and ordering.  ce_batch_set_*_yuv_hlg / ce_yuv_hlg_to_linear take what ce_batch_set_*_yuv_cicp / ce_yuv_to_linear
+ * take (CE_MEM_HOST planes consumed on return, CE_MEM_DEVICE planes read in place under the same lifetime rule); their
+ * definition is the composition of ce_yuv_to_rgb16(img, depth_out = h.depth) and ce_hlg_to_linear(rgb as CE_PIXEL_RGB16, h) and
+ * adds no arithmetic; h.depth must not be under img.depth.
+ * CE_ERR_INVALID_ARG, with the reason in ce_last_error and the batch still usable: a batch that is not linear, a null
+ * pointer, another format, an 8-bit format with depth != 8, primaries or depth outside the lists, peak_nits or white_nits
+ * that is not finite and > 0, a gamma - given or derived - outside [0.8, 1.6] or NaN, h.depth < img.depth, everything *_yuv
+ * refuses about the image, slot indices past the batch.  CE_ERR_BAD_LENGTH for a wrong len or out_len.
+ * Not part of this: a non-zero black level L_B, BT.2390's extended gamma rule, HLG -> PQ transcoding, limited-range RGB,
+ * non-D65 whites, ce_ref_* handles and the pooled ce_eval_batch on linear batches. */
+typedef struct ce_hlg {
+    int primaries;      /* H.273 ColourPrimaries: 1, 9 or 12 (BT.2100 itself: 9) */
+    uint32_t depth;     /* 8, 10, 12 or 16; samples above 2^depth - 1 are clamped */
+    float peak_nits;    /* L_W, the display's nominal peak luminance, > 0 */
+    float system_gamma; /* 0: BT.2100's rule from peak_nits; otherwise used as given; the result must lie in [0.8, 1.6] */
+    float white_nits;   /* the luminance that becomes 1.0, > 0 (203 is the usual suggestion) */
+} ce_hlg;               /* 20 bytes */
+int ce_batch_set_reference_hlg(ce_batch *b, uint32_t ref_index, const void *pixels, size_t len, int format, const ce_hlg *h);
+int ce_batch_set_test_hlg(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format, const ce_hlg *h);
+int ce_hlg_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_hlg *h, uint32_t w, uint32_t height, float *out,
+                     size_t out_len);
+int ce_batch_set_reference_yuv_hlg(ce_batch *b, uint32_t ref_index, const ce_yuv_image *image, const ce_hlg *h);
+int ce_batch_set_test_yuv_hlg(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const ce_yuv_image *image, const ce_hlg *h);
+int ce_yuv_hlg_to_linear(ce_ctx *ctx, const ce_yuv_image *image, const ce_hlg *h, uint32_t width, uint32_t height, float *out, size_t out_len);
+/* Pure host functions: the inverse-OETF table (n = 2^depth entries), and kR, kG, kB, gamma - 1, A of a description - exactly
+ * what the kernel is handed.  CE_ERR_INVALID_ARG for what the calls above refuse about depth and description. */
+int ce_hlg_table(uint32_t depth, float *out, size_t n);
+int ce_hlg_params(const ce_hlg *h, double out[5]);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------ */
 /* Bracket every kernel launch with a HIP event pair, recorded on the stream the kernel is launched on,
