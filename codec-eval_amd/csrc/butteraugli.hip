@@ -402,7 +402,9 @@ __global__ __launch_bounds__(TPB) void k_ba_front(const uint8_t *__restrict__ re
             p0 = p0 > mn ? p0 : mn;
             p1v = p1v > mn ? p1v : mn;
             p2v = p2v > mn ? p2v : mn;
-            // p >= 1e-4 (clamped above), gamma in [21, ~150]: IEEE quotients without the range-scaling steps (ce_internal.h)
+            // IEEE quotients without the range-scaling steps (ce_internal.h).  Measured ("Operand
+            // ranges"): RGB8 / deep batches p in [1.76, 7.2e3] (the opsin bias keeps p off its clamp), gamma in [24, 148];
+            // linear batches p in [1e-4 (the clamp above), 1.04e7], gamma in [21, 288], quotients in [2.8e-5, 2.1e5]
             float s0 = ce_div_noscale(gamma_f(p0), p0), s1 = ce_div_noscale(gamma_f(p1v), p1v), s2 = ce_div_noscale(gamma_f(p2v), p2v);
             s0 = s0 > mn ? s0 : mn;
             s1 = s1 > mn ? s1 : mn;
@@ -743,10 +745,12 @@ struct malta_bands {
 // Two correctly rounded f32 quotients a0 / b and a1 / b with ONE reciprocal.  hipcc expands every IEEE division into
 // v_div_scale x2, v_rcp, two fused steps that refine the reciprocal, a product, two fused quotient corrections, v_div_fmas
 // and v_div_fixup (11 instructions) and does not share anything between two divisions by the same denominator.  For
-// operands whose quotient cannot overflow, underflow or involve a denormal - here b = norm1 + |..| in [5, 2^28] and
-// the numerators are positive constants in [2, 4e7] - v_div_scale returns its operand unchanged, v_div_fmas is a plain
-// fma and v_div_fixup returns the quotient, so the same arithmetic is 3 shared + 5 per numerator = 13 instructions
-// instead of 22, bit for bit (ce_debug_div_sweep checks it against operator/ on the device).
+// operands whose quotient cannot overflow, underflow or involve a denormal, v_div_scale returns its operand unchanged,
+// v_div_fmas is a plain fma and v_div_fixup returns the quotient, so the same arithmetic is 3 shared + 5 per numerator =
+// 13 instructions instead of 22, bit for bit (ce_debug_div_sweep checks it against operator/ on the device).  Here the
+// numerators are positive constants in [1.7, 4.1e7] and b = norm1 + |..| is positive; measured (DESIGN.md section 15,
+// "Operand ranges"): b in [5, 1.3e8] on RGB8 / deep batches, [5, 7.5e12 < 2^43] on linear batches (a +-1024 checker at
+// intensity target 10 000), quotients down to 2.7e-13 = 2^-42.
 __device__ __forceinline__ void div2_shared_rcp(float a0, float a1, float b, float &q0, float &q1)
 {
     const float r = ce_rcp_refined(b);  // ce_internal.h
@@ -1146,7 +1150,14 @@ __global__ __launch_bounds__(TPB) void k_ba_score(const float *__restrict__ blk_
     }
 }
 
-// debug: div2_shared_rcp against operator/ on pseudo-random operands of the ranges Malta uses (and wider)
+// debug: div2_shared_rcp and ce_div_noscale against operator/ on pseudo-random operands of the ranges their call sites
+// use.  The range is the union over the batch kinds of what the oracle's probe records per site ("Operand ranges",
+// tests/test_wide_content_cpu.py), rounded outward to whole binades: [2^-40, 2^92) - RGB8 and deep batches stay inside
+// [2^-40, 2^40), a linear batch reaches 2^91.2 (cbrt_poly's second numerator at x = 1024) and 2^-20 (its first denominator
+// stepping over zero near x = 3.764).  Exponents are drawn independently, so quotients run from 2^-132 (subnormal) to 2^132
+// (overflow) - further than any site's: where a / b is subnormal, zero or infinite the two forms may round differently
+// and the sample is not counted, as no site produces one.
+constexpr uint32_t DIV_SWEEP_EXP_FIRST = 87u, DIV_SWEEP_EXP_SPAN = 132u;  // biased exponents 87 .. 218
 __global__ __launch_bounds__(256) void k_div_sweep(uint64_t seed, uint64_t count, unsigned long long *out)
 {
     unsigned long long bad = 0;
@@ -1155,17 +1166,22 @@ __global__ __launch_bounds__(256) void k_div_sweep(uint64_t seed, uint64_t count
         x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
         x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
         x ^= x >> 31;
-        // b, a0, a1 in [2^-40, 2^40), either sign for the numerators, a zero numerator now and then: random mantissas,
-        // exponents from the hash - the range every call site of ce_div_noscale / div2_shared_rcp stays inside
+        // random mantissas, exponents from the hash; either sign for the first numerator and - cbrt_poly's denominators are
+        // negative beyond the crossing - for the denominator; a zero numerator now and then
         const uint32_t mb = (uint32_t)x & 0x7fffffu, ma = (uint32_t)(x >> 23) & 0x7fffffu, m2 = (uint32_t)(x >> 41) & 0x7fffffu;
-        const uint32_t eb = 87u + (uint32_t)((x >> 17) % 80u), ea = 87u + (uint32_t)((x >> 7) % 80u), e2 = 87u + (uint32_t)((x >> 3) % 80u);
-        const float b = __uint_as_float((eb << 23) | mb);
+        const uint32_t eb = DIV_SWEEP_EXP_FIRST + (uint32_t)((x >> 17) % DIV_SWEEP_EXP_SPAN),
+                       ea = DIV_SWEEP_EXP_FIRST + (uint32_t)((x >> 7) % DIV_SWEEP_EXP_SPAN),
+                       e2 = DIV_SWEEP_EXP_FIRST + (uint32_t)((x >> 3) % DIV_SWEEP_EXP_SPAN);
+        const float b = __uint_as_float((eb << 23) | mb | ((uint32_t)(x >> 61) & 1u) << 31);
         float a0 = __uint_as_float((ea << 23) | ma | ((uint32_t)(x >> 60) & 1u) << 31), a1 = __uint_as_float((e2 << 23) | m2);
         if ((x >> 50 & 1023u) == 0) a0 = 0.0f;
         float q0, q1;
         div2_shared_rcp(a0, a1, b, q0, q1);
-        bad += (__float_as_uint(q0) != __float_as_uint(a0 / b)) + (__float_as_uint(q1) != __float_as_uint(a1 / b));
-        bad += __float_as_uint(ce_div_noscale(a1, b)) != __float_as_uint(a1 / b);
+        const float w0 = a0 / b, w1 = a1 / b;
+        const bool in0 = a0 == 0.0f || (fabsf(w0) >= 1.17549435e-38f && fabsf(w0) <= 3.40282347e+38f);
+        const bool in1 = fabsf(w1) >= 1.17549435e-38f && fabsf(w1) <= 3.40282347e+38f;
+        bad += (in0 && __float_as_uint(q0) != __float_as_uint(w0)) + (in1 && __float_as_uint(q1) != __float_as_uint(w1));
+        bad += in1 && __float_as_uint(ce_div_noscale(a1, b)) != __float_as_uint(w1);
     }
     if (bad) atomicAdd(out, bad);
 }

@@ -326,10 +326,15 @@ extern thread_local hipStream_t ce_tls_stream;
 // Correctly rounded f32 quotients without the range-scaling steps of the compiler's expansion.  hipcc turns a / b into
 // v_div_scale x2, v_rcp, two fused steps refining the reciprocal, a product, two fused quotient corrections, v_div_fmas
 // and v_div_fixup (11 instructions).  When neither operand is zero-denominator / infinite / NaN / denormal and the
-// quotient is far from overflow and underflow - every call site below divides values between 2^-40 and 2^40 (a zero
-// numerator included) - v_div_scale returns its operands unchanged, v_div_fmas is a plain fma and v_div_fixup returns
-// the quotient, so the same arithmetic is 8 instructions, bit for bit.  ce_debug_div_sweep checks both forms against
-// operator/ on the device over exactly that range.
+// quotient is far from overflow and underflow, v_div_scale returns its operands unchanged, v_div_fmas is a plain fma and
+// v_div_fixup returns the quotient, so the same arithmetic is 8 instructions, bit for bit.  Measured per call site with
+// the oracle's probe ("Operand ranges"; tests/test_wide_content_cpu.py): RGB8 and deep batches keep
+// operands and quotients between 2^-22 and 2^27; a LINEAR batch (samples to +-1024, intensity targets to 10 000) takes
+// operands from 2^-20 to 2^92, of either sign, and quotients from 2^-42 to 2^23 - still no zero, subnormal or infinite
+// operand and no quotient near the ends of the format.  ce_debug_div_sweep checks both forms against operator/ on the
+// device over [2^-40, 2^92) with either sign.  A zero denominator would give NaN here where operator/ gives an infinity:
+// no site has one (cbrt_poly's denominators step over zero without touching it, every float32 around each crossing is
+// in tests/wide_content.py: lab_crossing).
 __device__ __forceinline__ float ce_div_refined(float a, float b, float r)  // r = refined reciprocal of b
 {
     float q = a * r;

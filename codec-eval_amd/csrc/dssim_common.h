@@ -13,8 +13,14 @@ namespace {
 // ---- linear RGB -> normalised (L, a, b) ------------------------------------------------------------
 __device__ __forceinline__ float cbrt_poly(float x)
 {
-    // x in (216/24389, ~1], y in [0.2, 1.1]: numerators and denominators in (0.005, 3.5) - the two IEEE quotients take the
-    // expansion without range scaling (ce_internal.h: 8 instructions instead of 11, bit for bit; this kernel is VALU-bound)
+    // The two IEEE quotients take the expansion without range scaling (ce_internal.h: 8 instructions instead of 11, bit for
+    // bit; this kernel is VALU-bound).  Measured operands ("Operand ranges"):
+    //   RGB8 / deep batches, x in (216/24389, 1]: numerators in [0.0055, 4.6], denominators in [0.026, 4.6], all positive;
+    //   linear batches, x in (216/24389, 1024]: |numerator| in [2.3e-4, 2.9e27], |denominator| in [9.5e-7, 7.9e20], either
+    //     sign, |quotient| in [2.8e-5, 7.4e6].  Above x ~ 3.1 the seed polynomial is negative and this is no cube root any
+    //     more (the crate's definition, restated by the oracle): the first denominator 2 y^3 + x steps over zero at
+    //     x = 3.7800 (smallest magnitude 2^-20), the second at x = 3.4566 and 4.5567 (3.3e-6); no float32 x makes either 0.
+    // The discarded arm (x <= 216/24389, negative x included) sees magnitudes inside the same envelope.
     float y = (-0.5f * x + 1.51f) * x + 0.2f;
     float y3 = y * y * y;
     y = ce_div_noscale(y * (y3 + 2.0f * x), 2.0f * y3 + x);
@@ -33,7 +39,8 @@ __device__ __forceinline__ void rgb_to_lab(float r, float g, float b, float &L, 
     // Both arms are evaluated and the result is SELECTED: left alone the compiler puts each cube root behind a branch of its
     // own (exec-mask save, compare, branch), which serialises three independent 35-instruction dependency chains that a wave
     // otherwise interleaves.  The empty asm pins the cube root where it is computed (it cannot be sunk into a conditional
-    // block).  cbrt_poly of a value <= EPS is harmless (x >= 0: every denominator is >= 0.016) and discarded.
+    // block).  cbrt_poly of a value <= EPS is harmless and discarded: for 0 <= x <= EPS every denominator is >= 0.016; a
+    // linear batch's negative x gives finite garbage or, at worst, a NaN that the select below drops.
     float cx = cbrt_poly(fx), cy = cbrt_poly(fy), cz = cbrt_poly(fz);
     asm volatile("" : "+v"(cx), "+v"(cy), "+v"(cz));
     const float X = fx > EPS ? cx - 16.0f / 116.0f : K * fx;

@@ -604,7 +604,10 @@ int ce_composite_rgba16(ce_ctx *ctx, const uint16_t *rgba, size_t len, uint32_t 
  * - the diffmap, DSSIM's SSIM maps, CE_FLAG_SSIMULACRA2_MAPS included - is the code every batch runs, so a linear batch
  * loaded with ce_srgb_table(8, 0)[v] scores SSIMULACRA2 and Butteraugli bit for bit as the RGB8 batch of the bytes v does,
  * and one loaded with ce_srgb_table(8, 1)[v] DSSIM.  PSNR has no integer grid here: its bit stays clear in `valid` and the
- * other metrics run.  Butteraugli's intensity_target keeps its meaning: nits at 1.0.
+ * other metrics run.  Butteraugli's intensity_target keeps its meaning: nits at 1.0.  It is not range-checked; the range
+ * over which a linear batch is held to the oracle - every per-pixel map bit for bit, on samples from the smallest subnormal
+ * to +-CE_LINEAR_MAX - is 80 .. 10 000 ("Operand ranges"; tests/test_gpu_wide_content.py).  The
+ * oracle itself stays finite on such samples up to about 1e9 and not at 1e12.
  * On a linear batch
  *   ce_batch_set_reference_fmt / ce_batch_set_test_fmt take CE_PIXEL_RGB_F32 only (len = width * height * 12);
  *   ce_batch_set_reference_cicp / ce_batch_set_test_cicp take tagged integer code values (below);

@@ -171,7 +171,7 @@ static float fast_log2f(float x)
     const float t = m - 1.0f;
     const float yp = fmaf(fmaf(p2, t, p1), t, p0);
     const float yq = fmaf(fmaf(q2, t, q1), t, q0);
-    return yp / yq + (float)es;
+    return CEO_DIV(CEO_DIV_LOG2, yp, yq) + (float)es;
 }
 
 extern int ceo_variant[CEO_V_COUNT]; /* sensitivity switches, all 0 by default (ce_oracle.h) */
@@ -203,7 +203,8 @@ static void opsin_dynamics_image(const img rgb[3], float intensity_target, img x
         p0 = p0 > mn ? p0 : mn;
         p1 = p1 > mn ? p1 : mn;
         p2 = p2 > mn ? p2 : mn;
-        float s0 = gamma_f(p0) / p0, s1 = gamma_f(p1) / p1, s2 = gamma_f(p2) / p2;
+        float s0 = CEO_DIV(CEO_DIV_GAMMA_P, gamma_f(p0), p0), s1 = CEO_DIV(CEO_DIV_GAMMA_P, gamma_f(p1), p1),
+              s2 = CEO_DIV(CEO_DIV_GAMMA_P, gamma_f(p2), p2);
         s0 = s0 > mn ? s0 : mn;
         s1 = s1 > mn ? s1 : mn;
         s2 = s2 > mn ? s2 : mn;
@@ -422,9 +423,9 @@ static void malta_diff_map(const img *lum0, const img *lum1, double w_0gt1, doub
         const float v0 = lum0->p[k], v1 = lum1->p[k];
         const float absval = 0.5f * (fabsf(v0) + fabsf(v1));
         const float diff = v0 - v1;
-        const float scaler = norm2_0gt1 / ((float)norm1 + absval);
+        const float scaler = CEO_DIV(CEO_DIV_MALTA_0GT1, norm2_0gt1, (float)norm1 + absval);
         float r = scaler * diff;
-        const float scaler2 = norm2_0lt1 / ((float)norm1 + absval);
+        const float scaler2 = CEO_DIV(CEO_DIV_MALTA_0LT1, norm2_0lt1, (float)norm1 + absval);
         const double fabs0 = fabs((double)v0);
         const double too_small = 0.55 * fabs0, too_big = 1.05 * fabs0;
         if (ceo_variant[CEO_V_BA_MALTA_F32]) { /* the same four branches with f32 arithmetic */

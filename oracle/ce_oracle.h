@@ -65,6 +65,23 @@ enum ceo_variant_key {
 void ceo_set_variant(int key, int value);
 int ceo_get_variant(int key);
 
+/* ---- division sites (tests/cpp/linear_input_shim.c ONLY) ---------------------------------------------------------
+ * The f32 quotients the device expands by hand (ce_internal.h: ce_div_noscale, butteraugli.hip: div2_shared_rcp) are
+ * written CEO_DIV(site, a, b) here.  It is the plain expression unless the including file defines it first, as the
+ * linear-input shim does to record each site's operand ranges ("Operand ranges"). */
+enum ceo_div_site {
+    CEO_DIV_CBRT_1 = 0,     /* dssim.c cbrt_poly: first Halley step */
+    CEO_DIV_CBRT_2 = 1,     /* ... second Halley step */
+    CEO_DIV_LOG2 = 2,       /* butteraugli.c fast_log2f: yp / yq */
+    CEO_DIV_GAMMA_P = 3,    /* opsin_dynamics_image: gamma(p) / p */
+    CEO_DIV_MALTA_0GT1 = 4, /* malta_diff_map: norm2_0gt1 / (norm1 + absval) */
+    CEO_DIV_MALTA_0LT1 = 5, /* ... norm2_0lt1 / (norm1 + absval) */
+    CEO_DIV_SITES = 6
+};
+#ifndef CEO_DIV
+#define CEO_DIV(site, a, b) ((a) / (b))
+#endif
+
 /* ---- PSNR: src/metrics/mod.rs:312-331 ---------------------------------- */
 int ceo_psnr(const uint8_t *ref, size_t ref_len, const uint8_t *test, size_t test_len,
              size_t width, size_t height, double *out);

@@ -59,9 +59,9 @@ static float cbrt_poly(float x)
 {
     float y = (-0.5f * x + 1.51f) * x + 0.2f;
     float y3 = y * y * y;
-    y = y * (y3 + 2.0f * x) / (2.0f * y3 + x);
+    y = CEO_DIV(CEO_DIV_CBRT_1, y * (y3 + 2.0f * x), 2.0f * y3 + x);
     y3 = y * y * y;
-    y = y * (y3 + 2.0f * x) / (2.0f * y3 + x);
+    y = CEO_DIV(CEO_DIV_CBRT_2, y * (y3 + 2.0f * x), 2.0f * y3 + x);
     return y;
 }
 

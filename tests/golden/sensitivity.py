@@ -6,12 +6,18 @@ the oracle has a switch (ce_oracle.h, ceo_set_variant) that flips ONLY that choi
 score moves, relative to the 1e-4 parity bar, on the committed golden inputs plus one 768x512 pair, and writes
 tests/golden/sensitivity.json.  A failing crate pin (tests/test_crate_pin.py) therefore points at a line.
 
-Run:  python tests/golden/sensitivity.py
+The two switches the device runs with also get a row per wide-content case (tests/wide_content.py: floats up to +-1024 at
+intensity targets up to 10000, through tests/linear_input_shim.py), named "wide:<case>:<shape>@<intensity>";
+tests/test_wide_content_cpu.py holds them to what the shim returns.
+
+Run:  python tests/golden/sensitivity.py          (everything)
+      python tests/golden/sensitivity.py --wide   (adds or refreshes the wide rows only; every other row stays as it is)
 """
 import importlib
 import json
 import os
 import sys
+import tempfile
 
 import numpy as np
 
@@ -49,7 +55,42 @@ def score(metric, ref, test, w, h, blur_mode=1):
     return O.butteraugli(ref, test, w, h)[0]
 
 
+def wide_rows(out):
+    """Rows "wide:*" of the two device switches, into out[switch]["cases"]; max_rel follows."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import linear_input_shim as LS
+    import wide_content as WC
+
+    with tempfile.TemporaryDirectory() as tmp:
+        shim = LS.Shim(tmp)
+        for variant, idx in (("ba_malta_f32", LS.BA_MALTA_F32), ("ba_l2_early", LS.BA_L2_EARLY)):
+            rows = {k: v for k, v in out[variant]["cases"].items() if not k.startswith("wide:")}
+            for w, h, cases in ((WC.W, WC.H, WC.working_set()), (WC.ODD_W, WC.ODD_H, WC.odd_set())):
+                for it in WC.INTENSITIES:
+                    for name, ref, test in cases:
+                        base = shim.butteraugli(ref, test, w, h, it)[0]
+                        shim.set_variant(idx, 1)
+                        try:
+                            got = shim.butteraugli(ref, test, w, h, it)[0]
+                        finally:
+                            shim.set_variant(idx, 0)
+                        rows[f"wide:{name}:{w}x{h}@{it:g}"] = {"default": base, "variant": got,
+                                                              "rel": abs(got - base) / max(abs(base), FLOOR["butteraugli"])}
+            worst = max(r["rel"] for r in rows.values())
+            out[variant]["cases"] = rows
+            out[variant]["max_rel"] = worst
+            out[variant]["over_the_1e-4_bar"] = worst > 1e-4
+            print(f"{variant:22s} with wide content  max rel {worst:.3e}")
+
+
 def main():
+    if "--wide" in sys.argv[1:]:
+        with open(os.path.join(HERE, "sensitivity.json")) as f:
+            out = json.load(f)
+        wide_rows(out)
+        with open(os.path.join(HERE, "sensitivity.json"), "w") as f:
+            json.dump(out, f, indent=1, sort_keys=True)
+        return
     d = np.load(os.path.join(HERE, "inputs.npz"))
     cases = []
     for name in sorted({k.rsplit(".", 1)[0] for k in d.files}):
@@ -79,6 +120,7 @@ def main():
         out[variant] = {"metric": metric, "default": default, "variant": alt, "max_rel": worst["rel"],
                         "over_the_1e-4_bar": worst["rel"] > 1e-4, "cases": rows}
         print(f"{variant:22s} {metric:12s} max rel {worst['rel']:.3e}")
+    wide_rows(out)
     with open(os.path.join(HERE, "sensitivity.json"), "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
 
