@@ -588,6 +588,38 @@ impl HipMetrics {
         self.check(rc, width, height, out.len())?;
         Ok(out)
     }
+
+    /// `ce_eval_pair_hdr_fidelity`: PSNR in the PQ domain and BT.2124's Delta E ITP of one pair of packed f32 RGB, linear light
+    /// with sRGB primaries; `depth` (10, 12 or 16) is the PQ code grid, `white_nits` the luminance of sample value 1.0.
+    pub fn hdr_fidelity(&mut self, reference: &[f32], test: &[f32], width: u32, height: u32, depth: u32, white_nits: f32)
+                        -> Result<sys::ce_hdr_scores, HipError> {
+        let mut out = sys::ce_hdr_scores::default();
+        let rc = unsafe {
+            sys::ce_eval_pair_hdr_fidelity(self.ctx, reference.as_ptr(), reference.len() * 4, test.as_ptr(), test.len() * 4, width, height,
+                                           depth, white_nits, &mut out)
+        };
+        self.check(rc, width, height, test.len() * 4)?;
+        Ok(out)
+    }
+}
+
+/// `ce_pq_code_thresholds`: the decision thresholds of PQ code values on linear light, `T[1 ..= 2^depth - 1]`; a pure host
+/// function.  `None` for a depth other than 10, 12 or 16 or a `white_nits` that is not finite and > 0.
+pub fn pq_code_thresholds(depth: u32, white_nits: f32) -> Option<Vec<f32>> {
+    if !matches!(depth, 10 | 12 | 16) {
+        return None;
+    }
+    let mut out = vec![0f32; (1usize << depth) - 1];
+    let rc = unsafe { sys::ce_pq_code_thresholds(depth, white_nits, out.as_mut_ptr(), out.len()) };
+    (rc == sys::CE_OK).then_some(out)
+}
+
+/// `ce_hdr_fidelity_matrices`: the two row-major 3 x 3 matrices the HDR fidelity kernel is handed - BT.2020 <- sRGB primaries,
+/// and BT.2100's LMS <- BT.2020.
+pub fn hdr_fidelity_matrices() -> ([f32; 9], [f32; 9]) {
+    let (mut a, mut b) = ([0f32; 9], [0f32; 9]);
+    unsafe { sys::ce_hdr_fidelity_matrices(a.as_mut_ptr(), b.as_mut_ptr()) };
+    (a, b)
 }
 
 /// `ce_batch`: images of one shape resident on the device, scored in one launch.  Resampling one grid into another
@@ -693,6 +725,15 @@ impl HipBatch<'_> {
         let c = image.to_sys(self.width, self.height)?;
         let rc = unsafe { sys::ce_batch_set_test_yuv_hlg(self.handle, pair_index, ref_index, &c, hlg) };
         self.check(rc, 0)
+    }
+
+    /// `ce_batch_hdr_fidelity`: PQ-PSNR and BT.2124 Delta E ITP of pairs `[0, n_pairs)` of a LINEAR batch; returns once the
+    /// scores are on the host.
+    pub fn hdr_fidelity(&mut self, n_pairs: u32, depth: u32, white_nits: f32) -> Result<Vec<sys::ce_hdr_scores>, HipError> {
+        let mut out = vec![sys::ce_hdr_scores::default(); n_pairs as usize];
+        let rc = unsafe { sys::ce_batch_hdr_fidelity(self.handle, n_pairs, depth, white_nits, out.as_mut_ptr()) };
+        self.check(rc, 0)?;
+        Ok(out)
     }
 
     /// `ce_batch_resample`: references (`tests`: test images) `[first, first + count)` into the same indices of `dst`.

@@ -74,6 +74,19 @@ pub struct ce_hlg {
     pub white_nits: c_float,
 }
 
+/// `ce_hdr_scores` (48 bytes): PSNR in the PQ domain and BT.2124's Delta E ITP of one pair of a linear batch, with the three
+/// exact integers they are finished from.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct ce_hdr_scores {
+    pub pq_psnr: c_double,
+    pub delta_e_itp_mean: c_double,
+    pub delta_e_itp_max: c_double,
+    pub pq_sse: u64,
+    pub itp_sum_q20: u64,
+    pub itp_max_q20: u64,
+}
+
 /// `ce_scores` (40 bytes): a score is meaningful iff its bit is set in `valid`.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -311,6 +324,12 @@ extern "C" {
                                 out_len: usize) -> c_int;
     pub fn ce_hlg_table(depth: u32, out: *mut c_float, n: usize) -> c_int;
     pub fn ce_hlg_params(h: *const ce_hlg, out: *mut c_double) -> c_int;
+    pub fn ce_batch_hdr_fidelity(b: *mut ce_batch, n_pairs: u32, depth: u32, white_nits: c_float, out: *mut ce_hdr_scores) -> c_int;
+    pub fn ce_eval_pair_hdr_fidelity(ctx: *mut ce_ctx, reference: *const c_float, reference_len: usize, test: *const c_float,
+                                     test_len: usize, width: u32, height: u32, depth: u32, white_nits: c_float,
+                                     out: *mut ce_hdr_scores) -> c_int;
+    pub fn ce_pq_code_thresholds(depth: u32, white_nits: c_float, out: *mut c_float, n: usize) -> c_int;
+    pub fn ce_hdr_fidelity_matrices(a: *mut c_float, b: *mut c_float) -> c_int;
     pub fn ce_batch_set_reference_over(b: *mut ce_batch, first_ref: u32, pixels: *const c_void, len: usize, format: c_int, n_bg: u32,
                                        backgrounds: *const u16) -> c_int;
     pub fn ce_batch_set_test_over(b: *mut ce_batch, first_pair: u32, ref_indices: *const u32, pixels: *const c_void, len: usize,

@@ -134,6 +134,11 @@ class CeHlg(C.Structure):
     _fields_ = [("primaries", C.c_int), ("depth", C.c_uint32), ("peak_nits", C.c_float), ("system_gamma", C.c_float), ("white_nits", C.c_float)]
 
 
+class CeHdrScores(C.Structure):
+    _fields_ = [("pq_psnr", C.c_double), ("delta_e_itp_mean", C.c_double), ("delta_e_itp_max", C.c_double),
+                ("pq_sse", C.c_uint64), ("itp_sum_q20", C.c_uint64), ("itp_max_q20", C.c_uint64)]
+
+
 class CodecEvalError(RuntimeError):
     """Mirrors codec_eval::Error for this path (src/error.rs:31-49)."""
 
@@ -262,6 +267,10 @@ _PROTOTYPES = [
     ("ce_yuv_hlg_to_linear", _i, [_vp, C.POINTER(CeYuvImage), C.POINTER(CeHlg), _u32, _u32, _vp, _sz]),
     ("ce_hlg_table", _i, [_u32, _vp, _sz]),
     ("ce_hlg_params", _i, [C.POINTER(CeHlg), _dp]),
+    ("ce_batch_hdr_fidelity", _i, [_vp, _u32, _u32, _f32, C.POINTER(CeHdrScores)]),
+    ("ce_eval_pair_hdr_fidelity", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _f32, C.POINTER(CeHdrScores)]),
+    ("ce_pq_code_thresholds", _i, [_u32, _f32, _vp, _sz]),
+    ("ce_hdr_fidelity_matrices", _i, [_vp, _vp]),
     ("ce_batch_set_reference_over", _i, [_vp, _u32, _vp, _sz, _i, _u32, _vp]),
     ("ce_batch_set_test_over", _i, [_vp, _u32, _vp, _vp, _sz, _i, _u32, _vp]),
     ("ce_composite_rgba8", _i, [_vp, _vp, _sz, _u32, _u32, _vp, _vp, _sz]),
@@ -409,6 +418,42 @@ def hlg_params(description: "HlgDescription") -> np.ndarray:
     c = description._c()
     _host_check(lib().ce_hlg_params(C.byref(c), out.ctypes.data_as(_dp)))
     return out
+
+
+HDR_FIDELITY_DEPTHS = (10, 12, 16)  # the PQ code grids ce_batch_hdr_fidelity scores on
+
+
+def pq_code_thresholds(depth: int, white_nits: float = 203.0) -> np.ndarray:
+    """The decision thresholds of PQ code values on linear light (ce_pq_code_thresholds), float32 [2^depth - 1]: entry c - 1
+    is T[c] = PQ_EOTF((c - 0.5) / maxv) / white_nits, and a sample's code is numpy.searchsorted(T, x, side="right")."""
+    out = np.empty((1 << depth) - 1 if 0 < depth <= 16 else 1, np.float32)
+    _host_check(lib().ce_pq_code_thresholds(depth, white_nits, out.ctypes.data, out.size))
+    return out
+
+
+def hdr_fidelity_matrices() -> Tuple[np.ndarray, np.ndarray]:
+    """HDR fidelity's two 3 x 3 matrices (ce_hdr_fidelity_matrices), float32: BT.2020 <- sRGB primaries, and BT.2100's
+    LMS <- BT.2020."""
+    a, b = np.empty((3, 3), np.float32), np.empty((3, 3), np.float32)
+    _host_check(lib().ce_hdr_fidelity_matrices(a.ctypes.data, b.ctypes.data))
+    return a, b
+
+
+@dataclass(frozen=True)
+class HdrFidelity:
+    """PSNR in the PQ domain and BT.2124's Delta E ITP of one pair of a linear batch (ce_hdr_scores), with the three exact
+    integers they are finished from: the sum of squared PQ code differences, and the sum and the maximum of the per-pixel
+    Delta E in units of 2^-20."""
+    pq_psnr: float
+    delta_e_itp_mean: float
+    delta_e_itp_max: float
+    pq_sse: int
+    itp_sum_q20: int
+    itp_max_q20: int
+
+    @staticmethod
+    def from_c(s: CeHdrScores) -> "HdrFidelity":
+        return HdrFidelity(s.pq_psnr, s.delta_e_itp_mean, s.delta_e_itp_max, int(s.pq_sse), int(s.itp_sum_q20), int(s.itp_max_q20))
 
 
 def _cicp_fmt(a: np.ndarray) -> int:
@@ -1040,6 +1085,15 @@ class Context:
                                               config.flags, intensity_target, C.byref(s)))
         return MetricResult.from_c(s)
 
+    def hdr_fidelity(self, reference, test, width: int, height: int, depth: int = 10, white_nits: float = 203.0) -> HdrFidelity:
+        """PQ-PSNR and BT.2124 Delta E ITP of one pair of packed float32 RGB, linear light with sRGB primaries
+        (ce_eval_pair_hdr_fidelity): `depth` (10, 12 or 16) is the PQ code grid, `white_nits` the luminance of 1.0."""
+        r, t = _buf_f32(reference), _buf_f32(test)
+        s = CeHdrScores()
+        self._check(lib().ce_eval_pair_hdr_fidelity(self._h, r.ctypes.data, r.nbytes, t.ctypes.data, t.nbytes, width, height, depth,
+                                                    white_nits, C.byref(s)))
+        return HdrFidelity.from_c(s)
+
     def batch_linear(self, width: int, height: int, max_refs: int, max_pairs: int) -> "Batch":
         """A Batch whose slabs hold packed float32 RGB in linear light (ce_batch_create_linear): loaded with float32 arrays
         through set_reference / set_test, or with tagged code values through set_reference_cicp / set_test_cicp."""
@@ -1345,6 +1399,13 @@ class Batch:
         out = (CeScores * n_pairs)()
         self.ctx._check(lib().ce_batch_collect(self._h, n_pairs, out))
         return list(out)
+
+    def hdr_fidelity(self, n_pairs: int, depth: int = 10, white_nits: float = 203.0) -> List[HdrFidelity]:
+        """PQ-PSNR and BT.2124 Delta E ITP of pairs [0, n_pairs) of a linear batch (ce_batch_hdr_fidelity); returns once the
+        scores are on the host.  What launch() left to collect is untouched."""
+        out = (CeHdrScores * max(n_pairs, 1))()
+        self.ctx._check(lib().ce_batch_hdr_fidelity(self._h, n_pairs, depth, white_nits, out))
+        return [HdrFidelity.from_c(out[i]) for i in range(n_pairs)]
 
     def butteraugli_pnorm3(self, n_pairs: int) -> np.ndarray:
         out = np.zeros(n_pairs, np.float64)

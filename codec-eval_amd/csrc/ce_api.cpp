@@ -401,6 +401,8 @@ void ce_ctx_destroy(ce_ctx *ctx)
     ctx->deep_tables.clear();
     for (auto &kv : ctx->cicp_tables) hipFree(kv.second);
     ctx->cicp_tables.clear();
+    for (auto &kv : ctx->hdr_tables) hipFree(kv.second);
+    ctx->hdr_tables.clear();
     if (ctx->up2_stream) hipStreamSynchronize(ctx->up2_stream), hipStreamDestroy(ctx->up2_stream), hipEventDestroy(ctx->ev_up2);
     for (auto &st : ctx->aux_stream)  // after the last batch that may still drain them
         if (st) hipStreamSynchronize(st), hipStreamDestroy(st), st = nullptr;
@@ -550,6 +552,8 @@ void ce_batch_destroy(ce_batch *b)
     hipFree(b->d_pair_ref);
     hipFree(b->d_scores);
     if (b->h_scores) hipHostFree(b->h_scores);
+    hipFree(b->d_hdr);
+    if (b->h_hdr) hipHostFree(b->h_hdr);
     for (int k = 0; k < ce_batch::kStages; k++) {
         if (b->h_stage[k]) hipHostFree(b->h_stage[k]);
         if (b->ev_stage[k]) hipEventDestroy(b->ev_stage[k]);
@@ -921,6 +925,32 @@ void *ce_batch_reference_slab(ce_batch *b)
 }
 void *ce_batch_test_slab(ce_batch *b) { return b ? b->d_tests : nullptr; }
 
+// the pair -> reference table of the batch on the device, as the last ce_batch_bind_pair left it
+static int sync_pair_ref(ce_batch *b)
+{
+    if (!b->pair_ref_dirty) return CE_OK;
+    // pair_first[p] = the lowest pair index bound to the same reference as p: that pair's row pass also produces
+    // the two reference-only blur streams (a, a*a) which every pair of the reference then reads (ssim2.hip)
+    // ... and the inverse table, reference -> its pairs in ascending pair order (kernels that walk a reference's
+    // distorted images with the reference's planes held in registers: dssim.hip)
+    const size_t P = b->max_pairs, R = b->max_refs;
+    std::vector<uint32_t> table(3 * P + R + 1), first_of(R, ~0u), count(R + 1, 0);
+    for (uint32_t i = 0; i < P; i++) {
+        const uint32_t r = b->h_pair_ref[i];
+        if (first_of[r] == ~0u) first_of[r] = i;
+        table[i] = r;
+        table[P + i] = first_of[r];
+        count[r + 1]++;
+    }
+    for (size_t r = 0; r < R; r++) count[r + 1] += count[r];
+    for (size_t r = 0; r <= R; r++) table[2 * P + r] = count[r];
+    std::vector<uint32_t> fill(count.begin(), count.end() - 1);
+    for (uint32_t i = 0; i < P; i++) table[2 * P + R + 1 + fill[b->h_pair_ref[i]]++] = i;
+    if (int rc = ce_upload_table(b, b->d_pair_ref, table.data(), sizeof(uint32_t) * table.size())) return rc;  // `table` is pageable
+    b->pair_ref_dirty = false;
+    return CE_OK;
+}
+
 int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_t flags, float intensity_target)
 {
     if (!b) return CE_ERR_INVALID_ARG;
@@ -938,27 +968,7 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
         int rc = flush_uploads(b);
         if (rc != CE_OK) return rc;
     }
-    if (b->pair_ref_dirty) {
-        // pair_first[p] = the lowest pair index bound to the same reference as p: that pair's row pass also produces
-        // the two reference-only blur streams (a, a*a) which every pair of the reference then reads (ssim2.hip)
-        // ... and the inverse table, reference -> its pairs in ascending pair order (kernels that walk a reference's
-        // distorted images with the reference's planes held in registers: dssim.hip)
-        const size_t P = b->max_pairs, R = b->max_refs;
-        std::vector<uint32_t> table(3 * P + R + 1), first_of(R, ~0u), count(R + 1, 0);
-        for (uint32_t i = 0; i < P; i++) {
-            const uint32_t r = b->h_pair_ref[i];
-            if (first_of[r] == ~0u) first_of[r] = i;
-            table[i] = r;
-            table[P + i] = first_of[r];
-            count[r + 1]++;
-        }
-        for (size_t r = 0; r < R; r++) count[r + 1] += count[r];
-        for (size_t r = 0; r <= R; r++) table[2 * P + r] = count[r];
-        std::vector<uint32_t> fill(count.begin(), count.end() - 1);
-        for (uint32_t i = 0; i < P; i++) table[2 * P + R + 1 + fill[b->h_pair_ref[i]]++] = i;
-        if (int rc = ce_upload_table(b, b->d_pair_ref, table.data(), sizeof(uint32_t) * table.size())) return rc;  // `table` is pageable
-        b->pair_ref_dirty = false;
-    }
+    if (int rc = sync_pair_ref(b)) return rc;
     uint32_t n_refs_used = 0;
     for (uint32_t i = 0; i < n_pairs; i++) n_refs_used = std::max(n_refs_used, b->h_pair_ref[i] + 1);
 
@@ -2360,6 +2370,120 @@ int ce_yuv_hlg_to_linear(ce_ctx *ctx, const ce_yuv_image *image, const ce_hlg *h
     cicp_plan lin;
     if (int rc = yuv_hlg_check(ctx, image, hd, w, h, &plan, &lin)) return rc;
     return yuv_linear_to_host(ctx, image, plan, lin, w, h, out, out_len, "Y'CbCr HLG ingest");
+}
+
+// ---- HDR fidelity of linear batches: PQ-PSNR and BT.2124 Delta E ITP (hdr_fidelity.hip) ----------
+static bool hdr_depth_ok(uint32_t d) { return d == 10 || d == 12 || d == 16; }
+
+int ce_pq_code_thresholds(uint32_t depth, float white_nits, float *out, size_t n)
+{
+    if (!out || !hdr_depth_ok(depth) || n != ((size_t)1 << depth) - 1)
+        return fail(nullptr, CE_ERR_INVALID_ARG, "ce_pq_code_thresholds: depth 10, 12 or 16 and n = 2^depth - 1");
+    if (!ce_build_pq_code_thresholds((1u << depth) - 1u, (double)white_nits, out))
+        return fail(nullptr, CE_ERR_INVALID_ARG, "ce_pq_code_thresholds: white_nits must be finite and > 0");
+    return CE_OK;
+}
+
+int ce_hdr_fidelity_matrices(float a[9], float b[9])
+{
+    if (!a || !b) return fail(nullptr, CE_ERR_INVALID_ARG, "ce_hdr_fidelity_matrices: null pointer");
+    ce_build_hdr_fidelity_matrices(a, b);
+    return CE_OK;
+}
+
+// the thresholds of (depth, white_nits) on the device, built once per context and kept: [table, padded to 16 floats | at
+// depth 16 every 16th threshold]; *coarse is the level the kernel stages in LDS
+static int hdr_table_dev(ce_ctx *ctx, uint32_t depth, float white_nits, const float **table, const float **coarse)
+{
+    uint32_t white_bits;
+    std::memcpy(&white_bits, &white_nits, 4);
+    const size_t n = ((size_t)1 << depth) - 1, padded = (n + 15) & ~(size_t)15, n_coarse = depth > 12 ? ((size_t)1 << 12) - 1 : 0;
+    const auto key = std::make_pair(depth, white_bits);
+    auto it = ctx->hdr_tables.find(key);
+    if (it == ctx->hdr_tables.end()) {
+        std::vector<float> host(padded + n_coarse, INFINITY);
+        ce_build_pq_code_thresholds((uint32_t)n, (double)white_nits, host.data());
+        const size_t stride = (size_t)1 << (depth > 12 ? depth - 12 : 0);
+        for (size_t j = 0; j < n_coarse; j++) host[padded + j] = host[(j + 1) * stride - 1];
+        float *d = nullptr;
+        CE_HIP(ctx, hipMalloc(&d, host.size() * sizeof(float)));
+        if (hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+            hipFree(d);
+            return fail(ctx, CE_ERR_BACKEND, "H2D failed (PQ code thresholds)");
+        }
+        it = ctx->hdr_tables.emplace(key, d).first;
+    }
+    *table = it->second;
+    *coarse = n_coarse ? it->second + padded : it->second;
+    return CE_OK;
+}
+
+static int hdr_params_check(ce_ctx *ctx, uint32_t depth, float white_nits)
+{
+    if (!hdr_depth_ok(depth)) return fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: depth must be 10, 12 or 16, got " + std::to_string(depth));
+    if (!(white_nits > 0.0f && std::isfinite(white_nits))) return fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: white_nits must be finite and > 0");
+    return CE_OK;
+}
+
+int ce_batch_hdr_fidelity(ce_batch *b, uint32_t n_pairs, uint32_t depth, float white_nits, ce_hdr_scores *out)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    ce_ctx *ctx = b->ctx;
+    if (!out) return fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: null pointer");
+    if (!b->linear)
+        return fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity reads linear light: it needs a linear batch (ce_batch_create_linear)");
+    if (int rc = hdr_params_check(ctx, depth, white_nits)) return rc;
+    if (n_pairs == 0 || n_pairs > b->max_pairs) return fail(ctx, CE_ERR_INVALID_ARG, "n_pairs out of range");
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    const float *d_table = nullptr, *d_coarse = nullptr;
+    if (int rc = hdr_table_dev(ctx, depth, white_nits, &d_table, &d_coarse)) return rc;
+    if (!b->d_hdr) CE_HIP(ctx, hipMalloc(&b->d_hdr, sizeof(unsigned long long) * 3 * b->max_pairs));
+    if (!b->h_hdr) CE_HIP(ctx, hipHostMalloc(&b->h_hdr, sizeof(unsigned long long) * 3 * b->max_pairs, hipHostMallocDefault));
+    // on the context's stream, as a launch: behind the uploads queued so far, with the pair table of the last bind
+    if (int rc = flush_uploads(b)) return rc;
+    if (int rc = sync_pair_ref(b)) return rc;
+    float a[9], lms[9];
+    ce_build_hdr_fidelity_matrices(a, lms);
+    if (int rc = ce_launch_hdr_fidelity(b, n_pairs, depth, d_table, d_coarse, a, lms, b->d_hdr)) return rc;
+    CE_HIP(ctx, hipMemcpyAsync(b->h_hdr, b->d_hdr, sizeof(unsigned long long) * 3 * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
+    CE_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the slabs are free again: a later upload needs no fence against this
+    const double maxv = (double)((1u << depth) - 1u), n_px = (double)((size_t)b->w * b->h);
+    for (uint32_t i = 0; i < n_pairs; i++) {
+        ce_hdr_scores s{};
+        s.pq_sse = b->h_hdr[3 * i], s.itp_sum_q20 = b->h_hdr[3 * i + 1], s.itp_max_q20 = b->h_hdr[3 * i + 2];
+        s.pq_psnr = psnr_from_sse(s.pq_sse, b->w, b->h, maxv);
+        s.delta_e_itp_mean = (double)s.itp_sum_q20 / 1048576.0 / n_px;
+        s.delta_e_itp_max = (double)s.itp_max_q20 / 1048576.0;
+        out[i] = s;
+    }
+    return CE_OK;
+}
+
+// One pair of packed f32 RGB through the context's one-pair linear batch, as ce_eval_pair_linear
+int ce_eval_pair_hdr_fidelity(ce_ctx *ctx, const float *reference, size_t reference_len, const float *test, size_t test_len, uint32_t width,
+                              uint32_t height, uint32_t depth, float white_nits, ce_hdr_scores *out)
+{
+    if (!ctx) return CE_ERR_INVALID_ARG;
+    if (!out || !reference || !test) return fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: null pointer");
+    *out = ce_hdr_scores{};
+    if (width == 0 || height == 0) return fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: empty image");
+    if (int rc = hdr_params_check(ctx, depth, white_nits)) return rc;
+    const size_t want = (size_t)width * height * 12;
+    if (reference_len != want) return bad_length(ctx, want, reference_len);
+    if (test_len != want) return bad_length(ctx, want, test_len);
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    ce_batch *b = ctx->leaf_linear;
+    if (!b || b->w != width || b->h != height) {
+        ce_batch_destroy(b);
+        ctx->leaf_linear = nullptr;
+        if (int rc = ce_batch_create_linear(ctx, width, height, 1, 1, &ctx->leaf_linear)) return rc;
+        b = ctx->leaf_linear;
+    }
+    int rc = ce_batch_set_reference_fmt(b, 0, reference, reference_len, CE_PIXEL_RGB_F32);
+    if (rc == CE_OK) rc = ce_batch_set_test_fmt(b, 0, 0, test, test_len, CE_PIXEL_RGB_F32);
+    if (rc == CE_OK) rc = ce_batch_hdr_fidelity(b, 1, depth, white_nits, out);
+    if (rc != CE_OK) drain_batch(b);
+    return rc;
 }
 
 // ---- alpha: composited over solid backgrounds (alpha.hip) ----------------------------------------

@@ -88,6 +88,10 @@ struct ce_ctx {
     // built by the first ingest that needs one and kept until the context goes (ce_api.cpp: cicp_table).  The HLG ingest's
     // inverse-OETF tables (hlg.hip) live here too, one per depth, under H.273's code for HLG: (18, depth, 0) (hlg_table_dev)
     std::map<std::tuple<int, uint32_t, uint32_t>, float *> cicp_tables;
+    // threshold tables of the HDR fidelity scores (hdr_fidelity.hip), keyed by (depth, bits of white_nits), built by the first
+    // call that needs one and kept until the context goes (ce_api.cpp: hdr_table_dev): T[1 .. maxv], padded to a multiple of
+    // 16 floats, then at depth 16 the coarse level a block stages in LDS (every 16th threshold)
+    std::map<std::pair<uint32_t, uint32_t>, float *> hdr_tables;
 
     // profiling
     bool prof = false;         // record a HIP event pair around every launch (on the launch's own stream)
@@ -284,6 +288,9 @@ struct ce_batch {
     uint32_t ba_ref_count = 0;
     float ba_ref_intensity = 0.0f;
 
+    // HDR fidelity (hdr_fidelity.hip): [max_pairs][3] exact integers on the device and page-locked, made by the first call
+    unsigned long long *d_hdr = nullptr, *h_hdr = nullptr;
+
     uint32_t last_n_pairs = 0;
     bool caller_blocks = false;  // set by entry points that collect before returning: page-locked sources need no staging copy
     uint32_t last_mask = 0;
@@ -438,7 +445,17 @@ int ce_launch_hlg(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src
 int ce_launch_yuv_hlg(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32_t w, uint32_t h, float *d_dst, const float *d_table,
                       uint32_t maxv, const float *matrix, const double params[5]);
 
+// pairs [0, n_pairs) of a linear batch -> d_out[pair][3] = pq_sse, itp_sum_q20, itp_max_q20, cleared and filled on the
+// launching stream (hdr_fidelity.hip): d_table = T[1 .. maxv], 64-byte aligned, d_coarse the level staged in LDS (the table
+// itself at depths 10 and 12, every 16th threshold at 16), a / lms = ce_build_hdr_fidelity_matrices
+int ce_launch_hdr_fidelity(ce_batch *b, uint32_t n_pairs, uint32_t depth, const float *d_table, const float *d_coarse, const float a[9],
+                           const float lms[9], unsigned long long *d_out);
+
 // host-side constant builders (ce_tables.cpp)
+// HDR fidelity's PQ code thresholds (include/ce_metrics.h: ce_pq_code_thresholds; maxv entries; false unless white_nits is
+// finite and > 0) and its two matrices (ce_hdr_fidelity_matrices)
+bool ce_build_pq_code_thresholds(uint32_t maxv, double white_nits, float *out);
+void ce_build_hdr_fidelity_matrices(float a[9], float b[9]);
 // the HLG ingest's inverse-OETF table (include/ce_metrics.h: ce_hlg_table) and the Y row of the f64 XYZ <- src matrix of
 // `primaries` (ce_hlg_params' kR, kG, kB); false for primaries that are not offered
 void ce_build_hlg_table(uint32_t maxv, float *lut);

@@ -305,6 +305,24 @@ bool ce_build_transfer_table(int transfer, uint32_t maxv, double white_nits, flo
     return false;
 }
 
+// ---- HDR fidelity (include/ce_metrics.h: ce_pq_code_thresholds, ce_hdr_fidelity_matrices) ------------
+// The decision thresholds of PQ code values on linear light: T[c] = PQ_EOTF((c - 0.5) / maxv) / white_nits for c = 1 .. maxv,
+// at out[c - 1], with the constants and the operation order of the PQ branch above, in f64 and rounded once to f32.
+bool ce_build_pq_code_thresholds(uint32_t maxv, double white_nits, float *out)
+{
+    if (!(white_nits > 0.0) || !std::isfinite(white_nits)) return false;
+    const double m1 = 2610.0 / 16384.0, m2 = 2523.0 / 4096.0 * 128.0;
+    const double c1 = 3424.0 / 4096.0, c2 = 2413.0 / 4096.0 * 32.0, c3 = 2392.0 / 4096.0 * 32.0;
+    for (uint32_t c = 1; c <= maxv; c++) {
+        const double e = ((double)c - 0.5) / (double)maxv;
+        const double p = std::pow(e, 1.0 / m2);
+        const double num = std::fmax(p - c1, 0.0), den = c2 - c3 * p;
+        const double y = std::pow(num / den, 1.0 / m1);
+        out[c - 1] = (float)(10000.0 * y / white_nits);
+    }
+    return true;
+}
+
 namespace {
 // inverse of a 3 x 3 matrix by its adjugate, every operation written out (the restatement in tests/cicp_restatement.py
 // performs the same f64 operations in the same order)
@@ -362,6 +380,20 @@ bool ce_build_colour_matrix(int primaries, float m[9])
     for (int r = 0; r < 3; r++)
         for (int c = 0; c < 3; c++) m[3 * r + c] = (float)((ai[3 * r] * s[c] + ai[3 * r + 1] * s[3 + c]) + ai[3 * r + 2] * s[6 + c]);
     return true;
+}
+
+// HDR fidelity's two matrices, row-major: a = the inverse of ce_build_colour_matrix(9) - of the f32 matrix the ingest multiplies
+// by - taken in f64 by inv3 and rounded once to f32 (BT.2020 <- sRGB primaries); b = BT.2100's LMS <- BT.2020, n / 4096 each,
+// exact in f32.
+void ce_build_hdr_fidelity_matrices(float a[9], float b[9])
+{
+    static const int lms[9] = {1688, 2146, 262, 683, 2951, 462, 99, 309, 3688};
+    float m[9];
+    double md[9], inv[9];
+    ce_build_colour_matrix(9, m);
+    for (int i = 0; i < 9; i++) md[i] = (double)m[i];
+    inv3(md, inv);
+    for (int i = 0; i < 9; i++) a[i] = (float)inv[i], b[i] = (float)((double)lms[i] / 4096.0);
 }
 
 // ---- HLG ingest (include/ce_metrics.h: ce_hlg_table, ce_hlg_params) --------------------------------

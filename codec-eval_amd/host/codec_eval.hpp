@@ -524,6 +524,36 @@ inline void batch_set_test_yuv_hlg(const HipBackend &be, ce_batch *batch, uint32
 {
     detail::check(be, ce_batch_set_test_yuv_hlg(batch, pair_index, ref_index, &image, &hlg), "yuv_hlg", 0, 0, 0);
 }
+// ---- HDR fidelity of linear batches: PQ-PSNR and BT.2124 Delta E ITP (include/ce_metrics.h: ce_batch_hdr_fidelity) ----
+// depth (10, 12 or 16) names the PQ code grid, white_nits the luminance of sample value 1.0
+using HdrFidelity = ce_hdr_scores;
+// pairs [0, n_pairs) of a linear batch (eval::batch_linear); returns once the scores are on the host
+inline std::vector<HdrFidelity> batch_hdr_fidelity(const HipBackend &be, ce_batch *batch, uint32_t n_pairs, uint32_t depth = 10,
+                                                   float white_nits = 203.0f)
+{
+    std::vector<HdrFidelity> out(n_pairs);
+    detail::check(be, ce_batch_hdr_fidelity(batch, n_pairs, depth, white_nits, out.data()), "hdr_fidelity", 0, 0, 0);
+    return out;
+}
+// one pair of packed float RGB, linear light with sRGB primaries (width * height * 3 floats each)
+inline HdrFidelity hdr_fidelity(const HipBackend &be, const float *reference, const float *test, uint32_t width, uint32_t height,
+                                uint32_t depth = 10, float white_nits = 203.0f)
+{
+    HdrFidelity out{};
+    const size_t len = (size_t)width * height * 12;
+    detail::check(be, ce_eval_pair_hdr_fidelity(be.ctx(), reference, len, test, len, width, height, depth, white_nits, &out), "hdr_fidelity",
+                  width, height, len);
+    return out;
+}
+// the decision thresholds of PQ code values on linear light, T[1 .. 2^depth - 1] (a pure host function; empty when refused)
+inline std::vector<float> pq_code_thresholds(uint32_t depth, float white_nits = 203.0f)
+{
+    std::vector<float> out(depth == 10 || depth == 12 || depth == 16 ? ((size_t)1 << depth) - 1 : 0);
+    if (out.empty() || ce_pq_code_thresholds(depth, white_nits, out.data(), out.size()) != CE_OK) out.clear();
+    return out;
+}
+// the two matrices the kernel is handed, row-major: BT.2020 <- sRGB primaries, BT.2100's LMS <- BT.2020
+inline void hdr_fidelity_matrices(std::array<float, 9> &a, std::array<float, 9> &b) { ce_hdr_fidelity_matrices(a.data(), b.data()); }
 // straight into a slot of a resident batch (RGB8 or deep), host or device planes
 inline void batch_set_reference_yuv(const HipBackend &be, ce_batch *batch, uint32_t ref_index, const YuvImage &image)
 {

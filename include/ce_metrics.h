@@ -769,6 +769,64 @@ int ce_yuv_hlg_to_linear(ce_ctx *ctx, const ce_yuv_image *image, const ce_hlg *h
 int ce_hlg_table(uint32_t depth, float *out, size_t n);
 int ce_hlg_params(const ce_hlg *h, double out[5]);
 
+/* ---- HDR fidelity of linear batches: PQ-PSNR and BT.2124 Delta E ITP ----------------------------------
+ * The two plain fidelity numbers HDR encoders are compared by, next to the perceptual scores: PSNR of the PQ code values, and
+ * the Delta E ITP of Rec. ITU-R BT.2124 as a mean and a maximum over the pixels.  A linear batch has no integer grid of its
+ * own (which is why CE_METRIC_PSNR stays clear on it), so the call names one: `depth` (10, 12 or 16; maxv = 2^depth - 1) and
+ * `white_nits`, the luminance of sample value 1.0, finite and > 0 - Butteraugli's intensity target, the PQ ingest's white_nits.
+ * The definition is made of integers and correctly rounded IEEE operations only; everything that is summed is an integer, so
+ * the results do not depend on the order of summation.
+ * Thresholds.  T[c] = f32(PQ_EOTF((c - 0.5) / maxv) / white_nits) for c = 1 .. maxv, built on the host in f64 with ST 2084's
+ *   constants and operation order exactly as ce_transfer_table's PQ branch has them (e = (c - 0.5) / maxv, p = e^(1/m2),
+ *   nits = 10000 * (max(p - c1, 0) / (c2 - c3 p))^(1/m1), T = nits / white_nits) and rounded once to f32
+ *   (ce_pq_code_thresholds; out[c - 1] = T[c]).  code(x) = the number of c with T[c] <= x, a binary search:
+ *   numpy.searchsorted(T, x, side="right").  Negatives, zero and NaN give 0, anything at or above T[maxv] gives maxv.  The PQ
+ *   curve is never evaluated on the device.  code(ce_transfer_table(16, depth, white_nits)[v]) = v for every v: the search
+ *   inverts the PQ ingest exactly.
+ * Per pixel of either image (linear light, sRGB primaries):
+ *   1. q = A rgb, q_i = (A[i][0] * r + A[i][1] * g) + A[i][2] * b in f32, every product and sum rounded separately (no fused
+ *      multiply-add: the form of the CICP definition's step 3).  A = the inverse of ce_colour_matrix(9) - of that f32 matrix,
+ *      widened to f64, inverted by its adjugate in f64 and rounded once to f32: BT.2020 <- sRGB primaries.
+ *   2. l = B q in the same form, B = BT.2100's [[1688, 2146, 262], [683, 2951, 462], [99, 309, 3688]] / 4096, exact in f32.
+ *      (ce_hdr_fidelity_matrices returns A and B, row-major.)
+ *   3. Rc, Gc, Bc = code(q);  Lc, Mc, Sc = code(l).
+ *   4. in 64-bit integers, exactly: i = 2048 (Lc + Mc), ct = 6610 Lc - 13613 Mc + 7003 Sc, cp = 17933 Lc - 17390 Mc - 543 Sc:
+ *      BT.2100's ICtCp times 4096 * maxv.  BT.2124's T is Ct / 2.
+ * Per pair, d* = reference minus test:
+ *   pq_sse       = the sum over the pixels of dRc^2 + dGc^2 + dBc^2, in u64.
+ *   per pixel      s = (di * di + 0.25 * (dct * dct)) + dcp * dcp in f64, the integer differences converted first and every
+ *                  operation rounded separately; e = 720 * sqrt(s) / (4096 * maxv) with a correctly rounded sqrt, the product
+ *                  before the quotient; k = (u64) rint(e * 2^20), under 2^32.
+ *   itp_sum_q20  = the sum of k;  itp_max_q20 = the maximum of k.
+ *   pq_psnr          = 10 log10(maxv^2 / (pq_sse / (3 n))) in f64, n the pixels of an image; identical codes: what PSNR
+ *                      returns for identical images, +infinity
+ *   delta_e_itp_mean = itp_sum_q20 / 2^20 / n;  delta_e_itp_max = itp_max_q20 / 2^20.
+ * tests/hdr_fidelity_restatement.py restates this in numpy; the device equals it bit for bit. */
+typedef struct ce_hdr_scores {
+    double pq_psnr;          /* dB; +infinity when no PQ code differs */
+    double delta_e_itp_mean; /* BT.2124 Delta E ITP, mean over the pixels (1 is about one just noticeable difference) */
+    double delta_e_itp_max;  /* ... and its maximum */
+    uint64_t pq_sse;         /* the exact integers the three are finished from */
+    uint64_t itp_sum_q20;
+    uint64_t itp_max_q20;
+} ce_hdr_scores;             /* 48 bytes */
+/* Scores pairs [0, n_pairs) of a LINEAR batch into out[0 .. n_pairs): one kernel on the context's stream, ordered behind the
+ * uploads queued so far as a launch is; blocks until the scores are on the host.  ce_scores, its `valid` bits and whatever
+ * ce_batch_launch left to collect are untouched.  CE_ERR_INVALID_ARG, with the reason in ce_last_error and the batch still
+ * usable, for a batch that is not linear, a depth other than 10, 12 or 16, a white_nits that is not finite and > 0, a null
+ * pointer, n_pairs of 0 or past the batch. */
+int ce_batch_hdr_fidelity(ce_batch *b, uint32_t n_pairs, uint32_t depth, float white_nits, ce_hdr_scores *out);
+/* One pair of packed float RGB through the same kernel (lengths in bytes: width * height * 12; NaN -> 0 and the clamp of a
+ * linear image apply, as in ce_eval_pair_linear).  CE_ERR_INVALID_ARG as above and for an empty image, CE_ERR_BAD_LENGTH for a
+ * length that is not width * height * 12. */
+int ce_eval_pair_hdr_fidelity(ce_ctx *ctx, const float *reference, size_t reference_len, const float *test, size_t test_len,
+                              uint32_t width, uint32_t height, uint32_t depth, float white_nits, ce_hdr_scores *out);
+/* Pure host functions: the thresholds (n = 2^depth - 1 entries, out[c - 1] = T[c]; CE_ERR_INVALID_ARG for another depth or n,
+ * a null pointer, a white_nits that is not finite and > 0) and the two matrices, row-major - exactly what the kernel is
+ * handed. */
+int ce_pq_code_thresholds(uint32_t depth, float white_nits, float *out, size_t n);
+int ce_hdr_fidelity_matrices(float a[9], float b[9]);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------ */
 /* Bracket every kernel launch with a HIP event pair, recorded on the stream the kernel is launched on,
  * and accumulate per-kernel time.  on = 0: off (default).  on = 2: events only; the batch keeps its
