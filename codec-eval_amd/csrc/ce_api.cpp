@@ -1,6 +1,7 @@
 // Host runtime behind the C ABI (include/ce_metrics.h): contexts, the HBM-resident pair
 // grid, shape bucketing for mixed batches, input validation with the reference's error
-// kinds, profiling hooks.  All device work is in the .hip files; there is no CPU compute
+// kinds, profiling hooks.  Everything that writes a slot of a batch is in ce_ingest.cpp.
+// All device work is in the .hip files; there is no CPU compute
 // path here — if HIP is unavailable every entry point fails with CE_ERR_BACKEND.
 #include <algorithm>
 #include <atomic>
@@ -15,29 +16,29 @@
 
 #include "ce_internal.h"
 
-namespace {
+static thread_local std::string g_err_noctx;
 
-thread_local std::string g_err_noctx;
-
-int fail(ce_ctx *ctx, int code, const std::string &msg)
+int ce_fail(ce_ctx *ctx, int code, const std::string &msg)
 {
     if (ctx) ctx->err = msg; else g_err_noctx = msg;
     return code;
 }
 
-int bad_length(ce_ctx *ctx, size_t want, size_t got)
+int ce_bad_length(ce_ctx *ctx, size_t want, size_t got)
 {
-    return fail(ctx, CE_ERR_BAD_LENGTH, "Invalid image size: expected " + std::to_string(want) + " bytes, got " + std::to_string(got));
+    return ce_fail(ctx, CE_ERR_BAD_LENGTH, "Invalid image size: expected " + std::to_string(want) + " bytes, got " + std::to_string(got));
 }
+
+namespace {
 
 // validation order of calculate_ssimulacra2 / calculate_butteraugli
 // (src/metrics/ssimulacra2.rs:65-82, src/metrics/butteraugli.rs:51-67)
 int validate_pair(ce_ctx *ctx, size_t ref_len, size_t test_len, size_t w, size_t h)
 {
     if (ref_len != test_len)
-        return fail(ctx, CE_ERR_DIM_MISMATCH, "Dimension mismatch: reference " + std::to_string(ref_len) +
+        return ce_fail(ctx, CE_ERR_DIM_MISMATCH, "Dimension mismatch: reference " + std::to_string(ref_len) +
                                                    " bytes, test " + std::to_string(test_len) + " bytes");
-    if (ref_len != w * h * 3) return bad_length(ctx, w * h * 3, ref_len);
+    if (ref_len != w * h * 3) return ce_bad_length(ctx, w * h * 3, ref_len);
     return CE_OK;
 }
 
@@ -50,13 +51,13 @@ int check_map_readout(ce_ctx *ctx, const char *what, uint32_t stored, uint32_t f
                       uint32_t h, bool has_out, size_t out_floats)
 {
     if (count == 0 || first > stored || count > stored - first)
-        return fail(ctx, CE_ERR_INVALID_ARG, std::string(what) + " pairs [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) +
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, std::string(what) + " pairs [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) +
                                                  ") outside the " + std::to_string(stored) + " stored");
     if (block == 0 || block > 64 || (block & (block - 1)) != 0)
-        return fail(ctx, CE_ERR_INVALID_ARG, std::string(what) + " block must be 1 or a power of two up to 64");
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, std::string(what) + " block must be 1 or a power of two up to 64");
     const size_t want = has_out ? (size_t)count * ((w + block - 1) / block) * ((h + block - 1) / block) : 0;
     if (out_floats != want)
-        return fail(ctx, CE_ERR_INVALID_ARG, std::string(what) + " readout needs " + std::to_string(want) + " floats, got " + std::to_string(out_floats));
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, std::string(what) + " readout needs " + std::to_string(want) + " floats, got " + std::to_string(out_floats));
     return CE_OK;
 }
 
@@ -67,7 +68,7 @@ int read_diffmaps(ce_batch *b, uint32_t first, uint32_t count, uint32_t block, f
     if (!b || !out) return CE_ERR_INVALID_ARG;
     ce_ctx *ctx = b->ctx;
     if (b->ba_map_pairs == 0)
-        return fail(ctx, CE_ERR_INVALID_ARG, "no Butteraugli diffmaps: the last launch did not run Butteraugli with CE_FLAG_BUTTERAUGLI_DIFFMAP");
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "no Butteraugli diffmaps: the last launch did not run Butteraugli with CE_FLAG_BUTTERAUGLI_DIFFMAP");
     if (int rc = check_map_readout(ctx, "diffmap", b->ba_map_pairs, first, count, block, b->w, b->h, true, out_floats)) return rc;
     CE_HIP(ctx, hipSetDevice(ctx->device));
     return ce_butteraugli_read_maps(b, first, count, block, out);
@@ -80,9 +81,9 @@ int read_ssim_maps(ce_batch *b, uint32_t level, uint32_t first, uint32_t count, 
 {
     if (!b || (!maps && !ssim)) return CE_ERR_INVALID_ARG;
     ce_ctx *ctx = b->ctx;
-    if (b->ds_map_pairs == 0) return fail(ctx, CE_ERR_INVALID_ARG, "no DSSIM SSIM maps: the last launch did not run DSSIM");
+    if (b->ds_map_pairs == 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, "no DSSIM SSIM maps: the last launch did not run DSSIM");
     if (level >= (uint32_t)b->ds_levels)
-        return fail(ctx, CE_ERR_INVALID_ARG, "DSSIM level " + std::to_string(level) + " of " + std::to_string(b->ds_levels));
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "DSSIM level " + std::to_string(level) + " of " + std::to_string(b->ds_levels));
     const auto &d = b->ds[level];
     if (int rc = check_map_readout(ctx, "SSIM map", b->ds_map_pairs, first, count, block, d.w, d.h, maps != nullptr, maps_floats)) return rc;
     CE_HIP(ctx, hipSetDevice(ctx->device));
@@ -94,17 +95,17 @@ int read_ssim_maps(ce_batch *b, uint32_t level, uint32_t first, uint32_t count, 
 int read_ssim2_maps(ce_batch *b, uint32_t scale, uint32_t channel, uint32_t kind, uint32_t first, uint32_t count, uint32_t block,
                     float *maps, size_t maps_floats, double *norms)
 {
-    if (!b) return fail(nullptr, CE_ERR_INVALID_ARG, "null handle");
+    if (!b) return ce_fail(nullptr, CE_ERR_INVALID_ARG, "null handle");
     ce_ctx *ctx = b->ctx;
-    if (!maps && !norms) return fail(ctx, CE_ERR_INVALID_ARG, "SSIMULACRA2 maps readout without an output");
+    if (!maps && !norms) return ce_fail(ctx, CE_ERR_INVALID_ARG, "SSIMULACRA2 maps readout without an output");
     if (b->s2_norm_pairs == 0)
-        return fail(ctx, CE_ERR_INVALID_ARG, "no SSIMULACRA2 maps or norms: the last launch did not run SSIMULACRA2");
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "no SSIMULACRA2 maps or norms: the last launch did not run SSIMULACRA2");
     if (maps && b->s2_map_pairs == 0)
-        return fail(ctx, CE_ERR_INVALID_ARG, "no SSIMULACRA2 maps: the last launch did not run SSIMULACRA2 with CE_FLAG_SSIMULACRA2_MAPS");
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "no SSIMULACRA2 maps: the last launch did not run SSIMULACRA2 with CE_FLAG_SSIMULACRA2_MAPS");
     if (scale >= b->s2_scales_run)
-        return fail(ctx, CE_ERR_INVALID_ARG, "SSIMULACRA2 scale " + std::to_string(scale) + " of " + std::to_string(b->s2_scales_run) + " that ran");
-    if (channel >= 3) return fail(ctx, CE_ERR_INVALID_ARG, "SSIMULACRA2 channel " + std::to_string(channel) + " of 3");
-    if (kind >= 3) return fail(ctx, CE_ERR_INVALID_ARG, "SSIMULACRA2 map kind " + std::to_string(kind) + " of 3");
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "SSIMULACRA2 scale " + std::to_string(scale) + " of " + std::to_string(b->s2_scales_run) + " that ran");
+    if (channel >= 3) return ce_fail(ctx, CE_ERR_INVALID_ARG, "SSIMULACRA2 channel " + std::to_string(channel) + " of 3");
+    if (kind >= 3) return ce_fail(ctx, CE_ERR_INVALID_ARG, "SSIMULACRA2 map kind " + std::to_string(kind) + " of 3");
     const ce_scale_dims &d = b->sd[scale];
     if (int rc = check_map_readout(ctx, "SSIMULACRA2 map", maps ? b->s2_map_pairs : b->s2_norm_pairs, first, count, block, d.w, d.h,
                                    maps != nullptr, maps_floats))
@@ -122,8 +123,6 @@ double psnr_from_sse(unsigned long long sse, size_t w, size_t h, double maxv = 2
     return 10.0 * std::log10(maxv * maxv / mse);
 }
 
-bool deep_depth_ok(uint32_t d) { return d == 8 || d == 10 || d == 12 || d == 16; }
-
 // The sRGB -> linear table of a deep batch's side on the device: 2^depth entries by `rule` (0: ce_build_srgb_table_f64,
 // 1: ce_build_srgb_table_powf), built once per context and kept (ce_ctx::deep_tables).
 int ce_deep_table(ce_ctx *ctx, uint32_t depth, int rule, const float **out)
@@ -138,7 +137,7 @@ int ce_deep_table(ce_ctx *ctx, uint32_t depth, int rule, const float **out)
         CE_HIP(ctx, hipMalloc(&d, host.size() * sizeof(float)));
         if (hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
             hipFree(d);
-            return fail(ctx, CE_ERR_BACKEND, "H2D failed (deep sRGB table)");
+            return ce_fail(ctx, CE_ERR_BACKEND, "H2D failed (deep sRGB table)");
         }
         it = ctx->deep_tables.emplace(key, d).first;
     }
@@ -273,8 +272,8 @@ int ce_ctx_create_on_stream(int device, void *hip_stream, ce_ctx **out)
     *out = nullptr;
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return fail(nullptr, CE_ERR_BACKEND, "no HIP device visible");
-    if (device < 0 || device >= n) return fail(nullptr, CE_ERR_INVALID_ARG, "device index out of range");
+        return ce_fail(nullptr, CE_ERR_BACKEND, "no HIP device visible");
+    if (device < 0 || device >= n) return ce_fail(nullptr, CE_ERR_INVALID_ARG, "device index out of range");
     ce_ctx *ctx = new (std::nothrow) ce_ctx();
     if (!ctx) return CE_ERR_BACKEND;
     ctx->device = device;
@@ -520,8 +519,8 @@ int ce_batch_create_deep(ce_ctx *ctx, uint32_t width, uint32_t height, uint32_t 
 {
     if (!ctx || !out) return CE_ERR_INVALID_ARG;
     *out = nullptr;
-    if (!deep_depth_ok(ref_depth) || !deep_depth_ok(test_depth))
-        return fail(ctx, CE_ERR_INVALID_ARG, "a deep batch's depths must be 8, 10, 12 or 16 bits, got " + std::to_string(ref_depth) +
+    if (!ce_deep_depth_ok(ref_depth) || !ce_deep_depth_ok(test_depth))
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "a deep batch's depths must be 8, 10, 12 or 16 bits, got " + std::to_string(ref_depth) +
                                                  " / " + std::to_string(test_depth));
     return batch_create(ctx, width, height, max_refs, max_pairs, ref_depth, test_depth, out);
 }
@@ -568,363 +567,6 @@ void ce_batch_destroy(ce_batch *b)
     delete b;
 }
 
-// the reference slab is about to change: whatever was derived from it (XYB roundtrip, SSIMULACRA2 XYB pyramid, DSSIM
-// img / mu / sq pyramid, Butteraugli PsychoImage) is rebuilt by the next launch
-static void invalidate_reference_state(ce_batch *b)
-{
-    b->ssim2_ref_src = nullptr;
-    b->ds_ref_src = nullptr;
-    b->ba_ref_src = nullptr;
-    b->refs_rt_valid = false;
-}
-
-// true if the runtime knows `p` as page-locked host memory (hipHostMalloc / hipHostRegister): the DMA engine can
-// read it directly
-static bool is_pinned_host(const void *p)
-{
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();  // an ordinary pageable pointer is reported as an error: clear it
-        return false;
-    }
-    return a.type == hipMemoryTypeHost;
-}
-
-// kernels (context stream) must see everything uploaded so far
-static int flush_uploads(ce_batch *b)
-{
-    if (!b->uploads_pending) return CE_OK;
-    ce_ctx *ctx = b->ctx;
-    CE_HIP(ctx, hipEventRecord(b->ev_up, b->up_stream));
-    CE_HIP(ctx, hipStreamWaitEvent(ctx->stream, b->ev_up, 0));
-    b->uploads_pending = false;
-    return CE_OK;
-}
-
-// Called before every write into a slot; the one ordering rule of slot writes.  A slot is written either on the context's
-// stream (the inline route of a small batch, upload()) or on the batch's upload stream (everything else).  A write on the
-// context's stream while uploads are pending runs flush_uploads first; a write on the upload stream waits for the batch's
-// last launch, which may still read the slabs, and after an inline write that no launch has followed yet, for the
-// context's stream.  A batch whose images all take one route never meets either fence.
-static int order_write(ce_batch *b, bool on_ctx_stream)
-{
-    ce_ctx *ctx = b->ctx;
-    if (on_ctx_stream) {
-        b->inline_pending = true;  // cleared by the next launch, which runs behind it on the same stream
-        return flush_uploads(b);
-    }
-    if (b->run_pending) {
-        CE_HIP(ctx, hipStreamWaitEvent(b->up_stream, b->ev_run, 0));
-        b->run_pending = false;  // ordered from here on
-    }
-    if (b->inline_pending) {
-        CE_HIP(ctx, hipEventRecord(b->ev_up, ctx->stream));
-        CE_HIP(ctx, hipStreamWaitEvent(b->up_stream, b->ev_up, 0));
-        b->inline_pending = false;
-    }
-    return CE_OK;
-}
-
-// One image into a device slot on stream `s`; returns the HIP error (no ctx->err), so that upload threads can call it.
-// stage < 0: a page-locked source the DMA engine reads in place (the caller collects before it can go away); otherwise
-// the source goes through pinned staging slot `stage` (once its previous DMA is done) and is consumed on return.
-static hipError_t copy_in(ce_batch *b, int stage, uint8_t *dst, const uint8_t *src, hipStream_t s)
-{
-    if (stage < 0) return hipMemcpyAsync(dst, src, b->img_bytes, hipMemcpyHostToDevice, s);
-    hipError_t e = b->stage_busy[stage] ? hipEventSynchronize(b->ev_stage[stage]) : hipSuccess;
-    if (e == hipSuccess) {
-        std::memcpy(b->h_stage[stage], src, b->img_bytes);
-        e = hipMemcpyAsync(dst, b->h_stage[stage], b->img_bytes, hipMemcpyHostToDevice, s);
-    }
-    if (e == hipSuccess) e = hipEventRecord(b->ev_stage[stage], s);
-    b->stage_busy[stage] = true;
-    return e;
-}
-
-static int upload(ce_batch *b, uint8_t *dst, const uint8_t *src, bool allow_inline = true)
-{
-    ce_ctx *ctx = b->ctx;
-    // pageable source -> pinned staging ring -> device on the batch's upload stream: the DMA of this slot overlaps the
-    // host copy into the next one and the kernels of other batches
-    CE_HIP(ctx, hipSetDevice(ctx->device));  // the calling thread's current device may be another one (multi-device hosts)
-    // A small batch (the one-pair-per-call regime of a reference handle) uploads on the context's own stream: its launch
-    // follows at once, and a cross-stream event between the copy and the first kernel costs ~25 us of its ~0.5 ms
-    // (not for an image that a format conversion or a colour table follows on the upload stream: allow_inline = false)
-    const bool inline_copy = allow_inline && (double)b->max_pairs * b->w * b->h <= 4e6;
-    if (int rc = order_write(b, inline_copy)) return rc;
-    // A BLOCKING entry point (ce_ref_compare*, which collects before it returns) whose caller's image is page-locked
-    // (ce_host_alloc) needs no staging copy: the DMA engine reads the caller's buffer, which outlives the call's kernels.
-    const int stage = b->caller_blocks && is_pinned_host(src) ? -1 : b->next_stage;
-    if (stage >= 0) b->next_stage = (stage + 1) % ce_batch::kStages;
-    const hipError_t e = copy_in(b, stage, dst, src, inline_copy ? ctx->stream : b->up_stream);
-    if (!inline_copy) b->uploads_pending = true;
-    if (e != hipSuccess) return fail(ctx, CE_ERR_BACKEND, std::string("upload: ") + hipGetErrorString(e));
-    return CE_OK;
-}
-
-// Many images at once (ce_eval_batch): the host copies into the pinned ring are spread over a few threads, each
-// with its own pair of ring slots, because one thread's memcpy (~12 GB/s) is slower than the PCIe link.
-struct upload_job {
-    uint8_t *dst;
-    const uint8_t *src;
-};
-
-static int upload_many(ce_batch *b, const std::vector<upload_job> &jobs)
-{
-    ce_ctx *ctx = b->ctx;
-    if (jobs.empty()) return CE_OK;
-    CE_HIP(ctx, hipSetDevice(ctx->device));
-    // Page-locked sources skip the staging ring: one asynchronous copy per image straight from the caller's buffer.
-    // Only ce_eval_batch comes through here, and it collects (synchronises) before it returns, so the buffers
-    // outlive the copies.
-    const bool all_pinned = std::all_of(jobs.begin(), jobs.end(), [](const upload_job &j) { return is_pinned_host(j.src); });
-    const int n_threads = (int)std::min<size_t>({(size_t)ce_batch::kStages / 2, jobs.size(),
-                                                 (size_t)std::max(1u, std::thread::hardware_concurrency())});
-    if (!all_pinned && (n_threads <= 1 || b->img_bytes < (64u << 10))) {
-        for (const auto &j : jobs) {
-            int rc = upload(b, j.dst, j.src, false);
-            if (rc != CE_OK) return rc;
-        }
-        return CE_OK;
-    }
-    // One stream moves a 786 KB image in 38 us (20.6 GB/s): the 1.88 GB of the Kodak + CID22 sweep would take as long as its
-    // kernels.  The copies of a chunk therefore alternate between the batch's upload stream and a second one of the context,
-    // which is fenced on both sides so that everything else keeps seeing "the uploads are on up_stream".
-    static const int n_up = [] {
-        const char *e = std::getenv("CE_UPLOAD_STREAMS");
-        return e ? std::max(1, std::min(2, std::atoi(e))) : 2;  // 2000 pairs of 512x512, page-locked: 99.9 -> 95.4 ms; pageable: see r03_experiments 17
-    }();
-    const bool two_up = n_up == 2 && jobs.size() >= 16;
-    auto up2_begin = [&]() -> int {
-        if (!ctx->up2_stream) {
-            CE_HIP(ctx, hipStreamCreateWithFlags(&ctx->up2_stream, hipStreamNonBlocking));
-            CE_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_up2, hipEventDisableTiming));
-        }
-        CE_HIP(ctx, hipEventRecord(ctx->ev_up2, b->up_stream));  // behind whatever up_stream already waits for
-        CE_HIP(ctx, hipStreamWaitEvent(ctx->up2_stream, ctx->ev_up2, 0));
-        return CE_OK;
-    };
-    auto up2_end = [&]() -> int {
-        CE_HIP(ctx, hipEventRecord(ctx->ev_up2, ctx->up2_stream));
-        CE_HIP(ctx, hipStreamWaitEvent(b->up_stream, ctx->ev_up2, 0));
-        return CE_OK;
-    };
-    if (int rc = order_write(b, false)) return rc;
-    if (two_up)
-        if (int rc = up2_begin()) return rc;
-    std::atomic<size_t> next{0};
-    std::atomic<int> err{(int)hipSuccess};
-    const int device = ctx->device;
-    auto worker = [&](int t) {
-        if (hipSetDevice(device) != hipSuccess) return;
-        for (int flip = 0;; flip ^= 1) {
-            const size_t i = next.fetch_add(1);
-            if (i >= jobs.size()) break;
-            // page-locked: one thread whose copies alternate between the streams; staged: a worker's two ring slots stay on its stream
-            const hipStream_t us = (two_up && ((all_pinned ? i : (size_t)t) & 1)) ? ctx->up2_stream : b->up_stream;
-            const hipError_t e = copy_in(b, all_pinned ? -1 : 2 * t + flip, jobs[i].dst, jobs[i].src, us);
-            if (e != hipSuccess) {
-                err.store((int)e);
-                break;
-            }
-        }
-    };
-    std::vector<std::thread> pool;
-    for (int t = 1; t < (all_pinned ? 1 : n_threads); t++) {
-        try {
-            pool.emplace_back(worker, t);
-        } catch (...) {  // no thread to be had: the calling thread's loop below takes whatever is left (nothing may be thrown across the C ABI)
-            break;
-        }
-    }
-    worker(0);
-    for (auto &th : pool) th.join();
-    b->uploads_pending = true;
-    if (two_up)
-        if (int rc = up2_end()) return rc;
-    if (err.load() != (int)hipSuccess)
-        return fail(ctx, CE_ERR_BACKEND, std::string("upload: ") + hipGetErrorString((hipError_t)err.load()));
-    return CE_OK;
-}
-
-static const char *const kLinearWants =
-    "a linear batch takes CE_PIXEL_RGB_F32 through ce_batch_set_*_fmt and tagged code values through ce_batch_set_*_cicp";
-
-int ce_batch_set_reference(ce_batch *b, uint32_t ref_index, const uint8_t *rgb, size_t len)
-{
-    if (!b || !rgb) return CE_ERR_INVALID_ARG;
-    if (ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "ref_index out of range");
-    if (b->depth[0]) return ce_batch_set_reference_fmt(b, ref_index, rgb, len, CE_PIXEL_RGB8);  // a deep batch: widened on the device
-    if (b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kLinearWants);
-    if (len != b->img_bytes) return bad_length(b->ctx, b->img_bytes, len);
-    invalidate_reference_state(b);  // cached reference-side planes are stale
-    return upload(b, b->d_refs + (size_t)ref_index * b->img_bytes, rgb);
-}
-
-// `len` bytes of a decoder's image -> wide staging pair k -> its device half, on the batch's upload stream (the caller
-// launches the conversion behind it, records ev_wide[k] and marks the pair busy)
-static int wide_stage(ce_batch *b, int k, const void *pixels, size_t len)
-{
-    ce_ctx *ctx = b->ctx;
-    const size_t cap = (size_t)b->w * b->h * (b->linear ? 12 : 8);
-    if (!b->h_wide[k]) {
-        CE_HIP(ctx, hipHostMalloc((void **)&b->h_wide[k], cap, hipHostMallocDefault));
-        CE_HIP(ctx, hipMalloc((void **)&b->d_wide[k], cap));
-        CE_HIP(ctx, hipEventCreateWithFlags(&b->ev_wide[k], hipEventDisableTiming));
-    }
-    if (int rc = order_write(b, false)) return rc;
-    if (b->wide_busy[k]) CE_HIP(ctx, hipEventSynchronize(b->ev_wide[k]));  // this staging pair's previous image has been converted
-    std::memcpy(b->h_wide[k], pixels, len);
-    CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], len, hipMemcpyHostToDevice, b->up_stream));
-    return CE_OK;
-}
-
-// pixels in a decoder's format -> wide staging -> device -> ingest kernel writes the RGB8 slab slot
-// (a deep batch: -> the ingest kernel that writes the u16 slab slot of that side, depth `depth`; 0 = an RGB8 batch)
-static int upload_fmt(ce_batch *b, uint8_t *dst, const void *pixels, size_t len, int format, uint32_t depth)
-{
-    ce_ctx *ctx = b->ctx;
-    const size_t bpp = ce_pixel_bytes(format), n_px = (size_t)b->w * b->h;
-    if (bpp == 0) return fail(ctx, CE_ERR_INVALID_ARG, "unknown pixel format");
-    if (b->linear != (format == CE_PIXEL_RGB_F32))
-        return fail(ctx, CE_ERR_INVALID_ARG, b->linear ? kLinearWants : "CE_PIXEL_RGB_F32 needs a linear batch (ce_batch_create_linear)");
-    const bool fmt16 = format == CE_PIXEL_RGB16 || format == CE_PIXEL_RGBA16, fmt8 = format == CE_PIXEL_RGB8 || format == CE_PIXEL_RGBA8;
-    if (!depth && fmt16) return fail(ctx, CE_ERR_INVALID_ARG, "CE_PIXEL_RGB16 / CE_PIXEL_RGBA16 need a deep batch (ce_batch_create_deep)");
-    if (depth && !fmt16 && !fmt8)
-        return fail(ctx, CE_ERR_INVALID_ARG, "the *_10BIT formats round to 8 bits: a deep batch takes CE_PIXEL_RGB16 / CE_PIXEL_RGBA16");
-    if (depth && fmt8 && depth != 8)
-        return fail(ctx, CE_ERR_INVALID_ARG, "an 8-bit image needs a side of depth 8, this one has " + std::to_string(depth));
-    if (len != n_px * bpp) return bad_length(ctx, n_px * bpp, len);
-    if (format == CE_PIXEL_RGB8 && !depth) return upload(b, dst, static_cast<const uint8_t *>(pixels), false);
-    CE_HIP(ctx, hipSetDevice(ctx->device));  // the staging allocations and the ingest launch below go to the context's device
-    const int k = b->next_wide;
-    b->next_wide ^= 1;
-    if (int rc = wide_stage(b, k, pixels, len)) return rc;
-    int rc = b->linear ? ce_launch_linear_sanitise(ctx, b->up_stream, reinterpret_cast<const float *>(b->d_wide[k]), reinterpret_cast<float *>(dst), n_px * 3)
-             : depth ? ce_launch_ingest_deep(ctx, b->up_stream, format, depth, b->d_wide[k], reinterpret_cast<uint16_t *>(dst), n_px)
-                   : ce_launch_ingest(ctx, b->up_stream, format, b->d_wide[k], dst, n_px);
-    if (rc != CE_OK) return rc;
-    CE_HIP(ctx, hipEventRecord(b->ev_wide[k], b->up_stream));
-    b->wide_busy[k] = true;
-    b->uploads_pending = true;
-    return CE_OK;
-}
-
-int ce_batch_set_reference_fmt(ce_batch *b, uint32_t ref_index, const void *pixels, size_t len, int format)
-{
-    if (!b || !pixels) return CE_ERR_INVALID_ARG;
-    if (ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "ref_index out of range");
-    invalidate_reference_state(b);
-    return upload_fmt(b, b->d_refs + (size_t)ref_index * b->img_bytes, pixels, len, format, b->depth[0]);
-}
-
-// ---- ICC -> sRGB colour tables ----------------------------------------------------------------------------------------
-struct ce_lut {
-    ce_ctx *ctx;
-    uint32_t *d_table;  // [2^24] r | g << 8 | b << 16
-};
-
-int ce_lut_create(ce_ctx *ctx, const uint8_t *table, size_t table_len, ce_lut **out)
-{
-    if (!ctx || !table || !out) return CE_ERR_INVALID_ARG;
-    *out = nullptr;
-    const size_t want = (size_t)3 << 24;
-    if (table_len != want)
-        return fail(ctx, CE_ERR_BAD_LENGTH, "Invalid colour table size: expected " + std::to_string(want) + " bytes, got " + std::to_string(table_len));
-    CE_HIP(ctx, hipSetDevice(ctx->device));
-    uint8_t *d_packed = nullptr;
-    uint32_t *d_table = nullptr;
-    CE_HIP(ctx, hipMalloc(&d_packed, want));
-    if (hipMalloc(&d_table, sizeof(uint32_t) << 24) != hipSuccess) {
-        hipFree(d_packed);
-        return fail(ctx, CE_ERR_BACKEND, "hipMalloc failed (colour table)");
-    }
-    int rc = CE_OK;
-    if (hipMemcpyAsync(d_packed, table, want, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = fail(ctx, CE_ERR_BACKEND, "H2D failed (colour table)");
-    if (rc == CE_OK) rc = ce_launch_lut_expand(ctx, ctx->stream, d_packed, d_table);
-    if (rc == CE_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, CE_ERR_BACKEND, "sync failed (colour table)");
-    hipFree(d_packed);
-    if (rc != CE_OK) {
-        hipFree(d_table);
-        return rc;
-    }
-    *out = new ce_lut{ctx, d_table};
-    return CE_OK;
-}
-
-void ce_lut_destroy(ce_lut *lut)
-{
-    if (!lut) return;
-    hipSetDevice(lut->ctx->device);
-    hipStreamSynchronize(lut->ctx->stream);
-    hipFree(lut->d_table);
-    delete lut;
-}
-
-// the table runs on the batch's upload stream, behind the copy (and the format conversion) of the same image
-static int apply_lut(ce_batch *b, uint8_t *slot, const ce_lut *lut)
-{
-    if (!lut) return CE_OK;
-    if (lut->ctx->device != b->ctx->device) return fail(b->ctx, CE_ERR_INVALID_ARG, "colour table and batch are on different devices");
-    // the table was built on its context's stream and ce_lut_create synchronised: it is complete
-    return ce_launch_lut_apply(b->ctx, b->up_stream, slot, lut->d_table, (size_t)b->w * b->h);
-}
-
-int ce_batch_set_reference_lut(ce_batch *b, uint32_t ref_index, const void *pixels, size_t len, int format, const ce_lut *lut)
-{
-    if (b && lut && b->depth[0]) return fail(b->ctx, CE_ERR_INVALID_ARG, "a colour table is 2^24 8-bit colours: not for a deep batch");
-    if (b && lut && b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, "a colour table is 2^24 8-bit colours: not for a linear batch");
-    if (int rc = ce_batch_set_reference_fmt(b, ref_index, pixels, len, format)) return rc;
-    return apply_lut(b, b->d_refs + (size_t)ref_index * b->img_bytes, lut);
-}
-
-int ce_batch_set_test_lut(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format,
-                          const ce_lut *lut)
-{
-    if (b && lut && b->depth[0]) return fail(b->ctx, CE_ERR_INVALID_ARG, "a colour table is 2^24 8-bit colours: not for a deep batch");
-    if (b && lut && b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, "a colour table is 2^24 8-bit colours: not for a linear batch");
-    if (int rc = ce_batch_set_test_fmt(b, pair_index, ref_index, pixels, len, format)) return rc;
-    return apply_lut(b, b->d_tests + (size_t)pair_index * b->img_bytes, lut);
-}
-
-int ce_batch_bind_pair(ce_batch *b, uint32_t pair_index, uint32_t ref_index)
-{
-    if (!b) return CE_ERR_INVALID_ARG;
-    if (pair_index >= b->max_pairs || ref_index >= b->max_refs)
-        return fail(b->ctx, CE_ERR_INVALID_ARG, "pair/ref index out of range");
-    if (b->h_pair_ref[pair_index] != ref_index) {
-        b->h_pair_ref[pair_index] = ref_index;
-        b->pair_ref_dirty = true;
-        b->pair_ref_version++;  // device-side tables derived from it (pair_ref, XCD work lists) are rebuilt at the next launch
-    }
-    return CE_OK;
-}
-
-int ce_batch_set_test(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const uint8_t *rgb, size_t len)
-{
-    if (!b || !rgb) return CE_ERR_INVALID_ARG;
-    if (b->depth[0]) return ce_batch_set_test_fmt(b, pair_index, ref_index, rgb, len, CE_PIXEL_RGB8);
-    if (b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kLinearWants);
-    if (int rc = ce_batch_bind_pair(b, pair_index, ref_index)) return rc;
-    if (len != b->img_bytes) return bad_length(b->ctx, b->img_bytes, len);
-    return upload(b, b->d_tests + (size_t)pair_index * b->img_bytes, rgb);
-}
-
-int ce_batch_set_test_fmt(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format)
-{
-    if (!b || !pixels) return CE_ERR_INVALID_ARG;
-    if (int rc = ce_batch_bind_pair(b, pair_index, ref_index)) return rc;
-    return upload_fmt(b, b->d_tests + (size_t)pair_index * b->img_bytes, pixels, len, format, b->depth[1]);
-}
-
-void *ce_batch_reference_slab(ce_batch *b)
-{
-    if (!b) return nullptr;
-    invalidate_reference_state(b);  // the caller may overwrite references behind our back
-    return b->d_refs;
-}
-void *ce_batch_test_slab(ce_batch *b) { return b ? b->d_tests : nullptr; }
-
 // the pair -> reference table of the batch on the device, as the last ce_batch_bind_pair left it
 static int sync_pair_ref(ce_batch *b)
 {
@@ -955,17 +597,17 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
 {
     if (!b) return CE_ERR_INVALID_ARG;
     ce_ctx *ctx = b->ctx;
-    if (n_pairs == 0 || n_pairs > b->max_pairs) return fail(ctx, CE_ERR_INVALID_ARG, "n_pairs out of range");
-    if (metric_mask & ~kKnownMetrics) return fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
+    if (n_pairs == 0 || n_pairs > b->max_pairs) return ce_fail(ctx, CE_ERR_INVALID_ARG, "n_pairs out of range");
+    if (metric_mask & ~kKnownMetrics) return ce_fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
     if (b->depth[0] && (flags & CE_FLAG_XYB_ROUNDTRIP))
-        return fail(ctx, CE_ERR_INVALID_ARG, "CE_FLAG_XYB_ROUNDTRIP quantises to 8 bits by definition: not for a deep batch");
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "CE_FLAG_XYB_ROUNDTRIP quantises to 8 bits by definition: not for a deep batch");
     if (b->linear && (flags & CE_FLAG_XYB_ROUNDTRIP))
-        return fail(ctx, CE_ERR_INVALID_ARG, "CE_FLAG_XYB_ROUNDTRIP quantises to 8 bits by definition: not for a linear batch");
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "CE_FLAG_XYB_ROUNDTRIP quantises to 8 bits by definition: not for a linear batch");
     b->ba_map_pairs = b->ds_map_pairs = 0;  // whatever happens below, no readout returns the maps of an earlier launch
     b->s2_map_pairs = b->s2_norm_pairs = 0;
     CE_HIP(ctx, hipSetDevice(ctx->device));
     {
-        int rc = flush_uploads(b);
+        int rc = ce_flush_uploads(b);
         if (rc != CE_OK) return rc;
     }
     if (int rc = sync_pair_ref(b)) return rc;
@@ -1140,9 +782,9 @@ int ce_batch_collect(ce_batch *b, uint32_t n_pairs, ce_scores *out)
 {
     if (!b || !out) return CE_ERR_INVALID_ARG;
     ce_ctx *ctx = b->ctx;
-    if (n_pairs == 0 || n_pairs > b->max_pairs) return fail(ctx, CE_ERR_INVALID_ARG, "n_pairs out of range");
+    if (n_pairs == 0 || n_pairs > b->max_pairs) return ce_fail(ctx, CE_ERR_INVALID_ARG, "n_pairs out of range");
     CE_HIP(ctx, hipSetDevice(ctx->device));
-    if (n_pairs > b->last_n_pairs) return fail(ctx, CE_ERR_INVALID_ARG, "collect asks for more pairs than the last launch ran");
+    if (n_pairs > b->last_n_pairs) return ce_fail(ctx, CE_ERR_INVALID_ARG, "collect asks for more pairs than the last launch ran");
     CE_HIP(ctx, hipEventSynchronize(b->ev_run));  // the launch's kernels and the copy of its scores into h_scores (ce_batch_launch)
     b->run_pending = false;
     leave_flight(b);
@@ -1244,7 +886,7 @@ size_t ce_estimate_batch_bytes(uint32_t w, uint32_t h, uint32_t n_refs, uint32_t
 size_t ce_estimate_batch_bytes_deep(uint32_t w, uint32_t h, uint32_t n_refs, uint32_t n_pairs, uint32_t metric_mask, uint32_t ref_depth,
                                     uint32_t test_depth)
 {
-    if (!deep_depth_ok(ref_depth) || !deep_depth_ok(test_depth)) return 0;
+    if (!ce_deep_depth_ok(ref_depth) || !ce_deep_depth_ok(test_depth)) return 0;
     const size_t slabs = (size_t)3 * w * h * ((size_t)n_refs + n_pairs);
     return ce_estimate_batch_bytes(w, h, n_refs, n_pairs, metric_mask) + slabs + (((size_t)8 << ref_depth) + ((size_t)8 << test_depth));
 }
@@ -1366,9 +1008,9 @@ int ce_eval_batch_lut(ce_ctx *ctx, size_t n, const ce_pair_desc *pairs, const ce
     if (!ctx || (!pairs && n) || (!out && n)) return CE_ERR_INVALID_ARG;
     // the maps live in the pooled batches, which the next call reuses: they are read from a ce_batch or a ce_ref
     if (flags & CE_FLAG_BUTTERAUGLI_DIFFMAP)
-        return fail(ctx, CE_ERR_INVALID_ARG, "CE_FLAG_BUTTERAUGLI_DIFFMAP needs a ce_batch or a ce_ref: the pooled batches keep no maps");
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "CE_FLAG_BUTTERAUGLI_DIFFMAP needs a ce_batch or a ce_ref: the pooled batches keep no maps");
     if (flags & CE_FLAG_SSIMULACRA2_MAPS)
-        return fail(ctx, CE_ERR_INVALID_ARG, "CE_FLAG_SSIMULACRA2_MAPS needs a ce_batch or a ce_ref: the pooled batches keep no maps");
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "CE_FLAG_SSIMULACRA2_MAPS needs a ce_batch or a ce_ref: the pooled batches keep no maps");
     // bucket by shape (Kodak mixes 768x512 and 512x768); invalid items never reach the device
     std::map<std::pair<uint32_t, uint32_t>, std::vector<size_t>> buckets;
     for (size_t i = 0; i < n; i++) {
@@ -1382,12 +1024,12 @@ int ce_eval_batch_lut(ce_ctx *ctx, size_t n, const ce_pair_desc *pairs, const ce
             continue;
         }
         if (test_luts && test_luts[i] && test_luts[i]->ctx->device != ctx->device)
-            return fail(ctx, CE_ERR_INVALID_ARG, "colour table and batch are on different devices");
+            return ce_fail(ctx, CE_ERR_INVALID_ARG, "colour table and batch are on different devices");
         buckets[{d.width, d.height}].push_back(i);
     }
     if (buckets.empty()) return CE_OK;
     // what ce_batch_launch would reject is rejected before anything is uploaded
-    if (metric_mask & ~kKnownMetrics) return fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
+    if (metric_mask & ~kKnownMetrics) return ce_fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
     static const size_t forced_chunks = [] {  // CE_EVAL_BATCH_CHUNKS (1..3) forces the chunk count for A/B runs
         const char *e = std::getenv("CE_EVAL_BATCH_CHUNKS");
         const int v = e ? std::atoi(e) : 0;
@@ -1416,7 +1058,7 @@ int ce_eval_batch_lut(ce_ctx *ctx, size_t n, const ce_pair_desc *pairs, const ce
         ce_batch *b = nullptr;
         if (int r = shape_batch(ctx, w, h, p.max_pairs, p.slot, &b)) return r;
         filling = b;
-        std::vector<upload_job> jobs;
+        std::vector<ce_upload_job> jobs;
         std::vector<size_t> items;
         for (uint32_t s = 0; s < p.refs.size(); s++) {
             jobs.push_back({b->d_refs + (size_t)s * b->img_bytes, pairs[p.refs[s][0]].reference});
@@ -1426,11 +1068,11 @@ int ce_eval_batch_lut(ce_ctx *ctx, size_t n, const ce_pair_desc *pairs, const ce
                 items.push_back(i);
             }
         }
-        invalidate_reference_state(b);
-        if (int r = upload_many(b, jobs)) return r;
+        ce_invalidate_reference_state(b);
+        if (int r = ce_upload_many(b, jobs)) return r;
         if (test_luts)  // ICC -> sRGB of the decoded images, on the upload stream behind their copies (icc.rs:69-103)
             for (size_t k = 0; k < items.size(); k++)
-                if (int r = apply_lut(b, b->d_tests + k * b->img_bytes, test_luts[items[k]])) return r;
+                if (int r = ce_apply_lut(b, b->d_tests + k * b->img_bytes, test_luts[items[k]])) return r;
         if (int r = ce_batch_launch(b, (uint32_t)items.size(), metric_mask, flags, intensity_target)) return r;
         running[c] = {b, std::move(items)};
         return CE_OK;
@@ -1479,18 +1121,18 @@ int ce_eval_pair_deep(ce_ctx *ctx, const uint16_t *reference, size_t reference_l
 {
     if (!ctx || !out || !reference || !test) return CE_ERR_INVALID_ARG;
     *out = ce_scores{};
-    if (!deep_depth_ok(ref_depth) || !deep_depth_ok(test_depth))
-        return out->status = fail(ctx, CE_ERR_INVALID_ARG, "depths must be 8, 10, 12 or 16 bits, got " + std::to_string(ref_depth) + " / " +
+    if (!ce_deep_depth_ok(ref_depth) || !ce_deep_depth_ok(test_depth))
+        return out->status = ce_fail(ctx, CE_ERR_INVALID_ARG, "depths must be 8, 10, 12 or 16 bits, got " + std::to_string(ref_depth) + " / " +
                                                                std::to_string(test_depth));
     if (width == 0 || height == 0) return out->status = CE_ERR_INVALID_ARG;
     if (reference_len != test_len)
-        return out->status = fail(ctx, CE_ERR_DIM_MISMATCH, "Dimension mismatch: reference " + std::to_string(reference_len) +
+        return out->status = ce_fail(ctx, CE_ERR_DIM_MISMATCH, "Dimension mismatch: reference " + std::to_string(reference_len) +
                                                                 " bytes, test " + std::to_string(test_len) + " bytes");
     const size_t want = (size_t)width * height * 6;
-    if (reference_len != want) return out->status = bad_length(ctx, want, reference_len);
+    if (reference_len != want) return out->status = ce_bad_length(ctx, want, reference_len);
     if (flags & (CE_FLAG_BUTTERAUGLI_DIFFMAP | CE_FLAG_SSIMULACRA2_MAPS))
-        return out->status = fail(ctx, CE_ERR_INVALID_ARG, "map flags need a ce_batch: this call's batch does not outlive it");
-    if (metric_mask & ~kKnownMetrics) return out->status = fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
+        return out->status = ce_fail(ctx, CE_ERR_INVALID_ARG, "map flags need a ce_batch: this call's batch does not outlive it");
+    if (metric_mask & ~kKnownMetrics) return out->status = ce_fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
     CE_HIP(ctx, hipSetDevice(ctx->device));
     ce_batch *b = ctx->leaf_deep;
     if (!b || b->w != width || b->h != height || b->depth[0] != ref_depth || b->depth[1] != test_depth) {
@@ -1518,13 +1160,13 @@ int ce_eval_pair_linear(ce_ctx *ctx, const float *reference, size_t reference_le
     *out = ce_scores{};
     if (width == 0 || height == 0) return out->status = CE_ERR_INVALID_ARG;
     if (reference_len != test_len)
-        return out->status = fail(ctx, CE_ERR_DIM_MISMATCH, "Dimension mismatch: reference " + std::to_string(reference_len) +
+        return out->status = ce_fail(ctx, CE_ERR_DIM_MISMATCH, "Dimension mismatch: reference " + std::to_string(reference_len) +
                                                                 " bytes, test " + std::to_string(test_len) + " bytes");
     const size_t want = (size_t)width * height * 12;
-    if (reference_len != want) return out->status = bad_length(ctx, want, reference_len);
+    if (reference_len != want) return out->status = ce_bad_length(ctx, want, reference_len);
     if (flags & (CE_FLAG_BUTTERAUGLI_DIFFMAP | CE_FLAG_SSIMULACRA2_MAPS))
-        return out->status = fail(ctx, CE_ERR_INVALID_ARG, "map flags need a ce_batch: this call's batch does not outlive it");
-    if (metric_mask & ~kKnownMetrics) return out->status = fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
+        return out->status = ce_fail(ctx, CE_ERR_INVALID_ARG, "map flags need a ce_batch: this call's batch does not outlive it");
+    if (metric_mask & ~kKnownMetrics) return out->status = ce_fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
     CE_HIP(ctx, hipSetDevice(ctx->device));
     ce_batch *b = ctx->leaf_linear;
     if (!b || b->w != width || b->h != height) {
@@ -1541,290 +1183,6 @@ int ce_eval_pair_linear(ce_ctx *ctx, const float *reference, size_t reference_le
         return out->status = rc;
     }
     return out->status;
-}
-
-// ---- CICP ingest (cicp.hip) --------------------------------------------------------------------------
-int ce_srgb_table(uint32_t depth, int rule, float *out, size_t n)
-{
-    if (!out || !deep_depth_ok(depth) || (rule != 0 && rule != 1) || n != ((size_t)1 << depth))
-        return fail(nullptr, CE_ERR_INVALID_ARG, "ce_srgb_table: depth 8, 10, 12 or 16, rule 0 or 1, n = 2^depth");
-    if (rule == 0) ce_build_srgb_table_f64(out, (1u << depth) - 1u); else ce_build_srgb_table_powf(out, (1u << depth) - 1u);
-    return CE_OK;
-}
-
-int ce_transfer_table(int transfer, uint32_t depth, float white_nits, float *out, size_t n)
-{
-    if (!out || !deep_depth_ok(depth) || n != ((size_t)1 << depth))
-        return fail(nullptr, CE_ERR_INVALID_ARG, "ce_transfer_table: depth 8, 10, 12 or 16 and n = 2^depth");
-    if (!ce_build_transfer_table(transfer, (1u << depth) - 1u, (double)white_nits, out))
-        return fail(nullptr, CE_ERR_INVALID_ARG, "ce_transfer_table: transfer 13 (sRGB), 8 (linear) or 16 (PQ, white_nits > 0)");
-    return CE_OK;
-}
-
-int ce_colour_matrix(int primaries, float out[9])
-{
-    if (!out || !ce_build_colour_matrix(primaries, out))
-        return fail(nullptr, CE_ERR_INVALID_ARG, "ce_colour_matrix: primaries 1 (BT.709), 9 (BT.2020) or 12 (Display P3)");
-    return CE_OK;
-}
-
-namespace {
-// what one CICP ingest runs with: the device table of (transfer, depth, white_nits) and the matrix (has_matrix: primaries != 1);
-// an HLG ingest (hlg_colour_check) runs with the same and with ce_hlg_params' five doubles
-struct cicp_plan {
-    const float *d_table;
-    uint32_t maxv;
-    bool has_matrix;
-    float m[9];
-    bool hlg = false;
-    double hlg_params[5];
-};
-
-// the colour description alone: depth, transfer and primaries from the lists of the header; fills maxv and the matrix
-int cicp_colour_check(ce_ctx *ctx, const ce_colour *c, cicp_plan *plan)
-{
-    if (!deep_depth_ok(c->depth)) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: depth must be 8, 10, 12 or 16, got " + std::to_string(c->depth));
-    if (c->transfer != 13 && c->transfer != 8 && c->transfer != 16)
-        return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: transfer must be 13 (sRGB), 8 (linear) or 16 (PQ), got " + std::to_string(c->transfer) +
-                                                 (c->transfer == 18 ? " (HLG carries a display description: ce_batch_set_*_hlg)" : ""));
-    if (c->transfer == 16 && !(c->white_nits > 0.0f && std::isfinite(c->white_nits)))
-        return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: PQ needs white_nits > 0");
-    if (!ce_build_colour_matrix(c->primaries, plan->m))
-        return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: primaries must be 1 (BT.709), 9 (BT.2020) or 12 (Display P3), got " + std::to_string(c->primaries));
-    plan->has_matrix = c->primaries != 1;
-    plan->maxv = (1u << c->depth) - 1u;
-    plan->d_table = nullptr;
-    return CE_OK;
-}
-
-// the table of a checked description on the device, built once per context and (transfer, depth, white) and kept; white
-// only matters to PQ
-int cicp_table(ce_ctx *ctx, const ce_colour *c, cicp_plan *plan)
-{
-    const float white = c->transfer == 16 ? c->white_nits : 0.0f;
-    uint32_t white_bits;
-    std::memcpy(&white_bits, &white, 4);
-    const auto key = std::make_tuple(c->transfer, c->depth, white_bits);
-    auto it = ctx->cicp_tables.find(key);
-    if (it == ctx->cicp_tables.end()) {
-        std::vector<float> host((size_t)plan->maxv + 1);
-        ce_build_transfer_table(c->transfer, plan->maxv, (double)white, host.data());
-        CE_HIP(ctx, hipSetDevice(ctx->device));
-        float *d = nullptr;
-        CE_HIP(ctx, hipMalloc(&d, host.size() * sizeof(float)));
-        if (hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            hipFree(d);
-            return fail(ctx, CE_ERR_BACKEND, "H2D failed (transfer table)");
-        }
-        it = ctx->cicp_tables.emplace(key, d).first;
-    }
-    plan->d_table = it->second;
-    return CE_OK;
-}
-
-int cicp_check(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_colour *c, size_t n_px, cicp_plan *plan)
-{
-    if (!pixels || !c) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: null pointer");
-    const bool fmt8 = format == CE_PIXEL_RGB8 || format == CE_PIXEL_RGBA8, fmt16 = format == CE_PIXEL_RGB16 || format == CE_PIXEL_RGBA16;
-    if (!fmt8 && !fmt16) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: format must be CE_PIXEL_RGB8, RGBA8, RGB16 or RGBA16");
-    if (fmt8 && deep_depth_ok(c->depth) && c->depth != 8)
-        return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: an 8-bit format needs depth 8, got " + std::to_string(c->depth));
-    if (int rc = cicp_colour_check(ctx, c, plan)) return rc;
-    if (len != n_px * ce_pixel_bytes(format)) return bad_length(ctx, n_px * ce_pixel_bytes(format), len);
-    return cicp_table(ctx, c, plan);
-}
-
-// the conversion of one checked image of code values at d_src into d_dst: the CICP pixel, or with plan.hlg the HLG pixel
-int launch_cicp_into(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, float *d_dst, size_t n_px, const cicp_plan &plan)
-{
-    const float *m = plan.has_matrix ? plan.m : nullptr;
-    if (plan.hlg) return ce_launch_hlg(ctx, stream, format, d_src, d_dst, n_px, plan.d_table, plan.maxv, m, plan.hlg_params);
-    return ce_launch_cicp(ctx, stream, format, d_src, d_dst, n_px, plan.d_table, plan.maxv, m);
-}
-
-// one tagged image through the wide staging pair of upload_fmt into the slot at dst, on the batch's upload stream
-int upload_cicp(ce_batch *b, uint8_t *dst, const void *pixels, size_t len, int format, const cicp_plan &plan)
-{
-    ce_ctx *ctx = b->ctx;
-    CE_HIP(ctx, hipSetDevice(ctx->device));
-    const int k = b->next_wide;
-    b->next_wide ^= 1;
-    if (int rc = wide_stage(b, k, pixels, len)) return rc;
-    if (int rc = launch_cicp_into(ctx, b->up_stream, format, b->d_wide[k], reinterpret_cast<float *>(dst), (size_t)b->w * b->h, plan)) return rc;
-    CE_HIP(ctx, hipEventRecord(b->ev_wide[k], b->up_stream));
-    b->wide_busy[k] = true;
-    b->uploads_pending = true;
-    return CE_OK;
-}
-}  // namespace
-
-int ce_batch_set_reference_cicp(ce_batch *b, uint32_t ref_index, const void *pixels, size_t len, int format, const ce_colour *c)
-{
-    if (!b) return CE_ERR_INVALID_ARG;
-    if (!b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, "CICP ingest writes linear light: it needs a linear batch (ce_batch_create_linear)");
-    if (ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "ref_index out of range");
-    cicp_plan plan;
-    if (int rc = cicp_check(b->ctx, pixels, len, format, c, (size_t)b->w * b->h, &plan)) return rc;
-    invalidate_reference_state(b);
-    return upload_cicp(b, b->d_refs + (size_t)ref_index * b->img_bytes, pixels, len, format, plan);
-}
-
-int ce_batch_set_test_cicp(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format,
-                           const ce_colour *c)
-{
-    if (!b) return CE_ERR_INVALID_ARG;
-    if (!b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, "CICP ingest writes linear light: it needs a linear batch (ce_batch_create_linear)");
-    if (pair_index >= b->max_pairs || ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "pair/ref index out of range");
-    cicp_plan plan;
-    if (int rc = cicp_check(b->ctx, pixels, len, format, c, (size_t)b->w * b->h, &plan)) return rc;
-    if (int rc = ce_batch_bind_pair(b, pair_index, ref_index)) return rc;
-    return upload_cicp(b, b->d_tests + (size_t)pair_index * b->img_bytes, pixels, len, format, plan);
-}
-
-// one checked image of code values -> packed f32 RGB in host memory, on the context's stream
-static int cicp_to_host(ce_ctx *ctx, const void *pixels, size_t len, int format, const cicp_plan &plan, size_t n_px, float *out)
-{
-    CE_HIP(ctx, hipSetDevice(ctx->device));
-    void *d_in = nullptr;
-    float *d_out = nullptr;
-    CE_HIP(ctx, hipMalloc(&d_in, len));
-    if (hipMalloc(&d_out, n_px * 12) != hipSuccess) {
-        hipFree(d_in);
-        return fail(ctx, CE_ERR_BACKEND, "hipMalloc failed (CICP ingest)");
-    }
-    int rc = CE_OK;
-    if (hipMemcpyAsync(d_in, pixels, len, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = fail(ctx, CE_ERR_BACKEND, "H2D failed (CICP ingest)");
-    if (rc == CE_OK) rc = launch_cicp_into(ctx, ctx->stream, format, d_in, d_out, n_px, plan);
-    if (rc == CE_OK && hipMemcpyAsync(out, d_out, n_px * 12, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, CE_ERR_BACKEND, "D2H failed (CICP ingest)");
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == CE_OK) rc = fail(ctx, CE_ERR_BACKEND, "sync failed (CICP ingest)");
-    hipFree(d_in);
-    hipFree(d_out);
-    return rc;
-}
-
-int ce_cicp_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_colour *c, uint32_t w, uint32_t h, float *out,
-                      size_t out_len)
-{
-    if (!ctx || !out) return CE_ERR_INVALID_ARG;
-    if (w == 0 || h == 0) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: empty image");
-    const size_t n_px = (size_t)w * h;
-    cicp_plan plan;
-    if (int rc = cicp_check(ctx, pixels, len, format, c, n_px, &plan)) return rc;
-    if (out_len != n_px * 3) return fail(ctx, CE_ERR_BAD_LENGTH, "CICP ingest: out_len must be " + std::to_string(n_px * 3) + " floats, got " + std::to_string(out_len));
-    return cicp_to_host(ctx, pixels, len, format, plan, n_px, out);
-}
-
-// ---- HLG ingest (hlg.hip) ------------------------------------------------------------------------
-int ce_hlg_table(uint32_t depth, float *out, size_t n)
-{
-    if (!out || !deep_depth_ok(depth) || n != ((size_t)1 << depth))
-        return fail(nullptr, CE_ERR_INVALID_ARG, "ce_hlg_table: depth 8, 10, 12 or 16 and n = 2^depth");
-    ce_build_hlg_table((1u << depth) - 1u, out);
-    return CE_OK;
-}
-
-// the description alone: primaries and depth from the header's lists, the two luminances finite and > 0, the system gamma
-// - given, or BT.2100's rule from the peak - in [0.8, 1.6]; out = {kR, kG, kB, gamma - 1, A}
-static int hlg_describe(ce_ctx *ctx, const ce_hlg *h, double out[5])
-{
-    if (!deep_depth_ok(h->depth)) return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: depth must be 8, 10, 12 or 16, got " + std::to_string(h->depth));
-    if (!ce_build_luminance_row(h->primaries, out))
-        return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: primaries must be 1 (BT.709), 9 (BT.2020) or 12 (Display P3), got " + std::to_string(h->primaries));
-    if (!(h->peak_nits > 0.0f && std::isfinite(h->peak_nits))) return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: peak_nits must be finite and > 0");
-    if (!(h->white_nits > 0.0f && std::isfinite(h->white_nits))) return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: white_nits must be finite and > 0");
-    const double gamma = h->system_gamma != 0.0f ? (double)h->system_gamma : 1.2 + 0.42 * std::log10((double)h->peak_nits / 1000.0);
-    if (!(gamma >= 0.8 && gamma <= 1.6))
-        return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: the system gamma must lie in [0.8, 1.6], got " + std::to_string(gamma));
-    out[3] = gamma - 1.0;
-    out[4] = (double)h->peak_nits / (double)h->white_nits;
-    return CE_OK;
-}
-
-int ce_hlg_params(const ce_hlg *h, double out[5])
-{
-    if (!h || !out) return fail(nullptr, CE_ERR_INVALID_ARG, "ce_hlg_params: null pointer");
-    return hlg_describe(nullptr, h, out);
-}
-
-// a checked description as an ingest's plan: maxv, the primaries matrix and the five doubles
-static int hlg_colour_check(ce_ctx *ctx, const ce_hlg *h, cicp_plan *plan)
-{
-    if (int rc = hlg_describe(ctx, h, plan->hlg_params)) return rc;
-    ce_build_colour_matrix(h->primaries, plan->m);
-    plan->hlg = true;
-    plan->has_matrix = h->primaries != 1;
-    plan->maxv = (1u << h->depth) - 1u;
-    plan->d_table = nullptr;
-    return CE_OK;
-}
-
-// the inverse-OETF table of a checked description on the device, one per context and depth, kept next to the CICP tables
-static int hlg_table_dev(ce_ctx *ctx, const ce_hlg *h, cicp_plan *plan)
-{
-    const auto key = std::make_tuple(18, h->depth, 0u);
-    auto it = ctx->cicp_tables.find(key);
-    if (it == ctx->cicp_tables.end()) {
-        std::vector<float> host((size_t)plan->maxv + 1);
-        ce_build_hlg_table(plan->maxv, host.data());
-        CE_HIP(ctx, hipSetDevice(ctx->device));
-        float *d = nullptr;
-        CE_HIP(ctx, hipMalloc(&d, host.size() * sizeof(float)));
-        if (hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            hipFree(d);
-            return fail(ctx, CE_ERR_BACKEND, "H2D failed (HLG table)");
-        }
-        it = ctx->cicp_tables.emplace(key, d).first;
-    }
-    plan->d_table = it->second;
-    return CE_OK;
-}
-
-static int hlg_check(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_hlg *h, size_t n_px, cicp_plan *plan)
-{
-    if (!pixels || !h) return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: null pointer");
-    const bool fmt8 = format == CE_PIXEL_RGB8 || format == CE_PIXEL_RGBA8, fmt16 = format == CE_PIXEL_RGB16 || format == CE_PIXEL_RGBA16;
-    if (!fmt8 && !fmt16) return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: format must be CE_PIXEL_RGB8, RGBA8, RGB16 or RGBA16");
-    if (fmt8 && deep_depth_ok(h->depth) && h->depth != 8)
-        return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: an 8-bit format needs depth 8, got " + std::to_string(h->depth));
-    if (int rc = hlg_colour_check(ctx, h, plan)) return rc;
-    if (len != n_px * ce_pixel_bytes(format)) return bad_length(ctx, n_px * ce_pixel_bytes(format), len);
-    return hlg_table_dev(ctx, h, plan);
-}
-
-static const char *const kHlgWantsLinear = "HLG ingest writes linear light: it needs a linear batch (ce_batch_create_linear)";
-
-int ce_batch_set_reference_hlg(ce_batch *b, uint32_t ref_index, const void *pixels, size_t len, int format, const ce_hlg *h)
-{
-    if (!b) return CE_ERR_INVALID_ARG;
-    if (!b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kHlgWantsLinear);
-    if (ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "ref_index out of range");
-    cicp_plan plan;
-    if (int rc = hlg_check(b->ctx, pixels, len, format, h, (size_t)b->w * b->h, &plan)) return rc;
-    invalidate_reference_state(b);
-    return upload_cicp(b, b->d_refs + (size_t)ref_index * b->img_bytes, pixels, len, format, plan);
-}
-
-int ce_batch_set_test_hlg(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format, const ce_hlg *h)
-{
-    if (!b) return CE_ERR_INVALID_ARG;
-    if (!b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kHlgWantsLinear);
-    if (pair_index >= b->max_pairs || ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "pair/ref index out of range");
-    cicp_plan plan;
-    if (int rc = hlg_check(b->ctx, pixels, len, format, h, (size_t)b->w * b->h, &plan)) return rc;
-    if (int rc = ce_batch_bind_pair(b, pair_index, ref_index)) return rc;
-    return upload_cicp(b, b->d_tests + (size_t)pair_index * b->img_bytes, pixels, len, format, plan);
-}
-
-int ce_hlg_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_hlg *h, uint32_t w, uint32_t height, float *out,
-                     size_t out_len)
-{
-    if (!ctx || !out) return CE_ERR_INVALID_ARG;
-    if (w == 0 || height == 0) return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: empty image");
-    const size_t n_px = (size_t)w * height;
-    cicp_plan plan;
-    if (int rc = hlg_check(ctx, pixels, len, format, h, n_px, &plan)) return rc;
-    if (out_len != n_px * 3) return fail(ctx, CE_ERR_BAD_LENGTH, "HLG ingest: out_len must be " + std::to_string(n_px * 3) + " floats, got " + std::to_string(out_len));
-    return cicp_to_host(ctx, pixels, len, format, plan, n_px, out);
 }
 
 static int leaf(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test, size_t test_len,
@@ -1898,8 +1256,8 @@ int ce_calculate_butteraugli_diffmap(ce_ctx *ctx, const uint8_t *reference, size
 {
     if (!ctx || !reference || !test || !score || !diffmap_out) return CE_ERR_INVALID_ARG;
     if (int rc = validate_pair(ctx, reference_len, test_len, width, height)) return rc;
-    if (width < 8 || height < 8) return fail(ctx, CE_ERR_TOO_SMALL, "minimum 8x8 for butteraugli");  // src/eval/helpers.rs:89
-    if (width > UINT32_MAX || height > UINT32_MAX) return fail(ctx, CE_ERR_INVALID_ARG, "image too large");
+    if (width < 8 || height < 8) return ce_fail(ctx, CE_ERR_TOO_SMALL, "minimum 8x8 for butteraugli");  // src/eval/helpers.rs:89
+    if (width > UINT32_MAX || height > UINT32_MAX) return ce_fail(ctx, CE_ERR_INVALID_ARG, "image too large");
     ce_scores s{};
     ce_batch *b = nullptr;
     if (int rc = leaf_map_run(ctx, reference, reference_len, test, test_len, width, height, CE_METRIC_BUTTERAUGLI,
@@ -1914,15 +1272,15 @@ int ce_calculate_dssim_ssim_maps(ce_ctx *ctx, const uint8_t *reference, size_t r
                                  size_t width, size_t height, double *dssim, double *level_ssim, float *maps, size_t maps_floats)
 {
     if (!ctx || !reference || !test || !dssim || !level_ssim || !maps) return CE_ERR_INVALID_ARG;
-    if (width == 0 || height == 0) return fail(ctx, CE_ERR_INVALID_ARG, "empty image");  // ce_calculate_dssim's order
+    if (width == 0 || height == 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, "empty image");  // ce_calculate_dssim's order
     if (int rc = validate_pair(ctx, reference_len, test_len, width, height)) return rc;
-    if (width > UINT32_MAX || height > UINT32_MAX) return fail(ctx, CE_ERR_INVALID_ARG, "image too large");
+    if (width > UINT32_MAX || height > UINT32_MAX) return ce_fail(ctx, CE_ERR_INVALID_ARG, "image too large");
     uint32_t lw[CE_DSSIM_MAX_LEVELS], lh[CE_DSSIM_MAX_LEVELS];
     const uint32_t n = ce_plan_dssim_levels((uint32_t)width, (uint32_t)height, CE_DSSIM_MAX_LEVELS, lw, lh);
     size_t want = 0;
     for (uint32_t l = 0; l < n; l++) want += (size_t)lw[l] * lh[l];
     if (maps_floats != want)
-        return fail(ctx, CE_ERR_INVALID_ARG, "SSIM maps of every level need " + std::to_string(want) + " floats, got " + std::to_string(maps_floats));
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "SSIM maps of every level need " + std::to_string(want) + " floats, got " + std::to_string(maps_floats));
     ce_scores s{};
     ce_batch *b = nullptr;
     if (int rc = leaf_map_run(ctx, reference, reference_len, test, test_len, width, height, CE_METRIC_DSSIM, 0, 0.0f, &s, &b))
@@ -1942,16 +1300,16 @@ int ce_calculate_ssimulacra2_maps(ce_ctx *ctx, const uint8_t *reference, size_t 
                                   size_t width, size_t height, double *score, double *features, float *maps, size_t maps_floats)
 {
     if (!ctx || !reference || !test || !score || !features || !maps) return CE_ERR_INVALID_ARG;
-    if (width == 0 || height == 0) return fail(ctx, CE_ERR_INVALID_ARG, "empty image");  // ce_calculate_ssimulacra2's order
+    if (width == 0 || height == 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, "empty image");  // ce_calculate_ssimulacra2's order
     if (int rc = validate_pair(ctx, reference_len, test_len, width, height)) return rc;
-    if (width > UINT32_MAX || height > UINT32_MAX) return fail(ctx, CE_ERR_INVALID_ARG, "image too large");
-    if (width < 8 || height < 8) return fail(ctx, CE_ERR_TOO_SMALL, "minimum 8x8 for ssimulacra2");
+    if (width > UINT32_MAX || height > UINT32_MAX) return ce_fail(ctx, CE_ERR_INVALID_ARG, "image too large");
+    if (width < 8 || height < 8) return ce_fail(ctx, CE_ERR_TOO_SMALL, "minimum 8x8 for ssimulacra2");
     uint32_t sw[CE_SSIM2_MAX_SCALES], sh[CE_SSIM2_MAX_SCALES];
     const uint32_t n = ce_plan_ssim2_scales((uint32_t)width, (uint32_t)height, CE_SSIM2_MAX_SCALES, sw, sh);
     size_t want = 0;
     for (uint32_t s = 0; s < n; s++) want += 9 * (size_t)sw[s] * sh[s];
     if (maps_floats != want)
-        return fail(ctx, CE_ERR_INVALID_ARG, "SSIMULACRA2 maps of every scale need " + std::to_string(want) + " floats, got " + std::to_string(maps_floats));
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "SSIMULACRA2 maps of every scale need " + std::to_string(want) + " floats, got " + std::to_string(maps_floats));
     ce_scores s{};
     ce_batch *b = nullptr;
     if (int rc = leaf_map_run(ctx, reference, reference_len, test, test_len, width, height, CE_METRIC_SSIMULACRA2,
@@ -1973,49 +1331,13 @@ int ce_calculate_ssimulacra2_maps(ce_ctx *ctx, const uint8_t *reference, size_t 
     return CE_OK;
 }
 
-// leaf scratch (ce_internal.h): device buffers of at least in_bytes / out_bytes and a pinned staging buffer of the larger
-static int leaf_scratch(ce_ctx *ctx, size_t in_bytes, size_t out_bytes)
-{
-    CE_HIP(ctx, hipSetDevice(ctx->device));
-    auto grow = [&](uint8_t *&p, size_t &cap, size_t want, bool host) -> int {
-        if (cap >= want) return CE_OK;
-        if (p) CE_HIP(ctx, host ? hipHostFree(p) : hipFree(p));
-        p = nullptr;
-        cap = 0;
-        const size_t sz = want + want / 4;  // a little head room: a sweep over nearby shapes does not reallocate each time
-        CE_HIP(ctx, host ? hipHostMalloc((void **)&p, sz, hipHostMallocDefault) : hipMalloc((void **)&p, sz));
-        cap = sz;
-        return CE_OK;
-    };
-    int rc = grow(ctx->leaf_d_in, ctx->leaf_in_cap, in_bytes, false);
-    if (rc == CE_OK) rc = grow(ctx->leaf_d_out, ctx->leaf_out_cap, out_bytes, false);
-    if (rc == CE_OK) rc = grow(ctx->leaf_h, ctx->leaf_h_cap, std::max(in_bytes, out_bytes), true);
-    return rc;
-}
-
-// host image in -> kernel -> host image out through the leaf scratch, everything on the context's stream
-static int leaf_roundtrip(ce_ctx *ctx, const void *in, size_t in_bytes, void *out, size_t out_bytes,
-                          const std::function<int(uint8_t *, uint8_t *)> &launch)
-{
-    int rc = leaf_scratch(ctx, in_bytes, out_bytes);
-    if (rc != CE_OK) return rc;
-    std::memcpy(ctx->leaf_h, in, in_bytes);
-    CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_d_in, ctx->leaf_h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = launch(ctx->leaf_d_in, ctx->leaf_d_out);
-    if (rc != CE_OK) return rc;
-    CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_h, ctx->leaf_d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::memcpy(out, ctx->leaf_h, out_bytes);
-    return CE_OK;
-}
-
 int ce_xyb_roundtrip(ce_ctx *ctx, const uint8_t *rgb, size_t rgb_len, size_t width, size_t height, uint8_t *out)
 {
     if (!ctx || !rgb || !out) return CE_ERR_INVALID_ARG;
     if (rgb_len != width * height * 3)
-        return fail(ctx, CE_ERR_BAD_LENGTH, "Buffer size mismatch");  // xyb.rs:227
+        return ce_fail(ctx, CE_ERR_BAD_LENGTH, "Buffer size mismatch");  // xyb.rs:227
     if (rgb_len == 0) return CE_OK;
-    return leaf_roundtrip(ctx, rgb, rgb_len, out, rgb_len,
+    return ce_leaf_roundtrip(ctx, rgb, rgb_len, out, rgb_len,
                           [&](uint8_t *d_in, uint8_t *d_out) { return ce_launch_xyb_roundtrip(ctx, d_in, d_out, width * height); });
 }
 
@@ -2023,10 +1345,10 @@ int ce_rgb8_to_dssim_image(ce_ctx *ctx, const uint8_t *rgb, size_t rgb_len, size
                            float *rgba_out)
 {
     if (!ctx || !rgb || !rgba_out) return CE_ERR_INVALID_ARG;
-    if (rgb_len != width * height * 3) return fail(ctx, CE_ERR_BAD_LENGTH, "Buffer size mismatch");
+    if (rgb_len != width * height * 3) return ce_fail(ctx, CE_ERR_BAD_LENGTH, "Buffer size mismatch");
     const size_t n = width * height;
     if (n == 0) return CE_OK;
-    return leaf_roundtrip(ctx, rgb, rgb_len, rgba_out, n * 4 * sizeof(float), [&](uint8_t *d_in, uint8_t *d_out) {
+    return ce_leaf_roundtrip(ctx, rgb, rgb_len, rgba_out, n * 4 * sizeof(float), [&](uint8_t *d_in, uint8_t *d_out) {
         return ce_launch_rgb8_to_dssim_image(ctx, d_in, reinterpret_cast<float *>(d_out), n);
     });
 }
@@ -2037,16 +1359,16 @@ int ce_image_heuristics_rgb8(ce_ctx *ctx, const uint8_t *rgb, size_t len, size_t
 {
     if (!ctx || !rgb || !out) return CE_ERR_INVALID_ARG;
     if (width > UINT32_MAX || height > UINT32_MAX || (height && width > SIZE_MAX / 3 / height))
-        return fail(ctx, CE_ERR_INVALID_ARG, "image heuristics: image dimensions out of range");
-    if (len != width * height * 3) return bad_length(ctx, width * height * 3, len);
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "image heuristics: image dimensions out of range");
+    if (len != width * height * 3) return ce_bad_length(ctx, width * height * 3, len);
     if (width < 3 || height < 3)
-        return fail(ctx, CE_ERR_TOO_SMALL, "image heuristics need at least 3 x 3 pixels, got " + std::to_string(width) + " x " +
+        return ce_fail(ctx, CE_ERR_TOO_SMALL, "image heuristics need at least 3 x 3 pixels, got " + std::to_string(width) + " x " +
                                                std::to_string(height));
-    int rc = leaf_scratch(ctx, len, 0);
+    int rc = ce_leaf_scratch(ctx, len, 0);
     if (rc != CE_OK) return rc;
     std::memcpy(ctx->leaf_h, rgb, len);
     const hipError_t e = hipMemcpyAsync(ctx->leaf_d_in, ctx->leaf_h, len, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return fail(ctx, CE_ERR_BACKEND, std::string("image heuristics upload: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return ce_fail(ctx, CE_ERR_BACKEND, std::string("image heuristics upload: ") + hipGetErrorString(e));
     return ce_image_heuristics_run(ctx, ctx->leaf_d_in, len, (uint32_t)width, (uint32_t)height, 1, out);
 }
 
@@ -2054,322 +1376,24 @@ int ce_batch_image_heuristics(ce_batch *b, uint32_t which, uint32_t first, uint3
 {
     if (!b || !out) return CE_ERR_INVALID_ARG;
     ce_ctx *ctx = b->ctx;
-    if (b->depth[0]) return fail(ctx, CE_ERR_INVALID_ARG, "image heuristics are defined on u8 gray levels: not for a deep batch");
-    if (b->linear) return fail(ctx, CE_ERR_INVALID_ARG, "image heuristics are defined on u8 gray levels: not for a linear batch");
+    if (b->depth[0]) return ce_fail(ctx, CE_ERR_INVALID_ARG, "image heuristics are defined on u8 gray levels: not for a deep batch");
+    if (b->linear) return ce_fail(ctx, CE_ERR_INVALID_ARG, "image heuristics are defined on u8 gray levels: not for a linear batch");
     if (which != CE_BATCH_REFERENCES && which != CE_BATCH_TESTS)
-        return fail(ctx, CE_ERR_INVALID_ARG, "image heuristics: unknown slab " + std::to_string(which));
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "image heuristics: unknown slab " + std::to_string(which));
     const uint32_t slots = which == CE_BATCH_TESTS ? b->max_pairs : b->max_refs;
     if (count == 0 || first > slots || count > slots - first)
-        return fail(ctx, CE_ERR_INVALID_ARG, "image heuristics: images [" + std::to_string(first) + ", " +
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "image heuristics: images [" + std::to_string(first) + ", " +
                                                  std::to_string((uint64_t)first + count) + ") outside the " + std::to_string(slots) +
                                                  " slots");
     if (b->w < 3 || b->h < 3)
-        return fail(ctx, CE_ERR_TOO_SMALL, "image heuristics need at least 3 x 3 pixels, got " + std::to_string(b->w) + " x " +
+        return ce_fail(ctx, CE_ERR_TOO_SMALL, "image heuristics need at least 3 x 3 pixels, got " + std::to_string(b->w) + " x " +
                                                std::to_string(b->h));
     CE_HIP(ctx, hipSetDevice(ctx->device));
     // the kernels run on the context's stream: behind the inline route's copies already, behind the upload stream's
-    // copies, conversions and colour tables from here (the ordering of a launch, order_write)
-    if (int rc = flush_uploads(b)) return rc;
+    // copies, conversions and colour tables from here (the ordering of a launch, ce_order_write)
+    if (int rc = ce_flush_uploads(b)) return rc;
     const uint8_t *slab = which == CE_BATCH_TESTS ? b->d_tests : b->d_refs;
     return ce_image_heuristics_run(ctx, slab + (size_t)first * b->img_bytes, b->img_bytes, b->w, b->h, count, out);
-}
-
-// ---- planar Y'CbCr ingest (yuv.hip) --------------------------------------------------------------
-
-// a checked ce_yuv_image: what the kernel reads, and each plane's rows for the host copy
-struct yuv_plan {
-    ce_yuv_dev dev{};
-    int n_planes = 0;
-    size_t rows[3] = {}, row_bytes[3] = {};
-    size_t offset[3] = {}, total = 0;  // the planes packed without pitch padding, each at an even offset
-};
-
-static int yuv_check(ce_ctx *ctx, const ce_yuv_image *img, uint32_t w, uint32_t h, uint32_t depth_out, yuv_plan *plan)
-{
-    if (!img) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: null image");
-    if (img->subsampling < CE_YUV_444 || img->subsampling > CE_YUV_400)
-        return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: unknown subsampling " + std::to_string(img->subsampling));
-    if (img->layout != CE_YUV_PLANAR && img->layout != CE_YUV_SEMIPLANAR)
-        return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: unknown layout " + std::to_string(img->layout));
-    if (img->upsample != CE_CHROMA_NEAREST && img->upsample != CE_CHROMA_TRIANGLE)
-        return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: unknown chroma upsampling " + std::to_string(img->upsample));
-    if (img->memory != CE_MEM_HOST && img->memory != CE_MEM_DEVICE)
-        return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: unknown memory kind " + std::to_string(img->memory));
-    if (img->depth != 8 && img->depth != 10 && img->depth != 12)
-        return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: depth must be 8, 10 or 12 bits, got " + std::to_string(img->depth));
-    if (img->msb_aligned && img->depth == 8) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: msb_aligned is for u16 samples, not depth 8");
-    if (img->lut) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: a colour table is 2^24 RGB colours and is not offered for YUV");
-    ce_yuv_dev &d = plan->dev;
-    if (ce_yuv_coefficients(img->matrix, img->range, (uint32_t)img->depth, depth_out, d.k) != CE_OK)
-        return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: unknown matrix " + std::to_string(img->matrix) + " or range " + std::to_string(img->range));
-    const size_t bps = img->depth == 8 ? 1 : 2;
-    const size_t cw = img->subsampling == CE_YUV_444 ? w : ((size_t)w + 1) / 2, ch = img->subsampling == CE_YUV_420 ? ((size_t)h + 1) / 2 : h;
-    const bool semi = img->layout == CE_YUV_SEMIPLANAR;
-    plan->n_planes = img->subsampling == CE_YUV_400 ? 1 : semi ? 2 : 3;
-    for (int p = 0; p < plan->n_planes; p++) {
-        plan->rows[p] = p == 0 ? h : ch;
-        plan->row_bytes[p] = (p == 0 ? (size_t)w : semi ? 2 * cw : cw) * bps;
-        if (!img->plane[p]) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: plane " + std::to_string(p) + " is missing");
-        if (img->pitch[p] < plan->row_bytes[p])
-            return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: pitch " + std::to_string(img->pitch[p]) + " of plane " + std::to_string(p) +
-                                                     " is under its row's " + std::to_string(plan->row_bytes[p]) + " bytes");
-        if (bps == 2 && ((reinterpret_cast<uintptr_t>(img->plane[p]) | img->pitch[p]) & 1))
-            return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: the pointer and pitch of u16 plane " + std::to_string(p) + " must be 2-byte aligned");
-        plan->offset[p] = plan->total;
-        plan->total += (plan->rows[p] * plan->row_bytes[p] + 1) & ~(size_t)1;
-        d.plane[p] = static_cast<const uint8_t *>(img->plane[p]);
-        d.pitch[p] = img->pitch[p];
-    }
-    d.subsampling = img->subsampling, d.layout = img->layout, d.upsample = img->upsample;
-    d.depth = (uint32_t)img->depth;
-    d.shift = img->msb_aligned ? 16u - (uint32_t)img->depth : 0u;
-    return CE_OK;
-}
-
-// host planes -> `h_stage` without their pitch padding; the device copy at d_stage is what the kernel then reads
-static void yuv_pack(const ce_yuv_image *img, yuv_plan *plan, uint8_t *h_stage, const uint8_t *d_stage)
-{
-    for (int p = 0; p < plan->n_planes; p++) {
-        const uint8_t *src = static_cast<const uint8_t *>(img->plane[p]);
-        uint8_t *dst = h_stage + plan->offset[p];
-        for (size_t r = 0; r < plan->rows[p]; r++) std::memcpy(dst + r * plan->row_bytes[p], src + r * img->pitch[p], plan->row_bytes[p]);
-        plan->dev.plane[p] = d_stage + plan->offset[p];
-        plan->dev.pitch[p] = plan->row_bytes[p];
-    }
-}
-
-// the conversion of one checked image into dst: integer RGB (u8, or u16 of `depth`), or with `lin` the fused linear-light
-// ingest of a linear batch (yuv_cicp.hip; yuv_hlg.hip for an HLG plan), whose integer grid is the one plan.dev.k was built for
-static int launch_yuv_into(ce_ctx *ctx, hipStream_t stream, const yuv_plan &plan, uint32_t w, uint32_t h, uint8_t *dst, uint32_t depth,
-                           const cicp_plan *lin)
-{
-    if (lin && lin->hlg)
-        return ce_launch_yuv_hlg(ctx, stream, plan.dev, w, h, reinterpret_cast<float *>(dst), lin->d_table, lin->maxv, lin->has_matrix ? lin->m : nullptr,
-                                 lin->hlg_params);
-    if (lin)
-        return ce_launch_yuv_cicp(ctx, stream, plan.dev, w, h, reinterpret_cast<float *>(dst), lin->d_table, lin->maxv, lin->has_matrix ? lin->m : nullptr);
-    return ce_launch_yuv(ctx, stream, plan.dev, w, h, dst, depth != 0, depth ? depth : 8);
-}
-
-// one Y'CbCr image into a slab slot on the batch's upload stream: device planes are read in place, host planes go
-// through the wide staging pair of upload_fmt (8 bytes per pixel, 12 on a linear batch: the packed planes are at most 6 and
-// a few bytes)
-static int upload_yuv(ce_batch *b, uint8_t *dst, const ce_yuv_image *img, yuv_plan &plan, uint32_t depth, const cicp_plan *lin = nullptr)
-{
-    ce_ctx *ctx = b->ctx;
-    const size_t n_px = (size_t)b->w * b->h;
-    CE_HIP(ctx, hipSetDevice(ctx->device));
-    if (img->memory == CE_MEM_DEVICE) {
-        if (int rc = order_write(b, false)) return rc;
-        if (int rc = launch_yuv_into(ctx, b->up_stream, plan, b->w, b->h, dst, depth, lin)) return rc;
-        b->uploads_pending = true;
-        return CE_OK;
-    }
-    if (plan.total > n_px * 8) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: the packed planes do not fit the staging buffer");
-    const int k = b->next_wide;
-    b->next_wide ^= 1;
-    if (!b->h_wide[k]) {
-        const size_t cap = n_px * (b->linear ? 12 : 8);  // wide_stage's size: the pair is shared with *_fmt and *_cicp
-        CE_HIP(ctx, hipHostMalloc((void **)&b->h_wide[k], cap, hipHostMallocDefault));
-        CE_HIP(ctx, hipMalloc((void **)&b->d_wide[k], cap));
-        CE_HIP(ctx, hipEventCreateWithFlags(&b->ev_wide[k], hipEventDisableTiming));
-    }
-    if (int rc = order_write(b, false)) return rc;
-    if (b->wide_busy[k]) CE_HIP(ctx, hipEventSynchronize(b->ev_wide[k]));
-    yuv_pack(img, &plan, b->h_wide[k], b->d_wide[k]);
-    CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], plan.total, hipMemcpyHostToDevice, b->up_stream));
-    if (int rc = launch_yuv_into(ctx, b->up_stream, plan, b->w, b->h, dst, depth, lin)) return rc;
-    CE_HIP(ctx, hipEventRecord(b->ev_wide[k], b->up_stream));
-    b->wide_busy[k] = true;
-    b->uploads_pending = true;
-    return CE_OK;
-}
-
-static const char *const kYuvLinear = "Y'CbCr ingest writes integer RGB: a linear batch takes planes through ce_batch_set_*_yuv_cicp";
-
-int ce_batch_set_reference_yuv(ce_batch *b, uint32_t ref_index, const ce_yuv_image *image)
-{
-    if (!b) return CE_ERR_INVALID_ARG;
-    if (ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "ref_index out of range");
-    if (b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kYuvLinear);
-    yuv_plan plan;
-    if (int rc = yuv_check(b->ctx, image, b->w, b->h, b->depth[0] ? b->depth[0] : 8, &plan)) return rc;
-    invalidate_reference_state(b);
-    return upload_yuv(b, b->d_refs + (size_t)ref_index * b->img_bytes, image, plan, b->depth[0]);
-}
-
-int ce_batch_set_test_yuv(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const ce_yuv_image *image)
-{
-    if (!b) return CE_ERR_INVALID_ARG;
-    if (pair_index >= b->max_pairs || ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "pair/ref index out of range");
-    if (b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kYuvLinear);
-    yuv_plan plan;
-    if (int rc = yuv_check(b->ctx, image, b->w, b->h, b->depth[1] ? b->depth[1] : 8, &plan)) return rc;
-    if (int rc = ce_batch_bind_pair(b, pair_index, ref_index)) return rc;
-    return upload_yuv(b, b->d_tests + (size_t)pair_index * b->img_bytes, image, plan, b->depth[1]);
-}
-
-// one image -> host memory through the leaf scratch, on the context's stream
-static int yuv_to_host(ce_ctx *ctx, const ce_yuv_image *image, uint32_t w, uint32_t h, bool out16, uint32_t depth_out, void *out,
-                       size_t out_len)
-{
-    if (!ctx) return CE_ERR_INVALID_ARG;
-    if (!out) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: null output");
-    if (w == 0 || h == 0) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: empty image");
-    if (out16 && !deep_depth_ok(depth_out))
-        return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: the output depth must be 8, 10, 12 or 16 bits, got " + std::to_string(depth_out));
-    yuv_plan plan;
-    if (int rc = yuv_check(ctx, image, w, h, depth_out, &plan)) return rc;
-    const size_t samples = (size_t)w * h * 3, out_bytes = samples * (out16 ? 2 : 1);
-    if (out_len != samples)
-        return fail(ctx, CE_ERR_BAD_LENGTH, "Invalid image size: expected " + std::to_string(samples) + " samples, got " + std::to_string(out_len));
-    const bool host = image->memory == CE_MEM_HOST;
-    if (int rc = leaf_scratch(ctx, host ? plan.total : 1, out_bytes)) return rc;
-    if (host) {
-        yuv_pack(image, &plan, ctx->leaf_h, ctx->leaf_d_in);
-        CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_d_in, ctx->leaf_h, plan.total, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (int rc = ce_launch_yuv(ctx, ctx->stream, plan.dev, w, h, ctx->leaf_d_out, out16, depth_out)) return rc;
-    CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_h, ctx->leaf_d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::memcpy(out, ctx->leaf_h, out_bytes);
-    return CE_OK;
-}
-
-int ce_yuv_to_rgb8(ce_ctx *ctx, const ce_yuv_image *image, uint32_t width, uint32_t height, uint8_t *out, size_t out_len)
-{
-    return yuv_to_host(ctx, image, width, height, false, 8, out, out_len);
-}
-
-int ce_yuv_to_rgb16(ce_ctx *ctx, const ce_yuv_image *image, uint32_t width, uint32_t height, uint32_t depth_out, uint16_t *out,
-                    size_t out_len)
-{
-    return yuv_to_host(ctx, image, width, height, true, depth_out, out, out_len);
-}
-
-// ---- Y'CbCr planes with a CICP description into a linear batch (yuv_cicp.hip) ----------------
-
-// everything *_yuv refuses about the image and *_cicp about the description, and their one joint rule: the integer RGB
-// grid between the two halves (c->depth) is no coarser than the samples
-static int yuv_cicp_check(ce_ctx *ctx, const ce_yuv_image *img, const ce_colour *c, uint32_t w, uint32_t h, yuv_plan *plan, cicp_plan *lin)
-{
-    if (!img) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: null image");
-    if (!c) return fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: null pointer");
-    if (int rc = cicp_colour_check(ctx, c, lin)) return rc;
-    if (int rc = yuv_check(ctx, img, w, h, c->depth, plan)) return rc;
-    if (c->depth < (uint32_t)img->depth)
-        return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr CICP ingest: the colour description's depth " + std::to_string(c->depth) +
-                                                 " is under the samples' " + std::to_string(img->depth) + " bits");
-    return cicp_table(ctx, c, lin);
-}
-
-static const char *const kYuvCicpWantsLinear =
-    "Y'CbCr CICP ingest writes linear light: it needs a linear batch (ce_batch_create_linear); ce_batch_set_*_yuv serves the others";
-
-int ce_batch_set_reference_yuv_cicp(ce_batch *b, uint32_t ref_index, const ce_yuv_image *image, const ce_colour *c)
-{
-    if (!b) return CE_ERR_INVALID_ARG;
-    if (!b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kYuvCicpWantsLinear);
-    if (ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "ref_index out of range");
-    yuv_plan plan;
-    cicp_plan lin;
-    if (int rc = yuv_cicp_check(b->ctx, image, c, b->w, b->h, &plan, &lin)) return rc;
-    invalidate_reference_state(b);
-    return upload_yuv(b, b->d_refs + (size_t)ref_index * b->img_bytes, image, plan, 0, &lin);
-}
-
-int ce_batch_set_test_yuv_cicp(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const ce_yuv_image *image, const ce_colour *c)
-{
-    if (!b) return CE_ERR_INVALID_ARG;
-    if (!b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kYuvCicpWantsLinear);
-    if (pair_index >= b->max_pairs || ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "pair/ref index out of range");
-    yuv_plan plan;
-    cicp_plan lin;
-    if (int rc = yuv_cicp_check(b->ctx, image, c, b->w, b->h, &plan, &lin)) return rc;
-    if (int rc = ce_batch_bind_pair(b, pair_index, ref_index)) return rc;
-    return upload_yuv(b, b->d_tests + (size_t)pair_index * b->img_bytes, image, plan, 0, &lin);
-}
-
-// one checked image -> packed f32 RGB in host memory through the leaf scratch, on the context's stream (as yuv_to_host)
-static int yuv_linear_to_host(ce_ctx *ctx, const ce_yuv_image *image, yuv_plan &plan, const cicp_plan &lin, uint32_t w, uint32_t h, float *out,
-                              size_t out_len, const char *what)
-{
-    const size_t samples = (size_t)w * h * 3, out_bytes = samples * sizeof(float);
-    if (out_len != samples)
-        return fail(ctx, CE_ERR_BAD_LENGTH, std::string(what) + ": out_len must be " + std::to_string(samples) + " floats, got " + std::to_string(out_len));
-    const bool host = image->memory == CE_MEM_HOST;
-    if (int rc = leaf_scratch(ctx, host ? plan.total : 1, out_bytes)) return rc;
-    if (host) {
-        yuv_pack(image, &plan, ctx->leaf_h, ctx->leaf_d_in);
-        CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_d_in, ctx->leaf_h, plan.total, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (int rc = launch_yuv_into(ctx, ctx->stream, plan, w, h, ctx->leaf_d_out, 0, &lin)) return rc;
-    CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_h, ctx->leaf_d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::memcpy(out, ctx->leaf_h, out_bytes);
-    return CE_OK;
-}
-
-int ce_yuv_to_linear(ce_ctx *ctx, const ce_yuv_image *image, const ce_colour *c, uint32_t w, uint32_t h, float *out, size_t out_len)
-{
-    if (!ctx) return CE_ERR_INVALID_ARG;
-    if (!out) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: null output");
-    if (w == 0 || h == 0) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: empty image");
-    yuv_plan plan;
-    cicp_plan lin;
-    if (int rc = yuv_cicp_check(ctx, image, c, w, h, &plan, &lin)) return rc;
-    return yuv_linear_to_host(ctx, image, plan, lin, w, h, out, out_len, "Y'CbCr CICP ingest");
-}
-
-// ---- Y'CbCr planes in HLG into a linear batch (yuv_hlg.hip) -----------------------------------
-
-// everything *_yuv refuses about the image and *_hlg about the description, and their one joint rule: the integer RGB grid
-// between the two halves (h->depth) is no coarser than the samples
-static int yuv_hlg_check(ce_ctx *ctx, const ce_yuv_image *img, const ce_hlg *hd, uint32_t w, uint32_t h, yuv_plan *plan, cicp_plan *lin)
-{
-    if (!img) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: null image");
-    if (!hd) return fail(ctx, CE_ERR_INVALID_ARG, "HLG ingest: null pointer");
-    if (int rc = hlg_colour_check(ctx, hd, lin)) return rc;
-    if (int rc = yuv_check(ctx, img, w, h, hd->depth, plan)) return rc;
-    if (hd->depth < (uint32_t)img->depth)
-        return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr HLG ingest: the description's depth " + std::to_string(hd->depth) + " is under the samples' " +
-                                                 std::to_string(img->depth) + " bits");
-    return hlg_table_dev(ctx, hd, lin);
-}
-
-int ce_batch_set_reference_yuv_hlg(ce_batch *b, uint32_t ref_index, const ce_yuv_image *image, const ce_hlg *h)
-{
-    if (!b) return CE_ERR_INVALID_ARG;
-    if (!b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kHlgWantsLinear);
-    if (ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "ref_index out of range");
-    yuv_plan plan;
-    cicp_plan lin;
-    if (int rc = yuv_hlg_check(b->ctx, image, h, b->w, b->h, &plan, &lin)) return rc;
-    invalidate_reference_state(b);
-    return upload_yuv(b, b->d_refs + (size_t)ref_index * b->img_bytes, image, plan, 0, &lin);
-}
-
-int ce_batch_set_test_yuv_hlg(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const ce_yuv_image *image, const ce_hlg *h)
-{
-    if (!b) return CE_ERR_INVALID_ARG;
-    if (!b->linear) return fail(b->ctx, CE_ERR_INVALID_ARG, kHlgWantsLinear);
-    if (pair_index >= b->max_pairs || ref_index >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "pair/ref index out of range");
-    yuv_plan plan;
-    cicp_plan lin;
-    if (int rc = yuv_hlg_check(b->ctx, image, h, b->w, b->h, &plan, &lin)) return rc;
-    if (int rc = ce_batch_bind_pair(b, pair_index, ref_index)) return rc;
-    return upload_yuv(b, b->d_tests + (size_t)pair_index * b->img_bytes, image, plan, 0, &lin);
-}
-
-int ce_yuv_hlg_to_linear(ce_ctx *ctx, const ce_yuv_image *image, const ce_hlg *hd, uint32_t w, uint32_t h, float *out, size_t out_len)
-{
-    if (!ctx) return CE_ERR_INVALID_ARG;
-    if (!out) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: null output");
-    if (w == 0 || h == 0) return fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: empty image");
-    yuv_plan plan;
-    cicp_plan lin;
-    if (int rc = yuv_hlg_check(ctx, image, hd, w, h, &plan, &lin)) return rc;
-    return yuv_linear_to_host(ctx, image, plan, lin, w, h, out, out_len, "Y'CbCr HLG ingest");
 }
 
 // ---- HDR fidelity of linear batches: PQ-PSNR and BT.2124 Delta E ITP (hdr_fidelity.hip) ----------
@@ -2378,15 +1402,15 @@ static bool hdr_depth_ok(uint32_t d) { return d == 10 || d == 12 || d == 16; }
 int ce_pq_code_thresholds(uint32_t depth, float white_nits, float *out, size_t n)
 {
     if (!out || !hdr_depth_ok(depth) || n != ((size_t)1 << depth) - 1)
-        return fail(nullptr, CE_ERR_INVALID_ARG, "ce_pq_code_thresholds: depth 10, 12 or 16 and n = 2^depth - 1");
+        return ce_fail(nullptr, CE_ERR_INVALID_ARG, "ce_pq_code_thresholds: depth 10, 12 or 16 and n = 2^depth - 1");
     if (!ce_build_pq_code_thresholds((1u << depth) - 1u, (double)white_nits, out))
-        return fail(nullptr, CE_ERR_INVALID_ARG, "ce_pq_code_thresholds: white_nits must be finite and > 0");
+        return ce_fail(nullptr, CE_ERR_INVALID_ARG, "ce_pq_code_thresholds: white_nits must be finite and > 0");
     return CE_OK;
 }
 
 int ce_hdr_fidelity_matrices(float a[9], float b[9])
 {
-    if (!a || !b) return fail(nullptr, CE_ERR_INVALID_ARG, "ce_hdr_fidelity_matrices: null pointer");
+    if (!a || !b) return ce_fail(nullptr, CE_ERR_INVALID_ARG, "ce_hdr_fidelity_matrices: null pointer");
     ce_build_hdr_fidelity_matrices(a, b);
     return CE_OK;
 }
@@ -2409,7 +1433,7 @@ static int hdr_table_dev(ce_ctx *ctx, uint32_t depth, float white_nits, const fl
         CE_HIP(ctx, hipMalloc(&d, host.size() * sizeof(float)));
         if (hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
             hipFree(d);
-            return fail(ctx, CE_ERR_BACKEND, "H2D failed (PQ code thresholds)");
+            return ce_fail(ctx, CE_ERR_BACKEND, "H2D failed (PQ code thresholds)");
         }
         it = ctx->hdr_tables.emplace(key, d).first;
     }
@@ -2420,8 +1444,8 @@ static int hdr_table_dev(ce_ctx *ctx, uint32_t depth, float white_nits, const fl
 
 static int hdr_params_check(ce_ctx *ctx, uint32_t depth, float white_nits)
 {
-    if (!hdr_depth_ok(depth)) return fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: depth must be 10, 12 or 16, got " + std::to_string(depth));
-    if (!(white_nits > 0.0f && std::isfinite(white_nits))) return fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: white_nits must be finite and > 0");
+    if (!hdr_depth_ok(depth)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: depth must be 10, 12 or 16, got " + std::to_string(depth));
+    if (!(white_nits > 0.0f && std::isfinite(white_nits))) return ce_fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: white_nits must be finite and > 0");
     return CE_OK;
 }
 
@@ -2429,18 +1453,18 @@ int ce_batch_hdr_fidelity(ce_batch *b, uint32_t n_pairs, uint32_t depth, float w
 {
     if (!b) return CE_ERR_INVALID_ARG;
     ce_ctx *ctx = b->ctx;
-    if (!out) return fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: null pointer");
+    if (!out) return ce_fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: null pointer");
     if (!b->linear)
-        return fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity reads linear light: it needs a linear batch (ce_batch_create_linear)");
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity reads linear light: it needs a linear batch (ce_batch_create_linear)");
     if (int rc = hdr_params_check(ctx, depth, white_nits)) return rc;
-    if (n_pairs == 0 || n_pairs > b->max_pairs) return fail(ctx, CE_ERR_INVALID_ARG, "n_pairs out of range");
+    if (n_pairs == 0 || n_pairs > b->max_pairs) return ce_fail(ctx, CE_ERR_INVALID_ARG, "n_pairs out of range");
     CE_HIP(ctx, hipSetDevice(ctx->device));
     const float *d_table = nullptr, *d_coarse = nullptr;
     if (int rc = hdr_table_dev(ctx, depth, white_nits, &d_table, &d_coarse)) return rc;
     if (!b->d_hdr) CE_HIP(ctx, hipMalloc(&b->d_hdr, sizeof(unsigned long long) * 3 * b->max_pairs));
     if (!b->h_hdr) CE_HIP(ctx, hipHostMalloc(&b->h_hdr, sizeof(unsigned long long) * 3 * b->max_pairs, hipHostMallocDefault));
     // on the context's stream, as a launch: behind the uploads queued so far, with the pair table of the last bind
-    if (int rc = flush_uploads(b)) return rc;
+    if (int rc = ce_flush_uploads(b)) return rc;
     if (int rc = sync_pair_ref(b)) return rc;
     float a[9], lms[9];
     ce_build_hdr_fidelity_matrices(a, lms);
@@ -2464,13 +1488,13 @@ int ce_eval_pair_hdr_fidelity(ce_ctx *ctx, const float *reference, size_t refere
                               uint32_t height, uint32_t depth, float white_nits, ce_hdr_scores *out)
 {
     if (!ctx) return CE_ERR_INVALID_ARG;
-    if (!out || !reference || !test) return fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: null pointer");
+    if (!out || !reference || !test) return ce_fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: null pointer");
     *out = ce_hdr_scores{};
-    if (width == 0 || height == 0) return fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: empty image");
+    if (width == 0 || height == 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: empty image");
     if (int rc = hdr_params_check(ctx, depth, white_nits)) return rc;
     const size_t want = (size_t)width * height * 12;
-    if (reference_len != want) return bad_length(ctx, want, reference_len);
-    if (test_len != want) return bad_length(ctx, want, test_len);
+    if (reference_len != want) return ce_bad_length(ctx, want, reference_len);
+    if (test_len != want) return ce_bad_length(ctx, want, test_len);
     CE_HIP(ctx, hipSetDevice(ctx->device));
     ce_batch *b = ctx->leaf_linear;
     if (!b || b->w != width || b->h != height) {
@@ -2486,124 +1510,6 @@ int ce_eval_pair_hdr_fidelity(ce_ctx *ctx, const float *reference, size_t refere
     return rc;
 }
 
-// ---- alpha: composited over solid backgrounds (alpha.hip) ----------------------------------------
-
-static int alpha_backgrounds_ok(ce_ctx *ctx, uint32_t n_bg, const uint16_t *backgrounds, uint32_t depth)
-{
-    if (n_bg == 0 || n_bg > CE_MAX_BACKGROUNDS)
-        return fail(ctx, CE_ERR_INVALID_ARG, "alpha compositing: 1 to " + std::to_string(CE_MAX_BACKGROUNDS) + " backgrounds, got " + std::to_string(n_bg));
-    const uint32_t m = (1u << depth) - 1u;
-    for (uint32_t i = 0; i < 3 * n_bg; i++)
-        if (backgrounds[i] > m)
-            return fail(ctx, CE_ERR_INVALID_ARG, "alpha compositing: background sample " + std::to_string(backgrounds[i]) + " is above " + std::to_string(m));
-    return CE_OK;
-}
-
-// the checks of one ce_batch_set_*_over call that do not depend on the slots; depth = that side's (0: an RGB8 batch)
-static int alpha_check(ce_batch *b, size_t len, int format, uint32_t n_bg, const uint16_t *backgrounds, uint32_t depth)
-{
-    ce_ctx *ctx = b->ctx;
-    if (b->linear) return fail(ctx, CE_ERR_INVALID_ARG, "alpha compositing works on encoded integer samples: not for a linear batch");
-    if (format != CE_PIXEL_RGBA8 && format != CE_PIXEL_RGBA16)
-        return fail(ctx, CE_ERR_INVALID_ARG, format == CE_PIXEL_RGBA16_10BIT ? "alpha compositing: CE_PIXEL_RGBA16_10BIT rounds to 8 bits; a deep batch takes 10-bit alpha as CE_PIXEL_RGBA16"
-                                                                              : "alpha compositing: the format must be CE_PIXEL_RGBA8 or CE_PIXEL_RGBA16");
-    if (!depth && format == CE_PIXEL_RGBA16) return fail(ctx, CE_ERR_INVALID_ARG, "alpha compositing: CE_PIXEL_RGBA16 needs a deep batch (ce_batch_create_deep)");
-    if (depth && depth != 8 && format == CE_PIXEL_RGBA8)
-        return fail(ctx, CE_ERR_INVALID_ARG, "alpha compositing: an 8-bit image needs a side of depth 8, this one has " + std::to_string(depth));
-    const size_t want = (size_t)b->w * b->h * ce_pixel_bytes(format);
-    if (len != want)
-        return fail(ctx, CE_ERR_INVALID_ARG, "alpha compositing: expected " + std::to_string(want) + " bytes, got " + std::to_string(len));
-    return alpha_backgrounds_ok(ctx, n_bg, backgrounds, depth ? depth : 8);
-}
-
-// one RGBA image through the wide staging pair of upload_fmt into n_bg consecutive slots from dst on
-static int upload_over(ce_batch *b, uint8_t *dst, const void *pixels, size_t len, int format, uint32_t depth, uint32_t n_bg,
-                       const uint16_t *backgrounds)
-{
-    ce_ctx *ctx = b->ctx;
-    const size_t n_px = (size_t)b->w * b->h;
-    CE_HIP(ctx, hipSetDevice(ctx->device));
-    const int k = b->next_wide;
-    b->next_wide ^= 1;
-    if (!b->h_wide[k]) {
-        CE_HIP(ctx, hipHostMalloc((void **)&b->h_wide[k], n_px * 8, hipHostMallocDefault));
-        CE_HIP(ctx, hipMalloc((void **)&b->d_wide[k], n_px * 8));
-        CE_HIP(ctx, hipEventCreateWithFlags(&b->ev_wide[k], hipEventDisableTiming));
-    }
-    if (int rc = order_write(b, false)) return rc;
-    if (b->wide_busy[k]) CE_HIP(ctx, hipEventSynchronize(b->ev_wide[k]));
-    std::memcpy(b->h_wide[k], pixels, len);
-    CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], len, hipMemcpyHostToDevice, b->up_stream));
-    if (int rc = ce_launch_alpha(ctx, b->up_stream, b->d_wide[k], format == CE_PIXEL_RGBA16, dst, depth != 0, depth ? depth : 8, n_px, n_bg, backgrounds))
-        return rc;
-    CE_HIP(ctx, hipEventRecord(b->ev_wide[k], b->up_stream));
-    b->wide_busy[k] = true;
-    b->uploads_pending = true;
-    return CE_OK;
-}
-
-int ce_batch_set_reference_over(ce_batch *b, uint32_t first_ref, const void *pixels, size_t len, int format, uint32_t n_bg,
-                                const uint16_t *backgrounds)
-{
-    if (!b) return CE_ERR_INVALID_ARG;
-    if (!pixels || !backgrounds) return fail(b->ctx, CE_ERR_INVALID_ARG, "alpha compositing: null pointer");
-    if (int rc = alpha_check(b, len, format, n_bg, backgrounds, b->depth[0])) return rc;
-    if (first_ref > b->max_refs || n_bg > b->max_refs - first_ref)
-        return fail(b->ctx, CE_ERR_INVALID_ARG, "alpha compositing: reference slots [" + std::to_string(first_ref) + ", " + std::to_string((uint64_t)first_ref + n_bg) +
-                                                    ") outside the " + std::to_string(b->max_refs) + " slots");
-    invalidate_reference_state(b);
-    return upload_over(b, b->d_refs + (size_t)first_ref * b->img_bytes, pixels, len, format, b->depth[0], n_bg, backgrounds);
-}
-
-int ce_batch_set_test_over(ce_batch *b, uint32_t first_pair, const uint32_t *ref_indices, const void *pixels, size_t len,
-                           int format, uint32_t n_bg, const uint16_t *backgrounds)
-{
-    if (!b) return CE_ERR_INVALID_ARG;
-    if (!ref_indices || !pixels || !backgrounds) return fail(b->ctx, CE_ERR_INVALID_ARG, "alpha compositing: null pointer");
-    if (int rc = alpha_check(b, len, format, n_bg, backgrounds, b->depth[1])) return rc;
-    if (first_pair > b->max_pairs || n_bg > b->max_pairs - first_pair)
-        return fail(b->ctx, CE_ERR_INVALID_ARG, "alpha compositing: test slots [" + std::to_string(first_pair) + ", " + std::to_string((uint64_t)first_pair + n_bg) +
-                                                    ") outside the " + std::to_string(b->max_pairs) + " slots");
-    for (uint32_t k = 0; k < n_bg; k++)
-        if (ref_indices[k] >= b->max_refs) return fail(b->ctx, CE_ERR_INVALID_ARG, "alpha compositing: ref index " + std::to_string(ref_indices[k]) + " out of range");
-    for (uint32_t k = 0; k < n_bg; k++)
-        if (int rc = ce_batch_bind_pair(b, first_pair + k, ref_indices[k])) return rc;
-    return upload_over(b, b->d_tests + (size_t)first_pair * b->img_bytes, pixels, len, format, b->depth[1], n_bg, backgrounds);
-}
-
-// one image over one colour -> host memory through the leaf scratch, on the context's stream
-static int composite_to_host(ce_ctx *ctx, const void *rgba, size_t len, uint32_t w, uint32_t h, bool deep, uint32_t depth,
-                             const uint16_t bg[3], void *out, size_t out_len)
-{
-    if (!ctx) return CE_ERR_INVALID_ARG;
-    if (!rgba || !bg || !out) return fail(ctx, CE_ERR_INVALID_ARG, "alpha compositing: null pointer");
-    if (!deep_depth_ok(depth)) return fail(ctx, CE_ERR_INVALID_ARG, "alpha compositing: depth must be 8, 10, 12 or 16 bits, got " + std::to_string(depth));
-    const size_t n_px = (size_t)w * h;
-    if (len != n_px * 4 || out_len != n_px * 3)
-        return fail(ctx, CE_ERR_INVALID_ARG, "alpha compositing: expected " + std::to_string(n_px * 4) + " samples in and " + std::to_string(n_px * 3) +
-                                                 " out, got " + std::to_string(len) + " and " + std::to_string(out_len));
-    if (int rc = alpha_backgrounds_ok(ctx, 1, bg, depth)) return rc;
-    if (n_px == 0) return CE_OK;
-    const size_t bps = deep ? 2 : 1;
-    return leaf_roundtrip(ctx, rgba, len * bps, out, out_len * bps, [&](uint8_t *d_in, uint8_t *d_out) {
-        return ce_launch_alpha(ctx, ctx->stream, d_in, deep, d_out, deep, depth, n_px, 1, bg);
-    });
-}
-
-int ce_composite_rgba8(ce_ctx *ctx, const uint8_t *rgba, size_t len, uint32_t w, uint32_t h, const uint8_t bg[3], uint8_t *out,
-                       size_t out_len)
-{
-    uint16_t bg16[3] = {};
-    for (int c = 0; bg && c < 3; c++) bg16[c] = bg[c];
-    return composite_to_host(ctx, rgba, len, w, h, false, 8, bg ? bg16 : nullptr, out, out_len);
-}
-
-int ce_composite_rgba16(ce_ctx *ctx, const uint16_t *rgba, size_t len, uint32_t w, uint32_t h, uint32_t depth, const uint16_t bg[3],
-                        uint16_t *out, size_t out_len)
-{
-    return composite_to_host(ctx, rgba, len, w, h, true, depth, bg, out, out_len);
-}
-
 // ---- viewing simulation: resampling (resample.hip) ----------------------------------------------
 
 // the taps of one axis on the device, built on first use and kept with the context (ce_ctx::rs_tables)
@@ -2615,11 +1521,11 @@ static int resample_table(ce_ctx *ctx, uint32_t n_in, uint32_t n_out, int filter
         std::vector<int32_t> host;
         ce_resample_axis a;
         a.n_in = n_in, a.n_out = n_out;
-        if (!ce_build_resample_table(n_in, n_out, filter, host, &a.ksize)) return fail(ctx, CE_ERR_INVALID_ARG, "resample: bad axis");
+        if (!ce_build_resample_table(n_in, n_out, filter, host, &a.ksize)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: bad axis");
         CE_HIP(ctx, hipMalloc((void **)&a.d, host.size() * sizeof(int32_t)));
         if (hipMemcpy(a.d, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
             hipFree(a.d);
-            return fail(ctx, CE_ERR_BACKEND, "H2D failed (resample taps)");
+            return ce_fail(ctx, CE_ERR_BACKEND, "H2D failed (resample taps)");
         }
         it = ctx->rs_tables.emplace(key, a).first;
     }
@@ -2636,11 +1542,11 @@ static int resample_table_f64(ce_ctx *ctx, uint32_t n_in, uint32_t n_out, int fi
         std::vector<double> host;
         ce_resample_axis_f64 a;
         a.n_in = n_in, a.n_out = n_out;
-        if (!ce_build_resample_table_f64(n_in, n_out, filter, host, &a.ksize)) return fail(ctx, CE_ERR_INVALID_ARG, "resample: bad axis");
+        if (!ce_build_resample_table_f64(n_in, n_out, filter, host, &a.ksize)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: bad axis");
         CE_HIP(ctx, hipMalloc((void **)&a.d, host.size() * sizeof(double)));
         if (hipMemcpy(a.d, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
             hipFree(a.d);
-            return fail(ctx, CE_ERR_BACKEND, "H2D failed (resample taps)");
+            return ce_fail(ctx, CE_ERR_BACKEND, "H2D failed (resample taps)");
         }
         it = ctx->rs_tables_f64.emplace(key, a).first;
     }
@@ -2716,15 +1622,15 @@ static int resample_images_linear(ce_ctx *ctx, const uint8_t *d_src, size_t src_
 int ce_resample_rgb8(ce_ctx *ctx, const uint8_t *rgb, size_t len, uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h, int filter,
                      uint8_t *out, size_t out_len)
 {
-    if (!ctx || !rgb || !out) return fail(ctx, CE_ERR_INVALID_ARG, "resample: null pointer");
-    if (!resample_filter_ok(filter)) return fail(ctx, CE_ERR_INVALID_ARG, "resample: unknown filter " + std::to_string(filter));
+    if (!ctx || !rgb || !out) return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: null pointer");
+    if (!resample_filter_ok(filter)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: unknown filter " + std::to_string(filter));
     if (w == 0 || h == 0 || out_w == 0 || out_h == 0)
-        return fail(ctx, CE_ERR_INVALID_ARG, "resample: " + std::to_string(w) + " x " + std::to_string(h) + " to " + std::to_string(out_w) +
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: " + std::to_string(w) + " x " + std::to_string(h) + " to " + std::to_string(out_w) +
                                                  " x " + std::to_string(out_h) + " has an empty side");
     const size_t want_in = (size_t)w * h * 3, want_out = (size_t)out_w * out_h * 3;
-    if (len != want_in) return bad_length(ctx, want_in, len);
-    if (out_len != want_out) return bad_length(ctx, want_out, out_len);
-    return leaf_roundtrip(ctx, rgb, len, out, out_len, [&](uint8_t *d_in, uint8_t *d_out) {
+    if (len != want_in) return ce_bad_length(ctx, want_in, len);
+    if (out_len != want_out) return ce_bad_length(ctx, want_out, out_len);
+    return ce_leaf_roundtrip(ctx, rgb, len, out, out_len, [&](uint8_t *d_in, uint8_t *d_out) {
         return resample_images(ctx, d_in, want_in, d_out, want_out, w, h, out_w, out_h, 1, filter);
     });
 }
@@ -2732,15 +1638,15 @@ int ce_resample_rgb8(ce_ctx *ctx, const uint8_t *rgb, size_t len, uint32_t w, ui
 int ce_resample_linear(ce_ctx *ctx, const float *rgb, size_t len, uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h, int filter, float *out,
                        size_t out_len)
 {
-    if (!ctx || !rgb || !out) return fail(ctx, CE_ERR_INVALID_ARG, "resample: null pointer");
-    if (!resample_filter_ok(filter)) return fail(ctx, CE_ERR_INVALID_ARG, "resample: unknown filter " + std::to_string(filter));
+    if (!ctx || !rgb || !out) return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: null pointer");
+    if (!resample_filter_ok(filter)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: unknown filter " + std::to_string(filter));
     if (w == 0 || h == 0 || out_w == 0 || out_h == 0)
-        return fail(ctx, CE_ERR_INVALID_ARG, "resample: " + std::to_string(w) + " x " + std::to_string(h) + " to " + std::to_string(out_w) +
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: " + std::to_string(w) + " x " + std::to_string(h) + " to " + std::to_string(out_w) +
                                                  " x " + std::to_string(out_h) + " has an empty side");
     const size_t want_in = (size_t)w * h * 12, want_out = (size_t)out_w * out_h * 12;
-    if (len != want_in) return bad_length(ctx, want_in, len);
-    if (out_len != want_out) return bad_length(ctx, want_out, out_len);
-    return leaf_roundtrip(ctx, rgb, len, out, out_len, [&](uint8_t *d_in, uint8_t *d_out) {
+    if (len != want_in) return ce_bad_length(ctx, want_in, len);
+    if (out_len != want_out) return ce_bad_length(ctx, want_out, out_len);
+    return ce_leaf_roundtrip(ctx, rgb, len, out, out_len, [&](uint8_t *d_in, uint8_t *d_out) {
         return resample_images_linear(ctx, d_in, want_in, d_out, want_out, w, h, out_w, out_h, 1, filter);
     });
 }
@@ -2748,17 +1654,17 @@ int ce_resample_linear(ce_ctx *ctx, const float *rgb, size_t len, uint32_t w, ui
 // the checks two batches must pass before anything moves between them
 static int resample_check(ce_batch *src, ce_batch *dst, int filter)
 {
-    if (!src || !dst) return fail(src ? src->ctx : dst ? dst->ctx : nullptr, CE_ERR_INVALID_ARG, "resample: null batch");
+    if (!src || !dst) return ce_fail(src ? src->ctx : dst ? dst->ctx : nullptr, CE_ERR_INVALID_ARG, "resample: null batch");
     ce_ctx *ctx = src->ctx;
-    if (dst->ctx != ctx) return fail(ctx, CE_ERR_INVALID_ARG, "resample: the two batches belong to different contexts");
-    if (src == dst) return fail(ctx, CE_ERR_INVALID_ARG, "resample: source and destination are the same batch");
-    if (!resample_filter_ok(filter)) return fail(ctx, CE_ERR_INVALID_ARG, "resample: unknown filter " + std::to_string(filter));
+    if (dst->ctx != ctx) return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: the two batches belong to different contexts");
+    if (src == dst) return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: source and destination are the same batch");
+    if (!resample_filter_ok(filter)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: unknown filter " + std::to_string(filter));
     if (src->depth[0] || dst->depth[0])
-        return fail(ctx, CE_ERR_INVALID_ARG, src->linear || dst->linear
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, src->linear || dst->linear
                                                  ? "resample: a linear batch resamples into a linear batch only, and a deep batch is out of its scope"
                                                  : "resample works on RGB8 and linear batches: a deep batch is out of its scope");
     if (src->linear != dst->linear)
-        return fail(ctx, CE_ERR_INVALID_ARG, "resample: a linear batch resamples into a linear batch only, an RGB8 batch into an RGB8 one");
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: a linear batch resamples into a linear batch only, an RGB8 batch into an RGB8 one");
     return CE_OK;
 }
 
@@ -2768,15 +1674,15 @@ static int resample_slab(ce_batch *src, ce_batch *dst, uint32_t which, uint32_t 
     const bool tests = which == CE_BATCH_TESTS;
     CE_HIP(ctx, hipSetDevice(ctx->device));
     // the kernels run on the context's stream: behind src's uploads (the ordering of a launch), and as an inline write of
-    // dst (order_write: behind dst's own uploads, ahead of its next launch and of its later uploads)
-    if (int rc = flush_uploads(src)) return rc;
-    if (int rc = order_write(dst, true)) return rc;
-    if (!tests) invalidate_reference_state(dst);
+    // dst (ce_order_write: behind dst's own uploads, ahead of its next launch and of its later uploads)
+    if (int rc = ce_flush_uploads(src)) return rc;
+    if (int rc = ce_order_write(dst, true)) return rc;
+    if (!tests) ce_invalidate_reference_state(dst);
     const uint8_t *s = (tests ? src->d_tests : src->d_refs) + (size_t)first * src->img_bytes;
     uint8_t *d = (tests ? dst->d_tests : dst->d_refs) + (size_t)first * dst->img_bytes;
     const int rc = (src->linear ? resample_images_linear : resample_images)(ctx, s, src->img_bytes, d, dst->img_bytes, src->w, src->h, dst->w,
                                                                             dst->h, count, filter);
-    src->inline_pending = true;  // a later upload into src waits for these reads (order_write)
+    src->inline_pending = true;  // a later upload into src waits for these reads (ce_order_write)
     return rc;
 }
 
@@ -2784,7 +1690,7 @@ static int resample_range_check(ce_batch *src, ce_batch *dst, bool tests, uint32
 {
     const uint32_t slots = tests ? std::min(src->max_pairs, dst->max_pairs) : std::min(src->max_refs, dst->max_refs);
     if (count == 0 || first > slots || count > slots - first)
-        return fail(src->ctx, CE_ERR_INVALID_ARG, std::string("resample: ") + (tests ? "tests [" : "references [") + std::to_string(first) + ", " +
+        return ce_fail(src->ctx, CE_ERR_INVALID_ARG, std::string("resample: ") + (tests ? "tests [" : "references [") + std::to_string(first) + ", " +
                                                       std::to_string((uint64_t)first + count) + ") outside the " + std::to_string(slots) +
                                                       " slots both batches have");
     return CE_OK;
@@ -2794,7 +1700,7 @@ int ce_batch_resample(ce_batch *src, ce_batch *dst, uint32_t which, uint32_t fir
 {
     if (int rc = resample_check(src, dst, filter)) return rc;
     if (which != CE_BATCH_REFERENCES && which != CE_BATCH_TESTS)
-        return fail(src->ctx, CE_ERR_INVALID_ARG, "resample: unknown slab " + std::to_string(which));
+        return ce_fail(src->ctx, CE_ERR_INVALID_ARG, "resample: unknown slab " + std::to_string(which));
     if (int rc = resample_range_check(src, dst, which == CE_BATCH_TESTS, first, count)) return rc;
     return resample_slab(src, dst, which, first, count, filter);
 }
@@ -2806,7 +1712,7 @@ int ce_batch_resample_pairs(ce_batch *src, ce_batch *dst, uint32_t n_refs, uint3
     if (int rc = resample_range_check(src, dst, true, 0, n_pairs)) return rc;
     for (uint32_t i = 0; i < n_pairs; i++)
         if (src->h_pair_ref[i] >= n_refs)
-            return fail(src->ctx, CE_ERR_INVALID_ARG, "resample: pair " + std::to_string(i) + " is bound to reference " +
+            return ce_fail(src->ctx, CE_ERR_INVALID_ARG, "resample: pair " + std::to_string(i) + " is bound to reference " +
                                                           std::to_string(src->h_pair_ref[i]) + ", outside the " + std::to_string(n_refs) + " resampled");
     if (int rc = resample_slab(src, dst, CE_BATCH_REFERENCES, 0, n_refs, filter)) return rc;
     if (int rc = resample_slab(src, dst, CE_BATCH_TESTS, 0, n_pairs, filter)) return rc;
@@ -2828,7 +1734,7 @@ int ce_ref_create(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, u
 {
     if (!ctx || !reference || !out) return CE_ERR_INVALID_ARG;
     *out = nullptr;
-    if (reference_len != (size_t)width * height * 3) return bad_length(ctx, (size_t)width * height * 3, reference_len);
+    if (reference_len != (size_t)width * height * 3) return ce_bad_length(ctx, (size_t)width * height * 3, reference_len);
     ce_batch *b = nullptr;
     int rc = ce_batch_create(ctx, width, height, 1, 1, &b);
     if (rc != CE_OK) return rc;
@@ -2855,7 +1761,7 @@ int ce_ref_compare_many(ce_ref *ref, const uint8_t *const *tests, const size_t *
         ce_batch *nb = nullptr;
         int rc = ce_batch_create(ctx, b->w, b->h, 1, n_tests, &nb);
         if (rc != CE_OK) return rc;
-        rc = flush_uploads(b);
+        rc = ce_flush_uploads(b);
         if (rc != CE_OK) return rc;
         CE_HIP(ctx, hipMemcpyAsync(nb->d_refs, b->d_refs, b->img_bytes, hipMemcpyDeviceToDevice, ctx->stream));
         CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -2869,7 +1775,7 @@ int ce_ref_compare_many(ce_ref *ref, const uint8_t *const *tests, const size_t *
         out[i] = ce_scores{};
         if (!tests[i]) return CE_ERR_INVALID_ARG;
         if (test_lens[i] != b->img_bytes) {
-            out[i].status = fail(ctx, CE_ERR_DIM_MISMATCH, "Dimension mismatch: reference " + std::to_string(b->img_bytes) +
+            out[i].status = ce_fail(ctx, CE_ERR_DIM_MISMATCH, "Dimension mismatch: reference " + std::to_string(b->img_bytes) +
                                                                " bytes, test " + std::to_string(test_lens[i]) + " bytes");
             continue;
         }
@@ -2916,7 +1822,7 @@ int ce_ref_dssim_ssim_maps(ce_ref *ref, uint32_t level, uint32_t first, uint32_t
 int ce_ref_ssimulacra2_maps(ce_ref *ref, uint32_t scale, uint32_t channel, uint32_t kind, uint32_t first, uint32_t count, uint32_t block,
                             float *maps, size_t maps_floats, double *norms)
 {
-    if (!ref) return fail(nullptr, CE_ERR_INVALID_ARG, "null handle");
+    if (!ref) return ce_fail(nullptr, CE_ERR_INVALID_ARG, "null handle");
     return read_ssim2_maps(ref->batch, scale, channel, kind, first, count, block, maps, maps_floats, norms);  // the handle's current batch
 }
 
@@ -2928,16 +1834,16 @@ int ce_ref_image_heuristics(ce_ref *ref, ce_image_heuristics *out)
 
 int ce_ssimulacra2_scales(uint32_t width, uint32_t height, uint32_t *n_scales, uint32_t *scale_w, uint32_t *scale_h)
 {
-    if (!n_scales || !scale_w || !scale_h) return fail(nullptr, CE_ERR_INVALID_ARG, "null pointer");
-    if (width == 0 || height == 0) return fail(nullptr, CE_ERR_INVALID_ARG, "empty image");
+    if (!n_scales || !scale_w || !scale_h) return ce_fail(nullptr, CE_ERR_INVALID_ARG, "null pointer");
+    if (width == 0 || height == 0) return ce_fail(nullptr, CE_ERR_INVALID_ARG, "empty image");
     *n_scales = ce_plan_ssim2_scales(width, height, CE_SSIM2_MAX_SCALES, scale_w, scale_h);
     return CE_OK;
 }
 
 int ce_dssim_levels(uint32_t width, uint32_t height, uint32_t *n_levels, uint32_t *level_w, uint32_t *level_h)
 {
-    if (!n_levels || !level_w || !level_h) return fail(nullptr, CE_ERR_INVALID_ARG, "null pointer");
-    if (width == 0 || height == 0) return fail(nullptr, CE_ERR_INVALID_ARG, "empty image");
+    if (!n_levels || !level_w || !level_h) return ce_fail(nullptr, CE_ERR_INVALID_ARG, "null pointer");
+    if (width == 0 || height == 0) return ce_fail(nullptr, CE_ERR_INVALID_ARG, "empty image");
     *n_levels = ce_plan_dssim_levels(width, height, CE_DSSIM_MAX_LEVELS, level_w, level_h);
     return CE_OK;
 }

@@ -1,4 +1,4 @@
-// Internal declarations shared by the host runtime (ce_api.cpp) and the gfx950 kernels.
+// Internal declarations shared by the host runtime (ce_api.cpp, ce_ingest.cpp) and the gfx950 kernels.
 // Nothing here is part of the ABI; the ABI is include/ce_metrics.h.
 #pragma once
 
@@ -6,6 +6,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <functional>
 #include <map>
 #include <string>
 #include <tuple>
@@ -85,8 +86,8 @@ struct ce_ctx {
     struct ce_batch *leaf_deep = nullptr;  // the one-pair deep batch of ce_eval_pair_deep (remade when shape or depths change)
     struct ce_batch *leaf_linear = nullptr;  // the one-pair linear batch of ce_eval_pair_linear (remade when the shape changes)
     // transfer tables of the CICP ingest (cicp.hip), 2^depth entries each, keyed by (transfer, depth, bits of white_nits);
-    // built by the first ingest that needs one and kept until the context goes (ce_api.cpp: cicp_table).  The HLG ingest's
-    // inverse-OETF tables (hlg.hip) live here too, one per depth, under H.273's code for HLG: (18, depth, 0) (hlg_table_dev)
+    // built by the first ingest that needs one and kept until the context goes (ce_ingest.cpp: ingest_table).  The HLG ingest's
+    // inverse-OETF tables (hlg.hip) live here too, one per depth, under H.273's code for HLG: (18, depth, 0)
     std::map<std::tuple<int, uint32_t, uint32_t>, float *> cicp_tables;
     // threshold tables of the HDR fidelity scores (hdr_fidelity.hip), keyed by (depth, bits of white_nits), built by the first
     // call that needs one and kept until the context goes (ce_api.cpp: hdr_table_dev): T[1 .. maxv], padded to a multiple of
@@ -183,11 +184,10 @@ struct ce_batch {
     hipStream_t up_stream = nullptr;
     hipEvent_t ev_up = nullptr, ev_run = nullptr;  // uploads done / last launch done
     bool uploads_pending = false, run_pending = false;
-    bool inline_pending = false;  // a slot was written on the context's stream since the last launch (ce_api.cpp: order_write)
+    bool inline_pending = false;  // a slot was written on the context's stream since the last launch (ce_ingest.cpp: ce_order_write)
     bool counted_in_flight = false;  // this batch is in the device's launched-and-not-collected count (ce_api.cpp: g_in_flight)
-    // wide ingest (RGBA8 / 16-bit sources): one pinned + one device staging image of 8 B/px, made on first use
-    // (two of each: while image k's copy and conversion are in flight the host fills the other pair, so a sweep of wide
-    // decoded images does not synchronise the upload stream per image)
+    // the wide staging pairs of every image a conversion kernel follows: one pinned + one device staging image each, made
+    // on first use and handed out in turn (ce_ingest.cpp: wide_acquire, which states their size)
     uint8_t *h_wide[2] = {}, *d_wide[2] = {};
     hipEvent_t ev_wide[2] = {};
     bool wide_busy[2] = {};
@@ -305,6 +305,41 @@ struct ce_batch {
         }                                                                                          \
     } while (0)
 
+// ---- what the two halves of the host runtime share: ce_api.cpp (contexts, batch lifetime, launch, collect, the pooled
+// calls, resampling, HDR fidelity, reference handles, hooks) and ce_ingest.cpp (everything that writes a slot) ----------------
+
+// record `msg` as the context's last error (the calling thread's, without a context) and return `code` (ce_api.cpp)
+int ce_fail(ce_ctx *ctx, int code, const std::string &msg);
+int ce_bad_length(ce_ctx *ctx, size_t want, size_t got);  // CE_ERR_BAD_LENGTH, "Invalid image size: expected ... bytes, got ..."
+inline bool ce_deep_depth_ok(uint32_t d) { return d == 8 || d == 10 || d == 12 || d == 16; }
+
+// an ICC -> sRGB colour table on the device (ce_lut_create)
+struct ce_lut {
+    ce_ctx *ctx;
+    uint32_t *d_table;  // [2^24] r | g << 8 | b << 16
+};
+// one image of ce_upload_many
+struct ce_upload_job {
+    uint8_t *dst;
+    const uint8_t *src;
+};
+
+// The slot-write ordering (ce_ingest.cpp).  ce_order_write comes before every write into a slot, on the context's stream
+// or on the batch's upload stream; ce_flush_uploads before every kernel that reads one on the context's stream; a new
+// reference slab drops what was derived from the old one.
+int ce_order_write(ce_batch *b, bool on_ctx_stream);
+int ce_flush_uploads(ce_batch *b);
+void ce_invalidate_reference_state(ce_batch *b);
+// jobs.size() packed images of b->img_bytes into their slots, from a few host threads (ce_eval_batch; ce_ingest.cpp)
+int ce_upload_many(ce_batch *b, const std::vector<ce_upload_job> &jobs);
+// `lut` (nullptr: nothing) over the RGB8 image at `slot`, on the batch's upload stream behind its copy (ce_ingest.cpp)
+int ce_apply_lut(ce_batch *b, uint8_t *slot, const ce_lut *lut);
+// the context's leaf scratch grown to in_bytes / out_bytes, and one host image through it and `launch(d_in, d_out)` on the
+// context's stream, complete on return (ce_ingest.cpp)
+int ce_leaf_scratch(ce_ctx *ctx, size_t in_bytes, size_t out_bytes);
+int ce_leaf_roundtrip(ce_ctx *ctx, const void *in, size_t in_bytes, void *out, size_t out_bytes,
+                      const std::function<int(uint8_t *, uint8_t *)> &launch);
+
 // host table -> device memory of `b`, complete on return, without draining the context's stream (ce_api.cpp)
 int ce_upload_table(ce_batch *b, void *dst, const void *src, size_t bytes);
 
@@ -407,7 +442,7 @@ int ce_launch_resample_f32(ce_ctx *ctx, hipStream_t stream, const float *d_src, 
                            uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h, uint32_t n, const ce_resample_axis_f64 *horiz,
                            const ce_resample_axis_f64 *vert, float *mid);
 
-// One Y'CbCr image on the device as yuv.hip reads it: checked by ce_api.cpp (yuv_check), planes in device memory
+// One Y'CbCr image on the device as yuv.hip reads it: checked by ce_ingest.cpp (yuv_check), planes in device memory
 struct ce_yuv_dev {
     const uint8_t *plane[3];
     size_t pitch[3];         // bytes
@@ -417,6 +452,20 @@ struct ce_yuv_dev {
 };
 // w x h pixels of `src` -> packed RGB at d_dst: u8 (depth_out = 8, out16 = false) or u16 of depth_out, one launch (yuv.hip)
 int ce_launch_yuv(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32_t w, uint32_t h, void *d_dst, bool out16, uint32_t depth_out);
+// what the three launchers of Y'CbCr planes put into yuv_kernel.h's yuv_args: `src` at w x h, the integer RGB clamped to m
+template <class YuvArgs>
+inline void ce_fill_yuv_args(YuvArgs &a, const ce_yuv_dev &src, uint32_t w, uint32_t h, int64_t m)
+{
+    a.p0 = src.plane[0], a.p1 = src.plane[1], a.p2 = src.plane[2];
+    a.pitch0 = src.pitch[0], a.pitch1 = src.pitch[1], a.pitch2 = src.pitch[2];
+    a.w = w, a.h = h;
+    a.cw = src.subsampling == CE_YUV_444 ? w : (w + 1) / 2;
+    a.ch = src.subsampling == CE_YUV_420 ? (h + 1) / 2 : h;
+    a.shift = src.shift, a.maxv = (1u << src.depth) - 1u;
+    a.triangle = src.upsample == CE_CHROMA_TRIANGLE;
+    a.ky = src.k[0], a.krv = src.k[1], a.kgu = src.k[2], a.kgv = src.k[3], a.kbu = src.k[4], a.y0 = src.k[5], a.c0 = src.k[6];
+    a.m = m;
+}
 
 // n_pixels RGBA pixels at d_src (u8, or u16 of `depth` bits: src16) source-over onto each of n_bg solid colours
 // (backgrounds[n_bg][3], <= 2^depth - 1) -> n_bg consecutive packed RGB images from d_dst on, u8 or u16 (dst16; u8
@@ -431,6 +480,15 @@ int ce_launch_linear_sanitise(ce_ctx *ctx, hipStream_t stream, const float *d_sr
 // product in separately rounded f32 operations, then the clamp of a linear image (cicp.hip)
 int ce_launch_cicp(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, float *d_dst, size_t n_pixels, const float *d_table,
                    uint32_t maxv, const float *matrix);
+// what the four launchers of a linear-light pixel put into cicp_pixel.h's cicp_args: the slot, the table and the matrix
+// (nullptr: none, m is not read)
+template <class CicpArgs>
+inline void ce_fill_cicp_args(CicpArgs &a, float *d_dst, const float *d_table, uint32_t maxv, const float *matrix)
+{
+    a.dst = d_dst, a.table = d_table, a.maxv = maxv;
+    if (matrix)
+        for (int i = 0; i < 9; i++) a.m[i] = matrix[i];
+}
 
 // w x h pixels of `src`, whose k was built for depth_out = log2(maxv + 1), -> packed f32 RGB at d_dst: ce_launch_yuv's integer
 // RGB in [0, maxv] handed pixel by pixel to ce_launch_cicp's table, matrix (nullptr: none) and clamp, one launch (yuv_cicp.hip)

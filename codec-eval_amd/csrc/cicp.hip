@@ -45,9 +45,8 @@ int ce_launch_cicp(ce_ctx *ctx, hipStream_t stream, int format, const void *d_sr
         return CE_ERR_INVALID_ARG;
     }
     cicp_args a{};
-    a.src = d_src, a.dst = d_dst, a.n_pixels = n_pixels, a.table = d_table, a.maxv = maxv;
-    if (matrix)
-        for (int i = 0; i < 9; i++) a.m[i] = matrix[i];
+    a.src = d_src, a.n_pixels = n_pixels;
+    ce_fill_cicp_args(a, d_dst, d_table, maxv, matrix);
     const dim3 grid((uint32_t)blocks);
     switch (format) {
         case CE_PIXEL_RGB8: launch_cicp<CE_PIXEL_RGB8>(ctx, stream, "cicp_rgb8", "cicp_rgb8_m", grid, a, matrix != nullptr); break;

@@ -29,9 +29,8 @@ int ce_launch_hlg(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src
         return CE_ERR_INVALID_ARG;
     }
     hlg_args a{};
-    a.c.src = d_src, a.c.dst = d_dst, a.c.n_pixels = n_pixels, a.c.table = d_table, a.c.maxv = maxv;
-    if (matrix)
-        for (int i = 0; i < 9; i++) a.c.m[i] = matrix[i];
+    a.c.src = d_src, a.c.n_pixels = n_pixels;
+    ce_fill_cicp_args(a.c, d_dst, d_table, maxv, matrix);
     a.kr = params[0], a.kg = params[1], a.kb = params[2], a.gm1 = params[3], a.a = params[4];
     const dim3 grid((uint32_t)blocks);
     switch (format) {

@@ -49,15 +49,7 @@ int ce_launch_yuv(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32
         return CE_ERR_INVALID_ARG;
     }
     yuv_args a{};
-    a.p0 = src.plane[0], a.p1 = src.plane[1], a.p2 = src.plane[2];
-    a.pitch0 = src.pitch[0], a.pitch1 = src.pitch[1], a.pitch2 = src.pitch[2];
-    a.w = w, a.h = h;
-    a.cw = src.subsampling == CE_YUV_444 ? w : (w + 1) / 2;
-    a.ch = src.subsampling == CE_YUV_420 ? (h + 1) / 2 : h;
-    a.shift = src.shift, a.maxv = (1u << src.depth) - 1u;
-    a.triangle = src.upsample == CE_CHROMA_TRIANGLE;
-    a.ky = src.k[0], a.krv = src.k[1], a.kgu = src.k[2], a.kgv = src.k[3], a.kbu = src.k[4], a.y0 = src.k[5], a.c0 = src.k[6];
-    a.m = ((int64_t)1 << depth_out) - 1;
+    ce_fill_yuv_args(a, src, w, h, ((int64_t)1 << depth_out) - 1);
     const dim3 grid((uint32_t)blocks);
     const bool semi = src.layout == CE_YUV_SEMIPLANAR;
     uint8_t *dst = static_cast<uint8_t *>(d_dst);

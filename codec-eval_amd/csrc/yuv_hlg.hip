@@ -46,19 +46,8 @@ int ce_launch_yuv_hlg(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, ui
         return CE_ERR_INVALID_ARG;
     }
     yuv_hlg_args a{};
-    yuv_args &y = a.y;
-    y.p0 = src.plane[0], y.p1 = src.plane[1], y.p2 = src.plane[2];
-    y.pitch0 = src.pitch[0], y.pitch1 = src.pitch[1], y.pitch2 = src.pitch[2];
-    y.w = w, y.h = h;
-    y.cw = src.subsampling == CE_YUV_444 ? w : (w + 1) / 2;
-    y.ch = src.subsampling == CE_YUV_420 ? (h + 1) / 2 : h;
-    y.shift = src.shift, y.maxv = (1u << src.depth) - 1u;
-    y.triangle = src.upsample == CE_CHROMA_TRIANGLE;
-    y.ky = src.k[0], y.krv = src.k[1], y.kgu = src.k[2], y.kgv = src.k[3], y.kbu = src.k[4], y.y0 = src.k[5], y.c0 = src.k[6];
-    y.m = (int64_t)maxv;  // src.k was built for this output depth (yuv_check with depth_out = the HLG description's depth)
-    a.h.c.dst = d_dst, a.h.c.table = d_table, a.h.c.maxv = maxv;
-    if (matrix)
-        for (int i = 0; i < 9; i++) a.h.c.m[i] = matrix[i];
+    ce_fill_yuv_args(a.y, src, w, h, (int64_t)maxv);  // src.k was built for this output depth (yuv_check with depth_out = the HLG description's depth)
+    ce_fill_cicp_args(a.h.c, d_dst, d_table, maxv, matrix);
     a.h.kr = params[0], a.h.kg = params[1], a.h.kb = params[2], a.h.gm1 = params[3], a.h.a = params[4];
     const dim3 grid((uint32_t)blocks);
     const bool semi = src.layout == CE_YUV_SEMIPLANAR;
