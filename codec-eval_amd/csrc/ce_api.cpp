@@ -1,7 +1,8 @@
-// Host runtime behind the C ABI (include/ce_metrics.h): contexts, the HBM-resident pair
-// grid, shape bucketing for mixed batches, input validation with the reference's error
-// kinds, profiling hooks.  Everything that writes a slot of a batch is in ce_ingest.cpp.
-// All device work is in the .hip files; there is no CPU compute
+// Host runtime behind the C ABI (include/ce_metrics.h): errors, profiling hooks, the device copy of a host table, contexts,
+// the HBM-resident pair grid (batch lifetime, launch, collect, the map read-outs, HDR fidelity and image heuristics of a
+// batch's slabs), shape bucketing for mixed batches (ce_eval_batch), reference handles, the debug hooks.  Everything that
+// writes a slot of a batch is in ce_ingest.cpp, every call that takes host images and returns a result through scratch the
+// context owns in ce_leaf.cpp, resampling in ce_resample.cpp.  All device work is in the .hip files; there is no CPU compute
 // path here — if HIP is unavailable every entry point fails with CE_ERR_BACKEND.
 #include <algorithm>
 #include <atomic>
@@ -29,11 +30,9 @@ int ce_bad_length(ce_ctx *ctx, size_t want, size_t got)
     return ce_fail(ctx, CE_ERR_BAD_LENGTH, "Invalid image size: expected " + std::to_string(want) + " bytes, got " + std::to_string(got));
 }
 
-namespace {
-
 // validation order of calculate_ssimulacra2 / calculate_butteraugli
 // (src/metrics/ssimulacra2.rs:65-82, src/metrics/butteraugli.rs:51-67)
-int validate_pair(ce_ctx *ctx, size_t ref_len, size_t test_len, size_t w, size_t h)
+int ce_validate_pair(ce_ctx *ctx, size_t ref_len, size_t test_len, size_t w, size_t h)
 {
     if (ref_len != test_len)
         return ce_fail(ctx, CE_ERR_DIM_MISMATCH, "Dimension mismatch: reference " + std::to_string(ref_len) +
@@ -42,12 +41,24 @@ int validate_pair(ce_ctx *ctx, size_t ref_len, size_t test_len, size_t w, size_t
     return CE_OK;
 }
 
-constexpr uint32_t kKnownMetrics = CE_METRIC_DSSIM | CE_METRIC_SSIMULACRA2 | CE_METRIC_BUTTERAUGLI | CE_METRIC_PSNR;
+// A new device copy of a host table (ce_internal.h).  The context's table maps all fill through here: find; else build on
+// the host, copy, emplace.
+int ce_device_table(ce_ctx *ctx, const void *host, size_t bytes, const char *what, void **out)
+{
+    void *d = nullptr;
+    CE_HIP(ctx, hipMalloc(&d, bytes));
+    if (hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        hipFree(d);
+        return ce_fail(ctx, CE_ERR_BACKEND, std::string("H2D failed (") + what + ")");
+    }
+    *out = d;
+    return CE_OK;
+}
 
 // the argument checks of every map readout (what = "diffmap" / "SSIM map"): pairs [first, first + count) of the `stored`
 // ones of the last launch, block 1 or a power of two up to 64, and out_floats = count * ceil(w / B) * ceil(h / B) floats of
 // a w x h map (0 when there is no map output)
-int check_map_readout(ce_ctx *ctx, const char *what, uint32_t stored, uint32_t first, uint32_t count, uint32_t block, uint32_t w,
+static int check_map_readout(ce_ctx *ctx, const char *what, uint32_t stored, uint32_t first, uint32_t count, uint32_t block, uint32_t w,
                       uint32_t h, bool has_out, size_t out_floats)
 {
     if (count == 0 || first > stored || count > stored - first)
@@ -61,9 +72,9 @@ int check_map_readout(ce_ctx *ctx, const char *what, uint32_t stored, uint32_t f
     return CE_OK;
 }
 
-// the readouts of CE_FLAG_BUTTERAUGLI_DIFFMAP (ce_batch_butteraugli_diffmap, ce_ref_butteraugli_diffmap): checks, then the
-// device readout (butteraugli.hip)
-int read_diffmaps(ce_batch *b, uint32_t first, uint32_t count, uint32_t block, float *out, size_t out_floats)
+// the readouts of CE_FLAG_BUTTERAUGLI_DIFFMAP (also behind ce_ref_butteraugli_diffmap and ce_calculate_butteraugli_diffmap):
+// checks, then the device readout (butteraugli.hip)
+int ce_batch_butteraugli_diffmap(ce_batch *b, uint32_t first, uint32_t count, uint32_t block, float *out, size_t out_floats)
 {
     if (!b || !out) return CE_ERR_INVALID_ARG;
     ce_ctx *ctx = b->ctx;
@@ -74,10 +85,10 @@ int read_diffmaps(ce_batch *b, uint32_t first, uint32_t count, uint32_t block, f
     return ce_butteraugli_read_maps(b, first, count, block, out);
 }
 
-// the readouts of DSSIM's SsimMap (ce_batch_dssim_ssim_maps, ce_ref_dssim_ssim_maps): checks, then the device readout
-// (dssim.hip)
-int read_ssim_maps(ce_batch *b, uint32_t level, uint32_t first, uint32_t count, uint32_t block, float *maps, size_t maps_floats,
-                   double *ssim)
+// the readouts of DSSIM's SsimMap (also behind ce_ref_dssim_ssim_maps and ce_calculate_dssim_ssim_maps): checks, then the
+// device readout (dssim.hip)
+int ce_batch_dssim_ssim_maps(ce_batch *b, uint32_t level, uint32_t first, uint32_t count, uint32_t block, float *maps,
+                             size_t maps_floats, double *ssim)
 {
     if (!b || (!maps && !ssim)) return CE_ERR_INVALID_ARG;
     ce_ctx *ctx = b->ctx;
@@ -90,10 +101,11 @@ int read_ssim_maps(ce_batch *b, uint32_t level, uint32_t first, uint32_t count, 
     return ce_dssim_read_maps(b, level, first, count, block, maps, ssim);
 }
 
-// the readouts of SSIMULACRA2's maps and their norms (ce_batch_ssimulacra2_maps, ce_ref_ssimulacra2_maps): checks, then the
-// device readout (ssim2.hip).  Norms need a last launch with SSIMULACRA2, maps one with CE_FLAG_SSIMULACRA2_MAPS too.
-int read_ssim2_maps(ce_batch *b, uint32_t scale, uint32_t channel, uint32_t kind, uint32_t first, uint32_t count, uint32_t block,
-                    float *maps, size_t maps_floats, double *norms)
+// the readouts of SSIMULACRA2's maps and their norms (also behind ce_ref_ssimulacra2_maps and ce_calculate_ssimulacra2_maps):
+// checks, then the device readout (ssim2.hip).  Norms need a last launch with SSIMULACRA2, maps one with
+// CE_FLAG_SSIMULACRA2_MAPS too.
+int ce_batch_ssimulacra2_maps(ce_batch *b, uint32_t scale, uint32_t channel, uint32_t kind, uint32_t first, uint32_t count,
+                              uint32_t block, float *maps, size_t maps_floats, double *norms)
 {
     if (!b) return ce_fail(nullptr, CE_ERR_INVALID_ARG, "null handle");
     ce_ctx *ctx = b->ctx;
@@ -114,7 +126,7 @@ int read_ssim2_maps(ce_batch *b, uint32_t scale, uint32_t channel, uint32_t kind
     return ce_ssim2_read_maps(b, scale, channel, kind, first, count, block, maps, norms);
 }
 
-double psnr_from_sse(unsigned long long sse, size_t w, size_t h, double maxv = 255.0)
+static double psnr_from_sse(unsigned long long sse, size_t w, size_t h, double maxv = 255.0)
 {
     // src/metrics/mod.rs:317,324-330 (a deep batch: 255 replaced by its 2^depth - 1)
     const double pixel_count = (double)(w * h * 3);
@@ -125,7 +137,7 @@ double psnr_from_sse(unsigned long long sse, size_t w, size_t h, double maxv = 2
 
 // The sRGB -> linear table of a deep batch's side on the device: 2^depth entries by `rule` (0: ce_build_srgb_table_f64,
 // 1: ce_build_srgb_table_powf), built once per context and kept (ce_ctx::deep_tables).
-int ce_deep_table(ce_ctx *ctx, uint32_t depth, int rule, const float **out)
+static int ce_deep_table(ce_ctx *ctx, uint32_t depth, int rule, const float **out)
 {
     const auto key = std::make_pair(depth, rule);
     auto it = ctx->deep_tables.find(key);
@@ -133,19 +145,13 @@ int ce_deep_table(ce_ctx *ctx, uint32_t depth, int rule, const float **out)
         const uint32_t maxv = (1u << depth) - 1u;
         std::vector<float> host((size_t)maxv + 1);
         if (rule == 0) ce_build_srgb_table_f64(host.data(), maxv); else ce_build_srgb_table_powf(host.data(), maxv);
-        float *d = nullptr;
-        CE_HIP(ctx, hipMalloc(&d, host.size() * sizeof(float)));
-        if (hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            hipFree(d);
-            return ce_fail(ctx, CE_ERR_BACKEND, "H2D failed (deep sRGB table)");
-        }
-        it = ctx->deep_tables.emplace(key, d).first;
+        void *d = nullptr;
+        if (int rc = ce_device_table(ctx, host.data(), host.size() * sizeof(float), "deep sRGB table", &d)) return rc;
+        it = ctx->deep_tables.emplace(key, static_cast<float *>(d)).first;
     }
     *out = it->second;
     return CE_OK;
 }
-
-}  // namespace
 
 // ---- profiling -----------------------------------------------------------------------------
 
@@ -253,6 +259,34 @@ hipStream_t ce_ctx_aux_stream(ce_ctx *ctx, int which)
         }
     }
     return ctx->aux_stream[which];
+}
+
+// a failed call may leave copies from the caller's page-locked buffers queued: drain them before the buffers can go away
+void ce_drain_batch(ce_batch *b)
+{
+    hipStreamSynchronize(b->up_stream);
+    if (b->ctx->up2_stream) hipStreamSynchronize(b->ctx->up2_stream);
+    hipStreamSynchronize(b->ctx->stream);
+}
+
+// the device copies a table map of the context holds (ce_device_table made them), freed with the context
+static void *table_of(float *p) { return p; }
+static void *table_of(const ce_resample_axis &a) { return a.d; }
+template <class Map>
+static void free_tables(Map &m)
+{
+    for (auto &kv : m) hipFree(table_of(kv.second));
+    m.clear();
+}
+
+static bool hdr_depth_ok(uint32_t d) { return d == 10 || d == 12 || d == 16; }
+
+// HDR fidelity's two parameters, for ce_batch_hdr_fidelity and ce_eval_pair_hdr_fidelity (ce_leaf.cpp)
+int ce_hdr_params_check(ce_ctx *ctx, uint32_t depth, float white_nits)
+{
+    if (!hdr_depth_ok(depth)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: depth must be 10, 12 or 16, got " + std::to_string(depth));
+    if (!(white_nits > 0.0f && std::isfinite(white_nits))) return ce_fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: white_nits must be finite and > 0");
+    return CE_OK;
 }
 
 extern "C" {
@@ -390,18 +424,10 @@ void ce_ctx_destroy(ce_ctx *ctx)
     prof_drain(ctx);
     for (auto &kv : ctx->shape_pool) ce_batch_destroy(kv.second);
     ctx->shape_pool.clear();
-    ce_batch_destroy(ctx->leaf_map);
-    ctx->leaf_map = nullptr;
-    ce_batch_destroy(ctx->leaf_deep);
-    ctx->leaf_deep = nullptr;
-    ce_batch_destroy(ctx->leaf_linear);
-    ctx->leaf_linear = nullptr;
-    for (auto &kv : ctx->deep_tables) hipFree(kv.second);
-    ctx->deep_tables.clear();
-    for (auto &kv : ctx->cicp_tables) hipFree(kv.second);
-    ctx->cicp_tables.clear();
-    for (auto &kv : ctx->hdr_tables) hipFree(kv.second);
-    ctx->hdr_tables.clear();
+    for (ce_batch *&b : ctx->leaf_batch) ce_batch_destroy(b), b = nullptr;
+    free_tables(ctx->deep_tables);
+    free_tables(ctx->cicp_tables);
+    free_tables(ctx->hdr_tables);
     if (ctx->up2_stream) hipStreamSynchronize(ctx->up2_stream), hipStreamDestroy(ctx->up2_stream), hipEventDestroy(ctx->ev_up2);
     for (auto &st : ctx->aux_stream)  // after the last batch that may still drain them
         if (st) hipStreamSynchronize(st), hipStreamDestroy(st), st = nullptr;
@@ -414,10 +440,7 @@ void ce_ctx_destroy(ce_ctx *ctx)
     hipFree(ctx->heur_d);
     if (ctx->heur_h) hipHostFree(ctx->heur_h);
     hipFree(ctx->rs_mid);
-    for (auto &kv : ctx->rs_tables) hipFree(kv.second.d);
-    ctx->rs_tables.clear();
-    for (auto &kv : ctx->rs_tables_f64) hipFree(kv.second.d);
-    ctx->rs_tables_f64.clear();
+    free_tables(ctx->rs_tables);
     hipFree(ctx->d_lut_ssim2);
     hipFree(ctx->d_lut_powf);
     hipFree(ctx->d_xyb_thresh);
@@ -598,7 +621,7 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
     if (!b) return CE_ERR_INVALID_ARG;
     ce_ctx *ctx = b->ctx;
     if (n_pairs == 0 || n_pairs > b->max_pairs) return ce_fail(ctx, CE_ERR_INVALID_ARG, "n_pairs out of range");
-    if (metric_mask & ~kKnownMetrics) return ce_fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
+    if (metric_mask & ~ce_known_metrics) return ce_fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
     if (b->depth[0] && (flags & CE_FLAG_XYB_ROUNDTRIP))
         return ce_fail(ctx, CE_ERR_INVALID_ARG, "CE_FLAG_XYB_ROUNDTRIP quantises to 8 bits by definition: not for a deep batch");
     if (b->linear && (flags & CE_FLAG_XYB_ROUNDTRIP))
@@ -832,23 +855,6 @@ int ce_batch_butteraugli_pnorm3(ce_batch *b, uint32_t n_pairs, double *out)
     return CE_OK;
 }
 
-int ce_batch_butteraugli_diffmap(ce_batch *b, uint32_t first, uint32_t count, uint32_t block, float *out, size_t out_floats)
-{
-    return read_diffmaps(b, first, count, block, out, out_floats);
-}
-
-int ce_batch_dssim_ssim_maps(ce_batch *b, uint32_t level, uint32_t first, uint32_t count, uint32_t block, float *maps,
-                             size_t maps_floats, double *ssim)
-{
-    return read_ssim_maps(b, level, first, count, block, maps, maps_floats, ssim);
-}
-
-int ce_batch_ssimulacra2_maps(ce_batch *b, uint32_t scale, uint32_t channel, uint32_t kind, uint32_t first, uint32_t count,
-                              uint32_t block, float *maps, size_t maps_floats, double *norms)
-{
-    return read_ssim2_maps(b, scale, channel, kind, first, count, block, maps, maps_floats, norms);
-}
-
 int ce_batch_run(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_t flags, float intensity_target,
                  ce_scores *out)
 {
@@ -986,14 +992,6 @@ static int shape_batch(ce_ctx *ctx, uint32_t w, uint32_t h, uint32_t need_pairs,
     return CE_OK;
 }
 
-// a failed call may leave copies from the caller's page-locked buffers queued: drain them before the buffers can go away
-static void drain_batch(ce_batch *b)
-{
-    hipStreamSynchronize(b->up_stream);
-    if (b->ctx->up2_stream) hipStreamSynchronize(b->ctx->up2_stream);
-    hipStreamSynchronize(b->ctx->stream);
-}
-
 int ce_eval_batch(ce_ctx *ctx, size_t n, const ce_pair_desc *pairs, uint32_t metric_mask, uint32_t flags,
                   float intensity_target, ce_scores *out)
 {
@@ -1018,7 +1016,7 @@ int ce_eval_batch_lut(ce_ctx *ctx, size_t n, const ce_pair_desc *pairs, const ce
         const ce_pair_desc &d = pairs[i];
         int rc = (!d.reference || !d.test || d.width == 0 || d.height == 0)
                      ? CE_ERR_INVALID_ARG
-                     : validate_pair(ctx, d.reference_len, d.test_len, d.width, d.height);
+                     : ce_validate_pair(ctx, d.reference_len, d.test_len, d.width, d.height);
         if (rc != CE_OK) {
             out[i].status = rc;
             continue;
@@ -1029,7 +1027,7 @@ int ce_eval_batch_lut(ce_ctx *ctx, size_t n, const ce_pair_desc *pairs, const ce
     }
     if (buckets.empty()) return CE_OK;
     // what ce_batch_launch would reject is rejected before anything is uploaded
-    if (metric_mask & ~kKnownMetrics) return ce_fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
+    if (metric_mask & ~ce_known_metrics) return ce_fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
     static const size_t forced_chunks = [] {  // CE_EVAL_BATCH_CHUNKS (1..3) forces the chunk count for A/B runs
         const char *e = std::getenv("CE_EVAL_BATCH_CHUNKS");
         const int v = e ? std::atoi(e) : 0;
@@ -1098,279 +1096,11 @@ int ce_eval_batch_lut(ce_ctx *ctx, size_t n, const ce_pair_desc *pairs, const ce
             const int r = collect(c);
             if (rc == CE_OK) rc = r;
         }
-    if (rc != CE_OK && filling) drain_batch(filling);
+    if (rc != CE_OK && filling) ce_drain_batch(filling);
     return rc;
 }
 
-int ce_eval_pair(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test, size_t test_len,
-                 uint32_t width, uint32_t height, uint32_t metric_mask, uint32_t flags, float intensity_target,
-                 ce_scores *out)
-{
-    if (!ctx || !out || !reference || !test) return CE_ERR_INVALID_ARG;
-    ce_pair_desc d{reference, reference_len, test, test_len, width, height};
-    int rc = ce_eval_batch(ctx, 1, &d, metric_mask, flags, intensity_target, out);
-    if (rc != CE_OK) return rc;
-    return out->status;
-}
-
-// One pair of packed u16 RGB through the context's one-pair deep batch (kept while shape and depths stay the same).
-// Validation in ce_eval_pair's order: null pointers, empty image, length mismatch, wrong length; then the flags.
-int ce_eval_pair_deep(ce_ctx *ctx, const uint16_t *reference, size_t reference_len, uint32_t ref_depth, const uint16_t *test,
-                      size_t test_len, uint32_t test_depth, uint32_t width, uint32_t height, uint32_t metric_mask, uint32_t flags,
-                      float intensity_target, ce_scores *out)
-{
-    if (!ctx || !out || !reference || !test) return CE_ERR_INVALID_ARG;
-    *out = ce_scores{};
-    if (!ce_deep_depth_ok(ref_depth) || !ce_deep_depth_ok(test_depth))
-        return out->status = ce_fail(ctx, CE_ERR_INVALID_ARG, "depths must be 8, 10, 12 or 16 bits, got " + std::to_string(ref_depth) + " / " +
-                                                               std::to_string(test_depth));
-    if (width == 0 || height == 0) return out->status = CE_ERR_INVALID_ARG;
-    if (reference_len != test_len)
-        return out->status = ce_fail(ctx, CE_ERR_DIM_MISMATCH, "Dimension mismatch: reference " + std::to_string(reference_len) +
-                                                                " bytes, test " + std::to_string(test_len) + " bytes");
-    const size_t want = (size_t)width * height * 6;
-    if (reference_len != want) return out->status = ce_bad_length(ctx, want, reference_len);
-    if (flags & (CE_FLAG_BUTTERAUGLI_DIFFMAP | CE_FLAG_SSIMULACRA2_MAPS))
-        return out->status = ce_fail(ctx, CE_ERR_INVALID_ARG, "map flags need a ce_batch: this call's batch does not outlive it");
-    if (metric_mask & ~kKnownMetrics) return out->status = ce_fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
-    CE_HIP(ctx, hipSetDevice(ctx->device));
-    ce_batch *b = ctx->leaf_deep;
-    if (!b || b->w != width || b->h != height || b->depth[0] != ref_depth || b->depth[1] != test_depth) {
-        ce_batch_destroy(b);
-        ctx->leaf_deep = nullptr;
-        if (int rc = ce_batch_create_deep(ctx, width, height, 1, 1, ref_depth, test_depth, &ctx->leaf_deep)) return out->status = rc;
-        b = ctx->leaf_deep;
-    }
-    int rc = ce_batch_set_reference_fmt(b, 0, reference, reference_len, CE_PIXEL_RGB16);
-    if (rc == CE_OK) rc = ce_batch_set_test_fmt(b, 0, 0, test, test_len, CE_PIXEL_RGB16);
-    if (rc == CE_OK) rc = ce_batch_run(b, 1, metric_mask, flags, intensity_target, out);
-    if (rc != CE_OK) {
-        drain_batch(b);
-        return out->status = rc;
-    }
-    return out->status;
-}
-
-// One pair of packed f32 RGB through the context's one-pair linear batch (kept while the shape stays the same); validation
-// as ce_eval_pair_deep
-int ce_eval_pair_linear(ce_ctx *ctx, const float *reference, size_t reference_len, const float *test, size_t test_len, uint32_t width,
-                        uint32_t height, uint32_t metric_mask, uint32_t flags, float intensity_target, ce_scores *out)
-{
-    if (!ctx || !out || !reference || !test) return CE_ERR_INVALID_ARG;
-    *out = ce_scores{};
-    if (width == 0 || height == 0) return out->status = CE_ERR_INVALID_ARG;
-    if (reference_len != test_len)
-        return out->status = ce_fail(ctx, CE_ERR_DIM_MISMATCH, "Dimension mismatch: reference " + std::to_string(reference_len) +
-                                                                " bytes, test " + std::to_string(test_len) + " bytes");
-    const size_t want = (size_t)width * height * 12;
-    if (reference_len != want) return out->status = ce_bad_length(ctx, want, reference_len);
-    if (flags & (CE_FLAG_BUTTERAUGLI_DIFFMAP | CE_FLAG_SSIMULACRA2_MAPS))
-        return out->status = ce_fail(ctx, CE_ERR_INVALID_ARG, "map flags need a ce_batch: this call's batch does not outlive it");
-    if (metric_mask & ~kKnownMetrics) return out->status = ce_fail(ctx, CE_ERR_INVALID_ARG, "unknown metric bit");
-    CE_HIP(ctx, hipSetDevice(ctx->device));
-    ce_batch *b = ctx->leaf_linear;
-    if (!b || b->w != width || b->h != height) {
-        ce_batch_destroy(b);
-        ctx->leaf_linear = nullptr;
-        if (int rc = ce_batch_create_linear(ctx, width, height, 1, 1, &ctx->leaf_linear)) return out->status = rc;
-        b = ctx->leaf_linear;
-    }
-    int rc = ce_batch_set_reference_fmt(b, 0, reference, reference_len, CE_PIXEL_RGB_F32);
-    if (rc == CE_OK) rc = ce_batch_set_test_fmt(b, 0, 0, test, test_len, CE_PIXEL_RGB_F32);
-    if (rc == CE_OK) rc = ce_batch_run(b, 1, metric_mask, flags, intensity_target, out);
-    if (rc != CE_OK) {
-        drain_batch(b);
-        return out->status = rc;
-    }
-    return out->status;
-}
-
-static int leaf(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test, size_t test_len,
-                size_t width, size_t height, uint32_t metric, float intensity, double *out)
-{
-    if (!ctx || !out) return CE_ERR_INVALID_ARG;
-    ce_scores s{};
-    int rc = ce_eval_pair(ctx, reference, reference_len, test, test_len, (uint32_t)width, (uint32_t)height, metric, 0,
-                          intensity, &s);
-    if (rc != CE_OK) return rc;
-    *out = metric == CE_METRIC_PSNR          ? s.psnr
-           : metric == CE_METRIC_SSIMULACRA2 ? s.ssimulacra2
-           : metric == CE_METRIC_DSSIM       ? s.dssim
-                                             : s.butteraugli;
-    return CE_OK;
-}
-
-int ce_calculate_psnr(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test,
-                      size_t test_len, size_t width, size_t height, double *out)
-{
-    return leaf(ctx, reference, reference_len, test, test_len, width, height, CE_METRIC_PSNR, 0.f, out);
-}
-
-int ce_calculate_ssimulacra2(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test,
-                             size_t test_len, size_t width, size_t height, double *out)
-{
-    return leaf(ctx, reference, reference_len, test, test_len, width, height, CE_METRIC_SSIMULACRA2, 0.f, out);
-}
-
-int ce_calculate_dssim(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test,
-                       size_t test_len, size_t width, size_t height, double *out)
-{
-    return leaf(ctx, reference, reference_len, test, test_len, width, height, CE_METRIC_DSSIM, 0.f, out);
-}
-
-int ce_calculate_butteraugli(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test,
-                             size_t test_len, size_t width, size_t height, float intensity_target, double *out)
-{
-    return leaf(ctx, reference, reference_len, test, test_len, width, height, CE_METRIC_BUTTERAUGLI, intensity_target,
-                out);
-}
-
-// The one-pair map calls (ce_calculate_butteraugli_diffmap, ce_calculate_dssim_ssim_maps): the pair through a one-pair batch
-// of the context, kept while the shape stays the same (not the pooled ce_eval_batch batches, whose next call reuses them);
-// *out_b is that batch, with the maps of this run.  The caller has checked the arguments.
-static int leaf_map_run(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test, size_t test_len, size_t width,
-                        size_t height, uint32_t metric, uint32_t flags, float intensity_target, ce_scores *s, ce_batch **out_b)
-{
-    CE_HIP(ctx, hipSetDevice(ctx->device));
-    ce_batch *b = ctx->leaf_map;
-    if (!b || b->w != width || b->h != height) {
-        ce_batch_destroy(b);
-        ctx->leaf_map = nullptr;
-        if (int rc = ce_batch_create(ctx, (uint32_t)width, (uint32_t)height, 1, 1, &ctx->leaf_map)) return rc;
-        b = ctx->leaf_map;
-    }
-    b->caller_blocks = true;  // collected before return: page-locked images are read in place (upload())
-    int rc = ce_batch_set_reference(b, 0, reference, reference_len);
-    if (rc == CE_OK) rc = ce_batch_set_test(b, 0, 0, test, test_len);
-    if (rc == CE_OK) rc = ce_batch_run(b, 1, metric, flags, intensity_target, s);
-    if (rc != CE_OK) drain_batch(b);
-    b->caller_blocks = false;
-    if (rc != CE_OK) return rc;
-    *out_b = b;
-    return s->status;
-}
-
-int ce_calculate_butteraugli_diffmap(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test,
-                                     size_t test_len, size_t width, size_t height, float intensity_target, double *score,
-                                     float *diffmap_out)
-{
-    if (!ctx || !reference || !test || !score || !diffmap_out) return CE_ERR_INVALID_ARG;
-    if (int rc = validate_pair(ctx, reference_len, test_len, width, height)) return rc;
-    if (width < 8 || height < 8) return ce_fail(ctx, CE_ERR_TOO_SMALL, "minimum 8x8 for butteraugli");  // src/eval/helpers.rs:89
-    if (width > UINT32_MAX || height > UINT32_MAX) return ce_fail(ctx, CE_ERR_INVALID_ARG, "image too large");
-    ce_scores s{};
-    ce_batch *b = nullptr;
-    if (int rc = leaf_map_run(ctx, reference, reference_len, test, test_len, width, height, CE_METRIC_BUTTERAUGLI,
-                              CE_FLAG_BUTTERAUGLI_DIFFMAP, intensity_target, &s, &b))
-        return rc;
-    if (int r = read_diffmaps(b, 0, 1, 1, diffmap_out, width * height)) return r;
-    *score = s.butteraugli;
-    return CE_OK;
-}
-
-int ce_calculate_dssim_ssim_maps(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test, size_t test_len,
-                                 size_t width, size_t height, double *dssim, double *level_ssim, float *maps, size_t maps_floats)
-{
-    if (!ctx || !reference || !test || !dssim || !level_ssim || !maps) return CE_ERR_INVALID_ARG;
-    if (width == 0 || height == 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, "empty image");  // ce_calculate_dssim's order
-    if (int rc = validate_pair(ctx, reference_len, test_len, width, height)) return rc;
-    if (width > UINT32_MAX || height > UINT32_MAX) return ce_fail(ctx, CE_ERR_INVALID_ARG, "image too large");
-    uint32_t lw[CE_DSSIM_MAX_LEVELS], lh[CE_DSSIM_MAX_LEVELS];
-    const uint32_t n = ce_plan_dssim_levels((uint32_t)width, (uint32_t)height, CE_DSSIM_MAX_LEVELS, lw, lh);
-    size_t want = 0;
-    for (uint32_t l = 0; l < n; l++) want += (size_t)lw[l] * lh[l];
-    if (maps_floats != want)
-        return ce_fail(ctx, CE_ERR_INVALID_ARG, "SSIM maps of every level need " + std::to_string(want) + " floats, got " + std::to_string(maps_floats));
-    ce_scores s{};
-    ce_batch *b = nullptr;
-    if (int rc = leaf_map_run(ctx, reference, reference_len, test, test_len, width, height, CE_METRIC_DSSIM, 0, 0.0f, &s, &b))
-        return rc;
-    size_t off = 0;
-    for (uint32_t l = 0; l < CE_DSSIM_MAX_LEVELS; l++) {
-        level_ssim[l] = NAN;
-        if (l >= n) continue;
-        if (int r = read_ssim_maps(b, l, 0, 1, 1, maps + off, (size_t)lw[l] * lh[l], &level_ssim[l])) return r;
-        off += (size_t)lw[l] * lh[l];
-    }
-    *dssim = s.dssim;
-    return CE_OK;
-}
-
-int ce_calculate_ssimulacra2_maps(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test, size_t test_len,
-                                  size_t width, size_t height, double *score, double *features, float *maps, size_t maps_floats)
-{
-    if (!ctx || !reference || !test || !score || !features || !maps) return CE_ERR_INVALID_ARG;
-    if (width == 0 || height == 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, "empty image");  // ce_calculate_ssimulacra2's order
-    if (int rc = validate_pair(ctx, reference_len, test_len, width, height)) return rc;
-    if (width > UINT32_MAX || height > UINT32_MAX) return ce_fail(ctx, CE_ERR_INVALID_ARG, "image too large");
-    if (width < 8 || height < 8) return ce_fail(ctx, CE_ERR_TOO_SMALL, "minimum 8x8 for ssimulacra2");
-    uint32_t sw[CE_SSIM2_MAX_SCALES], sh[CE_SSIM2_MAX_SCALES];
-    const uint32_t n = ce_plan_ssim2_scales((uint32_t)width, (uint32_t)height, CE_SSIM2_MAX_SCALES, sw, sh);
-    size_t want = 0;
-    for (uint32_t s = 0; s < n; s++) want += 9 * (size_t)sw[s] * sh[s];
-    if (maps_floats != want)
-        return ce_fail(ctx, CE_ERR_INVALID_ARG, "SSIMULACRA2 maps of every scale need " + std::to_string(want) + " floats, got " + std::to_string(maps_floats));
-    ce_scores s{};
-    ce_batch *b = nullptr;
-    if (int rc = leaf_map_run(ctx, reference, reference_len, test, test_len, width, height, CE_METRIC_SSIMULACRA2,
-                              CE_FLAG_SSIMULACRA2_MAPS, 0.0f, &s, &b))
-        return rc;
-    double avg[CE_SSIM2_MAX_SCALES * 18];
-    CE_HIP(ctx, hipMemcpyAsync(avg, b->d_avg, sizeof(avg), hipMemcpyDeviceToHost, ctx->stream));
-    CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (uint32_t i = 0; i < CE_SSIM2_MAX_SCALES * 18; i++) features[i] = i < b->s2_scales_run * 18 ? avg[i] : NAN;
-    size_t off = 0;
-    for (uint32_t sc = 0; sc < b->s2_scales_run; sc++)
-        for (uint32_t c = 0; c < 3; c++)
-            for (uint32_t k = 0; k < 3; k++) {
-                const size_t np = (size_t)sw[sc] * sh[sc];
-                if (int r = read_ssim2_maps(b, sc, c, k, 0, 1, 1, maps + off, np, nullptr)) return r;
-                off += np;
-            }
-    *score = s.ssimulacra2;
-    return CE_OK;
-}
-
-int ce_xyb_roundtrip(ce_ctx *ctx, const uint8_t *rgb, size_t rgb_len, size_t width, size_t height, uint8_t *out)
-{
-    if (!ctx || !rgb || !out) return CE_ERR_INVALID_ARG;
-    if (rgb_len != width * height * 3)
-        return ce_fail(ctx, CE_ERR_BAD_LENGTH, "Buffer size mismatch");  // xyb.rs:227
-    if (rgb_len == 0) return CE_OK;
-    return ce_leaf_roundtrip(ctx, rgb, rgb_len, out, rgb_len,
-                          [&](uint8_t *d_in, uint8_t *d_out) { return ce_launch_xyb_roundtrip(ctx, d_in, d_out, width * height); });
-}
-
-int ce_rgb8_to_dssim_image(ce_ctx *ctx, const uint8_t *rgb, size_t rgb_len, size_t width, size_t height,
-                           float *rgba_out)
-{
-    if (!ctx || !rgb || !rgba_out) return CE_ERR_INVALID_ARG;
-    if (rgb_len != width * height * 3) return ce_fail(ctx, CE_ERR_BAD_LENGTH, "Buffer size mismatch");
-    const size_t n = width * height;
-    if (n == 0) return CE_OK;
-    return ce_leaf_roundtrip(ctx, rgb, rgb_len, rgba_out, n * 4 * sizeof(float), [&](uint8_t *d_in, uint8_t *d_out) {
-        return ce_launch_rgb8_to_dssim_image(ctx, d_in, reinterpret_cast<float *>(d_out), n);
-    });
-}
-
 // ---- image heuristics (heuristics.hip) ---------------------------------------------------------
-
-int ce_image_heuristics_rgb8(ce_ctx *ctx, const uint8_t *rgb, size_t len, size_t width, size_t height, ce_image_heuristics *out)
-{
-    if (!ctx || !rgb || !out) return CE_ERR_INVALID_ARG;
-    if (width > UINT32_MAX || height > UINT32_MAX || (height && width > SIZE_MAX / 3 / height))
-        return ce_fail(ctx, CE_ERR_INVALID_ARG, "image heuristics: image dimensions out of range");
-    if (len != width * height * 3) return ce_bad_length(ctx, width * height * 3, len);
-    if (width < 3 || height < 3)
-        return ce_fail(ctx, CE_ERR_TOO_SMALL, "image heuristics need at least 3 x 3 pixels, got " + std::to_string(width) + " x " +
-                                               std::to_string(height));
-    int rc = ce_leaf_scratch(ctx, len, 0);
-    if (rc != CE_OK) return rc;
-    std::memcpy(ctx->leaf_h, rgb, len);
-    const hipError_t e = hipMemcpyAsync(ctx->leaf_d_in, ctx->leaf_h, len, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return ce_fail(ctx, CE_ERR_BACKEND, std::string("image heuristics upload: ") + hipGetErrorString(e));
-    return ce_image_heuristics_run(ctx, ctx->leaf_d_in, len, (uint32_t)width, (uint32_t)height, 1, out);
-}
 
 int ce_batch_image_heuristics(ce_batch *b, uint32_t which, uint32_t first, uint32_t count, ce_image_heuristics *out)
 {
@@ -1397,7 +1127,6 @@ int ce_batch_image_heuristics(ce_batch *b, uint32_t which, uint32_t first, uint3
 }
 
 // ---- HDR fidelity of linear batches: PQ-PSNR and BT.2124 Delta E ITP (hdr_fidelity.hip) ----------
-static bool hdr_depth_ok(uint32_t d) { return d == 10 || d == 12 || d == 16; }
 
 int ce_pq_code_thresholds(uint32_t depth, float white_nits, float *out, size_t n)
 {
@@ -1429,23 +1158,12 @@ static int hdr_table_dev(ce_ctx *ctx, uint32_t depth, float white_nits, const fl
         ce_build_pq_code_thresholds((uint32_t)n, (double)white_nits, host.data());
         const size_t stride = (size_t)1 << (depth > 12 ? depth - 12 : 0);
         for (size_t j = 0; j < n_coarse; j++) host[padded + j] = host[(j + 1) * stride - 1];
-        float *d = nullptr;
-        CE_HIP(ctx, hipMalloc(&d, host.size() * sizeof(float)));
-        if (hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            hipFree(d);
-            return ce_fail(ctx, CE_ERR_BACKEND, "H2D failed (PQ code thresholds)");
-        }
-        it = ctx->hdr_tables.emplace(key, d).first;
+        void *d = nullptr;
+        if (int rc = ce_device_table(ctx, host.data(), host.size() * sizeof(float), "PQ code thresholds", &d)) return rc;
+        it = ctx->hdr_tables.emplace(key, static_cast<float *>(d)).first;
     }
     *table = it->second;
     *coarse = n_coarse ? it->second + padded : it->second;
-    return CE_OK;
-}
-
-static int hdr_params_check(ce_ctx *ctx, uint32_t depth, float white_nits)
-{
-    if (!hdr_depth_ok(depth)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: depth must be 10, 12 or 16, got " + std::to_string(depth));
-    if (!(white_nits > 0.0f && std::isfinite(white_nits))) return ce_fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: white_nits must be finite and > 0");
     return CE_OK;
 }
 
@@ -1456,7 +1174,7 @@ int ce_batch_hdr_fidelity(ce_batch *b, uint32_t n_pairs, uint32_t depth, float w
     if (!out) return ce_fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: null pointer");
     if (!b->linear)
         return ce_fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity reads linear light: it needs a linear batch (ce_batch_create_linear)");
-    if (int rc = hdr_params_check(ctx, depth, white_nits)) return rc;
+    if (int rc = ce_hdr_params_check(ctx, depth, white_nits)) return rc;
     if (n_pairs == 0 || n_pairs > b->max_pairs) return ce_fail(ctx, CE_ERR_INVALID_ARG, "n_pairs out of range");
     CE_HIP(ctx, hipSetDevice(ctx->device));
     const float *d_table = nullptr, *d_coarse = nullptr;
@@ -1480,244 +1198,6 @@ int ce_batch_hdr_fidelity(ce_batch *b, uint32_t n_pairs, uint32_t depth, float w
         s.delta_e_itp_max = (double)s.itp_max_q20 / 1048576.0;
         out[i] = s;
     }
-    return CE_OK;
-}
-
-// One pair of packed f32 RGB through the context's one-pair linear batch, as ce_eval_pair_linear
-int ce_eval_pair_hdr_fidelity(ce_ctx *ctx, const float *reference, size_t reference_len, const float *test, size_t test_len, uint32_t width,
-                              uint32_t height, uint32_t depth, float white_nits, ce_hdr_scores *out)
-{
-    if (!ctx) return CE_ERR_INVALID_ARG;
-    if (!out || !reference || !test) return ce_fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: null pointer");
-    *out = ce_hdr_scores{};
-    if (width == 0 || height == 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, "HDR fidelity: empty image");
-    if (int rc = hdr_params_check(ctx, depth, white_nits)) return rc;
-    const size_t want = (size_t)width * height * 12;
-    if (reference_len != want) return ce_bad_length(ctx, want, reference_len);
-    if (test_len != want) return ce_bad_length(ctx, want, test_len);
-    CE_HIP(ctx, hipSetDevice(ctx->device));
-    ce_batch *b = ctx->leaf_linear;
-    if (!b || b->w != width || b->h != height) {
-        ce_batch_destroy(b);
-        ctx->leaf_linear = nullptr;
-        if (int rc = ce_batch_create_linear(ctx, width, height, 1, 1, &ctx->leaf_linear)) return rc;
-        b = ctx->leaf_linear;
-    }
-    int rc = ce_batch_set_reference_fmt(b, 0, reference, reference_len, CE_PIXEL_RGB_F32);
-    if (rc == CE_OK) rc = ce_batch_set_test_fmt(b, 0, 0, test, test_len, CE_PIXEL_RGB_F32);
-    if (rc == CE_OK) rc = ce_batch_hdr_fidelity(b, 1, depth, white_nits, out);
-    if (rc != CE_OK) drain_batch(b);
-    return rc;
-}
-
-// ---- viewing simulation: resampling (resample.hip) ----------------------------------------------
-
-// the taps of one axis on the device, built on first use and kept with the context (ce_ctx::rs_tables)
-static int resample_table(ce_ctx *ctx, uint32_t n_in, uint32_t n_out, int filter, const ce_resample_axis **out)
-{
-    const auto key = std::make_tuple(n_in, n_out, filter);
-    auto it = ctx->rs_tables.find(key);
-    if (it == ctx->rs_tables.end()) {
-        std::vector<int32_t> host;
-        ce_resample_axis a;
-        a.n_in = n_in, a.n_out = n_out;
-        if (!ce_build_resample_table(n_in, n_out, filter, host, &a.ksize)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: bad axis");
-        CE_HIP(ctx, hipMalloc((void **)&a.d, host.size() * sizeof(int32_t)));
-        if (hipMemcpy(a.d, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
-            hipFree(a.d);
-            return ce_fail(ctx, CE_ERR_BACKEND, "H2D failed (resample taps)");
-        }
-        it = ctx->rs_tables.emplace(key, a).first;
-    }
-    *out = &it->second;
-    return CE_OK;
-}
-
-// the same for the float resampler (ce_ctx::rs_tables_f64)
-static int resample_table_f64(ce_ctx *ctx, uint32_t n_in, uint32_t n_out, int filter, const ce_resample_axis_f64 **out)
-{
-    const auto key = std::make_tuple(n_in, n_out, filter);
-    auto it = ctx->rs_tables_f64.find(key);
-    if (it == ctx->rs_tables_f64.end()) {
-        std::vector<double> host;
-        ce_resample_axis_f64 a;
-        a.n_in = n_in, a.n_out = n_out;
-        if (!ce_build_resample_table_f64(n_in, n_out, filter, host, &a.ksize)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: bad axis");
-        CE_HIP(ctx, hipMalloc((void **)&a.d, host.size() * sizeof(double)));
-        if (hipMemcpy(a.d, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-            hipFree(a.d);
-            return ce_fail(ctx, CE_ERR_BACKEND, "H2D failed (resample taps)");
-        }
-        it = ctx->rs_tables_f64.emplace(key, a).first;
-    }
-    *out = &it->second;
-    return CE_OK;
-}
-
-static bool resample_filter_ok(int filter) { return filter >= CE_RESAMPLE_BOX && filter <= CE_RESAMPLE_LANCZOS3; }
-
-// the image between the two passes: at least `need` bytes of ce_ctx::rs_mid
-static int resample_mid(ce_ctx *ctx, size_t need)
-{
-    if (ctx->rs_mid_cap < need) {
-        CE_HIP(ctx, hipStreamSynchronize(ctx->stream));  // an earlier resample may still be between its passes
-        CE_HIP(ctx, hipFree(ctx->rs_mid));
-        ctx->rs_mid = nullptr;
-        ctx->rs_mid_cap = 0;
-        CE_HIP(ctx, hipMalloc((void **)&ctx->rs_mid, need + need / 4));
-        ctx->rs_mid_cap = need + need / 4;
-    }
-    return CE_OK;
-}
-
-// n images of w x h at d_src (src_stride apart) to out_w x out_h at d_dst, queued on the context's stream
-static int resample_images(ce_ctx *ctx, const uint8_t *d_src, size_t src_stride, uint8_t *d_dst, size_t dst_stride, uint32_t w, uint32_t h,
-                           uint32_t out_w, uint32_t out_h, uint32_t n, int filter)
-{
-    if (w == out_w && h == out_h) {  // no pass changes a size: the bytes themselves
-        const size_t img = (size_t)w * h * 3;
-        if (src_stride == img && dst_stride == img) {
-            CE_HIP(ctx, hipMemcpyAsync(d_dst, d_src, img * n, hipMemcpyDeviceToDevice, ctx->stream));
-        } else {
-            for (uint32_t i = 0; i < n; i++)
-                CE_HIP(ctx, hipMemcpyAsync(d_dst + i * dst_stride, d_src + i * src_stride, img, hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        return CE_OK;
-    }
-    const ce_resample_axis *horiz = nullptr, *vert = nullptr;
-    if (w != out_w)
-        if (int rc = resample_table(ctx, w, out_w, filter, &horiz)) return rc;
-    if (h != out_h)
-        if (int rc = resample_table(ctx, h, out_h, filter, &vert)) return rc;
-    if (horiz && vert)
-        if (int rc = resample_mid(ctx, (size_t)n * h * out_w * 3)) return rc;
-    return ce_launch_resample(ctx, ctx->stream, d_src, src_stride, d_dst, dst_stride, w, h, out_w, out_h, n, horiz, vert, ctx->rs_mid);
-}
-
-// the same for packed f32 RGB (strides in bytes, multiples of 4): resample_f32.hip; equal sizes are a byte copy, unclamped
-static int resample_images_linear(ce_ctx *ctx, const uint8_t *d_src, size_t src_stride, uint8_t *d_dst, size_t dst_stride, uint32_t w,
-                                  uint32_t h, uint32_t out_w, uint32_t out_h, uint32_t n, int filter)
-{
-    if (w == out_w && h == out_h) {
-        const size_t img = (size_t)w * h * 12;
-        if (src_stride == img && dst_stride == img) {
-            CE_HIP(ctx, hipMemcpyAsync(d_dst, d_src, img * n, hipMemcpyDeviceToDevice, ctx->stream));
-        } else {
-            for (uint32_t i = 0; i < n; i++)
-                CE_HIP(ctx, hipMemcpyAsync(d_dst + i * dst_stride, d_src + i * src_stride, img, hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        return CE_OK;
-    }
-    const ce_resample_axis_f64 *horiz = nullptr, *vert = nullptr;
-    if (w != out_w)
-        if (int rc = resample_table_f64(ctx, w, out_w, filter, &horiz)) return rc;
-    if (h != out_h)
-        if (int rc = resample_table_f64(ctx, h, out_h, filter, &vert)) return rc;
-    if (horiz && vert)
-        if (int rc = resample_mid(ctx, (size_t)n * h * out_w * 12)) return rc;
-    return ce_launch_resample_f32(ctx, ctx->stream, reinterpret_cast<const float *>(d_src), src_stride / 4, reinterpret_cast<float *>(d_dst),
-                                  dst_stride / 4, w, h, out_w, out_h, n, horiz, vert, reinterpret_cast<float *>(ctx->rs_mid));
-}
-
-int ce_resample_rgb8(ce_ctx *ctx, const uint8_t *rgb, size_t len, uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h, int filter,
-                     uint8_t *out, size_t out_len)
-{
-    if (!ctx || !rgb || !out) return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: null pointer");
-    if (!resample_filter_ok(filter)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: unknown filter " + std::to_string(filter));
-    if (w == 0 || h == 0 || out_w == 0 || out_h == 0)
-        return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: " + std::to_string(w) + " x " + std::to_string(h) + " to " + std::to_string(out_w) +
-                                                 " x " + std::to_string(out_h) + " has an empty side");
-    const size_t want_in = (size_t)w * h * 3, want_out = (size_t)out_w * out_h * 3;
-    if (len != want_in) return ce_bad_length(ctx, want_in, len);
-    if (out_len != want_out) return ce_bad_length(ctx, want_out, out_len);
-    return ce_leaf_roundtrip(ctx, rgb, len, out, out_len, [&](uint8_t *d_in, uint8_t *d_out) {
-        return resample_images(ctx, d_in, want_in, d_out, want_out, w, h, out_w, out_h, 1, filter);
-    });
-}
-
-int ce_resample_linear(ce_ctx *ctx, const float *rgb, size_t len, uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h, int filter, float *out,
-                       size_t out_len)
-{
-    if (!ctx || !rgb || !out) return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: null pointer");
-    if (!resample_filter_ok(filter)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: unknown filter " + std::to_string(filter));
-    if (w == 0 || h == 0 || out_w == 0 || out_h == 0)
-        return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: " + std::to_string(w) + " x " + std::to_string(h) + " to " + std::to_string(out_w) +
-                                                 " x " + std::to_string(out_h) + " has an empty side");
-    const size_t want_in = (size_t)w * h * 12, want_out = (size_t)out_w * out_h * 12;
-    if (len != want_in) return ce_bad_length(ctx, want_in, len);
-    if (out_len != want_out) return ce_bad_length(ctx, want_out, out_len);
-    return ce_leaf_roundtrip(ctx, rgb, len, out, out_len, [&](uint8_t *d_in, uint8_t *d_out) {
-        return resample_images_linear(ctx, d_in, want_in, d_out, want_out, w, h, out_w, out_h, 1, filter);
-    });
-}
-
-// the checks two batches must pass before anything moves between them
-static int resample_check(ce_batch *src, ce_batch *dst, int filter)
-{
-    if (!src || !dst) return ce_fail(src ? src->ctx : dst ? dst->ctx : nullptr, CE_ERR_INVALID_ARG, "resample: null batch");
-    ce_ctx *ctx = src->ctx;
-    if (dst->ctx != ctx) return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: the two batches belong to different contexts");
-    if (src == dst) return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: source and destination are the same batch");
-    if (!resample_filter_ok(filter)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: unknown filter " + std::to_string(filter));
-    if (src->depth[0] || dst->depth[0])
-        return ce_fail(ctx, CE_ERR_INVALID_ARG, src->linear || dst->linear
-                                                 ? "resample: a linear batch resamples into a linear batch only, and a deep batch is out of its scope"
-                                                 : "resample works on RGB8 and linear batches: a deep batch is out of its scope");
-    if (src->linear != dst->linear)
-        return ce_fail(ctx, CE_ERR_INVALID_ARG, "resample: a linear batch resamples into a linear batch only, an RGB8 batch into an RGB8 one");
-    return CE_OK;
-}
-
-static int resample_slab(ce_batch *src, ce_batch *dst, uint32_t which, uint32_t first, uint32_t count, int filter)
-{
-    ce_ctx *ctx = src->ctx;
-    const bool tests = which == CE_BATCH_TESTS;
-    CE_HIP(ctx, hipSetDevice(ctx->device));
-    // the kernels run on the context's stream: behind src's uploads (the ordering of a launch), and as an inline write of
-    // dst (ce_order_write: behind dst's own uploads, ahead of its next launch and of its later uploads)
-    if (int rc = ce_flush_uploads(src)) return rc;
-    if (int rc = ce_order_write(dst, true)) return rc;
-    if (!tests) ce_invalidate_reference_state(dst);
-    const uint8_t *s = (tests ? src->d_tests : src->d_refs) + (size_t)first * src->img_bytes;
-    uint8_t *d = (tests ? dst->d_tests : dst->d_refs) + (size_t)first * dst->img_bytes;
-    const int rc = (src->linear ? resample_images_linear : resample_images)(ctx, s, src->img_bytes, d, dst->img_bytes, src->w, src->h, dst->w,
-                                                                            dst->h, count, filter);
-    src->inline_pending = true;  // a later upload into src waits for these reads (ce_order_write)
-    return rc;
-}
-
-static int resample_range_check(ce_batch *src, ce_batch *dst, bool tests, uint32_t first, uint32_t count)
-{
-    const uint32_t slots = tests ? std::min(src->max_pairs, dst->max_pairs) : std::min(src->max_refs, dst->max_refs);
-    if (count == 0 || first > slots || count > slots - first)
-        return ce_fail(src->ctx, CE_ERR_INVALID_ARG, std::string("resample: ") + (tests ? "tests [" : "references [") + std::to_string(first) + ", " +
-                                                      std::to_string((uint64_t)first + count) + ") outside the " + std::to_string(slots) +
-                                                      " slots both batches have");
-    return CE_OK;
-}
-
-int ce_batch_resample(ce_batch *src, ce_batch *dst, uint32_t which, uint32_t first, uint32_t count, int filter)
-{
-    if (int rc = resample_check(src, dst, filter)) return rc;
-    if (which != CE_BATCH_REFERENCES && which != CE_BATCH_TESTS)
-        return ce_fail(src->ctx, CE_ERR_INVALID_ARG, "resample: unknown slab " + std::to_string(which));
-    if (int rc = resample_range_check(src, dst, which == CE_BATCH_TESTS, first, count)) return rc;
-    return resample_slab(src, dst, which, first, count, filter);
-}
-
-int ce_batch_resample_pairs(ce_batch *src, ce_batch *dst, uint32_t n_refs, uint32_t n_pairs, int filter)
-{
-    if (int rc = resample_check(src, dst, filter)) return rc;
-    if (int rc = resample_range_check(src, dst, false, 0, n_refs)) return rc;
-    if (int rc = resample_range_check(src, dst, true, 0, n_pairs)) return rc;
-    for (uint32_t i = 0; i < n_pairs; i++)
-        if (src->h_pair_ref[i] >= n_refs)
-            return ce_fail(src->ctx, CE_ERR_INVALID_ARG, "resample: pair " + std::to_string(i) + " is bound to reference " +
-                                                          std::to_string(src->h_pair_ref[i]) + ", outside the " + std::to_string(n_refs) + " resampled");
-    if (int rc = resample_slab(src, dst, CE_BATCH_REFERENCES, 0, n_refs, filter)) return rc;
-    if (int rc = resample_slab(src, dst, CE_BATCH_TESTS, 0, n_pairs, filter)) return rc;
-    for (uint32_t i = 0; i < n_pairs; i++)
-        if (int rc = ce_batch_bind_pair(dst, i, src->h_pair_ref[i])) return rc;
     return CE_OK;
 }
 
@@ -1789,7 +1269,7 @@ int ce_ref_compare_many(ce_ref *ref, const uint8_t *const *tests, const size_t *
     for (uint32_t i = 0; i < n_tests && rc == CE_OK; i++)
         rc = out[i].status != CE_OK ? ce_batch_bind_pair(b, i, 0) : ce_batch_set_test(b, i, 0, tests[i], test_lens[i]);
     if (rc == CE_OK) rc = ce_batch_run(b, n_tests, metric_mask, ref->flags, intensity_target, tmp.data());
-    if (rc != CE_OK) drain_batch(b);  // copies straight from the caller's memory may still be queued
+    if (rc != CE_OK) ce_drain_batch(b);  // copies straight from the caller's memory may still be queued
     b->caller_blocks = false;
     if (rc != CE_OK) return rc;
     for (uint32_t i = 0; i < n_tests; i++)
@@ -1809,21 +1289,21 @@ int ce_ref_compare(ce_ref *ref, const uint8_t *test, size_t test_len, uint32_t m
 int ce_ref_butteraugli_diffmap(ce_ref *ref, uint32_t first, uint32_t count, uint32_t block, float *out, size_t out_floats)
 {
     if (!ref) return CE_ERR_INVALID_ARG;
-    return read_diffmaps(ref->batch, first, count, block, out, out_floats);  // the handle's current batch (compare_many may replace it)
+    return ce_batch_butteraugli_diffmap(ref->batch, first, count, block, out, out_floats);  // the handle's current batch (compare_many may replace it)
 }
 
 int ce_ref_dssim_ssim_maps(ce_ref *ref, uint32_t level, uint32_t first, uint32_t count, uint32_t block, float *maps,
                            size_t maps_floats, double *ssim)
 {
     if (!ref) return CE_ERR_INVALID_ARG;
-    return read_ssim_maps(ref->batch, level, first, count, block, maps, maps_floats, ssim);  // the handle's current batch
+    return ce_batch_dssim_ssim_maps(ref->batch, level, first, count, block, maps, maps_floats, ssim);  // the handle's current batch
 }
 
 int ce_ref_ssimulacra2_maps(ce_ref *ref, uint32_t scale, uint32_t channel, uint32_t kind, uint32_t first, uint32_t count, uint32_t block,
                             float *maps, size_t maps_floats, double *norms)
 {
     if (!ref) return ce_fail(nullptr, CE_ERR_INVALID_ARG, "null handle");
-    return read_ssim2_maps(ref->batch, scale, channel, kind, first, count, block, maps, maps_floats, norms);  // the handle's current batch
+    return ce_batch_ssimulacra2_maps(ref->batch, scale, channel, kind, first, count, block, maps, maps_floats, norms);  // the handle's current batch
 }
 
 int ce_ref_image_heuristics(ce_ref *ref, ce_image_heuristics *out)

@@ -188,42 +188,6 @@ int ce_upload_many(ce_batch *b, const std::vector<ce_upload_job> &jobs)
     return CE_OK;
 }
 
-// leaf scratch (ce_internal.h): device buffers of at least in_bytes / out_bytes and a pinned staging buffer of the larger
-int ce_leaf_scratch(ce_ctx *ctx, size_t in_bytes, size_t out_bytes)
-{
-    CE_HIP(ctx, hipSetDevice(ctx->device));
-    auto grow = [&](uint8_t *&p, size_t &cap, size_t want, bool host) -> int {
-        if (cap >= want) return CE_OK;
-        if (p) CE_HIP(ctx, host ? hipHostFree(p) : hipFree(p));
-        p = nullptr;
-        cap = 0;
-        const size_t sz = want + want / 4;  // a little head room: a sweep over nearby shapes does not reallocate each time
-        CE_HIP(ctx, host ? hipHostMalloc((void **)&p, sz, hipHostMallocDefault) : hipMalloc((void **)&p, sz));
-        cap = sz;
-        return CE_OK;
-    };
-    int rc = grow(ctx->leaf_d_in, ctx->leaf_in_cap, in_bytes, false);
-    if (rc == CE_OK) rc = grow(ctx->leaf_d_out, ctx->leaf_out_cap, out_bytes, false);
-    if (rc == CE_OK) rc = grow(ctx->leaf_h, ctx->leaf_h_cap, std::max(in_bytes, out_bytes), true);
-    return rc;
-}
-
-// host image in -> kernel -> host image out through the leaf scratch, everything on the context's stream
-int ce_leaf_roundtrip(ce_ctx *ctx, const void *in, size_t in_bytes, void *out, size_t out_bytes,
-                      const std::function<int(uint8_t *, uint8_t *)> &launch)
-{
-    int rc = ce_leaf_scratch(ctx, in_bytes, out_bytes);
-    if (rc != CE_OK) return rc;
-    std::memcpy(ctx->leaf_h, in, in_bytes);
-    CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_d_in, ctx->leaf_h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = launch(ctx->leaf_d_in, ctx->leaf_d_out);
-    if (rc != CE_OK) return rc;
-    CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_h, ctx->leaf_d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::memcpy(out, ctx->leaf_h, out_bytes);
-    return CE_OK;
-}
-
 // the table runs on the batch's upload stream, behind the copy (and the format conversion) of the same image
 int ce_apply_lut(ce_batch *b, uint8_t *slot, const ce_lut *lut)
 {
@@ -445,13 +409,9 @@ int ingest_table(ce_ctx *ctx, int transfer, uint32_t depth, uint32_t white_bits,
         std::vector<float> host((size_t)1 << depth);
         build(host.data());
         CE_HIP(ctx, hipSetDevice(ctx->device));
-        float *d = nullptr;
-        CE_HIP(ctx, hipMalloc(&d, host.size() * sizeof(float)));
-        if (hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            hipFree(d);
-            return ce_fail(ctx, CE_ERR_BACKEND, std::string("H2D failed (") + what + ")");
-        }
-        it = ctx->cicp_tables.emplace(key, d).first;
+        void *d = nullptr;
+        if (int rc = ce_device_table(ctx, host.data(), host.size() * sizeof(float), what, &d)) return rc;
+        it = ctx->cicp_tables.emplace(key, static_cast<float *>(d)).first;
     }
     *out = it->second;
     return CE_OK;

@@ -1,4 +1,5 @@
-// Internal declarations shared by the host runtime (ce_api.cpp, ce_ingest.cpp) and the gfx950 kernels.
+// Internal declarations shared by the host runtime (ce_api.cpp, ce_ingest.cpp, ce_leaf.cpp, ce_resample.cpp) and the
+// gfx950 kernels.
 // Nothing here is part of the ABI; the ABI is include/ce_metrics.h.
 #pragma once
 
@@ -57,18 +58,16 @@ struct ce_kernel_stat {
 #define CE_DEFAULT_FORK_ALONE_BELOW_MP 64.0
 #endif
 
-// One axis of a resample on the device: int32 [n_out] first tap | [n_out] tap count | [n_out][ksize] weights (22-bit fixed point)
+// One axis of a resample on the device.  resample.hip reads d as int32: [n_out] first tap | [n_out] tap count | [n_out][ksize]
+// weights (22-bit fixed point).  The float resampler (resample_f32.hip) reads it as n_out * (1 + ksize) doubles, the first
+// n_out of them holding, as int32, [n_out] first tap | [n_out] tap count; then [n_out][ksize] f64 weights.
 struct ce_resample_axis {
-    int32_t *d = nullptr;
+    void *d = nullptr;
     uint32_t n_in = 0, n_out = 0, ksize = 0;
 };
 
-// One axis of a float resample (resample_f32.hip): n_out * (1 + ksize) doubles, the first n_out of them holding, as int32,
-// [n_out] first tap | [n_out] tap count; then [n_out][ksize] f64 weights
-struct ce_resample_axis_f64 {
-    double *d = nullptr;
-    uint32_t n_in = 0, n_out = 0, ksize = 0;
-};
+// the kinds of one-pair batch a context keeps for its host-image calls (ce_ctx::leaf_batch)
+enum ce_leaf_kind { CE_LEAF_RGB8 = 0, CE_LEAF_DEEP = 1, CE_LEAF_LINEAR = 2, CE_LEAF_KINDS = 3 };
 
 struct ce_ctx {
     int device = 0;
@@ -83,8 +82,10 @@ struct ce_ctx {
     // sRGB->linear tables of the deep batches, 2^depth entries each, keyed by (depth, rule: 0 = the f64 curve, 1 = f32 powf);
     // built by the first deep batch that needs one and kept until the context goes (ce_api.cpp: ce_deep_table)
     std::map<std::pair<uint32_t, int>, float *> deep_tables;
-    struct ce_batch *leaf_deep = nullptr;  // the one-pair deep batch of ce_eval_pair_deep (remade when shape or depths change)
-    struct ce_batch *leaf_linear = nullptr;  // the one-pair linear batch of ce_eval_pair_linear (remade when the shape changes)
+    // the kept one-pair batches (ce_leaf.cpp: leaf_batch), remade when the shape or, deep, a depth changes: RGB8 for
+    // ce_calculate_butteraugli_diffmap, ce_calculate_dssim_ssim_maps and ce_calculate_ssimulacra2_maps, deep for
+    // ce_eval_pair_deep, linear for ce_eval_pair_linear and ce_eval_pair_hdr_fidelity
+    struct ce_batch *leaf_batch[CE_LEAF_KINDS] = {};
     // transfer tables of the CICP ingest (cicp.hip), 2^depth entries each, keyed by (transfer, depth, bits of white_nits);
     // built by the first ingest that needs one and kept until the context goes (ce_ingest.cpp: ingest_table).  The HLG ingest's
     // inverse-OETF tables (hlg.hip) live here too, one per depth, under H.273's code for HLG: (18, depth, 0)
@@ -116,20 +117,17 @@ struct ce_ctx {
     // ce_rgb8_to_dssim_image): device in / out and a page-locked staging buffer, kept between calls
     uint8_t *leaf_d_in = nullptr, *leaf_d_out = nullptr, *leaf_h = nullptr;
     size_t leaf_in_cap = 0, leaf_out_cap = 0, leaf_h_cap = 0;
-    // the one-pair batch of ce_calculate_butteraugli_diffmap, ce_calculate_dssim_ssim_maps and ce_calculate_ssimulacra2_maps
-    // (remade when the shape changes)
-    struct ce_batch *leaf_map = nullptr;
     // grow-only device scratch of the image heuristics (heuristics.hip: per-tile partial sums, per-image means and results)
     // and the page-locked buffer their results come back through
     uint8_t *heur_d = nullptr, *heur_h = nullptr;
     size_t heur_d_cap = 0, heur_h_cap = 0;
     // grow-only device scratch of the resamplers (resample.hip, resample_f32.hip): the image between the two passes - u8, or
     // f32 for a linear batch; both resamplers run on the context's stream, so one buffer serves them - and the tap tables of
-    // the (in, out, filter) pairs used so far, keyed by them and kept until the context goes (ce_api.cpp: resample_table)
+    // the (in, out, filter, f64 weights?) axes used so far, keyed by them and kept until the context goes (ce_resample.cpp:
+    // resample_table)
     uint8_t *rs_mid = nullptr;
     size_t rs_mid_cap = 0;
-    std::map<std::tuple<uint32_t, uint32_t, int>, struct ce_resample_axis> rs_tables;
-    std::map<std::tuple<uint32_t, uint32_t, int>, struct ce_resample_axis_f64> rs_tables_f64;
+    std::map<std::tuple<uint32_t, uint32_t, int, bool>, ce_resample_axis> rs_tables;
 
     // Auxiliary streams of the context, shared by all its batches (made on first use, destroyed with the context): the
     // three metric chains of a forked batch, SSIMULACRA2's level-0 passes, Butteraugli's half-resolution chain.  Rounds
@@ -305,8 +303,10 @@ struct ce_batch {
         }                                                                                          \
     } while (0)
 
-// ---- what the two halves of the host runtime share: ce_api.cpp (contexts, batch lifetime, launch, collect, the pooled
-// calls, resampling, HDR fidelity, reference handles, hooks) and ce_ingest.cpp (everything that writes a slot) ----------------
+// ---- what the parts of the host runtime share: ce_api.cpp (errors, profiling, contexts, batch lifetime, launch, collect,
+// the map read-outs, the calls on a batch's slabs, the pooled ce_eval_batch, reference handles, hooks), ce_ingest.cpp
+// (everything that writes a slot), ce_leaf.cpp (host images in, a result out through scratch the context owns) and
+// ce_resample.cpp (resampling) -------------------------------------------------------------------------------------------------
 
 // record `msg` as the context's last error (the calling thread's, without a context) and return `code` (ce_api.cpp)
 int ce_fail(ce_ctx *ctx, int code, const std::string &msg);
@@ -335,13 +335,24 @@ int ce_upload_many(ce_batch *b, const std::vector<ce_upload_job> &jobs);
 // `lut` (nullptr: nothing) over the RGB8 image at `slot`, on the batch's upload stream behind its copy (ce_ingest.cpp)
 int ce_apply_lut(ce_batch *b, uint8_t *slot, const ce_lut *lut);
 // the context's leaf scratch grown to in_bytes / out_bytes, and one host image through it and `launch(d_in, d_out)` on the
-// context's stream, complete on return (ce_ingest.cpp)
+// context's stream, complete on return (ce_leaf.cpp)
 int ce_leaf_scratch(ce_ctx *ctx, size_t in_bytes, size_t out_bytes);
 int ce_leaf_roundtrip(ce_ctx *ctx, const void *in, size_t in_bytes, void *out, size_t out_bytes,
                       const std::function<int(uint8_t *, uint8_t *)> &launch);
 
 // host table -> device memory of `b`, complete on return, without draining the context's stream (ce_api.cpp)
 int ce_upload_table(ce_batch *b, void *dst, const void *src, size_t bytes);
+// a new device copy of the `bytes` at `host`, complete on return, for the table maps a context keeps; a failed copy frees
+// the allocation and fails with "H2D failed (<what>)" (ce_api.cpp)
+int ce_device_table(ce_ctx *ctx, const void *host, size_t bytes, const char *what, void **out);
+// the metric bits a launch knows
+constexpr uint32_t ce_known_metrics = CE_METRIC_DSSIM | CE_METRIC_SSIMULACRA2 | CE_METRIC_BUTTERAUGLI | CE_METRIC_PSNR;
+// the length checks of a packed RGB8 pair in the reference's order: mismatch, then wrong length (ce_api.cpp)
+int ce_validate_pair(ce_ctx *ctx, size_t ref_len, size_t test_len, size_t w, size_t h);
+// a failed call drains the copies that may still read the caller's buffers (ce_api.cpp)
+void ce_drain_batch(ce_batch *b);
+// HDR fidelity's depth (10, 12 or 16) and white_nits (finite, > 0), refused in that order (ce_api.cpp)
+int ce_hdr_params_check(ce_ctx *ctx, uint32_t depth, float white_nits);
 
 // the context's auxiliary stream `which` (ce_ctx::AUX_*), made on first use; nullptr + ctx->err on failure (ce_api.cpp)
 hipStream_t ce_ctx_aux_stream(ce_ctx *ctx, int which);
@@ -435,12 +446,20 @@ int ce_image_heuristics_run(ce_ctx *ctx, const uint8_t *d_imgs, size_t img_strid
 int ce_launch_resample(ce_ctx *ctx, hipStream_t stream, const uint8_t *d_src, size_t src_stride, uint8_t *d_dst, size_t dst_stride,
                        uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h, uint32_t n, const ce_resample_axis *horiz,
                        const ce_resample_axis *vert, uint8_t *mid);
+// what both resample launchers end with: the launches' error, if any, as "resample: <HIP's words>"
+inline int ce_resample_launched(ce_ctx *ctx)
+{
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return CE_OK;
+    ctx->err = std::string("resample: ") + hipGetErrorString(e);
+    return CE_ERR_BACKEND;
+}
 
 // The same for packed f32 RGB (a linear batch's slabs; resample_f32.hip): strides in floats, `mid` the n x h x out_w x 3 floats
 // between the passes; the last pass that runs clamps its store to +-CE_LINEAR_MAX
 int ce_launch_resample_f32(ce_ctx *ctx, hipStream_t stream, const float *d_src, size_t src_stride, float *d_dst, size_t dst_stride,
-                           uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h, uint32_t n, const ce_resample_axis_f64 *horiz,
-                           const ce_resample_axis_f64 *vert, float *mid);
+                           uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h, uint32_t n, const ce_resample_axis *horiz,
+                           const ce_resample_axis *vert, float *mid);
 
 // One Y'CbCr image on the device as yuv.hip reads it: checked by ce_ingest.cpp (yuv_check), planes in device memory
 struct ce_yuv_dev {
@@ -525,7 +544,7 @@ bool ce_build_colour_matrix(int primaries, float m[9]);
 // the resampler's taps of one axis, n_in -> n_out samples (include/ce_metrics.h, enum ce_resample_filter): table = [n_out]
 // first tap | [n_out] tap count | [n_out][ksize] weights; false for an unknown filter or an empty axis
 bool ce_build_resample_table(uint32_t n_in, uint32_t n_out, int filter, std::vector<int32_t> &table, uint32_t *ksize);
-// the float resampler's: the same geometry with the normalised f64 weights themselves, in ce_resample_axis_f64's layout
+// the float resampler's: the same geometry with the normalised f64 weights themselves, in the layout ce_resample_axis gives for resample_f32.hip
 bool ce_build_resample_table_f64(uint32_t n_in, uint32_t n_out, int filter, std::vector<double> &table, uint32_t *ksize);
 void ce_build_srgb_lut_f64(float lut[256]);
 void ce_build_srgb_lut_powf(float lut[256]);

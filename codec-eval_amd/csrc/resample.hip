@@ -49,21 +49,15 @@ int ce_launch_resample(ce_ctx *ctx, hipStream_t stream, const uint8_t *d_src, si
         ctx->err = "resample: too many tiles for one launch";
         return CE_ERR_INVALID_ARG;
     }
+    const auto *htab = static_cast<const int32_t *>(horiz ? horiz->d : nullptr), *vtab = static_cast<const int32_t *>(vert ? vert->d : nullptr);
     if (horiz) {
         if (r.h.lds)
-            CE_LAUNCH_ON(ctx, stream, "resample_h", k_resample_h<true>, dim3(r.h.grid), dim3(kThreads), r.h.lds_bytes, r.h.g, horiz->d, out_w,
+            CE_LAUNCH_ON(ctx, stream, "resample_h", k_resample_h<true>, dim3(r.h.grid), dim3(kThreads), r.h.lds_bytes, r.h.g, htab, out_w,
                          horiz->ksize);
         else
-            CE_LAUNCH_ON(ctx, stream, "resample_h_wide", k_resample_h<false>, dim3(r.h.grid), dim3(kThreads), 0, r.h.g, horiz->d, out_w,
+            CE_LAUNCH_ON(ctx, stream, "resample_h_wide", k_resample_h<false>, dim3(r.h.grid), dim3(kThreads), 0, r.h.g, htab, out_w,
                          horiz->ksize);
     }
-    if (vert) CE_LAUNCH_ON(ctx, stream, "resample_v", k_resample_v, dim3(r.v.grid), dim3(kThreads), 0, r.v.g, vert->d, out_h, vert->ksize);
-    {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            ctx->err = std::string("resample: ") + hipGetErrorString(e);
-            return CE_ERR_BACKEND;
-        }
-    }
-    return CE_OK;
+    if (vert) CE_LAUNCH_ON(ctx, stream, "resample_v", k_resample_v, dim3(r.v.grid), dim3(kThreads), 0, r.v.g, vtab, out_h, vert->ksize);
+    return ce_resample_launched(ctx);
 }

@@ -42,8 +42,8 @@ __global__ __launch_bounds__(kThreads) void k_resample_f32_v(pass_geom g, const 
 static_assert(kLinearMax == CE_LINEAR_MAX, "the kernel header restates CE_LINEAR_MAX");
 
 int ce_launch_resample_f32(ce_ctx *ctx, hipStream_t stream, const float *d_src, size_t src_stride, float *d_dst, size_t dst_stride,
-                           uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h, uint32_t n, const ce_resample_axis_f64 *horiz,
-                           const ce_resample_axis_f64 *vert, float *mid)
+                           uint32_t w, uint32_t h, uint32_t out_w, uint32_t out_h, uint32_t n, const ce_resample_axis *horiz,
+                           const ce_resample_axis *vert, float *mid)
 {
     resample_launch r;
     if (!plan_resample(d_src, src_stride, d_dst, dst_stride, w, h, out_w, out_h, n, horiz != nullptr, vert != nullptr,
@@ -51,22 +51,16 @@ int ce_launch_resample_f32(ce_ctx *ctx, hipStream_t stream, const float *d_src, 
         ctx->err = "resample: too many tiles for one launch";
         return CE_ERR_INVALID_ARG;
     }
+    const auto *htab = static_cast<const double *>(horiz ? horiz->d : nullptr), *vtab = static_cast<const double *>(vert ? vert->d : nullptr);
     if (horiz) {
         if (r.h.lds)
-            CE_LAUNCH_ON(ctx, stream, "resample_f32_h", k_resample_f32_h<true>, dim3(r.h.grid), dim3(kThreads), r.h.lds_bytes, r.h.g, horiz->d,
+            CE_LAUNCH_ON(ctx, stream, "resample_f32_h", k_resample_f32_h<true>, dim3(r.h.grid), dim3(kThreads), r.h.lds_bytes, r.h.g, htab,
                          out_w, horiz->ksize);
         else
-            CE_LAUNCH_ON(ctx, stream, "resample_f32_h_wide", k_resample_f32_h<false>, dim3(r.h.grid), dim3(kThreads), 0, r.h.g, horiz->d, out_w,
+            CE_LAUNCH_ON(ctx, stream, "resample_f32_h_wide", k_resample_f32_h<false>, dim3(r.h.grid), dim3(kThreads), 0, r.h.g, htab, out_w,
                          horiz->ksize);
     }
     if (vert)
-        CE_LAUNCH_ON(ctx, stream, "resample_f32_v", k_resample_f32_v, dim3(r.v.grid), dim3(kThreads), 0, r.v.g, vert->d, out_h, vert->ksize);
-    {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            ctx->err = std::string("resample: ") + hipGetErrorString(e);
-            return CE_ERR_BACKEND;
-        }
-    }
-    return CE_OK;
+        CE_LAUNCH_ON(ctx, stream, "resample_f32_v", k_resample_f32_v, dim3(r.v.grid), dim3(kThreads), 0, r.v.g, vtab, out_h, vert->ksize);
+    return ce_resample_launched(ctx);
 }

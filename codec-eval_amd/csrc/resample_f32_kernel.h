@@ -104,7 +104,7 @@ __device__ __forceinline__ void store(const pass_geom &g, const place &p, double
     g.dst[(size_t)p.img * g.dst_stride + (size_t)p.y * g.out_row_floats + p.f] = v;
 }
 
-// tab: ce_resample_axis_f64's layout.  The int32 head and the weights behind it:
+// tab: ce_resample_axis's layout for this resampler.  The int32 head and the weights behind it:
 __device__ __forceinline__ const int32_t *tab_head(const double *tab) { return reinterpret_cast<const int32_t *>(tab); }
 
 // Before the barrier: the taps of the block's <= kTilePixels output pixels into s_tab, LDS of taps_lds_bytes(ksize): the
