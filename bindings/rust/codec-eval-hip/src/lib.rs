@@ -601,6 +601,49 @@ impl HipMetrics {
         self.check(rc, width, height, test.len() * 4)?;
         Ok(out)
     }
+
+    /// `ce_eval_pair_delta_e_itp_map`: where one pair of packed f32 RGB differs - see `HipBatch::delta_e_itp_map`.
+    pub fn delta_e_itp_map(&mut self, reference: &[f32], test: &[f32], width: u32, height: u32, depth: u32, white_nits: f32, block: u32,
+                           want_map: bool, thresholds_q20: &[u32]) -> Result<DeltaEItpMaps, HipError> {
+        let mut out = DeltaEItpMaps::sized(1, width, height, block, want_map, thresholds_q20.len());
+        let rc = unsafe {
+            sys::ce_eval_pair_delta_e_itp_map(self.ctx, reference.as_ptr(), reference.len() * 4, test.as_ptr(), test.len() * 4, width, height,
+                                              depth, white_nits, block, out.map_ptr(), out.map.len(), slice_or_null(thresholds_q20),
+                                              thresholds_q20.len() as u32, out.over_ptr())
+        };
+        self.check(rc, width, height, test.len() * 4)?;
+        Ok(out)
+    }
+}
+
+/// What `ce_batch_delta_e_itp_map` returns: per pair the BT.2124 Delta E ITP of every pixel in units of 2^-20
+/// (`sys::CE_DELTA_E_ITP_Q20` is 1.0), saturated at `u32::MAX` - or at `block` 2 ..= 64 the maximum of each block x block cell -
+/// as `[count][cells_h][cells_w]`, empty when no map was asked for; and `[count][n_thresholds]` counts of the pixels above each
+/// threshold, empty without thresholds.
+pub struct DeltaEItpMaps {
+    pub map: Vec<u32>,
+    pub cells_w: u32,
+    pub cells_h: u32,
+    pub over: Vec<u64>,
+}
+
+impl DeltaEItpMaps {
+    fn sized(count: u32, width: u32, height: u32, block: u32, want_map: bool, n_thresholds: usize) -> Self {
+        let b = block.max(1);
+        let (cells_w, cells_h) = ((width + b - 1) / b, (height + b - 1) / b);
+        let n = if want_map { count as usize * cells_w as usize * cells_h as usize } else { 0 };
+        DeltaEItpMaps { map: vec![0u32; n], cells_w, cells_h, over: vec![0u64; count as usize * n_thresholds] }
+    }
+    fn map_ptr(&mut self) -> *mut u32 {
+        if self.map.is_empty() { std::ptr::null_mut() } else { self.map.as_mut_ptr() }
+    }
+    fn over_ptr(&mut self) -> *mut u64 {
+        if self.over.is_empty() { std::ptr::null_mut() } else { self.over.as_mut_ptr() }
+    }
+}
+
+fn slice_or_null(s: &[u32]) -> *const u32 {
+    if s.is_empty() { std::ptr::null() } else { s.as_ptr() }
 }
 
 /// `ce_pq_code_thresholds`: the decision thresholds of PQ code values on linear light, `T[1 ..= 2^depth - 1]`; a pure host
@@ -732,6 +775,20 @@ impl HipBatch<'_> {
     pub fn hdr_fidelity(&mut self, n_pairs: u32, depth: u32, white_nits: f32) -> Result<Vec<sys::ce_hdr_scores>, HipError> {
         let mut out = vec![sys::ce_hdr_scores::default(); n_pairs as usize];
         let rc = unsafe { sys::ce_batch_hdr_fidelity(self.handle, n_pairs, depth, white_nits, out.as_mut_ptr()) };
+        self.check(rc, 0)?;
+        Ok(out)
+    }
+
+    /// `ce_batch_delta_e_itp_map`: where pairs `[first, first + count)` of a LINEAR batch differ - the per-pixel Delta E ITP map
+    /// (`block` 1) or its block x block cell maxima when `want_map`, and how many pixels of each pair exceed each of up to
+    /// `sys::CE_DELTA_E_ITP_MAX_THRESHOLDS` thresholds; one of the two must be asked for.
+    pub fn delta_e_itp_map(&mut self, first: u32, count: u32, depth: u32, white_nits: f32, block: u32, want_map: bool,
+                           thresholds_q20: &[u32]) -> Result<DeltaEItpMaps, HipError> {
+        let mut out = DeltaEItpMaps::sized(count, self.width, self.height, block, want_map, thresholds_q20.len());
+        let rc = unsafe {
+            sys::ce_batch_delta_e_itp_map(self.handle, first, count, depth, white_nits, block, out.map_ptr(), out.map.len(),
+                                          slice_or_null(thresholds_q20), thresholds_q20.len() as u32, out.over_ptr())
+        };
         self.check(rc, 0)?;
         Ok(out)
     }

@@ -135,6 +135,9 @@ pub struct ce_image_heuristics {
 }
 pub const CE_BATCH_REFERENCES: u32 = 0;
 pub const CE_BATCH_TESTS: u32 = 1;
+/// `CE_DELTA_E_ITP_MAX_THRESHOLDS`, and a Delta E ITP of 1.0 in the units of the maps and thresholds (`CE_DELTA_E_ITP_Q20`)
+pub const CE_DELTA_E_ITP_MAX_THRESHOLDS: u32 = 8;
+pub const CE_DELTA_E_ITP_Q20: u32 = 1 << 20;
 
 /// `ce_pair_desc` (40 bytes): one item of the (image x codec x quality) grid, host pointers.
 #[repr(C)]
@@ -330,6 +333,12 @@ extern "C" {
                                      out: *mut ce_hdr_scores) -> c_int;
     pub fn ce_pq_code_thresholds(depth: u32, white_nits: c_float, out: *mut c_float, n: usize) -> c_int;
     pub fn ce_hdr_fidelity_matrices(a: *mut c_float, b: *mut c_float) -> c_int;
+    pub fn ce_batch_delta_e_itp_map(b: *mut ce_batch, first: u32, count: u32, depth: u32, white_nits: c_float, block: u32, map: *mut u32,
+                                    map_len: usize, thresholds_q20: *const u32, n_thresholds: u32, over: *mut u64) -> c_int;
+    pub fn ce_eval_pair_delta_e_itp_map(ctx: *mut ce_ctx, reference: *const c_float, reference_len: usize, test: *const c_float,
+                                        test_len: usize, width: u32, height: u32, depth: u32, white_nits: c_float, block: u32,
+                                        map: *mut u32, map_len: usize, thresholds_q20: *const u32, n_thresholds: u32,
+                                        over: *mut u64) -> c_int;
     pub fn ce_batch_set_reference_over(b: *mut ce_batch, first_ref: u32, pixels: *const c_void, len: usize, format: c_int, n_bg: u32,
                                        backgrounds: *const u16) -> c_int;
     pub fn ce_batch_set_test_over(b: *mut ce_batch, first_pair: u32, ref_indices: *const u32, pixels: *const c_void, len: usize,

@@ -271,6 +271,8 @@ _PROTOTYPES = [
     ("ce_eval_pair_hdr_fidelity", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _f32, C.POINTER(CeHdrScores)]),
     ("ce_pq_code_thresholds", _i, [_u32, _f32, _vp, _sz]),
     ("ce_hdr_fidelity_matrices", _i, [_vp, _vp]),
+    ("ce_batch_delta_e_itp_map", _i, [_vp, _u32, _u32, _u32, _f32, _u32, _vp, _sz, _vp, _u32, _vp]),
+    ("ce_eval_pair_delta_e_itp_map", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _f32, _u32, _vp, _sz, _vp, _u32, _vp]),
     ("ce_batch_set_reference_over", _i, [_vp, _u32, _vp, _sz, _i, _u32, _vp]),
     ("ce_batch_set_test_over", _i, [_vp, _u32, _vp, _vp, _sz, _i, _u32, _vp]),
     ("ce_composite_rgba8", _i, [_vp, _vp, _sz, _u32, _u32, _vp, _vp, _sz]),
@@ -454,6 +456,23 @@ class HdrFidelity:
     @staticmethod
     def from_c(s: CeHdrScores) -> "HdrFidelity":
         return HdrFidelity(s.pq_psnr, s.delta_e_itp_mean, s.delta_e_itp_max, int(s.pq_sse), int(s.itp_sum_q20), int(s.itp_max_q20))
+
+
+DELTA_E_ITP_Q20 = 1 << 20  # a Delta E ITP of 1.0 in the units of the maps and thresholds (CE_DELTA_E_ITP_Q20)
+DELTA_E_ITP_MAX_THRESHOLDS = 8  # CE_DELTA_E_ITP_MAX_THRESHOLDS
+
+
+def _delta_e_itp_map(ctx: "Context", call, count: int, width: int, height: int, block: int, thresholds_q20, maps: bool):
+    """The outputs of ce_batch_delta_e_itp_map / ce_eval_pair_delta_e_itp_map around call(map, map_len, thresholds, n, over):
+    (uint32 [count, ceil(h / block), ceil(w / block)] or None, uint64 [count, n] or None)."""
+    if block < 1:
+        raise CodecEvalError(CE_ERR_INVALID_ARG, "block must be 1 or a power of two up to 64")
+    m = np.empty((count, -(-height // block), -(-width // block)), np.uint32) if maps else None
+    thr = None if thresholds_q20 is None else np.ascontiguousarray(thresholds_q20, dtype=np.uint32).reshape(-1)
+    over = None if thr is None else np.zeros((count, thr.size), np.uint64)
+    ctx._check(call(m.ctypes.data if maps else None, m.size if maps else 0, thr.ctypes.data if thr is not None and thr.size else None,
+                    thr.size if thr is not None else 0, over.ctypes.data if over is not None else None))
+    return m, over
 
 
 def _cicp_fmt(a: np.ndarray) -> int:
@@ -1094,6 +1113,15 @@ class Context:
                                                     white_nits, C.byref(s)))
         return HdrFidelity.from_c(s)
 
+    def delta_e_itp_map(self, reference, test, width: int, height: int, depth: int = 10, white_nits: float = 203.0, block: int = 1,
+                        thresholds_q20=None, maps: bool = True):
+        """Batch.delta_e_itp_maps for one pair of packed float32 RGB (ce_eval_pair_delta_e_itp_map): (uint32
+        [1, ceil(h / block), ceil(w / block)] or None, uint64 [1, n] or None)."""
+        r, t = _buf_f32(reference), _buf_f32(test)
+        return _delta_e_itp_map(self, lambda m, n, thr, k, over: lib().ce_eval_pair_delta_e_itp_map(
+            self._h, r.ctypes.data, r.nbytes, t.ctypes.data, t.nbytes, width, height, depth, white_nits, block, m, n, thr, k, over),
+            1, width, height, block, thresholds_q20, maps)
+
     def batch_linear(self, width: int, height: int, max_refs: int, max_pairs: int) -> "Batch":
         """A Batch whose slabs hold packed float32 RGB in linear light (ce_batch_create_linear): loaded with float32 arrays
         through set_reference / set_test, or with tagged code values through set_reference_cicp / set_test_cicp."""
@@ -1406,6 +1434,16 @@ class Batch:
         out = (CeHdrScores * max(n_pairs, 1))()
         self.ctx._check(lib().ce_batch_hdr_fidelity(self._h, n_pairs, depth, white_nits, out))
         return [HdrFidelity.from_c(out[i]) for i in range(n_pairs)]
+
+    def delta_e_itp_maps(self, first: int, count: int, depth: int = 10, white_nits: float = 203.0, block: int = 1, thresholds_q20=None,
+                         maps: bool = True):
+        """Where pairs [first, first + count) of a linear batch differ (ce_batch_delta_e_itp_map): every pixel's BT.2124
+        Delta E ITP in units of 2^-20 (DELTA_E_ITP_Q20 is 1.0), saturated at 2^32 - 1, as a uint32 [count, h, w] array, or at
+        block = 2 .. 64 the maximum of each block x block cell, [count, ceil(h / block), ceil(w / block)]; and for up to 8
+        `thresholds_q20` how many pixels of each pair exceed each, uint64 [count, n].  maps=False: counts only (None for the
+        maps); thresholds_q20=None: maps only.  What launch() left to collect is untouched."""
+        return _delta_e_itp_map(self.ctx, lambda m, n, thr, k, over: lib().ce_batch_delta_e_itp_map(
+            self._h, first, count, depth, white_nits, block, m, n, thr, k, over), count, self.width, self.height, block, thresholds_q20, maps)
 
     def butteraugli_pnorm3(self, n_pairs: int) -> np.ndarray:
         out = np.zeros(n_pairs, np.float64)

@@ -576,6 +576,9 @@ void ce_batch_destroy(ce_batch *b)
     if (b->h_scores) hipHostFree(b->h_scores);
     hipFree(b->d_hdr);
     if (b->h_hdr) hipHostFree(b->h_hdr);
+    hipFree(b->d_itp_map);
+    hipFree(b->d_itp_over);
+    if (b->h_itp_over) hipHostFree(b->h_itp_over);
     for (int k = 0; k < ce_batch::kStages; k++) {
         if (b->h_stage[k]) hipHostFree(b->h_stage[k]);
         if (b->ev_stage[k]) hipEventDestroy(b->ev_stage[k]);
@@ -1198,6 +1201,54 @@ int ce_batch_hdr_fidelity(ce_batch *b, uint32_t n_pairs, uint32_t depth, float w
         s.delta_e_itp_max = (double)s.itp_max_q20 / 1048576.0;
         out[i] = s;
     }
+    return CE_OK;
+}
+
+// Delta E ITP per pixel, per cell and over thresholds (include/ce_metrics.h): ce_batch_hdr_fidelity's
+// frame around the map kernel
+int ce_batch_delta_e_itp_map(ce_batch *b, uint32_t first, uint32_t count, uint32_t depth, float white_nits, uint32_t block, uint32_t *map,
+                             size_t map_len, const uint32_t *thresholds_q20, uint32_t n_thresholds, uint64_t *over)
+{
+    if (!b) return ce_fail(nullptr, CE_ERR_INVALID_ARG, "Delta E ITP map: null batch");
+    ce_ctx *ctx = b->ctx;
+    if (!b->linear)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "the Delta E ITP map reads linear light: it needs a linear batch (ce_batch_create_linear)");
+    if (int rc = ce_hdr_params_check(ctx, depth, white_nits)) return rc;
+    if (!map && !over) return ce_fail(ctx, CE_ERR_INVALID_ARG, "Delta E ITP map: neither a map nor counts asked for");
+    if (count == 0 || first > b->max_pairs || count > b->max_pairs - first)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "Delta E ITP map: pairs [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) +
+                                                 ") outside the batch's " + std::to_string(b->max_pairs));
+    if (int rc = check_map_readout(ctx, "Delta E ITP map", b->max_pairs, first, count, block, b->w, b->h, map != nullptr, map_len)) return rc;
+    if (n_thresholds > CE_DELTA_E_ITP_MAX_THRESHOLDS)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "Delta E ITP map: at most " + std::to_string(CE_DELTA_E_ITP_MAX_THRESHOLDS) + " thresholds, got " +
+                                                 std::to_string(n_thresholds));
+    if (over && (n_thresholds == 0 || !thresholds_q20)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "Delta E ITP map: counts asked for without thresholds");
+    if (!over && (n_thresholds != 0 || thresholds_q20)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "Delta E ITP map: thresholds given without a place for the counts");
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    const float *d_table = nullptr, *d_coarse = nullptr;
+    if (int rc = hdr_table_dev(ctx, depth, white_nits, &d_table, &d_coarse)) return rc;
+    if (map && b->itp_map_cap < map_len) {
+        hipFree(b->d_itp_map);
+        b->d_itp_map = nullptr, b->itp_map_cap = 0;
+        CE_HIP(ctx, hipMalloc(&b->d_itp_map, map_len * sizeof(uint32_t)));
+        b->itp_map_cap = map_len;
+    }
+    const size_t over_bytes = sizeof(unsigned long long) * CE_DELTA_E_ITP_MAX_THRESHOLDS;  // per pair
+    if (over && !b->d_itp_over) CE_HIP(ctx, hipMalloc(&b->d_itp_over, over_bytes * b->max_pairs));
+    if (over && !b->h_itp_over) CE_HIP(ctx, hipHostMalloc(&b->h_itp_over, over_bytes * b->max_pairs, hipHostMallocDefault));
+    // on the context's stream, as a launch: behind the uploads queued so far, with the pair table of the last bind
+    if (int rc = ce_flush_uploads(b)) return rc;
+    if (int rc = sync_pair_ref(b)) return rc;
+    float a[9], lms[9];
+    ce_build_hdr_fidelity_matrices(a, lms);
+    if (int rc = ce_launch_delta_e_itp_map(b, first, count, depth, d_table, d_coarse, a, lms, block, map ? b->d_itp_map : nullptr, thresholds_q20,
+                                           n_thresholds, over ? b->d_itp_over : nullptr))
+        return rc;
+    if (map) CE_HIP(ctx, hipMemcpyAsync(map, b->d_itp_map, map_len * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (over) CE_HIP(ctx, hipMemcpyAsync(b->h_itp_over, b->d_itp_over, over_bytes * count, hipMemcpyDeviceToHost, ctx->stream));
+    CE_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the slabs are free again: a later upload needs no fence against this
+    for (uint32_t i = 0; over && i < count; i++)
+        for (uint32_t j = 0; j < n_thresholds; j++) over[(size_t)i * n_thresholds + j] = b->h_itp_over[(size_t)i * CE_DELTA_E_ITP_MAX_THRESHOLDS + j];
     return CE_OK;
 }
 

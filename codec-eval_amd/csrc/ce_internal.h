@@ -288,6 +288,12 @@ struct ce_batch {
 
     // HDR fidelity (hdr_fidelity.hip): [max_pairs][3] exact integers on the device and page-locked, made by the first call
     unsigned long long *d_hdr = nullptr, *h_hdr = nullptr;
+    // Delta E ITP maps (hdr_fidelity.hip: k_delta_e_itp_map): the device buffer of the maps or cell maxima of one call, grow-only,
+    // made by the first call that asks for a map; [max_pairs][8] exceedance counts on the device and page-locked, made by the
+    // first call that asks for counts
+    uint32_t *d_itp_map = nullptr;
+    size_t itp_map_cap = 0;  // elements
+    unsigned long long *d_itp_over = nullptr, *h_itp_over = nullptr;
 
     uint32_t last_n_pairs = 0;
     bool caller_blocks = false;  // set by entry points that collect before returning: page-locked sources need no staging copy
@@ -527,6 +533,14 @@ int ce_launch_yuv_hlg(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, ui
 // itself at depths 10 and 12, every 16th threshold at 16), a / lms = ce_build_hdr_fidelity_matrices
 int ce_launch_hdr_fidelity(ce_batch *b, uint32_t n_pairs, uint32_t depth, const float *d_table, const float *d_coarse, const float a[9],
                            const float lms[9], unsigned long long *d_out);
+
+// pairs [first, first + count) of a linear batch, same tables and matrices: every pixel's Delta E ITP in units of 2^-20,
+// saturated to 32 bits, into d_map - [count][h][w] at block 1, else the maxima of block x block cells, [count][ceil(h / block)]
+// [ceil(w / block)], cleared here; nullptr: no map - and into d_over[count][8] how many pixels exceed thresholds[j],
+// j < n_thresholds <= 8, cleared here (nullptr: no counts)
+int ce_launch_delta_e_itp_map(ce_batch *b, uint32_t first, uint32_t count, uint32_t depth, const float *d_table, const float *d_coarse,
+                              const float a[9], const float lms[9], uint32_t block, uint32_t *d_map, const uint32_t *thresholds,
+                              uint32_t n_thresholds, unsigned long long *d_over);
 
 // host-side constant builders (ce_tables.cpp)
 // HDR fidelity's PQ code thresholds (include/ce_metrics.h: ce_pq_code_thresholds; maxv entries; false unless white_nits is

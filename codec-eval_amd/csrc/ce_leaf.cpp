@@ -337,4 +337,25 @@ int ce_eval_pair_hdr_fidelity(ce_ctx *ctx, const float *reference, size_t refere
     return leaf_pair(b, CE_LEAF_LINEAR, reference, test, want, [&] { return ce_batch_hdr_fidelity(b, 1, depth, white_nits, out); });
 }
 
+// ... and its Delta E ITP map and exceedance counts through the same batch; what concerns the outputs is ce_batch_delta_e_itp_map's
+// to refuse
+int ce_eval_pair_delta_e_itp_map(ce_ctx *ctx, const float *reference, size_t reference_len, const float *test, size_t test_len, uint32_t width,
+                                 uint32_t height, uint32_t depth, float white_nits, uint32_t block, uint32_t *map, size_t map_len,
+                                 const uint32_t *thresholds_q20, uint32_t n_thresholds, uint64_t *over)
+{
+    if (!ctx) return CE_ERR_INVALID_ARG;
+    if (!reference || !test) return ce_fail(ctx, CE_ERR_INVALID_ARG, "Delta E ITP map: null pointer");
+    if (width == 0 || height == 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, "Delta E ITP map: empty image");
+    if (int rc = ce_hdr_params_check(ctx, depth, white_nits)) return rc;
+    const size_t want = (size_t)width * height * 12;
+    if (reference_len != want) return ce_bad_length(ctx, want, reference_len);
+    if (test_len != want) return ce_bad_length(ctx, want, test_len);
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    ce_batch *b = nullptr;
+    if (int rc = leaf_batch(ctx, CE_LEAF_LINEAR, width, height, 0, 0, &b)) return rc;
+    return leaf_pair(b, CE_LEAF_LINEAR, reference, test, want, [&] {
+        return ce_batch_delta_e_itp_map(b, 0, 1, depth, white_nits, block, map, map_len, thresholds_q20, n_thresholds, over);
+    });
+}
+
 }  // extern "C"

@@ -85,18 +85,20 @@ __device__ __forceinline__ void hdrf_codes(const hdrf_args &a, const float *s_ta
     for (int i = 0; i < 3; i++) c[i] = hdrf_code<DEPTH>(a.table, s_tab, q[i]), c[3 + i] = hdrf_code<DEPTH>(a.table, s_tab, l[i]);
 }
 
-// one pixel of a pair into the lane's integers: acc = pq_sse, itp_sum_q20, itp_max_q20
+// the code differences of a pixel of a pair, reference minus test: d = dRc dGc dBc dLc dMc dSc
 template <int DEPTH>
-__device__ __forceinline__ void hdrf_pixel(const hdrf_args &a, const float *s_tab, const float ref[3], const float test[3],
-                                           unsigned long long acc[3])
+__device__ __forceinline__ void hdrf_diffs(const hdrf_args &a, const float *s_tab, const float ref[3], const float test[3], long long d[6])
 {
     int32_t cr[6], ct[6];
     hdrf_codes<DEPTH>(a, s_tab, ref[0], ref[1], ref[2], cr);
     hdrf_codes<DEPTH>(a, s_tab, test[0], test[1], test[2], ct);
-    long long d[6];
 #pragma unroll
     for (int i = 0; i < 6; i++) d[i] = (long long)cr[i] - (long long)ct[i];
-    acc[0] += (unsigned long long)(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+}
+
+// ... -> k, the pixel's Delta E ITP in units of 2^-20 (under 2^33): what the scores sum and the maps (hdr_fidelity_map_kernel.h) store
+__device__ __forceinline__ unsigned long long hdrf_itp_q20(const hdrf_args &a, const long long d[6])
+{
     // the differences of BT.2100's ICtCp times 4096 * maxv, exact
     const long long di = 2048 * (d[3] + d[4]);
     const long long dct = 6610 * d[3] - 13613 * d[4] + 7003 * d[5];
@@ -104,7 +106,18 @@ __device__ __forceinline__ void hdrf_pixel(const hdrf_args &a, const float *s_ta
     const double fi = (double)di, fct = (double)dct, fcp = (double)dcp;
     const double s = (fi * fi + 0.25 * (fct * fct)) + fcp * fcp;  // BT.2124: T = Ct / 2
     const double e = 720.0 * __builtin_sqrt(s) / a.denom;
-    const unsigned long long k = (unsigned long long)__builtin_rint(e * 1048576.0);
+    return (unsigned long long)__builtin_rint(e * 1048576.0);
+}
+
+// one pixel of a pair into the lane's integers: acc = pq_sse, itp_sum_q20, itp_max_q20
+template <int DEPTH>
+__device__ __forceinline__ void hdrf_pixel(const hdrf_args &a, const float *s_tab, const float ref[3], const float test[3],
+                                           unsigned long long acc[3])
+{
+    long long d[6];
+    hdrf_diffs<DEPTH>(a, s_tab, ref, test, d);
+    acc[0] += (unsigned long long)(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    const unsigned long long k = hdrf_itp_q20(a, d);
     acc[1] += k;
     acc[2] = k > acc[2] ? k : acc[2];
 }

@@ -545,6 +545,50 @@ inline HdrFidelity hdr_fidelity(const HipBackend &be, const float *reference, co
                   width, height, len);
     return out;
 }
+// Where pairs differ (include/ce_metrics.h: ce_batch_delta_e_itp_map): per pair every pixel's Delta E ITP in
+// units of 2^-20 (CE_DELTA_E_ITP_Q20 is 1.0), saturated at 2^32 - 1 - at block 2 .. 64 the maximum of each block x block cell -
+// as [count][cells_h][cells_w], empty when want_map is false; and [count][thresholds.size()] counts of the pixels above each
+// of up to CE_DELTA_E_ITP_MAX_THRESHOLDS thresholds, empty without thresholds
+struct DeltaEItpMaps {
+    std::vector<uint32_t> map;
+    uint32_t cells_w = 0, cells_h = 0;
+    std::vector<uint64_t> over;
+    static DeltaEItpMaps sized(uint32_t count, uint32_t width, uint32_t height, uint32_t block, bool want_map, size_t n_thresholds)
+    {
+        DeltaEItpMaps out;
+        const uint32_t b = block ? block : 1;
+        out.cells_w = (width + b - 1) / b, out.cells_h = (height + b - 1) / b;
+        if (want_map) out.map.resize((size_t)count * out.cells_w * out.cells_h);
+        out.over.resize((size_t)count * n_thresholds);
+        return out;
+    }
+};
+// pairs [first, first + count) of a linear batch of width x height; returns once the results are on the host
+inline DeltaEItpMaps batch_delta_e_itp_map(const HipBackend &be, ce_batch *batch, uint32_t width, uint32_t height, uint32_t first, uint32_t count,
+                                           uint32_t depth = 10, float white_nits = 203.0f, uint32_t block = 1, bool want_map = true,
+                                           const std::vector<uint32_t> &thresholds_q20 = {})
+{
+    DeltaEItpMaps out = DeltaEItpMaps::sized(count, width, height, block, want_map, thresholds_q20.size());
+    detail::check(be, ce_batch_delta_e_itp_map(batch, first, count, depth, white_nits, block, out.map.empty() ? nullptr : out.map.data(),
+                                               out.map.size(), thresholds_q20.empty() ? nullptr : thresholds_q20.data(),
+                                               (uint32_t)thresholds_q20.size(), out.over.empty() ? nullptr : out.over.data()),
+                  "delta_e_itp_map", 0, 0, 0);
+    return out;
+}
+// one pair of packed float RGB, linear light with sRGB primaries (width * height * 3 floats each)
+inline DeltaEItpMaps delta_e_itp_map(const HipBackend &be, const float *reference, const float *test, uint32_t width, uint32_t height,
+                                     uint32_t depth = 10, float white_nits = 203.0f, uint32_t block = 1, bool want_map = true,
+                                     const std::vector<uint32_t> &thresholds_q20 = {})
+{
+    DeltaEItpMaps out = DeltaEItpMaps::sized(1, width, height, block, want_map, thresholds_q20.size());
+    const size_t len = (size_t)width * height * 12;
+    detail::check(be, ce_eval_pair_delta_e_itp_map(be.ctx(), reference, len, test, len, width, height, depth, white_nits, block,
+                                                   out.map.empty() ? nullptr : out.map.data(), out.map.size(),
+                                                   thresholds_q20.empty() ? nullptr : thresholds_q20.data(), (uint32_t)thresholds_q20.size(),
+                                                   out.over.empty() ? nullptr : out.over.data()),
+                  "delta_e_itp_map", width, height, len);
+    return out;
+}
 // the decision thresholds of PQ code values on linear light, T[1 .. 2^depth - 1] (a pure host function; empty when refused)
 inline std::vector<float> pq_code_thresholds(uint32_t depth, float white_nits = 203.0f)
 {

@@ -796,7 +796,7 @@ int ce_hlg_params(const ce_hlg *h, double out[5]);
  *   pq_sse       = the sum over the pixels of dRc^2 + dGc^2 + dBc^2, in u64.
  *   per pixel      s = (di * di + 0.25 * (dct * dct)) + dcp * dcp in f64, the integer differences converted first and every
  *                  operation rounded separately; e = 720 * sqrt(s) / (4096 * maxv) with a correctly rounded sqrt, the product
- *                  before the quotient; k = (u64) rint(e * 2^20), under 2^32.
+ *                  before the quotient; k = (u64) rint(e * 2^20), under 2^33.
  *   itp_sum_q20  = the sum of k;  itp_max_q20 = the maximum of k.
  *   pq_psnr          = 10 log10(maxv^2 / (pq_sse / (3 n))) in f64, n the pixels of an image; identical codes: what PSNR
  *                      returns for identical images, +infinity
@@ -826,6 +826,42 @@ int ce_eval_pair_hdr_fidelity(ce_ctx *ctx, const float *reference, size_t refere
  * handed. */
 int ce_pq_code_thresholds(uint32_t depth, float white_nits, float *out, size_t n);
 int ce_hdr_fidelity_matrices(float a[9], float b[9]);
+
+/* ---- Delta E ITP per pixel, per cell and over thresholds ----------------------------------------------
+ * Where a pair is bad, and how much of it: for every pixel of a pair of a LINEAR batch, k exactly as defined above for `depth`
+ * and `white_nits` - Delta E ITP in units of 2^-20 - and nothing new in arithmetic.
+ * Map value.  m = min(k, 2^32 - 1) as uint32_t.  The saturation is real: k needs 33 bits for pairs of imaginary colours inside
+ *   +-CE_LINEAR_MAX (about 6.9e9, a Delta E ITP of 6500, nine times black to peak), so a map value of 2^32 - 1 reads "4096 or
+ *   more"; the scores above carry k in 64 bits and do not saturate.  map.sum() = itp_sum_q20 and map.max() = itp_max_q20 for
+ *   every pair whose k stay under 2^32.
+ * block.  1: the map itself, [h][w].  A power of two up to 64: the MAXIMUM of m over each block x block cell, edge cells clipped
+ *   to the image, [ceil(h / block)][ceil(w / block)] - ce_batch_butteraugli_diffmap's rules.
+ * Exceedance counts.  over[j] = the number of pixels of the pair with m > thresholds_q20[j] (same units; CE_DELTA_E_ITP_Q20
+ *   is 1.0), for up to CE_DELTA_E_ITP_MAX_THRESHOLDS thresholds: exact integers over the pixels, never over cells, whatever
+ *   `block` is.  A threshold of 2^32 - 1 counts nothing.
+ * Everything is an integer maximum or an integer sum, so nothing depends on the grid or on the order.
+ * The call scores pairs [first, first + count) in one kernel on the context's stream, ordered behind the uploads queued so far
+ * as a launch is, with the pair table of the last bind; it blocks until the results are on the host.  ce_scores, stored maps,
+ * the HDR fidelity scores and whatever ce_batch_launch left to collect are untouched.  `map` receives
+ * [count][ceil(h / block)][ceil(w / block)] values and map_len is that number of ELEMENTS; `over` receives
+ * [count][n_thresholds].  map may be NULL with map_len 0 (counts only: no map is stored and no map memory allocated), over may
+ * be NULL with n_thresholds 0 and thresholds_q20 NULL, not both.  The device buffer of the maps of one call (map_len * 4
+ * bytes; at block 1, count * w * h * 4) is a grow-only buffer of the batch, freed with it; it is outside
+ * ce_estimate_batch_bytes.
+ * CE_ERR_INVALID_ARG, with the reason in ce_last_error and the batch still usable: a null batch; a batch that is not linear; a
+ * depth other than 10, 12 or 16; a white_nits that is not finite and > 0; both outputs NULL; count of 0 or a range past the
+ * batch's max_pairs; a block that is not 1, 2, 4, 8, 16, 32 or 64; a map_len other than the above; n_thresholds above 8; over
+ * without thresholds; thresholds without over. */
+#define CE_DELTA_E_ITP_MAX_THRESHOLDS 8
+#define CE_DELTA_E_ITP_Q20 1048576u
+int ce_batch_delta_e_itp_map(ce_batch *b, uint32_t first, uint32_t count, uint32_t depth, float white_nits, uint32_t block,
+                             uint32_t *map, size_t map_len, const uint32_t *thresholds_q20, uint32_t n_thresholds, uint64_t *over);
+/* One pair of packed float RGB through the same kernel, as ce_eval_pair_hdr_fidelity: lengths in bytes (width * height * 12),
+ * NaN -> 0 and the clamp of a linear image apply.  CE_ERR_INVALID_ARG as above and for a null image or an empty one,
+ * CE_ERR_BAD_LENGTH for a length that is not width * height * 12. */
+int ce_eval_pair_delta_e_itp_map(ce_ctx *ctx, const float *reference, size_t reference_len, const float *test, size_t test_len,
+                                 uint32_t width, uint32_t height, uint32_t depth, float white_nits, uint32_t block, uint32_t *map,
+                                 size_t map_len, const uint32_t *thresholds_q20, uint32_t n_thresholds, uint64_t *over);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------ */
 /* Bracket every kernel launch with a HIP event pair, recorded on the stream the kernel is launched on,
