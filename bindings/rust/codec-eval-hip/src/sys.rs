@@ -266,6 +266,8 @@ extern "C" {
     pub fn ce_batch_set_test_lut(b: *mut ce_batch, pair_index: u32, ref_index: u32, pixels: *const c_void, len: usize, format: c_int,
                                  lut: *const ce_lut) -> c_int;
     pub fn ce_batch_reference_slab(b: *mut ce_batch) -> *mut c_void;
+    pub fn ce_batch_references_changed(b: *mut ce_batch) -> c_int;
+    pub fn ce_batch_ref_stats(b: *const ce_batch, builds: *mut u32) -> c_int;
     pub fn ce_batch_test_slab(b: *mut ce_batch) -> *mut c_void;
     pub fn ce_batch_bind_pair(b: *mut ce_batch, pair_index: u32, ref_index: u32) -> c_int;
     pub fn ce_batch_run(b: *mut ce_batch, n_pairs: u32, metric_mask: u32, flags: u32, intensity_target: c_float,

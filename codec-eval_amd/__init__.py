@@ -227,6 +227,8 @@ _PROTOTYPES = [
     ("ce_batch_set_reference_lut", _i, [_vp, _u32, _vp, _sz, _i, _vp]),
     ("ce_batch_set_test_lut", _i, [_vp, _u32, _u32, _vp, _sz, _i, _vp]),
     ("ce_batch_reference_slab", _vp, [_vp]),
+    ("ce_batch_references_changed", _i, [_vp]),
+    ("ce_batch_ref_stats", _i, [_vp, C.POINTER(_u32 * 3)]),
     ("ce_batch_test_slab", _vp, [_vp]),
     ("ce_batch_bind_pair", _i, [_vp, _u32, _u32]),
     ("ce_batch_run", _i, [_vp, _u32, _u32, _u32, _f32, C.POINTER(CeScores)]),
@@ -1408,6 +1410,17 @@ class Batch:
     @property
     def test_slab(self) -> int:
         return int(lib().ce_batch_test_slab(self._h))
+
+    def references_changed(self):
+        """References were written through a kept `reference_slab` address: the next launch rebuilds what the metrics
+        derive from them (reading `reference_slab` again says the same)."""
+        self.ctx._check(lib().ce_batch_references_changed(self._h))
+
+    def ref_stats(self):
+        """(ssimulacra2, dssim, butteraugli): launches so far that (re)built that metric's reference-side state."""
+        out = (_u32 * 3)()
+        self.ctx._check(lib().ce_batch_ref_stats(self._h, C.byref(out)))
+        return tuple(out)
 
     def run(self, n_pairs: int, config: MetricConfig, intensity_target: float = DEFAULT_INTENSITY_TARGET,
             butteraugli_diffmap: bool = False, ssimulacra2_maps: bool = False) -> List[CeScores]:

@@ -1080,7 +1080,7 @@ __device__ __forceinline__ void store_min3(float v, float &min0, float &min1, fl
 // mask = FuzzyErosion(blurred0); ac[1] += 10 (blurred0 - blurred1)^2; then CombineChannelsToDiffmap — one pass
 // MaskPsychoImage's per-pixel mask values depend on the REFERENCE's blurred mask input only (FuzzyErosion, then the two
 // f64 rational curves of MaskY / MaskDcY): formed once per reference slot - not once per pair - into two planes that a
-// reference handle keeps with the PsychoImage; the pair part of CombineChannelsToDiffmap is the Malta kernel's epilogue.
+// batch keeps with the PsychoImage between launches; the pair part of CombineChannelsToDiffmap is the Malta kernel's epilogue.
 __global__ __launch_bounds__(TPB) void k_ba_mask_vals(const float *__restrict__ blurred, float *__restrict__ vals, geom g)
 {
     const uint32_t z = blockIdx.z;  // reference slot
@@ -1265,7 +1265,7 @@ void ce_butteraugli_free(ce_batch *b)
     b->ba_blk_max = nullptr;
     b->ba_blk_sums = nullptr;
     b->ba_pnorm = nullptr;
-    b->ba_ref_src = nullptr;
+    b->refs.of[CE_REF_BUTTERAUGLI].invalidate();
     b->ba_ready = false;
 }
 
@@ -1330,11 +1330,10 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
         return CE_ERR_BACKEND;
     }
     const uint32_t n_slots = n_refs_used + n_pairs, mr = b->max_refs;
-    // reference handle (ce_ref_*): the references' PsychoImage (both resolutions) of an earlier launch with the same
-    // intensity target is still in ba_psy, so only the distorted slots go through the per-image chain
-    const bool cached = b->keep_ref_pyramid && b->ba_ref_src == d_refs && b->ba_ref_count >= n_refs_used && b->ba_ref_intensity == intensity_target;
+    // the references' PsychoImage, mask input and mask values (both resolutions) of an earlier launch with the same
+    // intensity target are still in place?  Then only the distorted slots go through the per-image chain
+    const bool cached = b->refs.reuse(CE_REF_BUTTERAUGLI, d_refs, n_refs_used, ce_ref_param_f32(intensity_target));
     const uint32_t z0 = cached ? n_refs_used : 0, nz = n_slots - z0;
-    if (!cached) b->ref_builds[2]++;
     const blur_kernel k12 = make_kernel(1.2f), kLf = make_kernel(7.15593339443f), kHf = make_kernel(3.22489901262f),
                       kUhf = make_kernel(1.56416327805f), kMask = make_kernel(2.7f);
     float sw = 0.0f;
@@ -1432,7 +1431,7 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
         }
 
         // mask input: DiffPrecompute of HF + UHF (written by the HF split's epilogue into ba_s[1]), blurred with sigma 2.7 -
-        // per image slot (the references' once per reference; cached with the PsychoImage for reference handles), into
+        // per image slot (the references' once per reference; kept with the PsychoImage between launches), into
         // the level's own per-slot planes; then the
         // references' mask values (FuzzyErosion + the two mask curves), also once per reference
         {
@@ -1476,15 +1475,11 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
         }
 #undef CE_MALTA_ARGS
     }
-    if (b->keep_ref_pyramid && !cached) {
-        b->ba_ref_src = d_refs;
-        b->ba_ref_count = n_refs_used;
-        b->ba_ref_intensity = intensity_target;
-    }
     const auto &d0 = b->ba[0];
     CE_LAUNCH(ctx, "ba_score", k_ba_score, dim3(n_pairs), dim3(TPB), 0, b->ba_blk_max, b->ba_blk_sums, b->d_scores, b->ba_pnorm,
               b->ba_blocks, final_tiles, (double)d0.w * (double)d0.h);
     CE_HIP(ctx, hipGetLastError());
+    if (!cached) b->refs.built(CE_REF_BUTTERAUGLI, d_refs, n_refs_used, ce_ref_param_f32(intensity_target));
     return CE_OK;
 }
 

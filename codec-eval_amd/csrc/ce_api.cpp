@@ -499,6 +499,9 @@ static int batch_create(ce_ctx *ctx, uint32_t width, uint32_t height, uint32_t m
     b->depth[0] = ref_depth, b->depth[1] = test_depth;
     std::memcpy(b->deep_lut, deep_lut, sizeof(deep_lut));
     b->h_pair_ref.assign(max_pairs, 0);
+    // CE_KEEP_REFERENCE_STATE=0: an ordinary batch rebuilds its reference-side planes on every launch, for A/B runs
+    static const bool keep_reference_state = [] { const char *e = std::getenv("CE_KEEP_REFERENCE_STATE"); return !(e && e[0] == '0'); }();
+    b->refs.keep = keep_reference_state;
     int rc = CE_OK;
     auto chk = [&](hipError_t e, const char *what) {
         if (e != hipSuccess && rc == CE_OK) {
@@ -644,10 +647,10 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
     if (flags & CE_FLAG_XYB_ROUNDTRIP) {
         // MetricConfig::xyb_roundtrip: every metric sees the roundtripped reference (session.rs:447-456)
         if (!b->d_refs_rt) CE_HIP(ctx, hipMalloc(&b->d_refs_rt, b->img_bytes * b->max_refs + 16));
-        if (!(b->keep_ref_pyramid && b->refs_rt_valid)) {
+        if (!b->refs.reuse(CE_REF_ROUNDTRIP, b->d_refs, n_refs_used, 0)) {
             int rc = ce_launch_xyb_roundtrip(ctx, b->d_refs, b->d_refs_rt, (size_t)n_refs_used * b->w * b->h);
             if (rc != CE_OK) return rc;
-            b->refs_rt_valid = true;
+            b->refs.built(CE_REF_ROUNDTRIP, b->d_refs, n_refs_used, 0);
         }
         d_refs = b->d_refs_rt;
     }
@@ -1274,7 +1277,7 @@ int ce_ref_create(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, u
         ce_batch_destroy(b);
         return rc;
     }
-    b->keep_ref_pyramid = true;
+    b->refs.keep = true;  // whatever CE_KEEP_REFERENCE_STATE says: keeping the state is what a handle is
     *out = new ce_ref{ctx, b, flags};
     return CE_OK;
 }
@@ -1296,8 +1299,9 @@ int ce_ref_compare_many(ce_ref *ref, const uint8_t *const *tests, const size_t *
         if (rc != CE_OK) return rc;
         CE_HIP(ctx, hipMemcpyAsync(nb->d_refs, b->d_refs, b->img_bytes, hipMemcpyDeviceToDevice, ctx->stream));
         CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        nb->keep_ref_pyramid = true;
-        for (int k = 0; k < 3; k++) nb->ref_builds[k] = b->ref_builds[k];  // the handle's history (ce_ref_stats) carries over
+        ce_invalidate_reference_state(nb);  // a new slab: the first compare on it builds
+        nb->refs.keep = true;
+        for (int k = 0; k < 3; k++) nb->refs.builds[k] = b->refs.builds[k];  // the handle's history (ce_ref_stats) carries over
         ce_batch_destroy(b);
         ref->batch = b = nb;
     }
@@ -1382,7 +1386,13 @@ int ce_dssim_levels(uint32_t width, uint32_t height, uint32_t *n_levels, uint32_
 int ce_ref_stats(const ce_ref *ref, uint32_t builds[3])
 {
     if (!ref || !builds) return CE_ERR_INVALID_ARG;
-    for (int k = 0; k < 3; k++) builds[k] = ref->batch->ref_builds[k];
+    return ce_batch_ref_stats(ref->batch, builds);
+}
+
+int ce_batch_ref_stats(const ce_batch *b, uint32_t builds[3])
+{
+    if (!b || !builds) return CE_ERR_INVALID_ARG;
+    for (int k = 0; k < 3; k++) builds[k] = b->refs.builds[k];
     return CE_OK;
 }
 
@@ -1506,6 +1516,7 @@ int ce_debug_dssim_walk_rows(ce_batch *b, uint32_t rows)
     // ds_part holds a strip's partial sums per 2-row tile (dssim.hip: ds_blocks), so every allowed walk fits
     if (!b || (rows != 0 && (rows < 2 || rows > 64 || (rows & (rows - 1)) != 0))) return CE_ERR_INVALID_ARG;
     b->debug_ds_rows = rows;
+    b->refs.of[CE_REF_DSSIM].invalidate();  // the references' planes are walked at the new length too
     return CE_OK;
 }
 

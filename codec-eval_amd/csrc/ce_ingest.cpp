@@ -16,13 +16,7 @@
 
 // the reference slab is about to change: whatever was derived from it (XYB roundtrip, SSIMULACRA2 XYB pyramid, DSSIM
 // img / mu / sq pyramid, Butteraugli PsychoImage) is rebuilt by the next launch
-void ce_invalidate_reference_state(ce_batch *b)
-{
-    b->ssim2_ref_src = nullptr;
-    b->ds_ref_src = nullptr;
-    b->ba_ref_src = nullptr;
-    b->refs_rt_valid = false;
-}
+void ce_invalidate_reference_state(ce_batch *b) { b->refs.invalidate(); }
 
 // kernels (context stream) must see everything uploaded so far
 int ce_flush_uploads(ce_batch *b)
@@ -798,6 +792,12 @@ void *ce_batch_reference_slab(ce_batch *b)
     if (!b) return nullptr;
     ce_invalidate_reference_state(b);  // the caller may overwrite references behind our back
     return b->d_refs;
+}
+int ce_batch_references_changed(ce_batch *b)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    ce_invalidate_reference_state(b);
+    return CE_OK;
 }
 void *ce_batch_test_slab(ce_batch *b) { return b ? b->d_tests : nullptr; }
 

@@ -17,6 +17,7 @@
 #include "ce_metrics.h"
 #include "ce_metrics_debug.h"
 #include "ce_plan.h"
+#include "ce_ref_state.h"
 
 #define CE_MAX_SCALES 6      // SSIMULACRA2 pyramid depth
 #define CE_SSIM2_STREAMS 5   // blur(a), blur(b), blur(a*a), blur(b*b), blur(a*b)
@@ -222,16 +223,11 @@ struct ce_batch {
     // XCD-aware work lists of the row / column pass (ssim2.hip): launch id -> (block, channel, pair)
     ce_xcd_list work_h, work_v;    // level 0
     ce_xcd_list work_ht, work_vt;  // the merged launch of levels 1..
-    // reference handles (ce_ref_*): the references' XYB pyramid of the last SSIMULACRA2 run stays valid
-    // until a reference is replaced, so later compares only build the distorted side
-    bool keep_ref_pyramid = false;
-    const uint8_t *ssim2_ref_src = nullptr;  // reference slab the cached pyramid was built from
-    uint32_t ssim2_ref_count = 0;            // ...and how many references it covers
-    int ssim2_ref_levels = 0;
-    bool refs_rt_valid = false;              // d_refs_rt holds the XYB roundtrip of the current references
+    // What the planes derived from the references were built from, per metric and for d_refs_rt (ce_ref_state.h): they stay
+    // valid until a reference is written, so later launches only build the distorted side.  Each metric's launch function
+    // touches its own record only (the chains of a forked batch are enqueued by three host threads).
+    ce_ref_states refs;
     int debug_max_scales = CE_MAX_SCALES;  // test hook: stop the pyramid early
-    // launches in which the reference-side state of [SSIMULACRA2, DSSIM, Butteraugli] was (re)built (ce_ref_stats)
-    uint32_t ref_builds[3] = {0, 0, 0};
 
     // DSSIM working set (dssim.hip); planes are [slot][3][plane] with the level's own geometry
     struct dssim_level { uint32_t w, h, pitch; size_t plane; };
@@ -240,8 +236,6 @@ struct ce_batch {
     float *ds_lin[2] = {};     // linear RGB of the current and the next level
     float *ds_img = nullptr;   // [max_pairs][3][plane_0]: L, a', b' (chroma pre-blurred) of the distorted images, one level at a time
     float *ds_rimg[CE_DSSIM_SCALES] = {}, *ds_rmu[CE_DSSIM_SCALES] = {}, *ds_rsq[CE_DSSIM_SCALES] = {};  // the references' planes, per level: [max_refs][3][plane_l]
-    const uint8_t *ds_ref_src = nullptr;  // reference slab those planes were built from (valid while keep_ref_pyramid)
-    uint32_t ds_ref_count = 0;
     float *ds_map = nullptr;   // [level][max_pairs][plane_l] channel-averaged SSIM maps (SsimMap.map)
     double *ds_part = nullptr; // [pairs][levels][2][blocks] partial sums (sum, abs-dev)
     double *ds_level_scores = nullptr;  // [pairs][CE_DSSIM_SCALES]: after a launch, every level's score (SsimMap.ssim)
@@ -282,9 +276,6 @@ struct ce_batch {
     uint32_t ba_blocks = 0;
     ce_xcd_list ba_work[2];  // Malta's launch order, per resolution level
     bool ba_ready = false;
-    const uint8_t *ba_ref_src = nullptr;  // reference slab the references' PsychoImage in ba_psy was built from
-    uint32_t ba_ref_count = 0;
-    float ba_ref_intensity = 0.0f;
 
     // HDR fidelity (hdr_fidelity.hip): [max_pairs][3] exact integers on the device and page-locked, made by the first call
     unsigned long long *d_hdr = nullptr, *h_hdr = nullptr;

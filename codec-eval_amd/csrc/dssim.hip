@@ -161,7 +161,7 @@ void ce_dssim_free(ce_batch *b)
         b->ds_rimg[l] = b->ds_rmu[l] = b->ds_rsq[l] = nullptr;
         ce_free_xcd_list(&b->ds_gwork[l]);
     }
-    b->ds_ref_src = nullptr;
+    b->refs.of[CE_REF_DSSIM].invalidate();
     hipFree(b->ds_part); hipFree(b->ds_level_scores); hipFree(b->ds_cells);
     b->ds_img = b->ds_map = b->ds_cells = nullptr;
     b->ds_cells_cap = 0;
@@ -190,7 +190,7 @@ static int dssim_allocate(ce_batch *b)
     CE_HIP(ctx, hipMalloc(&b->ds_lin[1], slots * 3 * p1 * sizeof(float)));
     CE_HIP(ctx, hipMalloc(&b->ds_img, (size_t)b->max_pairs * 3 * p0 * sizeof(float)));  // the distorted images' img, one level at a time
     // the references' planes, one set per level: they outlive the level loop (Dssim::create_image of the reference is
-    // run once per reference, dssim.rs:54-59; a reference handle keeps them across compares)
+    // run once per reference, dssim.rs:54-59; kept across launches until a reference is written, ce_ref_state.h)
     for (int l = 0; l < n; l++) {
         const size_t rb = (size_t)b->max_refs * 3 * b->ds[l].plane * sizeof(float);
         CE_HIP(ctx, hipMalloc(&b->ds_rimg[l], rb));
@@ -226,10 +226,9 @@ int ce_launch_dssim(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
     ce_ctx *ctx = b->ctx;
     int rc = dssim_prepare(b);
     if (rc != CE_OK) return rc;
-    // reference handle (ce_ref_*): the references' img / mu / sq pyramid of an earlier launch is still valid
-    const bool cached = b->keep_ref_pyramid && b->ds_ref_src == d_refs && b->ds_ref_count >= n_refs_used;
+    // the references' img / mu / sq pyramid of an earlier launch is still valid?
+    const bool cached = b->refs.reuse(CE_REF_DSSIM, d_refs, n_refs_used, 0);
     const uint32_t z0 = cached ? n_refs_used : 0;
-    if (!cached) b->ref_builds[1]++;
     ds_geom g{};
     ds_tail tail{};
     for (int l = 0; l < b->ds_levels; l++) {
@@ -252,13 +251,10 @@ int ce_launch_dssim(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
         CE_LAUNCH(ctx, "dssim_absdev", k_dssim_absdev, gp, dim3(TPB), 0, (const float *)b->ds_map, b->ds_level_scores, b->ds_part, tail, nl,
                   b->ds_blocks);
     }
-    if (b->keep_ref_pyramid && !cached) {
-        b->ds_ref_src = d_refs;
-        b->ds_ref_count = n_refs_used;
-    }
     CE_LAUNCH(ctx, "dssim_finalize", k_dssim_finalize_pairs, dim3(n_pairs), dim3(64), 0, b->ds_part,
               b->ds_level_scores, b->d_scores, n_pairs, (uint32_t)b->ds_levels, b->ds_blocks, g);
     CE_HIP(ctx, hipGetLastError());
+    if (!cached) b->refs.built(CE_REF_DSSIM, d_refs, n_refs_used, 0);
     return CE_OK;
 }
 

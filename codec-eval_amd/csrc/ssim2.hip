@@ -777,6 +777,7 @@ void ce_ssim2_free(ce_batch *b)
     b->s2_cells_cap = 0;
     b->s2_map_pairs = b->s2_norm_pairs = 0;
     for (ce_xcd_list *L : {&b->work_h, &b->work_v, &b->work_ht, &b->work_vt}) ce_free_xcd_list(L);
+    b->refs.of[CE_REF_SSIM2].invalidate();
     b->ssim2_ready = false;
 }
 
@@ -873,12 +874,11 @@ int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
     rg_consts rg;
     ce_ssim2_recursive_gaussian(rg.mul_in, rg.mul_prev);
     const uint32_t n_slots = n_refs_used + n_pairs;
-    // Ssimulacra2Reference semantics (crates/codec-iter/src/eval.rs:138-149): a reference handle keeps the
-    // references' XYB pyramid between compares, so the front end then only runs over the distorted slots
-    const bool cached = b->keep_ref_pyramid && b->ssim2_ref_src == d_refs && b->ssim2_ref_count >= n_refs_used &&
-                        b->ssim2_ref_levels == std::min(b->n_scales, b->debug_max_scales);
+    // Ssimulacra2Reference semantics (crates/codec-iter/src/eval.rs:138-149): a batch keeps the references' XYB pyramid
+    // between launches, so the front end then only runs over the distorted slots
+    const int levels = std::min(b->n_scales, b->debug_max_scales);
+    const bool cached = b->refs.reuse(CE_REF_SSIM2, d_refs, n_refs_used, (uint64_t)levels);
     const uint32_t z0 = cached ? n_refs_used : 0;
-    if (!cached) b->ref_builds[0]++;
     using hblur_fn = void (*)(const float *, const uint32_t *, float *, uint32_t, uint32_t, uint32_t, size_t, uint32_t,
                               rg_consts, lvl_table, const uint2 *, const uint32_t *);
     using vblur_fn = void (*)(const float *, const float *, const uint32_t *, double *, uint32_t, uint32_t, uint32_t,
@@ -888,7 +888,6 @@ int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
     const vblur_fn v_l0 = k_ssim2_vblur_dma<0, false>, v_tail = k_ssim2_vblur_dma<-1, false>;
     const vblur_fn v_l0_map = k_ssim2_vblur_dma<0, true>, v_tail_map = k_ssim2_vblur_dma<-1, true>;
     scale_geom g{};
-    const int levels = std::min(b->n_scales, b->debug_max_scales);
     // Front end on the context's stream, level by level (level s+1 needs level s's linear planes).  Level 0's row
     // and column pass run on their own stream as soon as level 0's planes exist; levels 1.. share ONE row-pass and
     // ONE column-pass launch that simply follow the front end on the context's stream, so they overlap level 0.
@@ -981,14 +980,10 @@ int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
         CE_HIP(ctx, hipStreamWaitEvent(CE_STREAM(ctx), b->ev_done[0], 0));
         if (tab.n && s1 != CE_STREAM(ctx)) CE_HIP(ctx, hipStreamWaitEvent(CE_STREAM(ctx), b->ev_done[1], 0));
     }
-    if (b->keep_ref_pyramid && !cached) {
-        b->ssim2_ref_src = d_refs;
-        b->ssim2_ref_count = n_refs_used;
-        b->ssim2_ref_levels = levels;
-    }
     CE_LAUNCH(ctx, "ssim2_finalize", k_ssim2_finalize, dim3(n_pairs), dim3(128), 0, b->d_partials, b->d_avg,
               b->d_scores, (uint32_t)levels, b->max_vblocks, g);
     CE_HIP(ctx, hipGetLastError());
+    if (!cached) b->refs.built(CE_REF_SSIM2, d_refs, n_refs_used, (uint64_t)levels);
     return CE_OK;
 }
 

@@ -248,9 +248,25 @@ int ce_batch_set_reference_lut(ce_batch *b, uint32_t ref_index, const void *pixe
 int ce_batch_set_test_lut(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format,
                           const ce_lut *lut);
 /* device pointers of the packed u8 slabs ([max_refs][h][w][3], [max_pairs][h][w][3]) so a caller that
- * already has pixels in HBM (e.g. a GPU decoder) can write them in place */
+ * already has pixels in HBM (e.g. a GPU decoder) can write them in place.
+ * A batch keeps what its metrics derive from the references alone (the XYB roundtrip, SSIMULACRA2's XYB pyramid, DSSIM's
+ * img / mu / sq pyramid, Butteraugli's PsychoImage and mask planes) from one launch to the next and rebuilds it only after
+ * a reference has been written.  Every ce_batch_set_reference*, ce_batch_resample into the batch and ce_eval_batch says so
+ * itself; a write through the slab pointer is invisible to the library.  ce_batch_reference_slab therefore drops that
+ * state when it hands the pointer out, and a caller that KEEPS the pointer must, after writing references through it and
+ * before the next launch, either fetch the pointer again or call ce_batch_references_changed (which drops the state and
+ * does nothing else; CE_ERR_INVALID_ARG for a null batch) - otherwise that launch scores against the planes of the old
+ * references.  The test slab has no such rule: nothing derived from a test image outlives a launch. */
 void *ce_batch_reference_slab(ce_batch *b);
+int ce_batch_references_changed(ce_batch *b);
 void *ce_batch_test_slab(ce_batch *b);
+/* builds[k] = launches of this batch so far that had to (re)build the reference-side state of SSIMULACRA2 (k = 0),
+ * DSSIM (1), Butteraugli (2): what ce_ref_stats returns for a handle.  A launch rebuilds a metric's state when a reference
+ * was written since it was built, when it uses more references than the state covers, when Butteraugli's intensity target
+ * or the CE_FLAG_XYB_ROUNDTRIP flag differs from the launch that built it, or when the metric has not run on the batch
+ * yet; rebinding pairs and replacing test images rebuild nothing.  CE_KEEP_REFERENCE_STATE=0 in the environment (read once
+ * per process; a measurement switch, no score depends on it) makes every launch of an ordinary batch rebuild. */
+int ce_batch_ref_stats(const ce_batch *b, uint32_t builds[3]);
 int ce_batch_bind_pair(ce_batch *b, uint32_t pair_index, uint32_t ref_index);
 /* run the hot path over pairs [0, n_pairs); blocks until scores are on the host */
 int ce_batch_run(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_t flags, float intensity_target,
