@@ -325,18 +325,7 @@ int set_rgb8(ce_batch *b, bool test, uint32_t pair_index, uint32_t ref_index, co
         [&](uint8_t *slot) { return upload(b, slot, rgb); });
 }
 
-// ---- tagged code values into a linear batch: CICP (cicp.hip) and HLG (hlg.hip; section 18) ------------
-
-// what one CICP ingest runs with: the device table of (transfer, depth, white_nits) and the matrix (has_matrix: primaries != 1);
-// an HLG ingest runs with the same and with ce_hlg_params' five doubles
-struct cicp_plan {
-    const float *d_table;
-    uint32_t maxv;
-    bool has_matrix;
-    float m[9];
-    bool hlg = false;
-    double hlg_params[5];
-};
+// ---- tagged code values into a linear batch: CICP and HLG (cicp.hip; DESIGN.md sections 15, 18) -------------------
 
 // The two descriptions share their checks and their entry points, written once below over `Desc`; what differs is here:
 // the words of their messages, the check of the description alone (colour_check: fills maxv, the matrix and, for HLG, the
@@ -348,7 +337,7 @@ route_words words(const ce_colour *) { return {"CICP", "colour description's"}; 
 route_words words(const ce_hlg *) { return {"HLG", "description's"}; }
 
 // depth, transfer and primaries from the lists of the header
-int colour_check(ce_ctx *ctx, const ce_colour *c, cicp_plan *plan)
+int colour_check(ce_ctx *ctx, const ce_colour *c, ce_linear_pixel *plan)
 {
     if (!ce_deep_depth_ok(c->depth)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "CICP ingest: depth must be 8, 10, 12 or 16, got " + std::to_string(c->depth));
     if (c->transfer != 13 && c->transfer != 8 && c->transfer != 16)
@@ -381,7 +370,7 @@ int hlg_describe(ce_ctx *ctx, const ce_hlg *h, double out[5])
     return CE_OK;
 }
 
-int colour_check(ce_ctx *ctx, const ce_hlg *h, cicp_plan *plan)
+int colour_check(ce_ctx *ctx, const ce_hlg *h, ce_linear_pixel *plan)
 {
     if (int rc = hlg_describe(ctx, h, plan->hlg_params)) return rc;
     ce_build_colour_matrix(h->primaries, plan->m);
@@ -412,7 +401,7 @@ int ingest_table(ce_ctx *ctx, int transfer, uint32_t depth, uint32_t white_bits,
 }
 
 // the transfer table of a checked description, keyed by (transfer, depth, white); white only matters to PQ
-int table_dev(ce_ctx *ctx, const ce_colour *c, cicp_plan *plan)
+int table_dev(ce_ctx *ctx, const ce_colour *c, ce_linear_pixel *plan)
 {
     const float white = c->transfer == 16 ? c->white_nits : 0.0f;
     uint32_t white_bits;
@@ -423,14 +412,14 @@ int table_dev(ce_ctx *ctx, const ce_colour *c, cicp_plan *plan)
 }
 
 // the inverse-OETF table of a checked description, one per depth, under H.273's code for HLG: (18, depth, 0)
-int table_dev(ce_ctx *ctx, const ce_hlg *h, cicp_plan *plan)
+int table_dev(ce_ctx *ctx, const ce_hlg *h, ce_linear_pixel *plan)
 {
     return ingest_table(ctx, 18, h->depth, 0u, "HLG table", [&](float *t) { ce_build_hlg_table(plan->maxv, t); }, &plan->d_table);
 }
 
 // one image of code values with its description: everything refused about either, then the plan
 template <class Desc>
-int tagged_check(ce_ctx *ctx, const void *pixels, size_t len, int format, const Desc *d, size_t n_px, cicp_plan *plan)
+int tagged_check(ce_ctx *ctx, const void *pixels, size_t len, int format, const Desc *d, size_t n_px, ce_linear_pixel *plan)
 {
     const std::string route = std::string(words(d).name) + " ingest: ";
     if (!pixels || !d) return ce_fail(ctx, CE_ERR_INVALID_ARG, route + "null pointer");
@@ -443,16 +432,8 @@ int tagged_check(ce_ctx *ctx, const void *pixels, size_t len, int format, const 
     return table_dev(ctx, d, plan);
 }
 
-// the conversion of one checked image of code values at d_src into d_dst: the CICP pixel, or with plan.hlg the HLG pixel
-int launch_cicp_into(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, float *d_dst, size_t n_px, const cicp_plan &plan)
-{
-    const float *m = plan.has_matrix ? plan.m : nullptr;
-    if (plan.hlg) return ce_launch_hlg(ctx, stream, format, d_src, d_dst, n_px, plan.d_table, plan.maxv, m, plan.hlg_params);
-    return ce_launch_cicp(ctx, stream, format, d_src, d_dst, n_px, plan.d_table, plan.maxv, m);
-}
-
 // one checked image through the wide staging pair into the slot at dst
-int upload_cicp(ce_batch *b, uint8_t *dst, const void *pixels, size_t len, int format, const cicp_plan &plan)
+int upload_cicp(ce_batch *b, uint8_t *dst, const void *pixels, size_t len, int format, const ce_linear_pixel &plan)
 {
     ce_ctx *ctx = b->ctx;
     CE_HIP(ctx, hipSetDevice(ctx->device));
@@ -460,7 +441,7 @@ int upload_cicp(ce_batch *b, uint8_t *dst, const void *pixels, size_t len, int f
     if (int rc = wide_acquire(b, &k)) return rc;
     std::memcpy(b->h_wide[k], pixels, len);
     CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], len, hipMemcpyHostToDevice, b->up_stream));
-    if (int rc = launch_cicp_into(ctx, b->up_stream, format, b->d_wide[k], reinterpret_cast<float *>(dst), (size_t)b->w * b->h, plan)) return rc;
+    if (int rc = ce_launch_tagged(ctx, b->up_stream, format, b->d_wide[k], reinterpret_cast<float *>(dst), (size_t)b->w * b->h, plan)) return rc;
     return wide_close(b, k);
 }
 
@@ -472,7 +453,7 @@ template <class Desc>
 int set_tagged(ce_batch *b, bool test, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format, const Desc *d,
                const char *wants_linear)
 {
-    cicp_plan plan;
+    ce_linear_pixel plan;
     return set_slot(
         b, test, pair_index, ref_index, kind_rule{false, wants_linear},
         [&] { return tagged_check(b->ctx, pixels, len, format, d, (size_t)b->w * b->h, &plan); },
@@ -487,15 +468,15 @@ int tagged_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, co
     const std::string route = std::string(words(d).name) + " ingest: ";
     if (w == 0 || h == 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, route + "empty image");
     const size_t n_px = (size_t)w * h;
-    cicp_plan plan;
+    ce_linear_pixel plan;
     if (int rc = tagged_check(ctx, pixels, len, format, d, n_px, &plan)) return rc;
     if (out_len != n_px * 3) return ce_fail(ctx, CE_ERR_BAD_LENGTH, route + "out_len must be " + std::to_string(n_px * 3) + " floats, got " + std::to_string(out_len));
     return ce_leaf_roundtrip(ctx, pixels, len, out, n_px * 12, [&](uint8_t *d_in, uint8_t *d_out) {
-        return launch_cicp_into(ctx, ctx->stream, format, d_in, reinterpret_cast<float *>(d_out), n_px, plan);
+        return ce_launch_tagged(ctx, ctx->stream, format, d_in, reinterpret_cast<float *>(d_out), n_px, plan);
     });
 }
 
-// ---- planar Y'CbCr (yuv.hip), and with a description into a linear batch (yuv_cicp.hip, yuv_hlg.hip) -----
+// ---- planar Y'CbCr (yuv.hip), and with a description into a linear batch (yuv_cicp.hip) -------------------
 
 // a checked ce_yuv_image: what the kernel reads, and each plane's rows for the host copy
 struct yuv_plan {
@@ -550,7 +531,7 @@ int yuv_check(ce_ctx *ctx, const ce_yuv_image *img, uint32_t w, uint32_t h, uint
 // everything *_yuv refuses about the image and *_cicp / *_hlg about the description, and their one joint rule: the integer
 // RGB grid between the two halves (d->depth) is no coarser than the samples
 template <class Desc>
-int yuv_tagged_check(ce_ctx *ctx, const ce_yuv_image *img, const Desc *d, uint32_t w, uint32_t h, yuv_plan *plan, cicp_plan *lin)
+int yuv_tagged_check(ce_ctx *ctx, const ce_yuv_image *img, const Desc *d, uint32_t w, uint32_t h, yuv_plan *plan, ce_linear_pixel *lin)
 {
     const route_words rw = words(d);
     if (!img) return ce_fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: null image");
@@ -576,21 +557,18 @@ void yuv_pack(const ce_yuv_image *img, yuv_plan *plan, uint8_t *h_stage, const u
 }
 
 // the conversion of one checked image into dst: integer RGB (u8, or u16 of `depth`), or with `lin` the fused linear-light
-// ingest of a linear batch (yuv_cicp.hip; yuv_hlg.hip for an HLG plan), whose integer grid is the one plan.dev.k was built for
+// ingest of a linear batch (yuv_cicp.hip: the CICP or the HLG pixel, as `lin` says), whose integer grid is the one plan.dev.k
+// was built for
 int launch_yuv_into(ce_ctx *ctx, hipStream_t stream, const yuv_plan &plan, uint32_t w, uint32_t h, uint8_t *dst, uint32_t depth,
-                    const cicp_plan *lin)
+                    const ce_linear_pixel *lin)
 {
-    if (lin && lin->hlg)
-        return ce_launch_yuv_hlg(ctx, stream, plan.dev, w, h, reinterpret_cast<float *>(dst), lin->d_table, lin->maxv, lin->has_matrix ? lin->m : nullptr,
-                                 lin->hlg_params);
-    if (lin)
-        return ce_launch_yuv_cicp(ctx, stream, plan.dev, w, h, reinterpret_cast<float *>(dst), lin->d_table, lin->maxv, lin->has_matrix ? lin->m : nullptr);
+    if (lin) return ce_launch_yuv_tagged(ctx, stream, plan.dev, w, h, reinterpret_cast<float *>(dst), *lin);
     return ce_launch_yuv(ctx, stream, plan.dev, w, h, dst, depth != 0, depth ? depth : 8);
 }
 
 // one Y'CbCr image into a slab slot on the batch's upload stream: device planes are read in place, host planes go
 // through the wide staging pair (the packed planes are at most 6 bytes per pixel and a few bytes)
-int upload_yuv(ce_batch *b, uint8_t *dst, const ce_yuv_image *img, yuv_plan &plan, uint32_t depth, const cicp_plan *lin)
+int upload_yuv(ce_batch *b, uint8_t *dst, const ce_yuv_image *img, yuv_plan &plan, uint32_t depth, const ce_linear_pixel *lin)
 {
     ce_ctx *ctx = b->ctx;
     CE_HIP(ctx, hipSetDevice(ctx->device));
@@ -610,7 +588,7 @@ int upload_yuv(ce_batch *b, uint8_t *dst, const ce_yuv_image *img, yuv_plan &pla
 }
 
 // one checked image -> host memory through the leaf scratch, on the context's stream; depth and lin as launch_yuv_into's
-int yuv_leaf(ce_ctx *ctx, const ce_yuv_image *image, yuv_plan &plan, uint32_t w, uint32_t h, uint32_t depth, const cicp_plan *lin, void *out,
+int yuv_leaf(ce_ctx *ctx, const ce_yuv_image *image, yuv_plan &plan, uint32_t w, uint32_t h, uint32_t depth, const ce_linear_pixel *lin, void *out,
              size_t out_bytes)
 {
     const bool host = image->memory == CE_MEM_HOST;
@@ -650,7 +628,7 @@ int yuv_to_linear(ce_ctx *ctx, const ce_yuv_image *image, const Desc *d, uint32_
     if (!out) return ce_fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: null output");
     if (w == 0 || h == 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: empty image");
     yuv_plan plan;
-    cicp_plan lin;
+    ce_linear_pixel lin;
     if (int rc = yuv_tagged_check(ctx, image, d, w, h, &plan, &lin)) return rc;
     const size_t samples = (size_t)w * h * 3;
     if (out_len != samples)
@@ -678,7 +656,7 @@ template <class Desc>
 int set_yuv_tagged(ce_batch *b, bool test, uint32_t pair_index, uint32_t ref_index, const ce_yuv_image *image, const Desc *d, const char *wants_linear)
 {
     yuv_plan plan;
-    cicp_plan lin;
+    ce_linear_pixel lin;
     return set_slot(
         b, test, pair_index, ref_index, kind_rule{false, wants_linear},
         [&] { return yuv_tagged_check(b->ctx, image, d, b->w, b->h, &plan, &lin); },

@@ -89,7 +89,7 @@ struct ce_ctx {
     struct ce_batch *leaf_batch[CE_LEAF_KINDS] = {};
     // transfer tables of the CICP ingest (cicp.hip), 2^depth entries each, keyed by (transfer, depth, bits of white_nits);
     // built by the first ingest that needs one and kept until the context goes (ce_ingest.cpp: ingest_table).  The HLG ingest's
-    // inverse-OETF tables (hlg.hip) live here too, one per depth, under H.273's code for HLG: (18, depth, 0)
+    // inverse-OETF tables (cicp.hip) live here too, one per depth, under H.273's code for HLG: (18, depth, 0)
     std::map<std::tuple<int, uint32_t, uint32_t>, float *> cicp_tables;
     // threshold tables of the HDR fidelity scores (hdr_fidelity.hip), keyed by (depth, bits of white_nits), built by the first
     // call that needs one and kept until the context goes (ce_api.cpp: hdr_table_dev): T[1 .. maxv], padded to a multiple of
@@ -468,7 +468,7 @@ struct ce_yuv_dev {
 };
 // w x h pixels of `src` -> packed RGB at d_dst: u8 (depth_out = 8, out16 = false) or u16 of depth_out, one launch (yuv.hip)
 int ce_launch_yuv(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32_t w, uint32_t h, void *d_dst, bool out16, uint32_t depth_out);
-// what the three launchers of Y'CbCr planes put into yuv_kernel.h's yuv_args: `src` at w x h, the integer RGB clamped to m
+// what the two launchers of Y'CbCr planes put into yuv_kernel.h's yuv_args: `src` at w x h, the integer RGB clamped to m
 template <class YuvArgs>
 inline void ce_fill_yuv_args(YuvArgs &a, const ce_yuv_dev &src, uint32_t w, uint32_t h, int64_t m)
 {
@@ -491,33 +491,35 @@ int ce_launch_alpha(ce_ctx *ctx, hipStream_t stream, const void *d_src, bool src
 
 // n_samples floats at d_src (16-byte aligned staging) -> d_dst with NaN -> 0 and the clamp to +-CE_LINEAR_MAX (cicp.hip)
 int ce_launch_linear_sanitise(ce_ctx *ctx, hipStream_t stream, const float *d_src, float *d_dst, size_t n_samples);
-// n_pixels RGB(A) pixels of u8 / u16 samples at d_src (16-byte aligned staging; format: CE_PIXEL_RGB8 / RGBA8 / RGB16 /
-// RGBA16) -> packed f32 RGB at d_dst: table[min(v, maxv)] per channel, then, with a matrix (nullptr: none), the 3 x 3
-// product in separately rounded f32 operations, then the clamp of a linear image (cicp.hip)
-int ce_launch_cicp(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, float *d_dst, size_t n_pixels, const float *d_table,
-                   uint32_t maxv, const float *matrix);
-// what the four launchers of a linear-light pixel put into cicp_pixel.h's cicp_args: the slot, the table and the matrix
-// (nullptr: none, m is not read)
-template <class CicpArgs>
-inline void ce_fill_cicp_args(CicpArgs &a, float *d_dst, const float *d_table, uint32_t maxv, const float *matrix)
+// What one ingest into a linear batch converts a pixel's three code values with (checked and filled by ce_ingest.cpp): the
+// device table of maxv + 1 floats - a CICP transfer's, or with `hlg` the inverse OETF's - the primaries matrix (has_matrix:
+// primaries other than 1) and, for HLG, ce_hlg_params' five doubles {kR, kG, kB, gamma - 1, A}
+struct ce_linear_pixel {
+    const float *d_table;
+    uint32_t maxv;
+    bool has_matrix;
+    float m[9];
+    bool hlg = false;
+    double hlg_params[5];
+};
+// what the two launchers below put into hlg_pixel.h's hlg_args, whose `c` alone is the CICP pixel's cicp_args: the slot, the
+// table, the matrix (without one m is not read) and, for HLG, the five doubles
+template <class HlgArgs>
+inline void ce_fill_pixel_args(HlgArgs &a, float *d_dst, const ce_linear_pixel &px)
 {
-    a.dst = d_dst, a.table = d_table, a.maxv = maxv;
-    if (matrix)
-        for (int i = 0; i < 9; i++) a.m[i] = matrix[i];
+    a.c.dst = d_dst, a.c.table = px.d_table, a.c.maxv = px.maxv;
+    if (px.has_matrix)
+        for (int i = 0; i < 9; i++) a.c.m[i] = px.m[i];
+    if (px.hlg) a.kr = px.hlg_params[0], a.kg = px.hlg_params[1], a.kb = px.hlg_params[2], a.gm1 = px.hlg_params[3], a.a = px.hlg_params[4];
 }
-
-// w x h pixels of `src`, whose k was built for depth_out = log2(maxv + 1), -> packed f32 RGB at d_dst: ce_launch_yuv's integer
-// RGB in [0, maxv] handed pixel by pixel to ce_launch_cicp's table, matrix (nullptr: none) and clamp, one launch (yuv_cicp.hip)
-int ce_launch_yuv_cicp(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32_t w, uint32_t h, float *d_dst, const float *d_table,
-                       uint32_t maxv, const float *matrix);
-
-// ce_launch_cicp with the HLG pixel (hlg.hip): d_table is the inverse-OETF table, params = {kR, kG, kB, gamma - 1, A} as
-// ce_hlg_params returns them; between the gather and the matrix, k = (float)(A * hlg_pow(ys, gamma - 1)) scales the three
-int ce_launch_hlg(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, float *d_dst, size_t n_pixels, const float *d_table,
-                  uint32_t maxv, const float *matrix, const double params[5]);
-// ce_launch_yuv_cicp with the HLG pixel, one launch (yuv_hlg.hip)
-int ce_launch_yuv_hlg(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32_t w, uint32_t h, float *d_dst, const float *d_table,
-                      uint32_t maxv, const float *matrix, const double params[5]);
+// n_pixels RGB(A) pixels of u8 / u16 samples at d_src (16-byte aligned staging; format: CE_PIXEL_RGB8 / RGBA8 / RGB16 /
+// RGBA16) -> packed f32 RGB at d_dst, one launch (cicp.hip).  CICP: table[min(v, maxv)] per channel, then, with a matrix, the
+// 3 x 3 product in separately rounded f32 operations, then the clamp of a linear image.  HLG: between the gather and the
+// matrix, k = (float)(A * hlg_pow(ys, gamma - 1)) scales the three.
+int ce_launch_tagged(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, float *d_dst, size_t n_pixels, const ce_linear_pixel &px);
+// w x h pixels of `src`, whose k was built for depth_out = log2(px.maxv + 1), -> packed f32 RGB at d_dst: ce_launch_yuv's
+// integer RGB in [0, maxv] handed pixel by pixel to ce_launch_tagged's pixel, one launch (yuv_cicp.hip)
+int ce_launch_yuv_tagged(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32_t w, uint32_t h, float *d_dst, const ce_linear_pixel &px);
 
 // pairs [0, n_pairs) of a linear batch -> d_out[pair][3] = pq_sse, itp_sum_q20, itp_max_q20, cleared and filled on the
 // launching stream (hdr_fidelity.hip): d_table = T[1 .. maxv], 64-byte aligned, d_coarse the level staged in LDS (the table

@@ -1,9 +1,11 @@
-// The device code of the CICP ingest and of the linear-f32 upload (cicp.hip), kept free of anything but the HIP keywords,
-// uint2 / uint4 / float4 and blockIdx / threadIdx, so that tests/cpp/cicp_kernel_host.cpp can compile the same text for the
-// host - thread and block indices as loop variables - and run it under the host sanitizers against a source and a slot
-// allocated at exactly their size.  Every product and every sum of the matrix is a separately rounded f32 operation: this
-// text is compiled with -ffp-contract=off on the device and on the host, and its expressions are written so that no
-// other evaluation order is allowed (include/ce_metrics.h: the definition of ce_batch_set_*_cicp).
+// The device code of the ingest of packed code values into a linear batch - CICP and HLG - and of the linear-f32 upload
+// (cicp.hip), kept free of anything but the HIP keywords, uint2 / uint4 / float4 and blockIdx / threadIdx, so that
+// tests/cpp/cicp_kernel_host.cpp and hlg_kernel_host.cpp can compile the same text for the host - thread and block indices as
+// loop variables - and run it under the host sanitizers against a source and a slot allocated at exactly their size.  One
+// frame, k_tagged, with the pixel as a parameter: cicp_pixel.h's cicp_px or hlg_pixel.h's hlg_px.  Every f32 and every f64
+// product and sum is a separately rounded operation: this text is compiled with -ffp-contract=off on the device and on the
+// host, and its expressions are written so that no other evaluation order is allowed (include/ce_metrics.h: the definitions
+// of ce_batch_set_*_cicp and ce_batch_set_*_hlg).
 #pragma once
 
 #include <cstddef>
@@ -31,7 +33,7 @@ __device__ __forceinline__ void store12(float *p, const float (&o)[12])
 }
 
 // The samples of group `tid` (four pixels) of a packed FMT image at src, in memory order, from aligned loads (12 bytes: three
-// dwords; 16: one uint4; 24: three uint2; 32: two uint4).  k_cicp's and, in hlg_kernel.h, k_hlg's.
+// dwords; 16: one uint4; 24: three uint2; 32: two uint4).
 template <int FMT>
 __device__ __forceinline__ void cicp_load_group(const void *src, size_t tid,
                                                 uint32_t (&s)[4 * ((FMT == CE_PIXEL_RGBA8 || FMT == CE_PIXEL_RGBA16) ? 4 : 3)])
@@ -79,14 +81,16 @@ __device__ __forceinline__ void cicp_load_pixel(const void *src, size_t p, uint3
     for (int c = 0; c < 3; c++) v[c] = S16 ? static_cast<const uint16_t *>(src)[p * NC + c] : static_cast<const uint8_t *>(src)[p * NC + c];
 }
 
-// FMT: CE_PIXEL_RGB8 / RGBA8 / RGB16 / RGBA16 (alpha dropped).  A thread converts one group of four pixels from the
-// registers its aligned loads filled and stores 48 bytes; the last n_pixels % 4 pixels go sample by sample, one pixel to a
-// thread of block 0.  The table is gathered from global memory at every depth: 1, 4 and 16 KB stay in the vector L1 and the
-// 256 KB of depth 16 in L2, one code path.
-template <int FMT, bool MATRIX>
-__global__ __launch_bounds__(kCicpBlock) void k_cicp(const cicp_args a)
+// FMT: CE_PIXEL_RGB8 / RGBA8 / RGB16 / RGBA16 (alpha dropped); Pixel: cicp_px<MATRIX> or hlg_px<MATRIX>, whose frame() holds
+// src, dst and n_pixels.  A thread converts one group of four pixels from the registers its aligned loads filled and stores
+// 48 bytes; the last n_pixels % 4 pixels go sample by sample, one pixel to a thread of block 0.  Either pixel gathers its
+// table from global memory at every depth: 1, 4 and 16 KB stay in the vector L1 and the 256 KB of depth 16 in L2, one code
+// path.
+template <int FMT, class Pixel>
+__global__ __launch_bounds__(kCicpBlock) void k_tagged(const Pixel px)
 {
     constexpr int NC = (FMT == CE_PIXEL_RGBA8 || FMT == CE_PIXEL_RGBA16) ? 4 : 3;
+    const cicp_args &a = px.frame();
     const size_t n_groups = a.n_pixels / 4;
     const size_t tid = (size_t)blockIdx.x * kCicpBlock + threadIdx.x;
     if (tid < n_groups) {
@@ -95,9 +99,9 @@ __global__ __launch_bounds__(kCicpBlock) void k_cicp(const cicp_args a)
         float o[12];
 #pragma unroll
         for (int p = 0; p < 4; p++) {
-            float px[3];
-            cicp_pixel<MATRIX>(a, s[NC * p], s[NC * p + 1], s[NC * p + 2], px);
-            o[3 * p] = px[0], o[3 * p + 1] = px[1], o[3 * p + 2] = px[2];
+            float v[3];
+            px(s[NC * p], s[NC * p + 1], s[NC * p + 2], v);
+            o[3 * p] = v[0], o[3 * p + 1] = v[1], o[3 * p + 2] = v[2];
         }
         store12(a.dst + tid * 12, o);
     }
@@ -105,10 +109,10 @@ __global__ __launch_bounds__(kCicpBlock) void k_cicp(const cicp_args a)
         const size_t p = n_groups * 4 + threadIdx.x;
         uint32_t v[3];
         cicp_load_pixel<FMT>(a.src, p, v);
-        float px[3];
-        cicp_pixel<MATRIX>(a, v[0], v[1], v[2], px);
+        float o[3];
+        px(v[0], v[1], v[2], o);
 #pragma unroll
-        for (int c = 0; c < 3; c++) a.dst[p * 3 + c] = px[c];
+        for (int c = 0; c < 3; c++) a.dst[p * 3 + c] = o[c];
     }
 }
 

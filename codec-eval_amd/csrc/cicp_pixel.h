@@ -1,6 +1,8 @@
-// One pixel of the CICP ingest (cicp_kernel.h: k_cicp; yuv_cicp_kernel.h: k_yuv_cicp): the arguments, the clamp of a linear
-// image and the table gather with the separately rounded f32 matrix, apart from the kernels so that a file that needs the
-// pixel does not emit them.  hlg_pixel.h builds its pixel on the same arguments, matrix and clamp.  Host-compilable like the headers that include it, and compiled with -ffp-contract=off.
+// One pixel of the CICP ingest: the arguments, the clamp of a linear image and the table gather with the separately rounded
+// f32 matrix, apart from the kernels so that a file that needs the pixel does not emit them, and cicp_px, the pixel as the
+// type that the two frames take (cicp_kernel.h: k_tagged; yuv_cicp_kernel.h: k_yuv_tagged).  hlg_pixel.h builds its pixel on
+// the same arguments, matrix and clamp.  Host-compilable like the headers that include it, and compiled with
+// -ffp-contract=off.
 #pragma once
 
 #include <cstddef>
@@ -49,5 +51,14 @@ __device__ __forceinline__ void cicp_pixel(const cicp_args &a, uint32_t r, uint3
     const float tr = a.table[r < a.maxv ? r : a.maxv], tg = a.table[g < a.maxv ? g : a.maxv], tb = a.table[b < a.maxv ? b : a.maxv];
     cicp_matrix_clamp<MATRIX>(a, tr, tg, tb, o);
 }
+
+// What a frame is given as its pixel: the arguments by value, the fields the frames themselves read (src, dst, n_pixels)
+// and the conversion of one pixel's three code values.  MATRIX: primaries other than 1.
+template <bool MATRIX>
+struct cicp_px {
+    cicp_args a;
+    __device__ __forceinline__ const cicp_args &frame() const { return a; }
+    __device__ __forceinline__ void operator()(uint32_t r, uint32_t g, uint32_t b, float (&o)[3]) const { cicp_pixel<MATRIX>(a, r, g, b, o); }
+};
 
 }  // namespace

@@ -1,5 +1,5 @@
-// One pixel of the HLG ingest (hlg_kernel.h: k_hlg; yuv_hlg_kernel.h: k_yuv_hlg; include/ce_metrics.h: the definition of
-// ce_batch_set_*_hlg): three gathers from the host-built inverse-OETF table, the scene luminance in f64, the OOTF's
+// One pixel of the HLG ingest (include/ce_metrics.h: the definition of ce_batch_set_*_hlg), and hlg_px, the pixel as the type
+// that cicp_kernel.h's k_tagged and yuv_cicp_kernel.h's k_yuv_tagged take in cicp_px's place: three gathers from the host-built inverse-OETF table, the scene luminance in f64, the OOTF's
 // Ys^(gamma - 1) through hlg_pow, one f32 scale per channel, then cicp_pixel.h's matrix and clamp.  hlg_pow is a fixed
 // sequence of IEEE f64 additions, multiplications, divisions, integer work on the exponent bits and one round-to-nearest,
 // each correctly rounded on the device and on the host alike; tests/hlg_restatement.py runs the same sequence in numpy.
@@ -16,7 +16,7 @@
 namespace {
 
 struct hlg_args {
-    cicp_args c;        // src, dst, n_pixels, table (the inverse OETF, maxv + 1 entries), maxv and m, as k_cicp reads them
+    cicp_args c;        // src, dst, n_pixels, table (the inverse OETF, maxv + 1 entries), maxv and m, as the CICP pixel reads them
     double kr, kg, kb;  // the Y row of the f64 XYZ <- src matrix of the tagged primaries
     double gm1;         // system gamma - 1
     double a;           // peak_nits / white_nits
@@ -93,5 +93,13 @@ __device__ __forceinline__ void hlg_pixel(const hlg_args &a, uint32_t r, uint32_
     const float dr = k * er, dg = k * eg, db = k * eb;
     cicp_matrix_clamp<MATRIX>(a.c, dr, dg, db, o);
 }
+
+// cicp_px's counterpart: on top of its gather, matrix and clamp a pixel costs about 70 f64 operations, two of them divisions
+template <bool MATRIX>
+struct hlg_px {
+    hlg_args a;
+    __device__ __forceinline__ const cicp_args &frame() const { return a.c; }
+    __device__ __forceinline__ void operator()(uint32_t r, uint32_t g, uint32_t b, float (&o)[3]) const { hlg_pixel<MATRIX>(a, r, g, b, o); }
+};
 
 }  // namespace

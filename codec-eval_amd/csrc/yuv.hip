@@ -16,29 +16,7 @@
 #include "ce_internal.h"
 
 #include "yuv_kernel.h"
-
-namespace {
-
-template <int BPS, bool OUT16, int SUB>
-void launch_layout(ce_ctx *ctx, hipStream_t stream, const char *name, bool semi, dim3 grid, const yuv_args &a, uint8_t *dst)
-{
-    if (semi && SUB != CE_YUV_400) CE_LAUNCH_ON(ctx, stream, name, (k_yuv<BPS, OUT16, SUB, true>), grid, dim3(64), 0, a, dst);
-    else CE_LAUNCH_ON(ctx, stream, name, (k_yuv<BPS, OUT16, SUB, false>), grid, dim3(64), 0, a, dst);
-}
-
-template <int BPS, bool OUT16>
-void launch_sub(ce_ctx *ctx, hipStream_t stream, int sub, bool semi, dim3 grid, const yuv_args &a, uint8_t *dst)
-{
-    // the profile names say what a dispatch moved: input sample size, subsampling, output sample size
-    switch (sub) {
-        case CE_YUV_444: launch_layout<BPS, OUT16, CE_YUV_444>(ctx, stream, BPS == 1 ? (OUT16 ? "yuv444_8_deep" : "yuv444_8") : (OUT16 ? "yuv444_16_deep" : "yuv444_16"), semi, grid, a, dst); break;
-        case CE_YUV_422: launch_layout<BPS, OUT16, CE_YUV_422>(ctx, stream, BPS == 1 ? (OUT16 ? "yuv422_8_deep" : "yuv422_8") : (OUT16 ? "yuv422_16_deep" : "yuv422_16"), semi, grid, a, dst); break;
-        case CE_YUV_420: launch_layout<BPS, OUT16, CE_YUV_420>(ctx, stream, BPS == 1 ? (OUT16 ? "yuv420_8_deep" : "yuv420_8") : (OUT16 ? "yuv420_16_deep" : "yuv420_16"), semi, grid, a, dst); break;
-        default: launch_layout<BPS, OUT16, CE_YUV_400>(ctx, stream, BPS == 1 ? (OUT16 ? "yuv400_8_deep" : "yuv400_8") : (OUT16 ? "yuv400_16_deep" : "yuv400_16"), semi, grid, a, dst); break;
-    }
-}
-
-}  // namespace
+#include "yuv_ladder.h"
 
 int ce_launch_yuv(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32_t w, uint32_t h, void *d_dst, bool out16, uint32_t depth_out)
 {
@@ -51,15 +29,14 @@ int ce_launch_yuv(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32
     yuv_args a{};
     ce_fill_yuv_args(a, src, w, h, ((int64_t)1 << depth_out) - 1);
     const dim3 grid((uint32_t)blocks);
-    const bool semi = src.layout == CE_YUV_SEMIPLANAR;
     uint8_t *dst = static_cast<uint8_t *>(d_dst);
-    if (src.depth == 8) {
-        if (out16) launch_sub<1, true>(ctx, stream, src.subsampling, semi, grid, a, dst);
-        else launch_sub<1, false>(ctx, stream, src.subsampling, semi, grid, a, dst);
-    } else {
-        if (out16) launch_sub<2, true>(ctx, stream, src.subsampling, semi, grid, a, dst);
-        else launch_sub<2, false>(ctx, stream, src.subsampling, semi, grid, a, dst);
-    }
+    // the profile names say what a dispatch moved: subsampling, input sample size, _deep for u16 output
+    yuv_ladder(src.depth == 8, src.subsampling, src.layout == CE_YUV_SEMIPLANAR, [&](auto bps, auto sub, auto semi) {
+        constexpr int BPS = decltype(bps)::value, SUB = decltype(sub)::value;
+        constexpr bool SEMI = decltype(semi)::value;
+        if (out16) CE_LAUNCH_ON(ctx, stream, yuv_profile_name(SUB, BPS, "_deep").s, (k_yuv<BPS, true, SUB, SEMI>), grid, dim3(64), 0, a, dst);
+        else CE_LAUNCH_ON(ctx, stream, yuv_profile_name(SUB, BPS, "").s, (k_yuv<BPS, false, SUB, SEMI>), grid, dim3(64), 0, a, dst);
+    });
     CE_HIP(ctx, hipGetLastError());
     return CE_OK;
 }

@@ -1,19 +1,16 @@
-// The device code of the fused Y'CbCr + CICP ingest (yuv_cicp.hip): yuv_kernel.h's block (loads, integer upsampling,
-// int64 matrix) followed by cicp_pixel.h's pixel (table gather, separately rounded f32 matrix, clamp of a linear image),
-// with nothing but the stores of its own.  Kept, like the two headers it builds on, free of anything but the HIP keywords,
-// min / max, float2 / float4 and blockIdx / threadIdx, so that tests/cpp/yuv_cicp_kernel_host.cpp can compile the same
-// text for the host and run it under the host sanitizers.  Compiled with -ffp-contract=off on the device and on the host.
+// The device code of the fused ingest of Y'CbCr planes into a linear batch, CICP and HLG (yuv_cicp.hip): yuv_kernel.h's block
+// (loads, integer upsampling, int64 matrix) followed by a pixel - cicp_pixel.h's cicp_px (table gather, separately rounded
+// f32 matrix, clamp of a linear image) or hlg_pixel.h's hlg_px (the same around the f64 OOTF) - with nothing but the stores
+// of its own.  One frame, k_yuv_tagged, with the pixel as a parameter.  Kept, like the headers it builds on, free of anything
+// but the HIP keywords, min / max, float2 / float4 and blockIdx / threadIdx, so that tests/cpp/yuv_cicp_kernel_host.cpp and
+// hlg_kernel_host.cpp can compile the same text for the host and run it under the host sanitizers.  Compiled with
+// -ffp-contract=off on the device and on the host.
 #pragma once
 
 #include "cicp_pixel.h"
 #include "yuv_kernel.h"
 
 namespace {
-
-struct yuv_cicp_args {
-    yuv_args y;   // y.m = c.maxv = 2^(the colour description's depth) - 1: the integer RGB grid between the two halves
-    cicp_args c;  // table, maxv, m and dst (the slot: packed f32 RGB, 4-byte aligned); src and n_pixels are not read
-};
 
 // One row of a full block, 24 floats, to p (4-byte aligned).  p is a multiple of 32 bytes past the row's start, and the
 // row's start moves through all four residues mod 16 with the slot, y * w and the image's size, so the choice is made per
@@ -48,43 +45,54 @@ __device__ __forceinline__ void store24(float *p, const float (&o)[24])
     }
 }
 
-// BPS: bytes per input sample; SUB: enum ce_yuv_subsampling; SEMI: interleaved CbCr; MATRIX: primaries other than 1.
-// The grid and the thread's 8 x 2 block are k_yuv's.  A cropped group (x0 + 8 > w) stores sample by sample; the second
-// row of an odd height's last pair repeats the first's loads (yuv_block) and is neither converted nor stored.
-template <int BPS, int SUB, bool SEMI, bool MATRIX>
-__global__ __launch_bounds__(64) void k_yuv_cicp(const yuv_cicp_args a)
+// What the frame is launched with: the planes and the pixel in one argument, laid out as the two structs behind each other.
+// y.m = the pixel's maxv = 2^(the description's depth) - 1 is the integer RGB grid between the two halves; of the pixel's
+// frame() only dst (the slot: packed f32 RGB, 4-byte aligned) is read, src and n_pixels are not.
+template <class Pixel>
+struct yuv_px_args {
+    yuv_args y;
+    Pixel px;
+};
+
+// BPS: bytes per input sample; SUB: enum ce_yuv_subsampling; SEMI: interleaved CbCr; Pixel: cicp_px<MATRIX> or
+// hlg_px<MATRIX>.  The grid and the thread's 8 x 2 block are k_yuv's.  A cropped group (x0 + 8 > w) stores sample by sample;
+// the second row of an odd height's last pair repeats the first's loads (yuv_block) and is neither converted nor stored.
+template <int BPS, int SUB, bool SEMI, class Pixel>
+__global__ __launch_bounds__(64) void k_yuv_tagged(const yuv_px_args<Pixel> k)
 {
-    const uint32_t gw = (a.y.w + 7) / 8, gh = (a.y.h + 1) / 2;
+    const yuv_args &a = k.y;
+    const Pixel &px = k.px;
+    const uint32_t gw = (a.w + 7) / 8, gh = (a.h + 1) / 2;
     const size_t tid = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (tid >= (size_t)gw * gh) return;
     const uint32_t gy = (uint32_t)(tid / gw), gx = (uint32_t)(tid - (size_t)gy * gw);
     const uint32_t x0 = gx * 8, y0 = gy * 2;
 
     int Y[2][8], CB[2][8], CR[2][8];
-    yuv_block<BPS, SUB, SEMI>(a.y, gx, gy, Y, CB, CR);
+    yuv_block<BPS, SUB, SEMI>(a, gx, gy, Y, CB, CR);
 
-    const bool full = x0 + 8 <= a.y.w;
+    const bool full = x0 + 8 <= a.w;
 #pragma unroll
     for (int j = 0; j < 2; j++) {
         const uint32_t y = y0 + j;
-        if (y >= a.y.h) break;
+        if (y >= a.h) break;
         uint32_t smp[24];
 #pragma unroll
-        for (int k = 0; k < 8; k++) yuv_matrix_px(a.y, Y[j][k], CB[j][k], CR[j][k], smp[3 * k], smp[3 * k + 1], smp[3 * k + 2]);
+        for (int k = 0; k < 8; k++) yuv_matrix_px(a, Y[j][k], CB[j][k], CR[j][k], smp[3 * k], smp[3 * k + 1], smp[3 * k + 2]);
         float o[24];
 #pragma unroll
         for (int k = 0; k < 8; k++) {
-            float px[3];
-            cicp_pixel<MATRIX>(a.c, smp[3 * k], smp[3 * k + 1], smp[3 * k + 2], px);
-            o[3 * k] = px[0], o[3 * k + 1] = px[1], o[3 * k + 2] = px[2];
+            float v[3];
+            px(smp[3 * k], smp[3 * k + 1], smp[3 * k + 2], v);
+            o[3 * k] = v[0], o[3 * k + 1] = v[1], o[3 * k + 2] = v[2];
         }
-        float *p = a.c.dst + ((size_t)y * a.y.w + x0) * 3;
+        float *p = px.frame().dst + ((size_t)y * a.w + x0) * 3;
         if (full) {
             store24(p, o);
         } else {
 #pragma unroll
             for (int k = 0; k < 8; k++) {
-                if (x0 + k < a.y.w) {
+                if (x0 + k < a.w) {
 #pragma unroll
                     for (int c = 0; c < 3; c++) p[3 * k + c] = o[3 * k + c];
                 }

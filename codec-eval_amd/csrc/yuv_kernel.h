@@ -98,7 +98,7 @@ __device__ __forceinline__ uint32_t clamp_m(int64_t v, int64_t m) { return (uint
 
 // The block of group (gx, gy) before the matrix: its 2 x 8 luma samples and its chroma at full resolution (the upsampling of
 // include/ce_metrics.h).  Every load goes through ld_luma / ld_chroma, whose clamped indices keep it inside the planes.
-// Shared by k_yuv and k_yuv_cicp (yuv_cicp_kernel.h).
+// Shared by k_yuv and k_yuv_tagged (yuv_cicp_kernel.h).
 template <int BPS, int SUB, bool SEMI>
 __device__ __forceinline__ void yuv_block(const yuv_args &a, uint32_t gx, uint32_t gy, int (&Y)[2][8], int (&CB)[2][8], int (&CR)[2][8])
 {

@@ -1,6 +1,7 @@
 """Per-dispatch medians of profiles/hlg_ingest_timing.py's phases from rocprofv3's kernel trace.
 usage: hlg_ingest_medians.py TRACE_DIR PLAN.txt - TRACE_DIR is searched for *kernel_trace.csv; PLAN.txt is the timing
-script's output, whose last line is the plan: the phases in order, each with the kernel it dispatches and how often.  The
+script's output, whose last line is the plan: the phases in order, each with the kernel it dispatches - the words that all
+occur in its name in the trace, the kernel's and its pixel's - and how often.  The
 dispatches of a kernel are taken in start order and dealt to the phases in plan order, the warm-up ones dropped.  Prints
 one line per phase (median microseconds, GB/s against the bytes the script printed) and the HLG-to-CICP ratios."""
 import csv
@@ -18,7 +19,7 @@ for path in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recurs
         for r in csv.DictReader(f):
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
 rows.sort()
-queues = {p["kernel"]: [(s, e) for s, e, name in rows if p["kernel"] in name] for p in plan}
+queues = {p["kernel"]: [(s, e) for s, e, name in rows if all(word in name for word in p["kernel"].split())] for p in plan}
 medians = {}
 for phase in plan:
     q = queues[phase["kernel"]]

@@ -1,6 +1,7 @@
 """Per-dispatch medians of profiles/yuv_cicp_ingest_timing.py's phases from rocprofv3's kernel trace.
 usage: yuv_cicp_ingest_medians.py TRACE_DIR PLAN.txt - TRACE_DIR is searched for *kernel_trace.csv; PLAN.txt is the timing
-script's output, whose last line is the plan: the phases in order, each with the kernel it dispatches and how often.  The
+script's output, whose last line is the plan: the phases in order, each with the kernel it dispatches - the words that all
+occur in its name in the trace, the kernel's and its pixel's - and how often.  The
 dispatches of a kernel are taken in start order and dealt to the phases in plan order, the warm-up ones dropped.  Prints
 one line per phase (median microseconds, GB/s against the bytes the script printed) and the fused-to-yardstick ratios."""
 import csv
@@ -22,7 +23,7 @@ queues = {}
 for phase in plan:
     k = phase["kernel"]
     if k not in queues:
-        queues[k] = [(s, e) for s, e, name in rows if k in name]
+        queues[k] = [(s, e) for s, e, name in rows if all(word in name for word in k.split())]
 medians = {}
 for phase in plan:
     q = queues[phase["kernel"]]

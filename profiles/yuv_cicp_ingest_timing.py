@@ -2,8 +2,8 @@
 images in the same run: 54 images of 768x512 and 8 of 3840x2160 into the test slot of a linear batch by
 ce_batch_set_test_yuv_cicp - P010 4:2:0 BT.2020 limited range at (9, 16, depth 16) and at (9, 16, depth 10), 8-bit I420 at
 (1, 13, depth 8) - and, as the yardstick, the same planes through ce_batch_set_test_yuv into a depth-16 deep batch (k_yuv)
-followed by the RGB16 image that writes through ce_batch_set_test_cicp (k_cicp); for the 8-bit planes the RGB8 pair of the
-same two.  All sources are host images: only the kernels are compared.  The phases run in the printed order with a
+followed by the RGB16 image that writes through ce_batch_set_test_cicp (k_tagged with cicp_px); for the 8-bit planes the
+RGB8 pair of the same two.  All sources are host images: only the kernels are compared.  The phases run in the printed order with a
 synchronise between them, one warm-up call first, and the last line printed is the plan as JSON:
 profiles/yuv_cicp_ingest_medians.py reads it with the kernel trace and gives the per-dispatch medians of each phase.  No
 counters: collect those in a run of their own.  Run under
@@ -39,13 +39,13 @@ with ce.Context(0) as ctx:
         pq16, pq10, srgb = ce.ColourDescription(9, 16, 16, 203.0), ce.ColourDescription(9, 16, 10, 203.0), ce.ColourDescription(1, 13, 8)
         # (label, kernel in the trace, bytes per pixel the kernel must move, call)
         phases = [
-            ("fused P010 (9, 16, 16)", "k_yuv_cicp<", 3 + 12, lambda: b_lin.set_test_yuv_cicp(0, 0, p010, pq16)),
-            ("fused P010 (9, 16, 10)", "k_yuv_cicp<", 3 + 12, lambda: b_lin.set_test_yuv_cicp(0, 0, p010, pq10)),
-            ("fused I420 (1, 13, 8)", "k_yuv_cicp<", 1.5 + 12, lambda: b_lin.set_test_yuv_cicp(0, 0, i420, srgb)),
+            ("fused P010 (9, 16, 16)", "k_yuv_tagged< cicp_px<", 3 + 12, lambda: b_lin.set_test_yuv_cicp(0, 0, p010, pq16)),
+            ("fused P010 (9, 16, 10)", "k_yuv_tagged< cicp_px<", 3 + 12, lambda: b_lin.set_test_yuv_cicp(0, 0, p010, pq10)),
+            ("fused I420 (1, 13, 8)", "k_yuv_tagged< cicp_px<", 1.5 + 12, lambda: b_lin.set_test_yuv_cicp(0, 0, i420, srgb)),
             ("yardstick P010 -> deep 16 (yuv420_16_deep)", "k_yuv<", 3 + 6, lambda: b_deep.set_test_yuv(0, 0, p010)),
-            ("yardstick RGB16 (9, 16, 16) (cicp_rgb16_m)", "k_cicp<", 6 + 12, lambda: b_lin.set_test_cicp(0, 0, rgb16, pq16)),
+            ("yardstick RGB16 (9, 16, 16) (cicp_rgb16_m)", "k_tagged< cicp_px<", 6 + 12, lambda: b_lin.set_test_cicp(0, 0, rgb16, pq16)),
             ("yardstick I420 -> RGB8 (yuv420_8)", "k_yuv<", 1.5 + 3, lambda: b_rgb8.set_test_yuv(0, 0, i420)),
-            ("yardstick RGB8 (1, 13, 8) (cicp_rgb8)", "k_cicp<", 3 + 12, lambda: b_lin.set_test_cicp(0, 0, rgb8, srgb)),
+            ("yardstick RGB8 (1, 13, 8) (cicp_rgb8)", "k_tagged< cicp_px<", 3 + 12, lambda: b_lin.set_test_cicp(0, 0, rgb8, srgb)),
         ]
         for name, kernel, bytes_per_px, call in phases:
             call()  # first use: staging allocations, table upload, code object load

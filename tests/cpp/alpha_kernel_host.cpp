@@ -15,25 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#define __device__
-#define __global__
-#define __forceinline__ inline
-#define __restrict__
-#define __launch_bounds__(x)
-struct idx3 {
-    unsigned x;
-};
-static idx3 blockIdx, threadIdx;
-using std::max;
-using std::min;
-struct uint4 {
-    uint32_t x, y, z, w;
-};
-struct uint2 {
-    uint32_t x, y;
-};
-static inline uint4 make_uint4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return {a, b, c, d}; }
-static inline uint2 make_uint2(uint32_t a, uint32_t b) { return {a, b}; }
+#include "hip_on_host.h"
 
 #include "alpha_kernel.h"
 

@@ -1,6 +1,6 @@
-// The device code of the CICP ingest and of the linear-f32 upload (codec-eval_amd/csrc/cicp_kernel.h) compiled for the
-// host: the HIP keywords are defined away, blockIdx / threadIdx are plain variables that a loop sets, and every thread of
-// every block of a launch runs in turn.  Built with -ffp-contract=off -fsanitize=address,undefined by
+// The device code of the CICP ingest (codec-eval_amd/csrc/cicp_kernel.h's k_tagged with cicp_pixel.h's cicp_px as its pixel)
+// and of the linear-f32 upload compiled for the host (hip_on_host.h): blockIdx / threadIdx are plain variables that a loop
+// sets, and every thread of every block of a launch runs in turn.  Built with -ffp-contract=off -fsanitize=address,undefined by
 // tests/test_cicp_kernel_host_cpu.py: the source, the table and the slab are allocated at exactly their size, the slab `off`
 // bytes after a 16-byte boundary with a guard in front, so a load outside the source or the table or a store outside the
 // slot stops the run, and so does a wide access to an address that is not a multiple of its width.
@@ -16,41 +16,19 @@
 #include <cstdlib>
 #include <cstring>
 
-#define __device__
-#define __global__
-#define __forceinline__ inline
-#define __restrict__
-#define __launch_bounds__(x)
-struct idx3 {
-    unsigned x;
-};
-static idx3 blockIdx, threadIdx;
-struct uint4 {
-    uint32_t x, y, z, w;
-};
-struct uint2 {
-    uint32_t x, y;
-};
-struct alignas(16) float4 {
-    float x, y, z, w;
-};
-static inline float4 make_float4(float a, float b, float c, float d) { return {a, b, c, d}; }
+#include "hip_on_host.h"
+#include "ingest_host.h"
 
 #include "cicp_kernel.h"
-
-static size_t ce_pixel_bytes_of(int format)  // ce_pixel_bytes of the four formats the ingest takes
-{
-    return format == CE_PIXEL_RGB8 ? 3 : format == CE_PIXEL_RGBA8 ? 4 : format == CE_PIXEL_RGB16 ? 6 : format == CE_PIXEL_RGBA16 ? 8 : 0;
-}
 
 template <int FMT>
 static void run(const cicp_args &a, bool matrix)
 {
-    const size_t blocks = std::max<size_t>((a.n_pixels / 4 + kCicpBlock - 1) / kCicpBlock, 1);  // ce_launch_cicp's grid
+    const size_t blocks = std::max<size_t>((a.n_pixels / 4 + kCicpBlock - 1) / kCicpBlock, 1);  // ce_launch_tagged's grid
     for (size_t b = 0; b < blocks; b++)
         for (unsigned t = 0; t < (unsigned)kCicpBlock; t++) {
             blockIdx.x = (unsigned)b, threadIdx.x = t;
-            if (matrix) k_cicp<FMT, true>(a); else k_cicp<FMT, false>(a);
+            if (matrix) k_tagged<FMT>(cicp_px<true>{a}); else k_tagged<FMT>(cicp_px<false>{a});
         }
 }
 
@@ -73,18 +51,9 @@ int main(int argc, char **argv)
         const bool f32 = format == CE_PIXEL_RGB_F32;
         const size_t bpp = f32 ? 12 : ce_pixel_bytes_of(format), src_bytes = (size_t)n_px * bpp, slot_bytes = (size_t)n_px * 12;
         if (bpp == 0) return 70;
-        auto next = [&seed] { return seed = seed * 1664525u + 1013904223u; };
-        uint8_t *src = static_cast<uint8_t *>(malloc(src_bytes));
-        if (!src || (reinterpret_cast<uintptr_t>(src) & 15)) return 67;  // malloc: 16-byte aligned, as the staging buffer is
-        for (size_t i = 0; i < src_bytes; i++) src[i] = (uint8_t)(next() >> 24);
-        if (format == CE_PIXEL_RGB16 || format == CE_PIXEL_RGBA16) {  // in range, but one sample in 16 above maxv
-            for (size_t i = 0; i < src_bytes / 2; i++) {
-                uint16_t v;
-                memcpy(&v, src + 2 * i, 2);
-                if ((next() >> 28) != 0) v &= (uint16_t)maxv;
-                memcpy(src + 2 * i, &v, 2);
-            }
-        }
+        auto next = [&seed] { return lcg_next(seed); };
+        uint8_t *src = make_packed_source(src_bytes, format == CE_PIXEL_RGB16 || format == CE_PIXEL_RGBA16, maxv, seed);
+        if (!src) return 67;
         if (f32) {  // plausible values, with NaN, infinities and huge values sprinkled in
             for (size_t i = 0; i < src_bytes / 4; i++) {
                 const unsigned sel = next() >> 28;
@@ -100,13 +69,12 @@ int main(int argc, char **argv)
         fwrite(src, 1, src_bytes, out);
         float *table = nullptr;
         if (!f32) {
-            table = static_cast<float *>(malloc(((size_t)maxv + 1) * 4));
-            if (!table || fseek(tf, (long)(table_offset * 4), SEEK_SET) != 0 || fread(table, 4, (size_t)maxv + 1, tf) != (size_t)maxv + 1) return 69;
+            table = read_table(tf, table_offset, maxv);
+            if (!table) return 69;
         }
         const size_t slab_bytes = (size_t)(slot + 2) * slot_bytes;
-        uint8_t *slab = static_cast<uint8_t *>(malloc(slab_bytes + (size_t)off));  // malloc: 16-byte aligned
-        if (!slab || (reinterpret_cast<uintptr_t>(slab) & 15)) return 68;
-        memset(slab, 0xEE, slab_bytes + (size_t)off);
+        uint8_t *slab = make_slab(slab_bytes, off);
+        if (!slab) return 68;
         float *dst = reinterpret_cast<float *>(slab + off + (size_t)slot * slot_bytes);
         if (f32) {
             const size_t n = (size_t)n_px * 3, blocks = std::max<size_t>((n / 4 + kCicpBlock - 1) / kCicpBlock, 1);
@@ -124,11 +92,7 @@ int main(int argc, char **argv)
                 default: run<CE_PIXEL_RGBA16>(a, has_matrix != 0); break;
             }
         }
-        for (int i = 0; i < off; i++)
-            if (slab[i] != 0xEE) {
-                fprintf(stderr, "case %d wrote in front of its slab\n", cases);
-                return 2;
-            }
+        if (!front_guard_intact(slab, off, cases)) return 2;
         fwrite(slab + off, 1, slab_bytes, out);
         free(slab);
         free(table);

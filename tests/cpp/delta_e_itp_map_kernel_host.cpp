@@ -20,21 +20,8 @@
 #include <cstdlib>
 #include <cstring>
 
-#define __device__
-#define __global__
-#define __forceinline__ inline
-#define __restrict__
-#define __launch_bounds__(x)
-struct idx3 {
-    unsigned x, y;
-};
-static idx3 blockIdx, threadIdx, gridDim;
-struct alignas(16) float4 {
-    float x, y, z, w;
-};
-struct alignas(16) uint4 {
-    uint32_t x, y, z, w;
-};
+#include "hip_on_host.h"
+
 static inline uint32_t atomicMax(uint32_t *p, uint32_t v)
 {
     const uint32_t old = *p;

@@ -18,18 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#define __device__
-#define __global__
-#define __forceinline__ inline
-#define __restrict__
-#define __launch_bounds__(x)
-struct idx3 {
-    unsigned x, y;
-};
-static idx3 blockIdx, threadIdx, gridDim;
-struct alignas(16) float4 {
-    float x, y, z, w;
-};
+#include "hip_on_host.h"
 
 #include "hdr_fidelity_kernel.h"
 

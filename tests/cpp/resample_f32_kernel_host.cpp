@@ -21,17 +21,7 @@
 #include <cstring>
 #include <vector>
 
-#define __device__
-#define __global__
-#define __forceinline__ inline
-#define __restrict__
-#define __launch_bounds__(x)
-struct idx3 {
-    unsigned x;
-};
-static idx3 blockIdx, threadIdx;
-using std::max;
-using std::min;
+#include "hip_on_host.h"
 
 #include "resample_f32_kernel.h"
 

@@ -14,53 +14,26 @@
 #include <cstring>
 #include <vector>
 
-#define __device__
-#define __global__
-#define __forceinline__ inline
-#define __restrict__
-#define __launch_bounds__(x)
-struct idx3 {
-    unsigned x;
-};
-static idx3 blockIdx, threadIdx;
-using std::max;
-using std::min;
-struct uint4 {
-    uint32_t x, y, z, w;
-};
-struct uint2 {
-    uint32_t x, y;
-};
-static inline uint4 make_uint4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return {a, b, c, d}; }
-static inline uint2 make_uint2(uint32_t a, uint32_t b) { return {a, b}; }
+#include "hip_on_host.h"
+#include "ingest_host.h"
 
 #include "yuv_kernel.h"
+#include "yuv_ladder.h"
 
-template <int BPS, bool OUT16, int SUB, bool SEMI>
-static void run(const yuv_args &a, uint8_t *dst)
+// one launch: every thread of every block of ce_launch_yuv's grid
+static void run(int bps, bool out16, int sub, bool semi, const yuv_args &a, uint8_t *dst)
 {
-    const size_t groups = (size_t)((a.w + 7) / 8) * ((a.h + 1) / 2), blocks = (groups + 63) / 64;  // ce_launch_yuv's grid
-    for (size_t b = 0; b < blocks; b++)
-        for (unsigned t = 0; t < 64; t++) {
-            blockIdx.x = (unsigned)b, threadIdx.x = t;
-            k_yuv<BPS, OUT16, SUB, SEMI>(a, dst);
-        }
-}
-template <int BPS, bool OUT16, int SUB>
-static void run_layout(bool semi, const yuv_args &a, uint8_t *dst)
-{
-    if (semi && SUB != CE_YUV_400) run<BPS, OUT16, SUB, true>(a, dst);
-    else run<BPS, OUT16, SUB, false>(a, dst);
-}
-template <int BPS, bool OUT16>
-static void run_sub(int sub, bool semi, const yuv_args &a, uint8_t *dst)
-{
-    switch (sub) {
-        case CE_YUV_444: run_layout<BPS, OUT16, CE_YUV_444>(semi, a, dst); break;
-        case CE_YUV_422: run_layout<BPS, OUT16, CE_YUV_422>(semi, a, dst); break;
-        case CE_YUV_420: run_layout<BPS, OUT16, CE_YUV_420>(semi, a, dst); break;
-        default: run_layout<BPS, OUT16, CE_YUV_400>(semi, a, dst); break;
-    }
+    const size_t groups = (size_t)((a.w + 7) / 8) * ((a.h + 1) / 2), blocks = (groups + 63) / 64;
+    yuv_ladder(bps == 1, sub, semi, [&](auto b, auto s, auto sm) {
+        constexpr int BPS = decltype(b)::value, SUB = decltype(s)::value;
+        constexpr bool SEMI = decltype(sm)::value;
+        for (size_t blk = 0; blk < blocks; blk++)
+            for (unsigned t = 0; t < 64; t++) {
+                blockIdx.x = (unsigned)blk, threadIdx.x = t;
+                if (out16) k_yuv<BPS, true, SUB, SEMI>(a, dst);
+                else k_yuv<BPS, false, SUB, SEMI>(a, dst);
+            }
+    });
 }
 
 int main(int argc, char **argv)
@@ -74,46 +47,14 @@ int main(int argc, char **argv)
     int cases = 0;
     while (fscanf(in, "%d %d %d %d %d %d %d %d %d %d %d %u %lld %lld %lld %lld %lld %lld %lld", &w, &h, &sub, &semi, &tri, &d, &msb, &D,
                   &out16, &pad, &off, &seed, &k[0], &k[1], &k[2], &k[3], &k[4], &k[5], &k[6]) == 19) {
-        const int bps = d == 8 ? 1 : 2;
-        const int cw = sub == CE_YUV_444 ? w : (w + 1) / 2, ch = sub == CE_YUV_420 ? (h + 1) / 2 : h;
-        const int n_planes = sub == CE_YUV_400 ? 1 : semi ? 2 : 3;
-        const size_t rows[3] = {(size_t)h, (size_t)ch, (size_t)ch};
-        const size_t row_bytes[3] = {(size_t)w * bps, (size_t)(semi ? 2 * cw : cw) * bps, (size_t)cw * bps};
-        uint8_t *plane[3] = {};
-        size_t pitch[3] = {};
-        auto next = [&seed] { return seed = seed * 1664525u + 1013904223u; };
-        for (int p = 0; p < n_planes; p++) {
-            pitch[p] = row_bytes[p] + (size_t)pad;
-            const size_t size = (rows[p] - 1) * pitch[p] + row_bytes[p];  // what a caller owns, to the byte
-            plane[p] = static_cast<uint8_t *>(malloc(size));
-            for (size_t i = 0; i < size; i++) plane[p][i] = (uint8_t)(next() >> 24);
-            if (bps == 2 && !msb)  // low-aligned: in range, but one sample in 16 above it (ingest clamps those)
-                for (size_t r = 0; r < rows[p]; r++)
-                    for (size_t i = 0; i < row_bytes[p] / 2; i++) {
-                        uint16_t v;
-                        memcpy(&v, plane[p] + r * pitch[p] + 2 * i, 2);
-                        if ((next() >> 28) != 0) v &= (uint16_t)((1u << d) - 1u);
-                        memcpy(plane[p] + r * pitch[p] + 2 * i, &v, 2);
-                    }
-            for (size_t r = 0; r < rows[p]; r++) fwrite(plane[p] + r * pitch[p], 1, row_bytes[p], out);
-        }
+        host_planes P;
+        if (!make_planes(P, w, h, sub, semi, d, msb, pad, seed, out)) return 67;
         const size_t out_bytes = (size_t)w * h * 3 * (out16 ? 2 : 1);
         uint8_t *slab = static_cast<uint8_t *>(malloc(out_bytes + (size_t)off));
         memset(slab, 0xEE, out_bytes + (size_t)off);
         yuv_args a{};
-        a.p0 = plane[0], a.p1 = plane[1], a.p2 = plane[2];
-        a.pitch0 = pitch[0], a.pitch1 = pitch[1], a.pitch2 = pitch[2];
-        a.w = (uint32_t)w, a.h = (uint32_t)h, a.cw = (uint32_t)cw, a.ch = (uint32_t)ch;
-        a.shift = msb ? 16u - (uint32_t)d : 0u, a.maxv = (1u << d) - 1u, a.triangle = tri;
-        a.ky = k[0], a.krv = k[1], a.kgu = k[2], a.kgv = k[3], a.kbu = k[4], a.y0 = k[5], a.c0 = k[6];
-        a.m = ((int64_t)1 << D) - 1;
-        if (bps == 1) {
-            if (out16) run_sub<1, true>(sub, semi != 0, a, slab + off);
-            else run_sub<1, false>(sub, semi != 0, a, slab + off);
-        } else {
-            if (out16) run_sub<2, true>(sub, semi != 0, a, slab + off);
-            else run_sub<2, false>(sub, semi != 0, a, slab + off);
-        }
+        fill_yuv_args(a, P, w, h, d, msb, tri, k, ((int64_t)1 << D) - 1);
+        run(d == 8 ? 1 : 2, out16 != 0, sub, semi != 0, a, slab + off);
         for (int i = 0; i < off; i++)
             if (slab[i] != 0xEE) {
                 fprintf(stderr, "case %d wrote in front of its slot\n", cases);
@@ -121,7 +62,7 @@ int main(int argc, char **argv)
             }
         fwrite(slab + off, 1, out_bytes, out);
         free(slab);
-        for (int p = 0; p < n_planes; p++) free(plane[p]);
+        free_planes(P);
         cases++;
     }
     fclose(in);

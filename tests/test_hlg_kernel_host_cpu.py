@@ -1,4 +1,4 @@
-"""The device code of the HLG ingest (codec-eval_amd/csrc/hlg_kernel.h and yuv_hlg_kernel.h, with the hlg_pixel.h they share)
+"""The device code of the HLG ingest (codec-eval_amd/csrc/cicp_kernel.h and yuv_cicp_kernel.h, with the hlg_pixel.h they run)
 compiled for the host with -ffp-contract=off and run under AddressSanitizer and UBSan (tests/cpp/hlg_kernel_host.cpp, a
 stand-alone program): the same text the GPU runs, every thread of every block in turn, on sources, planes, tables and slabs
 allocated at exactly their size, the image written into slot 0, 1 or 2 of the slab.  Its output must equal the numpy
