@@ -488,6 +488,43 @@ pub struct YuvPlanes<'p> {
     pub msb_aligned: bool,
 }
 
+/// A gain map in host memory with its metadata (`ce_gainmap_image`, `ce_gainmap`): `samples` holds `height` rows of
+/// `width * channels` bytes, `channels` 1 or 3, at most the base image's size.
+#[derive(Clone, Copy, Debug)]
+pub struct GainMap<'p> {
+    pub samples: &'p [u8],
+    pub width: u32,
+    pub height: u32,
+    pub channels: u32,
+    pub metadata: sys::ce_gainmap,
+}
+
+impl GainMap<'_> {
+    /// The C struct, after checking the slice's length: the struct carries none (the library checks the rest).
+    fn to_sys(&self) -> Result<sys::ce_gainmap_image, HipError> {
+        let want = self.width as usize * self.height as usize * self.channels as usize;
+        if self.samples.len() != want {
+            return Err(HipError::MetricCalculation {
+                metric: "hip".into(),
+                reason: format!("Invalid gain map size: expected {want} bytes, got {}", self.samples.len()),
+            });
+        }
+        Ok(sys::ce_gainmap_image { samples: self.samples.as_ptr(), width: self.width, height: self.height, channels: self.channels })
+    }
+}
+
+/// `ce_gainmap_weight`: W of a gain map's metadata, or `None` for metadata the library refuses.
+pub fn gainmap_weight(metadata: &sys::ce_gainmap) -> Option<f64> {
+    let mut w = 0f64;
+    (unsafe { sys::ce_gainmap_weight(metadata, &mut w) } == sys::CE_OK).then_some(w)
+}
+
+/// `ce_gainmap_tables`: the log2-gain tables the kernel is handed, 256 per channel, or `None` for what the library refuses.
+pub fn gainmap_tables(metadata: &sys::ce_gainmap, channels: u32) -> Option<Vec<f64>> {
+    let mut out = vec![0f64; 256 * channels as usize];
+    (unsafe { sys::ce_gainmap_tables(metadata, channels, out.as_mut_ptr(), out.len()) } == sys::CE_OK).then_some(out)
+}
+
 impl YuvPlanes<'_> {
     /// The C struct, after checking that every plane given holds `rows` rows of its pitch (the library checks the rest).
     fn to_sys(&self, width: u32, height: u32) -> Result<sys::ce_yuv_image, HipError> {
@@ -575,6 +612,20 @@ impl HipMetrics {
         let mut out = vec![0f32; width as usize * height as usize * 3];
         let rc = unsafe {
             sys::ce_hlg_to_linear(self.ctx, pixels.as_ptr().cast(), pixels.len(), format, hlg, width, height, out.as_mut_ptr(), out.len())
+        };
+        self.check(rc, width, height, pixels.len())?;
+        Ok(out)
+    }
+
+    /// `ce_gainmap_to_linear`: one SDR base image (`format` and `pixels` as `hlg_to_linear`) read by `colour`, with the gain
+    /// map `map` applied -> packed f32 RGB, the HDR rendition in linear light with sRGB primaries.
+    pub fn gainmap_to_linear(&mut self, pixels: &[u8], format: i32, colour: &sys::ce_colour, map: &GainMap<'_>, width: u32, height: u32)
+                             -> Result<Vec<f32>, HipError> {
+        let image = map.to_sys()?;
+        let mut out = vec![0f32; width as usize * height as usize * 3];
+        let rc = unsafe {
+            sys::ce_gainmap_to_linear(self.ctx, pixels.as_ptr().cast(), pixels.len(), format, colour, &image, &map.metadata, width, height,
+                                      out.as_mut_ptr(), out.len())
         };
         self.check(rc, width, height, pixels.len())?;
         Ok(out)
@@ -753,6 +804,28 @@ impl HipBatch<'_> {
     /// `ce_batch_set_test_hlg`: the same for the test image of pair `pair_index`, bound to reference `ref_index`.
     pub fn set_test_hlg(&mut self, pair_index: u32, ref_index: u32, pixels: &[u8], format: i32, hlg: &sys::ce_hlg) -> Result<(), HipError> {
         let rc = unsafe { sys::ce_batch_set_test_hlg(self.handle, pair_index, ref_index, pixels.as_ptr().cast(), pixels.len(), format, hlg) };
+        self.check(rc, pixels.len())
+    }
+
+    /// `ce_batch_set_reference_gainmap`: an SDR base image (`format` and `pixels` as `hlg_to_linear`) read by `colour`, with
+    /// the gain map `map` applied on the device, into a reference slot of a LINEAR batch.
+    pub fn set_reference_gainmap(&mut self, ref_index: u32, pixels: &[u8], format: i32, colour: &sys::ce_colour, map: &GainMap<'_>)
+                                 -> Result<(), HipError> {
+        let image = map.to_sys()?;
+        let rc = unsafe {
+            sys::ce_batch_set_reference_gainmap(self.handle, ref_index, pixels.as_ptr().cast(), pixels.len(), format, colour, &image, &map.metadata)
+        };
+        self.check(rc, pixels.len())
+    }
+
+    /// `ce_batch_set_test_gainmap`: the same for the test image of pair `pair_index`, bound to reference `ref_index`.
+    pub fn set_test_gainmap(&mut self, pair_index: u32, ref_index: u32, pixels: &[u8], format: i32, colour: &sys::ce_colour, map: &GainMap<'_>)
+                            -> Result<(), HipError> {
+        let image = map.to_sys()?;
+        let rc = unsafe {
+            sys::ce_batch_set_test_gainmap(self.handle, pair_index, ref_index, pixels.as_ptr().cast(), pixels.len(), format, colour, &image,
+                                           &map.metadata)
+        };
         self.check(rc, pixels.len())
     }
 

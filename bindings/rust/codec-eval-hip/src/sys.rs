@@ -74,6 +74,32 @@ pub struct ce_hlg {
     pub white_nits: c_float,
 }
 
+/// `ce_gainmap_image` (24 bytes): a gain map's samples in host memory, `height` rows of `width * channels` bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ce_gainmap_image {
+    pub samples: *const u8,
+    pub width: u32,
+    pub height: u32,
+    /// 1 or 3
+    pub channels: u32,
+}
+
+/// `ce_gainmap` (72 bytes): a gain map's metadata; gains and headrooms are log2 values, and a single-channel map reads
+/// index 0 of each array only.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct ce_gainmap {
+    pub gain_min: [c_float; 3],
+    pub gain_max: [c_float; 3],
+    pub gamma: [c_float; 3],
+    pub base_offset: [c_float; 3],
+    pub alternate_offset: [c_float; 3],
+    pub base_headroom: c_float,
+    pub alternate_headroom: c_float,
+    pub display_headroom: c_float,
+}
+
 /// `ce_hdr_scores` (48 bytes): PSNR in the PQ domain and BT.2124's Delta E ITP of one pair of a linear batch, with the three
 /// exact integers they are finished from.
 #[repr(C)]
@@ -329,6 +355,15 @@ extern "C" {
                                 out_len: usize) -> c_int;
     pub fn ce_hlg_table(depth: u32, out: *mut c_float, n: usize) -> c_int;
     pub fn ce_hlg_params(h: *const ce_hlg, out: *mut c_double) -> c_int;
+    pub fn ce_batch_set_reference_gainmap(b: *mut ce_batch, ref_index: u32, pixels: *const c_void, len: usize, format: c_int,
+                                          c: *const ce_colour, map: *const ce_gainmap_image, g: *const ce_gainmap) -> c_int;
+    pub fn ce_batch_set_test_gainmap(b: *mut ce_batch, pair_index: u32, ref_index: u32, pixels: *const c_void, len: usize, format: c_int,
+                                     c: *const ce_colour, map: *const ce_gainmap_image, g: *const ce_gainmap) -> c_int;
+    pub fn ce_gainmap_to_linear(ctx: *mut ce_ctx, pixels: *const c_void, len: usize, format: c_int, c: *const ce_colour,
+                                map: *const ce_gainmap_image, g: *const ce_gainmap, w: u32, h: u32, out: *mut c_float,
+                                out_len: usize) -> c_int;
+    pub fn ce_gainmap_tables(g: *const ce_gainmap, channels: u32, out: *mut c_double, n: usize) -> c_int;
+    pub fn ce_gainmap_weight(g: *const ce_gainmap, w: *mut c_double) -> c_int;
     pub fn ce_batch_hdr_fidelity(b: *mut ce_batch, n_pairs: u32, depth: u32, white_nits: c_float, out: *mut ce_hdr_scores) -> c_int;
     pub fn ce_eval_pair_hdr_fidelity(ctx: *mut ce_ctx, reference: *const c_float, reference_len: usize, test: *const c_float,
                                      test_len: usize, width: u32, height: u32, depth: u32, white_nits: c_float,

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -132,6 +132,16 @@ class CeColour(C.Structure):
 
 class CeHlg(C.Structure):
     _fields_ = [("primaries", C.c_int), ("depth", C.c_uint32), ("peak_nits", C.c_float), ("system_gamma", C.c_float), ("white_nits", C.c_float)]
+
+
+class CeGainmapImage(C.Structure):
+    _fields_ = [("samples", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("channels", C.c_uint32)]
+
+
+class CeGainmap(C.Structure):
+    _fields_ = [("gain_min", C.c_float * 3), ("gain_max", C.c_float * 3), ("gamma", C.c_float * 3), ("base_offset", C.c_float * 3),
+                ("alternate_offset", C.c_float * 3), ("base_headroom", C.c_float), ("alternate_headroom", C.c_float),
+                ("display_headroom", C.c_float)]
 
 
 class CeHdrScores(C.Structure):
@@ -269,6 +279,11 @@ _PROTOTYPES = [
     ("ce_yuv_hlg_to_linear", _i, [_vp, C.POINTER(CeYuvImage), C.POINTER(CeHlg), _u32, _u32, _vp, _sz]),
     ("ce_hlg_table", _i, [_u32, _vp, _sz]),
     ("ce_hlg_params", _i, [C.POINTER(CeHlg), _dp]),
+    ("ce_batch_set_reference_gainmap", _i, [_vp, _u32, _vp, _sz, _i, C.POINTER(CeColour), C.POINTER(CeGainmapImage), C.POINTER(CeGainmap)]),
+    ("ce_batch_set_test_gainmap", _i, [_vp, _u32, _u32, _vp, _sz, _i, C.POINTER(CeColour), C.POINTER(CeGainmapImage), C.POINTER(CeGainmap)]),
+    ("ce_gainmap_to_linear", _i, [_vp, _vp, _sz, _i, C.POINTER(CeColour), C.POINTER(CeGainmapImage), C.POINTER(CeGainmap), _u32, _u32, _vp, _sz]),
+    ("ce_gainmap_tables", _i, [C.POINTER(CeGainmap), _u32, _dp, _sz]),
+    ("ce_gainmap_weight", _i, [C.POINTER(CeGainmap), _dp]),
     ("ce_batch_hdr_fidelity", _i, [_vp, _u32, _u32, _f32, C.POINTER(CeHdrScores)]),
     ("ce_eval_pair_hdr_fidelity", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _f32, C.POINTER(CeHdrScores)]),
     ("ce_pq_code_thresholds", _i, [_u32, _f32, _vp, _sz]),
@@ -421,6 +436,73 @@ def hlg_params(description: "HlgDescription") -> np.ndarray:
     out = np.empty(5, np.float64)
     c = description._c()
     _host_check(lib().ce_hlg_params(C.byref(c), out.ctypes.data_as(_dp)))
+    return out
+
+
+def _three(v) -> tuple:
+    """one number for all three channels, or three"""
+    return tuple(float(x) for x in v) if isinstance(v, (tuple, list, np.ndarray)) else (float(v),) * 3
+
+
+@dataclass(frozen=True, eq=False)
+class GainMap:
+    """A gain map and its metadata (ce_gainmap_image, ce_gainmap): `samples` uint8 [gh, gw] or [gh, gw, 1 or 3], at most the
+    base image's size; log2 gains, the map's gamma and the two offsets as one number or three; the log2 headrooms of the
+    base and the alternate rendition and the one to render for (default: the alternate's, the full HDR rendition).  With a
+    single-channel map only the first of each three is read."""
+    samples: np.ndarray
+    gain_min: tuple = 0.0
+    gain_max: tuple = 1.0
+    gamma: tuple = 1.0
+    base_offset: tuple = 1.0 / 64.0
+    alternate_offset: tuple = 1.0 / 64.0
+    base_headroom: float = 0.0
+    alternate_headroom: float = 1.0
+    display_headroom: Optional[float] = None
+
+    def __post_init__(self):
+        a = np.ascontiguousarray(self.samples)
+        if a.dtype != np.uint8 or a.ndim not in (2, 3):
+            raise CodecEvalError(CE_ERR_INVALID_ARG, "GainMap: samples must be uint8 [gh, gw] or [gh, gw, channels]")
+        object.__setattr__(self, "samples", a if a.ndim == 3 else a[..., None])
+        for name in ("gain_min", "gain_max", "gamma", "base_offset", "alternate_offset"):
+            object.__setattr__(self, name, _three(getattr(self, name)))
+        if self.display_headroom is None:
+            object.__setattr__(self, "display_headroom", self.alternate_headroom)
+
+    @property
+    def channels(self) -> int:
+        return self.samples.shape[2]
+
+    def with_samples(self, samples) -> "GainMap":
+        return replace(self, samples=samples)
+
+    def _meta(self) -> CeGainmap:
+        f3 = lambda v: (C.c_float * 3)(*v)  # noqa: E731
+        return CeGainmap(f3(self.gain_min), f3(self.gain_max), f3(self.gamma), f3(self.base_offset), f3(self.alternate_offset),
+                         self.base_headroom, self.alternate_headroom, self.display_headroom)
+
+    def _c(self):
+        """(ce_gainmap_image, ce_gainmap); the image points into self.samples"""
+        gh, gw, ch = self.samples.shape
+        return CeGainmapImage(self.samples.ctypes.data, gw, gh, ch), self._meta()
+
+
+def gainmap_weight(gain_map: "GainMap") -> float:
+    """W of a gain map's metadata (ce_gainmap_weight): how far the rendered headroom lies between the base's and the alternate's."""
+    out = C.c_double()
+    m = gain_map._meta()
+    _host_check(lib().ce_gainmap_weight(C.byref(m), C.byref(out)))
+    return out.value
+
+
+def gainmap_tables(gain_map: "GainMap", channels: Optional[int] = None) -> np.ndarray:
+    """The gain-map ingest's tables of map sample -> log2 gain with W folded in (ce_gainmap_tables), float64 [channels, 256]:
+    exactly what the kernel is handed."""
+    channels = gain_map.channels if channels is None else channels
+    out = np.empty((channels if channels in (1, 3) else 1, 256), np.float64)
+    m = gain_map._meta()
+    _host_check(lib().ce_gainmap_tables(C.byref(m), channels, out.ctypes.data_as(_dp), out.size))
     return out
 
 
@@ -1149,6 +1231,17 @@ class Context:
                                            out.size))
         return out
 
+    def gainmap_to_linear(self, pixels, width: int, height: int, colour: "ColourDescription", gain_map: "GainMap") -> np.ndarray:
+        """One SDR base image of uint8 / uint16 RGB(A) code values read by `colour`, with `gain_map` applied -> [h, w, 3]
+        float32 linear light with sRGB primaries, on the device (ce_gainmap_to_linear)."""
+        a = np.ascontiguousarray(pixels)
+        out = np.empty((height, width, 3), np.float32)
+        c = colour._c()
+        img, meta = gain_map._c()
+        self._check(lib().ce_gainmap_to_linear(self._h, a.ctypes.data, a.nbytes, _cicp_fmt(a), C.byref(c), C.byref(img), C.byref(meta), width,
+                                               height, out.ctypes.data, out.size))
+        return out
+
     def yuv_hlg_to_linear(self, image: "YuvImage", width: int, height: int, description: "HlgDescription") -> np.ndarray:
         """A decoder's Y'CbCr planes in HLG -> (height, width, 3) float32, in one kernel (ce_yuv_hlg_to_linear): yuv_to_rgb16
         at depth_out = description.depth followed by hlg_to_linear, bit for bit."""
@@ -1369,6 +1462,20 @@ class Batch:
         c, _keep = image._c()
         d = description._c()
         self.ctx._check(lib().ce_batch_set_test_yuv_hlg(self._h, pair_index, ref_index, C.byref(c), C.byref(d)))
+        self._pair_ref[pair_index] = ref_index
+
+    # an SDR base image with a gain map -> the HDR rendition on the device, into a slot of a linear batch
+    def set_reference_gainmap(self, ref_index: int, pixels, colour: "ColourDescription", gain_map: "GainMap"):
+        a, c = np.ascontiguousarray(pixels), colour._c()
+        img, meta = gain_map._c()
+        self.ctx._check(lib().ce_batch_set_reference_gainmap(self._h, ref_index, a.ctypes.data, a.nbytes, _cicp_fmt(a), C.byref(c), C.byref(img),
+                                                             C.byref(meta)))
+
+    def set_test_gainmap(self, pair_index: int, ref_index: int, pixels, colour: "ColourDescription", gain_map: "GainMap"):
+        a, c = np.ascontiguousarray(pixels), colour._c()
+        img, meta = gain_map._c()
+        self.ctx._check(lib().ce_batch_set_test_gainmap(self._h, pair_index, ref_index, a.ctypes.data, a.nbytes, _cicp_fmt(a), C.byref(c),
+                                                        C.byref(img), C.byref(meta)))
         self._pair_ref[pair_index] = ref_index
 
     # a transparent image composited over solid colours on the device: one upload fills len(backgrounds) consecutive slots

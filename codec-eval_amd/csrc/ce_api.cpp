@@ -566,6 +566,8 @@ void ce_batch_destroy(ce_batch *b)
     for (int k = 0; k < 2; k++) {
         if (b->h_wide[k]) hipHostFree(b->h_wide[k]);
         hipFree(b->d_wide[k]);
+        if (b->h_side[k]) hipHostFree(b->h_side[k]);
+        hipFree(b->d_side[k]);
         if (b->ev_wide[k]) hipEventDestroy(b->ev_wide[k]);
     }
     if (b->ev_up) hipEventDestroy(b->ev_up);

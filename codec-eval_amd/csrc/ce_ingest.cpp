@@ -476,6 +476,129 @@ int tagged_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, co
     });
 }
 
+// ---- gain-map images into a linear batch (gainmap.hip) ------------------------------------------------
+
+// the three headrooms, which is all that W reads
+int gainmap_headrooms_check(ce_ctx *ctx, const ce_gainmap *g)
+{
+    const struct {
+        const char *name;
+        float v;
+    } rooms[3] = {{"base_headroom", g->base_headroom}, {"alternate_headroom", g->alternate_headroom}, {"display_headroom", g->display_headroom}};
+    for (const auto &r : rooms)
+        if (!std::isfinite(r.v) || std::fabs(r.v) > 16.0f)
+            return ce_fail(ctx, CE_ERR_INVALID_ARG, std::string("gain-map ingest: ") + r.name + " must be finite and within [-16, 16]");
+    if (g->alternate_headroom == g->base_headroom)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "gain-map ingest: alternate_headroom equals base_headroom, so no weight is defined");
+    return CE_OK;
+}
+
+// the metadata that `channels` channels read
+int gainmap_meta_check(ce_ctx *ctx, const ce_gainmap *g, uint32_t channels)
+{
+    if (channels != 1 && channels != 3) return ce_fail(ctx, CE_ERR_INVALID_ARG, "gain-map ingest: channels must be 1 or 3, got " + std::to_string(channels));
+    if (int rc = gainmap_headrooms_check(ctx, g)) return rc;
+    for (uint32_t c = 0; c < channels; c++) {
+        const std::string at = " of channel " + std::to_string(c);
+        for (float v : {g->gain_min[c], g->gain_max[c], g->gamma[c], g->base_offset[c], g->alternate_offset[c]})
+            if (!std::isfinite(v)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "gain-map ingest: a value that is not finite in the metadata" + at);
+        if (!(g->gamma[c] > 0.0f)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "gain-map ingest: gamma must be > 0" + at);
+        if (g->gain_min[c] > g->gain_max[c]) return ce_fail(ctx, CE_ERR_INVALID_ARG, "gain-map ingest: gain_min is above gain_max" + at);
+        if (std::fabs(g->gain_min[c]) > 16.0f || std::fabs(g->gain_max[c]) > 16.0f)
+            return ce_fail(ctx, CE_ERR_INVALID_ARG, "gain-map ingest: the log2 gains must lie within [-16, 16]" + at);
+        if (std::fabs(g->base_offset[c]) > 1.0f || std::fabs(g->alternate_offset[c]) > 1.0f)
+            return ce_fail(ctx, CE_ERR_INVALID_ARG, "gain-map ingest: the offsets must lie within [-1, 1]" + at);
+    }
+    return CE_OK;
+}
+
+// one base image with its description, map and metadata: everything refused about any of them, then the plan
+int gainmap_check(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_colour *c, const ce_gainmap_image *map, const ce_gainmap *g,
+                  uint32_t w, uint32_t h, ce_gainmap_plan *plan)
+{
+    if (!pixels || !c || !map || !g || !map->samples) return ce_fail(ctx, CE_ERR_INVALID_ARG, "gain-map ingest: null pointer");
+    if (int rc = gainmap_meta_check(ctx, g, map->channels)) return rc;
+    if (map->width == 0 || map->height == 0 || map->width > w || map->height > h)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "gain-map ingest: a map of " + std::to_string(map->width) + " x " + std::to_string(map->height) +
+                                                    " for a base of " + std::to_string(w) + " x " + std::to_string(h) + ": it must be 1 x 1 at least and the base's size at most");
+    if (int rc = tagged_check(ctx, pixels, len, format, c, (size_t)w * h, &plan->base)) return rc;
+    plan->gw = map->width, plan->gh = map->height, plan->channels = map->channels;
+    for (int i = 0; i < 3; i++) {
+        const int k = map->channels == 3 ? i : 0;
+        plan->base_offset[i] = (double)g->base_offset[k], plan->alternate_offset[i] = (double)g->alternate_offset[k];
+    }
+    ce_build_gainmap_tables(g, map->channels, plan->ytab);
+    return CE_OK;
+}
+
+// what travels beside the base image: the plan's tables, then the map's samples (ce_launch_gainmap's d_side)
+size_t gainmap_side(const ce_gainmap_plan &plan, const ce_gainmap_image *map, uint8_t *h_side)
+{
+    std::memcpy(h_side, plan.ytab, plan.table_bytes());
+    std::memcpy(h_side + plan.table_bytes(), map->samples, plan.map_bytes());
+    return plan.table_bytes() + plan.map_bytes();
+}
+
+// One checked image into the slot at dst: the base through the wide staging pair, the tables and the map through a pair of
+// their own beside it, made on first use for the largest map the batch's shape admits (three channels at the base's size) -
+// a wide pair is w * h * 12 bytes, which a small RGBA16 base with such a map would overrun.  Both are busy until the launch
+// is done, under the wide pair's event.
+int upload_gainmap(ce_batch *b, uint8_t *dst, const void *pixels, size_t len, int format, const ce_gainmap_image *map, const ce_gainmap_plan &plan)
+{
+    ce_ctx *ctx = b->ctx;
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    int k;
+    if (int rc = wide_acquire(b, &k)) return rc;
+    if (!b->h_side[k]) {
+        const size_t cap = 3 * 256 * sizeof(double) + (size_t)b->w * b->h * 3;
+        CE_HIP(ctx, hipHostMalloc((void **)&b->h_side[k], cap, hipHostMallocDefault));
+        CE_HIP(ctx, hipMalloc((void **)&b->d_side[k], cap));
+    }
+    std::memcpy(b->h_wide[k], pixels, len);
+    const size_t side = gainmap_side(plan, map, b->h_side[k]);
+    CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], len, hipMemcpyHostToDevice, b->up_stream));
+    CE_HIP(ctx, hipMemcpyAsync(b->d_side[k], b->h_side[k], side, hipMemcpyHostToDevice, b->up_stream));
+    if (int rc = ce_launch_gainmap(ctx, b->up_stream, format, b->d_wide[k], b->d_side[k], reinterpret_cast<float *>(dst), b->w, b->h, plan)) return rc;
+    return wide_close(b, k);
+}
+
+const char *const kGainmapWantsLinear = "gain-map ingest writes linear light: it needs a linear batch (ce_batch_create_linear)";
+
+// ce_batch_set_*_gainmap
+int set_gainmap(ce_batch *b, bool test, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format, const ce_colour *c,
+                const ce_gainmap_image *map, const ce_gainmap *g)
+{
+    ce_gainmap_plan plan;
+    return set_slot(
+        b, test, pair_index, ref_index, kind_rule{false, kGainmapWantsLinear},
+        [&] { return gainmap_check(b->ctx, pixels, len, format, c, map, g, b->w, b->h, &plan); },
+        [&](uint8_t *slot) { return upload_gainmap(b, slot, pixels, len, format, map, plan); });
+}
+
+// ce_gainmap_to_linear: through the leaf scratch on the context's stream, the tables and the map behind the base at the next
+// 16-byte boundary
+int gainmap_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_colour *c, const ce_gainmap_image *map, const ce_gainmap *g,
+                      uint32_t w, uint32_t h, float *out, size_t out_len)
+{
+    if (!ctx || !out) return CE_ERR_INVALID_ARG;
+    if (w == 0 || h == 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, "gain-map ingest: empty image");
+    ce_gainmap_plan plan;
+    if (int rc = gainmap_check(ctx, pixels, len, format, c, map, g, w, h, &plan)) return rc;
+    const size_t n_px = (size_t)w * h, at = (len + 15) & ~(size_t)15, in_bytes = at + plan.table_bytes() + plan.map_bytes();
+    if (out_len != n_px * 3)
+        return ce_fail(ctx, CE_ERR_BAD_LENGTH, "gain-map ingest: out_len must be " + std::to_string(n_px * 3) + " floats, got " + std::to_string(out_len));
+    if (int rc = ce_leaf_scratch(ctx, in_bytes, n_px * 12)) return rc;
+    std::memcpy(ctx->leaf_h, pixels, len);
+    gainmap_side(plan, map, ctx->leaf_h + at);
+    CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_d_in, ctx->leaf_h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = ce_launch_gainmap(ctx, ctx->stream, format, ctx->leaf_d_in, ctx->leaf_d_in + at, reinterpret_cast<float *>(ctx->leaf_d_out), w, h, plan))
+        return rc;
+    CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_h, ctx->leaf_d_out, n_px * 12, hipMemcpyDeviceToHost, ctx->stream));
+    CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(out, ctx->leaf_h, n_px * 12);
+    return CE_OK;
+}
+
 // ---- planar Y'CbCr (yuv.hip), and with a description into a linear batch (yuv_cicp.hip) -------------------
 
 // a checked ce_yuv_image: what the kernel reads, and each plane's rows for the host copy
@@ -905,6 +1028,40 @@ int ce_batch_set_test_hlg(ce_batch *b, uint32_t pair_index, uint32_t ref_index, 
 int ce_hlg_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_hlg *h, uint32_t w, uint32_t height, float *out, size_t out_len)
 {
     return tagged_to_linear(ctx, pixels, len, format, h, w, height, out, out_len);
+}
+
+// gain maps
+int ce_gainmap_weight(const ce_gainmap *g, double *w)
+{
+    if (!g || !w) return ce_fail(nullptr, CE_ERR_INVALID_ARG, "ce_gainmap_weight: null pointer");
+    if (int rc = gainmap_headrooms_check(nullptr, g)) return rc;
+    *w = ce_build_gainmap_weight(g);
+    return CE_OK;
+}
+
+int ce_gainmap_tables(const ce_gainmap *g, uint32_t channels, double *out, size_t n)
+{
+    if (!g || !out) return ce_fail(nullptr, CE_ERR_INVALID_ARG, "ce_gainmap_tables: null pointer");
+    if (int rc = gainmap_meta_check(nullptr, g, channels)) return rc;
+    if (n != (size_t)256 * channels) return ce_fail(nullptr, CE_ERR_INVALID_ARG, "ce_gainmap_tables: n must be 256 * channels");
+    ce_build_gainmap_tables(g, channels, out);
+    return CE_OK;
+}
+
+int ce_batch_set_reference_gainmap(ce_batch *b, uint32_t ref_index, const void *pixels, size_t len, int format, const ce_colour *c,
+                                   const ce_gainmap_image *map, const ce_gainmap *g)
+{
+    return set_gainmap(b, false, 0, ref_index, pixels, len, format, c, map, g);
+}
+int ce_batch_set_test_gainmap(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format, const ce_colour *c,
+                              const ce_gainmap_image *map, const ce_gainmap *g)
+{
+    return set_gainmap(b, true, pair_index, ref_index, pixels, len, format, c, map, g);
+}
+int ce_gainmap_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_colour *c, const ce_gainmap_image *map, const ce_gainmap *g,
+                         uint32_t w, uint32_t h, float *out, size_t out_len)
+{
+    return gainmap_to_linear(ctx, pixels, len, format, c, map, g, w, h, out, out_len);
 }
 
 // planar Y'CbCr, alone and with either description (DESIGN.md sections 13, 16, 18)

@@ -191,6 +191,9 @@ struct ce_batch {
     hipEvent_t ev_wide[2] = {};
     bool wide_busy[2] = {};
     int next_wide = 0;
+    // what a gain-map ingest stages beside its base image, which takes wide pair k: the log2-gain tables and the map's samples
+    // in a pinned + device pair of their own (ce_ingest.cpp: upload_gainmap, which states their size), busy with wide pair k
+    uint8_t *h_side[2] = {}, *d_side[2] = {};
 
     // SSIMULACRA2 working set.  Image slots: [0, max_refs) references, then tests.
     int n_scales = 0;
@@ -520,6 +523,21 @@ int ce_launch_tagged(ce_ctx *ctx, hipStream_t stream, int format, const void *d_
 // w x h pixels of `src`, whose k was built for depth_out = log2(px.maxv + 1), -> packed f32 RGB at d_dst: ce_launch_yuv's
 // integer RGB in [0, maxv] handed pixel by pixel to ce_launch_tagged's pixel, one launch (yuv_cicp.hip)
 int ce_launch_yuv_tagged(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32_t w, uint32_t h, float *d_dst, const ce_linear_pixel &px);
+// What one gain-map ingest applies (checked and filled by ce_ingest.cpp: gainmap_check): the base's CICP pixel, the map's
+// shape, the offsets per output channel as doubles and the log2-gain tables ce_gainmap_tables returns, 256 per map channel
+struct ce_gainmap_plan {
+    ce_linear_pixel base;
+    uint32_t gw, gh, channels;
+    double base_offset[3], alternate_offset[3];
+    double ytab[3 * 256];
+    size_t table_bytes() const { return (size_t)channels * 256 * sizeof(double); }
+    size_t map_bytes() const { return (size_t)gw * gh * channels; }
+};
+// w x h RGB(A) pixels of u8 / u16 samples at d_src (16-byte aligned staging; the four formats of ce_launch_tagged) with the
+// gain map applied -> packed f32 RGB at d_dst, one launch (gainmap.hip).  d_side holds the plan's tables (8-byte aligned) and
+// behind them the map's samples, as ce_ingest.cpp's gainmap_side packs them.
+int ce_launch_gainmap(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, const uint8_t *d_side, float *d_dst, uint32_t w, uint32_t h,
+                      const ce_gainmap_plan &plan);
 
 // pairs [0, n_pairs) of a linear batch -> d_out[pair][3] = pq_sse, itp_sum_q20, itp_max_q20, cleared and filled on the
 // launching stream (hdr_fidelity.hip): d_table = T[1 .. maxv], 64-byte aligned, d_coarse the level staged in LDS (the table
@@ -543,6 +561,10 @@ void ce_build_hdr_fidelity_matrices(float a[9], float b[9]);
 // the HLG ingest's inverse-OETF table (include/ce_metrics.h: ce_hlg_table) and the Y row of the f64 XYZ <- src matrix of
 // `primaries` (ce_hlg_params' kR, kG, kB); false for primaries that are not offered
 void ce_build_hlg_table(uint32_t maxv, float *lut);
+// the gain-map ingest's weight W (include/ce_metrics.h: ce_gainmap_weight) and its log2-gain tables, 256 doubles for each of
+// `channels` channels with W folded in (ce_gainmap_tables), of checked metadata
+double ce_build_gainmap_weight(const ce_gainmap *g);
+void ce_build_gainmap_tables(const ce_gainmap *g, uint32_t channels, double *out);
 bool ce_build_luminance_row(int primaries, double k[3]);
 // the CICP ingest's transfer table (include/ce_metrics.h: ce_transfer_table) and primaries matrix (ce_colour_matrix); false
 // for a code point that is not offered

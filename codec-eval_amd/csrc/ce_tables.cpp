@@ -419,3 +419,27 @@ bool ce_build_luminance_row(int primaries, double k[3])
     k[0] = m[3], k[1] = m[4], k[2] = m[5];
     return true;
 }
+
+// ---- gain-map ingest (include/ce_metrics.h: ce_gainmap_weight, ce_gainmap_tables) ------------------
+// W = clamp((display - base) / (alternate - base), 0, 1) over the three log2 headrooms, in f64; alternate != base was checked
+double ce_build_gainmap_weight(const ce_gainmap *g)
+{
+    const double w = ((double)g->display_headroom - (double)g->base_headroom) / ((double)g->alternate_headroom - (double)g->base_headroom);
+    return w < 0.0 ? 0.0 : (w > 1.0 ? 1.0 : w);
+}
+
+// Y_c[v] = W * (gain_min_c + (gain_max_c - gain_min_c) * (v / 255)^(1 / gamma_c)) in f64, every operation rounded separately;
+// gamma_c == 1 takes no power, so that Y_c is affine in v to the last bit
+void ce_build_gainmap_tables(const ce_gainmap *g, uint32_t channels, double *out)
+{
+    const double w = ce_build_gainmap_weight(g);
+    for (uint32_t c = 0; c < channels; c++) {
+        const double lo = (double)g->gain_min[c], span = (double)g->gain_max[c] - lo, inv_gamma = 1.0 / (double)g->gamma[c];
+        for (int v = 0; v < 256; v++) {
+            const double x = (double)v / 255.0;
+            const double e = g->gamma[c] == 1.0f ? x : std::pow(x, inv_gamma);
+            const double scaled = span * e;
+            out[256 * c + v] = w * (lo + scaled);
+        }
+    }
+}

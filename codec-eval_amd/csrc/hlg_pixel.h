@@ -22,6 +22,31 @@ struct hlg_args {
     double a;           // peak_nits / white_nits
 };
 
+// exp(f) * 2^n for |f| <= ln2 / 2 and an integral n with 2^n normal: exp f as the degree-14 Taylor series in Horner form from
+// 1 / 14! down, times 2^n built from bits.  The second half of hlg_pow, and of gainmap_pixel.h's gm_exp2.
+__device__ __forceinline__ double exp_times_pow2(double f, double n)
+{
+    double q = 1.0 / 87178291200.0;  // 1 / 14!
+    q = q * f + 1.0 / 6227020800.0;
+    q = q * f + 1.0 / 479001600.0;
+    q = q * f + 1.0 / 39916800.0;
+    q = q * f + 1.0 / 3628800.0;
+    q = q * f + 1.0 / 362880.0;
+    q = q * f + 1.0 / 40320.0;
+    q = q * f + 1.0 / 5040.0;
+    q = q * f + 1.0 / 720.0;
+    q = q * f + 1.0 / 120.0;
+    q = q * f + 1.0 / 24.0;
+    q = q * f + 1.0 / 6.0;
+    q = q * f + 1.0 / 2.0;
+    q = q * f + 1.0;
+    q = q * f + 1.0;
+    const uint64_t sbits = (uint64_t)((int64_t)n + 1023) << 52;
+    double scale;
+    __builtin_memcpy(&scale, &sbits, 8);
+    return q * scale;
+}
+
 // x^g for a normal x > 0.  x = m 2^e with m in [sqrt(1/2), sqrt(2)); ln m = 2 t P(t^2) with t = (m - 1) / (m + 1) and P the
 // odd-reciprocal series to 1/21 in Horner form; y = g (ln m + e ln2); n = rint(y / ln2), f = y - n ln2 in [-ln2 / 2, ln2 / 2];
 // exp f as the degree-14 Taylor series in Horner form; times 2^n built from bits.  Within 5e-15 relative of the real power
@@ -57,25 +82,7 @@ __device__ __forceinline__ double hlg_pow(double x, double g)
     const double y = g * (ln_m + (double)e * kLn2);
     const double n = __builtin_rint(y / kLn2);
     const double f = y - n * kLn2;
-    double q = 1.0 / 87178291200.0;  // 1 / 14!
-    q = q * f + 1.0 / 6227020800.0;
-    q = q * f + 1.0 / 479001600.0;
-    q = q * f + 1.0 / 39916800.0;
-    q = q * f + 1.0 / 3628800.0;
-    q = q * f + 1.0 / 362880.0;
-    q = q * f + 1.0 / 40320.0;
-    q = q * f + 1.0 / 5040.0;
-    q = q * f + 1.0 / 720.0;
-    q = q * f + 1.0 / 120.0;
-    q = q * f + 1.0 / 24.0;
-    q = q * f + 1.0 / 6.0;
-    q = q * f + 1.0 / 2.0;
-    q = q * f + 1.0;
-    q = q * f + 1.0;
-    const uint64_t sbits = (uint64_t)((int64_t)n + 1023) << 52;
-    double scale;
-    __builtin_memcpy(&scale, &sbits, 8);
-    return q * scale;
+    return exp_times_pow2(f, n);
 }
 
 // steps 1 - 5 of the definition: e = table[min(v, maxv)]; ys = (kR e_r + kG e_g) + kB e_b in f64; k = (float)(A ys^(gamma-1)),

@@ -524,6 +524,31 @@ inline void batch_set_test_yuv_hlg(const HipBackend &be, ce_batch *batch, uint32
 {
     detail::check(be, ce_batch_set_test_yuv_hlg(batch, pair_index, ref_index, &image, &hlg), "yuv_hlg", 0, 0, 0);
 }
+// ---- gain-map images -> their HDR rendition in linear light (include/ce_metrics.h: ce_gainmap_to_linear) ----
+// an SDR base image read by a ColourDescription, a small 8-bit map in host memory (the struct carries no length: width *
+// height * channels bytes are read) and the metadata, whose gains and headrooms are log2 values
+using GainMapImage = ce_gainmap_image;
+using GainMapMetadata = ce_gainmap;
+// One base image (format: CE_PIXEL_RGB8 / RGBA8 / RGB16 / RGBA16; len in bytes) with its map applied -> packed float RGB
+inline std::vector<float> gainmap_to_linear(const HipBackend &be, const void *pixels, size_t len, int format, const ColourDescription &colour,
+                                            const GainMapImage &map, const GainMapMetadata &metadata, uint32_t width, uint32_t height)
+{
+    std::vector<float> out((size_t)width * height * 3);
+    detail::check(be, ce_gainmap_to_linear(be.ctx(), pixels, len, format, &colour, &map, &metadata, width, height, out.data(), out.size()), "gainmap",
+                  width, height, len);
+    return out;
+}
+// straight into a slot of a linear batch (eval::batch_linear)
+inline void batch_set_reference_gainmap(const HipBackend &be, ce_batch *batch, uint32_t ref_index, const void *pixels, size_t len, int format,
+                                        const ColourDescription &colour, const GainMapImage &map, const GainMapMetadata &metadata)
+{
+    detail::check(be, ce_batch_set_reference_gainmap(batch, ref_index, pixels, len, format, &colour, &map, &metadata), "gainmap", 0, 0, 0);
+}
+inline void batch_set_test_gainmap(const HipBackend &be, ce_batch *batch, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len,
+                                   int format, const ColourDescription &colour, const GainMapImage &map, const GainMapMetadata &metadata)
+{
+    detail::check(be, ce_batch_set_test_gainmap(batch, pair_index, ref_index, pixels, len, format, &colour, &map, &metadata), "gainmap", 0, 0, 0);
+}
 // ---- HDR fidelity of linear batches: PQ-PSNR and BT.2124 Delta E ITP (include/ce_metrics.h: ce_batch_hdr_fidelity) ----
 // depth (10, 12 or 16) names the PQ code grid, white_nits the luminance of sample value 1.0
 using HdrFidelity = ce_hdr_scores;

@@ -16,7 +16,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from . import (ColourDescription, HlgDescription, DEEP_DEPTHS, PIXEL_RGB_F32, PIXEL_RGB8, PIXEL_RGB16, PIXEL_RGBA8, PIXEL_RGBA16, Batch, CodecEvalError, ColorTable, Context, DimensionMismatch, MetricCalculation,
+from . import (ColourDescription, GainMap, HlgDescription, DEEP_DEPTHS, PIXEL_RGB_F32, PIXEL_RGB8, PIXEL_RGB16, PIXEL_RGBA8, PIXEL_RGBA16, Batch, CodecEvalError, ColorTable, Context, DimensionMismatch, MetricCalculation,
                MetricConfig, MetricResult, _error_obj, estimate_batch_bytes, CE_ERR_BACKEND)
 from . import RESAMPLE_LANCZOS3
 from . import CHROMA_TRIANGLE, MEM_HOST, YUV_400, YUV_420, YUV_444, YUV_BT601, YUV_FULL, YUV_PLANAR, YUV_SEMIPLANAR, YuvImage, yuv_coefficients
@@ -28,6 +28,20 @@ __all__ = ["ImageData", "EncodeRequest", "EvalConfig", "EvalConfigBuilder", "Eva
 
 
 Colour = Union[ColourDescription, HlgDescription]  # what colour= takes: H.273 code points, or BT.2100 HLG with its display
+
+
+def _gain_map_for(gain_map: Optional[GainMap], colour: Optional["Colour"], width: int, height: int) -> Optional[GainMap]:
+    """A constructor's gain_map=: a GainMap no larger than the image, whose base a ColourDescription (or none: sRGB) reads."""
+    if gain_map is None:
+        return None
+    if not isinstance(gain_map, GainMap):
+        raise TypeError("gain_map= takes a GainMap")
+    if isinstance(colour, HlgDescription):
+        raise ValueError("a gain map's base image is read by a ColourDescription, not an HlgDescription")
+    gh, gw = gain_map.samples.shape[:2]
+    if not (1 <= gw <= int(width) and 1 <= gh <= int(height)):
+        raise ValueError(f"a gain map of {gw} x {gh} for an image of {width} x {height}: it must be 1 x 1 at least and the image's size at most")
+    return gain_map
 
 
 def _colour_at(colour: Optional[Colour], depth: int) -> Optional[Colour]:
@@ -49,14 +63,19 @@ class ImageData:
     # decode with a non-sRGB description is scored in linear light through a linear batch.
     colour: Optional[Colour] = None
     linear: bool = False  # `data` is packed float32 RGB, linear light with sRGB primaries (ImageData.linear_f32)
+    # `data` is the SDR base of a gain-map image (Ultra HDR JPEG, gain-map AVIF / HEIC / JPEG XL) and this its map with the
+    # metadata: the HDR rendition is scored, in linear light.  Not with an HlgDescription.
+    gain_map: Optional[GainMap] = None
 
     @staticmethod
-    def rgb(data, width: int, height: int, colour: Optional[Colour] = None) -> "ImageData":
-        return ImageData(np.ascontiguousarray(data, dtype=np.uint8).reshape(-1), int(width), int(height), 3, colour=_colour_at(colour, 8))
+    def rgb(data, width: int, height: int, colour: Optional[Colour] = None, gain_map: Optional[GainMap] = None) -> "ImageData":
+        return ImageData(np.ascontiguousarray(data, dtype=np.uint8).reshape(-1), int(width), int(height), 3, colour=_colour_at(colour, 8),
+                         gain_map=_gain_map_for(gain_map, colour, width, height))
 
     @staticmethod
-    def rgba(data, width: int, height: int, colour: Optional[Colour] = None) -> "ImageData":
-        return ImageData(np.ascontiguousarray(data, dtype=np.uint8).reshape(-1), int(width), int(height), 4, colour=_colour_at(colour, 8))
+    def rgba(data, width: int, height: int, colour: Optional[Colour] = None, gain_map: Optional[GainMap] = None) -> "ImageData":
+        return ImageData(np.ascontiguousarray(data, dtype=np.uint8).reshape(-1), int(width), int(height), 4, colour=_colour_at(colour, 8),
+                         gain_map=_gain_map_for(gain_map, colour, width, height))
 
     @staticmethod
     def linear_f32(data, width: int, height: int) -> "ImageData":
@@ -72,20 +91,20 @@ class ImageData:
         return ImageData(np.ascontiguousarray(data, dtype=np.uint8).reshape(-1), int(width), int(height), 3, bytes(icc_profile))
 
     @staticmethod
-    def rgb16(data, width: int, height: int, depth: int, colour: Optional[Colour] = None) -> "ImageData":
+    def rgb16(data, width: int, height: int, depth: int, colour: Optional[Colour] = None, gain_map: Optional[GainMap] = None) -> "ImageData":
         """A decoder's PixelData::Rgb16 (crates/codec-iter/src/avif_config.rs:122-170) kept as it is: packed uint16
         samples of `depth` bits, each meaning the sRGB value v / (2^depth - 1).  A session scores it through a deep batch."""
         if depth not in DEEP_DEPTHS:
             raise ValueError(f"depth must be one of {DEEP_DEPTHS}, got {depth}")
         return ImageData(np.ascontiguousarray(data, dtype=np.uint16).reshape(-1), int(width), int(height), 3, None, int(depth),
-                         colour=_colour_at(colour, depth))
+                         colour=_colour_at(colour, depth), gain_map=_gain_map_for(gain_map, colour, width, height))
 
     @staticmethod
-    def rgba16(data, width: int, height: int, depth: int, colour: Optional[Colour] = None) -> "ImageData":
+    def rgba16(data, width: int, height: int, depth: int, colour: Optional[Colour] = None, gain_map: Optional[GainMap] = None) -> "ImageData":
         if depth not in DEEP_DEPTHS:
             raise ValueError(f"depth must be one of {DEEP_DEPTHS}, got {depth}")
         return ImageData(np.ascontiguousarray(data, dtype=np.uint16).reshape(-1), int(width), int(height), 4, None, int(depth),
-                         colour=_colour_at(colour, depth))
+                         colour=_colour_at(colour, depth), gain_map=_gain_map_for(gain_map, colour, width, height))
 
     @staticmethod
     def yuv(planes, width: int, height: int, subsampling: int = YUV_420, layout: int = YUV_PLANAR, matrix: int = YUV_BT601,
@@ -143,6 +162,8 @@ class ImageData:
         return out
 
     def to_rgb8_vec(self) -> np.ndarray:  # session.rs:98-117 (host copy; the session itself strips alpha on the device)
+        if self.gain_map is not None:  # its RGB8 form would be the base alone, which scores a damaged gain map as identical
+            raise MetricCalculation(CE_ERR_BACKEND, "Metric calculation failed: an image with a gain map is scored in linear light and has no RGB8 form")
         if self.in_linear_light:  # no reference rule turns HDR or wide-gamut content into sRGB bytes: it is scored in linear light
             raise MetricCalculation(CE_ERR_BACKEND, "Metric calculation failed: an image in linear light or with a non-sRGB colour description has no RGB8 form")
         if self.yuv_image is not None:
@@ -155,8 +176,9 @@ class ImageData:
 
     @property
     def in_linear_light(self) -> bool:
-        """Scored through a linear batch: linear float32, or code values with a description other than sRGB's."""
-        return self.linear or (self.colour is not None and not self.colour.is_srgb)
+        """Scored through a linear batch: linear float32, code values with a description other than sRGB's, or a base image
+        with a gain map."""
+        return self.linear or self.gain_map is not None or (self.colour is not None and not self.colour.is_srgb)
 
     @property
     def has_alpha(self) -> bool:
@@ -447,7 +469,7 @@ class EvalSession:
     def _set_linear(self, batch: Batch, image: ImageData, ref_index: int, pair_index: Optional[int]):
         """One image into a slot of a linear batch: float32 as it is, code values through the CICP ingest - by their own
         description, an untagged image as sRGB (1, 13) at its own depth - and Y'CbCr planes through the fused ingest; an
-        HlgDescription takes the HLG calls of the same shape."""
+        HlgDescription takes the HLG calls of the same shape, an image with a gain map the gain-map calls."""
         def refuse(what):
             raise MetricCalculation(CE_ERR_BACKEND, f"Metric calculation failed: linear-light scoring: {what}")
         if image.yuv_image is not None:  # the planes' own tag, an untagged image as sRGB; depth 16 keeps what the matrix gives between code points
@@ -469,7 +491,12 @@ class EvalSession:
             return batch.set_reference(ref_index, image.data) if pair_index is None else batch.set_test(pair_index, ref_index, image.data)
         colour = image.colour or ColourDescription.SRGB.with_depth(image.depth or 8)
         px = image.data.reshape(image.height, image.width, image.channels)
-        if isinstance(colour, HlgDescription):
+        if image.gain_map is not None:
+            if pair_index is None:
+                batch.set_reference_gainmap(ref_index, px, colour, image.gain_map)
+            else:
+                batch.set_test_gainmap(pair_index, ref_index, px, colour, image.gain_map)
+        elif isinstance(colour, HlgDescription):
             if pair_index is None:
                 batch.set_reference_hlg(ref_index, px, colour)
             else:

@@ -629,6 +629,7 @@ int ce_composite_rgba16(ce_ctx *ctx, const uint16_t *rgba, size_t len, uint32_t 
  *   ce_batch_set_reference_cicp / ce_batch_set_test_cicp take tagged integer code values (below);
  *   ce_batch_set_reference_yuv_cicp / ce_batch_set_test_yuv_cicp take Y'CbCr planes with such a tag (below);
  *   ce_batch_set_reference_hlg / ce_batch_set_test_hlg and their *_yuv_hlg forms take BT.2100 HLG (below);
+ *   ce_batch_set_reference_gainmap / ce_batch_set_test_gainmap take an SDR base image with a gain map (below);
  *   ce_batch_bind_pair, ce_batch_run, ce_batch_launch, ce_batch_collect, ce_batch_butteraugli_pnorm3 and the three map
  *     readers work as on any batch;
  *   CE_ERR_INVALID_ARG, with the reason in ce_last_error and the batch still usable: CE_FLAG_XYB_ROUNDTRIP,
@@ -784,6 +785,71 @@ int ce_yuv_hlg_to_linear(ce_ctx *ctx, const ce_yuv_image *image, const ce_hlg *h
  * what the kernel is handed.  CE_ERR_INVALID_ARG for what the calls above refuse about depth and description. */
 int ce_hlg_table(uint32_t depth, float *out, size_t n);
 int ce_hlg_params(const ce_hlg *h, double out[5]);
+
+/* Gain-map ingest: an SDR base image, a small 8-bit gain map and a few numbers of metadata - what an
+ * Ultra HDR JPEG or a gain-map AVIF / HEIC / JPEG XL file carries, as ISO 21496-1 describes it - -> the HDR rendition in a
+ * slot of a linear batch, on the device.  The formula below is the ISO 21496-1 / Adobe gain-map application as its authors
+ * recalled it; it has not been checked against the text of the standard, so THIS text is the contract, not the standard.
+ * The base is an image of the batch's shape w x h in CE_PIXEL_RGB8 / RGBA8 / RGB16 / RGBA16 (alpha dropped), read by a
+ * ce_colour exactly as step 1 of the CICP definition reads it.  The map is gw x gh samples of `channels` (1 or 3) bytes,
+ * tightly packed, with 1 <= gw <= w and 1 <= gh <= h, in host memory and consumed on return; it carries no length of its
+ * own: gw * gh * channels bytes are read (the bindings check their containers).  Gains and headrooms are log2 values; with
+ * channels == 1 only index 0 of each array of the metadata is read, and serves all three colour channels.
+ * Per channel c of the map, on the host in f64 (ce_gainmap_weight, ce_gainmap_tables), every operation rounded separately:
+ *   W      = clamp((display_headroom - base_headroom) / (alternate_headroom - base_headroom), 0, 1)
+ *   Y_c[v] = W * (gain_min_c + (gain_max_c - gain_min_c) * (v / 255)^(1 / gamma_c))   for v = 0 .. 255
+ * with the power the host libm's pow, and no power at all for gamma_c == 1, so that Y_c is then affine in v to the last bit.
+ * W == 0 gives a table of zeros.
+ * Per pixel (x, y) of the base, on the device, every f32 and f64 operation rounded separately (no fused multiply-add):
+ *   1. t_c = table[min(v_c, maxv)] in f32, the CICP definition's step 1.
+ *   2. The map is sampled with centres aligned and edges clamped, in integers:
+ *        nx = clamp((2x + 1) * gw - w, 0, (gw - 1) * 2w);  i0 = nx / (2w);  i1 = min(i0 + 1, gw - 1);
+ *        fx = (double)(nx - i0 * 2w) / (double)(2w);   the same in y with gh and h, giving j0, j1, fy.
+ *      A map of the base's own size has fx = fy = 0 everywhere.
+ *   3. lerp(a, b, f) = a + f * (b - a), three operations;  m_ji = the map's sample at column i of row j;
+ *        y_c = lerp(lerp(Y_c[m_j0i0], Y_c[m_j0i1], fx), lerp(Y_c[m_j1i0], Y_c[m_j1i1], fx), fy).
+ *      The table values - log2 gains - are interpolated; for gamma 1 that is the interpolation of the encoded map.  A
+ *      constant map gives Y_c[v] exactly.
+ *   4. g_c = gm_exp2(y_c):  n = rint(y), f = (y - n) * 0.6931471805599453, exp f = the degree-14 Taylor series in Horner form
+ *      from 1/14! down that hlg_pow ends with, result = exp f * 2^n with 2^n built from bits.  gm_exp2 of an integer is exactly
+ *      that power of two; on [-16, 16] it stays within 1e-15 relative of the real 2^y (measured: 2.3e-16 against numpy.exp2).
+ *   5. o_c = (float)(((double)t_c + base_offset_c) * g_c - alternate_offset_c): one f64 sum, product and difference, one
+ *      rounding to f32.  A single-channel map computes one y and one g per pixel.
+ *   6. The CICP definition's steps 3 and 4 - the f32 matrix for primaries other than 1, the clamp of a linear image: the gain
+ *      is applied in the base's primaries.
+ * Exact anchors: W == 0 with zero offsets gives ce_cicp_to_linear(base) bit for bit; a constant map with gain_min = gain_max
+ * = 1, W = 1 and zero offsets gives exactly twice that (before the clamp).
+ * tests/gainmap_restatement.py restates all of this in numpy; the device equals it bit for bit, on every float.
+ * ce_batch_set_*_gainmap: one image into a reference / test slot of a LINEAR batch with the staging, stream and ordering of
+ * ce_batch_set_*_cicp.  ce_gainmap_to_linear: one w x h image to packed float RGB in host memory (out_len = w * h * 3).
+ * CE_ERR_INVALID_ARG, with the reason in ce_last_error and the batch still usable: everything ce_batch_set_*_cicp refuses
+ * about the base, a batch that is not linear, a null pointer, channels other than 1 or 3, a map dimension of 0 or above the
+ * base's, and in the metadata that is read: a value that is not finite, gamma <= 0, gain_min > gain_max, |gain| or
+ * |headroom| above 16, |offset| above 1, alternate_headroom == base_headroom.  CE_ERR_BAD_LENGTH for a wrong len or out_len.
+ * Not part of this: gain application in the alternate image's primaries, Y'CbCr-plane bases and device-resident sources,
+ * maps deeper than 8 bits, interpolation other than bilinear, parsing of the containers' metadata boxes (XMP / ISO box),
+ * ce_ref_* handles and the pooled ce_eval_batch on linear batches. */
+typedef struct ce_gainmap_image {
+    const uint8_t *samples; /* height rows of width * channels bytes, no padding */
+    uint32_t width, height, channels;
+} ce_gainmap_image;
+typedef struct ce_gainmap {
+    float gain_min[3], gain_max[3]; /* log2 of the smallest and the largest gain the map encodes */
+    float gamma[3];                 /* > 0: the map stores ((log2 gain - min) / (max - min))^gamma */
+    float base_offset[3], alternate_offset[3];
+    float base_headroom, alternate_headroom; /* log2 of the two renditions' HDR headroom */
+    float display_headroom;                  /* log2 of the headroom to render for */
+} ce_gainmap;                                /* 72 bytes */
+int ce_batch_set_reference_gainmap(ce_batch *b, uint32_t ref_index, const void *pixels, size_t len, int format, const ce_colour *c,
+                                   const ce_gainmap_image *map, const ce_gainmap *g);
+int ce_batch_set_test_gainmap(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format,
+                              const ce_colour *c, const ce_gainmap_image *map, const ce_gainmap *g);
+int ce_gainmap_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_colour *c, const ce_gainmap_image *map,
+                         const ce_gainmap *g, uint32_t w, uint32_t h, float *out, size_t out_len);
+/* Pure host functions: the log2-gain tables (n = 256 * channels doubles, channel by channel) and W - exactly what the kernel
+ * is handed.  CE_ERR_INVALID_ARG for what the calls above refuse about channels and metadata. */
+int ce_gainmap_tables(const ce_gainmap *g, uint32_t channels, double *out, size_t n);
+int ce_gainmap_weight(const ce_gainmap *g, double *w);
 
 /* ---- HDR fidelity of linear batches: PQ-PSNR and BT.2124 Delta E ITP ----------------------------------
  * The two plain fidelity numbers HDR encoders are compared by, next to the perceptual scores: PSNR of the PQ code values, and
