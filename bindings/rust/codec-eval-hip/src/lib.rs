@@ -716,6 +716,70 @@ pub fn hdr_fidelity_matrices() -> ([f32; 9], [f32; 9]) {
     (a, b)
 }
 
+/// `ce_icc_describe`: what the library's parser reads from an ICC profile, without a device.  `kind` is
+/// `sys::CE_ICC_SUPPORTED` for the matrix/TRC profiles `HipIccProfile` takes.
+pub fn icc_describe(profile: &[u8]) -> sys::ce_icc_description {
+    let mut d: sys::ce_icc_description = unsafe { std::mem::zeroed() };
+    unsafe { sys::ce_icc_describe(profile.as_ptr(), profile.len(), &mut d) };
+    d
+}
+
+/// `ce_icc`: a matrix/TRC ICC profile applied on the device, parsed by the library itself (no CMS).  A LUT-based, Gray, CMYK
+/// or malformed profile is refused with the reason; those keep the colour-table route (`ce_lut_*`).
+pub struct HipIccProfile<'a> {
+    owner: &'a HipMetrics,
+    handle: *mut sys::ce_icc,
+}
+
+impl<'a> HipIccProfile<'a> {
+    pub fn new(owner: &'a HipMetrics, profile: &[u8]) -> Result<Self, HipError> {
+        let mut handle = ptr::null_mut();
+        let rc = unsafe { sys::ce_icc_create(owner.ctx, profile.as_ptr(), profile.len(), &mut handle) };
+        owner.check(rc, 0, 0, 0)?;
+        Ok(Self { owner, handle })
+    }
+
+    /// `ce_icc_to_linear`: one image (`format` and `pixels` as `hlg_to_linear`, samples of `depth` bits) -> packed f32 RGB,
+    /// linear light with sRGB primaries.
+    pub fn to_linear(&self, pixels: &[u8], format: i32, depth: u32, width: u32, height: u32) -> Result<Vec<f32>, HipError> {
+        let mut out = vec![0f32; width as usize * height as usize * 3];
+        let rc = unsafe {
+            sys::ce_icc_to_linear(self.owner.ctx, pixels.as_ptr().cast(), pixels.len(), format, depth, self.handle, width, height,
+                                  out.as_mut_ptr(), out.len())
+        };
+        self.owner.check(rc, width, height, pixels.len())?;
+        Ok(out)
+    }
+
+    /// `ce_icc_to_srgb8`: the same image as packed sRGB8, what `transform_to_srgb` (src/metrics/icc.rs:69-103) returns.
+    pub fn to_srgb8(&self, pixels: &[u8], format: i32, depth: u32, width: u32, height: u32) -> Result<Vec<u8>, HipError> {
+        let mut out = vec![0u8; width as usize * height as usize * 3];
+        let rc = unsafe {
+            sys::ce_icc_to_srgb8(self.owner.ctx, pixels.as_ptr().cast(), pixels.len(), format, depth, self.handle, width, height,
+                                 out.as_mut_ptr(), out.len())
+        };
+        self.owner.check(rc, width, height, pixels.len())?;
+        Ok(out)
+    }
+
+    /// `ce_icc_to_srgb16`: the same image as packed u16 sRGB code values of `depth_out` bits (8, 10, 12 or 16).
+    pub fn to_srgb16(&self, pixels: &[u8], format: i32, depth: u32, width: u32, height: u32, depth_out: u32) -> Result<Vec<u16>, HipError> {
+        let mut out = vec![0u16; width as usize * height as usize * 3];
+        let rc = unsafe {
+            sys::ce_icc_to_srgb16(self.owner.ctx, pixels.as_ptr().cast(), pixels.len(), format, depth, self.handle, width, height, depth_out,
+                                  out.as_mut_ptr(), out.len())
+        };
+        self.owner.check(rc, width, height, pixels.len())?;
+        Ok(out)
+    }
+}
+
+impl Drop for HipIccProfile<'_> {
+    fn drop(&mut self) {
+        unsafe { sys::ce_icc_destroy(self.handle) };
+    }
+}
+
 /// `ce_batch`: images of one shape resident on the device, scored in one launch.  Resampling one grid into another
 /// (`resample_pairs_into`) scores a sweep at the size a `ViewingCondition` displays it (src/viewing.rs:244-301) without
 /// another upload.
@@ -761,6 +825,25 @@ impl HipBatch<'_> {
         let rc = unsafe {
             sys::ce_batch_set_test_over(self.handle, first_pair, ref_indices.as_ptr(), pixels.as_ptr().cast(), pixels.len(), format,
                                         backgrounds.len() as u32, backgrounds.as_ptr().cast())
+        };
+        self.check(rc, pixels.len())
+    }
+
+    /// `ce_batch_set_reference_icc`: code values of `depth` bits (`format` and `pixels` as `hlg_to_linear`) read through a
+    /// matrix/TRC profile into a reference slot of any batch: linear light in a linear batch, sRGB code values of the slot's
+    /// depth otherwise.
+    pub fn set_reference_icc(&mut self, ref_index: u32, pixels: &[u8], format: i32, depth: u32, icc: &HipIccProfile<'_>) -> Result<(), HipError> {
+        let rc = unsafe {
+            sys::ce_batch_set_reference_icc(self.handle, ref_index, pixels.as_ptr().cast(), pixels.len(), format, depth, icc.handle)
+        };
+        self.check(rc, pixels.len())
+    }
+
+    /// `ce_batch_set_test_icc`: the same for the test image of pair `pair_index`, bound to reference `ref_index`.
+    pub fn set_test_icc(&mut self, pair_index: u32, ref_index: u32, pixels: &[u8], format: i32, depth: u32, icc: &HipIccProfile<'_>)
+                        -> Result<(), HipError> {
+        let rc = unsafe {
+            sys::ce_batch_set_test_icc(self.handle, pair_index, ref_index, pixels.as_ptr().cast(), pixels.len(), format, depth, icc.handle)
         };
         self.check(rc, pixels.len())
     }

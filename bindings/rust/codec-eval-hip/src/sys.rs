@@ -52,6 +52,42 @@ pub const CE_PIXEL_RGB_F32: c_int = 7;
 /// `CE_LINEAR_MAX`: the clamp of a linear image's samples on ingest
 pub const CE_LINEAR_MAX: c_float = 1024.0;
 
+/// a matrix/TRC ICC profile on a context's device (`ce_icc_create`)
+#[repr(C)]
+pub struct ce_icc {
+    _private: [u8; 0],
+}
+pub const CE_ICC_MAX_PROFILE_BYTES: usize = 4194304;
+pub const CE_ICC_MAX_CURVE_POINTS: u32 = 65536;
+pub const CE_ICC_SUPPORTED: c_int = 0;
+pub const CE_ICC_LUT_BASED: c_int = 1;
+pub const CE_ICC_NOT_RGB_XYZ: c_int = 2;
+pub const CE_ICC_MALFORMED: c_int = 3;
+pub const CE_ICC_CURVE_CURV: c_int = 0;
+pub const CE_ICC_CURVE_PARA: c_int = 1;
+
+/// `ce_icc_curve` (40 bytes): one tone curve of a matrix/TRC profile as the parser read it.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ce_icc_curve {
+    pub type_: c_int,
+    pub count: u32,
+    pub params: [i32; 7],
+    pub offset: u32,
+}
+
+/// `ce_icc_description` (264 bytes): what `ce_icc_describe` reads from a profile.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ce_icc_description {
+    pub kind: c_int,
+    pub version: u32,
+    pub profile_class: u32,
+    pub colorants: [i32; 9],
+    pub curves: [ce_icc_curve; 3],
+    pub reason: [c_char; 96],
+}
+
 /// `ce_colour` (16 bytes): how integer RGB code values are to be read (ITU-T H.273 code points).
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -384,6 +420,22 @@ extern "C" {
                               out_len: usize) -> c_int;
     pub fn ce_composite_rgba16(ctx: *mut ce_ctx, rgba: *const u16, len: usize, w: u32, h: u32, depth: u32, bg: *const u16,
                                out: *mut u16, out_len: usize) -> c_int;
+    pub fn ce_icc_describe(bytes: *const u8, len: usize, out: *mut ce_icc_description) -> c_int;
+    pub fn ce_icc_build_matrix(bytes: *const u8, len: usize, out: *mut c_float) -> c_int;
+    pub fn ce_icc_build_tables(bytes: *const u8, len: usize, depth: u32, out: *mut c_float, n: usize) -> c_int;
+    pub fn ce_srgb_encode_thresholds(depth: u32, out: *mut c_float, n: usize) -> c_int;
+    pub fn ce_icc_create(ctx: *mut ce_ctx, bytes: *const u8, len: usize, out: *mut *mut ce_icc) -> c_int;
+    pub fn ce_icc_destroy(icc: *mut ce_icc);
+    pub fn ce_batch_set_reference_icc(b: *mut ce_batch, ref_index: u32, pixels: *const c_void, len: usize, format: c_int, depth: u32,
+                                      icc: *const ce_icc) -> c_int;
+    pub fn ce_batch_set_test_icc(b: *mut ce_batch, pair_index: u32, ref_index: u32, pixels: *const c_void, len: usize, format: c_int,
+                                 depth: u32, icc: *const ce_icc) -> c_int;
+    pub fn ce_icc_to_linear(ctx: *mut ce_ctx, pixels: *const c_void, len: usize, format: c_int, depth: u32, icc: *const ce_icc, w: u32,
+                            h: u32, out: *mut c_float, out_len: usize) -> c_int;
+    pub fn ce_icc_to_srgb8(ctx: *mut ce_ctx, pixels: *const c_void, len: usize, format: c_int, depth: u32, icc: *const ce_icc, w: u32,
+                           h: u32, out: *mut u8, out_len: usize) -> c_int;
+    pub fn ce_icc_to_srgb16(ctx: *mut ce_ctx, pixels: *const c_void, len: usize, format: c_int, depth: u32, icc: *const ce_icc, w: u32,
+                            h: u32, depth_out: u32, out: *mut u16, out_len: usize) -> c_int;
     pub fn ce_prof_enable(ctx: *mut ce_ctx, on: c_int) -> c_int;
     pub fn ce_prof_filter(ctx: *mut ce_ctx, substring: *const c_char) -> c_int;
     pub fn ce_prof_reset(ctx: *mut ce_ctx) -> c_int;

@@ -144,6 +144,15 @@ class CeGainmap(C.Structure):
                 ("display_headroom", C.c_float)]
 
 
+class CeIccCurve(C.Structure):
+    _fields_ = [("type", C.c_int), ("count", C.c_uint32), ("params", C.c_int32 * 7), ("offset", C.c_uint32)]
+
+
+class CeIccDescription(C.Structure):
+    _fields_ = [("kind", C.c_int), ("version", C.c_uint32), ("profile_class", C.c_uint32), ("colorants", C.c_int32 * 9),
+                ("curves", CeIccCurve * 3), ("reason", C.c_char * 96)]
+
+
 class CeHdrScores(C.Structure):
     _fields_ = [("pq_psnr", C.c_double), ("delta_e_itp_mean", C.c_double), ("delta_e_itp_max", C.c_double),
                 ("pq_sse", C.c_uint64), ("itp_sum_q20", C.c_uint64), ("itp_max_q20", C.c_uint64)]
@@ -290,6 +299,17 @@ _PROTOTYPES = [
     ("ce_hdr_fidelity_matrices", _i, [_vp, _vp]),
     ("ce_batch_delta_e_itp_map", _i, [_vp, _u32, _u32, _u32, _f32, _u32, _vp, _sz, _vp, _u32, _vp]),
     ("ce_eval_pair_delta_e_itp_map", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _f32, _u32, _vp, _sz, _vp, _u32, _vp]),
+    ("ce_icc_describe", _i, [_vp, _sz, C.POINTER(CeIccDescription)]),
+    ("ce_icc_build_matrix", _i, [_vp, _sz, _vp]),
+    ("ce_icc_build_tables", _i, [_vp, _sz, _u32, _vp, _sz]),
+    ("ce_srgb_encode_thresholds", _i, [_u32, _vp, _sz]),
+    ("ce_icc_create", _i, [_vp, _vp, _sz, C.POINTER(_vp)]),
+    ("ce_icc_destroy", None, [_vp]),
+    ("ce_batch_set_reference_icc", _i, [_vp, _u32, _vp, _sz, _i, _u32, _vp]),
+    ("ce_batch_set_test_icc", _i, [_vp, _u32, _u32, _vp, _sz, _i, _u32, _vp]),
+    ("ce_icc_to_linear", _i, [_vp, _vp, _sz, _i, _u32, _vp, _u32, _u32, _vp, _sz]),
+    ("ce_icc_to_srgb8", _i, [_vp, _vp, _sz, _i, _u32, _vp, _u32, _u32, _vp, _sz]),
+    ("ce_icc_to_srgb16", _i, [_vp, _vp, _sz, _i, _u32, _vp, _u32, _u32, _u32, _vp, _sz]),
     ("ce_batch_set_reference_over", _i, [_vp, _u32, _vp, _sz, _i, _u32, _vp]),
     ("ce_batch_set_test_over", _i, [_vp, _u32, _vp, _vp, _sz, _i, _u32, _vp]),
     ("ce_composite_rgba8", _i, [_vp, _vp, _sz, _u32, _u32, _vp, _vp, _sz]),
@@ -370,6 +390,67 @@ def colour_matrix(primaries: int) -> np.ndarray:
     """The CICP ingest's 3 x 3 matrix from `primaries` to BT.709 / sRGB primaries (ce_colour_matrix), float32."""
     out = np.empty((3, 3), np.float32)
     _host_check(lib().ce_colour_matrix(primaries, out.ctypes.data))
+    return out
+
+
+ICC_SUPPORTED, ICC_LUT_BASED, ICC_NOT_RGB_XYZ, ICC_MALFORMED = 0, 1, 2, 3
+
+
+@dataclass(frozen=True)
+class IccCurve:
+    """One tone curve of a matrix/TRC profile (ce_icc_curve): type 0 `curv` (count samples; 0 the identity, 1 a gamma whose
+    u8Fixed8 number is params[0]) or 1 `para` (count = the function type 0 .. 4, params = g a b c d e f as s15Fixed16)."""
+    type: int
+    count: int
+    params: Tuple[int, ...]
+    offset: int
+
+
+@dataclass(frozen=True)
+class IccDescription:
+    """What the library's parser reads from an ICC profile (ce_icc_describe): kind 0 supported, 1 LUT-based, 2 not RGB / XYZ,
+    3 malformed, with the reason; the version, the class, the nine colorant integers (rows X Y Z, columns r g b) and the
+    three curves as far as parsing got."""
+    kind: int
+    version: int
+    profile_class: int
+    colorants: Tuple[int, ...]
+    curves: Tuple[IccCurve, ...]
+    reason: str
+
+
+def icc_describe(profile: bytes) -> IccDescription:
+    """ce_icc_describe: a pure host function, usable with no GPU."""
+    b = bytes(profile)
+    d = CeIccDescription()
+    _host_check(lib().ce_icc_describe(b, len(b), C.byref(d)))
+    return IccDescription(d.kind, d.version, d.profile_class, tuple(d.colorants),
+                          tuple(IccCurve(c.type, c.count, tuple(c.params), c.offset) for c in d.curves), d.reason.decode(errors="replace"))
+
+
+def icc_matrix(profile: bytes) -> np.ndarray:
+    """The 3 x 3 float32 matrix from a matrix/TRC profile's colorants to sRGB primaries (ce_icc_build_matrix)."""
+    b = bytes(profile)
+    out = np.empty((3, 3), np.float32)
+    if lib().ce_icc_build_matrix(b, len(b), out.ctypes.data) != CE_OK:
+        raise CodecEvalError(CE_ERR_INVALID_ARG, "ICC profile: " + (icc_describe(b).reason or "bad argument"))
+    return out
+
+
+def icc_tables(profile: bytes, depth: int) -> np.ndarray:
+    """The three tone tables of a matrix/TRC profile at `depth` bits, [3, 2^depth] float32 (ce_icc_build_tables)."""
+    b = bytes(profile)
+    out = np.empty((3, 1 << depth if 0 < depth <= 16 else 1), np.float32)
+    if lib().ce_icc_build_tables(b, len(b), depth, out.ctypes.data, out.size) != CE_OK:
+        raise CodecEvalError(CE_ERR_INVALID_ARG, "ICC profile: " + (icc_describe(b).reason or f"depth {depth} or the table size"))
+    return out
+
+
+def srgb_encode_thresholds(depth: int) -> np.ndarray:
+    """T[1 .. 2^depth - 1] of the sRGB encode of integer slots (ce_srgb_encode_thresholds), float32."""
+    out = np.empty((1 << depth) - 1 if 0 < depth <= 16 else 1, np.float32)
+    if lib().ce_srgb_encode_thresholds(depth, out.ctypes.data, out.size) != CE_OK:
+        raise CodecEvalError(CE_ERR_INVALID_ARG, f"ce_srgb_encode_thresholds: depth 8, 10, 12 or 16, got {depth}")
     return out
 
 
@@ -1221,6 +1302,29 @@ class Context:
                                             out.size))
         return out
 
+    def icc_to_linear(self, pixels, width: int, height: int, depth: int, profile: "IccProfile") -> np.ndarray:
+        """One image of uint8 / uint16 RGB(A) code values of `depth` bits read through a matrix/TRC profile -> [h, w, 3]
+        float32 linear light with sRGB primaries, on the device (ce_icc_to_linear)."""
+        a = np.ascontiguousarray(pixels)
+        out = np.empty((height, width, 3), np.float32)
+        self._check(lib().ce_icc_to_linear(self._h, a.ctypes.data, a.nbytes, _cicp_fmt(a), depth, profile._h, width, height, out.ctypes.data,
+                                           out.size))
+        return out
+
+    def icc_to_srgb(self, pixels, width: int, height: int, depth: int, profile: "IccProfile", depth_out: int = 8) -> np.ndarray:
+        """The same image as sRGB code values: [h, w, 3] uint8 (depth_out = 8, ce_icc_to_srgb8) or uint16 of depth_out bits
+        (10, 12 or 16, ce_icc_to_srgb16)."""
+        a = np.ascontiguousarray(pixels)
+        if depth_out == 8:
+            out = np.empty((height, width, 3), np.uint8)
+            self._check(lib().ce_icc_to_srgb8(self._h, a.ctypes.data, a.nbytes, _cicp_fmt(a), depth, profile._h, width, height, out.ctypes.data,
+                                              out.size))
+        else:
+            out = np.empty((height, width, 3), np.uint16)
+            self._check(lib().ce_icc_to_srgb16(self._h, a.ctypes.data, a.nbytes, _cicp_fmt(a), depth, profile._h, width, height, depth_out,
+                                               out.ctypes.data, out.size))
+        return out
+
     def hlg_to_linear(self, pixels, width: int, height: int, description: "HlgDescription") -> np.ndarray:
         """One image of uint8 / uint16 RGB(A) HLG code values read by `description` -> [h, w, 3] float32 display light with
         sRGB primaries, 1.0 = white_nits, on the device (ce_hlg_to_linear)."""
@@ -1345,6 +1449,30 @@ class ColorTable:
             pass
 
 
+class IccProfile:
+    """A matrix/TRC ICC profile applied on the device (ce_icc_*): three colorants and three tone curves, parsed by the
+    library itself - no CMS.  Any other profile (LUT-based, Gray, CMYK, malformed) raises CodecEvalError with the reason;
+    `icc_describe(profile).kind` tells which without raising.  Close it after the last batch that was given it has been
+    collected."""
+
+    def __init__(self, ctx: "Context", profile: bytes):
+        b = bytes(profile)
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        ctx._check(lib().ce_icc_create(ctx._h, b, len(b), C.byref(self._h)))
+
+    def close(self):
+        if self._h and self.ctx._h:
+            lib().ce_icc_destroy(self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Batch:
     """HBM-resident grid of (reference, test) pairs of one shape (ce_batch_*)."""
 
@@ -1429,6 +1557,19 @@ class Batch:
     def set_test_yuv(self, pair_index: int, ref_index: int, image: "YuvImage"):
         c, _keep = image._c()
         self.ctx._check(lib().ce_batch_set_test_yuv(self._h, pair_index, ref_index, C.byref(c)))
+        self._pair_ref[pair_index] = ref_index
+
+    # code values with a matrix/TRC ICC profile, applied by the library itself, into a slot of any batch
+    def set_reference_icc(self, ref_index: int, pixels, depth: int, profile: "IccProfile"):
+        """uint8 / uint16 RGB(A) code values of `depth` bits read through a matrix/TRC profile, into a reference slot of any
+        batch: linear light in a linear batch, sRGB code values of the slot's depth otherwise (ce_batch_set_reference_icc)."""
+        a = np.ascontiguousarray(pixels)
+        self.ctx._check(lib().ce_batch_set_reference_icc(self._h, ref_index, a.ctypes.data, a.nbytes, _cicp_fmt(a), depth, profile._h))
+
+    def set_test_icc(self, pair_index: int, ref_index: int, pixels, depth: int, profile: "IccProfile"):
+        """The same for the test image of pair `pair_index`, bound to reference `ref_index` (ce_batch_set_test_icc)."""
+        a = np.ascontiguousarray(pixels)
+        self.ctx._check(lib().ce_batch_set_test_icc(self._h, pair_index, ref_index, a.ctypes.data, a.nbytes, _cicp_fmt(a), depth, profile._h))
         self._pair_ref[pair_index] = ref_index
 
     # the same planes with a colour description -> linear light in one kernel, into a slot of a linear batch

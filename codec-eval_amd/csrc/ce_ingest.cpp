@@ -599,6 +599,88 @@ int gainmap_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, c
     return CE_OK;
 }
 
+// ---- matrix/TRC ICC profiles into any batch (icc.hip) ---------------------------------------------------
+
+// the device copy of the sRGB code thresholds of an integer slot of `depth` bits (ce_ctx::icc_thresholds)
+int icc_thresholds_dev(ce_ctx *ctx, uint32_t depth, const float **out)
+{
+    auto it = ctx->icc_thresholds.find(depth);
+    if (it == ctx->icc_thresholds.end()) {
+        std::vector<float> host((size_t)1 << depth, 0.0f);  // entry 0 is not read
+        ce_srgb_encode_thresholds(depth, host.data() + 1, host.size() - 1);
+        CE_HIP(ctx, hipSetDevice(ctx->device));
+        void *d = nullptr;
+        if (int rc = ce_device_table(ctx, host.data(), host.size() * sizeof(float), "sRGB code thresholds", &d)) return rc;
+        it = ctx->icc_thresholds.emplace(depth, static_cast<float *>(d)).first;
+    }
+    *out = it->second;
+    return CE_OK;
+}
+
+// One image of code values with its profile for a slot of depth_out bits (0: linear light; out16: u16 samples; wide_ok: the
+// slot takes 16-bit sources): everything refused about either, then the plan
+int icc_check(ce_ctx *ctx, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc, size_t n_px, uint32_t depth_out, bool out16,
+              bool wide_ok, ce_icc_pixel *plan)
+{
+    if (!pixels || !icc) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: null pointer");
+    if (icc->ctx->device != ctx->device) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: the profile and the destination are on different devices");
+    const bool fmt8 = format == CE_PIXEL_RGB8 || format == CE_PIXEL_RGBA8, fmt16 = format == CE_PIXEL_RGB16 || format == CE_PIXEL_RGBA16;
+    if (!fmt8 && !fmt16) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: format must be CE_PIXEL_RGB8, RGBA8, RGB16 or RGBA16");
+    if (!ce_deep_depth_ok(depth)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: depth must be 8, 10, 12 or 16, got " + std::to_string(depth));
+    if (fmt8 && depth != 8) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: an 8-bit format needs depth 8, got " + std::to_string(depth));
+    if (fmt16 && !wide_ok)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: an RGB8 batch takes CE_PIXEL_RGB8 / RGBA8; 16-bit samples need a deep or a linear batch");
+    if (len != n_px * ce_pixel_bytes(format)) return ce_bad_length(ctx, n_px * ce_pixel_bytes(format), len);
+    plan->maxv = (1u << depth) - 1u;
+    plan->has_matrix = icc->has_matrix;
+    for (int i = 0; i < 9; i++) plan->m[i] = icc->m[i];
+    plan->depth_out = depth_out, plan->out16 = out16;
+    if (depth_out)
+        if (int rc = icc_thresholds_dev(ctx, depth_out, &plan->d_thr)) return rc;
+    plan->d_tables = icc->d_tables[ce_icc_depth_index(depth)];
+    return CE_OK;
+}
+
+// ce_batch_set_*_icc: the frame of upload_cicp around the ICC launch
+int set_icc(ce_batch *b, bool test, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    ce_icc_pixel plan;
+    const uint32_t side = b->depth[test];
+    return set_slot(
+        b, test, pair_index, ref_index, kind_rule{},
+        [&] { return icc_check(b->ctx, pixels, len, format, depth, icc, (size_t)b->w * b->h, b->linear ? 0 : side ? side : 8, side != 0, b->linear || side, &plan); },
+        [&](uint8_t *slot) -> int {
+            ce_ctx *ctx = b->ctx;
+            CE_HIP(ctx, hipSetDevice(ctx->device));
+            int k;
+            if (int rc = wide_acquire(b, &k)) return rc;
+            std::memcpy(b->h_wide[k], pixels, len);
+            CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], len, hipMemcpyHostToDevice, b->up_stream));
+            if (int rc = ce_launch_icc(ctx, b->up_stream, format, b->d_wide[k], slot, (size_t)b->w * b->h, plan)) return rc;
+            return wide_close(b, k);
+        });
+}
+
+// ce_icc_to_linear (depth_out = 0), ce_icc_to_srgb8 and ce_icc_to_srgb16: one image -> host memory through the leaf scratch
+int icc_to_host(ce_ctx *ctx, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc, uint32_t w, uint32_t h, uint32_t depth_out,
+                bool out16, void *out, size_t out_len)
+{
+    if (!ctx) return CE_ERR_INVALID_ARG;
+    if (!out) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: null output");
+    if (w == 0 || h == 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: empty image");
+    if (out16 && !ce_deep_depth_ok(depth_out))
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: the output depth must be 8, 10, 12 or 16 bits, got " + std::to_string(depth_out));
+    const size_t n_px = (size_t)w * h;
+    ce_icc_pixel plan;
+    if (int rc = icc_check(ctx, pixels, len, format, depth, icc, n_px, depth_out, out16, true, &plan)) return rc;
+    if (out_len != n_px * 3)
+        return ce_fail(ctx, CE_ERR_BAD_LENGTH, "ICC ingest: out_len must be " + std::to_string(n_px * 3) + " samples, got " + std::to_string(out_len));
+    const size_t sample = depth_out == 0 ? sizeof(float) : out16 ? 2 : 1;
+    return ce_leaf_roundtrip(ctx, pixels, len, out, n_px * 3 * sample,
+                             [&](uint8_t *d_in, uint8_t *d_out) { return ce_launch_icc(ctx, ctx->stream, format, d_in, d_out, n_px, plan); });
+}
+
 // ---- planar Y'CbCr (yuv.hip), and with a description into a linear batch (yuv_cicp.hip) -------------------
 
 // a checked ce_yuv_image: what the kernel reads, and each plane's rows for the host copy
@@ -1062,6 +1144,74 @@ int ce_gainmap_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format
                          uint32_t w, uint32_t h, float *out, size_t out_len)
 {
     return gainmap_to_linear(ctx, pixels, len, format, c, map, g, w, h, out, out_len);
+}
+
+// matrix/TRC ICC profiles; the pure host functions are in ce_icc.cpp
+int ce_icc_create(ce_ctx *ctx, const uint8_t *bytes, size_t len, ce_icc **out)
+{
+    if (!ctx || !out) return CE_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (!bytes) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC profile: null pointer");
+    ce_icc_description d;
+    ce_icc_describe(bytes, len, &d);
+    if (d.kind != CE_ICC_SUPPORTED) {
+        static const char *const kKinds[4] = {"", "a LUT-based profile", "not an RGB profile with an XYZ connection space", "a malformed profile"};
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, std::string("ICC profile: ") + kKinds[d.kind & 3] + " (" + d.reason + ")");
+    }
+    ce_icc *icc = new ce_icc{ctx, {}, false, {}};
+    ce_icc_build_matrix(bytes, len, icc->m);
+    for (int i = 0; i < 9; i++) icc->has_matrix |= icc->m[i] != ((i % 4 == 0) ? 1.0f : 0.0f);
+    // the tone tables of all four source depths now (0.85 MB of device memory in all): the handle is read-only from here on
+    int rc = hipSetDevice(ctx->device) == hipSuccess ? CE_OK : ce_fail(ctx, CE_ERR_BACKEND, "hipSetDevice failed (ICC profile)");
+    for (uint32_t depth : {8u, 10u, 12u, 16u}) {
+        if (rc != CE_OK) break;
+        std::vector<float> host((size_t)3 << depth);
+        ce_icc_build_tables(bytes, len, depth, host.data(), host.size());
+        void *d = nullptr;
+        rc = ce_device_table(ctx, host.data(), host.size() * sizeof(float), "ICC tone tables", &d);
+        icc->d_tables[ce_icc_depth_index(depth)] = static_cast<float *>(d);
+    }
+    if (rc != CE_OK) {
+        for (float *t : icc->d_tables) hipFree(t);
+        delete icc;
+        return rc;
+    }
+    *out = icc;
+    return CE_OK;
+}
+
+void ce_icc_destroy(ce_icc *icc)
+{
+    if (!icc) return;
+    hipSetDevice(icc->ctx->device);
+    hipDeviceSynchronize();  // the batches' upload streams may still gather from the tables
+    for (float *t : icc->d_tables) hipFree(t);
+    delete icc;
+}
+
+int ce_batch_set_reference_icc(ce_batch *b, uint32_t ref_index, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc)
+{
+    return set_icc(b, false, 0, ref_index, pixels, len, format, depth, icc);
+}
+int ce_batch_set_test_icc(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format, uint32_t depth,
+                          const ce_icc *icc)
+{
+    return set_icc(b, true, pair_index, ref_index, pixels, len, format, depth, icc);
+}
+int ce_icc_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc, uint32_t w, uint32_t h, float *out,
+                     size_t out_len)
+{
+    return icc_to_host(ctx, pixels, len, format, depth, icc, w, h, 0, false, out, out_len);
+}
+int ce_icc_to_srgb8(ce_ctx *ctx, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc, uint32_t w, uint32_t h, uint8_t *out,
+                    size_t out_len)
+{
+    return icc_to_host(ctx, pixels, len, format, depth, icc, w, h, 8, false, out, out_len);
+}
+int ce_icc_to_srgb16(ce_ctx *ctx, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc, uint32_t w, uint32_t h,
+                     uint32_t depth_out, uint16_t *out, size_t out_len)
+{
+    return icc_to_host(ctx, pixels, len, format, depth, icc, w, h, depth_out, true, out, out_len);
 }
 
 // planar Y'CbCr, alone and with either description (DESIGN.md sections 13, 16, 18)

@@ -95,6 +95,10 @@ struct ce_ctx {
     // call that needs one and kept until the context goes (ce_api.cpp: hdr_table_dev): T[1 .. maxv], padded to a multiple of
     // 16 floats, then at depth 16 the coarse level a block stages in LDS (every 16th threshold)
     std::map<std::pair<uint32_t, uint32_t>, float *> hdr_tables;
+    // sRGB code thresholds of the ICC ingest into integer slots (icc.hip), keyed by the slot's depth D: 2^D floats with
+    // entry k = T[k] for k >= 1 (entry 0 is not read); built by the first such ingest and kept until the context goes
+    // (ce_ingest.cpp: icc_thresholds_dev)
+    std::map<uint32_t, float *> icc_thresholds;
 
     // profiling
     bool prof = false;         // record a HIP event pair around every launch (on the launch's own stream)
@@ -318,6 +322,16 @@ struct ce_lut {
     ce_ctx *ctx;
     uint32_t *d_table;  // [2^24] r | g << 8 | b << 16
 };
+// a matrix/TRC ICC profile on the device (ce_icc_create; ce_ingest.cpp): its matrix and the device copies of
+// ce_icc_build_tables for the four source depths 8, 10, 12 and 16, all made by ce_icc_create - nothing in the handle changes
+// after that - and kept until the handle goes
+struct ce_icc {
+    ce_ctx *ctx;
+    float m[9];
+    bool has_matrix;
+    float *d_tables[4];  // [3][2^depth] floats each, by ce_icc_depth_index
+};
+inline int ce_icc_depth_index(uint32_t depth) { return depth == 8 ? 0 : depth == 10 ? 1 : depth == 12 ? 2 : 3; }
 // one image of ce_upload_many
 struct ce_upload_job {
     uint8_t *dst;
@@ -538,6 +552,23 @@ struct ce_gainmap_plan {
 // behind them the map's samples, as ce_ingest.cpp's gainmap_side packs them.
 int ce_launch_gainmap(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, const uint8_t *d_side, float *d_dst, uint32_t w, uint32_t h,
                       const ce_gainmap_plan &plan);
+
+// What one ICC ingest converts a pixel with (checked and filled by ce_ingest.cpp: icc_check): the profile's three device
+// tables of the source depth, [3][maxv + 1] floats, its matrix (has_matrix: colorants other than the canonical sRGB profile's)
+// and, for an integer slot of depth_out bits (0: a linear slot; out16: u16 samples), the sRGB code thresholds of that depth
+// with d_thr[k] = T[k] for k = 1 .. 2^depth_out - 1
+struct ce_icc_pixel {
+    const float *d_tables = nullptr;
+    uint32_t maxv = 0;
+    bool has_matrix = false;
+    float m[9] = {};
+    uint32_t depth_out = 0;
+    bool out16 = false;
+    const float *d_thr = nullptr;
+};
+// n_pixels RGB(A) pixels of u8 / u16 samples at d_src (16-byte aligned staging; the four formats of ce_launch_tagged) ->
+// packed f32 RGB, or packed u8 / u16 sRGB code values, at d_dst, one launch (icc.hip)
+int ce_launch_icc(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, void *d_dst, size_t n_pixels, const ce_icc_pixel &px);
 
 // pairs [0, n_pairs) of a linear batch -> d_out[pair][3] = pq_sse, itp_sum_q20, itp_max_q20, cleared and filled on the
 // launching stream (hdr_fidelity.hip): d_table = T[1 .. maxv], 64-byte aligned, d_coarse the level staged in LDS (the table

@@ -463,6 +463,66 @@ inline void batch_set_test_cicp(const HipBackend &be, ce_batch *batch, uint32_t 
 {
     detail::check(be, ce_batch_set_test_cicp(batch, pair_index, ref_index, pixels, len, format, &colour), "cicp", 0, 0, 0);
 }
+// ---- matrix/TRC ICC profiles applied on the device (include/ce_metrics.h: ce_icc_*) -------------------
+// what the library's parser reads from a profile, without a device: kind CE_ICC_SUPPORTED for the profiles HipIccProfile takes
+inline ce_icc_description icc_describe(const std::vector<uint8_t> &icc_profile)
+{
+    ce_icc_description d{};
+    ce_icc_describe(icc_profile.data() ? icc_profile.data() : reinterpret_cast<const uint8_t *>(""), icc_profile.size(), &d);
+    return d;
+}
+// A profile of three colorants and three tone curves on the device, parsed by the library itself (no Cms).  A LUT-based, Gray,
+// CMYK or malformed profile throws with the reason; those keep HipColorTable's route.
+class HipIccProfile {
+public:
+    HipIccProfile(const HipBackend &be, const std::vector<uint8_t> &icc_profile)
+    {
+        if (ce_icc_create(be.ctx(), icc_profile.data(), icc_profile.size(), &icc_) != CE_OK)
+            throw Error(Error::Kind::MetricCalculation, "Metric calculation failed: ICC: Failed to create ICC transform: " + be.last_error());
+    }
+    ~HipIccProfile() { ce_icc_destroy(icc_); }
+    HipIccProfile(const HipIccProfile &) = delete;
+    HipIccProfile &operator=(const HipIccProfile &) = delete;
+    const ce_icc *get() const { return icc_; }
+
+private:
+    ce_icc *icc_ = nullptr;
+};
+// One image of integer RGB(A) code values of `depth` bits (format: CE_PIXEL_RGB8 / RGBA8 / RGB16 / RGBA16; len in bytes) read
+// through the profile -> packed float RGB, linear light with sRGB primaries; -> packed sRGB8; -> packed u16 sRGB of depth_out
+inline std::vector<float> icc_to_linear(const HipBackend &be, const void *pixels, size_t len, int format, uint32_t depth, const HipIccProfile &icc,
+                                        uint32_t width, uint32_t height)
+{
+    std::vector<float> out((size_t)width * height * 3);
+    detail::check(be, ce_icc_to_linear(be.ctx(), pixels, len, format, depth, icc.get(), width, height, out.data(), out.size()), "icc", width, height, len);
+    return out;
+}
+inline std::vector<uint8_t> icc_to_srgb8(const HipBackend &be, const void *pixels, size_t len, int format, uint32_t depth, const HipIccProfile &icc,
+                                         uint32_t width, uint32_t height)
+{
+    std::vector<uint8_t> out((size_t)width * height * 3);
+    detail::check(be, ce_icc_to_srgb8(be.ctx(), pixels, len, format, depth, icc.get(), width, height, out.data(), out.size()), "icc", width, height, len);
+    return out;
+}
+inline std::vector<uint16_t> icc_to_srgb16(const HipBackend &be, const void *pixels, size_t len, int format, uint32_t depth, const HipIccProfile &icc,
+                                           uint32_t width, uint32_t height, uint32_t depth_out)
+{
+    std::vector<uint16_t> out((size_t)width * height * 3);
+    detail::check(be, ce_icc_to_srgb16(be.ctx(), pixels, len, format, depth, icc.get(), width, height, depth_out, out.data(), out.size()), "icc", width,
+                  height, len);
+    return out;
+}
+// straight into a slot of any batch: linear light in a linear batch, sRGB code values of the slot's depth otherwise
+inline void batch_set_reference_icc(const HipBackend &be, ce_batch *batch, uint32_t ref_index, const void *pixels, size_t len, int format,
+                                    uint32_t depth, const HipIccProfile &icc)
+{
+    detail::check(be, ce_batch_set_reference_icc(batch, ref_index, pixels, len, format, depth, icc.get()), "icc", 0, 0, 0);
+}
+inline void batch_set_test_icc(const HipBackend &be, ce_batch *batch, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len,
+                               int format, uint32_t depth, const HipIccProfile &icc)
+{
+    detail::check(be, ce_batch_set_test_icc(batch, pair_index, ref_index, pixels, len, format, depth, icc.get()), "icc", 0, 0, 0);
+}
 // ---- Y'CbCr planes with a colour description -> linear light in one kernel ---------------------------
 // yuv_to_rgb16 at depth_out = colour.depth followed by cicp_to_linear, bit for bit; colour.depth >= image.depth
 inline std::vector<float> yuv_to_linear(const HipBackend &be, const YuvImage &image, const ColourDescription &colour, uint32_t width, uint32_t height)

@@ -16,7 +16,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from . import (ColourDescription, GainMap, HlgDescription, DEEP_DEPTHS, PIXEL_RGB_F32, PIXEL_RGB8, PIXEL_RGB16, PIXEL_RGBA8, PIXEL_RGBA16, Batch, CodecEvalError, ColorTable, Context, DimensionMismatch, MetricCalculation,
+from . import (ColourDescription, GainMap, HlgDescription, DEEP_DEPTHS, PIXEL_RGB_F32, PIXEL_RGB8, PIXEL_RGB16, PIXEL_RGBA8, PIXEL_RGBA16, Batch, CodecEvalError, ColorTable, Context, IccProfile, icc_describe, DimensionMismatch, MetricCalculation,
                MetricConfig, MetricResult, _error_obj, estimate_batch_bytes, CE_ERR_BACKEND)
 from . import RESAMPLE_LANCZOS3
 from . import CHROMA_TRIANGLE, MEM_HOST, YUV_400, YUV_420, YUV_444, YUV_BT601, YUV_FULL, YUV_PLANAR, YUV_SEMIPLANAR, YuvImage, yuv_coefficients
@@ -91,12 +91,15 @@ class ImageData:
         return ImageData(np.ascontiguousarray(data, dtype=np.uint8).reshape(-1), int(width), int(height), 3, bytes(icc_profile))
 
     @staticmethod
-    def rgb16(data, width: int, height: int, depth: int, colour: Optional[Colour] = None, gain_map: Optional[GainMap] = None) -> "ImageData":
+    def rgb16(data, width: int, height: int, depth: int, colour: Optional[Colour] = None, gain_map: Optional[GainMap] = None,
+              icc_profile: Optional[bytes] = None) -> "ImageData":
         """A decoder's PixelData::Rgb16 (crates/codec-iter/src/avif_config.rs:122-170) kept as it is: packed uint16
-        samples of `depth` bits, each meaning the sRGB value v / (2^depth - 1).  A session scores it through a deep batch."""
+        samples of `depth` bits, each meaning the sRGB value v / (2^depth - 1).  A session scores it through a deep batch.
+        icc_profile: the decode's matrix/TRC profile, applied on the device by a session without a cms."""
         if depth not in DEEP_DEPTHS:
             raise ValueError(f"depth must be one of {DEEP_DEPTHS}, got {depth}")
-        return ImageData(np.ascontiguousarray(data, dtype=np.uint16).reshape(-1), int(width), int(height), 3, None, int(depth),
+        return ImageData(np.ascontiguousarray(data, dtype=np.uint16).reshape(-1), int(width), int(height), 3,
+                         None if icc_profile is None else bytes(icc_profile), int(depth),
                          colour=_colour_at(colour, depth), gain_map=_gain_map_for(gain_map, colour, width, height))
 
     @staticmethod
@@ -335,27 +338,47 @@ class EvalSession:
         """cms(profile_bytes, rgb (n, 3) uint8) -> (n, 3) uint8: the host's ICC -> sRGB transform (the reference's default
         build uses moxcms, icc.rs:69-103).  It is evaluated ONCE per distinct profile on the identity colour cube; the
         resulting 2^24-entry table lives on the device and is applied to every decoded image tagged with that profile
-        (session.rs:394: only DECODED images go through to_rgb8_srgb, the source image does not).  Without a cms a tagged
-        decoded image raises what a build without the `icc` feature raises."""
+        (session.rs:394: only DECODED images go through to_rgb8_srgb, the source image does not).  Without a cms a decoded
+        image tagged with a matrix/TRC profile (icc_describe(profile).kind == 0) has it applied on the device by the library
+        itself (IccProfile), in RGB8, deep and linear groups alike; one tagged with any other profile
+        raises what a build without the `icc` feature raises."""
         self.config = config
         self.ctx = ctx or Context(device)
         self._own_ctx = ctx is None
         self._codecs: List[_CodecEntry] = []
         self._cms = cms
         self._tables: Dict[bytes, ColorTable] = {}
+        self._profiles: Dict[bytes, Optional[IccProfile]] = {}
 
     def close(self):
         for t in self._tables.values():
             t.close()
         self._tables.clear()
+        for p in self._profiles.values():
+            if p is not None:
+                p.close()
+        self._profiles.clear()
         if self._own_ctx:
             self.ctx.close()
+
+    def _profile_for(self, image: ImageData) -> Optional[IccProfile]:
+        """The device profile of a decoded image tagged with a matrix/TRC profile, in a session without a cms; None for
+        an untagged image, a session with a cms (which applies every profile) and any other profile.  A profile is parsed
+        once per session: the handle, or None for a profile the library does not take, is kept by the profile's bytes."""
+        if image.icc_profile is None or self._cms is not None:
+            return None
+        key = bytes(image.icc_profile)
+        if key not in self._profiles:
+            self._profiles[key] = IccProfile(self.ctx, key) if icc_describe(key).kind == 0 else None
+        return self._profiles[key]
 
     def _table_for(self, image: ImageData) -> Optional[ColorTable]:
         """The device colour table of a decoded image's profile (None for untagged = sRGB images, icc.rs:73)."""
         if image.icc_profile is None:
             return None
         if self._cms is None:
+            if self._profile_for(image) is not None:
+                return None  # applied by set_*_icc instead
             image._check_profile()
         key = bytes(image.icc_profile)
         t = self._tables.get(key)
@@ -397,7 +420,7 @@ class EvalSession:
                     t0 = time.perf_counter()
                     decoded = codec.decode(encoded)
                     row.decode_time_ms = int((time.perf_counter() - t0) * 1000)
-                    if self._cms is None:
+                    if self._cms is None and self._profile_for(decoded) is None:
                         decoded._check_profile()  # to_rgb8_srgb's failure mode without colour management, before anything reaches the device
                     pending.append((len(report.results), decoded))
                 report.results.append(row)
@@ -483,10 +506,13 @@ class EvalSession:
             return batch.set_test_yuv_cicp(pair_index, ref_index, image.yuv_image, colour)
         if image.colour is not None and image.icc_profile is not None:
             refuse("an image with both a colour description and an ICC profile is not supported")
-        if image.icc_profile is not None and pair_index is not None:  # the source's own profile is not applied, as ever
+        profile = self._profile_for(image) if pair_index is not None and not image.linear and image.gain_map is None else None
+        if image.icc_profile is not None and pair_index is not None and profile is None:  # the source's own profile is not applied, as ever
             refuse("an ICC profile is not applied in linear light")
         if image.has_alpha and self.config.alpha_backgrounds:
             refuse("alpha_backgrounds with a colour description is not supported")
+        if profile is not None:  # a matrix/TRC profile, no cms: the library's own transform, into linear light
+            return batch.set_test_icc(pair_index, ref_index, image.data.reshape(image.height, image.width, image.channels), image.depth or 8, profile)
         if image.linear:
             return batch.set_reference(ref_index, image.data) if pair_index is None else batch.set_test(pair_index, ref_index, image.data)
         colour = image.colour or ColourDescription.SRGB.with_depth(image.depth or 8)
@@ -572,14 +598,18 @@ class EvalSession:
                     if (decoded.width, decoded.height) != (w, h):  # calculate_metrics' length check, ssimulacra2.rs:65-70
                         raise DimensionMismatch(1, f"Dimension mismatch: expected ({w}, {h}), got ({decoded.width}, {decoded.height})")
                     n = fan(image, decoded)
+                    profile = self._profile_for(decoded)  # a matrix/TRC profile in a session without a cms, else None
                     if bgs and decoded.has_alpha:
-                        if self._table_for(decoded) is not None:
+                        if profile is not None or self._table_for(decoded) is not None:
                             raise MetricCalculation(CE_ERR_BACKEND, "Metric calculation failed: alpha_backgrounds: a decode with alpha and an ICC profile is not supported")
                         batch.set_test_over(k, ref_of, decoded.data, decoded.pixel_format, bg_side[1])
                     else:
                         for j in range(n):  # an opaque decode against a source with alpha: the same image over every background
                             if decoded.yuv_image is not None:  # a decoder's Y'CbCr planes: upsampled and converted on the device, into the slot
                                 batch.set_test_yuv(k + j, ref_of[j], decoded.yuv_image)
+                            elif profile is not None:  # to_rgb8_srgb by the library's own transform
+                                batch.set_test_icc(k + j, ref_of[j], decoded.data.reshape(decoded.height, decoded.width, decoded.channels),
+                                                   decoded.depth or 8, profile)
                             else:
                                 batch.set_test_lut(k + j, ref_of[j], decoded.data, decoded.pixel_format, self._table_for(decoded))  # to_rgb8_srgb, session.rs:394
                     rows.append((report, row_index, k, n))

@@ -945,6 +945,92 @@ int ce_eval_pair_delta_e_itp_map(ce_ctx *ctx, const float *reference, size_t ref
                                  uint32_t width, uint32_t height, uint32_t depth, float white_nits, uint32_t block, uint32_t *map,
                                  size_t map_len, const uint32_t *thresholds_q20, uint32_t n_thresholds, uint64_t *over);
 
+/* ---- matrix/TRC ICC profiles applied on the device ------------------------------------------------
+ * transform_to_srgb (src/metrics/icc.rs:69-103) for the profiles photographs carry - three colorant tags and three tone
+ * curves - without a CMS on the host.  ce_lut_* above stays the route for every other profile.
+ * Accepted: ICC v2 and v4; `acsp`; data colour space `RGB `, PCS `XYZ `; class `mntr`, `scnr` or `spac`; rXYZ / gXYZ / bXYZ
+ * of type `XYZ `; rTRC / gTRC / bTRC of type `curv` or `para`.  A profile with an A2B0, A2B1 or A2B2 tag is LUT-based and not
+ * accepted (a CMS would use the LUT).  PCS white, wtpt and chad are not read: the colorants are D50-adapted by the format's
+ * own rule.  Every length, offset and count is checked against the buffer before use; a profile is at most
+ * CE_ICC_MAX_PROFILE_BYTES long (its header's size field must lie within the buffer) and a curv at most
+ * CE_ICC_MAX_CURVE_POINTS samples.
+ * Curves, in f64 at e = v / maxv, the result clipped to [0, 1] (NaN -> 0) and rounded once to f32:
+ *   curv n = 0: e.  n = 1: e^g, g the u8Fixed8 number.  n >= 2: samples s = u16 / 65535 interpolated at p = e * (n - 1):
+ *     i = min(floor(p), n - 2), s[i] + (s[i + 1] - s[i]) * (p - i).
+ *   para (parameters s15Fixed16 / 65536; a negative base of the power is taken as 0):
+ *     0: X^g.  1: (aX + b)^g for X >= -b / a, else 0.  2: (aX + b)^g + c for X >= -b / a, else c.  A profile whose type 1 or 2
+ *     curve has a = 0 has no breakpoint and is malformed.
+ *     3: (aX + b)^g for X >= d, else cX.  4: (aX + b)^g + e for X >= d, else cX + f.
+ * Matrix: M = inv(A) * P in f64 rounded once to f32, row-major; P has the profile's colorants as columns (the s15Fixed16
+ * integers / 65536, exactly), A those of the canonical sRGB profile - rXYZ (0x6FA2, 0x38F5, 0x0390), gXYZ (0x6299, 0xB785,
+ * 0x18DA), bXYZ (0x24A0, 0x0F84, 0xB6CF) - inverted by ce_colour_matrix's adjugate / determinant sequence and multiplied as
+ * (ai0 * p0 + ai1 * p1) + ai2 * p2.  A profile whose nine integers are A's has M = I exactly and is not multiplied.
+ * Definition, per pixel of a CE_PIXEL_RGB8 / RGBA8 / RGB16 / RGBA16 image (alpha dropped) of source depth d in {8, 10, 12,
+ * 16}, maxv = 2^d - 1:
+ *   1. t_c = table_c[min(v_c, maxv)], one table per channel (ce_icc_build_tables).
+ *   2. unless M = I: o_i = (M[i][0] * t_r + M[i][1] * t_g) + M[i][2] * t_b in f32, each product and sum rounded separately.
+ *   3. the clamp of a linear image (NaN -> 0, [-CE_LINEAR_MAX, CE_LINEAR_MAX]).  This is the value a linear batch stores.
+ *   4. an RGB8 batch (D = 8) or a side of depth D of a deep batch stores, for each of the three values x,
+ *        code = #{ k in 1 .. 2^D - 1 : x >= T[k] },  T[k] = f32(srgb_eotf_f64((k - 0.5) / (2^D - 1)))
+ *      with srgb_eotf_f64 the curve of ce_srgb_table's rule 0: a search in a strictly increasing table (ce_srgb_encode_thresholds),
+ *      NaN -> 0, out-of-gamut values clip.  The integer routes are the encode of the linear route and add no other arithmetic.
+ * tests/icc_restatement.py restates this in numpy; the device equals it bit for bit.
+ * Not part of this: LUT-based profiles (mAB, lut8, lut16), Gray and CMYK profiles, rendering intents, black-point
+ * compensation, Y'CbCr planes with a profile, alpha compositing with a profile, ce_ref_* handles and the pooled ce_eval_batch. */
+#define CE_ICC_MAX_PROFILE_BYTES 4194304u
+#define CE_ICC_MAX_CURVE_POINTS 65536u
+enum { CE_ICC_SUPPORTED = 0, CE_ICC_LUT_BASED = 1, CE_ICC_NOT_RGB_XYZ = 2, CE_ICC_MALFORMED = 3 };
+enum { CE_ICC_CURVE_CURV = 0, CE_ICC_CURVE_PARA = 1 };
+typedef struct ce_icc_curve {
+    int type;          /* CE_ICC_CURVE_CURV or CE_ICC_CURVE_PARA */
+    uint32_t count;    /* curv: the number of samples (0: identity, 1: a gamma); para: the function type 0 .. 4 */
+    int32_t params[7]; /* para: g a b c d e f as s15Fixed16 (those the type has; the rest 0); curv n = 1: params[0] = u8Fixed8 */
+    uint32_t offset;   /* curv n >= 2: where the first u16 sample lies in the profile */
+} ce_icc_curve;
+typedef struct ce_icc_description {
+    int kind;               /* CE_ICC_SUPPORTED, _LUT_BASED, _NOT_RGB_XYZ or _MALFORMED; the fields below are filled as far as parsing got */
+    uint32_t version;       /* header bytes 8 .. 11, e.g. 0x04300000 */
+    uint32_t profile_class; /* the signature as a big-endian number: 'mntr' = 0x6d6e7472 */
+    int32_t colorants[9];   /* P row-major as s15Fixed16: rows X Y Z, columns r g b */
+    ce_icc_curve curves[3]; /* rTRC, gTRC, bTRC */
+    char reason[96];        /* kind != 0: why, NUL-terminated */
+} ce_icc_description;
+/* Pure host functions.  ce_icc_describe returns CE_OK whenever `out` is filled, whatever the kind.  The builders return
+ * CE_ERR_INVALID_ARG for a profile whose kind != 0 (ce_icc_describe has the reason), a depth outside {8, 10, 12, 16} or a
+ * wrong n.  ce_icc_build_tables: out = [3][2^depth] floats, n = 3 << depth.  ce_srgb_encode_thresholds: out[k - 1] = T[k],
+ * n = 2^depth - 1. */
+int ce_icc_describe(const uint8_t *bytes, size_t len, ce_icc_description *out);
+int ce_icc_build_matrix(const uint8_t *bytes, size_t len, float out[9]);
+int ce_icc_build_tables(const uint8_t *bytes, size_t len, uint32_t depth, float *out, size_t n);
+int ce_srgb_encode_thresholds(uint32_t depth, float *out, size_t n);
+/* A parsed profile on a context's device, with its tone tables of all four source depths (0.85 MB of device memory), built
+ * by ce_icc_create; the handle does not change afterwards.  It belongs to its context and follows the context's threading
+ * rule: one in-flight call per context, the calls that take the handle included (the thresholds of a slot depth are made on
+ * the context by the first ingest that needs them).  CE_ERR_INVALID_ARG with the reason in ce_last_error for a profile whose
+ * kind != 0.  Destroy it after the last batch that was given it has been collected. */
+typedef struct ce_icc ce_icc;
+int ce_icc_create(ce_ctx *ctx, const uint8_t *bytes, size_t len, ce_icc **out);
+void ce_icc_destroy(ce_icc *icc);
+/* One image of the batch's shape into a reference / test slot of a linear, an RGB8 or a deep batch, with the staging, stream
+ * and ordering of ce_batch_set_*_cicp; the pixels are consumed on return.  `depth` is the source's.  An RGB8 batch takes
+ * CE_PIXEL_RGB8 / RGBA8 only; a deep side is written at its own depth from any of the four formats.  CE_ERR_INVALID_ARG, with
+ * the reason in ce_last_error and the batch still usable, for a null pointer, a profile of another device, another format, a
+ * depth outside {8, 10, 12, 16}, an 8-bit format with depth != 8, a 16-bit format on an RGB8 batch; CE_ERR_BAD_LENGTH for a
+ * wrong len. */
+int ce_batch_set_reference_icc(ce_batch *b, uint32_t ref_index, const void *pixels, size_t len, int format, uint32_t depth,
+                               const ce_icc *icc);
+int ce_batch_set_test_icc(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format,
+                          uint32_t depth, const ce_icc *icc);
+/* One image of w x h to host memory: packed float RGB (out_len = w * h * 3 floats), packed sRGB8 (out_len = w * h * 3
+ * bytes) or packed u16 sRGB of depth_out in {8, 10, 12, 16} (out_len = w * h * 3 samples).  Errors as above, and
+ * CE_ERR_BAD_LENGTH for a wrong out_len. */
+int ce_icc_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc, uint32_t w,
+                     uint32_t h, float *out, size_t out_len);
+int ce_icc_to_srgb8(ce_ctx *ctx, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc, uint32_t w,
+                    uint32_t h, uint8_t *out, size_t out_len);
+int ce_icc_to_srgb16(ce_ctx *ctx, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc, uint32_t w,
+                     uint32_t h, uint32_t depth_out, uint16_t *out, size_t out_len);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------ */
 /* Bracket every kernel launch with a HIP event pair, recorded on the stream the kernel is launched on,
  * and accumulate per-kernel time.  on = 0: off (default).  on = 2: events only; the batch keeps its
