@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "ba_front_geom.h"
 #include "ce_internal.h"
 
 namespace {
@@ -61,12 +62,6 @@ __device__ __forceinline__ uint32_t slot_of(uint32_t z, uint32_t n_refs_used, ui
 struct plane_sel {
     uint32_t per_unit, first, n;
 };
-
-__device__ __forceinline__ uint32_t mirror(int x, int n)
-{
-    while (x < 0 || x >= n) x = x < 0 ? -x - 1 : 2 * n - 1 - x;
-    return (uint32_t)x;
-}
 
 // Long separable blurs, LDS-tiled with a register window: a thread produces 8 consecutive outputs
 // from 8 + LEN - 1 inputs held in registers (5 LDS reads per output at LEN = 33 instead of 33), each
@@ -265,10 +260,12 @@ constexpr int FT = 32, FR = FT + 4;
 // HALF: the half-resolution level - its linear RGB is the 2x2 average of the full-resolution image's (Subsample2x: the
 // four quarter-weighted samples added in row-major order, the last odd row / column doubled), formed here from the u8
 // source instead of in a pass of its own; gi = the full-resolution geometry.
-// T: the sample type - uint8_t (the 256-entry table in LDS, packed loads on interior tiles) or the uint16_t of a deep batch
-// (2^depth entries per side in global memory, lut for the references and lut_test for the distorted images; every tile
-// takes the per-sample loads of the border path) or the float of a linear batch (the sample is the
-// linear value: no table, the same per-sample path)
+// T: the sample type - uint8_t (the 256-entry table in LDS, packed loads wherever a group of pixels lies inside its row) or
+// the uint16_t of a deep batch (2^depth entries per side in global memory, lut for the references and lut_test for the
+// distorted images; every cell takes the per-sample loads) or the float of a linear batch (the sample
+// is the linear value: no table, the same per-sample loads).
+// Every tile runs the same two blur passes with plain indices: a tile that touches the image's edge first writes the
+// mirrored values into the out-of-image cells of its region (ba_front_geom.h), once, instead of mirroring at every tap.
 template <typename T>
 __device__ __forceinline__ float ba_linear_of(const float *tab, T v) { return tab[v]; }
 template <>
@@ -293,7 +290,9 @@ __global__ __launch_bounds__(TPB) void k_ba_front(const uint8_t *__restrict__ re
     const float *tab = U8 ? s_lut : (z < n_refs_used ? lut : lut_test);
     const int W8 = HALF ? (int)gi.w : w, H8 = HALF ? (int)gi.h : h;  // the u8 image
     __syncthreads();
+    // block-uniform: the whole 36x36 region lies inside the image, so there is no rim to fill
     const bool interior = gx0 >= 0 && gy0 >= 0 && gx0 + FR <= w && gy0 + FR <= h;
+    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(src8) & 3);
     // four u8 pixels (12 bytes, any alignment) from four aligned dwords
     auto load12 = [&](const uint8_t *p, uint32_t &v0, uint32_t &v1, uint32_t &v2) {
         const uintptr_t a = reinterpret_cast<uintptr_t>(p);
@@ -301,40 +300,9 @@ __global__ __launch_bounds__(TPB) void k_ba_front(const uint8_t *__restrict__ re
         const uint32_t d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3], sh = (uint32_t)(a & 3);
         v0 = __builtin_amdgcn_alignbyte(d1, d0, sh), v1 = __builtin_amdgcn_alignbyte(d2, d1, sh), v2 = __builtin_amdgcn_alignbyte(d3, d2, sh);
     };
-    if (U8 && !HALF && interior) {
-        // four pixels per task; nine tasks per row of the region
-        for (int i = threadIdx.x; i < FR * (FR / 4); i += TPB) {
-            const int ly = i / (FR / 4), lx = 4 * (i % (FR / 4));
-            uint32_t v0, v1, v2;
-            load12(src8 + ((size_t)(gy0 + ly) * w + gx0 + lx) * 3, v0, v1, v2);
-            const int o = ly * FR + lx;
-            L[0][o] = s_lut[v0 & 255u], L[1][o] = s_lut[(v0 >> 8) & 255u], L[2][o] = s_lut[(v0 >> 16) & 255u];
-            L[0][o + 1] = s_lut[v0 >> 24], L[1][o + 1] = s_lut[v1 & 255u], L[2][o + 1] = s_lut[(v1 >> 8) & 255u];
-            L[0][o + 2] = s_lut[(v1 >> 16) & 255u], L[1][o + 2] = s_lut[v1 >> 24], L[2][o + 2] = s_lut[v2 & 255u];
-            L[0][o + 3] = s_lut[(v2 >> 8) & 255u], L[1][o + 3] = s_lut[(v2 >> 16) & 255u], L[2][o + 3] = s_lut[v2 >> 24];
-        }
-    } else if (U8 && HALF && interior && 2 * (gx0 + FR) <= W8 && 2 * (gy0 + FR) <= H8) {
-        // two half-resolution elements (2 x 4 u8 pixels) per task: ((0 + q00) + q01) + q10) + q11, q = 0.25 * linear
-        for (int i = threadIdx.x; i < FR * (FR / 2); i += TPB) {
-            const int ly = i / (FR / 2), lx = 2 * (i % (FR / 2));
-            uint32_t a0, a1, a2, b0, b1, b2;
-            const uint8_t *p = src8 + ((size_t)(2 * (gy0 + ly)) * W8 + 2 * (gx0 + lx)) * 3;
-            load12(p, a0, a1, a2);
-            load12(p + (size_t)W8 * 3, b0, b1, b2);
-            const int o = ly * FR + lx;
-            // row pixels: p0 = (v0.b0, v0.b1, v0.b2), p1 = (v0.b3, v1.b0, v1.b1), p2 = (v1.b2, v1.b3, v2.b0), p3 = (v2.b1, v2.b2, v2.b3)
-#define CE_Q(v) (0.25f * s_lut[(v)])
-            L[0][o] = ((0.0f + CE_Q(a0 & 255u)) + CE_Q(a0 >> 24)) + CE_Q(b0 & 255u) + CE_Q(b0 >> 24);
-            L[1][o] = ((0.0f + CE_Q((a0 >> 8) & 255u)) + CE_Q(a1 & 255u)) + CE_Q((b0 >> 8) & 255u) + CE_Q(b1 & 255u);
-            L[2][o] = ((0.0f + CE_Q((a0 >> 16) & 255u)) + CE_Q((a1 >> 8) & 255u)) + CE_Q((b0 >> 16) & 255u) + CE_Q((b1 >> 8) & 255u);
-            L[0][o + 1] = ((0.0f + CE_Q((a1 >> 16) & 255u)) + CE_Q((a2 >> 8) & 255u)) + CE_Q((b1 >> 16) & 255u) + CE_Q((b2 >> 8) & 255u);
-            L[1][o + 1] = ((0.0f + CE_Q(a1 >> 24)) + CE_Q((a2 >> 16) & 255u)) + CE_Q(b1 >> 24) + CE_Q((b2 >> 16) & 255u);
-            L[2][o + 1] = ((0.0f + CE_Q(a2 & 255u)) + CE_Q(a2 >> 24)) + CE_Q(b2 & 255u) + CE_Q(b2 >> 24);
-#undef CE_Q
-        }
-    } else
-    for (int i = threadIdx.x; i < FR * FR; i += TPB) {
-        const int lx = i % FR, ly = i / FR, X = gx0 + lx, Y = gy0 + ly;
+    // the per-element route: one region cell, sample by sample; a cell outside the image loads nothing
+    auto load_cell = [&](int lx, int ly) {
+        const int i = ly * FR + lx, X = gx0 + lx, Y = gy0 + ly;
         if (X >= 0 && X < w && Y >= 0 && Y < h) {
             if (!HALF) {
                 const T *px = srcT + ((size_t)Y * w + X) * 3;
@@ -363,71 +331,138 @@ __global__ __launch_bounds__(TPB) void k_ba_front(const uint8_t *__restrict__ re
                 }
             }
         }
-    }
-    __syncthreads();
-    // IN (block-uniform): the whole 36x36 region lies inside the image, so nothing is mirrored and nothing is masked
-    auto stages = [&](auto in_tag) {
-        constexpr bool IN = decltype(in_tag)::value;
-        // row pass on every in-image row of the region, tile columns only; mirror in GLOBAL coordinates
-        for (int i = threadIdx.x; i < FR * FT; i += TPB) {
-            const int tx = i % FT, ly = i / FT, X = x0 + tx, Y = gy0 + ly;
-            if (IN || (X < w && Y >= 0 && Y < h)) {
-                const int c0 = X - gx0;
-                const int m1 = IN ? c0 - 1 : (int)mirror(X - 1, w) - gx0, p1 = IN ? c0 + 1 : (int)mirror(X + 1, w) - gx0,
-                          m2 = IN ? c0 - 2 : (int)mirror(X - 2, w) - gx0, p2 = IN ? c0 + 2 : (int)mirror(X + 2, w) - gx0;
-    #pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    const float *r = &L[c][ly * FR];
-                    H[c][i] = r[c0] * w0 + (r[m1] + r[p1]) * w1 + (r[m2] + r[p2]) * w2;
+    };
+    // Load phase (ba_front_geom.h): a u8 task takes the packed route wherever its row is inside the image and its group inside
+    // the row, on every tile; only the groups across the left or right edge go element by element
+    if (U8 && !HALF) {
+        // four pixels per task; nine tasks per row of the region
+        auto packed4 = [&](int lx, int ly) {
+            uint32_t v0, v1, v2;
+            load12(src8 + ((size_t)(gy0 + ly) * w + gx0 + lx) * 3, v0, v1, v2);
+            const int o = ly * FR + lx;
+            L[0][o] = s_lut[v0 & 255u], L[1][o] = s_lut[(v0 >> 8) & 255u], L[2][o] = s_lut[(v0 >> 16) & 255u];
+            L[0][o + 1] = s_lut[v0 >> 24], L[1][o + 1] = s_lut[v1 & 255u], L[2][o + 1] = s_lut[(v1 >> 8) & 255u];
+            L[0][o + 2] = s_lut[(v1 >> 16) & 255u], L[1][o + 2] = s_lut[v1 >> 24], L[2][o + 2] = s_lut[v2 & 255u];
+            L[0][o + 3] = s_lut[(v2 >> 8) & 255u], L[1][o + 3] = s_lut[(v2 >> 16) & 255u], L[2][o + 3] = s_lut[v2 >> 24];
+        };
+        if (ba_front_all_fast4(gx0, gy0, w, h, mis)) {  // block-uniform
+            for (int i = threadIdx.x; i < FR * ba_front_groups4; i += TPB) packed4(4 * (i % ba_front_groups4), i / ba_front_groups4);
+        } else {
+            const int shift = ba_front_shift4(gx0, w);
+            for (int i = threadIdx.x; i < FR * ba_front_groups4; i += TPB) {
+                const int g = i % ba_front_groups4, ly = i / ba_front_groups4, lx = ba_front_group4_cell(g, 0, shift);
+                if (ba_front_group4_contiguous(g, shift) && ba_front_fast4(gx0 + lx, gy0 + ly, w, h, mis))
+                    packed4(lx, ly);
+                else
+                    for (int k = 0; k < 4; k++) load_cell(ba_front_group4_cell(g, k, shift), ly);
+            }
+        }
+    } else if (U8 && HALF) {
+        // two half-resolution elements (2 x 4 u8 pixels) per task: ((0 + q00) + q01) + q10) + q11, q = 0.25 * linear
+        auto packed2 = [&](int lx, int ly) {
+            uint32_t a0, a1, a2, b0, b1, b2;
+            const uint8_t *p = src8 + ((size_t)(2 * (gy0 + ly)) * W8 + 2 * (gx0 + lx)) * 3;
+            load12(p, a0, a1, a2);
+            load12(p + (size_t)W8 * 3, b0, b1, b2);
+            const int o = ly * FR + lx;
+            // row pixels: p0 = (v0.b0, v0.b1, v0.b2), p1 = (v0.b3, v1.b0, v1.b1), p2 = (v1.b2, v1.b3, v2.b0), p3 = (v2.b1, v2.b2, v2.b3)
+#define CE_Q(v) (0.25f * s_lut[(v)])
+            L[0][o] = ((0.0f + CE_Q(a0 & 255u)) + CE_Q(a0 >> 24)) + CE_Q(b0 & 255u) + CE_Q(b0 >> 24);
+            L[1][o] = ((0.0f + CE_Q((a0 >> 8) & 255u)) + CE_Q(a1 & 255u)) + CE_Q((b0 >> 8) & 255u) + CE_Q(b1 & 255u);
+            L[2][o] = ((0.0f + CE_Q((a0 >> 16) & 255u)) + CE_Q((a1 >> 8) & 255u)) + CE_Q((b0 >> 16) & 255u) + CE_Q((b1 >> 8) & 255u);
+            L[0][o + 1] = ((0.0f + CE_Q((a1 >> 16) & 255u)) + CE_Q((a2 >> 8) & 255u)) + CE_Q((b1 >> 16) & 255u) + CE_Q((b2 >> 8) & 255u);
+            L[1][o + 1] = ((0.0f + CE_Q(a1 >> 24)) + CE_Q((a2 >> 16) & 255u)) + CE_Q(b1 >> 24) + CE_Q((b2 >> 16) & 255u);
+            L[2][o + 1] = ((0.0f + CE_Q(a2 & 255u)) + CE_Q(a2 >> 24)) + CE_Q(b2 & 255u) + CE_Q(b2 >> 24);
+#undef CE_Q
+        };
+        if (ba_front_all_fast2_half(gx0, gy0, W8, H8, mis)) {  // block-uniform
+            for (int i = threadIdx.x; i < FR * ba_front_groups2; i += TPB) packed2(2 * (i % ba_front_groups2), i / ba_front_groups2);
+        } else {
+            for (int i = threadIdx.x; i < FR * ba_front_groups2; i += TPB) {
+                int lx, ly;
+                ba_front_task2(i, lx, ly);
+                if (ba_front_fast2_half(gx0 + lx, gy0 + ly, W8, H8, mis)) {
+                    packed2(lx, ly);
+                } else {
+                    load_cell(lx, ly);
+                    load_cell(lx + 1, ly);
                 }
             }
         }
-        __syncthreads();
-        for (int i = threadIdx.x; i < FT * FT; i += TPB) {
-            const int tx = i % FT, ty = i / FT, X = x0 + tx, Y = y0 + ty;
-            if (!IN && (X >= w || Y >= h)) continue;
-            const int r0 = Y - gy0;
-            const int rm1 = IN ? r0 - 1 : (int)mirror(Y - 1, h) - gy0, rp1 = IN ? r0 + 1 : (int)mirror(Y + 1, h) - gy0,
-                      rm2 = IN ? r0 - 2 : (int)mirror(Y - 2, h) - gy0, rp2 = IN ? r0 + 2 : (int)mirror(Y + 2, h) - gy0;
-            float bl[3], ln[3];
-    #pragma unroll
-            for (int c = 0; c < 3; c++) {
-                const float *col = &H[c][tx];
-                bl[c] = col[r0 * FT] * w0 + (col[rm1 * FT] + col[rp1 * FT]) * w1 + (col[rm2 * FT] + col[rp2 * FT]) * w2;
-                ln[c] = L[c][(ty + 2) * FR + tx + 2];
-            }
-            const float mn = 1e-4f;
-            float p0, p1v, p2v;
-            opsin_absorbance(bl[0] * intensity_target, bl[1] * intensity_target, bl[2] * intensity_target, p0, p1v, p2v);
-            p0 = p0 > mn ? p0 : mn;
-            p1v = p1v > mn ? p1v : mn;
-            p2v = p2v > mn ? p2v : mn;
-            // IEEE quotients without the range-scaling steps (ce_internal.h).  Measured ("Operand
-            // ranges"): RGB8 / deep batches p in [1.76, 7.2e3] (the opsin bias keeps p off its clamp), gamma in [24, 148];
-            // linear batches p in [1e-4 (the clamp above), 1.04e7], gamma in [21, 288], quotients in [2.8e-5, 2.1e5]
-            float s0 = ce_div_noscale(gamma_f(p0), p0), s1 = ce_div_noscale(gamma_f(p1v), p1v), s2 = ce_div_noscale(gamma_f(p2v), p2v);
-            s0 = s0 > mn ? s0 : mn;
-            s1 = s1 > mn ? s1 : mn;
-            s2 = s2 > mn ? s2 : mn;
-            float c0, c1, c2;
-            opsin_absorbance(ln[0] * intensity_target, ln[1] * intensity_target, ln[2] * intensity_target, c0, c1, c2);
-            c0 *= s0;
-            c1 *= s1;
-            c2 *= s2;
-            const float min01 = 1.7557483643287353f, min2 = 12.226454707163354f;
-            c0 = c0 > min01 ? c0 : min01;
-            c1 = c1 > min01 ? c1 : min01;
-            c2 = c2 > min2 ? c2 : min2;
-            const size_t o = (size_t)slot * 3 * g.plane + (size_t)Y * g.pitch + X;
-            xyb[o] = c0 - c1;
-            xyb[o + g.plane] = c0 + c1;
-            xyb[o + 2 * g.plane] = c2;
+    } else {
+        for (int i = threadIdx.x; i < FR * FR; i += TPB) load_cell(i % FR, i / FR);
+    }
+    __syncthreads();
+    // Rim fill, edge tiles only: every out-of-image cell a tap can reach takes the value of the cell the blur's mirroring
+    // names (an in-image cell: written before the barrier above, read-only here), every other out-of-image cell is zeroed.
+    // The out-of-image columns first, then the out-of-image rows over the in-image columns: few cells, each visited once
+    if (!interior) {
+        auto fill = [&](int lx, int ly) {
+            const int i = ly * FR + lx;
+            int src = 0;
+            if (ba_front_rim(gx0 + lx, gy0 + ly, w, h, gx0, gy0, src) == BA_RIM_COPY)
+                L[0][i] = L[0][src], L[1][i] = L[1][src], L[2][i] = L[2][src];
+            else
+                L[0][i] = 0.0f, L[1][i] = 0.0f, L[2][i] = 0.0f;
+        };
+        const int xlo = ba_front_out_lo(gx0), xhi = ba_front_out_hi(gx0, w), ylo = ba_front_out_lo(gy0), yhi = ba_front_out_hi(gy0, h);
+        for (int t = threadIdx.x; t < (xlo + FR - xhi) * FR; t += TPB) fill(ba_front_out_line(t / FR, xlo, xhi), t % FR);
+        for (int t = threadIdx.x; t < (ylo + FR - yhi) * FR; t += TPB) {
+            const int lx = t % FR;
+            if (lx >= xlo && lx < xhi) fill(lx, ba_front_out_line(t / FR, ylo, yhi));
         }
-    };
-    if (interior)
-        stages(std::true_type{});
-    else
-        stages(std::false_type{});
+        __syncthreads();
+    }
+    // Row pass on every row of the region, tile columns only, with plain indices: a rim row holds its mirror source's cells,
+    // so its H row is that row's, from the same inputs and the same expression.  Columns right of the image blur zeros and
+    // are not stored.
+    for (int i = threadIdx.x; i < FR * FT; i += TPB) {
+        const int tx = i % FT, ly = i / FT, c0 = tx + 2;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float *r = &L[c][ly * FR];
+            H[c][i] = r[c0] * w0 + (r[c0 - 1] + r[c0 + 1]) * w1 + (r[c0 - 2] + r[c0 + 2]) * w2;
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < FT * FT; i += TPB) {
+        const int tx = i % FT, ty = i / FT, X = x0 + tx, Y = y0 + ty;
+        if (X >= w || Y >= h) continue;
+        const int r0 = ty + 2;
+        float bl[3], ln[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float *col = &H[c][tx];
+            bl[c] = col[r0 * FT] * w0 + (col[(r0 - 1) * FT] + col[(r0 + 1) * FT]) * w1 + (col[(r0 - 2) * FT] + col[(r0 + 2) * FT]) * w2;
+            ln[c] = L[c][(ty + 2) * FR + tx + 2];
+        }
+        const float mn = 1e-4f;
+        float p0, p1v, p2v;
+        opsin_absorbance(bl[0] * intensity_target, bl[1] * intensity_target, bl[2] * intensity_target, p0, p1v, p2v);
+        p0 = p0 > mn ? p0 : mn;
+        p1v = p1v > mn ? p1v : mn;
+        p2v = p2v > mn ? p2v : mn;
+        // IEEE quotients without the range-scaling steps (ce_internal.h).  Measured ("Operand
+        // ranges"): RGB8 / deep batches p in [1.76, 7.2e3] (the opsin bias keeps p off its clamp), gamma in [24, 148];
+        // linear batches p in [1e-4 (the clamp above), 1.04e7], gamma in [21, 288], quotients in [2.8e-5, 2.1e5]
+        float s0 = ce_div_noscale(gamma_f(p0), p0), s1 = ce_div_noscale(gamma_f(p1v), p1v), s2 = ce_div_noscale(gamma_f(p2v), p2v);
+        s0 = s0 > mn ? s0 : mn;
+        s1 = s1 > mn ? s1 : mn;
+        s2 = s2 > mn ? s2 : mn;
+        float c0, c1, c2;
+        opsin_absorbance(ln[0] * intensity_target, ln[1] * intensity_target, ln[2] * intensity_target, c0, c1, c2);
+        c0 *= s0;
+        c1 *= s1;
+        c2 *= s2;
+        const float min01 = 1.7557483643287353f, min2 = 12.226454707163354f;
+        c0 = c0 > min01 ? c0 : min01;
+        c1 = c1 > min01 ? c1 : min01;
+        c2 = c2 > min2 ? c2 : min2;
+        const size_t o = (size_t)slot * 3 * g.plane + (size_t)Y * g.pitch + X;
+        xyb[o] = c0 - c1;
+        xyb[o + g.plane] = c0 + c1;
+        xyb[o + 2 * g.plane] = c2;
+    }
 }
 
 // ---- SeparateFrequencies pointwise stages ------------------------------------------------------------------
