@@ -724,6 +724,14 @@ pub fn icc_describe(profile: &[u8]) -> sys::ce_icc_description {
     d
 }
 
+/// `ce_icc_lut_describe`: what the library's parser reads from a LUT-based ICC profile, without a device.  `kind` is
+/// `sys::CE_ICC_LUT_SUPPORTED` for the profiles `HipIccProfile::new_lut` takes.
+pub fn icc_lut_describe(profile: &[u8], intent: i32) -> sys::ce_icc_lut_description {
+    let mut d: sys::ce_icc_lut_description = unsafe { std::mem::zeroed() };
+    unsafe { sys::ce_icc_lut_describe(profile.as_ptr(), profile.len(), intent, &mut d) };
+    d
+}
+
 /// `ce_icc`: a matrix/TRC ICC profile applied on the device, parsed by the library itself (no CMS).  A LUT-based, Gray, CMYK
 /// or malformed profile is refused with the reason; those keep the colour-table route (`ce_lut_*`).
 pub struct HipIccProfile<'a> {
@@ -735,6 +743,16 @@ impl<'a> HipIccProfile<'a> {
     pub fn new(owner: &'a HipMetrics, profile: &[u8]) -> Result<Self, HipError> {
         let mut handle = ptr::null_mut();
         let rc = unsafe { sys::ce_icc_create(owner.ctx, profile.as_ptr(), profile.len(), &mut handle) };
+        owner.check(rc, 0, 0, 0)?;
+        Ok(Self { owner, handle })
+    }
+
+    /// `ce_icc_lut_create`: the same handle for a LUT-based profile (an A2B tag of type mAB, mft2 or mft1),
+    /// evaluated from the profile itself.  `intent` 0, 1 or 2 chooses A2B0 / A2B1 / A2B2; `interpolation` is
+    /// `sys::CE_ICC_CLUT_TRILINEAR` or `sys::CE_ICC_CLUT_TETRAHEDRAL`.  Every call that takes a `HipIccProfile` takes it.
+    pub fn new_lut(owner: &'a HipMetrics, profile: &[u8], intent: i32, interpolation: i32) -> Result<Self, HipError> {
+        let mut handle = ptr::null_mut();
+        let rc = unsafe { sys::ce_icc_lut_create(owner.ctx, profile.as_ptr(), profile.len(), intent, interpolation, &mut handle) };
         owner.check(rc, 0, 0, 0)?;
         Ok(Self { owner, handle })
     }

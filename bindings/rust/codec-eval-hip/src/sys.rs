@@ -76,6 +76,59 @@ pub struct ce_icc_curve {
     pub offset: u32,
 }
 
+/// `ce_icc_lut_describe` only: `count` u8 samples at `offset` (the tables of an `mft1` tag)
+pub const CE_ICC_CURVE_TABLE8: c_int = 2;
+
+pub const CE_ICC_MAX_CLUT_NODES: u32 = 274625;
+pub const CE_ICC_LUT_SUPPORTED: c_int = 0;
+pub const CE_ICC_LUT_NOT_LUT: c_int = 1;
+pub const CE_ICC_LUT_UNSUPPORTED: c_int = 2;
+pub const CE_ICC_LUT_MALFORMED: c_int = 3;
+pub const CE_ICC_CLUT_TRILINEAR: c_int = 0;
+pub const CE_ICC_CLUT_TETRAHEDRAL: c_int = 1;
+pub const CE_ICC_STAGE_A: u32 = 1;
+pub const CE_ICC_STAGE_CLUT: u32 = 2;
+pub const CE_ICC_STAGE_M: u32 = 4;
+pub const CE_ICC_STAGE_MATRIX: u32 = 8;
+pub const CE_ICC_STAGE_B: u32 = 16;
+pub const CE_ICC_LUT_CURVE_IDENTITY: c_int = 0;
+pub const CE_ICC_LUT_CURVE_SAMPLED: c_int = 1;
+pub const CE_ICC_LUT_CURVE_POWER: c_int = 2;
+
+/// `ce_icc_lut_description` (560 bytes): what `ce_icc_lut_describe` reads from a LUT-based profile.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ce_icc_lut_description {
+    pub kind: c_int,
+    pub version: u32,
+    pub profile_class: u32,
+    pub pcs: u32,
+    pub tag: u32,
+    pub tag_type: u32,
+    pub tag_offset: u32,
+    pub tag_size: u32,
+    pub stages: u32,
+    pub grid: [u32; 3],
+    pub precision: u32,
+    pub clut_offset: u32,
+    pub matrix: [i32; 12],
+    pub a: [ce_icc_curve; 3],
+    pub m: [ce_icc_curve; 3],
+    pub b: [ce_icc_curve; 3],
+    pub reason: [c_char; 96],
+}
+
+/// `ce_icc_lut_curve` (72 bytes): a post-CLUT curve as the kernel takes it.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ce_icc_lut_curve {
+    pub kind: c_int,
+    pub ftype: u32,
+    pub count: u32,
+    pub first_sample: u32,
+    pub q: [f64; 7],
+}
+
 /// `ce_icc_description` (264 bytes): what `ce_icc_describe` reads from a profile.
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -426,6 +479,15 @@ extern "C" {
     pub fn ce_srgb_encode_thresholds(depth: u32, out: *mut c_float, n: usize) -> c_int;
     pub fn ce_icc_create(ctx: *mut ce_ctx, bytes: *const u8, len: usize, out: *mut *mut ce_icc) -> c_int;
     pub fn ce_icc_destroy(icc: *mut ce_icc);
+    pub fn ce_icc_lut_describe(bytes: *const u8, len: usize, intent: c_int, out: *mut ce_icc_lut_description) -> c_int;
+    pub fn ce_icc_lut_build_input_tables(bytes: *const u8, len: usize, intent: c_int, depth: u32, out: *mut c_float, n: usize) -> c_int;
+    pub fn ce_icc_lut_build_clut(bytes: *const u8, len: usize, intent: c_int, out: *mut c_float, n: usize) -> c_int;
+    pub fn ce_icc_lut_build_matrix(bytes: *const u8, len: usize, intent: c_int, out: *mut c_float) -> c_int;
+    pub fn ce_icc_lut_build_curves(bytes: *const u8, len: usize, intent: c_int, out: *mut ce_icc_lut_curve, samples: *mut c_float,
+                                   n_samples: usize, needed: *mut usize) -> c_int;
+    pub fn ce_icc_lut_build_pcs_matrix(out: *mut c_float) -> c_int;
+    pub fn ce_icc_lut_create(ctx: *mut ce_ctx, bytes: *const u8, len: usize, intent: c_int, interpolation: c_int,
+                             out: *mut *mut ce_icc) -> c_int;
     pub fn ce_batch_set_reference_icc(b: *mut ce_batch, ref_index: u32, pixels: *const c_void, len: usize, format: c_int, depth: u32,
                                       icc: *const ce_icc) -> c_int;
     pub fn ce_batch_set_test_icc(b: *mut ce_batch, pair_index: u32, ref_index: u32, pixels: *const c_void, len: usize, format: c_int,

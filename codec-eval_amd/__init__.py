@@ -153,6 +153,17 @@ class CeIccDescription(C.Structure):
                 ("curves", CeIccCurve * 3), ("reason", C.c_char * 96)]
 
 
+class CeIccLutDescription(C.Structure):
+    _fields_ = [("kind", C.c_int), ("version", C.c_uint32), ("profile_class", C.c_uint32), ("pcs", C.c_uint32), ("tag", C.c_uint32),
+                ("tag_type", C.c_uint32), ("tag_offset", C.c_uint32), ("tag_size", C.c_uint32), ("stages", C.c_uint32), ("grid", C.c_uint32 * 3),
+                ("precision", C.c_uint32), ("clut_offset", C.c_uint32), ("matrix", C.c_int32 * 12), ("a", CeIccCurve * 3), ("m", CeIccCurve * 3),
+                ("b", CeIccCurve * 3), ("reason", C.c_char * 96)]
+
+
+class CeIccLutCurve(C.Structure):
+    _fields_ = [("kind", C.c_int), ("ftype", C.c_uint32), ("count", C.c_uint32), ("first_sample", C.c_uint32), ("q", C.c_double * 7)]
+
+
 class CeHdrScores(C.Structure):
     _fields_ = [("pq_psnr", C.c_double), ("delta_e_itp_mean", C.c_double), ("delta_e_itp_max", C.c_double),
                 ("pq_sse", C.c_uint64), ("itp_sum_q20", C.c_uint64), ("itp_max_q20", C.c_uint64)]
@@ -304,6 +315,13 @@ _PROTOTYPES = [
     ("ce_icc_build_tables", _i, [_vp, _sz, _u32, _vp, _sz]),
     ("ce_srgb_encode_thresholds", _i, [_u32, _vp, _sz]),
     ("ce_icc_create", _i, [_vp, _vp, _sz, C.POINTER(_vp)]),
+    ("ce_icc_lut_describe", _i, [_vp, _sz, _i, C.POINTER(CeIccLutDescription)]),
+    ("ce_icc_lut_build_input_tables", _i, [_vp, _sz, _i, _u32, _vp, _sz]),
+    ("ce_icc_lut_build_clut", _i, [_vp, _sz, _i, _vp, _sz]),
+    ("ce_icc_lut_build_matrix", _i, [_vp, _sz, _i, _vp]),
+    ("ce_icc_lut_build_curves", _i, [_vp, _sz, _i, C.POINTER(CeIccLutCurve), _vp, _sz, C.POINTER(C.c_size_t)]),
+    ("ce_icc_lut_build_pcs_matrix", _i, [_vp]),
+    ("ce_icc_lut_create", _i, [_vp, _vp, _sz, _i, _i, C.POINTER(_vp)]),
     ("ce_icc_destroy", None, [_vp]),
     ("ce_batch_set_reference_icc", _i, [_vp, _u32, _vp, _sz, _i, _u32, _vp]),
     ("ce_batch_set_test_icc", _i, [_vp, _u32, _u32, _vp, _sz, _i, _u32, _vp]),
@@ -443,6 +461,121 @@ def icc_tables(profile: bytes, depth: int) -> np.ndarray:
     out = np.empty((3, 1 << depth if 0 < depth <= 16 else 1), np.float32)
     if lib().ce_icc_build_tables(b, len(b), depth, out.ctypes.data, out.size) != CE_OK:
         raise CodecEvalError(CE_ERR_INVALID_ARG, "ICC profile: " + (icc_describe(b).reason or f"depth {depth} or the table size"))
+    return out
+
+
+ICC_LUT_SUPPORTED, ICC_LUT_NOT_LUT, ICC_LUT_UNSUPPORTED, ICC_LUT_MALFORMED = 0, 1, 2, 3
+ICC_CLUT_TRILINEAR, ICC_CLUT_TETRAHEDRAL = 0, 1
+ICC_STAGE_A, ICC_STAGE_CLUT, ICC_STAGE_M, ICC_STAGE_MATRIX, ICC_STAGE_B = 1, 2, 4, 8, 16
+ICC_LUT_CURVE_IDENTITY, ICC_LUT_CURVE_SAMPLED, ICC_LUT_CURVE_POWER = 0, 1, 2
+
+
+@dataclass(frozen=True)
+class IccLutDescription:
+    """What the library's parser reads from a LUT-based ICC profile (ce_icc_lut_describe): kind 0 supported, 1 not LUT-based,
+    2 not RGB / a PCS, class or channel count not taken, 3 malformed, with the reason; the tag used, its type and the PCS as
+    four-character signatures; the ICC_STAGE_* present, the grid, the CLUT's bytes per sample, the matrix's integers and the A,
+    M and B curves (input and output tables for mft*: type 0 with u16, type 2 with u8 samples at `offset`)."""
+    kind: int
+    version: int
+    profile_class: int
+    pcs: bytes
+    tag: bytes
+    tag_type: bytes
+    tag_offset: int
+    tag_size: int
+    stages: int
+    grid: Tuple[int, ...]
+    precision: int
+    clut_offset: int
+    matrix: Tuple[int, ...]
+    a: Tuple[IccCurve, ...]
+    m: Tuple[IccCurve, ...]
+    b: Tuple[IccCurve, ...]
+    reason: str
+
+
+@dataclass(frozen=True)
+class IccLutCurve:
+    """A post-CLUT curve as the kernel takes it (ce_icc_lut_curve): kind 0 identity, 1 sampled (its float32 samples), 2 a power
+    (the para function type and g a b c d e f as floats)."""
+    kind: int
+    ftype: int
+    samples: Optional[np.ndarray]
+    q: Tuple[float, ...]
+
+
+def _sig(v: int) -> bytes:
+    return int(v).to_bytes(4, "big") if v else b""
+
+
+def icc_lut_describe(profile: bytes, intent: int = 0) -> IccLutDescription:
+    """ce_icc_lut_describe: a pure host function, usable with no GPU."""
+    b = bytes(profile)
+    d = CeIccLutDescription()
+    _host_check(lib().ce_icc_lut_describe(b, len(b), intent, C.byref(d)))
+    curves = lambda cs: tuple(IccCurve(c.type, c.count, tuple(c.params), c.offset) for c in cs)
+    return IccLutDescription(d.kind, d.version, d.profile_class, _sig(d.pcs), _sig(d.tag), _sig(d.tag_type), d.tag_offset, d.tag_size, d.stages,
+                             tuple(d.grid), d.precision, d.clut_offset, tuple(d.matrix), curves(d.a), curves(d.m), curves(d.b),
+                             d.reason.decode(errors="replace"))
+
+
+def _icc_lut_refused(b: bytes, intent: int, what: str) -> "CodecEvalError":
+    reason = icc_lut_describe(b, intent).reason if 0 <= intent <= 2 else ""
+    return CodecEvalError(CE_ERR_INVALID_ARG, "ICC profile: " + (reason or what))
+
+
+def icc_lut_input_tables(profile: bytes, depth: int, intent: int = 0) -> np.ndarray:
+    """The three input-side tables of a LUT-based profile at `depth` bits, [3, 2^depth] float32 (ce_icc_lut_build_input_tables)."""
+    b = bytes(profile)
+    out = np.empty((3, 1 << depth if 0 < depth <= 16 else 1), np.float32)
+    if lib().ce_icc_lut_build_input_tables(b, len(b), intent, depth, out.ctypes.data, out.size) != CE_OK:
+        raise _icc_lut_refused(b, intent, f"depth {depth} or the table size")
+    return out
+
+
+def icc_lut_clut(profile: bytes, intent: int = 0) -> Optional[np.ndarray]:
+    """The CLUT's nodes as the device holds them, [g0 * g1 * g2, 4] float32 with the fourth 0 (ce_icc_lut_build_clut); None for a
+    profile without a CLUT."""
+    b = bytes(profile)
+    d = icc_lut_describe(b, intent)
+    if d.kind != 0:
+        raise _icc_lut_refused(b, intent, "bad argument")
+    if not d.stages & ICC_STAGE_CLUT:
+        return None
+    out = np.empty((d.grid[0] * d.grid[1] * d.grid[2], 4), np.float32)
+    if lib().ce_icc_lut_build_clut(b, len(b), intent, out.ctypes.data, out.size) != CE_OK:
+        raise _icc_lut_refused(b, intent, "bad argument")
+    return out
+
+
+def icc_lut_matrix(profile: bytes, intent: int = 0) -> np.ndarray:
+    """The 12 float32 numbers of the mAB matrix, 3 x 3 row-major then the offsets (ce_icc_lut_build_matrix)."""
+    b = bytes(profile)
+    out = np.empty(12, np.float32)
+    if lib().ce_icc_lut_build_matrix(b, len(b), intent, out.ctypes.data) != CE_OK:
+        raise _icc_lut_refused(b, intent, "bad argument")
+    return out
+
+
+def icc_lut_curves(profile: bytes, intent: int = 0) -> Tuple[IccLutCurve, ...]:
+    """The six post-CLUT curves, M then B / output tables (ce_icc_lut_build_curves)."""
+    b = bytes(profile)
+    cs = (CeIccLutCurve * 6)()
+    needed = C.c_size_t()
+    rc = lib().ce_icc_lut_build_curves(b, len(b), intent, cs, None, 0, C.byref(needed))
+    if rc not in (CE_OK, CE_ERR_BAD_LENGTH):
+        raise _icc_lut_refused(b, intent, "bad argument")
+    samples = np.empty(needed.value, np.float32)
+    _host_check(lib().ce_icc_lut_build_curves(b, len(b), intent, cs, samples.ctypes.data, samples.size, C.byref(needed)))
+    return tuple(IccLutCurve(c.kind, c.ftype, samples[c.first_sample:c.first_sample + c.count].copy() if c.kind == ICC_LUT_CURVE_SAMPLED else None,
+                             tuple(c.q)) for c in cs)
+
+
+def icc_lut_pcs_matrix() -> np.ndarray:
+    """The 3 x 3 float32 matrix from PCS XYZ to linear light with sRGB primaries (ce_icc_lut_build_pcs_matrix)."""
+    out = np.empty((3, 3), np.float32)
+    _host_check(lib().ce_icc_lut_build_pcs_matrix(out.ctypes.data))
     return out
 
 
@@ -1471,6 +1604,19 @@ class IccProfile:
             self.close()
         except Exception:
             pass
+
+
+class IccLutProfile(IccProfile):
+    """A LUT-based ICC profile applied on the device (ce_icc_lut_create): an A2B tag of type mAB, mft2 or mft1, evaluated from
+    the profile itself - no CMS, no 2^24-entry table.  Accepted wherever an IccProfile is.  `intent` 0, 1 or 2 chooses A2B0 /
+    A2B1 / A2B2 (A2B0 where the other is absent); `interpolation` is ICC_CLUT_TRILINEAR or ICC_CLUT_TETRAHEDRAL.  Any other
+    profile raises CodecEvalError with the reason; `icc_lut_describe(profile).kind` tells which without raising."""
+
+    def __init__(self, ctx: "Context", profile: bytes, intent: int = 0, interpolation: int = ICC_CLUT_TRILINEAR):
+        b = bytes(profile)
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        ctx._check(lib().ce_icc_lut_create(ctx._h, b, len(b), intent, interpolation, C.byref(self._h)))
 
 
 class Batch:

@@ -638,6 +638,7 @@ int icc_check(ce_ctx *ctx, const void *pixels, size_t len, int format, uint32_t 
     if (depth_out)
         if (int rc = icc_thresholds_dev(ctx, depth_out, &plan->d_thr)) return rc;
     plan->d_tables = icc->d_tables[ce_icc_depth_index(depth)];
+    plan->lut = icc->lut;
     return CE_OK;
 }
 
@@ -1180,13 +1181,85 @@ int ce_icc_create(ce_ctx *ctx, const uint8_t *bytes, size_t len, ce_icc **out)
     return CE_OK;
 }
 
+// what both flavours of handle own
+static void icc_free(ce_icc *icc)
+{
+    for (float *t : icc->d_tables) hipFree(t);
+    if (icc->lut) {
+        hipFree(icc->lut->d_clut);
+        hipFree(icc->lut->d_samples);
+        delete icc->lut;
+    }
+    delete icc;
+}
+
 void ce_icc_destroy(ce_icc *icc)
 {
     if (!icc) return;
     hipSetDevice(icc->ctx->device);
     hipDeviceSynchronize();  // the batches' upload streams may still gather from the tables
-    for (float *t : icc->d_tables) hipFree(t);
-    delete icc;
+    icc_free(icc);
+}
+
+// LUT-based ICC profiles; the pure host functions are in ce_icc_lut.cpp
+int ce_icc_lut_create(ce_ctx *ctx, const uint8_t *bytes, size_t len, int intent, int interpolation, ce_icc **out)
+{
+    if (!ctx || !out) return CE_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (!bytes) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC profile: null pointer");
+    if (intent < 0 || intent > 2) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC profile: intent must be 0, 1 or 2, got " + std::to_string(intent));
+    if (interpolation != CE_ICC_CLUT_TRILINEAR && interpolation != CE_ICC_CLUT_TETRAHEDRAL)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC profile: interpolation must be CE_ICC_CLUT_TRILINEAR or CE_ICC_CLUT_TETRAHEDRAL");
+    ce_icc_lut_description d;
+    ce_icc_lut_describe(bytes, len, intent, &d);
+    if (d.kind != CE_ICC_LUT_SUPPORTED) {
+        static const char *const kKinds[4] = {"", "not a LUT-based profile", "a LUT-based profile of a kind not taken", "a malformed profile"};
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, std::string("ICC profile: ") + kKinds[d.kind & 3] + " (" + d.reason + ")");
+    }
+    ce_icc *icc = new ce_icc{ctx, {}, true, {}};
+    ce_icc_lut *lut = icc->lut = new ce_icc_lut{};
+    ce_icc_lut_build_pcs_matrix(icc->m);
+    lut->tetra = interpolation == CE_ICC_CLUT_TETRAHEDRAL;
+    lut->has_matrix = (d.stages & CE_ICC_STAGE_MATRIX) != 0;
+    ce_icc_lut_build_matrix(bytes, len, intent, lut->mat);
+    constexpr uint32_t kLab = 0x4c616220u, kMft2 = 0x6d667432u;  // 'Lab ', 'mft2'
+    lut->pcs = d.pcs != kLab ? 0u : d.tag_type == kMft2 ? 2u : 1u;
+    for (int k = 0; k < 3; k++) lut->grid[k] = d.grid[k];
+    // everything the kernel gathers from now (the input tables of all four depths, 0.85 MB; the CLUT, 16 bytes a node; the
+    // sampled curves): the handle is read-only from here on
+    int rc = hipSetDevice(ctx->device) == hipSuccess ? CE_OK : ce_fail(ctx, CE_ERR_BACKEND, "hipSetDevice failed (ICC profile)");
+    for (uint32_t depth : {8u, 10u, 12u, 16u}) {
+        if (rc != CE_OK) break;
+        std::vector<float> host((size_t)3 << depth);
+        ce_icc_lut_build_input_tables(bytes, len, intent, depth, host.data(), host.size());
+        void *p = nullptr;
+        rc = ce_device_table(ctx, host.data(), host.size() * sizeof(float), "ICC input tables", &p);
+        icc->d_tables[ce_icc_depth_index(depth)] = static_cast<float *>(p);
+    }
+    if (rc == CE_OK && (d.stages & CE_ICC_STAGE_CLUT)) {
+        std::vector<float> host((size_t)d.grid[0] * d.grid[1] * d.grid[2] * 4);
+        ce_icc_lut_build_clut(bytes, len, intent, host.data(), host.size());
+        void *p = nullptr;
+        rc = ce_device_table(ctx, host.data(), host.size() * sizeof(float), "ICC CLUT", &p);
+        lut->d_clut = static_cast<float *>(p);
+    }
+    if (rc == CE_OK) {
+        size_t needed = 0;
+        ce_icc_lut_build_curves(bytes, len, intent, lut->curves, nullptr, 0, &needed);
+        std::vector<float> host(needed);
+        ce_icc_lut_build_curves(bytes, len, intent, lut->curves, host.data(), host.size(), &needed);
+        if (needed) {
+            void *p = nullptr;
+            rc = ce_device_table(ctx, host.data(), host.size() * sizeof(float), "ICC curve samples", &p);
+            lut->d_samples = static_cast<float *>(p);
+        }
+    }
+    if (rc != CE_OK) {
+        icc_free(icc);
+        return rc;
+    }
+    *out = icc;
+    return CE_OK;
 }
 
 int ce_batch_set_reference_icc(ce_batch *b, uint32_t ref_index, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc)

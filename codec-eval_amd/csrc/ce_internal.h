@@ -325,11 +325,24 @@ struct ce_lut {
 // a matrix/TRC ICC profile on the device (ce_icc_create; ce_ingest.cpp): its matrix and the device copies of
 // ce_icc_build_tables for the four source depths 8, 10, 12 and 16, all made by ce_icc_create - nothing in the handle changes
 // after that - and kept until the handle goes
+struct ce_icc_lut;
 struct ce_icc {
     ce_ctx *ctx;
     float m[9];
     bool has_matrix;
     float *d_tables[4];  // [3][2^depth] floats each, by ce_icc_depth_index
+    ce_icc_lut *lut = nullptr;  // ce_icc_lut_create's handles: the rest of a LUT-based profile; m is then f32(inv(A))
+};
+// what a LUT-based profile adds to its input tables (ce_icc_lut_create), immutable like the rest
+struct ce_icc_lut {
+    bool tetra;              // CE_ICC_CLUT_TETRAHEDRAL
+    float *d_clut;           // [g0 * g1 * g2][4] floats, null without a CLUT
+    uint32_t grid[3];
+    float *d_samples;        // the samples of the SAMPLED curves, null without one
+    ce_icc_lut_curve curves[6];  // M then B, as ce_icc_lut_build_curves gives them
+    float mat[12];
+    bool has_matrix;
+    uint32_t pcs;            // 0 XYZ, 1 Lab, 2 Lab in the legacy 16-bit encoding
 };
 inline int ce_icc_depth_index(uint32_t depth) { return depth == 8 ? 0 : depth == 10 ? 1 : depth == 12 ? 2 : 3; }
 // one image of ce_upload_many
@@ -565,10 +578,13 @@ struct ce_icc_pixel {
     uint32_t depth_out = 0;
     bool out16 = false;
     const float *d_thr = nullptr;
+    const ce_icc_lut *lut = nullptr;  // a LUT-based profile: m is f32(inv(A)) and icc_lut.hip's launch takes the image
 };
 // n_pixels RGB(A) pixels of u8 / u16 samples at d_src (16-byte aligned staging; the four formats of ce_launch_tagged) ->
 // packed f32 RGB, or packed u8 / u16 sRGB code values, at d_dst, one launch (icc.hip)
 int ce_launch_icc(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, void *d_dst, size_t n_pixels, const ce_icc_pixel &px);
+// the same for px.lut != nullptr, which ce_launch_icc hands on (icc_lut.hip)
+int ce_launch_icc_lut(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, void *d_dst, size_t n_pixels, const ce_icc_pixel &px);
 
 // pairs [0, n_pairs) of a linear batch -> d_out[pair][3] = pq_sse, itp_sum_q20, itp_max_q20, cleared and filled on the
 // launching stream (hdr_fidelity.hip): d_table = T[1 .. maxv], 64-byte aligned, d_coarse the level staged in LDS (the table

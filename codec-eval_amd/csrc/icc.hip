@@ -44,6 +44,7 @@ void launch_format(ce_ctx *ctx, hipStream_t stream, const char *const (&names)[2
 int ce_launch_icc(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, void *d_dst, size_t n_pixels, const ce_icc_pixel &px)
 {
     if (n_pixels == 0) return CE_OK;
+    if (px.lut) return ce_launch_icc_lut(ctx, stream, format, d_src, d_dst, n_pixels, px);
     const size_t blocks = std::max<size_t>((n_pixels / 4 + kCicpBlock - 1) / kCicpBlock, 1);
     const bool integer = px.depth_out != 0;
     if (blocks > 0x7fffffffu || !px.d_tables || !d_src || !d_dst || (integer && !px.d_thr)) {

@@ -471,6 +471,14 @@ inline ce_icc_description icc_describe(const std::vector<uint8_t> &icc_profile)
     ce_icc_describe(icc_profile.data() ? icc_profile.data() : reinterpret_cast<const uint8_t *>(""), icc_profile.size(), &d);
     return d;
 }
+// what the parser of LUT-based profiles reads, without a device: kind CE_ICC_LUT_SUPPORTED for those the four-argument
+// constructor of HipIccProfile takes
+inline ce_icc_lut_description icc_lut_describe(const std::vector<uint8_t> &icc_profile, int intent = 0)
+{
+    ce_icc_lut_description d{};
+    ce_icc_lut_describe(icc_profile.data() ? icc_profile.data() : reinterpret_cast<const uint8_t *>(""), icc_profile.size(), intent, &d);
+    return d;
+}
 // A profile of three colorants and three tone curves on the device, parsed by the library itself (no Cms).  A LUT-based, Gray,
 // CMYK or malformed profile throws with the reason; those keep HipColorTable's route.
 class HipIccProfile {
@@ -478,6 +486,13 @@ public:
     HipIccProfile(const HipBackend &be, const std::vector<uint8_t> &icc_profile)
     {
         if (ce_icc_create(be.ctx(), icc_profile.data(), icc_profile.size(), &icc_) != CE_OK)
+            throw Error(Error::Kind::MetricCalculation, "Metric calculation failed: ICC: Failed to create ICC transform: " + be.last_error());
+    }
+    // a LUT-based profile (an A2B tag of type mAB, mft2 or mft1) evaluated from the profile itself: intent
+    // 0, 1 or 2 chooses A2B0 / A2B1 / A2B2, interpolation is CE_ICC_CLUT_TRILINEAR or CE_ICC_CLUT_TETRAHEDRAL
+    HipIccProfile(const HipBackend &be, const std::vector<uint8_t> &icc_profile, int intent, int interpolation)
+    {
+        if (ce_icc_lut_create(be.ctx(), icc_profile.data(), icc_profile.size(), intent, interpolation, &icc_) != CE_OK)
             throw Error(Error::Kind::MetricCalculation, "Metric calculation failed: ICC: Failed to create ICC transform: " + be.last_error());
     }
     ~HipIccProfile() { ce_icc_destroy(icc_); }

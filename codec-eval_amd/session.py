@@ -16,7 +16,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from . import (ColourDescription, GainMap, HlgDescription, DEEP_DEPTHS, PIXEL_RGB_F32, PIXEL_RGB8, PIXEL_RGB16, PIXEL_RGBA8, PIXEL_RGBA16, Batch, CodecEvalError, ColorTable, Context, IccProfile, icc_describe, DimensionMismatch, MetricCalculation,
+from . import (ColourDescription, GainMap, HlgDescription, DEEP_DEPTHS, PIXEL_RGB_F32, PIXEL_RGB8, PIXEL_RGB16, PIXEL_RGBA8, PIXEL_RGBA16, Batch, CodecEvalError, ColorTable, Context, IccLutProfile, IccProfile, icc_describe, icc_lut_describe, DimensionMismatch, MetricCalculation,
                MetricConfig, MetricResult, _error_obj, estimate_batch_bytes, CE_ERR_BACKEND)
 from . import RESAMPLE_LANCZOS3
 from . import CHROMA_TRIANGLE, MEM_HOST, YUV_400, YUV_420, YUV_444, YUV_BT601, YUV_FULL, YUV_PLANAR, YUV_SEMIPLANAR, YuvImage, yuv_coefficients
@@ -362,14 +362,20 @@ class EvalSession:
             self.ctx.close()
 
     def _profile_for(self, image: ImageData) -> Optional[IccProfile]:
-        """The device profile of a decoded image tagged with a matrix/TRC profile, in a session without a cms; None for
+        """The device profile of a decoded image tagged with a matrix/TRC profile or with a LUT-based one that
+        icc_lut_describe supports (its A2B0 tag, trilinear interpolation), in a session without a cms; None for
         an untagged image, a session with a cms (which applies every profile) and any other profile.  A profile is parsed
         once per session: the handle, or None for a profile the library does not take, is kept by the profile's bytes."""
         if image.icc_profile is None or self._cms is not None:
             return None
         key = bytes(image.icc_profile)
         if key not in self._profiles:
-            self._profiles[key] = IccProfile(self.ctx, key) if icc_describe(key).kind == 0 else None
+            if icc_describe(key).kind == 0:
+                self._profiles[key] = IccProfile(self.ctx, key)
+            elif icc_lut_describe(key).kind == 0:  # a LUT-based profile the library evaluates itself (DESIGN.md section 23)
+                self._profiles[key] = IccLutProfile(self.ctx, key)
+            else:
+                self._profiles[key] = None
         return self._profiles[key]
 
     def _table_for(self, image: ImageData) -> Optional[ColorTable]:

@@ -975,12 +975,13 @@ int ce_eval_pair_delta_e_itp_map(ce_ctx *ctx, const float *reference, size_t ref
  *      with srgb_eotf_f64 the curve of ce_srgb_table's rule 0: a search in a strictly increasing table (ce_srgb_encode_thresholds),
  *      NaN -> 0, out-of-gamut values clip.  The integer routes are the encode of the linear route and add no other arithmetic.
  * tests/icc_restatement.py restates this in numpy; the device equals it bit for bit.
- * Not part of this: LUT-based profiles (mAB, lut8, lut16), Gray and CMYK profiles, rendering intents, black-point
- * compensation, Y'CbCr planes with a profile, alpha compositing with a profile, ce_ref_* handles and the pooled ce_eval_batch. */
+ * Not part of this: LUT-based profiles (mAB, lut8, lut16: ce_icc_lut_create below takes those), Gray and CMYK profiles,
+ * rendering intents, black-point compensation, Y'CbCr planes with a profile, alpha compositing with a profile, ce_ref_*
+ * handles and the pooled ce_eval_batch. */
 #define CE_ICC_MAX_PROFILE_BYTES 4194304u
 #define CE_ICC_MAX_CURVE_POINTS 65536u
 enum { CE_ICC_SUPPORTED = 0, CE_ICC_LUT_BASED = 1, CE_ICC_NOT_RGB_XYZ = 2, CE_ICC_MALFORMED = 3 };
-enum { CE_ICC_CURVE_CURV = 0, CE_ICC_CURVE_PARA = 1 };
+enum { CE_ICC_CURVE_CURV = 0, CE_ICC_CURVE_PARA = 1, CE_ICC_CURVE_TABLE8 = 2 /* ce_icc_lut_describe only: count u8 samples at offset (mft1) */ };
 typedef struct ce_icc_curve {
     int type;          /* CE_ICC_CURVE_CURV or CE_ICC_CURVE_PARA */
     uint32_t count;    /* curv: the number of samples (0: identity, 1: a gamma); para: the function type 0 .. 4 */
@@ -1030,6 +1031,121 @@ int ce_icc_to_srgb8(ce_ctx *ctx, const void *pixels, size_t len, int format, uin
                     uint32_t h, uint8_t *out, size_t out_len);
 int ce_icc_to_srgb16(ce_ctx *ctx, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc, uint32_t w,
                      uint32_t h, uint32_t depth_out, uint16_t *out, size_t out_len);
+
+/* ---- LUT-based ICC profiles applied on the device ----------------------------------------------------
+ * transform_to_srgb (src/metrics/icc.rs:69-103) for the profiles whose transform is a table: an A2B tag of type `mAB `
+ * (lutAToBType), `mft2` (lut16) or `mft1` (lut8) - the jpegli XYB profile is one - evaluated from the profile itself, with
+ * no CMS on the host and no 2^24-entry table.  ce_icc_describe / ce_icc_create above keep answering CE_ICC_LUT_BASED for them.
+ * Accepted: ICC v2 and v4; `acsp`; data colour space `RGB `; PCS `XYZ ` or `Lab `; class `mntr`, `scnr` or `spac`; the tag
+ * A2B0, or with intent 1 / 2 the tag A2B1 / A2B2 where the profile has it and A2B0 otherwise; 3 input and 3 output channels.
+ *   mAB : B curves alone; M curves, the 3 x 4 matrix and B; A curves, the CLUT and B; or A, CLUT, M, matrix and B - what its
+ *         five offsets name must be one of these four, each curve sequence three `curv` / `para` elements padded to 4 bytes,
+ *         the CLUT of 1 or 2 bytes per sample with its own grid size per axis.
+ *   mft2, mft1: input tables (2 .. 4096 u16 entries; 256 u8 entries), the CLUT, output tables.  Their 3 x 3 matrix is read
+ *         and not applied: the format applies it to XYZ input only.  mft1 with PCS XYZ is refused: the format has no such.
+ * Every grid size lies in [2, 255] and the nodes number at most CE_ICC_MAX_CLUT_NODES; curves follow the rules of the
+ * matrix/TRC section (a = 0 in a type 1 or 2 para is malformed; a curv has at most CE_ICC_MAX_CURVE_POINTS samples); the
+ * profile is at most CE_ICC_MAX_PROFILE_BYTES long.  Every offset, count and size is checked in size_t against the tag, and
+ * the tag against the profile, before anything is read.
+ * Definition, per pixel of a CE_PIXEL_RGB8 / RGBA8 / RGB16 / RGBA16 image (alpha dropped) of source depth d, maxv = 2^d - 1.
+ * f32 unless stated, every product and sum rounded separately (no contraction), in the order written:
+ *   1. a_c = table_c[min(v_c, maxv)] (ce_icc_lut_build_input_tables): the A curve (mAB) or the input table (mft*, its samples
+ *      u16 / 65535 or u8 / 255 interpolated by the `curv n >= 2` rule above) in f64 at v / maxv, clipped to [0, 1], rounded once
+ *      to f32; v / maxv itself where the stage is absent.
+ *   2. With a CLUT of grid (g0, g1, g2), nodes N[i0][i1][i2][k] = f32(u16 / 65535) or f32(u8 / 255), the first channel's index
+ *      slowest: per axis p = a * f32(g - 1), i = min(floor(p), g - 2), f = p - f32(i), so the last node is reached with f = 1.
+ *      With cxyz the node at (i0 + x, i1 + y, i2 + z) and (fx, fy, fz) the three fractions, per output channel:
+ *      CE_ICC_CLUT_TRILINEAR: c00 = c000 + (c001 - c000) * fz, c01 = c010 + (c011 - c010) * fz, c10 and c11 likewise from
+ *        c100, c101 and c110, c111; c0 = c00 + (c01 - c00) * fy, c1 = c10 + (c11 - c10) * fy; v = c0 + (c1 - c0) * fx.
+ *      CE_ICC_CLUT_TETRAHEDRAL: v = ((c000 + (ca - c000) * hi) + (cb - ca) * mid) + (c111 - cb) * lo, where
+ *        fx >= fy: fy >= fz: (hi, mid, lo) = (fx, fy, fz), ca = c100, cb = c110;  else fx >= fz: (fx, fz, fy), c100, c101;
+ *                  else (fz, fx, fy), c001, c101;
+ *        fx <  fy: fx >= fz: (fy, fx, fz), c010, c110;  else fy >= fz: (fy, fz, fx), c010, c011;  else (fz, fy, fx), c001, c011.
+ *        A tie therefore goes to the earlier axis: fx = fy = fz walks c100, c110.  Where an output channel depends on one axis
+ *        alone both interpolations give c000 + (c1 - c000) * f of that axis, bit for bit; on an affine CLUT they agree
+ *        within rounding only.
+ *      Without a CLUT v = a.
+ *   3. mAB: the M curves, the matrix, the B curves; mft*: the output tables (as B).  A curve on x:
+ *        curv n = 0: x, unchanged and unclipped.  Every other curve first clips x to [0, 1] (NaN -> 0).
+ *        curv n >= 2, output table: samples s = f32(u16 / 65535) (f32(u8 / 255)), p = x * f32(n - 1), i = min(floor(p), n - 2),
+ *          s[i] + (s[i + 1] - s[i]) * (p - f32(i)).
+ *        curv n = 1, para: the formulas above in f64 on X = (double)x, the result clipped to [0, 1] (NaN -> 0) and rounded once
+ *          to f32.  The power B^g: B <= 0 or B < 2^-1022 is taken as 0, and 0^g is +inf for g < 0, 1 for g = 0, else 0.  With E
+ *          the unbiased binary exponent of B, |g| * (|E| + 1) > 1000 is not evaluated: the power is +inf where g * (E + 0.5) > 0
+ *          and 0 otherwise (exact to the clip for |g| <= 500; beyond that a base in [1/2, 2) is misjudged - no profile known
+ *          to us has such a curve).  Otherwise it is the fixed sequence of IEEE f64 operations the HLG and gain-map ingests
+ *          use (csrc/hlg_pixel.h: hlg_pow; tests/hlg_restatement.py), the same on the device and in the restatement.  Measured
+ *          against the host libm's pow over bases in [2^-40, 2] and twelve exponents from 1/3 to 3 (1e6 seeded bases and the
+ *          curves' own breakpoints): 2.2e-14 relative at most; bounded by 2.4e-14 (|g ln B| <= 83.2 there, one rounding of
+ *          which is 1.85e-14 of the result, on top of hlg_pow's own 5e-15).
+ *        matrix: m = f32(s15Fixed16 / 65536), y_i = ((m[i][0] * x0 + m[i][1] * x1) + m[i][2] * x2) + m[i][3].
+ *   4. PCS decode.  XYZ: X = v * f32(1 + 32767 / 32768).  Lab in mAB and mft1: L = 100 * v, a = 255 * v - 128, b likewise.
+ *      Lab in mft2, in a v2 and in a v4 profile alike (the legacy 16-bit encoding, which is what lcms2 decodes in both):
+ *      L = v * f32(65535 / 652.8), a = v * f32(65535 / 256) - 128.  Lab -> XYZ: fy = (L + 16) / 116, fx = fy + a / 500,
+ *      fz = fy - b / 200; t(f) = (f * f) * f for f > f32(6 / 29), else (f - f32(4 / 29)) * f32(108 / 841); X = f32(0xF6D6 / 65536)
+ *      * t(fx), Y = t(fy), Z = f32(0xD32D / 65536) * t(fz).
+ *   5. o_i = (M[i][0] * X + M[i][1] * Y) + M[i][2] * Z with M = f32(inv(A)), A and the inversion as in the matrix/TRC section
+ *      (ce_icc_lut_build_pcs_matrix).
+ *   6. the clamp of a linear image: the value a linear batch stores.  An RGB8 batch or a deep side stores its code by step 4 of
+ *      the matrix/TRC definition, unchanged.
+ * tests/icc_lut_restatement.py restates this in numpy; the device equals it bit for bit.
+ * Not part of this: Gray and CMYK profiles, mBA / B2A tags, multiProcessElements (D2B*), black-point compensation, Y'CbCr
+ * planes or alpha with a profile in one kernel, ce_ref_* handles and the pooled ce_eval_batch. */
+#define CE_ICC_MAX_CLUT_NODES 274625u /* 65^3: 4.4 MB on the device, a node being 16 bytes there */
+enum { CE_ICC_LUT_SUPPORTED = 0, CE_ICC_LUT_NOT_LUT = 1, CE_ICC_LUT_UNSUPPORTED = 2, CE_ICC_LUT_MALFORMED = 3 };
+enum { CE_ICC_CLUT_TRILINEAR = 0, CE_ICC_CLUT_TETRAHEDRAL = 1 };
+enum { CE_ICC_STAGE_A = 1, CE_ICC_STAGE_CLUT = 2, CE_ICC_STAGE_M = 4, CE_ICC_STAGE_MATRIX = 8, CE_ICC_STAGE_B = 16 };
+typedef struct ce_icc_lut_description {
+    int kind;               /* CE_ICC_LUT_SUPPORTED, _NOT_LUT (no A2B tag), _UNSUPPORTED (not RGB, a PCS other than XYZ / Lab, a
+                               class or a channel count not taken) or _MALFORMED; the fields below as far as parsing got */
+    uint32_t version;       /* header bytes 8 .. 11 */
+    uint32_t profile_class; /* signatures as big-endian numbers */
+    uint32_t pcs;           /* 'XYZ ' or 'Lab ' */
+    uint32_t tag;           /* the tag used: 'A2B0', 'A2B1' or 'A2B2' */
+    uint32_t tag_type;      /* 'mAB ', 'mft2' or 'mft1' */
+    uint32_t tag_offset, tag_size;
+    uint32_t stages;        /* CE_ICC_STAGE_* present; mft*: A (input tables), CLUT and B (output tables) */
+    uint32_t grid[3];       /* nodes per axis, the first input channel's first */
+    uint32_t precision;     /* bytes per CLUT sample: 1 or 2 */
+    uint32_t clut_offset;   /* where the first sample lies in the profile */
+    int32_t matrix[12];     /* mAB: e1 .. e12 as s15Fixed16 (3 x 3 row-major, then the three offsets); mft*: e1 .. e9, not applied */
+    ce_icc_curve a[3];      /* A curves / input tables (mft2: CURV with count entries at offset; mft1: TABLE8) */
+    ce_icc_curve m[3];      /* M curves */
+    ce_icc_curve b[3];      /* B curves / output tables */
+    char reason[96];        /* kind != 0: why, NUL-terminated */
+} ce_icc_lut_description;
+/* A post-CLUT curve as the kernel takes it (ce_icc_lut_build_curves) */
+enum { CE_ICC_LUT_CURVE_IDENTITY = 0, CE_ICC_LUT_CURVE_SAMPLED = 1, CE_ICC_LUT_CURVE_POWER = 2 };
+typedef struct ce_icc_lut_curve {
+    int kind;              /* CE_ICC_LUT_CURVE_* */
+    uint32_t ftype;        /* POWER: the para function type 0 .. 4 (curv n = 1: 0) */
+    uint32_t count;        /* SAMPLED: the number of samples */
+    uint32_t first_sample; /* SAMPLED: where they start in the samples array */
+    double q[7];           /* POWER: g a b c d e f */
+} ce_icc_lut_curve;
+/* Pure host functions; `intent` 0, 1 or 2 chooses the tag as above.  ce_icc_lut_describe returns CE_OK whenever `out` is filled
+ * (CE_ERR_INVALID_ARG for a null pointer or another intent).  The builders return CE_ERR_INVALID_ARG for a profile whose kind
+ * != 0, a bad depth or a wrong n, and give exactly what the kernel is handed:
+ *   input_tables: [3][2^depth] floats, n = 3 << depth.
+ *   clut: nodes padded to four floats, [g0 * g1 * g2][4] with the fourth 0, n = 4 * the node count; n = 0 and nothing written
+ *     for a profile without a CLUT.
+ *   matrix: the 12 floats of step 3 (3 x 3 row-major, then the offsets); the identity and 0 without the stage.
+ *   curves: out[0 .. 2] the M curves, out[3 .. 5] the B curves / output tables (IDENTITY where the stage is absent); the
+ *     samples of SAMPLED curves one after another in `samples`, n_samples floats of room; *needed = the floats they take
+ *     (call with samples = NULL, n_samples = 0 to learn it; CE_ERR_BAD_LENGTH when the room is less).
+ *   pcs_matrix: the 9 floats of step 5. */
+int ce_icc_lut_describe(const uint8_t *bytes, size_t len, int intent, ce_icc_lut_description *out);
+int ce_icc_lut_build_input_tables(const uint8_t *bytes, size_t len, int intent, uint32_t depth, float *out, size_t n);
+int ce_icc_lut_build_clut(const uint8_t *bytes, size_t len, int intent, float *out, size_t n);
+int ce_icc_lut_build_matrix(const uint8_t *bytes, size_t len, int intent, float out[12]);
+int ce_icc_lut_build_curves(const uint8_t *bytes, size_t len, int intent, ce_icc_lut_curve out[6], float *samples, size_t n_samples,
+                            size_t *needed);
+int ce_icc_lut_build_pcs_matrix(float out[9]);
+/* The same handle type as ce_icc_create's, for a LUT-based profile: the input tables of all four source depths, the CLUT and
+ * the sampled curves on the device, immutable afterwards; `interpolation` is CE_ICC_CLUT_TRILINEAR or _TETRAHEDRAL.  Every call
+ * that takes a ce_icc takes this one, with the same staging, stream, ordering, formats, depths and refusals.
+ * CE_ERR_INVALID_ARG with the reason in ce_last_error for a profile whose kind != 0, another intent or interpolation. */
+int ce_icc_lut_create(ce_ctx *ctx, const uint8_t *bytes, size_t len, int intent, int interpolation, ce_icc **out);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------ */
 /* Bracket every kernel launch with a HIP event pair, recorded on the stream the kernel is launched on,
