@@ -605,6 +605,41 @@ impl HipMetrics {
         Ok(out)
     }
 
+    /// `ce_cicp_over_to_linear`: `cicp_to_linear` of an RGBA image, blended in linear light over `background`.
+    pub fn cicp_over_to_linear(&mut self, pixels: &[u8], format: i32, colour: &sys::ce_colour, width: u32, height: u32, background: [f32; 3])
+                               -> Result<Vec<f32>, HipError> {
+        let mut out = vec![0f32; width as usize * height as usize * 3];
+        let rc = unsafe {
+            sys::ce_cicp_over_to_linear(self.ctx, pixels.as_ptr().cast(), pixels.len(), format, colour, width, height, background.as_ptr(),
+                                        out.as_mut_ptr(), out.len())
+        };
+        self.check(rc, width, height, pixels.len())?;
+        Ok(out)
+    }
+
+    /// `ce_hlg_over_to_linear`: `hlg_to_linear` of an RGBA image, blended in linear light over `background`.
+    pub fn hlg_over_to_linear(&mut self, pixels: &[u8], format: i32, hlg: &sys::ce_hlg, width: u32, height: u32, background: [f32; 3])
+                              -> Result<Vec<f32>, HipError> {
+        let mut out = vec![0f32; width as usize * height as usize * 3];
+        let rc = unsafe {
+            sys::ce_hlg_over_to_linear(self.ctx, pixels.as_ptr().cast(), pixels.len(), format, hlg, width, height, background.as_ptr(),
+                                       out.as_mut_ptr(), out.len())
+        };
+        self.check(rc, width, height, pixels.len())?;
+        Ok(out)
+    }
+
+    /// `ce_linear_over`: one float RGBA image in linear light, straight or premultiplied, over `background`.
+    pub fn linear_over(&mut self, rgba: &[f32], premultiplied: bool, width: u32, height: u32, background: [f32; 3]) -> Result<Vec<f32>, HipError> {
+        let mut out = vec![0f32; width as usize * height as usize * 3];
+        let rc = unsafe {
+            sys::ce_linear_over(self.ctx, rgba.as_ptr().cast(), rgba.len() * 4, sys::CE_PIXEL_RGBA_F32, premultiplied as i32, width, height,
+                                background.as_ptr(), out.as_mut_ptr(), out.len())
+        };
+        self.check(rc, width, height, rgba.len() * 4)?;
+        Ok(out)
+    }
+
     /// `ce_hlg_to_linear`: one image of BT.2100 HLG code values (`format`: `sys::CE_PIXEL_RGB8` / `RGBA8` / `RGB16` / `RGBA16`;
     /// `pixels` are its bytes) read by `hlg` - primaries, depth, the display's peak and system gamma, the white that becomes
     /// 1.0 - -> packed f32 RGB, display light with sRGB primaries.
@@ -757,6 +792,18 @@ impl<'a> HipIccProfile<'a> {
         Ok(Self { owner, handle })
     }
 
+    /// `ce_icc_over_to_linear`: `to_linear` of an RGBA image, blended in linear light over `background`.
+    pub fn over_to_linear(&self, pixels: &[u8], format: i32, depth: u32, width: u32, height: u32, background: [f32; 3])
+                          -> Result<Vec<f32>, HipError> {
+        let mut out = vec![0f32; width as usize * height as usize * 3];
+        let rc = unsafe {
+            sys::ce_icc_over_to_linear(self.owner.ctx, pixels.as_ptr().cast(), pixels.len(), format, depth, self.handle, width, height,
+                                       background.as_ptr(), out.as_mut_ptr(), out.len())
+        };
+        self.owner.check(rc, width, height, pixels.len())?;
+        Ok(out)
+    }
+
     /// `ce_icc_to_linear`: one image (`format` and `pixels` as `hlg_to_linear`, samples of `depth` bits) -> packed f32 RGB,
     /// linear light with sRGB primaries.
     pub fn to_linear(&self, pixels: &[u8], format: i32, depth: u32, width: u32, height: u32) -> Result<Vec<f32>, HipError> {
@@ -845,6 +892,101 @@ impl HipBatch<'_> {
                                         backgrounds.len() as u32, backgrounds.as_ptr().cast())
         };
         self.check(rc, pixels.len())
+    }
+
+    /// `ce_batch_set_reference_cicp_over`: one straight-alpha RGBA image of tagged code values (`format`:
+    /// `sys::CE_PIXEL_RGBA8` / `RGBA16`; `pixels` are its bytes) turned into linear light and blended there over each of
+    /// `backgrounds` (linear light, sRGB primaries) into reference slots `first_ref ..` of a linear batch.
+    pub fn set_reference_cicp_over(&mut self, first_ref: u32, pixels: &[u8], format: i32, colour: &sys::ce_colour, backgrounds: &[[f32; 3]])
+                                   -> Result<(), HipError> {
+        let rc = unsafe {
+            sys::ce_batch_set_reference_cicp_over(self.handle, first_ref, pixels.as_ptr().cast(), pixels.len(), format, colour,
+                                                  backgrounds.len() as u32, backgrounds.as_ptr().cast())
+        };
+        self.check(rc, pixels.len())
+    }
+
+    /// `ce_batch_set_test_cicp_over`: the same into test slots `first_pair ..`, pair `first_pair + k` bound to `ref_indices[k]`.
+    pub fn set_test_cicp_over(&mut self, first_pair: u32, ref_indices: &[u32], pixels: &[u8], format: i32, colour: &sys::ce_colour,
+                              backgrounds: &[[f32; 3]]) -> Result<(), HipError> {
+        self.one_ref_per_background(ref_indices, backgrounds)?;
+        let rc = unsafe {
+            sys::ce_batch_set_test_cicp_over(self.handle, first_pair, ref_indices.as_ptr(), pixels.as_ptr().cast(), pixels.len(), format,
+                                             colour, backgrounds.len() as u32, backgrounds.as_ptr().cast())
+        };
+        self.check(rc, pixels.len())
+    }
+
+    /// `ce_batch_set_reference_hlg_over`: the same for BT.2100 HLG code values read by `hlg`.
+    pub fn set_reference_hlg_over(&mut self, first_ref: u32, pixels: &[u8], format: i32, hlg: &sys::ce_hlg, backgrounds: &[[f32; 3]])
+                                  -> Result<(), HipError> {
+        let rc = unsafe {
+            sys::ce_batch_set_reference_hlg_over(self.handle, first_ref, pixels.as_ptr().cast(), pixels.len(), format, hlg,
+                                                 backgrounds.len() as u32, backgrounds.as_ptr().cast())
+        };
+        self.check(rc, pixels.len())
+    }
+
+    /// `ce_batch_set_test_hlg_over`
+    pub fn set_test_hlg_over(&mut self, first_pair: u32, ref_indices: &[u32], pixels: &[u8], format: i32, hlg: &sys::ce_hlg,
+                             backgrounds: &[[f32; 3]]) -> Result<(), HipError> {
+        self.one_ref_per_background(ref_indices, backgrounds)?;
+        let rc = unsafe {
+            sys::ce_batch_set_test_hlg_over(self.handle, first_pair, ref_indices.as_ptr(), pixels.as_ptr().cast(), pixels.len(), format, hlg,
+                                            backgrounds.len() as u32, backgrounds.as_ptr().cast())
+        };
+        self.check(rc, pixels.len())
+    }
+
+    /// `ce_batch_set_reference_icc_over`: the same for code values of `depth` bits read through either flavour of profile.
+    pub fn set_reference_icc_over(&mut self, first_ref: u32, pixels: &[u8], format: i32, depth: u32, icc: &HipIccProfile<'_>,
+                                  backgrounds: &[[f32; 3]]) -> Result<(), HipError> {
+        let rc = unsafe {
+            sys::ce_batch_set_reference_icc_over(self.handle, first_ref, pixels.as_ptr().cast(), pixels.len(), format, depth, icc.handle,
+                                                 backgrounds.len() as u32, backgrounds.as_ptr().cast())
+        };
+        self.check(rc, pixels.len())
+    }
+
+    /// `ce_batch_set_test_icc_over`
+    pub fn set_test_icc_over(&mut self, first_pair: u32, ref_indices: &[u32], pixels: &[u8], format: i32, depth: u32, icc: &HipIccProfile<'_>,
+                             backgrounds: &[[f32; 3]]) -> Result<(), HipError> {
+        self.one_ref_per_background(ref_indices, backgrounds)?;
+        let rc = unsafe {
+            sys::ce_batch_set_test_icc_over(self.handle, first_pair, ref_indices.as_ptr(), pixels.as_ptr().cast(), pixels.len(), format, depth,
+                                            icc.handle, backgrounds.len() as u32, backgrounds.as_ptr().cast())
+        };
+        self.check(rc, pixels.len())
+    }
+
+    /// `ce_batch_set_reference_linear_over`: float RGBA in linear light (`sys::CE_PIXEL_RGBA_F32`), straight or premultiplied.
+    pub fn set_reference_linear_over(&mut self, first_ref: u32, rgba: &[f32], premultiplied: bool, backgrounds: &[[f32; 3]])
+                                     -> Result<(), HipError> {
+        let len = rgba.len() * 4;
+        let rc = unsafe {
+            sys::ce_batch_set_reference_linear_over(self.handle, first_ref, rgba.as_ptr().cast(), len, sys::CE_PIXEL_RGBA_F32,
+                                                    premultiplied as i32, backgrounds.len() as u32, backgrounds.as_ptr().cast())
+        };
+        self.check(rc, len)
+    }
+
+    /// `ce_batch_set_test_linear_over`
+    pub fn set_test_linear_over(&mut self, first_pair: u32, ref_indices: &[u32], rgba: &[f32], premultiplied: bool, backgrounds: &[[f32; 3]])
+                                -> Result<(), HipError> {
+        self.one_ref_per_background(ref_indices, backgrounds)?;
+        let len = rgba.len() * 4;
+        let rc = unsafe {
+            sys::ce_batch_set_test_linear_over(self.handle, first_pair, ref_indices.as_ptr(), rgba.as_ptr().cast(), len, sys::CE_PIXEL_RGBA_F32,
+                                               premultiplied as i32, backgrounds.len() as u32, backgrounds.as_ptr().cast())
+        };
+        self.check(rc, len)
+    }
+
+    fn one_ref_per_background(&self, ref_indices: &[u32], backgrounds: &[[f32; 3]]) -> Result<(), HipError> {
+        if ref_indices.len() != backgrounds.len() {
+            return Err(HipError::MetricCalculation { metric: "hip".into(), reason: "one reference index per background".into() });
+        }
+        Ok(())
     }
 
     /// `ce_batch_set_reference_icc`: code values of `depth` bits (`format` and `pixels` as `hlg_to_linear`) read through a

@@ -49,6 +49,8 @@ pub const CE_PIXEL_RGB16: c_int = 4;
 pub const CE_PIXEL_RGBA16: c_int = 5;
 /// linear batches only (`ce_batch_create_linear`): packed f32 RGB, linear light with BT.709 / sRGB primaries
 pub const CE_PIXEL_RGB_F32: c_int = 7;
+/// packed float RGBA, 16 bytes per pixel, linear light: the `*_linear_over` calls only
+pub const CE_PIXEL_RGBA_F32: c_int = 8;
 /// `CE_LINEAR_MAX`: the clamp of a linear image's samples on ingest
 pub const CE_LINEAR_MAX: c_float = 1024.0;
 
@@ -498,6 +500,31 @@ extern "C" {
                            h: u32, out: *mut u8, out_len: usize) -> c_int;
     pub fn ce_icc_to_srgb16(ctx: *mut ce_ctx, pixels: *const c_void, len: usize, format: c_int, depth: u32, icc: *const ce_icc, w: u32,
                             h: u32, depth_out: u32, out: *mut u16, out_len: usize) -> c_int;
+    pub fn ce_alpha_table(depth: u32, out: *mut c_float, n: usize) -> c_int;
+    pub fn ce_batch_set_reference_cicp_over(b: *mut ce_batch, first_ref: u32, pixels: *const c_void, len: usize, format: c_int,
+                                            c: *const ce_colour, n_bg: u32, backgrounds: *const c_float) -> c_int;
+    pub fn ce_batch_set_test_cicp_over(b: *mut ce_batch, first_pair: u32, ref_indices: *const u32, pixels: *const c_void, len: usize,
+                                       format: c_int, c: *const ce_colour, n_bg: u32, backgrounds: *const c_float) -> c_int;
+    pub fn ce_batch_set_reference_hlg_over(b: *mut ce_batch, first_ref: u32, pixels: *const c_void, len: usize, format: c_int,
+                                           h: *const ce_hlg, n_bg: u32, backgrounds: *const c_float) -> c_int;
+    pub fn ce_batch_set_test_hlg_over(b: *mut ce_batch, first_pair: u32, ref_indices: *const u32, pixels: *const c_void, len: usize,
+                                      format: c_int, h: *const ce_hlg, n_bg: u32, backgrounds: *const c_float) -> c_int;
+    pub fn ce_batch_set_reference_icc_over(b: *mut ce_batch, first_ref: u32, pixels: *const c_void, len: usize, format: c_int, depth: u32,
+                                           icc: *const ce_icc, n_bg: u32, backgrounds: *const c_float) -> c_int;
+    pub fn ce_batch_set_test_icc_over(b: *mut ce_batch, first_pair: u32, ref_indices: *const u32, pixels: *const c_void, len: usize,
+                                      format: c_int, depth: u32, icc: *const ce_icc, n_bg: u32, backgrounds: *const c_float) -> c_int;
+    pub fn ce_batch_set_reference_linear_over(b: *mut ce_batch, first_ref: u32, pixels: *const c_void, len: usize, format: c_int,
+                                              premultiplied: c_int, n_bg: u32, backgrounds: *const c_float) -> c_int;
+    pub fn ce_batch_set_test_linear_over(b: *mut ce_batch, first_pair: u32, ref_indices: *const u32, pixels: *const c_void, len: usize,
+                                         format: c_int, premultiplied: c_int, n_bg: u32, backgrounds: *const c_float) -> c_int;
+    pub fn ce_cicp_over_to_linear(ctx: *mut ce_ctx, pixels: *const c_void, len: usize, format: c_int, c: *const ce_colour, w: u32, h: u32,
+                                  bg: *const c_float, out: *mut c_float, out_len: usize) -> c_int;
+    pub fn ce_hlg_over_to_linear(ctx: *mut ce_ctx, pixels: *const c_void, len: usize, format: c_int, hd: *const ce_hlg, w: u32, h: u32,
+                                 bg: *const c_float, out: *mut c_float, out_len: usize) -> c_int;
+    pub fn ce_icc_over_to_linear(ctx: *mut ce_ctx, pixels: *const c_void, len: usize, format: c_int, depth: u32, icc: *const ce_icc,
+                                 w: u32, h: u32, bg: *const c_float, out: *mut c_float, out_len: usize) -> c_int;
+    pub fn ce_linear_over(ctx: *mut ce_ctx, pixels: *const c_void, len: usize, format: c_int, premultiplied: c_int, w: u32, h: u32,
+                          bg: *const c_float, out: *mut c_float, out_len: usize) -> c_int;
     pub fn ce_prof_enable(ctx: *mut ce_ctx, on: c_int) -> c_int;
     pub fn ce_prof_filter(ctx: *mut ce_ctx, substring: *const c_char) -> c_int;
     pub fn ce_prof_reset(ctx: *mut ce_ctx) -> c_int;

@@ -37,6 +37,7 @@ FLAG_SSIMULACRA2_MAPS = 1 << 2
 PIXEL_RGB8, PIXEL_RGBA8, PIXEL_RGB16_10BIT, PIXEL_RGBA16_10BIT = 0, 1, 2, 3
 PIXEL_RGB16, PIXEL_RGBA16 = 4, 5  # deep batches only (Context.batch_deep): u16 samples at the side's own depth
 PIXEL_RGB_F32 = 7  # linear batches only (Context.batch_linear): packed float RGB, linear light with sRGB primaries
+PIXEL_RGBA_F32 = 8  # packed float RGBA, linear light: Batch.set_*_linear_over and Context.linear_over only
 LINEAR_MAX = 1024.0  # CE_LINEAR_MAX: the clamp of a linear image's samples on ingest
 DEEP_DEPTHS = (8, 10, 12, 16)
 # ITU-T H.273 code points the CICP ingest takes (include/ce_metrics.h)
@@ -58,6 +59,9 @@ CHROMA_NEAREST, CHROMA_TRIANGLE = 0, 1  # enum ce_chroma_upsample
 MEM_HOST, MEM_DEVICE = 0, 1  # enum ce_mem
 MAX_BACKGROUNDS = 8  # CE_MAX_BACKGROUNDS: solid colours one upload is composited over
 ALPHA_BLACK_WHITE = ((0, 0, 0), (255, 255, 255))  # the two page colours a transparent image is most often seen on, 8-bit
+# EvalConfig.alpha_blend: transparent images scored in linear light are blended over alpha_backgrounds THERE, after the pixel
+# has been turned into linear light (Batch.set_*_cicp_over and its kin)
+ALPHA_BLEND_LINEAR = "linear"
 
 _STATUS_NAMES = {
     CE_ERR_DIM_MISMATCH: "DimensionMismatch",
@@ -331,6 +335,19 @@ _PROTOTYPES = [
     ("ce_batch_set_reference_over", _i, [_vp, _u32, _vp, _sz, _i, _u32, _vp]),
     ("ce_batch_set_test_over", _i, [_vp, _u32, _vp, _vp, _sz, _i, _u32, _vp]),
     ("ce_composite_rgba8", _i, [_vp, _vp, _sz, _u32, _u32, _vp, _vp, _sz]),
+    ("ce_alpha_table", _i, [_u32, _vp, _sz]),
+    ("ce_batch_set_reference_cicp_over", _i, [_vp, _u32, _vp, _sz, _i, C.POINTER(CeColour), _u32, _vp]),
+    ("ce_batch_set_test_cicp_over", _i, [_vp, _u32, _vp, _vp, _sz, _i, C.POINTER(CeColour), _u32, _vp]),
+    ("ce_batch_set_reference_hlg_over", _i, [_vp, _u32, _vp, _sz, _i, C.POINTER(CeHlg), _u32, _vp]),
+    ("ce_batch_set_test_hlg_over", _i, [_vp, _u32, _vp, _vp, _sz, _i, C.POINTER(CeHlg), _u32, _vp]),
+    ("ce_batch_set_reference_icc_over", _i, [_vp, _u32, _vp, _sz, _i, _u32, _vp, _u32, _vp]),
+    ("ce_batch_set_test_icc_over", _i, [_vp, _u32, _vp, _vp, _sz, _i, _u32, _vp, _u32, _vp]),
+    ("ce_batch_set_reference_linear_over", _i, [_vp, _u32, _vp, _sz, _i, _i, _u32, _vp]),
+    ("ce_batch_set_test_linear_over", _i, [_vp, _u32, _vp, _vp, _sz, _i, _i, _u32, _vp]),
+    ("ce_cicp_over_to_linear", _i, [_vp, _vp, _sz, _i, C.POINTER(CeColour), _u32, _u32, _vp, _vp, _sz]),
+    ("ce_hlg_over_to_linear", _i, [_vp, _vp, _sz, _i, C.POINTER(CeHlg), _u32, _u32, _vp, _vp, _sz]),
+    ("ce_icc_over_to_linear", _i, [_vp, _vp, _sz, _i, _u32, _vp, _u32, _u32, _vp, _vp, _sz]),
+    ("ce_linear_over", _i, [_vp, _vp, _sz, _i, _i, _u32, _u32, _vp, _vp, _sz]),
     ("ce_composite_rgba16", _i, [_vp, _vp, _sz, _u32, _u32, _u32, _vp, _vp, _sz]),
     ("ce_prof_enable", _i, [_vp, _i]),
     ("ce_prof_filter", _i, [_vp, C.c_char_p]),
@@ -824,6 +841,28 @@ def composite_over(rgba, background: Sequence[int], depth: int = 8) -> np.ndarra
     v = np.minimum(a.astype(np.uint64), m)
     c, al = v[..., :3], v[..., 3:4]
     return ((c * al + bg * (m - al) + (m >> 1)) // m).astype(a.dtype)
+
+
+def alpha_table(depth: int) -> np.ndarray:
+    """The linear-light composite's coverage table of `depth` bits (ce_alpha_table): float32(k) / float32(2^depth - 1)."""
+    out = np.empty(1 << depth if 0 < depth <= 16 else 1, np.float32)
+    _host_check(lib().ce_alpha_table(depth, out.ctypes.data, out.size))
+    return out
+
+
+def _backgrounds_linear(backgrounds) -> np.ndarray:
+    """[n_bg][3] linear-light background colours as the contiguous float32 array the ABI takes"""
+    b = np.asarray(backgrounds, dtype=np.float32)
+    if b.ndim != 2 or b.shape[1] != 3:
+        raise ValueError("backgrounds are rows of three linear-light values")
+    return np.ascontiguousarray(b)
+
+
+def _rgba_f32(pixels) -> np.ndarray:
+    a = np.asarray(pixels)
+    if a.dtype != np.float32 or a.shape[-1] != 4:
+        raise TypeError("PIXEL_RGBA_F32 takes (..., 4) float32 samples")
+    return np.ascontiguousarray(a)
 
 
 def _backgrounds(backgrounds) -> np.ndarray:
@@ -1435,6 +1474,34 @@ class Context:
                                             out.size))
         return out
 
+    # the same leaves with alpha, blended in linear light over one background (include/ce_metrics.h: alpha in linear light)
+    def _over_leaf(self, call, a, width, height, background, *mid):
+        bg = _backgrounds_linear([background])
+        out = np.empty((height, width, 3), np.float32)
+        self._check(call(self._h, a.ctypes.data, a.nbytes, *mid, width, height, bg.ctypes.data, out.ctypes.data, out.size))
+        return out
+
+    def cicp_over_to_linear(self, pixels, width: int, height: int, colour: "ColourDescription", background) -> np.ndarray:
+        """cicp_to_linear of an RGBA image, blended in linear light over `background` (three linear-light floats, sRGB
+        primaries) on the device (ce_cicp_over_to_linear)."""
+        a, c = np.ascontiguousarray(pixels), colour._c()
+        return self._over_leaf(lib().ce_cicp_over_to_linear, a, width, height, background, _cicp_fmt(a), C.byref(c))
+
+    def hlg_over_to_linear(self, pixels, width: int, height: int, description: "HlgDescription", background) -> np.ndarray:
+        """hlg_to_linear of an RGBA image, blended in linear light over `background` (ce_hlg_over_to_linear)."""
+        a, c = np.ascontiguousarray(pixels), description._c()
+        return self._over_leaf(lib().ce_hlg_over_to_linear, a, width, height, background, _cicp_fmt(a), C.byref(c))
+
+    def icc_over_to_linear(self, pixels, width: int, height: int, depth: int, profile: "IccProfile", background) -> np.ndarray:
+        """icc_to_linear of an RGBA image, blended in linear light over `background` (ce_icc_over_to_linear)."""
+        a = np.ascontiguousarray(pixels)
+        return self._over_leaf(lib().ce_icc_over_to_linear, a, width, height, background, _cicp_fmt(a), depth, profile._h)
+
+    def linear_over(self, pixels, width: int, height: int, background, premultiplied: bool = False) -> np.ndarray:
+        """One (h, w, 4) float32 linear-light RGBA image, straight or premultiplied, over `background` (ce_linear_over)."""
+        a = _rgba_f32(pixels)
+        return self._over_leaf(lib().ce_linear_over, a, width, height, background, PIXEL_RGBA_F32, int(bool(premultiplied)))
+
     def icc_to_linear(self, pixels, width: int, height: int, depth: int, profile: "IccProfile") -> np.ndarray:
         """One image of uint8 / uint16 RGB(A) code values of `depth` bits read through a matrix/TRC profile -> [h, w, 3]
         float32 linear light with sRGB primaries, on the device (ce_icc_to_linear)."""
@@ -1778,6 +1845,51 @@ class Batch:
         self.ctx._check(lib().ce_batch_set_test_over(self._h, first_pair, refs.ctypes.data, a.ctypes.data, a.nbytes, fmt, len(bg), bg.ctypes.data))
         for k, r in enumerate(refs):
             self._pair_ref[first_pair + k] = int(r)
+
+    # an image with alpha turned into linear light and blended there over solid colours (include/ce_metrics.h: alpha in linear
+    # light): one upload fills len(backgrounds) consecutive slots of a linear batch; backgrounds are rows of three linear floats
+    def _set_over_linear(self, name, test, first, ref_indices, a, backgrounds, *mid):
+        bg = _backgrounds_linear(backgrounds)
+        if not test:
+            self.ctx._check(getattr(lib(), "ce_batch_set_reference_" + name)(self._h, first, a.ctypes.data, a.nbytes, *mid, len(bg), bg.ctypes.data))
+            return
+        refs = np.ascontiguousarray(ref_indices, dtype=np.uint32)
+        if refs.shape != (len(bg),):
+            raise ValueError("set_test_*_over takes one reference index per background")
+        self.ctx._check(getattr(lib(), "ce_batch_set_test_" + name)(self._h, first, refs.ctypes.data, a.ctypes.data, a.nbytes, *mid, len(bg),
+                                                                    bg.ctypes.data))
+        for k, r in enumerate(refs):
+            self._pair_ref[first + k] = int(r)
+
+    def set_reference_cicp_over(self, first_ref: int, pixels, colour: "ColourDescription", backgrounds):
+        a, c = np.ascontiguousarray(pixels), colour._c()
+        self._set_over_linear("cicp_over", False, first_ref, None, a, backgrounds, _cicp_fmt(a), C.byref(c))
+
+    def set_test_cicp_over(self, first_pair: int, ref_indices: Sequence[int], pixels, colour: "ColourDescription", backgrounds):
+        a, c = np.ascontiguousarray(pixels), colour._c()
+        self._set_over_linear("cicp_over", True, first_pair, ref_indices, a, backgrounds, _cicp_fmt(a), C.byref(c))
+
+    def set_reference_hlg_over(self, first_ref: int, pixels, description: "HlgDescription", backgrounds):
+        a, c = np.ascontiguousarray(pixels), description._c()
+        self._set_over_linear("hlg_over", False, first_ref, None, a, backgrounds, _cicp_fmt(a), C.byref(c))
+
+    def set_test_hlg_over(self, first_pair: int, ref_indices: Sequence[int], pixels, description: "HlgDescription", backgrounds):
+        a, c = np.ascontiguousarray(pixels), description._c()
+        self._set_over_linear("hlg_over", True, first_pair, ref_indices, a, backgrounds, _cicp_fmt(a), C.byref(c))
+
+    def set_reference_icc_over(self, first_ref: int, pixels, depth: int, profile: "IccProfile", backgrounds):
+        a = np.ascontiguousarray(pixels)
+        self._set_over_linear("icc_over", False, first_ref, None, a, backgrounds, _cicp_fmt(a), depth, profile._h)
+
+    def set_test_icc_over(self, first_pair: int, ref_indices: Sequence[int], pixels, depth: int, profile: "IccProfile", backgrounds):
+        a = np.ascontiguousarray(pixels)
+        self._set_over_linear("icc_over", True, first_pair, ref_indices, a, backgrounds, _cicp_fmt(a), depth, profile._h)
+
+    def set_reference_linear_over(self, first_ref: int, pixels, backgrounds, premultiplied: bool = False):
+        self._set_over_linear("linear_over", False, first_ref, None, _rgba_f32(pixels), backgrounds, PIXEL_RGBA_F32, int(bool(premultiplied)))
+
+    def set_test_linear_over(self, first_pair: int, ref_indices: Sequence[int], pixels, backgrounds, premultiplied: bool = False):
+        self._set_over_linear("linear_over", True, first_pair, ref_indices, _rgba_f32(pixels), backgrounds, PIXEL_RGBA_F32, int(bool(premultiplied)))
 
     # ... and through a colour table (ICC -> sRGB on the device)
     def set_reference_lut(self, ref_index: int, pixels, fmt: int, table: Optional["ColorTable"]):

@@ -429,6 +429,7 @@ void ce_ctx_destroy(ce_ctx *ctx)
     free_tables(ctx->cicp_tables);
     free_tables(ctx->hdr_tables);
     free_tables(ctx->icc_thresholds);
+    free_tables(ctx->alpha_tables);
     if (ctx->up2_stream) hipStreamSynchronize(ctx->up2_stream), hipStreamDestroy(ctx->up2_stream), hipEventDestroy(ctx->ev_up2);
     for (auto &st : ctx->aux_stream)  // after the last batch that may still drain them
         if (st) hipStreamSynchronize(st), hipStreamDestroy(st), st = nullptr;

@@ -1,5 +1,6 @@
 // Everything that writes a slot of a resident batch (include/ce_metrics.h: ce_batch_set_*, ce_batch_bind_pair, ce_lut_*),
-// the tables and the one-image leaves of the same conversions (ce_*_table, ce_*_to_linear, ce_yuv_to_rgb*, ce_composite_*).
+// the tables and the one-image leaves of the same conversions (ce_*_table, ce_*_to_linear, ce_yuv_to_rgb*, ce_composite_*,
+// ce_linear_over).
 // Three things live here once and every route goes through them: the ordering rule of slot writes (ce_order_write), the
 // wide staging pair (wide_acquire / wide_close) and the frame of a setter (set_slot).  A route adds its check, which fills
 // its plan, and its write.  All device work is in the .hip files.
@@ -201,14 +202,14 @@ namespace {
 // fills h_wide[k], queues the copy to d_wide[k] and its launch on up_stream, and closes the pair.
 //
 // wide_acquire hands out the next pair, ordered as a slot write and free of its previous image.  A pair holds 8 bytes per
-// pixel, the widest decoder format (12 on a linear batch: packed f32 RGB).
+// pixel, the widest decoder format (16 on a linear batch: packed f32 RGBA, which the linear-light composite takes).
 int wide_acquire(ce_batch *b, int *k_out)
 {
     ce_ctx *ctx = b->ctx;
     const int k = b->next_wide;
     b->next_wide ^= 1;
     if (!b->h_wide[k]) {
-        const size_t cap = (size_t)b->w * b->h * (b->linear ? 12 : 8);
+        const size_t cap = (size_t)b->w * b->h * (b->linear ? 16 : 8);
         CE_HIP(ctx, hipHostMalloc((void **)&b->h_wide[k], cap, hipHostMallocDefault));
         CE_HIP(ctx, hipMalloc((void **)&b->d_wide[k], cap));
         CE_HIP(ctx, hipEventCreateWithFlags(&b->ev_wide[k], hipEventDisableTiming));
@@ -952,6 +953,164 @@ int composite_to_host(ce_ctx *ctx, const void *rgba, size_t len, uint32_t w, uin
     });
 }
 
+// ---- alpha in linear light: blended over solid backgrounds behind the pixel (over_linear_kernel.h) -------
+
+// ce_alpha_table: atab[k] = float32(k) / float32(m), one correctly rounded f32 division each
+void build_alpha_table(uint32_t depth, float *out)
+{
+    const uint32_t m = (1u << depth) - 1u;
+    const float fm = (float)m;
+    for (uint32_t k = 0; k <= m; k++) out[k] = (float)k / fm;
+}
+
+// the device copy of the alpha table of a source depth (ce_ctx::alpha_tables)
+int alpha_table_dev(ce_ctx *ctx, uint32_t depth, const float **out)
+{
+    auto it = ctx->alpha_tables.find(depth);
+    if (it == ctx->alpha_tables.end()) {
+        std::vector<float> host((size_t)1 << depth);
+        build_alpha_table(depth, host.data());
+        CE_HIP(ctx, hipSetDevice(ctx->device));
+        void *d = nullptr;
+        if (int rc = ce_device_table(ctx, host.data(), host.size() * sizeof(float), "alpha table", &d)) return rc;
+        it = ctx->alpha_tables.emplace(depth, static_cast<float *>(d)).first;
+    }
+    *out = it->second;
+    return CE_OK;
+}
+
+// n_bg and the backgrounds of a linear-light composite, into the plan
+int over_backgrounds(ce_ctx *ctx, uint32_t n_bg, const float *backgrounds, ce_over_plan *ov)
+{
+    if (!backgrounds) return ce_fail(ctx, CE_ERR_INVALID_ARG, "linear-light compositing: null pointer");
+    if (n_bg == 0 || n_bg > CE_MAX_BACKGROUNDS)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "linear-light compositing: 1 to " + std::to_string(CE_MAX_BACKGROUNDS) + " backgrounds, got " + std::to_string(n_bg));
+    for (uint32_t i = 0; i < 3 * n_bg; i++) {
+        if (!std::isfinite(backgrounds[i]) || std::fabs(backgrounds[i]) > CE_LINEAR_MAX)
+            return ce_fail(ctx, CE_ERR_INVALID_ARG, "linear-light compositing: a background must be finite and within +-" + std::to_string((int)CE_LINEAR_MAX));
+        ov->bg[i / 3][i % 3] = backgrounds[i];
+    }
+    ov->n_bg = n_bg;
+    return CE_OK;
+}
+
+const char *const kOverWantsLinear = "linear-light compositing writes linear light: it needs a linear batch (ce_batch_create_linear)";
+
+int over_format_check(ce_ctx *ctx, int format)
+{
+    if (format != CE_PIXEL_RGBA8 && format != CE_PIXEL_RGBA16)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "linear-light compositing: the format must be CE_PIXEL_RGBA8 or CE_PIXEL_RGBA16");
+    return CE_OK;
+}
+
+// Every ce_batch_set_*_*_over call: set_over's frame - n_bg consecutive slots from `first` on, the test slots bound to
+// ref_indices[] - around a route's check(ov), which holds its own refusals and fills its plan and the alpha table, and its
+// launch(d_src, d_dst, ov) behind the copy of the `len` bytes at `pixels` through the wide staging pair.
+template <class Check, class Launch>
+int set_over_linear(ce_batch *b, bool test, uint32_t first, const uint32_t *ref_indices, const void *pixels, size_t len, uint32_t n_bg,
+                    const float *backgrounds, Check check, Launch launch)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    ce_ctx *ctx = b->ctx;
+    if (!b->linear) return ce_fail(ctx, CE_ERR_INVALID_ARG, kOverWantsLinear);
+    if ((test && !ref_indices) || !pixels || !backgrounds) return ce_fail(ctx, CE_ERR_INVALID_ARG, "linear-light compositing: null pointer");
+    ce_over_plan ov;
+    if (int rc = check(&ov)) return rc;
+    if (int rc = over_backgrounds(ctx, n_bg, backgrounds, &ov)) return rc;
+    const uint32_t slots = test ? b->max_pairs : b->max_refs;
+    if (first > slots || n_bg > slots - first)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, std::string("linear-light compositing: ") + (test ? "test" : "reference") + " slots [" + std::to_string(first) +
+                                                    ", " + std::to_string((uint64_t)first + n_bg) + ") outside the " + std::to_string(slots) + " slots");
+    for (uint32_t k = 0; test && k < n_bg; k++)
+        if (ref_indices[k] >= b->max_refs)
+            return ce_fail(ctx, CE_ERR_INVALID_ARG, "linear-light compositing: ref index " + std::to_string(ref_indices[k]) + " out of range");
+    for (uint32_t k = 0; test && k < n_bg; k++)
+        if (int rc = ce_batch_bind_pair(b, first + k, ref_indices[k])) return rc;
+    if (!test) ce_invalidate_reference_state(b);
+    ov.slot_floats = (size_t)b->w * b->h * 3;
+    float *dst = reinterpret_cast<float *>((test ? b->d_tests : b->d_refs) + (size_t)first * b->img_bytes);
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    int k;
+    if (int rc = wide_acquire(b, &k)) return rc;
+    std::memcpy(b->h_wide[k], pixels, len);
+    CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], len, hipMemcpyHostToDevice, b->up_stream));
+    if (int rc = launch(b->up_stream, b->d_wide[k], dst, ov)) return rc;
+    return wide_close(b, k);
+}
+
+// One image over one background -> packed f32 RGB in host memory, through the leaf scratch on the context's stream
+template <class Check, class Launch>
+int over_to_linear(ce_ctx *ctx, const void *pixels, size_t len, uint32_t w, uint32_t h, const float bg[3], float *out, size_t out_len, Check check,
+                   Launch launch)
+{
+    if (!ctx) return CE_ERR_INVALID_ARG;
+    if (!pixels || !bg || !out) return ce_fail(ctx, CE_ERR_INVALID_ARG, "linear-light compositing: null pointer");
+    if (w == 0 || h == 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, "linear-light compositing: empty image");
+    const size_t n_px = (size_t)w * h;
+    ce_over_plan ov;
+    if (int rc = check(&ov)) return rc;
+    if (int rc = over_backgrounds(ctx, 1, bg, &ov)) return rc;
+    if (out_len != n_px * 3)
+        return ce_fail(ctx, CE_ERR_BAD_LENGTH, "linear-light compositing: out_len must be " + std::to_string(n_px * 3) + " floats, got " + std::to_string(out_len));
+    ov.slot_floats = n_px * 3;
+    return ce_leaf_roundtrip(ctx, pixels, len, out, n_px * 12,
+                             [&](uint8_t *d_in, uint8_t *d_out) { return launch(ctx->stream, d_in, reinterpret_cast<float *>(d_out), ov); });
+}
+
+// what ce_batch_set_*_cicp_over / _hlg_over and their leaves check: the format, then everything the plain call refuses
+template <class Desc>
+int tagged_over_check(ce_ctx *ctx, const void *pixels, size_t len, int format, const Desc *d, size_t n_px, ce_linear_pixel *plan, ce_over_plan *ov)
+{
+    if (!d) return ce_fail(ctx, CE_ERR_INVALID_ARG, std::string(words(d).name) + " ingest: null pointer");
+    if (int rc = over_format_check(ctx, format)) return rc;
+    if (int rc = tagged_check(ctx, pixels, len, format, d, n_px, plan)) return rc;
+    return alpha_table_dev(ctx, d->depth, &ov->d_atab);
+}
+
+template <class Desc>
+int set_tagged_over(ce_batch *b, bool test, uint32_t first, const uint32_t *ref_indices, const void *pixels, size_t len, int format, const Desc *d,
+                    uint32_t n_bg, const float *backgrounds)
+{
+    ce_linear_pixel plan;
+    return set_over_linear(
+        b, test, first, ref_indices, pixels, len, n_bg, backgrounds,
+        [&](ce_over_plan *ov) { return tagged_over_check(b->ctx, pixels, len, format, d, (size_t)b->w * b->h, &plan, ov); },
+        [&](hipStream_t s, const uint8_t *d_src, float *d_dst, const ce_over_plan &ov) {
+            return ce_launch_tagged_over(b->ctx, s, format, d_src, d_dst, (size_t)b->w * b->h, plan, ov);
+        });
+}
+
+template <class Desc>
+int tagged_over_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, const Desc *d, uint32_t w, uint32_t h, const float bg[3], float *out,
+                          size_t out_len)
+{
+    ce_linear_pixel plan;
+    const size_t n_px = (size_t)w * h;
+    return over_to_linear(
+        ctx, pixels, len, w, h, bg, out, out_len, [&](ce_over_plan *ov) { return tagged_over_check(ctx, pixels, len, format, d, n_px, &plan, ov); },
+        [&](hipStream_t s, const uint8_t *d_src, float *d_dst, const ce_over_plan &ov) {
+            return ce_launch_tagged_over(ctx, s, format, d_src, d_dst, n_px, plan, ov);
+        });
+}
+
+// ... ce_batch_set_*_icc_over and its leaf: the format, then everything ce_batch_set_*_icc refuses of a linear slot
+int icc_over_check(ce_ctx *ctx, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc, size_t n_px, ce_icc_pixel *plan,
+                   ce_over_plan *ov)
+{
+    if (!icc) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: null pointer");
+    if (int rc = over_format_check(ctx, format)) return rc;
+    if (int rc = icc_check(ctx, pixels, len, format, depth, icc, n_px, 0, false, true, plan)) return rc;
+    return alpha_table_dev(ctx, depth, &ov->d_atab);
+}
+
+// ... ce_batch_set_*_linear_over and its leaf
+int linear_over_check(ce_ctx *ctx, size_t len, int format, size_t n_px)
+{
+    if (format != CE_PIXEL_RGBA_F32) return ce_fail(ctx, CE_ERR_INVALID_ARG, "linear-light compositing: the format must be CE_PIXEL_RGBA_F32");
+    if (len != n_px * 16) return ce_bad_length(ctx, n_px * 16, len);
+    return CE_OK;
+}
+
 }  // namespace
 
 // ---- the entry points -------------------------------------------------------------------------------------------------------
@@ -1350,6 +1509,109 @@ int ce_composite_rgba16(ce_ctx *ctx, const uint16_t *rgba, size_t len, uint32_t 
                         size_t out_len)
 {
     return composite_to_host(ctx, rgba, len, w, h, true, depth, bg, out, out_len);
+}
+
+// alpha in linear light
+int ce_alpha_table(uint32_t depth, float *out, size_t n)
+{
+    if (!out || !ce_deep_depth_ok(depth) || n != ((size_t)1 << depth))
+        return ce_fail(nullptr, CE_ERR_INVALID_ARG, "ce_alpha_table: depth 8, 10, 12 or 16 and n = 2^depth");
+    build_alpha_table(depth, out);
+    return CE_OK;
+}
+
+int ce_batch_set_reference_cicp_over(ce_batch *b, uint32_t first_ref, const void *pixels, size_t len, int format, const ce_colour *c, uint32_t n_bg,
+                                     const float *backgrounds)
+{
+    return set_tagged_over(b, false, first_ref, nullptr, pixels, len, format, c, n_bg, backgrounds);
+}
+int ce_batch_set_test_cicp_over(ce_batch *b, uint32_t first_pair, const uint32_t *ref_indices, const void *pixels, size_t len, int format,
+                                const ce_colour *c, uint32_t n_bg, const float *backgrounds)
+{
+    return set_tagged_over(b, true, first_pair, ref_indices, pixels, len, format, c, n_bg, backgrounds);
+}
+int ce_batch_set_reference_hlg_over(ce_batch *b, uint32_t first_ref, const void *pixels, size_t len, int format, const ce_hlg *h, uint32_t n_bg,
+                                    const float *backgrounds)
+{
+    return set_tagged_over(b, false, first_ref, nullptr, pixels, len, format, h, n_bg, backgrounds);
+}
+int ce_batch_set_test_hlg_over(ce_batch *b, uint32_t first_pair, const uint32_t *ref_indices, const void *pixels, size_t len, int format,
+                               const ce_hlg *h, uint32_t n_bg, const float *backgrounds)
+{
+    return set_tagged_over(b, true, first_pair, ref_indices, pixels, len, format, h, n_bg, backgrounds);
+}
+
+static int set_icc_over(ce_batch *b, bool test, uint32_t first, const uint32_t *ref_indices, const void *pixels, size_t len, int format, uint32_t depth,
+                        const ce_icc *icc, uint32_t n_bg, const float *backgrounds)
+{
+    ce_icc_pixel plan;
+    return set_over_linear(
+        b, test, first, ref_indices, pixels, len, n_bg, backgrounds,
+        [&](ce_over_plan *ov) { return icc_over_check(b->ctx, pixels, len, format, depth, icc, (size_t)b->w * b->h, &plan, ov); },
+        [&](hipStream_t s, const uint8_t *d_src, float *d_dst, const ce_over_plan &ov) {
+            return ce_launch_icc(b->ctx, s, format, d_src, d_dst, (size_t)b->w * b->h, plan, &ov);
+        });
+}
+int ce_batch_set_reference_icc_over(ce_batch *b, uint32_t first_ref, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc,
+                                    uint32_t n_bg, const float *backgrounds)
+{
+    return set_icc_over(b, false, first_ref, nullptr, pixels, len, format, depth, icc, n_bg, backgrounds);
+}
+int ce_batch_set_test_icc_over(ce_batch *b, uint32_t first_pair, const uint32_t *ref_indices, const void *pixels, size_t len, int format, uint32_t depth,
+                               const ce_icc *icc, uint32_t n_bg, const float *backgrounds)
+{
+    return set_icc_over(b, true, first_pair, ref_indices, pixels, len, format, depth, icc, n_bg, backgrounds);
+}
+
+static int set_linear_over(ce_batch *b, bool test, uint32_t first, const uint32_t *ref_indices, const void *pixels, size_t len, int format,
+                           int premultiplied, uint32_t n_bg, const float *backgrounds)
+{
+    return set_over_linear(
+        b, test, first, ref_indices, pixels, len, n_bg, backgrounds,
+        [&](ce_over_plan *) { return linear_over_check(b->ctx, len, format, (size_t)b->w * b->h); },
+        [&](hipStream_t s, const uint8_t *d_src, float *d_dst, const ce_over_plan &ov) {
+            return ce_launch_linear_over(b->ctx, s, reinterpret_cast<const float *>(d_src), d_dst, (size_t)b->w * b->h, premultiplied != 0, ov);
+        });
+}
+int ce_batch_set_reference_linear_over(ce_batch *b, uint32_t first_ref, const void *pixels, size_t len, int format, int premultiplied, uint32_t n_bg,
+                                       const float *backgrounds)
+{
+    return set_linear_over(b, false, first_ref, nullptr, pixels, len, format, premultiplied, n_bg, backgrounds);
+}
+int ce_batch_set_test_linear_over(ce_batch *b, uint32_t first_pair, const uint32_t *ref_indices, const void *pixels, size_t len, int format,
+                                  int premultiplied, uint32_t n_bg, const float *backgrounds)
+{
+    return set_linear_over(b, true, first_pair, ref_indices, pixels, len, format, premultiplied, n_bg, backgrounds);
+}
+
+int ce_cicp_over_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_colour *c, uint32_t w, uint32_t h, const float bg[3],
+                           float *out, size_t out_len)
+{
+    return tagged_over_to_linear(ctx, pixels, len, format, c, w, h, bg, out, out_len);
+}
+int ce_hlg_over_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_hlg *hd, uint32_t w, uint32_t h, const float bg[3],
+                          float *out, size_t out_len)
+{
+    return tagged_over_to_linear(ctx, pixels, len, format, hd, w, h, bg, out, out_len);
+}
+int ce_icc_over_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc, uint32_t w, uint32_t h,
+                          const float bg[3], float *out, size_t out_len)
+{
+    ce_icc_pixel plan;
+    const size_t n_px = (size_t)w * h;
+    return over_to_linear(
+        ctx, pixels, len, w, h, bg, out, out_len, [&](ce_over_plan *ov) { return icc_over_check(ctx, pixels, len, format, depth, icc, n_px, &plan, ov); },
+        [&](hipStream_t s, const uint8_t *d_src, float *d_dst, const ce_over_plan &ov) { return ce_launch_icc(ctx, s, format, d_src, d_dst, n_px, plan, &ov); });
+}
+int ce_linear_over(ce_ctx *ctx, const void *pixels, size_t len, int format, int premultiplied, uint32_t w, uint32_t h, const float bg[3], float *out,
+                   size_t out_len)
+{
+    const size_t n_px = (size_t)w * h;
+    return over_to_linear(
+        ctx, pixels, len, w, h, bg, out, out_len, [&](ce_over_plan *) { return linear_over_check(ctx, len, format, n_px); },
+        [&](hipStream_t s, const uint8_t *d_src, float *d_dst, const ce_over_plan &ov) {
+            return ce_launch_linear_over(ctx, s, reinterpret_cast<const float *>(d_src), d_dst, n_px, premultiplied != 0, ov);
+        });
 }
 
 }  // extern "C"

@@ -99,6 +99,9 @@ struct ce_ctx {
     // entry k = T[k] for k >= 1 (entry 0 is not read); built by the first such ingest and kept until the context goes
     // (ce_ingest.cpp: icc_thresholds_dev)
     std::map<uint32_t, float *> icc_thresholds;
+    // alpha tables of the linear-light composite (over_linear_kernel.h), keyed by the source depth: ce_alpha_table's 2^depth
+    // floats; built by the first such composite and kept until the context goes (ce_ingest.cpp: alpha_table_dev)
+    std::map<uint32_t, float *> alpha_tables;
 
     // profiling
     bool prof = false;         // record a HIP event pair around every launch (on the launch's own stream)
@@ -581,10 +584,41 @@ struct ce_icc_pixel {
     const ce_icc_lut *lut = nullptr;  // a LUT-based profile: m is f32(inv(A)) and icc_lut.hip's launch takes the image
 };
 // n_pixels RGB(A) pixels of u8 / u16 samples at d_src (16-byte aligned staging; the four formats of ce_launch_tagged) ->
-// packed f32 RGB, or packed u8 / u16 sRGB code values, at d_dst, one launch (icc.hip)
-int ce_launch_icc(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, void *d_dst, size_t n_pixels, const ce_icc_pixel &px);
+// packed f32 RGB, or packed u8 / u16 sRGB code values, at d_dst, one launch (icc.hip).  With `ov` (a linear slot, RGBA8 /
+// RGBA16 only): blended over ov->n_bg backgrounds into as many consecutive slots from d_dst on (ce_over_plan, below)
+struct ce_over_plan;
+int ce_launch_icc(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, void *d_dst, size_t n_pixels, const ce_icc_pixel &px,
+                  const ce_over_plan *ov = nullptr);
 // the same for px.lut != nullptr, which ce_launch_icc hands on (icc_lut.hip)
-int ce_launch_icc_lut(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, void *d_dst, size_t n_pixels, const ce_icc_pixel &px);
+int ce_launch_icc_lut(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, void *d_dst, size_t n_pixels, const ce_icc_pixel &px,
+                      const ce_over_plan *ov = nullptr);
+
+// What a linear-light composite blends with (checked and filled by ce_ingest.cpp: over_check): the
+// device alpha table of the source depth (ce_alpha_table; nullptr for CE_PIXEL_RGBA_F32, whose alpha is the coverage), the
+// checked backgrounds in linear light and the distance from one slot to the next in floats
+struct ce_over_plan {
+    const float *d_atab = nullptr;
+    uint32_t n_bg = 0;
+    float bg[CE_MAX_BACKGROUNDS][3] = {};
+    size_t slot_floats = 0;
+};
+// ce_launch_tagged's pixel on an RGBA8 / RGBA16 image, blended over ov.n_bg backgrounds into as many consecutive slots from
+// d_dst on, one launch (cicp.hip: over_linear_kernel.h's k_tagged_over)
+int ce_launch_tagged_over(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, float *d_dst, size_t n_pixels, const ce_linear_pixel &px,
+                          const ce_over_plan &ov);
+// (ce_launch_icc and ce_launch_icc_lut take the plan as their last argument: the ICC pixel of a linear slot in the same frame)
+// n_pixels CE_PIXEL_RGBA_F32 pixels at d_src (16-byte aligned staging), straight or premultiplied, over ov.n_bg backgrounds
+// (cicp.hip: k_linear_over)
+int ce_launch_linear_over(ce_ctx *ctx, hipStream_t stream, const float *d_src, float *d_dst, size_t n_pixels, bool premultiplied,
+                          const ce_over_plan &ov);
+// what the launchers put into over_linear_kernel.h's over_args
+template <class OverArgs>
+inline void ce_fill_over_args(OverArgs &o, const ce_over_plan &ov)
+{
+    o.atab = ov.d_atab, o.n_bg = ov.n_bg, o.slot_floats = ov.slot_floats;
+    for (uint32_t k = 0; k < CE_MAX_BACKGROUNDS; k++)
+        for (int c = 0; c < 3; c++) o.bg[k][c] = ov.bg[k][c];
+}
 
 // pairs [0, n_pairs) of a linear batch -> d_out[pair][3] = pq_sse, itp_sum_q20, itp_max_q20, cleared and filled on the
 // launching stream (hdr_fidelity.hip): d_table = T[1 .. maxv], 64-byte aligned, d_coarse the level staged in LDS (the table

@@ -19,6 +19,7 @@
 
 #include "cicp_kernel.h"
 #include "hlg_pixel.h"
+#include "over_linear_kernel.h"
 
 int ce_launch_linear_sanitise(ce_ctx *ctx, hipStream_t stream, const float *d_src, float *d_dst, size_t n_samples)
 {
@@ -80,6 +81,71 @@ int ce_launch_tagged(ce_ctx *ctx, hipStream_t stream, int format, const void *d_
         ctx->err = std::string(px.hlg ? "HLG" : "CICP") + " ingest: format must be RGB8, RGBA8, RGB16 or RGBA16";
         return CE_ERR_INVALID_ARG;
     }
+    CE_HIP(ctx, hipGetLastError());
+    return CE_OK;
+}
+
+// ---- the same pixels blended over solid backgrounds in linear light (over_linear_kernel.h) ----------------
+
+namespace {
+
+// [HLG][RGBA16][with the primaries matrix]
+constexpr const char *kOverNames[2][2][2] = {{{"cicp_over_rgba8", "cicp_over_rgba8_m"}, {"cicp_over_rgba16", "cicp_over_rgba16_m"}},
+                                             {{"hlg_over_rgba8", "hlg_over_rgba8_m"}, {"hlg_over_rgba16", "hlg_over_rgba16_m"}}};
+
+template <int FMT, template <bool> class Px, class Args>
+void launch_over_format(ce_ctx *ctx, hipStream_t stream, const char *const (&names)[2], dim3 grid, const Args &a, bool matrix, const over_args &o)
+{
+    if (matrix) CE_LAUNCH_ON(ctx, stream, names[1], (k_tagged_over<FMT, Px<true>>), grid, dim3(kCicpBlock), 0, Px<true>{a}, o);
+    else CE_LAUNCH_ON(ctx, stream, names[0], (k_tagged_over<FMT, Px<false>>), grid, dim3(kCicpBlock), 0, Px<false>{a}, o);
+}
+
+template <template <bool> class Px, class Args>
+void launch_over_pixel(ce_ctx *ctx, hipStream_t stream, bool wide, const char *const (&names)[2][2], dim3 grid, const Args &a, bool matrix,
+                       const over_args &o)
+{
+    if (wide) launch_over_format<CE_PIXEL_RGBA16, Px>(ctx, stream, names[1], grid, a, matrix, o);
+    else launch_over_format<CE_PIXEL_RGBA8, Px>(ctx, stream, names[0], grid, a, matrix, o);
+}
+
+}  // namespace
+
+int ce_launch_tagged_over(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, float *d_dst, size_t n_pixels, const ce_linear_pixel &px,
+                          const ce_over_plan &ov)
+{
+    if (n_pixels == 0) return CE_OK;
+    const size_t blocks = std::max<size_t>((n_pixels / 4 + kCicpBlock - 1) / kCicpBlock, 1);
+    if (blocks > 0x7fffffffu || !px.d_table || !ov.d_atab || ov.n_bg == 0 || ov.n_bg > CE_MAX_BACKGROUNDS ||
+        (format != CE_PIXEL_RGBA8 && format != CE_PIXEL_RGBA16)) {
+        ctx->err = px.hlg ? "HLG composite: bad launch" : "CICP composite: bad launch";
+        return CE_ERR_INVALID_ARG;
+    }
+    hlg_args a{};  // the CICP pixel takes its `c` alone
+    a.c.src = d_src, a.c.n_pixels = n_pixels;
+    ce_fill_pixel_args(a, d_dst, px);
+    over_args o{};
+    ce_fill_over_args(o, ov);
+    const dim3 grid((uint32_t)blocks);
+    if (px.hlg) launch_over_pixel<hlg_px>(ctx, stream, format == CE_PIXEL_RGBA16, kOverNames[1], grid, a, px.has_matrix, o);
+    else launch_over_pixel<cicp_px>(ctx, stream, format == CE_PIXEL_RGBA16, kOverNames[0], grid, a.c, px.has_matrix, o);
+    CE_HIP(ctx, hipGetLastError());
+    return CE_OK;
+}
+
+int ce_launch_linear_over(ce_ctx *ctx, hipStream_t stream, const float *d_src, float *d_dst, size_t n_pixels, bool premultiplied,
+                          const ce_over_plan &ov)
+{
+    if (n_pixels == 0) return CE_OK;
+    const size_t blocks = std::max<size_t>((n_pixels / 4 + kCicpBlock - 1) / kCicpBlock, 1);
+    if (blocks > 0x7fffffffu || ov.n_bg == 0 || ov.n_bg > CE_MAX_BACKGROUNDS) {
+        ctx->err = "linear composite: bad launch";
+        return CE_ERR_INVALID_ARG;
+    }
+    over_args o{};
+    ce_fill_over_args(o, ov);
+    const dim3 grid((uint32_t)blocks);
+    if (premultiplied) CE_LAUNCH_ON(ctx, stream, "linear_over_premul", k_linear_over<true>, grid, dim3(kCicpBlock), 0, d_src, d_dst, n_pixels, o);
+    else CE_LAUNCH_ON(ctx, stream, "linear_over", k_linear_over<false>, grid, dim3(kCicpBlock), 0, d_src, d_dst, n_pixels, o);
     CE_HIP(ctx, hipGetLastError());
     return CE_OK;
 }

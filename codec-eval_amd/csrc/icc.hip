@@ -12,6 +12,7 @@
 #include "ce_internal.h"
 
 #include "icc_kernel.h"
+#include "over_linear_kernel.h"
 
 namespace {
 
@@ -39,12 +40,28 @@ void launch_format(ce_ctx *ctx, hipStream_t stream, const char *const (&names)[2
     else launch_one<FMT, false>(ctx, stream, names[0], grid, a, kind, d_dst, d_thr, top);
 }
 
+// the pixel of a linear slot blended over solid backgrounds (over_linear_kernel.h): [RGBA16][with the matrix]
+constexpr const char *kIccOverNames[2][2] = {{"icc_over_rgba8", "icc_over_rgba8_m"}, {"icc_over_rgba16", "icc_over_rgba16_m"}};
+
+template <int FMT>
+void launch_over(ce_ctx *ctx, hipStream_t stream, const char *const (&names)[2], dim3 grid, const icc_args &a, bool matrix, const over_args &o)
+{
+    if (matrix) CE_LAUNCH_ON(ctx, stream, names[1], (k_tagged_over<FMT, icc_px<true>>), grid, dim3(kCicpBlock), 0, icc_px<true>{a}, o);
+    else CE_LAUNCH_ON(ctx, stream, names[0], (k_tagged_over<FMT, icc_px<false>>), grid, dim3(kCicpBlock), 0, icc_px<false>{a}, o);
+}
+
 }  // namespace
 
-int ce_launch_icc(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, void *d_dst, size_t n_pixels, const ce_icc_pixel &px)
+int ce_launch_icc(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, void *d_dst, size_t n_pixels, const ce_icc_pixel &px,
+                  const ce_over_plan *ov)
 {
     if (n_pixels == 0) return CE_OK;
-    if (px.lut) return ce_launch_icc_lut(ctx, stream, format, d_src, d_dst, n_pixels, px);
+    if (ov && (px.depth_out != 0 || !ov->d_atab || ov->n_bg == 0 || ov->n_bg > CE_MAX_BACKGROUNDS ||
+               (format != CE_PIXEL_RGBA8 && format != CE_PIXEL_RGBA16))) {
+        ctx->err = "ICC composite: bad launch";
+        return CE_ERR_INVALID_ARG;
+    }
+    if (px.lut) return ce_launch_icc_lut(ctx, stream, format, d_src, d_dst, n_pixels, px, ov);
     const size_t blocks = std::max<size_t>((n_pixels / 4 + kCicpBlock - 1) / kCicpBlock, 1);
     const bool integer = px.depth_out != 0;
     if (blocks > 0x7fffffffu || !px.d_tables || !d_src || !d_dst || (integer && !px.d_thr)) {
@@ -60,6 +77,14 @@ int ce_launch_icc(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src
     const int kind = !integer ? 0 : px.out16 ? 2 : 1;
     const uint32_t top = integer ? 1u << (px.depth_out - 1) : 0u;
     const dim3 grid((uint32_t)blocks);
+    if (ov) {
+        over_args o{};
+        ce_fill_over_args(o, *ov);
+        if (format == CE_PIXEL_RGBA16) launch_over<CE_PIXEL_RGBA16>(ctx, stream, kIccOverNames[1], grid, a, px.has_matrix, o);
+        else launch_over<CE_PIXEL_RGBA8>(ctx, stream, kIccOverNames[0], grid, a, px.has_matrix, o);
+        CE_HIP(ctx, hipGetLastError());
+        return CE_OK;
+    }
     switch (format) {
         case CE_PIXEL_RGB8: launch_format<CE_PIXEL_RGB8>(ctx, stream, kIccNames[kind][0], grid, a, px.has_matrix, kind, d_dst, px.d_thr, top); break;
         case CE_PIXEL_RGBA8: launch_format<CE_PIXEL_RGBA8>(ctx, stream, kIccNames[kind][1], grid, a, px.has_matrix, kind, d_dst, px.d_thr, top); break;

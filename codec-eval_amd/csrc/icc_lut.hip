@@ -12,6 +12,7 @@
 
 #include "icc_kernel.h"
 #include "icc_lut_pixel.h"
+#include "over_linear_kernel.h"
 
 namespace {
 
@@ -42,9 +43,20 @@ void launch_format(ce_ctx *ctx, hipStream_t stream, int f, dim3 grid, const icc_
     else launch_one<FMT, false>(ctx, stream, kIccLutNames[0][kind][f], grid, a, kind, d_dst, d_thr, top);
 }
 
+// the pixel of a linear slot blended over solid backgrounds (over_linear_kernel.h): [interpolation][RGBA16]
+constexpr const char *kIccLutOverNames[2][2] = {{"icc_lut_tri_over_rgba8", "icc_lut_tri_over_rgba16"}, {"icc_lut_tet_over_rgba8", "icc_lut_tet_over_rgba16"}};
+
+template <int FMT>
+void launch_over(ce_ctx *ctx, hipStream_t stream, int f, dim3 grid, const icc_lut_args &a, bool tetra, const over_args &o)
+{
+    if (tetra) CE_LAUNCH_ON(ctx, stream, kIccLutOverNames[1][f], (k_tagged_over<FMT, icc_lut_px<true>>), grid, dim3(kCicpBlock), 0, icc_lut_px<true>{a}, o);
+    else CE_LAUNCH_ON(ctx, stream, kIccLutOverNames[0][f], (k_tagged_over<FMT, icc_lut_px<false>>), grid, dim3(kCicpBlock), 0, icc_lut_px<false>{a}, o);
+}
+
 }  // namespace
 
-int ce_launch_icc_lut(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, void *d_dst, size_t n_pixels, const ce_icc_pixel &px)
+int ce_launch_icc_lut(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, void *d_dst, size_t n_pixels, const ce_icc_pixel &px,
+                      const ce_over_plan *ov)
 {
     if (n_pixels == 0) return CE_OK;
     const size_t blocks = std::max<size_t>((n_pixels / 4 + kCicpBlock - 1) / kCicpBlock, 1);
@@ -79,6 +91,14 @@ int ce_launch_icc_lut(ce_ctx *ctx, hipStream_t stream, int format, const void *d
     const int kind = !integer ? 0 : px.out16 ? 2 : 1;
     const uint32_t top = integer ? 1u << (px.depth_out - 1) : 0u;
     const dim3 grid((uint32_t)blocks);
+    if (ov) {  // ce_launch_icc has checked the plan, the format and the slot kind
+        over_args o{};
+        ce_fill_over_args(o, *ov);
+        if (format == CE_PIXEL_RGBA16) launch_over<CE_PIXEL_RGBA16>(ctx, stream, 1, grid, a, lut->tetra, o);
+        else launch_over<CE_PIXEL_RGBA8>(ctx, stream, 0, grid, a, lut->tetra, o);
+        CE_HIP(ctx, hipGetLastError());
+        return CE_OK;
+    }
     switch (format) {
         case CE_PIXEL_RGB8: launch_format<CE_PIXEL_RGB8>(ctx, stream, 0, grid, a, lut->tetra, kind, d_dst, px.d_thr, top); break;
         case CE_PIXEL_RGBA8: launch_format<CE_PIXEL_RGBA8>(ctx, stream, 1, grid, a, lut->tetra, kind, d_dst, px.d_thr, top); break;

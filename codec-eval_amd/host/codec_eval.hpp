@@ -740,6 +740,111 @@ inline void batch_set_test_over(const HipBackend &be, ce_batch *batch, uint32_t 
     detail::check(be, ce_batch_set_test_over(batch, first_pair, ref_indices.data(), pixels, len, format, (uint32_t)backgrounds.size(),
                                              backgrounds.empty() ? nullptr : backgrounds[0].data()), "alpha", 0, 0, len);
 }
+
+// ---- alpha in linear light: the pixel turned into linear light, then blended over solid colours ---------
+// o = (t == 1) ? v : (t == 0) ? bg : (v t) + (bg (1 - t)) in separately rounded f32; include/ce_metrics.h holds the definition
+using LinearBackground = std::array<float, 3>;  // linear light, sRGB primaries, finite and within +-CE_LINEAR_MAX
+inline std::vector<float> alpha_table(uint32_t depth)
+{
+    std::vector<float> out(depth <= 16 ? (size_t)1 << depth : 1);
+    if (ce_alpha_table(depth, out.data(), out.size()) != CE_OK) throw Error(Error::Kind::MetricCalculation, ce_last_error(nullptr));
+    return out;
+}
+inline const float *linear_bg_data(const std::vector<LinearBackground> &b) { return b.empty() ? nullptr : b[0].data(); }
+inline void one_ref_per_background(const std::vector<uint32_t> &refs, const std::vector<LinearBackground> &b)
+{
+    if (refs.size() != b.size()) throw Error(Error::Kind::MetricCalculation, "alpha: one reference index per background");
+}
+// one image over one background to packed float RGB in host memory
+inline std::vector<float> cicp_over_to_linear(const HipBackend &be, const void *pixels, size_t len, int format, const ColourDescription &colour,
+                                              uint32_t width, uint32_t height, const LinearBackground &background)
+{
+    std::vector<float> out((size_t)width * height * 3);
+    detail::check(be, ce_cicp_over_to_linear(be.ctx(), pixels, len, format, &colour, width, height, background.data(), out.data(), out.size()),
+                  "alpha", width, height, len);
+    return out;
+}
+inline std::vector<float> hlg_over_to_linear(const HipBackend &be, const void *pixels, size_t len, int format, const HlgDescription &hlg,
+                                             uint32_t width, uint32_t height, const LinearBackground &background)
+{
+    std::vector<float> out((size_t)width * height * 3);
+    detail::check(be, ce_hlg_over_to_linear(be.ctx(), pixels, len, format, &hlg, width, height, background.data(), out.data(), out.size()),
+                  "alpha", width, height, len);
+    return out;
+}
+inline std::vector<float> icc_over_to_linear(const HipBackend &be, const void *pixels, size_t len, int format, uint32_t depth,
+                                             const HipIccProfile &icc, uint32_t width, uint32_t height, const LinearBackground &background)
+{
+    std::vector<float> out((size_t)width * height * 3);
+    detail::check(be, ce_icc_over_to_linear(be.ctx(), pixels, len, format, depth, icc.get(), width, height, background.data(), out.data(), out.size()),
+                  "alpha", width, height, len);
+    return out;
+}
+inline std::vector<float> linear_over(const HipBackend &be, const std::vector<float> &rgba, bool premultiplied, uint32_t width, uint32_t height,
+                                      const LinearBackground &background)
+{
+    std::vector<float> out((size_t)width * height * 3);
+    detail::check(be, ce_linear_over(be.ctx(), rgba.data(), rgba.size() * sizeof(float), CE_PIXEL_RGBA_F32, premultiplied, width, height,
+                                     background.data(), out.data(), out.size()), "alpha", width, height, rgba.size() * sizeof(float));
+    return out;
+}
+// one upload into backgrounds.size() consecutive slots of a linear batch, slot k over backgrounds[k]
+inline void batch_set_reference_cicp_over(const HipBackend &be, ce_batch *batch, uint32_t first_ref, const void *pixels, size_t len, int format,
+                                          const ColourDescription &colour, const std::vector<LinearBackground> &backgrounds)
+{
+    detail::check(be, ce_batch_set_reference_cicp_over(batch, first_ref, pixels, len, format, &colour, (uint32_t)backgrounds.size(),
+                                                       linear_bg_data(backgrounds)), "alpha", 0, 0, len);
+}
+inline void batch_set_test_cicp_over(const HipBackend &be, ce_batch *batch, uint32_t first_pair, const std::vector<uint32_t> &ref_indices,
+                                     const void *pixels, size_t len, int format, const ColourDescription &colour,
+                                     const std::vector<LinearBackground> &backgrounds)
+{
+    one_ref_per_background(ref_indices, backgrounds);
+    detail::check(be, ce_batch_set_test_cicp_over(batch, first_pair, ref_indices.data(), pixels, len, format, &colour, (uint32_t)backgrounds.size(),
+                                                  linear_bg_data(backgrounds)), "alpha", 0, 0, len);
+}
+inline void batch_set_reference_hlg_over(const HipBackend &be, ce_batch *batch, uint32_t first_ref, const void *pixels, size_t len, int format,
+                                         const HlgDescription &hlg, const std::vector<LinearBackground> &backgrounds)
+{
+    detail::check(be, ce_batch_set_reference_hlg_over(batch, first_ref, pixels, len, format, &hlg, (uint32_t)backgrounds.size(),
+                                                      linear_bg_data(backgrounds)), "alpha", 0, 0, len);
+}
+inline void batch_set_test_hlg_over(const HipBackend &be, ce_batch *batch, uint32_t first_pair, const std::vector<uint32_t> &ref_indices,
+                                    const void *pixels, size_t len, int format, const HlgDescription &hlg,
+                                    const std::vector<LinearBackground> &backgrounds)
+{
+    one_ref_per_background(ref_indices, backgrounds);
+    detail::check(be, ce_batch_set_test_hlg_over(batch, first_pair, ref_indices.data(), pixels, len, format, &hlg, (uint32_t)backgrounds.size(),
+                                                 linear_bg_data(backgrounds)), "alpha", 0, 0, len);
+}
+inline void batch_set_reference_icc_over(const HipBackend &be, ce_batch *batch, uint32_t first_ref, const void *pixels, size_t len, int format,
+                                         uint32_t depth, const HipIccProfile &icc, const std::vector<LinearBackground> &backgrounds)
+{
+    detail::check(be, ce_batch_set_reference_icc_over(batch, first_ref, pixels, len, format, depth, icc.get(), (uint32_t)backgrounds.size(),
+                                                      linear_bg_data(backgrounds)), "alpha", 0, 0, len);
+}
+inline void batch_set_test_icc_over(const HipBackend &be, ce_batch *batch, uint32_t first_pair, const std::vector<uint32_t> &ref_indices,
+                                    const void *pixels, size_t len, int format, uint32_t depth, const HipIccProfile &icc,
+                                    const std::vector<LinearBackground> &backgrounds)
+{
+    one_ref_per_background(ref_indices, backgrounds);
+    detail::check(be, ce_batch_set_test_icc_over(batch, first_pair, ref_indices.data(), pixels, len, format, depth, icc.get(),
+                                                 (uint32_t)backgrounds.size(), linear_bg_data(backgrounds)), "alpha", 0, 0, len);
+}
+inline void batch_set_reference_linear_over(const HipBackend &be, ce_batch *batch, uint32_t first_ref, const std::vector<float> &rgba,
+                                            bool premultiplied, const std::vector<LinearBackground> &backgrounds)
+{
+    detail::check(be, ce_batch_set_reference_linear_over(batch, first_ref, rgba.data(), rgba.size() * sizeof(float), CE_PIXEL_RGBA_F32, premultiplied,
+                                                         (uint32_t)backgrounds.size(), linear_bg_data(backgrounds)), "alpha", 0, 0, rgba.size() * 4);
+}
+inline void batch_set_test_linear_over(const HipBackend &be, ce_batch *batch, uint32_t first_pair, const std::vector<uint32_t> &ref_indices,
+                                       const std::vector<float> &rgba, bool premultiplied, const std::vector<LinearBackground> &backgrounds)
+{
+    one_ref_per_background(ref_indices, backgrounds);
+    detail::check(be, ce_batch_set_test_linear_over(batch, first_pair, ref_indices.data(), rgba.data(), rgba.size() * sizeof(float), CE_PIXEL_RGBA_F32,
+                                                    premultiplied, (uint32_t)backgrounds.size(), linear_bg_data(backgrounds)), "alpha", 0, 0,
+                  rgba.size() * 4);
+}
 }  // namespace metrics
 
 namespace eval {

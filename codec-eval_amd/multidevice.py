@@ -180,6 +180,8 @@ class MultiDeviceEvalSession:
     images[i] and its rows are in the reference's loop order (session.rs:375-410)."""
 
     def __init__(self, config: EvalConfig, pool: Optional[DevicePool] = None, cms: Optional[Callable[[bytes, np.ndarray], np.ndarray]] = None):
+        if getattr(config, "alpha_blend", None) is not None:  # the linear-light composite runs on a device's batch (DESIGN.md section 24)
+            raise ValueError("MultiDeviceEvalSession does not take alpha_blend: linear-light blending is offered by EvalSession only")
         self.config = config
         self.pool = pool or DevicePool(cms=cms)
         self._own_pool = pool is None

@@ -20,11 +20,11 @@ from . import (ColourDescription, GainMap, HlgDescription, DEEP_DEPTHS, PIXEL_RG
                MetricConfig, MetricResult, _error_obj, estimate_batch_bytes, CE_ERR_BACKEND)
 from . import RESAMPLE_LANCZOS3
 from . import CHROMA_TRIANGLE, MEM_HOST, YUV_400, YUV_420, YUV_444, YUV_BT601, YUV_FULL, YUV_PLANAR, YUV_SEMIPLANAR, YuvImage, yuv_coefficients
-from . import ALPHA_BLACK_WHITE, MAX_BACKGROUNDS, composite_over, scale_background
+from . import ALPHA_BLACK_WHITE, ALPHA_BLEND_LINEAR, MAX_BACKGROUNDS, PIXEL_RGBA_F32, composite_over, scale_background, srgb_table
 from . import reports as R
 from .viewing import SimulationMode, ViewingCondition
 
-__all__ = ["ImageData", "EncodeRequest", "EvalConfig", "EvalConfigBuilder", "EvalSession", "ALPHA_BLACK_WHITE"]
+__all__ = ["ImageData", "EncodeRequest", "EvalConfig", "EvalConfigBuilder", "EvalSession", "ALPHA_BLACK_WHITE", "ALPHA_BLEND_LINEAR"]
 
 
 Colour = Union[ColourDescription, HlgDescription]  # what colour= takes: H.273 code points, or BT.2100 HLG with its display
@@ -66,6 +66,7 @@ class ImageData:
     # `data` is the SDR base of a gain-map image (Ultra HDR JPEG, gain-map AVIF / HEIC / JPEG XL) and this its map with the
     # metadata: the HDR rendition is scored, in linear light.  Not with an HlgDescription.
     gain_map: Optional[GainMap] = None
+    premultiplied: bool = False  # a linear RGBA image whose colour samples already hold colour * coverage
 
     @staticmethod
     def rgb(data, width: int, height: int, colour: Optional[Colour] = None, gain_map: Optional[GainMap] = None) -> "ImageData":
@@ -78,13 +79,18 @@ class ImageData:
                          gain_map=_gain_map_for(gain_map, colour, width, height))
 
     @staticmethod
-    def linear_f32(data, width: int, height: int) -> "ImageData":
+    def linear_f32(data, width: int, height: int, channels: int = 3, premultiplied: bool = False) -> "ImageData":
         """Packed float32 RGB in linear light with BT.709 / sRGB primaries, 1.0 = the white an 8-bit 255 maps to; values
-        below 0 and above 1 are scored.  A session scores it through a linear batch."""
+        below 0 and above 1 are scored.  A session scores it through a linear batch.  channels = 4: float RGBA, straight
+        or `premultiplied` alpha in [0, 1], which a session with alpha_blend blends over its alpha_backgrounds."""
+        if channels not in (3, 4):
+            raise ValueError(f"a linear image has 3 or 4 channels, got {channels}")
+        if premultiplied and channels != 4:
+            raise ValueError("premultiplied= is for a linear image with alpha (channels = 4)")
         a = np.ascontiguousarray(data, dtype=np.float32).reshape(-1)
-        if a.size != int(width) * int(height) * 3:
-            raise ValueError(f"a linear image is width * height * 3 floats, got {a.size}")
-        return ImageData(a, int(width), int(height), 3, linear=True)
+        if a.size != int(width) * int(height) * channels:
+            raise ValueError(f"a linear image is width * height * {channels} floats, got {a.size}")
+        return ImageData(a, int(width), int(height), int(channels), linear=True, premultiplied=bool(premultiplied))
 
     @staticmethod
     def rgb_with_icc(data, width: int, height: int, icc_profile: bytes) -> "ImageData":
@@ -218,7 +224,7 @@ class ImageData:
     @property
     def pixel_format(self) -> int:
         if self.linear:
-            return PIXEL_RGB_F32
+            return PIXEL_RGB_F32 if self.channels == 3 else PIXEL_RGBA_F32
         if self.depth:
             return PIXEL_RGB16 if self.channels == 3 else PIXEL_RGBA16
         return PIXEL_RGB8 if self.channels == 3 else PIXEL_RGBA8
@@ -255,6 +261,11 @@ class EvalConfig:  # session.rs:188-279
     # composited over each on the device (Batch.set_*_over) and scored over each; the row carries the
     # worst value per metric and the report keeps the per-background scores (ImageReport.alpha_scores).
     alpha_backgrounds: Optional[Sequence[Tuple[int, int, int]]] = None
+    # None: a pair scored in linear light (a colour description, HLG, float32, an ICC profile into a linear group) whose
+    # source or decode has alpha is refused under alpha_backgrounds, as ever.  ALPHA_BLEND_LINEAR: such a pair is blended
+    # over each background in linear light, after the pixel's own conversion (Batch.set_*_cicp_over / _hlg_over /
+    # _icc_over / _linear_over), and reported like a composited 8-bit pair.
+    alpha_blend: Optional[str] = None
 
     @staticmethod
     def builder() -> "EvalConfigBuilder":
@@ -264,7 +275,7 @@ class EvalConfig:  # session.rs:188-279
 class EvalConfigBuilder:
     def __init__(self):
         self._report_dir = self._cache_dir = self._viewing = self._metrics = self._levels = self._simulate = None
-        self._alpha = None
+        self._alpha = self._alpha_blend = None
 
     def report_dir(self, path):
         self._report_dir = str(path)
@@ -295,6 +306,14 @@ class EvalConfigBuilder:
         self._alpha = backgrounds
         return self
 
+    def alpha_blend(self, mode: Optional[str]):
+        """ALPHA_BLEND_LINEAR: blend transparent images that are scored in linear light over alpha_backgrounds there; None:
+        such pairs stay refused"""
+        if mode not in (None, ALPHA_BLEND_LINEAR):
+            raise ValueError(f"alpha_blend: None or ALPHA_BLEND_LINEAR, got {mode!r}")
+        self._alpha_blend = mode
+        return self
+
     def quality_levels(self, levels: Sequence[float]):
         self._levels = [float(q) for q in levels]
         return self
@@ -309,6 +328,7 @@ class EvalConfigBuilder:
             cfg.quality_levels = self._levels
         cfg.simulate_viewing = self._simulate
         cfg.alpha_backgrounds = self._alpha
+        cfg.alpha_blend = self._alpha_blend
         return cfg
 
 
@@ -517,6 +537,8 @@ class EvalSession:
             refuse("an ICC profile is not applied in linear light")
         if image.has_alpha and self.config.alpha_backgrounds:
             refuse("alpha_backgrounds with a colour description is not supported")
+        if image.linear and image.channels == 4:
+            refuse("a float RGBA image is blended over alpha_backgrounds: it needs both alpha_backgrounds and alpha_blend")
         if profile is not None:  # a matrix/TRC profile, no cms: the library's own transform, into linear light
             return batch.set_test_icc(pair_index, ref_index, image.data.reshape(image.height, image.width, image.channels), image.depth or 8, profile)
         if image.linear:
@@ -538,30 +560,73 @@ class EvalSession:
         else:
             batch.set_test_cicp(pair_index, ref_index, px, colour)
 
+    def _set_linear_over(self, batch: Batch, image: ImageData, first: int, ref_of: Optional[List[int]], bgs: np.ndarray):
+        """One image with alpha into len(bgs) consecutive slots of a linear batch from `first` on (the test slots bound to
+        ref_of), turned into linear light by _set_linear's route and blended there over each of bgs (alpha_blend)."""
+        def refuse(what):
+            raise MetricCalculation(CE_ERR_BACKEND, f"Metric calculation failed: linear-light scoring: {what}")
+        test = ref_of is not None
+        if image.gain_map is not None:
+            refuse("a gain-map image with alpha is not supported by alpha_blend")
+        if image.colour is not None and image.icc_profile is not None:
+            refuse("an image with both a colour description and an ICC profile is not supported")
+        profile = self._profile_for(image) if test and not image.linear else None
+        if image.icc_profile is not None and test and profile is None:  # the source's own profile is not applied, as ever
+            refuse("an ICC profile is not applied in linear light")
+        if image.linear:
+            px = image.data.reshape(image.height, image.width, 4)
+            if test:
+                return batch.set_test_linear_over(first, ref_of, px, bgs, premultiplied=image.premultiplied)
+            return batch.set_reference_linear_over(first, px, bgs, premultiplied=image.premultiplied)
+        px = image.data.reshape(image.height, image.width, image.channels)
+        if profile is not None:
+            return batch.set_test_icc_over(first, ref_of, px, image.depth or 8, profile, bgs)
+        colour = image.colour or ColourDescription.SRGB.with_depth(image.depth or 8)
+        if isinstance(colour, HlgDescription):
+            return batch.set_test_hlg_over(first, ref_of, px, colour, bgs) if test else batch.set_reference_hlg_over(first, px, colour, bgs)
+        return batch.set_test_cicp_over(first, ref_of, px, colour, bgs) if test else batch.set_reference_cicp_over(first, px, colour, bgs)
+
     def _score_cells_linear(self, w: int, h: int, group, cfg: MetricConfig):
         """The cells scored in linear light: one linear batch, a reference slot per image, a test slot
         per cell; PSNR is not defined there and stays None.  With simulate_viewing they are scored at the displayed size: the
         batch of the uploads is resampled in linear light into a linear batch of that shape."""
         if cfg.flags & 1:  # CE_FLAG_XYB_ROUNDTRIP
             raise MetricCalculation(CE_ERR_BACKEND, "Metric calculation failed: linear-light scoring: xyb_roundtrip is an 8-bit quantisation")
-        n_pairs = sum(len(p) for _, _, p in group)
-        batch = Batch(self.ctx, w, h, len(group), n_pairs, linear=True)
+        # with alpha_blend a pair whose source or decode has alpha is fanned over alpha_backgrounds exactly as _score_cells
+        # does it, the blend done in linear light; each 8-bit background goes through the sRGB curve once
+        bgs = (self.config.alpha_backgrounds or ()) if self.config.alpha_blend == ALPHA_BLEND_LINEAR else ()
+        bgs_lin = srgb_table(8, 0)[np.asarray(bgs, np.int64).reshape(-1, 3)] if bgs else None
+        fan = lambda image, decoded: len(bgs) if bgs and (image.has_alpha or decoded.has_alpha) else 1
+        n_refs = sum(len(bgs) if bgs and image.has_alpha else 1 for image, _, _ in group)
+        n_pairs = sum(fan(image, decoded) for image, _, p in group for _, decoded in p)
+        batch = Batch(self.ctx, w, h, n_refs, n_pairs, linear=True)
         try:
             rows = []
-            k = 0
-            for ri, (image, report, pending) in enumerate(group):
-                self._set_linear(batch, image, ri, None)
+            k = ri = 0
+            for image, report, pending in group:
+                if bgs and image.has_alpha:
+                    self._set_linear_over(batch, image, ri, None, bgs_lin)
+                    ref_of = list(range(ri, ri + len(bgs)))
+                else:
+                    self._set_linear(batch, image, ri, None)
+                    ref_of = [ri] * max(len(bgs), 1)
+                ri = ref_of[-1] + 1
                 for row_index, decoded in pending:
                     if (decoded.width, decoded.height) != (w, h):
                         raise DimensionMismatch(1, f"Dimension mismatch: expected ({w}, {h}), got ({decoded.width}, {decoded.height})")
-                    self._set_linear(batch, decoded, ri, k)
-                    rows.append((report, row_index, k))
-                    k += 1
+                    n = fan(image, decoded)
+                    if bgs and decoded.has_alpha:
+                        self._set_linear_over(batch, decoded, k, ref_of, bgs_lin)
+                    else:
+                        for j in range(n):  # an opaque decode against a source with alpha: the same image over every background
+                            self._set_linear(batch, decoded, ref_of[j], k + j)
+                    rows.append((report, row_index, k, n))
+                    k += n
             shown = self._displayed(w, h)
             if shown != (w, h):
-                dst = Batch(self.ctx, shown[0], shown[1], len(group), n_pairs, linear=True)
+                dst = Batch(self.ctx, shown[0], shown[1], n_refs, n_pairs, linear=True)
                 try:
-                    batch.resample_pairs_into(dst, len(group), n_pairs, self.config.resample_filter)
+                    batch.resample_pairs_into(dst, n_refs, n_pairs, self.config.resample_filter)
                     scores = dst.run(n_pairs, cfg)
                 finally:
                     dst.close()
@@ -569,13 +634,18 @@ class EvalSession:
                 scores = batch.run(n_pairs, cfg)
         finally:
             batch.close()
-        for report, row_index, k in rows:
-            if scores[k].status != 0:
-                raise _error_obj(scores[k].status, self.ctx._err())
-            m = MetricResult.from_c(scores[k])
+        for report, row_index, first, n in rows:
+            per_bg = []
+            for s in scores[first:first + n]:
+                if s.status != 0:
+                    raise _error_obj(s.status, self.ctx._err())
+                per_bg.append(MetricResult.from_c(s))
+            m = worst_over_backgrounds(per_bg)
             row = report.results[row_index]
             row.dssim, row.ssimulacra2, row.butteraugli, row.psnr = m.dssim, m.ssimulacra2, m.butteraugli, m.psnr
             row.perception = m.perception_level()
+            if n > 1:
+                report.alpha_scores[row_index] = per_bg
 
     def _score_cells(self, w: int, h: int, group, cfg: MetricConfig, depths: Optional[Tuple[int, int]]):
         # a pair whose source or decode has alpha takes one test slot per background (config.alpha_backgrounds); a source

@@ -630,6 +630,8 @@ int ce_composite_rgba16(ce_ctx *ctx, const uint16_t *rgba, size_t len, uint32_t 
  *   ce_batch_set_reference_yuv_cicp / ce_batch_set_test_yuv_cicp take Y'CbCr planes with such a tag (below);
  *   ce_batch_set_reference_hlg / ce_batch_set_test_hlg and their *_yuv_hlg forms take BT.2100 HLG (below);
  *   ce_batch_set_reference_gainmap / ce_batch_set_test_gainmap take an SDR base image with a gain map (below);
+ *   ce_batch_set_*_cicp_over / _hlg_over / _icc_over / _linear_over take an image with alpha and blend it over solid
+ *     backgrounds in linear light (the section "alpha in linear light" at the end of this header);
  *   ce_batch_bind_pair, ce_batch_run, ce_batch_launch, ce_batch_collect, ce_batch_butteraugli_pnorm3 and the three map
  *     readers work as on any batch;
  *   CE_ERR_INVALID_ARG, with the reason in ce_last_error and the batch still usable: CE_FLAG_XYB_ROUNDTRIP,
@@ -1146,6 +1148,74 @@ int ce_icc_lut_build_pcs_matrix(float out[9]);
  * that takes a ce_icc takes this one, with the same staging, stream, ordering, formats, depths and refusals.
  * CE_ERR_INVALID_ARG with the reason in ce_last_error for a profile whose kind != 0, another intent or interpolation. */
 int ce_icc_lut_create(ce_ctx *ctx, const uint8_t *bytes, size_t len, int intent, int interpolation, ce_icc **out);
+
+/* ---- alpha in linear light: transparent HDR and wide-gamut images over solid backgrounds ------------
+ * Every route into a linear batch above drops alpha, which brings back for transparent images the two faults that the alpha
+ * section removed for SDR: colour left under a = 0 is scored, damage to the alpha plane is not.  These calls blend instead,
+ * AFTER the pixel has been turned into linear light - the "linear-light blending" that the alpha section leaves out.  There
+ * the blend is physically meaningful and does not depend on the transfer the file happened to use: a 0 / 1 edge at half
+ * coverage gives 0.5 of the light, not code 128.  (Blending the encoded samples first is ce_composite_rgba* followed by the
+ * plain ingest.)
+ * Definition, per pixel of a CE_PIXEL_RGBA8 / CE_PIXEL_RGBA16 image of source depth d, m = 2^d - 1, STRAIGHT alpha; every
+ * product and sum is a separately rounded f32 operation (no fused multiply-add):
+ *   1. v[3] = the pixel of the plain call of the same kind on the three colour samples, its final clamp included: the CICP
+ *      definition, the HLG definition, the matrix/TRC or the LUT definition above, unchanged.
+ *   2. t = atab[min(a, m)] with atab[k] = float32(k) / float32(m), one correctly rounded f32 division, built on the host per
+ *      depth (ce_alpha_table); the device only gathers.  u = 1.0f - t, one f32 subtraction on the device.
+ *   3. over background k with linear colour bg[k][3], per channel: o = (t == 1) ? v : (t == 0) ? bg : (v * t) + (bg * u).
+ *      The two selects make an opaque pixel equal to the plain ingest on every bit, -0.0 included, and a hidden pixel equal
+ *      to the background on every bit.
+ *   4. the clamp of a linear image on o: NaN -> 0, then [-CE_LINEAR_MAX, CE_LINEAR_MAX].
+ * CE_PIXEL_RGBA_F32 is float RGBA, 16 bytes per pixel, linear light with sRGB primaries; only the *_linear_over calls below
+ * accept it (ce_batch_set_*_fmt refuses it).  v = the clamp of a linear image on each colour sample; t = alpha with NaN -> 0,
+ * then clamped to [0, 1]; u, the blend and the clamp as above.  With premultiplied != 0 the colour samples already hold
+ * colour * coverage and step 3 is o = (u == 0) ? v : v + (bg * u).
+ * backgrounds: float [n_bg][3], linear light with sRGB primaries, 1 <= n_bg <= CE_MAX_BACKGROUNDS, every value finite and
+ * within +-CE_LINEAR_MAX.  As in the alpha section one upload fills n_bg consecutive slots, slot k over backgrounds[k]; the
+ * pixel is read and converted once.  tests/alpha_linear_restatement.py restates this in numpy; the device equals it bit for
+ * bit.
+ * Not part of this: premultiplied integer formats, gain-map images with alpha, Y'CbCr planes with a separate alpha plane, ICC
+ * with alpha into RGB8 / deep slots, patterned backgrounds, device-resident sources, ce_ref_* handles and ce_eval_batch. */
+enum {
+    CE_PIXEL_RGBA_F32 = 8 /* packed float RGBA, 16 bytes per pixel, linear light: the *_linear_over calls only */
+};
+/* atab of `depth` bits (8, 10, 12 or 16; n = 2^depth entries).  A pure host function. */
+int ce_alpha_table(uint32_t depth, float *out, size_t n);
+/* ce_batch_set_*_cicp (the description, its formats with alpha, staging, upload stream and ordering) with ce_batch_set_*_over's
+ * slots: reference slots first_ref .. first_ref + n_bg - 1 / test slots first_pair .. first_pair + n_bg - 1, pair
+ * first_pair + k bound to reference ref_indices[k]; the pixels are consumed on return.  CE_ERR_INVALID_ARG, with the reason in
+ * ce_last_error and the batch still usable, for a batch that is not linear, a null handle or pointer, a format without alpha,
+ * every refusal of ce_batch_set_*_cicp, n_bg = 0 or n_bg > CE_MAX_BACKGROUNDS, a background that is not finite or beyond
+ * +-CE_LINEAR_MAX, a slot range or a ref_indices entry past the batch; CE_ERR_BAD_LENGTH for a wrong len. */
+int ce_batch_set_reference_cicp_over(ce_batch *b, uint32_t first_ref, const void *pixels, size_t len, int format, const ce_colour *c,
+                                     uint32_t n_bg, const float *backgrounds);
+int ce_batch_set_test_cicp_over(ce_batch *b, uint32_t first_pair, const uint32_t *ref_indices, const void *pixels, size_t len, int format,
+                                const ce_colour *c, uint32_t n_bg, const float *backgrounds);
+/* the same around ce_batch_set_*_hlg and its refusals */
+int ce_batch_set_reference_hlg_over(ce_batch *b, uint32_t first_ref, const void *pixels, size_t len, int format, const ce_hlg *h,
+                                    uint32_t n_bg, const float *backgrounds);
+int ce_batch_set_test_hlg_over(ce_batch *b, uint32_t first_pair, const uint32_t *ref_indices, const void *pixels, size_t len, int format,
+                               const ce_hlg *h, uint32_t n_bg, const float *backgrounds);
+/* the same around ce_batch_set_*_icc and its refusals, either flavour of handle; a linear batch only */
+int ce_batch_set_reference_icc_over(ce_batch *b, uint32_t first_ref, const void *pixels, size_t len, int format, uint32_t depth,
+                                    const ce_icc *icc, uint32_t n_bg, const float *backgrounds);
+int ce_batch_set_test_icc_over(ce_batch *b, uint32_t first_pair, const uint32_t *ref_indices, const void *pixels, size_t len, int format,
+                               uint32_t depth, const ce_icc *icc, uint32_t n_bg, const float *backgrounds);
+/* CE_PIXEL_RGBA_F32 (len = width * height * 16), straight or premultiplied; extends ce_batch_set_*_fmt(CE_PIXEL_RGB_F32) */
+int ce_batch_set_reference_linear_over(ce_batch *b, uint32_t first_ref, const void *pixels, size_t len, int format, int premultiplied,
+                                       uint32_t n_bg, const float *backgrounds);
+int ce_batch_set_test_linear_over(ce_batch *b, uint32_t first_pair, const uint32_t *ref_indices, const void *pixels, size_t len, int format,
+                                  int premultiplied, uint32_t n_bg, const float *backgrounds);
+/* One image of w x h over one background to packed float RGB in host memory (out_len = w * h * 3 floats): ce_cicp_to_linear,
+ * ce_hlg_to_linear, ce_icc_to_linear and the float upload with the blend.  Errors as above. */
+int ce_cicp_over_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_colour *c, uint32_t w, uint32_t h,
+                           const float bg[3], float *out, size_t out_len);
+int ce_hlg_over_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, const ce_hlg *hd, uint32_t w, uint32_t h,
+                          const float bg[3], float *out, size_t out_len);
+int ce_icc_over_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc, uint32_t w,
+                          uint32_t h, const float bg[3], float *out, size_t out_len);
+int ce_linear_over(ce_ctx *ctx, const void *pixels, size_t len, int format, int premultiplied, uint32_t w, uint32_t h, const float bg[3],
+                   float *out, size_t out_len);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------ */
 /* Bracket every kernel launch with a HIP event pair, recorded on the stream the kernel is launched on,
