@@ -1037,6 +1037,23 @@ impl HipBatch<'_> {
         self.check(rc, 0)
     }
 
+    /// `ce_batch_set_reference_yuv_icc`: a decoder's planes read through `icc` (either flavour of profile) into a reference slot
+    /// of any batch, in one kernel: linear light in a linear batch, sRGB code values of the slot's depth otherwise.  `rgb_depth`
+    /// (8, 10, 12 or 16, not under the planes' depth) is the integer RGB grid between the colour matrix and the profile.
+    pub fn set_reference_yuv_icc(&mut self, ref_index: u32, image: &YuvPlanes<'_>, rgb_depth: u32, icc: &HipIccProfile<'_>) -> Result<(), HipError> {
+        let c = image.to_sys(self.width, self.height)?;
+        let rc = unsafe { sys::ce_batch_set_reference_yuv_icc(self.handle, ref_index, &c, rgb_depth, icc.handle) };
+        self.check(rc, 0)
+    }
+
+    /// `ce_batch_set_test_yuv_icc`: the same for the test image of pair `pair_index`, bound to reference `ref_index`.
+    pub fn set_test_yuv_icc(&mut self, pair_index: u32, ref_index: u32, image: &YuvPlanes<'_>, rgb_depth: u32, icc: &HipIccProfile<'_>)
+                            -> Result<(), HipError> {
+        let c = image.to_sys(self.width, self.height)?;
+        let rc = unsafe { sys::ce_batch_set_test_yuv_icc(self.handle, pair_index, ref_index, &c, rgb_depth, icc.handle) };
+        self.check(rc, 0)
+    }
+
     /// `ce_batch_set_reference_hlg`: BT.2100 HLG code values (`format` and `pixels` as `hlg_to_linear`) into a reference slot
     /// of a LINEAR batch.
     pub fn set_reference_hlg(&mut self, ref_index: u32, pixels: &[u8], format: i32, hlg: &sys::ce_hlg) -> Result<(), HipError> {

@@ -433,6 +433,15 @@ extern "C" {
                                       c: *const ce_colour) -> c_int;
     pub fn ce_yuv_to_linear(ctx: *mut ce_ctx, image: *const ce_yuv_image, c: *const ce_colour, width: u32, height: u32, out: *mut c_float,
                             out_len: usize) -> c_int;
+    pub fn ce_batch_set_reference_yuv_icc(b: *mut ce_batch, ref_index: u32, image: *const ce_yuv_image, rgb_depth: u32, icc: *const ce_icc) -> c_int;
+    pub fn ce_batch_set_test_yuv_icc(b: *mut ce_batch, pair_index: u32, ref_index: u32, image: *const ce_yuv_image, rgb_depth: u32,
+                                     icc: *const ce_icc) -> c_int;
+    pub fn ce_yuv_icc_to_linear(ctx: *mut ce_ctx, image: *const ce_yuv_image, rgb_depth: u32, icc: *const ce_icc, width: u32, height: u32,
+                                out: *mut c_float, out_len: usize) -> c_int;
+    pub fn ce_yuv_icc_to_srgb8(ctx: *mut ce_ctx, image: *const ce_yuv_image, rgb_depth: u32, icc: *const ce_icc, width: u32, height: u32,
+                               out: *mut u8, out_len: usize) -> c_int;
+    pub fn ce_yuv_icc_to_srgb16(ctx: *mut ce_ctx, image: *const ce_yuv_image, rgb_depth: u32, icc: *const ce_icc, width: u32, height: u32,
+                                depth_out: u32, out: *mut u16, out_len: usize) -> c_int;
     pub fn ce_batch_set_reference_hlg(b: *mut ce_batch, ref_index: u32, pixels: *const c_void, len: usize, format: c_int,
                                       h: *const ce_hlg) -> c_int;
     pub fn ce_batch_set_test_hlg(b: *mut ce_batch, pair_index: u32, ref_index: u32, pixels: *const c_void, len: usize, format: c_int,

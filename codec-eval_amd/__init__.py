@@ -295,6 +295,11 @@ _PROTOTYPES = [
     ("ce_batch_set_reference_yuv_cicp", _i, [_vp, _u32, C.POINTER(CeYuvImage), C.POINTER(CeColour)]),
     ("ce_batch_set_test_yuv_cicp", _i, [_vp, _u32, _u32, C.POINTER(CeYuvImage), C.POINTER(CeColour)]),
     ("ce_yuv_to_linear", _i, [_vp, C.POINTER(CeYuvImage), C.POINTER(CeColour), _u32, _u32, _vp, _sz]),
+    ("ce_batch_set_reference_yuv_icc", _i, [_vp, _u32, C.POINTER(CeYuvImage), _u32, _vp]),
+    ("ce_batch_set_test_yuv_icc", _i, [_vp, _u32, _u32, C.POINTER(CeYuvImage), _u32, _vp]),
+    ("ce_yuv_icc_to_linear", _i, [_vp, C.POINTER(CeYuvImage), _u32, _vp, _u32, _u32, _vp, _sz]),
+    ("ce_yuv_icc_to_srgb8", _i, [_vp, C.POINTER(CeYuvImage), _u32, _vp, _u32, _u32, _vp, _sz]),
+    ("ce_yuv_icc_to_srgb16", _i, [_vp, C.POINTER(CeYuvImage), _u32, _vp, _u32, _u32, _u32, _vp, _sz]),
     ("ce_batch_set_reference_hlg", _i, [_vp, _u32, _vp, _sz, _i, C.POINTER(CeHlg)]),
     ("ce_batch_set_test_hlg", _i, [_vp, _u32, _u32, _vp, _sz, _i, C.POINTER(CeHlg)]),
     ("ce_hlg_to_linear", _i, [_vp, _vp, _sz, _i, C.POINTER(CeHlg), _u32, _u32, _vp, _sz]),
@@ -1391,6 +1396,29 @@ class Context:
         self._check(lib().ce_yuv_to_linear(self._h, C.byref(c), C.byref(col), width, height, out.ctypes.data, out.size))
         return out
 
+    def yuv_icc_to_linear(self, image: "YuvImage", width: int, height: int, rgb_depth: int, profile: "IccProfile") -> np.ndarray:
+        """A decoder's Y'CbCr planes read through an ICC profile of either flavour -> (height, width, 3) float32 linear light
+        with sRGB primaries, in one kernel (ce_yuv_icc_to_linear): yuv_to_rgb16 at depth_out = rgb_depth followed by
+        icc_to_linear at depth = rgb_depth, bit for bit.  rgb_depth: 8, 10, 12 or 16, not under the planes' depth."""
+        c, _keep = image._c()
+        out = np.empty((height, width, 3), np.float32)
+        self._check(lib().ce_yuv_icc_to_linear(self._h, C.byref(c), rgb_depth, profile._h if profile is not None else None, width, height,
+                                               out.ctypes.data, out.size))
+        return out
+
+    def yuv_icc_to_srgb(self, image: "YuvImage", width: int, height: int, rgb_depth: int, profile: "IccProfile", depth_out: int = 8) -> np.ndarray:
+        """The same planes as sRGB code values: (height, width, 3) uint8 (depth_out = 8, ce_yuv_icc_to_srgb8) or uint16 of
+        depth_out bits (10, 12 or 16, ce_yuv_icc_to_srgb16): yuv_to_rgb16 followed by icc_to_srgb, bit for bit."""
+        c, _keep = image._c()
+        h = profile._h if profile is not None else None
+        if depth_out == 8:
+            out = np.empty((height, width, 3), np.uint8)
+            self._check(lib().ce_yuv_icc_to_srgb8(self._h, C.byref(c), rgb_depth, h, width, height, out.ctypes.data, out.size))
+        else:
+            out = np.empty((height, width, 3), np.uint16)
+            self._check(lib().ce_yuv_icc_to_srgb16(self._h, C.byref(c), rgb_depth, h, width, height, depth_out, out.ctypes.data, out.size))
+        return out
+
     def composite_rgba8(self, rgba, width: int, height: int, background: Sequence[int]) -> np.ndarray:
         """Straight-alpha RGBA8 source-over onto the opaque 8-bit colour `background` -> (height, width, 3) uint8, on the
         device (ce_composite_rgba8; the definition is in include/ce_metrics.h)."""
@@ -1795,6 +1823,20 @@ class Batch:
         c, _keep = image._c()
         col = colour._c()
         self.ctx._check(lib().ce_batch_set_test_yuv_cicp(self._h, pair_index, ref_index, C.byref(c), C.byref(col)))
+        self._pair_ref[pair_index] = ref_index
+
+    # the same planes with an ICC profile of either flavour, in one kernel, into a slot of any batch
+    def set_reference_yuv_icc(self, ref_index: int, image: "YuvImage", rgb_depth: int, profile: "IccProfile"):
+        """A decoder's Y'CbCr planes, host or device, read through `profile` into a reference slot of any batch: linear light in
+        a linear batch, sRGB code values of the slot's depth otherwise (ce_batch_set_reference_yuv_icc).  rgb_depth (8, 10, 12 or
+        16, not under the planes' depth) is the integer RGB grid between the colour matrix and the profile."""
+        c, _keep = image._c()
+        self.ctx._check(lib().ce_batch_set_reference_yuv_icc(self._h, ref_index, C.byref(c), rgb_depth, profile._h if profile is not None else None))
+
+    def set_test_yuv_icc(self, pair_index: int, ref_index: int, image: "YuvImage", rgb_depth: int, profile: "IccProfile"):
+        """The same for the test image of pair `pair_index`, bound to reference `ref_index` (ce_batch_set_test_yuv_icc)."""
+        c, _keep = image._c()
+        self.ctx._check(lib().ce_batch_set_test_yuv_icc(self._h, pair_index, ref_index, C.byref(c), rgb_depth, profile._h if profile is not None else None))
         self._pair_ref[pair_index] = ref_index
 
     # BT.2100 HLG code values, and planes, -> display light on the device, into a slot of a linear batch

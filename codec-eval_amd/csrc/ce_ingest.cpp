@@ -764,24 +764,26 @@ void yuv_pack(const ce_yuv_image *img, yuv_plan *plan, uint8_t *h_stage, const u
 }
 
 // the conversion of one checked image into dst: integer RGB (u8, or u16 of `depth`), or with `lin` the fused linear-light
-// ingest of a linear batch (yuv_cicp.hip: the CICP or the HLG pixel, as `lin` says), whose integer grid is the one plan.dev.k
-// was built for
+// ingest of a linear batch (yuv_cicp.hip: the CICP or the HLG pixel, as `lin` says), or with `icc` the fused ICC ingest into
+// the slot its depth_out names (yuv_icc.hip); the integer grid of either is the one plan.dev.k was built for
 int launch_yuv_into(ce_ctx *ctx, hipStream_t stream, const yuv_plan &plan, uint32_t w, uint32_t h, uint8_t *dst, uint32_t depth,
-                    const ce_linear_pixel *lin)
+                    const ce_linear_pixel *lin, const ce_icc_pixel *icc = nullptr)
 {
+    if (icc) return ce_launch_yuv_icc(ctx, stream, plan.dev, w, h, dst, *icc);
     if (lin) return ce_launch_yuv_tagged(ctx, stream, plan.dev, w, h, reinterpret_cast<float *>(dst), *lin);
     return ce_launch_yuv(ctx, stream, plan.dev, w, h, dst, depth != 0, depth ? depth : 8);
 }
 
 // one Y'CbCr image into a slab slot on the batch's upload stream: device planes are read in place, host planes go
 // through the wide staging pair (the packed planes are at most 6 bytes per pixel and a few bytes)
-int upload_yuv(ce_batch *b, uint8_t *dst, const ce_yuv_image *img, yuv_plan &plan, uint32_t depth, const ce_linear_pixel *lin)
+int upload_yuv(ce_batch *b, uint8_t *dst, const ce_yuv_image *img, yuv_plan &plan, uint32_t depth, const ce_linear_pixel *lin,
+               const ce_icc_pixel *icc = nullptr)
 {
     ce_ctx *ctx = b->ctx;
     CE_HIP(ctx, hipSetDevice(ctx->device));
     if (img->memory == CE_MEM_DEVICE) {
         if (int rc = ce_order_write(b, false)) return rc;
-        if (int rc = launch_yuv_into(ctx, b->up_stream, plan, b->w, b->h, dst, depth, lin)) return rc;
+        if (int rc = launch_yuv_into(ctx, b->up_stream, plan, b->w, b->h, dst, depth, lin, icc)) return rc;
         b->uploads_pending = true;
         return CE_OK;
     }
@@ -790,13 +792,13 @@ int upload_yuv(ce_batch *b, uint8_t *dst, const ce_yuv_image *img, yuv_plan &pla
     if (int rc = wide_acquire(b, &k)) return rc;
     yuv_pack(img, &plan, b->h_wide[k], b->d_wide[k]);
     CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], plan.total, hipMemcpyHostToDevice, b->up_stream));
-    if (int rc = launch_yuv_into(ctx, b->up_stream, plan, b->w, b->h, dst, depth, lin)) return rc;
+    if (int rc = launch_yuv_into(ctx, b->up_stream, plan, b->w, b->h, dst, depth, lin, icc)) return rc;
     return wide_close(b, k);
 }
 
-// one checked image -> host memory through the leaf scratch, on the context's stream; depth and lin as launch_yuv_into's
+// one checked image -> host memory through the leaf scratch, on the context's stream; depth, lin and icc as launch_yuv_into's
 int yuv_leaf(ce_ctx *ctx, const ce_yuv_image *image, yuv_plan &plan, uint32_t w, uint32_t h, uint32_t depth, const ce_linear_pixel *lin, void *out,
-             size_t out_bytes)
+             size_t out_bytes, const ce_icc_pixel *icc = nullptr)
 {
     const bool host = image->memory == CE_MEM_HOST;
     if (int rc = ce_leaf_scratch(ctx, host ? plan.total : 1, out_bytes)) return rc;
@@ -804,7 +806,7 @@ int yuv_leaf(ce_ctx *ctx, const ce_yuv_image *image, yuv_plan &plan, uint32_t w,
         yuv_pack(image, &plan, ctx->leaf_h, ctx->leaf_d_in);
         CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_d_in, ctx->leaf_h, plan.total, hipMemcpyHostToDevice, ctx->stream));
     }
-    if (int rc = launch_yuv_into(ctx, ctx->stream, plan, w, h, ctx->leaf_d_out, depth, lin)) return rc;
+    if (int rc = launch_yuv_into(ctx, ctx->stream, plan, w, h, ctx->leaf_d_out, depth, lin, icc)) return rc;
     CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_h, ctx->leaf_d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
     std::memcpy(out, ctx->leaf_h, out_bytes);
@@ -868,6 +870,64 @@ int set_yuv_tagged(ce_batch *b, bool test, uint32_t pair_index, uint32_t ref_ind
         b, test, pair_index, ref_index, kind_rule{false, wants_linear},
         [&] { return yuv_tagged_check(b->ctx, image, d, b->w, b->h, &plan, &lin); },
         [&](uint8_t *slot) { return upload_yuv(b, slot, image, plan, 0, &lin); });
+}
+
+// ---- Y'CbCr planes with an ICC profile into any batch (yuv_icc.hip) ----------------------------------------
+
+// everything *_yuv refuses about the image and *_icc about the handle, and their joint rule: the integer RGB grid between the
+// two halves (rgb_depth) is one of the handle's four and no coarser than the samples.  depth_out, out16: the slot, as icc_check's
+int yuv_icc_check(ce_ctx *ctx, const ce_yuv_image *img, uint32_t rgb_depth, const ce_icc *icc, uint32_t w, uint32_t h, uint32_t depth_out, bool out16,
+                  yuv_plan *plan, ce_icc_pixel *px)
+{
+    if (!img) return ce_fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: null image");
+    if (!icc) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: null pointer");
+    if (icc->ctx->device != ctx->device) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: the profile and the destination are on different devices");
+    if (!ce_deep_depth_ok(rgb_depth))
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ICC ingest: rgb_depth must be 8, 10, 12 or 16, got " + std::to_string(rgb_depth));
+    if (int rc = yuv_check(ctx, img, w, h, rgb_depth, plan)) return rc;
+    if (rgb_depth < (uint32_t)img->depth)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ICC ingest: rgb_depth " + std::to_string(rgb_depth) + " is under the samples' " +
+                                                    std::to_string(img->depth) + " bits");
+    px->maxv = (1u << rgb_depth) - 1u;
+    px->has_matrix = icc->has_matrix;
+    for (int i = 0; i < 9; i++) px->m[i] = icc->m[i];
+    px->depth_out = depth_out, px->out16 = out16;
+    if (depth_out)
+        if (int rc = icc_thresholds_dev(ctx, depth_out, &px->d_thr)) return rc;
+    px->d_tables = icc->d_tables[ce_icc_depth_index(rgb_depth)];
+    px->lut = icc->lut;
+    return CE_OK;
+}
+
+// ce_batch_set_*_yuv_icc: set_yuv's frame around the fused launch, into a linear, an RGB8 or a deep batch
+int set_yuv_icc(ce_batch *b, bool test, uint32_t pair_index, uint32_t ref_index, const ce_yuv_image *image, uint32_t rgb_depth, const ce_icc *icc)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    yuv_plan plan;
+    ce_icc_pixel px;
+    const uint32_t side = b->depth[test];
+    return set_slot(
+        b, test, pair_index, ref_index, kind_rule{},
+        [&] { return yuv_icc_check(b->ctx, image, rgb_depth, icc, b->w, b->h, b->linear ? 0 : side ? side : 8, side != 0, &plan, &px); },
+        [&](uint8_t *slot) { return upload_yuv(b, slot, image, plan, 0, nullptr, &px); });
+}
+
+// ce_yuv_icc_to_linear (depth_out = 0), ce_yuv_icc_to_srgb8 and ce_yuv_icc_to_srgb16: one image -> host memory through the leaf scratch
+int yuv_icc_to_host(ce_ctx *ctx, const ce_yuv_image *image, uint32_t rgb_depth, const ce_icc *icc, uint32_t w, uint32_t h, uint32_t depth_out, bool out16,
+                    void *out, size_t out_len)
+{
+    if (!ctx) return CE_ERR_INVALID_ARG;
+    if (!out) return ce_fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ICC ingest: null output");
+    if (w == 0 || h == 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ICC ingest: empty image");
+    if (out16 && !ce_deep_depth_ok(depth_out))
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ICC ingest: the output depth must be 8, 10, 12 or 16 bits, got " + std::to_string(depth_out));
+    yuv_plan plan;
+    ce_icc_pixel px;
+    if (int rc = yuv_icc_check(ctx, image, rgb_depth, icc, w, h, depth_out, out16, &plan, &px)) return rc;
+    const size_t samples = (size_t)w * h * 3;
+    if (out_len != samples)
+        return ce_fail(ctx, CE_ERR_BAD_LENGTH, "Y'CbCr ICC ingest: out_len must be " + std::to_string(samples) + " samples, got " + std::to_string(out_len));
+    return yuv_leaf(ctx, image, plan, w, h, 0, nullptr, out, samples * (depth_out == 0 ? sizeof(float) : out16 ? 2 : 1), &px);
 }
 
 // ---- alpha: composited over solid backgrounds (alpha.hip) -------------------------------------------------------------------
@@ -1472,6 +1532,28 @@ int ce_batch_set_test_yuv_cicp(ce_batch *b, uint32_t pair_index, uint32_t ref_in
 int ce_yuv_to_linear(ce_ctx *ctx, const ce_yuv_image *image, const ce_colour *c, uint32_t w, uint32_t h, float *out, size_t out_len)
 {
     return yuv_to_linear(ctx, image, c, w, h, out, out_len);
+}
+
+int ce_batch_set_reference_yuv_icc(ce_batch *b, uint32_t ref_index, const ce_yuv_image *image, uint32_t rgb_depth, const ce_icc *icc)
+{
+    return set_yuv_icc(b, false, 0, ref_index, image, rgb_depth, icc);
+}
+int ce_batch_set_test_yuv_icc(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const ce_yuv_image *image, uint32_t rgb_depth, const ce_icc *icc)
+{
+    return set_yuv_icc(b, true, pair_index, ref_index, image, rgb_depth, icc);
+}
+int ce_yuv_icc_to_linear(ce_ctx *ctx, const ce_yuv_image *image, uint32_t rgb_depth, const ce_icc *icc, uint32_t w, uint32_t h, float *out, size_t out_len)
+{
+    return yuv_icc_to_host(ctx, image, rgb_depth, icc, w, h, 0, false, out, out_len);
+}
+int ce_yuv_icc_to_srgb8(ce_ctx *ctx, const ce_yuv_image *image, uint32_t rgb_depth, const ce_icc *icc, uint32_t w, uint32_t h, uint8_t *out, size_t out_len)
+{
+    return yuv_icc_to_host(ctx, image, rgb_depth, icc, w, h, 8, false, out, out_len);
+}
+int ce_yuv_icc_to_srgb16(ce_ctx *ctx, const ce_yuv_image *image, uint32_t rgb_depth, const ce_icc *icc, uint32_t w, uint32_t h, uint32_t depth_out,
+                         uint16_t *out, size_t out_len)
+{
+    return yuv_icc_to_host(ctx, image, rgb_depth, icc, w, h, depth_out, true, out, out_len);
 }
 
 int ce_batch_set_reference_yuv_hlg(ce_batch *b, uint32_t ref_index, const ce_yuv_image *image, const ce_hlg *h)

@@ -592,6 +592,52 @@ int ce_launch_icc(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src
 // the same for px.lut != nullptr, which ce_launch_icc hands on (icc_lut.hip)
 int ce_launch_icc_lut(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, void *d_dst, size_t n_pixels, const ce_icc_pixel &px,
                       const ce_over_plan *ov = nullptr);
+// what the launchers of a matrix/TRC profile put into icc_pixel.h's icc_args beside the frame's own src, dst and n_pixels:
+// the three tables of maxv + 1 floats and the matrix (without one m is not read)
+template <class IccArgs>
+inline void ce_fill_icc_args(IccArgs &a, const ce_icc_pixel &px)
+{
+    a.c.maxv = px.maxv;
+    a.c.table = px.d_tables, a.table_g = px.d_tables + (size_t)px.maxv + 1, a.table_b = px.d_tables + 2 * ((size_t)px.maxv + 1);
+    if (px.has_matrix)
+        for (int i = 0; i < 9; i++) a.c.m[i] = px.m[i];
+}
+// the same for a LUT-based profile (px.lut != nullptr) and icc_lut_pixel.h's icc_lut_args: the tables, f32(inv(A)), the CLUT's
+// geometry, the 3 x 4 matrix, the PCS and the six post-CLUT curves
+template <class IccLutArgs>
+inline void ce_fill_icc_lut_args(IccLutArgs &a, const ce_icc_pixel &px)
+{
+    const ce_icc_lut *lut = px.lut;
+    a.c.maxv = px.maxv;
+    a.c.table = px.d_tables, a.table_g = px.d_tables + (size_t)px.maxv + 1, a.table_b = px.d_tables + 2 * ((size_t)px.maxv + 1);
+    for (int i = 0; i < 9; i++) a.c.m[i] = px.m[i];
+    a.clut = reinterpret_cast<decltype(a.clut)>(lut->d_clut);
+    if (lut->d_clut) {
+        a.s0 = lut->grid[1] * lut->grid[2], a.s1 = lut->grid[2];
+        a.i0 = lut->grid[0] - 2, a.i1 = lut->grid[1] - 2, a.i2 = lut->grid[2] - 2;
+        a.g0 = (float)(lut->grid[0] - 1), a.g1 = (float)(lut->grid[1] - 1), a.g2 = (float)(lut->grid[2] - 1);
+    }
+    a.has_matrix = lut->has_matrix, a.pcs = lut->pcs;
+    for (int i = 0; i < 12; i++) a.mat[i] = lut->mat[i];
+    for (int k = 0; k < 6; k++) {
+        const ce_icc_lut_curve &c = lut->curves[k];
+        auto &o = k < 3 ? a.mc[k] : a.bc[k - 3];
+        o.kind = (uint32_t)c.kind;
+        o.n = c.kind == CE_ICC_LUT_CURVE_SAMPLED ? c.count : c.ftype;
+        o.s = c.kind == CE_ICC_LUT_CURVE_SAMPLED ? lut->d_samples + c.first_sample : nullptr;
+        for (int i = 0; i < 7; i++) o.q[i] = c.q[i];
+        (k < 3 ? a.has_m : a.has_b) |= c.kind != CE_ICC_LUT_CURVE_IDENTITY;
+    }
+}
+// w x h pixels of `src`, whose k was built for depth_out = log2(px.maxv + 1) (the call's rgb_depth), -> what ce_launch_icc
+// makes of ce_launch_yuv's integer RGB: packed f32 RGB, or packed u8 / u16 sRGB code values of px.depth_out bits, at d_dst,
+// one launch and no integer RGB image between the halves (yuv_icc.hip); either flavour of profile
+int ce_launch_yuv_icc(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32_t w, uint32_t h, void *d_dst, const ce_icc_pixel &px);
+// its three halves, one per slot kind (0 f32, 1 u8, 2 u16) and per object that yuv_icc.hip is compiled into: the launch alone,
+// the arguments checked by ce_launch_yuv_icc
+int ce_launch_yuv_icc_0(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32_t w, uint32_t h, void *d_dst, const ce_icc_pixel &px);
+int ce_launch_yuv_icc_1(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32_t w, uint32_t h, void *d_dst, const ce_icc_pixel &px);
+int ce_launch_yuv_icc_2(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32_t w, uint32_t h, void *d_dst, const ce_icc_pixel &px);
 
 // What a linear-light composite blends with (checked and filled by ce_ingest.cpp: over_check): the
 // device alpha table of the source depth (ce_alpha_table; nullptr for CE_PIXEL_RGBA_F32, whose alpha is the coverage), the

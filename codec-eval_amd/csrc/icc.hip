@@ -69,11 +69,9 @@ int ce_launch_icc(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src
         return CE_ERR_INVALID_ARG;
     }
     icc_args a{};
-    a.c.src = d_src, a.c.n_pixels = n_pixels, a.c.maxv = px.maxv;
+    a.c.src = d_src, a.c.n_pixels = n_pixels;
     a.c.dst = integer ? nullptr : static_cast<float *>(d_dst);
-    a.c.table = px.d_tables, a.table_g = px.d_tables + (size_t)px.maxv + 1, a.table_b = px.d_tables + 2 * ((size_t)px.maxv + 1);
-    if (px.has_matrix)
-        for (int i = 0; i < 9; i++) a.c.m[i] = px.m[i];
+    ce_fill_icc_args(a, px);
     const int kind = !integer ? 0 : px.out16 ? 2 : 1;
     const uint32_t top = integer ? 1u << (px.depth_out - 1) : 0u;
     const dim3 grid((uint32_t)blocks);

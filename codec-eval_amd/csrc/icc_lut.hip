@@ -67,27 +67,9 @@ int ce_launch_icc_lut(ce_ctx *ctx, hipStream_t stream, int format, const void *d
         return CE_ERR_INVALID_ARG;
     }
     icc_lut_args a{};
-    a.c.src = d_src, a.c.n_pixels = n_pixels, a.c.maxv = px.maxv;
+    a.c.src = d_src, a.c.n_pixels = n_pixels;
     a.c.dst = integer ? nullptr : static_cast<float *>(d_dst);
-    a.c.table = px.d_tables, a.table_g = px.d_tables + (size_t)px.maxv + 1, a.table_b = px.d_tables + 2 * ((size_t)px.maxv + 1);
-    for (int i = 0; i < 9; i++) a.c.m[i] = px.m[i];
-    a.clut = reinterpret_cast<const icc_lut_node *>(lut->d_clut);
-    if (lut->d_clut) {
-        a.s0 = lut->grid[1] * lut->grid[2], a.s1 = lut->grid[2];
-        a.i0 = lut->grid[0] - 2, a.i1 = lut->grid[1] - 2, a.i2 = lut->grid[2] - 2;
-        a.g0 = (float)(lut->grid[0] - 1), a.g1 = (float)(lut->grid[1] - 1), a.g2 = (float)(lut->grid[2] - 1);
-    }
-    a.has_matrix = lut->has_matrix, a.pcs = lut->pcs;
-    for (int i = 0; i < 12; i++) a.mat[i] = lut->mat[i];
-    for (int k = 0; k < 6; k++) {
-        const ce_icc_lut_curve &c = lut->curves[k];
-        icc_lut_curve &o = k < 3 ? a.mc[k] : a.bc[k - 3];
-        o.kind = (uint32_t)c.kind;
-        o.n = c.kind == CE_ICC_LUT_CURVE_SAMPLED ? c.count : c.ftype;
-        o.s = c.kind == CE_ICC_LUT_CURVE_SAMPLED ? lut->d_samples + c.first_sample : nullptr;
-        for (int i = 0; i < 7; i++) o.q[i] = c.q[i];
-        (k < 3 ? a.has_m : a.has_b) |= c.kind != CE_ICC_LUT_CURVE_IDENTITY;
-    }
+    ce_fill_icc_lut_args(a, px);
     const int kind = !integer ? 0 : px.out16 ? 2 : 1;
     const uint32_t top = integer ? 1u << (px.depth_out - 1) : 0u;
     const dim3 grid((uint32_t)blocks);

@@ -556,6 +556,41 @@ inline void batch_set_test_yuv_cicp(const HipBackend &be, ce_batch *batch, uint3
 {
     detail::check(be, ce_batch_set_test_yuv_cicp(batch, pair_index, ref_index, &image, &colour), "yuv_cicp", 0, 0, 0);
 }
+// ---- Y'CbCr planes with an ICC profile, in one kernel (include/ce_metrics.h: ce_batch_set_*_yuv_icc) ----
+// rgb_depth (8, 10, 12 or 16, not under the planes' depth): the integer RGB grid between the colour matrix and the profile
+inline std::vector<float> yuv_icc_to_linear(const HipBackend &be, const YuvImage &image, uint32_t rgb_depth, const HipIccProfile &icc, uint32_t width,
+                                            uint32_t height)
+{
+    std::vector<float> out((size_t)width * height * 3);
+    detail::check(be, ce_yuv_icc_to_linear(be.ctx(), &image, rgb_depth, icc.get(), width, height, out.data(), out.size()), "yuv_icc", width, height, out.size());
+    return out;
+}
+inline std::vector<uint8_t> yuv_icc_to_srgb8(const HipBackend &be, const YuvImage &image, uint32_t rgb_depth, const HipIccProfile &icc, uint32_t width,
+                                             uint32_t height)
+{
+    std::vector<uint8_t> out((size_t)width * height * 3);
+    detail::check(be, ce_yuv_icc_to_srgb8(be.ctx(), &image, rgb_depth, icc.get(), width, height, out.data(), out.size()), "yuv_icc", width, height, out.size());
+    return out;
+}
+inline std::vector<uint16_t> yuv_icc_to_srgb16(const HipBackend &be, const YuvImage &image, uint32_t rgb_depth, const HipIccProfile &icc, uint32_t width,
+                                               uint32_t height, uint32_t depth_out)
+{
+    std::vector<uint16_t> out((size_t)width * height * 3);
+    detail::check(be, ce_yuv_icc_to_srgb16(be.ctx(), &image, rgb_depth, icc.get(), width, height, depth_out, out.data(), out.size()), "yuv_icc", width,
+                  height, out.size());
+    return out;
+}
+// straight into a slot of any batch, host or device planes: linear light in a linear batch, sRGB code values of the slot's depth otherwise
+inline void batch_set_reference_yuv_icc(const HipBackend &be, ce_batch *batch, uint32_t ref_index, const YuvImage &image, uint32_t rgb_depth,
+                                        const HipIccProfile &icc)
+{
+    detail::check(be, ce_batch_set_reference_yuv_icc(batch, ref_index, &image, rgb_depth, icc.get()), "yuv_icc", 0, 0, 0);
+}
+inline void batch_set_test_yuv_icc(const HipBackend &be, ce_batch *batch, uint32_t pair_index, uint32_t ref_index, const YuvImage &image,
+                                   uint32_t rgb_depth, const HipIccProfile &icc)
+{
+    detail::check(be, ce_batch_set_test_yuv_icc(batch, pair_index, ref_index, &image, rgb_depth, icc.get()), "yuv_icc", 0, 0, 0);
+}
 // ---- BT.2100 HLG -> display light, linear, with sRGB primaries (include/ce_metrics.h: ce_hlg_to_linear) ----
 // HLG carries the display it is shown on - peak luminance and system gamma (0: BT.2100's rule from the peak) - besides the
 // primaries, the depth and the luminance that becomes 1.0

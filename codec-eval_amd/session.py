@@ -118,14 +118,18 @@ class ImageData:
     @staticmethod
     def yuv(planes, width: int, height: int, subsampling: int = YUV_420, layout: int = YUV_PLANAR, matrix: int = YUV_BT601,
             range: int = YUV_FULL, upsample: int = CHROMA_TRIANGLE, *, depth: int = 8, msb_aligned: bool = False,
-            colour: Optional[Colour] = None) -> "ImageData":
+            colour: Optional[Colour] = None, icc_profile: Optional[bytes] = None) -> "ImageData":
         """A decoder's Y'CbCr planes in host memory (a JPEG decoder in raw mode, dav1d: 2-D arrays, Y, Cb, Cr or Y,
         interleaved CbCr; uint8 at depth 8, uint16 at 10 and 12, low- or MSB-aligned as P010 is) as they are: the session
         upsamples and converts them on the device, straight into the batch slot (Batch.set_*_yuv, the definition of
         include/ce_metrics.h), and scores the result as RGB8; the multi-device session converts them on the host with
         to_rgb8_vec, the same definition.  With a `colour` other than sRGB's (an HDR10 frame: BT2020_PQ) the image is
         scored in linear light, its planes going through Batch.set_*_yuv_cicp, or through
-        Batch.set_*_yuv_hlg for an HlgDescription (section 18)."""
+        Batch.set_*_yuv_hlg for an HlgDescription (section 18).
+        icc_profile: the decode's embedded profile (a phone's JPEG or HEIC: Display P3).  A session without a cms applies a
+        profile the library takes (matrix/TRC or LUT-based) on the device in the same launch that converts the planes
+        (Batch.set_*_yuv_icc); a session with a cms, and the multi-device session, convert on the host
+        (to_rgb8_srgb) and upload RGB8.  As with packed images, the source image's own profile stays unapplied."""
         if depth not in (8, 10, 12):
             raise ValueError(f"Y'CbCr samples are 8, 10 or 12 bits, got {depth}")
         img = YuvImage([np.asarray(p) for p in planes], subsampling, layout, matrix, range, upsample, int(depth), bool(msb_aligned), MEM_HOST)
@@ -133,7 +137,8 @@ class ImageData:
         for p in img.planes:
             if p.dtype != want or p.ndim != 2:
                 raise TypeError("ImageData.yuv takes 2-D uint8 planes" if depth == 8 else f"ImageData.yuv at depth {depth} takes 2-D uint16 planes")
-        return ImageData(np.empty(0, np.uint8), int(width), int(height), 3, None, 0, img, colour=_colour_at(colour, depth))
+        return ImageData(np.empty(0, np.uint8), int(width), int(height), 3, None if icc_profile is None else bytes(icc_profile), 0, img,
+                         colour=_colour_at(colour, depth))
 
     def _yuv_to_rgb8_host(self) -> np.ndarray:
         """The device's conversion restated on the host for to_rgb8_vec (int64, the definition of include/ce_metrics.h)."""
@@ -522,6 +527,13 @@ class EvalSession:
         def refuse(what):
             raise MetricCalculation(CE_ERR_BACKEND, f"Metric calculation failed: linear-light scoring: {what}")
         if image.yuv_image is not None:  # the planes' own tag, an untagged image as sRGB; depth 16 keeps what the matrix gives between code points
+            if image.colour is not None and image.icc_profile is not None:
+                refuse("an image with both a colour description and an ICC profile is not supported")
+            if image.icc_profile is not None and pair_index is not None:  # a decode's profile; the source's own is not applied, as ever
+                profile = self._profile_for(image)
+                if profile is None:
+                    refuse("an ICC profile is not applied in linear light")
+                return batch.set_test_yuv_icc(pair_index, ref_index, image.yuv_image, 16, profile)  # the library's own transform, planes and profile in one launch
             colour = (image.colour or ColourDescription.SRGB).with_depth(16)
             if isinstance(colour, HlgDescription):
                 if pair_index is None:
@@ -681,7 +693,11 @@ class EvalSession:
                         batch.set_test_over(k, ref_of, decoded.data, decoded.pixel_format, bg_side[1])
                     else:
                         for j in range(n):  # an opaque decode against a source with alpha: the same image over every background
-                            if decoded.yuv_image is not None:  # a decoder's Y'CbCr planes: upsampled and converted on the device, into the slot
+                            if decoded.yuv_image is not None and profile is not None:  # planes with a profile the library takes: one launch, at the planes' own depth
+                                batch.set_test_yuv_icc(k + j, ref_of[j], decoded.yuv_image, decoded.yuv_image.depth, profile)
+                            elif decoded.yuv_image is not None and decoded.icc_profile is not None:  # a session with a cms: to_rgb8_srgb on the host
+                                batch.set_test(k + j, ref_of[j], decoded.to_rgb8_srgb(self._cms))
+                            elif decoded.yuv_image is not None:  # a decoder's Y'CbCr planes: upsampled and converted on the device, into the slot
                                 batch.set_test_yuv(k + j, ref_of[j], decoded.yuv_image)
                             elif profile is not None:  # to_rgb8_srgb by the library's own transform
                                 batch.set_test_icc(k + j, ref_of[j], decoded.data.reshape(decoded.height, decoded.width, decoded.channels),

@@ -725,6 +725,39 @@ int ce_batch_set_reference_yuv_cicp(ce_batch *b, uint32_t ref_index, const ce_yu
 int ce_batch_set_test_yuv_cicp(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const ce_yuv_image *image, const ce_colour *c);
 int ce_yuv_to_linear(ce_ctx *ctx, const ce_yuv_image *image, const ce_colour *c, uint32_t width, uint32_t height, float *out, size_t out_len);
 
+/* Y'CbCr planes with an ICC profile -> a slot of any batch, on the device, in one kernel: what a
+ * phone's JPEG or HEIC is - planes with a Display P3 profile - and what a rocJPEG surface of one is.  The definition is the
+ * composition of ce_yuv_to_rgb16 and the ICC section's (below) and adds no arithmetic.  For an image img, a profile handle
+ * icc of either flavour (ce_icc_create: matrix/TRC; ce_icc_lut_create: LUT-based) and an integer grid depth rgb_depth,
+ *     rgb = the integer RGB that ce_yuv_to_rgb16(img, depth_out = rgb_depth) defines (samples, chroma upsampling, fixed-point
+ *           matrix, clamp to 2^rgb_depth - 1)
+ *     a linear slot:  what ce_icc_to_linear(rgb as CE_PIXEL_RGB16, depth = rgb_depth, icc) defines
+ *     an RGB8 slot (D = 8, stored as u8) / a deep side of depth D:
+ *                     what ce_icc_to_srgb16(rgb as CE_PIXEL_RGB16, depth = rgb_depth, icc, depth_out = D) defines
+ * img.depth (8, 10 or 12) is the depth of the Y'CbCr samples; rgb_depth (8, 10, 12 or 16) is the depth of the integer RGB
+ * grid between the two steps and picks the handle's tone tables, and must not be under img.depth - what c.depth is to
+ * ce_batch_set_*_yuv_cicp.  rgb_depth = img.depth is what the decoder's own RGB output handed to a CMS would have been;
+ * rgb_depth = 16 keeps what the matrix produces between the samples' code points.  The composition of
+ * tests/yuv_restatement.py (yuv_to_rgb with D = rgb_depth) and tests/icc_restatement.py / icc_lut_restatement.py (to_linear,
+ * to_srgb) restates it in numpy (tests/yuv_icc_cases.py); the device equals it bit for bit.
+ * ce_batch_set_*_yuv_icc: one image of the batch's shape into a reference / test slot of a linear, an RGB8 or a deep batch (a
+ * deep side is written at its own depth), with the staging, the stream and the ordering of ce_batch_set_*_yuv; CE_MEM_HOST
+ * planes are consumed on return, CE_MEM_DEVICE planes are read in place under the lifetime rule given there.
+ * CE_ERR_INVALID_ARG, with the reason in ce_last_error and the batch still usable, for everything ce_batch_set_*_yuv refuses
+ * about the image (the reserved lut field included), a null handle, a profile of another device, and rgb_depth outside {8,
+ * 10, 12, 16} or under img.depth.  (ce_batch_set_*_yuv on a linear batch stays refused.)
+ * ce_yuv_icc_to_linear / _to_srgb8 / _to_srgb16: one image of width x height to packed float RGB, u8 sRGB codes or u16 sRGB
+ * codes of depth_out bits (8, 10, 12 or 16) in host memory (out_len = width * height * 3 samples); errors as above,
+ * CE_ERR_BAD_LENGTH for a wrong out_len.
+ * Not part of this: chroma sitings other than the centred one, alpha planes and the *_over calls with planes, Gray and CMYK
+ * profiles, ce_ref_* handles and the pooled ce_eval_batch, gain maps on planes. */
+struct ce_icc; /* the handle ce_icc_create / ce_icc_lut_create make: ce_icc, in the ICC section below */
+int ce_batch_set_reference_yuv_icc(ce_batch *b, uint32_t ref_index, const ce_yuv_image *image, uint32_t rgb_depth, const struct ce_icc *icc);
+int ce_batch_set_test_yuv_icc(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const ce_yuv_image *image, uint32_t rgb_depth, const struct ce_icc *icc);
+int ce_yuv_icc_to_linear(ce_ctx *ctx, const ce_yuv_image *image, uint32_t rgb_depth, const struct ce_icc *icc, uint32_t width, uint32_t height, float *out, size_t out_len);
+int ce_yuv_icc_to_srgb8(ce_ctx *ctx, const ce_yuv_image *image, uint32_t rgb_depth, const struct ce_icc *icc, uint32_t width, uint32_t height, uint8_t *out, size_t out_len);
+int ce_yuv_icc_to_srgb16(ce_ctx *ctx, const ce_yuv_image *image, uint32_t rgb_depth, const struct ce_icc *icc, uint32_t width, uint32_t height, uint32_t depth_out, uint16_t *out, size_t out_len);
+
 /* HLG ingest: integer RGB code values, or Y'CbCr planes, in BT.2100 Hybrid Log-Gamma (H.273 transfer
  * 18) -> a slot of a linear batch, on the device.  HLG is scene-referred: the inverse OETF is per channel, but the OOTF that
  * turns scene light into display light scales all three channels by Ys^(gamma - 1), Ys the pixel's scene luminance and gamma
@@ -978,8 +1011,8 @@ int ce_eval_pair_delta_e_itp_map(ce_ctx *ctx, const float *reference, size_t ref
  *      NaN -> 0, out-of-gamut values clip.  The integer routes are the encode of the linear route and add no other arithmetic.
  * tests/icc_restatement.py restates this in numpy; the device equals it bit for bit.
  * Not part of this: LUT-based profiles (mAB, lut8, lut16: ce_icc_lut_create below takes those), Gray and CMYK profiles,
- * rendering intents, black-point compensation, Y'CbCr planes with a profile, alpha compositing with a profile, ce_ref_*
- * handles and the pooled ce_eval_batch. */
+ * rendering intents, black-point compensation, alpha compositing with a profile, ce_ref_* handles and the pooled
+ * ce_eval_batch.  (Y'CbCr planes with a profile: ce_batch_set_*_yuv_icc, next to the other plane routes above.) */
 #define CE_ICC_MAX_PROFILE_BYTES 4194304u
 #define CE_ICC_MAX_CURVE_POINTS 65536u
 enum { CE_ICC_SUPPORTED = 0, CE_ICC_LUT_BASED = 1, CE_ICC_NOT_RGB_XYZ = 2, CE_ICC_MALFORMED = 3 };
@@ -1091,8 +1124,9 @@ int ce_icc_to_srgb16(ce_ctx *ctx, const void *pixels, size_t len, int format, ui
  *   6. the clamp of a linear image: the value a linear batch stores.  An RGB8 batch or a deep side stores its code by step 4 of
  *      the matrix/TRC definition, unchanged.
  * tests/icc_lut_restatement.py restates this in numpy; the device equals it bit for bit.
- * Not part of this: Gray and CMYK profiles, mBA / B2A tags, multiProcessElements (D2B*), black-point compensation, Y'CbCr
- * planes or alpha with a profile in one kernel, ce_ref_* handles and the pooled ce_eval_batch. */
+ * Not part of this: Gray and CMYK profiles, mBA / B2A tags, multiProcessElements (D2B*), black-point compensation, alpha
+ * with a profile in one kernel, ce_ref_* handles and the pooled ce_eval_batch.  (Y'CbCr planes with a profile of either
+ * flavour: ce_batch_set_*_yuv_icc above.) */
 #define CE_ICC_MAX_CLUT_NODES 274625u /* 65^3: 4.4 MB on the device, a node being 16 bytes there */
 enum { CE_ICC_LUT_SUPPORTED = 0, CE_ICC_LUT_NOT_LUT = 1, CE_ICC_LUT_UNSUPPORTED = 2, CE_ICC_LUT_MALFORMED = 3 };
 enum { CE_ICC_CLUT_TRILINEAR = 0, CE_ICC_CLUT_TETRAHEDRAL = 1 };
