@@ -1,9 +1,10 @@
-// Everything that writes a slot of a resident batch (include/ce_metrics.h: ce_batch_set_*, ce_batch_bind_pair, ce_lut_*),
-// the tables and the one-image leaves of the same conversions (ce_*_table, ce_*_to_linear, ce_yuv_to_rgb*, ce_composite_*,
-// ce_linear_over).
-// Three things live here once and every route goes through them: the ordering rule of slot writes (ce_order_write), the
-// wide staging pair (wide_acquire / wide_close) and the frame of a setter (set_slot).  A route adds its check, which fills
-// its plan, and its write.  All device work is in the .hip files.
+// Everything that writes a slot of a resident batch (include/ce_metrics.h: ce_batch_set_*, ce_batch_bind_pair), the tables
+// and the one-image leaves of the same conversions (ce_*_table, ce_*_to_linear, ce_yuv_to_rgb*, ce_composite_*,
+// ce_linear_over).  The handles some routes take (colour tables, ICC profiles) are made in ce_handles.cpp.
+// Four things live here once and every route goes through them: the ordering rule of slot writes (ce_order_write), the
+// wide staging pair (wide_send), the frame of a setter of one slot (set_slot) and of n consecutive slots (set_slots).  A
+// route adds its check, which fills its plan, its fill of the staging pair and its launch.  All device work is in the .hip
+// files.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -198,14 +199,22 @@ namespace {
 
 // Every image that a conversion kernel follows (a decoder's format, tagged code values, host Y'CbCr planes, RGBA over
 // backgrounds) goes host -> h_wide[k] -> d_wide[k] -> kernel -> slot on the batch's upload stream.  There are two pairs, made
-// on first use: while pair k's copy and conversion are in flight the host fills the other.  A route acquires the next pair,
-// fills h_wide[k], queues the copy to d_wide[k] and its launch on up_stream, and closes the pair.
-//
-// wide_acquire hands out the next pair, ordered as a slot write and free of its previous image.  A pair holds 8 bytes per
-// pixel, the widest decoder format (16 on a linear batch: packed f32 RGBA, which the linear-light composite takes).
-int wide_acquire(ce_batch *b, int *k_out)
+// on first use: while pair k's copy and conversion are in flight the host fills the other.  A pair holds 8 bytes per pixel,
+// the widest decoder format (16 on a linear batch: packed f32 RGBA, which the linear-light composite takes).
+struct wide_pair {
+    uint8_t *h, *d;  // the pinned host buffer to fill and where its device copy will be
+    int k;           // which of the two, for a route that keeps a pair of its own beside it (the gain map's side pair)
+};
+
+// One image through the next wide pair, and the only code that touches the pairs: the pair is taken ordered as a slot write
+// and free of its previous image; fill(pair) writes `bytes` into pair.h (pair.d is for a route whose launch arguments point
+// into the device copy); then the copy, launch(pair) on up_stream, and the event behind it that keeps the pair busy until
+// up_stream gets there.  A fill or a launch that fails returns before the pair is closed.
+template <class Fill, class Launch>
+int wide_send(ce_batch *b, size_t bytes, Fill fill, Launch launch)
 {
     ce_ctx *ctx = b->ctx;
+    CE_HIP(ctx, hipSetDevice(ctx->device));  // the staging allocations and the launch go to the context's device
     const int k = b->next_wide;
     b->next_wide ^= 1;
     if (!b->h_wide[k]) {
@@ -216,17 +225,23 @@ int wide_acquire(ce_batch *b, int *k_out)
     }
     if (int rc = ce_order_write(b, false)) return rc;
     if (b->wide_busy[k]) CE_HIP(ctx, hipEventSynchronize(b->ev_wide[k]));  // this staging pair's previous image has been converted
-    *k_out = k;
-    return CE_OK;
-}
-
-// behind the conversion launch: the pair is busy until up_stream gets here
-int wide_close(ce_batch *b, int k)
-{
-    CE_HIP(b->ctx, hipEventRecord(b->ev_wide[k], b->up_stream));
+    const wide_pair pair{b->h_wide[k], b->d_wide[k], k};
+    if (int rc = fill(pair)) return rc;
+    CE_HIP(ctx, hipMemcpyAsync(pair.d, pair.h, bytes, hipMemcpyHostToDevice, b->up_stream));
+    if (int rc = launch(pair)) return rc;
+    CE_HIP(ctx, hipEventRecord(b->ev_wide[k], b->up_stream));
     b->wide_busy[k] = true;
     b->uploads_pending = true;
     return CE_OK;
+}
+
+// the fill of a route whose image is packed already
+auto packed_fill(const void *pixels, size_t len)
+{
+    return [=](const wide_pair &p) {
+        std::memcpy(p.h, pixels, len);
+        return CE_OK;
+    };
 }
 
 // ---- the frame of a setter --------------------------------------------------------------------------------------------------
@@ -253,6 +268,30 @@ int set_slot(ce_batch *b, bool test, uint32_t pair_index, uint32_t ref_index, ki
         ce_invalidate_reference_state(b);  // cached reference-side planes are stale
     }
     return write(test ? b->d_tests + (size_t)pair_index * b->img_bytes : b->d_refs + (size_t)ref_index * b->img_bytes);
+}
+
+// Every setter of n consecutive slots from `first` on, the test slots bound to ref_indices[]: set_slot's frame with `route`
+// ("alpha compositing: ") in front of its own messages.  null_arg: one of the route's pointers is null; check() and
+// write(first slot) as set_slot's.
+template <class Check, class Write>
+int set_slots(ce_batch *b, bool test, uint32_t first, uint32_t n, const uint32_t *ref_indices, const char *route, kind_rule refuses, bool null_arg,
+              Check check, Write write)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    ce_ctx *ctx = b->ctx;
+    if (refuses.text && b->linear == refuses.linear) return ce_fail(ctx, CE_ERR_INVALID_ARG, refuses.text);
+    if ((test && !ref_indices) || null_arg) return ce_fail(ctx, CE_ERR_INVALID_ARG, std::string(route) + "null pointer");
+    if (int rc = check()) return rc;
+    const uint32_t slots = test ? b->max_pairs : b->max_refs;
+    if (first > slots || n > slots - first)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, std::string(route) + (test ? "test" : "reference") + " slots [" + std::to_string(first) + ", " +
+                                                    std::to_string((uint64_t)first + n) + ") outside the " + std::to_string(slots) + " slots");
+    for (uint32_t k = 0; test && k < n; k++)
+        if (ref_indices[k] >= b->max_refs) return ce_fail(ctx, CE_ERR_INVALID_ARG, std::string(route) + "ref index " + std::to_string(ref_indices[k]) + " out of range");
+    for (uint32_t k = 0; test && k < n; k++)
+        if (int rc = ce_batch_bind_pair(b, first + k, ref_indices[k])) return rc;
+    if (!test) ce_invalidate_reference_state(b);
+    return write((test ? b->d_tests : b->d_refs) + (size_t)first * b->img_bytes);
 }
 
 // ---- RGB8, a decoder's formats, colour tables ---------------------------------------------------------------------------------
@@ -284,16 +323,11 @@ int upload_fmt(ce_batch *b, uint8_t *dst, const void *pixels, size_t len, int fo
     ce_ctx *ctx = b->ctx;
     const size_t n_px = (size_t)b->w * b->h;
     if (format == CE_PIXEL_RGB8 && !depth) return upload(b, dst, static_cast<const uint8_t *>(pixels), false);
-    CE_HIP(ctx, hipSetDevice(ctx->device));  // the staging allocations and the ingest launch below go to the context's device
-    int k;
-    if (int rc = wide_acquire(b, &k)) return rc;
-    std::memcpy(b->h_wide[k], pixels, len);
-    CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], len, hipMemcpyHostToDevice, b->up_stream));
-    int rc = b->linear ? ce_launch_linear_sanitise(ctx, b->up_stream, reinterpret_cast<const float *>(b->d_wide[k]), reinterpret_cast<float *>(dst), n_px * 3)
-             : depth ? ce_launch_ingest_deep(ctx, b->up_stream, format, depth, b->d_wide[k], reinterpret_cast<uint16_t *>(dst), n_px)
-                   : ce_launch_ingest(ctx, b->up_stream, format, b->d_wide[k], dst, n_px);
-    if (rc != CE_OK) return rc;
-    return wide_close(b, k);
+    return wide_send(b, len, packed_fill(pixels, len), [&](const wide_pair &p) {
+        return b->linear ? ce_launch_linear_sanitise(ctx, b->up_stream, reinterpret_cast<const float *>(p.d), reinterpret_cast<float *>(dst), n_px * 3)
+               : depth   ? ce_launch_ingest_deep(ctx, b->up_stream, format, depth, p.d, reinterpret_cast<uint16_t *>(dst), n_px)
+                         : ce_launch_ingest(ctx, b->up_stream, format, p.d, dst, n_px);
+    });
 }
 
 // ce_batch_set_*_fmt (lut = nullptr) and ce_batch_set_*_lut
@@ -436,14 +470,9 @@ int tagged_check(ce_ctx *ctx, const void *pixels, size_t len, int format, const 
 // one checked image through the wide staging pair into the slot at dst
 int upload_cicp(ce_batch *b, uint8_t *dst, const void *pixels, size_t len, int format, const ce_linear_pixel &plan)
 {
-    ce_ctx *ctx = b->ctx;
-    CE_HIP(ctx, hipSetDevice(ctx->device));
-    int k;
-    if (int rc = wide_acquire(b, &k)) return rc;
-    std::memcpy(b->h_wide[k], pixels, len);
-    CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], len, hipMemcpyHostToDevice, b->up_stream));
-    if (int rc = ce_launch_tagged(ctx, b->up_stream, format, b->d_wide[k], reinterpret_cast<float *>(dst), (size_t)b->w * b->h, plan)) return rc;
-    return wide_close(b, k);
+    return wide_send(b, len, packed_fill(pixels, len), [&](const wide_pair &p) {
+        return ce_launch_tagged(b->ctx, b->up_stream, format, p.d, reinterpret_cast<float *>(dst), (size_t)b->w * b->h, plan);
+    });
 }
 
 const char *const kCicpWantsLinear = "CICP ingest writes linear light: it needs a linear batch (ce_batch_create_linear)";
@@ -543,24 +572,27 @@ size_t gainmap_side(const ce_gainmap_plan &plan, const ce_gainmap_image *map, ui
 // One checked image into the slot at dst: the base through the wide staging pair, the tables and the map through a pair of
 // their own beside it, made on first use for the largest map the batch's shape admits (three channels at the base's size) -
 // a wide pair is w * h * 12 bytes, which a small RGBA16 base with such a map would overrun.  Both are busy until the launch
-// is done, under the wide pair's event.
+// is done, under the wide pair's event: the side pair is filled before the copies are queued, and its copy goes behind the base's.
 int upload_gainmap(ce_batch *b, uint8_t *dst, const void *pixels, size_t len, int format, const ce_gainmap_image *map, const ce_gainmap_plan &plan)
 {
     ce_ctx *ctx = b->ctx;
-    CE_HIP(ctx, hipSetDevice(ctx->device));
-    int k;
-    if (int rc = wide_acquire(b, &k)) return rc;
-    if (!b->h_side[k]) {
-        const size_t cap = 3 * 256 * sizeof(double) + (size_t)b->w * b->h * 3;
-        CE_HIP(ctx, hipHostMalloc((void **)&b->h_side[k], cap, hipHostMallocDefault));
-        CE_HIP(ctx, hipMalloc((void **)&b->d_side[k], cap));
-    }
-    std::memcpy(b->h_wide[k], pixels, len);
-    const size_t side = gainmap_side(plan, map, b->h_side[k]);
-    CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], len, hipMemcpyHostToDevice, b->up_stream));
-    CE_HIP(ctx, hipMemcpyAsync(b->d_side[k], b->h_side[k], side, hipMemcpyHostToDevice, b->up_stream));
-    if (int rc = ce_launch_gainmap(ctx, b->up_stream, format, b->d_wide[k], b->d_side[k], reinterpret_cast<float *>(dst), b->w, b->h, plan)) return rc;
-    return wide_close(b, k);
+    size_t side = 0;
+    return wide_send(
+        b, len,
+        [&](const wide_pair &p) -> int {
+            if (!b->h_side[p.k]) {
+                const size_t cap = 3 * 256 * sizeof(double) + (size_t)b->w * b->h * 3;
+                CE_HIP(ctx, hipHostMalloc((void **)&b->h_side[p.k], cap, hipHostMallocDefault));
+                CE_HIP(ctx, hipMalloc((void **)&b->d_side[p.k], cap));
+            }
+            std::memcpy(p.h, pixels, len);
+            side = gainmap_side(plan, map, b->h_side[p.k]);
+            return CE_OK;
+        },
+        [&](const wide_pair &p) -> int {
+            CE_HIP(ctx, hipMemcpyAsync(b->d_side[p.k], b->h_side[p.k], side, hipMemcpyHostToDevice, b->up_stream));
+            return ce_launch_gainmap(ctx, b->up_stream, format, p.d, b->d_side[p.k], reinterpret_cast<float *>(dst), b->w, b->h, plan);
+        });
 }
 
 const char *const kGainmapWantsLinear = "gain-map ingest writes linear light: it needs a linear batch (ce_batch_create_linear)";
@@ -588,16 +620,14 @@ int gainmap_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format, c
     const size_t n_px = (size_t)w * h, at = (len + 15) & ~(size_t)15, in_bytes = at + plan.table_bytes() + plan.map_bytes();
     if (out_len != n_px * 3)
         return ce_fail(ctx, CE_ERR_BAD_LENGTH, "gain-map ingest: out_len must be " + std::to_string(n_px * 3) + " floats, got " + std::to_string(out_len));
-    if (int rc = ce_leaf_scratch(ctx, in_bytes, n_px * 12)) return rc;
-    std::memcpy(ctx->leaf_h, pixels, len);
-    gainmap_side(plan, map, ctx->leaf_h + at);
-    CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_d_in, ctx->leaf_h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = ce_launch_gainmap(ctx, ctx->stream, format, ctx->leaf_d_in, ctx->leaf_d_in + at, reinterpret_cast<float *>(ctx->leaf_d_out), w, h, plan))
-        return rc;
-    CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_h, ctx->leaf_d_out, n_px * 12, hipMemcpyDeviceToHost, ctx->stream));
-    CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::memcpy(out, ctx->leaf_h, n_px * 12);
-    return CE_OK;
+    return ce_leaf_roundtrip(
+        ctx, in_bytes,
+        [&](uint8_t *h_in, uint8_t *) {
+            std::memcpy(h_in, pixels, len);
+            gainmap_side(plan, map, h_in + at);
+        },
+        out, n_px * 12,
+        [&](uint8_t *d_in, uint8_t *d_out) { return ce_launch_gainmap(ctx, ctx->stream, format, d_in, d_in + at, reinterpret_cast<float *>(d_out), w, h, plan); });
 }
 
 // ---- matrix/TRC ICC profiles into any batch (icc.hip) ---------------------------------------------------
@@ -618,10 +648,36 @@ int icc_thresholds_dev(ce_ctx *ctx, uint32_t depth, const float **out)
     return CE_OK;
 }
 
-// One image of code values with its profile for a slot of depth_out bits (0: linear light; out16: u16 samples; wide_ok: the
-// slot takes 16-bit sources): everything refused about either, then the plan
-int icc_check(ce_ctx *ctx, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc, size_t n_px, uint32_t depth_out, bool out16,
-              bool wide_ok, ce_icc_pixel *plan)
+// the slot an ICC ingest writes: depth_out bits (0: linear light), out16: u16 samples, wide_ok: it takes 16-bit sources
+struct icc_slot {
+    uint32_t depth_out;
+    bool out16, wide_ok;
+};
+
+// the slot kind of a batch's side
+icc_slot icc_slot_of(const ce_batch *b, bool test)
+{
+    const uint32_t side = b->depth[test];
+    return {b->linear ? 0 : side ? side : 8, side != 0, b->linear || side != 0};
+}
+
+// the plan of a checked handle for sources of `depth` bits (one of the handle's four) into `slot`: the tables of that depth,
+// the matrix, the LUT stages and, for an integer slot, the thresholds of its depth, made on demand
+int icc_plan(ce_ctx *ctx, const ce_icc *icc, uint32_t depth, icc_slot slot, ce_icc_pixel *plan)
+{
+    plan->maxv = (1u << depth) - 1u;
+    plan->has_matrix = icc->has_matrix;
+    for (int i = 0; i < 9; i++) plan->m[i] = icc->m[i];
+    plan->depth_out = slot.depth_out, plan->out16 = slot.out16;
+    if (slot.depth_out)
+        if (int rc = icc_thresholds_dev(ctx, slot.depth_out, &plan->d_thr)) return rc;
+    plan->d_tables = icc->d_tables[ce_icc_depth_index(depth)];
+    plan->lut = icc->lut;
+    return CE_OK;
+}
+
+// One image of code values with its profile for `slot`: everything refused about either, then the plan
+int icc_check(ce_ctx *ctx, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc, size_t n_px, icc_slot slot, ce_icc_pixel *plan)
 {
     if (!pixels || !icc) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: null pointer");
     if (icc->ctx->device != ctx->device) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: the profile and the destination are on different devices");
@@ -629,38 +685,24 @@ int icc_check(ce_ctx *ctx, const void *pixels, size_t len, int format, uint32_t 
     if (!fmt8 && !fmt16) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: format must be CE_PIXEL_RGB8, RGBA8, RGB16 or RGBA16");
     if (!ce_deep_depth_ok(depth)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: depth must be 8, 10, 12 or 16, got " + std::to_string(depth));
     if (fmt8 && depth != 8) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: an 8-bit format needs depth 8, got " + std::to_string(depth));
-    if (fmt16 && !wide_ok)
+    if (fmt16 && !slot.wide_ok)
         return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: an RGB8 batch takes CE_PIXEL_RGB8 / RGBA8; 16-bit samples need a deep or a linear batch");
     if (len != n_px * ce_pixel_bytes(format)) return ce_bad_length(ctx, n_px * ce_pixel_bytes(format), len);
-    plan->maxv = (1u << depth) - 1u;
-    plan->has_matrix = icc->has_matrix;
-    for (int i = 0; i < 9; i++) plan->m[i] = icc->m[i];
-    plan->depth_out = depth_out, plan->out16 = out16;
-    if (depth_out)
-        if (int rc = icc_thresholds_dev(ctx, depth_out, &plan->d_thr)) return rc;
-    plan->d_tables = icc->d_tables[ce_icc_depth_index(depth)];
-    plan->lut = icc->lut;
-    return CE_OK;
+    return icc_plan(ctx, icc, depth, slot, plan);
 }
 
-// ce_batch_set_*_icc: the frame of upload_cicp around the ICC launch
+// ce_batch_set_*_icc
 int set_icc(ce_batch *b, bool test, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc)
 {
     if (!b) return CE_ERR_INVALID_ARG;
     ce_icc_pixel plan;
-    const uint32_t side = b->depth[test];
     return set_slot(
         b, test, pair_index, ref_index, kind_rule{},
-        [&] { return icc_check(b->ctx, pixels, len, format, depth, icc, (size_t)b->w * b->h, b->linear ? 0 : side ? side : 8, side != 0, b->linear || side, &plan); },
-        [&](uint8_t *slot) -> int {
-            ce_ctx *ctx = b->ctx;
-            CE_HIP(ctx, hipSetDevice(ctx->device));
-            int k;
-            if (int rc = wide_acquire(b, &k)) return rc;
-            std::memcpy(b->h_wide[k], pixels, len);
-            CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], len, hipMemcpyHostToDevice, b->up_stream));
-            if (int rc = ce_launch_icc(ctx, b->up_stream, format, b->d_wide[k], slot, (size_t)b->w * b->h, plan)) return rc;
-            return wide_close(b, k);
+        [&] { return icc_check(b->ctx, pixels, len, format, depth, icc, (size_t)b->w * b->h, icc_slot_of(b, test), &plan); },
+        [&](uint8_t *slot) {
+            return wide_send(b, len, packed_fill(pixels, len), [&](const wide_pair &p) {
+                return ce_launch_icc(b->ctx, b->up_stream, format, p.d, slot, (size_t)b->w * b->h, plan);
+            });
         });
 }
 
@@ -675,7 +717,7 @@ int icc_to_host(ce_ctx *ctx, const void *pixels, size_t len, int format, uint32_
         return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: the output depth must be 8, 10, 12 or 16 bits, got " + std::to_string(depth_out));
     const size_t n_px = (size_t)w * h;
     ce_icc_pixel plan;
-    if (int rc = icc_check(ctx, pixels, len, format, depth, icc, n_px, depth_out, out16, true, &plan)) return rc;
+    if (int rc = icc_check(ctx, pixels, len, format, depth, icc, n_px, icc_slot{depth_out, out16, true}, &plan)) return rc;
     if (out_len != n_px * 3)
         return ce_fail(ctx, CE_ERR_BAD_LENGTH, "ICC ingest: out_len must be " + std::to_string(n_px * 3) + " samples, got " + std::to_string(out_len));
     const size_t sample = depth_out == 0 ? sizeof(float) : out16 ? 2 : 1;
@@ -780,37 +822,36 @@ int upload_yuv(ce_batch *b, uint8_t *dst, const ce_yuv_image *img, yuv_plan &pla
                const ce_icc_pixel *icc = nullptr)
 {
     ce_ctx *ctx = b->ctx;
-    CE_HIP(ctx, hipSetDevice(ctx->device));
+    auto launch = [&] { return launch_yuv_into(ctx, b->up_stream, plan, b->w, b->h, dst, depth, lin, icc); };
     if (img->memory == CE_MEM_DEVICE) {
+        CE_HIP(ctx, hipSetDevice(ctx->device));
         if (int rc = ce_order_write(b, false)) return rc;
-        if (int rc = launch_yuv_into(ctx, b->up_stream, plan, b->w, b->h, dst, depth, lin, icc)) return rc;
+        if (int rc = launch()) return rc;
         b->uploads_pending = true;
         return CE_OK;
     }
+    // 8 bytes per pixel on a linear batch too, whose pairs hold 16
     if (plan.total > (size_t)b->w * b->h * 8) return ce_fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: the packed planes do not fit the staging buffer");
-    int k;
-    if (int rc = wide_acquire(b, &k)) return rc;
-    yuv_pack(img, &plan, b->h_wide[k], b->d_wide[k]);
-    CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], plan.total, hipMemcpyHostToDevice, b->up_stream));
-    if (int rc = launch_yuv_into(ctx, b->up_stream, plan, b->w, b->h, dst, depth, lin, icc)) return rc;
-    return wide_close(b, k);
+    return wide_send(
+        b, plan.total,
+        [&](const wide_pair &p) {
+            yuv_pack(img, &plan, p.h, p.d);
+            return CE_OK;
+        },
+        [&](const wide_pair &) { return launch(); });
 }
 
 // one checked image -> host memory through the leaf scratch, on the context's stream; depth, lin and icc as launch_yuv_into's
 int yuv_leaf(ce_ctx *ctx, const ce_yuv_image *image, yuv_plan &plan, uint32_t w, uint32_t h, uint32_t depth, const ce_linear_pixel *lin, void *out,
              size_t out_bytes, const ce_icc_pixel *icc = nullptr)
 {
-    const bool host = image->memory == CE_MEM_HOST;
-    if (int rc = ce_leaf_scratch(ctx, host ? plan.total : 1, out_bytes)) return rc;
-    if (host) {
-        yuv_pack(image, &plan, ctx->leaf_h, ctx->leaf_d_in);
-        CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_d_in, ctx->leaf_h, plan.total, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (int rc = launch_yuv_into(ctx, ctx->stream, plan, w, h, ctx->leaf_d_out, depth, lin, icc)) return rc;
-    CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_h, ctx->leaf_d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::memcpy(out, ctx->leaf_h, out_bytes);
-    return CE_OK;
+    const bool host = image->memory == CE_MEM_HOST;  // device planes are read in place: nothing goes in
+    return ce_leaf_roundtrip(
+        ctx, host ? plan.total : 0,
+        [&](uint8_t *h_in, uint8_t *d_in) {
+            if (host) yuv_pack(image, &plan, h_in, d_in);
+        },
+        out, out_bytes, [&](uint8_t *, uint8_t *d_out) { return launch_yuv_into(ctx, ctx->stream, plan, w, h, d_out, depth, lin, icc); });
 }
 
 // ce_yuv_to_rgb8 (out16 = false, depth_out = 8) and ce_yuv_to_rgb16
@@ -875,9 +916,9 @@ int set_yuv_tagged(ce_batch *b, bool test, uint32_t pair_index, uint32_t ref_ind
 // ---- Y'CbCr planes with an ICC profile into any batch (yuv_icc.hip) ----------------------------------------
 
 // everything *_yuv refuses about the image and *_icc about the handle, and their joint rule: the integer RGB grid between the
-// two halves (rgb_depth) is one of the handle's four and no coarser than the samples.  depth_out, out16: the slot, as icc_check's
-int yuv_icc_check(ce_ctx *ctx, const ce_yuv_image *img, uint32_t rgb_depth, const ce_icc *icc, uint32_t w, uint32_t h, uint32_t depth_out, bool out16,
-                  yuv_plan *plan, ce_icc_pixel *px)
+// two halves (rgb_depth) is one of the handle's four and no coarser than the samples
+int yuv_icc_check(ce_ctx *ctx, const ce_yuv_image *img, uint32_t rgb_depth, const ce_icc *icc, uint32_t w, uint32_t h, icc_slot slot, yuv_plan *plan,
+                  ce_icc_pixel *px)
 {
     if (!img) return ce_fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ingest: null image");
     if (!icc) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: null pointer");
@@ -888,15 +929,7 @@ int yuv_icc_check(ce_ctx *ctx, const ce_yuv_image *img, uint32_t rgb_depth, cons
     if (rgb_depth < (uint32_t)img->depth)
         return ce_fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ICC ingest: rgb_depth " + std::to_string(rgb_depth) + " is under the samples' " +
                                                     std::to_string(img->depth) + " bits");
-    px->maxv = (1u << rgb_depth) - 1u;
-    px->has_matrix = icc->has_matrix;
-    for (int i = 0; i < 9; i++) px->m[i] = icc->m[i];
-    px->depth_out = depth_out, px->out16 = out16;
-    if (depth_out)
-        if (int rc = icc_thresholds_dev(ctx, depth_out, &px->d_thr)) return rc;
-    px->d_tables = icc->d_tables[ce_icc_depth_index(rgb_depth)];
-    px->lut = icc->lut;
-    return CE_OK;
+    return icc_plan(ctx, icc, rgb_depth, slot, px);
 }
 
 // ce_batch_set_*_yuv_icc: set_yuv's frame around the fused launch, into a linear, an RGB8 or a deep batch
@@ -905,10 +938,9 @@ int set_yuv_icc(ce_batch *b, bool test, uint32_t pair_index, uint32_t ref_index,
     if (!b) return CE_ERR_INVALID_ARG;
     yuv_plan plan;
     ce_icc_pixel px;
-    const uint32_t side = b->depth[test];
     return set_slot(
         b, test, pair_index, ref_index, kind_rule{},
-        [&] { return yuv_icc_check(b->ctx, image, rgb_depth, icc, b->w, b->h, b->linear ? 0 : side ? side : 8, side != 0, &plan, &px); },
+        [&] { return yuv_icc_check(b->ctx, image, rgb_depth, icc, b->w, b->h, icc_slot_of(b, test), &plan, &px); },
         [&](uint8_t *slot) { return upload_yuv(b, slot, image, plan, 0, nullptr, &px); });
 }
 
@@ -923,7 +955,7 @@ int yuv_icc_to_host(ce_ctx *ctx, const ce_yuv_image *image, uint32_t rgb_depth, 
         return ce_fail(ctx, CE_ERR_INVALID_ARG, "Y'CbCr ICC ingest: the output depth must be 8, 10, 12 or 16 bits, got " + std::to_string(depth_out));
     yuv_plan plan;
     ce_icc_pixel px;
-    if (int rc = yuv_icc_check(ctx, image, rgb_depth, icc, w, h, depth_out, out16, &plan, &px)) return rc;
+    if (int rc = yuv_icc_check(ctx, image, rgb_depth, icc, w, h, icc_slot{depth_out, out16, true}, &plan, &px)) return rc;
     const size_t samples = (size_t)w * h * 3;
     if (out_len != samples)
         return ce_fail(ctx, CE_ERR_BAD_LENGTH, "Y'CbCr ICC ingest: out_len must be " + std::to_string(samples) + " samples, got " + std::to_string(out_len));
@@ -963,35 +995,19 @@ int alpha_check(ce_batch *b, size_t len, int format, uint32_t n_bg, const uint16
 // one RGBA image through the wide staging pair into n_bg consecutive slots from dst on
 int upload_over(ce_batch *b, uint8_t *dst, const void *pixels, size_t len, int format, uint32_t depth, uint32_t n_bg, const uint16_t *backgrounds)
 {
-    ce_ctx *ctx = b->ctx;
-    CE_HIP(ctx, hipSetDevice(ctx->device));
-    int k;
-    if (int rc = wide_acquire(b, &k)) return rc;
-    std::memcpy(b->h_wide[k], pixels, len);
-    CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], len, hipMemcpyHostToDevice, b->up_stream));
-    if (int rc = ce_launch_alpha(ctx, b->up_stream, b->d_wide[k], format == CE_PIXEL_RGBA16, dst, depth != 0, depth ? depth : 8, (size_t)b->w * b->h, n_bg,
-                                 backgrounds))
-        return rc;
-    return wide_close(b, k);
+    return wide_send(b, len, packed_fill(pixels, len), [&](const wide_pair &p) {
+        return ce_launch_alpha(b->ctx, b->up_stream, p.d, format == CE_PIXEL_RGBA16, dst, depth != 0, depth ? depth : 8, (size_t)b->w * b->h, n_bg, backgrounds);
+    });
 }
 
-// ce_batch_set_*_over: set_slot's frame for n_bg consecutive slots from `first` on, the test slots bound to ref_indices[]
+// ce_batch_set_*_over (a linear batch is refused behind a null pointer, by alpha_check)
 int set_over(ce_batch *b, bool test, uint32_t first, const uint32_t *ref_indices, const void *pixels, size_t len, int format, uint32_t n_bg,
              const uint16_t *backgrounds)
 {
-    if (!b) return CE_ERR_INVALID_ARG;
-    if ((test && !ref_indices) || !pixels || !backgrounds) return ce_fail(b->ctx, CE_ERR_INVALID_ARG, "alpha compositing: null pointer");
-    if (int rc = alpha_check(b, len, format, n_bg, backgrounds, b->depth[test])) return rc;
-    const uint32_t slots = test ? b->max_pairs : b->max_refs;
-    if (first > slots || n_bg > slots - first)
-        return ce_fail(b->ctx, CE_ERR_INVALID_ARG, std::string("alpha compositing: ") + (test ? "test" : "reference") + " slots [" + std::to_string(first) +
-                                                       ", " + std::to_string((uint64_t)first + n_bg) + ") outside the " + std::to_string(slots) + " slots");
-    for (uint32_t k = 0; test && k < n_bg; k++)
-        if (ref_indices[k] >= b->max_refs) return ce_fail(b->ctx, CE_ERR_INVALID_ARG, "alpha compositing: ref index " + std::to_string(ref_indices[k]) + " out of range");
-    for (uint32_t k = 0; test && k < n_bg; k++)
-        if (int rc = ce_batch_bind_pair(b, first + k, ref_indices[k])) return rc;
-    if (!test) ce_invalidate_reference_state(b);
-    return upload_over(b, (test ? b->d_tests : b->d_refs) + (size_t)first * b->img_bytes, pixels, len, format, b->depth[test], n_bg, backgrounds);
+    return set_slots(
+        b, test, first, n_bg, ref_indices, "alpha compositing: ", kind_rule{}, !pixels || !backgrounds,
+        [&] { return alpha_check(b, len, format, n_bg, backgrounds, b->depth[test]); },
+        [&](uint8_t *dst) { return upload_over(b, dst, pixels, len, format, b->depth[test], n_bg, backgrounds); });
 }
 
 // one image over one colour -> host memory through the leaf scratch, on the context's stream
@@ -1063,39 +1079,24 @@ int over_format_check(ce_ctx *ctx, int format)
     return CE_OK;
 }
 
-// Every ce_batch_set_*_*_over call: set_over's frame - n_bg consecutive slots from `first` on, the test slots bound to
-// ref_indices[] - around a route's check(ov), which holds its own refusals and fills its plan and the alpha table, and its
-// launch(d_src, d_dst, ov) behind the copy of the `len` bytes at `pixels` through the wide staging pair.
+// Every ce_batch_set_*_*_over call: set_slots around a route's check(ov), which holds its own refusals and fills its plan and
+// the alpha table, and its launch(d_src, d_dst, ov) behind the copy of the `len` bytes at `pixels` through the wide staging pair.
 template <class Check, class Launch>
 int set_over_linear(ce_batch *b, bool test, uint32_t first, const uint32_t *ref_indices, const void *pixels, size_t len, uint32_t n_bg,
                     const float *backgrounds, Check check, Launch launch)
 {
-    if (!b) return CE_ERR_INVALID_ARG;
-    ce_ctx *ctx = b->ctx;
-    if (!b->linear) return ce_fail(ctx, CE_ERR_INVALID_ARG, kOverWantsLinear);
-    if ((test && !ref_indices) || !pixels || !backgrounds) return ce_fail(ctx, CE_ERR_INVALID_ARG, "linear-light compositing: null pointer");
     ce_over_plan ov;
-    if (int rc = check(&ov)) return rc;
-    if (int rc = over_backgrounds(ctx, n_bg, backgrounds, &ov)) return rc;
-    const uint32_t slots = test ? b->max_pairs : b->max_refs;
-    if (first > slots || n_bg > slots - first)
-        return ce_fail(ctx, CE_ERR_INVALID_ARG, std::string("linear-light compositing: ") + (test ? "test" : "reference") + " slots [" + std::to_string(first) +
-                                                    ", " + std::to_string((uint64_t)first + n_bg) + ") outside the " + std::to_string(slots) + " slots");
-    for (uint32_t k = 0; test && k < n_bg; k++)
-        if (ref_indices[k] >= b->max_refs)
-            return ce_fail(ctx, CE_ERR_INVALID_ARG, "linear-light compositing: ref index " + std::to_string(ref_indices[k]) + " out of range");
-    for (uint32_t k = 0; test && k < n_bg; k++)
-        if (int rc = ce_batch_bind_pair(b, first + k, ref_indices[k])) return rc;
-    if (!test) ce_invalidate_reference_state(b);
-    ov.slot_floats = (size_t)b->w * b->h * 3;
-    float *dst = reinterpret_cast<float *>((test ? b->d_tests : b->d_refs) + (size_t)first * b->img_bytes);
-    CE_HIP(ctx, hipSetDevice(ctx->device));
-    int k;
-    if (int rc = wide_acquire(b, &k)) return rc;
-    std::memcpy(b->h_wide[k], pixels, len);
-    CE_HIP(ctx, hipMemcpyAsync(b->d_wide[k], b->h_wide[k], len, hipMemcpyHostToDevice, b->up_stream));
-    if (int rc = launch(b->up_stream, b->d_wide[k], dst, ov)) return rc;
-    return wide_close(b, k);
+    return set_slots(
+        b, test, first, n_bg, ref_indices, "linear-light compositing: ", kind_rule{false, kOverWantsLinear}, !pixels || !backgrounds,
+        [&]() -> int {
+            if (int rc = check(&ov)) return rc;
+            return over_backgrounds(b->ctx, n_bg, backgrounds, &ov);
+        },
+        [&](uint8_t *dst) {
+            ov.slot_floats = (size_t)b->w * b->h * 3;
+            return wide_send(b, len, packed_fill(pixels, len),
+                             [&](const wide_pair &p) { return launch(b->up_stream, p.d, reinterpret_cast<float *>(dst), ov); });
+        });
 }
 
 // One image over one background -> packed f32 RGB in host memory, through the leaf scratch on the context's stream
@@ -1159,7 +1160,7 @@ int icc_over_check(ce_ctx *ctx, const void *pixels, size_t len, int format, uint
 {
     if (!icc) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC ingest: null pointer");
     if (int rc = over_format_check(ctx, format)) return rc;
-    if (int rc = icc_check(ctx, pixels, len, format, depth, icc, n_px, 0, false, true, plan)) return rc;
+    if (int rc = icc_check(ctx, pixels, len, format, depth, icc, n_px, icc_slot{0, false, true}, plan)) return rc;
     return alpha_table_dev(ctx, depth, &ov->d_atab);
 }
 
@@ -1217,44 +1218,6 @@ int ce_batch_set_reference_fmt(ce_batch *b, uint32_t ref_index, const void *pixe
 int ce_batch_set_test_fmt(ce_batch *b, uint32_t pair_index, uint32_t ref_index, const void *pixels, size_t len, int format)
 {
     return set_fmt(b, true, pair_index, ref_index, pixels, len, format, nullptr);
-}
-
-// ICC -> sRGB colour tables: [2^24] r | g << 8 | b << 16 on the device (struct ce_lut, ce_internal.h)
-int ce_lut_create(ce_ctx *ctx, const uint8_t *table, size_t table_len, ce_lut **out)
-{
-    if (!ctx || !table || !out) return CE_ERR_INVALID_ARG;
-    *out = nullptr;
-    const size_t want = (size_t)3 << 24;
-    if (table_len != want)
-        return ce_fail(ctx, CE_ERR_BAD_LENGTH, "Invalid colour table size: expected " + std::to_string(want) + " bytes, got " + std::to_string(table_len));
-    CE_HIP(ctx, hipSetDevice(ctx->device));
-    uint8_t *d_packed = nullptr;
-    uint32_t *d_table = nullptr;
-    CE_HIP(ctx, hipMalloc(&d_packed, want));
-    if (hipMalloc(&d_table, sizeof(uint32_t) << 24) != hipSuccess) {
-        hipFree(d_packed);
-        return ce_fail(ctx, CE_ERR_BACKEND, "hipMalloc failed (colour table)");
-    }
-    int rc = CE_OK;
-    if (hipMemcpyAsync(d_packed, table, want, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = ce_fail(ctx, CE_ERR_BACKEND, "H2D failed (colour table)");
-    if (rc == CE_OK) rc = ce_launch_lut_expand(ctx, ctx->stream, d_packed, d_table);
-    if (rc == CE_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = ce_fail(ctx, CE_ERR_BACKEND, "sync failed (colour table)");
-    hipFree(d_packed);
-    if (rc != CE_OK) {
-        hipFree(d_table);
-        return rc;
-    }
-    *out = new ce_lut{ctx, d_table};
-    return CE_OK;
-}
-
-void ce_lut_destroy(ce_lut *lut)
-{
-    if (!lut) return;
-    hipSetDevice(lut->ctx->device);
-    hipStreamSynchronize(lut->ctx->stream);
-    hipFree(lut->d_table);
-    delete lut;
 }
 
 int ce_batch_set_reference_lut(ce_batch *b, uint32_t ref_index, const void *pixels, size_t len, int format, const ce_lut *lut)
@@ -1366,121 +1329,7 @@ int ce_gainmap_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int format
     return gainmap_to_linear(ctx, pixels, len, format, c, map, g, w, h, out, out_len);
 }
 
-// matrix/TRC ICC profiles; the pure host functions are in ce_icc.cpp
-int ce_icc_create(ce_ctx *ctx, const uint8_t *bytes, size_t len, ce_icc **out)
-{
-    if (!ctx || !out) return CE_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (!bytes) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC profile: null pointer");
-    ce_icc_description d;
-    ce_icc_describe(bytes, len, &d);
-    if (d.kind != CE_ICC_SUPPORTED) {
-        static const char *const kKinds[4] = {"", "a LUT-based profile", "not an RGB profile with an XYZ connection space", "a malformed profile"};
-        return ce_fail(ctx, CE_ERR_INVALID_ARG, std::string("ICC profile: ") + kKinds[d.kind & 3] + " (" + d.reason + ")");
-    }
-    ce_icc *icc = new ce_icc{ctx, {}, false, {}};
-    ce_icc_build_matrix(bytes, len, icc->m);
-    for (int i = 0; i < 9; i++) icc->has_matrix |= icc->m[i] != ((i % 4 == 0) ? 1.0f : 0.0f);
-    // the tone tables of all four source depths now (0.85 MB of device memory in all): the handle is read-only from here on
-    int rc = hipSetDevice(ctx->device) == hipSuccess ? CE_OK : ce_fail(ctx, CE_ERR_BACKEND, "hipSetDevice failed (ICC profile)");
-    for (uint32_t depth : {8u, 10u, 12u, 16u}) {
-        if (rc != CE_OK) break;
-        std::vector<float> host((size_t)3 << depth);
-        ce_icc_build_tables(bytes, len, depth, host.data(), host.size());
-        void *d = nullptr;
-        rc = ce_device_table(ctx, host.data(), host.size() * sizeof(float), "ICC tone tables", &d);
-        icc->d_tables[ce_icc_depth_index(depth)] = static_cast<float *>(d);
-    }
-    if (rc != CE_OK) {
-        for (float *t : icc->d_tables) hipFree(t);
-        delete icc;
-        return rc;
-    }
-    *out = icc;
-    return CE_OK;
-}
-
-// what both flavours of handle own
-static void icc_free(ce_icc *icc)
-{
-    for (float *t : icc->d_tables) hipFree(t);
-    if (icc->lut) {
-        hipFree(icc->lut->d_clut);
-        hipFree(icc->lut->d_samples);
-        delete icc->lut;
-    }
-    delete icc;
-}
-
-void ce_icc_destroy(ce_icc *icc)
-{
-    if (!icc) return;
-    hipSetDevice(icc->ctx->device);
-    hipDeviceSynchronize();  // the batches' upload streams may still gather from the tables
-    icc_free(icc);
-}
-
-// LUT-based ICC profiles; the pure host functions are in ce_icc_lut.cpp
-int ce_icc_lut_create(ce_ctx *ctx, const uint8_t *bytes, size_t len, int intent, int interpolation, ce_icc **out)
-{
-    if (!ctx || !out) return CE_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (!bytes) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC profile: null pointer");
-    if (intent < 0 || intent > 2) return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC profile: intent must be 0, 1 or 2, got " + std::to_string(intent));
-    if (interpolation != CE_ICC_CLUT_TRILINEAR && interpolation != CE_ICC_CLUT_TETRAHEDRAL)
-        return ce_fail(ctx, CE_ERR_INVALID_ARG, "ICC profile: interpolation must be CE_ICC_CLUT_TRILINEAR or CE_ICC_CLUT_TETRAHEDRAL");
-    ce_icc_lut_description d;
-    ce_icc_lut_describe(bytes, len, intent, &d);
-    if (d.kind != CE_ICC_LUT_SUPPORTED) {
-        static const char *const kKinds[4] = {"", "not a LUT-based profile", "a LUT-based profile of a kind not taken", "a malformed profile"};
-        return ce_fail(ctx, CE_ERR_INVALID_ARG, std::string("ICC profile: ") + kKinds[d.kind & 3] + " (" + d.reason + ")");
-    }
-    ce_icc *icc = new ce_icc{ctx, {}, true, {}};
-    ce_icc_lut *lut = icc->lut = new ce_icc_lut{};
-    ce_icc_lut_build_pcs_matrix(icc->m);
-    lut->tetra = interpolation == CE_ICC_CLUT_TETRAHEDRAL;
-    lut->has_matrix = (d.stages & CE_ICC_STAGE_MATRIX) != 0;
-    ce_icc_lut_build_matrix(bytes, len, intent, lut->mat);
-    constexpr uint32_t kLab = 0x4c616220u, kMft2 = 0x6d667432u;  // 'Lab ', 'mft2'
-    lut->pcs = d.pcs != kLab ? 0u : d.tag_type == kMft2 ? 2u : 1u;
-    for (int k = 0; k < 3; k++) lut->grid[k] = d.grid[k];
-    // everything the kernel gathers from now (the input tables of all four depths, 0.85 MB; the CLUT, 16 bytes a node; the
-    // sampled curves): the handle is read-only from here on
-    int rc = hipSetDevice(ctx->device) == hipSuccess ? CE_OK : ce_fail(ctx, CE_ERR_BACKEND, "hipSetDevice failed (ICC profile)");
-    for (uint32_t depth : {8u, 10u, 12u, 16u}) {
-        if (rc != CE_OK) break;
-        std::vector<float> host((size_t)3 << depth);
-        ce_icc_lut_build_input_tables(bytes, len, intent, depth, host.data(), host.size());
-        void *p = nullptr;
-        rc = ce_device_table(ctx, host.data(), host.size() * sizeof(float), "ICC input tables", &p);
-        icc->d_tables[ce_icc_depth_index(depth)] = static_cast<float *>(p);
-    }
-    if (rc == CE_OK && (d.stages & CE_ICC_STAGE_CLUT)) {
-        std::vector<float> host((size_t)d.grid[0] * d.grid[1] * d.grid[2] * 4);
-        ce_icc_lut_build_clut(bytes, len, intent, host.data(), host.size());
-        void *p = nullptr;
-        rc = ce_device_table(ctx, host.data(), host.size() * sizeof(float), "ICC CLUT", &p);
-        lut->d_clut = static_cast<float *>(p);
-    }
-    if (rc == CE_OK) {
-        size_t needed = 0;
-        ce_icc_lut_build_curves(bytes, len, intent, lut->curves, nullptr, 0, &needed);
-        std::vector<float> host(needed);
-        ce_icc_lut_build_curves(bytes, len, intent, lut->curves, host.data(), host.size(), &needed);
-        if (needed) {
-            void *p = nullptr;
-            rc = ce_device_table(ctx, host.data(), host.size() * sizeof(float), "ICC curve samples", &p);
-            lut->d_samples = static_cast<float *>(p);
-        }
-    }
-    if (rc != CE_OK) {
-        icc_free(icc);
-        return rc;
-    }
-    *out = icc;
-    return CE_OK;
-}
-
+// ICC profiles of both flavours (DESIGN.md sections 22, 23); the handles are made in ce_handles.cpp
 int ce_batch_set_reference_icc(ce_batch *b, uint32_t ref_index, const void *pixels, size_t len, int format, uint32_t depth, const ce_icc *icc)
 {
     return set_icc(b, false, 0, ref_index, pixels, len, format, depth, icc);

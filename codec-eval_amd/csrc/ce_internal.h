@@ -1,4 +1,4 @@
-// Internal declarations shared by the host runtime (ce_api.cpp, ce_ingest.cpp, ce_leaf.cpp, ce_resample.cpp) and the
+// Internal declarations shared by the host runtime (ce_api.cpp, ce_ingest.cpp, ce_handles.cpp, ce_leaf.cpp, ce_resample.cpp) and the
 // gfx950 kernels.
 // Nothing here is part of the ABI; the ABI is include/ce_metrics.h.
 #pragma once
@@ -193,7 +193,7 @@ struct ce_batch {
     bool inline_pending = false;  // a slot was written on the context's stream since the last launch (ce_ingest.cpp: ce_order_write)
     bool counted_in_flight = false;  // this batch is in the device's launched-and-not-collected count (ce_api.cpp: g_in_flight)
     // the wide staging pairs of every image a conversion kernel follows: one pinned + one device staging image each, made
-    // on first use and handed out in turn (ce_ingest.cpp: wide_acquire, which states their size)
+    // on first use and handed out in turn (ce_ingest.cpp: wide_send, which states their size and alone touches them)
     uint8_t *h_wide[2] = {}, *d_wide[2] = {};
     hipEvent_t ev_wide[2] = {};
     bool wide_busy[2] = {};
@@ -325,7 +325,7 @@ struct ce_lut {
     ce_ctx *ctx;
     uint32_t *d_table;  // [2^24] r | g << 8 | b << 16
 };
-// a matrix/TRC ICC profile on the device (ce_icc_create; ce_ingest.cpp): its matrix and the device copies of
+// a matrix/TRC ICC profile on the device (ce_icc_create; ce_handles.cpp): its matrix and the device copies of
 // ce_icc_build_tables for the four source depths 8, 10, 12 and 16, all made by ce_icc_create - nothing in the handle changes
 // after that - and kept until the handle goes
 struct ce_icc_lut;
@@ -365,9 +365,12 @@ int ce_upload_many(ce_batch *b, const std::vector<ce_upload_job> &jobs);
 // `lut` (nullptr: nothing) over the RGB8 image at `slot`, on the batch's upload stream behind its copy (ce_ingest.cpp)
 int ce_apply_lut(ce_batch *b, uint8_t *slot, const ce_lut *lut);
 // the context's leaf scratch grown to in_bytes / out_bytes, and one host image through it and `launch(d_in, d_out)` on the
-// context's stream, complete on return (ce_leaf.cpp)
+// context's stream, complete on return (ce_leaf.cpp): the `in_bytes` at `in`, or what fill(h_in, d_in) writes into the pinned
+// h_in, whose device copy will be at d_in (in_bytes = 0: nothing is copied in)
 int ce_leaf_scratch(ce_ctx *ctx, size_t in_bytes, size_t out_bytes);
 int ce_leaf_roundtrip(ce_ctx *ctx, const void *in, size_t in_bytes, void *out, size_t out_bytes,
+                      const std::function<int(uint8_t *, uint8_t *)> &launch);
+int ce_leaf_roundtrip(ce_ctx *ctx, size_t in_bytes, const std::function<void(uint8_t *, uint8_t *)> &fill, void *out, size_t out_bytes,
                       const std::function<int(uint8_t *, uint8_t *)> &launch);
 
 // host table -> device memory of `b`, complete on return, without draining the context's stream (ce_api.cpp)
@@ -569,7 +572,7 @@ struct ce_gainmap_plan {
 int ce_launch_gainmap(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, const uint8_t *d_side, float *d_dst, uint32_t w, uint32_t h,
                       const ce_gainmap_plan &plan);
 
-// What one ICC ingest converts a pixel with (checked and filled by ce_ingest.cpp: icc_check): the profile's three device
+// What one ICC ingest converts a pixel with (checked by ce_ingest.cpp: icc_check, filled by its icc_plan): the profile's three device
 // tables of the source depth, [3][maxv + 1] floats, its matrix (has_matrix: colorants other than the canonical sRGB profile's)
 // and, for an integer slot of depth_out bits (0: a linear slot; out16: u16 samples), the sRGB code thresholds of that depth
 // with d_thr[k] = T[k] for k = 1 .. 2^depth_out - 1

@@ -31,20 +31,28 @@ int ce_leaf_scratch(ce_ctx *ctx, size_t in_bytes, size_t out_bytes)
     return rc;
 }
 
-// host image in -> kernel -> host image out through the leaf scratch, everything on the context's stream
-int ce_leaf_roundtrip(ce_ctx *ctx, const void *in, size_t in_bytes, void *out, size_t out_bytes,
+// fill(h_in, d_in) writes in_bytes of input into h_in (d_in is where its device copy will be; nothing with in_bytes = 0, for
+// input that is on the device already) -> kernel -> host image out through the leaf scratch, everything on the context's stream
+int ce_leaf_roundtrip(ce_ctx *ctx, size_t in_bytes, const std::function<void(uint8_t *, uint8_t *)> &fill, void *out, size_t out_bytes,
                       const std::function<int(uint8_t *, uint8_t *)> &launch)
 {
-    int rc = ce_leaf_scratch(ctx, in_bytes, out_bytes);
+    int rc = ce_leaf_scratch(ctx, in_bytes ? in_bytes : 1, out_bytes);
     if (rc != CE_OK) return rc;
-    std::memcpy(ctx->leaf_h, in, in_bytes);
-    CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_d_in, ctx->leaf_h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    fill(ctx->leaf_h, ctx->leaf_d_in);
+    if (in_bytes) CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_d_in, ctx->leaf_h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     rc = launch(ctx->leaf_d_in, ctx->leaf_d_out);
     if (rc != CE_OK) return rc;
     CE_HIP(ctx, hipMemcpyAsync(ctx->leaf_h, ctx->leaf_d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
     std::memcpy(out, ctx->leaf_h, out_bytes);
     return CE_OK;
+}
+
+// the same for a host image that is packed already
+int ce_leaf_roundtrip(ce_ctx *ctx, const void *in, size_t in_bytes, void *out, size_t out_bytes,
+                      const std::function<int(uint8_t *, uint8_t *)> &launch)
+{
+    return ce_leaf_roundtrip(ctx, in_bytes, [&](uint8_t *h_in, uint8_t *) { std::memcpy(h_in, in, in_bytes); }, out, out_bytes, launch);
 }
 
 // ---- the kept one-pair batches -----------------------------------------------------------------------------------------------

@@ -18,8 +18,9 @@
 #include "ce_internal.h"
 
 #include "cicp_kernel.h"
-#include "hlg_pixel.h"
 #include "over_linear_kernel.h"
+#include "packed_ladder.h"
+#include "tagged_pick.h"
 
 int ce_launch_linear_sanitise(ce_ctx *ctx, hipStream_t stream, const float *d_src, float *d_dst, size_t n_samples)
 {
@@ -34,35 +35,6 @@ int ce_launch_linear_sanitise(ce_ctx *ctx, hipStream_t stream, const float *d_sr
     return CE_OK;
 }
 
-namespace {
-
-// what a launch reports to the profiler: [HLG][format][with the primaries matrix]
-constexpr const char *kTaggedNames[2][4][2] = {
-    {{"cicp_rgb8", "cicp_rgb8_m"}, {"cicp_rgba8", "cicp_rgba8_m"}, {"cicp_rgb16", "cicp_rgb16_m"}, {"cicp_rgba16", "cicp_rgba16_m"}},
-    {{"hlg_rgb8", "hlg_rgb8_m"}, {"hlg_rgba8", "hlg_rgba8_m"}, {"hlg_rgb16", "hlg_rgb16_m"}, {"hlg_rgba16", "hlg_rgba16_m"}}};
-
-template <int FMT, template <bool> class Px, class Args>
-void launch_format(ce_ctx *ctx, hipStream_t stream, const char *const (&names)[2], dim3 grid, const Args &a, bool matrix)
-{
-    if (matrix) CE_LAUNCH_ON(ctx, stream, names[1], (k_tagged<FMT, Px<true>>), grid, dim3(kCicpBlock), 0, Px<true>{a});
-    else CE_LAUNCH_ON(ctx, stream, names[0], (k_tagged<FMT, Px<false>>), grid, dim3(kCicpBlock), 0, Px<false>{a});
-}
-
-// false: not one of the four formats
-template <template <bool> class Px, class Args>
-bool launch_pixel(ce_ctx *ctx, hipStream_t stream, int format, const char *const (&names)[4][2], dim3 grid, const Args &a, bool matrix)
-{
-    switch (format) {
-        case CE_PIXEL_RGB8: launch_format<CE_PIXEL_RGB8, Px>(ctx, stream, names[0], grid, a, matrix); return true;
-        case CE_PIXEL_RGBA8: launch_format<CE_PIXEL_RGBA8, Px>(ctx, stream, names[1], grid, a, matrix); return true;
-        case CE_PIXEL_RGB16: launch_format<CE_PIXEL_RGB16, Px>(ctx, stream, names[2], grid, a, matrix); return true;
-        case CE_PIXEL_RGBA16: launch_format<CE_PIXEL_RGBA16, Px>(ctx, stream, names[3], grid, a, matrix); return true;
-        default: return false;
-    }
-}
-
-}  // namespace
-
 int ce_launch_tagged(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, float *d_dst, size_t n_pixels, const ce_linear_pixel &px)
 {
     if (n_pixels == 0) return CE_OK;
@@ -71,13 +43,15 @@ int ce_launch_tagged(ce_ctx *ctx, hipStream_t stream, int format, const void *d_
         ctx->err = px.hlg ? "HLG ingest: bad launch" : "CICP ingest: bad launch";
         return CE_ERR_INVALID_ARG;
     }
-    hlg_args a{};  // the CICP pixel takes its `c` alone
-    a.c.src = d_src, a.c.n_pixels = n_pixels;
-    ce_fill_pixel_args(a, d_dst, px);
     const dim3 grid((uint32_t)blocks);
-    // the one place that knows which pixel a plan means
-    if (!(px.hlg ? launch_pixel<hlg_px>(ctx, stream, format, kTaggedNames[1], grid, a, px.has_matrix)
-                 : launch_pixel<cicp_px>(ctx, stream, format, kTaggedNames[0], grid, a.c, px.has_matrix))) {
+    bool known = false;
+    tagged_pick(px, d_src, n_pixels, d_dst, [&](const auto &pixel, const char *stem, const char *m) {
+        known = packed_ladder(format, [&](auto fmt) {
+            constexpr int FMT = decltype(fmt)::value;
+            CE_LAUNCH_ON(ctx, stream, packed_profile_name(stem, "", FMT, m).s, (k_tagged<FMT, std::decay_t<decltype(pixel)>>), grid, dim3(kCicpBlock), 0, pixel);
+        });
+    });
+    if (!known) {
         ctx->err = std::string(px.hlg ? "HLG" : "CICP") + " ingest: format must be RGB8, RGBA8, RGB16 or RGBA16";
         return CE_ERR_INVALID_ARG;
     }
@@ -87,47 +61,25 @@ int ce_launch_tagged(ce_ctx *ctx, hipStream_t stream, int format, const void *d_
 
 // ---- the same pixels blended over solid backgrounds in linear light (over_linear_kernel.h) ----------------
 
-namespace {
-
-// [HLG][RGBA16][with the primaries matrix]
-constexpr const char *kOverNames[2][2][2] = {{{"cicp_over_rgba8", "cicp_over_rgba8_m"}, {"cicp_over_rgba16", "cicp_over_rgba16_m"}},
-                                             {{"hlg_over_rgba8", "hlg_over_rgba8_m"}, {"hlg_over_rgba16", "hlg_over_rgba16_m"}}};
-
-template <int FMT, template <bool> class Px, class Args>
-void launch_over_format(ce_ctx *ctx, hipStream_t stream, const char *const (&names)[2], dim3 grid, const Args &a, bool matrix, const over_args &o)
-{
-    if (matrix) CE_LAUNCH_ON(ctx, stream, names[1], (k_tagged_over<FMT, Px<true>>), grid, dim3(kCicpBlock), 0, Px<true>{a}, o);
-    else CE_LAUNCH_ON(ctx, stream, names[0], (k_tagged_over<FMT, Px<false>>), grid, dim3(kCicpBlock), 0, Px<false>{a}, o);
-}
-
-template <template <bool> class Px, class Args>
-void launch_over_pixel(ce_ctx *ctx, hipStream_t stream, bool wide, const char *const (&names)[2][2], dim3 grid, const Args &a, bool matrix,
-                       const over_args &o)
-{
-    if (wide) launch_over_format<CE_PIXEL_RGBA16, Px>(ctx, stream, names[1], grid, a, matrix, o);
-    else launch_over_format<CE_PIXEL_RGBA8, Px>(ctx, stream, names[0], grid, a, matrix, o);
-}
-
-}  // namespace
-
 int ce_launch_tagged_over(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, float *d_dst, size_t n_pixels, const ce_linear_pixel &px,
                           const ce_over_plan &ov)
 {
     if (n_pixels == 0) return CE_OK;
     const size_t blocks = std::max<size_t>((n_pixels / 4 + kCicpBlock - 1) / kCicpBlock, 1);
-    if (blocks > 0x7fffffffu || !px.d_table || !ov.d_atab || ov.n_bg == 0 || ov.n_bg > CE_MAX_BACKGROUNDS ||
-        (format != CE_PIXEL_RGBA8 && format != CE_PIXEL_RGBA16)) {
+    if (blocks > 0x7fffffffu || !px.d_table || !ov.d_atab || ov.n_bg == 0 || ov.n_bg > CE_MAX_BACKGROUNDS || !packed_has_alpha(format)) {
         ctx->err = px.hlg ? "HLG composite: bad launch" : "CICP composite: bad launch";
         return CE_ERR_INVALID_ARG;
     }
-    hlg_args a{};  // the CICP pixel takes its `c` alone
-    a.c.src = d_src, a.c.n_pixels = n_pixels;
-    ce_fill_pixel_args(a, d_dst, px);
     over_args o{};
     ce_fill_over_args(o, ov);
     const dim3 grid((uint32_t)blocks);
-    if (px.hlg) launch_over_pixel<hlg_px>(ctx, stream, format == CE_PIXEL_RGBA16, kOverNames[1], grid, a, px.has_matrix, o);
-    else launch_over_pixel<cicp_px>(ctx, stream, format == CE_PIXEL_RGBA16, kOverNames[0], grid, a.c, px.has_matrix, o);
+    tagged_pick(px, d_src, n_pixels, d_dst, [&](const auto &pixel, const char *stem, const char *m) {
+        packed_ladder(format, [&](auto fmt) {
+            constexpr int FMT = decltype(fmt)::value;
+            if constexpr (packed_has_alpha(FMT))
+                CE_LAUNCH_ON(ctx, stream, packed_profile_name(stem, "_over", FMT, m).s, (k_tagged_over<FMT, std::decay_t<decltype(pixel)>>), grid, dim3(kCicpBlock), 0, pixel, o);
+        });
+    });
     CE_HIP(ctx, hipGetLastError());
     return CE_OK;
 }

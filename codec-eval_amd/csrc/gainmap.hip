@@ -15,30 +15,7 @@
 #include "ce_internal.h"
 
 #include "gainmap_kernel.h"
-
-namespace {
-
-// what a launch reports to the profiler: [format][three-channel map][with the primaries matrix]
-constexpr const char *kGainmapNames[4][2][2] = {{{"gainmap_rgb8_1", "gainmap_rgb8_1_m"}, {"gainmap_rgb8_3", "gainmap_rgb8_3_m"}},
-                                                {{"gainmap_rgba8_1", "gainmap_rgba8_1_m"}, {"gainmap_rgba8_3", "gainmap_rgba8_3_m"}},
-                                                {{"gainmap_rgb16_1", "gainmap_rgb16_1_m"}, {"gainmap_rgb16_3", "gainmap_rgb16_3_m"}},
-                                                {{"gainmap_rgba16_1", "gainmap_rgba16_1_m"}, {"gainmap_rgba16_3", "gainmap_rgba16_3_m"}}};
-
-template <int FMT, int NCH>
-void launch_matrix(ce_ctx *ctx, hipStream_t stream, const char *const (&names)[2], dim3 grid, const gainmap_args &a, bool matrix)
-{
-    if (matrix) CE_LAUNCH_ON(ctx, stream, names[1], (k_gainmap<FMT, NCH, true>), grid, dim3(kCicpBlock), 0, a);
-    else CE_LAUNCH_ON(ctx, stream, names[0], (k_gainmap<FMT, NCH, false>), grid, dim3(kCicpBlock), 0, a);
-}
-
-template <int FMT>
-void launch_channels(ce_ctx *ctx, hipStream_t stream, const char *const (&names)[2][2], dim3 grid, const gainmap_args &a, bool three, bool matrix)
-{
-    if (three) launch_matrix<FMT, 3>(ctx, stream, names[1], grid, a, matrix);
-    else launch_matrix<FMT, 1>(ctx, stream, names[0], grid, a, matrix);
-}
-
-}  // namespace
+#include "packed_ladder.h"
 
 int ce_launch_gainmap(ce_ctx *ctx, hipStream_t stream, int format, const void *d_src, const uint8_t *d_side, float *d_dst, uint32_t w, uint32_t h,
                       const ce_gainmap_plan &plan)
@@ -60,12 +37,18 @@ int ce_launch_gainmap(ce_ctx *ctx, hipStream_t stream, int format, const void *d
     for (int c = 0; c < 3; c++) a.kb[c] = plan.base_offset[c], a.ka[c] = plan.alternate_offset[c];
     const dim3 grid((uint32_t)blocks);
     const bool three = plan.channels == 3, matrix = plan.base.has_matrix;
-    switch (format) {
-        case CE_PIXEL_RGB8: launch_channels<CE_PIXEL_RGB8>(ctx, stream, kGainmapNames[0], grid, a, three, matrix); break;
-        case CE_PIXEL_RGBA8: launch_channels<CE_PIXEL_RGBA8>(ctx, stream, kGainmapNames[1], grid, a, three, matrix); break;
-        case CE_PIXEL_RGB16: launch_channels<CE_PIXEL_RGB16>(ctx, stream, kGainmapNames[2], grid, a, three, matrix); break;
-        case CE_PIXEL_RGBA16: launch_channels<CE_PIXEL_RGBA16>(ctx, stream, kGainmapNames[3], grid, a, three, matrix); break;
-        default: ctx->err = "gain-map ingest: format must be RGB8, RGBA8, RGB16 or RGBA16"; return CE_ERR_INVALID_ARG;
+    const char *suffix = three ? (matrix ? "_3_m" : "_3") : (matrix ? "_1_m" : "_1");
+    const bool known = packed_ladder(format, [&](auto fmt) {
+        constexpr int FMT = decltype(fmt)::value;
+        const packed_profile_name name("gainmap", "", FMT, suffix);
+        if (three && matrix) CE_LAUNCH_ON(ctx, stream, name.s, (k_gainmap<FMT, 3, true>), grid, dim3(kCicpBlock), 0, a);
+        else if (three) CE_LAUNCH_ON(ctx, stream, name.s, (k_gainmap<FMT, 3, false>), grid, dim3(kCicpBlock), 0, a);
+        else if (matrix) CE_LAUNCH_ON(ctx, stream, name.s, (k_gainmap<FMT, 1, true>), grid, dim3(kCicpBlock), 0, a);
+        else CE_LAUNCH_ON(ctx, stream, name.s, (k_gainmap<FMT, 1, false>), grid, dim3(kCicpBlock), 0, a);
+    });
+    if (!known) {
+        ctx->err = "gain-map ingest: format must be RGB8, RGBA8, RGB16 or RGBA16";
+        return CE_ERR_INVALID_ARG;
     }
     CE_HIP(ctx, hipGetLastError());
     return CE_OK;

@@ -12,28 +12,9 @@
 // except where it wraps to the next row pair).  A cropped group stores sample by sample.  No LDS, no scratch.
 #include "ce_internal.h"
 
-#include "hlg_pixel.h"
+#include "tagged_pick.h"
 #include "yuv_cicp_kernel.h"
 #include "yuv_ladder.h"
-
-namespace {
-
-// the profile names follow yuv.hip's: subsampling, input sample size, then `suffix`, or `suffix_m` with the primaries matrix
-template <template <bool> class Px, class Args>
-void launch_pixel(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, const char *suffix, const char *suffix_m, dim3 grid,
-                  const yuv_args &y, const Args &a, bool matrix)
-{
-    yuv_ladder(src.depth == 8, src.subsampling, src.layout == CE_YUV_SEMIPLANAR, [&](auto bps, auto sub, auto semi) {
-        constexpr int BPS = decltype(bps)::value, SUB = decltype(sub)::value;
-        constexpr bool SEMI = decltype(semi)::value;
-        if (matrix)
-            CE_LAUNCH_ON(ctx, stream, yuv_profile_name(SUB, BPS, suffix_m).s, (k_yuv_tagged<BPS, SUB, SEMI, Px<true>>), grid, dim3(64), 0, yuv_px_args<Px<true>>{y, Px<true>{a}});
-        else
-            CE_LAUNCH_ON(ctx, stream, yuv_profile_name(SUB, BPS, suffix).s, (k_yuv_tagged<BPS, SUB, SEMI, Px<false>>), grid, dim3(64), 0, yuv_px_args<Px<false>>{y, Px<false>{a}});
-    });
-}
-
-}  // namespace
 
 int ce_launch_yuv_tagged(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src, uint32_t w, uint32_t h, float *d_dst, const ce_linear_pixel &px)
 {
@@ -45,12 +26,18 @@ int ce_launch_yuv_tagged(ce_ctx *ctx, hipStream_t stream, const ce_yuv_dev &src,
     }
     yuv_args y{};
     ce_fill_yuv_args(y, src, w, h, (int64_t)px.maxv);  // src.k was built for this output depth (yuv_check with depth_out = the description's depth)
-    hlg_args a{};  // the CICP pixel takes its `c` alone
-    ce_fill_pixel_args(a, d_dst, px);
     const dim3 grid((uint32_t)blocks);
-    // the one place that knows which pixel a plan means
-    if (px.hlg) launch_pixel<hlg_px>(ctx, stream, src, "_hlg", "_hlg_m", grid, y, a, px.has_matrix);
-    else launch_pixel<cicp_px>(ctx, stream, src, "_lin", "_lin_m", grid, y, a.c, px.has_matrix);
+    // the profile names follow yuv.hip's: subsampling, input sample size, then _lin or _hlg, and _m with the primaries matrix
+    tagged_pick(px, nullptr, 0, d_dst, [&](const auto &pixel, const char *, const char *m) {
+        using P = std::decay_t<decltype(pixel)>;
+        char suffix[8];
+        std::snprintf(suffix, sizeof suffix, "%s%s", px.hlg ? "_hlg" : "_lin", m);
+        yuv_ladder(src.depth == 8, src.subsampling, src.layout == CE_YUV_SEMIPLANAR, [&](auto bps, auto sub, auto semi) {
+            constexpr int BPS = decltype(bps)::value, SUB = decltype(sub)::value;
+            constexpr bool SEMI = decltype(semi)::value;
+            CE_LAUNCH_ON(ctx, stream, yuv_profile_name(SUB, BPS, suffix).s, (k_yuv_tagged<BPS, SUB, SEMI, P>), grid, dim3(64), 0, yuv_px_args<P>{y, pixel});
+        });
+    });
     CE_HIP(ctx, hipGetLastError());
     return CE_OK;
 }
