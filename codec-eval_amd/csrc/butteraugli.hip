@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "ba_front_geom.h"
+#include "ba_slot_order.h"
 #include "ce_internal.h"
 
 namespace {
@@ -120,15 +121,17 @@ constexpr int BH_TILES = CE_BH_TILES;  // 8-row tiles per block of the row blur
 template <int LEN>
 __global__ __launch_bounds__(TPB) void k_ba_blur_h(const float *__restrict__ in, float *__restrict__ out, geom g, plane_sel si,
                                                    plane_sel so, blur_kernel bk, float inv_wsum, uint32_t n_refs_used,
-                                                   uint32_t max_refs, int by_slot, uint32_t z0)
+                                                   uint32_t max_refs, int by_slot, ba_slot_grid sg)
 {
+    const ba_slot_item it = ba_slot_decode3(sg, sg.planes, blockIdx.x, blockIdx.y, blockIdx.z);  // (tile, plane, slot): ba_slot_order.h
+    if (!it.live) return;
     constexpr int off = LEN / 2, TW = 256, TR = 8, LEFT = 16, RAW = TW + 2 * LEFT, ROWF = RAW + RAW / 8 + 1, SH = LEFT - off;
     static_assert(off <= LEFT, "tile halo");
     __shared__ float tile[TR * ROWF];
-    const uint32_t u = blockIdx.z / si.n + z0, k = blockIdx.z % si.n;
+    const uint32_t u = it.z, k = it.plane;
     const uint32_t unit = by_slot ? slot_of(u, n_refs_used, max_refs) : u;
     const float *p = in + ((size_t)unit * si.per_unit + si.first + k) * g.plane;
-    const int x0 = blockIdx.x * TW;
+    const int x0 = it.x * TW;
     // A block walks BH_TILES consecutive 8-row tiles; the next tile's float4 pieces are fetched into registers while
     // the current one is filtered out of LDS.
     constexpr int NF = (TR * (RAW / 4) + TPB - 1) / TPB;
@@ -162,7 +165,7 @@ __global__ __launch_bounds__(TPB) void k_ba_blur_h(const float *__restrict__ in,
     constexpr int NV = BW_OUT + LEN - 1, NP = (NV + 1) / 2;
     const float *row = &tile[r * ROWF + 9 * cx];  // element j of the window sits at j + SH + ((j + SH) >> 3)
     auto at = [&](int j) { return row[(j + SH) + ((j + SH) >> 3)]; };
-    const int y_first = blockIdx.y * (TR * BH_TILES);
+    const int y_first = it.y * (TR * BH_TILES);
     fetch(y_first);
 #pragma unroll 1
     for (int t = 0; t < BH_TILES; t++) {
@@ -276,15 +279,17 @@ __global__ __launch_bounds__(TPB) void k_ba_front(const uint8_t *__restrict__ re
                                                   const float *__restrict__ lut, const float *__restrict__ lut_test, geom gi,
                                                   float *__restrict__ xyb, geom g, float w0, float w1, float w2,
                                                   float intensity_target, size_t img_bytes, uint32_t n_refs_used, uint32_t max_refs,
-                                                  uint32_t z0)
+                                                  ba_slot_grid sg)
 {
+    const ba_slot_item it = ba_slot_decode3(sg, 1, blockIdx.x, blockIdx.y, blockIdx.z);  // (tile, slot): ba_slot_order.h
+    if (!it.live) return;
     __shared__ float L[3][FR * FR];   // linear, region = tile + 2
     __shared__ float H[3][FR * FT];   // row-blurred: FR rows x FT columns
     constexpr bool U8 = sizeof(T) == 1;
     __shared__ float s_lut[256];
     if (U8) s_lut[threadIdx.x] = lut[threadIdx.x];
-    const uint32_t z = blockIdx.z + z0, slot = slot_of(z, n_refs_used, max_refs);
-    const int w = (int)g.w, h = (int)g.h, x0 = blockIdx.x * FT, y0 = blockIdx.y * FT, gx0 = x0 - 2, gy0 = y0 - 2;
+    const uint32_t z = it.z, slot = slot_of(z, n_refs_used, max_refs);
+    const int w = (int)g.w, h = (int)g.h, x0 = it.x * FT, y0 = it.y * FT, gx0 = x0 - 2, gy0 = y0 - 2;
     const uint8_t *src8 = z < n_refs_used ? refs + (size_t)z * img_bytes : tests + (size_t)(z - n_refs_used) * img_bytes;
     const T *srcT = reinterpret_cast<const T *>(src8);
     const float *tab = U8 ? s_lut : (z < n_refs_used ? lut : lut_test);
@@ -511,9 +516,11 @@ __device__ __forceinline__ float mask_pre_one(float uhf0, float hf0, float uhf1,
 template <int LEN, int EPI, bool HV, int TR>
 __global__ __launch_bounds__(TPB) void k_ba_blur_v_split(const float *__restrict__ tmp, const float *__restrict__ xyb,
                                                          float *__restrict__ psy, geom g, blur_kernel bk, float inv_wsum,
-                                                         uint32_t n_refs_used, uint32_t max_refs, uint32_t z0,
+                                                         uint32_t n_refs_used, uint32_t max_refs, ba_slot_grid sg,
                                                          float *__restrict__ mask_in, float *__restrict__ aux_out)
 {
+    const ba_slot_item it = ba_slot_decode3(sg, 1, blockIdx.x, blockIdx.y, blockIdx.z);  // (tile, slot): ba_slot_order.h
+    if (!it.live) return;
     constexpr int NP = EPI == EPI_HF ? 2 : EPI == EPI_MASK ? 1 : 3;
     // 64 columns x 64 rows per block (two 8-row groups per thread): the halo of LEN - 1 rows is read once per 64 rows
     constexpr int off = LEN / 2, TW = 64, PARTS = TR / 32, RAW = TR + LEN - 1;
@@ -523,8 +530,8 @@ __global__ __launch_bounds__(TPB) void k_ba_blur_v_split(const float *__restrict
     static_assert(!HV || off <= LEFT, "row-pass halo");
     __shared__ __attribute__((aligned(16))) float tile[RAW * TW];
     __shared__ __attribute__((aligned(16))) float in_t[HV ? RAW * IW : 4];
-    const uint32_t slot = slot_of(blockIdx.z + z0, n_refs_used, max_refs);
-    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TR;
+    const uint32_t slot = slot_of(it.z, n_refs_used, max_refs);
+    const int x0 = it.x * TW, y0 = it.y * TR;
     const int c = threadIdx.x & 63, wv = threadIdx.x >> 6, gx = x0 + c;
     const bool col_live = gx < (int)g.w;
     float res[NP][PARTS][BW_OUT];
@@ -1402,6 +1409,17 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
         CE_HIP(ctx, hipEventRecord(b->ev_ba_fork, s_main));
         CE_HIP(ctx, hipStreamWaitEvent(s_half, b->ev_ba_fork, 0));
     }
+    // The per-slot kernels' launch order (ba_slot_order.h).  A/B knobs: CE_BA_SLOT_ORDER_MIN = slots per launch from which a
+    // slot's tiles stay on one XCD, CE_BA_SLOT_ORDER_KERNELS = the kernels that follow it (bits: 1 front, 2 h33, 4 v_lf,
+    // 8 hv_mf, 16 hv_hf, 32 hv_mask; the others keep tile order at every size)
+    static const uint32_t order_min = [] {
+        const char *e = std::getenv("CE_BA_SLOT_ORDER_MIN");
+        return e ? (uint32_t)std::atol(e) : ba_slot_order_min;
+    }();
+    static const uint32_t order_kernels = [] {
+        const char *e = std::getenv("CE_BA_SLOT_ORDER_KERNELS");
+        return e ? (uint32_t)std::atol(e) : 63u;
+    }();
     uint32_t final_tiles = 0;
     for (int l = b->ba_levels - 1; l >= 0; l--) {
         const auto &d = b->ba[l];
@@ -1413,31 +1431,47 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
         float *psy = b->ba_psy[l], *sA = scr[0], *sC = scr[2];
         // ---- per image slot: PsychoImage ----
         const plane_sel s3{3, 0, 3};
-        const dim3 ft((d.w + FT - 1) / FT, (d.h + FT - 1) / FT, nz);
+        // the launch order (ba_slot_order.h): a slot's tiles on one XCD when the launch has enough slots
+        auto SG = [&](uint32_t tile_w, uint32_t tile_h, uint32_t planes, uint32_t kernel_bit) {
+            return ba_slot_grid_make((d.w + tile_w - 1) / tile_w, (d.h + tile_h - 1) / tile_h, planes, nz, z0,
+                                     (order_kernels & kernel_bit) ? order_min : ~0u);
+        };
+        auto SB = [](const ba_slot_grid &s) {
+            const ba_slot_dims3 dims = ba_slot_dims(s);
+            return dim3(dims.x, dims.y, dims.z);
+        };
+        const ba_slot_grid sg_front = SG(FT, FT, 1, 1), sg_h33 = SG(256, 8 * BH_TILES, 3, 2), sg_vlf = SG(64, 32, 1, 4),
+                           sg_mf = SG(64, 32, 1, 8), sg_hf = SG(64, 32, 1, 16), sg_mask = SG(64, 32, 1, 32);
+        for (const ba_slot_grid &s : {sg_front, sg_h33, sg_vlf, sg_mf, sg_hf, sg_mask})
+            if (ba_slot_dims(s).y > ba_slot_grid_yz_max || ba_slot_dims(s).z > ba_slot_grid_yz_max) {
+                ctx->err = "Butteraugli batch too large for one launch";
+                return CE_ERR_BACKEND;
+            }
+        const dim3 ft = SB(sg_front);
         const auto &pd = b->ba[0];
         const geom gfull{pd.w, pd.h, pd.pitch, pd.plane};
         if (b->linear) {  // a linear batch: f32 samples, no table
             const float *none = nullptr;
             if (l == 0)
                 CE_LAUNCH_ON(ctx, st, "ba_front_lin", (k_ba_front<false, float>), ft, dim3(TPB), 0, d_refs, b->d_tests, none, none, g, sC, g,
-                             w0, w1, w2, intensity_target, b->img_bytes, n_refs_used, mr, z0);
+                             w0, w1, w2, intensity_target, b->img_bytes, n_refs_used, mr, sg_front);
             else
                 CE_LAUNCH_ON(ctx, st, "ba_front_half_lin", (k_ba_front<true, float>), ft, dim3(TPB), 0, d_refs, b->d_tests, none, none, gfull,
-                             sC, g, w0, w1, w2, intensity_target, b->img_bytes, n_refs_used, mr, z0);
+                             sC, g, w0, w1, w2, intensity_target, b->img_bytes, n_refs_used, mr, sg_front);
         } else if (b->depth[0]) {  // a deep batch: u16 samples, one table per side (rule 0, the f64 curve)
             const float *lr = b->deep_lut[0][0], *lt = b->deep_lut[0][1];
             if (l == 0)
                 CE_LAUNCH_ON(ctx, st, "ba_front_u16", (k_ba_front<false, uint16_t>), ft, dim3(TPB), 0, d_refs, b->d_tests, lr, lt, g, sC, g,
-                             w0, w1, w2, intensity_target, b->img_bytes, n_refs_used, mr, z0);
+                             w0, w1, w2, intensity_target, b->img_bytes, n_refs_used, mr, sg_front);
             else
                 CE_LAUNCH_ON(ctx, st, "ba_front_half_u16", (k_ba_front<true, uint16_t>), ft, dim3(TPB), 0, d_refs, b->d_tests, lr, lt, gfull,
-                             sC, g, w0, w1, w2, intensity_target, b->img_bytes, n_refs_used, mr, z0);
+                             sC, g, w0, w1, w2, intensity_target, b->img_bytes, n_refs_used, mr, sg_front);
         } else if (l == 0) {
             CE_LAUNCH_ON(ctx, st, "ba_front_u8", (k_ba_front<false, uint8_t>), ft, dim3(TPB), 0, d_refs, b->d_tests, ctx->d_lut_ssim2,
-                         ctx->d_lut_ssim2, g, sC, g, w0, w1, w2, intensity_target, b->img_bytes, n_refs_used, mr, z0);
+                         ctx->d_lut_ssim2, g, sC, g, w0, w1, w2, intensity_target, b->img_bytes, n_refs_used, mr, sg_front);
         } else {
             CE_LAUNCH_ON(ctx, st, "ba_front_half", (k_ba_front<true, uint8_t>), ft, dim3(TPB), 0, d_refs, b->d_tests, ctx->d_lut_ssim2,
-                         ctx->d_lut_ssim2, gfull, sC, g, w0, w1, w2, intensity_target, b->img_bytes, n_refs_used, mr, z0);
+                         ctx->d_lut_ssim2, gfull, sC, g, w0, w1, w2, intensity_target, b->img_bytes, n_refs_used, mr, sg_front);
         }
         // LF = blur(xyb, 7.156) -> psy[LF0..2]
         // SeparateFrequencies: row blur of a band, then column blur fused with the pointwise split (k_ba_blur_v_split)
@@ -1446,23 +1480,21 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
                 ctx->err = "unexpected blur kernel length";
                 return CE_ERR_BACKEND;
             }
-            const dim3 gh3((g.w + 255) / 256, (g.h + 8 * BH_TILES - 1) / (8 * BH_TILES), nz * 3);
             float *sB = scr[1];
             // LF: row pass sC -> sA, column pass + split: LF -> psy, raw MF -> sB
-            CE_LAUNCH_ON(ctx, st, "ba_blur_h33", k_ba_blur_h<33>, gh3, dim3(TPB), 0, (const float *)sC, sA, g, s3, s3, kLf, inv_weight_sum(kLf),
-                      n_refs_used, mr, 1, z0);
+            CE_LAUNCH_ON(ctx, st, "ba_blur_h33", k_ba_blur_h<33>, SB(sg_h33), dim3(TPB), 0, (const float *)sC, sA, g, s3, s3, kLf, inv_weight_sum(kLf),
+                      n_refs_used, mr, 1, sg_h33);
             // 32 rows per block of the column / fused stages (26 / 21 KB of LDS and ~100 / 56 registers: five blocks per
             // CU).  64 rows (smaller halo, 45 / 38 KB, three or four blocks) measured equal or slower
             // (profiles/r02_experiments.md section 18, r03_experiments.md section 12).
-            const dim3 gvs((g.w + 63) / 64, (g.h + 31) / 32, nz);
-            CE_LAUNCH_ON(ctx, st, "ba_blur_v_lf", (k_ba_blur_v_split<33, EPI_LF, false, 32>), gvs, dim3(TPB), 0, (const float *)sA,
-                         (const float *)sC, psy, g, kLf, inv_weight_sum(kLf), n_refs_used, mr, z0, (float *)nullptr, sB);
+            CE_LAUNCH_ON(ctx, st, "ba_blur_v_lf", (k_ba_blur_v_split<33, EPI_LF, false, 32>), SB(sg_vlf), dim3(TPB), 0, (const float *)sA,
+                         (const float *)sC, psy, g, kLf, inv_weight_sum(kLf), n_refs_used, mr, sg_vlf, (float *)nullptr, sB);
             // MF: row + column pass of raw MF (sB) + split: MF -> psy, raw HF -> sA (its old contents are dead)
-            CE_LAUNCH_ON(ctx, st, "ba_blur_hv_mf", (k_ba_blur_v_split<15, EPI_MF, true, 32>), gvs, dim3(TPB), 0, (const float *)sB,
-                         (const float *)nullptr, psy, g, kHf, inv_weight_sum(kHf), n_refs_used, mr, z0, (float *)nullptr, sA);
+            CE_LAUNCH_ON(ctx, st, "ba_blur_hv_mf", (k_ba_blur_v_split<15, EPI_MF, true, 32>), SB(sg_mf), dim3(TPB), 0, (const float *)sB,
+                         (const float *)nullptr, psy, g, kHf, inv_weight_sum(kHf), n_refs_used, mr, sg_mf, (float *)nullptr, sA);
             // HF: row + column pass of raw HF (sA) + split: HF, UHF -> psy, the mask input -> sB (raw MF is dead)
-            CE_LAUNCH_ON(ctx, st, "ba_blur_hv_hf", (k_ba_blur_v_split<7, EPI_HF, true, 32>), gvs, dim3(TPB), 0, (const float *)sA,
-                         (const float *)nullptr, psy, g, kUhf, inv_weight_sum(kUhf), n_refs_used, mr, z0, sB, (float *)nullptr);
+            CE_LAUNCH_ON(ctx, st, "ba_blur_hv_hf", (k_ba_blur_v_split<7, EPI_HF, true, 32>), SB(sg_hf), dim3(TPB), 0, (const float *)sA,
+                         (const float *)nullptr, psy, g, kUhf, inv_weight_sum(kUhf), n_refs_used, mr, sg_hf, sB, (float *)nullptr);
         }
 
         // mask input: DiffPrecompute of HF + UHF (written by the HF split's epilogue into ba_s[1]), blurred with sigma 2.7 -
@@ -1474,9 +1506,8 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
                 ctx->err = "unexpected blur kernel length";
                 return CE_ERR_BACKEND;
             }
-            const dim3 gm((g.w + 63) / 64, (g.h + 31) / 32, nz);
-            CE_LAUNCH_ON(ctx, st, "ba_blur_hv_mask", (k_ba_blur_v_split<13, EPI_MASK, true, 32>), gm, dim3(TPB), 0, (const float *)scr[1],
-                      (const float *)nullptr, psy, g, kMask, inv_weight_sum(kMask), n_refs_used, mr, z0, (float *)nullptr, b->ba_mask[l]);
+            CE_LAUNCH_ON(ctx, st, "ba_blur_hv_mask", (k_ba_blur_v_split<13, EPI_MASK, true, 32>), SB(sg_mask), dim3(TPB), 0, (const float *)scr[1],
+                      (const float *)nullptr, psy, g, kMask, inv_weight_sum(kMask), n_refs_used, mr, sg_mask, (float *)nullptr, b->ba_mask[l]);
         }
         if (!cached)
             CE_LAUNCH_ON(ctx, st, "ba_mask_vals", k_ba_mask_vals, G(n_refs_used), dim3(TPB), 0, (const float *)b->ba_mask[l], b->ba_mask_vals[l], g);
