@@ -116,7 +116,33 @@ int ce_device_count(void); /* number of visible HIP devices; <0 on runtime failu
 /* GpuSsim2::new (crates/codec-iter/src/gpu.rs:40-80) without the fixed-shape limit:
  * scratch is keyed by (w,h) and grows on demand. */
 int ce_ctx_create(int device, ce_ctx **out);
-/* same, launching on a caller-owned hipStream_t (passed as void*); NULL = own stream */
+/* same, launching on a caller-owned hipStream_t (passed as void*); NULL (0) = own stream, exactly ce_ctx_create: the
+ * legacy default stream, whose handle is 0, cannot be adopted (nor can a framework's default stream that is it: pass a
+ * stream the framework created, INTEGRATION.md "Stream order").  The context never
+ * destroys a caller's stream; ce_ctx_destroy synchronises it.
+ *
+ * Stream order.  "The context's stream" is ce_ctx_stream(): the caller's, or the context's own - a caller may enqueue on
+ * either.  The library fans a call out to further streams of its own (metric chains, upload streams, helper threads) and
+ * fences them so that, seen from outside, every call behaves as if its device work ran on the context's stream at the
+ * point of the call:
+ *  - Work the caller enqueued on the context's stream BEFORE a call (a decoder's kernels or copies into the slabs of
+ *    ce_batch_reference_slab / ce_batch_test_slab, followed by ce_batch_references_changed where references changed) is
+ *    visible to that call's device work.  No host synchronisation is needed in between.
+ *  - Work enqueued on the context's stream AFTER a call returns runs after that call's device work, a launch that has not
+ *    been collected included.
+ *  - No other stream is ever waited for.  What a call reads from device memory the caller wrote on another stream
+ *    (slabs, CE_MEM_DEVICE planes) must be complete before the call, or that stream be made to precede the context's
+ *    (hipStreamWaitEvent) before the call.  (HIP maps streams onto a few hardware queues and may run a stream behind
+ *    another that shares its queue; the library adds no such dependency and none may be relied on.)
+ *  - A ce_batch_set_*, ce_batch_bind_pair or ce_batch_resample into a batch issued after ce_batch_launch does not
+ *    disturb that launch: it is ordered behind the launch's reads, whichever stream carries it, and the launch's scores
+ *    and maps are those of the images it was launched on.
+ *  - Host sources of ce_batch_set_* are consumed on return (copied to page-locked staging), whatever is still queued.
+ * ce_batch_launch, the setters and ce_batch_resample* return without waiting for the stream (a launch waits, for the
+ * batch's own previous launch only, when the pair bindings or the pair count changed since: it rebuilds its tables, and
+ * a setter waits for a staging buffer it used a few images ago).  Calls that return results to the host
+ * (ce_batch_run, ce_batch_collect, the leaves, ce_batch_image_heuristics, ce_batch_hdr_fidelity, map readouts) wait for what
+ * they return. */
 int ce_ctx_create_on_stream(int device, void *hip_stream, ce_ctx **out);
 /* Drop for GpuSsim2 (gpu.rs:118-133): synchronises the stream, then frees */
 void ce_ctx_destroy(ce_ctx *ctx);
