@@ -666,6 +666,40 @@ impl HipMetrics {
         Ok(out)
     }
 
+    /// `ce_tensor_to_rgb8`: image 0 of a strided tensor as an RGB8 slot would hold it.
+    ///
+    /// # Safety
+    /// `t.data` and its strides must describe memory of the kind `t.memory` names that holds every element of a
+    /// `width` x `height` image of three channels.
+    pub unsafe fn tensor_to_rgb8(&mut self, t: &sys::ce_tensor_image, width: u32, height: u32) -> Result<Vec<u8>, HipError> {
+        let mut out = vec![0u8; width as usize * height as usize * 3];
+        let rc = sys::ce_tensor_to_rgb8(self.ctx, t, width, height, out.as_mut_ptr(), out.len());
+        self.check(rc, width, height, out.len())?;
+        Ok(out)
+    }
+
+    /// `ce_tensor_to_rgb16`: the same as a deep side of `depth_out` bits (8, 10, 12 or 16) would hold it.
+    ///
+    /// # Safety
+    /// As `tensor_to_rgb8`.
+    pub unsafe fn tensor_to_rgb16(&mut self, t: &sys::ce_tensor_image, width: u32, height: u32, depth_out: u32) -> Result<Vec<u16>, HipError> {
+        let mut out = vec![0u16; width as usize * height as usize * 3];
+        let rc = sys::ce_tensor_to_rgb16(self.ctx, t, width, height, depth_out, out.as_mut_ptr(), out.len());
+        self.check(rc, width, height, out.len())?;
+        Ok(out)
+    }
+
+    /// `ce_tensor_to_linear`: a float tensor as a slot of a linear batch would hold it.
+    ///
+    /// # Safety
+    /// As `tensor_to_rgb8`.
+    pub unsafe fn tensor_to_linear(&mut self, t: &sys::ce_tensor_image, width: u32, height: u32) -> Result<Vec<f32>, HipError> {
+        let mut out = vec![0f32; width as usize * height as usize * 3];
+        let rc = sys::ce_tensor_to_linear(self.ctx, t, width, height, out.as_mut_ptr(), out.len());
+        self.check(rc, width, height, out.len())?;
+        Ok(out)
+    }
+
     /// `ce_yuv_hlg_to_linear`: one image's planes in HLG, in one kernel (`hlg.depth` is the integer RGB grid's, >= the samples').
     pub fn yuv_hlg_to_linear(&mut self, image: &YuvPlanes<'_>, hlg: &sys::ce_hlg, width: u32, height: u32) -> Result<Vec<f32>, HipError> {
         let c = image.to_sys(width, height)?;
@@ -1087,6 +1121,27 @@ impl HipBatch<'_> {
                                            &map.metadata)
         };
         self.check(rc, pixels.len())
+    }
+
+    /// `ce_batch_set_reference_tensor`: images `0 .. count` of a strided tensor of the batch's shape into reference slots
+    /// `first_ref ..`; a device tensor is read in place by one launch, behind what the context's stream holds at the call.
+    ///
+    /// # Safety
+    /// `t.data` and its strides must describe memory of the kind `t.memory` names that holds every element of `count`
+    /// images; a device tensor must stay alive and unchanged until the batch's next launch has been collected.
+    pub unsafe fn set_reference_tensor(&mut self, first_ref: u32, count: u32, t: &sys::ce_tensor_image) -> Result<(), HipError> {
+        let rc = sys::ce_batch_set_reference_tensor(self.handle, first_ref, count, t);
+        self.check(rc, 0)
+    }
+
+    /// `ce_batch_set_test_tensor`: the same into test slots `first_pair ..`, pair `first_pair + n` bound to reference
+    /// `ref_indices[n]`; the tensor holds `ref_indices.len()` images.
+    ///
+    /// # Safety
+    /// As `set_reference_tensor`.
+    pub unsafe fn set_test_tensor(&mut self, first_pair: u32, ref_indices: &[u32], t: &sys::ce_tensor_image) -> Result<(), HipError> {
+        let rc = sys::ce_batch_set_test_tensor(self.handle, first_pair, ref_indices.as_ptr(), ref_indices.len() as u32, t);
+        self.check(rc, 0)
     }
 
     /// `ce_batch_set_reference_yuv_hlg`: a decoder's planes in HLG into a reference slot of a LINEAR batch.

@@ -285,6 +285,29 @@ pub const CE_CHROMA_TRIANGLE: c_int = 1;
 pub const CE_MEM_HOST: c_int = 0;
 pub const CE_MEM_DEVICE: c_int = 1;
 
+// enum ce_dtype, enum ce_quantise: the tensor ingest
+pub const CE_DTYPE_U8: c_int = 0;
+pub const CE_DTYPE_U16: c_int = 1;
+pub const CE_DTYPE_F16: c_int = 2;
+pub const CE_DTYPE_BF16: c_int = 3;
+pub const CE_DTYPE_F32: c_int = 4;
+pub const CE_QUANT_NEAREST_EVEN: c_int = 0;
+pub const CE_QUANT_TRUNCATE: c_int = 1;
+
+/// `ce_tensor_image` (56 bytes): a framework's strided image tensor, in host or device memory; strides in ELEMENTS.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ce_tensor_image {
+    pub data: *const c_void,
+    pub stride_n: i64,
+    pub stride_c: i64,
+    pub stride_y: i64,
+    pub stride_x: i64,
+    pub dtype: c_int,
+    pub memory: c_int,
+    pub quantise: c_int,
+}
+
 /// `CE_MAX_BACKGROUNDS`: solid colours one upload is composited over
 pub const CE_MAX_BACKGROUNDS: usize = 8;
 
@@ -453,6 +476,11 @@ extern "C" {
                                      h: *const ce_hlg) -> c_int;
     pub fn ce_yuv_hlg_to_linear(ctx: *mut ce_ctx, image: *const ce_yuv_image, h: *const ce_hlg, width: u32, height: u32, out: *mut c_float,
                                 out_len: usize) -> c_int;
+    pub fn ce_batch_set_reference_tensor(b: *mut ce_batch, first_ref: u32, count: u32, t: *const ce_tensor_image) -> c_int;
+    pub fn ce_batch_set_test_tensor(b: *mut ce_batch, first_pair: u32, ref_indices: *const u32, count: u32, t: *const ce_tensor_image) -> c_int;
+    pub fn ce_tensor_to_rgb8(ctx: *mut ce_ctx, t: *const ce_tensor_image, w: u32, h: u32, out: *mut u8, out_len: usize) -> c_int;
+    pub fn ce_tensor_to_rgb16(ctx: *mut ce_ctx, t: *const ce_tensor_image, w: u32, h: u32, depth_out: u32, out: *mut u16, out_len: usize) -> c_int;
+    pub fn ce_tensor_to_linear(ctx: *mut ce_ctx, t: *const ce_tensor_image, w: u32, h: u32, out: *mut c_float, out_len: usize) -> c_int;
     pub fn ce_hlg_table(depth: u32, out: *mut c_float, n: usize) -> c_int;
     pub fn ce_hlg_params(h: *const ce_hlg, out: *mut c_double) -> c_int;
     pub fn ce_batch_set_reference_gainmap(b: *mut ce_batch, ref_index: u32, pixels: *const c_void, len: usize, format: c_int,

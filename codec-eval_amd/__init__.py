@@ -57,6 +57,9 @@ YUV_BT601, YUV_BT709, YUV_BT2020 = 0, 1, 2  # enum ce_yuv_matrix
 YUV_FULL, YUV_LIMITED = 0, 1  # enum ce_yuv_range
 CHROMA_NEAREST, CHROMA_TRIANGLE = 0, 1  # enum ce_chroma_upsample
 MEM_HOST, MEM_DEVICE = 0, 1  # enum ce_mem
+# tensor ingest (include/ce_metrics.h)
+DTYPE_U8, DTYPE_U16, DTYPE_F16, DTYPE_BF16, DTYPE_F32 = 0, 1, 2, 3, 4  # enum ce_dtype
+QUANT_NEAREST_EVEN, QUANT_TRUNCATE = 0, 1  # enum ce_quantise
 MAX_BACKGROUNDS = 8  # CE_MAX_BACKGROUNDS: solid colours one upload is composited over
 ALPHA_BLACK_WHITE = ((0, 0, 0), (255, 255, 255))  # the two page colours a transparent image is most often seen on, 8-bit
 # EvalConfig.alpha_blend: transparent images scored in linear light are blended over alpha_backgrounds THERE, after the pixel
@@ -127,6 +130,19 @@ class CeYuvImage(C.Structure):
         ("msb_aligned", C.c_int),
         ("memory", C.c_int),
         ("lut", C.c_void_p),
+    ]
+
+
+class CeTensorImage(C.Structure):
+    _fields_ = [
+        ("data", C.c_void_p),
+        ("stride_n", C.c_int64),
+        ("stride_c", C.c_int64),
+        ("stride_y", C.c_int64),
+        ("stride_x", C.c_int64),
+        ("dtype", C.c_int),
+        ("memory", C.c_int),
+        ("quantise", C.c_int),
     ]
 
 
@@ -306,6 +322,11 @@ _PROTOTYPES = [
     ("ce_batch_set_reference_yuv_hlg", _i, [_vp, _u32, C.POINTER(CeYuvImage), C.POINTER(CeHlg)]),
     ("ce_batch_set_test_yuv_hlg", _i, [_vp, _u32, _u32, C.POINTER(CeYuvImage), C.POINTER(CeHlg)]),
     ("ce_yuv_hlg_to_linear", _i, [_vp, C.POINTER(CeYuvImage), C.POINTER(CeHlg), _u32, _u32, _vp, _sz]),
+    ("ce_batch_set_reference_tensor", _i, [_vp, _u32, _u32, C.POINTER(CeTensorImage)]),
+    ("ce_batch_set_test_tensor", _i, [_vp, _u32, _vp, _u32, C.POINTER(CeTensorImage)]),
+    ("ce_tensor_to_rgb8", _i, [_vp, C.POINTER(CeTensorImage), _u32, _u32, _vp, _sz]),
+    ("ce_tensor_to_rgb16", _i, [_vp, C.POINTER(CeTensorImage), _u32, _u32, _u32, _vp, _sz]),
+    ("ce_tensor_to_linear", _i, [_vp, C.POINTER(CeTensorImage), _u32, _u32, _vp, _sz]),
     ("ce_hlg_table", _i, [_u32, _vp, _sz]),
     ("ce_hlg_params", _i, [C.POINTER(CeHlg), _dp]),
     ("ce_batch_set_reference_gainmap", _i, [_vp, _u32, _vp, _sz, _i, C.POINTER(CeColour), C.POINTER(CeGainmapImage), C.POINTER(CeGainmap)]),
@@ -929,6 +950,124 @@ class YuvImage:
         return c, keep
 
 
+_TENSOR_DTYPES = {"uint8": DTYPE_U8, "uint16": DTYPE_U16, "float16": DTYPE_F16, "half": DTYPE_F16, "bfloat16": DTYPE_BF16, "float32": DTYPE_F32,
+                  "float": DTYPE_F32}
+_TENSOR_LAYOUTS = {"CHW": (None, 0, 1, 2), "HWC": (None, 2, 0, 1), "NCHW": (0, 1, 2, 3), "NHWC": (0, 3, 1, 2)}  # the axes of n, c, y, x
+
+
+def _tensor_dtype(dtype) -> int:
+    """enum ce_dtype of a numpy or a framework dtype, recognised by name ("torch.bfloat16" -> DTYPE_BF16)"""
+    name = str(getattr(dtype, "name", dtype)).rsplit(".", 1)[-1]
+    if name not in _TENSOR_DTYPES:
+        raise TypeError(f"a tensor image is uint8, uint16, float16, bfloat16 or float32, got {dtype}")
+    return _TENSOR_DTYPES[name]
+
+
+class TensorImage:
+    """A framework's image tensor as the library reads it (struct ce_tensor_image): the address of element (0, 0, 0, 0), the
+    strides of n, c, y, x in elements, the dtype and where the memory is.  `count` images of `width` x `height`.  Built by
+    from_array; it keeps the array or tensor alive, and a device tensor must stay unchanged until the batch's next launch
+    has been collected."""
+
+    def __init__(self, data: int, strides: Sequence[int], count: int, height: int, width: int, dtype: int, memory: int = MEM_HOST,
+                 quantise: int = QUANT_NEAREST_EVEN, keep=None, layout: Optional[str] = None):
+        self.data, self.strides = int(data), tuple(int(s) for s in strides)
+        self.count, self.height, self.width = int(count), int(height), int(width)
+        self.dtype, self.memory, self.quantise = int(dtype), int(memory), int(quantise)
+        self.keep, self.layout = keep, layout  # the array or tensor it was built from, and the names of its axes
+        if len(self.strides) != 4:
+            raise ValueError("a tensor image has four strides: n, c, y, x")
+
+    @staticmethod
+    def from_array(obj, layout: str = "CHW", quantise: int = QUANT_NEAREST_EVEN, dtype: Optional[int] = None) -> "TensorImage":
+        """obj: a numpy array (host memory), or any object with data_ptr(), stride(), shape, dtype and is_cuda - a torch
+        tensor, on the host or the device; the package itself does not import torch.  layout names obj's axes: "CHW", "HWC",
+        "NCHW" or "NHWC"; the channel axis holds 3 channels, 4 (RGBA: the fourth is never read) or 1 (gray, read as all
+        three).  Views are taken as they are: a crop, a permute or an expand costs nothing.  dtype: an enum ce_dtype that
+        overrides the array's own (a uint16 numpy array of bfloat16 bit patterns: DTYPE_BF16)."""
+        if layout not in _TENSOR_LAYOUTS:
+            raise ValueError(f"layout must be one of {tuple(_TENSOR_LAYOUTS)}, got {layout!r}")
+        axes = _TENSOR_LAYOUTS[layout]
+        if hasattr(obj, "data_ptr") and hasattr(obj, "stride"):
+            shape, strides = tuple(int(s) for s in obj.shape), tuple(int(s) for s in obj.stride())
+            address, memory = int(obj.data_ptr()), MEM_DEVICE if getattr(obj, "is_cuda", False) else MEM_HOST
+            dt = _tensor_dtype(obj.dtype) if dtype is None else int(dtype)
+        else:
+            obj = np.asarray(obj)
+            dt = _tensor_dtype(obj.dtype) if dtype is None else int(dtype)
+            if any(s % obj.itemsize for s in obj.strides):
+                raise ValueError("the array's strides are not whole elements")
+            shape, strides = obj.shape, tuple(s // obj.itemsize for s in obj.strides)
+            address, memory = obj.ctypes.data, MEM_HOST
+        if len(shape) != len(layout):
+            raise ValueError(f"a {layout} tensor has {len(layout)} axes, got shape {shape}")
+        an, ac, ay, ax = axes
+        if shape[ac] not in (1, 3, 4):
+            raise ValueError(f"the channel axis holds 1, 3 or 4 channels, got {shape[ac]}")
+        sn, count = (0, 1) if an is None else (strides[an] if shape[an] > 1 else 0, shape[an])
+        sc = 0 if shape[ac] == 1 else strides[ac]
+        # the stride of an axis of length 1 is never applied and a view may report anything for it: a contiguous one is given
+        sx = strides[ax] if shape[ax] > 1 else 1
+        sy = strides[ay] if shape[ay] > 1 else shape[ax] * sx
+        return TensorImage(address, (sn, sc, sy, sx), count, shape[ay], shape[ax], dt, memory, quantise, keep=obj, layout=layout)
+
+    def host_elements(self) -> np.ndarray:
+        """The tensor's elements on the host as [count][height][width][3]: uint8 / uint16 as they are, float dtypes widened to
+        float32, which is exact.  For the host restatements (quantise_tensor); needs the object from_array was given."""
+        if self.keep is None or self.layout is None:
+            raise ValueError("host_elements needs a TensorImage built by from_array")
+        obj = self.keep
+        if hasattr(obj, "detach"):
+            obj = obj.detach().cpu()
+            obj = obj.numpy() if self.dtype in (DTYPE_U8, DTYPE_U16) else obj.float().numpy()
+        a = np.asarray(obj)
+        if a.dtype == np.uint16 and self.dtype == DTYPE_BF16:
+            a = (a.astype(np.uint32) << np.uint32(16)).view(np.float32)
+        elif a.dtype == np.uint16 and self.dtype == DTYPE_F16:
+            a = a.view(np.float16)
+        if a.dtype == np.float16:
+            a = a.astype(np.float32)
+        an, ac, ay, ax = _TENSOR_LAYOUTS[self.layout]
+        if an is None:
+            a, an, ac, ay, ax = a[None], 0, ac + 1, ay + 1, ax + 1
+        a = np.transpose(a, (an, ay, ax, ac))
+        return np.repeat(a, 3, axis=-1) if a.shape[-1] == 1 else a[..., :3]
+
+    def _c(self) -> CeTensorImage:
+        c = CeTensorImage()
+        c.data = self.data
+        c.stride_n, c.stride_c, c.stride_y, c.stride_x = self.strides
+        c.dtype, c.memory, c.quantise = self.dtype, self.memory, self.quantise
+        return c
+
+
+def quantise_tensor(array, depth: int = 8, quantise: int = QUANT_NEAREST_EVEN, dtype: Optional[int] = None) -> np.ndarray:
+    """The tensor ingest's rule for a float dtype into an integer slot of `depth` bits, on the host in numpy (the definition of
+    include/ce_metrics.h): v = f32(x) exactly; c = v > 0 ? min(v, 1) : 0; p = c * f32(2^depth - 1), one f32 multiply; rint
+    (ties to even) or floor.  uint8 at depth 8, uint16 otherwise, in array's shape.  array: float16 / float32 numpy, uint16
+    bit patterns with dtype=DTYPE_BF16 or DTYPE_F16, or a framework tensor (brought to the host and widened, which is exact)."""
+    if depth not in DEEP_DEPTHS:
+        raise ValueError(f"depth must be one of {DEEP_DEPTHS}, got {depth}")
+    if quantise not in (QUANT_NEAREST_EVEN, QUANT_TRUNCATE):
+        raise ValueError(f"unknown quantise rule {quantise}")
+    if hasattr(array, "data_ptr") and hasattr(array, "detach"):
+        array = array.detach().cpu().float().numpy()
+    a = np.asarray(array)
+    if dtype == DTYPE_BF16 and a.dtype == np.uint16:
+        v = (a.astype(np.uint32) << np.uint32(16)).view(np.float32)
+    elif dtype == DTYPE_F16 and a.dtype == np.uint16:
+        v = a.view(np.float16).astype(np.float32)
+    elif a.dtype in (np.float16, np.float32):
+        v = a.astype(np.float32)
+    else:
+        raise TypeError(f"quantise_tensor takes float16 or float32 values, or uint16 bit patterns with dtype=, got {a.dtype}")
+    with np.errstate(invalid="ignore"):
+        c = np.where(v > np.float32(0), np.minimum(v, np.float32(1)), np.float32(0)).astype(np.float32)
+    p = (c * np.float32((1 << depth) - 1)).astype(np.float32)
+    q = np.rint(p) if quantise == QUANT_NEAREST_EVEN else np.floor(p)
+    return q.astype(np.uint8 if depth == 8 else np.uint16)
+
+
 def version() -> str:
     return lib().ce_version().decode()
 
@@ -1387,6 +1526,28 @@ class Context:
         self._check(lib().ce_yuv_to_rgb16(self._h, C.byref(c), width, height, depth_out, out.ctypes.data, out.size))
         return out
 
+    def tensor_to_rgb8(self, image: "TensorImage") -> np.ndarray:
+        """Image 0 of a tensor as an RGB8 slot would hold it: (height, width, 3) uint8 (ce_tensor_to_rgb8; the definition is
+        in include/ce_metrics.h)."""
+        c = image._c()
+        out = np.empty((image.height, image.width, 3), np.uint8)
+        self._check(lib().ce_tensor_to_rgb8(self._h, C.byref(c), image.width, image.height, out.ctypes.data, out.size))
+        return out
+
+    def tensor_to_rgb16(self, image: "TensorImage", depth_out: int) -> np.ndarray:
+        """The same as a deep side of depth_out bits (8, 10, 12 or 16) would: (height, width, 3) uint16 (ce_tensor_to_rgb16)."""
+        c = image._c()
+        out = np.empty((image.height, image.width, 3), np.uint16)
+        self._check(lib().ce_tensor_to_rgb16(self._h, C.byref(c), image.width, image.height, depth_out, out.ctypes.data, out.size))
+        return out
+
+    def tensor_to_linear(self, image: "TensorImage") -> np.ndarray:
+        """A float tensor as a slot of a linear batch would hold it: (height, width, 3) float32 (ce_tensor_to_linear)."""
+        c = image._c()
+        out = np.empty((image.height, image.width, 3), np.float32)
+        self._check(lib().ce_tensor_to_linear(self._h, C.byref(c), image.width, image.height, out.ctypes.data, out.size))
+        return out
+
     def yuv_to_linear(self, image: "YuvImage", width: int, height: int, colour: "ColourDescription") -> np.ndarray:
         """A decoder's Y'CbCr planes read by `colour` -> (height, width, 3) float32 linear light with sRGB primaries, in one
         kernel (ce_yuv_to_linear): yuv_to_rgb16 at depth_out = colour.depth followed by cicp_to_linear, bit for bit."""
@@ -1799,6 +1960,29 @@ class Batch:
         c, _keep = image._c()
         self.ctx._check(lib().ce_batch_set_test_yuv(self._h, pair_index, ref_index, C.byref(c)))
         self._pair_ref[pair_index] = ref_index
+
+    # a framework's strided tensors, host or device: read through their strides and converted on the device, all images of
+    # the tensor in consecutive slots; a device tensor is read in place, behind what the context's stream holds at the call
+    def _tensor_c(self, image: "TensorImage") -> CeTensorImage:
+        if (image.width, image.height) != (self.width, self.height):
+            raise ValueError(f"a tensor of {image.width} x {image.height} for a batch of {self.width} x {self.height}")
+        return image._c()
+
+    def set_reference_tensor(self, first_ref: int, image: "TensorImage"):
+        """Images 0 .. image.count - 1 into reference slots first_ref .. (ce_batch_set_reference_tensor)."""
+        c = self._tensor_c(image)
+        self.ctx._check(lib().ce_batch_set_reference_tensor(self._h, first_ref, image.count, C.byref(c)))
+
+    def set_test_tensor(self, first_pair: int, ref_indices: Sequence[int], image: "TensorImage"):
+        """Images 0 .. image.count - 1 into test slots first_pair .., pair first_pair + n bound to reference ref_indices[n]
+        (ce_batch_set_test_tensor)."""
+        c = self._tensor_c(image)
+        refs = np.ascontiguousarray(ref_indices, dtype=np.uint32)
+        if refs.shape != (image.count,):
+            raise ValueError("set_test_tensor takes one reference index per image of the tensor")
+        self.ctx._check(lib().ce_batch_set_test_tensor(self._h, first_pair, refs.ctypes.data, image.count, C.byref(c)))
+        for k, r in enumerate(refs):
+            self._pair_ref[first_pair + k] = int(r)
 
     # code values with a matrix/TRC ICC profile, applied by the library itself, into a slot of any batch
     def set_reference_icc(self, ref_index: int, pixels, depth: int, profile: "IccProfile"):

@@ -1,5 +1,5 @@
 // Everything that writes a slot of a resident batch (include/ce_metrics.h: ce_batch_set_*, ce_batch_bind_pair), the tables
-// and the one-image leaves of the same conversions (ce_*_table, ce_*_to_linear, ce_yuv_to_rgb*, ce_composite_*,
+// and the one-image leaves of the same conversions (ce_*_table, ce_*_to_linear, ce_yuv_to_rgb*, ce_tensor_to_*, ce_composite_*,
 // ce_linear_over).  The handles some routes take (colour tables, ICC profiles) are made in ce_handles.cpp.
 // Four things live here once and every route goes through them: the ordering rule of slot writes (ce_order_write), the
 // wide staging pair (wide_send), the frame of a setter of one slot (set_slot) and of n consecutive slots (set_slots).  A
@@ -217,14 +217,21 @@ int wide_send(ce_batch *b, size_t bytes, Fill fill, Launch launch)
     CE_HIP(ctx, hipSetDevice(ctx->device));  // the staging allocations and the launch go to the context's device
     const int k = b->next_wide;
     b->next_wide ^= 1;
-    if (!b->h_wide[k]) {
-        const size_t cap = (size_t)b->w * b->h * (b->linear ? 16 : 8);
-        CE_HIP(ctx, hipHostMalloc((void **)&b->h_wide[k], cap, hipHostMallocDefault));
-        CE_HIP(ctx, hipMalloc((void **)&b->d_wide[k], cap));
-        CE_HIP(ctx, hipEventCreateWithFlags(&b->ev_wide[k], hipEventDisableTiming));
-    }
+    if (!b->ev_wide[k]) CE_HIP(ctx, hipEventCreateWithFlags(&b->ev_wide[k], hipEventDisableTiming));
     if (int rc = ce_order_write(b, false)) return rc;
     if (b->wide_busy[k]) CE_HIP(ctx, hipEventSynchronize(b->ev_wide[k]));  // this staging pair's previous image has been converted
+    b->wide_busy[k] = false;
+    if (!b->h_wide[k] || bytes > b->wide_cap[k]) {
+        // A tensor image takes up to 16 bytes per pixel in any batch (f32 RGBA; planar f32: 12): the pair grows for the call
+        // that needs more, behind its event, so every other workload keeps the memory it had.
+        const size_t cap = std::max((size_t)b->w * b->h * (b->linear ? 16 : 8), bytes);
+        if (b->h_wide[k]) CE_HIP(ctx, hipHostFree(b->h_wide[k]));
+        if (b->d_wide[k]) CE_HIP(ctx, hipFree(b->d_wide[k]));
+        b->h_wide[k] = b->d_wide[k] = nullptr, b->wide_cap[k] = 0;
+        CE_HIP(ctx, hipHostMalloc((void **)&b->h_wide[k], cap, hipHostMallocDefault));
+        CE_HIP(ctx, hipMalloc((void **)&b->d_wide[k], cap));
+        b->wide_cap[k] = cap;
+    }
     const wide_pair pair{b->h_wide[k], b->d_wide[k], k};
     if (int rc = fill(pair)) return rc;
     CE_HIP(ctx, hipMemcpyAsync(pair.d, pair.h, bytes, hipMemcpyHostToDevice, b->up_stream));
@@ -962,6 +969,155 @@ int yuv_icc_to_host(ce_ctx *ctx, const ce_yuv_image *image, uint32_t rgb_depth, 
     return yuv_leaf(ctx, image, plan, w, h, 0, nullptr, out, samples * (depth_out == 0 ? sizeof(float) : out16 ? 2 : 1), &px);
 }
 
+// ---- strided tensors of a framework (tensor.hip) ---------------------------------------------------------
+
+// the slot kinds of ce_launch_tensor
+enum { kTensorSlotU8 = 0, kTensorSlotU16 = 1, kTensorSlotLin = 2 };
+
+// the slot kind a batch's side gives a tensor, and its depth (read for u16 slots)
+struct tensor_slot {
+    int kind;
+    uint32_t depth;
+};
+tensor_slot tensor_slot_of(const ce_batch *b, bool test)
+{
+    return b->linear ? tensor_slot{kTensorSlotLin, 0} : b->depth[test] ? tensor_slot{kTensorSlotU16, b->depth[test]} : tensor_slot{kTensorSlotU8, 8};
+}
+
+// a checked ce_tensor_image: what the kernel reads in place, and for a host source what one image takes in staging
+struct tensor_plan {
+    ce_tensor_dev dev{};
+    size_t es = 0;           // bytes per element
+    bool interleaved = false;  // host: rows are runs of whole pixels (stride_c = 1, stride_x 3 or 4), else of one plane's elements
+    size_t stage_bytes = 0;  // host: one image in staging
+};
+
+int tensor_check(ce_ctx *ctx, const ce_tensor_image *t, uint32_t w, uint32_t h, uint32_t count, tensor_slot slot, tensor_plan *plan)
+{
+    const std::string route = "tensor ingest: ";
+    if (!t || !t->data) return ce_fail(ctx, CE_ERR_INVALID_ARG, route + "null pointer");
+    if (t->dtype < CE_DTYPE_U8 || t->dtype > CE_DTYPE_F32) return ce_fail(ctx, CE_ERR_INVALID_ARG, route + "unknown dtype " + std::to_string(t->dtype));
+    if (t->memory != CE_MEM_HOST && t->memory != CE_MEM_DEVICE)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, route + "unknown memory kind " + std::to_string(t->memory));
+    if (t->quantise != CE_QUANT_NEAREST_EVEN && t->quantise != CE_QUANT_TRUNCATE)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, route + "unknown quantise rule " + std::to_string(t->quantise));
+    const bool integer = t->dtype == CE_DTYPE_U8 || t->dtype == CE_DTYPE_U16;
+    if (t->quantise != 0 && (integer || slot.kind == kTensorSlotLin))
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, route + "quantise is for float dtypes into integer slots: it must be 0 here");
+    if (t->stride_n < 0 || t->stride_c < 0 || t->stride_y < 0 || t->stride_x < 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, route + "negative stride");
+    if (t->stride_x < 1 || t->stride_y < 1) return ce_fail(ctx, CE_ERR_INVALID_ARG, route + "stride_x and stride_y must be at least 1");
+    const size_t es = t->dtype == CE_DTYPE_U8 ? 1 : t->dtype == CE_DTYPE_F32 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(t->data) % es)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, route + "the data pointer is not aligned to its " + std::to_string(es) + "-byte elements");
+    const unsigned __int128 last = (unsigned __int128)(count ? count - 1 : 0) * (uint64_t)t->stride_n + (unsigned __int128)2 * (uint64_t)t->stride_c +
+                                   (unsigned __int128)(h ? h - 1 : 0) * (uint64_t)t->stride_y + (unsigned __int128)(w ? w - 1 : 0) * (uint64_t)t->stride_x;
+    if ((last + 1) * es > (unsigned __int128)INT64_MAX) return ce_fail(ctx, CE_ERR_INVALID_ARG, route + "the tensor's extent overflows size_t");
+    if (t->dtype == CE_DTYPE_U8 && slot.kind == kTensorSlotU16 && slot.depth != 8)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, route + "an 8-bit tensor needs a side of depth 8, this one has " + std::to_string(slot.depth));
+    if (t->dtype == CE_DTYPE_U16 && slot.kind == kTensorSlotU8)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, route + "CE_DTYPE_U16 needs a deep batch (ce_batch_create_deep)");
+    if (integer && slot.kind == kTensorSlotLin)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, route + "a linear batch takes float tensors, which are linear light; integer code values go through ce_batch_set_*_cicp");
+    if (count == 0 || count > 65535u) return ce_fail(ctx, CE_ERR_INVALID_ARG, route + "count must be 1 to 65535, got " + std::to_string(count));
+    plan->es = es;
+    plan->dev = ce_tensor_dev{t->data, t->stride_n, t->stride_c, t->stride_y, t->stride_x, t->dtype, t->quantise};
+    if (t->memory == CE_MEM_HOST) {
+        plan->interleaved = t->stride_x != 1;
+        if (plan->interleaved && !(t->stride_c == 1 && (t->stride_x == 3 || t->stride_x == 4)))
+            return ce_fail(ctx, CE_ERR_INVALID_ARG, route + "a host tensor's rows must be contiguous runs (stride_x = 1, or stride_c = 1 with stride_x 3 or 4): "
+                                                            "make it contiguous or pass device memory");
+        plan->stage_bytes = (size_t)w * h * es * (plan->interleaved ? (size_t)t->stride_x : t->stride_c == 0 ? 1 : 3);
+    }
+    return CE_OK;
+}
+
+// image n of a checked host tensor -> `h_stage`, its rows as they are, one after another; what the kernel then reads at d_stage
+ce_tensor_dev tensor_stage(const tensor_plan &plan, uint32_t n, uint32_t w, uint32_t h, uint8_t *h_stage, const uint8_t *d_stage)
+{
+    const ce_tensor_dev &s = plan.dev;
+    const size_t es = plan.es;
+    const uint8_t *img = static_cast<const uint8_t *>(s.data) + (size_t)n * (size_t)s.stride_n * es;
+    ce_tensor_dev d = s;
+    d.data = d_stage, d.stride_n = 0;
+    if (plan.interleaved) {
+        // the last pixel's run ends with its third channel: a fourth one behind it need not exist
+        const size_t row = (size_t)w * (size_t)s.stride_x * es, run = ((size_t)(w - 1) * (size_t)s.stride_x + 3) * es;
+        for (size_t y = 0; y < h; y++) std::memcpy(h_stage + y * row, img + y * (size_t)s.stride_y * es, run);
+        d.stride_y = (int64_t)w * s.stride_x;
+        return d;
+    }
+    const size_t row = (size_t)w * es;
+    for (size_t c = 0; c < (s.stride_c == 0 ? 1u : 3u); c++)
+        for (size_t y = 0; y < h; y++)
+            std::memcpy(h_stage + (c * h + y) * row, img + (c * (size_t)s.stride_c + y * (size_t)s.stride_y) * es, row);
+    d.stride_c = s.stride_c == 0 ? 0 : (int64_t)w * h, d.stride_y = w;
+    return d;
+}
+
+// `count` checked images into consecutive slots from dst on, on the batch's upload stream.  A device tensor is read in place by
+// one launch, ordered as every slot write and - this source alone - behind what the context's stream holds at this point, so
+// that a model running on that stream needs no host synchronisation; host images go one by one through the wide staging pair.
+int upload_tensor(ce_batch *b, uint8_t *dst, const ce_tensor_image *t, const tensor_plan &plan, uint32_t count, tensor_slot slot)
+{
+    ce_ctx *ctx = b->ctx;
+    if (t->memory == CE_MEM_DEVICE) {
+        CE_HIP(ctx, hipSetDevice(ctx->device));
+        if (int rc = ce_order_write(b, false)) return rc;
+        CE_HIP(ctx, hipEventRecord(b->ev_up, ctx->stream));
+        CE_HIP(ctx, hipStreamWaitEvent(b->up_stream, b->ev_up, 0));
+        if (int rc = ce_launch_tensor(ctx, b->up_stream, plan.dev, b->w, b->h, count, dst, b->img_bytes, slot.kind, slot.depth)) return rc;
+        b->uploads_pending = true;
+        return CE_OK;
+    }
+    for (uint32_t n = 0; n < count; n++) {
+        ce_tensor_dev staged{};
+        const int rc = wide_send(
+            b, plan.stage_bytes,
+            [&](const wide_pair &p) {
+                staged = tensor_stage(plan, n, b->w, b->h, p.h, p.d);
+                return CE_OK;
+            },
+            [&](const wide_pair &) {
+                return ce_launch_tensor(ctx, b->up_stream, staged, b->w, b->h, 1, dst + (size_t)n * b->img_bytes, b->img_bytes, slot.kind, slot.depth);
+            });
+        if (rc != CE_OK) return rc;
+    }
+    return CE_OK;
+}
+
+// ce_batch_set_*_tensor
+int set_tensor(ce_batch *b, bool test, uint32_t first, const uint32_t *ref_indices, uint32_t count, const ce_tensor_image *t)
+{
+    tensor_plan plan;
+    return set_slots(
+        b, test, first, count, ref_indices, "tensor ingest: ", kind_rule{}, !t || !t->data,
+        [&] { return tensor_check(b->ctx, t, b->w, b->h, count, tensor_slot_of(b, test), &plan); },
+        [&](uint8_t *dst) { return upload_tensor(b, dst, t, plan, count, tensor_slot_of(b, test)); });
+}
+
+// ce_tensor_to_rgb8 / _to_rgb16 / _to_linear: image 0 -> host memory through the leaf scratch, on the context's stream
+int tensor_to_host(ce_ctx *ctx, const ce_tensor_image *t, uint32_t w, uint32_t h, tensor_slot slot, void *out, size_t out_len)
+{
+    if (!ctx) return CE_ERR_INVALID_ARG;
+    if (!out) return ce_fail(ctx, CE_ERR_INVALID_ARG, "tensor ingest: null output");
+    if (w == 0 || h == 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, "tensor ingest: empty image");
+    if (slot.kind == kTensorSlotU16 && !ce_deep_depth_ok(slot.depth))
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "tensor ingest: the output depth must be 8, 10, 12 or 16 bits, got " + std::to_string(slot.depth));
+    tensor_plan plan;
+    if (int rc = tensor_check(ctx, t, w, h, 1, slot, &plan)) return rc;
+    const size_t samples = (size_t)w * h * 3, out_bytes = samples * (slot.kind == kTensorSlotU8 ? 1 : slot.kind == kTensorSlotU16 ? 2 : 4);
+    if (out_len != samples)
+        return ce_fail(ctx, CE_ERR_BAD_LENGTH, "tensor ingest: out_len must be " + std::to_string(samples) + " samples, got " + std::to_string(out_len));
+    const bool host = t->memory == CE_MEM_HOST;  // a device tensor is read in place: nothing goes in
+    ce_tensor_dev src = plan.dev;
+    return ce_leaf_roundtrip(
+        ctx, host ? plan.stage_bytes : 0,
+        [&](uint8_t *h_in, uint8_t *d_in) {
+            if (host) src = tensor_stage(plan, 0, w, h, h_in, d_in);
+        },
+        out, out_bytes, [&](uint8_t *, uint8_t *d_out) { return ce_launch_tensor(ctx, ctx->stream, src, w, h, 1, d_out, out_bytes, slot.kind, slot.depth); });
+}
+
 // ---- alpha: composited over solid backgrounds (alpha.hip) -------------------------------------------------------------------
 
 int alpha_backgrounds_ok(ce_ctx *ctx, uint32_t n_bg, const uint16_t *backgrounds, uint32_t depth)
@@ -1416,6 +1572,28 @@ int ce_batch_set_test_yuv_hlg(ce_batch *b, uint32_t pair_index, uint32_t ref_ind
 int ce_yuv_hlg_to_linear(ce_ctx *ctx, const ce_yuv_image *image, const ce_hlg *hd, uint32_t w, uint32_t h, float *out, size_t out_len)
 {
     return yuv_to_linear(ctx, image, hd, w, h, out, out_len);
+}
+
+// strided tensors
+int ce_batch_set_reference_tensor(ce_batch *b, uint32_t first_ref, uint32_t count, const ce_tensor_image *t)
+{
+    return set_tensor(b, false, first_ref, nullptr, count, t);
+}
+int ce_batch_set_test_tensor(ce_batch *b, uint32_t first_pair, const uint32_t *ref_indices, uint32_t count, const ce_tensor_image *t)
+{
+    return set_tensor(b, true, first_pair, ref_indices, count, t);
+}
+int ce_tensor_to_rgb8(ce_ctx *ctx, const ce_tensor_image *t, uint32_t w, uint32_t h, uint8_t *out, size_t out_len)
+{
+    return tensor_to_host(ctx, t, w, h, tensor_slot{kTensorSlotU8, 8}, out, out_len);
+}
+int ce_tensor_to_rgb16(ce_ctx *ctx, const ce_tensor_image *t, uint32_t w, uint32_t h, uint32_t depth_out, uint16_t *out, size_t out_len)
+{
+    return tensor_to_host(ctx, t, w, h, tensor_slot{kTensorSlotU16, depth_out}, out, out_len);
+}
+int ce_tensor_to_linear(ce_ctx *ctx, const ce_tensor_image *t, uint32_t w, uint32_t h, float *out, size_t out_len)
+{
+    return tensor_to_host(ctx, t, w, h, tensor_slot{kTensorSlotLin, 0}, out, out_len);
 }
 
 // alpha

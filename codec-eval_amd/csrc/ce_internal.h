@@ -195,6 +195,7 @@ struct ce_batch {
     // the wide staging pairs of every image a conversion kernel follows: one pinned + one device staging image each, made
     // on first use and handed out in turn (ce_ingest.cpp: wide_send, which states their size and alone touches them)
     uint8_t *h_wide[2] = {}, *d_wide[2] = {};
+    size_t wide_cap[2] = {};  // bytes a pair holds: what wide_send states, more once a tensor image needed more
     hipEvent_t ev_wide[2] = {};
     bool wide_busy[2] = {};
     int next_wide = 0;
@@ -524,6 +525,20 @@ inline void ce_fill_yuv_args(YuvArgs &a, const ce_yuv_dev &src, uint32_t w, uint
 // samples: depth 8), one launch (alpha.hip)
 int ce_launch_alpha(ce_ctx *ctx, hipStream_t stream, const void *d_src, bool src16, void *d_dst, bool dst16, uint32_t depth,
                     size_t n_pixels, uint32_t n_bg, const uint16_t *backgrounds);
+
+// `count` images of a strided tensor on the device as tensor.hip reads them: checked by ce_ingest.cpp (tensor_check), the
+// strides in elements, data in device memory
+struct ce_tensor_dev {
+    const void *data;
+    int64_t stride_n, stride_c, stride_y, stride_x;
+    int dtype;     // enum ce_dtype
+    int quantise;  // enum ce_quantise
+};
+// w x h pixels of each of `count` images of `src` -> packed RGB in `count` slots slot_bytes apart from d_dst on, one launch
+// (tensor.hip).  slot: 0 u8, 1 u16 of `depth` bits, 2 f32 linear light (depth unused); the (dtype, slot) pairs the header
+// admits, anything else is CE_ERR_INVALID_ARG
+int ce_launch_tensor(ce_ctx *ctx, hipStream_t stream, const ce_tensor_dev &src, uint32_t w, uint32_t h, uint32_t count, void *d_dst,
+                     size_t slot_bytes, int slot, uint32_t depth);
 
 // n_samples floats at d_src (16-byte aligned staging) -> d_dst with NaN -> 0 and the clamp to +-CE_LINEAR_MAX (cicp.hip)
 int ce_launch_linear_sanitise(ce_ctx *ctx, hipStream_t stream, const float *d_src, float *d_dst, size_t n_samples);

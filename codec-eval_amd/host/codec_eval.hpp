@@ -634,6 +634,54 @@ inline void batch_set_test_yuv_hlg(const HipBackend &be, ce_batch *batch, uint32
 {
     detail::check(be, ce_batch_set_test_yuv_hlg(batch, pair_index, ref_index, &image, &hlg), "yuv_hlg", 0, 0, 0);
 }
+// ---- tensors of a framework (include/ce_metrics.h: ce_batch_set_*_tensor) ------------------------------------
+// The struct is the ABI's; tensor_chw() / tensor_hwc() fill the two common layouts of `count` contiguous images (NCHW planar;
+// NHWC interleaved with `channels` 3 or 4) and the caller changes what differs: a crop's stride_y, a gray tensor's stride_c = 0.
+using TensorImage = ce_tensor_image;
+inline TensorImage tensor_chw(const void *data, uint32_t width, uint32_t height, int dtype, int memory = CE_MEM_HOST,
+                              int quantise = CE_QUANT_NEAREST_EVEN)
+{
+    TensorImage t{};
+    t.data = data, t.dtype = dtype, t.memory = memory, t.quantise = quantise;
+    t.stride_x = 1, t.stride_y = width, t.stride_c = (int64_t)width * height, t.stride_n = 3 * t.stride_c;
+    return t;
+}
+inline TensorImage tensor_hwc(const void *data, uint32_t width, uint32_t height, int dtype, int channels = 3, int memory = CE_MEM_HOST,
+                              int quantise = CE_QUANT_NEAREST_EVEN)
+{
+    TensorImage t{};
+    t.data = data, t.dtype = dtype, t.memory = memory, t.quantise = quantise;
+    t.stride_c = 1, t.stride_x = channels, t.stride_y = (int64_t)width * channels, t.stride_n = t.stride_y * height;
+    return t;
+}
+inline std::vector<uint8_t> tensor_to_rgb8(const HipBackend &be, const TensorImage &t, uint32_t width, uint32_t height)
+{
+    std::vector<uint8_t> out((size_t)width * height * 3);
+    detail::check(be, ce_tensor_to_rgb8(be.ctx(), &t, width, height, out.data(), out.size()), "tensor", width, height, out.size());
+    return out;
+}
+inline std::vector<uint16_t> tensor_to_rgb16(const HipBackend &be, const TensorImage &t, uint32_t width, uint32_t height, uint32_t depth_out)
+{
+    std::vector<uint16_t> out((size_t)width * height * 3);
+    detail::check(be, ce_tensor_to_rgb16(be.ctx(), &t, width, height, depth_out, out.data(), out.size()), "tensor", width, height, out.size());
+    return out;
+}
+inline std::vector<float> tensor_to_linear(const HipBackend &be, const TensorImage &t, uint32_t width, uint32_t height)
+{
+    std::vector<float> out((size_t)width * height * 3);
+    detail::check(be, ce_tensor_to_linear(be.ctx(), &t, width, height, out.data(), out.size()), "tensor", width, height, out.size());
+    return out;
+}
+// images 0 .. count - 1 into consecutive slots; a device tensor is read in place, behind what the context's stream holds at the call
+inline void batch_set_reference_tensor(const HipBackend &be, ce_batch *batch, uint32_t first_ref, uint32_t count, const TensorImage &t)
+{
+    detail::check(be, ce_batch_set_reference_tensor(batch, first_ref, count, &t), "tensor", 0, 0, 0);
+}
+inline void batch_set_test_tensor(const HipBackend &be, ce_batch *batch, uint32_t first_pair, const uint32_t *ref_indices, uint32_t count,
+                                  const TensorImage &t)
+{
+    detail::check(be, ce_batch_set_test_tensor(batch, first_pair, ref_indices, count, &t), "tensor", 0, 0, 0);
+}
 // ---- gain-map images -> their HDR rendition in linear light (include/ce_metrics.h: ce_gainmap_to_linear) ----
 // an SDR base image read by a ColourDescription, a small 8-bit map in host memory (the struct carries no length: width *
 // height * channels bytes are read) and the metadata, whose gains and headrooms are log2 values

@@ -20,6 +20,7 @@ from . import (ColourDescription, GainMap, HlgDescription, DEEP_DEPTHS, PIXEL_RG
                MetricConfig, MetricResult, _error_obj, estimate_batch_bytes, CE_ERR_BACKEND)
 from . import RESAMPLE_LANCZOS3
 from . import CHROMA_TRIANGLE, MEM_HOST, YUV_400, YUV_420, YUV_444, YUV_BT601, YUV_FULL, YUV_PLANAR, YUV_SEMIPLANAR, YuvImage, yuv_coefficients
+from . import QUANT_NEAREST_EVEN, TensorImage, quantise_tensor
 from . import ALPHA_BLACK_WHITE, ALPHA_BLEND_LINEAR, MAX_BACKGROUNDS, PIXEL_RGBA_F32, composite_over, scale_background, srgb_table
 from . import reports as R
 from .viewing import SimulationMode, ViewingCondition
@@ -67,6 +68,7 @@ class ImageData:
     # metadata: the HDR rendition is scored, in linear light.  Not with an HlgDescription.
     gain_map: Optional[GainMap] = None
     premultiplied: bool = False  # a linear RGBA image whose colour samples already hold colour * coverage
+    tensor_image: Optional[TensorImage] = None  # a framework's tensor as it is (ImageData.tensor); `data` is then empty
 
     @staticmethod
     def rgb(data, width: int, height: int, colour: Optional[Colour] = None, gain_map: Optional[GainMap] = None) -> "ImageData":
@@ -140,6 +142,32 @@ class ImageData:
         return ImageData(np.empty(0, np.uint8), int(width), int(height), 3, None if icc_profile is None else bytes(icc_profile), 0, img,
                          colour=_colour_at(colour, depth))
 
+    @staticmethod
+    def tensor(obj, layout: str = "CHW", depth: int = 0, linear: bool = False, quantise: int = QUANT_NEAREST_EVEN) -> "ImageData":
+        """One image as a framework holds it - a learned codec's float tensor in [0, 1], a GPU decoder's uint8 planes; a numpy
+        array or a torch tensor, on the host or the device, any strides (TensorImage.from_array) - as it is: the session reads
+        it through its strides on the device, straight into the batch slot (Batch.set_*_tensor, the definition of
+        include/ce_metrics.h).  depth = 0: scored as RGB8, a float tensor quantised to 8 bits by
+        `quantise`; depth 8, 10, 12 or 16: scored through a deep batch at that depth; linear=True: a float tensor of linear
+        light with sRGB primaries, scored through a linear batch.  The multi-device session and to_rgb8_vec quantise on the
+        host with quantise_tensor, the same definition.  A device tensor must stay alive and unchanged until the scores are in."""
+        if depth and depth not in DEEP_DEPTHS:
+            raise ValueError(f"depth must be 0 or one of {DEEP_DEPTHS}, got {depth}")
+        if linear and depth:
+            raise ValueError("a tensor is scored at an integer depth or in linear light, not both")
+        t = obj if isinstance(obj, TensorImage) else TensorImage.from_array(obj, layout, quantise)
+        if t.count != 1:
+            raise ValueError(f"ImageData.tensor holds one image, the tensor has {t.count}")
+        return ImageData(np.empty(0, np.uint8), t.width, t.height, 3, None, int(depth), linear=bool(linear), tensor_image=t)
+
+    def _tensor_to_host(self, depth: int) -> np.ndarray:
+        """The device's conversion of the tensor restated on the host: packed samples of `depth` bits."""
+        t = self.tensor_image
+        a = t.host_elements()[0]
+        if a.dtype in (np.uint8, np.uint16):  # integer code values: clamped as deep ingest clamps
+            return np.minimum(a, (1 << depth) - 1).astype(np.uint8 if a.dtype == np.uint8 and depth == 8 else np.uint16).reshape(-1)
+        return quantise_tensor(a, depth, t.quantise).reshape(-1)
+
     def _yuv_to_rgb8_host(self) -> np.ndarray:
         """The device's conversion restated on the host for to_rgb8_vec (int64, the definition of include/ce_metrics.h)."""
         y, w, h = self.yuv_image, self.width, self.height
@@ -182,7 +210,12 @@ class ImageData:
             raise MetricCalculation(CE_ERR_BACKEND, "Metric calculation failed: an image in linear light or with a non-sRGB colour description has no RGB8 form")
         if self.yuv_image is not None:
             return self._yuv_to_rgb8_host()
-        data = self.data if self.channels == 3 else np.ascontiguousarray(self.data.reshape(-1, 4)[:, :3]).reshape(-1)
+        if self.tensor_image is not None and not self.depth:
+            return self._tensor_to_host(8).astype(np.uint8)
+        if self.tensor_image is not None:
+            data = self._tensor_to_host(self.depth)
+        else:
+            data = self.data if self.channels == 3 else np.ascontiguousarray(self.data.reshape(-1, 4)[:, :3]).reshape(-1)
         if self.depth:  # to_8bit's rule for any depth: what the reference does to a 10-bit decode before it measures
             maxv = (1 << self.depth) - 1
             return np.minimum((np.minimum(data, maxv).astype(np.uint64) * 255 + maxv // 2) // maxv, 255).astype(np.uint8)
@@ -542,6 +575,10 @@ class EvalSession:
             if pair_index is None:
                 return batch.set_reference_yuv_cicp(ref_index, image.yuv_image, colour)
             return batch.set_test_yuv_cicp(pair_index, ref_index, image.yuv_image, colour)
+        if image.tensor_image is not None:  # a float tensor of linear light, read in place
+            if pair_index is None:
+                return batch.set_reference_tensor(ref_index, image.tensor_image)
+            return batch.set_test_tensor(pair_index, [ref_index], image.tensor_image)
         if image.colour is not None and image.icc_profile is not None:
             refuse("an image with both a colour description and an ICC profile is not supported")
         profile = self._profile_for(image) if pair_index is not None and not image.linear and image.gain_map is None else None
@@ -678,6 +715,8 @@ class EvalSession:
                 else:
                     if image.yuv_image is not None:
                         batch.set_reference_yuv(ri, image.yuv_image)
+                    elif image.tensor_image is not None:  # a framework's tensor: read through its strides on the device, into the slot
+                        batch.set_reference_tensor(ri, image.tensor_image)
                     else:
                         batch.set_reference_fmt(ri, image.data, image.pixel_format)
                     ref_of = [ri] * max(len(bgs), 1)
@@ -693,7 +732,9 @@ class EvalSession:
                         batch.set_test_over(k, ref_of, decoded.data, decoded.pixel_format, bg_side[1])
                     else:
                         for j in range(n):  # an opaque decode against a source with alpha: the same image over every background
-                            if decoded.yuv_image is not None and profile is not None:  # planes with a profile the library takes: one launch, at the planes' own depth
+                            if decoded.tensor_image is not None:
+                                batch.set_test_tensor(k + j, [ref_of[j]], decoded.tensor_image)
+                            elif decoded.yuv_image is not None and profile is not None:  # planes with a profile the library takes: one launch, at the planes' own depth
                                 batch.set_test_yuv_icc(k + j, ref_of[j], decoded.yuv_image, decoded.yuv_image.depth, profile)
                             elif decoded.yuv_image is not None and decoded.icc_profile is not None:  # a session with a cms: to_rgb8_srgb on the host
                                 batch.set_test(k + j, ref_of[j], decoded.to_rgb8_srgb(self._cms))

@@ -1277,6 +1277,66 @@ int ce_icc_over_to_linear(ce_ctx *ctx, const void *pixels, size_t len, int forma
 int ce_linear_over(ce_ctx *ctx, const void *pixels, size_t len, int format, int premultiplied, uint32_t w, uint32_t h, const float bg[3],
                    float *out, size_t out_len);
 
+/* ---- tensors: a framework's strided image tensors into slots of a resident batch -------------------
+ * A learned codec returns its decoded images as an N x 3 x H x W tensor of float32, float16 or bfloat16 in [0, 1] on the
+ * device; a GPU decoder (a framework's JPEG decoder on a device, rocJPEG's RGB outputs) returns 3 x H x W or pitched H x W x 3
+ * uint8 there.  These calls read such a tensor through its strides and write the slots in one kernel: nothing crosses the bus
+ * for a device tensor, and the rounding from float to the integer grid is the definition below, not whatever the glue did.
+ * Channel c in {0, 1, 2} of pixel (y, x) of image n is the element at n * stride_n + c * stride_c + y * stride_y + x * stride_x
+ * (strides in ELEMENTS, not bytes): CHW / NCHW (stride_x = 1), HWC / NHWC and channels_last (stride_c = 1, stride_x = 3),
+ * RGBA (stride_x = 4; the fourth channel is never read), cropped views and pitched surfaces (stride_y above the row), a gray
+ * tensor expanded to three channels (stride_c = 0).
+ * Definition, per sample, with m = 2^D - 1 for the slot's depth D (8 on an RGB8 batch, that side's depth on a deep batch):
+ *   a float dtype into an integer slot:
+ *     v = f32(x), an exact widening (bf16: the 16 bits shifted left by 16)
+ *     c = (v > 0) ? min(v, 1.0f) : 0.0f             NaN and -0 become +0
+ *     p = c * f32(m)                                one f32 multiply
+ *     q = rint(p), ties to even, under CE_QUANT_NEAREST_EVEN; floor(p) under CE_QUANT_TRUNCATE
+ *     NEAREST_EVEN is a framework's round(clamp(float32(x), 0, 1) * m), ties to even, on every input that is not NaN; TRUNCATE is the
+ *     mul(255).byte() idiom on in-range input.
+ *   a float dtype into a slot of a linear batch: the sample is linear light, f32(x), then the clamp of a linear image (NaN ->
+ *     0, then [-CE_LINEAR_MAX, CE_LINEAR_MAX]); quantise must be 0.
+ *   CE_DTYPE_U8 into an RGB8 batch or a deep side of depth 8: as it is (widened to u16 on the deep side).
+ *   CE_DTYPE_U16 into a deep side: min(v, m), as deep ingest clamps.  Integer dtypes: quantise must be 0.
+ * tests/tensor_restatement.py restates this in numpy; the device equals it bit for bit.
+ * ce_batch_set_reference_tensor / ce_batch_set_test_tensor: images n = 0 .. count - 1 of the batch's shape into reference slots
+ * first_ref + n / test slots first_pair + n, pair first_pair + n bound to reference ref_indices[n].
+ *   CE_MEM_HOST: one staged copy and one launch per image on the batch's upload stream, with the ordering of
+ *     ce_batch_set_*_fmt; the rows are copied as they are and the tensor is consumed on return.  Only layouts whose rows are
+ *     contiguous runs are taken: stride_x = 1 (planar, or gray with stride_c = 0), or stride_c = 1 with stride_x 3 or 4.
+ *   CE_MEM_DEVICE: read in place on the context's device, ONE launch for all count images, on the batch's upload stream,
+ *     ordered as every slot write and, for this source alone, behind everything the caller has enqueued on the context's stream
+ *     (ce_ctx_stream) before the call: a model that runs on the stream the context was created on (ce_ctx_create_on_stream)
+ *     needs no host synchronisation between its last kernel and this call.  A tensor written on any other stream must be
+ *     complete before the call, as device planes must.  The caller keeps the tensor alive and unchanged until the batch's next
+ *     launch has been collected.  The call returns without waiting.
+ * CE_ERR_INVALID_ARG, with the reason in ce_last_error and the batch still usable, for a null struct or data pointer, an unknown
+ * dtype, memory or quantise value, quantise != 0 where it has no meaning (integer dtypes, linear slots), a negative stride,
+ * stride_x < 1 or stride_y < 1 (stride_c = 0 and stride_n = 0 are allowed), a data pointer not aligned to its element size, an
+ * extent in bytes that overflows size_t, CE_DTYPE_U8 onto a deep side whose depth is not 8, CE_DTYPE_U16 into an RGB8 batch, an
+ * integer dtype into a linear batch, count = 0 or above 65535, a slot range or a ref_indices entry past the batch, and a host
+ * layout other than the three above ("make it contiguous or pass device memory").
+ * ce_tensor_to_rgb8 / _to_rgb16 / _to_linear: image n = 0 of width x height through the same kernel into host memory, as an
+ * RGB8 slot, a deep side of depth_out in {8, 10, 12, 16} or a linear slot would hold it (out_len = width * height * 3
+ * samples); errors as above, CE_ERR_BAD_LENGTH for a wrong out_len.
+ * Not part of this: tensors through ce_eval_batch, ce_ref_* and the *_over / ICC / CICP routes (a tensor is sRGB-encoded, or
+ * linear light with sRGB primaries on a linear batch); signed or 64-bit dtypes; negative strides; float tensors scaled to
+ * anything but [0, 1]. */
+enum ce_dtype { CE_DTYPE_U8 = 0, CE_DTYPE_U16 = 1, CE_DTYPE_F16 = 2, CE_DTYPE_BF16 = 3, CE_DTYPE_F32 = 4 };
+enum ce_quantise { CE_QUANT_NEAREST_EVEN = 0, CE_QUANT_TRUNCATE = 1 };
+typedef struct ce_tensor_image {
+    const void *data;   /* element (n = 0, c = 0, y = 0, x = 0) */
+    int64_t stride_n, stride_c, stride_y, stride_x;   /* in ELEMENTS, not bytes */
+    int dtype;          /* enum ce_dtype */
+    int memory;         /* enum ce_mem */
+    int quantise;       /* enum ce_quantise; float dtypes into integer slots only, otherwise must be 0 */
+} ce_tensor_image;
+int ce_batch_set_reference_tensor(ce_batch *b, uint32_t first_ref, uint32_t count, const ce_tensor_image *t);
+int ce_batch_set_test_tensor(ce_batch *b, uint32_t first_pair, const uint32_t *ref_indices, uint32_t count, const ce_tensor_image *t);
+int ce_tensor_to_rgb8(ce_ctx *ctx, const ce_tensor_image *t, uint32_t w, uint32_t h, uint8_t *out, size_t out_len);
+int ce_tensor_to_rgb16(ce_ctx *ctx, const ce_tensor_image *t, uint32_t w, uint32_t h, uint32_t depth_out, uint16_t *out, size_t out_len);
+int ce_tensor_to_linear(ce_ctx *ctx, const ce_tensor_image *t, uint32_t w, uint32_t h, float *out, size_t out_len);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------ */
 /* Bracket every kernel launch with a HIP event pair, recorded on the stream the kernel is launched on,
  * and accumulate per-kernel time.  on = 0: off (default).  on = 2: events only; the batch keeps its
