@@ -876,14 +876,17 @@ int ce_batch_run(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_t f
 
 // Device bytes a batch of this shape needs once the metrics in `mask` have run (working sets are allocated lazily,
 // per metric).  Mirrors ce_ssim2_prepare / dssim_prepare / ba_prepare, with the plane padding folded into one factor.
-size_t ce_estimate_batch_bytes(uint32_t w, uint32_t h, uint32_t n_refs, uint32_t n_pairs, uint32_t metric_mask)
+// ref_planes: with SSIMULACRA2's final reference planes, which a batch allocates when it first builds them (ssim2.hip:
+// ssim2_ref_blur_allocate).  The ABI's estimate always counts them; ce_eval_batch, whose pooled batches never build, does not.
+static size_t estimate_batch_bytes(uint32_t w, uint32_t h, uint32_t n_refs, uint32_t n_pairs, uint32_t metric_mask, bool ref_planes)
 {
     const double px = (double)w * h, slots = (double)n_refs + n_pairs, pairs = n_pairs;
     double bytes = 3.0 * px * slots + 64.0 * pairs;  // u8 slabs, scores
     double allocations = 8;                          // each device allocation is rounded up; budget 256 KiB of slack apiece
-    if (metric_mask & CE_METRIC_SSIMULACRA2) {  // linear pyramid (levels >= 1) 4, XYB pyramid 16 per slot; 15 row-blurred planes x 1.333 per pair
-        bytes += px * (20.0 * slots + 80.0 * pairs);
-        allocations += 24;
+    if (metric_mask & CE_METRIC_SSIMULACRA2) {  // linear pyramid (levels >= 1) 4, XYB pyramid 16 per slot; 15 row-blurred planes x 1.333 per pair;
+        // a reference's final mu1 / s11: 6 planes x 1.333 per reference
+        bytes += px * (20.0 * slots + 80.0 * pairs + (ref_planes ? 32.0 * n_refs : 0.0));
+        allocations += ref_planes ? 30 : 24;
     }
     if (metric_mask & CE_METRIC_DSSIM) {  // linear ping-pong 6 per slot; img 12 + the SSIM maps of all levels 5.4 per pair; the references' per-level img / mu / sq 48
         bytes += px * (6.0 * slots + 48.0 * n_refs + 17.4 * pairs);
@@ -895,6 +898,11 @@ size_t ce_estimate_batch_bytes(uint32_t w, uint32_t h, uint32_t n_refs, uint32_t
     }
     if (metric_mask & CE_METRIC_PSNR) bytes += 8.0 * pairs;
     return (size_t)(bytes * 1.2) + (size_t)(allocations * (256u << 10)) + (8u << 20);  // row / pitch padding of the planar buffers
+}
+
+size_t ce_estimate_batch_bytes(uint32_t w, uint32_t h, uint32_t n_refs, uint32_t n_pairs, uint32_t metric_mask)
+{
+    return estimate_batch_bytes(w, h, n_refs, n_pairs, metric_mask, true);
 }
 
 // the u16 slabs hold 6 bytes per pixel instead of 3, and the tables 4 * 2^depth bytes per side and rule; the working sets
@@ -956,7 +964,7 @@ static size_t chunk_budget(ce_ctx *ctx)
         const ce_batch *pb = kv.second;
         const uint32_t held = (pb->ssim2_ready ? CE_METRIC_SSIMULACRA2 : 0u) | (pb->dssim_ready ? CE_METRIC_DSSIM : 0u) |
                               (pb->ba_ready ? CE_METRIC_BUTTERAUGLI : 0u);
-        pooled += ce_estimate_batch_bytes(pb->w, pb->h, pb->max_refs, pb->max_pairs, held);
+        pooled += estimate_batch_bytes(pb->w, pb->h, pb->max_refs, pb->max_pairs, held, pb->s2_ref_blur[0] != nullptr);
     }
     // ... and no chunk asks for more than kChunkBytesMax: on a 288 GB device a third of the free memory is a 70+ GB batch whose
     // hipMalloc calls alone take seconds (measured: 2000 pairs of 512x512, three metrics - first call 3.7 s + 6.5 s for the
@@ -1090,8 +1098,9 @@ int ce_eval_batch_lut(ce_ctx *ctx, size_t n, const ce_pair_desc *pairs, const ce
         const uint32_t w = it->first.first, h = it->first.second;
         std::vector<const void *> refs;
         for (size_t i : it->second) refs.push_back(pairs[i].reference);
-        const size_t per_pair = ce_estimate_batch_bytes(w, h, 1, 2, metric_mask) - ce_estimate_batch_bytes(w, h, 1, 1, metric_mask) +
-                                ce_estimate_batch_bytes(w, h, 2, 1, metric_mask) - ce_estimate_batch_bytes(w, h, 1, 1, metric_mask);  // a pair with a reference of its own
+        // without SSIMULACRA2's final reference planes: a pooled batch's references are written before every launch, so it never builds them
+        const size_t per_pair = estimate_batch_bytes(w, h, 1, 2, metric_mask, false) - estimate_batch_bytes(w, h, 1, 1, metric_mask, false) +
+                                estimate_batch_bytes(w, h, 2, 1, metric_mask, false) - estimate_batch_bytes(w, h, 1, 1, metric_mask, false);  // a pair with a reference of its own
         auto pooled = ctx->shape_pool.find(std::make_tuple(w, h, 0u));
         const ce_plan_inputs in{chunk_budget(ctx), per_pair, pooled != ctx->shape_pool.end() ? pooled->second->max_pairs : 0u, forced_chunks, ramp0};
         const size_t first = plan.size();
@@ -1282,6 +1291,7 @@ int ce_ref_create(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, u
         return rc;
     }
     b->refs.keep = true;  // whatever CE_KEEP_REFERENCE_STATE says: keeping the state is what a handle is
+    b->ref_handle = true;
     *out = new ce_ref{ctx, b, flags};
     return CE_OK;
 }
@@ -1305,6 +1315,7 @@ int ce_ref_compare_many(ce_ref *ref, const uint8_t *const *tests, const size_t *
         CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
         ce_invalidate_reference_state(nb);  // a new slab: the first compare on it builds
         nb->refs.keep = true;
+        nb->ref_handle = true;
         for (int k = 0; k < 3; k++) nb->refs.builds[k] = b->refs.builds[k];  // the handle's history (ce_ref_stats) carries over
         ce_batch_destroy(b);
         ref->batch = b = nb;
@@ -1494,6 +1505,8 @@ int ce_debug_ssim2_planes(ce_batch *b, int scale, int which, int channel, float 
         case 4:
             if (channel < 0 || channel > 2) return CE_ERR_INVALID_ARG;
             src = b->d_hbuf[scale] + (size_t)channel * CE_SSIM2_STREAMS * d.hplane;
+            // after a split-path launch the row-blurred a, a*a exist nowhere (they were scratch of the build)
+            if (b->s2_split_last) return ce_fail(ctx, CE_ERR_INVALID_ARG, "the last launch took SSIMULACRA2's split path: it leaves no row-blurred reference streams to read");
             break;
         default: return CE_ERR_INVALID_ARG;
     }

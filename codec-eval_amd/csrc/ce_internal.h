@@ -209,6 +209,11 @@ struct ce_batch {
     float *d_lin[CE_MAX_SCALES] = {};  // [slots][3][plane_s] linear RGB pyramid
     float *d_xyb[CE_MAX_SCALES] = {};   // [slots][3][plane_s] positive XYB, one buffer per level
     float *d_hbuf[CE_MAX_SCALES] = {};  // [pairs][3][5][plane_s] row-blurred streams, one buffer per level
+    // The references' final planes mu1 = blur(a), s11 = blur(a*a), per level [max_refs][3][2][plane_s], which the pair column
+    // pass of the split path reads (ssim2.hip: ce_launch_ssim2; record CE_REF_SSIM2_BLUR).  s2_split_last: the last launch
+    // took the split path, so d_hbuf holds no streams 0 and 2 (ce_debug_ssim2_planes).  ref_handle: a reference handle's batch.
+    float *s2_ref_blur[CE_MAX_SCALES] = {};
+    bool s2_split_last = false, ref_handle = false;
     // level 0's row/column pass runs on lvl_stream[0], fenced by events against the front end and the final reduction;
     // the other levels follow the front end on the context's stream (entries 1.. are unused)
     hipStream_t lvl_stream[CE_MAX_SCALES] = {};

@@ -117,6 +117,28 @@ inline std::vector<ce_plan_entry> ce_plan_xcd_list(const uint32_t *pair_ref, uin
     return list;
 }
 
+// Which blur passes an SSIMULACRA2 launch runs.  A reference's own streams mu1 = blur(a), s11 = blur(a*a) do not depend on
+// the distorted image: the split path keeps them as final planes per reference and the pair passes filter only the three
+// streams that involve the distorted image.  It runs when the planes' record covers the launch's references, or when they
+// can be built and amortised.  Building costs about four launches' worth of what a launch then saves, so it must be
+// followed by launches that reuse the planes: the batch keeps reference state, the launch has more pairs than references,
+// and the launch itself REUSED the references' XYB pyramid (`reused`) - the references have outlived a launch, the one
+// sign a batch gives that they stay.  A batch's first launch, and every launch of a batch whose references are written
+// before each one (ce_eval_batch's pooled batches), therefore run the passes as they always were.  A reference handle's
+// batch builds without waiting: staying is what a handle is.  A launch with one pair per reference and nothing to reuse -
+// ce_eval_pair, the one-pair leaves - also keeps the passes as they were: the build would put four dependent launches in
+// front of its own.  enabled = false (CE_SSIM2_REF_BLUR=0): always those.
+enum { CE_SSIM2_BLUR_TODAY = 0, CE_SSIM2_BLUR_SPLIT = 1, CE_SSIM2_BLUR_SPLIT_BUILD = 2 };
+
+inline int ce_plan_ssim2_ref_blur(bool enabled, bool keeps_state, bool handle, bool reused, bool covered, uint32_t n_pairs,
+                                  uint32_t n_refs)
+{
+    if (!enabled || !keeps_state) return CE_SSIM2_BLUR_TODAY;  // a batch that keeps nothing has no record to be covered by
+    if (covered) return CE_SSIM2_BLUR_SPLIT;
+    if (handle) return CE_SSIM2_BLUR_SPLIT_BUILD;
+    return (reused && n_pairs > n_refs) ? CE_SSIM2_BLUR_SPLIT_BUILD : CE_SSIM2_BLUR_TODAY;
+}
+
 // DSSIM's scale pyramid (Dssim::create_image, make_scales_recursive): level 0 is the image, and a level is halved (floor)
 // into the next only while it is at least 8 x 8, up to max_levels levels.  Writes the level sizes, returns their count (0
 // for an empty image).  The one rule of dssim.hip's working set and of ce_dssim_levels.

@@ -8,8 +8,10 @@
 #include <cstdint>
 #include <cstring>
 
-// the records of a batch: the three metric chains in ce_batch_launch's order, then the roundtripped slab (d_refs_rt)
-enum { CE_REF_SSIM2 = 0, CE_REF_DSSIM = 1, CE_REF_BUTTERAUGLI = 2, CE_REF_ROUNDTRIP = 3, CE_REF_KINDS = 4 };
+// the records of a batch: the three metric chains in ce_batch_launch's order, then the roundtripped slab (d_refs_rt), then
+// SSIMULACRA2's final reference planes mu1 / s11 (marked and invalidated like CE_REF_SSIM2: same slab, count and scale count;
+// not a chain of its own, so it does not count in builds[])
+enum { CE_REF_SSIM2 = 0, CE_REF_DSSIM = 1, CE_REF_BUTTERAUGLI = 2, CE_REF_ROUNDTRIP = 3, CE_REF_SSIM2_BLUR = 4, CE_REF_KINDS = 5 };
 
 // the bits of a float parameter (Butteraugli's intensity target): equal bits, equal planes
 inline uint64_t ce_ref_param_f32(float v)

@@ -347,7 +347,14 @@ __device__ __forceinline__ void hblur_chunk(const float *__restrict__ p_cur, con
 // (columns < 0 are the zero padding; its outputs n < 0 do not exist).
 // Wave v loads rows [24*(v&1), +24) of plane (v>>1); the 1920 float4 of a chunk's five output tiles are stored
 // by all 256 threads, consecutive threads writing consecutive 16-byte pieces of a row.
-template <int LEVEL>
+//
+// JOBS, which streams a block filters (only the job -> stream mapping differs, in the worker set-up and in the store loop):
+//   HB_BY_FIRST  block = pair; a reference's first pair runs all five streams, its other pairs the three that involve b
+//   HB_PAIR3     block = pair; every pair runs streams 1, 3, 4 (the column pass takes mu1 / s11 from the references' final planes)
+//   HB_REF2      block = REFERENCE slot p; streams 0 and 2 (a, a*a) of the reference's own planes into [ref][channel][2][plane]
+enum { HB_BY_FIRST = 0, HB_PAIR3 = 1, HB_REF2 = 2 };
+
+template <int LEVEL, int JOBS = HB_BY_FIRST>
 __global__ __launch_bounds__(HB_THREADS) void k_ssim2_hblur_lds(const float *__restrict__ xyb,
                                                                 const uint32_t *__restrict__ pair_ref,
                                                                 float *__restrict__ hbuf, uint32_t w, uint32_t h,
@@ -372,8 +379,8 @@ __global__ __launch_bounds__(HB_THREADS) void k_ssim2_hblur_lds(const float *__r
         w = tab.w[l], h = tab.h[l], pitch = tab.pitch[l], plane = tab.plane[l];
     }
     const uint32_t y0 = bx * HB_ROWS;
-    const float *ga = xyb + ((size_t)pair_ref[p] * 3 + c) * plane;
-    const float *gb = xyb + ((size_t)(max_refs + p) * 3 + c) * plane;
+    const float *ga = xyb + ((size_t)(JOBS == HB_REF2 ? p : pair_ref[p]) * 3 + c) * plane;
+    const float *gb = JOBS == HB_REF2 ? ga : xyb + ((size_t)(max_refs + p) * 3 + c) * plane;
     const int n_chunks = (int)(pitch / HB_CW);  // N + 1
     // Loads and stores are kept in DIFFERENT waves.  vmcnt retires in order, so in a wave that does both a load
     // issued after a burst of row stores cannot be seen complete before those stores are acknowledged by the memory
@@ -427,11 +434,12 @@ __global__ __launch_bounds__(HB_THREADS) void k_ssim2_hblur_lds(const float *__r
     // filter task of this thread.  The reference-only streams (a, a*a) are the same for every distorted image of a
     // reference: only the reference's first pair (pair_first[p] == p) produces them, the other pairs run the three
     // streams that involve b - the column pass reads streams 0 and 2 from the first pair's planes.
-    const bool full = pair_first[p] == p;
-    const uint32_t n_jobs = full ? CE_SSIM2_STREAMS : 3;
+    const bool full = JOBS == HB_BY_FIRST && pair_first[p] == p;
+    const uint32_t n_jobs = JOBS == HB_REF2 ? 2 : full ? CE_SSIM2_STREAMS : 3;
     const bool worker = tid < n_jobs * HB_ROWS;
     const uint32_t tj = worker ? tid / HB_ROWS : 0, tr = worker ? tid % HB_ROWS : 0;
-    const uint32_t ts = full ? tj : (tj == 0 ? 1u : tj + 2u);  // jobs of a later pair: streams 1, 3, 4
+    // jobs of a later pair: streams 1, 3, 4; of a reference: streams 0, 2
+    const uint32_t ts = JOBS == HB_REF2 ? 2u * tj : full ? tj : (tj == 0 ? 1u : tj + 2u);
     const bool plain = ts < 2;
     const float *sp = &s_in[(ts == 1 || ts == 3) ? 1 : 0][tr];
     const float *sq = &s_in[(ts == 2) ? 0 : 1][tr];  // a*a -> a, b*b and a*b -> b (ignored when plain)
@@ -441,7 +449,7 @@ __global__ __launch_bounds__(HB_THREADS) void k_ssim2_hblur_lds(const float *__r
     st.p2 = st.q2 = 0.0f;
 #pragma unroll
     for (int j = 0; j < 10; j++) st.d[j] = 0.0f;  // inputs before column -28 of chunk 0: zero padding
-    float *obase = hbuf + ((size_t)p * 3 + c) * CE_SSIM2_STREAMS * plane;
+    float *obase = hbuf + ((size_t)p * 3 + c) * (JOBS == HB_REF2 ? 2 : CE_SSIM2_STREAMS) * plane;
 
     // Iteration k: (wave 3) lay chunk k+1 into the half nobody reads and request chunk k+2; filter chunk k; barrier;
     // (waves 0-2) store chunk k's outputs; barrier.
@@ -457,11 +465,12 @@ __global__ __launch_bounds__(HB_THREADS) void k_ssim2_hblur_lds(const float *__r
                 const uint32_t idx = it * 192 + tid;
                 if (idx >= n_jobs * (HB_ROWS * 8)) break;
                 const uint32_t oj = idx / (HB_ROWS * 8), rem = idx % (HB_ROWS * 8), orow = rem >> 3, oq = rem & 7;
-                const uint32_t os = full ? oj : (oj == 0 ? 1u : oj + 2u);
+                const uint32_t os = JOBS == HB_REF2 ? 2u * oj : full ? oj : (oj == 0 ? 1u : oj + 2u);
+                const uint32_t op = JOBS == HB_REF2 ? oj : os;  // the stream's plane behind obase
                 const float *src = &s_out[os * HB_HALF + (4 * oq) * HB_LD + orow];
                 const float4 v = make_float4(src[0], src[HB_LD], src[2 * HB_LD], src[3 * HB_LD]);
                 if (y0 + orow < h)
-                    *reinterpret_cast<float4 *>(obase + (size_t)os * plane + (size_t)(y0 + orow) * pitch + HB_CW * (k - 1) + 4 * oq) = v;
+                    *reinterpret_cast<float4 *>(obase + (size_t)op * plane + (size_t)(y0 + orow) * pitch + HB_CW * (k - 1) + 4 * oq) = v;
             }
         }
         lds_barrier();  // the output tiles may be overwritten by chunk k+1
@@ -499,7 +508,9 @@ struct vblur_state {
 // STORE = true (CE_FLAG_SSIMULACRA2_MAPS) also writes the three per-pixel terms the pool sums - d, artifact, detail - of
 // output row i - 4 to column `lane` of the wave's strip of `map` (planes kind * plane apart), one 256-byte row store per term
 // and wave.  `map` and the row offsets are wave-uniform: the addresses are scalar bases plus the lane's offset.
-template <int GG, bool CHECKED, bool STORE>
+// REFB = true: mu1 and s11 are not filtered here - ring slots 0 and 2 hold the reference's FINAL planes (k_ssim2_ref_vblur) at
+// the XYB planes' row offset, i.e. output row i - 4 - and only streams 1, 3, 4 keep a recursion and a delay line.
+template <int GG, bool CHECKED, bool STORE, bool REFB>
 __device__ __forceinline__ void vblur_group(vblur_state &st, const float *__restrict__ slot, int g, uint32_t h,
                                             const rg_consts &rg, float *__restrict__ map, uint32_t pitch, size_t plane,
                                             uint32_t lane, bool active)
@@ -514,6 +525,7 @@ __device__ __forceinline__ void vblur_group(vblur_state &st, const float *__rest
         float v[CE_SSIM2_STREAMS];
 #pragma unroll
         for (int s = 0; s < CE_SSIM2_STREAMS; s++) {
+            if (REFB && (s == 0 || s == 2)) continue;
             const float ld = slot[s * VB_SLOT + e * 64];
             const float right = (!CHECKED || i < h) ? ld : 0.0f;
             const float left = st.rr[(re + 6) & 15][s];  // row i-10
@@ -522,7 +534,8 @@ __device__ __forceinline__ void vblur_group(vblur_state &st, const float *__rest
         }
         if (!CHECKED || (i >= 4 && i < h + 4)) {
             const float img1 = slot[5 * VB_SLOT + e * 64], img2 = slot[6 * VB_SLOT + e * 64];
-            const float mu1 = v[0], mu2 = v[1], s11 = v[2], s22 = v[3], s12 = v[4];
+            const float mu1 = REFB ? slot[0 * VB_SLOT + e * 64] : v[0], s11 = REFB ? slot[2 * VB_SLOT + e * 64] : v[2];
+            const float mu2 = v[1], s22 = v[3], s12 = v[4];
             const float mu11 = mu1 * mu1, mu22 = mu2 * mu2, mu12 = mu1 * mu2;
             const float mu_diff = mu1 - mu2;
             const float num_m = __builtin_fmaf(mu_diff, -mu_diff, 1.0f);
@@ -565,14 +578,22 @@ struct ssim2_map_table {
     float *lvl[CE_MAX_SCALES];
 };
 
-template <int LEVEL, bool STORE>
+// the references' final planes mu1 = colblur(rowblur(a)), s11 = colblur(rowblur(a*a)) per scale: [ref][channel][2][plane]
+struct ssim2_ref_table {
+    float *lvl[CE_MAX_SCALES];
+};
+
+// REFB = false is the pass as it always was (streams 0 and 2 from the planes of the reference's first pair, 15 recurrences per
+// lane; refb is not read).  REFB = true, the pair column pass of the split path: mu1 / s11 come from refb.lvl[scale], 9
+// recurrences per lane.  refb comes after all the other arguments, which stay at the offsets they always had.
+template <int LEVEL, bool STORE, bool REFB = false>
 __global__ __launch_bounds__(64) void k_ssim2_vblur_dma(const float *__restrict__ hbuf, const float *__restrict__ xyb,
                                                         const uint32_t *__restrict__ pair_ref,
                                                         double *__restrict__ partials, uint32_t w, uint32_t h,
                                                         uint32_t pitch, size_t plane, uint32_t max_refs, uint32_t scale,
                                                         uint32_t max_vblocks, rg_consts rg, lvl_table tab,
                                                         const uint2 *__restrict__ work, const uint32_t *__restrict__ pair_first,
-                                                        ssim2_map_table maps)
+                                                        ssim2_map_table maps, ssim2_ref_table refb)
 {
     __shared__ __attribute__((aligned(16))) float ring[2 * VB_GROUP];
     uint32_t bx = blockIdx.x, c = blockIdx.y, p = blockIdx.z;
@@ -593,7 +614,9 @@ __global__ __launch_bounds__(64) void k_ssim2_vblur_dma(const float *__restrict_
     const bool active = x0 + lane < w;
     const float *hb = hbuf + ((size_t)p * 3 + c) * CE_SSIM2_STREAMS * plane + x0;
     // streams 0 and 2 (blurred a, a*a) exist once per reference, in the planes of its first pair
-    const float *hb_ref = hbuf + ((size_t)pair_first[p] * 3 + c) * CE_SSIM2_STREAMS * plane + x0;
+    const float *hb_ref = REFB ? nullptr : hbuf + ((size_t)pair_first[p] * 3 + c) * CE_SSIM2_STREAMS * plane + x0;
+    // REFB: mu1 at plane 0, s11 at plane 1 of the reference's final planes
+    const float *fin = REFB ? refb.lvl[scale] + ((size_t)pair_ref[p] * 3 + c) * 2 * plane + x0 : nullptr;
     const float *xa = xyb + ((size_t)pair_ref[p] * 3 + c) * plane + x0;
     const float *xb = xyb + ((size_t)(max_refs + p) * 3 + c) * plane + x0;
     const uint32_t dr = lane >> 4, dc = (lane & 15) * 4;  // DMA: 16 lanes x 16 B per row, 4 rows per instruction
@@ -607,6 +630,18 @@ __global__ __launch_bounds__(64) void k_ssim2_vblur_dma(const float *__restrict_
         float *dst = ring + (g & 1) * VB_GROUP;
         const uint32_t row = min((uint32_t)(4 * g) + dr, h - 1);
         const size_t off = (size_t)row * pitch + dc;
+        if (REFB) {  // the same 7 requests in the same order (the vmcnt(7) below counts them); slots 0 and 2 from the final planes
+            const int rx = 4 * g - 4 + (int)dr;
+            const size_t offx = (size_t)min((uint32_t)max(rx, 0), h - 1) * pitch + dc;
+#pragma unroll
+            for (int s = 0; s < CE_SSIM2_STREAMS; s++) {
+                const float *from = (s == 0 || s == 2) ? fin + (size_t)(s >> 1) * plane + offx : hb + (size_t)s * plane + off;
+                __builtin_amdgcn_global_load_lds((gptr)from, (lptr)(dst + s * VB_SLOT), 16, 0, 0);
+            }
+            __builtin_amdgcn_global_load_lds((gptr)(xa + offx), (lptr)(dst + 5 * VB_SLOT), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gptr)(xb + offx), (lptr)(dst + 6 * VB_SLOT), 16, 0, 0);
+            return;
+        }
 #pragma unroll
         for (int s = 0; s < CE_SSIM2_STREAMS; s++)
             __builtin_amdgcn_global_load_lds((gptr)(((s == 0 || s == 2) ? hb_ref : hb) + (size_t)s * plane + off), (lptr)(dst + s * VB_SLOT), 16, 0, 0);
@@ -637,7 +672,7 @@ __global__ __launch_bounds__(64) void k_ssim2_vblur_dma(const float *__restrict_
         /* group g has landed once at most the 7 requests of group g+1 are outstanding (STORE: the     \
            map stores of group g-1 count too and are older, so this also waits for them) */            \
         asm volatile("s_waitcnt vmcnt(7)" ::: "memory");                                               \
-        vblur_group<GG, CHECKED, STORE>(st, ring + ((GG) & 1) * VB_GROUP + lane, g0 + (GG), h, rg, map, \
+        vblur_group<GG, CHECKED, STORE, REFB>(st, ring + ((GG) & 1) * VB_GROUP + lane, g0 + (GG), h, rg, map, \
                                         pitch, plane, lane, active);                                   \
         /* the slot is free once its LDS reads have returned; refill it with group g+2 */              \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                             \
@@ -672,6 +707,65 @@ __global__ __launch_bounds__(64) void k_ssim2_vblur_dma(const float *__restrict_
     for (int q = 0; q < 6; q++) {
         const double sum = wave_sum(active ? st.acc[q] : 0.0);
         if (lane == 0) dst[q] = sum;
+    }
+}
+
+// ---- reference-only column pass: mu1 and s11 of a reference, once per reference ----------------------------------------------
+// One wave per 64-column strip, channel and reference slot, thread = column.  The two streams a, a*a of the reference's
+// row-blurred planes hin ([ref][channel][2][plane], k_ssim2_hblur_lds<.., HB_REF2>) go through exactly the steps
+// vblur_group runs on its streams 0 and 2 - the same rg_step on the same sums in the same order, a zero right tap for rows
+// i >= h, the left tap 10 rows back - and the output of step i is stored to row i - 4 of out (same layout).  Plain loads, the
+// 32 of a 16-row turn requested together ahead of its steps (rows clamped into the image; a row >= h counts as zero): the
+// recursion is one dependent chain per stream, so nothing else hides the loads' latency.  hin is scratch: it lives in the
+// pairs' row-blurred planes, which the pair row pass overwrites behind this kernel on the same stream.
+template <int LEVEL>
+__global__ __launch_bounds__(64) void k_ssim2_ref_vblur(const float *__restrict__ hin, float *__restrict__ out, uint32_t w, uint32_t h,
+                                                        uint32_t pitch, size_t plane, rg_consts rg, lvl_table tab,
+                                                        ssim2_ref_table hins, ssim2_ref_table outs)
+{
+    uint32_t bx = blockIdx.x;
+    const uint32_t c = blockIdx.y, r = blockIdx.z;
+    if (LEVEL < 0) {  // merged launch of levels 1..
+        uint32_t l = 0;
+        while (l + 1 < tab.n && bx >= tab.blk_end[l]) l++;
+        bx -= l ? tab.blk_end[l - 1] : 0;
+        hin = hins.lvl[tab.first_level + l], out = outs.lvl[tab.first_level + l];
+        w = tab.w[l], h = tab.h[l], pitch = tab.pitch[l], plane = tab.plane[l];
+    }
+    const uint32_t x = bx * 64 + threadIdx.x;
+    if (x >= w) return;  // no barrier below
+    const float *src = hin + ((size_t)r * 3 + c) * 2 * plane + x;         // stream a; a*a is one plane on
+    float *dst = out + ((size_t)r * 3 + c) * 2 * plane + x;               // row i - 4 of mu1, from step i = 4 on
+    float prev[2][3], prev2[2][3], rr[16][2];
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) prev[s][k] = prev2[s][k] = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 16; e++) rr[e][s] = 0.0f;
+    }
+    for (uint32_t i0 = 0; i0 < h + 4; i0 += 16) {  // one turn of the 16-deep register ring: every ring index is static
+        float in[16][2];
+#pragma unroll
+        for (int e = 0; e < 16; e++) {
+            const size_t row = (size_t)min(i0 + e, h - 1) * pitch;
+            in[e][0] = src[row], in[e][1] = src[plane + row];
+        }
+#pragma unroll
+        for (int e = 0; e < 16; e++) {
+            const uint32_t i = i0 + e;
+            if (i < h + 4) {  // wave-uniform
+#pragma unroll
+                for (int s = 0; s < 2; s++) {
+                    const float right = i < h ? in[e][s] : 0.0f;
+                    const float left = rr[(e + 6) & 15][s];  // row i-10
+                    rr[e][s] = right;
+                    const float v = rg_step(left + right, prev[s], prev2[s], rg);
+                    if (i >= 4) dst[(size_t)s * plane] = v;
+                }
+                if (i >= 4) dst += pitch;
+            }
+        }
     }
 }
 
@@ -759,7 +853,8 @@ void ce_ssim2_free(ce_batch *b)
         hipFree(b->d_lin[s]);
         hipFree(b->d_xyb[s]);
         hipFree(b->d_hbuf[s]);
-        b->d_lin[s] = b->d_xyb[s] = b->d_hbuf[s] = nullptr;
+        hipFree(b->s2_ref_blur[s]);
+        b->d_lin[s] = b->d_xyb[s] = b->d_hbuf[s] = b->s2_ref_blur[s] = nullptr;
         if (b->lvl_stream[s]) hipStreamSynchronize(b->lvl_stream[s]);  // the context's stream: drained, not destroyed
         if (b->ev_prep[s]) hipEventDestroy(b->ev_prep[s]);
         if (b->ev_done[s]) hipEventDestroy(b->ev_done[s]);
@@ -778,6 +873,8 @@ void ce_ssim2_free(ce_batch *b)
     b->s2_map_pairs = b->s2_norm_pairs = 0;
     for (ce_xcd_list *L : {&b->work_h, &b->work_v, &b->work_ht, &b->work_vt}) ce_free_xcd_list(L);
     b->refs.of[CE_REF_SSIM2].invalidate();
+    b->refs.of[CE_REF_SSIM2_BLUR].invalidate();
+    b->s2_split_last = false;
     b->ssim2_ready = false;
 }
 
@@ -799,6 +896,25 @@ static int ssim2_allocate(ce_batch *b)
     CE_HIP(ctx, hipMalloc(&b->d_partials, (size_t)b->max_pairs * CE_MAX_SCALES * 3 * b->max_vblocks * 6 * sizeof(double)));
     CE_HIP(ctx, hipMalloc(&b->d_avg, (size_t)b->max_pairs * CE_MAX_SCALES * 18 * sizeof(double)));
     return CE_OK;
+}
+
+// The references' final planes mu1, s11 of every level, allocated by the first launch that builds them - a batch whose
+// references never outlive a launch (ce_eval_batch's pooled batches) never holds them, and ce_eval_batch sizes its chunks
+// without them (ce_api.cpp: estimate_batch_bytes).  All or nothing: false leaves no plane behind and no error, and the launch
+// keeps the unsplit passes.
+static bool ssim2_ref_blur_allocate(ce_batch *b)
+{
+    if (b->s2_ref_blur[0]) return true;
+    for (int s = 0; s < b->n_scales; s++)
+        if (hipMalloc(&b->s2_ref_blur[s], (size_t)b->max_refs * 3 * 2 * b->sd[s].plane * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            for (int t = 0; t < b->n_scales; t++) {
+                hipFree(b->s2_ref_blur[t]);
+                b->s2_ref_blur[t] = nullptr;
+            }
+            return false;
+        }
+    return true;
 }
 
 int ce_ssim2_prepare(ce_batch *b)
@@ -879,12 +995,34 @@ int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
     const int levels = std::min(b->n_scales, b->debug_max_scales);
     const bool cached = b->refs.reuse(CE_REF_SSIM2, d_refs, n_refs_used, (uint64_t)levels);
     const uint32_t z0 = cached ? n_refs_used : 0;
+    // Which blur passes (ce_plan.h: ce_plan_ssim2_ref_blur)?  Split path: mu1 and s11 of every reference are final planes of
+    // the batch, built by two reference-only launches per level group whenever their record does not cover this launch's
+    // references, and the pair passes filter the three streams that involve the distorted image.  Otherwise the passes as
+    // they always were.  CE_SSIM2_REF_BLUR=0 forces the latter, for A/B runs.  The record follows the XYB pyramid's: planes
+    // built from a rebuilt pyramid are rebuilt.
+    static const bool ref_blur_enabled = [] { const char *e = std::getenv("CE_SSIM2_REF_BLUR"); return !(e && e[0] == '0'); }();
+    if (!cached) b->refs.of[CE_REF_SSIM2_BLUR].invalidate();
+    const bool blur_covered = b->refs.keep && b->refs.of[CE_REF_SSIM2_BLUR].covers(d_refs, n_refs_used, (uint64_t)levels);
+    int blur_path = ce_plan_ssim2_ref_blur(ref_blur_enabled, b->refs.keep, b->ref_handle, cached, blur_covered, n_pairs, n_refs_used);
+    // the build's scratch - the references' row-blurred streams, [ref][channel][2][plane] - lives at the start of d_hbuf: it
+    // fits whenever the rule builds (6 planes per reference against 15 per pair), and is checked all the same
+    if (blur_path == CE_SSIM2_BLUR_SPLIT_BUILD && (size_t)n_refs_used * 2 > (size_t)b->max_pairs * CE_SSIM2_STREAMS) blur_path = CE_SSIM2_BLUR_TODAY;
+    if (blur_path == CE_SSIM2_BLUR_SPLIT_BUILD && !ssim2_ref_blur_allocate(b)) blur_path = CE_SSIM2_BLUR_TODAY;  // no room: as before
+    const bool split = blur_path != CE_SSIM2_BLUR_TODAY, build_ref = blur_path == CE_SSIM2_BLUR_SPLIT_BUILD;
+    if (build_ref) b->refs.of[CE_REF_SSIM2_BLUR].invalidate();  // a launch that fails half way leaves nothing valid
+    b->s2_split_last = split;
+    ssim2_ref_table ref_h{}, ref_blur{};
+    for (int s = 0; s < b->n_scales; s++) ref_h.lvl[s] = b->d_hbuf[s], ref_blur.lvl[s] = b->s2_ref_blur[s];
     using hblur_fn = void (*)(const float *, const uint32_t *, float *, uint32_t, uint32_t, uint32_t, size_t, uint32_t,
                               rg_consts, lvl_table, const uint2 *, const uint32_t *);
     using vblur_fn = void (*)(const float *, const float *, const uint32_t *, double *, uint32_t, uint32_t, uint32_t,
                               size_t, uint32_t, uint32_t, uint32_t, rg_consts, lvl_table, const uint2 *, const uint32_t *,
-                              ssim2_map_table);
-    const hblur_fn h_l0 = k_ssim2_hblur_lds<0>, h_tail = k_ssim2_hblur_lds<-1>;
+                              ssim2_map_table, ssim2_ref_table);
+    const hblur_fn h_l0 = split ? k_ssim2_hblur_lds<0, HB_PAIR3> : k_ssim2_hblur_lds<0>;
+    const hblur_fn h_tail = split ? k_ssim2_hblur_lds<-1, HB_PAIR3> : k_ssim2_hblur_lds<-1>;
+    const hblur_fn h_l0_ref = k_ssim2_hblur_lds<0, HB_REF2>, h_tail_ref = k_ssim2_hblur_lds<-1, HB_REF2>;
+    const vblur_fn vr_l0 = k_ssim2_vblur_dma<0, false, true>, vr_tail = k_ssim2_vblur_dma<-1, false, true>;
+    const vblur_fn vr_l0_map = k_ssim2_vblur_dma<0, true, true>, vr_tail_map = k_ssim2_vblur_dma<-1, true, true>;
     const vblur_fn v_l0 = k_ssim2_vblur_dma<0, false>, v_tail = k_ssim2_vblur_dma<-1, false>;
     const vblur_fn v_l0_map = k_ssim2_vblur_dma<0, true>, v_tail_map = k_ssim2_vblur_dma<-1, true>;
     scale_geom g{};
@@ -930,13 +1068,24 @@ int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
             }
             if ((rc = build_pass_list(b, n_pairs, hblk, &b->work_h)) != CE_OK) return rc;
             if ((rc = build_pass_list(b, n_pairs, vblk, &b->work_v)) != CE_OK) return rc;
+            if (build_ref) {  // in front of the pair passes, on their stream; plain 3-D grids over the reference slots
+                CE_LAUNCH_ON(ctx, s0, "ssim2_ref_hblur_L0", h_l0_ref, dim3(hblk, 3, n_refs_used), dim3(HB_THREADS), 0, b->d_xyb[0], b->d_pair_ref,
+                             b->d_hbuf[0], d.w, d.h, d.pitch, d.plane, b->max_refs, rg, tab, (const uint2 *)nullptr,
+                             (const uint32_t *)b->d_pair_first);
+                CE_LAUNCH_ON(ctx, s0, "ssim2_ref_vblur_L0", k_ssim2_ref_vblur<0>, dim3(vblk, 3, n_refs_used), dim3(64), 0,
+                             (const float *)b->d_hbuf[0], b->s2_ref_blur[0], d.w, d.h, d.pitch, d.plane, rg, tab, ref_h, ref_blur);
+            }
             CE_LAUNCH_ON(ctx, s0, "ssim2_hblur_L0", h_l0, dim3(b->work_h.len), dim3(HB_THREADS), 0, b->d_xyb[0], b->d_pair_ref,
                          b->d_hbuf[0], d.w, d.h, d.pitch, d.plane, b->max_refs, rg, tab, (const uint2 *)b->work_h.d,
                          (const uint32_t *)b->d_pair_first);
 #define CE_VBLUR_L0_ARGS                                                                                                   \
     b->d_hbuf[0], b->d_xyb[0], b->d_pair_ref, b->d_partials, d.w, d.h, d.pitch, d.plane, b->max_refs, 0u, b->max_vblocks, rg, tab, \
-        (const uint2 *)b->work_v.d, (const uint32_t *)b->d_pair_first, maps
-            if (store_maps)  // the same pass, also writing the maps: a profiler name of its own
+        (const uint2 *)b->work_v.d, (const uint32_t *)b->d_pair_first, maps, ref_blur
+            if (split && store_maps)
+                CE_LAUNCH_ON(ctx, s0, "ssim2_vblur_ssim_map_L0", vr_l0_map, dim3(b->work_v.len), dim3(64), 0, CE_VBLUR_L0_ARGS);
+            else if (split)
+                CE_LAUNCH_ON(ctx, s0, "ssim2_vblur_ssim_L0", vr_l0, dim3(b->work_v.len), dim3(64), 0, CE_VBLUR_L0_ARGS);
+            else if (store_maps)  // the same pass, also writing the maps: a profiler name of its own
                 CE_LAUNCH_ON(ctx, s0, "ssim2_vblur_ssim_map_L0", v_l0_map, dim3(b->work_v.len), dim3(64), 0, CE_VBLUR_L0_ARGS);
             else
                 CE_LAUNCH_ON(ctx, s0, "ssim2_vblur_ssim_L0", v_l0, dim3(b->work_v.len), dim3(64), 0, CE_VBLUR_L0_ARGS);
@@ -963,13 +1112,25 @@ int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
         }
         if ((rc = build_pass_list(b, n_pairs, tab.blk_end[tab.n - 1], &b->work_ht)) != CE_OK) return rc;
         if ((rc = build_pass_list(b, n_pairs, tab_v.blk_end[tab_v.n - 1], &b->work_vt)) != CE_OK) return rc;
+        if (build_ref) {
+            // the row pass writes to tab.hbuf[l]: the scratch at the start of each level's d_hbuf
+            CE_LAUNCH_ON(ctx, s1, "ssim2_ref_hblur_L1-5", h_tail_ref, dim3(tab.blk_end[tab.n - 1], 3, n_refs_used), dim3(HB_THREADS), 0,
+                         (const float *)nullptr, b->d_pair_ref, (float *)nullptr, 0u, 0u, 0u, (size_t)0, b->max_refs, rg, tab,
+                         (const uint2 *)nullptr, (const uint32_t *)b->d_pair_first);
+            CE_LAUNCH_ON(ctx, s1, "ssim2_ref_vblur_L1-5", k_ssim2_ref_vblur<-1>, dim3(tab_v.blk_end[tab_v.n - 1], 3, n_refs_used), dim3(64), 0,
+                         (const float *)nullptr, (float *)nullptr, 0u, 0u, 0u, (size_t)0, rg, tab_v, ref_h, ref_blur);
+        }
         CE_LAUNCH_ON(ctx, s1, "ssim2_hblur_L1-5", h_tail, dim3(b->work_ht.len), dim3(HB_THREADS), 0,
                      (const float *)nullptr, b->d_pair_ref, (float *)nullptr, 0u, 0u, 0u, (size_t)0, b->max_refs, rg, tab,
                      (const uint2 *)b->work_ht.d, (const uint32_t *)b->d_pair_first);
 #define CE_VBLUR_TAIL_ARGS                                                                                                  \
     (const float *)nullptr, (const float *)nullptr, b->d_pair_ref, b->d_partials, 0u, 0u, 0u, (size_t)0, b->max_refs, 0u,        \
-        b->max_vblocks, rg, tab_v, (const uint2 *)b->work_vt.d, (const uint32_t *)b->d_pair_first, maps
-        if (store_maps)
+        b->max_vblocks, rg, tab_v, (const uint2 *)b->work_vt.d, (const uint32_t *)b->d_pair_first, maps, ref_blur
+        if (split && store_maps)
+            CE_LAUNCH_ON(ctx, s1, "ssim2_vblur_ssim_map_L1-5", vr_tail_map, dim3(b->work_vt.len), dim3(64), 0, CE_VBLUR_TAIL_ARGS);
+        else if (split)
+            CE_LAUNCH_ON(ctx, s1, "ssim2_vblur_ssim_L1-5", vr_tail, dim3(b->work_vt.len), dim3(64), 0, CE_VBLUR_TAIL_ARGS);
+        else if (store_maps)
             CE_LAUNCH_ON(ctx, s1, "ssim2_vblur_ssim_map_L1-5", v_tail_map, dim3(b->work_vt.len), dim3(64), 0, CE_VBLUR_TAIL_ARGS);
         else
             CE_LAUNCH_ON(ctx, s1, "ssim2_vblur_ssim_L1-5", v_tail, dim3(b->work_vt.len), dim3(64), 0, CE_VBLUR_TAIL_ARGS);
@@ -984,6 +1145,7 @@ int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
               b->d_scores, (uint32_t)levels, b->max_vblocks, g);
     CE_HIP(ctx, hipGetLastError());
     if (!cached) b->refs.built(CE_REF_SSIM2, d_refs, n_refs_used, (uint64_t)levels);
+    if (build_ref) b->refs.built(CE_REF_SSIM2_BLUR, d_refs, n_refs_used, (uint64_t)levels);
     return CE_OK;
 }
 
