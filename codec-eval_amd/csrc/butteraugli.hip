@@ -33,11 +33,6 @@ constexpr int TPB = 256;
 constexpr int PSY = 10;  // uhf0 uhf1 hf0 hf1 mf0 mf1 mf2 lf0 lf1 lf2
 enum { UHF0 = 0, UHF1, HF0, HF1, MF0, MF1, MF2, LF0, LF1, LF2 };
 
-struct geom {
-    uint32_t w, h, pitch;
-    size_t plane;
-};
-
 struct blur_kernel {
     int len;
     float k[40];
@@ -119,7 +114,7 @@ typedef float ba_f2 __attribute__((ext_vector_type(2)));
 constexpr int BH_TILES = CE_BH_TILES;  // 8-row tiles per block of the row blur
 
 template <int LEN>
-__global__ __launch_bounds__(TPB) void k_ba_blur_h(const float *__restrict__ in, float *__restrict__ out, geom g, plane_sel si,
+__global__ __launch_bounds__(TPB) void k_ba_blur_h(const float *__restrict__ in, float *__restrict__ out, ce_plane_geom g, plane_sel si,
                                                    plane_sel so, blur_kernel bk, float inv_wsum, uint32_t n_refs_used,
                                                    uint32_t max_refs, int by_slot, ba_slot_grid sg)
 {
@@ -276,8 +271,8 @@ __device__ __forceinline__ float ba_linear_of<float>(const float *, float v) { r
 
 template <bool HALF, typename T>
 __global__ __launch_bounds__(TPB) void k_ba_front(const uint8_t *__restrict__ refs, const uint8_t *__restrict__ tests,
-                                                  const float *__restrict__ lut, const float *__restrict__ lut_test, geom gi,
-                                                  float *__restrict__ xyb, geom g, float w0, float w1, float w2,
+                                                  const float *__restrict__ lut, const float *__restrict__ lut_test, ce_plane_geom gi,
+                                                  float *__restrict__ xyb, ce_plane_geom g, float w0, float w1, float w2,
                                                   float intensity_target, size_t img_bytes, uint32_t n_refs_used, uint32_t max_refs,
                                                   ba_slot_grid sg)
 {
@@ -515,7 +510,7 @@ __device__ __forceinline__ float mask_pre_one(float uhf0, float hf0, float uhf1,
 
 template <int LEN, int EPI, bool HV, int TR>
 __global__ __launch_bounds__(TPB) void k_ba_blur_v_split(const float *__restrict__ tmp, const float *__restrict__ xyb,
-                                                         float *__restrict__ psy, geom g, blur_kernel bk, float inv_wsum,
+                                                         float *__restrict__ psy, ce_plane_geom g, blur_kernel bk, float inv_wsum,
                                                          uint32_t n_refs_used, uint32_t max_refs, ba_slot_grid sg,
                                                          float *__restrict__ mask_in, float *__restrict__ aux_out)
 {
@@ -911,9 +906,9 @@ __device__ __forceinline__ void malta_rows_xy(const ba_f2 *__restrict__ base, ba
 template <int MR, int NT, bool FINAL, bool STORE>
 __global__ __launch_bounds__(NT, NT == 256 ? 3 : 4) void k_ba_malta_l2_xy(const float *__restrict__ psy, const uint32_t *__restrict__ pair_ref,
                                                            const float *__restrict__ blurred, const float *__restrict__ mask_vals,
-                                                           float *__restrict__ diffmap, geom g, uint32_t max_refs,
+                                                           float *__restrict__ diffmap, ce_plane_geom g, uint32_t max_refs,
                                                            malta_bands mb, const uint2 *__restrict__ work, uint32_t tiles_x,
-                                                           const float *__restrict__ sub_map, geom gs, int has_sub,
+                                                           const float *__restrict__ sub_map, ce_plane_geom gs, int has_sub,
                                                            float *__restrict__ blk_max, double *__restrict__ blk_sums, uint32_t n_blocks)
 {
     constexpr int MLR = MR + 2 * MH, RSTEP = NT / 32;  // tile rows; output rows per step of the whole block
@@ -1123,7 +1118,7 @@ __device__ __forceinline__ void store_min3(float v, float &min0, float &min1, fl
 // MaskPsychoImage's per-pixel mask values depend on the REFERENCE's blurred mask input only (FuzzyErosion, then the two
 // f64 rational curves of MaskY / MaskDcY): formed once per reference slot - not once per pair - into two planes that a
 // batch keeps with the PsychoImage between launches; the pair part of CombineChannelsToDiffmap is the Malta kernel's epilogue.
-__global__ __launch_bounds__(TPB) void k_ba_mask_vals(const float *__restrict__ blurred, float *__restrict__ vals, geom g)
+__global__ __launch_bounds__(TPB) void k_ba_mask_vals(const float *__restrict__ blurred, float *__restrict__ vals, ce_plane_geom g)
 {
     const uint32_t z = blockIdx.z;  // reference slot
     BA_XY;
@@ -1278,82 +1273,40 @@ int ce_butteraugli_div_sweep(ce_ctx *ctx, uint64_t seed, uint64_t count, uint64_
     return CE_OK;
 }
 
-void ce_butteraugli_free(ce_batch *b)
+static int ba_prepare(ce_batch *b)
 {
-    for (int l = 0; l < 2; l++) {
-        hipFree(b->ba_psy[l]);
-        hipFree(b->ba_diff[l]);
-        hipFree(b->ba_mask[l]);
-        hipFree(b->ba_mask_vals[l]);
-        b->ba_mask_vals[l] = nullptr;
-        ce_free_xcd_list(&b->ba_work[l]);
-        b->ba_psy[l] = b->ba_diff[l] = b->ba_mask[l] = nullptr;
-    }
-    for (auto &p : b->ba_s) hipFree(p), p = nullptr;
-    for (auto &p : b->ba_s_half) hipFree(p), p = nullptr;
-    if (b->ba_half_stream) hipStreamSynchronize(b->ba_half_stream);  // the context's stream: drained, not destroyed
-    if (b->ev_ba_fork) hipEventDestroy(b->ev_ba_fork);
-    if (b->ev_ba_join) hipEventDestroy(b->ev_ba_join);
-    b->ba_half_stream = nullptr;
-    b->ev_ba_fork = b->ev_ba_join = nullptr;
-    hipFree(b->ba_blk_max);
-    hipFree(b->ba_blk_sums);
-    hipFree(b->ba_pnorm);
-    hipFree(b->ba_map);
-    hipFree(b->ba_cells);
-    b->ba_map = b->ba_cells = nullptr;
-    b->ba_cells_cap = 0;
-    b->ba_map_pairs = 0;
-    b->ba_blk_max = nullptr;
-    b->ba_blk_sums = nullptr;
-    b->ba_pnorm = nullptr;
-    b->refs.of[CE_REF_BUTTERAUGLI].invalidate();
-    b->ba_ready = false;
-}
-
-static int ba_allocate(ce_batch *b)
-{
+    if (b->ba.engaged()) return CE_OK;
     ce_ctx *ctx = b->ctx;
-    auto set = [](ce_batch::ba_level &d, uint32_t w, uint32_t h) {
+    ce_ba_set B;
+    auto set = [](ce_plane_geom &d, uint32_t w, uint32_t h) {
         d.w = w;
         d.h = h;
         d.pitch = (w + 31u) & ~31u;
         d.plane = (size_t)d.pitch * h;
     };
-    set(b->ba[0], b->w, b->h);
-    set(b->ba[1], (b->w + 1) / 2, (b->h + 1) / 2);
-    b->ba_levels = (b->ba[1].w >= 8 && b->ba[1].h >= 8) ? 2 : 1;
-    const size_t slots = (size_t)b->max_refs + b->max_pairs, P = b->max_pairs, p0 = b->ba[0].plane;
-    for (int l = 0; l < b->ba_levels; l++) {
-        CE_HIP(ctx, hipMalloc(&b->ba_psy[l], slots * PSY * b->ba[l].plane * sizeof(float)));
-        if (l == 1) CE_HIP(ctx, hipMalloc(&b->ba_diff[l], P * b->ba[l].plane * sizeof(float)));  // the full-resolution diffmap: ba_map, on request
+    set(B.lvl[0], b->w, b->h);
+    set(B.lvl[1], (b->w + 1) / 2, (b->h + 1) / 2);
+    B.levels = (B.lvl[1].w >= 8 && B.lvl[1].h >= 8) ? 2 : 1;
+    const size_t slots = (size_t)b->max_refs + b->max_pairs, P = b->max_pairs, p0 = B.lvl[0].plane;
+    int rc = CE_OK;
+    for (int l = 0; l < B.levels && rc == CE_OK; l++) {
+        rc = B.psy[l].alloc(ctx, slots * PSY * B.lvl[l].plane);
+        if (l == 1 && rc == CE_OK) rc = B.diff[l].alloc(ctx, P * B.lvl[l].plane);  // the full-resolution diffmap: map, on request
     }
-    for (auto &p : b->ba_s) CE_HIP(ctx, hipMalloc(&p, slots * 3 * p0 * sizeof(float)));
+    for (auto &p : B.s)
+        if (rc == CE_OK) rc = p.alloc(ctx, slots * 3 * p0);
     // blurred mask input per image slot and level, the references' two mask-value planes per level (both persist like the
     // PsychoImage)
-    for (int l = 0; l < b->ba_levels; l++) {
-        CE_HIP(ctx, hipMalloc(&b->ba_mask[l], slots * b->ba[l].plane * sizeof(float)));
-        CE_HIP(ctx, hipMalloc(&b->ba_mask_vals[l], (size_t)b->max_refs * 2 * b->ba[l].plane * sizeof(float)));
+    for (int l = 0; l < B.levels && rc == CE_OK; l++) {
+        rc = B.mask[l].alloc(ctx, slots * B.lvl[l].plane);
+        if (rc == CE_OK) rc = B.mask_vals[l].alloc(ctx, (size_t)b->max_refs * 2 * B.lvl[l].plane);
     }
-    b->ba_blocks = ((b->ba[0].w + 63) / 64) * ((b->ba[0].h + 3) / 4);
-    CE_HIP(ctx, hipMalloc(&b->ba_blk_max, P * b->ba_blocks * sizeof(float)));
-    CE_HIP(ctx, hipMalloc(&b->ba_blk_sums, P * b->ba_blocks * 3 * sizeof(double)));
-    CE_HIP(ctx, hipMalloc(&b->ba_pnorm, P * sizeof(double)));
-    return CE_OK;
-}
-
-static int ba_prepare(ce_batch *b)
-{
-    if (b->ba_ready) return CE_OK;
-    const int rc = ba_allocate(b);
-    if (rc != CE_OK) {  // all or nothing (see ce_ssim2_prepare)
-        const std::string why = b->ctx->err;
-        ce_butteraugli_free(b);
-        (void)hipGetLastError();
-        b->ctx->err = why;
-        return rc;
-    }
-    b->ba_ready = true;
+    B.blocks = ((B.lvl[0].w + 63) / 64) * ((B.lvl[0].h + 3) / 4);
+    if (rc == CE_OK) rc = B.blk_max.alloc(ctx, P * B.blocks);
+    if (rc == CE_OK) rc = B.blk_sums.alloc(ctx, P * B.blocks * 3);
+    if (rc == CE_OK) rc = B.pnorm.alloc(ctx, P);
+    if (rc != CE_OK) return rc;  // all or nothing: B releases what it got
+    b->ba = std::move(B);
     return CE_OK;
 }
 
@@ -1364,10 +1317,8 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
     int rc = ba_prepare(b);
     if (rc != CE_OK) return rc;
     // CE_FLAG_BUTTERAUGLI_DIFFMAP: the full-resolution diffmaps of all pairs, allocated by the first launch that asks for
-    // them (one allocation: there is nothing to undo if it fails) and kept until the working set is freed
-    if (store_map && !b->ba_map && hipMalloc(&b->ba_map, (size_t)b->max_pairs * b->ba[0].plane * sizeof(float)) != hipSuccess) {
-        b->ba_map = nullptr;
-        (void)hipGetLastError();
+    // them (one allocation: there is nothing to undo if it fails) and kept with the working set
+    if (store_map && !b->ba.map && b->ba.map.alloc((ce_ctx *)nullptr, (size_t)b->max_pairs * b->ba.lvl[0].plane) != CE_OK) {
         ctx->err = "out of device memory for the Butteraugli diffmaps";
         return CE_ERR_BACKEND;
     }
@@ -1395,19 +1346,21 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
     // resolution levels are independent until the full-resolution Malta kernel, so the half-resolution chain runs on a stream
     // of its own (with its own scratch planes) beside the full-resolution one: two cross-stream events instead of seven
     // launches on the critical path (profiles/r03_experiments.md section 14).
-    const bool two_streams = b->ba_levels == 2 && !ctx->prof_serial && (double)n_pairs * b->w * b->h <= 4e6;
+    const bool two_streams = b->ba.levels == 2 && !ctx->prof_serial && (double)n_pairs * b->w * b->h <= 4e6;
     hipStream_t s_main = CE_STREAM(ctx), s_half = s_main;
     if (two_streams) {
-        if (!b->ba_half_stream) {
-            if (!(b->ba_half_stream = ce_ctx_aux_stream(ctx, ce_ctx::AUX_BA_HALF))) return CE_ERR_BACKEND;
-            CE_HIP(ctx, hipEventCreateWithFlags(&b->ev_ba_fork, hipEventDisableTiming));
-            CE_HIP(ctx, hipEventCreateWithFlags(&b->ev_ba_join, hipEventDisableTiming));
+        if (!b->ba.half.stream) {  // whole or not at all: a failure leaves no stream behind for the next launch to trust
+            ce_ba_half half;
+            if (!(half.stream = ce_ctx_aux_stream(ctx, ce_ctx::AUX_BA_HALF))) return CE_ERR_BACKEND;
+            if ((rc = half.ev_fork.create(ctx)) != CE_OK || (rc = half.ev_join.create(ctx)) != CE_OK) return rc;
             const size_t slots = (size_t)b->max_refs + b->max_pairs;
-            for (auto &p : b->ba_s_half) CE_HIP(ctx, hipMalloc(&p, slots * 3 * b->ba[1].plane * sizeof(float)));
+            for (auto &p : half.s)
+                if ((rc = p.alloc(ctx, slots * 3 * b->ba.lvl[1].plane)) != CE_OK) return rc;
+            b->ba.half = std::move(half);
         }
-        s_half = b->ba_half_stream;
-        CE_HIP(ctx, hipEventRecord(b->ev_ba_fork, s_main));
-        CE_HIP(ctx, hipStreamWaitEvent(s_half, b->ev_ba_fork, 0));
+        s_half = b->ba.half.stream;
+        CE_HIP(ctx, hipEventRecord(b->ba.half.ev_fork, s_main));
+        CE_HIP(ctx, hipStreamWaitEvent(s_half, b->ba.half.ev_fork, 0));
     }
     // The per-slot kernels' launch order (ba_slot_order.h).  A/B knobs: CE_BA_SLOT_ORDER_MIN = slots per launch from which a
     // slot's tiles stay on one XCD, CE_BA_SLOT_ORDER_KERNELS = the kernels that follow it (bits: 1 front, 2 h33, 4 v_lf,
@@ -1421,14 +1374,13 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
         return e ? (uint32_t)std::atol(e) : 63u;
     }();
     uint32_t final_tiles = 0;
-    for (int l = b->ba_levels - 1; l >= 0; l--) {
-        const auto &d = b->ba[l];
-        const geom g{d.w, d.h, d.pitch, d.plane};
+    for (int l = b->ba.levels - 1; l >= 0; l--) {
+        const ce_plane_geom &d = b->ba.lvl[l], &g = d;
         const dim3 gx((d.w + 63) / 64, (d.h + 3) / 4, 1);
         auto G = [&](uint32_t z) { return dim3(gx.x, gx.y, z); };
         hipStream_t st = l == 1 ? s_half : s_main;
-        float *const *scr = (two_streams && l == 1) ? b->ba_s_half : b->ba_s;
-        float *psy = b->ba_psy[l], *sA = scr[0], *sC = scr[2];
+        const ce_dev<float> *scr = (two_streams && l == 1) ? b->ba.half.s : b->ba.s;
+        float *psy = b->ba.psy[l], *sA = scr[0], *sC = scr[2];
         // ---- per image slot: PsychoImage ----
         const plane_sel s3{3, 0, 3};
         // the launch order (ba_slot_order.h): a slot's tiles on one XCD when the launch has enough slots
@@ -1448,8 +1400,7 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
                 return CE_ERR_BACKEND;
             }
         const dim3 ft = SB(sg_front);
-        const auto &pd = b->ba[0];
-        const geom gfull{pd.w, pd.h, pd.pitch, pd.plane};
+        const ce_plane_geom &gfull = b->ba.lvl[0];
         if (b->linear) {  // a linear batch: f32 samples, no table
             const float *none = nullptr;
             if (l == 0)
@@ -1497,7 +1448,7 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
                          (const float *)nullptr, psy, g, kUhf, inv_weight_sum(kUhf), n_refs_used, mr, sg_hf, sB, (float *)nullptr);
         }
 
-        // mask input: DiffPrecompute of HF + UHF (written by the HF split's epilogue into ba_s[1]), blurred with sigma 2.7 -
+        // mask input: DiffPrecompute of HF + UHF (written by the HF split's epilogue into scratch plane 1), blurred with sigma 2.7 -
         // per image slot (the references' once per reference; kept with the PsychoImage between launches), into
         // the level's own per-slot planes; then the
         // references' mask values (FuzzyErosion + the two mask curves), also once per reference
@@ -1507,10 +1458,10 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
                 return CE_ERR_BACKEND;
             }
             CE_LAUNCH_ON(ctx, st, "ba_blur_hv_mask", (k_ba_blur_v_split<13, EPI_MASK, true, 32>), SB(sg_mask), dim3(TPB), 0, (const float *)scr[1],
-                      (const float *)nullptr, psy, g, kMask, inv_weight_sum(kMask), n_refs_used, mr, sg_mask, (float *)nullptr, b->ba_mask[l]);
+                      (const float *)nullptr, psy, g, kMask, inv_weight_sum(kMask), n_refs_used, mr, sg_mask, (float *)nullptr, b->ba.mask[l]);
         }
         if (!cached)
-            CE_LAUNCH_ON(ctx, st, "ba_mask_vals", k_ba_mask_vals, G(n_refs_used), dim3(TPB), 0, (const float *)b->ba_mask[l], b->ba_mask_vals[l], g);
+            CE_LAUNCH_ON(ctx, st, "ba_mask_vals", k_ba_mask_vals, G(n_refs_used), dim3(TPB), 0, (const float *)b->ba.mask[l], b->ba.mask_vals[l], g);
 
         // ---- per pair: Malta + L2 terms + CombineChannelsToDiffmap -> the level's diffmap ----
         // 32-row tiles, 256 threads: the 64-row / 512-thread tile was slower (profiles/r02_experiments.md section 6,
@@ -1519,31 +1470,30 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
         mb.p[0][0] = mUhfX; mb.p[0][1] = mHfX; mb.p[0][2] = mMfX;
         mb.p[1][0] = mUhfY; mb.p[1][1] = mHfY; mb.p[1][2] = mMfY;
         const uint32_t tiles_x = (d.w + MT - 1) / MT, tiles_y = (d.h + 31) / 32;
-        if ((rc = ce_build_xcd_list(b, n_pairs, ce_xcd_keys{1, tiles_x * tiles_y, 1}, &b->ba_work[l])) != CE_OK) return rc;
-        const bool has_sub = b->ba_levels == 2;
-        const auto &ds = b->ba[has_sub ? 1 : 0];
-        const geom gsub{ds.w, ds.h, ds.pitch, ds.plane};
+        if ((rc = ce_build_xcd_list(b, n_pairs, ce_xcd_keys{1, tiles_x * tiles_y, 1}, &b->ba.work[l])) != CE_OK) return rc;
+        const bool has_sub = b->ba.levels == 2;
+        const ce_plane_geom &gsub = b->ba.lvl[has_sub ? 1 : 0];
 #define CE_MALTA_ARGS(FINAL, STORE)                                                                                                \
-    psy, b->d_pair_ref, (const float *)b->ba_mask[l], (const float *)b->ba_mask_vals[l],                                               \
-        STORE ? b->ba_map : FINAL ? (float *)nullptr : b->ba_diff[1], g, mr, mb, (const uint2 *)b->ba_work[l].d, tiles_x,             \
-        FINAL ? (const float *)b->ba_diff[1] : (const float *)nullptr, gsub, has_sub ? 1 : 0, b->ba_blk_max, b->ba_blk_sums, b->ba_blocks
-        const dim3 gmalta(b->ba_work[l].len);
+    psy, b->d_pair_ref, (const float *)b->ba.mask[l], (const float *)b->ba.mask_vals[l],                                               \
+        STORE ? b->ba.map : FINAL ? (float *)nullptr : b->ba.diff[1], g, mr, mb, (const uint2 *)b->ba.work[l].d, tiles_x,             \
+        FINAL ? (const float *)b->ba.diff[1] : (const float *)nullptr, gsub, has_sub ? 1 : 0, b->ba.blk_max, b->ba.blk_sums, b->ba.blocks
+        const dim3 gmalta(b->ba.work[l].len);
         if (l == 0) {
             final_tiles = tiles_x * tiles_y;
-            if (two_streams) CE_HIP(ctx, hipStreamWaitEvent(s_main, b->ev_ba_join, 0));  // the half-resolution diffmap
+            if (two_streams) CE_HIP(ctx, hipStreamWaitEvent(s_main, b->ba.half.ev_join, 0));  // the half-resolution diffmap
             if (store_map)  // the same kernel, also writing the diffmap: a profiler name of its own
                 CE_LAUNCH_ON(ctx, st, "ba_malta_l2_map", (k_ba_malta_l2_xy<32, 256, true, true>), gmalta, dim3(256), 0, CE_MALTA_ARGS(true, true));
             else
                 CE_LAUNCH_ON(ctx, st, "ba_malta_l2", (k_ba_malta_l2_xy<32, 256, true, false>), gmalta, dim3(256), 0, CE_MALTA_ARGS(true, false));
         } else {
             CE_LAUNCH_ON(ctx, st, "ba_malta_l2", (k_ba_malta_l2_xy<32, 256, false, false>), gmalta, dim3(256), 0, CE_MALTA_ARGS(false, false));
-            if (two_streams) CE_HIP(ctx, hipEventRecord(b->ev_ba_join, s_half));
+            if (two_streams) CE_HIP(ctx, hipEventRecord(b->ba.half.ev_join, s_half));
         }
 #undef CE_MALTA_ARGS
     }
-    const auto &d0 = b->ba[0];
-    CE_LAUNCH(ctx, "ba_score", k_ba_score, dim3(n_pairs), dim3(TPB), 0, b->ba_blk_max, b->ba_blk_sums, b->d_scores, b->ba_pnorm,
-              b->ba_blocks, final_tiles, (double)d0.w * (double)d0.h);
+    const auto &d0 = b->ba.lvl[0];
+    CE_LAUNCH(ctx, "ba_score", k_ba_score, dim3(n_pairs), dim3(TPB), 0, b->ba.blk_max, b->ba.blk_sums, b->d_scores, b->ba.pnorm,
+              b->ba.blocks, final_tiles, (double)d0.w * (double)d0.h);
     CE_HIP(ctx, hipGetLastError());
     if (!cached) b->refs.built(CE_REF_BUTTERAUGLI, d_refs, n_refs_used, ce_ref_param_f32(intensity_target));
     return CE_OK;
@@ -1553,7 +1503,5 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
 // count * ceil(h / B) * ceil(w / B) floats); the caller has checked the range and B.  maps.hip: ce_read_map_cells.
 int ce_butteraugli_read_maps(ce_batch *b, uint32_t first, uint32_t count, uint32_t block, float *out)
 {
-    const auto &d = b->ba[0];
-    return ce_read_map_cells(b, "ba_block_max", b->ba_map, ce_map_geom{d.w, d.h, d.pitch, d.plane}, first, count, block, false,
-                             &b->ba_cells, &b->ba_cells_cap, out);
+    return ce_read_map_cells(b, "ba_block_max", b->ba.map, b->ba.lvl[0], first, count, block, false, b->ba.cells, out);
 }

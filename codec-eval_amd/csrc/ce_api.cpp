@@ -93,9 +93,9 @@ int ce_batch_dssim_ssim_maps(ce_batch *b, uint32_t level, uint32_t first, uint32
     if (!b || (!maps && !ssim)) return CE_ERR_INVALID_ARG;
     ce_ctx *ctx = b->ctx;
     if (b->ds_map_pairs == 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, "no DSSIM SSIM maps: the last launch did not run DSSIM");
-    if (level >= (uint32_t)b->ds_levels)
-        return ce_fail(ctx, CE_ERR_INVALID_ARG, "DSSIM level " + std::to_string(level) + " of " + std::to_string(b->ds_levels));
-    const auto &d = b->ds[level];
+    if (level >= (uint32_t)b->ds.levels)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "DSSIM level " + std::to_string(level) + " of " + std::to_string(b->ds.levels));
+    const auto &d = b->ds.lvl[level];
     if (int rc = check_map_readout(ctx, "SSIM map", b->ds_map_pairs, first, count, block, d.w, d.h, maps != nullptr, maps_floats)) return rc;
     CE_HIP(ctx, hipSetDevice(ctx->device));
     return ce_dssim_read_maps(b, level, first, count, block, maps, ssim);
@@ -118,7 +118,7 @@ int ce_batch_ssimulacra2_maps(ce_batch *b, uint32_t scale, uint32_t channel, uin
         return ce_fail(ctx, CE_ERR_INVALID_ARG, "SSIMULACRA2 scale " + std::to_string(scale) + " of " + std::to_string(b->s2_scales_run) + " that ran");
     if (channel >= 3) return ce_fail(ctx, CE_ERR_INVALID_ARG, "SSIMULACRA2 channel " + std::to_string(channel) + " of 3");
     if (kind >= 3) return ce_fail(ctx, CE_ERR_INVALID_ARG, "SSIMULACRA2 map kind " + std::to_string(kind) + " of 3");
-    const ce_scale_dims &d = b->sd[scale];
+    const ce_plane_geom &d = b->s2.lvl[scale];
     if (int rc = check_map_readout(ctx, "SSIMULACRA2 map", maps ? b->s2_map_pairs : b->s2_norm_pairs, first, count, block, d.w, d.h,
                                    maps != nullptr, maps_floats))
         return rc;
@@ -209,25 +209,13 @@ int ce_build_xcd_list(ce_batch *b, uint32_t n_pairs, const ce_xcd_keys &keys, ce
     if (L->d && L->version == b->pair_ref_version && L->pairs == n_pairs && L->keys == keys) return CE_OK;
     ce_ctx *ctx = b->ctx;
     const std::vector<ce_plan_entry> flat = ce_plan_xcd_list(b->h_pair_ref.data(), n_pairs, b->max_refs, keys);
-    if (flat.size() > L->cap) {
-        if (L->d) CE_HIP(ctx, hipFree(L->d));
-        L->d = nullptr;
-        L->cap = 0;
-        CE_HIP(ctx, hipMalloc(&L->d, flat.size() * sizeof(uint2)));
-        L->cap = (uint32_t)flat.size();
-    }
+    if (int rc = L->d.reserve(ctx, flat.size())) return rc;
     if (int rc = ce_upload_table(b, L->d, flat.data(), flat.size() * sizeof(uint2))) return rc;  // `flat` is pageable and goes out of scope
     L->len = (uint32_t)flat.size();
     L->version = b->pair_ref_version;
     L->pairs = n_pairs;
     L->keys = keys;
     return CE_OK;
-}
-
-void ce_free_xcd_list(ce_xcd_list *L)
-{
-    hipFree(L->d);
-    *L = ce_xcd_list{};
 }
 
 thread_local hipStream_t ce_tls_stream = nullptr;  // ce_internal.h: CE_STREAM
@@ -504,31 +492,26 @@ static int batch_create(ce_ctx *ctx, uint32_t width, uint32_t height, uint32_t m
     // CE_KEEP_REFERENCE_STATE=0: an ordinary batch rebuilds its reference-side planes on every launch, for A/B runs
     static const bool keep_reference_state = [] { const char *e = std::getenv("CE_KEEP_REFERENCE_STATE"); return !(e && e[0] == '0'); }();
     b->refs.keep = keep_reference_state;
-    int rc = CE_OK;
-    auto chk = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && rc == CE_OK) {
-            ctx->err = std::string(what) + ": " + hipGetErrorString(e);
-            rc = CE_ERR_BACKEND;
-        }
-    };
     // +16 bytes: the PSNR kernel reads whole 16-byte words
-    chk(hipMalloc(&b->d_refs, b->img_bytes * max_refs + 16), "hipMalloc refs");
-    chk(hipMalloc(&b->d_tests, b->img_bytes * max_pairs + 16), "hipMalloc tests");
+    int rc = b->d_refs.alloc(ctx, b->img_bytes * max_refs + 16, "hipMalloc refs");
+    if (rc == CE_OK) rc = b->d_tests.alloc(ctx, b->img_bytes * max_pairs + 16, "hipMalloc tests");
     // [pair_ref (P) | pair_first (P) | ref_off (R + 1) | ref_idx (P)]
-    chk(hipMalloc(&b->d_pair_ref, sizeof(uint32_t) * (3 * (size_t)max_pairs + max_refs + 1)), "hipMalloc pair_ref");
-    b->d_pair_first = b->d_pair_ref ? b->d_pair_ref + max_pairs : nullptr;
-    b->d_ref_off = b->d_pair_ref ? b->d_pair_ref + 2 * (size_t)max_pairs : nullptr;
-    b->d_ref_idx = b->d_pair_ref ? b->d_ref_off + max_refs + 1 : nullptr;
-    chk(hipMalloc(&b->d_scores, sizeof(ce_dev_scores) * max_pairs), "hipMalloc scores");
-    chk(hipHostMalloc(&b->h_scores, sizeof(ce_dev_scores) * max_pairs, hipHostMallocDefault), "hipHostMalloc scores");
-    chk(hipStreamCreateWithFlags(&b->up_stream, hipStreamNonBlocking), "hipStreamCreate upload");
-    chk(hipEventCreateWithFlags(&b->ev_up, hipEventDisableTiming), "hipEventCreate");
-    chk(hipEventCreateWithFlags(&b->ev_run, hipEventDisableTiming), "hipEventCreate");
-    for (int k = 0; k < ce_batch::kStages; k++) {
-        chk(hipHostMalloc(&b->h_stage[k], b->img_bytes, hipHostMallocDefault), "hipHostMalloc stage");
-        chk(hipEventCreateWithFlags(&b->ev_stage[k], hipEventDisableTiming), "hipEventCreate stage");
+    if (rc == CE_OK) rc = b->d_pair_ref.alloc(ctx, 3 * (size_t)max_pairs + max_refs + 1, "hipMalloc pair_ref");
+    if (rc == CE_OK) {
+        b->d_pair_first = b->d_pair_ref + max_pairs;
+        b->d_ref_off = b->d_pair_ref + 2 * (size_t)max_pairs;
+        b->d_ref_idx = b->d_ref_off + max_refs + 1;
+        rc = b->d_scores.alloc(ctx, max_pairs, "hipMalloc scores");
     }
-    if (rc == CE_OK) chk(hipMemsetAsync(b->d_scores, 0, sizeof(ce_dev_scores) * max_pairs, ctx->stream), "memset");
+    if (rc == CE_OK) rc = b->h_scores.alloc(ctx, max_pairs, "hipHostMalloc scores");
+    if (rc == CE_OK) rc = b->up_stream.create(ctx, "hipStreamCreate upload");
+    if (rc == CE_OK) rc = b->ev_up.create(ctx);
+    if (rc == CE_OK) rc = b->ev_run.create(ctx);
+    for (int k = 0; k < ce_batch::kStages && rc == CE_OK; k++) {
+        rc = b->h_stage[k].alloc(ctx, b->img_bytes, "hipHostMalloc stage");
+        if (rc == CE_OK) rc = b->ev_stage[k].create(ctx, "hipEventCreate stage");
+    }
+    if (rc == CE_OK) rc = ce_owned_status(ctx, hipMemsetAsync(b->d_scores, 0, sizeof(ce_dev_scores) * max_pairs, ctx->stream), "memset");
     if (rc != CE_OK) {
         ce_batch_destroy(b);
         return rc;
@@ -564,39 +547,11 @@ void ce_batch_destroy(ce_batch *b)
     hipSetDevice(b->ctx->device);
     hipStreamSynchronize(b->ctx->stream);
     leave_flight(b);
-    if (b->up_stream) hipStreamSynchronize(b->up_stream), hipStreamDestroy(b->up_stream);
-    for (int k = 0; k < 2; k++) {
-        if (b->h_wide[k]) hipHostFree(b->h_wide[k]);
-        hipFree(b->d_wide[k]);
-        if (b->h_side[k]) hipHostFree(b->h_side[k]);
-        hipFree(b->d_side[k]);
-        if (b->ev_wide[k]) hipEventDestroy(b->ev_wide[k]);
-    }
-    if (b->ev_up) hipEventDestroy(b->ev_up);
-    if (b->ev_run) hipEventDestroy(b->ev_run);
-    if (b->ev_fork) hipEventDestroy(b->ev_fork);
-    hipFree(b->d_refs);
-    hipFree(b->d_refs_rt);
-    hipFree(b->d_tests);
-    hipFree(b->d_pair_ref);
-    hipFree(b->d_scores);
-    if (b->h_scores) hipHostFree(b->h_scores);
-    hipFree(b->d_hdr);
-    if (b->h_hdr) hipHostFree(b->h_hdr);
-    hipFree(b->d_itp_map);
-    hipFree(b->d_itp_over);
-    if (b->h_itp_over) hipHostFree(b->h_itp_over);
-    for (int k = 0; k < ce_batch::kStages; k++) {
-        if (b->h_stage[k]) hipHostFree(b->h_stage[k]);
-        if (b->ev_stage[k]) hipEventDestroy(b->ev_stage[k]);
-    }
-    for (int l = 0; l < 3; l++) {
-        if (b->metric_stream[l]) hipStreamSynchronize(b->metric_stream[l]);  // the context's stream: drained, not destroyed
-        if (b->ev_join[l]) hipEventDestroy(b->ev_join[l]);
-    }
-    ce_ssim2_free(b);
-    ce_dssim_free(b);
-    ce_butteraugli_free(b);
+    // what the batch queued elsewhere: its uploads, and the context's auxiliary streams it used (drained, never destroyed
+    // here); then every owner in the batch releases itself
+    if (b->up_stream) hipStreamSynchronize(b->up_stream);
+    for (hipStream_t st : {b->fork[0].stream, b->fork[1].stream, b->fork[2].stream, b->s2.l0_stream, b->ba.half.stream})
+        if (st) hipStreamSynchronize(st);
     delete b;
 }
 
@@ -650,7 +605,8 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
     const uint8_t *d_refs = b->d_refs;
     if (flags & CE_FLAG_XYB_ROUNDTRIP) {
         // MetricConfig::xyb_roundtrip: every metric sees the roundtripped reference (session.rs:447-456)
-        if (!b->d_refs_rt) CE_HIP(ctx, hipMalloc(&b->d_refs_rt, b->img_bytes * b->max_refs + 16));
+        if (!b->d_refs_rt)
+            if (int rc = b->d_refs_rt.alloc(ctx, b->img_bytes * b->max_refs + 16, "hipMalloc roundtripped refs")) return rc;
         if (!b->refs.reuse(CE_REF_ROUNDTRIP, b->d_refs, n_refs_used, 0)) {
             int rc = ce_launch_xyb_roundtrip(ctx, b->d_refs, b->d_refs_rt, (size_t)n_refs_used * b->w * b->h);
             if (rc != CE_OK) return rc;
@@ -703,16 +659,19 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
     const unsigned fork_mask = (!ctx->prof_serial && (int)run_ssim2 + (int)run_dssim + (int)run_ba > 1) ? fork_wanted : 0u;
     hipStream_t base = ctx->stream;
     if (fork_mask) {
-        if (!b->ev_fork) CE_HIP(ctx, hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming));
+        if (!b->ev_fork)
+            if (int rc = b->ev_fork.create(ctx)) return rc;
         CE_HIP(ctx, hipEventRecord(b->ev_fork, base));
     }
     unsigned joined = 0;
     auto prepare_fork = [&](int k) -> int {  // the chain's stream exists and waits for the fork point
-        if (!b->metric_stream[k]) {
-            if (!(b->metric_stream[k] = ce_ctx_aux_stream(ctx, ce_ctx::AUX_METRIC0 + k))) return CE_ERR_BACKEND;
-            CE_HIP(ctx, hipEventCreateWithFlags(&b->ev_join[k], hipEventDisableTiming));
+        if (!b->fork[k].stream) {  // the stream is seen only with its event
+            ce_batch::metric_fork f;
+            if (!(f.stream = ce_ctx_aux_stream(ctx, ce_ctx::AUX_METRIC0 + k))) return CE_ERR_BACKEND;
+            if (int rc = f.ev_join.create(ctx)) return rc;
+            b->fork[k] = std::move(f);
         }
-        CE_HIP(ctx, hipStreamWaitEvent(b->metric_stream[k], b->ev_fork, 0));
+        CE_HIP(ctx, hipStreamWaitEvent(b->fork[k].stream, b->ev_fork, 0));
         return CE_OK;
     };
     auto launch_metric = [&](int k) -> int {
@@ -739,10 +698,10 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
                 last = k;
             }
         auto body = [&](int k) {
-            ce_tls_stream = b->metric_stream[k];
+            ce_tls_stream = b->fork[k].stream;
             rcs[k] = launch_metric(k);
             ce_tls_stream = nullptr;
-            if (rcs[k] == CE_OK && hipEventRecord(b->ev_join[k], b->metric_stream[k]) != hipSuccess) rcs[k] = CE_ERR_BACKEND;
+            if (rcs[k] == CE_OK && hipEventRecord(b->fork[k].ev_join, b->fork[k].stream) != hipSuccess) rcs[k] = CE_ERR_BACKEND;
         };
         if (!ctx->helpers) {
             try {
@@ -776,11 +735,11 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
             }
             int rc = prepare_fork(k);
             if (rc != CE_OK) return rc;
-            ce_tls_stream = b->metric_stream[k];  // the chain's launches go to its own stream
+            ce_tls_stream = b->fork[k].stream;  // the chain's launches go to its own stream
             rc = launch_metric(k);
             ce_tls_stream = nullptr;
             if (rc != CE_OK) return rc;
-            CE_HIP(ctx, hipEventRecord(b->ev_join[k], b->metric_stream[k]));
+            CE_HIP(ctx, hipEventRecord(b->fork[k].ev_join, b->fork[k].stream));
             joined |= 1u << k;  // the context's stream waits for it after every chain has been launched
         }
     }
@@ -789,14 +748,14 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
         if (rc != CE_OK) return rc;
     }
     for (int k = 0; k < 3; k++)
-        if (joined & (1u << k)) CE_HIP(ctx, hipStreamWaitEvent(base, b->ev_join[k], 0));
+        if (joined & (1u << k)) CE_HIP(ctx, hipStreamWaitEvent(base, b->fork[k].ev_join, 0));
     b->last_n_pairs = n_pairs;
     b->last_mask = metric_mask;
     b->ba_map_pairs = store_maps ? n_pairs : 0;
     b->ds_map_pairs = run_dssim ? n_pairs : 0;  // DSSIM writes its SSIM maps on every launch
     b->s2_norm_pairs = run_ssim2 ? n_pairs : 0;  // ... and SSIMULACRA2 its pooled norms (d_avg)
     b->s2_map_pairs = store_ssim2_maps ? n_pairs : 0;
-    b->s2_scales_run = run_ssim2 ? (uint32_t)std::min(b->n_scales, b->debug_max_scales) : 0;
+    b->s2_scales_run = run_ssim2 ? (uint32_t)std::min(b->s2.n_scales, b->debug_max_scales) : 0;
     // the scores come back behind the last kernel of THIS launch and ev_run marks them: ce_batch_collect waits for the event,
     // not for the stream (round 2 copied at collect time and drained the context's stream, so collecting one batch waited
     // for every batch launched after it - in ce_eval_batch the next chunk's upload then started only when the device was idle)
@@ -857,11 +816,11 @@ int ce_batch_collect(ce_batch *b, uint32_t n_pairs, ce_scores *out)
 
 int ce_batch_butteraugli_pnorm3(ce_batch *b, uint32_t n_pairs, double *out)
 {
-    if (!b || !out || !b->ba_ready || n_pairs == 0 || n_pairs > b->max_pairs) return CE_ERR_INVALID_ARG;
+    if (!b || !out || !b->ba.engaged() || n_pairs == 0 || n_pairs > b->max_pairs) return CE_ERR_INVALID_ARG;
     ce_ctx *ctx = b->ctx;
     CE_HIP(ctx, hipSetDevice(ctx->device));
     CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    CE_HIP(ctx, hipMemcpy(out, b->ba_pnorm, sizeof(double) * n_pairs, hipMemcpyDeviceToHost));
+    CE_HIP(ctx, hipMemcpy(out, b->ba.pnorm, sizeof(double) * n_pairs, hipMemcpyDeviceToHost));
     return CE_OK;
 }
 
@@ -962,9 +921,9 @@ static size_t chunk_budget(ce_ctx *ctx)
     size_t pooled = 0;
     for (auto &kv : ctx->shape_pool) {
         const ce_batch *pb = kv.second;
-        const uint32_t held = (pb->ssim2_ready ? CE_METRIC_SSIMULACRA2 : 0u) | (pb->dssim_ready ? CE_METRIC_DSSIM : 0u) |
-                              (pb->ba_ready ? CE_METRIC_BUTTERAUGLI : 0u);
-        pooled += estimate_batch_bytes(pb->w, pb->h, pb->max_refs, pb->max_pairs, held, pb->s2_ref_blur[0] != nullptr);
+        const uint32_t held = (pb->s2.engaged() ? CE_METRIC_SSIMULACRA2 : 0u) | (pb->ds.engaged() ? CE_METRIC_DSSIM : 0u) |
+                              (pb->ba.engaged() ? CE_METRIC_BUTTERAUGLI : 0u);
+        pooled += estimate_batch_bytes(pb->w, pb->h, pb->max_refs, pb->max_pairs, held, pb->s2.ref_blur[0] != nullptr);
     }
     // ... and no chunk asks for more than kChunkBytesMax: on a 288 GB device a third of the free memory is a 70+ GB batch whose
     // hipMalloc calls alone take seconds (measured: 2000 pairs of 512x512, three metrics - first call 3.7 s + 6.5 s for the
@@ -1198,20 +1157,20 @@ int ce_batch_hdr_fidelity(ce_batch *b, uint32_t n_pairs, uint32_t depth, float w
     CE_HIP(ctx, hipSetDevice(ctx->device));
     const float *d_table = nullptr, *d_coarse = nullptr;
     if (int rc = hdr_table_dev(ctx, depth, white_nits, &d_table, &d_coarse)) return rc;
-    if (!b->d_hdr) CE_HIP(ctx, hipMalloc(&b->d_hdr, sizeof(unsigned long long) * 3 * b->max_pairs));
-    if (!b->h_hdr) CE_HIP(ctx, hipHostMalloc(&b->h_hdr, sizeof(unsigned long long) * 3 * b->max_pairs, hipHostMallocDefault));
+    if (!b->hdr)
+        if (int rc = b->hdr.alloc(ctx, (size_t)3 * b->max_pairs)) return rc;
     // on the context's stream, as a launch: behind the uploads queued so far, with the pair table of the last bind
     if (int rc = ce_flush_uploads(b)) return rc;
     if (int rc = sync_pair_ref(b)) return rc;
     float a[9], lms[9];
     ce_build_hdr_fidelity_matrices(a, lms);
-    if (int rc = ce_launch_hdr_fidelity(b, n_pairs, depth, d_table, d_coarse, a, lms, b->d_hdr)) return rc;
-    CE_HIP(ctx, hipMemcpyAsync(b->h_hdr, b->d_hdr, sizeof(unsigned long long) * 3 * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = ce_launch_hdr_fidelity(b, n_pairs, depth, d_table, d_coarse, a, lms, b->hdr.d)) return rc;
+    CE_HIP(ctx, hipMemcpyAsync(b->hdr.h, b->hdr.d, sizeof(unsigned long long) * 3 * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
     CE_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the slabs are free again: a later upload needs no fence against this
     const double maxv = (double)((1u << depth) - 1u), n_px = (double)((size_t)b->w * b->h);
     for (uint32_t i = 0; i < n_pairs; i++) {
         ce_hdr_scores s{};
-        s.pq_sse = b->h_hdr[3 * i], s.itp_sum_q20 = b->h_hdr[3 * i + 1], s.itp_max_q20 = b->h_hdr[3 * i + 2];
+        s.pq_sse = b->hdr.h[3 * i], s.itp_sum_q20 = b->hdr.h[3 * i + 1], s.itp_max_q20 = b->hdr.h[3 * i + 2];
         s.pq_psnr = psnr_from_sse(s.pq_sse, b->w, b->h, maxv);
         s.delta_e_itp_mean = (double)s.itp_sum_q20 / 1048576.0 / n_px;
         s.delta_e_itp_max = (double)s.itp_max_q20 / 1048576.0;
@@ -1243,28 +1202,24 @@ int ce_batch_delta_e_itp_map(ce_batch *b, uint32_t first, uint32_t count, uint32
     CE_HIP(ctx, hipSetDevice(ctx->device));
     const float *d_table = nullptr, *d_coarse = nullptr;
     if (int rc = hdr_table_dev(ctx, depth, white_nits, &d_table, &d_coarse)) return rc;
-    if (map && b->itp_map_cap < map_len) {
-        hipFree(b->d_itp_map);
-        b->d_itp_map = nullptr, b->itp_map_cap = 0;
-        CE_HIP(ctx, hipMalloc(&b->d_itp_map, map_len * sizeof(uint32_t)));
-        b->itp_map_cap = map_len;
-    }
+    if (map)
+        if (int rc = b->d_itp_map.reserve(ctx, map_len)) return rc;
     const size_t over_bytes = sizeof(unsigned long long) * CE_DELTA_E_ITP_MAX_THRESHOLDS;  // per pair
-    if (over && !b->d_itp_over) CE_HIP(ctx, hipMalloc(&b->d_itp_over, over_bytes * b->max_pairs));
-    if (over && !b->h_itp_over) CE_HIP(ctx, hipHostMalloc(&b->h_itp_over, over_bytes * b->max_pairs, hipHostMallocDefault));
+    if (over && !b->itp_over)
+        if (int rc = b->itp_over.alloc(ctx, (size_t)CE_DELTA_E_ITP_MAX_THRESHOLDS * b->max_pairs)) return rc;
     // on the context's stream, as a launch: behind the uploads queued so far, with the pair table of the last bind
     if (int rc = ce_flush_uploads(b)) return rc;
     if (int rc = sync_pair_ref(b)) return rc;
     float a[9], lms[9];
     ce_build_hdr_fidelity_matrices(a, lms);
-    if (int rc = ce_launch_delta_e_itp_map(b, first, count, depth, d_table, d_coarse, a, lms, block, map ? b->d_itp_map : nullptr, thresholds_q20,
-                                           n_thresholds, over ? b->d_itp_over : nullptr))
+    if (int rc = ce_launch_delta_e_itp_map(b, first, count, depth, d_table, d_coarse, a, lms, block, map ? b->d_itp_map.get() : nullptr, thresholds_q20,
+                                           n_thresholds, over ? b->itp_over.d.get() : nullptr))
         return rc;
     if (map) CE_HIP(ctx, hipMemcpyAsync(map, b->d_itp_map, map_len * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (over) CE_HIP(ctx, hipMemcpyAsync(b->h_itp_over, b->d_itp_over, over_bytes * count, hipMemcpyDeviceToHost, ctx->stream));
+    if (over) CE_HIP(ctx, hipMemcpyAsync(b->itp_over.h, b->itp_over.d, over_bytes * count, hipMemcpyDeviceToHost, ctx->stream));
     CE_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the slabs are free again: a later upload needs no fence against this
     for (uint32_t i = 0; over && i < count; i++)
-        for (uint32_t j = 0; j < n_thresholds; j++) over[(size_t)i * n_thresholds + j] = b->h_itp_over[(size_t)i * CE_DELTA_E_ITP_MAX_THRESHOLDS + j];
+        for (uint32_t j = 0; j < n_thresholds; j++) over[(size_t)i * n_thresholds + j] = b->itp_over.h[(size_t)i * CE_DELTA_E_ITP_MAX_THRESHOLDS + j];
     return CE_OK;
 }
 
@@ -1487,9 +1442,9 @@ int ce_timer_stop(ce_ctx *ctx, double *elapsed_ms)
 int ce_debug_ssim2_planes(ce_batch *b, int scale, int which, int channel, float *out, size_t out_floats,
                           uint32_t *w_out, uint32_t *h_out)
 {
-    if (!b || !out || !b->ssim2_ready || scale < 0 || scale >= b->n_scales) return CE_ERR_INVALID_ARG;
+    if (!b || !out || !b->s2.engaged() || scale < 0 || scale >= b->s2.n_scales) return CE_ERR_INVALID_ARG;
     ce_ctx *ctx = b->ctx;
-    const ce_scale_dims &d = b->sd[scale];
+    const ce_plane_geom &d = b->s2.lvl[scale];
     const int nplanes = which == 4 ? CE_SSIM2_STREAMS : 3;
     if (out_floats < (size_t)nplanes * d.w * d.h) return CE_ERR_INVALID_ARG;
     const uint32_t ref_slot = b->h_pair_ref[0], test_slot = b->max_refs;
@@ -1498,24 +1453,23 @@ int ce_debug_ssim2_planes(ce_batch *b, int scale, int which, int channel, float 
         case 0:
         case 1:
             if (scale == 0) return CE_ERR_INVALID_ARG;  // level 0 has no linear plane (read from u8 on the fly)
-            src = b->d_lin[scale] + (size_t)(which == 0 ? ref_slot : test_slot) * 3 * d.plane;
+            src = b->s2.lin[scale] + (size_t)(which == 0 ? ref_slot : test_slot) * 3 * d.plane;
             break;
-        case 2: src = b->d_xyb[scale] + (size_t)ref_slot * 3 * d.plane; break;
-        case 3: src = b->d_xyb[scale] + (size_t)test_slot * 3 * d.plane; break;
+        case 2: src = b->s2.xyb[scale] + (size_t)ref_slot * 3 * d.plane; break;
+        case 3: src = b->s2.xyb[scale] + (size_t)test_slot * 3 * d.plane; break;
         case 4:
             if (channel < 0 || channel > 2) return CE_ERR_INVALID_ARG;
-            src = b->d_hbuf[scale] + (size_t)channel * CE_SSIM2_STREAMS * d.hplane;
+            src = b->s2.hbuf[scale] + (size_t)channel * CE_SSIM2_STREAMS * d.plane;
             // after a split-path launch the row-blurred a, a*a exist nowhere (they were scratch of the build)
-            if (b->s2_split_last) return ce_fail(ctx, CE_ERR_INVALID_ARG, "the last launch took SSIMULACRA2's split path: it leaves no row-blurred reference streams to read");
+            if (b->s2.split_last) return ce_fail(ctx, CE_ERR_INVALID_ARG, "the last launch took SSIMULACRA2's split path: it leaves no row-blurred reference streams to read");
             break;
         default: return CE_ERR_INVALID_ARG;
     }
     CE_HIP(ctx, hipSetDevice(ctx->device));
     CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const size_t spl = which == 4 ? d.hplane : d.plane, spitch = which == 4 ? d.hpitch : d.pitch;
     for (int p = 0; p < nplanes; p++)
-        CE_HIP(ctx, hipMemcpy2D(out + (size_t)p * d.w * d.h, (size_t)d.w * sizeof(float), src + (size_t)p * spl,
-                                spitch * sizeof(float), (size_t)d.w * sizeof(float), d.h, hipMemcpyDeviceToHost));
+        CE_HIP(ctx, hipMemcpy2D(out + (size_t)p * d.w * d.h, (size_t)d.w * sizeof(float), src + (size_t)p * d.plane,
+                                d.pitch * sizeof(float), (size_t)d.w * sizeof(float), d.h, hipMemcpyDeviceToHost));
     if (w_out) *w_out = d.w;
     if (h_out) *h_out = d.h;
     return CE_OK;
@@ -1530,7 +1484,7 @@ int ce_debug_ssim2_limit_scales(ce_batch *b, int max_scales)
 
 int ce_debug_dssim_walk_rows(ce_batch *b, uint32_t rows)
 {
-    // ds_part holds a strip's partial sums per 2-row tile (dssim.hip: ds_blocks), so every allowed walk fits
+    // ds.part holds a strip's partial sums per 2-row tile (dssim.hip: ce_dssim_set::blocks), so every allowed walk fits
     if (!b || (rows != 0 && (rows < 2 || rows > 64 || (rows & (rows - 1)) != 0))) return CE_ERR_INVALID_ARG;
     b->debug_ds_rows = rows;
     b->refs.of[CE_REF_DSSIM].invalidate();  // the references' planes are walked at the new length too
@@ -1539,13 +1493,13 @@ int ce_debug_dssim_walk_rows(ce_batch *b, uint32_t rows)
 
 int ce_debug_ssim2_averages(ce_batch *b, uint32_t pair_index, double *avg, int *n_scales)
 {
-    if (!b || !avg || !b->ssim2_ready || pair_index >= b->max_pairs) return CE_ERR_INVALID_ARG;
+    if (!b || !avg || !b->s2.engaged() || pair_index >= b->max_pairs) return CE_ERR_INVALID_ARG;
     ce_ctx *ctx = b->ctx;
     CE_HIP(ctx, hipSetDevice(ctx->device));
     CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    CE_HIP(ctx, hipMemcpy(avg, b->d_avg + (size_t)pair_index * CE_MAX_SCALES * 18, sizeof(double) * CE_MAX_SCALES * 18,
+    CE_HIP(ctx, hipMemcpy(avg, b->s2.avg + (size_t)pair_index * CE_MAX_SCALES * 18, sizeof(double) * CE_MAX_SCALES * 18,
                           hipMemcpyDeviceToHost));
-    if (n_scales) *n_scales = b->n_scales;
+    if (n_scales) *n_scales = b->s2.n_scales;
     return CE_OK;
 }
 

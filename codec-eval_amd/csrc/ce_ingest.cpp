@@ -217,22 +217,18 @@ int wide_send(ce_batch *b, size_t bytes, Fill fill, Launch launch)
     CE_HIP(ctx, hipSetDevice(ctx->device));  // the staging allocations and the launch go to the context's device
     const int k = b->next_wide;
     b->next_wide ^= 1;
-    if (!b->ev_wide[k]) CE_HIP(ctx, hipEventCreateWithFlags(&b->ev_wide[k], hipEventDisableTiming));
+    if (!b->ev_wide[k])
+        if (int rc = b->ev_wide[k].create(ctx)) return rc;
     if (int rc = ce_order_write(b, false)) return rc;
     if (b->wide_busy[k]) CE_HIP(ctx, hipEventSynchronize(b->ev_wide[k]));  // this staging pair's previous image has been converted
     b->wide_busy[k] = false;
-    if (!b->h_wide[k] || bytes > b->wide_cap[k]) {
+    if (!b->wide[k] || b->wide[k].h.size() < bytes) {
         // A tensor image takes up to 16 bytes per pixel in any batch (f32 RGBA; planar f32: 12): the pair grows for the call
         // that needs more, behind its event, so every other workload keeps the memory it had.
-        const size_t cap = std::max((size_t)b->w * b->h * (b->linear ? 16 : 8), bytes);
-        if (b->h_wide[k]) CE_HIP(ctx, hipHostFree(b->h_wide[k]));
-        if (b->d_wide[k]) CE_HIP(ctx, hipFree(b->d_wide[k]));
-        b->h_wide[k] = b->d_wide[k] = nullptr, b->wide_cap[k] = 0;
-        CE_HIP(ctx, hipHostMalloc((void **)&b->h_wide[k], cap, hipHostMallocDefault));
-        CE_HIP(ctx, hipMalloc((void **)&b->d_wide[k], cap));
-        b->wide_cap[k] = cap;
+        b->wide[k].reset();
+        if (int rc = b->wide[k].alloc(ctx, std::max((size_t)b->w * b->h * (b->linear ? 16 : 8), bytes))) return rc;
     }
-    const wide_pair pair{b->h_wide[k], b->d_wide[k], k};
+    const wide_pair pair{b->wide[k].h, b->wide[k].d, k};
     if (int rc = fill(pair)) return rc;
     CE_HIP(ctx, hipMemcpyAsync(pair.d, pair.h, bytes, hipMemcpyHostToDevice, b->up_stream));
     if (int rc = launch(pair)) return rc;
@@ -587,18 +583,15 @@ int upload_gainmap(ce_batch *b, uint8_t *dst, const void *pixels, size_t len, in
     return wide_send(
         b, len,
         [&](const wide_pair &p) -> int {
-            if (!b->h_side[p.k]) {
-                const size_t cap = 3 * 256 * sizeof(double) + (size_t)b->w * b->h * 3;
-                CE_HIP(ctx, hipHostMalloc((void **)&b->h_side[p.k], cap, hipHostMallocDefault));
-                CE_HIP(ctx, hipMalloc((void **)&b->d_side[p.k], cap));
-            }
+            if (!b->side[p.k])
+                if (int rc = b->side[p.k].alloc(ctx, 3 * 256 * sizeof(double) + (size_t)b->w * b->h * 3)) return rc;
             std::memcpy(p.h, pixels, len);
-            side = gainmap_side(plan, map, b->h_side[p.k]);
+            side = gainmap_side(plan, map, b->side[p.k].h);
             return CE_OK;
         },
         [&](const wide_pair &p) -> int {
-            CE_HIP(ctx, hipMemcpyAsync(b->d_side[p.k], b->h_side[p.k], side, hipMemcpyHostToDevice, b->up_stream));
-            return ce_launch_gainmap(ctx, b->up_stream, format, p.d, b->d_side[p.k], reinterpret_cast<float *>(dst), b->w, b->h, plan);
+            CE_HIP(ctx, hipMemcpyAsync(b->side[p.k].d, b->side[p.k].h, side, hipMemcpyHostToDevice, b->up_stream));
+            return ce_launch_gainmap(ctx, b->up_stream, format, p.d, b->side[p.k].d, reinterpret_cast<float *>(dst), b->w, b->h, plan);
         });
 }
 

@@ -18,6 +18,7 @@
 #include "ce_metrics_debug.h"
 #include "ce_plan.h"
 #include "ce_ref_state.h"
+#include "ce_owned.h"
 
 #define CE_MAX_SCALES 6      // SSIMULACRA2 pyramid depth
 #define CE_SSIM2_STREAMS 5   // blur(a), blur(b), blur(a*a), blur(b*b), blur(a*b)
@@ -27,13 +28,6 @@
 // is the linear value, no table)
 enum { CE_SRC_F32 = 0, CE_SRC_U8 = 1, CE_SRC_U16 = 2, CE_SRC_LIN = 3 };
 static_assert(CE_MAX_SCALES == CE_SSIM2_MAX_SCALES, "the ABI's scale count is the pyramid's");
-
-struct ce_scale_dims {
-    uint32_t w, h, pitch;  // pitch in floats, multiple of 32 (128-byte rows)
-    size_t plane;          // pitch * h
-    uint32_t hpitch;       // row-blur planes: pitch padded to 32 * ceil((w + 4) / 32) floats,
-    size_t hplane;         //   rows padded to a multiple of 64 (branch-free row stores)
-};
 
 // per-pair device results; PSNR leaves the device as the exact integer SSE and is
 // finished on the host with the host libm (bit-identical to the reference's f64 log10).
@@ -153,11 +147,108 @@ struct ce_ctx {
 };
 
 // XCD-aware 1-D launch order of a per-pair tile kernel on the device (ce_plan.h, ce_build_xcd_list in ce_api.cpp):
-// entry = (tile, pair), with the inputs it was built from
+// entry = (tile, pair), with the inputs it was built from; the device list is grow-only
 struct ce_xcd_list {
-    uint2 *d = nullptr;
-    uint32_t len = 0, cap = 0, version = ~0u, pairs = 0;
+    ce_dev<uint2> d;
+    uint32_t len = 0, version = ~0u, pairs = 0;
     ce_xcd_keys keys{};
+};
+
+// a device buffer and the page-locked block it is copied from or into, `n` elements each: made together or not at all
+template <class T>
+struct ce_mirror {
+    ce_dev<T> d;
+    ce_pinned<T> h;
+    int alloc(ce_ctx *ctx, size_t n)
+    {
+        ce_mirror m;
+        if (int rc = m.d.alloc(ctx, n)) return rc;
+        if (int rc = m.h.alloc(ctx, n)) return rc;
+        *this = std::move(m);
+        return CE_OK;
+    }
+    void reset() { d.reset(), h.reset(); }
+    explicit operator bool() const { return d != nullptr; }
+};
+
+// A metric's device working set is a value: its *_prepare builds one in a local and moves it into the batch when every
+// allocation has succeeded, so a set is whole or empty (engaged()), and it releases itself with the batch.  What a later
+// launch adds on first use (the members marked "lazily") is committed the same way, whole or not at all.  Streams in a set
+// are the context's auxiliary streams: used and drained (ce_batch_destroy), never destroyed here.
+
+// SSIMULACRA2 working set (ssim2.hip).  Image slots: [0, max_refs) references, then tests.
+struct ce_ssim2_set {
+    int n_scales = 0;
+    ce_plane_geom lvl[CE_MAX_SCALES] = {};  // pitch a multiple of 32 floats (128-byte rows), rows padded to the row pass's block
+    ce_dev<float> lin[CE_MAX_SCALES];   // [slots][3][plane_s] linear RGB pyramid (levels 1..: level 0 is read from the slabs)
+    ce_dev<float> xyb[CE_MAX_SCALES];   // [slots][3][plane_s] positive XYB, one buffer per level
+    ce_dev<float> hbuf[CE_MAX_SCALES];  // [pairs][3][5][plane_s] row-blurred streams, one buffer per level
+    // The references' final planes mu1 = blur(a), s11 = blur(a*a), per level [max_refs][3][2][plane_s], which the pair column
+    // pass of the split path reads (ssim2.hip: ce_launch_ssim2; record CE_REF_SSIM2_BLUR); lazily, every level or none.
+    // split_last: the last launch took the split path, so hbuf holds no streams 0 and 2 (ce_debug_ssim2_planes).
+    ce_dev<float> ref_blur[CE_MAX_SCALES];
+    bool split_last = false;
+    // level 0's row/column pass runs on l0_stream, fenced by ev_prep[0] / ev_done[0] against the front end and the final
+    // reduction; the other levels follow the front end on the launching stream ([1]: if they ever leave it)
+    hipStream_t l0_stream = nullptr;
+    ce_event ev_prep[2], ev_done[2];
+    ce_dev<double> partials;  // [pairs][scales][3][max_vblocks][6]
+    uint32_t max_vblocks = 0;
+    ce_dev<double> avg;       // [pairs][6][3][6]
+    // CE_FLAG_SSIMULACRA2_MAPS: per scale s, [max_pairs][channel 3][kind 3][plane_s] per-pixel error maps (d, artifact, detail
+    // lost) in one allocation, lazily; map_lvl[s] = scale s's part.  cells: the block-max readouts' device buffer (grow-only)
+    ce_dev<float> map;
+    float *map_lvl[CE_MAX_SCALES] = {};
+    ce_dev<float> cells;
+    // XCD-aware work lists of the row / column pass: launch id -> (block, channel, pair)
+    ce_xcd_list work_h, work_v;    // level 0
+    ce_xcd_list work_ht, work_vt;  // the merged launch of levels 1..
+    bool engaged() const { return avg != nullptr; }
+};
+
+// DSSIM working set (dssim.hip); planes are [slot][3][plane] with the level's own geometry
+struct ce_dssim_set {
+    int levels = 0;
+    ce_plane_geom lvl[CE_DSSIM_SCALES] = {};
+    ce_dev<float> lin[2];  // linear RGB of the current and the next level
+    ce_dev<float> img;     // [max_pairs][3][plane_0]: L, a', b' (chroma pre-blurred) of the distorted images, one level at a time
+    ce_dev<float> rimg[CE_DSSIM_SCALES], rmu[CE_DSSIM_SCALES], rsq[CE_DSSIM_SCALES];  // the references' planes, per level: [max_refs][3][plane_l]
+    ce_dev<float> map;     // [level][max_pairs][plane_l] channel-averaged SSIM maps (SsimMap.map)
+    ce_dev<double> part;   // [pairs][levels][2][blocks] partial sums (sum, abs-dev)
+    ce_dev<double> level_scores;  // [pairs][CE_DSSIM_SCALES]: after a launch, every level's score (SsimMap.ssim)
+    ce_dev<float> cells;   // the block-min readouts' device buffer (grow-only)
+    uint32_t blocks = 0;
+    ce_xcd_list gwork[CE_DSSIM_SCALES];  // k_dssim_compare_stream's launch order, per level
+    bool engaged() const { return level_scores != nullptr; }
+};
+
+// a small batch runs Butteraugli's half-resolution chain on a stream of its own, beside the full-resolution one, with its
+// own scratch (butteraugli.hip: ce_launch_butteraugli)
+struct ce_ba_half {
+    hipStream_t stream = nullptr;
+    ce_event ev_fork, ev_join;
+    ce_dev<float> s[3];
+};
+
+// Butteraugli working set (butteraugli.hip): level 0 = full resolution, 1 = 2x-subsampled
+struct ce_ba_set {
+    ce_plane_geom lvl[2] = {};
+    int levels = 0;
+    ce_dev<float> psy[2];   // [slot][10][plane_l]  PsychoImage
+    ce_dev<float> diff[2];  // [pair][plane_1]      the half-resolution diffmap ([1]; the full-resolution one is reduced in registers)
+    ce_dev<float> mask[2];  // [slot][plane_l]      blurred mask input (DiffPrecompute of HF + UHF, sigma 2.7)
+    ce_dev<float> s[3];     // per-slot scratch, 3 planes each
+    ce_ba_half half;        // lazily
+    ce_dev<float> mask_vals[2];  // [ref][2][plane_l]    maskval / dc_maskval of the references (FuzzyErosion + mask curves)
+    // CE_FLAG_BUTTERAUGLI_DIFFMAP: [pair][plane_0] full-resolution diffmaps, lazily; cells: the block-max readouts' device
+    // buffer (grow-only)
+    ce_dev<float> map, cells;
+    ce_dev<float> blk_max;
+    ce_dev<double> blk_sums;
+    ce_dev<double> pnorm;  // [pair] libjxl 3-norm of the last run
+    uint32_t blocks = 0;
+    ce_xcd_list work[2];  // Malta's launch order, per resolution level
+    bool engaged() const { return pnorm != nullptr; }
 };
 
 struct ce_batch {
@@ -171,10 +262,10 @@ struct ce_batch {
     uint32_t depth[2] = {0, 0};
     const float *deep_lut[2][2] = {};
 
-    uint8_t *d_refs = nullptr;     // [max_refs][h][w][3]
-    uint8_t *d_refs_rt = nullptr;  // XYB-roundtripped references (lazily allocated)
-    uint8_t *d_tests = nullptr;    // [max_pairs][h][w][3]
-    uint32_t *d_pair_ref = nullptr;
+    ce_dev<uint8_t> d_refs;     // [max_refs][h][w][3]
+    ce_dev<uint8_t> d_refs_rt;  // XYB-roundtripped references (lazily)
+    ce_dev<uint8_t> d_tests;    // [max_pairs][h][w][3]
+    ce_dev<uint32_t> d_pair_ref;
     uint32_t *d_pair_first = nullptr;  // second part of the d_pair_ref allocation
     uint32_t *d_ref_off = nullptr, *d_ref_idx = nullptr;  // ... then reference -> its pairs (CSR: [max_refs + 1] offsets, [max_pairs] pair indices)
     std::vector<uint32_t> h_pair_ref;
@@ -182,125 +273,59 @@ struct ce_batch {
     uint32_t pair_ref_version = 0;  // bumped whenever the pair -> reference table changes
     // pinned staging ring for host -> device uploads: the host copy into slot k overlaps the DMA of slot k-1
     static constexpr int kStages = 8;  // two per upload worker (ce_eval_batch fills a bucket with 4 host threads)
-    uint8_t *h_stage[kStages] = {};
-    hipEvent_t ev_stage[kStages] = {};
+    ce_pinned<uint8_t> h_stage[kStages];
+    ce_event ev_stage[kStages];
     bool stage_busy[kStages] = {};
     int next_stage = 0;
     // uploads run on their own stream so that filling one batch overlaps another batch's kernels
-    hipStream_t up_stream = nullptr;
-    hipEvent_t ev_up = nullptr, ev_run = nullptr;  // uploads done / last launch done
+    ce_stream up_stream;
+    ce_event ev_up, ev_run;  // uploads done / last launch done
     bool uploads_pending = false, run_pending = false;
     bool inline_pending = false;  // a slot was written on the context's stream since the last launch (ce_ingest.cpp: ce_order_write)
     bool counted_in_flight = false;  // this batch is in the device's launched-and-not-collected count (ce_api.cpp: g_in_flight)
     // the wide staging pairs of every image a conversion kernel follows: one pinned + one device staging image each, made
-    // on first use and handed out in turn (ce_ingest.cpp: wide_send, which states their size and alone touches them)
-    uint8_t *h_wide[2] = {}, *d_wide[2] = {};
-    size_t wide_cap[2] = {};  // bytes a pair holds: what wide_send states, more once a tensor image needed more
-    hipEvent_t ev_wide[2] = {};
+    // on first use and handed out in turn (ce_ingest.cpp: wide_send, which states their size - more once a tensor image needed
+    // more - and alone touches them)
+    ce_mirror<uint8_t> wide[2];
+    ce_event ev_wide[2];
     bool wide_busy[2] = {};
     int next_wide = 0;
     // what a gain-map ingest stages beside its base image, which takes wide pair k: the log2-gain tables and the map's samples
     // in a pinned + device pair of their own (ce_ingest.cpp: upload_gainmap, which states their size), busy with wide pair k
-    uint8_t *h_side[2] = {}, *d_side[2] = {};
+    ce_mirror<uint8_t> side[2];
 
-    // SSIMULACRA2 working set.  Image slots: [0, max_refs) references, then tests.
-    int n_scales = 0;
-    ce_scale_dims sd[CE_MAX_SCALES];
-    float *d_lin[CE_MAX_SCALES] = {};  // [slots][3][plane_s] linear RGB pyramid
-    float *d_xyb[CE_MAX_SCALES] = {};   // [slots][3][plane_s] positive XYB, one buffer per level
-    float *d_hbuf[CE_MAX_SCALES] = {};  // [pairs][3][5][plane_s] row-blurred streams, one buffer per level
-    // The references' final planes mu1 = blur(a), s11 = blur(a*a), per level [max_refs][3][2][plane_s], which the pair column
-    // pass of the split path reads (ssim2.hip: ce_launch_ssim2; record CE_REF_SSIM2_BLUR).  s2_split_last: the last launch
-    // took the split path, so d_hbuf holds no streams 0 and 2 (ce_debug_ssim2_planes).  ref_handle: a reference handle's batch.
-    float *s2_ref_blur[CE_MAX_SCALES] = {};
-    bool s2_split_last = false, ref_handle = false;
-    // level 0's row/column pass runs on lvl_stream[0], fenced by events against the front end and the final reduction;
-    // the other levels follow the front end on the context's stream (entries 1.. are unused)
-    hipStream_t lvl_stream[CE_MAX_SCALES] = {};
-    // one stream per metric chain when a launch runs several of them (SSIMULACRA2, DSSIM, Butteraugli side by side)
-    hipStream_t metric_stream[3] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[3] = {};
-    hipEvent_t ev_prep[CE_MAX_SCALES] = {}, ev_done[CE_MAX_SCALES] = {};
-    double *d_partials = nullptr;      // [pairs][scales][3][max_blocks][6]
-    uint32_t max_vblocks = 0;
-    double *d_avg = nullptr;           // [pairs][6][3][6]
-    // CE_FLAG_SSIMULACRA2_MAPS: per scale s, [max_pairs][channel 3][kind 3][plane_s] per-pixel error maps (d, artifact,
-    // detail lost; one allocation s2_map made by the first such launch, s2_map_lvl[s] = scale s's part); how many pairs of
-    // the LAST launch stored their maps (0 after a launch without the flag or without SSIMULACRA2) and left their pooled
-    // norms in d_avg (every launch with SSIMULACRA2), the scales it ran; the device buffer of the block-max readouts (grow-only)
-    float *s2_map = nullptr;
-    float *s2_map_lvl[CE_MAX_SCALES] = {};
-    uint32_t s2_map_pairs = 0, s2_norm_pairs = 0, s2_scales_run = 0;
-    float *s2_cells = nullptr;
-    size_t s2_cells_cap = 0;
-    ce_dev_scores *d_scores = nullptr;
-    ce_dev_scores *h_scores = nullptr;  // pinned
-    bool ssim2_ready = false;
-    // XCD-aware work lists of the row / column pass (ssim2.hip): launch id -> (block, channel, pair)
-    ce_xcd_list work_h, work_v;    // level 0
-    ce_xcd_list work_ht, work_vt;  // the merged launch of levels 1..
+    // one stream per metric chain when a launch runs several of them (SSIMULACRA2, DSSIM, Butteraugli side by side): the
+    // context's auxiliary stream and the event that joins it back, lazily
+    struct metric_fork {
+        hipStream_t stream = nullptr;
+        ce_event ev_join;
+    } fork[3];
+    ce_event ev_fork;
+
+    // The metrics' working sets, and what the LAST launch left in them: how many pairs stored their SSIMULACRA2 maps (0 after
+    // a launch without the flag or without SSIMULACRA2) and left their pooled norms in s2.avg (every launch with SSIMULACRA2),
+    // the scales it ran; how many left their SSIM maps in ds.map (every launch with DSSIM does) and their diffmaps in ba.map
+    // (CE_FLAG_BUTTERAUGLI_DIFFMAP).  ref_handle: a reference handle's batch.
+    ce_ssim2_set s2;
+    ce_dssim_set ds;
+    ce_ba_set ba;
+    uint32_t s2_map_pairs = 0, s2_norm_pairs = 0, s2_scales_run = 0, ds_map_pairs = 0, ba_map_pairs = 0;
+    bool ref_handle = false;
+    ce_dev<ce_dev_scores> d_scores;
+    ce_pinned<ce_dev_scores> h_scores;
     // What the planes derived from the references were built from, per metric and for d_refs_rt (ce_ref_state.h): they stay
     // valid until a reference is written, so later launches only build the distorted side.  Each metric's launch function
     // touches its own record only (the chains of a forked batch are enqueued by three host threads).
     ce_ref_states refs;
     int debug_max_scales = CE_MAX_SCALES;  // test hook: stop the pyramid early
+    uint32_t debug_ds_rows = 0;  // test hook (ce_debug_dssim_walk_rows): forced walk length of DSSIM's streaming kernels, 0 = automatic
 
-    // DSSIM working set (dssim.hip); planes are [slot][3][plane] with the level's own geometry
-    struct dssim_level { uint32_t w, h, pitch; size_t plane; };
-    int ds_levels = 0;
-    dssim_level ds[CE_DSSIM_SCALES];
-    float *ds_lin[2] = {};     // linear RGB of the current and the next level
-    float *ds_img = nullptr;   // [max_pairs][3][plane_0]: L, a', b' (chroma pre-blurred) of the distorted images, one level at a time
-    float *ds_rimg[CE_DSSIM_SCALES] = {}, *ds_rmu[CE_DSSIM_SCALES] = {}, *ds_rsq[CE_DSSIM_SCALES] = {};  // the references' planes, per level: [max_refs][3][plane_l]
-    float *ds_map = nullptr;   // [level][max_pairs][plane_l] channel-averaged SSIM maps (SsimMap.map)
-    double *ds_part = nullptr; // [pairs][levels][2][blocks] partial sums (sum, abs-dev)
-    double *ds_level_scores = nullptr;  // [pairs][CE_DSSIM_SCALES]: after a launch, every level's score (SsimMap.ssim)
-    // how many pairs of the LAST launch left their SSIM maps in ds_map (every launch with DSSIM does; 0 after one without),
-    // and the device buffer of the block-min readouts (grow-only)
-    uint32_t ds_map_pairs = 0;
-    float *ds_cells = nullptr;
-    size_t ds_cells_cap = 0;
-    uint32_t ds_blocks = 0;
-    uint32_t debug_ds_rows = 0;  // test hook (ce_debug_dssim_walk_rows): forced walk length of the streaming kernels, 0 = automatic
-    ce_xcd_list ds_gwork[CE_DSSIM_SCALES];  // k_dssim_compare_stream's launch order, per level
-    bool dssim_ready = false;
-
-    // Butteraugli working set (butteraugli.hip): level 0 = full resolution, 1 = 2x-subsampled
-    struct ba_level { uint32_t w, h, pitch; size_t plane; };
-    ba_level ba[2];
-    int ba_levels = 0;
-    float *ba_psy[2] = {};    // [slot][10][plane_l]  PsychoImage
-    float *ba_diff[2] = {};   // [pair][plane_1]      the half-resolution diffmap ([1]; the full-resolution one is reduced in registers)
-    float *ba_mask[2] = {};   // [slot][plane_l]      blurred mask input (DiffPrecompute of HF + UHF, sigma 2.7)
-    float *ba_s[3] = {};      // per-slot scratch, 3 planes each
-    // a small batch runs its half-resolution chain on a stream of its own, beside the full-resolution one, with its own
-    // scratch (butteraugli.hip: ce_launch_butteraugli); made on first use
-    float *ba_s_half[3] = {};
-    hipStream_t ba_half_stream = nullptr;
-    hipEvent_t ev_ba_fork = nullptr, ev_ba_join = nullptr;
-    float *ba_mask_vals[2] = {};  // [ref][2][plane_l]    maskval / dc_maskval of the references (FuzzyErosion + mask curves)
-    // CE_FLAG_BUTTERAUGLI_DIFFMAP: [pair][plane_0] full-resolution diffmaps (made on the first such launch), how many pairs
-    // of the LAST launch stored theirs (0 after a launch without the flag or without Butteraugli), and the device buffer
-    // of the block-max readouts (grow-only)
-    float *ba_map = nullptr;
-    uint32_t ba_map_pairs = 0;
-    float *ba_cells = nullptr;
-    size_t ba_cells_cap = 0;
-    float *ba_blk_max = nullptr;
-    double *ba_blk_sums = nullptr;
-    double *ba_pnorm = nullptr;  // [pair] libjxl 3-norm of the last run
-    uint32_t ba_blocks = 0;
-    ce_xcd_list ba_work[2];  // Malta's launch order, per resolution level
-    bool ba_ready = false;
-
-    // HDR fidelity (hdr_fidelity.hip): [max_pairs][3] exact integers on the device and page-locked, made by the first call
-    unsigned long long *d_hdr = nullptr, *h_hdr = nullptr;
-    // Delta E ITP maps (hdr_fidelity.hip: k_delta_e_itp_map): the device buffer of the maps or cell maxima of one call, grow-only,
-    // made by the first call that asks for a map; [max_pairs][8] exceedance counts on the device and page-locked, made by the
-    // first call that asks for counts
-    uint32_t *d_itp_map = nullptr;
-    size_t itp_map_cap = 0;  // elements
-    unsigned long long *d_itp_over = nullptr, *h_itp_over = nullptr;
+    // HDR fidelity (hdr_fidelity.hip): [max_pairs][3] exact integers on the device and page-locked, lazily
+    ce_mirror<unsigned long long> hdr;
+    // Delta E ITP maps (hdr_fidelity.hip: k_delta_e_itp_map): the device buffer of the maps or cell maxima of one call, grow-only;
+    // [max_pairs][8] exceedance counts on the device and page-locked, made by the first call that asks for counts
+    ce_dev<uint32_t> d_itp_map;
+    ce_mirror<unsigned long long> itp_over;
 
     uint32_t last_n_pairs = 0;
     bool caller_blocks = false;  // set by entry points that collect before returning: page-locked sources need no staging copy
@@ -448,7 +473,6 @@ int ce_launch_ingest_deep(ce_ctx *ctx, hipStream_t stream, int format, uint32_t 
 int ce_launch_lut_expand(ce_ctx *ctx, hipStream_t stream, const uint8_t *d_packed, uint32_t *d_table);
 int ce_launch_lut_apply(ce_ctx *ctx, hipStream_t stream, uint8_t *d_rgb, const uint32_t *d_table, size_t n_pixels);
 int ce_ssim2_prepare(ce_batch *b);
-void ce_ssim2_free(ce_batch *b);
 int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, uint32_t n_pairs, bool store_maps);
 int ce_ssim2_read_maps(ce_batch *b, uint32_t scale, uint32_t channel, uint32_t kind, uint32_t first, uint32_t count,
                        uint32_t block, float *maps, double *norms);
@@ -456,23 +480,16 @@ int ce_ssim2_occupancy(int which);
 int ce_ssim2_cbrt_sweep(ce_ctx *ctx, uint32_t first_bits, uint64_t count, uint64_t *mismatches, uint64_t *slow_path);
 int ce_launch_xyb_roundtrip(ce_ctx *ctx, const uint8_t *d_in, uint8_t *d_out, size_t n_pixels);
 int ce_launch_dssim(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, uint32_t n_pairs);
-void ce_dssim_free(ce_batch *b);
 int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, uint32_t n_pairs, float intensity_target,
                           bool store_map);
 int ce_butteraugli_read_maps(ce_batch *b, uint32_t first, uint32_t count, uint32_t block, float *out);
 int ce_dssim_read_maps(ce_batch *b, uint32_t level, uint32_t first, uint32_t count, uint32_t block, float *maps, double *ssim);
-// a pitched per-pair map plane set (maps.hip)
-struct ce_map_geom {
-    uint32_t w, h, pitch;
-    size_t plane;
-};
-int ce_read_map_cells(ce_batch *b, const char *name, const float *map, ce_map_geom g, uint32_t first, uint32_t count, uint32_t block,
-                      bool take_min, float **cells, size_t *cells_cap, float *out);
-void ce_butteraugli_free(ce_batch *b);
+// a readout of pitched per-pair maps, g.plane floats from one pair's to the next's, through the grow-only `cells` (maps.hip)
+int ce_read_map_cells(ce_batch *b, const char *name, const float *map, ce_plane_geom g, uint32_t first, uint32_t count, uint32_t block,
+                      bool take_min, ce_dev<float> &cells, float *out);
 int ce_butteraugli_div_sweep(ce_ctx *ctx, uint64_t seed, uint64_t count, uint64_t *mismatches);
 int ce_calibrate_traffic(ce_ctx *ctx, size_t bytes);
 int ce_build_xcd_list(ce_batch *b, uint32_t n_pairs, const ce_xcd_keys &keys, ce_xcd_list *list);
-void ce_free_xcd_list(ce_xcd_list *list);
 int ce_launch_rgb8_to_dssim_image(ce_ctx *ctx, const uint8_t *d_rgb, float *d_rgba, size_t n_pixels);
 // compute_heuristics of n packed RGB8 images of one shape, img_stride bytes apart on the device, on the context's stream;
 // returns after the results are in out (heuristics.hip)

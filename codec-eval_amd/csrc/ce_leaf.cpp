@@ -273,7 +273,7 @@ int ce_calculate_ssimulacra2_maps(ce_ctx *ctx, const uint8_t *reference, size_t 
                               CE_FLAG_SSIMULACRA2_MAPS, 0.0f, &s, &b))
         return rc;
     double avg[CE_SSIM2_MAX_SCALES * 18];
-    CE_HIP(ctx, hipMemcpyAsync(avg, b->d_avg, sizeof(avg), hipMemcpyDeviceToHost, ctx->stream));
+    CE_HIP(ctx, hipMemcpyAsync(avg, b->s2.avg, sizeof(avg), hipMemcpyDeviceToHost, ctx->stream));
     CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (uint32_t i = 0; i < CE_SSIM2_MAX_SCALES * 18; i++) features[i] = i < b->s2_scales_run * 18 ? avg[i] : NAN;
     size_t off = 0;

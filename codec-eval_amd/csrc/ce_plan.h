@@ -8,6 +8,13 @@
 #include <map>
 #include <vector>
 
+// one pitched float plane of every metric's working set and of the per-pixel maps: w x h samples, rows `pitch` floats apart,
+// the next plane `plane` floats on.  Kernels take it by value.
+struct ce_plane_geom {
+    uint32_t w, h, pitch;
+    size_t plane;
+};
+
 inline constexpr uint32_t ce_plan_ring_slots = 3;  // pooled batches per shape a bucket streams through (ce_ctx::kPoolRing)
 inline constexpr size_t ce_plan_none = ~(size_t)0;
 

@@ -142,82 +142,53 @@ __global__ __launch_bounds__(64) void k_dssim_finalize_pairs(const double *__res
     if (lane == 0) scores[p].dssim = 1.0 / ssim - 1.0;
 }
 
-// level l's SSIM maps start at ds_map + map_offset(b, l): the levels one after the other, max_pairs planes each
-size_t map_offset(const ce_batch *b, int l)
+// level l's SSIM maps start at ds.map + map_offset(b, l): the levels one after the other, max_pairs planes each
+size_t map_offset(const ce_batch *b, const ce_dssim_set &ds, int l)
 {
     size_t off = 0;
-    for (int k = 0; k < l; k++) off += (size_t)b->max_pairs * b->ds[k].plane;
+    for (int k = 0; k < l; k++) off += (size_t)b->max_pairs * ds.lvl[k].plane;
     return off;
 }
+size_t map_offset(const ce_batch *b, int l) { return map_offset(b, b->ds, l); }
 
 }  // namespace
 
-void ce_dssim_free(ce_batch *b)
+static int dssim_prepare(ce_batch *b)
 {
-    for (auto &p : b->ds_lin) hipFree(p), p = nullptr;
-    hipFree(b->ds_img); hipFree(b->ds_map);
-    for (int l = 0; l < CE_DSSIM_SCALES; l++) {
-        hipFree(b->ds_rimg[l]); hipFree(b->ds_rmu[l]); hipFree(b->ds_rsq[l]);
-        b->ds_rimg[l] = b->ds_rmu[l] = b->ds_rsq[l] = nullptr;
-        ce_free_xcd_list(&b->ds_gwork[l]);
-    }
-    b->refs.of[CE_REF_DSSIM].invalidate();
-    hipFree(b->ds_part); hipFree(b->ds_level_scores); hipFree(b->ds_cells);
-    b->ds_img = b->ds_map = b->ds_cells = nullptr;
-    b->ds_cells_cap = 0;
-    b->ds_map_pairs = 0;
-    b->ds_part = b->ds_level_scores = nullptr;
-    b->dssim_ready = false;
-}
-
-static int dssim_allocate(ce_batch *b)
-{
+    if (b->ds.engaged()) return CE_OK;
     ce_ctx *ctx = b->ctx;
+    ce_dssim_set D;
     uint32_t lw[CE_DSSIM_SCALES], lh[CE_DSSIM_SCALES];
-    const int n = (int)ce_plan_dssim_levels(b->w, b->h, CE_DSSIM_SCALES, lw, lh);  // make_scales_recursive (ce_plan.h)
+    const int n = D.levels = (int)ce_plan_dssim_levels(b->w, b->h, CE_DSSIM_SCALES, lw, lh);  // make_scales_recursive (ce_plan.h)
     for (int l = 0; l < n; l++) {
-        auto &d = b->ds[l];
+        ce_plane_geom &d = D.lvl[l];
         d.w = lw[l];
         d.h = lh[l];
         d.pitch = (d.w + 31u) & ~31u;
         d.plane = (size_t)d.pitch * d.h;
     }
-    b->ds_levels = n;
-    const size_t slots = (size_t)b->max_refs + b->max_pairs, p0 = b->ds[0].plane;
-    // linear RGB ping-pong for levels >= 1 (level 0 is read from the u8 slabs): level l lives in ds_lin[l & 1]
-    const size_t p1 = n > 1 ? b->ds[1].plane : 1;
-    CE_HIP(ctx, hipMalloc(&b->ds_lin[0], slots * 3 * p1 * sizeof(float)));
-    CE_HIP(ctx, hipMalloc(&b->ds_lin[1], slots * 3 * p1 * sizeof(float)));
-    CE_HIP(ctx, hipMalloc(&b->ds_img, (size_t)b->max_pairs * 3 * p0 * sizeof(float)));  // the distorted images' img, one level at a time
+    const size_t slots = (size_t)b->max_refs + b->max_pairs, p0 = D.lvl[0].plane;
+    // linear RGB ping-pong for levels >= 1 (level 0 is read from the u8 slabs): level l lives in lin[l & 1]
+    const size_t p1 = n > 1 ? D.lvl[1].plane : 1;
+    int rc = D.lin[0].alloc(ctx, slots * 3 * p1);
+    if (rc == CE_OK) rc = D.lin[1].alloc(ctx, slots * 3 * p1);
+    if (rc == CE_OK) rc = D.img.alloc(ctx, (size_t)b->max_pairs * 3 * p0);  // the distorted images' img, one level at a time
     // the references' planes, one set per level: they outlive the level loop (Dssim::create_image of the reference is
     // run once per reference, dssim.rs:54-59; kept across launches until a reference is written, ce_ref_state.h)
-    for (int l = 0; l < n; l++) {
-        const size_t rb = (size_t)b->max_refs * 3 * b->ds[l].plane * sizeof(float);
-        CE_HIP(ctx, hipMalloc(&b->ds_rimg[l], rb));
-        CE_HIP(ctx, hipMalloc(&b->ds_rmu[l], rb));
-        CE_HIP(ctx, hipMalloc(&b->ds_rsq[l], rb));
+    for (int l = 0; l < n && rc == CE_OK; l++) {
+        const size_t rn = (size_t)b->max_refs * 3 * D.lvl[l].plane;
+        rc = D.rimg[l].alloc(ctx, rn);
+        if (rc == CE_OK) rc = D.rmu[l].alloc(ctx, rn);
+        if (rc == CE_OK) rc = D.rsq[l].alloc(ctx, rn);
     }
     // every level's SSIM maps, kept until the next launch (ce_dssim_read_maps)
-    CE_HIP(ctx, hipMalloc(&b->ds_map, map_offset(b, n) * sizeof(float)));
+    if (rc == CE_OK) rc = D.map.alloc(ctx, map_offset(b, D, n));
     // partial sums per (pair, level): the absdev kernel's blocks, or the compare kernel's strip tiles (>= 2 rows each)
-    b->ds_blocks = std::max(((b->ds[0].w + 63) / 64) * ((b->ds[0].h + AD_ROWS - 1) / AD_ROWS), ((b->ds[0].w + CE_DSSIM_STRIP - 1) / CE_DSSIM_STRIP) * ((b->ds[0].h + 1) / 2));
-    CE_HIP(ctx, hipMalloc(&b->ds_part, (size_t)b->max_pairs * CE_DSSIM_SCALES * 2 * b->ds_blocks * sizeof(double)));
-    CE_HIP(ctx, hipMalloc(&b->ds_level_scores, (size_t)b->max_pairs * CE_DSSIM_SCALES * sizeof(double)));  // avg, then score
-    return CE_OK;
-}
-
-static int dssim_prepare(ce_batch *b)
-{
-    if (b->dssim_ready) return CE_OK;
-    const int rc = dssim_allocate(b);
-    if (rc != CE_OK) {  // all or nothing (see ce_ssim2_prepare)
-        const std::string why = b->ctx->err;
-        ce_dssim_free(b);
-        (void)hipGetLastError();
-        b->ctx->err = why;
-        return rc;
-    }
-    b->dssim_ready = true;
+    D.blocks = std::max(((D.lvl[0].w + 63) / 64) * ((D.lvl[0].h + AD_ROWS - 1) / AD_ROWS), ((D.lvl[0].w + CE_DSSIM_STRIP - 1) / CE_DSSIM_STRIP) * ((D.lvl[0].h + 1) / 2));
+    if (rc == CE_OK) rc = D.part.alloc(ctx, (size_t)b->max_pairs * CE_DSSIM_SCALES * 2 * D.blocks);
+    if (rc == CE_OK) rc = D.level_scores.alloc(ctx, (size_t)b->max_pairs * CE_DSSIM_SCALES);  // avg, then score
+    if (rc != CE_OK) return rc;  // all or nothing: D releases what it got
+    b->ds = std::move(D);
     return CE_OK;
 }
 
@@ -231,12 +202,12 @@ int ce_launch_dssim(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
     const uint32_t z0 = cached ? n_refs_used : 0;
     ds_geom g{};
     ds_tail tail{};
-    for (int l = 0; l < b->ds_levels; l++) {
-        const auto &d = b->ds[l];
+    for (int l = 0; l < b->ds.levels; l++) {
+        const auto &d = b->ds.lvl[l];
         // create_image for every used slot (references once per reference), then compare per pair: dssim_stream.hip
         if ((rc = ce_dssim_create_stream(b, l, d_refs, n_refs_used, n_pairs, z0)) != CE_OK) return rc;
         uint32_t n_part = 0;
-        if ((rc = ce_dssim_compare_stream(b, l, n_pairs, b->ds_map + map_offset(b, l), &n_part)) != CE_OK) return rc;
+        if ((rc = ce_dssim_compare_stream(b, l, n_pairs, b->ds.map + map_offset(b, l), &n_part)) != CE_OK) return rc;
         tail.w[l] = d.w, tail.h[l] = d.h, tail.pitch[l] = d.pitch, tail.plane[l] = d.plane, tail.n_part[l] = n_part;
         tail.gx[l] = (d.w + 63) / 64;
         tail.map_off[l] = map_offset(b, l);
@@ -245,14 +216,14 @@ int ce_launch_dssim(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
         tail.blk_end[l] = (l ? tail.blk_end[l - 1] : 0u) + g.nblk[l];
     }
     {
-        const uint32_t nl = (uint32_t)b->ds_levels;
-        CE_LAUNCH(ctx, "dssim_avg", k_dssim_avg, dim3(n_pairs, nl), dim3(TPB), 0, b->ds_part, b->ds_level_scores, tail, nl, b->ds_blocks);
+        const uint32_t nl = (uint32_t)b->ds.levels;
+        CE_LAUNCH(ctx, "dssim_avg", k_dssim_avg, dim3(n_pairs, nl), dim3(TPB), 0, b->ds.part, b->ds.level_scores, tail, nl, b->ds.blocks);
         const dim3 gp(tail.blk_end[nl - 1] * n_pairs);
-        CE_LAUNCH(ctx, "dssim_absdev", k_dssim_absdev, gp, dim3(TPB), 0, (const float *)b->ds_map, b->ds_level_scores, b->ds_part, tail, nl,
-                  b->ds_blocks);
+        CE_LAUNCH(ctx, "dssim_absdev", k_dssim_absdev, gp, dim3(TPB), 0, (const float *)b->ds.map, b->ds.level_scores, b->ds.part, tail, nl,
+                  b->ds.blocks);
     }
-    CE_LAUNCH(ctx, "dssim_finalize", k_dssim_finalize_pairs, dim3(n_pairs), dim3(64), 0, b->ds_part,
-              b->ds_level_scores, b->d_scores, n_pairs, (uint32_t)b->ds_levels, b->ds_blocks, g);
+    CE_LAUNCH(ctx, "dssim_finalize", k_dssim_finalize_pairs, dim3(n_pairs), dim3(64), 0, b->ds.part,
+              b->ds.level_scores, b->d_scores, n_pairs, (uint32_t)b->ds.levels, b->ds.blocks, g);
     CE_HIP(ctx, hipGetLastError());
     if (!cached) b->refs.built(CE_REF_DSSIM, d_refs, n_refs_used, 0);
     return CE_OK;
@@ -265,14 +236,13 @@ int ce_dssim_read_maps(ce_batch *b, uint32_t level, uint32_t first, uint32_t cou
 {
     ce_ctx *ctx = b->ctx;
     if (ssim) {  // every pair's score of this level: a strided gather out of [pair][CE_DSSIM_SCALES]
-        CE_HIP(ctx, hipMemcpy2DAsync(ssim, sizeof(double), b->ds_level_scores + (size_t)first * CE_DSSIM_SCALES + level,
+        CE_HIP(ctx, hipMemcpy2DAsync(ssim, sizeof(double), b->ds.level_scores + (size_t)first * CE_DSSIM_SCALES + level,
                                      CE_DSSIM_SCALES * sizeof(double), sizeof(double), count, hipMemcpyDeviceToHost, ctx->stream));
         if (!maps) CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (!maps) return CE_OK;
-    const auto &d = b->ds[level];
-    return ce_read_map_cells(b, "dssim_block_min", b->ds_map + map_offset(b, (int)level), ce_map_geom{d.w, d.h, d.pitch, d.plane},
-                             first, count, block, true, &b->ds_cells, &b->ds_cells_cap, maps);
+    const auto &d = b->ds.lvl[level];
+    return ce_read_map_cells(b, "dssim_block_min", b->ds.map + map_offset(b, (int)level), d, first, count, block, true, b->ds.cells, maps);
 }
 
 int ce_launch_rgb8_to_dssim_image(ce_ctx *ctx, const uint8_t *d_rgb, float *d_rgba, size_t n_pixels)

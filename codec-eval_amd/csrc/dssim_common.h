@@ -3,11 +3,6 @@
 
 #include "ce_internal.h"
 
-struct lvl_geom {
-    uint32_t w, h, pitch;
-    size_t plane;
-};
-
 #if defined(__HIPCC__)
 namespace {
 // ---- linear RGB -> normalised (L, a, b) ------------------------------------------------------------

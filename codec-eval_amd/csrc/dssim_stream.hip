@@ -71,7 +71,7 @@ struct cmp_planes {  // wave-uniform plane bases (scalar registers); a lane adds
 };
 
 template <bool EDGE>
-__device__ __forceinline__ double dssim_compare_strip(const cmp_planes &pl, float *__restrict__ map, const lvl_geom &g, int xs, int y0, int y1)
+__device__ __forceinline__ double dssim_compare_strip(const cmp_planes &pl, float *__restrict__ map, const ce_plane_geom &g, int xs, int y0, int y1)
 {
     const int w = (int)g.w, h = (int)g.h, lane = (int)(threadIdx.x & 63);
     const uint32_t pitch = g.pitch;
@@ -176,7 +176,7 @@ __device__ __forceinline__ double dssim_compare_strip(const cmp_planes &pl, floa
 __global__ __launch_bounds__(CS_WAVES * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_dssim_compare_stream(const float *__restrict__ img, const float *__restrict__ rimg,
                                                                         const float *__restrict__ rmu, const float *__restrict__ rsq,
                                                                         const uint32_t *__restrict__ pair_ref, float *__restrict__ map,
-                                                                        double *__restrict__ part, lvl_geom g, uint32_t level,
+                                                                        double *__restrict__ part, ce_plane_geom g, uint32_t level,
                                                                         uint32_t n_levels, uint32_t n_blocks,
                                                                         const uint2 *__restrict__ work, uint32_t strips, uint32_t rows)
 {
@@ -219,7 +219,7 @@ constexpr int CR_HALO_REF = 4, CR_HALO_DIST = 2;
 template <int SRC, bool REF, bool EDGE>
 __device__ __forceinline__ void dssim_create_strip(const uint8_t *__restrict__ src8, const float *const (&srcf)[3], const float *s_lut,
                                                    float *const (&lin_out)[3], float *const (&oimg)[3], float *const (&omu)[3],
-                                                   float *const (&osq)[3], const lvl_geom &g, const lvl_geom &gn, int has_next, int xs,
+                                                   float *const (&osq)[3], const ce_plane_geom &g, const ce_plane_geom &gn, int has_next, int xs,
                                                    int y0, int y1)
 {
     constexpr bool FROM_U8 = SRC == CE_SRC_U8, FROM_U16 = SRC == CE_SRC_U16;
@@ -371,7 +371,7 @@ __global__ __launch_bounds__(CS_WAVES * 64) void k_dssim_create_stream(const uin
                                                                        const float *__restrict__ lin_in,
                                                                        float *__restrict__ lin_out, float *__restrict__ img,
                                                                        float *__restrict__ rimg, float *__restrict__ rmu,
-                                                                       float *__restrict__ rsq, lvl_geom g, lvl_geom gn, int has_next,
+                                                                       float *__restrict__ rsq, ce_plane_geom g, ce_plane_geom gn, int has_next,
                                                                        size_t img_bytes, uint32_t n_refs_used, uint32_t max_refs, uint32_t z0,
                                                                        uint32_t rows)
 {
@@ -435,10 +435,9 @@ uint32_t stream_rows(uint32_t strips, uint32_t h, uint32_t n_images)
 int ce_dssim_create_stream(ce_batch *b, int l, const uint8_t *d_refs, uint32_t n_refs_used, uint32_t n_pairs, uint32_t z0)
 {
     ce_ctx *ctx = b->ctx;
-    const auto &d = b->ds[l];
-    const bool has_next = l + 1 < b->ds_levels;
-    const auto &nd = b->ds[has_next ? l + 1 : l];
-    const lvl_geom lg{d.w, d.h, d.pitch, d.plane}, ng{nd.w, nd.h, nd.pitch, nd.plane};
+    const auto &d = b->ds.lvl[l];
+    const bool has_next = l + 1 < b->ds.levels;
+    const auto &nd = b->ds.lvl[has_next ? l + 1 : l];
     const uint32_t n_slots = n_refs_used + n_pairs;
     if (n_slots <= z0) return CE_OK;
     const uint32_t strips_ref = (d.w + 64 - 2 * CR_HALO_REF - 1) / (64 - 2 * CR_HALO_REF), strips = (d.w + CS_OUT - 1) / CS_OUT;
@@ -446,8 +445,8 @@ int ce_dssim_create_stream(ce_batch *b, int l, const uint8_t *d_refs, uint32_t n
     const uint32_t tiles = std::max(z0 < n_refs_used ? strips_ref : 0u, strips) * ((d.h + rows - 1) / rows);
 #define CE_CREATE_LAUNCH(NAME, U8, GRID, Z0, LUT_R, LUT_T)                                                                                      \
     CE_LAUNCH(ctx, NAME, (k_dssim_create_stream<U8>), GRID, dim3(CS_WAVES * 64), 0, d_refs, (const uint8_t *)b->d_tests,            \
-              (const float *)LUT_R, (const float *)LUT_T, (const float *)(l == 0 ? nullptr : b->ds_lin[l & 1]), b->ds_lin[(l + 1) & 1], b->ds_img,      \
-              b->ds_rimg[l], b->ds_rmu[l], b->ds_rsq[l], lg, ng, has_next ? 1 : 0, b->img_bytes, n_refs_used, b->max_refs, Z0, rows)
+              (const float *)LUT_R, (const float *)LUT_T, (const float *)(l == 0 ? nullptr : b->ds.lin[l & 1].get()), b->ds.lin[(l + 1) & 1], b->ds.img,      \
+              b->ds.rimg[l], b->ds.rmu[l], b->ds.rsq[l], d, nd, has_next ? 1 : 0, b->img_bytes, n_refs_used, b->max_refs, Z0, rows)
     const dim3 grid((tiles + CS_WAVES - 1) / CS_WAVES, n_slots - z0);
     if (l == 0 && b->linear) CE_CREATE_LAUNCH("dssim_create_lin", CE_SRC_LIN, grid, z0, nullptr, nullptr);
     else if (l == 0 && b->depth[0]) CE_CREATE_LAUNCH("dssim_create_u16", CE_SRC_U16, grid, z0, b->deep_lut[1][0], b->deep_lut[1][1]);
@@ -460,20 +459,19 @@ int ce_dssim_create_stream(ce_batch *b, int l, const uint8_t *d_refs, uint32_t n
 int ce_dssim_compare_stream(ce_batch *b, int l, uint32_t n_pairs, float *level_map, uint32_t *n_part)
 {
     ce_ctx *ctx = b->ctx;
-    const auto &d = b->ds[l];
-    const lvl_geom lg{d.w, d.h, d.pitch, d.plane};
+    const auto &d = b->ds.lvl[l];
     const uint32_t strips = (d.w + CS_OUT - 1) / CS_OUT, rows = b->debug_ds_rows ? b->debug_ds_rows : stream_rows(strips, d.h, n_pairs);
     // Launch order (ce_plan.h: ce_plan_xcd_list): one key per row block, entries (row block * strips + strip, pair).  A
     // block's CS_WAVES waves take consecutive entries of one XCD class, and all entries of one (reference, row block) - its
     // strips, and on each strip the reference's distorted images one after the other - go to ONE class, so that the
     // 128-byte lines two neighbouring strips share (a strip starts two columns left of a multiple of 60) and the
     // reference's lines are fetched into one L2 (and mostly by one CU) while they are in use.
-    const int rc = ce_build_xcd_list(b, n_pairs, ce_xcd_keys{1, (d.h + rows - 1) / rows, strips, CS_WAVES}, &b->ds_gwork[l]);
+    const int rc = ce_build_xcd_list(b, n_pairs, ce_xcd_keys{1, (d.h + rows - 1) / rows, strips, CS_WAVES}, &b->ds.gwork[l]);
     if (rc != CE_OK) return rc;
-    CE_LAUNCH(ctx, "dssim_compare", k_dssim_compare_stream, dim3(b->ds_gwork[l].len / CS_WAVES), dim3(CS_WAVES * 64), 0,
-              (const float *)b->ds_img, (const float *)b->ds_rimg[l], (const float *)b->ds_rmu[l], (const float *)b->ds_rsq[l],
-              b->d_pair_ref, level_map, b->ds_part, lg, (uint32_t)l, (uint32_t)b->ds_levels, b->ds_blocks,
-              (const uint2 *)b->ds_gwork[l].d, strips, rows);
+    CE_LAUNCH(ctx, "dssim_compare", k_dssim_compare_stream, dim3(b->ds.gwork[l].len / CS_WAVES), dim3(CS_WAVES * 64), 0,
+              (const float *)b->ds.img, (const float *)b->ds.rimg[l], (const float *)b->ds.rmu[l], (const float *)b->ds.rsq[l],
+              b->d_pair_ref, level_map, b->ds.part, d, (uint32_t)l, (uint32_t)b->ds.levels, b->ds.blocks,
+              (const uint2 *)b->ds.gwork[l].d, strips, rows);
     *n_part = strips * ((d.h + rows - 1) / rows);
     return CE_OK;
 }

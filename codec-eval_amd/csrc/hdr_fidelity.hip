@@ -87,8 +87,8 @@ hdrf_args hdrf_fill(const ce_batch *b, uint32_t first, uint32_t depth, const flo
 {
     hdrf_args g{};
     g.n_pixels = (size_t)b->w * b->h;
-    g.refs = reinterpret_cast<const float *>(b->d_refs);
-    g.tests = reinterpret_cast<const float *>(b->d_tests) + (size_t)first * g.n_pixels * 3;
+    g.refs = reinterpret_cast<const float *>(b->d_refs.get());
+    g.tests = reinterpret_cast<const float *>(b->d_tests.get()) + (size_t)first * g.n_pixels * 3;
     g.pair_ref = b->d_pair_ref + first, g.table = d_table, g.coarse = d_coarse;
     for (int i = 0; i < 9; i++) g.a[i] = a[i], g.b[i] = lms[i];
     g.denom = 4096.0 * (double)((1u << depth) - 1u);

@@ -21,7 +21,7 @@ struct reduce_min {
 // or past w enter as the identity and read nothing, so the pitch padding is never read; max and min of the same floats
 // are exact.
 template <class R>
-__global__ __launch_bounds__(256) void k_map_block_reduce(const float *__restrict__ map, ce_map_geom g, uint32_t first, uint32_t lb,
+__global__ __launch_bounds__(256) void k_map_block_reduce(const float *__restrict__ map, ce_plane_geom g, uint32_t first, uint32_t lb,
                                                           uint32_t tiles_x, uint32_t bw, uint32_t bh, float *__restrict__ out)
 {
     const uint32_t t = blockIdx.x % tiles_x, cy = (blockIdx.x / tiles_x) % bh, q = blockIdx.x / tiles_x / bh;
@@ -40,10 +40,10 @@ __global__ __launch_bounds__(256) void k_map_block_reduce(const float *__restric
 
 // The maps of pairs [first, first + count) of `map` (geometry g) into `out` (host, count * ceil(h / B) * ceil(w / B)
 // floats): B = 1 the maps themselves, else the cell max (take_min false) or min (take_min true), reduced into the grow-only
-// device buffer *cells.  The caller has checked the range and B.  Enqueued on the context's stream, behind the launch that
+// device buffer `cells`.  The caller has checked the range and B.  Enqueued on the context's stream, behind the launch that
 // wrote the maps (a forked metric chain joins that stream before the launch returns), and waited for.
-int ce_read_map_cells(ce_batch *b, const char *name, const float *map, ce_map_geom g, uint32_t first, uint32_t count, uint32_t block,
-                      bool take_min, float **cells, size_t *cells_cap, float *out)
+int ce_read_map_cells(ce_batch *b, const char *name, const float *map, ce_plane_geom g, uint32_t first, uint32_t count, uint32_t block,
+                      bool take_min, ce_dev<float> &cells, float *out)
 {
     ce_ctx *ctx = b->ctx;
     if (block == 1 && g.plane == (size_t)g.pitch * g.h) {  // [pair][h][pitch] rows are contiguous over the pairs: one pitched copy
@@ -64,13 +64,7 @@ int ce_read_map_cells(ce_batch *b, const char *name, const float *map, ce_map_ge
     while ((1u << lb) < block) lb++;
     const uint32_t bw = (g.w + block - 1) >> lb, bh = (g.h + block - 1) >> lb, tiles_x = (g.w + 255) / 256;
     const size_t n = (size_t)count * bw * bh;
-    if (*cells_cap < n) {
-        hipFree(*cells);
-        *cells = nullptr;
-        *cells_cap = 0;
-        CE_HIP(ctx, hipMalloc(cells, n * sizeof(float)));
-        *cells_cap = n;
-    }
+    if (int rc = cells.reserve(ctx, n)) return rc;
     const size_t blocks = (size_t)tiles_x * bh * count;
     if (blocks > 0x7fffffffu) {
         ctx->err = "map readout too large for one launch";
@@ -78,12 +72,12 @@ int ce_read_map_cells(ce_batch *b, const char *name, const float *map, ce_map_ge
     }
     if (take_min)
         CE_LAUNCH_ON(ctx, ctx->stream, name, k_map_block_reduce<reduce_min>, dim3((uint32_t)blocks), dim3(256), 0, map, g, first, lb,
-                     tiles_x, bw, bh, *cells);
+                     tiles_x, bw, bh, cells.get());
     else
         CE_LAUNCH_ON(ctx, ctx->stream, name, k_map_block_reduce<reduce_max>, dim3((uint32_t)blocks), dim3(256), 0, map, g, first, lb,
-                     tiles_x, bw, bh, *cells);
+                     tiles_x, bw, bh, cells.get());
     CE_HIP(ctx, hipGetLastError());
-    CE_HIP(ctx, hipMemcpyAsync(out, *cells, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    CE_HIP(ctx, hipMemcpyAsync(out, cells.get(), n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CE_OK;
 }

@@ -572,7 +572,7 @@ __device__ __forceinline__ void vblur_group(vblur_state &st, const float *__rest
 }
 
 // STORE = true: the same pass, also writing every pixel's three map terms (vblur_group) to maps.lvl[scale], laid out
-// [pair][channel][kind][plane of the scale] (ce_batch::s2_map).  The last argument comes after all the others, so the
+// [pair][channel][kind][plane of the scale] (ce_ssim2_set::map).  The last argument comes after all the others, so the
 // STORE = false instances read their arguments at the offsets they always had.
 struct ssim2_map_table {
     float *lvl[CE_MAX_SCALES];
@@ -847,104 +847,54 @@ __global__ __launch_bounds__(128) void k_ssim2_finalize(const double *__restrict
 
 // ---- host side ---------------------------------------------------------------------------
 
-void ce_ssim2_free(ce_batch *b)
-{
-    for (int s = 0; s < CE_MAX_SCALES; s++) {
-        hipFree(b->d_lin[s]);
-        hipFree(b->d_xyb[s]);
-        hipFree(b->d_hbuf[s]);
-        hipFree(b->s2_ref_blur[s]);
-        b->d_lin[s] = b->d_xyb[s] = b->d_hbuf[s] = b->s2_ref_blur[s] = nullptr;
-        if (b->lvl_stream[s]) hipStreamSynchronize(b->lvl_stream[s]);  // the context's stream: drained, not destroyed
-        if (b->ev_prep[s]) hipEventDestroy(b->ev_prep[s]);
-        if (b->ev_done[s]) hipEventDestroy(b->ev_done[s]);
-        b->lvl_stream[s] = nullptr;
-        b->ev_prep[s] = b->ev_done[s] = nullptr;
-    }
-    hipFree(b->d_partials);
-    hipFree(b->d_avg);
-    hipFree(b->s2_map);
-    hipFree(b->s2_cells);
-    b->d_partials = nullptr;
-    b->d_avg = nullptr;
-    b->s2_map = b->s2_cells = nullptr;
-    for (int s = 0; s < CE_MAX_SCALES; s++) b->s2_map_lvl[s] = nullptr;
-    b->s2_cells_cap = 0;
-    b->s2_map_pairs = b->s2_norm_pairs = 0;
-    for (ce_xcd_list *L : {&b->work_h, &b->work_v, &b->work_ht, &b->work_vt}) ce_free_xcd_list(L);
-    b->refs.of[CE_REF_SSIM2].invalidate();
-    b->refs.of[CE_REF_SSIM2_BLUR].invalidate();
-    b->s2_split_last = false;
-    b->ssim2_ready = false;
-}
-
-static int ssim2_allocate(ce_batch *b)
-{
-    ce_ctx *ctx = b->ctx;
-    const int ns = b->n_scales;
-    const size_t slots = (size_t)b->max_refs + b->max_pairs;
-    for (int s = 1; s < ns; s++)  // level 0 is read straight from the u8 slabs
-        CE_HIP(ctx, hipMalloc(&b->d_lin[s], slots * 3 * b->sd[s].plane * sizeof(float)));
-    for (int s = 0; s < ns; s++) {
-        CE_HIP(ctx, hipMalloc(&b->d_xyb[s], slots * 3 * b->sd[s].plane * sizeof(float)));
-        CE_HIP(ctx, hipMalloc(&b->d_hbuf[s], (size_t)b->max_pairs * 3 * CE_SSIM2_STREAMS * b->sd[s].plane * sizeof(float)));
-        if (s == 0 && !(b->lvl_stream[0] = ce_ctx_aux_stream(ctx, ce_ctx::AUX_SSIM2_L0))) return CE_ERR_BACKEND;  // level 0's passes; the other levels follow the front end
-        CE_HIP(ctx, hipEventCreateWithFlags(&b->ev_prep[s], hipEventDisableTiming));
-        CE_HIP(ctx, hipEventCreateWithFlags(&b->ev_done[s], hipEventDisableTiming));
-    }
-    b->max_vblocks = (b->sd[0].w + kColsPerBlock - 1) / kColsPerBlock;
-    CE_HIP(ctx, hipMalloc(&b->d_partials, (size_t)b->max_pairs * CE_MAX_SCALES * 3 * b->max_vblocks * 6 * sizeof(double)));
-    CE_HIP(ctx, hipMalloc(&b->d_avg, (size_t)b->max_pairs * CE_MAX_SCALES * 18 * sizeof(double)));
-    return CE_OK;
-}
-
 // The references' final planes mu1, s11 of every level, allocated by the first launch that builds them - a batch whose
 // references never outlive a launch (ce_eval_batch's pooled batches) never holds them, and ce_eval_batch sizes its chunks
 // without them (ce_api.cpp: estimate_batch_bytes).  All or nothing: false leaves no plane behind and no error, and the launch
 // keeps the unsplit passes.
 static bool ssim2_ref_blur_allocate(ce_batch *b)
 {
-    if (b->s2_ref_blur[0]) return true;
-    for (int s = 0; s < b->n_scales; s++)
-        if (hipMalloc(&b->s2_ref_blur[s], (size_t)b->max_refs * 3 * 2 * b->sd[s].plane * sizeof(float)) != hipSuccess) {
-            (void)hipGetLastError();
-            for (int t = 0; t < b->n_scales; t++) {
-                hipFree(b->s2_ref_blur[t]);
-                b->s2_ref_blur[t] = nullptr;
-            }
-            return false;
-        }
+    ce_ssim2_set &S = b->s2;
+    if (S.ref_blur[0]) return true;
+    ce_dev<float> planes[CE_MAX_SCALES];
+    for (int s = 0; s < S.n_scales; s++)
+        if (planes[s].alloc((ce_ctx *)nullptr, (size_t)b->max_refs * 3 * 2 * S.lvl[s].plane) != CE_OK) return false;
+    for (int s = 0; s < S.n_scales; s++) S.ref_blur[s] = std::move(planes[s]);
     return true;
 }
 
 int ce_ssim2_prepare(ce_batch *b)
 {
-    if (b->ssim2_ready) return CE_OK;
+    if (b->s2.engaged()) return CE_OK;
+    ce_ctx *ctx = b->ctx;
+    ce_ssim2_set S;
     uint32_t sw[CE_MAX_SCALES], sh[CE_MAX_SCALES];
-    const int ns = (int)ce_plan_ssim2_scales(b->w, b->h, CE_MAX_SCALES, sw, sh);
-    for (int s = 0; s < ns; s++) {
-        const uint32_t w = sw[s], h = sh[s];
-        ce_scale_dims &d = b->sd[s];
-        d.w = w;
-        d.h = h;
-        d.pitch = ((w + HB_CW - 1) / HB_CW) * HB_CW + HB_CW;
-        d.plane = (size_t)d.pitch * (((size_t)h + HB_ROWS - 1) / HB_ROWS * HB_ROWS);
-        d.hpitch = d.pitch;
-        d.hplane = d.plane;
-    }
-    b->n_scales = ns;
+    const int ns = S.n_scales = (int)ce_plan_ssim2_scales(b->w, b->h, CE_MAX_SCALES, sw, sh);
     if (ns == 0) return CE_OK;
-    // all or nothing: a partial working set (an allocation failed half-way) is released, so that a retry
-    // after the caller has made room starts clean instead of overwriting live pointers
-    const int rc = ssim2_allocate(b);
-    if (rc != CE_OK) {
-        const std::string why = b->ctx->err;
-        ce_ssim2_free(b);
-        (void)hipGetLastError();
-        b->ctx->err = why;
-        return rc;
+    const size_t slots = (size_t)b->max_refs + b->max_pairs;
+    int rc = CE_OK;
+    for (int s = 0; s < ns; s++) {
+        ce_plane_geom &d = S.lvl[s];
+        d.w = sw[s];
+        d.h = sh[s];
+        d.pitch = ((d.w + HB_CW - 1) / HB_CW) * HB_CW + HB_CW;
+        d.plane = (size_t)d.pitch * (((size_t)d.h + HB_ROWS - 1) / HB_ROWS * HB_ROWS);
     }
-    b->ssim2_ready = true;
+    for (int s = 1; s < ns && rc == CE_OK; s++)  // level 0 is read straight from the u8 slabs
+        rc = S.lin[s].alloc(ctx, slots * 3 * S.lvl[s].plane);
+    for (int s = 0; s < ns && rc == CE_OK; s++) {
+        const ce_plane_geom &d = S.lvl[s];
+        rc = S.xyb[s].alloc(ctx, slots * 3 * d.plane);
+        if (rc == CE_OK) rc = S.hbuf[s].alloc(ctx, (size_t)b->max_pairs * 3 * CE_SSIM2_STREAMS * d.plane);
+        if (rc == CE_OK && s < 2) rc = S.ev_prep[s].create(ctx);
+        if (rc == CE_OK && s < 2) rc = S.ev_done[s].create(ctx);
+    }
+    // level 0's passes; the other levels follow the front end
+    if (rc == CE_OK && !(S.l0_stream = ce_ctx_aux_stream(ctx, ce_ctx::AUX_SSIM2_L0))) rc = CE_ERR_BACKEND;
+    S.max_vblocks = (S.lvl[0].w + kColsPerBlock - 1) / kColsPerBlock;
+    if (rc == CE_OK) rc = S.partials.alloc(ctx, (size_t)b->max_pairs * CE_MAX_SCALES * 3 * S.max_vblocks * 6);
+    if (rc == CE_OK) rc = S.avg.alloc(ctx, (size_t)b->max_pairs * CE_MAX_SCALES * 18);
+    if (rc != CE_OK) return rc;  // S releases what it got: a retry after the caller has made room starts clean
+    b->s2 = std::move(S);
     return CE_OK;
 }
 
@@ -967,32 +917,30 @@ int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
     int rc = ce_ssim2_prepare(b);
     if (rc != CE_OK) return rc;
     // CE_FLAG_SSIMULACRA2_MAPS: every scale's nine maps of all pairs, allocated by the first launch that asks for them (one
-    // allocation: there is nothing to undo if it fails) and kept until the working set is freed
+    // allocation: there is nothing to undo if it fails) and kept with the working set
     ssim2_map_table maps{};
     if (store_maps) {
-        if (!b->s2_map) {
+        if (!b->s2.map) {
             size_t total = 0;
-            for (int s = 0; s < b->n_scales; s++) total += (size_t)b->max_pairs * 9 * b->sd[s].plane;
-            if (hipMalloc(&b->s2_map, total * sizeof(float)) != hipSuccess) {
-                b->s2_map = nullptr;
-                (void)hipGetLastError();
+            for (int s = 0; s < b->s2.n_scales; s++) total += (size_t)b->max_pairs * 9 * b->s2.lvl[s].plane;
+            if (b->s2.map.alloc((ce_ctx *)nullptr, total) != CE_OK) {
                 ctx->err = "out of device memory for the SSIMULACRA2 maps";
                 return CE_ERR_BACKEND;
             }
             size_t off = 0;
-            for (int s = 0; s < b->n_scales; s++) {
-                b->s2_map_lvl[s] = b->s2_map + off;
-                off += (size_t)b->max_pairs * 9 * b->sd[s].plane;
+            for (int s = 0; s < b->s2.n_scales; s++) {
+                b->s2.map_lvl[s] = b->s2.map + off;
+                off += (size_t)b->max_pairs * 9 * b->s2.lvl[s].plane;
             }
         }
-        for (int s = 0; s < b->n_scales; s++) maps.lvl[s] = b->s2_map_lvl[s];
+        for (int s = 0; s < b->s2.n_scales; s++) maps.lvl[s] = b->s2.map_lvl[s];
     }
     rg_consts rg;
     ce_ssim2_recursive_gaussian(rg.mul_in, rg.mul_prev);
     const uint32_t n_slots = n_refs_used + n_pairs;
     // Ssimulacra2Reference semantics (crates/codec-iter/src/eval.rs:138-149): a batch keeps the references' XYB pyramid
     // between launches, so the front end then only runs over the distorted slots
-    const int levels = std::min(b->n_scales, b->debug_max_scales);
+    const int levels = std::min(b->s2.n_scales, b->debug_max_scales);
     const bool cached = b->refs.reuse(CE_REF_SSIM2, d_refs, n_refs_used, (uint64_t)levels);
     const uint32_t z0 = cached ? n_refs_used : 0;
     // Which blur passes (ce_plan.h: ce_plan_ssim2_ref_blur)?  Split path: mu1 and s11 of every reference are final planes of
@@ -1004,15 +952,15 @@ int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
     if (!cached) b->refs.of[CE_REF_SSIM2_BLUR].invalidate();
     const bool blur_covered = b->refs.keep && b->refs.of[CE_REF_SSIM2_BLUR].covers(d_refs, n_refs_used, (uint64_t)levels);
     int blur_path = ce_plan_ssim2_ref_blur(ref_blur_enabled, b->refs.keep, b->ref_handle, cached, blur_covered, n_pairs, n_refs_used);
-    // the build's scratch - the references' row-blurred streams, [ref][channel][2][plane] - lives at the start of d_hbuf: it
+    // the build's scratch - the references' row-blurred streams, [ref][channel][2][plane] - lives at the start of hbuf: it
     // fits whenever the rule builds (6 planes per reference against 15 per pair), and is checked all the same
     if (blur_path == CE_SSIM2_BLUR_SPLIT_BUILD && (size_t)n_refs_used * 2 > (size_t)b->max_pairs * CE_SSIM2_STREAMS) blur_path = CE_SSIM2_BLUR_TODAY;
     if (blur_path == CE_SSIM2_BLUR_SPLIT_BUILD && !ssim2_ref_blur_allocate(b)) blur_path = CE_SSIM2_BLUR_TODAY;  // no room: as before
     const bool split = blur_path != CE_SSIM2_BLUR_TODAY, build_ref = blur_path == CE_SSIM2_BLUR_SPLIT_BUILD;
     if (build_ref) b->refs.of[CE_REF_SSIM2_BLUR].invalidate();  // a launch that fails half way leaves nothing valid
-    b->s2_split_last = split;
+    b->s2.split_last = split;
     ssim2_ref_table ref_h{}, ref_blur{};
-    for (int s = 0; s < b->n_scales; s++) ref_h.lvl[s] = b->d_hbuf[s], ref_blur.lvl[s] = b->s2_ref_blur[s];
+    for (int s = 0; s < b->s2.n_scales; s++) ref_h.lvl[s] = b->s2.hbuf[s], ref_blur.lvl[s] = b->s2.ref_blur[s];
     using hblur_fn = void (*)(const float *, const uint32_t *, float *, uint32_t, uint32_t, uint32_t, size_t, uint32_t,
                               rg_consts, lvl_table, const uint2 *, const uint32_t *);
     using vblur_fn = void (*)(const float *, const float *, const uint32_t *, double *, uint32_t, uint32_t, uint32_t,
@@ -1033,64 +981,64 @@ int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
     // default) and a stream that shares a hardware queue with a busy one waits for it - with three streams per batch
     // the second shape bucket's front end sat behind the first bucket's kernels for most of a step.
     // In the serial profiling mode everything stays on one stream so that per-kernel times do not overlap.
-    hipStream_t s0 = ctx->prof_serial ? CE_STREAM(ctx) : b->lvl_stream[0];
+    hipStream_t s0 = ctx->prof_serial ? CE_STREAM(ctx) : b->s2.l0_stream;
     hipStream_t s1 = CE_STREAM(ctx);
     lvl_table tab{};
     lvl_table tab_v{};
     for (int s = 0; s < levels; s++) {
-        const ce_scale_dims &d = b->sd[s];
+        const ce_plane_geom &d = b->s2.lvl[s];
         const bool has_next = s + 1 < levels;
-        const ce_scale_dims &nd = b->sd[has_next ? s + 1 : s];
+        const ce_plane_geom &nd = b->s2.lvl[has_next ? s + 1 : s];
         const dim3 quad_grid(((d.w + 1) / 2 + 63) / 64, ((d.h + 1) / 2 + 3) / 4, n_slots - z0);
         if (s == 0 && b->linear)
             CE_LAUNCH(ctx, "ssim2_prep_lin", k_ssim2_prep<CE_SRC_LIN>, quad_grid, dim3(256), 0, d_refs, b->d_tests, (const float *)nullptr,
-                      (const float *)nullptr, (const float *)nullptr, b->d_xyb[0], b->d_lin[1], d.w, d.h, d.pitch, d.plane, nd.pitch,
+                      (const float *)nullptr, (const float *)nullptr, b->s2.xyb[0], b->s2.lin[1], d.w, d.h, d.pitch, d.plane, nd.pitch,
                       nd.plane, has_next ? 1 : 0, b->img_bytes, n_refs_used, b->max_refs, z0);
         else if (s == 0 && b->depth[0])
             CE_LAUNCH(ctx, "ssim2_prep_u16", k_ssim2_prep<CE_SRC_U16>, quad_grid, dim3(256), 0, d_refs, b->d_tests, b->deep_lut[0][0],
-                      b->deep_lut[0][1], (const float *)nullptr, b->d_xyb[0], b->d_lin[1], d.w, d.h, d.pitch, d.plane, nd.pitch,
+                      b->deep_lut[0][1], (const float *)nullptr, b->s2.xyb[0], b->s2.lin[1], d.w, d.h, d.pitch, d.plane, nd.pitch,
                       nd.plane, has_next ? 1 : 0, b->img_bytes, n_refs_used, b->max_refs, z0);
         else if (s == 0)
             CE_LAUNCH(ctx, "ssim2_prep_u8", k_ssim2_prep<CE_SRC_U8>, quad_grid, dim3(256), 0, d_refs, b->d_tests, ctx->d_lut_ssim2, ctx->d_lut_ssim2,
-                      (const float *)nullptr, b->d_xyb[0], b->d_lin[1], d.w, d.h, d.pitch, d.plane, nd.pitch, nd.plane,
+                      (const float *)nullptr, b->s2.xyb[0], b->s2.lin[1], d.w, d.h, d.pitch, d.plane, nd.pitch, nd.plane,
                       has_next ? 1 : 0, b->img_bytes, n_refs_used, b->max_refs, z0);
         else
             CE_LAUNCH(ctx, "ssim2_prep", k_ssim2_prep<CE_SRC_F32>, quad_grid, dim3(256), 0, d_refs, b->d_tests, ctx->d_lut_ssim2, ctx->d_lut_ssim2,
-                      (const float *)b->d_lin[s], b->d_xyb[s], b->d_lin[has_next ? s + 1 : s], d.w, d.h, d.pitch, d.plane,
+                      (const float *)b->s2.lin[s], b->s2.xyb[s], b->s2.lin[has_next ? s + 1 : s], d.w, d.h, d.pitch, d.plane,
                       nd.pitch, nd.plane, has_next ? 1 : 0, b->img_bytes, n_refs_used, b->max_refs, z0);
         const uint32_t hblk = (d.h + HB_ROWS - 1) / HB_ROWS, vblk = (d.w + kColsPerBlock - 1) / kColsPerBlock;
         g.npix[s] = d.w * d.h;
         g.nblk[s] = vblk;
         if (s == 0) {
             if (s0 != CE_STREAM(ctx)) {
-                CE_HIP(ctx, hipEventRecord(b->ev_prep[0], CE_STREAM(ctx)));
-                CE_HIP(ctx, hipStreamWaitEvent(s0, b->ev_prep[0], 0));
+                CE_HIP(ctx, hipEventRecord(b->s2.ev_prep[0], CE_STREAM(ctx)));
+                CE_HIP(ctx, hipStreamWaitEvent(s0, b->s2.ev_prep[0], 0));
             }
-            if ((rc = build_pass_list(b, n_pairs, hblk, &b->work_h)) != CE_OK) return rc;
-            if ((rc = build_pass_list(b, n_pairs, vblk, &b->work_v)) != CE_OK) return rc;
+            if ((rc = build_pass_list(b, n_pairs, hblk, &b->s2.work_h)) != CE_OK) return rc;
+            if ((rc = build_pass_list(b, n_pairs, vblk, &b->s2.work_v)) != CE_OK) return rc;
             if (build_ref) {  // in front of the pair passes, on their stream; plain 3-D grids over the reference slots
-                CE_LAUNCH_ON(ctx, s0, "ssim2_ref_hblur_L0", h_l0_ref, dim3(hblk, 3, n_refs_used), dim3(HB_THREADS), 0, b->d_xyb[0], b->d_pair_ref,
-                             b->d_hbuf[0], d.w, d.h, d.pitch, d.plane, b->max_refs, rg, tab, (const uint2 *)nullptr,
+                CE_LAUNCH_ON(ctx, s0, "ssim2_ref_hblur_L0", h_l0_ref, dim3(hblk, 3, n_refs_used), dim3(HB_THREADS), 0, b->s2.xyb[0], b->d_pair_ref,
+                             b->s2.hbuf[0], d.w, d.h, d.pitch, d.plane, b->max_refs, rg, tab, (const uint2 *)nullptr,
                              (const uint32_t *)b->d_pair_first);
                 CE_LAUNCH_ON(ctx, s0, "ssim2_ref_vblur_L0", k_ssim2_ref_vblur<0>, dim3(vblk, 3, n_refs_used), dim3(64), 0,
-                             (const float *)b->d_hbuf[0], b->s2_ref_blur[0], d.w, d.h, d.pitch, d.plane, rg, tab, ref_h, ref_blur);
+                             (const float *)b->s2.hbuf[0], b->s2.ref_blur[0], d.w, d.h, d.pitch, d.plane, rg, tab, ref_h, ref_blur);
             }
-            CE_LAUNCH_ON(ctx, s0, "ssim2_hblur_L0", h_l0, dim3(b->work_h.len), dim3(HB_THREADS), 0, b->d_xyb[0], b->d_pair_ref,
-                         b->d_hbuf[0], d.w, d.h, d.pitch, d.plane, b->max_refs, rg, tab, (const uint2 *)b->work_h.d,
+            CE_LAUNCH_ON(ctx, s0, "ssim2_hblur_L0", h_l0, dim3(b->s2.work_h.len), dim3(HB_THREADS), 0, b->s2.xyb[0], b->d_pair_ref,
+                         b->s2.hbuf[0], d.w, d.h, d.pitch, d.plane, b->max_refs, rg, tab, (const uint2 *)b->s2.work_h.d,
                          (const uint32_t *)b->d_pair_first);
 #define CE_VBLUR_L0_ARGS                                                                                                   \
-    b->d_hbuf[0], b->d_xyb[0], b->d_pair_ref, b->d_partials, d.w, d.h, d.pitch, d.plane, b->max_refs, 0u, b->max_vblocks, rg, tab, \
-        (const uint2 *)b->work_v.d, (const uint32_t *)b->d_pair_first, maps, ref_blur
+    b->s2.hbuf[0], b->s2.xyb[0], b->d_pair_ref, b->s2.partials, d.w, d.h, d.pitch, d.plane, b->max_refs, 0u, b->s2.max_vblocks, rg, tab, \
+        (const uint2 *)b->s2.work_v.d, (const uint32_t *)b->d_pair_first, maps, ref_blur
             if (split && store_maps)
-                CE_LAUNCH_ON(ctx, s0, "ssim2_vblur_ssim_map_L0", vr_l0_map, dim3(b->work_v.len), dim3(64), 0, CE_VBLUR_L0_ARGS);
+                CE_LAUNCH_ON(ctx, s0, "ssim2_vblur_ssim_map_L0", vr_l0_map, dim3(b->s2.work_v.len), dim3(64), 0, CE_VBLUR_L0_ARGS);
             else if (split)
-                CE_LAUNCH_ON(ctx, s0, "ssim2_vblur_ssim_L0", vr_l0, dim3(b->work_v.len), dim3(64), 0, CE_VBLUR_L0_ARGS);
+                CE_LAUNCH_ON(ctx, s0, "ssim2_vblur_ssim_L0", vr_l0, dim3(b->s2.work_v.len), dim3(64), 0, CE_VBLUR_L0_ARGS);
             else if (store_maps)  // the same pass, also writing the maps: a profiler name of its own
-                CE_LAUNCH_ON(ctx, s0, "ssim2_vblur_ssim_map_L0", v_l0_map, dim3(b->work_v.len), dim3(64), 0, CE_VBLUR_L0_ARGS);
+                CE_LAUNCH_ON(ctx, s0, "ssim2_vblur_ssim_map_L0", v_l0_map, dim3(b->s2.work_v.len), dim3(64), 0, CE_VBLUR_L0_ARGS);
             else
-                CE_LAUNCH_ON(ctx, s0, "ssim2_vblur_ssim_L0", v_l0, dim3(b->work_v.len), dim3(64), 0, CE_VBLUR_L0_ARGS);
+                CE_LAUNCH_ON(ctx, s0, "ssim2_vblur_ssim_L0", v_l0, dim3(b->s2.work_v.len), dim3(64), 0, CE_VBLUR_L0_ARGS);
 #undef CE_VBLUR_L0_ARGS
-            if (s0 != CE_STREAM(ctx)) CE_HIP(ctx, hipEventRecord(b->ev_done[0], s0));
+            if (s0 != CE_STREAM(ctx)) CE_HIP(ctx, hipEventRecord(b->s2.ev_done[0], s0));
         } else {
             const uint32_t l = tab.n++;
             tab_v.n = tab.n;
@@ -1101,48 +1049,48 @@ int ce_launch_ssim2(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_used, ui
             tab.h[l] = tab_v.h[l] = d.h;
             tab.pitch[l] = tab_v.pitch[l] = d.pitch;
             tab.plane[l] = tab_v.plane[l] = d.plane;
-            tab.xyb[l] = tab_v.xyb[l] = b->d_xyb[s];
-            tab.hbuf[l] = tab_v.hbuf[l] = b->d_hbuf[s];
+            tab.xyb[l] = tab_v.xyb[l] = b->s2.xyb[s];
+            tab.hbuf[l] = tab_v.hbuf[l] = b->s2.hbuf[s];
         }
     }
     if (tab.n) {
         if (s1 != CE_STREAM(ctx)) {
-            CE_HIP(ctx, hipEventRecord(b->ev_prep[1], CE_STREAM(ctx)));
-            CE_HIP(ctx, hipStreamWaitEvent(s1, b->ev_prep[1], 0));
+            CE_HIP(ctx, hipEventRecord(b->s2.ev_prep[1], CE_STREAM(ctx)));
+            CE_HIP(ctx, hipStreamWaitEvent(s1, b->s2.ev_prep[1], 0));
         }
-        if ((rc = build_pass_list(b, n_pairs, tab.blk_end[tab.n - 1], &b->work_ht)) != CE_OK) return rc;
-        if ((rc = build_pass_list(b, n_pairs, tab_v.blk_end[tab_v.n - 1], &b->work_vt)) != CE_OK) return rc;
+        if ((rc = build_pass_list(b, n_pairs, tab.blk_end[tab.n - 1], &b->s2.work_ht)) != CE_OK) return rc;
+        if ((rc = build_pass_list(b, n_pairs, tab_v.blk_end[tab_v.n - 1], &b->s2.work_vt)) != CE_OK) return rc;
         if (build_ref) {
-            // the row pass writes to tab.hbuf[l]: the scratch at the start of each level's d_hbuf
+            // the row pass writes to tab.hbuf[l]: the scratch at the start of each level's hbuf
             CE_LAUNCH_ON(ctx, s1, "ssim2_ref_hblur_L1-5", h_tail_ref, dim3(tab.blk_end[tab.n - 1], 3, n_refs_used), dim3(HB_THREADS), 0,
                          (const float *)nullptr, b->d_pair_ref, (float *)nullptr, 0u, 0u, 0u, (size_t)0, b->max_refs, rg, tab,
                          (const uint2 *)nullptr, (const uint32_t *)b->d_pair_first);
             CE_LAUNCH_ON(ctx, s1, "ssim2_ref_vblur_L1-5", k_ssim2_ref_vblur<-1>, dim3(tab_v.blk_end[tab_v.n - 1], 3, n_refs_used), dim3(64), 0,
                          (const float *)nullptr, (float *)nullptr, 0u, 0u, 0u, (size_t)0, rg, tab_v, ref_h, ref_blur);
         }
-        CE_LAUNCH_ON(ctx, s1, "ssim2_hblur_L1-5", h_tail, dim3(b->work_ht.len), dim3(HB_THREADS), 0,
+        CE_LAUNCH_ON(ctx, s1, "ssim2_hblur_L1-5", h_tail, dim3(b->s2.work_ht.len), dim3(HB_THREADS), 0,
                      (const float *)nullptr, b->d_pair_ref, (float *)nullptr, 0u, 0u, 0u, (size_t)0, b->max_refs, rg, tab,
-                     (const uint2 *)b->work_ht.d, (const uint32_t *)b->d_pair_first);
+                     (const uint2 *)b->s2.work_ht.d, (const uint32_t *)b->d_pair_first);
 #define CE_VBLUR_TAIL_ARGS                                                                                                  \
-    (const float *)nullptr, (const float *)nullptr, b->d_pair_ref, b->d_partials, 0u, 0u, 0u, (size_t)0, b->max_refs, 0u,        \
-        b->max_vblocks, rg, tab_v, (const uint2 *)b->work_vt.d, (const uint32_t *)b->d_pair_first, maps, ref_blur
+    (const float *)nullptr, (const float *)nullptr, b->d_pair_ref, b->s2.partials, 0u, 0u, 0u, (size_t)0, b->max_refs, 0u,        \
+        b->s2.max_vblocks, rg, tab_v, (const uint2 *)b->s2.work_vt.d, (const uint32_t *)b->d_pair_first, maps, ref_blur
         if (split && store_maps)
-            CE_LAUNCH_ON(ctx, s1, "ssim2_vblur_ssim_map_L1-5", vr_tail_map, dim3(b->work_vt.len), dim3(64), 0, CE_VBLUR_TAIL_ARGS);
+            CE_LAUNCH_ON(ctx, s1, "ssim2_vblur_ssim_map_L1-5", vr_tail_map, dim3(b->s2.work_vt.len), dim3(64), 0, CE_VBLUR_TAIL_ARGS);
         else if (split)
-            CE_LAUNCH_ON(ctx, s1, "ssim2_vblur_ssim_L1-5", vr_tail, dim3(b->work_vt.len), dim3(64), 0, CE_VBLUR_TAIL_ARGS);
+            CE_LAUNCH_ON(ctx, s1, "ssim2_vblur_ssim_L1-5", vr_tail, dim3(b->s2.work_vt.len), dim3(64), 0, CE_VBLUR_TAIL_ARGS);
         else if (store_maps)
-            CE_LAUNCH_ON(ctx, s1, "ssim2_vblur_ssim_map_L1-5", v_tail_map, dim3(b->work_vt.len), dim3(64), 0, CE_VBLUR_TAIL_ARGS);
+            CE_LAUNCH_ON(ctx, s1, "ssim2_vblur_ssim_map_L1-5", v_tail_map, dim3(b->s2.work_vt.len), dim3(64), 0, CE_VBLUR_TAIL_ARGS);
         else
-            CE_LAUNCH_ON(ctx, s1, "ssim2_vblur_ssim_L1-5", v_tail, dim3(b->work_vt.len), dim3(64), 0, CE_VBLUR_TAIL_ARGS);
+            CE_LAUNCH_ON(ctx, s1, "ssim2_vblur_ssim_L1-5", v_tail, dim3(b->s2.work_vt.len), dim3(64), 0, CE_VBLUR_TAIL_ARGS);
 #undef CE_VBLUR_TAIL_ARGS
-        if (s1 != CE_STREAM(ctx)) CE_HIP(ctx, hipEventRecord(b->ev_done[1], s1));
+        if (s1 != CE_STREAM(ctx)) CE_HIP(ctx, hipEventRecord(b->s2.ev_done[1], s1));
     }
     if (s0 != CE_STREAM(ctx)) {
-        CE_HIP(ctx, hipStreamWaitEvent(CE_STREAM(ctx), b->ev_done[0], 0));
-        if (tab.n && s1 != CE_STREAM(ctx)) CE_HIP(ctx, hipStreamWaitEvent(CE_STREAM(ctx), b->ev_done[1], 0));
+        CE_HIP(ctx, hipStreamWaitEvent(CE_STREAM(ctx), b->s2.ev_done[0], 0));
+        if (tab.n && s1 != CE_STREAM(ctx)) CE_HIP(ctx, hipStreamWaitEvent(CE_STREAM(ctx), b->s2.ev_done[1], 0));
     }
-    CE_LAUNCH(ctx, "ssim2_finalize", k_ssim2_finalize, dim3(n_pairs), dim3(128), 0, b->d_partials, b->d_avg,
-              b->d_scores, (uint32_t)levels, b->max_vblocks, g);
+    CE_LAUNCH(ctx, "ssim2_finalize", k_ssim2_finalize, dim3(n_pairs), dim3(128), 0, b->s2.partials, b->s2.avg,
+              b->d_scores, (uint32_t)levels, b->s2.max_vblocks, g);
     CE_HIP(ctx, hipGetLastError());
     if (!cached) b->refs.built(CE_REF_SSIM2, d_refs, n_refs_used, (uint64_t)levels);
     if (build_ref) b->refs.built(CE_REF_SSIM2_BLUR, d_refs, n_refs_used, (uint64_t)levels);
@@ -1172,15 +1120,14 @@ int ce_ssim2_read_maps(ce_batch *b, uint32_t scale, uint32_t channel, uint32_t k
 {
     ce_ctx *ctx = b->ctx;
     if (norms) {  // d_avg is [pair][scale][channel][6]; the kind's (mean, 4-norm) are entries 2 kind, 2 kind + 1
-        CE_HIP(ctx, hipMemcpy2DAsync(norms, 2 * sizeof(double), b->d_avg + (size_t)first * CE_MAX_SCALES * 18 + scale * 18 + channel * 6 + 2 * kind,
+        CE_HIP(ctx, hipMemcpy2DAsync(norms, 2 * sizeof(double), b->s2.avg + (size_t)first * CE_MAX_SCALES * 18 + scale * 18 + channel * 6 + 2 * kind,
                                      CE_MAX_SCALES * 18 * sizeof(double), 2 * sizeof(double), count, hipMemcpyDeviceToHost, ctx->stream));
         if (!maps) CE_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (!maps) return CE_OK;
-    const ce_scale_dims &d = b->sd[scale];
-    return ce_read_map_cells(b, "ssim2_block_max", b->s2_map_lvl[scale] + (size_t)(channel * 3 + kind) * d.plane,
-                             ce_map_geom{d.w, d.h, d.pitch, 9 * d.plane}, first, count, block, false, &b->s2_cells, &b->s2_cells_cap,
-                             maps);
+    const ce_plane_geom &d = b->s2.lvl[scale];
+    return ce_read_map_cells(b, "ssim2_block_max", b->s2.map_lvl[scale] + (size_t)(channel * 3 + kind) * d.plane,
+                             ce_plane_geom{d.w, d.h, d.pitch, 9 * d.plane}, first, count, block, false, b->s2.cells, maps);
 }
 
 // debug: resident blocks per CU the runtime computes for the two blur kernels (which: 0 = row pass, 1 = column pass)
