@@ -722,6 +722,28 @@ impl HipMetrics {
         Ok(out)
     }
 
+    /// `ce_eval_pair_msssim`: SSIM (`levels` 1) and MS-SSIM (5) of one pair of packed RGB8 on the encoded sample values.
+    pub fn ms_ssim(&mut self, reference: &[u8], test: &[u8], width: u32, height: u32, levels: u32) -> Result<sys::ce_msssim_scores, HipError> {
+        let mut out = sys::ce_msssim_scores::default();
+        let rc = unsafe {
+            sys::ce_eval_pair_msssim(self.ctx, reference.as_ptr(), reference.len(), test.as_ptr(), test.len(), width, height, levels, &mut out)
+        };
+        self.check(rc, width, height, test.len())?;
+        Ok(out)
+    }
+
+    /// `ce_eval_pair_msssim_deep`: the same for packed u16 RGB of `depth` bits (8, 10, 12 or 16) on both sides.
+    pub fn ms_ssim_deep(&mut self, reference: &[u16], test: &[u16], depth: u32, width: u32, height: u32, levels: u32)
+                        -> Result<sys::ce_msssim_scores, HipError> {
+        let mut out = sys::ce_msssim_scores::default();
+        let rc = unsafe {
+            sys::ce_eval_pair_msssim_deep(self.ctx, reference.as_ptr(), reference.len() * 2, test.as_ptr(), test.len() * 2, depth, width,
+                                          height, levels, &mut out)
+        };
+        self.check(rc, width, height, test.len() * 2)?;
+        Ok(out)
+    }
+
     /// `ce_eval_pair_delta_e_itp_map`: where one pair of packed f32 RGB differs - see `HipBatch::delta_e_itp_map`.
     pub fn delta_e_itp_map(&mut self, reference: &[f32], test: &[f32], width: u32, height: u32, depth: u32, white_nits: f32, block: u32,
                            want_map: bool, thresholds_q20: &[u32]) -> Result<DeltaEItpMaps, HipError> {
@@ -775,6 +797,21 @@ pub fn pq_code_thresholds(depth: u32, white_nits: f32) -> Option<Vec<f32>> {
     let mut out = vec![0f32; (1usize << depth) - 1];
     let rc = unsafe { sys::ce_pq_code_thresholds(depth, white_nits, out.as_mut_ptr(), out.len()) };
     (rc == sys::CE_OK).then_some(out)
+}
+
+/// `ce_msssim_window`: the eleven literals of the SSIM / MS-SSIM window; a pure host function.
+pub fn msssim_window() -> [f64; 11] {
+    let mut g = [0f64; 11];
+    unsafe { sys::ce_msssim_window(g.as_mut_ptr()) };
+    g
+}
+
+/// `ce_msssim_levels`: the (width, height) of every level of SSIM (`levels` 1) or MS-SSIM (5) on a width x height image; `None`
+/// for other `levels` and for an image too small.  A pure host function.
+pub fn msssim_levels(width: u32, height: u32, levels: u32) -> Option<Vec<(u32, u32)>> {
+    let (mut n, mut w, mut h) = (0u32, [0u32; 5], [0u32; 5]);
+    let rc = unsafe { sys::ce_msssim_levels(width, height, levels, &mut n, w.as_mut_ptr(), h.as_mut_ptr()) };
+    (rc == sys::CE_OK).then(|| (0..n as usize).map(|l| (w[l], h[l])).collect())
 }
 
 /// `ce_hdr_fidelity_matrices`: the two row-major 3 x 3 matrices the HDR fidelity kernel is handed - BT.2020 <- sRGB primaries,
@@ -1163,6 +1200,15 @@ impl HipBatch<'_> {
     pub fn hdr_fidelity(&mut self, n_pairs: u32, depth: u32, white_nits: f32) -> Result<Vec<sys::ce_hdr_scores>, HipError> {
         let mut out = vec![sys::ce_hdr_scores::default(); n_pairs as usize];
         let rc = unsafe { sys::ce_batch_hdr_fidelity(self.handle, n_pairs, depth, white_nits, out.as_mut_ptr()) };
+        self.check(rc, 0)?;
+        Ok(out)
+    }
+
+    /// `ce_batch_msssim`: SSIM (`levels` 1) and MS-SSIM (5) of pairs `[0, n_pairs)` of an RGB8 or equal-depth deep batch on the
+    /// encoded sample values; returns once the scores are on the host.
+    pub fn ms_ssim(&mut self, n_pairs: u32, levels: u32) -> Result<Vec<sys::ce_msssim_scores>, HipError> {
+        let mut out = vec![sys::ce_msssim_scores::default(); n_pairs as usize];
+        let rc = unsafe { sys::ce_batch_msssim(self.handle, n_pairs, levels, out.as_mut_ptr()) };
         self.check(rc, 0)?;
         Ok(out)
     }

@@ -204,6 +204,22 @@ pub struct ce_hdr_scores {
     pub itp_max_q20: u64,
 }
 
+/// `ce_msssim_scores` (352 bytes): SSIM and MS-SSIM of one pair on the encoded sample values, with the exact integers they are
+/// finished from - per level and channel the sums of the per-position values in units of 2^-32 - and the positions of a level.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct ce_msssim_scores {
+    pub ms_ssim: c_double,
+    pub ssim: c_double,
+    pub ms_ssim_rgb: [c_double; 3],
+    pub ssim_rgb: [c_double; 3],
+    pub ssim_q: [[i64; 3]; 5],
+    pub cs_q: [[i64; 3]; 5],
+    pub n: [u64; 5],
+    pub n_levels: u32,
+    pub reserved: u32,
+}
+
 /// `ce_scores` (40 bytes): a score is meaningful iff its bit is set in `valid`.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -498,6 +514,13 @@ extern "C" {
                                      out: *mut ce_hdr_scores) -> c_int;
     pub fn ce_pq_code_thresholds(depth: u32, white_nits: c_float, out: *mut c_float, n: usize) -> c_int;
     pub fn ce_hdr_fidelity_matrices(a: *mut c_float, b: *mut c_float) -> c_int;
+    pub fn ce_batch_msssim(b: *mut ce_batch, n_pairs: u32, levels: u32, out: *mut ce_msssim_scores) -> c_int;
+    pub fn ce_eval_pair_msssim(ctx: *mut ce_ctx, reference: *const u8, reference_len: usize, test: *const u8, test_len: usize, width: u32,
+                               height: u32, levels: u32, out: *mut ce_msssim_scores) -> c_int;
+    pub fn ce_eval_pair_msssim_deep(ctx: *mut ce_ctx, reference: *const u16, reference_len: usize, test: *const u16, test_len: usize,
+                                    depth: u32, width: u32, height: u32, levels: u32, out: *mut ce_msssim_scores) -> c_int;
+    pub fn ce_msssim_window(out: *mut c_double) -> c_int;
+    pub fn ce_msssim_levels(w: u32, h: u32, levels: u32, n_levels: *mut u32, level_w: *mut u32, level_h: *mut u32) -> c_int;
     pub fn ce_batch_delta_e_itp_map(b: *mut ce_batch, first: u32, count: u32, depth: u32, white_nits: c_float, block: u32, map: *mut u32,
                                     map_len: usize, thresholds_q20: *const u32, n_thresholds: u32, over: *mut u64) -> c_int;
     pub fn ce_eval_pair_delta_e_itp_map(ctx: *mut ce_ctx, reference: *const c_float, reference_len: usize, test: *const c_float,

@@ -189,6 +189,12 @@ class CeHdrScores(C.Structure):
                 ("pq_sse", C.c_uint64), ("itp_sum_q20", C.c_uint64), ("itp_max_q20", C.c_uint64)]
 
 
+class CeMsssimScores(C.Structure):
+    _fields_ = [("ms_ssim", C.c_double), ("ssim", C.c_double), ("ms_ssim_rgb", C.c_double * 3), ("ssim_rgb", C.c_double * 3),
+                ("ssim_q", (C.c_int64 * 3) * 5), ("cs_q", (C.c_int64 * 3) * 5), ("n", C.c_uint64 * 5), ("n_levels", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class CodecEvalError(RuntimeError):
     """Mirrors codec_eval::Error for this path (src/error.rs:31-49)."""
 
@@ -340,6 +346,11 @@ _PROTOTYPES = [
     ("ce_hdr_fidelity_matrices", _i, [_vp, _vp]),
     ("ce_batch_delta_e_itp_map", _i, [_vp, _u32, _u32, _u32, _f32, _u32, _vp, _sz, _vp, _u32, _vp]),
     ("ce_eval_pair_delta_e_itp_map", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _f32, _u32, _vp, _sz, _vp, _u32, _vp]),
+    ("ce_batch_msssim", _i, [_vp, _u32, _u32, C.POINTER(CeMsssimScores)]),
+    ("ce_eval_pair_msssim", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, C.POINTER(CeMsssimScores)]),
+    ("ce_eval_pair_msssim_deep", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, C.POINTER(CeMsssimScores)]),
+    ("ce_msssim_window", _i, [_vp]),
+    ("ce_msssim_levels", _i, [_u32, _u32, _u32, _vp, _vp, _vp]),
     ("ce_icc_describe", _i, [_vp, _sz, C.POINTER(CeIccDescription)]),
     ("ce_icc_build_matrix", _i, [_vp, _sz, _vp]),
     ("ce_icc_build_tables", _i, [_vp, _sz, _u32, _vp, _sz]),
@@ -797,6 +808,42 @@ class HdrFidelity:
     @staticmethod
     def from_c(s: CeHdrScores) -> "HdrFidelity":
         return HdrFidelity(s.pq_psnr, s.delta_e_itp_mean, s.delta_e_itp_max, int(s.pq_sse), int(s.itp_sum_q20), int(s.itp_max_q20))
+
+
+def msssim_window() -> np.ndarray:
+    """The 11-tap Gaussian window of SSIM / MS-SSIM (ce_msssim_window), float64: the library's literals."""
+    out = np.empty(11, np.float64)
+    _host_check(lib().ce_msssim_window(out.ctypes.data))
+    return out
+
+
+def msssim_levels(width: int, height: int, levels: int = 5) -> List[Tuple[int, int]]:
+    """The (width, height) of every level of SSIM (levels = 1) or MS-SSIM (5) on a width x height image (ce_msssim_levels);
+    raises for other `levels` and for an image too small."""
+    n, w, h = np.zeros(1, np.uint32), np.zeros(5, np.uint32), np.zeros(5, np.uint32)
+    _host_check(lib().ce_msssim_levels(width, height, levels, n.ctypes.data, w.ctypes.data, h.ctypes.data))
+    return [(int(w[l]), int(h[l])) for l in range(int(n[0]))]
+
+
+@dataclass(frozen=True)
+class MsSsim:
+    """SSIM and MS-SSIM of one pair on the encoded sample values (ce_msssim_scores): the means over R, G, B, the per-channel
+    values, and the exact integers they are finished from - per level and channel the sums of the per-position SSIM and
+    contrast-structure values in units of 2^-32 - with the positions n of every level.  ms_ssim is NaN with one level."""
+    ms_ssim: float
+    ssim: float
+    ms_ssim_rgb: Tuple[float, float, float]
+    ssim_rgb: Tuple[float, float, float]
+    ssim_q: Tuple[Tuple[int, int, int], ...]
+    cs_q: Tuple[Tuple[int, int, int], ...]
+    n: Tuple[int, ...]
+    n_levels: int
+
+    @staticmethod
+    def from_c(s: CeMsssimScores) -> "MsSsim":
+        return MsSsim(s.ms_ssim, s.ssim, tuple(s.ms_ssim_rgb), tuple(s.ssim_rgb),
+                      tuple(tuple(int(v) for v in s.ssim_q[l]) for l in range(5)),
+                      tuple(tuple(int(v) for v in s.cs_q[l]) for l in range(5)), tuple(int(v) for v in s.n), int(s.n_levels))
 
 
 DELTA_E_ITP_Q20 = 1 << 20  # a Delta E ITP of 1.0 in the units of the maps and thresholds (CE_DELTA_E_ITP_Q20)
@@ -1639,6 +1686,19 @@ class Context:
                                                     white_nits, C.byref(s)))
         return HdrFidelity.from_c(s)
 
+    def ms_ssim(self, reference, test, width: int, height: int, levels: int = 5, depth: int = 0) -> MsSsim:
+        """SSIM (levels = 1) and MS-SSIM (5) of one pair on the encoded sample values: packed uint8 RGB (depth 0;
+        ce_eval_pair_msssim) or packed uint16 RGB of `depth` bits on both sides (ce_eval_pair_msssim_deep)."""
+        s = CeMsssimScores()
+        if depth == 0:
+            r, t = _buf(reference), _buf(test)
+            self._check(lib().ce_eval_pair_msssim(self._h, r.ctypes.data, r.size, t.ctypes.data, t.size, width, height, levels, C.byref(s)))
+        else:
+            r, t = _buf16(reference), _buf16(test)
+            self._check(lib().ce_eval_pair_msssim_deep(self._h, r.ctypes.data, r.nbytes, t.ctypes.data, t.nbytes, depth, width, height,
+                                                       levels, C.byref(s)))
+        return MsSsim.from_c(s)
+
     def delta_e_itp_map(self, reference, test, width: int, height: int, depth: int = 10, white_nits: float = 203.0, block: int = 1,
                         thresholds_q20=None, maps: bool = True):
         """Batch.delta_e_itp_maps for one pair of packed float32 RGB (ce_eval_pair_delta_e_itp_map): (uint32
@@ -2172,6 +2232,13 @@ class Batch:
         out = (CeScores * n_pairs)()
         self.ctx._check(lib().ce_batch_collect(self._h, n_pairs, out))
         return list(out)
+
+    def ms_ssim(self, n_pairs: int, levels: int = 5) -> List[MsSsim]:
+        """SSIM (levels = 1) and MS-SSIM (5) of pairs [0, n_pairs) of an RGB8 or equal-depth deep batch on the encoded sample
+        values (ce_batch_msssim); returns once the scores are on the host.  Scores and maps of a launch are untouched."""
+        out = (CeMsssimScores * max(n_pairs, 1))()
+        self.ctx._check(lib().ce_batch_msssim(self._h, n_pairs, levels, out))
+        return [MsSsim.from_c(out[i]) for i in range(n_pairs)]
 
     def hdr_fidelity(self, n_pairs: int, depth: int = 10, white_nits: float = 203.0) -> List[HdrFidelity]:
         """PQ-PSNR and BT.2124 Delta E ITP of pairs [0, n_pairs) of a linear batch (ce_batch_hdr_fidelity); returns once the

@@ -1223,6 +1223,89 @@ int ce_batch_delta_e_itp_map(ce_batch *b, uint32_t first, uint32_t count, uint32
     return CE_OK;
 }
 
+// ---- SSIM and MS-SSIM of RGB8 and deep batches (msssim.hip) -------------------------------------------
+
+// (ce_msssim_window is in msssim.hip, beside the literals the kernel filters with)
+
+// the levels' geometry, or why there is none (the reason goes to ctx, or to the calling thread without one)
+static int msssim_levels(ce_ctx *ctx, uint32_t w, uint32_t h, uint32_t levels, uint32_t *lw, uint32_t *lh)
+{
+    if (levels != 1 && levels != CE_MSSSIM_LEVELS)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "MS-SSIM: levels must be 1 (SSIM) or 5 (MS-SSIM), got " + std::to_string(levels));
+    const uint32_t m = std::min(w, h);
+    if (levels == 1 ? m < 11 : m <= 160)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, std::string("MS-SSIM: ") + (levels == 1 ? "one level needs min(w, h) >= 11" : "five levels need min(w, h) > 160") +
+                                                 ", got " + std::to_string(w) + " x " + std::to_string(h));
+    for (uint32_t l = 0; l < levels; l++) {
+        lw[l] = w, lh[l] = h;
+        w = (w + (w & 1u)) / 2, h = (h + (h & 1u)) / 2;
+    }
+    return CE_OK;
+}
+
+int ce_msssim_levels(uint32_t w, uint32_t h, uint32_t levels, uint32_t *n_levels, uint32_t *level_w, uint32_t *level_h)
+{
+    if (!n_levels || !level_w || !level_h) return ce_fail(nullptr, CE_ERR_INVALID_ARG, "ce_msssim_levels: null pointer");
+    if (int rc = msssim_levels(nullptr, w, h, levels, level_w, level_h)) return rc;
+    *n_levels = levels;
+    return CE_OK;
+}
+
+int ce_batch_msssim(ce_batch *b, uint32_t n_pairs, uint32_t levels, ce_msssim_scores *out)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    ce_ctx *ctx = b->ctx;
+    if (!out) return ce_fail(ctx, CE_ERR_INVALID_ARG, "MS-SSIM: null pointer");
+    if (b->linear) return ce_fail(ctx, CE_ERR_INVALID_ARG, "MS-SSIM reads encoded sample values: not for a linear batch");
+    if (b->depth[0] != b->depth[1])
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "MS-SSIM needs both sides at one depth, got " + std::to_string(b->depth[0]) + " / " +
+                                                 std::to_string(b->depth[1]));
+    uint32_t lw[CE_MSSSIM_LEVELS] = {}, lh[CE_MSSSIM_LEVELS] = {};
+    if (int rc = msssim_levels(ctx, b->w, b->h, levels, lw, lh)) return rc;
+    if (n_pairs == 0 || n_pairs > b->max_pairs) return ce_fail(ctx, CE_ERR_INVALID_ARG, "n_pairs out of range");
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    constexpr size_t per_pair = (size_t)CE_MSSSIM_LEVELS * 3 * 2;
+    if (!b->msssim)
+        if (int rc = b->msssim.alloc(ctx, per_pair * b->max_pairs)) return rc;
+    size_t pyr = 0;
+    for (uint32_t l = 1; l < levels; l++) pyr += ((size_t)b->max_refs + b->max_pairs) * 3 * lw[l] * lh[l];
+    if (int rc = b->d_msssim_pyr.reserve(ctx, pyr)) return rc;
+    // on the context's stream, as a launch: behind the uploads queued so far, with the pair table of the last bind
+    if (int rc = ce_flush_uploads(b)) return rc;
+    if (int rc = sync_pair_ref(b)) return rc;
+    if (int rc = ce_launch_msssim(b, n_pairs, levels, lw, lh, b->d_msssim_pyr, b->msssim.d)) return rc;
+    CE_HIP(ctx, hipMemcpyAsync(b->msssim.h, b->msssim.d, sizeof(unsigned long long) * per_pair * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
+    CE_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the slabs are free again: a later upload needs no fence against this
+    static const double wt[CE_MSSSIM_LEVELS] = {0.0448, 0.2856, 0.3001, 0.2363, 0.1333};
+    for (uint32_t i = 0; i < n_pairs; i++) {
+        ce_msssim_scores s{};
+        s.n_levels = levels;
+        double ms[CE_MSSSIM_LEVELS][3], mc[CE_MSSSIM_LEVELS][3];
+        for (uint32_t l = 0; l < levels; l++) {
+            s.n[l] = (uint64_t)(lw[l] - 10) * (lh[l] - 10);
+            for (int c = 0; c < 3; c++) {
+                const unsigned long long *q = b->msssim.h + (((size_t)i * CE_MSSSIM_LEVELS + l) * 3 + c) * 2;
+                s.ssim_q[l][c] = (int64_t)q[0], s.cs_q[l][c] = (int64_t)q[1];
+                ms[l][c] = ((double)s.ssim_q[l][c] / 4294967296.0) / (double)s.n[l];
+                mc[l][c] = ((double)s.cs_q[l][c] / 4294967296.0) / (double)s.n[l];
+            }
+        }
+        for (int c = 0; c < 3; c++) {
+            s.ssim_rgb[c] = ms[0][c];
+            s.ms_ssim_rgb[c] = NAN;
+            if (levels == CE_MSSSIM_LEVELS) {
+                double p = std::pow(std::max(mc[0][c], 0.0), wt[0]);
+                for (int l = 1; l < 4; l++) p = p * std::pow(std::max(mc[l][c], 0.0), wt[l]);
+                s.ms_ssim_rgb[c] = p * std::pow(std::max(ms[4][c], 0.0), wt[4]);
+            }
+        }
+        s.ssim = ((s.ssim_rgb[0] + s.ssim_rgb[1]) + s.ssim_rgb[2]) / 3.0;
+        s.ms_ssim = levels == CE_MSSSIM_LEVELS ? ((s.ms_ssim_rgb[0] + s.ms_ssim_rgb[1]) + s.ms_ssim_rgb[2]) / 3.0 : NAN;
+        out[i] = s;
+    }
+    return CE_OK;
+}
+
 // ---- reference handle -------------------------------------------------------------------------
 
 struct ce_ref {

@@ -326,6 +326,11 @@ struct ce_batch {
     // [max_pairs][8] exceedance counts on the device and page-locked, made by the first call that asks for counts
     ce_dev<uint32_t> d_itp_map;
     ce_mirror<unsigned long long> itp_over;
+    // SSIM / MS-SSIM (msssim.hip): [max_pairs][5][3][2] exact integers on the device and page-locked, lazily; the f32 pyramid
+    // of levels 1 - 4 of every slot (references, then tests), level by level [slot][3][h_l][w_l], made by the first call with
+    // five levels and kept
+    ce_mirror<unsigned long long> msssim;
+    ce_dev<float> d_msssim_pyr;
 
     uint32_t last_n_pairs = 0;
     bool caller_blocks = false;  // set by entry points that collect before returning: page-locked sources need no staging copy
@@ -719,6 +724,13 @@ int ce_launch_hdr_fidelity(ce_batch *b, uint32_t n_pairs, uint32_t depth, const 
 int ce_launch_delta_e_itp_map(ce_batch *b, uint32_t first, uint32_t count, uint32_t depth, const float *d_table, const float *d_coarse,
                               const float a[9], const float lms[9], uint32_t block, uint32_t *d_map, const uint32_t *thresholds,
                               uint32_t n_thresholds, unsigned long long *d_over);
+
+// pairs [0, n_pairs) of an RGB8 or equal-depth deep batch, whose level l is lw[l] x lh[l] (ce_msssim_levels) -> d_out[pair][5]
+// [3][2] = ssim_q, cs_q, cleared and filled on the launching stream (msssim.hip): with five levels, every reference slot the
+// pairs name and the pairs' test slots are pooled level by level into d_pyr (ce_batch::d_msssim_pyr's layout), and each level
+// is one launch of the fused kernel
+int ce_launch_msssim(ce_batch *b, uint32_t n_pairs, uint32_t levels, const uint32_t *lw, const uint32_t *lh, float *d_pyr,
+                     unsigned long long *d_out);
 
 // host-side constant builders (ce_tables.cpp)
 // HDR fidelity's PQ code thresholds (include/ce_metrics.h: ce_pq_code_thresholds; maxv entries; false unless white_nits is

@@ -366,4 +366,38 @@ int ce_eval_pair_delta_e_itp_map(ce_ctx *ctx, const float *reference, size_t ref
     });
 }
 
+// One pair through the context's one-pair RGB8 batch (depth 0) or deep batch of depth / depth into ce_batch_msssim, which
+// refuses what concerns levels and the image's size
+static int leaf_msssim(ce_ctx *ctx, ce_leaf_kind kind, uint32_t depth, size_t bytes_per_pixel, const void *reference, size_t reference_len,
+                       const void *test, size_t test_len, uint32_t width, uint32_t height, uint32_t levels, ce_msssim_scores *out)
+{
+    if (!ctx) return CE_ERR_INVALID_ARG;
+    if (!out || !reference || !test) return ce_fail(ctx, CE_ERR_INVALID_ARG, "MS-SSIM: null pointer");
+    *out = ce_msssim_scores{};
+    if (kind == CE_LEAF_DEEP && !ce_deep_depth_ok(depth))
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "MS-SSIM: depth must be 8, 10, 12 or 16 bits, got " + std::to_string(depth));
+    if (width == 0 || height == 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, "MS-SSIM: empty image");
+    const size_t want = (size_t)width * height * bytes_per_pixel;
+    if (reference_len != want) return ce_bad_length(ctx, want, reference_len);
+    if (test_len != want) return ce_bad_length(ctx, want, test_len);
+    uint32_t n = 0, lw[CE_MSSSIM_LEVELS], lh[CE_MSSSIM_LEVELS];
+    if (int rc = ce_msssim_levels(width, height, levels, &n, lw, lh)) return ce_fail(ctx, rc, ce_last_error(nullptr));  // before a batch is made
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    ce_batch *b = nullptr;
+    if (int rc = leaf_batch(ctx, kind, width, height, depth, depth, &b)) return rc;
+    return leaf_pair(b, kind, reference, test, want, [&] { return ce_batch_msssim(b, 1, levels, out); });
+}
+
+int ce_eval_pair_msssim(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test, size_t test_len, uint32_t width,
+                        uint32_t height, uint32_t levels, ce_msssim_scores *out)
+{
+    return leaf_msssim(ctx, CE_LEAF_RGB8, 0, 3, reference, reference_len, test, test_len, width, height, levels, out);
+}
+
+int ce_eval_pair_msssim_deep(ce_ctx *ctx, const uint16_t *reference, size_t reference_len, const uint16_t *test, size_t test_len,
+                             uint32_t depth, uint32_t width, uint32_t height, uint32_t levels, ce_msssim_scores *out)
+{
+    return leaf_msssim(ctx, CE_LEAF_DEEP, depth, 6, reference, reference_len, test, test_len, width, height, levels, out);
+}
+
 }  // extern "C"

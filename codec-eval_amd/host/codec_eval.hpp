@@ -781,6 +781,49 @@ inline std::vector<float> pq_code_thresholds(uint32_t depth, float white_nits = 
 }
 // the two matrices the kernel is handed, row-major: BT.2020 <- sRGB primaries, BT.2100's LMS <- BT.2020
 inline void hdr_fidelity_matrices(std::array<float, 9> &a, std::array<float, 9> &b) { ce_hdr_fidelity_matrices(a.data(), b.data()); }
+// ---- SSIM and MS-SSIM on the encoded sample values (include/ce_metrics.h: ce_batch_msssim) ----
+// levels: 1 (SSIM) or 5 (MS-SSIM); the struct carries the doubles and the exact integers they are finished from
+using MsSsim = ce_msssim_scores;
+// pairs [0, n_pairs) of an RGB8 batch or a deep batch of one depth; returns once the scores are on the host
+inline std::vector<MsSsim> batch_ms_ssim(const HipBackend &be, ce_batch *batch, uint32_t n_pairs, uint32_t levels = 5)
+{
+    std::vector<MsSsim> out(n_pairs);
+    detail::check(be, ce_batch_msssim(batch, n_pairs, levels, out.data()), "ms_ssim", 0, 0, 0);
+    return out;
+}
+// one pair of packed RGB8 (width * height * 3 bytes each)
+inline MsSsim ms_ssim(const HipBackend &be, const uint8_t *reference, const uint8_t *test, uint32_t width, uint32_t height, uint32_t levels = 5)
+{
+    MsSsim out{};
+    const size_t len = (size_t)width * height * 3;
+    detail::check(be, ce_eval_pair_msssim(be.ctx(), reference, len, test, len, width, height, levels, &out), "ms_ssim", width, height, len);
+    return out;
+}
+// one pair of packed u16 RGB of `depth` bits on both sides (width * height * 3 samples each)
+inline MsSsim ms_ssim_deep(const HipBackend &be, const uint16_t *reference, const uint16_t *test, uint32_t depth, uint32_t width,
+                           uint32_t height, uint32_t levels = 5)
+{
+    MsSsim out{};
+    const size_t len = (size_t)width * height * 6;
+    detail::check(be, ce_eval_pair_msssim_deep(be.ctx(), reference, len, test, len, depth, width, height, levels, &out), "ms_ssim", width, height,
+                  len);
+    return out;
+}
+// the window's eleven literals, and the (width, height) of every level (pure host functions; empty when refused)
+inline std::array<double, 11> msssim_window()
+{
+    std::array<double, 11> g{};
+    ce_msssim_window(g.data());
+    return g;
+}
+inline std::vector<std::pair<uint32_t, uint32_t>> msssim_levels(uint32_t width, uint32_t height, uint32_t levels = 5)
+{
+    uint32_t n = 0, w[CE_MSSSIM_LEVELS], h[CE_MSSSIM_LEVELS];
+    std::vector<std::pair<uint32_t, uint32_t>> out;
+    if (ce_msssim_levels(width, height, levels, &n, w, h) != CE_OK) return out;
+    for (uint32_t l = 0; l < n; l++) out.emplace_back(w[l], h[l]);
+    return out;
+}
 // straight into a slot of a resident batch (RGB8 or deep), host or device planes
 inline void batch_set_reference_yuv(const HipBackend &be, ce_batch *batch, uint32_t ref_index, const YuvImage &image)
 {

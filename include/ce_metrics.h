@@ -1006,6 +1006,71 @@ int ce_eval_pair_delta_e_itp_map(ce_ctx *ctx, const float *reference, size_t ref
                                  uint32_t width, uint32_t height, uint32_t depth, float white_nits, uint32_t block, uint32_t *map,
                                  size_t map_len, const uint32_t *thresholds_q20, uint32_t n_thresholds, uint64_t *over);
 
+/* ---- SSIM and MS-SSIM of RGB8 and deep batches, exactly -------------------------------------------------
+ * The two numbers learned-codec papers tabulate beside PSNR, in the form they use (Wang et al. 2003 as the frameworks' MS-SSIM
+ * packages compute it): an 11-tap Gaussian window of sigma 1.5, "valid" filtering, each of R, G and B on the encoded sample values, 2 x 2 mean
+ * pooling between five scales.  A call of its own beside the launch, as HDR fidelity is.  Everything is pinned to f64
+ * operations in a stated order and the per-pixel values are summed as integers, so no result depends on the grid or on the
+ * order of summation.
+ * Samples.  The integers in the slabs of an RGB8 batch, or of a deep batch whose two sides have EQUAL depth d; L = 2^d - 1
+ *   (255 for RGB8).  Each channel c of R, G, B separately.
+ * Window.  g[0 .. 10], symmetric, g[i] = g[10 - i]; g[0 .. 5] are the doubles 0.00102838008447911, 0.007598758135239185,
+ *   0.03600077212843083, 0.10936068950970002, 0.2130055377112537, 0.26601172486179436: exp(-(i - 5)^2 / 4.5) divided by their
+ *   sum in index order, as numpy gives them; literals in the library, not computed at run time (ce_msssim_window).
+ * Filter F(p) of a plane p of h x w doubles, h, w >= 11.  First down the columns, v[y][x] = sum_i g[i] * p[y + i][x], (h - 10)
+ *   x w; then along the rows, o[y][x] = sum_i g[i] * v[y][x + i], (h - 10) x (w - 10).  Each sum starts at +0.0 and adds the
+ *   taps in order i = 0 .. 10; every product and every sum is rounded separately in f64 (no fused multiply-add); v stays f64.
+ * Per level and channel, x the reference plane and y the test plane, both f64:
+ *   mx = F(x), my = F(y);  sxx = F(x * x) - mx * mx, syy = F(y * y) - my * my, sxy = F(x * y) - mx * my;
+ *   C1 = (0.01 * L) * (0.01 * L) and C2 = (0.03 * L) * (0.03 * L) in f64;
+ *   cs = (2.0 * sxy + C2) / ((sxx + syy) + C2);  lum = (2.0 * (mx * my) + C1) / ((mx * mx + my * my) + C1);  s = lum * cs.
+ *   The divisions are correctly rounded and the parentheses are as written, so identical images give exactly 1.0 everywhere.
+ *   qs = (int64) rint(s * 2^32) and qc = (int64) rint(cs * 2^32), ties to even.  ssim_q[level][c] = the sum of qs over the
+ *   (h - 10) x (w - 10) positions, cs_q[level][c] = the sum of qc: signed 64-bit, possibly negative.  n[level] = the number
+ *   of positions.
+ * Next level.  From level planes p of h x w, with ph = h & 1 and pw = w & 1: q = p with ph rows of zeros above and pw columns
+ *   of zeros on the left; next[Y][X] = ((q[2Y][2X] + q[2Y][2X+1]) + (q[2Y+1][2X] + q[2Y+1][2X+1])) * 0.25, shape
+ *   ((h + ph) / 2) x ((w + pw) / 2): avg_pool2d(2, padding = size % 2) with the pad counted in the divisor.  Every value is a
+ *   dyadic rational of at most 16 + 8 bits, exact in f32 and f64 (the pyramid is stored in f32); x * x and x * y are exact in f64.
+ * levels.  1 (SSIM; needs min(w, h) >= 11) or 5 (MS-SSIM; needs min(w, h) > 160: its last level is at least 11 x 11).
+ * Finishing, on the host in f64.  ms[l][c] = ((double) ssim_q[l][c] / 4294967296.0) / n[l], mc[l][c] the same from cs_q;
+ *   ssim_rgb[c] = ms[0][c];  ms_ssim_rgb[c] = the product over l = 0 .. 3 of pow(max(mc[l][c], 0), wt[l]), multiplied in level
+ *   order, then multiplied by pow(max(ms[4][c], 0), wt[4]), wt = {0.0448, 0.2856, 0.3001, 0.2363, 0.1333};
+ *   ssim = ((ssim_rgb[0] + ssim_rgb[1]) + ssim_rgb[2]) / 3.0, ms_ssim the same over ms_ssim_rgb.  With levels = 1 the MS-SSIM
+ *   fields are NaN and n_levels is 1; the integers of levels that did not run are 0.
+ * tests/msssim_restatement.py restates this in numpy; the device equals it on every integer. */
+#define CE_MSSSIM_LEVELS 5
+typedef struct ce_msssim_scores {
+    double ms_ssim;         /* NaN with levels = 1 */
+    double ssim;            /* level 0's mean SSIM over R, G, B */
+    double ms_ssim_rgb[3];
+    double ssim_rgb[3];
+    int64_t ssim_q[5][3];   /* the exact integers the doubles are finished from: [level][channel] */
+    int64_t cs_q[5][3];
+    uint64_t n[5];          /* positions of a level: (h_l - 10) * (w_l - 10) */
+    uint32_t n_levels;
+    uint32_t reserved;      /* 0 */
+} ce_msssim_scores;         /* 352 bytes */
+/* Scores pairs [0, n_pairs) of an RGB8 or equal-depth deep batch into out[0 .. n_pairs): on the context's stream, ordered behind
+ * the uploads queued so far as a launch is, with the pair table of the last bind; blocks until the scores are on the host.
+ * ce_scores, the stored maps and whatever ce_batch_launch left to collect are untouched.  Each reference slot the pairs name is
+ * pooled once.  The pyramid of levels 1 - 4 (f32, 4/3 bytes per sample of every slot of the batch) is a grow-only buffer of the
+ * batch, made by the first call with levels = 5 and freed with the batch; it is outside ce_estimate_batch_bytes.
+ * CE_ERR_INVALID_ARG, with the reason in ce_last_error and the batch still usable: a linear batch; a deep batch of unequal
+ * depths; levels other than 1 or 5; an image too small for `levels`; a null pointer; n_pairs of 0 or past the batch. */
+int ce_batch_msssim(ce_batch *b, uint32_t n_pairs, uint32_t levels, ce_msssim_scores *out);
+/* One pair of packed RGB8 host images (lengths in bytes: width * height * 3), and one pair of packed u16 RGB of one `depth`
+ * (8, 10, 12 or 16; width * height * 6 bytes), through the context's one-pair batches.  CE_ERR_INVALID_ARG as above and for an
+ * empty image, CE_ERR_BAD_LENGTH for a length that is not the image's. */
+int ce_eval_pair_msssim(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test, size_t test_len,
+                        uint32_t width, uint32_t height, uint32_t levels, ce_msssim_scores *out);
+int ce_eval_pair_msssim_deep(ce_ctx *ctx, const uint16_t *reference, size_t reference_len, const uint16_t *test, size_t test_len,
+                             uint32_t depth, uint32_t width, uint32_t height, uint32_t levels, ce_msssim_scores *out);
+/* Pure host functions: the window's eleven literals, and the geometry of the levels of a w x h image - *n_levels = levels and
+ * level_w / level_h [0 .. levels) - with CE_ERR_INVALID_ARG for a null pointer, levels other than 1 or 5 and an image too small. */
+int ce_msssim_window(double out[11]);
+int ce_msssim_levels(uint32_t w, uint32_t h, uint32_t levels, uint32_t *n_levels, uint32_t *level_w, uint32_t *level_h);
+
 /* ---- matrix/TRC ICC profiles applied on the device ------------------------------------------------
  * transform_to_srgb (src/metrics/icc.rs:69-103) for the profiles photographs carry - three colorant tags and three tone
  * curves - without a CMS on the host.  ce_lut_* above stays the route for every other profile.
