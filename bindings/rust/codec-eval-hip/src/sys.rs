@@ -220,6 +220,26 @@ pub struct ce_msssim_scores {
     pub reserved: u32,
 }
 
+/// `ce_plane_scores` (512 bytes): one pair of Y'CbCr images scored plane by plane, index 0, 1, 2 = Y, Cb, Cr: the exact squared
+/// error and sample count, the PSNRs finished from them, and per plane and level the integers of SSIM / MS-SSIM with the
+/// positions of a level.  What did not run is 0 (integers) or NaN (doubles).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct ce_plane_scores {
+    pub sse: [u64; 3],
+    pub n: [u64; 3],
+    pub psnr: [c_double; 3],
+    pub psnr_weighted: c_double,
+    pub psnr_overall: c_double,
+    pub ssim: [c_double; 3],
+    pub ms_ssim: [c_double; 3],
+    pub ssim_q: [[i64; 5]; 3],
+    pub cs_q: [[i64; 5]; 3],
+    pub n_pos: [[u64; 5]; 3],
+    pub n_levels: [u32; 3],
+    pub n_planes: u32,
+}
+
 /// `ce_scores` (40 bytes): a score is meaningful iff its bit is set in `valid`.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -521,6 +541,8 @@ extern "C" {
                                     depth: u32, width: u32, height: u32, levels: u32, out: *mut ce_msssim_scores) -> c_int;
     pub fn ce_msssim_window(out: *mut c_double) -> c_int;
     pub fn ce_msssim_levels(w: u32, h: u32, levels: u32, n_levels: *mut u32, level_w: *mut u32, level_h: *mut u32) -> c_int;
+    pub fn ce_yuv_plane_fidelity(ctx: *mut ce_ctx, width: u32, height: u32, refs: *const ce_yuv_image, n_refs: u32, tests: *const ce_yuv_image,
+                                 n_pairs: u32, pair_ref: *const u32, levels: u32, out: *mut ce_plane_scores) -> c_int;
     pub fn ce_batch_delta_e_itp_map(b: *mut ce_batch, first: u32, count: u32, depth: u32, white_nits: c_float, block: u32, map: *mut u32,
                                     map_len: usize, thresholds_q20: *const u32, n_thresholds: u32, over: *mut u64) -> c_int;
     pub fn ce_eval_pair_delta_e_itp_map(ctx: *mut ce_ctx, reference: *const c_float, reference_len: usize, test: *const c_float,

@@ -195,6 +195,12 @@ class CeMsssimScores(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class CePlaneScores(C.Structure):
+    _fields_ = [("sse", C.c_uint64 * 3), ("n", C.c_uint64 * 3), ("psnr", C.c_double * 3), ("psnr_weighted", C.c_double),
+                ("psnr_overall", C.c_double), ("ssim", C.c_double * 3), ("ms_ssim", C.c_double * 3), ("ssim_q", (C.c_int64 * 5) * 3),
+                ("cs_q", (C.c_int64 * 5) * 3), ("n_pos", (C.c_uint64 * 5) * 3), ("n_levels", C.c_uint32 * 3), ("n_planes", C.c_uint32)]
+
+
 class CodecEvalError(RuntimeError):
     """Mirrors codec_eval::Error for this path (src/error.rs:31-49)."""
 
@@ -349,6 +355,8 @@ _PROTOTYPES = [
     ("ce_batch_msssim", _i, [_vp, _u32, _u32, C.POINTER(CeMsssimScores)]),
     ("ce_eval_pair_msssim", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, C.POINTER(CeMsssimScores)]),
     ("ce_eval_pair_msssim_deep", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, C.POINTER(CeMsssimScores)]),
+    ("ce_yuv_plane_fidelity", _i, [_vp, _u32, _u32, C.POINTER(CeYuvImage), _u32, C.POINTER(CeYuvImage), _u32, _vp, _u32,
+                               C.POINTER(CePlaneScores)]),
     ("ce_msssim_window", _i, [_vp]),
     ("ce_msssim_levels", _i, [_u32, _u32, _u32, _vp, _vp, _vp]),
     ("ce_icc_describe", _i, [_vp, _sz, C.POINTER(CeIccDescription)]),
@@ -844,6 +852,34 @@ class MsSsim:
         return MsSsim(s.ms_ssim, s.ssim, tuple(s.ms_ssim_rgb), tuple(s.ssim_rgb),
                       tuple(tuple(int(v) for v in s.ssim_q[l]) for l in range(5)),
                       tuple(tuple(int(v) for v in s.cs_q[l]) for l in range(5)), tuple(int(v) for v in s.n), int(s.n_levels))
+
+
+@dataclass(frozen=True)
+class PlaneScores:
+    """One pair of Y'CbCr images scored plane by plane (ce_plane_scores): index p = 0, 1, 2 is Y, Cb, Cr, each at its own
+    resolution.  sse and n are the exact squared error and the sample count of a plane, psnr the planes' PSNR, psnr_weighted
+    the 6:1:1 figure and psnr_overall the PSNR of the three planes' joint error.  ssim and ms_ssim are per plane, from the exact
+    integers ssim_q[p][level] and cs_q[p][level] over n_pos[p][level] positions; n_levels[p] is how many levels plane p ran.
+    What did not run is 0 (integers) or NaN (doubles)."""
+    sse: Tuple[int, int, int]
+    n: Tuple[int, int, int]
+    psnr: Tuple[float, float, float]
+    psnr_weighted: float
+    psnr_overall: float
+    ssim: Tuple[float, float, float]
+    ms_ssim: Tuple[float, float, float]
+    ssim_q: Tuple[Tuple[int, ...], ...]
+    cs_q: Tuple[Tuple[int, ...], ...]
+    n_pos: Tuple[Tuple[int, ...], ...]
+    n_levels: Tuple[int, int, int]
+    n_planes: int
+
+    @staticmethod
+    def from_c(s: CePlaneScores) -> "PlaneScores":
+        grid = lambda a: tuple(tuple(int(v) for v in a[p]) for p in range(3))  # noqa: E731
+        return PlaneScores(tuple(int(v) for v in s.sse), tuple(int(v) for v in s.n), tuple(s.psnr), s.psnr_weighted, s.psnr_overall,
+                           tuple(s.ssim), tuple(s.ms_ssim), grid(s.ssim_q), grid(s.cs_q), grid(s.n_pos),
+                           tuple(int(v) for v in s.n_levels), int(s.n_planes))
 
 
 DELTA_E_ITP_Q20 = 1 << 20  # a Delta E ITP of 1.0 in the units of the maps and thresholds (CE_DELTA_E_ITP_Q20)
@@ -1698,6 +1734,26 @@ class Context:
             self._check(lib().ce_eval_pair_msssim_deep(self._h, r.ctypes.data, r.nbytes, t.ctypes.data, t.nbytes, depth, width, height,
                                                        levels, C.byref(s)))
         return MsSsim.from_c(s)
+
+    def plane_fidelity(self, refs: Sequence["YuvImage"], tests: Sequence["YuvImage"], width: int, height: int,
+                       pair_ref: Optional[Sequence[int]] = None, levels: int = 5) -> List[PlaneScores]:
+        """PSNR (levels = 0), + SSIM (1), + MS-SSIM (5) of Y'CbCr images plane by plane, on the planes as a decoder wrote
+        them (ce_yuv_plane_fidelity): tests[i] against refs[pair_ref[i]], or against refs[i] without a pair table.  Every
+        image is width x height with one subsampling and one depth; layout, pitch, alignment and memory are each image's
+        own.  Returns once the scores are on the host; no batch is touched and device planes are only read."""
+        cr, ct = (CeYuvImage * max(len(refs), 1))(), (CeYuvImage * max(len(tests), 1))()
+        keep = []
+        for arr, imgs in ((cr, refs), (ct, tests)):
+            for i, img in enumerate(imgs):
+                arr[i], k = img._c()
+                keep.append(k)
+        table = None if pair_ref is None else np.ascontiguousarray(pair_ref, dtype=np.uint32).reshape(-1)
+        if table is not None and table.size != len(tests):
+            raise CodecEvalError(CE_ERR_INVALID_ARG, f"pair_ref names {table.size} pairs for {len(tests)} tests")
+        out = (CePlaneScores * max(len(tests), 1))()
+        self._check(lib().ce_yuv_plane_fidelity(self._h, width, height, cr, len(refs), ct, len(tests),
+                                                table.ctypes.data if table is not None else None, levels, out))
+        return [PlaneScores.from_c(out[i]) for i in range(len(tests))]
 
     def delta_e_itp_map(self, reference, test, width: int, height: int, depth: int = 10, white_nits: float = 203.0, block: int = 1,
                         thresholds_q20=None, maps: bool = True):

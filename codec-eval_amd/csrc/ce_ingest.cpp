@@ -1323,6 +1323,18 @@ int linear_over_check(ce_ctx *ctx, size_t len, int format, size_t n_px)
 
 }  // namespace
 
+// yuv_check for the plane-domain scores (plane_fidelity.hip): the matrix and range are validated for the image's own depth and
+// not applied
+int ce_yuv_planes_check(ce_ctx *ctx, const ce_yuv_image *img, uint32_t w, uint32_t h, ce_yuv_planes *out)
+{
+    yuv_plan plan;
+    if (int rc = yuv_check(ctx, img, w, h, img ? (uint32_t)img->depth : 8u, &plan)) return rc;
+    out->n_stored = plan.n_planes;
+    for (int p = 0; p < plan.n_planes; p++) out->rows[p] = plan.rows[p], out->row_bytes[p] = plan.row_bytes[p];
+    out->shift = plan.dev.shift;
+    return CE_OK;
+}
+
 // ---- the entry points -------------------------------------------------------------------------------------------------------
 
 extern "C" {

@@ -130,6 +130,14 @@ struct ce_ctx {
     uint8_t *rs_mid = nullptr;
     size_t rs_mid_cap = 0;
     std::map<std::tuple<uint32_t, uint32_t, int, bool>, ce_resample_axis> rs_tables;
+    // grow-only scratch of the plane-domain scores (plane_fidelity.hip), outside ce_estimate_batch_bytes as the heuristics'
+    // is: the host planes of a call without their pitch padding, page-locked and on the device; the plane table with the pair
+    // table behind it; the f32 pyramid of levels 1 - 4, [plane][level][image][h][w]; the result integers, [pair][33]
+    ce_dev<uint8_t> pf_planes_d, pf_tables_d;
+    ce_pinned<uint8_t> pf_planes_h, pf_tables_h;
+    ce_dev<float> pf_pyr;
+    ce_dev<unsigned long long> pf_out_d;
+    ce_pinned<unsigned long long> pf_out_h;
 
     // Auxiliary streams of the context, shared by all its batches (made on first use, destroyed with the context): the
     // three metric chains of a forked batch, SSIMULACRA2's level-0 passes, Butteraugli's half-resolution chain.  Rounds
@@ -731,6 +739,16 @@ int ce_launch_delta_e_itp_map(ce_batch *b, uint32_t first, uint32_t count, uint3
 // is one launch of the fused kernel
 int ce_launch_msssim(ce_batch *b, uint32_t n_pairs, uint32_t levels, const uint32_t *lw, const uint32_t *lh, float *d_pyr,
                      unsigned long long *d_out);
+
+// What the plane-domain scores (plane_fidelity.hip) take from the Y'CbCr ingest's own check of an image (ce_ingest.cpp:
+// yuv_check, with every refusal of it): the planes as the layout stores them - 1, or 2 (semiplanar), or 3 - with their rows
+// and their rows' bytes, and the shift of MSB-aligned samples
+struct ce_yuv_planes {
+    int n_stored = 0;
+    size_t rows[3] = {}, row_bytes[3] = {};
+    uint32_t shift = 0;
+};
+int ce_yuv_planes_check(ce_ctx *ctx, const ce_yuv_image *img, uint32_t w, uint32_t h, ce_yuv_planes *out);
 
 // host-side constant builders (ce_tables.cpp)
 // HDR fidelity's PQ code thresholds (include/ce_metrics.h: ce_pq_code_thresholds; maxv entries; false unless white_nits is

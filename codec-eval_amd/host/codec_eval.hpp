@@ -824,6 +824,22 @@ inline std::vector<std::pair<uint32_t, uint32_t>> msssim_levels(uint32_t width, 
     for (uint32_t l = 0; l < n; l++) out.emplace_back(w[l], h[l]);
     return out;
 }
+// ---- a decoder's Y'CbCr planes scored as planes (include/ce_metrics.h: ce_yuv_plane_fidelity) ----
+// PSNR-Y / -Cb / -Cr with the weighted and the overall figure, and SSIM / MS-SSIM per plane, each plane at its own size;
+// levels: 0 (PSNR only), 1 (+ SSIM) or 5 (+ MS-SSIM)
+using PlaneScores = ce_plane_scores;
+// tests[i] against refs[pair_ref[i]], or against refs[i] with an empty pair_ref (then refs.size() == tests.size()); host or
+// device planes, every image width x height with one subsampling and one depth; returns once the scores are on the host
+inline std::vector<PlaneScores> plane_fidelity(const HipBackend &be, const std::vector<ce_yuv_image> &refs, const std::vector<ce_yuv_image> &tests,
+                                               uint32_t width, uint32_t height, const std::vector<uint32_t> &pair_ref = {}, uint32_t levels = 5)
+{
+    std::vector<PlaneScores> out(tests.size());
+    if (!pair_ref.empty() && pair_ref.size() != tests.size()) detail::check(be, CE_ERR_INVALID_ARG, "plane_fidelity", width, height, 0);
+    detail::check(be, ce_yuv_plane_fidelity(be.ctx(), width, height, refs.data(), (uint32_t)refs.size(), tests.data(), (uint32_t)tests.size(),
+                                            pair_ref.empty() ? nullptr : pair_ref.data(), levels, out.data()),
+                  "plane_fidelity", width, height, 0);
+    return out;
+}
 // straight into a slot of a resident batch (RGB8 or deep), host or device planes
 inline void batch_set_reference_yuv(const HipBackend &be, ce_batch *batch, uint32_t ref_index, const YuvImage &image)
 {

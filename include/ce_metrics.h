@@ -1071,6 +1071,67 @@ int ce_eval_pair_msssim_deep(ce_ctx *ctx, const uint16_t *reference, size_t refe
 int ce_msssim_window(double out[11]);
 int ce_msssim_levels(uint32_t w, uint32_t h, uint32_t levels, uint32_t *n_levels, uint32_t *level_w, uint32_t *level_h);
 
+/* ---- a decoder's Y'CbCr planes scored as planes: PSNR, SSIM and MS-SSIM per plane -----------------------
+ * What codec test conditions (AOM, JVET, JPEG) tabulate: PSNR-Y, PSNR-Cb, PSNR-Cr on the planes the decoder wrote, each at its
+ * own resolution - no chroma upsampling, no colour matrix, no RGB clamp - with the 6:1:1 weighted and the overall PSNR, and
+ * SSIM / MS-SSIM per plane.  One call on the context, no batch.  Every value the device returns is an exact integer.
+ * Images.  ce_yuv_image as the ingest takes it (above), with the ingest's own checks.  Every image of a call has the call's width
+ *   x height and one subsampling and one depth d in {8, 10, 12}; layout, pitch, msb_aligned and memory are per image (an I420
+ *   file on the host against a decoder's NV12 / P010 surface on the device).  matrix, range and upsample are validated and not
+ *   applied; the two sides of a pair must agree in matrix and range, since their code values would not mean the same otherwise.
+ * Planes.  p = 0, 1, 2 = Y, Cb, Cr; 4:0:0 has plane 0 only (n_planes = 1).  Plane 0 is w x h; planes 1 and 2 are cw x ch, cw =
+ *   ceil(w / 2) for 4:2:0 and 4:2:2 (else w), ch = ceil(h / 2) for 4:2:0 (else h).  In a semiplanar image Cb and Cr are the even
+ *   and odd samples of plane[1].
+ * Samples.  min(v >> shift, L), L = 2^d - 1, shift = 16 - d for MSB-aligned samples and 0 otherwise, as the ingest reads them.
+ * PSNR.  sse[p] = the sum over plane p's samples of (x - y)^2, x the reference's sample and y the test's, unsigned 64-bit;
+ *   n[p] = the plane's sample count.  psnr[p]: mse = (double) sse[p] / (double) n[p]; +INFINITY when mse == 0, otherwise
+ *   10.0 * log10(L * L / mse) with L * L formed in f64.  psnr_weighted = ((6.0 * psnr[0] + psnr[1]) + psnr[2]) / 8.0 (the 6:1:1
+ *   figure of the HEVC / VVC literature).  psnr_overall = the same expression as psnr[p] on sse[0] + sse[1] + sse[2] and n[0] +
+ *   n[1] + n[2] (aomenc's "overall").  4:0:0: the chroma integers are 0, the chroma doubles and psnr_weighted NaN, psnr_overall
+ *   luma's.
+ * SSIM / MS-SSIM.  The definition of ce_batch_msssim above, unchanged - the window literals, the filter first down the columns
+ *   and then along the rows, separately rounded f64 operations, C1 and C2 from L, qs and qc = rint(. * 2^32) summed as int64,
+ *   the padded 2 x 2 pooling, the finishing with wt - applied to each plane at its own size as it is applied there to a channel;
+ *   planes are not averaged.  levels: 0 (PSNR only), 1 (SSIM) or 5 (MS-SSIM); luma must admit `levels` by ce_msssim_levels' rule.
+ *   A chroma plane runs n_levels[p] levels: `levels` if the plane admits them by that rule, else 1 if levels >= 1 and
+ *   min(cw, ch) >= 11, else 0.  ssim_q[p][l], cs_q[p][l] and n_pos[p][l] = (h_l - 10) * (w_l - 10) are level l of plane p;
+ *   ssim[p] = ((double) ssim_q[p][0] / 4294967296.0) / n_pos[p][0]; ms_ssim[p] as ms_ssim_rgb[c] there, NaN unless
+ *   n_levels[p] == 5.  Of levels that did not run the integers are 0 and the doubles NaN.
+ * tests/plane_fidelity_restatement.py restates this in numpy; the device equals it on every integer.
+ * Not part of this: ce_ref_* handles, ce_eval_batch, the session and the report wire formats, 16-bit planes, chroma sitings
+ * (no sample is moved, so siting does not enter), and plane-domain Butteraugli / SSIMULACRA2 / DSSIM. */
+typedef struct ce_plane_scores {
+    uint64_t sse[3];
+    uint64_t n[3];
+    double psnr[3];
+    double psnr_weighted;
+    double psnr_overall;
+    double ssim[3];
+    double ms_ssim[3];
+    int64_t ssim_q[3][5];   /* [plane][level] */
+    int64_t cs_q[3][5];
+    uint64_t n_pos[3][5];
+    uint32_t n_levels[3];
+    uint32_t n_planes;
+} ce_plane_scores;          /* 512 bytes */
+/* Scores n_pairs tests, tests[i] against refs[pair_ref[i]] - or against refs[i] with pair_ref NULL, which needs n_refs ==
+ * n_pairs - into out[0 .. n_pairs).  Runs on the context's stream and blocks until the scores are on the host; touches no
+ * batch, and a batch launch that is still to be collected is unaffected.  CE_MEM_HOST planes are copied row by row, without
+ * their pitch padding, through page-locked staging into a grow-only scratch buffer of the context and are consumed on return.
+ * CE_MEM_DEVICE planes are read in place by the kernels, on the context's device, and no full-resolution copy of them is made:
+ * the caller must have finished writing them before the call and may reuse them when it returns.  The pyramid of levels 1 - 4,
+ * the plane table and the result integers are grow-only scratch of the context too, freed with it and outside
+ * ce_estimate_batch_bytes.  A reference that several pairs name is pooled once per call.
+ * CE_ERR_INVALID_ARG, with the reason in ce_last_error and the context still usable: a null pointer; n_pairs or n_refs of 0;
+ * pair_ref[i] >= n_refs; NULL pair_ref with n_refs != n_pairs; levels outside {0, 1, 5}; a luma plane too small for `levels`;
+ * width or height of 0; images that disagree in subsampling or depth; a pair that disagrees in matrix or range; and whatever
+ * the ingest refuses of an image (a missing plane of the layout, an unknown enum, a depth outside {8, 10, 12}, a pitch under
+ * the row's bytes, a u16 plane pointer or pitch that is not 2-byte aligned, msb_aligned with depth 8, a colour table).  A
+ * scratch allocation that fails returns CE_ERR_BACKEND and leaves the context usable. */
+int ce_yuv_plane_fidelity(ce_ctx *ctx, uint32_t width, uint32_t height, const ce_yuv_image *refs, uint32_t n_refs,
+                          const ce_yuv_image *tests, uint32_t n_pairs, const uint32_t *pair_ref, uint32_t levels,
+                          ce_plane_scores *out);
+
 /* ---- matrix/TRC ICC profiles applied on the device ------------------------------------------------
  * transform_to_srgb (src/metrics/icc.rs:69-103) for the profiles photographs carry - three colorant tags and three tone
  * curves - without a CMS on the host.  ce_lut_* above stays the route for every other profile.
