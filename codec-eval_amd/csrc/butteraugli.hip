@@ -775,9 +775,18 @@ static_assert(malta_tables_monotone(), "the row-streaming Malta unit needs every
 // the image, as PaddedMaltaUnit does) and the 16 line sums are squared and accumulated.  Then the
 // L2DiffAsymmetric (HF), L2Diff (MF) and SetL2Diff (LF) terms of the channel are added and ac[c] / dc[c] are written
 // once.  Channel B has no Malta term: only L2Diff (MF) and SetL2Diff (LF).
-struct malta_bands {
-    malta_params p[2][3];  // [channel][band: uhf, hf, mf]
+// A band's constants as (X, Y) pairs: the kernel's arguments arrive in scalar registers, and a pair that is adjacent here is
+// an aligned register pair there, which is what a packed instruction takes as one operand.
+struct malta_params_xy {
+    ba_f2 norm2_0gt1, norm2_0lt1, norm1;
 };
+struct malta_bands {
+    malta_params_xy p[3];  // [band: uhf, hf, mf]
+};
+__host__ inline malta_params_xy malta_pair(const malta_params &x, const malta_params &y)
+{
+    return malta_params_xy{ba_f2{x.norm2_0gt1, y.norm2_0gt1}, ba_f2{x.norm2_0lt1, y.norm2_0lt1}, ba_f2{x.norm1, y.norm1}};
+}
 
 // Two correctly rounded f32 quotients a0 / b and a1 / b with ONE reciprocal.  hipcc expands every IEEE division into
 // v_div_scale x2, v_rcp, two fused steps that refine the reciprocal, a product, two fused quotient corrections, v_div_fmas
@@ -788,20 +797,32 @@ struct malta_bands {
 // numerators are positive constants in [1.7, 4.1e7] and b = norm1 + |..| is positive; measured (DESIGN.md section 15,
 // "Operand ranges"): b in [5, 1.3e8] on RGB8 / deep batches, [5, 7.5e12 < 2^43] on linear batches (a +-1024 checker at
 // intensity target 10 000), quotients down to 2.7e-13 = 2^-42.
-__device__ __forceinline__ void div2_shared_rcp(float a0, float a1, float b, float &q0, float &q1)
+// Written on (X, Y) pairs - ce_rcp_refined / ce_div_refined (ce_internal.h) on both halves at once, the same IEEE
+// operations per half in the same order.  v_rcp_f32 has no packed form: two scalar instructions.
+__device__ __forceinline__ ba_f2 rcp_refined_xy(ba_f2 b)
 {
-    const float r = ce_rcp_refined(b);  // ce_internal.h
-    q0 = ce_div_refined(a0, b, r);
-    q1 = ce_div_refined(a1, b, r);
+    const ba_f2 r0 = {__builtin_amdgcn_rcpf(b.x), __builtin_amdgcn_rcpf(b.y)};
+    return __builtin_elementwise_fma(__builtin_elementwise_fma(-b, r0, ba_f2{1.0f, 1.0f}), r0, r0);
+}
+__device__ __forceinline__ ba_f2 div_refined_xy(ba_f2 a, ba_f2 b, ba_f2 r)  // r = refined reciprocal of b
+{
+    ba_f2 q = a * r;
+    q = __builtin_elementwise_fma(__builtin_elementwise_fma(-b, q, a), r, q);
+    return __builtin_elementwise_fma(__builtin_elementwise_fma(-b, q, a), r, q);
 }
 
-__device__ __forceinline__ float malta_pre_diff(float v0, float v1, const malta_params &mp)
+// MaltaDiffMap's pre-scaled difference of one position for channels X and Y together: v0 / v1 are the (X, Y) samples of the
+// two images, the result is the pair the LDS tile stores.  Each half is the scalar chain; its fused steps, products, sums
+// and differences run on v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32, the reciprocal, the comparisons and the selects per
+// half.  |x| is formed explicitly: a packed instruction has no |.| source modifier.
+__device__ __forceinline__ ba_f2 malta_pre_diff_xy(ba_f2 v0, ba_f2 v1, const malta_params_xy &mp)
 {
-    const float absval = 0.5f * (fabsf(v0) + fabsf(v1));
-    const float diff = v0 - v1;
-    float scaler, scaler2;  // norm2_0gt1 / (norm1 + absval), norm2_0lt1 / (norm1 + absval)
-    div2_shared_rcp(mp.norm2_0gt1, mp.norm2_0lt1, mp.norm1 + absval, scaler, scaler2);
-    const float r = scaler * diff;
+    const ba_f2 fabs0 = __builtin_elementwise_abs(v0);
+    const ba_f2 absval = ba_f2{0.5f, 0.5f} * (fabs0 + __builtin_elementwise_abs(v1));
+    const ba_f2 diff = v0 - v1;
+    const ba_f2 den = mp.norm1 + absval, rden = rcp_refined_xy(den);
+    const ba_f2 scaler = div_refined_xy(mp.norm2_0gt1, den, rden), scaler2 = div_refined_xy(mp.norm2_0lt1, den, rden);
+    const ba_f2 r = scaler * diff;
     // The four branches of MaltaDiffMap's asymmetry term, without divergence, in f32 (the lineage forms it in f64: worth
     // 9e-8 of the score, tests/golden/sensitivity.json "ba_malta_f32" - the oracle's switch of that name is this arithmetic
     // bit for bit; round 2 paid ten f64-rate instructions per sample for it).  Mirror v1 for a negative v0:
@@ -810,13 +831,14 @@ __device__ __forceinline__ float malta_pre_diff(float v0, float v1, const malta_
     //   v0 >= 0: v1 <  too_small  <=>  u < too_small   r + scaler2 (too_small - v1)
     //            v1 >  too_big    <=>  u > too_big     r - scaler2 (v1 - too_big)
     // with u = v0 < 0 ? -v1 : v1.
-    const float fabs0 = fabsf(v0), too_small = 0.55f * fabs0, too_big = 1.05f * fabs0;
-    const bool neg = v0 < 0;
-    const float u = neg ? -v1 : v1;
-    const bool lo = u < too_small, hi = u > too_big;
-    const float impact = scaler2 * (lo ? too_small - u : u - too_big);
-    const float rn = r + ((neg == lo) ? -impact : impact);
-    return (lo || hi) ? rn : r;
+    const ba_f2 too_small = ba_f2{0.55f, 0.55f} * fabs0, too_big = ba_f2{1.05f, 1.05f} * fabs0;
+    const bool negx = v0.x < 0, negy = v0.y < 0;
+    const ba_f2 u = {negx ? -v1.x : v1.x, negy ? -v1.y : v1.y};
+    const bool lox = u.x < too_small.x, loy = u.y < too_small.y, hix = u.x > too_big.x, hiy = u.y > too_big.y;
+    const ba_f2 below = too_small - u, above = u - too_big;
+    const ba_f2 impact = scaler2 * ba_f2{lox ? below.x : above.x, loy ? below.y : above.y};
+    const ba_f2 rn = r + ba_f2{(negx == lox) ? -impact.x : impact.x, (negy == loy) ? -impact.y : impact.y};
+    return ba_f2{(lox || hix) ? rn.x : r.x, (loy || hiy) ? rn.y : r.y};
 }
 
 // L2DiffAsymmetric's in-place accumulation for one sample of hf[c] (libjxl / oracle l2_diff_asymmetric)
@@ -903,6 +925,11 @@ __device__ __forceinline__ void malta_rows_xy(const ba_f2 *__restrict__ base, ba
 // FINAL && STORE (CE_FLAG_BUTTERAUGLI_DIFFMAP): the same reductions, and the final value of every pixel is also written
 // to `diffmap` ([pair][h][pitch] of the full resolution), one float2 per thread and row - the thread's two columns (0 past
 // the image's right edge, inside the pitch padding).
+// The tile fill of a band (profiles/r08_malta_fill.md): a thread's three quads of the 72 x 40 region are laid out and their
+// twelve float4 loads requested before any arithmetic; a position's X and Y samples are pre-scaled as one pair
+// (malta_pre_diff_xy); nothing is loaded or computed behind a branch - a position outside the image is computed on
+// whatever stands at the plane's start and 0 is selected for it at the end.  A block whose whole region lies inside the
+// image (decided once, uniformly) takes the same body without the flags and selects.
 template <int MR, int NT, bool FINAL, bool STORE>
 __global__ __launch_bounds__(NT, NT == 256 ? 3 : 4) void k_ba_malta_l2_xy(const float *__restrict__ psy, const uint32_t *__restrict__ pair_ref,
                                                            const float *__restrict__ blurred, const float *__restrict__ mask_vals,
@@ -925,64 +952,111 @@ __global__ __launch_bounds__(NT, NT == 256 ? 3 : 4) void k_ba_malta_l2_xy(const 
     const int tq = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const float wmul[9] = {400.0f, 1.50815703118f, 0.0f, 2150.0f, 10.6195433239f, 16.2176043152f, 29.2353797994f, 0.844626970982f, 0.703646627719f};
     const float hf_asymmetry = 1.0f;
+    // The tile fill.  Per band a thread fills NI quads (four adjacent positions of one tile row): quads threadIdx.x + k NT of
+    // the tile's MLR x ML / 4.  NQ is no multiple of NT: the threads past the last quad fill it once more - the same values to
+    // the same addresses, and it lies in the halo, so no L2 term is added twice - so that no quad stands behind a branch,
+    // which would keep its loads behind it too.
+    constexpr int NQ = MLR * (ML / 4), NI = (NQ + NT - 1) / NT;
+    static_assert(MH > 0, "the tile's last quad must hold no own pixel");
+    // A quad's word: bits 0 .. 3 - sample j lies inside the image (gx + j < w: the pitch padding is outside); FQ_LOAD - its 16
+    // bytes lie inside the plane's rows; FQ_OWN - it holds own pixels of the tile, whose L2 terms this block adds; the tile
+    // row from bit 8, the quad of the row from bit 16.
+    constexpr uint32_t FQ_LOAD = 16, FQ_OWN = 32;
+    // A block whose whole region lies inside the image (84 of the 128 tiles of a 512 x 512 image) has every flag of every quad
+    // set: it fills without predicates and selects.  Uniform - bx, by and g are scalars.
+    const bool interior = x0 >= 0 && y0 >= 0 && x0 + ML <= (int)g.w && y0 + MLR <= (int)g.h;
 #pragma unroll
     for (int band = 0; band < 3; band++) {
-        const malta_params mpx = mb.p[0][band], mpy = mb.p[1][band];
+        const malta_params_xy mp = mb.p[band];
         const uint32_t plane0 = band == 0 ? UHF0 : band == 1 ? HF0 : MF0;  // channel X's plane; channel Y's is the next one
         const float *pax = a + (size_t)plane0 * g.plane, *pbx = b + (size_t)plane0 * g.plane;
         const float *pay = pax + g.plane, *pby = pbx + g.plane;
-        for (int i = threadIdx.x; i < MLR * (ML / 4); i += NT) {
-            const int ly = i / (ML / 4), lq = i % (ML / 4), gx = x0 + 4 * lq, gy = y0 + ly;
-            float4 vax = make_float4(0.f, 0.f, 0.f, 0.f), vbx = vax, vay = vax, vby = vax;
+        // The quads' words are formed ahead of the band's arithmetic, once per band and not once per block: they are the same
+        // for the three bands, but kept across the line sums - which take the whole register budget of four waves per SIMD -
+        // they cost the kernel a wave (168 VGPRs, 5 - 9 of them spilled; profiles/r08_malta_fill.md).  The empty asm keeps
+        // the compiler from keeping them by itself.
+        uint32_t fq[NI];
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+#pragma unroll
+        for (int k = 0; k < NI; k++) {
+            const int i = min(tid + k * NT, NQ - 1), ly = i / (ML / 4), lq = i % (ML / 4), gx = x0 + 4 * lq, gy = y0 + ly;
             const bool in = gx >= 0 && gy >= 0 && gx < (int)g.pitch && gy < (int)g.h;
-            if (in) {
-                const size_t o = (size_t)gy * g.pitch + gx;
-                vax = *reinterpret_cast<const float4 *>(pax + o);
-                vbx = *reinterpret_cast<const float4 *>(pbx + o);
-                vay = *reinterpret_cast<const float4 *>(pay + o);
-                vby = *reinterpret_cast<const float4 *>(pby + o);
-            }
-            const bool i0 = in && gx < (int)g.w, i1 = in && gx + 1 < (int)g.w, i2 = in && gx + 2 < (int)g.w, i3 = in && gx + 3 < (int)g.w;
-            float4 r01, r23;  // (x0, y0, x1, y1), (x2, y2, x3, y3)
-            r01.x = i0 ? malta_pre_diff(vax.x, vbx.x, mpx) : 0.0f;
-            r01.y = i0 ? malta_pre_diff(vay.x, vby.x, mpy) : 0.0f;
-            r01.z = i1 ? malta_pre_diff(vax.y, vbx.y, mpx) : 0.0f;
-            r01.w = i1 ? malta_pre_diff(vay.y, vby.y, mpy) : 0.0f;
-            r23.x = i2 ? malta_pre_diff(vax.z, vbx.z, mpx) : 0.0f;
-            r23.y = i2 ? malta_pre_diff(vay.z, vby.z, mpy) : 0.0f;
-            r23.z = i3 ? malta_pre_diff(vax.w, vbx.w, mpx) : 0.0f;
-            r23.w = i3 ? malta_pre_diff(vay.w, vby.w, mpy) : 0.0f;
-            float4 *dst = reinterpret_cast<float4 *>(s + ly * ML + 4 * lq);
-            dst[0] = r01;
-            dst[1] = r23;
-            // The HF / MF samples of the tile's OWN pixels are in registers here: their L2DiffAsymmetric (hf) / L2Diff (mf)
-            // terms join the running block_diff_ac sums now (after the previous band's Malta sums, before this band's),
-            // instead of being loaded again - 32 B per pixel - by the epilogue.  The same in-place accumulations as the
-            // lineage's, in another order: the oracle's switch "ba_l2_early" is this order bit for bit.
-            if (band >= 1 && ly >= MH && ly < MH + MR && lq >= MH / 4 && lq < (MH + MT) / 4 && gy < (int)g.h) {
-                float4 *pa = reinterpret_cast<float4 *>(s_acc + (ly - MH) * MT + 4 * lq - MH);
-                float4 t01 = pa[0], t23 = pa[1];  // (x0, y0, x1, y1), (x2, y2, x3, y3)
-                if (band == 1) {
-                    const float gx_ = wmul[0] * hf_asymmetry * 0.8f, lx_ = wmul[0] / hf_asymmetry * 0.8f;
-                    const float gy_ = wmul[1] * hf_asymmetry * 0.8f, ly_ = wmul[1] / hf_asymmetry * 0.8f;
-                    if (i0) t01.x = l2_asym_acc(t01.x, vax.x, vbx.x, gx_, lx_), t01.y = l2_asym_acc(t01.y, vay.x, vby.x, gy_, ly_);
-                    if (i1) t01.z = l2_asym_acc(t01.z, vax.y, vbx.y, gx_, lx_), t01.w = l2_asym_acc(t01.w, vay.y, vby.y, gy_, ly_);
-                    if (i2) t23.x = l2_asym_acc(t23.x, vax.z, vbx.z, gx_, lx_), t23.y = l2_asym_acc(t23.y, vay.z, vby.z, gy_, ly_);
-                    if (i3) t23.z = l2_asym_acc(t23.z, vax.w, vbx.w, gx_, lx_), t23.w = l2_asym_acc(t23.w, vay.w, vby.w, gy_, ly_);
-                } else {
-                    auto l2 = [](float total, float v0, float v1, float w) {
-                        const float diff = v0 - v1;
-                        return __builtin_fmaf(diff * diff, w, total);
-                    };
-                    if (i0) t01.x = l2(t01.x, vax.x, vbx.x, wmul[3]), t01.y = l2(t01.y, vay.x, vby.x, wmul[4]);
-                    if (i1) t01.z = l2(t01.z, vax.y, vbx.y, wmul[3]), t01.w = l2(t01.w, vay.y, vby.y, wmul[4]);
-                    if (i2) t23.x = l2(t23.x, vax.z, vbx.z, wmul[3]), t23.y = l2(t23.y, vay.z, vby.z, wmul[4]);
-                    if (i3) t23.z = l2(t23.z, vax.w, vbx.w, wmul[3]), t23.w = l2(t23.w, vay.w, vby.w, wmul[4]);
-                }
-                pa[0] = t01;
-                pa[1] = t23;
-            }
+            const bool own = ly >= MH && ly < MH + MR && lq >= MH / 4 && lq < (MH + MT) / 4 && gy < (int)g.h;
+            uint32_t m = (uint32_t)ly << 8 | (uint32_t)lq << 16 | (own ? FQ_OWN : 0u) | (in ? FQ_LOAD : 0u);
+#pragma unroll
+            for (int j = 0; j < 4; j++) m |= (in && gx + j < (int)g.w) ? 1u << j : 0u;
+            fq[k] = m;
         }
+        auto fill = [&](auto interior_c) {
+            constexpr bool INTERIOR = decltype(interior_c)::value;
+            // the band's loads of all the thread's quads are requested together, ahead of the first pre-scaling: the first
+            // quad waits for its own 64 bytes only, the others' round trips pass behind its arithmetic.  No branch stands
+            // between the quads (band 0) or only the L2 terms' (bands 1, 2), so their chains are scheduled into each other.
+            float4 vax[NI], vbx[NI], vay[NI], vby[NI];
+            auto load = [&](int k) {
+                // no branch around a load: a quad with nothing to load reads the plane's first 16 bytes instead, and what it
+                // makes of them is never used (0 is selected for a position outside the image, the L2 terms look at the flags)
+                const bool in = INTERIOR || (fq[k] & FQ_LOAD);
+                const int gy = in ? y0 + (int)(fq[k] >> 8 & 0xff) : 0, gx = in ? x0 + 4 * (int)(fq[k] >> 16) : 0;
+                const size_t o = (size_t)gy * g.pitch + gx;
+                vax[k] = *reinterpret_cast<const float4 *>(pax + o);
+                vbx[k] = *reinterpret_cast<const float4 *>(pbx + o);
+                vay[k] = *reinterpret_cast<const float4 *>(pay + o);
+                vby[k] = *reinterpret_cast<const float4 *>(pby + o);
+            };
+            auto scale = [&](int k) {
+                const int ly = fq[k] >> 8 & 0xff, lq = fq[k] >> 16;
+                const bool i0 = INTERIOR || (fq[k] & 1), i1 = INTERIOR || (fq[k] & 2), i2 = INTERIOR || (fq[k] & 4), i3 = INTERIOR || (fq[k] & 8);
+                // computed on whatever was loaded (the denominator is norm1 + |..| > 0); outside the image and in the pitch
+                // padding the tile holds 0, selected afterwards
+                const ba_f2 zero = {0.0f, 0.0f};
+                const ba_f2 d0 = malta_pre_diff_xy(ba_f2{vax[k].x, vay[k].x}, ba_f2{vbx[k].x, vby[k].x}, mp);
+                const ba_f2 d1 = malta_pre_diff_xy(ba_f2{vax[k].y, vay[k].y}, ba_f2{vbx[k].y, vby[k].y}, mp);
+                const ba_f2 d2 = malta_pre_diff_xy(ba_f2{vax[k].z, vay[k].z}, ba_f2{vbx[k].z, vby[k].z}, mp);
+                const ba_f2 d3 = malta_pre_diff_xy(ba_f2{vax[k].w, vay[k].w}, ba_f2{vbx[k].w, vby[k].w}, mp);
+                const ba_f2 e0 = i0 ? d0 : zero, e1 = i1 ? d1 : zero, e2 = i2 ? d2 : zero, e3 = i3 ? d3 : zero;
+                float4 *dst = reinterpret_cast<float4 *>(s + ly * ML + 4 * lq);
+                dst[0] = make_float4(e0.x, e0.y, e1.x, e1.y);
+                dst[1] = make_float4(e2.x, e2.y, e3.x, e3.y);
+                // The HF / MF samples of the tile's OWN pixels are in registers here: their L2DiffAsymmetric (hf) / L2Diff (mf)
+                // terms join the running block_diff_ac sums now (after the previous band's Malta sums, before this band's),
+                // instead of being loaded again - 32 B per pixel - by the epilogue.  The same in-place accumulations as the
+                // lineage's, in another order: the oracle's switch "ba_l2_early" is this order bit for bit.
+                if (band >= 1 && (fq[k] & FQ_OWN)) {
+                    const float4 ax = vax[k], bx_ = vbx[k], ay = vay[k], by_ = vby[k];
+                    float4 *pa = reinterpret_cast<float4 *>(s_acc + (ly - MH) * MT + 4 * lq - MH);
+                    float4 t01 = pa[0], t23 = pa[1];  // (x0, y0, x1, y1), (x2, y2, x3, y3)
+                    if (band == 1) {
+                        const float gx_ = wmul[0] * hf_asymmetry * 0.8f, lx_ = wmul[0] / hf_asymmetry * 0.8f;
+                        const float gy_ = wmul[1] * hf_asymmetry * 0.8f, ly_ = wmul[1] / hf_asymmetry * 0.8f;
+                        if (i0) t01.x = l2_asym_acc(t01.x, ax.x, bx_.x, gx_, lx_), t01.y = l2_asym_acc(t01.y, ay.x, by_.x, gy_, ly_);
+                        if (i1) t01.z = l2_asym_acc(t01.z, ax.y, bx_.y, gx_, lx_), t01.w = l2_asym_acc(t01.w, ay.y, by_.y, gy_, ly_);
+                        if (i2) t23.x = l2_asym_acc(t23.x, ax.z, bx_.z, gx_, lx_), t23.y = l2_asym_acc(t23.y, ay.z, by_.z, gy_, ly_);
+                        if (i3) t23.z = l2_asym_acc(t23.z, ax.w, bx_.w, gx_, lx_), t23.w = l2_asym_acc(t23.w, ay.w, by_.w, gy_, ly_);
+                    } else {
+                        auto l2 = [](float total, float v0, float v1, float w) {
+                            const float diff = v0 - v1;
+                            return __builtin_fmaf(diff * diff, w, total);
+                        };
+                        if (i0) t01.x = l2(t01.x, ax.x, bx_.x, wmul[3]), t01.y = l2(t01.y, ay.x, by_.x, wmul[4]);
+                        if (i1) t01.z = l2(t01.z, ax.y, bx_.y, wmul[3]), t01.w = l2(t01.w, ay.y, by_.y, wmul[4]);
+                        if (i2) t23.x = l2(t23.x, ax.z, bx_.z, wmul[3]), t23.y = l2(t23.y, ay.z, by_.z, wmul[4]);
+                        if (i3) t23.z = l2(t23.z, ax.w, bx_.w, wmul[3]), t23.w = l2(t23.w, ay.w, by_.w, wmul[4]);
+                    }
+                    pa[0] = t01;
+                    pa[1] = t23;
+                }
+            };
+#pragma unroll
+            for (int k = 0; k < NI; k++) load(k);
+#pragma unroll
+            for (int k = 0; k < NI; k++) scale(k);
+        };
+        if (interior)
+            fill(std::true_type{});
+        else
+            fill(std::false_type{});
         __syncthreads();
 #pragma unroll 1
         for (int sub = 0; sub < MR / RSTEP; sub++) {
@@ -1187,7 +1261,7 @@ __global__ __launch_bounds__(TPB) void k_ba_score(const float *__restrict__ blk_
     }
 }
 
-// debug: div2_shared_rcp and ce_div_noscale against operator/ on pseudo-random operands of the ranges their call sites
+// debug: rcp_refined_xy / div_refined_xy (two numerators over one denominator) and ce_div_noscale against operator/ on pseudo-random operands of the ranges their call sites
 // use.  The range is the union over the batch kinds of what the oracle's probe records per site ("Operand ranges",
 // tests/test_wide_content_cpu.py), rounded outward to whole binades: [2^-40, 2^92) - RGB8 and deep batches stay inside
 // [2^-40, 2^40), a linear batch reaches 2^91.2 (cbrt_poly's second numerator at x = 1024) and 2^-20 (its first denominator
@@ -1212,8 +1286,9 @@ __global__ __launch_bounds__(256) void k_div_sweep(uint64_t seed, uint64_t count
         const float b = __uint_as_float((eb << 23) | mb | ((uint32_t)(x >> 61) & 1u) << 31);
         float a0 = __uint_as_float((ea << 23) | ma | ((uint32_t)(x >> 60) & 1u) << 31), a1 = __uint_as_float((e2 << 23) | m2);
         if ((x >> 50 & 1023u) == 0) a0 = 0.0f;
-        float q0, q1;
-        div2_shared_rcp(a0, a1, b, q0, q1);
+        // the Malta fill's form: both numerators as one pair over the denominator twice
+        const ba_f2 bb = {b, b}, q01 = div_refined_xy(ba_f2{a0, a1}, bb, rcp_refined_xy(bb));
+        const float q0 = q01.x, q1 = q01.y;
         const float w0 = a0 / b, w1 = a1 / b;
         const bool in0 = a0 == 0.0f || (fabsf(w0) >= 1.17549435e-38f && fabsf(w0) <= 3.40282347e+38f);
         const bool in1 = fabsf(w1) >= 1.17549435e-38f && fabsf(w1) <= 3.40282347e+38f;
@@ -1467,8 +1542,7 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
         // 32-row tiles, 256 threads: the 64-row / 512-thread tile was slower (profiles/r02_experiments.md section 6,
         // r03_experiments.md section 12)
         malta_bands mb;
-        mb.p[0][0] = mUhfX; mb.p[0][1] = mHfX; mb.p[0][2] = mMfX;
-        mb.p[1][0] = mUhfY; mb.p[1][1] = mHfY; mb.p[1][2] = mMfY;
+        mb.p[0] = malta_pair(mUhfX, mUhfY); mb.p[1] = malta_pair(mHfX, mHfY); mb.p[2] = malta_pair(mMfX, mMfY);
         const uint32_t tiles_x = (d.w + MT - 1) / MT, tiles_y = (d.h + 31) / 32;
         if ((rc = ce_build_xcd_list(b, n_pairs, ce_xcd_keys{1, tiles_x * tiles_y, 1}, &b->ba.work[l])) != CE_OK) return rc;
         const bool has_sub = b->ba.levels == 2;
