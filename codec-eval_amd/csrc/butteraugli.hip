@@ -493,7 +493,16 @@ __device__ __forceinline__ float maximum_clamp(float v, float maxval)
 // scratch planes (`aux`): LF stage -> raw MF -> aux_out;  MF stage: aux_in -> MF (psy), raw HF -> aux_out;  HF stage:
 // aux_in -> HF, UHF (psy), mask input.  (The 33-tap LF stage keeps its separate row pass: its halo would be half a tile.)
 //   EPI_MASK (1 plane per slot, sigma 2.7, HV): the mask input's blur, no pointwise stage: tmp[slot] -> aux_out[slot]
-enum { EPI_LF = 0, EPI_MF = 1, EPI_HF = 2, EPI_MASK = 3 };
+//   EPI_LF_TERM: EPI_LF for a launch whose references' state is kept (ce_plan.h: ce_plan_ba_lf_term_in_blur).  A distorted
+//     slot's psy LF has one reader, the LF term of CombineChannelsToDiffmap in Malta's epilogue, and that term's other operands -
+//     the reference's psy LF and dc_maskval - are in place before the launch: the term is formed here, on the registers that
+//     hold the distorted LF, with the epilogue's expressions in its order (the same float), and stored to the slot's LF0 plane;
+//     LF1 and LF2 of a distorted slot are not written.  Such a launch skips the reference slots (their state is kept), so
+//     every slot the instance sees is a distorted one.
+enum { EPI_LF = 0, EPI_MF = 1, EPI_HF = 2, EPI_MASK = 3, EPI_LF_TERM = 4 };
+
+// SetL2Diff's weights of the three LF channels (wmul[6 .. 8] of the Malta kernel)
+__device__ constexpr float BA_LF_WMUL[3] = {29.2353797994f, 0.844626970982f, 0.703646627719f};
 
 // MaskPsychoImage's input at one pixel: DiffPrecompute of (UHF + HF) of X and Y (pointwise on the FINAL band values)
 __device__ __forceinline__ float mask_pre_one(float uhf0, float hf0, float uhf1, float hf1)
@@ -512,9 +521,24 @@ template <int LEN, int EPI, bool HV, int TR>
 __global__ __launch_bounds__(TPB) void k_ba_blur_v_split(const float *__restrict__ tmp, const float *__restrict__ xyb,
                                                          float *__restrict__ psy, ce_plane_geom g, blur_kernel bk, float inv_wsum,
                                                          uint32_t n_refs_used, uint32_t max_refs, ba_slot_grid sg,
-                                                         float *__restrict__ mask_in, float *__restrict__ aux_out)
+                                                         float *__restrict__ mask_in, float *__restrict__ aux_out,
+                                                         const uint32_t *__restrict__ pair_ref, const float *__restrict__ ref_psy,
+                                                         const float *__restrict__ mask_vals, const uint2 *__restrict__ lf_work)
 {
-    const ba_slot_item it = ba_slot_decode3(sg, 1, blockIdx.x, blockIdx.y, blockIdx.z);  // (tile, slot): ba_slot_order.h
+    // (pair_ref, ref_psy, mask_vals, lf_work: EPI_LF_TERM only.  ref_psy is psy again, for the references' planes, which this
+    // launch only reads: through a pointer of their own the loads need not wait for the stores of the pixel before.)
+    // (tile, slot): ba_slot_order.h - or, lf_work given, a 1-D launch over that list (ce_plan_xcd_list with one key per tile
+    // column: tile = row | column << 16, pair), which keeps a column's tiles of all pairs of one reference on one XCD - a tile
+    // is followed by the same tile of the reference's other pairs, whose L2 then serves the reference's lines to all of them,
+    // and by the tile below, which shares its halo rows
+    auto decode = [&]() {
+        if (EPI == EPI_LF_TERM && lf_work) {
+            const uint2 wi = lf_work[blockIdx.x];
+            return ba_slot_item{wi.x >> 16, wi.x & 0xffffu, 0, n_refs_used + wi.y, wi.x != ~0u};
+        }
+        return ba_slot_decode3(sg, 1, blockIdx.x, blockIdx.y, blockIdx.z);
+    };
+    const ba_slot_item it = decode();
     if (!it.live) return;
     constexpr int NP = EPI == EPI_HF ? 2 : EPI == EPI_MASK ? 1 : 3;
     // 64 columns x 64 rows per block (two 8-row groups per thread): the halo of LEN - 1 rows is read once per 64 rows
@@ -627,6 +651,68 @@ __global__ __launch_bounds__(TPB) void k_ba_blur_v_split(const float *__restrict
     }
     if (!col_live) return;
     const size_t pl = g.plane;
+    if constexpr (EPI == EPI_LF_TERM) {
+        // Every slot of such a launch is a distorted one: pair it.z - n_refs_used, whose reference is the same for the whole
+        // block.  Two rows at a time: their 14 loads (raw XYB, the reference's LF, dc_maskval) are requested together, from
+        // addresses that no branch guards - a row past the image reads the last row instead and stores nothing.  (Behind a
+        // branch per row the kernel made two dependent round trips for every row and lost 0.87 ms per step; four rows at a
+        // time take 113 VGPRs and the fifth block of a CU: profiles/r09_ba_lf_term.md.)
+        const size_t rslot = (uint32_t)__builtin_amdgcn_readfirstlane((int)pair_ref[it.z - n_refs_used]);
+        const float *xs = xyb + (size_t)slot * 3 * pl + gx, *a = ref_psy + (rslot * PSY + LF0) * pl + gx;
+        const float *dcm = mask_vals + (rslot * 2 + 1) * pl + gx;
+        float *raw = aux_out + (size_t)slot * 3 * pl + gx, *term = psy + ((size_t)slot * PSY + LF0) * pl + gx;
+        constexpr int ROWS = 2;
+#pragma unroll
+        for (int part = 0; part < PARTS; part++) {
+            const int gy0 = y0 + 32 * part + 8 * wv;
+            if (gy0 >= (int)g.h) break;
+#pragma unroll
+            for (int o0 = 0; o0 < BW_OUT; o0 += ROWS) {
+                float vx[ROWS][3], va[ROWS][3], vm[ROWS];
+#pragma unroll
+                for (int k = 0; k < ROWS; k++) {
+                    const size_t px = (size_t)min(gy0 + o0 + k, (int)g.h - 1) * g.pitch;
+#pragma unroll
+                    for (int c = 0; c < 3; c++) vx[k][c] = xs[c * pl + px], va[k][c] = a[c * pl + px];
+                    vm[k] = dcm[px];
+                }
+                // (the empty asm keeps the compiler from moving each row's loads down to the row's stores, behind its branch)
+#pragma unroll
+                for (int k = 0; k < ROWS; k++) {
+#pragma unroll
+                    for (int c = 0; c < 3; c++) asm volatile("" : "+v"(vx[k][c]), "+v"(va[k][c]));
+                    asm volatile("" : "+v"(vm[k]));
+                }
+#pragma unroll
+                for (int k = 0; k < ROWS; k++) {
+                    const int o = o0 + k;
+                    if (gy0 + o >= (int)g.h) break;
+                    const size_t px = (size_t)(gy0 + o) * g.pitch;
+                    const float lx = res[0][part][o], ly = res[1][part][o], lb = res[2][part][o];
+                    raw[px] = vx[k][0] - lx;  // raw MF, as EPI_LF
+                    raw[px + pl] = vx[k][1] - ly;
+                    raw[px + 2 * pl] = vx[k][2] - lb;
+                    // XybLowFreqToVals, as EPI_LF
+                    const float xmul = 33.832837186260f, ymul = 14.458268100570f, bmul = 49.87984651440f, y_to_b_mul = -0.362267051518f;
+                    const float bb = __builtin_fmaf(y_to_b_mul, ly, lb);
+                    const float lf[3] = {lx * xmul, ly * ymul, bb * bmul};
+                    // the LF term of Malta's epilogue (k_ba_malta_l2_xy: dcv, mc_dc), expression for expression
+                    float dcv[3];
+#pragma unroll
+                    for (int c = 0; c < 3; c++) {
+                        const float diff = va[k][c] - lf[c];
+                        dcv[c] = (diff * diff) * BA_LF_WMUL[c];
+                    }
+                    const float dc_maskval = vm[k];
+                    float dc0 = dcv[0], dc1 = dcv[1], dc2 = dcv[2];
+                    const float one = 1.0f;
+                    dc0 *= one;
+                    term[px] = dc0 * dc_maskval + dc1 * dc_maskval + dc2 * dc_maskval;
+                }
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int part = 0; part < PARTS; part++) {
         const int gy0 = y0 + 32 * part + 8 * wv;
@@ -936,7 +1022,8 @@ __global__ __launch_bounds__(NT, NT == 256 ? 3 : 4) void k_ba_malta_l2_xy(const 
                                                            float *__restrict__ diffmap, ce_plane_geom g, uint32_t max_refs,
                                                            malta_bands mb, const uint2 *__restrict__ work, uint32_t tiles_x,
                                                            const float *__restrict__ sub_map, ce_plane_geom gs, int has_sub,
-                                                           float *__restrict__ blk_max, double *__restrict__ blk_sums, uint32_t n_blocks)
+                                                           float *__restrict__ blk_max, double *__restrict__ blk_sums, uint32_t n_blocks,
+                                                           int lf_term)
 {
     constexpr int MLR = MR + 2 * MH, RSTEP = NT / 32;  // tile rows; output rows per step of the whole block
     __shared__ __attribute__((aligned(16))) ba_f2 s[MLR * ML];
@@ -1096,23 +1183,30 @@ __global__ __launch_bounds__(NT, NT == 256 ? 3 : 4) void k_ba_malta_l2_xy(const 
                 total = __builtin_fmaf(diff * diff, wmul[3 + c], total);
             }
             acv[c] = total;
-            {  // SetL2Diff on lf[c]
-                const float diff = a[(LF0 + c) * g.plane + o] - b[(LF0 + c) * g.plane + o];
-                dcv[c] = (diff * diff) * wmul[6 + c];
-            }
         }
         // CombineChannelsToDiffmap for this pixel (the mask values come from k_ba_mask_vals, once per reference): the
         // block_diff_ac / block_diff_dc triples never leave registers
         const size_t rslot = pair_ref[p];
-        const float maskval = mask_vals[(rslot * 2 + 0) * g.plane + o], dc_maskval = mask_vals[(rslot * 2 + 1) * g.plane + o];
+        const float maskval = mask_vals[(rslot * 2 + 0) * g.plane + o];
         const float mdiff = blurred[rslot * g.plane + o] - blurred[((size_t)max_refs + p) * g.plane + o];
         float ac0 = acv[0], ac1 = acv[1], ac2 = acv[2];
-        float dc0 = dcv[0], dc1 = dcv[1], dc2 = dcv[2];
         ac1 += 10.0f * mdiff * mdiff;  // kMaskToErrorMul
         const float xmul = 1.0f;
         ac0 *= xmul;
-        dc0 *= xmul;
-        const float mc_dc = dc0 * dc_maskval + dc1 * dc_maskval + dc2 * dc_maskval;
+        float mc_dc;
+        if (lf_term) {  // uniform: the LF column blur formed the term (EPI_LF_TERM) into the distorted slot's LF0 plane
+            mc_dc = b[LF0 * g.plane + o];
+        } else {
+            const float dc_maskval = mask_vals[(rslot * 2 + 1) * g.plane + o];
+#pragma unroll
+            for (uint32_t c = 0; c < 3; c++) {  // SetL2Diff on lf[c]
+                const float diff = a[(LF0 + c) * g.plane + o] - b[(LF0 + c) * g.plane + o];
+                dcv[c] = (diff * diff) * wmul[6 + c];
+            }
+            float dc0 = dcv[0], dc1 = dcv[1], dc2 = dcv[2];
+            dc0 *= xmul;
+            mc_dc = dc0 * dc_maskval + dc1 * dc_maskval + dc2 * dc_maskval;
+        }
         const float mc_ac = ac0 * maskval + ac1 * maskval + ac2 * maskval;
         float d = sqrtf(mc_dc + mc_ac);
         if (!FINAL) {
@@ -1402,6 +1496,14 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
     // intensity target are still in place?  Then only the distorted slots go through the per-image chain
     const bool cached = b->refs.reuse(CE_REF_BUTTERAUGLI, d_refs, n_refs_used, ce_ref_param_f32(intensity_target));
     const uint32_t z0 = cached ? n_refs_used : 0, nz = n_slots - z0;
+    // Where the LF term of CombineChannelsToDiffmap is formed (ce_plan.h: ce_plan_ba_lf_term_in_blur): in the LF column blur
+    // when the references' LF planes and mask values are already in place, else in Malta's epilogue as always.
+    // CE_BA_LF_TERM=0 forces the latter, for A/B runs; 2 forms the term in the blur but keeps the blur's launches in slot
+    // order, where 1 (the default) walks the reference-ordered list (k_ba_blur_v_split: lf_work).
+    static const int lf_term_mode = [] { const char *e = std::getenv("CE_BA_LF_TERM"); return e && e[0] >= '0' && e[0] <= '2' ? e[0] - '0' : 1; }();
+    const bool lf_term = ce_plan_ba_lf_term_in_blur(lf_term_mode != 0, cached);
+// the arguments of k_ba_blur_v_split that only EPI_LF_TERM reads
+#define BA_NO_LF_TERM (const uint32_t *)nullptr, (const float *)nullptr, (const float *)nullptr, (const uint2 *)nullptr
     const blur_kernel k12 = make_kernel(1.2f), kLf = make_kernel(7.15593339443f), kHf = make_kernel(3.22489901262f),
                       kUhf = make_kernel(1.56416327805f), kMask = make_kernel(2.7f);
     float sw = 0.0f;
@@ -1513,14 +1615,31 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
             // 32 rows per block of the column / fused stages (26 / 21 KB of LDS and ~100 / 56 registers: five blocks per
             // CU).  64 rows (smaller halo, 45 / 38 KB, three or four blocks) measured equal or slower
             // (profiles/r02_experiments.md section 18, r03_experiments.md section 12).
-            CE_LAUNCH_ON(ctx, st, "ba_blur_v_lf", (k_ba_blur_v_split<33, EPI_LF, false, 32>), SB(sg_vlf), dim3(TPB), 0, (const float *)sA,
-                         (const float *)sC, psy, g, kLf, inv_weight_sum(kLf), n_refs_used, mr, sg_vlf, (float *)nullptr, sB);
+            // (lf_term: the distorted slots' LF term instead of their three LF planes, see EPI_LF_TERM)
+            if (lf_term) {
+                // A launch large enough for the slot order spreads a reference's distorted slots over the XCDs, and every
+                // XCD's L2 then fetches the reference's lines for itself (16 B per pixel: profiles/r09_ba_lf_term.md).  It
+                // walks a list instead that keeps the pairs of a reference, tile by tile, on one XCD (one key per tile column:
+                // a tile's lower neighbour follows it on the same XCD, as in slot order).  Smaller launches keep their grid.
+                const uint2 *lf_work = nullptr;
+                dim3 grid = SB(sg_vlf);
+                if (sg_vlf.by_xcd && lf_term_mode == 1 && sg_vlf.tiles_x <= 0xffffu && sg_vlf.tiles_y <= 0xffffu) {
+                    if ((rc = ce_build_xcd_list(b, n_pairs, ce_xcd_keys{sg_vlf.tiles_x, 1, sg_vlf.tiles_y}, &b->ba.work_lf[l])) != CE_OK) return rc;
+                    lf_work = b->ba.work_lf[l].d;
+                    grid = dim3(b->ba.work_lf[l].len);
+                }
+                CE_LAUNCH_ON(ctx, st, "ba_blur_v_lf", (k_ba_blur_v_split<33, EPI_LF_TERM, false, 32>), grid, dim3(TPB), 0,
+                             (const float *)sA, (const float *)sC, psy, g, kLf, inv_weight_sum(kLf), n_refs_used, mr, sg_vlf, (float *)nullptr,
+                             sB, (const uint32_t *)b->d_pair_ref, (const float *)psy, (const float *)b->ba.mask_vals[l], lf_work);
+            } else
+                CE_LAUNCH_ON(ctx, st, "ba_blur_v_lf", (k_ba_blur_v_split<33, EPI_LF, false, 32>), SB(sg_vlf), dim3(TPB), 0, (const float *)sA,
+                             (const float *)sC, psy, g, kLf, inv_weight_sum(kLf), n_refs_used, mr, sg_vlf, (float *)nullptr, sB, BA_NO_LF_TERM);
             // MF: row + column pass of raw MF (sB) + split: MF -> psy, raw HF -> sA (its old contents are dead)
             CE_LAUNCH_ON(ctx, st, "ba_blur_hv_mf", (k_ba_blur_v_split<15, EPI_MF, true, 32>), SB(sg_mf), dim3(TPB), 0, (const float *)sB,
-                         (const float *)nullptr, psy, g, kHf, inv_weight_sum(kHf), n_refs_used, mr, sg_mf, (float *)nullptr, sA);
+                         (const float *)nullptr, psy, g, kHf, inv_weight_sum(kHf), n_refs_used, mr, sg_mf, (float *)nullptr, sA, BA_NO_LF_TERM);
             // HF: row + column pass of raw HF (sA) + split: HF, UHF -> psy, the mask input -> sB (raw MF is dead)
             CE_LAUNCH_ON(ctx, st, "ba_blur_hv_hf", (k_ba_blur_v_split<7, EPI_HF, true, 32>), SB(sg_hf), dim3(TPB), 0, (const float *)sA,
-                         (const float *)nullptr, psy, g, kUhf, inv_weight_sum(kUhf), n_refs_used, mr, sg_hf, sB, (float *)nullptr);
+                         (const float *)nullptr, psy, g, kUhf, inv_weight_sum(kUhf), n_refs_used, mr, sg_hf, sB, (float *)nullptr, BA_NO_LF_TERM);
         }
 
         // mask input: DiffPrecompute of HF + UHF (written by the HF split's epilogue into scratch plane 1), blurred with sigma 2.7 -
@@ -1533,7 +1652,7 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
                 return CE_ERR_BACKEND;
             }
             CE_LAUNCH_ON(ctx, st, "ba_blur_hv_mask", (k_ba_blur_v_split<13, EPI_MASK, true, 32>), SB(sg_mask), dim3(TPB), 0, (const float *)scr[1],
-                      (const float *)nullptr, psy, g, kMask, inv_weight_sum(kMask), n_refs_used, mr, sg_mask, (float *)nullptr, b->ba.mask[l]);
+                      (const float *)nullptr, psy, g, kMask, inv_weight_sum(kMask), n_refs_used, mr, sg_mask, (float *)nullptr, b->ba.mask[l], BA_NO_LF_TERM);
         }
         if (!cached)
             CE_LAUNCH_ON(ctx, st, "ba_mask_vals", k_ba_mask_vals, G(n_refs_used), dim3(TPB), 0, (const float *)b->ba.mask[l], b->ba.mask_vals[l], g);
@@ -1550,7 +1669,7 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
 #define CE_MALTA_ARGS(FINAL, STORE)                                                                                                \
     psy, b->d_pair_ref, (const float *)b->ba.mask[l], (const float *)b->ba.mask_vals[l],                                               \
         STORE ? b->ba.map : FINAL ? (float *)nullptr : b->ba.diff[1], g, mr, mb, (const uint2 *)b->ba.work[l].d, tiles_x,             \
-        FINAL ? (const float *)b->ba.diff[1] : (const float *)nullptr, gsub, has_sub ? 1 : 0, b->ba.blk_max, b->ba.blk_sums, b->ba.blocks
+        FINAL ? (const float *)b->ba.diff[1] : (const float *)nullptr, gsub, has_sub ? 1 : 0, b->ba.blk_max, b->ba.blk_sums, b->ba.blocks, lf_term ? 1 : 0
         const dim3 gmalta(b->ba.work[l].len);
         if (l == 0) {
             final_tiles = tiles_x * tiles_y;
@@ -1565,6 +1684,7 @@ int ce_launch_butteraugli(ce_batch *b, const uint8_t *d_refs, uint32_t n_refs_us
         }
 #undef CE_MALTA_ARGS
     }
+#undef BA_NO_LF_TERM
     const auto &d0 = b->ba.lvl[0];
     CE_LAUNCH(ctx, "ba_score", k_ba_score, dim3(n_pairs), dim3(TPB), 0, b->ba.blk_max, b->ba.blk_sums, b->d_scores, b->ba.pnorm,
               b->ba.blocks, final_tiles, (double)d0.w * (double)d0.h);

@@ -256,6 +256,7 @@ struct ce_ba_set {
     ce_dev<double> pnorm;  // [pair] libjxl 3-norm of the last run
     uint32_t blocks = 0;
     ce_xcd_list work[2];  // Malta's launch order, per resolution level
+    ce_xcd_list work_lf[2];  // the LF column blur's launch order when it forms the LF term (EPI_LF_TERM), lazily
     bool engaged() const { return pnorm != nullptr; }
 };
 

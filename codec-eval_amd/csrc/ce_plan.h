@@ -146,6 +146,15 @@ inline int ce_plan_ssim2_ref_blur(bool enabled, bool keeps_state, bool handle, b
     return (reused && n_pairs > n_refs) ? CE_SSIM2_BLUR_SPLIT_BUILD : CE_SSIM2_BLUR_TODAY;
 }
 
+// Where a Butteraugli launch forms the LF term of CombineChannelsToDiffmap, mc_dc = sum over c of (lf_ref[c] - lf_dist[c])^2 *
+// w[c] * dc_maskval.  Both of its reference operands - the reference's LF planes and dc_maskval - are state that a launch
+// which found its references kept (`cached`) has in place before its first kernel: there the LF column blur forms the term
+// where the distorted LF is still in registers and writes one plane per distorted slot instead of three, and Malta's epilogue
+// reads that plane.  A batch's first launch, ce_eval_batch's pooled batches and everything else that rebuilds its references
+// makes the mask values AFTER the blurs, so it keeps the term in Malta's epilogue.  enabled = false (CE_BA_LF_TERM=0):
+// always there.
+inline bool ce_plan_ba_lf_term_in_blur(bool enabled, bool cached) { return enabled && cached; }
+
 // DSSIM's scale pyramid (Dssim::create_image, make_scales_recursive): level 0 is the image, and a level is halved (floor)
 // into the next only while it is at least 8 x 8, up to max_levels levels.  Writes the level sizes, returns their count (0
 // for an empty image).  The one rule of dssim.hip's working set and of ce_dssim_levels.
