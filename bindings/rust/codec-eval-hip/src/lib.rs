@@ -744,6 +744,32 @@ impl HipMetrics {
         Ok(out)
     }
 
+    /// `ce_eval_pair_msssim_map`: where one pair of packed RGB8 differs at `level` - see `HipBatch::ms_ssim_map`.
+    pub fn ms_ssim_map(&mut self, reference: &[u8], test: &[u8], width: u32, height: u32, levels: u32, level: u32, what: u32, block: u32,
+                       want_map: bool, thresholds_q32: &[u32]) -> Result<MsSsimMaps, HipError> {
+        let mut out = MsSsimMaps::sized(1, width, height, levels, level, block, want_map, thresholds_q32.len());
+        let rc = unsafe {
+            sys::ce_eval_pair_msssim_map(self.ctx, reference.as_ptr(), reference.len(), test.as_ptr(), test.len(), width, height, levels, level,
+                                         what, block, out.map_ptr(), out.map.len(), slice_or_null(thresholds_q32),
+                                         thresholds_q32.len() as u32, out.over_ptr())
+        };
+        self.check(rc, width, height, test.len())?;
+        Ok(out)
+    }
+
+    /// `ce_eval_pair_msssim_map_deep`: the same for packed u16 RGB of `depth` bits (8, 10, 12 or 16) on both sides.
+    pub fn ms_ssim_map_deep(&mut self, reference: &[u16], test: &[u16], depth: u32, width: u32, height: u32, levels: u32, level: u32,
+                            what: u32, block: u32, want_map: bool, thresholds_q32: &[u32]) -> Result<MsSsimMaps, HipError> {
+        let mut out = MsSsimMaps::sized(1, width, height, levels, level, block, want_map, thresholds_q32.len());
+        let rc = unsafe {
+            sys::ce_eval_pair_msssim_map_deep(self.ctx, reference.as_ptr(), reference.len() * 2, test.as_ptr(), test.len() * 2, depth, width,
+                                              height, levels, level, what, block, out.map_ptr(), out.map.len(),
+                                              slice_or_null(thresholds_q32), thresholds_q32.len() as u32, out.over_ptr())
+        };
+        self.check(rc, width, height, test.len() * 2)?;
+        Ok(out)
+    }
+
     /// `ce_yuv_plane_fidelity`: PSNR (`levels` 0), + SSIM (1), + MS-SSIM (5) of host Y'CbCr images plane by plane, on the planes
     /// as a decoder wrote them: `tests[i]` against `refs[pair_ref[i]]`, or against `refs[i]` without a pair table.  Every image is
     /// `width` x `height` with one subsampling and one depth.  Device surfaces go through `sys::ce_yuv_plane_fidelity` directly.
@@ -794,6 +820,36 @@ impl DeltaEItpMaps {
         let (cells_w, cells_h) = ((width + b - 1) / b, (height + b - 1) / b);
         let n = if want_map { count as usize * cells_w as usize * cells_h as usize } else { 0 };
         DeltaEItpMaps { map: vec![0u32; n], cells_w, cells_h, over: vec![0u64; count as usize * n_thresholds] }
+    }
+    fn map_ptr(&mut self) -> *mut u32 {
+        if self.map.is_empty() { std::ptr::null_mut() } else { self.map.as_mut_ptr() }
+    }
+    fn over_ptr(&mut self) -> *mut u64 {
+        if self.over.is_empty() { std::ptr::null_mut() } else { self.over.as_mut_ptr() }
+    }
+}
+
+/// What `ce_batch_msssim_map` returns: per pair and channel every valid position's `2^32 - q` in units of 2^-32
+/// (`sys::CE_MSSSIM_Q32` is an SSIM of 1.0), `q` the integer `ms_ssim` sums, saturated to `[0, u32::MAX]` - or at `block` 2 ..= 64
+/// the maximum of each block x block cell - as `[count][3][cells_h][cells_w]`, empty when no map was asked for; and
+/// `[count][3][n_thresholds]` counts of the positions above each threshold, empty without thresholds.  What the library refuses
+/// (`levels`, `level`, an image too small) leaves the map empty for it to refuse.
+pub struct MsSsimMaps {
+    pub map: Vec<u32>,
+    pub cells_w: u32,
+    pub cells_h: u32,
+    pub over: Vec<u64>,
+}
+
+impl MsSsimMaps {
+    fn sized(count: u32, width: u32, height: u32, levels: u32, level: u32, block: u32, want_map: bool, n_thresholds: usize) -> Self {
+        let b = block.max(1);
+        let (cells_w, cells_h) = match msssim_levels(width, height, levels) {
+            Some(lv) if (level as usize) < lv.len() => ((lv[level as usize].0 - 10 + b - 1) / b, (lv[level as usize].1 - 10 + b - 1) / b),
+            _ => (0, 0),
+        };
+        let n = if want_map { count as usize * 3 * cells_w as usize * cells_h as usize } else { 0 };
+        MsSsimMaps { map: vec![0u32; n], cells_w, cells_h, over: vec![0u64; count as usize * 3 * n_thresholds] }
     }
     fn map_ptr(&mut self) -> *mut u32 {
         if self.map.is_empty() { std::ptr::null_mut() } else { self.map.as_mut_ptr() }
@@ -1228,6 +1284,21 @@ impl HipBatch<'_> {
     pub fn ms_ssim(&mut self, n_pairs: u32, levels: u32) -> Result<Vec<sys::ce_msssim_scores>, HipError> {
         let mut out = vec![sys::ce_msssim_scores::default(); n_pairs as usize];
         let rc = unsafe { sys::ce_batch_msssim(self.handle, n_pairs, levels, out.as_mut_ptr()) };
+        self.check(rc, 0)?;
+        Ok(out)
+    }
+
+    /// `ce_batch_msssim_map`: where pairs `[first, first + count)` of an RGB8 or equal-depth deep batch differ at `level` of the
+    /// SSIM (`levels` 1) or MS-SSIM (5) pyramid - the per-position map of `what` (`sys::CE_MSSSIM_MAP_SSIM` or
+    /// `sys::CE_MSSSIM_MAP_CS`) at `block` 1 or its block x block cell maxima when `want_map`, and how many positions of each pair
+    /// and channel exceed each of up to `sys::CE_MSSSIM_MAP_MAX_THRESHOLDS` thresholds; one of the two must be asked for.
+    pub fn ms_ssim_map(&mut self, first: u32, count: u32, levels: u32, level: u32, what: u32, block: u32, want_map: bool,
+                       thresholds_q32: &[u32]) -> Result<MsSsimMaps, HipError> {
+        let mut out = MsSsimMaps::sized(count, self.width, self.height, levels, level, block, want_map, thresholds_q32.len());
+        let rc = unsafe {
+            sys::ce_batch_msssim_map(self.handle, first, count, levels, level, what, block, out.map_ptr(), out.map.len(),
+                                     slice_or_null(thresholds_q32), thresholds_q32.len() as u32, out.over_ptr())
+        };
         self.check(rc, 0)?;
         Ok(out)
     }

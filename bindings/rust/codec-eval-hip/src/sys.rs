@@ -291,6 +291,12 @@ pub const CE_BATCH_TESTS: u32 = 1;
 /// `CE_DELTA_E_ITP_MAX_THRESHOLDS`, and a Delta E ITP of 1.0 in the units of the maps and thresholds (`CE_DELTA_E_ITP_Q20`)
 pub const CE_DELTA_E_ITP_MAX_THRESHOLDS: u32 = 8;
 pub const CE_DELTA_E_ITP_Q20: u32 = 1 << 20;
+/// `CE_MSSSIM_MAP_MAX_THRESHOLDS`, an SSIM of 1.0 in the units of the SSIM / MS-SSIM maps and thresholds (`CE_MSSSIM_Q32`), and
+/// the two terms a map can hold (`CE_MSSSIM_MAP_SSIM`, `CE_MSSSIM_MAP_CS`)
+pub const CE_MSSSIM_MAP_MAX_THRESHOLDS: u32 = 8;
+pub const CE_MSSSIM_Q32: u64 = 1 << 32;
+pub const CE_MSSSIM_MAP_SSIM: u32 = 0;
+pub const CE_MSSSIM_MAP_CS: u32 = 1;
 
 /// `ce_pair_desc` (40 bytes): one item of the (image x codec x quality) grid, host pointers.
 #[repr(C)]
@@ -539,6 +545,15 @@ extern "C" {
                                height: u32, levels: u32, out: *mut ce_msssim_scores) -> c_int;
     pub fn ce_eval_pair_msssim_deep(ctx: *mut ce_ctx, reference: *const u16, reference_len: usize, test: *const u16, test_len: usize,
                                     depth: u32, width: u32, height: u32, levels: u32, out: *mut ce_msssim_scores) -> c_int;
+    pub fn ce_batch_msssim_map(b: *mut ce_batch, first: u32, count: u32, levels: u32, level: u32, what: u32, block: u32, map: *mut u32,
+                               map_len: usize, thresholds_q32: *const u32, n_thresholds: u32, over: *mut u64) -> c_int;
+    pub fn ce_eval_pair_msssim_map(ctx: *mut ce_ctx, reference: *const u8, reference_len: usize, test: *const u8, test_len: usize,
+                                   width: u32, height: u32, levels: u32, level: u32, what: u32, block: u32, map: *mut u32, map_len: usize,
+                                   thresholds_q32: *const u32, n_thresholds: u32, over: *mut u64) -> c_int;
+    pub fn ce_eval_pair_msssim_map_deep(ctx: *mut ce_ctx, reference: *const u16, reference_len: usize, test: *const u16, test_len: usize,
+                                        depth: u32, width: u32, height: u32, levels: u32, level: u32, what: u32, block: u32,
+                                        map: *mut u32, map_len: usize, thresholds_q32: *const u32, n_thresholds: u32,
+                                        over: *mut u64) -> c_int;
     pub fn ce_msssim_window(out: *mut c_double) -> c_int;
     pub fn ce_msssim_levels(w: u32, h: u32, levels: u32, n_levels: *mut u32, level_w: *mut u32, level_h: *mut u32) -> c_int;
     pub fn ce_yuv_plane_fidelity(ctx: *mut ce_ctx, width: u32, height: u32, refs: *const ce_yuv_image, n_refs: u32, tests: *const ce_yuv_image,

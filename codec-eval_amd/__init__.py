@@ -357,6 +357,9 @@ _PROTOTYPES = [
     ("ce_eval_pair_msssim_deep", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, C.POINTER(CeMsssimScores)]),
     ("ce_yuv_plane_fidelity", _i, [_vp, _u32, _u32, C.POINTER(CeYuvImage), _u32, C.POINTER(CeYuvImage), _u32, _vp, _u32,
                                C.POINTER(CePlaneScores)]),
+    ("ce_batch_msssim_map", _i, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
+    ("ce_eval_pair_msssim_map", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
+    ("ce_eval_pair_msssim_map_deep", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
     ("ce_msssim_window", _i, [_vp]),
     ("ce_msssim_levels", _i, [_u32, _u32, _u32, _vp, _vp, _vp]),
     ("ce_icc_describe", _i, [_vp, _sz, C.POINTER(CeIccDescription)]),
@@ -896,6 +899,35 @@ def _delta_e_itp_map(ctx: "Context", call, count: int, width: int, height: int, 
     over = None if thr is None else np.zeros((count, thr.size), np.uint64)
     ctx._check(call(m.ctypes.data if maps else None, m.size if maps else 0, thr.ctypes.data if thr is not None and thr.size else None,
                     thr.size if thr is not None else 0, over.ctypes.data if over is not None else None))
+    return m, over
+
+
+MSSSIM_Q32 = 1 << 32  # an SSIM of 1.0 in the units of the SSIM / MS-SSIM maps and their thresholds (CE_MSSSIM_Q32)
+MSSSIM_MAP_MAX_THRESHOLDS = 8  # CE_MSSSIM_MAP_MAX_THRESHOLDS
+_MSSSIM_MAP_WHAT = {"ssim": 0, "cs": 1}  # CE_MSSSIM_MAP_SSIM, CE_MSSSIM_MAP_CS
+
+
+def _msssim_map(ctx: "Context", call, count: int, width: int, height: int, levels: int, level: int, what: str, block: int,
+                thresholds_q32, maps: bool):
+    """The outputs of ce_batch_msssim_map / ce_eval_pair_msssim_map{,_deep} around call(what, map, map_len, thresholds, n, over):
+    (uint32 [count, 3, ceil(vh / block), ceil(vw / block)] or None, uint64 [count, 3, n] or None), vw x vh the level's valid
+    region.  What the library refuses (levels, level, the image's size) it refuses itself: the map is then empty."""
+    if what not in _MSSSIM_MAP_WHAT:
+        raise CodecEvalError(CE_ERR_INVALID_ARG, 'what must be "ssim" or "cs"')
+    if block < 1:
+        raise CodecEvalError(CE_ERR_INVALID_ARG, "block must be 1 or a power of two up to 64")
+    vw = vh = 0
+    if levels in (1, 5) and 0 <= level < levels and (min(width, height) >= 11 if levels == 1 else min(width, height) > 160):
+        w, h = width, height
+        for _ in range(level):
+            w, h = (w + (w & 1)) // 2, (h + (h & 1)) // 2
+        vw, vh = w - 10, h - 10
+    m = np.empty((max(count, 0), 3, -(-vh // block), -(-vw // block)), np.uint32) if maps else None
+    thr = None if thresholds_q32 is None else np.ascontiguousarray(thresholds_q32, dtype=np.uint32).reshape(-1)
+    over = None if thr is None else np.zeros((max(count, 0), 3, thr.size), np.uint64)
+    ctx._check(call(_MSSSIM_MAP_WHAT[what], m.ctypes.data if maps and m.size else None, m.size if maps else 0,
+                    thr.ctypes.data if thr is not None and thr.size else None, thr.size if thr is not None else 0,
+                    over.ctypes.data if over is not None else None))
     return m, over
 
 
@@ -1735,6 +1767,20 @@ class Context:
                                                        levels, C.byref(s)))
         return MsSsim.from_c(s)
 
+    def ms_ssim_map(self, reference, test, width: int, height: int, levels: int = 5, level: int = 0, what: str = "ssim", block: int = 1,
+                    thresholds_q32=None, maps: bool = True, depth: int = 0):
+        """Batch.ms_ssim_maps for one pair of packed uint8 RGB (depth 0; ce_eval_pair_msssim_map) or packed uint16 RGB of `depth`
+        bits on both sides (ce_eval_pair_msssim_map_deep): (uint32 [1, 3, ch, cw] or None, uint64 [1, 3, n] or None)."""
+        if depth == 0:
+            r, t = _buf(reference), _buf(test)
+            call = lambda wh, m, n, thr, k, over: lib().ce_eval_pair_msssim_map(  # noqa: E731
+                self._h, r.ctypes.data, r.size, t.ctypes.data, t.size, width, height, levels, level, wh, block, m, n, thr, k, over)
+        else:
+            r, t = _buf16(reference), _buf16(test)
+            call = lambda wh, m, n, thr, k, over: lib().ce_eval_pair_msssim_map_deep(  # noqa: E731
+                self._h, r.ctypes.data, r.nbytes, t.ctypes.data, t.nbytes, depth, width, height, levels, level, wh, block, m, n, thr, k, over)
+        return _msssim_map(self, call, 1, width, height, levels, level, what, block, thresholds_q32, maps)
+
     def plane_fidelity(self, refs: Sequence["YuvImage"], tests: Sequence["YuvImage"], width: int, height: int,
                        pair_ref: Optional[Sequence[int]] = None, levels: int = 5) -> List[PlaneScores]:
         """PSNR (levels = 0), + SSIM (1), + MS-SSIM (5) of Y'CbCr images plane by plane, on the planes as a decoder wrote
@@ -2295,6 +2341,19 @@ class Batch:
         out = (CeMsssimScores * max(n_pairs, 1))()
         self.ctx._check(lib().ce_batch_msssim(self._h, n_pairs, levels, out))
         return [MsSsim.from_c(out[i]) for i in range(n_pairs)]
+
+    def ms_ssim_maps(self, first: int, count: int, levels: int = 5, level: int = 0, what: str = "ssim", block: int = 1, thresholds_q32=None,
+                     maps: bool = True):
+        """Where pairs [first, first + count) of an RGB8 or equal-depth deep batch differ at `level` of the SSIM (levels = 1) or
+        MS-SSIM (5) pyramid (ce_batch_msssim_map): at every valid position of R, G and B the dissimilarity 2^32 - q in units of
+        2^-32 (MSSSIM_Q32 is an SSIM of 1.0), q the very integer ms_ssim() sums - of SSIM with what="ssim", of the
+        contrast-structure term with "cs" - saturated to [0, 2^32 - 1], as a uint32 [count, 3, vh, vw] array, or at block = 2 ..
+        64 the maximum of each block x block cell, [count, 3, ceil(vh / block), ceil(vw / block)]; and for up to 8
+        `thresholds_q32` how many positions of each pair and channel exceed each, uint64 [count, 3, n].  maps=False: counts only
+        (None for the maps); thresholds_q32=None: maps only.  What launch() left to collect and ms_ssim()'s results are untouched."""
+        return _msssim_map(self.ctx, lambda wh, m, n, thr, k, over: lib().ce_batch_msssim_map(
+            self._h, first, count, levels, level, wh, block, m, n, thr, k, over), count, self.width, self.height, levels, level, what, block,
+            thresholds_q32, maps)
 
     def hdr_fidelity(self, n_pairs: int, depth: int = 10, white_nits: float = 203.0) -> List[HdrFidelity]:
         """PQ-PSNR and BT.2124 Delta E ITP of pairs [0, n_pairs) of a linear batch (ce_batch_hdr_fidelity); returns once the

@@ -1306,6 +1306,64 @@ int ce_batch_msssim(ce_batch *b, uint32_t n_pairs, uint32_t levels, ce_msssim_sc
     return CE_OK;
 }
 
+// SSIM / MS-SSIM per position, per cell and over thresholds (include/ce_metrics.h): ce_batch_msssim's frame
+// around the map kernel, ce_batch_delta_e_itp_map's rules for the outputs
+int ce_batch_msssim_map(ce_batch *b, uint32_t first, uint32_t count, uint32_t levels, uint32_t level, uint32_t what, uint32_t block,
+                        uint32_t *map, size_t map_len, const uint32_t *thresholds_q32, uint32_t n_thresholds, uint64_t *over)
+{
+    if (!b) return ce_fail(nullptr, CE_ERR_INVALID_ARG, "MS-SSIM map: null batch");
+    ce_ctx *ctx = b->ctx;
+    if (b->linear) return ce_fail(ctx, CE_ERR_INVALID_ARG, "the MS-SSIM map reads encoded sample values: not for a linear batch");
+    if (b->depth[0] != b->depth[1])
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "the MS-SSIM map needs both sides at one depth, got " + std::to_string(b->depth[0]) + " / " +
+                                                 std::to_string(b->depth[1]));
+    uint32_t lw[CE_MSSSIM_LEVELS] = {}, lh[CE_MSSSIM_LEVELS] = {};
+    if (int rc = msssim_levels(ctx, b->w, b->h, levels, lw, lh)) return rc;
+    if (level >= levels)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "MS-SSIM map: level " + std::to_string(level) + " of " + std::to_string(levels));
+    if (what > CE_MSSSIM_MAP_CS)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "MS-SSIM map: what must be CE_MSSSIM_MAP_SSIM or CE_MSSSIM_MAP_CS, got " + std::to_string(what));
+    if (!map && !over) return ce_fail(ctx, CE_ERR_INVALID_ARG, "MS-SSIM map: neither a map nor counts asked for");
+    if (count == 0 || first > b->max_pairs || count > b->max_pairs - first)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "MS-SSIM map: pairs [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) +
+                                                 ") outside the batch's " + std::to_string(b->max_pairs));
+    if (block == 0 || block > 64 || (block & (block - 1)) != 0)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "MS-SSIM map: block must be 1 or a power of two up to 64");
+    const uint32_t vw = lw[level] - 10, vh = lh[level] - 10;
+    const size_t want = map ? (size_t)count * 3 * ((vw + block - 1) / block) * ((vh + block - 1) / block) : 0;
+    if (map_len != want)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "MS-SSIM map: the map needs " + std::to_string(want) + " elements, got " + std::to_string(map_len));
+    if (n_thresholds > CE_MSSSIM_MAP_MAX_THRESHOLDS)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "MS-SSIM map: at most " + std::to_string(CE_MSSSIM_MAP_MAX_THRESHOLDS) + " thresholds, got " +
+                                                 std::to_string(n_thresholds));
+    if (over && (n_thresholds == 0 || !thresholds_q32)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "MS-SSIM map: counts asked for without thresholds");
+    if (!over && (n_thresholds != 0 || thresholds_q32)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "MS-SSIM map: thresholds given without a place for the counts");
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    if (map)
+        if (int rc = b->d_msssim_map.reserve(ctx, map_len)) return rc;
+    constexpr size_t per_pair = (size_t)3 * CE_MSSSIM_MAP_MAX_THRESHOLDS;
+    if (over && !b->msssim_over)
+        if (int rc = b->msssim_over.alloc(ctx, per_pair * b->max_pairs)) return rc;
+    // the pyramid whole, as ce_batch_msssim makes it: the two calls share it, and its layout does not depend on the level asked for
+    size_t pyr = 0;
+    for (uint32_t l = 1; l < levels; l++) pyr += ((size_t)b->max_refs + b->max_pairs) * 3 * lw[l] * lh[l];
+    if (level)
+        if (int rc = b->d_msssim_pyr.reserve(ctx, pyr)) return rc;
+    // on the context's stream, as a launch: behind the uploads queued so far, with the pair table of the last bind
+    if (int rc = ce_flush_uploads(b)) return rc;
+    if (int rc = sync_pair_ref(b)) return rc;
+    if (int rc = ce_launch_msssim_map(b, first, count, level, lw, lh, b->d_msssim_pyr, what, block, map ? b->d_msssim_map.get() : nullptr,
+                                      thresholds_q32, n_thresholds, over ? b->msssim_over.d.get() : nullptr))
+        return rc;
+    if (map) CE_HIP(ctx, hipMemcpyAsync(map, b->d_msssim_map, map_len * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (over)
+        CE_HIP(ctx, hipMemcpyAsync(b->msssim_over.h, b->msssim_over.d, sizeof(unsigned long long) * per_pair * count, hipMemcpyDeviceToHost, ctx->stream));
+    CE_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the slabs are free again: a later upload needs no fence against this
+    for (size_t i = 0; over && i < (size_t)count * 3; i++)
+        for (uint32_t j = 0; j < n_thresholds; j++) over[i * n_thresholds + j] = b->msssim_over.h[i * CE_MSSSIM_MAP_MAX_THRESHOLDS + j];
+    return CE_OK;
+}
+
 // ---- reference handle -------------------------------------------------------------------------
 
 struct ce_ref {

@@ -340,6 +340,10 @@ struct ce_batch {
     // five levels and kept
     ce_mirror<unsigned long long> msssim;
     ce_dev<float> d_msssim_pyr;
+    // SSIM / MS-SSIM maps (msssim_map.hip): the device buffer of the maps or cell maxima of one call, grow-only; [max_pairs][3][8]
+    // exceedance counts on the device and page-locked, made by the first call that asks for counts
+    ce_dev<uint32_t> d_msssim_map;
+    ce_mirror<unsigned long long> msssim_over;
 
     uint32_t last_n_pairs = 0;
     bool caller_blocks = false;  // set by entry points that collect before returning: page-locked sources need no staging copy
@@ -740,6 +744,29 @@ int ce_launch_delta_e_itp_map(ce_batch *b, uint32_t first, uint32_t count, uint3
 // is one launch of the fused kernel
 int ce_launch_msssim(ce_batch *b, uint32_t n_pairs, uint32_t levels, const uint32_t *lw, const uint32_t *lh, float *d_pyr,
                      unsigned long long *d_out);
+
+// Level l of the two sides of such a batch as the level kernels read it (msssim.hip): slot 0 of the references and of the tests -
+// the slabs at level 0 (packed RGB: px = 3, chan = 1), the planar f32 pyramid above (px = 1, chan = w * h) - with the elements
+// from a slot to the next; kind: 0 u8 slabs, 1 u16 slabs, 2 the pyramid
+struct ce_msssim_planes {
+    const void *refs, *tests;
+    size_t slot, chan, px;
+    int kind;
+};
+ce_msssim_planes ce_msssim_level_planes(const ce_batch *b, uint32_t l, const uint32_t *lw, const uint32_t *lh, float *d_pyr);
+// Levels from + 1 .. last of d_pyr from level `from`, on the launching stream: every reference slot that pairs [first, first +
+// count) name, once each, and those pairs' test slots.  from == last: nothing.
+int ce_msssim_pool(ce_batch *b, uint32_t first, uint32_t count, uint32_t from, uint32_t last, const uint32_t *lw, const uint32_t *lh,
+                   float *d_pyr);
+
+// Pairs [first, first + count) of such a batch at `level` (msssim_map.hip; include/ce_metrics.h: ce_batch_msssim_map): the
+// pyramid pooled as far as `level`, then every valid position's 2^32 - qs (what = 0) or 2^32 - qc (1), saturated to 32 bits,
+// into d_map - [count][3][vh][vw] at block 1, else the maxima of block x block cells, [count][3][ceil(vh / block)]
+// [ceil(vw / block)]; nullptr: no map - and into d_over[count][3][8] how many positions exceed thresholds[j], j <
+// n_thresholds <= 8, cleared here (nullptr: no counts)
+int ce_launch_msssim_map(ce_batch *b, uint32_t first, uint32_t count, uint32_t level, const uint32_t *lw, const uint32_t *lh, float *d_pyr,
+                         uint32_t what, uint32_t block, uint32_t *d_map, const uint32_t *thresholds, uint32_t n_thresholds,
+                         unsigned long long *d_over);
 
 // What the plane-domain scores (plane_fidelity.hip) take from the Y'CbCr ingest's own check of an image (ce_ingest.cpp:
 // yuv_check, with every refusal of it): the planes as the layout stores them - 1, or 2 (semiplanar), or 3 - with their rows

@@ -400,4 +400,44 @@ int ce_eval_pair_msssim_deep(ce_ctx *ctx, const uint16_t *reference, size_t refe
     return leaf_msssim(ctx, CE_LEAF_DEEP, depth, 6, reference, reference_len, test, test_len, width, height, levels, out);
 }
 
+// ... and its SSIM / MS-SSIM map and exceedance counts through the same batches, as leaf_msssim; what concerns level, what, block
+// and the outputs is ce_batch_msssim_map's to refuse
+static int leaf_msssim_map(ce_ctx *ctx, ce_leaf_kind kind, uint32_t depth, size_t bytes_per_pixel, const void *reference, size_t reference_len,
+                           const void *test, size_t test_len, uint32_t width, uint32_t height, uint32_t levels, uint32_t level, uint32_t what,
+                           uint32_t block, uint32_t *map, size_t map_len, const uint32_t *thresholds_q32, uint32_t n_thresholds, uint64_t *over)
+{
+    if (!ctx) return CE_ERR_INVALID_ARG;
+    if (!reference || !test) return ce_fail(ctx, CE_ERR_INVALID_ARG, "MS-SSIM map: null pointer");
+    if (kind == CE_LEAF_DEEP && !ce_deep_depth_ok(depth))
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "MS-SSIM map: depth must be 8, 10, 12 or 16 bits, got " + std::to_string(depth));
+    if (width == 0 || height == 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, "MS-SSIM map: empty image");
+    const size_t want = (size_t)width * height * bytes_per_pixel;
+    if (reference_len != want) return ce_bad_length(ctx, want, reference_len);
+    if (test_len != want) return ce_bad_length(ctx, want, test_len);
+    uint32_t n = 0, lw[CE_MSSSIM_LEVELS], lh[CE_MSSSIM_LEVELS];
+    if (int rc = ce_msssim_levels(width, height, levels, &n, lw, lh)) return ce_fail(ctx, rc, ce_last_error(nullptr));  // before a batch is made
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    ce_batch *b = nullptr;
+    if (int rc = leaf_batch(ctx, kind, width, height, depth, depth, &b)) return rc;
+    return leaf_pair(b, kind, reference, test, want, [&] {
+        return ce_batch_msssim_map(b, 0, 1, levels, level, what, block, map, map_len, thresholds_q32, n_thresholds, over);
+    });
+}
+
+int ce_eval_pair_msssim_map(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test, size_t test_len, uint32_t width,
+                            uint32_t height, uint32_t levels, uint32_t level, uint32_t what, uint32_t block, uint32_t *map, size_t map_len,
+                            const uint32_t *thresholds_q32, uint32_t n_thresholds, uint64_t *over)
+{
+    return leaf_msssim_map(ctx, CE_LEAF_RGB8, 0, 3, reference, reference_len, test, test_len, width, height, levels, level, what, block, map,
+                           map_len, thresholds_q32, n_thresholds, over);
+}
+
+int ce_eval_pair_msssim_map_deep(ce_ctx *ctx, const uint16_t *reference, size_t reference_len, const uint16_t *test, size_t test_len,
+                                 uint32_t depth, uint32_t width, uint32_t height, uint32_t levels, uint32_t level, uint32_t what, uint32_t block,
+                                 uint32_t *map, size_t map_len, const uint32_t *thresholds_q32, uint32_t n_thresholds, uint64_t *over)
+{
+    return leaf_msssim_map(ctx, CE_LEAF_DEEP, depth, 6, reference, reference_len, test, test_len, width, height, levels, level, what, block, map,
+                           map_len, thresholds_q32, n_thresholds, over);
+}
+
 }  // extern "C"

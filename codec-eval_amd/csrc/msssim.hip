@@ -65,7 +65,56 @@ int pool_run(ce_ctx *ctx, int kind, mss_pool_args a, uint32_t first, uint32_t co
     return CE_OK;
 }
 
+// the pyramid: level l = 1 .. 4 at this many floats, [slots][3][lh[l]][lw[l]]
+size_t pyr_off(const ce_batch *b, uint32_t l, const uint32_t *lw, const uint32_t *lh)
+{
+    const size_t slots = (size_t)b->max_refs + b->max_pairs;
+    size_t off = 0;
+    for (uint32_t k = 1; k < l; k++) off += slots * 3 * lw[k] * lh[k];
+    return off;
+}
+
 }  // namespace
+
+ce_msssim_planes ce_msssim_level_planes(const ce_batch *b, uint32_t l, const uint32_t *lw, const uint32_t *lh, float *d_pyr)
+{
+    const size_t plane = (size_t)lw[l] * lh[l], off = pyr_off(b, l, lw, lh);
+    ce_msssim_planes p{};
+    p.refs = l ? static_cast<const void *>(d_pyr + off) : static_cast<const void *>(b->d_refs.get());
+    p.tests = l ? static_cast<const void *>(d_pyr + off + (size_t)b->max_refs * 3 * plane) : static_cast<const void *>(b->d_tests.get());
+    p.slot = 3 * plane, p.chan = l ? plane : 1, p.px = l ? 1 : 3;
+    p.kind = l ? 2 : (b->depth[0] ? 1 : 0);
+    return p;
+}
+
+int ce_msssim_pool(ce_batch *b, uint32_t first, uint32_t count, uint32_t from, uint32_t last, const uint32_t *lw, const uint32_t *lh,
+                   float *d_pyr)
+{
+    if (from >= last) return CE_OK;
+    ce_ctx *ctx = b->ctx;
+    // the reference slots the pairs name, as runs of consecutive slots: each is pooled once
+    std::vector<bool> named(b->max_refs, false);
+    for (uint32_t i = 0; i < count; i++) named[b->h_pair_ref[first + i]] = true;
+    std::vector<std::pair<uint32_t, uint32_t>> runs;  // first, count
+    for (uint32_t r = 0; r < b->max_refs; r++)
+        if (named[r]) {
+            if (!runs.empty() && runs.back().first + runs.back().second == r) runs.back().second++;
+            else runs.emplace_back(r, 1u);
+        }
+    for (uint32_t l = from; l < last; l++) {
+        const ce_msssim_planes src = ce_msssim_level_planes(b, l, lw, lh, d_pyr);
+        float *dst = d_pyr + pyr_off(b, l + 1, lw, lh);
+        mss_pool_args p{};
+        p.src_slot = src.slot, p.chan = src.chan, p.px = src.px, p.w = lw[l], p.h = lh[l], p.ow = lw[l + 1], p.oh = lh[l + 1];
+        p.dst_slot = (size_t)3 * p.ow * p.oh;
+        p.src = src.refs, p.dst = dst;
+        for (const auto &run : runs)
+            if (int rc = pool_run(ctx, src.kind, p, run.first, run.second)) return rc;
+        p.src = src.tests, p.dst = dst + (size_t)b->max_refs * p.dst_slot;
+        if (int rc = pool_run(ctx, src.kind, p, first, count)) return rc;
+    }
+    return CE_OK;
+}
 
 int ce_launch_msssim(ce_batch *b, uint32_t n_pairs, uint32_t levels, const uint32_t *lw, const uint32_t *lh, float *d_pyr,
                      unsigned long long *d_out)
@@ -73,32 +122,12 @@ int ce_launch_msssim(ce_batch *b, uint32_t n_pairs, uint32_t levels, const uint3
     ce_ctx *ctx = b->ctx;
     hipStream_t stream = CE_STREAM(ctx);
     CE_HIP(ctx, hipMemsetAsync(d_out, 0, sizeof(unsigned long long) * CE_MSSSIM_LEVELS * 6 * n_pairs, stream));
-    const int slab_kind = b->depth[0] ? 1 : 0;
     const uint32_t depth = b->depth[0] ? b->depth[0] : 8;
     const double maxv = (double)((1u << depth) - 1u);
-    const size_t slots = (size_t)b->max_refs + b->max_pairs;
-    // the pyramid: level l = 1 .. 4 at off[l], [slots][3][lh[l]][lw[l]]
-    size_t off[CE_MSSSIM_LEVELS] = {};
-    for (uint32_t l = 2; l < levels; l++) off[l] = off[l - 1] + slots * 3 * lw[l - 1] * lh[l - 1];
-    // the reference slots the pairs name, as runs of consecutive slots: each is pooled once
-    std::vector<bool> named(b->max_refs, false);
-    for (uint32_t i = 0; i < n_pairs; i++) named[b->h_pair_ref[i]] = true;
-    std::vector<std::pair<uint32_t, uint32_t>> runs;  // first, count
-    for (uint32_t r = 0; r < b->max_refs; r++)
-        if (named[r]) {
-            if (!runs.empty() && runs.back().first + runs.back().second == r) runs.back().second++;
-            else runs.emplace_back(r, 1u);
-        }
     for (uint32_t l = 0; l < levels; l++) {
-        const size_t plane = (size_t)lw[l] * lh[l];
-        const int kind = l ? 2 : slab_kind;
-        // level l's planes of the two sides
-        const void *refs = l ? static_cast<const void *>(d_pyr + off[l]) : static_cast<const void *>(b->d_refs.get());
-        const void *tests = l ? static_cast<const void *>(d_pyr + off[l] + (size_t)b->max_refs * 3 * plane)
-                              : static_cast<const void *>(b->d_tests.get());
-        const size_t slot = 3 * plane, chan = l ? plane : 1, px = l ? 1 : 3;
+        const ce_msssim_planes p = ce_msssim_level_planes(b, l, lw, lh, d_pyr);
         mss_args g{};
-        g.refs = refs, g.tests = tests, g.ref_slot = g.test_slot = slot, g.chan = chan, g.px = px;
+        g.refs = p.refs, g.tests = p.tests, g.ref_slot = g.test_slot = p.slot, g.chan = p.chan, g.px = p.px;
         g.pair_ref = b->d_pair_ref, g.w = lw[l], g.h = lh[l], g.level = l;
         g.tiles_x = (lw[l] - kMssHalo + kMssTileW - 1) / kMssTileW;
         const uint32_t tiles_y = (lh[l] - kMssHalo + kMssTileH - 1) / kMssTileH;
@@ -107,19 +136,12 @@ int ce_launch_msssim(ce_batch *b, uint32_t n_pairs, uint32_t levels, const uint3
         for (uint32_t done = 0; done < n_pairs; done += pairs_a_launch) {
             g.first = done;
             const dim3 grid(g.tiles_x * tiles_y, 3 * std::min(n_pairs - done, pairs_a_launch));
-            if (kind == 0) CE_LAUNCH(ctx, "msssim_level_u8", k_msssim_level<uint8_t>, grid, dim3(kMssThreads), 0, g, d_out);
-            else if (kind == 1) CE_LAUNCH(ctx, "msssim_level_u16", k_msssim_level<uint16_t>, grid, dim3(kMssThreads), 0, g, d_out);
+            if (p.kind == 0) CE_LAUNCH(ctx, "msssim_level_u8", k_msssim_level<uint8_t>, grid, dim3(kMssThreads), 0, g, d_out);
+            else if (p.kind == 1) CE_LAUNCH(ctx, "msssim_level_u16", k_msssim_level<uint16_t>, grid, dim3(kMssThreads), 0, g, d_out);
             else CE_LAUNCH(ctx, "msssim_level_f32", k_msssim_level<float>, grid, dim3(kMssThreads), 0, g, d_out);
         }
         if (l + 1 == levels) break;
-        mss_pool_args p{};
-        p.src_slot = slot, p.chan = chan, p.px = px, p.w = lw[l], p.h = lh[l], p.ow = lw[l + 1], p.oh = lh[l + 1];
-        p.dst_slot = (size_t)3 * p.ow * p.oh;
-        p.src = refs, p.dst = d_pyr + off[l + 1];
-        for (const auto &run : runs)
-            if (int rc = pool_run(ctx, kind, p, run.first, run.second)) return rc;
-        p.src = tests, p.dst = d_pyr + off[l + 1] + (size_t)b->max_refs * p.dst_slot;
-        if (int rc = pool_run(ctx, kind, p, 0, n_pairs)) return rc;
+        if (int rc = ce_msssim_pool(b, 0, n_pairs, l, l + 1, lw, lh, d_pyr)) return rc;
     }
     CE_HIP(ctx, hipGetLastError());
     return CE_OK;

@@ -2,8 +2,9 @@
 // hdr_fidelity_kernel.h free of anything but the HIP keywords and blockIdx / threadIdx / gridDim, so that
 // tests/cpp/msssim_kernel_host.cpp can compile the same text for the host and run it under the host sanitizers.  The level
 // kernel is split at its two barriers for that: mss_stage fills the LDS tile of the two planes, mss_columns filters the five
-// streams down the columns into LDS, mss_lane filters them along the rows and returns the lane's two integers; the reduction
-// across lanes stays in msssim.hip.  mss_pool_sample is the pooling kernel's one output sample.
+// streams down the columns into LDS, mss_lane filters them along the rows (mss_rows) and returns the lane's two integers, the
+// sums of its positions' values (mss_position); the reduction across lanes stays in msssim.hip.  The map kernel
+// (msssim_map_kernel.h) calls mss_rows and mss_position itself.  mss_pool_sample is the pooling kernel's one output sample.
 //
 // The arithmetic is f64 throughout, every product, sum and quotient rounded separately - this text is compiled with
 // -ffp-contract=off on the device and on the host - and integers from the quantisation on.
@@ -93,25 +94,33 @@ __device__ __forceinline__ void mss_columns(const float *s_in, double *s_col)
     }
 }
 
-// s and cs of one position from the five filtered values, quantised
-__device__ __forceinline__ void mss_quantise(const mss_args &a, const double f[kMssStreams], long long acc[2])
+// s and cs of one position from the five filtered values, quantised: q[0] = qs, q[1] = qc.  The one text of a position's
+// values: the scores sum it (mss_quantise), the maps store it (msssim_map_kernel.h).
+__device__ __forceinline__ void mss_position(const mss_args &a, const double f[kMssStreams], long long q[2])
 {
     const double mx = f[0], my = f[1];
     const double sxx = f[2] - mx * mx, syy = f[3] - my * my, sxy = f[4] - mx * my;
     const double cs = (2.0 * sxy + a.c2) / ((sxx + syy) + a.c2);
     const double lum = (2.0 * (mx * my) + a.c1) / ((mx * mx + my * my) + a.c1);
     const double s = lum * cs;
-    acc[0] += (long long)__builtin_rint(s * 4294967296.0);
-    acc[1] += (long long)__builtin_rint(cs * 4294967296.0);
+    q[0] = (long long)__builtin_rint(s * 4294967296.0);
+    q[1] = (long long)__builtin_rint(cs * 4294967296.0);
 }
 
-// After the second barrier: the lane's two outputs, neighbours of one row - twelve values of each stream, read as six
-// 16-byte pairs - into acc = sum of qs, sum of qc over those of them that lie in the plane's valid region.
-__device__ __forceinline__ void mss_lane(const mss_args &a, const double *s_col, long long acc[2])
+// ... added to the lane's sums
+__device__ __forceinline__ void mss_quantise(const mss_args &a, const double f[kMssStreams], long long acc[2])
 {
-    const mss_where o = mss_block(a);
+    long long q[2];
+    mss_position(a, f, q);
+    acc[0] += q[0];
+    acc[1] += q[1];
+}
+
+// After the second barrier: the five streams filtered along the rows for the lane's two outputs, neighbours of one row -
+// twelve values of each stream, read as six 16-byte pairs.
+__device__ __forceinline__ void mss_rows(const double *s_col, double f0[kMssStreams], double f1[kMssStreams])
+{
     const int lx = (threadIdx.x % (kMssTileW / 2)) * 2, ly = threadIdx.x / (kMssTileW / 2);
-    double f0[kMssStreams], f1[kMssStreams];
 #pragma unroll
     for (int k = 0; k < kMssStreams; k++) {
         const mss_d2 *row = reinterpret_cast<const mss_d2 *>(s_col + k * kMssColLen + ly * kMssInW + lx);
@@ -129,6 +138,15 @@ __device__ __forceinline__ void mss_lane(const mss_args &a, const double *s_col,
         }
         f0[k] = o0, f1[k] = o1;
     }
+}
+
+// ... and the lane's two integers: acc = sum of qs, sum of qc over those of its two outputs that lie in the plane's valid region.
+__device__ __forceinline__ void mss_lane(const mss_args &a, const double *s_col, long long acc[2])
+{
+    const mss_where o = mss_block(a);
+    const int lx = (threadIdx.x % (kMssTileW / 2)) * 2, ly = threadIdx.x / (kMssTileW / 2);
+    double f0[kMssStreams], f1[kMssStreams];
+    mss_rows(s_col, f0, f1);
     acc[0] = acc[1] = 0;
     const uint32_t vw = a.w - kMssHalo, vh = a.h - kMssHalo, gx = o.x0 + lx, gy = o.y0 + ly;
     if (gy < vh && gx < vw) mss_quantise(a, f0, acc);

@@ -824,6 +824,68 @@ inline std::vector<std::pair<uint32_t, uint32_t>> msssim_levels(uint32_t width, 
     for (uint32_t l = 0; l < n; l++) out.emplace_back(w[l], h[l]);
     return out;
 }
+// Where pairs differ at one level of the pyramid (include/ce_metrics.h: ce_batch_msssim_map): per pair and
+// channel every valid position's 2^32 - q in units of 2^-32 (CE_MSSSIM_Q32 is an SSIM of 1.0), q the integer ms_ssim sums - of
+// SSIM (CE_MSSSIM_MAP_SSIM) or of the contrast-structure term (CE_MSSSIM_MAP_CS) - saturated to [0, 2^32 - 1]; at block 2 .. 64
+// the maximum of each block x block cell - as [count][3][cells_h][cells_w], empty when want_map is false; and [count][3]
+// [thresholds.size()] counts of the positions above each of up to CE_MSSSIM_MAP_MAX_THRESHOLDS thresholds, empty without
+// thresholds.  What the library refuses (levels, level, an image too small) leaves the map empty for it to refuse.
+struct MsSsimMaps {
+    std::vector<uint32_t> map;
+    uint32_t cells_w = 0, cells_h = 0;
+    std::vector<uint64_t> over;
+    static MsSsimMaps sized(uint32_t count, uint32_t width, uint32_t height, uint32_t levels, uint32_t level, uint32_t block, bool want_map,
+                            size_t n_thresholds)
+    {
+        MsSsimMaps out;
+        const uint32_t b = block ? block : 1;
+        const auto lv = msssim_levels(width, height, levels);
+        if (level < lv.size()) out.cells_w = (lv[level].first - 10 + b - 1) / b, out.cells_h = (lv[level].second - 10 + b - 1) / b;
+        if (want_map) out.map.resize((size_t)count * 3 * out.cells_w * out.cells_h);
+        out.over.resize((size_t)count * 3 * n_thresholds);
+        return out;
+    }
+};
+// pairs [first, first + count) of an RGB8 batch or a deep batch of one depth, of width x height; returns once the results are on the host
+inline MsSsimMaps batch_ms_ssim_map(const HipBackend &be, ce_batch *batch, uint32_t width, uint32_t height, uint32_t first, uint32_t count,
+                                    uint32_t levels = 5, uint32_t level = 0, uint32_t what = CE_MSSSIM_MAP_SSIM, uint32_t block = 1,
+                                    bool want_map = true, const std::vector<uint32_t> &thresholds_q32 = {})
+{
+    MsSsimMaps out = MsSsimMaps::sized(count, width, height, levels, level, block, want_map, thresholds_q32.size());
+    detail::check(be, ce_batch_msssim_map(batch, first, count, levels, level, what, block, out.map.empty() ? nullptr : out.map.data(),
+                                          out.map.size(), thresholds_q32.empty() ? nullptr : thresholds_q32.data(),
+                                          (uint32_t)thresholds_q32.size(), out.over.empty() ? nullptr : out.over.data()),
+                  "ms_ssim_map", 0, 0, 0);
+    return out;
+}
+// one pair of packed RGB8 (width * height * 3 bytes each)
+inline MsSsimMaps ms_ssim_map(const HipBackend &be, const uint8_t *reference, const uint8_t *test, uint32_t width, uint32_t height,
+                              uint32_t levels = 5, uint32_t level = 0, uint32_t what = CE_MSSSIM_MAP_SSIM, uint32_t block = 1,
+                              bool want_map = true, const std::vector<uint32_t> &thresholds_q32 = {})
+{
+    MsSsimMaps out = MsSsimMaps::sized(1, width, height, levels, level, block, want_map, thresholds_q32.size());
+    const size_t len = (size_t)width * height * 3;
+    detail::check(be, ce_eval_pair_msssim_map(be.ctx(), reference, len, test, len, width, height, levels, level, what, block,
+                                              out.map.empty() ? nullptr : out.map.data(), out.map.size(),
+                                              thresholds_q32.empty() ? nullptr : thresholds_q32.data(), (uint32_t)thresholds_q32.size(),
+                                              out.over.empty() ? nullptr : out.over.data()),
+                  "ms_ssim_map", width, height, len);
+    return out;
+}
+// one pair of packed u16 RGB of `depth` bits on both sides (width * height * 3 samples each)
+inline MsSsimMaps ms_ssim_map_deep(const HipBackend &be, const uint16_t *reference, const uint16_t *test, uint32_t depth, uint32_t width,
+                                   uint32_t height, uint32_t levels = 5, uint32_t level = 0, uint32_t what = CE_MSSSIM_MAP_SSIM,
+                                   uint32_t block = 1, bool want_map = true, const std::vector<uint32_t> &thresholds_q32 = {})
+{
+    MsSsimMaps out = MsSsimMaps::sized(1, width, height, levels, level, block, want_map, thresholds_q32.size());
+    const size_t len = (size_t)width * height * 6;
+    detail::check(be, ce_eval_pair_msssim_map_deep(be.ctx(), reference, len, test, len, depth, width, height, levels, level, what, block,
+                                                   out.map.empty() ? nullptr : out.map.data(), out.map.size(),
+                                                   thresholds_q32.empty() ? nullptr : thresholds_q32.data(), (uint32_t)thresholds_q32.size(),
+                                                   out.over.empty() ? nullptr : out.over.data()),
+                  "ms_ssim_map", width, height, len);
+    return out;
+}
 // ---- a decoder's Y'CbCr planes scored as planes (include/ce_metrics.h: ce_yuv_plane_fidelity) ----
 // PSNR-Y / -Cb / -Cr with the weighted and the overall figure, and SSIM / MS-SSIM per plane, each plane at its own size;
 // levels: 0 (PSNR only), 1 (+ SSIM) or 5 (+ MS-SSIM)

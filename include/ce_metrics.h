@@ -1071,6 +1071,56 @@ int ce_eval_pair_msssim_deep(ce_ctx *ctx, const uint16_t *reference, size_t refe
 int ce_msssim_window(double out[11]);
 int ce_msssim_levels(uint32_t w, uint32_t h, uint32_t levels, uint32_t *n_levels, uint32_t *level_w, uint32_t *level_h);
 
+/* ---- SSIM and MS-SSIM per position, per cell and over thresholds ----------------------------------------
+ * Where a pair is bad, and how much of it, at one level of the pyramid above: the very integers ce_batch_msssim sums, before
+ * they are summed, and nothing new in arithmetic.
+ * Position values.  For a pair, a level l of the pyramid defined above (samples, window, filter F, C1, C2, next level: all
+ *   unchanged) and a channel c, at each of the vh x vw = (h_l - 10) x (w_l - 10) valid positions: qs = (int64) rint(s * 2^32)
+ *   and qc = (int64) rint(cs * 2^32) exactly as defined above - the same filter order, parentheses and quotients.
+ * Map value.  A dissimilarity in units of 2^-32 (CE_MSSSIM_Q32 is 1.0) as uint32_t: d = min(max(2^32 - q, 0), 2^32 - 1), q =
+ *   qs with what = CE_MSSSIM_MAP_SSIM and qc with what = CE_MSSSIM_MAP_CS.  Identical images give 0 everywhere.  The
+ *   saturation is real: s and cs can be zero or negative (a pattern against its inverse), so a map value of 2^32 - 1 reads
+ *   "SSIM of 2^-32 or less, negatives included"; a q above 2^32, should rounding ever give one, reads 0.  The sums above
+ *   carry q signed in 64 bits and do not saturate.  For every (pair, level, channel) none of whose q lies outside
+ *   [1, 2^32]:  n[l] * 2^32 - map.sum() == ssim_q[l][c]  (cs_q[l][c] with CE_MSSSIM_MAP_CS), both from ce_batch_msssim on the
+ *   same pair.
+ * block.  1: the map itself, [vh][vw].  A power of two up to 64: the MAXIMUM of d over each block x block cell of the valid
+ *   region, edge cells clipped to the region, [ceil(vh / block)][ceil(vw / block)] - ce_batch_delta_e_itp_map's rules.
+ * Exceedance counts.  over[pair][c][j] = the number of valid positions with d > thresholds_q32[j] (same units), for up to
+ *   CE_MSSSIM_MAP_MAX_THRESHOLDS thresholds: exact integers over the positions, never over cells, whatever `block` is.  A
+ *   threshold of 2^32 - 1 counts nothing.
+ * levels, level.  levels is 1 or 5 by ce_msssim_levels' rule, level in [0, levels): one level per call.  The pyramid is pooled
+ *   only as far as `level`, for the reference slots that pairs [first, first + count) name - once each - and those pairs' test
+ *   slots.
+ * Everything is an integer maximum, an integer sum or a plain store, so nothing depends on the grid or on the order.
+ * The call runs on the context's stream, ordered behind the uploads queued so far as a launch is, with the pair table of the
+ * last bind; it blocks until the results are on the host.  ce_scores, stored maps, the integers ce_batch_msssim keeps and
+ * whatever ce_batch_launch left to collect are untouched.  `map` receives [count][3][ceil(vh / block)][ceil(vw / block)] values
+ * and map_len is that number of ELEMENTS; `over` receives [count][3][n_thresholds].  map may be NULL with map_len 0 (counts only:
+ * no map is stored and no map memory allocated), over may be NULL with n_thresholds 0 and thresholds_q32 NULL, not both.  The
+ * device buffer of the maps of one call (map_len * 4 bytes) and the counts are grow-only buffers of the batch, freed with it;
+ * like the pyramid they are outside ce_estimate_batch_bytes.
+ * CE_ERR_INVALID_ARG, with the reason in ce_last_error and the batch still usable: a null batch; a linear batch; a deep batch
+ * of unequal depths; levels other than 1 or 5; an image too small for `levels`; level >= levels; what above 1; both outputs
+ * NULL; count of 0 or a range past the batch's max_pairs; a block that is not 1, 2, 4, 8, 16, 32 or 64; a map_len other than
+ * the above; n_thresholds above 8; over without thresholds; thresholds without over.
+ * tests/msssim_map_restatement.py restates this in numpy; the device equals it on every element. */
+#define CE_MSSSIM_MAP_MAX_THRESHOLDS 8
+#define CE_MSSSIM_Q32 4294967296ull
+enum { CE_MSSSIM_MAP_SSIM = 0, CE_MSSSIM_MAP_CS = 1 };
+int ce_batch_msssim_map(ce_batch *b, uint32_t first, uint32_t count, uint32_t levels, uint32_t level, uint32_t what, uint32_t block,
+                        uint32_t *map, size_t map_len, const uint32_t *thresholds_q32, uint32_t n_thresholds, uint64_t *over);
+/* One pair of packed RGB8 host images (lengths in bytes: width * height * 3), and one pair of packed u16 RGB of one `depth`
+ * (8, 10, 12 or 16; width * height * 6 bytes), through the context's one-pair batches as ce_eval_pair_msssim takes them.
+ * CE_ERR_INVALID_ARG as above and for a null image or an empty one, CE_ERR_BAD_LENGTH for a length that is not the image's. */
+int ce_eval_pair_msssim_map(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test, size_t test_len,
+                            uint32_t width, uint32_t height, uint32_t levels, uint32_t level, uint32_t what, uint32_t block,
+                            uint32_t *map, size_t map_len, const uint32_t *thresholds_q32, uint32_t n_thresholds, uint64_t *over);
+int ce_eval_pair_msssim_map_deep(ce_ctx *ctx, const uint16_t *reference, size_t reference_len, const uint16_t *test, size_t test_len,
+                                 uint32_t depth, uint32_t width, uint32_t height, uint32_t levels, uint32_t level, uint32_t what,
+                                 uint32_t block, uint32_t *map, size_t map_len, const uint32_t *thresholds_q32, uint32_t n_thresholds,
+                                 uint64_t *over);
+
 /* ---- a decoder's Y'CbCr planes scored as planes: PSNR, SSIM and MS-SSIM per plane -----------------------
  * What codec test conditions (AOM, JVET, JPEG) tabulate: PSNR-Y, PSNR-Cb, PSNR-Cr on the planes the decoder wrote, each at its
  * own resolution - no chroma upsampling, no colour matrix, no RGB clamp - with the 6:1:1 weighted and the overall PSNR, and
