@@ -744,6 +744,32 @@ impl HipMetrics {
         Ok(out)
     }
 
+    /// `ce_eval_pair_ciede2000`: CIEDE2000 of one pair of packed RGB8 read as sRGB; `thresholds_q20` (at most eight, in units of
+    /// 2^-20) are what `n_above` counts the pixels above.
+    pub fn ciede2000(&mut self, reference: &[u8], test: &[u8], width: u32, height: u32, thresholds_q20: &[u32])
+                     -> Result<sys::ce_ciede2000_scores, HipError> {
+        let mut out = sys::ce_ciede2000_scores::default();
+        let rc = unsafe {
+            sys::ce_eval_pair_ciede2000(self.ctx, reference.as_ptr(), reference.len(), test.as_ptr(), test.len(), width, height,
+                                        thresholds_q20.as_ptr(), thresholds_q20.len() as u32, &mut out)
+        };
+        self.check(rc, width, height, test.len())?;
+        Ok(out)
+    }
+
+    /// `ce_eval_pair_ciede2000_deep`: the same for packed u16 RGB, the reference at `ref_depth` and the test at `test_depth` bits
+    /// (each 8, 10, 12 or 16).
+    pub fn ciede2000_deep(&mut self, reference: &[u16], test: &[u16], ref_depth: u32, test_depth: u32, width: u32, height: u32,
+                          thresholds_q20: &[u32]) -> Result<sys::ce_ciede2000_scores, HipError> {
+        let mut out = sys::ce_ciede2000_scores::default();
+        let rc = unsafe {
+            sys::ce_eval_pair_ciede2000_deep(self.ctx, reference.as_ptr(), reference.len() * 2, test.as_ptr(), test.len() * 2, ref_depth,
+                                             test_depth, width, height, thresholds_q20.as_ptr(), thresholds_q20.len() as u32, &mut out)
+        };
+        self.check(rc, width, height, test.len() * 2)?;
+        Ok(out)
+    }
+
     /// `ce_eval_pair_msssim_map`: where one pair of packed RGB8 differs at `level` - see `HipBatch::ms_ssim_map`.
     pub fn ms_ssim_map(&mut self, reference: &[u8], test: &[u8], width: u32, height: u32, levels: u32, level: u32, what: u32, block: u32,
                        want_map: bool, thresholds_q32: &[u32]) -> Result<MsSsimMaps, HipError> {
@@ -879,6 +905,18 @@ pub fn msssim_window() -> [f64; 11] {
     let mut g = [0f64; 11];
     unsafe { sys::ce_msssim_window(g.as_mut_ptr()) };
     g
+}
+
+/// `ce_ciede2000_pixels`: the per-pixel CIEDE2000 in units of 2^-20 of packed u16 RGB at `ref_depth` / `test_depth` bits - the
+/// kernel's pixel text compiled for the host; `None` for sides of unequal length, a length that is no multiple of 3 or a depth
+/// that is none of 8, 10, 12, 16.  A pure host function.
+pub fn ciede2000_pixels(reference: &[u16], ref_depth: u32, test: &[u16], test_depth: u32) -> Option<Vec<u32>> {
+    if reference.len() != test.len() || reference.len() % 3 != 0 {
+        return None;
+    }
+    let mut out = vec![0u32; reference.len() / 3];
+    let rc = unsafe { sys::ce_ciede2000_pixels(reference.as_ptr(), ref_depth, test.as_ptr(), test_depth, out.len(), out.as_mut_ptr()) };
+    (rc == sys::CE_OK).then_some(out)
 }
 
 /// `ce_msssim_levels`: the (width, height) of every level of SSIM (`levels` 1) or MS-SSIM (5) on a width x height image; `None`
@@ -1284,6 +1322,17 @@ impl HipBatch<'_> {
     pub fn ms_ssim(&mut self, n_pairs: u32, levels: u32) -> Result<Vec<sys::ce_msssim_scores>, HipError> {
         let mut out = vec![sys::ce_msssim_scores::default(); n_pairs as usize];
         let rc = unsafe { sys::ce_batch_msssim(self.handle, n_pairs, levels, out.as_mut_ptr()) };
+        self.check(rc, 0)?;
+        Ok(out)
+    }
+
+    /// `ce_batch_ciede2000`: CIEDE2000 of pairs `[0, n_pairs)` of an RGB8 or deep batch read as sRGB; `thresholds_q20` (at most
+    /// eight, in units of 2^-20) are what `n_above` counts the pixels above; returns once the scores are on the host.
+    pub fn ciede2000(&mut self, n_pairs: u32, thresholds_q20: &[u32]) -> Result<Vec<sys::ce_ciede2000_scores>, HipError> {
+        let mut out = vec![sys::ce_ciede2000_scores::default(); n_pairs as usize];
+        let rc = unsafe {
+            sys::ce_batch_ciede2000(self.handle, n_pairs, thresholds_q20.as_ptr(), thresholds_q20.len() as u32, out.as_mut_ptr())
+        };
         self.check(rc, 0)?;
         Ok(out)
     }

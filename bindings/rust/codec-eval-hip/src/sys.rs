@@ -220,6 +220,22 @@ pub struct ce_msssim_scores {
     pub reserved: u32,
 }
 
+/// `ce_ciede2000_scores` (120 bytes): CIEDE2000 of one pair read as sRGB - the mean and the maximum of the per-pixel Delta E 2000
+/// and 45 - 20 log10(mean) - with the exact integers they are finished from, in units of 2^-20, and the pixels above each threshold.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct ce_ciede2000_scores {
+    pub sum_q20: u64,
+    pub n: u64,
+    pub n_above: [u64; 8],
+    pub mean: c_double,
+    pub max: c_double,
+    pub ciede2000_db: c_double,
+    pub max_q20: u32,
+    pub n_thresholds: u32,
+    pub reserved: [u32; 2],
+}
+
 /// `ce_plane_scores` (512 bytes): one pair of Y'CbCr images scored plane by plane, index 0, 1, 2 = Y, Cb, Cr: the exact squared
 /// error and sample count, the PSNRs finished from them, and per plane and level the integers of SSIM / MS-SSIM with the
 /// positions of a level.  What did not run is 0 (integers) or NaN (doubles).
@@ -555,6 +571,13 @@ extern "C" {
                                         map: *mut u32, map_len: usize, thresholds_q32: *const u32, n_thresholds: u32,
                                         over: *mut u64) -> c_int;
     pub fn ce_msssim_window(out: *mut c_double) -> c_int;
+    pub fn ce_batch_ciede2000(b: *mut ce_batch, n_pairs: u32, thresholds_q20: *const u32, n_thresholds: u32, out: *mut ce_ciede2000_scores) -> c_int;
+    pub fn ce_eval_pair_ciede2000(ctx: *mut ce_ctx, reference: *const u8, reference_len: usize, test: *const u8, test_len: usize, width: u32,
+                                  height: u32, thresholds_q20: *const u32, n_thresholds: u32, out: *mut ce_ciede2000_scores) -> c_int;
+    pub fn ce_eval_pair_ciede2000_deep(ctx: *mut ce_ctx, reference: *const u16, reference_len: usize, test: *const u16, test_len: usize,
+                                       ref_depth: u32, test_depth: u32, width: u32, height: u32, thresholds_q20: *const u32,
+                                       n_thresholds: u32, out: *mut ce_ciede2000_scores) -> c_int;
+    pub fn ce_ciede2000_pixels(ref_rgb: *const u16, ref_depth: u32, test_rgb: *const u16, test_depth: u32, n: usize, out_q20: *mut u32) -> c_int;
     pub fn ce_msssim_levels(w: u32, h: u32, levels: u32, n_levels: *mut u32, level_w: *mut u32, level_h: *mut u32) -> c_int;
     pub fn ce_yuv_plane_fidelity(ctx: *mut ce_ctx, width: u32, height: u32, refs: *const ce_yuv_image, n_refs: u32, tests: *const ce_yuv_image,
                                  n_pairs: u32, pair_ref: *const u32, levels: u32, out: *mut ce_plane_scores) -> c_int;

@@ -195,6 +195,11 @@ class CeMsssimScores(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class CeCiede2000Scores(C.Structure):
+    _fields_ = [("sum_q20", C.c_uint64), ("n", C.c_uint64), ("n_above", C.c_uint64 * 8), ("mean", C.c_double), ("max", C.c_double),
+                ("ciede2000_db", C.c_double), ("max_q20", C.c_uint32), ("n_thresholds", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class CePlaneScores(C.Structure):
     _fields_ = [("sse", C.c_uint64 * 3), ("n", C.c_uint64 * 3), ("psnr", C.c_double * 3), ("psnr_weighted", C.c_double),
                 ("psnr_overall", C.c_double), ("ssim", C.c_double * 3), ("ms_ssim", C.c_double * 3), ("ssim_q", (C.c_int64 * 5) * 3),
@@ -361,6 +366,10 @@ _PROTOTYPES = [
     ("ce_eval_pair_msssim_map", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
     ("ce_eval_pair_msssim_map_deep", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
     ("ce_msssim_window", _i, [_vp]),
+    ("ce_batch_ciede2000", _i, [_vp, _u32, _vp, _u32, C.POINTER(CeCiede2000Scores)]),
+    ("ce_eval_pair_ciede2000", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _vp, _u32, C.POINTER(CeCiede2000Scores)]),
+    ("ce_eval_pair_ciede2000_deep", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, _vp, _u32, C.POINTER(CeCiede2000Scores)]),
+    ("ce_ciede2000_pixels", _i, [_vp, _u32, _vp, _u32, _sz, _vp]),
     ("ce_msssim_levels", _i, [_u32, _u32, _u32, _vp, _vp, _vp]),
     ("ce_icc_describe", _i, [_vp, _sz, C.POINTER(CeIccDescription)]),
     ("ce_icc_build_matrix", _i, [_vp, _sz, _vp]),
@@ -855,6 +864,46 @@ class MsSsim:
         return MsSsim(s.ms_ssim, s.ssim, tuple(s.ms_ssim_rgb), tuple(s.ssim_rgb),
                       tuple(tuple(int(v) for v in s.ssim_q[l]) for l in range(5)),
                       tuple(tuple(int(v) for v in s.cs_q[l]) for l in range(5)), tuple(int(v) for v in s.n), int(s.n_levels))
+
+
+CIEDE2000_Q20 = 1 << 20  # a CIEDE2000 of 1.0 in the units of q and of the thresholds (CE_CIEDE2000_Q20)
+CIEDE2000_MAX_THRESHOLDS = 8  # CE_CIEDE2000_MAX_THRESHOLDS
+
+
+@dataclass(frozen=True)
+class Ciede2000:
+    """CIEDE2000 of one pair read as sRGB (ce_ciede2000_scores): the mean and the maximum of the per-pixel Delta E 2000, the
+    PSNR-like 45 - 20 log10(mean) (inf for a mean of 0), and the exact integers they are finished from - the sum and the maximum
+    of the per-pixel values in units of 2^-20 over n pixels - with n_above[k], the pixels above the k-th threshold."""
+    mean: float
+    max: float
+    ciede2000_db: float
+    sum_q20: int
+    max_q20: int
+    n: int
+    n_above: Tuple[int, ...]
+
+    @staticmethod
+    def from_c(s: CeCiede2000Scores) -> "Ciede2000":
+        return Ciede2000(s.mean, s.max, s.ciede2000_db, int(s.sum_q20), int(s.max_q20), int(s.n),
+                         tuple(int(s.n_above[k]) for k in range(int(s.n_thresholds))))
+
+
+def _thresholds_q20(thresholds_q20) -> np.ndarray:
+    """Up to 2^32 - 1 each, as the uint32 array the C calls take (more than eight are the library's to refuse)."""
+    return np.ascontiguousarray(np.asarray(() if thresholds_q20 is None else thresholds_q20, np.uint64).reshape(-1).astype(np.uint32))
+
+
+def ciede2000_pixels(reference, test, ref_depth: int = 8, test_depth: int = 8) -> np.ndarray:
+    """The per-pixel CIEDE2000 in units of 2^-20 (ce_ciede2000_pixels), uint32 [n]: reference and test hold n * 3 integer samples
+    of ref_depth / test_depth bits.  A pure host function - the kernel's pixel text compiled for the host - that needs no GPU."""
+    r = np.ascontiguousarray(np.asarray(reference).astype(np.uint16).reshape(-1))
+    t = np.ascontiguousarray(np.asarray(test).astype(np.uint16).reshape(-1))
+    if r.size != t.size or r.size % 3:
+        raise ValueError("ciede2000_pixels: both sides need the same number of RGB triples")
+    out = np.empty(r.size // 3, np.uint32)
+    _host_check(lib().ce_ciede2000_pixels(r.ctypes.data, ref_depth, t.ctypes.data, test_depth, out.size, out.ctypes.data))
+    return out
 
 
 @dataclass(frozen=True)
@@ -1767,6 +1816,23 @@ class Context:
                                                        levels, C.byref(s)))
         return MsSsim.from_c(s)
 
+    def ciede2000(self, reference, test, width: int, height: int, thresholds_q20=None, depth: int = 0, test_depth: Optional[int] = None) -> Ciede2000:
+        """CIEDE2000 of one pair read as sRGB: packed uint8 RGB (`depth` 0, ce_eval_pair_ciede2000) or packed uint16 RGB with the
+        reference at `depth` and the test at `test_depth` bits (`depth` again when None; ce_eval_pair_ciede2000_deep).
+        thresholds_q20: up to eight values in units of 2^-20 whose exceedance counts come back in n_above."""
+        s = CeCiede2000Scores()
+        thr = _thresholds_q20(thresholds_q20)
+        if depth == 0:
+            r, t = _buf(reference), _buf(test)
+            self._check(lib().ce_eval_pair_ciede2000(self._h, r.ctypes.data, r.size, t.ctypes.data, t.size, width, height,
+                                                     thr.ctypes.data if thr.size else None, thr.size, C.byref(s)))
+        else:
+            r, t = _buf16(reference), _buf16(test)
+            self._check(lib().ce_eval_pair_ciede2000_deep(self._h, r.ctypes.data, r.nbytes, t.ctypes.data, t.nbytes, depth,
+                                                          depth if test_depth is None else test_depth, width, height,
+                                                          thr.ctypes.data if thr.size else None, thr.size, C.byref(s)))
+        return Ciede2000.from_c(s)
+
     def ms_ssim_map(self, reference, test, width: int, height: int, levels: int = 5, level: int = 0, what: str = "ssim", block: int = 1,
                     thresholds_q32=None, maps: bool = True, depth: int = 0):
         """Batch.ms_ssim_maps for one pair of packed uint8 RGB (depth 0; ce_eval_pair_msssim_map) or packed uint16 RGB of `depth`
@@ -2341,6 +2407,15 @@ class Batch:
         out = (CeMsssimScores * max(n_pairs, 1))()
         self.ctx._check(lib().ce_batch_msssim(self._h, n_pairs, levels, out))
         return [MsSsim.from_c(out[i]) for i in range(n_pairs)]
+
+    def ciede2000(self, n_pairs: int, thresholds_q20=None) -> List[Ciede2000]:
+        """CIEDE2000 of pairs [0, n_pairs) of an RGB8 or deep batch read as sRGB (ce_batch_ciede2000); returns once the scores
+        are on the host.  thresholds_q20: up to eight values in units of 2^-20 whose exceedance counts come back in n_above.
+        Scores and maps of a launch are untouched."""
+        out = (CeCiede2000Scores * max(n_pairs, 1))()
+        thr = _thresholds_q20(thresholds_q20)
+        self.ctx._check(lib().ce_batch_ciede2000(self._h, n_pairs, thr.ctypes.data if thr.size else None, thr.size, out))
+        return [Ciede2000.from_c(out[i]) for i in range(n_pairs)]
 
     def ms_ssim_maps(self, first: int, count: int, levels: int = 5, level: int = 0, what: str = "ssim", block: int = 1, thresholds_q32=None,
                      maps: bool = True):

@@ -1364,6 +1364,63 @@ int ce_batch_msssim_map(ce_batch *b, uint32_t first, uint32_t count, uint32_t le
     return CE_OK;
 }
 
+// ---- CIEDE2000 of RGB8 and deep batches (ciede2000.hip) ------------------------------------------------
+
+int ce_batch_ciede2000(ce_batch *b, uint32_t n_pairs, const uint32_t *thresholds_q20, uint32_t n_thresholds, ce_ciede2000_scores *out)
+{
+    if (!b) return CE_ERR_INVALID_ARG;
+    ce_ctx *ctx = b->ctx;
+    if (!out || (n_thresholds && !thresholds_q20)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "CIEDE2000: null pointer");
+    if (b->linear)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "CIEDE2000 reads sRGB sample values: not for a linear batch, whose colour difference is Delta E ITP "
+                                                "(ce_batch_hdr_fidelity)");
+    if (n_thresholds > CE_CIEDE2000_MAX_THRESHOLDS)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "CIEDE2000: at most " + std::to_string(CE_CIEDE2000_MAX_THRESHOLDS) + " thresholds, got " +
+                                                 std::to_string(n_thresholds));
+    if (n_pairs == 0 || n_pairs > b->max_pairs) return ce_fail(ctx, CE_ERR_INVALID_ARG, "n_pairs out of range");
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    // the tables SSIMULACRA2 reads a deep batch through, per side; an RGB8 batch through the 8-bit one
+    const float *d_tab[2] = {nullptr, nullptr};
+    for (int s = 0; s < 2; s++)
+        if (int rc = ce_deep_table(ctx, b->depth[s] ? b->depth[s] : 8, 0, &d_tab[s])) return rc;
+    constexpr size_t per_pair = 2 + CE_CIEDE2000_MAX_THRESHOLDS;
+    if (!b->ciede2000)
+        if (int rc = b->ciede2000.alloc(ctx, per_pair * b->max_pairs)) return rc;
+    // on the context's stream, as a launch: behind the uploads queued so far, with the pair table of the last bind
+    if (int rc = ce_flush_uploads(b)) return rc;
+    if (int rc = sync_pair_ref(b)) return rc;
+    if (int rc = ce_launch_ciede2000(b, n_pairs, d_tab[0], d_tab[1], thresholds_q20, n_thresholds, b->ciede2000.d)) return rc;
+    CE_HIP(ctx, hipMemcpyAsync(b->ciede2000.h, b->ciede2000.d, sizeof(unsigned long long) * per_pair * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
+    CE_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the slabs are free again: a later upload needs no fence against this
+    for (uint32_t i = 0; i < n_pairs; i++) {
+        const unsigned long long *v = b->ciede2000.h + per_pair * i;
+        ce_ciede2000_scores s{};
+        s.sum_q20 = v[0], s.max_q20 = (uint32_t)v[1], s.n = (uint64_t)b->w * b->h, s.n_thresholds = n_thresholds;
+        for (uint32_t j = 0; j < n_thresholds; j++) s.n_above[j] = v[2 + j];
+        s.mean = ((double)s.sum_q20 / 1048576.0) / (double)s.n;
+        s.max = (double)s.max_q20 / 1048576.0;
+        s.ciede2000_db = s.sum_q20 ? 45.0 - 20.0 * std::log10(s.mean) : INFINITY;
+        out[i] = s;
+    }
+    return CE_OK;
+}
+
+int ce_ciede2000_pixels(const uint16_t *ref_rgb, uint32_t ref_depth, const uint16_t *test_rgb, uint32_t test_depth, size_t n, uint32_t *out_q20)
+{
+    if (!ce_deep_depth_ok(ref_depth) || !ce_deep_depth_ok(test_depth))
+        return ce_fail(nullptr, CE_ERR_INVALID_ARG, "ce_ciede2000_pixels: depths must be 8, 10, 12 or 16 bits, got " + std::to_string(ref_depth) +
+                                                     " / " + std::to_string(test_depth));
+    if (!ref_rgb || !test_rgb || !out_q20) return ce_fail(nullptr, CE_ERR_INVALID_ARG, "ce_ciede2000_pixels: null pointer");
+    const uint32_t maxv[2] = {(1u << ref_depth) - 1u, (1u << test_depth) - 1u};
+    std::vector<float> tab[2];
+    for (int s = 0; s < (ref_depth == test_depth ? 1 : 2); s++) {
+        tab[s].resize((size_t)maxv[s] + 1);
+        ce_build_srgb_table_f64(tab[s].data(), maxv[s]);
+    }
+    ce_ciede2000_pixels_host(ref_rgb, tab[0].data(), maxv[0], test_rgb, tab[ref_depth == test_depth ? 0 : 1].data(), maxv[1], n, out_q20);
+    return CE_OK;
+}
+
 // ---- reference handle -------------------------------------------------------------------------
 
 struct ce_ref {

@@ -344,6 +344,8 @@ struct ce_batch {
     // exceedance counts on the device and page-locked, made by the first call that asks for counts
     ce_dev<uint32_t> d_msssim_map;
     ce_mirror<unsigned long long> msssim_over;
+    // CIEDE2000 (ciede2000.hip): [max_pairs][10] exact integers on the device and page-locked, lazily
+    ce_mirror<unsigned long long> ciede2000;
 
     uint32_t last_n_pairs = 0;
     bool caller_blocks = false;  // set by entry points that collect before returning: page-locked sources need no staging copy
@@ -737,6 +739,16 @@ int ce_launch_hdr_fidelity(ce_batch *b, uint32_t n_pairs, uint32_t depth, const 
 int ce_launch_delta_e_itp_map(ce_batch *b, uint32_t first, uint32_t count, uint32_t depth, const float *d_table, const float *d_coarse,
                               const float a[9], const float lms[9], uint32_t block, uint32_t *d_map, const uint32_t *thresholds,
                               uint32_t n_thresholds, unsigned long long *d_over);
+
+// pairs [0, n_pairs) of an RGB8 or deep batch -> d_out[pair][10] = sum_q20, max_q20, n_above[8], cleared and filled on the
+// launching stream (ciede2000.hip): d_table_ref / d_table_test = ce_srgb_table(depth, 0) of the two sides (depth 8 for an RGB8
+// batch), thresholds[j], j < n_thresholds <= 8, what n_above[j] counts the pixels above
+int ce_launch_ciede2000(ce_batch *b, uint32_t n_pairs, const float *d_table_ref, const float *d_table_test, const uint32_t *thresholds,
+                        uint32_t n_thresholds, unsigned long long *d_out);
+// ce_ciede2000_pixels' loop (ce_ciede2000_host.cpp: ciede2000_pixel.h compiled for the host): n pixels of packed u16 RGB a side,
+// read through the sides' tables of maxv + 1 floats
+void ce_ciede2000_pixels_host(const uint16_t *ref_rgb, const float *ref_table, uint32_t ref_maxv, const uint16_t *test_rgb,
+                              const float *test_table, uint32_t test_maxv, size_t n, uint32_t *out_q20);
 
 // pairs [0, n_pairs) of an RGB8 or equal-depth deep batch, whose level l is lw[l] x lh[l] (ce_msssim_levels) -> d_out[pair][5]
 // [3][2] = ssim_q, cs_q, cleared and filled on the launching stream (msssim.hip): with five levels, every reference slot the

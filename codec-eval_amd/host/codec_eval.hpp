@@ -809,6 +809,46 @@ inline MsSsim ms_ssim_deep(const HipBackend &be, const uint16_t *reference, cons
                   len);
     return out;
 }
+// ---- CIEDE2000 of RGB8 and deep batches read as sRGB (include/ce_metrics.h: ce_batch_ciede2000) ----
+// the struct carries the doubles and the exact integers they are finished from; thresholds_q20: at most eight, in units of 2^-20
+using Ciede2000 = ce_ciede2000_scores;
+// pairs [0, n_pairs) of an RGB8 or deep batch; returns once the scores are on the host
+inline std::vector<Ciede2000> batch_ciede2000(const HipBackend &be, ce_batch *batch, uint32_t n_pairs, const std::vector<uint32_t> &thresholds_q20 = {})
+{
+    std::vector<Ciede2000> out(n_pairs);
+    detail::check(be, ce_batch_ciede2000(batch, n_pairs, thresholds_q20.empty() ? nullptr : thresholds_q20.data(), (uint32_t)thresholds_q20.size(), out.data()),
+                  "ciede2000", 0, 0, 0);
+    return out;
+}
+// one pair of packed RGB8 (width * height * 3 bytes each)
+inline Ciede2000 ciede2000(const HipBackend &be, const uint8_t *reference, const uint8_t *test, uint32_t width, uint32_t height,
+                           const std::vector<uint32_t> &thresholds_q20 = {})
+{
+    Ciede2000 out{};
+    const size_t len = (size_t)width * height * 3;
+    detail::check(be, ce_eval_pair_ciede2000(be.ctx(), reference, len, test, len, width, height, thresholds_q20.empty() ? nullptr : thresholds_q20.data(),
+                                             (uint32_t)thresholds_q20.size(), &out),
+                  "ciede2000", width, height, len);
+    return out;
+}
+// one pair of packed u16 RGB, the reference at ref_depth and the test at test_depth bits (width * height * 3 samples each)
+inline Ciede2000 ciede2000_deep(const HipBackend &be, const uint16_t *reference, const uint16_t *test, uint32_t ref_depth, uint32_t test_depth,
+                                uint32_t width, uint32_t height, const std::vector<uint32_t> &thresholds_q20 = {})
+{
+    Ciede2000 out{};
+    const size_t len = (size_t)width * height * 6;
+    detail::check(be, ce_eval_pair_ciede2000_deep(be.ctx(), reference, len, test, len, ref_depth, test_depth, width, height,
+                                                  thresholds_q20.empty() ? nullptr : thresholds_q20.data(), (uint32_t)thresholds_q20.size(), &out),
+                  "ciede2000", width, height, len);
+    return out;
+}
+// the per-pixel values in units of 2^-20 of n pixels of packed u16 RGB (a pure host function; empty when refused)
+inline std::vector<uint32_t> ciede2000_pixels(const uint16_t *reference, uint32_t ref_depth, const uint16_t *test, uint32_t test_depth, size_t n)
+{
+    std::vector<uint32_t> out(n);
+    if (ce_ciede2000_pixels(reference, ref_depth, test, test_depth, n, out.data()) != CE_OK) out.clear();
+    return out;
+}
 // the window's eleven literals, and the (width, height) of every level (pure host functions; empty when refused)
 inline std::array<double, 11> msssim_window()
 {

@@ -1121,6 +1121,103 @@ int ce_eval_pair_msssim_map_deep(ce_ctx *ctx, const uint16_t *reference, size_t 
                                  uint32_t block, uint32_t *map, size_t map_len, const uint32_t *thresholds_q32, uint32_t n_thresholds,
                                  uint64_t *over);
 
+/* ---- CIEDE2000 of RGB8 and deep batches, exactly ----------------------------------------------------------
+ * How far colour drifts, on average and at worst: the CIE's Delta E 2000 between the two sides of every pixel, read as sRGB.  A
+ * call of its own beside the launch, as HDR fidelity and MS-SSIM are.  Every operation below is one IEEE f64 operation, rounded
+ * separately (no fused multiply-add), in the order the parentheses give; the per-pixel value is quantised and everything after
+ * it is an integer, so no result depends on the grid or on the order of summation.
+ * Samples.  The integers in the slabs of an RGB8 batch (depth 8) or of a deep batch, each side at its own depth d (8, 10, 12 or
+ *   16); the two depths may differ.  Per pixel and per side, channels R, G, B:
+ * 1. Linear value.  e_c = (double) T_d[min(v_c, 2^d - 1)], T_d = ce_srgb_table(d, 0): the f32 values SSIMULACRA2 reads, widened
+ *    exactly.
+ * 2. XYZ (OpenCV's and scikit-image's matrix).  X = ((0.412453 * e_r) + (0.357580 * e_g)) + (0.180423 * e_b);
+ *    Y = ((0.212671 * e_r) + (0.715160 * e_g)) + (0.072169 * e_b);  Z = ((0.019334 * e_r) + (0.119193 * e_g)) + (0.950227 * e_b).
+ *    The white is the row sums: tx = X / 0.950456, ty = Y, tz = Z / 1.088754.
+ * 3. Lab.  f(t) = cbrt(t) if t > 216.0 / 24389.0, else (((24389.0 / 27.0) * t) + 16.0) / 116.0;  fx = f(tx), fy = f(ty), fz = f(tz);
+ *    L = (116.0 * fy) - 16.0;  a = 500.0 * (fx - fy);  b = 200.0 * (fy - fz).
+ * 4. CIEDE2000 with kL = kC = kH = 1, in the form of Sharma, Wu and Dalal (2005); side 1 is the reference, side 2 the test:
+ *    C_i = sqrt((a_i * a_i) + (b_i * b_i));  Cb = 0.5 * (C_1 + C_2);  p7(c) = (((c * c) * c) * ((c * c) * c)) * c;
+ *    G = 0.5 * (1.0 - sqrt(p7(Cb) / (p7(Cb) + 6103515625.0)));  a'_i = (1.0 + G) * a_i;  C'_i = sqrt((a'_i * a'_i) + (b_i * b_i));
+ *    h_i = hue(b_i, a'_i) in degrees in [0, 360), 0 when a'_i = b_i = 0;
+ *    dL = L_2 - L_1;  dC = C'_2 - C'_1;  cc = C'_1 * C'_2;
+ *    dh = h_2 - h_1, minus 360.0 if above 180.0, plus 360.0 if below -180.0, and 0.0 when cc == 0;
+ *    dH = (2.0 * sqrt(cc)) * sin_deg(0.5 * dh);
+ *    hs = h_1 + h_2;  hb = hs when cc == 0; else 0.5 * hs when |h_1 - h_2| <= 180.0; else 0.5 * (hs + 360.0) when hs < 360.0;
+ *    else 0.5 * (hs - 360.0);
+ *    Lb = 0.5 * (L_1 + L_2);  Cpb = 0.5 * (C'_1 + C'_2);
+ *    T = (((1.0 - (0.17 * cos_deg(hb - 30.0))) + (0.24 * cos_deg(2.0 * hb))) + (0.32 * cos_deg((3.0 * hb) + 6.0)))
+ *        - (0.20 * cos_deg((4.0 * hb) - 63.0));
+ *    z = (hb - 275.0) / 25.0;  dtheta = 30.0 * exp(-(z * z));  R_C = 2.0 * sqrt(p7(Cpb) / (p7(Cpb) + 6103515625.0));
+ *    l2 = (Lb - 50.0) * (Lb - 50.0);  S_L = 1.0 + ((0.015 * l2) / sqrt(20.0 + l2));  S_C = 1.0 + (0.045 * Cpb);
+ *    S_H = 1.0 + ((0.015 * Cpb) * T);  R_T = (-sin_deg(2.0 * dtheta)) * R_C;
+ *    tl = dL / S_L;  tc = dC / S_C;  th = dH / S_H;
+ *    dE = sqrt(max((((tl * tl) + (tc * tc)) + (th * th)) + (R_T * (tc * th)), 0.0)) - the max because the form is positive
+ *    definite only in exact arithmetic.
+ * 5. q = rint(dE * 2^20), ties to even: an integer under 2^32 (dE stays under 120 for sRGB colours), the unit of
+ *    ce_batch_delta_e_itp_map's values.
+ * Elementary functions.  Fixed sequences of f64 + - * /, sqrt, one rint, comparisons and integer work on exponent bits; no libm
+ *   and no device math library (codec-eval_amd/csrc/ciede2000_pixel.h holds them; hlg_pixel.h the exponential's series):
+ *   cbrt(t), t = m * 2^e with m in [1, 2), e = 3 * k + r, r in {0, 1, 2}:  y = 0.7401 + (0.2599 * m); three times
+ *     y3 = (y * y) * y, y = (y * (y3 + (m + m))) / ((y3 + y3) + m);  result ((y * c_r) * 2^k), c = {1, 1.2599210498948732,
+ *     1.5874010519681994}.
+ *   hue(b, a):  t = min(|a|, |b|) / max(|a|, |b|);  u = (t - 1.0) / (t + 1.0) when t > 0.41421356237309503, else t;  P = the
+ *     polynomial in (u * u) with coefficients 1, -1/3, 1/5, ... 1/49 (each the correctly rounded quotient) in Horner form from
+ *     1/49 down, p = (p * u2) + c;  d = (u * P) * 57.29577951308232, plus 45.0 in the first case;  d = 90.0 - d when |b| > |a|;
+ *     d = 180.0 - d when a < 0;  d = 360.0 - d when b < 0;  d = d - 360.0 when d >= 360.0.
+ *   sin_deg(x), cos_deg(x):  n = rint(x / 90.0);  r = x - (90.0 * n) (exact);  rr = r * 0.017453292519943295;  S = rr * the
+ *     polynomial in (rr * rr) with coefficients 1, -1/3!, ... 1/17!, C = the one with 1, -1/2!, ... -1/18!, both in Horner form
+ *     from the highest down;  n mod 4 = 0, 1, 2, 3 gives sin = S, C, -S, -C and cos = C, -S, -C, S.
+ *   exp(y), y <= 0:  n = rint(y / 0.6931471805599453);  f = y - (n * 0.6931471805599453);  the Taylor series of exp f to degree 14
+ *     in Horner form from 1/14! down, times 2^n built from bits (ce_batch_set_*_hlg's exp_times_pow2).
+ * 6. Per pair, over its width * height pixels:  sum_q20 = the sum of q (64 bits);  max_q20 = the largest q;  n = the number of
+ *    pixels;  n_above[k] = the number of pixels with q > thresholds_q20[k], k < n_thresholds <= CE_CIEDE2000_MAX_THRESHOLDS (the
+ *    rest 0).  A threshold of 2^32 - 1 counts nothing.
+ * 7. Finishing, on the host in f64:  mean = ((double) sum_q20 / 1048576.0) / (double) n;  max = (double) max_q20 / 1048576.0;
+ *    ciede2000_db = 45.0 - 20.0 * log10(mean), +infinity when sum_q20 is 0.  The last is the PSNR-like form in which Daala's
+ *    tools and libvmaf's feature report CIEDE2000, as remembered: it could not be verified against either where this was
+ *    written, so treat the constant as this library's own.
+ * Properties.  Identical samples at one depth give q = 0 exactly, and so does any pixel whose two sides hold the same table
+ *   values - 8-bit v against 16-bit 257 * v.  Black against white gives q = 100 * 2^20 exactly.  The fixed sequences stay within
+ *   1e-8 of the same formula through libm on 8-bit content, so q differs by at most one; of the 34 pairs of Sharma
+ *   et al.'s table they reproduce 33 to the fourth decimal, and (50, -0.001, 2.49) against (50, 0.0010, -2.49), whose hues are
+ *   180 degrees apart on the formula's own discontinuity, falls on the other side of it: 4.7461 for 4.8045.
+ * tests/ciede2000_restatement.py restates this in numpy; the device and ce_ciede2000_pixels equal it on every integer. */
+#define CE_CIEDE2000_MAX_THRESHOLDS 8
+#define CE_CIEDE2000_Q20 1048576u
+typedef struct ce_ciede2000_scores {
+    uint64_t sum_q20;       /* the exact integers the doubles are finished from */
+    uint64_t n;
+    uint64_t n_above[8];    /* pixels with q > thresholds_q20[k]; 0 from n_thresholds on */
+    double mean;            /* mean Delta E 2000 of the pair's pixels */
+    double max;             /* the largest */
+    double ciede2000_db;    /* 45 - 20 log10(mean); +infinity for a mean of 0 */
+    uint32_t max_q20;
+    uint32_t n_thresholds;
+    uint32_t reserved[2];   /* 0 */
+} ce_ciede2000_scores;      /* 120 bytes */
+/* Scores pairs [0, n_pairs) of an RGB8 or deep batch into out[0 .. n_pairs): on the context's stream, ordered behind the uploads
+ * queued so far as a launch is, with the pair table of the last bind; blocks until the scores are on the host.  ce_scores, the
+ * stored maps and whatever ce_batch_launch left to collect are untouched.  thresholds_q20 may be NULL with n_thresholds 0.
+ * CE_ERR_INVALID_ARG, with the reason in ce_last_error and the batch still usable: a linear batch (its colour difference is
+ * ce_batch_hdr_fidelity's Delta E ITP); more than 8 thresholds; a null pointer (out; thresholds_q20 with n_thresholds > 0);
+ * n_pairs of 0 or past the batch. */
+int ce_batch_ciede2000(ce_batch *b, uint32_t n_pairs, const uint32_t *thresholds_q20, uint32_t n_thresholds, ce_ciede2000_scores *out);
+/* One pair of packed RGB8 host images (lengths in bytes: width * height * 3), and one pair of packed u16 RGB at ref_depth /
+ * test_depth (each 8, 10, 12 or 16; width * height * 6 bytes a side), through the context's one-pair batches.
+ * CE_ERR_INVALID_ARG as above and for an empty image or a depth that is none of the four, CE_ERR_BAD_LENGTH for a length that is
+ * not the image's. */
+int ce_eval_pair_ciede2000(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test, size_t test_len,
+                           uint32_t width, uint32_t height, const uint32_t *thresholds_q20, uint32_t n_thresholds,
+                           ce_ciede2000_scores *out);
+int ce_eval_pair_ciede2000_deep(ce_ctx *ctx, const uint16_t *reference, size_t reference_len, const uint16_t *test, size_t test_len,
+                                uint32_t ref_depth, uint32_t test_depth, uint32_t width, uint32_t height,
+                                const uint32_t *thresholds_q20, uint32_t n_thresholds, ce_ciede2000_scores *out);
+/* A pure host function, no GPU needed: q of n pixels, ref_rgb and test_rgb holding n * 3 samples of ref_depth / test_depth bits
+ * (8, 10, 12 or 16) - the same pixel text as the kernel's, compiled for the host.  CE_ERR_INVALID_ARG for a null pointer or such
+ * a depth. */
+int ce_ciede2000_pixels(const uint16_t *ref_rgb, uint32_t ref_depth, const uint16_t *test_rgb, uint32_t test_depth, size_t n,
+                        uint32_t *out_q20);
+
 /* ---- a decoder's Y'CbCr planes scored as planes: PSNR, SSIM and MS-SSIM per plane -----------------------
  * What codec test conditions (AOM, JVET, JPEG) tabulate: PSNR-Y, PSNR-Cb, PSNR-Cr on the planes the decoder wrote, each at its
  * own resolution - no chroma upsampling, no colour matrix, no RGB clamp - with the 6:1:1 weighted and the overall PSNR, and
