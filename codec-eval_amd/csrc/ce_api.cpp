@@ -581,6 +581,30 @@ static int sync_pair_ref(ce_batch *b)
     return CE_OK;
 }
 
+// What a launch of DSSIM, SSIMULACRA2 and Butteraugli takes (ce_plan.h): their front ends put the
+// launch's image slots, or a plane's rows, into a grid's y or z.  The rule counts the references the pairs name whether or not
+// the launch would find their state kept, so a launch is refused or runs whatever ran before it.  PSNR takes any n_pairs.
+static_assert(ce_grid_yz_max == CE_LAUNCH_GRID_MAX && ce_launch_slots_max == CE_LAUNCH_MAX_SLOTS &&
+                  ce_ba_height_max == CE_BUTTERAUGLI_MAX_HEIGHT && ce_ssim2_height_max == CE_SSIMULACRA2_MAX_HEIGHT,
+              "ce_plan.h and ce_metrics.h state the same limits");
+static int launch_fits(ce_ctx *ctx, uint32_t w, uint32_t h, uint32_t n_refs_used, uint32_t n_pairs, uint32_t metric_mask)
+{
+    const bool ssim2 = (metric_mask & CE_METRIC_SSIMULACRA2) && w >= 8 && h >= 8, ba = (metric_mask & CE_METRIC_BUTTERAUGLI) && w >= 8 && h >= 8;
+    if (!ssim2 && !ba && !(metric_mask & CE_METRIC_DSSIM)) return CE_OK;
+    if ((uint64_t)n_refs_used + n_pairs > ce_launch_slots_max)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG,
+                       "launch too large: " + std::to_string(n_refs_used) + " references + " + std::to_string(n_pairs) + " pairs = " +
+                           std::to_string((uint64_t)n_refs_used + n_pairs) + " image slots, DSSIM, SSIMULACRA2 and Butteraugli take at most " +
+                           std::to_string(ce_launch_slots_max) + " slots in one launch");
+    if (ba && h > ce_ba_height_max)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG,
+                       "image too tall: height " + std::to_string(h) + ", Butteraugli takes at most " + std::to_string(ce_ba_height_max) + " rows");
+    if (ssim2 && h > ce_ssim2_height_max)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG,
+                       "image too tall: height " + std::to_string(h) + ", SSIMULACRA2 takes at most " + std::to_string(ce_ssim2_height_max) + " rows");
+    return CE_OK;
+}
+
 int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_t flags, float intensity_target)
 {
     if (!b) return CE_ERR_INVALID_ARG;
@@ -591,6 +615,10 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
         return ce_fail(ctx, CE_ERR_INVALID_ARG, "CE_FLAG_XYB_ROUNDTRIP quantises to 8 bits by definition: not for a deep batch");
     if (b->linear && (flags & CE_FLAG_XYB_ROUNDTRIP))
         return ce_fail(ctx, CE_ERR_INVALID_ARG, "CE_FLAG_XYB_ROUNDTRIP quantises to 8 bits by definition: not for a linear batch");
+    uint32_t n_refs_used = 0;
+    for (uint32_t i = 0; i < n_pairs; i++) n_refs_used = std::max(n_refs_used, b->h_pair_ref[i] + 1);
+    // a launch that does not fit a grid is refused here: nothing has run, and every record of reference state stands
+    if (int rc = launch_fits(ctx, b->w, b->h, n_refs_used, n_pairs, metric_mask)) return rc;
     b->ba_map_pairs = b->ds_map_pairs = 0;  // whatever happens below, no readout returns the maps of an earlier launch
     b->s2_map_pairs = b->s2_norm_pairs = 0;
     CE_HIP(ctx, hipSetDevice(ctx->device));
@@ -599,8 +627,6 @@ int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_
         if (rc != CE_OK) return rc;
     }
     if (int rc = sync_pair_ref(b)) return rc;
-    uint32_t n_refs_used = 0;
-    for (uint32_t i = 0; i < n_pairs; i++) n_refs_used = std::max(n_refs_used, b->h_pair_ref[i] + 1);
 
     const uint8_t *d_refs = b->d_refs;
     if (flags & CE_FLAG_XYB_ROUNDTRIP) {
@@ -1061,7 +1087,8 @@ int ce_eval_batch_lut(ce_ctx *ctx, size_t n, const ce_pair_desc *pairs, const ce
         const size_t per_pair = estimate_batch_bytes(w, h, 1, 2, metric_mask, false) - estimate_batch_bytes(w, h, 1, 1, metric_mask, false) +
                                 estimate_batch_bytes(w, h, 2, 1, metric_mask, false) - estimate_batch_bytes(w, h, 1, 1, metric_mask, false);  // a pair with a reference of its own
         auto pooled = ctx->shape_pool.find(std::make_tuple(w, h, 0u));
-        const ce_plan_inputs in{chunk_budget(ctx), per_pair, pooled != ctx->shape_pool.end() ? pooled->second->max_pairs : 0u, forced_chunks, ramp0};
+        const ce_plan_inputs in{chunk_budget(ctx), per_pair, pooled != ctx->shape_pool.end() ? pooled->second->max_pairs : 0u, forced_chunks, ramp0,
+                                 ce_launch_slots_max};
         const size_t first = plan.size();
         ce_plan_bucket(it->second, refs, in, ring, plan);
         running.resize(plan.size());

@@ -15,6 +15,13 @@ struct ce_plane_geom {
     size_t plane;
 };
 
+// What one launch takes.  A grid's y and z hold at most 65535 blocks, and the main metrics' front ends
+// put the launch's image slots - the references it uses plus its pairs - or a plane's rows into one of them.
+inline constexpr uint32_t ce_grid_yz_max = 65535;
+inline constexpr uint32_t ce_launch_slots_max = ce_grid_yz_max;    // references + pairs of a launch with DSSIM, SSIMULACRA2 or Butteraugli
+inline constexpr uint32_t ce_ba_height_max = 4 * ce_grid_yz_max;     // Butteraugli: k_ba_mask_vals, 4 rows to a block of y
+inline constexpr uint32_t ce_ssim2_height_max = 8 * ce_grid_yz_max;  // SSIMULACRA2: k_ssim2_prep, 4 rows of 2 x 2 quads to a block of y
+
 inline constexpr uint32_t ce_plan_ring_slots = 3;  // pooled batches per shape a bucket streams through (ce_ctx::kPoolRing)
 inline constexpr size_t ce_plan_none = ~(size_t)0;
 
@@ -24,6 +31,7 @@ struct ce_plan_inputs {
     uint32_t pooled_pairs;  // max_pairs of this shape's pooled batch on ring slot 0, 0 if there is none
     size_t forced_chunks;   // CE_EVAL_BATCH_CHUNKS, 0 = by size
     size_t ramp;            // CE_EVAL_BATCH_RAMP: pairs of the call's first chunk, 0 = every chunk at the target
+    size_t max_slots = ce_launch_slots_max;  // references plus pairs one launch takes, at least 2; a caller that names none gets the launch's own
 };
 
 struct ce_plan_chunk {
@@ -55,6 +63,8 @@ inline void ce_plan_bucket(const std::vector<size_t> &items, const std::vector<c
     // ... and fits the budget (a larger grid streams through the ring in more chunks; a reference with more tests than
     // that is split and uploaded once per part)
     size_t target = std::min((n + n_chunks - 1) / n_chunks, std::max<size_t>(1, in.budget / std::max<size_t>(in.per_pair, 1)));
+    // ... and a launch: a chunk holds its references beside its pairs, the smallest one reference beside `target` pairs
+    target = std::min(target, std::max<size_t>(in.max_slots, 2) - 1);
     // a pooled batch a little smaller than that (estimate and free memory move by a few per cent) is used as it is
     if (in.pooled_pairs < target && (size_t)in.pooled_pairs * 4 >= target * 3) target = in.pooled_pairs;
     std::vector<std::vector<size_t>> split;
@@ -67,7 +77,10 @@ inline void ce_plan_bucket(const std::vector<size_t> &items, const std::vector<c
     const size_t bucket_begin = plan.size();
     for (size_t g0 = 0, g1 = 0; g0 < split.size(); g0 = g1) {
         size_t count = 0;
-        while (g1 < split.size() && (count == 0 || count + split[g1].size() <= limit)) count += split[g1++].size();
+        // (g1 - g0 references so far; a part is at most `target` pairs, so the chunk's first part always fits the launch)
+        while (g1 < split.size() && (count == 0 || (count + split[g1].size() <= limit &&
+                                                    count + split[g1].size() + (g1 - g0) + 1 <= in.max_slots)))
+            count += split[g1++].size();
         limit = std::min(target, limit * 2);
         // several chunks: every ring slot is sized for the target, so that a later, larger chunk does not reallocate it
         ce_plan_chunk c{ring++ % ce_plan_ring_slots, (uint32_t)(several ? std::max(count, target) : count), ce_plan_none,

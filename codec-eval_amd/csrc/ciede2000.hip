@@ -1,6 +1,6 @@
 // CIEDE2000 of an RGB8 or deep batch (include/ce_metrics.h: ce_batch_ciede2000): per pair the sum and
 // the maximum of the per-pixel colour difference in units of 2^-20 and how many pixels exceed each of up to eight thresholds -
-// exact integers, which the host finishes in f64.  One launch over (blocks, pairs) in k_hdr_fidelity's frame: the two slabs
+// exact integers, which the host finishes in f64.  One launch over (blocks, pairs) - one per 65535 pairs - in k_hdr_fidelity's frame: the two slabs
 // through pair_ref, a u64 sum, a maximum and eight counts a lane, a reduction across the wave by shuffles and across the block
 // in LDS, and one integer vector atomic per block and value.  Integer sums, maxima and counts do not depend on the order, so
 // the scores do not depend on the grid.
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(kCieThreads) void k_ciede2000(const cie_args a, uns
         unsigned long long t = 0;
 #pragma unroll
         for (int w = 0; w < (int)kCieThreads / 64; w++) t = j == 1 ? (s_part[w][j] > t ? s_part[w][j] : t) : t + s_part[w][j];
-        unsigned long long *o = out + (size_t)blockIdx.y * kCieOut + j;
+        unsigned long long *o = out + (size_t)cie_pair(a) * kCieOut + j;
         if (t) {
             if (j == 1) atomicMax(o, t); else atomicAdd(o, t);
         }
@@ -65,10 +65,14 @@ int ce_launch_ciede2000(ce_batch *b, uint32_t n_pairs, const float *d_table_ref,
     g.depth[0] = deep ? b->depth[0] : 8, g.depth[1] = deep ? b->depth[1] : 8;
     g.n_pixels = (size_t)b->w * b->h;
     for (uint32_t j = 0; j < (uint32_t)kCieMaxThresholds; j++) g.thr[j] = j < n_thresholds ? thresholds[j] : 0xffffffffu;
-    const dim3 grid(cie_blocks(g.n_pixels, n_pairs, deep), n_pairs);
+    const uint32_t blocks = cie_blocks(g.n_pixels, n_pairs, deep);
     const size_t lds = sizeof(float) * cie_lds_floats(g.depth[0], g.depth[1]);
-    if (deep) CE_LAUNCH(ctx, "ciede2000_u16", k_ciede2000<true>, grid, dim3(kCieThreads), lds, g, d_out);
-    else CE_LAUNCH(ctx, "ciede2000_u8", k_ciede2000<false>, grid, dim3(kCieThreads), lds, g, d_out);
+    // pairs [first, first + count) a launch: a grid's y holds at most ce_grid_yz_max pairs
+    for (g.first = 0; g.first < n_pairs; g.first += ce_grid_yz_max) {
+        const dim3 grid(blocks, std::min(n_pairs - g.first, ce_grid_yz_max));
+        if (deep) CE_LAUNCH(ctx, "ciede2000_u16", k_ciede2000<true>, grid, dim3(kCieThreads), lds, g, d_out);
+        else CE_LAUNCH(ctx, "ciede2000_u8", k_ciede2000<false>, grid, dim3(kCieThreads), lds, g, d_out);
+    }
     CE_HIP(ctx, hipGetLastError());
     return CE_OK;
 }

@@ -28,7 +28,11 @@ struct cie_args {
     uint32_t depth[2];          // 8, 10, 12 or 16 (8 / 8 for an RGB8 batch)
     size_t n_pixels;
     uint32_t thr[kCieMaxThresholds];  // q > thr[j] is counted; 2^32 - 1 past the caller's thresholds
+    uint32_t first;             // the launch's pairs are [first, first + gridDim.y)
 };
+
+// the pair of this block
+__device__ __forceinline__ uint32_t cie_pair(const cie_args &a) { return a.first + blockIdx.y; }
 
 // what a lane carries: the sum and the maximum of its pixels' q and how many exceed each threshold
 struct cie_acc {
@@ -101,7 +105,7 @@ __device__ __forceinline__ void cie_pixel(const cie_args &a, const cie_tab &tr, 
     for (int j = 0; j < kCieMaxThresholds; j++) acc.cnt[j] += q > a.thr[j] ? 1u : 0u;
 }
 
-// After the barrier: this lane's share of pair blockIdx.y, in k_hdr_fidelity's frame.  On the wide path a lane's unit is the
+// After the barrier: this lane's share of pair first + blockIdx.y, in k_hdr_fidelity's frame.  On the wide path a lane's unit is the
 // twelve dwords of three 16-byte loads a side; its pixels are taken from the low end one at a time - the loop is not unrolled,
 // the pixel being some thousand instructions - and the dwords are shifted down by a pixel (3 or 6 bytes) in between, so that
 // no register is indexed by a variable.
@@ -110,7 +114,7 @@ __device__ __forceinline__ void cie_lane(const cie_args &a, const float *s_tab, 
 {
     cie_tab tr, tt;
     cie_tabs(a, s_tab, tr, tt);
-    const uint32_t p = blockIdx.y;
+    const uint32_t p = cie_pair(a);
     const size_t img = a.n_pixels * 3 * (DEEP ? 2 : 1);  // bytes
     const uint8_t *ref = static_cast<const uint8_t *>(a.refs) + (size_t)a.pair_ref[p] * img;
     const uint8_t *test = static_cast<const uint8_t *>(a.tests) + (size_t)p * img;

@@ -1,7 +1,7 @@
 // HDR fidelity of a linear batch (include/ce_metrics.h: ce_batch_hdr_fidelity): PSNR in the PQ domain and
 // the Delta E ITP of Rec. ITU-R BT.2124, as three exact integers per pair - the sum of squared PQ code differences, and the sum
 // and the maximum of the per-pixel Delta E in units of 2^-20 - which the host finishes in f64.  One launch over
-// (blocks, pairs) in psnr.hip's frame: the two f32 slabs through pair_ref, three u64 accumulators a lane, a reduction across
+// (blocks, pairs) - one per 65535 pairs, which is what a grid's y holds - in psnr.hip's frame: the two f32 slabs through pair_ref, three u64 accumulators a lane, a reduction across
 // the wave and the block, and one integer atomic per block and value.  Integer sums and maxima do not depend on the order, so
 // the scores do not depend on the grid.
 //
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(kHdrfThreads) void k_hdr_fidelity(const hdrf_args a
             t[0] += s_part[w][0], t[1] += s_part[w][1];
             t[2] = s_part[w][2] > t[2] ? s_part[w][2] : t[2];
         }
-        unsigned long long *o = out + (size_t)blockIdx.y * 3;
+        unsigned long long *o = out + (size_t)hdrf_pair(a) * 3;
         atomicAdd(o, t[0]);
         atomicAdd(o + 1, t[1]);
         atomicMax(o + 2, t[2]);
@@ -77,11 +77,12 @@ __global__ __launch_bounds__(kHdrfThreads) void k_delta_e_itp_map(const hdrf_arg
         unsigned long long t = 0;
 #pragma unroll
         for (int w = 0; w < (int)kHdrfThreads / 64; w++) t += s_part[w][threadIdx.x];
-        if (t) atomicAdd(over + (size_t)blockIdx.y * kItpMaxThresholds + threadIdx.x, t);
+        if (t) atomicAdd(over + (size_t)hdrf_pair(a) * kItpMaxThresholds + threadIdx.x, t);
     }
 }
 
-// what both launches hand their kernel: pairs [first, ...) of the batch at `depth`
+// what both launches hand their kernel: pairs [first, ...) of the batch at `depth`; a launch then takes a range of those
+// (hdrf_args::first), at most ce_grid_yz_max to a grid's y
 hdrf_args hdrf_fill(const ce_batch *b, uint32_t first, uint32_t depth, const float *d_table, const float *d_coarse, const float a[9],
                     const float lms[9])
 {
@@ -103,13 +104,16 @@ int ce_launch_hdr_fidelity(ce_batch *b, uint32_t n_pairs, uint32_t depth, const 
     ce_ctx *ctx = b->ctx;
     hipStream_t stream = CE_STREAM(ctx);
     CE_HIP(ctx, hipMemsetAsync(d_out, 0, sizeof(unsigned long long) * 3 * n_pairs, stream));
-    const hdrf_args g = hdrf_fill(b, 0, depth, d_table, d_coarse, a, lms);
-    const dim3 grid(hdrf_blocks(g.n_pixels, n_pairs), n_pairs);
-    switch (depth) {
-        case 10: CE_LAUNCH(ctx, "hdr_fidelity_10", k_hdr_fidelity<10>, grid, dim3(kHdrfThreads), 0, g, d_out); break;
-        case 12: CE_LAUNCH(ctx, "hdr_fidelity_12", k_hdr_fidelity<12>, grid, dim3(kHdrfThreads), 0, g, d_out); break;
-        case 16: CE_LAUNCH(ctx, "hdr_fidelity_16", k_hdr_fidelity<16>, grid, dim3(kHdrfThreads), 0, g, d_out); break;
-        default: ctx->err = "HDR fidelity: depth must be 10, 12 or 16"; return CE_ERR_INVALID_ARG;
+    hdrf_args g = hdrf_fill(b, 0, depth, d_table, d_coarse, a, lms);
+    const uint32_t blocks = hdrf_blocks(g.n_pixels, n_pairs);
+    for (g.first = 0; g.first < n_pairs; g.first += ce_grid_yz_max) {
+        const dim3 grid(blocks, std::min(n_pairs - g.first, ce_grid_yz_max));
+        switch (depth) {
+            case 10: CE_LAUNCH(ctx, "hdr_fidelity_10", k_hdr_fidelity<10>, grid, dim3(kHdrfThreads), 0, g, d_out); break;
+            case 12: CE_LAUNCH(ctx, "hdr_fidelity_12", k_hdr_fidelity<12>, grid, dim3(kHdrfThreads), 0, g, d_out); break;
+            case 16: CE_LAUNCH(ctx, "hdr_fidelity_16", k_hdr_fidelity<16>, grid, dim3(kHdrfThreads), 0, g, d_out); break;
+            default: ctx->err = "HDR fidelity: depth must be 10, 12 or 16"; return CE_ERR_INVALID_ARG;
+        }
     }
     CE_HIP(ctx, hipGetLastError());
     return CE_OK;
@@ -121,7 +125,7 @@ int ce_launch_delta_e_itp_map(ce_batch *b, uint32_t first, uint32_t count, uint3
 {
     ce_ctx *ctx = b->ctx;
     hipStream_t stream = CE_STREAM(ctx);
-    const hdrf_args g = hdrf_fill(b, first, depth, d_table, d_coarse, a, lms);
+    hdrf_args g = hdrf_fill(b, first, depth, d_table, d_coarse, a, lms);
     hdrf_map_args m{};
     m.map = d_map, m.w = b->w;
     while ((1u << m.lb) < block) m.lb++;
@@ -130,12 +134,15 @@ int ce_launch_delta_e_itp_map(ce_batch *b, uint32_t first, uint32_t count, uint3
     for (uint32_t j = 0; j < (uint32_t)kItpMaxThresholds; j++) m.thr[j] = j < n_thresholds ? thresholds[j] : 0xffffffffu;
     if (d_map && m.lb) CE_HIP(ctx, hipMemsetAsync(d_map, 0, sizeof(uint32_t) * m.pair_len * count, stream));
     if (d_over) CE_HIP(ctx, hipMemsetAsync(d_over, 0, sizeof(unsigned long long) * kItpMaxThresholds * count, stream));
-    const dim3 grid(hdrf_blocks(g.n_pixels, count), count);
-    switch (depth) {
-        case 10: CE_LAUNCH(ctx, "delta_e_itp_map_10", k_delta_e_itp_map<10>, grid, dim3(kHdrfThreads), 0, g, m, n_thresholds, d_over); break;
-        case 12: CE_LAUNCH(ctx, "delta_e_itp_map_12", k_delta_e_itp_map<12>, grid, dim3(kHdrfThreads), 0, g, m, n_thresholds, d_over); break;
-        case 16: CE_LAUNCH(ctx, "delta_e_itp_map_16", k_delta_e_itp_map<16>, grid, dim3(kHdrfThreads), 0, g, m, n_thresholds, d_over); break;
-        default: ctx->err = "Delta E ITP map: depth must be 10, 12 or 16"; return CE_ERR_INVALID_ARG;
+    const uint32_t blocks = hdrf_blocks(g.n_pixels, count);
+    for (g.first = 0; g.first < count; g.first += ce_grid_yz_max) {
+        const dim3 grid(blocks, std::min(count - g.first, ce_grid_yz_max));
+        switch (depth) {
+            case 10: CE_LAUNCH(ctx, "delta_e_itp_map_10", k_delta_e_itp_map<10>, grid, dim3(kHdrfThreads), 0, g, m, n_thresholds, d_over); break;
+            case 12: CE_LAUNCH(ctx, "delta_e_itp_map_12", k_delta_e_itp_map<12>, grid, dim3(kHdrfThreads), 0, g, m, n_thresholds, d_over); break;
+            case 16: CE_LAUNCH(ctx, "delta_e_itp_map_16", k_delta_e_itp_map<16>, grid, dim3(kHdrfThreads), 0, g, m, n_thresholds, d_over); break;
+            default: ctx->err = "Delta E ITP map: depth must be 10, 12 or 16"; return CE_ERR_INVALID_ARG;
+        }
     }
     CE_HIP(ctx, hipGetLastError());
     return CE_OK;

@@ -28,7 +28,11 @@ struct hdrf_args {
     size_t n_pixels;
     float a[9], b[9];              // BT.2020 <- sRGB primaries; BT.2100's LMS <- BT.2020
     double denom;                  // 4096 * maxv
+    uint32_t first;                // the launch's pairs are [first, first + gridDim.y) of those that tests and pair_ref start at
 };
+
+// the pair of this block
+__device__ __forceinline__ uint32_t hdrf_pair(const hdrf_args &a) { return a.first + blockIdx.y; }
 
 // The blocks a pair gets in a launch of n_pairs: a lane's unit of work is four pixels on the wide path and one on the other; a
 // block has up to 16 KB of table to stage, so at most 64 blocks a pair, or what keeps a launch of few pairs near 1024 blocks.
@@ -122,13 +126,13 @@ __device__ __forceinline__ void hdrf_pixel(const hdrf_args &a, const float *s_ta
     acc[2] = k > acc[2] ? k : acc[2];
 }
 
-// After the barrier: this lane's share of pair blockIdx.y, in k_psnr_sse's frame.  An image whose byte size is a multiple of
+// After the barrier: this lane's share of pair first + blockIdx.y, in k_psnr_sse's frame.  An image whose byte size is a multiple of
 // 16 - a multiple of four pixels; every image of a slab then starts 16-byte aligned - is read as groups of four pixels, three
 // 16-byte loads a side; any other pixel by pixel.
 template <int DEPTH>
 __device__ __forceinline__ void hdrf_lane(const hdrf_args &a, const float *s_tab, unsigned long long acc[3])
 {
-    const uint32_t p = blockIdx.y;
+    const uint32_t p = hdrf_pair(a);
     const size_t img = a.n_pixels * 3;
     const float *ref = a.refs + (size_t)a.pair_ref[p] * img;
     const float *test = a.tests + (size_t)p * img;

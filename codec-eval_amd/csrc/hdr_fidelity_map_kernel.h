@@ -57,12 +57,12 @@ __device__ __forceinline__ void hdrf_cell_put(uint32_t *cells, hdrf_cell_run &r,
     r.best = v > r.best ? v : r.best;
 }
 
-// After the barrier: this lane's share of pair blockIdx.y in hdrf_lane's frame.  cnt[j] = how many of its pixels exceed
+// After the barrier: this lane's share of pair first + blockIdx.y in hdrf_lane's frame.  cnt[j] = how many of its pixels exceed
 // thr[j].  A pair's map starts 16-byte aligned on the wide path: pair_len = n_pixels is a multiple of four there.
 template <int DEPTH>
 __device__ __forceinline__ void hdrf_map_lane(const hdrf_args &a, const hdrf_map_args &m, const float *s_tab, uint32_t cnt[kItpMaxThresholds])
 {
-    const uint32_t p = blockIdx.y;
+    const uint32_t p = hdrf_pair(a);
     const size_t img = a.n_pixels * 3;
     const float *ref = a.refs + (size_t)a.pair_ref[p] * img;
     const float *test = a.tests + (size_t)p * img;

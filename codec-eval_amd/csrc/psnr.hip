@@ -27,9 +27,9 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 __global__ __launch_bounds__(kThreads) void k_psnr_sse(const uint8_t *__restrict__ refs,
                                                        const uint8_t *__restrict__ tests,
                                                        const uint32_t *__restrict__ pair_ref,
-                                                       ce_dev_scores *__restrict__ scores, size_t img_bytes)
+                                                       ce_dev_scores *__restrict__ scores, size_t img_bytes, uint32_t first)
 {
-    const uint32_t p = blockIdx.y;
+    const uint32_t p = first + blockIdx.y;
     const uint8_t *a = refs + (size_t)pair_ref[p] * img_bytes;
     const uint8_t *b = tests + (size_t)p * img_bytes;
     unsigned long long sse = 0;
@@ -79,9 +79,9 @@ __global__ __launch_bounds__(kThreads) void k_psnr_sse(const uint8_t *__restrict
 // 2^32 and added in u64.
 __global__ __launch_bounds__(kThreads) void k_psnr_sse_u16(const uint8_t *__restrict__ refs, const uint8_t *__restrict__ tests,
                                                            const uint32_t *__restrict__ pair_ref, ce_dev_scores *__restrict__ scores,
-                                                           size_t img_bytes)
+                                                           size_t img_bytes, uint32_t first)
 {
-    const uint32_t p = blockIdx.y;
+    const uint32_t p = first + blockIdx.y;
     const uint8_t *a = refs + (size_t)pair_ref[p] * img_bytes;
     const uint8_t *b = tests + (size_t)p * img_bytes;
     unsigned long long sse = 0;
@@ -137,12 +137,16 @@ int ce_launch_psnr(ce_batch *b, const uint8_t *d_refs, uint32_t n_pairs)
     const uint32_t cap = std::max<uint32_t>(kBlocksPerPair, 4096u / n_pairs);
     if (blocks > cap) blocks = cap;
     if (blocks == 0) blocks = 1;
-    if (b->depth[0])
-        CE_LAUNCH(ctx, "psnr_sse_u16", k_psnr_sse_u16, dim3(blocks, n_pairs), dim3(kThreads), 0, d_refs, b->d_tests, b->d_pair_ref,
-                  b->d_scores, b->img_bytes);
-    else
-        CE_LAUNCH(ctx, "psnr_sse", k_psnr_sse, dim3(blocks, n_pairs), dim3(kThreads), 0, d_refs, b->d_tests, b->d_pair_ref,
-                  b->d_scores, b->img_bytes);
+    // pairs [first, first + count) a launch: a grid's y holds at most ce_grid_yz_max pairs
+    for (uint32_t first = 0; first < n_pairs; first += ce_grid_yz_max) {
+        const dim3 grid(blocks, std::min(n_pairs - first, ce_grid_yz_max));
+        if (b->depth[0])
+            CE_LAUNCH(ctx, "psnr_sse_u16", k_psnr_sse_u16, grid, dim3(kThreads), 0, d_refs, b->d_tests, b->d_pair_ref, b->d_scores,
+                      b->img_bytes, first);
+        else
+            CE_LAUNCH(ctx, "psnr_sse", k_psnr_sse, grid, dim3(kThreads), 0, d_refs, b->d_tests, b->d_pair_ref, b->d_scores, b->img_bytes,
+                      first);
+    }
     CE_HIP(ctx, hipGetLastError());
     return CE_OK;
 }

@@ -300,7 +300,28 @@ int ce_batch_run(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_t f
 /* same, without the final wait (for back-to-back timed steps and pipelines of several batches): the launch queues the
  * kernels and, behind them, the copy of the scores into the batch's page-locked buffer; ce_batch_collect waits for THAT
  * launch only (not for batches launched after it on the same context) and converts the first n_pairs scores
- * (n_pairs <= the launched count, CE_ERR_INVALID_ARG otherwise) */
+ * (n_pairs <= the launched count, CE_ERR_INVALID_ARG otherwise).
+ *
+ * What one launch takes.  ce_batch_create accepts any max_pairs, and the calls that are one kernel
+ * over (blocks, pairs) - CE_METRIC_PSNR here, ce_batch_ciede2000, ce_batch_hdr_fidelity, ce_batch_delta_e_itp_map, and
+ * ce_batch_msssim / ce_batch_msssim_map / ce_batch_plane_fidelity - score any n_pairs <= max_pairs: they CHUNK the pair
+ * range into kernel launches of at most CE_LAUNCH_GRID_MAX pairs.  CE_METRIC_DSSIM, CE_METRIC_SSIMULACRA2 and
+ * CE_METRIC_BUTTERAUGLI do not chunk; a launch that asks for any of them is REFUSED - CE_ERR_INVALID_ARG, the limit in
+ * ce_last_error, before any kernel runs and with the batch, its kept reference state and its earlier results as they were -
+ * when
+ *   - the references the pairs [0, n_pairs) name (the highest bound index + 1) plus n_pairs exceed CE_LAUNCH_MAX_SLOTS image
+ *     slots.  The count is the same whether or not the launch would find its references' state kept, so a launch is refused
+ *     or runs whatever ran before it;
+ *   - CE_METRIC_BUTTERAUGLI runs (an image of 8 x 8 or more) and height > CE_BUTTERAUGLI_MAX_HEIGHT;
+ *   - CE_METRIC_SSIMULACRA2 runs and height > CE_SSIMULACRA2_MAX_HEIGHT.
+ * A caller with more pairs launches them in parts (ce_batch_bind_pair and the test slab cost nothing to rearrange);
+ * ce_eval_batch plans its own chunks under the same limit and takes any n.  No grid limits the width (a grid's x holds
+ * 2^31 - 1 blocks); what SSIMULACRA2's work lists add (65535 blocks of 32 rows or 64 columns a launch) lies past 2 000 000 pixels a side
+ * and is refused with CE_ERR_INVALID_ARG from inside the metric. */
+#define CE_LAUNCH_GRID_MAX 65535u
+#define CE_LAUNCH_MAX_SLOTS 65535u
+#define CE_BUTTERAUGLI_MAX_HEIGHT 262140u
+#define CE_SSIMULACRA2_MAX_HEIGHT 524280u
 int ce_batch_launch(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_t flags,
                     float intensity_target);
 int ce_batch_collect(ce_batch *b, uint32_t n_pairs, ce_scores *out);

@@ -32,15 +32,18 @@ static T *exact(size_t n)
 }
 
 template <bool DEEP>
-static void run(const cie_args &a, uint32_t n_pairs, uint32_t blocks, unsigned long long *out)
+static void run(cie_args a, uint32_t n_pairs, uint32_t blocks, unsigned long long *out)
 {
     const size_t lds_floats = cie_lds_floats(a.depth[0], a.depth[1]);
     float *lds = exact<float>(lds_floats);
-    gridDim.x = blocks, gridDim.y = n_pairs;
+    // two launches, as the launcher cuts a batch at a grid's y: pairs [0, half) and [half, n_pairs), the second with first = half
+    const uint32_t half = n_pairs / 2;
+    gridDim.x = blocks;
     for (uint32_t p = 0; p < n_pairs; p++) {
         unsigned long long t[kCieOut] = {};
         for (uint32_t b = 0; b < blocks; b++) {
-            blockIdx.x = b, blockIdx.y = p;
+            a.first = p < half ? 0 : half, gridDim.y = p < half ? half : n_pairs - half;
+            blockIdx.x = b, blockIdx.y = p - a.first;
             memset(lds, 0xff, lds_floats * sizeof(float));  // NaN
             for (unsigned th = 0; th < kCieThreads; th++) {
                 threadIdx.x = th;

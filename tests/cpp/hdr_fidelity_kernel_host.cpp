@@ -31,15 +31,18 @@ static T *exact(size_t n)
 }
 
 template <int DEPTH>
-static void run(const hdrf_args &a, uint32_t n_pairs, uint32_t blocks, unsigned long long *out)
+static void run(hdrf_args a, uint32_t n_pairs, uint32_t blocks, unsigned long long *out)
 {
     const size_t lds_floats = hdrf_coarse_len(DEPTH);
     float *lds = exact<float>(lds_floats);
-    gridDim.x = blocks, gridDim.y = n_pairs;
+    // two launches, as the launcher cuts a batch at a grid's y: pairs [0, half) and [half, n_pairs), the second with first = half
+    const uint32_t half = n_pairs / 2;
+    gridDim.x = blocks;
     for (uint32_t p = 0; p < n_pairs; p++) {
         unsigned long long t[3] = {0, 0, 0};
         for (uint32_t b = 0; b < blocks; b++) {
-            blockIdx.x = b, blockIdx.y = p;
+            a.first = p < half ? 0 : half, gridDim.y = p < half ? half : n_pairs - half;
+            blockIdx.x = b, blockIdx.y = p - a.first;
             memset(lds, 0xff, lds_floats * sizeof(float));  // NaN: a threshold nothing is at or above
             for (unsigned th = 0; th < kHdrfThreads; th++) {
                 threadIdx.x = th;

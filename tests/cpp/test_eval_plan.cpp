@@ -23,9 +23,9 @@ static int g_fail = 0;
 static const size_t kNone = ce_plan_none;
 static const size_t kPerPair = 1000;
 
-static ce_plan_inputs inputs(size_t cap_pairs, size_t ramp, uint32_t pooled = 0, size_t forced = 0)
+static ce_plan_inputs inputs(size_t cap_pairs, size_t ramp, uint32_t pooled = 0, size_t forced = 0, size_t max_slots = (size_t)1 << 40)
 {
-    return ce_plan_inputs{cap_pairs * kPerPair, kPerPair, pooled, forced, ramp};
+    return ce_plan_inputs{cap_pairs * kPerPair, kPerPair, pooled, forced, ramp, max_slots};
 }
 
 // n_refs references with n_tests tests each; the items are listed test-major (item t * n_refs + r belongs to reference r),
@@ -48,6 +48,27 @@ static size_t pairs_of(const ce_plan_chunk &c)
     size_t k = 0;
     for (auto &g : c.refs) k += g.size();
     return k;
+}
+
+// what a launch counts: the chunk's references beside its pairs
+static size_t slots_of(const ce_plan_chunk &c) { return c.refs.size() + pairs_of(c); }
+
+// every item of the bucket in exactly one chunk, no chunk past max_slots, every part of a chunk non-empty
+static void check_cap(const std::vector<ce_plan_chunk> &plan, size_t n_items, size_t max_slots)
+{
+    std::vector<int> seen(n_items, 0);
+    for (const ce_plan_chunk &c : plan) {
+        CHECK(slots_of(c) <= max_slots);
+        CHECK(c.max_pairs >= pairs_of(c));
+        for (auto &g : c.refs) {
+            CHECK(!g.empty());
+            for (size_t i : g)
+                if (i < n_items) seen[i]++;
+        }
+    }
+    size_t once = 0;
+    for (int s : seen) once += s == 1;
+    CHECK(once == n_items);
 }
 
 static void check_chunks(const std::vector<ce_plan_chunk> &plan, size_t first, const std::vector<size_t> &counts,
@@ -264,6 +285,63 @@ int main()
         uint32_t ring = 0;
         ce_plan_bucket(b.items, b.refs, inputs(1u << 20, 64, 0, 2), ring, plan);
         check_chunks(plan, 0, {5, 5}, {0, 1}, {kNone, kNone}, 5);
+    }
+    {  // the launch cap: 3 references x 100 000 tests, no budget cap, a launch of 65535 slots.  By bytes alone: three chunks
+       // of 100 001 slots.  Target 65534 (one reference beside it), each reference split 65534 + 34466, no two parts share a chunk
+        bucket b(3, 100000);
+        std::vector<ce_plan_chunk> plan;
+        uint32_t ring = 0;
+        ce_plan_bucket(b.items, b.refs, inputs((size_t)1 << 30, 0), ring, plan);
+        check_chunks(plan, 0, {100000, 100000, 100000}, {0, 1, 2}, {kNone, kNone, kNone}, 100000);
+        plan.clear();
+        ring = 0;
+        ce_plan_bucket(b.items, b.refs, inputs((size_t)1 << 30, 0, 0, 0, ce_launch_slots_max), ring, plan);
+        check_chunks(plan, 0, {65534, 34466, 65534, 34466, 65534, 34466}, {0, 1, 2, 0, 1, 2}, {kNone, kNone, kNone, 0, 1, 2}, 65534);
+        check_cap(plan, b.items.size(), ce_launch_slots_max);
+        CHECK(slots_of(plan[0]) == ce_launch_slots_max);
+        // ... which is what inputs that name no limit plan under
+        plan.clear();
+        ring = 0;
+        ce_plan_bucket(b.items, b.refs, ce_plan_inputs{((size_t)1 << 30) * kPerPair, kPerPair, 0, 0, 0}, ring, plan);
+        check_cap(plan, b.items.size(), ce_launch_slots_max);
+        CHECK(plan.size() == 6);
+        // ... and with the ramp: a chunk's first part is taken whole, so the same chunks
+        plan.clear();
+        ring = 0;
+        ce_plan_bucket(b.items, b.refs, inputs((size_t)1 << 30, 64, 0, 0, ce_launch_slots_max), ring, plan);
+        check_chunks(plan, 0, {65534, 34466, 65534, 34466, 65534, 34466}, {0, 1, 2, 0, 1, 2}, {kNone, kNone, kNone, 0, 1, 2}, 65534);
+    }
+    {  // every pair with a reference of its own counts two slots: 10 such pairs, a launch of 7 slots -> target 6, but three
+       // references and their three pairs fill a chunk (a fourth pair would make 8 slots)
+        bucket b(10, 1);
+        std::vector<ce_plan_chunk> plan;
+        uint32_t ring = 0;
+        ce_plan_bucket(b.items, b.refs, inputs(1u << 20, 0, 0, 0, 7), ring, plan);
+        check_chunks(plan, 0, {3, 3, 3, 1}, {0, 1, 2, 0}, {kNone, kNone, kNone, 0}, 6);
+        check_cap(plan, 10, 7);
+        // one reference with 20 tests, a launch of 5 slots: five chunks of the reference and 4 tests
+        bucket one(1, 20);
+        plan.clear();
+        ring = 0;
+        ce_plan_bucket(one.items, one.refs, inputs(1u << 20, 64, 0, 0, 5), ring, plan);
+        check_chunks(plan, 0, {4, 4, 4, 4, 4}, {0, 1, 2, 0, 1}, {kNone, kNone, kNone, 0, 1}, 4);
+        check_cap(plan, 20, 5);
+        // a budget below the launch cap still rules: cap 8 pairs, a launch of 100 slots
+        plan.clear();
+        ring = 0;
+        ce_plan_bucket(one.items, one.refs, inputs(8, 64, 0, 0, 100), ring, plan);
+        check_chunks(plan, 0, {8, 8, 4}, {0, 1, 2}, {kNone, kNone, kNone}, 8);
+    }
+    {  // a sweep: references with 1 .. 9 tests, launches of 2 .. 40 slots, with and without the ramp
+        for (size_t max_slots = 2; max_slots <= 40; max_slots += 3)
+            for (size_t n_tests = 1; n_tests <= 9; n_tests += 4)
+                for (size_t ramp : {(size_t)0, (size_t)4}) {
+                    bucket b(17, n_tests);
+                    std::vector<ce_plan_chunk> plan;
+                    uint32_t ring = 0;
+                    ce_plan_bucket(b.items, b.refs, inputs(1u << 20, ramp, 0, 0, max_slots), ring, plan);
+                    check_cap(plan, b.items.size(), max_slots);
+                }
     }
     if (g_fail) std::printf("%d check(s) failed\n", g_fail);
     else std::printf("eval plan: all checks passed\n");
