@@ -256,6 +256,20 @@ pub struct ce_plane_scores {
     pub n_planes: u32,
 }
 
+/// `ce_plane_hvs_scores` (176 bytes): PSNR-HVS and PSNR-HVS-M of one pair of Y'CbCr images plane by plane: the exact sums as
+/// [low 32 bits, the rest], the DCT blocks of a plane and the two scores.  A plane without a block has 0 and NaN.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct ce_plane_hvs_scores {
+    pub hvs_q: [[u64; 2]; 3],
+    pub hvsm_q: [[u64; 2]; 3],
+    pub n_blocks: [u64; 3],
+    pub psnr_hvs: [c_double; 3],
+    pub psnr_hvsm: [c_double; 3],
+    pub n_planes: u32,
+    pub step: u32,
+}
+
 /// `ce_scores` (40 bytes): a score is meaningful iff its bit is set in `valid`.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -581,6 +595,8 @@ extern "C" {
     pub fn ce_msssim_levels(w: u32, h: u32, levels: u32, n_levels: *mut u32, level_w: *mut u32, level_h: *mut u32) -> c_int;
     pub fn ce_yuv_plane_fidelity(ctx: *mut ce_ctx, width: u32, height: u32, refs: *const ce_yuv_image, n_refs: u32, tests: *const ce_yuv_image,
                                  n_pairs: u32, pair_ref: *const u32, levels: u32, out: *mut ce_plane_scores) -> c_int;
+    pub fn ce_yuv_plane_hvs(ctx: *mut ce_ctx, width: u32, height: u32, refs: *const ce_yuv_image, n_refs: u32, tests: *const ce_yuv_image,
+                            n_pairs: u32, pair_ref: *const u32, step: u32, out: *mut ce_plane_hvs_scores) -> c_int;
     pub fn ce_batch_delta_e_itp_map(b: *mut ce_batch, first: u32, count: u32, depth: u32, white_nits: c_float, block: u32, map: *mut u32,
                                     map_len: usize, thresholds_q20: *const u32, n_thresholds: u32, over: *mut u64) -> c_int;
     pub fn ce_eval_pair_delta_e_itp_map(ctx: *mut ce_ctx, reference: *const c_float, reference_len: usize, test: *const c_float,

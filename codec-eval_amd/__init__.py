@@ -206,6 +206,11 @@ class CePlaneScores(C.Structure):
                 ("cs_q", (C.c_int64 * 5) * 3), ("n_pos", (C.c_uint64 * 5) * 3), ("n_levels", C.c_uint32 * 3), ("n_planes", C.c_uint32)]
 
 
+class CePlaneHvsScores(C.Structure):
+    _fields_ = [("hvs_q", (C.c_uint64 * 2) * 3), ("hvsm_q", (C.c_uint64 * 2) * 3), ("n_blocks", C.c_uint64 * 3),
+                ("psnr_hvs", C.c_double * 3), ("psnr_hvsm", C.c_double * 3), ("n_planes", C.c_uint32), ("step", C.c_uint32)]
+
+
 class CodecEvalError(RuntimeError):
     """Mirrors codec_eval::Error for this path (src/error.rs:31-49)."""
 
@@ -362,6 +367,8 @@ _PROTOTYPES = [
     ("ce_eval_pair_msssim_deep", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, C.POINTER(CeMsssimScores)]),
     ("ce_yuv_plane_fidelity", _i, [_vp, _u32, _u32, C.POINTER(CeYuvImage), _u32, C.POINTER(CeYuvImage), _u32, _vp, _u32,
                                C.POINTER(CePlaneScores)]),
+    ("ce_yuv_plane_hvs", _i, [_vp, _u32, _u32, C.POINTER(CeYuvImage), _u32, C.POINTER(CeYuvImage), _u32, _vp, _u32,
+                          C.POINTER(CePlaneHvsScores)]),
     ("ce_batch_msssim_map", _i, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
     ("ce_eval_pair_msssim_map", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
     ("ce_eval_pair_msssim_map_deep", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
@@ -932,6 +939,35 @@ class PlaneScores:
         return PlaneScores(tuple(int(v) for v in s.sse), tuple(int(v) for v in s.n), tuple(s.psnr), s.psnr_weighted, s.psnr_overall,
                            tuple(s.ssim), tuple(s.ms_ssim), grid(s.ssim_q), grid(s.cs_q), grid(s.n_pos),
                            tuple(int(v) for v in s.n_levels), int(s.n_planes))
+
+
+@dataclass(frozen=True)
+class PlaneHvsScores:
+    """PSNR-HVS and PSNR-HVS-M of one pair of Y'CbCr images plane by plane (ce_plane_hvs_scores): index p = 0, 1, 2 is Y, Cb,
+    Cr.  hvs_sum[p] and hvsm_sum[p] are the exact sums of the quantised, CSF-weighted squared DCT differences without and with
+    the contrast mask (hvs_q[p] and hvsm_q[p] are the same as [low 32 bits, the rest]), n_blocks[p] the plane's 8 x 8 blocks at
+    the call's step, psnr_hvs and psnr_hvsm the scores.  A plane without a block has 0 and NaN."""
+    hvs_q: Tuple[Tuple[int, int], ...]
+    hvsm_q: Tuple[Tuple[int, int], ...]
+    n_blocks: Tuple[int, int, int]
+    psnr_hvs: Tuple[float, float, float]
+    psnr_hvsm: Tuple[float, float, float]
+    n_planes: int
+    step: int
+
+    @property
+    def hvs_sum(self) -> Tuple[int, ...]:
+        return tuple(q[0] + (q[1] << 32) for q in self.hvs_q)
+
+    @property
+    def hvsm_sum(self) -> Tuple[int, ...]:
+        return tuple(q[0] + (q[1] << 32) for q in self.hvsm_q)
+
+    @staticmethod
+    def from_c(s: CePlaneHvsScores) -> "PlaneHvsScores":
+        pairs = lambda a: tuple((int(a[p][0]), int(a[p][1])) for p in range(3))  # noqa: E731
+        return PlaneHvsScores(pairs(s.hvs_q), pairs(s.hvsm_q), tuple(int(v) for v in s.n_blocks), tuple(s.psnr_hvs), tuple(s.psnr_hvsm),
+                              int(s.n_planes), int(s.step))
 
 
 DELTA_E_ITP_Q20 = 1 << 20  # a Delta E ITP of 1.0 in the units of the maps and thresholds (CE_DELTA_E_ITP_Q20)
@@ -1866,6 +1902,24 @@ class Context:
         self._check(lib().ce_yuv_plane_fidelity(self._h, width, height, cr, len(refs), ct, len(tests),
                                                 table.ctypes.data if table is not None else None, levels, out))
         return [PlaneScores.from_c(out[i]) for i in range(len(tests))]
+
+    def plane_hvs(self, refs: Sequence["YuvImage"], tests: Sequence["YuvImage"], width: int, height: int,
+                  pair_ref: Optional[Sequence[int]] = None, step: int = 8) -> List[PlaneHvsScores]:
+        """PSNR-HVS and PSNR-HVS-M of Y'CbCr images plane by plane (ce_yuv_plane_hvs), with plane_fidelity's images, pair table
+        and semantics.  step: samples from an 8 x 8 DCT block to the next, 1 to 8 (8: the blocks do not overlap)."""
+        cr, ct = (CeYuvImage * max(len(refs), 1))(), (CeYuvImage * max(len(tests), 1))()
+        keep = []
+        for arr, imgs in ((cr, refs), (ct, tests)):
+            for i, img in enumerate(imgs):
+                arr[i], k = img._c()
+                keep.append(k)
+        table = None if pair_ref is None else np.ascontiguousarray(pair_ref, dtype=np.uint32).reshape(-1)
+        if table is not None and table.size != len(tests):
+            raise CodecEvalError(CE_ERR_INVALID_ARG, f"pair_ref names {table.size} pairs for {len(tests)} tests")
+        out = (CePlaneHvsScores * max(len(tests), 1))()
+        self._check(lib().ce_yuv_plane_hvs(self._h, width, height, cr, len(refs), ct, len(tests),
+                                           table.ctypes.data if table is not None else None, step, out))
+        return [PlaneHvsScores.from_c(out[i]) for i in range(len(tests))]
 
     def delta_e_itp_map(self, reference, test, width: int, height: int, depth: int = 10, white_nits: float = 203.0, block: int = 1,
                         thresholds_q20=None, maps: bool = True):

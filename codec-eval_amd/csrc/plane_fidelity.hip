@@ -6,7 +6,7 @@
 // where they lie, through the plane table, the others the context's planar f32 pyramid.  k_plane_pool writes the next level of
 // a run of images.  Integer sums do not depend on the order, so the scores do not depend on the grid.  The device code is
 // plane_fidelity_kernel.h's, which a test also compiles for the host; here are the kernels' entry points, the reductions, the
-// launches and the call itself.
+// launches and the call itself.  The checks of the images and their upload are plane_images.h's, shared with plane_hvs.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -15,6 +15,8 @@
 #include "ce_internal.h"
 
 #include "plane_fidelity_kernel.h"
+
+#include "plane_images.h"
 
 namespace {
 
@@ -158,8 +160,6 @@ int launch(ce_ctx *ctx, const pf_job &j)
     return CE_OK;
 }
 
-size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
-
 double psnr_of(uint64_t sse, uint64_t n, double maxv)
 {
     // ce_api.cpp: psnr_from_sse, on a plane's own count
@@ -175,44 +175,21 @@ int ce_yuv_plane_fidelity(ce_ctx *ctx, uint32_t width, uint32_t height, const ce
 {
     if (!ctx) return CE_ERR_INVALID_ARG;
     const auto bad = [ctx](const std::string &why) { return ce_fail(ctx, CE_ERR_INVALID_ARG, "plane fidelity: " + why); };
-    if (!refs || !tests || !out) return bad("null pointer");
-    if (n_refs == 0 || n_pairs == 0) return bad("no references or no pairs");
-    if (!pair_ref && n_refs != n_pairs)
-        return bad("without a pair table pair i scores against reference i: " + std::to_string(n_refs) + " references for " + std::to_string(n_pairs) + " pairs");
-    for (uint32_t i = 0; pair_ref && i < n_pairs; i++)
-        if (pair_ref[i] >= n_refs)
-            return bad("pair " + std::to_string(i) + " names reference " + std::to_string(pair_ref[i]) + " of " + std::to_string(n_refs));
+    if (int rc = pf_check_pairs(ctx, "plane fidelity", refs, n_refs, tests, n_pairs, pair_ref, out)) return rc;
     if (levels != 0 && levels != 1 && levels != CE_MSSSIM_LEVELS) return bad("levels must be 0 (PSNR), 1 (+ SSIM) or 5 (+ MS-SSIM), got " + std::to_string(levels));
-    if (width == 0 || height == 0) return bad("empty image");
-    // the images: the ingest's checks, one subsampling and one depth a call, one matrix and one range a pair
+    pf_images im;
+    if (int rc = pf_check_images(ctx, "plane fidelity", width, height, refs, n_refs, tests, n_pairs, pair_ref, &im)) return rc;
     const size_t n_img = (size_t)n_refs + n_pairs;
-    const auto image = [&](size_t i) -> const ce_yuv_image & { return i < n_refs ? refs[i] : tests[i - n_refs]; };
-    std::vector<ce_yuv_planes> plans(n_img);
-    for (size_t i = 0; i < n_img; i++) {
-        if (int rc = ce_yuv_planes_check(ctx, &image(i), width, height, &plans[i])) return rc;
-        if (image(i).subsampling != refs[0].subsampling || image(i).depth != refs[0].depth)
-            return bad(std::string(i < n_refs ? "reference " : "test ") + std::to_string(i < n_refs ? i : i - n_refs) +
-                       " differs from reference 0 in subsampling or depth: every image of a call has one of each");
-    }
-    std::vector<uint32_t> ref_of(n_pairs);
-    for (uint32_t i = 0; i < n_pairs; i++) {
-        ref_of[i] = pair_ref ? pair_ref[i] : i;
-        if (tests[i].matrix != refs[ref_of[i]].matrix || tests[i].range != refs[ref_of[i]].range)
-            return bad("pair " + std::to_string(i) + ": the two sides differ in matrix or range, their code values do not mean the same");
-    }
     pf_job j;
-    j.n_refs = n_refs, j.n_pairs = n_pairs, j.h_pair_ref = ref_of.data();
-    const int sub = refs[0].subsampling;
-    j.n_planes = sub == CE_YUV_400 ? 1 : 3;
-    j.bps = refs[0].depth == 8 ? 1 : 2, j.maxv = (1u << refs[0].depth) - 1u;
-    const uint32_t cw = sub == CE_YUV_444 ? width : (uint32_t)(((size_t)width + 1) / 2), ch = sub == CE_YUV_420 ? (uint32_t)(((size_t)height + 1) / 2) : height;
+    j.n_refs = n_refs, j.n_pairs = n_pairs, j.h_pair_ref = im.ref_of.data();
+    j.n_planes = im.n_planes, j.bps = im.bps, j.maxv = im.maxv;
     if (levels) {  // luma must admit them
         uint32_t n = 0;
         if (int rc = ce_msssim_levels(width, height, levels, &n, j.lw[0], j.lh[0])) return ce_fail(ctx, rc, std::string("plane fidelity, luma: ") + ce_last_error(nullptr));
     }
     size_t pyr = 0;
     for (uint32_t p = 0; p < j.n_planes; p++) {
-        const uint32_t pw = p ? cw : width, ph = p ? ch : height, m = std::min(pw, ph);
+        const uint32_t pw = im.pw[p], ph = im.ph[p], m = std::min(pw, ph);
         j.n_levels[p] = levels == CE_MSSSIM_LEVELS && m > 160 ? CE_MSSSIM_LEVELS : levels >= 1 && m >= 11 ? 1 : 0;
         uint32_t w = pw, h = ph;
         for (uint32_t l = 0; l < std::max(j.n_levels[p], 1u); l++) {
@@ -221,52 +198,13 @@ int ce_yuv_plane_fidelity(ce_ctx *ctx, uint32_t width, uint32_t height, const ce
             w = (w + (w & 1u)) / 2, h = (h + (h & 1u)) / 2;
         }
     }
-    // scratch: host planes without their pitch padding (rows 16 bytes apart at least, so that the wide path reads them), the
-    // tables, the pyramid, the results
-    size_t stage = 0;
-    for (size_t i = 0; i < n_img; i++)
-        if (image(i).memory == CE_MEM_HOST)
-            for (int s = 0; s < plans[i].n_stored; s++) stage += round_up(round_up(plans[i].row_bytes[s], 16) * plans[i].rows[s], 256);
-    const size_t tab_bytes = round_up(n_img * 3 * sizeof(pf_plane), 16), tables = tab_bytes + sizeof(uint32_t) * n_pairs;
+    // scratch: the pyramid and the results here; the planes and the tables in pf_upload (plane_images.h)
     CE_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = ctx->pf_planes_h.reserve(ctx, stage)) return rc;
-    if (int rc = ctx->pf_planes_d.reserve(ctx, stage)) return rc;
-    if (int rc = ctx->pf_tables_h.reserve(ctx, tables)) return rc;
-    if (int rc = ctx->pf_tables_d.reserve(ctx, tables)) return rc;
     if (int rc = ctx->pf_pyr.reserve(ctx, pyr)) return rc;
     if (int rc = ctx->pf_out_h.reserve(ctx, (size_t)kPfOut * n_pairs)) return rc;
     if (int rc = ctx->pf_out_d.reserve(ctx, (size_t)kPfOut * n_pairs)) return rc;
-    // the plane table: device planes where they lie, host planes where their copy will be
-    pf_plane *tab = reinterpret_cast<pf_plane *>(ctx->pf_tables_h.get());
-    size_t at = 0;
-    for (size_t i = 0; i < n_img; i++) {
-        const ce_yuv_image &img = image(i);
-        const uint8_t *base[3] = {};
-        size_t pitch[3] = {};
-        for (int s = 0; s < plans[i].n_stored; s++) {
-            base[s] = static_cast<const uint8_t *>(img.plane[s]), pitch[s] = img.pitch[s];
-            if (img.memory != CE_MEM_HOST) continue;
-            const size_t row = plans[i].row_bytes[s], to = round_up(row, 16);
-            uint8_t *dst = ctx->pf_planes_h.get() + at;
-            for (size_t r = 0; r < plans[i].rows[s]; r++) std::memcpy(dst + r * to, base[s] + r * pitch[s], row);
-            base[s] = ctx->pf_planes_d.get() + at, pitch[s] = to;
-            at += round_up(to * plans[i].rows[s], 256);
-        }
-        const bool semi = img.layout == CE_YUV_SEMIPLANAR;
-        for (uint32_t p = 0; p < 3; p++) {
-            pf_plane e{};
-            if (p < j.n_planes) {
-                const int s = semi && p == 2 ? 1 : (int)p;
-                e.base = base[s] + (semi && p == 2 ? j.bps : 0), e.pitch = pitch[s], e.step = semi && p ? 2 : 1, e.shift = plans[i].shift;
-            }
-            tab[i * 3 + p] = e;
-        }
-    }
-    std::memcpy(ctx->pf_tables_h.get() + tab_bytes, ref_of.data(), sizeof(uint32_t) * n_pairs);
-    if (stage) CE_HIP(ctx, hipMemcpyAsync(ctx->pf_planes_d.get(), ctx->pf_planes_h.get(), stage, hipMemcpyHostToDevice, ctx->stream));
-    CE_HIP(ctx, hipMemcpyAsync(ctx->pf_tables_d.get(), ctx->pf_tables_h.get(), tables, hipMemcpyHostToDevice, ctx->stream));
-    j.d_tab = reinterpret_cast<const pf_plane *>(ctx->pf_tables_d.get());
-    j.d_pair_ref = reinterpret_cast<const uint32_t *>(ctx->pf_tables_d.get() + tab_bytes);
+    if (int rc = pf_upload(ctx, im, refs, tests)) return rc;
+    j.d_tab = im.d_tab, j.d_pair_ref = im.d_pair_ref;
     j.d_pyr = ctx->pf_pyr, j.d_out = ctx->pf_out_d;
     if (int rc = launch(ctx, j)) return rc;
     CE_HIP(ctx, hipMemcpyAsync(ctx->pf_out_h.get(), ctx->pf_out_d.get(), sizeof(unsigned long long) * kPfOut * n_pairs, hipMemcpyDeviceToHost, ctx->stream));

@@ -942,6 +942,19 @@ inline std::vector<PlaneScores> plane_fidelity(const HipBackend &be, const std::
                   "plane_fidelity", width, height, 0);
     return out;
 }
+// ---- PSNR-HVS and PSNR-HVS-M of the same planes (include/ce_metrics.h: ce_yuv_plane_hvs) ----
+// per plane the two exact sums, the block count and the two scores; step: samples from a DCT block to the next, 1 .. 8
+using PlaneHvsScores = ce_plane_hvs_scores;
+inline std::vector<PlaneHvsScores> plane_hvs(const HipBackend &be, const std::vector<ce_yuv_image> &refs, const std::vector<ce_yuv_image> &tests,
+                                             uint32_t width, uint32_t height, const std::vector<uint32_t> &pair_ref = {}, uint32_t step = 8)
+{
+    std::vector<PlaneHvsScores> out(tests.size());
+    if (!pair_ref.empty() && pair_ref.size() != tests.size()) detail::check(be, CE_ERR_INVALID_ARG, "plane_hvs", width, height, 0);
+    detail::check(be, ce_yuv_plane_hvs(be.ctx(), width, height, refs.data(), (uint32_t)refs.size(), tests.data(), (uint32_t)tests.size(),
+                                       pair_ref.empty() ? nullptr : pair_ref.data(), step, out.data()),
+                  "plane_hvs", width, height, 0);
+    return out;
+}
 // straight into a slot of a resident batch (RGB8 or deep), host or device planes
 inline void batch_set_reference_yuv(const HipBackend &be, ce_batch *batch, uint32_t ref_index, const YuvImage &image)
 {

@@ -302,7 +302,7 @@ int ce_batch_run(ce_batch *b, uint32_t n_pairs, uint32_t metric_mask, uint32_t f
  * launch only (not for batches launched after it on the same context) and converts the first n_pairs scores
  * (n_pairs <= the launched count, CE_ERR_INVALID_ARG otherwise).
  *
- * What one launch takes (DESIGN.md section 31).  ce_batch_create accepts any max_pairs, and the calls that are one kernel
+ * What one launch takes (DESIGN.md section 32).  ce_batch_create accepts any max_pairs, and the calls that are one kernel
  * over (blocks, pairs) - CE_METRIC_PSNR here, ce_batch_ciede2000, ce_batch_hdr_fidelity, ce_batch_delta_e_itp_map, and
  * ce_batch_msssim / ce_batch_msssim_map / ce_batch_plane_fidelity - score any n_pairs <= max_pairs: they CHUNK the pair
  * range into kernel launches of at most CE_LAUNCH_GRID_MAX pairs.  CE_METRIC_DSSIM, CE_METRIC_SSIMULACRA2 and
@@ -1299,6 +1299,61 @@ typedef struct ce_plane_scores {
 int ce_yuv_plane_fidelity(ce_ctx *ctx, uint32_t width, uint32_t height, const ce_yuv_image *refs, uint32_t n_refs,
                           const ce_yuv_image *tests, uint32_t n_pairs, const uint32_t *pair_ref, uint32_t levels,
                           ce_plane_scores *out);
+
+/* ---- PSNR-HVS and PSNR-HVS-M of a decoder's Y'CbCr planes -------------------------------------------------
+ * The DCT-domain, CSF-weighted PSNR of Egiazarian et al. (PSNR-HVS) and its contrast-masked form of Ponomarenko et al.
+ * (PSNR-HVS-M), per plane, on the planes as the decoder wrote them: the fifth figure codec dashboards tabulate beside PSNR, SSIM,
+ * MS-SSIM (above) and CIEDE2000.  This text and its numpy restatement, tests/plane_hvs_restatement.py, are the contract - not
+ * the output of any tool: the device equals the restatement on every integer.  Every f64 operation named below is one
+ * separately rounded IEEE operation (no contraction, no libm on the device); sqrt and division are correctly rounded.
+ * Inputs.  The images, planes p = 0, 1, 2, plane sizes and samples min(v >> shift, L), L = 2^d - 1, d in {8, 10, 12}, of
+ *   ce_yuv_plane_fidelity above, unchanged.  One `step` in [1, 8] a call: 8 is Ponomarenko's non-overlapping blocks, 7 the
+ *   stride of Daala's and libaom's tools.  The blocks of a pw x ph plane are the 8 x 8 windows at (x, y) = (i step, j step) with
+ *   x + 8 <= pw and y + 8 <= ph: n_blocks[p] = ((pw - 8) / step + 1) * ((ph - 8) / step + 1), or 0 if pw < 8 or ph < 8.  Luma
+ *   must have a block.  A chroma plane with none has integers 0 and doubles NaN.  The same luma tables serve all three planes:
+ *   that is this library's choice - Daala's per-plane chroma CSF tables and its mask normalisation are not part of it, so step 7
+ *   is not claimed to reproduce Daala's or libaom's figures.
+ * Tables.  Q[8][8] = JPEG (ITU-T T.81) Annex K's luminance table K.1 in natural order (16 11 10 16 24 40 51 61 / 12 12 14 19 26
+ *   58 60 55 / 14 13 16 24 40 57 69 56 / 14 17 22 29 51 87 80 62 / 18 22 37 56 68 109 103 77 / 24 35 55 64 81 104 113 92 / 49 64
+ *   78 87 103 121 120 101 / 72 92 95 98 112 100 103 99).  csf[k][l] = 25.73509 / (double) Q[k][l]; mc[k][l] = 100.0 / (double)
+ *   (Q[k][l] * Q[k][l]): the published CSFCof and MaskCof to their printed decimals.
+ * DCT.  Orthonormal 8-point DCT-II in the direct form.  g[0] = sqrt(1 / 8) and g[m] = cos(m pi / 16) / 2, m = 1 .. 7, each the
+ *   nearest f64 (plane_hvs_kernel.h has them as hex-float literals).  T[0][j] = g[0]; T[k][j] = +-g[m] with a = (2j + 1) k mod
+ *   32, a > 16 -> 32 - a, then a > 8 -> sign -, m = 16 - a, else m = a.  out[k] = ((((((T[k][0] x0 + T[k][1] x1) + T[k][2] x2) +
+ *   ...) + T[k][7] x7: products separately rounded, sums left to right.  Along the rows of the block first, then down the columns:
+ *   D[k][l], k the vertical frequency.
+ * Per block and side, z its 64 samples and D its DCT.  m = sum over (k, l) != (0, 0) of (D[k][l] * D[k][l]) * mc[k][l]: per
+ *   column l from k = 0 down without the DC term, the eight column sums as ((c0 + c1) + (c2 + c3)) + ((c4 + c5) + (c6 + c7)).
+ *   I(z) = N sum z^2 - (sum z)^2 as an exact integer, N the sample count.  pop = 0 if I(block) == 0, else (63.0 * (double)
+ *   (I(q00) + I(q01) + I(q10) + I(q11))) / (15.0 * (double) I(block)) over the four 4 x 4 quadrants.  mask = sqrt(m * pop) / 32.0.
+ * Per block.  M = max(maskA, maskB).  Per coefficient u = |DA - DB|, t = M / mc[k][l]; um = u at DC, elsewhere 0 if u < t, else
+ *   u - t.  q_hvs = rint(((u * csf[k][l]) * (u * csf[k][l])) * 2^(36 - 2d)), q_hvsm the same of um: the unit is 2^-20 of a
+ *   squared 8-bit code at every depth.
+ * Per pair and plane.  The exact sums of q_hvs and q_hvsm over all coefficients of all blocks, each as two integers: sum =
+ *   x_q[p][0] + x_q[p][1] * 2^32, x_q[p][0] < 2^32.  S = (((double) x_q[p][1] * 4294967296.0 + (double) x_q[p][0]) / 2^(36 - 2d))
+ *   / (64.0 * n_blocks[p]); the score is +INFINITY if the sum is 0 (the MATLAB tool prints 100000 there), else 10.0 * log10(L *
+ *   L / S) with L * L formed in f64.
+ * Not part of this: per-block maps, a plane batch kind, ce_ref_* handles and ce_eval_batch, a factorised DCT (another summation
+ *   order would be another contract), chroma CSF tables, RGB batches. */
+typedef struct ce_plane_hvs_scores {
+    uint64_t hvs_q[3][2];   /* [plane][low 32 bits of the sum, the rest] */
+    uint64_t hvsm_q[3][2];
+    uint64_t n_blocks[3];
+    double psnr_hvs[3];
+    double psnr_hvsm[3];
+    uint32_t n_planes;
+    uint32_t step;
+} ce_plane_hvs_scores;      /* 176 bytes */
+/* Scores n_pairs tests, tests[i] against refs[pair_ref[i]] - or against refs[i] with pair_ref NULL, which needs n_refs ==
+ * n_pairs - into out[0 .. n_pairs), with ce_yuv_plane_fidelity's semantics: on the context's stream, blocking until the scores
+ * are on the host; no batch is touched and a batch launch that is still to be collected is unaffected; CE_MEM_HOST planes go
+ * through the same page-locked staging and grow-only scratch and are consumed on return; CE_MEM_DEVICE planes are read in
+ * place.  One launch covers every plane of up to 21845 pairs.
+ * CE_ERR_INVALID_ARG, with the reason in ce_last_error and the context still usable: everything ce_yuv_plane_fidelity refuses
+ * of the pointers, the counts, the pair table and the images; step outside [1, 8]; a luma plane under 8 x 8. */
+int ce_yuv_plane_hvs(ce_ctx *ctx, uint32_t width, uint32_t height, const ce_yuv_image *refs, uint32_t n_refs,
+                     const ce_yuv_image *tests, uint32_t n_pairs, const uint32_t *pair_ref, uint32_t step,
+                     ce_plane_hvs_scores *out);
 
 /* ---- matrix/TRC ICC profiles applied on the device ------------------------------------------------
  * transform_to_srgb (src/metrics/icc.rs:69-103) for the profiles photographs carry - three colorant tags and three tone
