@@ -834,6 +834,24 @@ impl HipMetrics {
         Ok(out)
     }
 
+    /// `ce_yuv_plane_vif`: pixel-domain VIF (VIFp) of host Y'CbCr images plane by plane, with `plane_fidelity`'s images and pair
+    /// table; a plane needs 41 x 41 samples to run and luma must.  Device surfaces go through `sys::ce_yuv_plane_vif` directly.
+    pub fn plane_vif(&mut self, refs: &[YuvPlanes<'_>], tests: &[YuvPlanes<'_>], width: u32, height: u32,
+                     pair_ref: Option<&[u32]>) -> Result<Vec<sys::ce_plane_vif_scores>, HipError> {
+        if pair_ref.is_some_and(|t| t.len() != tests.len()) {
+            return Err(HipError::MetricCalculation { metric: "hip".into(), reason: "the pair table names another number of pairs than there are tests".into() });
+        }
+        let r = refs.iter().map(|p| p.to_sys(width, height)).collect::<Result<Vec<_>, _>>()?;
+        let t = tests.iter().map(|p| p.to_sys(width, height)).collect::<Result<Vec<_>, _>>()?;
+        let mut out = vec![sys::ce_plane_vif_scores::default(); tests.len()];
+        let rc = unsafe {
+            sys::ce_yuv_plane_vif(self.ctx, width, height, r.as_ptr(), r.len() as u32, t.as_ptr(), t.len() as u32,
+                                  pair_ref.map_or(ptr::null(), |p| p.as_ptr()), out.as_mut_ptr())
+        };
+        self.check(rc, width, height, 0)?;
+        Ok(out)
+    }
+
     /// `ce_eval_pair_delta_e_itp_map`: where one pair of packed f32 RGB differs - see `HipBatch::delta_e_itp_map`.
     pub fn delta_e_itp_map(&mut self, reference: &[f32], test: &[f32], width: u32, height: u32, depth: u32, white_nits: f32, block: u32,
                            want_map: bool, thresholds_q20: &[u32]) -> Result<DeltaEItpMaps, HipError> {
@@ -917,6 +935,16 @@ pub fn pq_code_thresholds(depth: u32, white_nits: f32) -> Option<Vec<f32>> {
     let mut out = vec![0f32; (1usize << depth) - 1];
     let rc = unsafe { sys::ce_pq_code_thresholds(depth, white_nits, out.as_mut_ptr(), out.len()) };
     (rc == sys::CE_OK).then_some(out)
+}
+
+/// `ce_vif_window`: the 17, 9, 5 or 3 literals of the window of VIFp's scale 1 .. 4 (empty for another scale); a pure host
+/// function.
+pub fn vif_window(scale: u32) -> Vec<f64> {
+    let mut g = [0.0f64; 17];
+    if unsafe { sys::ce_vif_window(scale, g.as_mut_ptr()) } != sys::CE_OK {
+        return Vec::new();
+    }
+    g[..[17, 9, 5, 3][scale as usize - 1]].to_vec()
 }
 
 /// `ce_msssim_window`: the eleven literals of the SSIM / MS-SSIM window; a pure host function.

@@ -270,6 +270,21 @@ pub struct ce_plane_hvs_scores {
     pub step: u32,
 }
 
+/// `ce_plane_vif_scores` (424 bytes): pixel-domain VIF of one pair of Y'CbCr images plane by plane: per plane and scale the exact
+/// sums of the test's and the reference's information in units of 2^-24 nat, the positions and their ratio; `vifp` over the four
+/// scales.  A plane that did not run (`ran[p] == 0`) has 0 and NaN.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct ce_plane_vif_scores {
+    pub num_q: [[u64; 4]; 3],
+    pub den_q: [[u64; 4]; 3],
+    pub n_pos: [[u64; 4]; 3],
+    pub vif_scale: [[c_double; 4]; 3],
+    pub vifp: [c_double; 3],
+    pub ran: [u32; 3],
+    pub n_planes: u32,
+}
+
 /// `ce_scores` (40 bytes): a score is meaningful iff its bit is set in `valid`.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -597,6 +612,9 @@ extern "C" {
                                  n_pairs: u32, pair_ref: *const u32, levels: u32, out: *mut ce_plane_scores) -> c_int;
     pub fn ce_yuv_plane_hvs(ctx: *mut ce_ctx, width: u32, height: u32, refs: *const ce_yuv_image, n_refs: u32, tests: *const ce_yuv_image,
                             n_pairs: u32, pair_ref: *const u32, step: u32, out: *mut ce_plane_hvs_scores) -> c_int;
+    pub fn ce_yuv_plane_vif(ctx: *mut ce_ctx, width: u32, height: u32, refs: *const ce_yuv_image, n_refs: u32, tests: *const ce_yuv_image,
+                            n_pairs: u32, pair_ref: *const u32, out: *mut ce_plane_vif_scores) -> c_int;
+    pub fn ce_vif_window(scale: u32, out: *mut c_double) -> c_int;
     pub fn ce_batch_delta_e_itp_map(b: *mut ce_batch, first: u32, count: u32, depth: u32, white_nits: c_float, block: u32, map: *mut u32,
                                     map_len: usize, thresholds_q20: *const u32, n_thresholds: u32, over: *mut u64) -> c_int;
     pub fn ce_eval_pair_delta_e_itp_map(ctx: *mut ce_ctx, reference: *const c_float, reference_len: usize, test: *const c_float,

@@ -211,6 +211,11 @@ class CePlaneHvsScores(C.Structure):
                 ("psnr_hvs", C.c_double * 3), ("psnr_hvsm", C.c_double * 3), ("n_planes", C.c_uint32), ("step", C.c_uint32)]
 
 
+class CePlaneVifScores(C.Structure):
+    _fields_ = [("num_q", (C.c_uint64 * 4) * 3), ("den_q", (C.c_uint64 * 4) * 3), ("n_pos", (C.c_uint64 * 4) * 3),
+                ("vif_scale", (C.c_double * 4) * 3), ("vifp", C.c_double * 3), ("ran", C.c_uint32 * 3), ("n_planes", C.c_uint32)]
+
+
 class CodecEvalError(RuntimeError):
     """Mirrors codec_eval::Error for this path (src/error.rs:31-49)."""
 
@@ -369,6 +374,8 @@ _PROTOTYPES = [
                                C.POINTER(CePlaneScores)]),
     ("ce_yuv_plane_hvs", _i, [_vp, _u32, _u32, C.POINTER(CeYuvImage), _u32, C.POINTER(CeYuvImage), _u32, _vp, _u32,
                           C.POINTER(CePlaneHvsScores)]),
+    ("ce_yuv_plane_vif", _i, [_vp, _u32, _u32, C.POINTER(CeYuvImage), _u32, C.POINTER(CeYuvImage), _u32, _vp, C.POINTER(CePlaneVifScores)]),
+    ("ce_vif_window", _i, [_u32, _vp]),
     ("ce_batch_msssim_map", _i, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
     ("ce_eval_pair_msssim_map", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
     ("ce_eval_pair_msssim_map_deep", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
@@ -968,6 +975,34 @@ class PlaneHvsScores:
         pairs = lambda a: tuple((int(a[p][0]), int(a[p][1])) for p in range(3))  # noqa: E731
         return PlaneHvsScores(pairs(s.hvs_q), pairs(s.hvsm_q), tuple(int(v) for v in s.n_blocks), tuple(s.psnr_hvs), tuple(s.psnr_hvsm),
                               int(s.n_planes), int(s.step))
+
+
+@dataclass(frozen=True)
+class PlaneVifScores:
+    """Pixel-domain VIF (VIFp) of one pair of Y'CbCr images plane by plane (ce_plane_vif_scores): index p = 0, 1, 2 is Y, Cb,
+    Cr.  num_q[p][s] and den_q[p][s] are the exact sums, in units of 2^-24 nat, of the information the test and the reference
+    carry at scale s + 1 over n_pos[p][s] positions; vif_scale[p][s] is their ratio and vifp[p] the ratio of the sums over the
+    four scales (1.0 where the denominator is 0).  ran[p] is 1 where plane p ran; a plane that did not has 0 and NaN."""
+    num_q: Tuple[Tuple[int, ...], ...]
+    den_q: Tuple[Tuple[int, ...], ...]
+    n_pos: Tuple[Tuple[int, ...], ...]
+    vif_scale: Tuple[Tuple[float, ...], ...]
+    vifp: Tuple[float, float, float]
+    ran: Tuple[int, int, int]
+    n_planes: int
+
+    @staticmethod
+    def from_c(s: CePlaneVifScores) -> "PlaneVifScores":
+        grid = lambda a, t: tuple(tuple(t(v) for v in a[p]) for p in range(3))  # noqa: E731
+        return PlaneVifScores(grid(s.num_q, int), grid(s.den_q, int), grid(s.n_pos, int), grid(s.vif_scale, float), tuple(s.vifp),
+                              tuple(int(v) for v in s.ran), int(s.n_planes))
+
+
+def vif_window(scale: int) -> np.ndarray:
+    """The Gaussian window of VIFp's scale 1 .. 4 (ce_vif_window), 17, 9, 5 or 3 float64: the library's literals."""
+    out = np.empty(17, np.float64)
+    _host_check(lib().ce_vif_window(scale, out.ctypes.data))
+    return out[:(17, 9, 5, 3)[scale - 1]].copy()
 
 
 DELTA_E_ITP_Q20 = 1 << 20  # a Delta E ITP of 1.0 in the units of the maps and thresholds (CE_DELTA_E_ITP_Q20)
@@ -1920,6 +1955,24 @@ class Context:
         self._check(lib().ce_yuv_plane_hvs(self._h, width, height, cr, len(refs), ct, len(tests),
                                            table.ctypes.data if table is not None else None, step, out))
         return [PlaneHvsScores.from_c(out[i]) for i in range(len(tests))]
+
+    def plane_vif(self, refs: Sequence["YuvImage"], tests: Sequence["YuvImage"], width: int, height: int,
+                  pair_ref: Optional[Sequence[int]] = None) -> List[PlaneVifScores]:
+        """Pixel-domain VIF (VIFp) of Y'CbCr images plane by plane (ce_yuv_plane_vif), with plane_fidelity's images, pair table
+        and semantics.  A plane needs 41 x 41 samples to run; luma must."""
+        cr, ct = (CeYuvImage * max(len(refs), 1))(), (CeYuvImage * max(len(tests), 1))()
+        keep = []
+        for arr, imgs in ((cr, refs), (ct, tests)):
+            for i, img in enumerate(imgs):
+                arr[i], k = img._c()
+                keep.append(k)
+        table = None if pair_ref is None else np.ascontiguousarray(pair_ref, dtype=np.uint32).reshape(-1)
+        if table is not None and table.size != len(tests):
+            raise CodecEvalError(CE_ERR_INVALID_ARG, f"pair_ref names {table.size} pairs for {len(tests)} tests")
+        out = (CePlaneVifScores * max(len(tests), 1))()
+        self._check(lib().ce_yuv_plane_vif(self._h, width, height, cr, len(refs), ct, len(tests),
+                                           table.ctypes.data if table is not None else None, out))
+        return [PlaneVifScores.from_c(out[i]) for i in range(len(tests))]
 
     def delta_e_itp_map(self, reference, test, width: int, height: int, depth: int = 10, white_nits: float = 203.0, block: int = 1,
                         thresholds_q20=None, maps: bool = True):

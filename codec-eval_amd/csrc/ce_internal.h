@@ -138,6 +138,9 @@ struct ce_ctx {
     ce_dev<float> pf_pyr;
     ce_dev<unsigned long long> pf_out_d;
     ce_pinned<unsigned long long> pf_out_h;
+    // ... and of VIFp on the same planes (plane_vif.hip): the f64 pyramid of scales 2 - 4, [plane][scale][image][h][w]; its
+    // result integers, [pair][24], go through pf_out_d / pf_out_h
+    ce_dev<double> pf_vif_pyr;
 
     // Auxiliary streams of the context, shared by all its batches (made on first use, destroyed with the context): the
     // three metric chains of a forked batch, SSIMULACRA2's level-0 passes, Butteraugli's half-resolution chain.  Rounds

@@ -955,6 +955,27 @@ inline std::vector<PlaneHvsScores> plane_hvs(const HipBackend &be, const std::ve
                   "plane_hvs", width, height, 0);
     return out;
 }
+// ---- pixel-domain VIF (VIFp) of the same planes (include/ce_metrics.h: ce_yuv_plane_vif) ----
+// per plane and scale the two exact sums in units of 2^-24 nat, the positions, their ratio, and vifp over the four scales
+using PlaneVifScores = ce_plane_vif_scores;
+inline std::vector<PlaneVifScores> plane_vif(const HipBackend &be, const std::vector<ce_yuv_image> &refs, const std::vector<ce_yuv_image> &tests,
+                                             uint32_t width, uint32_t height, const std::vector<uint32_t> &pair_ref = {})
+{
+    std::vector<PlaneVifScores> out(tests.size());
+    if (!pair_ref.empty() && pair_ref.size() != tests.size()) detail::check(be, CE_ERR_INVALID_ARG, "plane_vif", width, height, 0);
+    detail::check(be, ce_yuv_plane_vif(be.ctx(), width, height, refs.data(), (uint32_t)refs.size(), tests.data(), (uint32_t)tests.size(),
+                                       pair_ref.empty() ? nullptr : pair_ref.data(), out.data()),
+                  "plane_vif", width, height, 0);
+    return out;
+}
+// the 17, 9, 5 or 3 literals of scale 1 .. 4's window (a pure host function; empty when refused)
+inline std::vector<double> vif_window(uint32_t scale)
+{
+    std::vector<double> g(17);
+    if (ce_vif_window(scale, g.data()) != CE_OK) return {};
+    g.resize(scale == 1 ? 17 : scale == 2 ? 9 : scale == 3 ? 5 : 3);
+    return g;
+}
 // straight into a slot of a resident batch (RGB8 or deep), host or device planes
 inline void batch_set_reference_yuv(const HipBackend &be, ce_batch *batch, uint32_t ref_index, const YuvImage &image)
 {

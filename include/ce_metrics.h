@@ -1355,6 +1355,64 @@ int ce_yuv_plane_hvs(ce_ctx *ctx, uint32_t width, uint32_t height, const ce_yuv_
                      const ce_yuv_image *tests, uint32_t n_pairs, const uint32_t *pair_ref, uint32_t step,
                      ce_plane_hvs_scores *out);
 
+/* ---- pixel-domain VIF (VIFp) of a decoder's Y'CbCr planes ---------------------------------------------------
+ * Sheikh & Bovik's visual information fidelity in the pixel domain (vifp_mscale), per plane, on the planes as the decoder wrote
+ * them: the "VIF" of learned-codec papers and of the JPEG AI common test conditions; its per-scale ratios are the four VIF
+ * features a VMAF model reads.  This text and its numpy restatement, tests/plane_vif_restatement.py, are the contract - not the
+ * output of any tool: the device equals the restatement on every integer.  Every f64 operation named below is one separately
+ * rounded IEEE operation (no contraction, no libm on the device); division is correctly rounded.
+ * Inputs.  The images, planes p = 0, 1, 2, plane sizes and samples min(v >> shift, L), L = 2^d - 1, d in {8, 10, 12}, of
+ *   ce_yuv_plane_fidelity above, unchanged.  A sample enters as x = (double) v * 2^(8 - d), which is exact: the constants 2.0
+ *   and 1e-10 below keep their 8-bit meaning at every depth.
+ * Windows.  Scale s = 1 .. 4 has N_s = 17, 9, 5, 3 taps: g_s[i] = exp(-(i - c)^2 / (2 sd^2)) over their sum, c = (N_s - 1) / 2,
+ *   sd = N_s / 5, the f64 numbers numpy gives, literals in the library (ce_vif_window).
+ * Filter F_s(p).  "Valid" filtering, first down the columns and then along the rows, each pass ((g[0] p0 + g[1] p1) + g[2] p2)
+ *   + ...: products separately rounded, sums left to right.  A w x h plane gives (w - N_s + 1) x (h - N_s + 1).
+ * Pyramid.  Scale 1 is the plane.  For s >= 2 both sides become F_s(previous)[0::2, 0::2] - the outputs at even rows and even
+ *   columns - so w_s = (w_(s-1) - N_s + 2) / 2 in integers, h_s alike; the values stay f64.  A plane runs all four scales iff
+ *   pw >= 41 and ph >= 41, the smallest size that leaves one position at scale 4.  Luma must run; a chroma plane that does not
+ *   has integers 0, doubles NaN and ran[p] = 0.
+ * Per scale and position, X the reference and Y the test at scale s: mu1 = F(X), mu2 = F(Y), s1 = F(X * X) - mu1 * mu1, s2 =
+ *   F(Y * Y) - mu2 * mu2, s12 = F(X * Y) - mu1 * mu2, the products X * X, Y * Y, X * Y formed per sample before filtering.
+ *   Then in this order: (1) s1 < 0 -> s1 = 0; s2 < 0 -> s2 = 0.  (2) g = s12 / (s1 + 1e-10); sv = s2 - g * s12.  (3) where
+ *   s1 < 1e-10: g = 0, sv = s2, s1 = 0.  (4) where s2 < 1e-10: g = 0, sv = 0.  (5) where g < 0: sv = s2, g = 0.  (6) where
+ *   sv <= 1e-10: sv = 1e-10.  (7) a = 1.0 + ((g * g) * s1) / (sv + 2.0); b = 1.0 + s1 / 2.0.
+ * Logarithm.  ln_fixed(x) for a normal x >= 1: the exponent e and the mantissa m in [1, 2) split from the bits; m >=
+ *   1.4142135623730951 -> m = m * 0.5, e = e + 1; t = (m - 1.0) / (m + 1.0); t2 = t * t; p = 1.0 / 21.0, then p = p * t2 + 1.0 /
+ *   k for k = 19, 17, ... 3, 1 (the quotients of literals correctly rounded); ln_fixed = (2.0 * t) * p + (double) e *
+ *   0.6931471805599453.  qa = (uint64) rint(ln_fixed(a) * 16777216.0), qb the same of b: the unit is 2^-24 nat, each q is
+ *   under 2^28.
+ * Per pair, plane and scale.  num_q[p][s-1] = sum qa, den_q[p][s-1] = sum qb, n_pos[p][s-1] = (w_s - N_s + 1) * (h_s - N_s +
+ *   1): exact unsigned 64-bit integers, whatever the grid.
+ * Finishing, on the host.  vif_scale[p][s-1] = (double) num_q / (double) den_q; vifp[p] the same of the sums over the four
+ *   scales; a denominator of 0 (a reference with nothing to lose) gives 1.0 - libvmaf's convention, here this library's
+ *   choice.  Planes are not averaged.
+ * Not part of this: wavelet-domain VIF, VMAF's integer VIF and its model, per-position maps, RGB batches, ce_ref_* handles and
+ *   ce_eval_batch, f32 pyramids (another rounding would be another contract). */
+typedef struct ce_plane_vif_scores {
+    uint64_t num_q[3][4];   /* [plane][scale - 1] */
+    uint64_t den_q[3][4];
+    uint64_t n_pos[3][4];
+    double vif_scale[3][4];
+    double vifp[3];
+    uint32_t ran[3];        /* 1: the plane ran its four scales */
+    uint32_t n_planes;
+} ce_plane_vif_scores;      /* 424 bytes */
+/* Scores n_pairs tests, tests[i] against refs[pair_ref[i]] - or against refs[i] with pair_ref NULL, which needs n_refs ==
+ * n_pairs - into out[0 .. n_pairs), with ce_yuv_plane_hvs's semantics: on the context's stream, blocking until the scores are
+ * on the host; no batch is touched and a batch launch that is still to be collected is unaffected; CE_MEM_HOST planes go
+ * through the same page-locked staging and grow-only scratch and are consumed on return; CE_MEM_DEVICE planes are read in
+ * place.  The f64 pyramid of scales 2 - 4 and the result integers are grow-only scratch of the context too, freed with it and
+ * outside ce_estimate_batch_bytes; a scratch allocation that fails returns CE_ERR_BACKEND and leaves the context usable.  A
+ * reference that several pairs name is reduced once per call.
+ * CE_ERR_INVALID_ARG, with the reason in ce_last_error and the context still usable: everything ce_yuv_plane_fidelity refuses
+ * of the pointers, the counts, the pair table and the images; a luma plane under 41 x 41. */
+int ce_yuv_plane_vif(ce_ctx *ctx, uint32_t width, uint32_t height, const ce_yuv_image *refs, uint32_t n_refs,
+                     const ce_yuv_image *tests, uint32_t n_pairs, const uint32_t *pair_ref, ce_plane_vif_scores *out);
+/* The N_s literals of scale 1 .. 4's window (17, 9, 5, 3) into out[0 .. N_s); a pure host function.  CE_ERR_INVALID_ARG for a
+ * null pointer or another scale. */
+int ce_vif_window(uint32_t scale, double *out);
+
 /* ---- matrix/TRC ICC profiles applied on the device ------------------------------------------------
  * transform_to_srgb (src/metrics/icc.rs:69-103) for the profiles photographs carry - three colorant tags and three tone
  * curves - without a CMS on the host.  ce_lut_* above stays the route for every other profile.
