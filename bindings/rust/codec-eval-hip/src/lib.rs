@@ -770,6 +770,34 @@ impl HipMetrics {
         Ok(out)
     }
 
+    /// `ce_eval_pair_ciede2000_map`: where one pair of packed RGB8 read as sRGB differs, and in which direction of colour space -
+    /// see `HipBatch::ciede2000_map`.
+    pub fn ciede2000_map(&mut self, reference: &[u8], test: &[u8], width: u32, height: u32, what: u32, block: u32, want_map: bool,
+                         thresholds_q20: &[u32]) -> Result<Ciede2000Maps, HipError> {
+        let mut out = Ciede2000Maps::sized(1, width, height, block, want_map, thresholds_q20.len());
+        let rc = unsafe {
+            sys::ce_eval_pair_ciede2000_map(self.ctx, reference.as_ptr(), reference.len(), test.as_ptr(), test.len(), width, height, what,
+                                            block, out.map_ptr(), out.map.len(), slice_or_null(thresholds_q20),
+                                            thresholds_q20.len() as u32, out.over_ptr())
+        };
+        self.check(rc, width, height, test.len())?;
+        Ok(out)
+    }
+
+    /// `ce_eval_pair_ciede2000_map_deep`: the same for packed u16 RGB, the reference at `ref_depth` and the test at `test_depth`
+    /// bits (each 8, 10, 12 or 16).
+    pub fn ciede2000_map_deep(&mut self, reference: &[u16], test: &[u16], ref_depth: u32, test_depth: u32, width: u32, height: u32,
+                              what: u32, block: u32, want_map: bool, thresholds_q20: &[u32]) -> Result<Ciede2000Maps, HipError> {
+        let mut out = Ciede2000Maps::sized(1, width, height, block, want_map, thresholds_q20.len());
+        let rc = unsafe {
+            sys::ce_eval_pair_ciede2000_map_deep(self.ctx, reference.as_ptr(), reference.len() * 2, test.as_ptr(), test.len() * 2, ref_depth,
+                                                 test_depth, width, height, what, block, out.map_ptr(), out.map.len(),
+                                                 slice_or_null(thresholds_q20), thresholds_q20.len() as u32, out.over_ptr())
+        };
+        self.check(rc, width, height, test.len() * 2)?;
+        Ok(out)
+    }
+
     /// `ce_eval_pair_msssim_map`: where one pair of packed RGB8 differs at `level` - see `HipBatch::ms_ssim_map`.
     pub fn ms_ssim_map(&mut self, reference: &[u8], test: &[u8], width: u32, height: u32, levels: u32, level: u32, what: u32, block: u32,
                        want_map: bool, thresholds_q32: &[u32]) -> Result<MsSsimMaps, HipError> {
@@ -892,6 +920,32 @@ impl DeltaEItpMaps {
     }
 }
 
+/// What `ce_batch_ciede2000_map` returns: per pair one of a pixel's four values in units of 2^-20 (`sys::CE_CIEDE2000_Q20` is
+/// 1.0) - the Delta E 2000 itself or the magnitude of its lightness, chroma or hue term, which may exceed the Delta E - or at
+/// `block` 2 ..= 64 the maximum of each block x block cell - as `[count][cells_h][cells_w]`, empty when no map was asked for; and
+/// `[count][n_thresholds]` counts of the pixels above each threshold, empty without thresholds.
+pub struct Ciede2000Maps {
+    pub map: Vec<u32>,
+    pub cells_w: u32,
+    pub cells_h: u32,
+    pub over: Vec<u64>,
+}
+
+impl Ciede2000Maps {
+    fn sized(count: u32, width: u32, height: u32, block: u32, want_map: bool, n_thresholds: usize) -> Self {
+        let b = block.max(1);
+        let (cells_w, cells_h) = ((width + b - 1) / b, (height + b - 1) / b);
+        let n = if want_map { count as usize * cells_w as usize * cells_h as usize } else { 0 };
+        Ciede2000Maps { map: vec![0u32; n], cells_w, cells_h, over: vec![0u64; count as usize * n_thresholds] }
+    }
+    fn map_ptr(&mut self) -> *mut u32 {
+        if self.map.is_empty() { std::ptr::null_mut() } else { self.map.as_mut_ptr() }
+    }
+    fn over_ptr(&mut self) -> *mut u64 {
+        if self.over.is_empty() { std::ptr::null_mut() } else { self.over.as_mut_ptr() }
+    }
+}
+
 /// What `ce_batch_msssim_map` returns: per pair and channel every valid position's `2^32 - q` in units of 2^-32
 /// (`sys::CE_MSSSIM_Q32` is an SSIM of 1.0), `q` the integer `ms_ssim` sums, saturated to `[0, u32::MAX]` - or at `block` 2 ..= 64
 /// the maximum of each block x block cell - as `[count][3][cells_h][cells_w]`, empty when no map was asked for; and
@@ -963,6 +1017,19 @@ pub fn ciede2000_pixels(reference: &[u16], ref_depth: u32, test: &[u16], test_de
     }
     let mut out = vec![0u32; reference.len() / 3];
     let rc = unsafe { sys::ce_ciede2000_pixels(reference.as_ptr(), ref_depth, test.as_ptr(), test_depth, out.len(), out.as_mut_ptr()) };
+    (rc == sys::CE_OK).then_some(out)
+}
+
+/// `ce_ciede2000_pixel_terms`: the four per-pixel values of the CIEDE2000 maps in units of 2^-20, `[n][4]` indexed by
+/// `sys::CE_CIEDE2000_MAP_DE`, `_DL`, `_DC`, `_DH` - column 0 is `ciede2000_pixels`' value; `None` as there.  A pure host function.
+pub fn ciede2000_pixel_terms(reference: &[u16], ref_depth: u32, test: &[u16], test_depth: u32) -> Option<Vec<[u32; 4]>> {
+    if reference.len() != test.len() || reference.len() % 3 != 0 {
+        return None;
+    }
+    let mut out = vec![[0u32; 4]; reference.len() / 3];
+    let rc = unsafe {
+        sys::ce_ciede2000_pixel_terms(reference.as_ptr(), ref_depth, test.as_ptr(), test_depth, out.len(), out.as_mut_ptr() as *mut u32)
+    };
     (rc == sys::CE_OK).then_some(out)
 }
 
@@ -1379,6 +1446,21 @@ impl HipBatch<'_> {
         let mut out = vec![sys::ce_ciede2000_scores::default(); n_pairs as usize];
         let rc = unsafe {
             sys::ce_batch_ciede2000(self.handle, n_pairs, thresholds_q20.as_ptr(), thresholds_q20.len() as u32, out.as_mut_ptr())
+        };
+        self.check(rc, 0)?;
+        Ok(out)
+    }
+
+    /// `ce_batch_ciede2000_map`: where pairs `[first, first + count)` of an RGB8 or deep batch read as sRGB differ - the per-pixel
+    /// map of `what` (`sys::CE_CIEDE2000_MAP_DE`, `_DL`, `_DC` or `_DH`) at `block` 1 or its block x block cell maxima when
+    /// `want_map`, and how many pixels of each pair exceed each of up to `sys::CE_CIEDE2000_MAX_THRESHOLDS` thresholds; one of the
+    /// two must be asked for.
+    pub fn ciede2000_map(&mut self, first: u32, count: u32, what: u32, block: u32, want_map: bool, thresholds_q20: &[u32])
+                         -> Result<Ciede2000Maps, HipError> {
+        let mut out = Ciede2000Maps::sized(count, self.width, self.height, block, want_map, thresholds_q20.len());
+        let rc = unsafe {
+            sys::ce_batch_ciede2000_map(self.handle, first, count, what, block, out.map_ptr(), out.map.len(),
+                                        slice_or_null(thresholds_q20), thresholds_q20.len() as u32, out.over_ptr())
         };
         self.check(rc, 0)?;
         Ok(out)

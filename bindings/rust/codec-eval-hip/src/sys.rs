@@ -342,6 +342,14 @@ pub const CE_MSSSIM_MAP_MAX_THRESHOLDS: u32 = 8;
 pub const CE_MSSSIM_Q32: u64 = 1 << 32;
 pub const CE_MSSSIM_MAP_SSIM: u32 = 0;
 pub const CE_MSSSIM_MAP_CS: u32 = 1;
+/// `CE_CIEDE2000_MAX_THRESHOLDS`, a CIEDE2000 of 1.0 in the units of q, the maps and the thresholds (`CE_CIEDE2000_Q20`), and the
+/// four values a CIEDE2000 map can hold: q itself or the magnitude of its lightness, chroma or hue term (`CE_CIEDE2000_MAP_*`)
+pub const CE_CIEDE2000_MAX_THRESHOLDS: u32 = 8;
+pub const CE_CIEDE2000_Q20: u32 = 1 << 20;
+pub const CE_CIEDE2000_MAP_DE: u32 = 0;
+pub const CE_CIEDE2000_MAP_DL: u32 = 1;
+pub const CE_CIEDE2000_MAP_DC: u32 = 2;
+pub const CE_CIEDE2000_MAP_DH: u32 = 3;
 
 /// `ce_pair_desc` (40 bytes): one item of the (image x codec x quality) grid, host pointers.
 #[repr(C)]
@@ -607,6 +615,15 @@ extern "C" {
                                        ref_depth: u32, test_depth: u32, width: u32, height: u32, thresholds_q20: *const u32,
                                        n_thresholds: u32, out: *mut ce_ciede2000_scores) -> c_int;
     pub fn ce_ciede2000_pixels(ref_rgb: *const u16, ref_depth: u32, test_rgb: *const u16, test_depth: u32, n: usize, out_q20: *mut u32) -> c_int;
+    pub fn ce_batch_ciede2000_map(b: *mut ce_batch, first: u32, count: u32, what: u32, block: u32, map: *mut u32, map_len: usize,
+                                  thresholds_q20: *const u32, n_thresholds: u32, over: *mut u64) -> c_int;
+    pub fn ce_eval_pair_ciede2000_map(ctx: *mut ce_ctx, reference: *const u8, reference_len: usize, test: *const u8, test_len: usize,
+                                      width: u32, height: u32, what: u32, block: u32, map: *mut u32, map_len: usize,
+                                      thresholds_q20: *const u32, n_thresholds: u32, over: *mut u64) -> c_int;
+    pub fn ce_eval_pair_ciede2000_map_deep(ctx: *mut ce_ctx, reference: *const u16, reference_len: usize, test: *const u16, test_len: usize,
+                                           ref_depth: u32, test_depth: u32, width: u32, height: u32, what: u32, block: u32, map: *mut u32,
+                                           map_len: usize, thresholds_q20: *const u32, n_thresholds: u32, over: *mut u64) -> c_int;
+    pub fn ce_ciede2000_pixel_terms(ref_rgb: *const u16, ref_depth: u32, test_rgb: *const u16, test_depth: u32, n: usize, out: *mut u32) -> c_int;
     pub fn ce_msssim_levels(w: u32, h: u32, levels: u32, n_levels: *mut u32, level_w: *mut u32, level_h: *mut u32) -> c_int;
     pub fn ce_yuv_plane_fidelity(ctx: *mut ce_ctx, width: u32, height: u32, refs: *const ce_yuv_image, n_refs: u32, tests: *const ce_yuv_image,
                                  n_pairs: u32, pair_ref: *const u32, levels: u32, out: *mut ce_plane_scores) -> c_int;

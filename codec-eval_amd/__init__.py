@@ -384,6 +384,10 @@ _PROTOTYPES = [
     ("ce_eval_pair_ciede2000", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _vp, _u32, C.POINTER(CeCiede2000Scores)]),
     ("ce_eval_pair_ciede2000_deep", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, _vp, _u32, C.POINTER(CeCiede2000Scores)]),
     ("ce_ciede2000_pixels", _i, [_vp, _u32, _vp, _u32, _sz, _vp]),
+    ("ce_batch_ciede2000_map", _i, [_vp, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
+    ("ce_eval_pair_ciede2000_map", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
+    ("ce_eval_pair_ciede2000_map_deep", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
+    ("ce_ciede2000_pixel_terms", _i, [_vp, _u32, _vp, _u32, _sz, _vp]),
     ("ce_msssim_levels", _i, [_u32, _u32, _u32, _vp, _vp, _vp]),
     ("ce_icc_describe", _i, [_vp, _sz, C.POINTER(CeIccDescription)]),
     ("ce_icc_build_matrix", _i, [_vp, _sz, _vp]),
@@ -918,6 +922,44 @@ def ciede2000_pixels(reference, test, ref_depth: int = 8, test_depth: int = 8) -
     out = np.empty(r.size // 3, np.uint32)
     _host_check(lib().ce_ciede2000_pixels(r.ctypes.data, ref_depth, t.ctypes.data, test_depth, out.size, out.ctypes.data))
     return out
+
+
+# which of a pixel's four values a CIEDE2000 map holds (CE_CIEDE2000_MAP_*): q itself, or the magnitude of its lightness, chroma
+# or hue term, all in units of 2^-20
+CIEDE2000_MAP_DE, CIEDE2000_MAP_DL, CIEDE2000_MAP_DC, CIEDE2000_MAP_DH = 0, 1, 2, 3
+_CIEDE2000_MAP_WHAT = {"de": CIEDE2000_MAP_DE, "dl": CIEDE2000_MAP_DL, "dc": CIEDE2000_MAP_DC, "dh": CIEDE2000_MAP_DH}
+
+
+def ciede2000_pixel_terms(reference, test, ref_depth: int = 8, test_depth: int = 8) -> np.ndarray:
+    """The four per-pixel values of the CIEDE2000 maps in units of 2^-20 (ce_ciede2000_pixel_terms), uint32 [n, 4]: column
+    CIEDE2000_MAP_DE is ciede2000_pixels' q, columns _DL, _DC and _DH the magnitudes of the lightness, chroma and hue terms.
+    A pure host function - the kernel's pixel text compiled for the host - that needs no GPU."""
+    r = np.ascontiguousarray(np.asarray(reference).astype(np.uint16).reshape(-1))
+    t = np.ascontiguousarray(np.asarray(test).astype(np.uint16).reshape(-1))
+    if r.size != t.size or r.size % 3:
+        raise ValueError("ciede2000_pixel_terms: both sides need the same number of RGB triples")
+    out = np.empty((r.size // 3, 4), np.uint32)
+    _host_check(lib().ce_ciede2000_pixel_terms(r.ctypes.data, ref_depth, t.ctypes.data, test_depth, out.shape[0], out.ctypes.data))
+    return out
+
+
+def _ciede2000_map(ctx: "Context", call, count: int, width: int, height: int, what, block: int, thresholds_q20, maps: bool):
+    """The outputs of ce_batch_ciede2000_map / ce_eval_pair_ciede2000_map{,_deep} around call(what, map, map_len, thresholds, n,
+    over): (uint32 [count, ceil(h / block), ceil(w / block)] or None, uint64 [count, n] or None).  what: "de", "dl", "dc", "dh"
+    or a CIEDE2000_MAP_* integer, which the library checks."""
+    if isinstance(what, str):
+        if what not in _CIEDE2000_MAP_WHAT:
+            raise CodecEvalError(CE_ERR_INVALID_ARG, 'what must be "de", "dl", "dc" or "dh"')
+        what = _CIEDE2000_MAP_WHAT[what]
+    if block < 1:
+        raise CodecEvalError(CE_ERR_INVALID_ARG, "block must be 1 or a power of two up to 64")
+    m = np.empty((max(count, 0), -(-height // block), -(-width // block)), np.uint32) if maps else None
+    thr = None if thresholds_q20 is None else _thresholds_q20(thresholds_q20)
+    over = None if thr is None else np.zeros((max(count, 0), thr.size), np.uint64)
+    ctx._check(call(what, m.ctypes.data if maps and m.size else None, m.size if maps else 0,
+                    thr.ctypes.data if thr is not None and thr.size else None, thr.size if thr is not None else 0,
+                    over.ctypes.data if over is not None else None))
+    return m, over
 
 
 @dataclass(frozen=True)
@@ -1904,6 +1946,22 @@ class Context:
                                                           thr.ctypes.data if thr.size else None, thr.size, C.byref(s)))
         return Ciede2000.from_c(s)
 
+    def ciede2000_map(self, reference, test, width: int, height: int, what="de", block: int = 1, thresholds_q20=None, maps: bool = True,
+                      depth: int = 0, test_depth: Optional[int] = None):
+        """Batch.ciede2000_maps for one pair of packed uint8 RGB (`depth` 0; ce_eval_pair_ciede2000_map) or packed uint16 RGB with
+        the reference at `depth` and the test at `test_depth` bits (`depth` again when None; ce_eval_pair_ciede2000_map_deep):
+        (uint32 [1, ceil(h / block), ceil(w / block)] or None, uint64 [1, n] or None)."""
+        if depth == 0:
+            r, t = _buf(reference), _buf(test)
+            call = lambda wh, m, n, thr, k, over: lib().ce_eval_pair_ciede2000_map(  # noqa: E731
+                self._h, r.ctypes.data, r.size, t.ctypes.data, t.size, width, height, wh, block, m, n, thr, k, over)
+        else:
+            r, t = _buf16(reference), _buf16(test)
+            call = lambda wh, m, n, thr, k, over: lib().ce_eval_pair_ciede2000_map_deep(  # noqa: E731
+                self._h, r.ctypes.data, r.nbytes, t.ctypes.data, t.nbytes, depth, depth if test_depth is None else test_depth, width, height,
+                wh, block, m, n, thr, k, over)
+        return _ciede2000_map(self, call, 1, width, height, what, block, thresholds_q20, maps)
+
     def ms_ssim_map(self, reference, test, width: int, height: int, levels: int = 5, level: int = 0, what: str = "ssim", block: int = 1,
                     thresholds_q32=None, maps: bool = True, depth: int = 0):
         """Batch.ms_ssim_maps for one pair of packed uint8 RGB (depth 0; ce_eval_pair_msssim_map) or packed uint16 RGB of `depth`
@@ -2523,6 +2581,17 @@ class Batch:
         thr = _thresholds_q20(thresholds_q20)
         self.ctx._check(lib().ce_batch_ciede2000(self._h, n_pairs, thr.ctypes.data if thr.size else None, thr.size, out))
         return [Ciede2000.from_c(out[i]) for i in range(n_pairs)]
+
+    def ciede2000_maps(self, first: int, count: int, what="de", block: int = 1, thresholds_q20=None, maps: bool = True):
+        """Where pairs [first, first + count) of an RGB8 or deep batch read as sRGB differ, and in which direction of colour space
+        (ce_batch_ciede2000_map): per pixel one of four values in units of 2^-20 (CIEDE2000_Q20 is 1.0) - with what="de" the
+        Delta E 2000, the very integer ciede2000() sums; with "dl", "dc" or "dh" the magnitude of its lightness, chroma or hue
+        term, which may exceed the Delta E - as a uint32 [count, h, w] array, or at block = 2 .. 64 the maximum of each block x
+        block cell, [count, ceil(h / block), ceil(w / block)]; and for up to 8 `thresholds_q20` how many pixels of each pair
+        exceed each, uint64 [count, n].  maps=False: counts only (None for the maps); thresholds_q20=None: maps only.  What
+        launch() left to collect and ciede2000()'s results are untouched."""
+        return _ciede2000_map(self.ctx, lambda wh, m, n, thr, k, over: lib().ce_batch_ciede2000_map(
+            self._h, first, count, wh, block, m, n, thr, k, over), count, self.width, self.height, what, block, thresholds_q20, maps)
 
     def ms_ssim_maps(self, first: int, count: int, levels: int = 5, level: int = 0, what: str = "ssim", block: int = 1, thresholds_q32=None,
                      maps: bool = True):

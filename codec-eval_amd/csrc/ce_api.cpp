@@ -1448,6 +1448,67 @@ int ce_ciede2000_pixels(const uint16_t *ref_rgb, uint32_t ref_depth, const uint1
     return CE_OK;
 }
 
+// CIEDE2000 per pixel, per cell and over thresholds, for q or one of its terms (include/ce_metrics.h):
+// ce_batch_ciede2000's frame around the map kernel, ce_batch_delta_e_itp_map's rules for the outputs
+int ce_batch_ciede2000_map(ce_batch *b, uint32_t first, uint32_t count, uint32_t what, uint32_t block, uint32_t *map, size_t map_len,
+                           const uint32_t *thresholds_q20, uint32_t n_thresholds, uint64_t *over)
+{
+    if (!b) return ce_fail(nullptr, CE_ERR_INVALID_ARG, "CIEDE2000 map: null batch");
+    ce_ctx *ctx = b->ctx;
+    if (b->linear)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "the CIEDE2000 map reads sRGB sample values: not for a linear batch, whose map is Delta E ITP's "
+                                                "(ce_batch_delta_e_itp_map)");
+    if (what > CE_CIEDE2000_MAP_DH)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "CIEDE2000 map: what must be CE_CIEDE2000_MAP_DE, _DL, _DC or _DH, got " + std::to_string(what));
+    if (!map && !over) return ce_fail(ctx, CE_ERR_INVALID_ARG, "CIEDE2000 map: neither a map nor counts asked for");
+    if (count == 0 || first > b->max_pairs || count > b->max_pairs - first)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "CIEDE2000 map: pairs [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) +
+                                                 ") outside the batch's " + std::to_string(b->max_pairs));
+    if (int rc = check_map_readout(ctx, "CIEDE2000 map", b->max_pairs, first, count, block, b->w, b->h, map != nullptr, map_len)) return rc;
+    if (n_thresholds > CE_CIEDE2000_MAX_THRESHOLDS)
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "CIEDE2000 map: at most " + std::to_string(CE_CIEDE2000_MAX_THRESHOLDS) + " thresholds, got " +
+                                                 std::to_string(n_thresholds));
+    if (over && (n_thresholds == 0 || !thresholds_q20)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "CIEDE2000 map: counts asked for without thresholds");
+    if (!over && (n_thresholds != 0 || thresholds_q20)) return ce_fail(ctx, CE_ERR_INVALID_ARG, "CIEDE2000 map: thresholds given without a place for the counts");
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    const float *d_tab[2] = {nullptr, nullptr};
+    for (int s = 0; s < 2; s++)
+        if (int rc = ce_deep_table(ctx, b->depth[s] ? b->depth[s] : 8, 0, &d_tab[s])) return rc;
+    if (map)
+        if (int rc = b->d_ciede2000_map.reserve(ctx, map_len)) return rc;
+    const size_t over_bytes = sizeof(unsigned long long) * CE_CIEDE2000_MAX_THRESHOLDS;  // per pair
+    if (over && !b->ciede2000_over)
+        if (int rc = b->ciede2000_over.alloc(ctx, (size_t)CE_CIEDE2000_MAX_THRESHOLDS * b->max_pairs)) return rc;
+    // on the context's stream, as a launch: behind the uploads queued so far, with the pair table of the last bind
+    if (int rc = ce_flush_uploads(b)) return rc;
+    if (int rc = sync_pair_ref(b)) return rc;
+    if (int rc = ce_launch_ciede2000_map(b, first, count, what, d_tab[0], d_tab[1], block, map ? b->d_ciede2000_map.get() : nullptr, thresholds_q20,
+                                         n_thresholds, over ? b->ciede2000_over.d.get() : nullptr))
+        return rc;
+    if (map) CE_HIP(ctx, hipMemcpyAsync(map, b->d_ciede2000_map, map_len * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (over) CE_HIP(ctx, hipMemcpyAsync(b->ciede2000_over.h, b->ciede2000_over.d, over_bytes * count, hipMemcpyDeviceToHost, ctx->stream));
+    CE_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the slabs are free again: a later upload needs no fence against this
+    for (uint32_t i = 0; over && i < count; i++)
+        for (uint32_t j = 0; j < n_thresholds; j++) over[(size_t)i * n_thresholds + j] = b->ciede2000_over.h[(size_t)i * CE_CIEDE2000_MAX_THRESHOLDS + j];
+    return CE_OK;
+}
+
+int ce_ciede2000_pixel_terms(const uint16_t *ref_rgb, uint32_t ref_depth, const uint16_t *test_rgb, uint32_t test_depth, size_t n, uint32_t *out)
+{
+    if (!ce_deep_depth_ok(ref_depth) || !ce_deep_depth_ok(test_depth))
+        return ce_fail(nullptr, CE_ERR_INVALID_ARG, "ce_ciede2000_pixel_terms: depths must be 8, 10, 12 or 16 bits, got " + std::to_string(ref_depth) +
+                                                     " / " + std::to_string(test_depth));
+    if (!ref_rgb || !test_rgb || !out) return ce_fail(nullptr, CE_ERR_INVALID_ARG, "ce_ciede2000_pixel_terms: null pointer");
+    const uint32_t maxv[2] = {(1u << ref_depth) - 1u, (1u << test_depth) - 1u};
+    std::vector<float> tab[2];
+    for (int s = 0; s < (ref_depth == test_depth ? 1 : 2); s++) {
+        tab[s].resize((size_t)maxv[s] + 1);
+        ce_build_srgb_table_f64(tab[s].data(), maxv[s]);
+    }
+    ce_ciede2000_pixel_terms_host(ref_rgb, tab[0].data(), maxv[0], test_rgb, tab[ref_depth == test_depth ? 0 : 1].data(), maxv[1], n, out);
+    return CE_OK;
+}
+
 // ---- reference handle -------------------------------------------------------------------------
 
 struct ce_ref {

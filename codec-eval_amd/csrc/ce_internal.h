@@ -349,6 +349,10 @@ struct ce_batch {
     ce_mirror<unsigned long long> msssim_over;
     // CIEDE2000 (ciede2000.hip): [max_pairs][10] exact integers on the device and page-locked, lazily
     ce_mirror<unsigned long long> ciede2000;
+    // CIEDE2000 maps (ciede2000_map.hip: k_ciede2000_map): the device buffer of the maps or cell maxima of one call, grow-only;
+    // [max_pairs][8] exceedance counts on the device and page-locked, made by the first call that asks for counts
+    ce_dev<uint32_t> d_ciede2000_map;
+    ce_mirror<unsigned long long> ciede2000_over;
 
     uint32_t last_n_pairs = 0;
     bool caller_blocks = false;  // set by entry points that collect before returning: page-locked sources need no staging copy
@@ -752,6 +756,15 @@ int ce_launch_ciede2000(ce_batch *b, uint32_t n_pairs, const float *d_table_ref,
 // read through the sides' tables of maxv + 1 floats
 void ce_ciede2000_pixels_host(const uint16_t *ref_rgb, const float *ref_table, uint32_t ref_maxv, const uint16_t *test_rgb,
                               const float *test_table, uint32_t test_maxv, size_t n, uint32_t *out_q20);
+// ce_ciede2000_pixel_terms' loop, beside it: out[n][4] = q and the magnitudes of the lightness, chroma and hue terms
+void ce_ciede2000_pixel_terms_host(const uint16_t *ref_rgb, const float *ref_table, uint32_t ref_maxv, const uint16_t *test_rgb,
+                                   const float *test_table, uint32_t test_maxv, size_t n, uint32_t *out);
+// pairs [first, first + count) of an RGB8 or deep batch (ciede2000_map.hip): value `what` (CE_CIEDE2000_MAP_*) of every pixel into
+// d_map[count][h][w] (block 1) or its maximum over block x block cells into d_map[count][ch][cw], which is cleared first (nullptr:
+// no map); d_over[count][8] (nullptr: no counts) = how many pixels exceed thresholds[j], j < n_thresholds <= 8, cleared first.
+// The tables are ce_launch_ciede2000's.
+int ce_launch_ciede2000_map(ce_batch *b, uint32_t first, uint32_t count, uint32_t what, const float *d_table_ref, const float *d_table_test,
+                            uint32_t block, uint32_t *d_map, const uint32_t *thresholds, uint32_t n_thresholds, unsigned long long *d_over);
 
 // pairs [0, n_pairs) of an RGB8 or equal-depth deep batch, whose level l is lw[l] x lh[l] (ce_msssim_levels) -> d_out[pair][5]
 // [3][2] = ssim_q, cs_q, cleared and filled on the launching stream (msssim.hip): with five levels, every reference slot the

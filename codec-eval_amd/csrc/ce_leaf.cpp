@@ -436,6 +436,45 @@ int ce_eval_pair_ciede2000_deep(ce_ctx *ctx, const uint16_t *reference, size_t r
                           n_thresholds, out);
 }
 
+// ... and its CIEDE2000 map and exceedance counts through the same batches, as leaf_ciede2000; what concerns what, block and the
+// outputs is ce_batch_ciede2000_map's to refuse
+static int leaf_ciede2000_map(ce_ctx *ctx, ce_leaf_kind kind, uint32_t ref_depth, uint32_t test_depth, size_t bytes_per_pixel, const void *reference,
+                              size_t reference_len, const void *test, size_t test_len, uint32_t width, uint32_t height, uint32_t what,
+                              uint32_t block, uint32_t *map, size_t map_len, const uint32_t *thresholds_q20, uint32_t n_thresholds, uint64_t *over)
+{
+    if (!ctx) return CE_ERR_INVALID_ARG;
+    if (!reference || !test) return ce_fail(ctx, CE_ERR_INVALID_ARG, "CIEDE2000 map: null pointer");
+    if (kind == CE_LEAF_DEEP && (!ce_deep_depth_ok(ref_depth) || !ce_deep_depth_ok(test_depth)))
+        return ce_fail(ctx, CE_ERR_INVALID_ARG, "CIEDE2000 map: depths must be 8, 10, 12 or 16 bits, got " + std::to_string(ref_depth) + " / " +
+                                                 std::to_string(test_depth));
+    if (width == 0 || height == 0) return ce_fail(ctx, CE_ERR_INVALID_ARG, "CIEDE2000 map: empty image");
+    const size_t want = (size_t)width * height * bytes_per_pixel;
+    if (reference_len != want) return ce_bad_length(ctx, want, reference_len);
+    if (test_len != want) return ce_bad_length(ctx, want, test_len);
+    CE_HIP(ctx, hipSetDevice(ctx->device));
+    ce_batch *b = nullptr;
+    if (int rc = leaf_batch(ctx, kind, width, height, ref_depth, test_depth, &b)) return rc;
+    return leaf_pair(b, kind, reference, test, want, [&] {
+        return ce_batch_ciede2000_map(b, 0, 1, what, block, map, map_len, thresholds_q20, n_thresholds, over);
+    });
+}
+
+int ce_eval_pair_ciede2000_map(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test, size_t test_len, uint32_t width,
+                               uint32_t height, uint32_t what, uint32_t block, uint32_t *map, size_t map_len, const uint32_t *thresholds_q20,
+                               uint32_t n_thresholds, uint64_t *over)
+{
+    return leaf_ciede2000_map(ctx, CE_LEAF_RGB8, 0, 0, 3, reference, reference_len, test, test_len, width, height, what, block, map, map_len,
+                              thresholds_q20, n_thresholds, over);
+}
+
+int ce_eval_pair_ciede2000_map_deep(ce_ctx *ctx, const uint16_t *reference, size_t reference_len, const uint16_t *test, size_t test_len,
+                                    uint32_t ref_depth, uint32_t test_depth, uint32_t width, uint32_t height, uint32_t what, uint32_t block,
+                                    uint32_t *map, size_t map_len, const uint32_t *thresholds_q20, uint32_t n_thresholds, uint64_t *over)
+{
+    return leaf_ciede2000_map(ctx, CE_LEAF_DEEP, ref_depth, test_depth, 6, reference, reference_len, test, test_len, width, height, what, block,
+                              map, map_len, thresholds_q20, n_thresholds, over);
+}
+
 // ... and its SSIM / MS-SSIM map and exceedance counts through the same batches, as leaf_msssim; what concerns level, what, block
 // and the outputs is ce_batch_msssim_map's to refuse
 static int leaf_msssim_map(ce_ctx *ctx, ce_leaf_kind kind, uint32_t depth, size_t bytes_per_pixel, const void *reference, size_t reference_len,

@@ -169,8 +169,12 @@ __device__ __forceinline__ cie_lab cie_lab_of(float fr, float fg, float fb)
     return o;
 }
 
-// steps 4 and 5: CIEDE2000 of two Lab values -> q = rint(dE 2^20)
-__device__ __forceinline__ uint32_t cie_de2000_q20(const cie_lab &p1, const cie_lab &p2)
+// step 4 up to its last line: the lightness, chroma and hue terms dL / S_L, dC / S_C, dH / S_H of two Lab values, signed, and
+// the rotation factor R_T - what cie_de2000_q20 finishes and what the maps (ciede2000_map_kernel.h) show term by term
+struct cie_terms {
+    double tl, tc, th, rt;
+};
+__device__ __forceinline__ cie_terms cie_de2000_terms(const cie_lab &p1, const cie_lab &p2)
 {
     constexpr double k25_7 = 6103515625.0;
     const double c1 = __builtin_sqrt((p1.a * p1.a) + (p1.b * p1.b));
@@ -209,9 +213,24 @@ __device__ __forceinline__ uint32_t cie_de2000_q20(const cie_lab &p1, const cie_
     const double sh = 1.0 + ((0.015 * cpb) * t);
     const double rt = (-cie_sin_deg(2.0 * dth)) * rc;
     const double tl = dl / sl, tc = dc / sc, th = dH / sh;
+    cie_terms o;
+    o.tl = tl, o.tc = tc, o.th = th, o.rt = rt;
+    return o;
+}
+
+// the last line of step 4 and step 5: the terms -> q = rint(dE 2^20)
+__device__ __forceinline__ uint32_t cie_terms_q20(const cie_terms &e)
+{
+    const double tl = e.tl, tc = e.tc, th = e.th, rt = e.rt;
     const double s = (((tl * tl) + (tc * tc)) + (th * th)) + (rt * (tc * th));
     const double de = __builtin_sqrt(s > 0.0 ? s : 0.0);
     return (uint32_t)(unsigned long long)__builtin_rint(de * 1048576.0);
+}
+
+// steps 4 and 5: CIEDE2000 of two Lab values -> q
+__device__ __forceinline__ uint32_t cie_de2000_q20(const cie_lab &p1, const cie_lab &p2)
+{
+    return cie_terms_q20(cie_de2000_terms(p1, p2));
 }
 
 // one pixel of a pair: the six table values of its two sides -> q

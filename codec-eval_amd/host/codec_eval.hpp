@@ -849,6 +849,73 @@ inline std::vector<uint32_t> ciede2000_pixels(const uint16_t *reference, uint32_
     if (ce_ciede2000_pixels(reference, ref_depth, test, test_depth, n, out.data()) != CE_OK) out.clear();
     return out;
 }
+// Where pairs differ and in which direction of colour space (include/ce_metrics.h: ce_batch_ciede2000_map):
+// per pair one of a pixel's four values in units of 2^-20 (CE_CIEDE2000_Q20 is 1.0), selected by `what` - CE_CIEDE2000_MAP_DE the
+// Delta E 2000 itself, _DL, _DC, _DH the magnitude of its lightness, chroma or hue term, which may exceed the Delta E - at block
+// 2 .. 64 the maximum of each block x block cell - as [count][cells_h][cells_w], empty when want_map is false; and
+// [count][thresholds.size()] counts of the pixels above each of up to CE_CIEDE2000_MAX_THRESHOLDS thresholds, empty without
+// thresholds
+struct Ciede2000Maps {
+    std::vector<uint32_t> map;
+    uint32_t cells_w = 0, cells_h = 0;
+    std::vector<uint64_t> over;
+    static Ciede2000Maps sized(uint32_t count, uint32_t width, uint32_t height, uint32_t block, bool want_map, size_t n_thresholds)
+    {
+        Ciede2000Maps out;
+        const uint32_t b = block ? block : 1;
+        out.cells_w = (width + b - 1) / b, out.cells_h = (height + b - 1) / b;
+        if (want_map) out.map.resize((size_t)count * out.cells_w * out.cells_h);
+        out.over.resize((size_t)count * n_thresholds);
+        return out;
+    }
+};
+// pairs [first, first + count) of an RGB8 or deep batch of width x height; returns once the results are on the host
+inline Ciede2000Maps batch_ciede2000_map(const HipBackend &be, ce_batch *batch, uint32_t width, uint32_t height, uint32_t first, uint32_t count,
+                                         uint32_t what = CE_CIEDE2000_MAP_DE, uint32_t block = 1, bool want_map = true,
+                                         const std::vector<uint32_t> &thresholds_q20 = {})
+{
+    Ciede2000Maps out = Ciede2000Maps::sized(count, width, height, block, want_map, thresholds_q20.size());
+    detail::check(be, ce_batch_ciede2000_map(batch, first, count, what, block, out.map.empty() ? nullptr : out.map.data(), out.map.size(),
+                                             thresholds_q20.empty() ? nullptr : thresholds_q20.data(), (uint32_t)thresholds_q20.size(),
+                                             out.over.empty() ? nullptr : out.over.data()),
+                  "ciede2000_map", 0, 0, 0);
+    return out;
+}
+// one pair of packed RGB8 (width * height * 3 bytes each)
+inline Ciede2000Maps ciede2000_map(const HipBackend &be, const uint8_t *reference, const uint8_t *test, uint32_t width, uint32_t height,
+                                   uint32_t what = CE_CIEDE2000_MAP_DE, uint32_t block = 1, bool want_map = true,
+                                   const std::vector<uint32_t> &thresholds_q20 = {})
+{
+    Ciede2000Maps out = Ciede2000Maps::sized(1, width, height, block, want_map, thresholds_q20.size());
+    const size_t len = (size_t)width * height * 3;
+    detail::check(be, ce_eval_pair_ciede2000_map(be.ctx(), reference, len, test, len, width, height, what, block,
+                                                 out.map.empty() ? nullptr : out.map.data(), out.map.size(),
+                                                 thresholds_q20.empty() ? nullptr : thresholds_q20.data(), (uint32_t)thresholds_q20.size(),
+                                                 out.over.empty() ? nullptr : out.over.data()),
+                  "ciede2000_map", width, height, len);
+    return out;
+}
+// one pair of packed u16 RGB, the reference at ref_depth and the test at test_depth bits (width * height * 3 samples each)
+inline Ciede2000Maps ciede2000_map_deep(const HipBackend &be, const uint16_t *reference, const uint16_t *test, uint32_t ref_depth,
+                                        uint32_t test_depth, uint32_t width, uint32_t height, uint32_t what = CE_CIEDE2000_MAP_DE,
+                                        uint32_t block = 1, bool want_map = true, const std::vector<uint32_t> &thresholds_q20 = {})
+{
+    Ciede2000Maps out = Ciede2000Maps::sized(1, width, height, block, want_map, thresholds_q20.size());
+    const size_t len = (size_t)width * height * 6;
+    detail::check(be, ce_eval_pair_ciede2000_map_deep(be.ctx(), reference, len, test, len, ref_depth, test_depth, width, height, what, block,
+                                                      out.map.empty() ? nullptr : out.map.data(), out.map.size(),
+                                                      thresholds_q20.empty() ? nullptr : thresholds_q20.data(),
+                                                      (uint32_t)thresholds_q20.size(), out.over.empty() ? nullptr : out.over.data()),
+                  "ciede2000_map", width, height, len);
+    return out;
+}
+// the four values of n pixels of packed u16 RGB, [n][4] indexed by CE_CIEDE2000_MAP_* (a pure host function; empty when refused)
+inline std::vector<uint32_t> ciede2000_pixel_terms(const uint16_t *reference, uint32_t ref_depth, const uint16_t *test, uint32_t test_depth, size_t n)
+{
+    std::vector<uint32_t> out(n * 4);
+    if (ce_ciede2000_pixel_terms(reference, ref_depth, test, test_depth, n, out.data()) != CE_OK) out.clear();
+    return out;
+}
 // the window's eleven literals, and the (width, height) of every level (pure host functions; empty when refused)
 inline std::array<double, 11> msssim_window()
 {

@@ -1239,6 +1239,69 @@ int ce_eval_pair_ciede2000_deep(ce_ctx *ctx, const uint16_t *reference, size_t r
 int ce_ciede2000_pixels(const uint16_t *ref_rgb, uint32_t ref_depth, const uint16_t *test_rgb, uint32_t test_depth, size_t n,
                         uint32_t *out_q20);
 
+/* ---- CIEDE2000 per pixel, per cell and over thresholds, whole or term by term ---------------------------
+ * Which pixels of a pair drift, and in which direction of colour space: for every pixel of a pair of an RGB8 or deep batch,
+ * steps 1 to 4 above up to tl = dL / S_L, tc = dC / S_C, th = dH / S_H, R_T and dE, exactly as defined there - no operation is
+ * new and none is reordered - and then one of four values, selected by `what`, each a uint32_t in the unit of step 5 (2^-20):
+ *   CE_CIEDE2000_MAP_DE (0):  q = rint(dE * 2^20), step 5 itself: the very integer ce_batch_ciede2000 sums.
+ *   CE_CIEDE2000_MAP_DL (1):  rint(|tl| * 2^20), the lightness term dL' / S_L.
+ *   CE_CIEDE2000_MAP_DC (2):  rint(|tc| * 2^20), the chroma term dC' / S_C.
+ *   CE_CIEDE2000_MAP_DH (3):  rint(|th| * 2^20), the hue term dH' / S_H.
+ *   Magnitudes only: |x| clears the sign bit of the f64, so -0 gives 0; rint rounds ties to even.
+ * Range.  No saturation rule is needed: over 400 000 random pairs of 8-bit colours and all 64 pairs of cube corners
+ *   (tests/test_ciede2000_map_cpu.py) the largest values are dE 115.37 (other samples reach 116.84; step 5's bound of 120
+ *   holds), |tl| 100 (black against white: the largest there is, L spanning 0 .. 100 with S_L >= 1), |tc| 33.36 and |th| 109.56,
+ *   so every value stays under 2^27.
+ * The terms are not bounded by dE.  dE^2 = tl^2 + tc^2 + th^2 + R_T * (tc * th), and the rotation term is negative where
+ *   tc * th > 0 (R_T <= 0): of the 400 064 references above against themselves moved by up to +-3 codes, 3667 have |tc| > dE
+ *   and 15 168 have |th| > dE.  Nothing promises "term <= dE"; a term map is read beside the DE map, not as a share of it.
+ * Equal pixels.  A pixel whose two code triples and depths are equal has all four values 0 exactly: dL = 0, dC = 0, and dH is a
+ *   multiple of sin_deg(0) = 0.  So has any pixel whose two sides hold the same table values.
+ * block.  1: the map itself, [h][w].  A power of two up to 64: the MAXIMUM of the selected value over each block x block cell,
+ *   edge cells clipped to the image, [ceil(h / block)][ceil(w / block)] - ce_batch_delta_e_itp_map's rules.
+ * Exceedance counts.  over[j] = the number of pixels of the pair whose selected value is > thresholds_q20[j] (same unit;
+ *   CE_CIEDE2000_Q20 is 1.0), for up to CE_CIEDE2000_MAX_THRESHOLDS thresholds: exact integers over the pixels, never over
+ *   cells, whatever `block` is.  A threshold of 2^32 - 1 counts nothing.
+ * For what = CE_CIEDE2000_MAP_DE and every pair: map.sum() == sum_q20, map.max() == max_q20 and over == n_above of
+ *   ce_batch_ciede2000 with the same thresholds.
+ * Everything is an integer maximum or an integer sum, so nothing depends on the grid or on the order.
+ * The call works on pairs [first, first + count) on the context's stream, ordered behind the uploads queued so far as a launch
+ * is, with the pair table of the last bind; it blocks until the results are on the host.  ce_scores, stored maps, the CIEDE2000
+ * scores and whatever ce_batch_launch left to collect are untouched.  `map` receives [count][ceil(h / block)][ceil(w / block)]
+ * values and map_len is that number of ELEMENTS; `over` receives [count][n_thresholds].  map may be NULL with map_len 0 (counts
+ * only: no map is stored and no map memory allocated), over may be NULL with n_thresholds 0 and thresholds_q20 NULL, not both.
+ * The device buffer of the maps of one call (map_len * 4 bytes; at block 1, count * w * h * 4) is a grow-only buffer of the
+ * batch, freed with it; it is outside ce_estimate_batch_bytes, and where it cannot be had the call returns CE_ERR_BACKEND with
+ * the batch still usable.
+ * CE_ERR_INVALID_ARG, with the reason in ce_last_error and the batch still usable: a null batch; a linear batch (its map is
+ * ce_batch_delta_e_itp_map's); a `what` above 3; both outputs NULL; count of 0 or a range past the batch's max_pairs; a block
+ * that is not 1, 2, 4, 8, 16, 32 or 64; a map_len other than the above; n_thresholds above 8; over without thresholds;
+ * thresholds without over.
+ * tests/ciede2000_map_restatement.py restates the four values, the cells and the counts in numpy; the device and
+ * ce_ciede2000_pixel_terms equal it on every integer. */
+#define CE_CIEDE2000_MAP_DE 0u
+#define CE_CIEDE2000_MAP_DL 1u
+#define CE_CIEDE2000_MAP_DC 2u
+#define CE_CIEDE2000_MAP_DH 3u
+int ce_batch_ciede2000_map(ce_batch *b, uint32_t first, uint32_t count, uint32_t what, uint32_t block, uint32_t *map, size_t map_len,
+                           const uint32_t *thresholds_q20, uint32_t n_thresholds, uint64_t *over);
+/* One pair of packed RGB8 host images, and one pair of packed u16 RGB at ref_depth / test_depth, through the same kernel and
+ * the context's one-pair batches, as ce_eval_pair_ciede2000{,_deep} take them (lengths in bytes).  CE_ERR_INVALID_ARG as above
+ * and for a null image, an empty one or a depth that is none of 8, 10, 12 and 16; CE_ERR_BAD_LENGTH for a length that is not
+ * the image's. */
+int ce_eval_pair_ciede2000_map(ce_ctx *ctx, const uint8_t *reference, size_t reference_len, const uint8_t *test, size_t test_len,
+                               uint32_t width, uint32_t height, uint32_t what, uint32_t block, uint32_t *map, size_t map_len,
+                               const uint32_t *thresholds_q20, uint32_t n_thresholds, uint64_t *over);
+int ce_eval_pair_ciede2000_map_deep(ce_ctx *ctx, const uint16_t *reference, size_t reference_len, const uint16_t *test, size_t test_len,
+                                    uint32_t ref_depth, uint32_t test_depth, uint32_t width, uint32_t height, uint32_t what,
+                                    uint32_t block, uint32_t *map, size_t map_len, const uint32_t *thresholds_q20,
+                                    uint32_t n_thresholds, uint64_t *over);
+/* A pure host function, no GPU needed, beside ce_ciede2000_pixels: the four values of n pixels, out[i * 4 + what] - the same
+ * pixel text as the kernel's, compiled for the host; out[i * 4] is ce_ciede2000_pixels' q.  CE_ERR_INVALID_ARG for a null
+ * pointer or a depth that is none of 8, 10, 12 and 16. */
+int ce_ciede2000_pixel_terms(const uint16_t *ref_rgb, uint32_t ref_depth, const uint16_t *test_rgb, uint32_t test_depth, size_t n,
+                             uint32_t *out);
+
 /* ---- a decoder's Y'CbCr planes scored as planes: PSNR, SSIM and MS-SSIM per plane -----------------------
  * What codec test conditions (AOM, JVET, JPEG) tabulate: PSNR-Y, PSNR-Cb, PSNR-Cr on the planes the decoder wrote, each at its
  * own resolution - no chroma upsampling, no colour matrix, no RGB clamp - with the 6:1:1 weighted and the overall PSNR, and
