@@ -880,6 +880,25 @@ impl HipMetrics {
         Ok(out)
     }
 
+    /// `ce_yuv_plane_gmsd`: GMSD (gradient magnitude similarity deviation) and its mean of host Y'CbCr images plane by plane, with
+    /// `plane_fidelity`'s images and pair table; every plane of any size runs.  `sum_q2[p]` is [low 64 bits, high 64 bits]:
+    /// `(hi as u128) << 64 | lo as u128` is the sum of squares.  Device surfaces go through `sys::ce_yuv_plane_gmsd` directly.
+    pub fn plane_gmsd(&mut self, refs: &[YuvPlanes<'_>], tests: &[YuvPlanes<'_>], width: u32, height: u32,
+                      pair_ref: Option<&[u32]>) -> Result<Vec<sys::ce_plane_gmsd_scores>, HipError> {
+        if pair_ref.is_some_and(|t| t.len() != tests.len()) {
+            return Err(HipError::MetricCalculation { metric: "hip".into(), reason: "the pair table names another number of pairs than there are tests".into() });
+        }
+        let r = refs.iter().map(|p| p.to_sys(width, height)).collect::<Result<Vec<_>, _>>()?;
+        let t = tests.iter().map(|p| p.to_sys(width, height)).collect::<Result<Vec<_>, _>>()?;
+        let mut out = vec![sys::ce_plane_gmsd_scores::default(); tests.len()];
+        let rc = unsafe {
+            sys::ce_yuv_plane_gmsd(self.ctx, width, height, r.as_ptr(), r.len() as u32, t.as_ptr(), t.len() as u32,
+                                   pair_ref.map_or(ptr::null(), |p| p.as_ptr()), out.as_mut_ptr())
+        };
+        self.check(rc, width, height, 0)?;
+        Ok(out)
+    }
+
     /// `ce_eval_pair_delta_e_itp_map`: where one pair of packed f32 RGB differs - see `HipBatch::delta_e_itp_map`.
     pub fn delta_e_itp_map(&mut self, reference: &[f32], test: &[f32], width: u32, height: u32, depth: u32, white_nits: f32, block: u32,
                            want_map: bool, thresholds_q20: &[u32]) -> Result<DeltaEItpMaps, HipError> {

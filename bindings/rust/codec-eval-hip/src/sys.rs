@@ -285,6 +285,21 @@ pub struct ce_plane_vif_scores {
     pub n_planes: u32,
 }
 
+/// `ce_plane_gmsd_scores` (160 bytes): GMSD of one pair of Y'CbCr images plane by plane: the exact sum of the gradient magnitude
+/// similarities in units of 2^-32, the exact sum of their squares as [low 64 bits, high 64 bits], the positions, the deviation
+/// (dividing by N), the mean and the largest 2^32 - q.  A plane the subsampling lacks has 0 and NaN.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct ce_plane_gmsd_scores {
+    pub sum_q: [u64; 3],
+    pub sum_q2: [[u64; 2]; 3],
+    pub n_pos: [u64; 3],
+    pub gmsd: [c_double; 3],
+    pub gmsm: [c_double; 3],
+    pub max_dis: [u32; 3],
+    pub n_planes: u32,
+}
+
 /// `ce_scores` (40 bytes): a score is meaningful iff its bit is set in `valid`.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -632,6 +647,8 @@ extern "C" {
     pub fn ce_yuv_plane_vif(ctx: *mut ce_ctx, width: u32, height: u32, refs: *const ce_yuv_image, n_refs: u32, tests: *const ce_yuv_image,
                             n_pairs: u32, pair_ref: *const u32, out: *mut ce_plane_vif_scores) -> c_int;
     pub fn ce_vif_window(scale: u32, out: *mut c_double) -> c_int;
+    pub fn ce_yuv_plane_gmsd(ctx: *mut ce_ctx, width: u32, height: u32, refs: *const ce_yuv_image, n_refs: u32, tests: *const ce_yuv_image,
+                             n_pairs: u32, pair_ref: *const u32, out: *mut ce_plane_gmsd_scores) -> c_int;
     pub fn ce_batch_delta_e_itp_map(b: *mut ce_batch, first: u32, count: u32, depth: u32, white_nits: c_float, block: u32, map: *mut u32,
                                     map_len: usize, thresholds_q20: *const u32, n_thresholds: u32, over: *mut u64) -> c_int;
     pub fn ce_eval_pair_delta_e_itp_map(ctx: *mut ce_ctx, reference: *const c_float, reference_len: usize, test: *const c_float,

@@ -216,6 +216,11 @@ class CePlaneVifScores(C.Structure):
                 ("vif_scale", (C.c_double * 4) * 3), ("vifp", C.c_double * 3), ("ran", C.c_uint32 * 3), ("n_planes", C.c_uint32)]
 
 
+class CePlaneGmsdScores(C.Structure):
+    _fields_ = [("sum_q", C.c_uint64 * 3), ("sum_q2", (C.c_uint64 * 2) * 3), ("n_pos", C.c_uint64 * 3), ("gmsd", C.c_double * 3),
+                ("gmsm", C.c_double * 3), ("max_dis", C.c_uint32 * 3), ("n_planes", C.c_uint32)]
+
+
 class CodecEvalError(RuntimeError):
     """Mirrors codec_eval::Error for this path (src/error.rs:31-49)."""
 
@@ -376,6 +381,7 @@ _PROTOTYPES = [
                           C.POINTER(CePlaneHvsScores)]),
     ("ce_yuv_plane_vif", _i, [_vp, _u32, _u32, C.POINTER(CeYuvImage), _u32, C.POINTER(CeYuvImage), _u32, _vp, C.POINTER(CePlaneVifScores)]),
     ("ce_vif_window", _i, [_u32, _vp]),
+    ("ce_yuv_plane_gmsd", _i, [_vp, _u32, _u32, C.POINTER(CeYuvImage), _u32, C.POINTER(CeYuvImage), _u32, _vp, C.POINTER(CePlaneGmsdScores)]),
     ("ce_batch_msssim_map", _i, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
     ("ce_eval_pair_msssim_map", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
     ("ce_eval_pair_msssim_map_deep", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
@@ -1038,6 +1044,31 @@ class PlaneVifScores:
         grid = lambda a, t: tuple(tuple(t(v) for v in a[p]) for p in range(3))  # noqa: E731
         return PlaneVifScores(grid(s.num_q, int), grid(s.den_q, int), grid(s.n_pos, int), grid(s.vif_scale, float), tuple(s.vifp),
                               tuple(int(v) for v in s.ran), int(s.n_planes))
+
+
+@dataclass(frozen=True)
+class PlaneGmsdScores:
+    """GMSD of one pair of Y'CbCr images plane by plane (ce_plane_gmsd_scores): index p = 0, 1, 2 is Y, Cb, Cr.  sum_q[p] is
+    the exact sum of the gradient magnitude similarities in units of 2^-32 over n_pos[p] positions, sum_q2[p] the exact sum of
+    their squares as [low 64 bits, high 64 bits] (sum_q2_int[p] is the same as one integer), max_dis[p] the largest 2^32 - q;
+    gmsd[p] is the deviation (dividing by N) and gmsm[p] the mean.  A plane the subsampling lacks has 0 and NaN."""
+    sum_q: Tuple[int, int, int]
+    sum_q2: Tuple[Tuple[int, int], ...]
+    n_pos: Tuple[int, int, int]
+    gmsd: Tuple[float, float, float]
+    gmsm: Tuple[float, float, float]
+    max_dis: Tuple[int, int, int]
+    n_planes: int
+
+    @property
+    def sum_q2_int(self) -> Tuple[int, ...]:
+        return tuple(q[0] + (q[1] << 64) for q in self.sum_q2)
+
+    @staticmethod
+    def from_c(s: CePlaneGmsdScores) -> "PlaneGmsdScores":
+        ints = lambda a: tuple(int(v) for v in a)  # noqa: E731
+        return PlaneGmsdScores(ints(s.sum_q), tuple((int(s.sum_q2[p][0]), int(s.sum_q2[p][1])) for p in range(3)), ints(s.n_pos),
+                               tuple(s.gmsd), tuple(s.gmsm), ints(s.max_dis), int(s.n_planes))
 
 
 def vif_window(scale: int) -> np.ndarray:
@@ -2031,6 +2062,24 @@ class Context:
         self._check(lib().ce_yuv_plane_vif(self._h, width, height, cr, len(refs), ct, len(tests),
                                            table.ctypes.data if table is not None else None, out))
         return [PlaneVifScores.from_c(out[i]) for i in range(len(tests))]
+
+    def plane_gmsd(self, refs: Sequence["YuvImage"], tests: Sequence["YuvImage"], width: int, height: int,
+                   pair_ref: Optional[Sequence[int]] = None) -> List[PlaneGmsdScores]:
+        """GMSD (gradient magnitude similarity deviation) and its mean of Y'CbCr images plane by plane (ce_yuv_plane_gmsd),
+        with plane_fidelity's images, pair table and semantics.  Every plane of any size runs."""
+        cr, ct = (CeYuvImage * max(len(refs), 1))(), (CeYuvImage * max(len(tests), 1))()
+        keep = []
+        for arr, imgs in ((cr, refs), (ct, tests)):
+            for i, img in enumerate(imgs):
+                arr[i], k = img._c()
+                keep.append(k)
+        table = None if pair_ref is None else np.ascontiguousarray(pair_ref, dtype=np.uint32).reshape(-1)
+        if table is not None and table.size != len(tests):
+            raise CodecEvalError(CE_ERR_INVALID_ARG, f"pair_ref names {table.size} pairs for {len(tests)} tests")
+        out = (CePlaneGmsdScores * max(len(tests), 1))()
+        self._check(lib().ce_yuv_plane_gmsd(self._h, width, height, cr, len(refs), ct, len(tests),
+                                            table.ctypes.data if table is not None else None, out))
+        return [PlaneGmsdScores.from_c(out[i]) for i in range(len(tests))]
 
     def delta_e_itp_map(self, reference, test, width: int, height: int, depth: int = 10, white_nits: float = 203.0, block: int = 1,
                         thresholds_q20=None, maps: bool = True):

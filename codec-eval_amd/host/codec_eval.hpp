@@ -1043,6 +1043,20 @@ inline std::vector<double> vif_window(uint32_t scale)
     g.resize(scale == 1 ? 17 : scale == 2 ? 9 : scale == 3 ? 5 : 3);
     return g;
 }
+// ---- GMSD of the same planes (include/ce_metrics.h: ce_yuv_plane_gmsd) ----
+// per plane the exact sum of the similarities in units of 2^-32, the exact sum of their squares as [low, high] 64 bits, the
+// positions, the deviation (dividing by N), the mean and the largest 2^32 - q
+using PlaneGmsdScores = ce_plane_gmsd_scores;
+inline std::vector<PlaneGmsdScores> plane_gmsd(const HipBackend &be, const std::vector<ce_yuv_image> &refs, const std::vector<ce_yuv_image> &tests,
+                                               uint32_t width, uint32_t height, const std::vector<uint32_t> &pair_ref = {})
+{
+    std::vector<PlaneGmsdScores> out(tests.size());
+    if (!pair_ref.empty() && pair_ref.size() != tests.size()) detail::check(be, CE_ERR_INVALID_ARG, "plane_gmsd", width, height, 0);
+    detail::check(be, ce_yuv_plane_gmsd(be.ctx(), width, height, refs.data(), (uint32_t)refs.size(), tests.data(), (uint32_t)tests.size(),
+                                        pair_ref.empty() ? nullptr : pair_ref.data(), out.data()),
+                  "plane_gmsd", width, height, 0);
+    return out;
+}
 // straight into a slot of a resident batch (RGB8 or deep), host or device planes
 inline void batch_set_reference_yuv(const HipBackend &be, ce_batch *batch, uint32_t ref_index, const YuvImage &image)
 {

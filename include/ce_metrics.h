@@ -1476,6 +1476,53 @@ int ce_yuv_plane_vif(ce_ctx *ctx, uint32_t width, uint32_t height, const ce_yuv_
  * null pointer or another scale. */
 int ce_vif_window(uint32_t scale, double *out);
 
+/* ---- GMSD of a decoder's Y'CbCr planes -----------------------------------------------------------------------
+ * Gradient magnitude similarity deviation (Xue, Zhang, Mou and Bovik 2014), per plane, on the planes as the decoder wrote them,
+ * with its mean (GMSM) beside it.  The paper's MATLAB code is restated here as remembered; nothing available while this was
+ * written could confirm it against that code.  This text and its numpy restatement, tests/plane_gmsd_restatement.py, are the
+ * contract - not the output of any tool: the device equals the restatement on every integer.  Every f64 operation named below is
+ * one separately rounded IEEE operation (no contraction, no libm on the device); sqrt and division are correctly rounded.
+ * Inputs.  The images, planes p = 0, 1, 2, plane sizes pw x ph and samples v = min(raw >> shift, L), L = 2^d - 1, d in {8, 10,
+ *   12}, of ce_yuv_plane_fidelity above, unchanged.  Every plane of the subsampling is scored; a plane of any size >= 1 x 1
+ *   runs.  Planes are not averaged.
+ * Downsample.  W2 = (pw + 1) / 2, H2 = (ph + 1) / 2 in integers.  S[j][i] = v[2j][2i] + v[2j][2i+1] + v[2j+1][2i] + v[2j+1][2i+1],
+ *   a sample outside the plane counting 0: conv2(Y, ones(2) / 4, 'same') taken at 1:2:end, times 4, so an odd last row or column
+ *   gets the half sum the MATLAB code gives it.  S is an exact integer <= 4 L.
+ * Gradients, at each of the n_pos = W2 * H2 positions, S outside the grid counting 0 (conv2(.., 'same')): Gx = (S[j-1][i-1] +
+ *   S[j][i-1] + S[j+1][i-1]) - (S[j-1][i+1] + S[j][i+1] + S[j+1][i+1]); Gy its transpose, row j - 1 less row j + 1.  A = Gx * Gx +
+ *   Gy * Gy, an exact integer <= 2 (12 L)^2 < 2^33: 144 * 4^(d - 8) times the squared Prewitt (/ 3) gradient magnitude of the
+ *   2 x 2 mean of the image scaled to 8 bits.
+ * Similarity.  K = 24480 * 4^(d - 8) = 144 * 170 at the depth's scale: the paper's constant keeps its 8-bit meaning.  Per side m
+ *   = sqrt((double) A).  Per position num = (2.0 * (m_ref * m_test)) + (double) K; den = (double) (A_ref + A_test + K), the sum
+ *   formed in integers and converted once, exactly; g = num / den; q = (uint64) rint(g * 4294967296.0).  1 <= q <= 2^32, q =
+ *   2^32 where both sides are flat; 2^32 - q fits a uint32.
+ * Per pair and plane, exact integers whatever the grid: sum_q = sum q (< 2^64); sum_q2 = sum q * q as a 128-bit integer, [low
+ *   64 bits, high 64 bits]; max_dis = max (2^32 - q); n_pos.
+ * Finishing, on the host.  V = n_pos * sum_q2 - sum_q * sum_q as an exact integer (it fits 128 bits since n_pos < 2^32); gmsd =
+ *   sqrt((double) V) / ((double) n_pos * 4294967296.0) with (double) V the nearest double; gmsm = (double) sum_q / ((double)
+ *   n_pos * 4294967296.0).  The deviation divides by N as the paper's formula does - this library's choice; MATLAB's std2
+ *   divides by N - 1, and the integers let a caller form either.
+ * Not part of this: per-position maps and cell maxima, RGB batches, ce_ref_* handles and ce_eval_batch, keeping a reference's
+ *   A between pairs. */
+typedef struct ce_plane_gmsd_scores {
+    uint64_t sum_q[3];
+    uint64_t sum_q2[3][2];   /* [plane][low 64 bits, high 64 bits] */
+    uint64_t n_pos[3];
+    double gmsd[3];
+    double gmsm[3];
+    uint32_t max_dis[3];
+    uint32_t n_planes;
+} ce_plane_gmsd_scores;      /* 160 bytes */
+/* Scores n_pairs tests, tests[i] against refs[pair_ref[i]] - or against refs[i] with pair_ref NULL, which needs n_refs ==
+ * n_pairs - into out[0 .. n_pairs), with ce_yuv_plane_hvs's semantics: on the context's stream, blocking until the scores are
+ * on the host; no batch is touched and a batch launch that is still to be collected is unaffected; CE_MEM_HOST planes go
+ * through the same page-locked staging and grow-only scratch and are consumed on return; CE_MEM_DEVICE planes are read in
+ * place.  One launch covers every plane of up to 21845 pairs.  Planes beyond n_planes have integers 0 and doubles NaN.
+ * CE_ERR_INVALID_ARG, with a reason that starts "plane gmsd: " in ce_last_error and the context still usable: everything
+ * ce_yuv_plane_fidelity refuses of the pointers, the counts, the pair table and the images; a luma plane with W2 * H2 >= 2^32. */
+int ce_yuv_plane_gmsd(ce_ctx *ctx, uint32_t width, uint32_t height, const ce_yuv_image *refs, uint32_t n_refs,
+                      const ce_yuv_image *tests, uint32_t n_pairs, const uint32_t *pair_ref, ce_plane_gmsd_scores *out);
+
 /* ---- matrix/TRC ICC profiles applied on the device ------------------------------------------------
  * transform_to_srgb (src/metrics/icc.rs:69-103) for the profiles photographs carry - three colorant tags and three tone
  * curves - without a CMS on the host.  ce_lut_* above stays the route for every other profile.
